@@ -13,8 +13,14 @@ form of the same partition is pt_group_* / `pt_render --gpus K`.)
 
 Arithmetic mode (--arith, PT_ARITH_* in include/pt_amd.h): the timed run uses `fast` by default — same
 algorithm, draws and decisions as the reference, f32 throughout, held to the stated tolerance against the
-reference semantics by tests/test_gpu_arith.py; `modes` reports exact (bit-identical to the oracle) and fma
-from the same process.
+reference semantics by tests/test_gpu_arith.py; `modes` (--full) reports exact (bit-identical to the oracle) and
+fma from the same process.
+
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the JSON line with
+the objects computed from that timed run alone (roofline, roofline_valu, pipeline).  `--full` adds the legs that
+need runs of their own: modes, psnr, cpu_baseline (N=1 only).  `--dump-outputs DIR` writes what the timed path
+returned after its last step, the running SUM image of the whole frame, as DIR/image.npy (float32 [H*W, 3],
+~25 MB); the same arguments give the same inputs from run to run.
 
 Extra objects on the JSON line:
   roofline       dominant kernel k_paths (computeIntersections + shadeAndExtendRays + compaction of ALL depths >= 1 in one
@@ -32,9 +38,10 @@ Extra objects on the JSON line:
                  so `frac` is a lower bound.
   pipeline       the whole batch (k_primary + k_paths + k_collect): algorithmic HBM bytes per sample, PMC-measured bytes per
                  sample (profiles/dominant_kernel_traffic.json "pipeline"), and the rate at which this run moved them vs 8 TB/s.
-  cpu_baseline   the oracle (kind "port": oracle/pt_oracle.cpp, reference-literal loop, libm math)
+  modes          (--full, N=1 only) exact / fma / fast measured alike, each on a renderer of its own.
+  cpu_baseline   (--full) the oracle (kind "port": oracle/pt_oracle.cpp, reference-literal loop, libm math)
                  timed on ONE host thread on a bounded sample of the same workload (rank 0, N=1 only).
-  psnr           (N=1 only, outside the timed region) PSNR of 16/64/256/1000-spp prefixes against a 5000-spp
+  psnr           (--full, N=1 only, outside the timed region) PSNR of 16/64/256/1000-spp prefixes against a 5000-spp
                  GPU image; on a row subset the same PSNRs for the reference semantics (oracle, LIBM) against
                  ITS 5000-spp rows, and their difference (north_star: within 0.1 dB).
 """
@@ -118,9 +125,12 @@ def main() -> None:
     ap.add_argument("--unfused-bounces", action="store_true", help="A/B: depths >= 1 as separate intersect + shade launches")
     ap.add_argument("--debug-flags", type=int, default=0, help="A/B switches (16 / 32: result-neutral; 1-8 need a -DPT_ABLATE library)")
     ap.add_argument("--no-kernel-events", action="store_true", help="do not bracket the dominant kernel's launches with HIP events")
-    ap.add_argument("--no-extras", action="store_true", help="skip modes, cpu_baseline and psnr (N=1 extras)")
+    ap.add_argument("--full", action="store_true", help="also measure modes, psnr and cpu_baseline (N=1 extras, runs of their own)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip modes, cpu_baseline and psnr after all")
     ap.add_argument("--stress", action="store_true", help="second JSON line: BASELINE config C5 (10,170 primitives, 1080p)")
     ap.add_argument("--save", type=str, default="", help="write the final image as PREFIX.png/.pfm")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="write the timed path's output after its last step (SUM image, float32 [H*W, 3]) as DIR/image.npy")
     args = ap.parse_args()
 
     import torch
@@ -289,8 +299,18 @@ def main() -> None:
                            "frac": round(alg_ps * samples / dt / 1e9 / HBM_PEAK_GBS, 4),
                            "frac_pmc": round(pmc_ps * samples / dt / 1e9 / HBM_PEAK_GBS, 4) if pmc_ps else None}
 
-    if rank == 0 and world == 1 and not args.no_extras:
-        img = full.cpu().numpy()
+    extras = args.full and not args.no_extras and rank == 0 and world == 1
+    img = None
+    if rank == 0 and (args.dump_outputs or args.save or extras):
+        img = full.cpu().numpy().reshape(-1, 3)  # before any further leg reuses `tile`
+    if rank == 0 and args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "image.npy"), np.ascontiguousarray(img, np.float32))
+    if rank == 0 and world == 1 and args.save:
+        capi.save_png(args.save + ".png", img, W, H, float(args.steps))
+        capi.save_pfm(args.save + ".pfm", img, W, H, float(args.steps))
+
+    if extras:
         r.free()
         # ---- all three arithmetic modes measured ALIKE, same process, same workload: a renderer of its own, 200 untimed
         # steps, accumulation restarted, <= 1000 timed steps (`steady_value`).  The headline `value` stays what the
@@ -371,9 +391,6 @@ def main() -> None:
         out["psnr"] = ps
         assert ps["within_0.1_db"], f"PSNR differs from the reference semantics by {ps['max_delta_db']} dB (> 0.1)"
         out["cpu_baseline"] = cpu_baseline(scene_path)
-        if args.save:
-            capi.save_png(args.save + ".png", img, W, H, float(args.steps))
-            capi.save_pfm(args.save + ".pfm", img, W, H, float(args.steps))
     else:
         r.free()
 

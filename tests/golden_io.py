@@ -3,12 +3,34 @@
 Data only: the fixtures hold inputs and the outputs the reference's own code (compiled in place by `make -C oracle
 goldens`, in the build container) produced for them; nothing here needs /root/reference at test time."""
 import gzip
+import hashlib
+import json
 import os
 import struct
+import sys
 
 import numpy as np
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def scene_tokens(text: str) -> list:
+    """A scene file as the loaders see it: whitespace-split lines, comment and blank lines dropped, numbers as floats."""
+    lines = [l.split() for l in text.splitlines()]
+    lines = [t for t in lines if t and not t[0].startswith("//")]
+    return [[float(x) if x.replace(".", "", 1).replace("-", "", 1).isdigit() else x for x in t] for t in lines]
+
+
+def scene_tokens_digest(text: str) -> str:
+    return hashlib.sha256(json.dumps(scene_tokens(text)).encode()).hexdigest()
+
+
+def write_scene_digests(out_path: str, scene_dir: str, names=("cornell.txt", "sphere.txt")) -> None:
+    """tests/golden/ref_scene_tokens.json: digests of the reference's scenes/*.txt token streams (`make -C oracle goldens`)."""
+    d = {n: scene_tokens_digest(open(os.path.join(scene_dir, n)).read()) for n in names}
+    with open(out_path, "w") as f:
+        json.dump({"sha256_of_scene_tokens": d}, f, indent=1, sort_keys=True)
+        f.write("\n")
 
 
 def load(name: str) -> dict:
@@ -94,3 +116,7 @@ def expected_closest_hits(gold: dict, s: int, bvh):
         best_g = np.where(take, g, best_g)
     rows = hits[np.arange(nr), np.maximum(best_g, 0)]
     return rows, best_g
+
+
+if __name__ == "__main__" and len(sys.argv) == 4 and sys.argv[1] == "scene-digests":
+    write_scene_digests(sys.argv[2], sys.argv[3])

@@ -158,7 +158,7 @@ def test_product_never_touches_oracle():
                 assert "liboracle" not in txt and "oracle.binding" not in txt and "from oracle" not in txt, os.path.join(d, f)
 
 
-REF_SCENES = "/root/reference/scenes"
+REF_TOKENS = os.path.join(HERE, "golden", "ref_scene_tokens.json")  # SHA-256 of the reference's scenes/*.txt token streams
 
 
 def _with_comments(text: str) -> str:
@@ -183,12 +183,15 @@ def test_comment_lines_are_skipped(oracle, name, scene_dir, tmp_path):
     assert all(bytes(x) == bytes(y) for x, y in zip(a.bvh(), oracle.bvh()))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_SCENES), reason="the reference checkout only exists in the build container")
 @pytest.mark.parametrize("name", ["cornell", "sphere"])
-def test_reference_scene_files_parse_like_the_synthesised_ones(oracle, name, scene_dir):
-    """scenes.py must describe exactly the reference's scenes/*.txt (read in place, never copied): same camera,
-    geometry, materials, iteration count, depth and output name through the product loader and the oracle loader."""
-    path = os.path.join(REF_SCENES, name + ".txt")
+def test_reference_scene_files_parse_like_the_synthesised_ones(oracle, name, scene_dir, tmp_path):
+    """scenes.py must describe exactly the reference's scenes/*.txt: the reference's file is the synthesised text token
+    for token (REF_TOKENS) in the reference's layout, `// ...` lines before each block; that layout must give the same
+    camera, geometry, materials, iteration count, depth and output name through the product loader and the oracle loader."""
+    import golden_io as gio
+    text = open(scene_dir[name]).read()
+    assert gio.scene_tokens_digest(text) == json.load(open(REF_TOKENS))["sha256_of_scene_tokens"][name + ".txt"]
+    path = scenes.write_scene(_with_comments(text), str(tmp_path / (name + ".txt")))
     sc, syn = capi.Scene(path), capi.Scene(scene_dir[name])
     oracle.load_scene(path)
     assert bytes(sc.desc.camera) == bytes(syn.desc.camera) == bytes(oracle.camera())

@@ -1,8 +1,8 @@
 """INTEGRATION.md §2 is code that compiles: tests/integration/pathtrace_amd_glue.cpp against the reference's own
 headers (scene.h, pathtrace.h, sceneStructs.h, GLM, the genuine cuda_runtime.h for uchar4) with static_asserts on
 every Material / Camera field offset; linked with the reference's loader into oracle/_ref/ref_glue_demo, which must
-fail LOUDLY without a GPU (no CPU fallback behind the reference's entry points either).  Only where the reference is
-mounted; the GPU-side run is tests/test_gpu_cli.py::test_reference_side_glue_end_to_end."""
+fail LOUDLY without a GPU (no CPU fallback behind the reference's entry points either).  The two builds only where the
+reference is mounted; the GPU-side run is tests/test_gpu_cli.py::test_reference_side_glue_end_to_end."""
 import os
 import shutil
 import subprocess
@@ -14,7 +14,7 @@ from conftest import has_gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference"
 
-pytestmark = pytest.mark.skipif(not (os.path.isdir(REF + "/src") and shutil.which("g++")), reason="reference not mounted")
+needs_reference = pytest.mark.skipif(not (os.path.isdir(REF + "/src") and shutil.which("g++")), reason="reference not mounted")
 
 
 def _cuda_inc():
@@ -24,6 +24,7 @@ def _cuda_inc():
     return d if d and os.path.isfile(os.path.join(d, "cuda_runtime.h")) else None
 
 
+@needs_reference
 def test_glue_compiles_against_reference_headers(tmp_path):
     inc = _cuda_inc()
     if not inc:
@@ -53,6 +54,7 @@ def test_inline_glue_in_integration_md_is_the_compiled_file():
             assert line in src, f"INTEGRATION.md shows a line the compiled glue does not contain: {line}"
 
 
+@needs_reference
 @pytest.mark.skipif(has_gpu(), reason="the GPU run is in tests/test_gpu_cli.py")
 def test_glue_demo_fails_loudly_without_gpu(tmp_path):
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "ref"], stdout=subprocess.DEVNULL,

@@ -209,15 +209,12 @@ def test_isect_golden_geoms_are_the_loaders(isect, tmp_path, oracle):
             assert gio.same_bits_or_both_nan(got, row).all()
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/scenes"), reason="reference not mounted (GPU box)")
 def test_synthesised_scene_text_equals_reference_files():
-    """What scenes.py emits parses like the reference's own files: token streams equal line by line."""
+    """What scenes.py emits parses like the reference's own files: token streams equal line by line (the reference's
+    streams pinned by their SHA-256 in tests/golden/ref_scene_tokens.json, made by `make -C oracle goldens`)."""
+    gold = json.load(open(os.path.join(HERE, "golden", "ref_scene_tokens.json")))["sha256_of_scene_tokens"]
     for name, text in (("cornell.txt", scenes.cornell_scene_text()), ("sphere.txt", scenes.sphere_scene_text())):
-        ref = [l.split() for l in open(f"/root/reference/scenes/{name}").read().splitlines()]
-        ours = [l.split() for l in text.splitlines()]
-        strip = lambda ls: [t for t in ls if t and not t[0].startswith("//")]
-        num = lambda ls: [[float(x) if x.replace(".", "", 1).replace("-", "", 1).isdigit() else x for x in t] for t in ls]
-        assert num(strip(ref)) == num(strip(ours)), name
+        assert gio.scene_tokens_digest(text) == gold[name], name
 
 
 @pytest.mark.skipif(not (os.path.isdir("/root/reference/src") and shutil.which("make")), reason="reference not mounted")

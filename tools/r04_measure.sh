@@ -16,12 +16,12 @@ for M in fast exact fma; do
 done
 cp profiles/dominant_kernel_traffic.json $O/dominant_kernel_traffic.json
 # 2. kernel stats of a bench run (rocprofv3 --kernel-trace --stats) + the bench line of that same run
-(cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/kstats -o t -- python3 $R/bench.py --steps 1200 --warmup 25 > $R/$O/kernel_stats_bench_line.json 2> $R/$O/kstats.err)
+(cd "$TMPDIR" && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/kstats -o t -- python3 $R/bench.py --steps 1200 --warmup 25 --full > $R/$O/kernel_stats_bench_line.json 2> $R/$O/kstats.err)
 rm -f $O/kstats/*.db
-# 3. the driver's command line, and the default run (5000 spp, all legs) with the C5 line
-timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_style_20spp.json 2> $O/bench20.err
+# 3. the driver's command line and the default run (5000 spp) with the C5 line, both with --full (all legs)
+timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver_style_20spp.json 2> $O/bench20.err
 if [ -z "$QUICK" ]; then
-  timeout -k 10 600 python3 bench.py --stress > $O/bench_default_fast_5000spp_stress.json 2> $O/bench_default.err
+  timeout -k 10 600 python3 bench.py --stress --full > $O/bench_default_fast_5000spp_stress.json 2> $O/bench_default.err
 fi
 # 4. the scene-size ladder
 timeout -k 10 400 python3 tools/scene_ladder.py --spp 100 > $O/scene_ladder.log 2>&1
