@@ -26,13 +26,9 @@
 
 namespace {
 
-#ifdef PT_ABLATE
-constexpr bool kAblateBuild = true;   // tools/pmc_ablate.sh A/B library: PtOptions.debug_flags bits 0-3 honoured
-#else
-constexpr bool kAblateBuild = false;  // release library: pt_init rejects them
-#endif
-
 std::string g_err;
+constexpr int kDebugFlags = 16 | 32 | 64 | 256 | 512 | 2048;  // the PtOptions.debug_flags bits pt_init accepts
+static_assert(sizeof(PtOptions) == 80, "capi.PtOptions mirrors this layout");
 constexpr int kGridNodes = 600;        // scenes from this many BVH nodes on are candidates for the uniform grid (build_grid, choose_traversal); the ladder scene of 500 primitives (999 nodes): scan 3.9 k, grid 4.7 k Msamples/s, 156 primitives (311 nodes): 5.5 / 5.3
 constexpr int kTightNodes = 64;        // scenes from this many BVH nodes on test sphere leaves against the ellipsoid's box (sphere_tight_box); the
                                        // reference's own scenes (cornell.txt: 13 nodes) keep the reference's boxes
@@ -98,6 +94,9 @@ struct PtContext {
   float cull_margin = 0.f;
   unsigned long long top_xor = 0;  // SceneTables::top_xor
   int lds_table_bytes = -1;        // SceneTables::lds_table_bytes
+  int lds_table_forced = -1;       // PtOptions.lds_table_kb in bytes; -1: KernelApi::lds_table_limit decides
+  int primary_pieces = 0;          // BatchInfo::primary_pieces forced by PtOptions.primary_pieces; 0: run_batch decides
+  int paths_pieces = 0;            // BatchInfo::paths_pieces (PtOptions.paths_pieces, paths_min_piece)
   // uniform grid over the leaf boxes (build_grid; SceneTables::grid_*), large scenes where it beats the BVH scan (choose_traversal)
   uint32_t* d_grid_start = nullptr;
   size_t grid_guard = 0;  // empty cells in front of (and behind) the cell table proper
@@ -224,10 +223,7 @@ void build_top(const std::vector<PtBVHNode>& ref, const std::vector<ptd::Node>& 
   };
   std::vector<Cut> cut{{0, 0u, 0}};
   auto span = [&](int ref_idx) { return thr[where[ref_idx]].skip - where[ref_idx]; };
-  const char* te = getenv("PT_TOP_ENTRIES");  // experiment knob: a smaller cut (scenes with subtrees only: the LDS-table kernels need every leaf in the list)
-  const int want = te ? std::max(1, std::min(atoi(te), ptk::kMaxTop)) : ptk::kMaxTop;
-  const int max_top = ((int)(ref.size() + 1) / 2 <= ptk::kMaxTop && !getenv("PT_LDS_TABLE_KB")) ? ptk::kMaxTop : want;
-  while ((int)cut.size() < max_top) {
+  while ((int)cut.size() < ptk::kMaxTop) {
     int best = -1;
     for (size_t i = 0; i < cut.size(); ++i)
       if (ref[cut[i].ref_idx].left >= 0 && cut[i].len < 24 && (best < 0 || span(cut[i].ref_idx) > span(cut[best].ref_idx)))
@@ -549,7 +545,7 @@ ptk::SceneTables tables(const Ctx& g) {
   t.nodes_b = g.d_nodes_b ? g.d_nodes_b : g.d_nodes;
   t.top_b = g.d_top_b ? g.d_top_b : g.d_top;
   t.grid_items_b = nullptr;
-  t.num_top = (kAblateBuild && (g.debug_flags & 1)) ? 0 : g.num_top;
+  t.num_top = g.num_top;
   std::memcpy(t.root_min, g.root_min, 12);
   std::memcpy(t.root_max, g.root_max, 12);
   t.cull_margin = (g.debug_flags & 16) ? INFINITY : g.cull_margin;
@@ -558,10 +554,7 @@ ptk::SceneTables tables(const Ctx& g) {
   t.max_batch_iters = g.K;
   t.has_triangles = g.has_triangles ? 1 : 0;
   t.trace_depth = g.depth;
-  {
-    const char* e = getenv("PT_SCAN_NODES_LDS");  // experiment knob: 0 / 1 = never / always; default: when it costs k_paths no resident workgroup
-    t.scan_nodes_lds = e ? (atoi(e) ? 1 : 0) : -1;
-  }
+  t.scan_nodes_lds = -1;  // resolved per kernel (pt_launch.inc resolve_scan_nodes)
   // debug_flags 256 builds and uses the grid for any scene, 512 never (A/B, same results)
   t.use_grid = g.have_grid && g.grid_enabled && !(g.debug_flags & 512) ? 1 : 0;
   if (t.use_grid) {
@@ -606,18 +599,14 @@ int run_batch(Ctx& g, int iter_first, int kb) {
   b.trace_depth = g.depth;
   b.slot_shift = g.slot_shift;
   b.aa_jitter = g.aa_jitter ? 1 : 0;
-  b.debug = kAblateBuild ? g.debug_flags : 0;
   b.flat = g.fuse_bounces ? 0 : 1;
   {
     // k_primary's strands in pieces (BatchInfo::primary_pieces): a piece pays for its own pipeline drain, so it should hold a
     // few dozen 64-sample groups; a wave's strand has K * nq / (waves per queue) of them
-    const char* e = getenv("PT_PRIMARY_PIECES");  // experiment knob
     const int64_t groups = (int64_t)kb * g.qs.nq / std::max(1, g.ret.wq0);
-    b.primary_pieces = e ? atoi(e) : (int)std::min<int64_t>(4, std::max<int64_t>(1, groups / 48));
-    const char* ep = getenv("PT_PATHS_PIECES");  // experiment knob
-    const char* em = getenv("PT_PATHS_MIN_PIECE");  // test knob: pieces of a few paths, so that small images exercise the piece switches
-    b.paths_pieces = (ep ? std::min(std::max(atoi(ep), 1), 0x7fff) : 2) | (em ? std::min(std::max(atoi(em), 1), 0x7fff) : 64) << 16;
+    b.primary_pieces = g.primary_pieces ? g.primary_pieces : (int)std::min<int64_t>(4, std::max<int64_t>(1, groups / 48));
   }
+  b.paths_pieces = g.paths_pieces;
   b.stripe = g.stripe;
   b.gap = g.stripe ? g.stripe_stride - g.stripe : 0;
   b.inv_stripe = g.stripe ? 1.0f / (float)g.stripe : 0.0f;
@@ -665,19 +654,6 @@ int run_batch(Ctx& g, int iter_first, int kb) {
     k.shade(g.stream, g.grid_shade, sc, b, d, queues_for(g, g.grid_shade), cin, cout, g.buf[src], g.hits, g.buf[src ^ 1], g.ret);
     src ^= 1;
   }
-  if (getenv("PT_DUMP_QUEUE_BALANCE")) {  // diagnostics: fill levels of the queues per depth (before k_count_stats zeroes them)
-    HIP_OK(hipStreamSynchronize(g.stream));
-    std::vector<int32_t> h((size_t)(g.depth + 1) * per_depth);
-    HIP_OK(hipMemcpy(h.data(), g.d_cnt, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    for (int d = 0; d <= g.depth; ++d) {
-      double sum = 0, mx = 0, mn = 1e30;
-      for (int q = 0; q < g.qs.Q; ++q) {
-        const double v = h[(size_t)d * per_depth + (size_t)q * g.qs.cnt_stride];
-        sum += v, mx = std::max(mx, v), mn = std::min(mn, v);
-      }
-      std::fprintf(stderr, "queue balance depth %d: mean %.0f min %.0f max %.0f (max/mean %.3f)\n", d, sum / g.qs.Q, mn, mx, sum > 0 ? mx / (sum / g.qs.Q) : 0.0);
-    }
-  }
   k.count_stats(g.stream, g.qs, g.d_cnt, g.depth, g.d_stats);
   k.collect(g.stream, b, g.qs, g.ret, g.d_image);
   HIP_OK(hipGetLastError());
@@ -691,8 +667,7 @@ int run_batch(Ctx& g, int iter_first, int kb) {
 
 // Launch geometry (persistent grids = resident workgroups) for the kernels the current tables select.
 void plan_launch(Ctx& g) {
-  const char* kb = getenv("PT_LDS_TABLE_KB");  // test / experiment knob: force the LDS staging limit of the scene tables
-  g.lds_table_bytes = g.k->lds_table_limit(tables(g), kb ? atoi(kb) * 1024 : -1);
+  g.lds_table_bytes = g.k->lds_table_limit(tables(g), g.lds_table_forced);
   const ptk::SceneTables t = tables(g);
   g.grid_gen = g.num_cus * std::min(g.cap_bpc, g.k->resident_blocks_per_cu(ptk::kGenerate, t));
   g.grid_isect = g.num_cus * std::min(g.cap_bpc, g.k->resident_blocks_per_cu(g.legacy ? ptk::kIntersectLegacy : ptk::kIntersect, t));
@@ -820,8 +795,7 @@ int setup(Ctx& g, const PtSceneDesc* sc, const PtOptions& opt) {
   g.arith = opt.arith;
   g.k = ptk::api_for(opt.arith);
   if (!g.k) return fail("pt_init: arith %d is not one of PT_ARITH_EXACT / PT_ARITH_FMA / PT_ARITH_FAST", opt.arith);
-  if (!kAblateBuild && (opt.debug_flags & 15))
-    return fail("pt_init: debug_flags bits 0-3 (ablations with wrong results) exist only in -DPT_ABLATE builds of the library");
+  if (opt.debug_flags & ~kDebugFlags) return fail("pt_init: debug_flags 0x%x: bits 0x%x are not defined", opt.debug_flags, opt.debug_flags & ~kDebugFlags);
   int ndev = 0;
   HIP_OK(hipGetDeviceCount(&ndev));
   if (ndev <= 0) return fail("pt_init: no HIP device (this library has no CPU fallback)");
@@ -936,6 +910,10 @@ int setup(Ctx& g, const PtSceneDesc* sc, const PtOptions& opt) {
   g.legacy = opt.legacy_traversal != 0;
   g.aa_jitter = opt.aa_jitter != 0;
   g.debug_flags = opt.debug_flags;
+  auto pieces = [](int v, int automatic) { return v ? std::clamp(v, 1, 0x7fff) : automatic; };
+  g.lds_table_forced = opt.lds_table_kb ? std::clamp(opt.lds_table_kb, 0, ptk::kLdsTableBytes / 1024) * 1024 : -1;
+  g.primary_pieces = pieces(opt.primary_pieces, 0);
+  g.paths_pieces = pieces(opt.paths_pieces, 2) | pieces(opt.paths_min_piece, 64) << 16;
   g.fuse_primary = !g.legacy && !opt.unfused_primary;
   g.fuse_bounces = g.fuse_primary && !opt.unfused_bounces;
   std::vector<ptd::Geom> dg(g.geoms.size());
@@ -980,16 +958,15 @@ int setup(Ctx& g, const PtSceneDesc* sc, const PtOptions& opt) {
     HIP_OK(hipMemcpy(g.d_top_b, tb.data(), tb.size() * sizeof(ptd::TopEntry), hipMemcpyHostToDevice));
   }
   if ((g.num_nodes >= kGridNodes || (g.debug_flags & 256)) && !(g.debug_flags & 512)) {
-    const char* dens = getenv("PT_GRID_DENSITY");  // experiment knob: cells per primitive instead of the search
     double cam_mag = 0.0;
     for (int a = 0; a < 3; ++a) cam_mag = std::max(cam_mag, std::fabs((double)g.cam.position[a]));
     // Candidates: the resolution the host's cost model finds (about one cell per primitive; build_grid) and two finer ones.
     // The model prices a uniform spread of primitives and rays; where the primitives cluster, a finer grid pays (clustered 1500
     // objects: 2319 Msamples/s at the model's resolution, 2931 at 8 cells per primitive; a lattice wants exactly its pitch),
-    // so choose_traversal() measures.  A forced grid (debug_flags 256) or a forced density is the only candidate.
+    // so choose_traversal() measures.  A forced grid (debug_flags 256) is the only candidate.
     const bool forced = (g.debug_flags & 256) != 0;
-    std::vector<double> densities{dens ? atof(dens) : 0.0};
-    if (!forced && !dens) densities.insert(densities.end(), {4.0, 8.0});
+    std::vector<double> densities{0.0};
+    if (!forced) densities.insert(densities.end(), {4.0, 8.0});
     for (double density : densities) {
       GridBuild gb;
       if (!build_grid(nodes, g.geoms, g.root_min, g.root_max, cam_mag, density, forced, gb)) continue;
@@ -1038,7 +1015,7 @@ int setup(Ctx& g, const PtSceneDesc* sc, const PtOptions& opt) {
   if (dalloc(g, &g.d_cnt, (size_t)(g.depth + 1) * Q * g.qs.cnt_stride)) return -1;
   HIP_OK(hipMemset(g.d_cnt, 0, (size_t)(g.depth + 1) * Q * g.qs.cnt_stride * sizeof(int32_t)));  // k_count_stats re-zeroes it after every batch
   if (dalloc(g, &g.d_stats, PT_MAX_DEPTH)) return -1;
-  if (!getenv("PT_NO_DEAL")) {  // (A/B knob: W / Q waves per queue in every batch; same image)
+  if (!(g.debug_flags & 64)) {  // (64: W / Q waves per queue in every batch; same image)
     if (dalloc(g, &g.qs.deal, 4 * (size_t)Q + 2)) return -1;
     HIP_OK(hipMemset(g.qs.deal, 0, (4 * (size_t)Q + 2) * sizeof(int32_t)));  // nothing measured yet: W / Q each
   }
@@ -1060,7 +1037,6 @@ int need(const PtContext* c, const char* who) {
 extern "C" {
 
 const char* pt_last_error(void) { return g_err.c_str(); }
-int pt_library_has_ablations(void) { return kAblateBuild ? 1 : 0; }
 
 int pt_selfcheck_ieee(int arith, int kind, uint64_t first, uint64_t count, uint32_t seed, uint64_t* mismatches) {
   const ptk::KernelApi* k = ptk::api_for(arith);
@@ -1147,8 +1123,7 @@ int pt_build_grid(const PtGeom* geoms, int num_geoms, int forced, PtGridInfo* in
   info->num_leaves = num_geoms;
   if (!forced && (int)nodes.size() < kGridNodes) return 0;
   GridBuild gb;
-  const char* dens = getenv("PT_GRID_DENSITY");
-  if (!build_grid(nodes, std::vector<PtGeom>(geoms, geoms + num_geoms), ref_nodes[0].bmin, ref_nodes[0].bmax, 0.0, dens ? atof(dens) : 0.0, forced != 0, gb)) return 0;
+  if (!build_grid(nodes, std::vector<PtGeom>(geoms, geoms + num_geoms), ref_nodes[0].bmin, ref_nodes[0].bmax, 0.0, 0.0, forced != 0, gb)) return 0;
   for (int a = 0; a < 3; ++a) info->res[a] = gb.res[a], info->origin[a] = gb.gmin[a], info->cell_size[a] = gb.cs[a];
   info->pad = gb.pad;
   info->num_cells = (int32_t)(gb.start.size() - 1);

@@ -81,8 +81,6 @@ struct BatchInfo {
                            // itself, the others by whoever is free (an atomic counter behind ptd::Queues::deal); <= 1: one piece
   int32_t paths_pieces;    // k_paths: low 16 bits: a queue's depth-1 rays cut into this many pieces per wave, one its own, the others first
                            // come, first served (counters behind ptd::Queues::deal); <= 1: one piece per wave; high 16 bits: fewest paths in a piece
-  int32_t debug;  // profiling ablations (wrong results; honoured only by -DPT_ABLATE builds): 4 = skip primitive tests,
-                  // 8 = skip shade_bounce
 };
 
 // Resident workgroups per CU for each persistent kernel (hipOccupancyMaxActiveBlocksPerMultiprocessor),
@@ -133,7 +131,7 @@ struct KernelApi {
   void (*shade_stage)(hipStream_t s, const SceneTables& sc, int trace_depth, int depth, int n, const int32_t* iter,
                       const int32_t* pixel, ptd::HitBuf hits, ptd::PathBuf paths, int32_t* alive);
   // Scene tables (nodes + geoms) up to the returned number of bytes are staged in LDS by the traversal kernels:
-  // `forced_bytes` >= 0 is a test / experiment knob (only honoured for scenes whose leaves all fit the top list),
+  // `forced_bytes` >= 0 forces the limit (PtOptions.lds_table_kb; only honoured for scenes whose leaves all fit the top list),
   // otherwise exactly when staging them costs the bounce kernel no resident block per CU.
   int (*lds_table_limit)(const SceneTables& sc, int forced_bytes);
   int (*resident_blocks_per_cu)(KernelId id, const SceneTables& sc);

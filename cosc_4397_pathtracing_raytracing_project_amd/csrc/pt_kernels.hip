@@ -103,12 +103,6 @@ constexpr bool kFastPoint = kFast && PT_FAST_POINT;
 constexpr bool kFloatTrig = PT_ARITH == 1 && PT_FMA_FLOAT_TRIG;
 constexpr bool kFastTrig = kFast && PT_FAST_TRIG, kFastDiv = kFast && PT_FAST_DIV, kFastSqrt = kFast && PT_FAST_SQRT,
                kFastSlab = kFast && PT_FAST_SLAB, kFastMV = kFast && PT_FAST_MV, kFastRenorm = kFast && PT_FAST_RENORM, kFastQO = PT_ARITH == 0 || (kFast && PT_FAST_QO);
-// Ablation switches of tools/pmc_ablate.sh (BatchInfo::debug, wrong results) exist only in -DPT_ABLATE builds.
-#ifdef PT_ABLATE
-constexpr bool kAblate = true;
-#else
-constexpr bool kAblate = false;
-#endif
 
 // Diagnostic builds only (-DPT_WALK_STATS, tools/walk_stats.py): event counts of the large-scene kernels' search loops, added up
 // over a launch in a buffer nothing else reads.  The product build compiles none of it.
@@ -403,9 +397,6 @@ PT_DEV Retire retire_of(const ptd::RetireBuf& rb, int q) {
 PT_DEV int sub_chunks(int quo, int rem, int rho) { return quo + (rho < rem ? 1 : 0); }
 PT_DEV int sub_offset(int quo, int rem, int rho) { return rho * quo + min(rho, rem); }
 PT_DEV void retire_store(const Retire& rt, bool dead, int k, int pos, int pl, f3 c) {
-#ifdef PT_ABL_NO_RETIRE  // timing experiment only (wrong images)
-  return;
-#endif
   if (dead) rt.rec[(int64_t)k * rt.seg_cap + pos] = ptd::Word4{c.x, c.y, c.z, __int_as_float(pl)};
 }
 // The unfused stage kernels: every record appended at the front of its region, one returning atomic per record on the
@@ -940,7 +931,6 @@ struct Carry {
   const float* qo_tab;       // QO chunks (primary rays) only: the camera position in every geom's object space, [geom][3]
   int head, count;           // wave-uniform
   int appended, processed;   // running totals (wave-uniform)
-  int debug;                 // BatchInfo::debug
   const __attribute__((address_space(3))) v4f* lnodes;  // the threaded nodes in LDS (k_paths mode 1 on scenes of a few hundred nodes) when lds_nodes
   bool lds_nodes;
 };
@@ -959,7 +949,6 @@ PT_DEV Carry<SMALL, NPAR> carry_init(char* base) {
   c.slot = reinterpret_cast<int*>(base + NPAR * 64 * 8 + NPAR * 6 * 64 * 4 + ray_bytes + kRing * 4);
   c.cam_o = mk(0.f, 0.f, 0.f);
   c.head = c.count = c.appended = c.processed = 0;
-  c.debug = 0;
   c.gix = nullptr;
   c.qo_tab = nullptr;
   c.lnodes = nullptr;
@@ -992,11 +981,9 @@ PT_DEV void carry_chunk(Carry<SMALL, NPAR>& c, int n, int lane, const ptd::Node*
   f3 pt = mk(0.f, 0.f, 0.f), nrm = mk(0.f, 0.f, 0.f);
   float t = -1.0f;
   // cube / sphere decided per lane; shared pre and post parts
-  if (!(kAblate && (c.debug & 4))) {
-    if (LEAN) t = Ar<EX>::template geom_test<-1, false, true>(G, ro, rd, pt, nrm, mk(0.f, 0.f, 0.f), valid ? (int)(gw >> 30) : 0);
-    else if (QO) t = Ar<EX>::template geom_test<-1, true>(G, ro, rd, pt, nrm, mk(c.qo_tab[3 * gi], c.qo_tab[3 * gi + 1], c.qo_tab[3 * gi + 2]));
-    else t = Ar<EX>::template geom_test<-1, false>(G, ro, rd, pt, nrm, mk(0.f, 0.f, 0.f));
-  }
+  if (LEAN) t = Ar<EX>::template geom_test<-1, false, true>(G, ro, rd, pt, nrm, mk(0.f, 0.f, 0.f), valid ? (int)(gw >> 30) : 0);
+  else if (QO) t = Ar<EX>::template geom_test<-1, true>(G, ro, rd, pt, nrm, mk(c.qo_tab[3 * gi], c.qo_tab[3 * gi + 1], c.qo_tab[3 * gi + 2]));
+  else t = Ar<EX>::template geom_test<-1, false>(G, ro, rd, pt, nrm, mk(0.f, 0.f, 0.f));
   const uint32_t tb = __float_as_uint(t);
   if (valid && t > 0.f && tb < 0x7f7fffffu) {
     const unsigned long long key = ((unsigned long long)tb << 32) | leaf;
@@ -1214,7 +1201,6 @@ __global__ __launch_bounds__(kBlock, kPrimaryWaves) void k_primary(SceneTables s
   WaveLds w;
   Carry<false, 1> cy = carry_init<false, 1>(lds + tbl + wib * kWaveBytes);  // GRID: the bounce kernel's rings
   CellRing cr{reinterpret_cast<uint32_t*>(lds + tbl + wib * kWaveBytes + carry_bytes<false, 1>()), 0, 0, nullptr};
-  cy.debug = b.debug;
   if (GRID) {
     cy.gix = cr.ent + kCellRing;
     cr.rinv = reinterpret_cast<float*>(cr.ent + kCellRing + kRing);
@@ -1316,7 +1302,6 @@ __global__ __launch_bounds__(kBlock, kPrimaryWaves) void k_primary(SceneTables s
     } pp;
     pp.any = false;
     Carry<true, 2> rc = carry_init<true, 2>(lds + tbl + wib * kWaveBytes);  // RING only (the same bytes as `w` otherwise)
-    rc.debug = b.debug;
     rc.qo_tab = cam_qo;
     rc.cam_o = o;
     int it = 0;
@@ -1544,10 +1529,16 @@ PT_DEV void paths_search(Lanes& c, TOP* top, const uint32_t* tword, int ntop, co
 #ifndef PT_SLOTS_MODES
 #define PT_SLOTS_MODES 0  // experiment: 0 = only mode 0 keeps refill slots in LDS
 #endif
+// k_paths' visit ring (fillc): one record counter per sub-list visit of the cursor, kVisitRing per wave, taken modulo the ring.
+// A refill starts only while every path in flight was taken fewer than kVisitLap visits ago; it makes at most kVisitsPerRefill
+// new visits and the seek of a new piece one more, so no counter of a path in flight is handed to another visit.
+constexpr int kVisitRing = 64, kVisitLap = 32, kVisitsPerRefill = 31;
+static_assert(kVisitLap + kVisitsPerRefill + 1 <= kVisitRing, "the visit ring laps a path in flight");
+static_assert((kVisitRing & (kVisitRing - 1)) == 0, "visit numbers wrap with a mask");
 template <int MODE>
 constexpr bool paths_slots_in_lds() { return MODE == 0 || (MODE == 1 && PT_SLOTS_MODES == 1); }
 template <int MODE>
-constexpr int paths_extra_bytes() { return (paths_slots_in_lds<MODE>() ? kSlotBytes : 0) + 512; }  // refill slots + 64 counters: paths retired per depth + 64: record slots per sub-list
+constexpr int paths_extra_bytes() { return (paths_slots_in_lds<MODE>() ? kSlotBytes : 0) + 64 * 4 + kVisitRing * 4; }  // refill slots + 64 counters: paths retired per depth + the visit ring
 template <int MODE>
 constexpr int paths_wave_bytes() {
   return (MODE == 0 ? kLanesBytes : MODE == 1 ? carry_bytes<false, 1>() : grid_wave_bytes<false>()) + paths_extra_bytes<MODE>();
@@ -1602,12 +1593,11 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? PT_PA
   Carry<false, 1> cb = carry_init<false, 1>(wbase);  // MODES 1, 2 (the same bytes)
   CellRing cr{reinterpret_cast<uint32_t*>(wbase + carry_bytes<false, 1>()), 0, 0, nullptr};
   if (MODE == 2) cb.gix = cr.ent + kCellRing, cr.rinv = reinterpret_cast<float*>(cr.ent + kCellRing + kRing);
-  cb.debug = b.debug;
   cb.lnodes = (const __attribute__((address_space(3))) v4f*)(lnodes ? lnodes : lds), cb.lds_nodes = lnodes != nullptr;
   constexpr bool SLOTS = paths_slots_in_lds<MODE>();
   char* slots = wbase + core_bytes;  // SLOTS: [64] x 16 B, [64] x 16 B, [64] x 4 B, [64] x 4 B
   int* died = reinterpret_cast<int*>(slots + (SLOTS ? kSlotBytes : 0));  // [64]: paths of this wave retired AT depth d (statistics; PT_MAX_DEPTH = 64)
-  int* fillc = died + 64;                                                 // [64]: next record slot per sub-list the wave's slice touches
+  int* fillc = died + 64;                                                 // [kVisitRing]: next record slot per sub-list visit
   const int ntop = sc.num_top;
   const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + wib);  // (the compiler cannot see that threadIdx.x >> 6 is wave-uniform)
   const int lane = lane_id();
@@ -1685,15 +1675,15 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? PT_PA
   };
   window_to(0);
   // The records of the paths a wave takes out of ONE visit of a sub-list fill a contiguous range of its sub-region, whatever
-  // order they arrive in, so the wave appends them in order of retirement through a counter per visit in LDS (fillc, a ring of
-  // 64: lanes of one sub-list that die together get consecutive slots, as the per-iteration counters of the earlier layouts
+  // order they arrive in, so the wave appends them in order of retirement through a counter per visit in LDS (fillc, the visit
+  // ring: lanes of one sub-list that die together get consecutive slots, as the per-iteration counters of the earlier layouts
   // gave).  A lane remembers the visit number of its path; the refill below keeps the ring from lapping a path in flight.
   auto cursor_bases = [&](int first_rank) {
     const int ec = min(ce, ne - 1), ck = ec / wq0, crho = ec - ck * wq0;  // (wave-uniform: scalar instructions)
     clist = ck * rt.seg_cap + sub_offset(quo, rem, crho) * 64;
     window_to(ec);
     const int crec = clist + (int)(uint32_t)(sub_word(ec) >> 32);
-    if (lane == 0) fillc[cord & 63] = crec + (first_rank - cstart);  // where this wave's first record of the visit goes
+    if (lane == 0) fillc[cord & (kVisitRing - 1)] = crec + (first_rank - cstart);  // where this wave's first record of the visit goes
   };
   // put the cursor on the sub-list that rank `at_rank` (< total) lies in: a new visit
   auto seek = [&](int at_rank) {
@@ -1724,7 +1714,7 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? PT_PA
   };
   // Path index (inside the queue's region) of the rays of global rank `rank`, for the lanes that `want` one (consecutive ranks in
   // lane order), and the visit their retirement records are counted under.  Ranks only grow inside a piece, so the cursor only
-  // moves forward; it stops after 31 new visits (sub-lists of a path or two: tiles of a few pixels per wave) — the lanes behind
+  // moves forward; it stops after kVisitsPerRefill new visits (sub-lists of a path or two: tiles of a few pixels per wave) — the lanes behind
   // that are served by a later refill.  Returns whether the lane was served.  Wave-uniform control flow.
   auto assign = [&](bool want, int rank, int& at, int& rs) -> bool {
     bool pending = want;
@@ -1733,7 +1723,7 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? PT_PA
       const bool in = pending && rank < cstart + ccnt;
       if (in) at = clist + (rank - cstart), rs = cord;
       pending = pending && !in;
-      if (!ballot(pending) || ce >= ne || cord - cord0 >= 31) break;
+      if (!ballot(pending) || ce >= ne || cord - cord0 >= kVisitsPerRefill) break;
       cstart += ccnt;  // on to the next sub-list that holds anything: the first non-empty one behind ce in the window, else the window moves on
       ccnt = 0;
       int nxt = ce + 1;
@@ -1821,9 +1811,7 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? PT_PA
         w0 = v4f{nx.o.x, nx.o.y, nx.o.z, nx.d.x}, w1 = v4f{nx.d.y, nx.d.z, nx.c.x, nx.c.y}, cz = nx.c.z, nslot = nx.tag.slot, nrs = nx_rs;
       }
       if (owes) {  // the record of the path that died in this lane (its colour and sample id are still here)
-#ifndef PT_ABL_NO_RETIRE
         rt.rec[rslot] = ptd::Word4{c.x, c.y, c.z, __int_as_float(slot & ((1 << b.slot_shift) - 1))};
-#endif
         owes = false;
       }
       if (take) {
@@ -1834,13 +1822,9 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? PT_PA
         valid = fresh = true;
         has_next = false;
       }
-      // every lane without a waiting record gets the next one of the piece — unless a path in flight was taken 32 or more visits
-      // ago: its counter in the ring of 64 must not be handed to another visit (the cursor moves by at most 31 per refill)
-#ifdef PT_EXP_NO_LAP_GUARD  // timing experiment only (records of tiny sub-lists may collide)
-      const bool lapping = false;
-#else
-      const bool lapping = ballot(valid && cord - rslot >= 32) != 0ull;
-#endif
+      // every lane without a waiting record gets the next one of the piece — unless a path in flight was taken kVisitLap or more visits
+      // ago: its counter in the visit ring must not be handed to another visit (the cursor moves by at most kVisitsPerRefill per refill)
+      const bool lapping = ballot(valid && cord - rslot >= kVisitLap) != 0ull;
       const bool empty = !has_next && !lapping;  // takers (just emptied) and lanes that found nothing at an earlier refill
       const unsigned long long em = ballot(empty);
       const int rank = rank_in(em);
@@ -1916,7 +1900,7 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? PT_PA
       }
       const bool alive = ready && s.alive, dead = ready && !s.alive;
       if (dead) atomicAdd(&died[depth & 63], 1);  // statistics: rays traced at depth d = paths retired at depth >= d
-      if (dead) rslot = atomicAdd(&fillc[rslot & 63], 1);  // lanes of one visit get consecutive record slots
+      if (dead) rslot = atomicAdd(&fillc[rslot & (kVisitRing - 1)], 1);  // lanes of one visit get consecutive record slots
       if (alive) shade_bounce(bo, hn, hp, s);
       if (ready) {
         c = s.c;

@@ -18,7 +18,7 @@ SceneTables resolve_scan_nodes(const SceneTables& sc_in) {
   SceneTables sc = sc_in;
   // ... and k_paths' table of the RNG's per-(depth, iteration) hash factors (depth - 1 rows of max_batch_iters words; small tiles
   // run ~100-200 iterations per batch): kept while it costs no resident workgroup per CU, else the factor is hashed per ray
-  // (~18 VALU per shaded ray against a sixth of the waves).  PT_PATHS_ITER_TABLE=0 / 1: never / always (A/B).
+  // (~18 VALU per shaded ray against a sixth of the waves).
   if (iter_hash_entries(sc) > 0) {
     SceneTables without = sc;
     without.max_batch_iters = kIterHashMax + 1;
@@ -27,8 +27,7 @@ SceneTables resolve_scan_nodes(const SceneTables& sc_in) {
     SceneTables a = sc, b = without;
     if (a.scan_nodes_lds < 0) a.scan_nodes_lds = b.scan_nodes_lds = 0;
     const bool costs = min(lds_share_limit(paths_lds_bytes(b, mode)), reg_waves) > min(lds_share_limit(paths_lds_bytes(a, mode)), reg_waves);
-    const char* e = getenv("PT_PATHS_ITER_TABLE");
-    if (e ? atoi(e) == 0 : costs) sc = without;
+    if (costs) sc = without;
   }
   SceneTables t = sc;
   if (t.scan_nodes_lds >= 0) return t;

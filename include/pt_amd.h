@@ -97,15 +97,13 @@ typedef struct PtOptions {
                            /*    HIP events on the render stream (pt_get_stats)  */
   int32_t legacy_traversal; /* 1: per-lane BVH walk kernel instead of the wave-cooperative one (A/B) */
   int32_t debug_flags;      /* A-B switches with UNCHANGED results: 16 no closer-hit cull in the subtree scans, 32 no
-                               near-first subtree order, 256 / 512 force / forbid the uniform-grid walk of the fused kernels
-                               (default: for large scenes, whichever of the BVH scan and up to three grid resolutions renders a
-                               few iterations fastest at pt_init), 2048 keep the reference's leaf boxes for spheres (default for
-                               large scenes: tightened to the ellipsoid's box, PtStats.tight_leaves; pt_stage_intersect on such
-                               a scene then expects ray origins inside the scene bounds or at the camera).  Bits 0-3 are
-                               profiling ablations with WRONG results (1 no top list, 4 skip the primitive tests, 8 skip the
-                               bounce-direction sampling); they exist only in -DPT_ABLATE builds of the library
-                               (tools/pmc_ablate.sh) and pt_init fails on them otherwise (pt_library_has_ablations()).
-                               (Environment, tests only: PT_LDS_TABLE_KB forces the LDS staging limit of the scene tables.) */
+                               near-first subtree order, 64 W / Q waves per queue in every batch of the fused bounce kernel
+                               (default: dealt by the time the queues' waves took, PtStats.paths_waves), 256 / 512 force /
+                               forbid the uniform-grid walk of the fused kernels (default: for large scenes, whichever of the
+                               BVH scan and up to three grid resolutions renders a few iterations fastest at pt_init), 2048
+                               keep the reference's leaf boxes for spheres (default for large scenes: tightened to the
+                               ellipsoid's box, PtStats.tight_leaves; pt_stage_intersect on such a scene then expects ray
+                               origins inside the scene bounds or at the camera).  pt_init fails on any other bit. */
   int32_t unfused_primary;  /* 1: run depth 0 as generate + intersect + shade launches instead of the fused
                                primary kernel (A/B and stage-parity runs) */
   int32_t unfused_bounces;  /* 1: depths >= 1 as separate computeIntersections + shade launches (hit records
@@ -121,6 +119,15 @@ typedef struct PtOptions {
                                u1, u2 come from a hash domain of their own, every other random stream is unchanged.
                                Parity unpinned (nothing in the reference to compare with): tested GPU == oracle. */
   int32_t reserved[1];
+  /* Overrides of automatic choices (tests, A/B): 0 = automatic; no value changes the image. */
+  int32_t lds_table_kb;     /* LDS staging limit of the scene tables: N > 0 forces N KB (at most 64), < 0 keeps the tables
+                               in memory (automatic: staged when every leaf is a top-list entry and staging costs the fused
+                               bounce kernel no resident workgroup) */
+  int32_t primary_pieces;   /* the fused primary kernel's per-wave strands cut into this many pieces (automatic:
+                               min(4, max(1, strand groups / 48))) */
+  int32_t paths_pieces;     /* the fused bounce kernel's depth-1 rays cut into this many pieces per wave (automatic: 2) */
+  int32_t paths_min_piece;  /* fewest paths in one of those pieces (automatic: 64; small values send small images through
+                               the piece switches).  The three piece counts are clamped to 1..0x7fff. */
 } PtOptions;
 
 /* Arithmetic modes (PtOptions.arith).  All modes run the same algorithm with the same random draws and decisions;
@@ -158,7 +165,7 @@ typedef struct PtStats {
                                          transformed unit cube to the box of the ellipsoid (large scenes; same image)     */
   int32_t paths_waves;                /* 0: every queue has the same number of waves in the fused bounce kernel; otherwise
                                          fewest << 16 | most waves a queue gets in the next batch — dealt by the time the
-                                         queues' waves took in the last one (small tiles; same image, PT_NO_DEAL=1 turns it off) */
+                                         queues' waves took in the last one (small tiles; same image, debug_flags 64 turns it off) */
 } PtStats;
 
 /* ---- scene loading (host).  Replaces `new Scene(file)` (src/main.cpp:45,
@@ -247,7 +254,6 @@ int pt_reset_stats(void);
  * (main.cpp:134-135), minus the teardown. */
 int pt_clear(void);
 const char* pt_last_error(void);
-int pt_library_has_ablations(void); /* 1: -DPT_ABLATE build (debug_flags bits 0-3 honoured) */
 /* Device self-check.  The exact and fma kernels (and depth 0 of every mode) take correctly rounded square roots,
  * reciprocals and quotients from instruction sequences shorter than the compiler's general expansions whenever every
  * lane's operands are in a range where the two are the same computation (csrc/pt_kernels.hip, namespace ieee).  This runs

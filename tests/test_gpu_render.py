@@ -86,21 +86,19 @@ def test_image_bit_exact_vs_oracle(scene_dir, oracle, scene, res, spp, depth, kw
 
 
 @pytest.mark.parametrize("kw", [{}, dict(unfused_bounces=True), dict(unfused_primary=True)])
-def test_table_placement_is_result_neutral(oracle, tmp_path, monkeypatch, kw):
+def test_table_placement_is_result_neutral(oracle, tmp_path, kw):
     """Scene tables live in LDS only for scenes whose leaves all fit the top list and only while that keeps every
     resident block (cornell); a 26-leaf scene (8.7 KB of tables) defaults to global memory — force it into LDS
-    (PT_LDS_TABLE_KB=64) and out of it (=0): same pixels."""
+    (lds_table_kb=64) and out of it (lds_table_kb=-1): same pixels."""
     from cosc_4397_pathtracing_raytracing_project_amd import scenes
     res = (96, 64)
     path = scenes.write_scene(scenes.random_scene_text(11, 20, res=res), str(tmp_path / "s26.txt"))
     oracle.set_math_mode(oracle.PORTABLE)
     oracle.load_scene(path, res=res)
     ref = oracle.render(1, 5, depth=8, variant=oracle.RETIRE, nthreads=16)
-    for kb in ("64", "0"):
-        monkeypatch.setenv("PT_LDS_TABLE_KB", kb)
-        img, _ = gpu_render(path, res, 5, 8, **kw)
+    for kb in (64, -1):
+        img, _ = gpu_render(path, res, 5, 8, lds_table_kb=kb, **kw)
         assert np.array_equal(bits(img), bits(ref)), kb
-    monkeypatch.delenv("PT_LDS_TABLE_KB")
 
 
 def test_image_vs_reference_semantics_tolerance(scene_dir, oracle):
@@ -163,11 +161,11 @@ def test_striped_tiles_compose(scene_dir):
         assert np.array_equal(bits(out.reshape(-1, 3)), bits(full))
 
 
-def test_waves_dealt_by_measured_work_change_no_sample(scene_dir, oracle, monkeypatch):
+def test_waves_dealt_by_measured_work_or_evenly_change_no_sample(scene_dir, oracle):
     """k_paths' waves are dealt to the queues by the time the queues' waves took in the previous batch (ptd::Queues::deal): on a
     rank's tile of an eight-way split the queues differ enough for the deal to take effect (PtStats.paths_waves), and the image
     over several batches — the first with W / Q waves each, the rest dealt — is the oracle's bit for bit, and equal to the image
-    with the deal switched off.  A whole small frame with few queues: queues too close together, no deal."""
+    with the deal switched off (debug_flags 64).  A whole small frame with few queues: queues too close together, no deal."""
     from cosc_4397_pathtracing_raytracing_project_amd import capi, parallel
     res, spp = (640, 360), 12
     w, h = res
@@ -175,9 +173,7 @@ def test_waves_dealt_by_measured_work_change_no_sample(scene_dir, oracle, monkey
     sc = capi.Scene(scene_dir["cornell"], res=res)
     imgs = {}
     for deal in (True, False):
-        if not deal:
-            monkeypatch.setenv("PT_NO_DEAL", "1")
-        r = capi.Renderer(sc, iters_per_batch=3, **o)
+        r = capi.Renderer(sc, iters_per_batch=3, debug_flags=0 if deal else 64, **o)
         try:
             r.render(1, spp)
             imgs[deal] = r.readback()
@@ -188,7 +184,6 @@ def test_waves_dealt_by_measured_work_change_no_sample(scene_dir, oracle, monkey
             assert pw != 0 and (pw >> 16) >= 1 and (pw >> 16) < (pw & 0xffff), pw
         else:
             assert pw == 0
-    monkeypatch.delenv("PT_NO_DEAL")
     assert np.array_equal(bits(imgs[True]), bits(imgs[False]))
     oracle.set_math_mode(oracle.PORTABLE)
     oracle.load_scene(scene_dir["cornell"], res=res)
@@ -196,6 +191,30 @@ def test_waves_dealt_by_measured_work_change_no_sample(scene_dir, oracle, monkey
     for row in rows:
         ref = oracle.render(1, spp, depth=8, variant=oracle.RETIRE, nthreads=8, pix_begin=row * w, pix_count=w)
         assert np.array_equal(bits(imgs[True].reshape(-1, w, 3)[row // 8]), bits(ref.reshape(-1, 3))), row
+
+
+@pytest.mark.parametrize("tile", ["frame", "rank 0 of 8"])
+@pytest.mark.parametrize("scene", ["cornell", "random 26 leaves"])
+@pytest.mark.parametrize("pieces", [dict(paths_min_piece=3, primary_pieces=3), dict(paths_pieces=1),
+                                    dict(paths_pieces=4, paths_min_piece=1)])
+def test_forced_pieces_change_no_sample(scene_dir, oracle, tmp_path, tile, scene, pieces):
+    """k_primary's strands and k_paths' depth-1 rays in forced pieces (PtOptions.primary_pieces, paths_pieces,
+    paths_min_piece): pieces of a few paths send a small image through the piece switches, the guarded visit ring and
+    the strand counter.  Bit for bit the oracle's image."""
+    from cosc_4397_pathtracing_raytracing_project_amd import parallel, scenes
+    res, spp = (96, 64), 7
+    w, h = res
+    path = scene_dir["cornell"] if scene == "cornell" else \
+        scenes.write_scene(scenes.random_scene_text(11, 20, res=res), str(tmp_path / "s26.txt"))
+    o = parallel.striped_tile_for_rank(w, h, 0, 8) if tile != "frame" else {}
+    img, st = gpu_render(path, res, spp, 8, **o, **pieces)
+    oracle.set_math_mode(oracle.PORTABLE)
+    oracle.load_scene(path, res=res)
+    ref = oracle.render(1, spp, depth=8, variant=oracle.RETIRE, nthreads=16).reshape(h, w, 3)
+    if o:
+        ref = ref[0::8]
+    assert st.samples == img.shape[0] * spp
+    assert np.array_equal(bits(img), bits(ref.reshape(-1, 3)))
 
 
 @pytest.mark.parametrize("res,kw", [

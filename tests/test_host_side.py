@@ -33,6 +33,12 @@ def test_struct_sizes_match_reference_layouts():
     assert C.sizeof(capi.PtGeom) == 8 + 3 * 64
 
 
+def test_options_struct_size_matches_header():
+    import ctypes as C
+    # include/pt_amd.h PtOptions: 20 int32 fields (pt_api.cpp asserts the same size)
+    assert C.sizeof(capi.PtOptions) == 80
+
+
 @pytest.mark.parametrize("name,res", [("cornell", None), ("cornell", (1920, 1080)), ("sphere", (256, 256)), ("stress", None)])
 def test_scene_tables_match_oracle(scene_dir, oracle, name, res):
     sc = capi.Scene(scene_dir[name], res=res)

@@ -24,13 +24,8 @@ K="/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unu
 $K -ffp-contract=off -DPT_ARITH=0 -c $KSRC/pt_kernels.hip -o $OUT/obj_$NAME/k0.o &
 $K -ffp-contract=fast-honor-pragmas -DPT_ARITH=1 -c $KSRC/pt_kernels.hip -o $OUT/obj_$NAME/k1.o &
 $K -ffp-contract=fast-honor-pragmas -DPT_ARITH=2 -c $KSRC/pt_kernels.hip -o $OUT/obj_$NAME/k2.o &
-API=$SRC/build/pt_api.o
-if echo "$FLAGS" | grep -q PT_ABLATE; then
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -DPT_ABLATE -x hip -c $SRC/pt_api.cpp -o $OUT/obj_$NAME/api.o
-  API=$OUT/obj_$NAME/api.o
-fi
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $OUT/$NAME.so $OUT/obj_$NAME/k0.o $OUT/obj_$NAME/k1.o $OUT/obj_$NAME/k2.o $API \
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $OUT/$NAME.so $OUT/obj_$NAME/k0.o $OUT/obj_$NAME/k1.o $OUT/obj_$NAME/k2.o $SRC/build/pt_api.o \
   $SRC/build/pt_group.o $SRC/build/pt_scene.o $SRC/build/pt_image.o $SRC/build/pathtrace_shim.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 rm -rf $OUT/obj_$NAME
 echo "$OUT/$NAME.so"

@@ -36,11 +36,8 @@ for seed in range(first, first + count):
     kw = dict(kw, debug_flags=flags)
     # every other seed: k_paths' pieces of three paths and k_primary's strands in three pieces, so that small images go through the
     # piece switches, the guarded counter ring and the strand counter (same image)
-    for name in ("PT_PATHS_MIN_PIECE", "PT_PRIMARY_PIECES"):
-        if seed % 2:
-            os.environ[name] = "3"
-        else:
-            os.environ.pop(name, None)
+    if seed % 2:
+        kw = dict(kw, paths_min_piece=3, primary_pieces=3)
     r = capi.Renderer(sc, **kw); r.render(1, spp); img = r.readback(); r_tight = r.stats().tight_leaves; r.free()
     ob.load_scene(path, res=res)
     ref = ob.render(1, spp, depth=depth, variant=ob.RETIRE, nthreads=min(16, os.cpu_count() or 1))

@@ -34,16 +34,13 @@ for seed in range(first, first + count):
     K = int(rs.choice([0, 1, 2, 3, 5, 8, 17, 40, 130]))
     spp = int(min(3 * max(K, 1) + 1, rs.choice([4, 9, 23, 60])))
     kw = dict(iters_per_batch=K, num_queues=int(rs.choice([0, 0, 4, 16, 64, 256, 1024])), blocks_per_cu=int(rs.choice([0, 0, 1, 2, 3])))
-    env = {}
-    if rs.randint(2): env["PT_PATHS_MIN_PIECE"] = str(int(rs.choice([1, 2, 8, 32])))
-    if rs.randint(2): env["PT_PRIMARY_PIECES"] = str(int(rs.choice([2, 3, 5])))
-    if rs.randint(4) == 0: env["PT_PATHS_PIECES"] = str(int(rs.choice([1, 3, 4])))
-    for k in ("PT_PATHS_MIN_PIECE", "PT_PRIMARY_PIECES", "PT_PATHS_PIECES"):
-        os.environ.pop(k, None)
-    os.environ.update(env)
+    pieces = {}
+    if rs.randint(2): pieces["paths_min_piece"] = int(rs.choice([1, 2, 8, 32]))
+    if rs.randint(2): pieces["primary_pieces"] = int(rs.choice([2, 3, 5]))
+    if rs.randint(4) == 0: pieces["paths_pieces"] = int(rs.choice([1, 3, 4]))
     imgs = []
     for unf in (False, True):
-        r = capi.Renderer(sc, unfused_primary=unf, unfused_bounces=unf, **kw, **tile)
+        r = capi.Renderer(sc, unfused_primary=unf, unfused_bounces=unf, **kw, **tile, **pieces)
         r.render(1, spp)
         imgs.append(r.readback())
         pw = r.stats().paths_waves
@@ -51,6 +48,6 @@ for seed in range(first, first + count):
         if not unf: dealt = pw
     ok = np.array_equal(imgs[0].view(np.uint32), imgs[1].view(np.uint32)) and np.isfinite(imgs[0]).all()
     bad += not ok
-    print(f"seed {seed}: kind {kind} {w}x{h} tile {rank}/{world} spp {spp} {kw} {env} dealt {dealt >> 16}-{dealt & 0xffff}: {'ok' if ok else 'MISMATCH'}", flush=True)
+    print(f"seed {seed}: kind {kind} {w}x{h} tile {rank}/{world} spp {spp} {kw} {pieces} dealt {dealt >> 16}-{dealt & 0xffff}: {'ok' if ok else 'MISMATCH'}", flush=True)
 print("mismatches:", bad)
 sys.exit(1 if bad else 0)
