@@ -1,8 +1,9 @@
 // pt_arith.inc — float helpers and the primitive tests, included TWICE by pt_kernels.hip:
-//   namespace ex   under `#pragma clang fp contract(off)` with every fast component off: the reference's arithmetic
+//   namespace ex   under `#pragma clang fp contract(off)`, neither fast nor fused: the reference's arithmetic
 //                  (GLM operation order, IEEE divide / sqrt, no FMA) in EVERY build — used for the primary rays;
-//   namespace md   under the build's own contraction setting with the mode's components (kFast*): exact / fma / fast.
-// The including file defines kFastDiv, kFastSqrt, kFastMV, kFastRenorm, kFastSlab, kFusedRef in the enclosing namespace first.
+//   namespace md   under the build's own contraction setting in the build's mode: exact / fma / fast.
+// The including file defines kFastArith (this namespace has the fast build's arithmetic) and kFusedRef (the fma build's
+// explicit contractions, below) in the enclosing namespace first.
 PT_DEV f3 add(f3 a, f3 b) { return mk(a.x + b.x, a.y + b.y, a.z + b.z); }
 PT_DEV f3 sub(f3 a, f3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
 PT_DEV f3 mul(f3 a, f3 b) { return mk(a.x * b.x, a.y * b.y, a.z * b.z); }
@@ -12,27 +13,27 @@ PT_DEV f3 neg(f3 a) { return mk(-a.x, -a.y, -a.z); }
 // rounded expansions); fast: the hardware approximations v_rcp_f32 / v_rsq_f32 / v_sqrt_f32 (1 ulp).
 PT_DEV float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 // (ieee::*: the same correctly rounded results as `/` and __builtin_sqrtf from a shorter instruction sequence, pt_kernels.hip)
-PT_DEV float rcp_(float x) { return kFastDiv ? __builtin_amdgcn_rcpf(x) : ieee::rcp(x); }
-PT_DEV float div_(float a, float b) { return kFastDiv ? a * __builtin_amdgcn_rcpf(b) : ieee::div(a, b); }
-PT_DEV float sqrt_(float x) { return kFastSqrt ? __builtin_amdgcn_sqrtf(x) : ieee::sqrt(x); }
+PT_DEV float rcp_(float x) { return kFastArith ? __builtin_amdgcn_rcpf(x) : ieee::rcp(x); }
+PT_DEV float div_(float a, float b) { return kFastArith ? a * __builtin_amdgcn_rcpf(b) : ieee::div(a, b); }
+PT_DEV float sqrt_(float x) { return kFastArith ? __builtin_amdgcn_sqrtf(x) : ieee::sqrt(x); }
 // kFusedRef (the fma build): sums of two products are contracted EXPLICITLY, first product fused, in the reference's
 // association.  Left to the compiler, `a * b + c * d` becomes fma(a, b, c * d) or fma(c, d, a * b) depending on how many uses
 // each product has after inlining — the same source then rounds differently in two kernels (seen: 1 ulp in the normalised
 // bounce direction of 1 sample in 20,000 between k_paths and k_bounce, visible through the sky factor), and "one mode, one
 // image" (tests/test_gpu_arith.py) is lost.  The forms below are the ones the compiler picks in the common case.
 PT_DEV float dot(f3 a, f3 b) {
-  if (kFastMV) return fma_(a.x, b.x, fma_(a.y, b.y, a.z * b.z));
+  if (kFastArith) return fma_(a.x, b.x, fma_(a.y, b.y, a.z * b.z));
   if (kFusedRef) return fma_(a.z, b.z, fma_(a.x, b.x, a.y * b.y));
   return (a.x * b.x + a.y * b.y) + a.z * b.z;
 }
 PT_DEV f3 cross(f3 x, f3 y) {
-  if (kFusedRef || kFastMV) return mk(fma_(x.y, y.z, -(y.y * x.z)), fma_(x.z, y.x, -(y.z * x.x)), fma_(x.x, y.y, -(y.x * x.y)));
+  if (kFusedRef || kFastArith) return mk(fma_(x.y, y.z, -(y.y * x.z)), fma_(x.z, y.x, -(y.z * x.x)), fma_(x.x, y.y, -(y.x * x.y)));
   return mk(x.y * y.z - y.y * x.z, x.z * y.x - y.z * x.x, x.x * y.y - y.x * x.y);
 }
-PT_DEV f3 normalize(f3 v) { return scl(v, kFastSqrt ? __builtin_amdgcn_rsqf(dot(v, v)) : ieee::rcp_sqrt(dot(v, v))); }
+PT_DEV f3 normalize(f3 v) { return scl(v, kFastArith ? __builtin_amdgcn_rsqf(dot(v, v)) : ieee::rcp_sqrt(dot(v, v))); }
 PT_DEV float length(f3 v) { return sqrt_(dot(v, v)); }
 PT_DEV f3 madd(f3 a, float s, f3 b) {  // a * s + b
-  if (kFastMV) return mk(fma_(a.x, s, b.x), fma_(a.y, s, b.y), fma_(a.z, s, b.z));
+  if (kFastArith) return mk(fma_(a.x, s, b.x), fma_(a.y, s, b.y), fma_(a.z, s, b.z));
   return add(scl(a, s), b);
 }
 
@@ -41,7 +42,7 @@ PT_DEV f3 madd(f3 a, float s, f3 b) {  // a * s + b
 template <int W>
 PT_DEV f3 mulMV(const float* m, f3 v) {
   f3 r;
-  if (kFastMV) {
+  if (kFastArith) {
     r.x = fma_(m[0], v.x, fma_(m[3], v.y, W ? fma_(m[6], v.z, m[9]) : m[6] * v.z));
     r.y = fma_(m[1], v.x, fma_(m[4], v.y, W ? fma_(m[7], v.z, m[10]) : m[7] * v.z));
     r.z = fma_(m[2], v.x, fma_(m[5], v.y, W ? fma_(m[8], v.z, m[11]) : m[8] * v.z));
@@ -66,9 +67,11 @@ PT_DEV f3 mulMV(const float* m, f3 v) {
 // TYPE: 1 cube (boxIntersectionTest, intersections.h:48-90), 0 sphere (sphereIntersectionTest,
 // intersections.h:102-144), -1 decided per lane from G->type.  Returns t (-1 = no hit).
 // QO: the object-space origin is supplied by the caller (primary rays share the camera position, so it is one
-// value per geom: computed once per block by the primary kernel with this same mulMV).
+// value per geom: computed once per block by the primary kernel, in the same operation order).
 // (m * vec4(v, 1)) in the reference's operation order WITHOUT contraction, whatever the build's setting: the one
-// ill-conditioned product of the primitive test (a thin wall's object-space coordinate is 100 * z + 500), see kFastQO.
+// ill-conditioned product of the primitive test (a thin wall's object-space coordinate is 100 * z + 500).  Rounding it like the
+// reference removes 90 % of the remaining fma / fast sample flips (cornell 256^2 x 16 spp: 25 -> 3 pixels for fma, 46 -> 3 for
+// fast; LABNOTES.md §3).
 PT_DEV f3 mulMV_point_ref(const float* m, f3 v) {
 #pragma clang fp contract(off)
   f3 r;
@@ -97,7 +100,7 @@ PT_DEV float tri_test(const ptd::Geom* __restrict__ G, f3 ro, f3 rd, f3& point, 
   if (by < 0.0f || by + bx > 1.0f) return -1.0f;
   const float t = f * dot(e2, q);
   if (!(t >= 0.0f)) return -1.0f;
-  point = kFastRenorm ? madd(rd, t - .0001f, ro) : add(ro, scl(normalize(rd), t - .0001f));  // getPointOnRay
+  point = kFastArith ? madd(rd, t - .0001f, ro) : add(ro, scl(normalize(rd), t - .0001f));  // getPointOnRay
   normal = normalize(cross(e1, e2));
   return length(sub(ro, point));
 }
@@ -121,16 +124,14 @@ PT_DEV float geom_test(const ptd::Geom* __restrict__ G_in, f3 ro_w, f3 rd_w, f3&
     inv[0] = r0.x, inv[1] = r0.y, inv[2] = r0.z, inv[3] = r0.w, inv[4] = r1.x, inv[5] = r1.y, inv[6] = r1.z, inv[7] = r1.w;
     inv[8] = r2.x, inv[9] = r2.y, inv[10] = r2.z, inv[11] = r2.w;
   }
-  const f3 qo = QO ? qo_pre : (kFastQO ? mulMV<1>(inv, ro_w) : mulMV_point_ref(inv, ro_w));
-  const f3 qv = mulMV<0>(inv, rd_w);
-  const float rl = kFastPoint ? __builtin_amdgcn_rsqf(dot(qv, qv)) : 0.0f;  // world units per object unit along the ray
-  const f3 qd = kFastPoint ? scl(qv, rl) : normalize(qv);
+  const f3 qo = QO ? qo_pre : mulMV_point_ref(inv, ro_w);
+  const f3 qd = normalize(mulMV<0>(inv, rd_w));
   const bool is_box = gtype == 1;
   float t;
   f3 nobj = mk(0.f, 0.f, 0.f);
   bool flip = false;
   int ncode = 0;  // cube: which of the 7 possible object-space normals (0 = zero vector, 1 + 2*axis + (sign > 0))
-  if (is_box && kFastDiv) {
+  if (is_box && kFastArith) {
     // fast mode: the unit cube is symmetric about the object-space origin, so with r = 1 / d, n = o * r and h = |r| / 2 the
     // near and far plane distances of an axis are -n - h and h - n: no min / max per axis, and the object-space normal's sign
     // is the sign of r (t2 < t1 iff r < 0).  The reference's scan over the axes (intersections.h:60-79) keeps the LARGEST
@@ -161,13 +162,7 @@ PT_DEV float geom_test(const ptd::Geom* __restrict__ G_in, f3 ro_w, f3 rd_w, f3&
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       float t1, t2;
-      if (kFastDiv) {  // one reciprocal per axis; the subtract-then-multiply form keeps 0-direction axes at +-inf
-        const float r = __builtin_amdgcn_rcpf(qdv[a]);
-        t1 = (-0.5f - qov[a]) * r;
-        t2 = (+0.5f - qov[a]) * r;
-      } else {
-        ieee::div2(-0.5f - qov[a], +0.5f - qov[a], qdv[a], t1, t2);
-      }
+      ieee::div2(-0.5f - qov[a], +0.5f - qov[a], qdv[a], t1, t2);
       const float ta = t1 < t2 ? t1 : t2;  // glm::min
       const float tb = t1 > t2 ? t1 : t2;  // glm::max
       const int c = 1 + 2 * a + (t2 < t1 ? 1 : 0);  // n[xyz] = t2 < t1 ? +1 : -1
@@ -190,7 +185,7 @@ PT_DEV float geom_test(const ptd::Geom* __restrict__ G_in, f3 ro_w, f3 rd_w, f3&
   } else {
     // radius .5 → powf(.5, 2) = .25
     const float along = dot(qo, qd);
-    const float disc = kFastMV ? fma_(along, along, 0.25f - dot(qo, qo)) : along * along - (dot(qo, qo) - 0.25f);
+    const float disc = kFastArith ? fma_(along, along, 0.25f - dot(qo, qo)) : along * along - (dot(qo, qo) - 0.25f);
     if (disc < 0.f) return -1.0f;
     const float root = sqrt_(disc);
     const float t1 = -along + root;
@@ -205,9 +200,8 @@ PT_DEV float geom_test(const ptd::Geom* __restrict__ G_in, f3 ro_w, f3 rd_w, f3&
   }
   // getPointOnRay (intersections.h:27-29): origin + (t - .0001f) * normalize(direction); qd is already a unit
   // vector, so the fast mode does not normalise it a second time
-  const f3 objp = kFastRenorm ? madd(qd, t - .0001f, qo) : add(qo, scl(normalize(qd), t - .0001f));
+  const f3 objp = kFastArith ? madd(qd, t - .0001f, qo) : add(qo, scl(normalize(qd), t - .0001f));
   if (!is_box) nobj = objp;
-  const float tw = (t - .0001f) * rl;  // kFastPoint: the world distance to the (pulled-back) point
   float xf[12];
   {
     const v4f* gv = reinterpret_cast<const v4f*>(G->xf);
@@ -215,7 +209,9 @@ PT_DEV float geom_test(const ptd::Geom* __restrict__ G_in, f3 ro_w, f3 rd_w, f3&
     xf[0] = r0.x, xf[1] = r0.y, xf[2] = r0.z, xf[3] = r0.w, xf[4] = r1.x, xf[5] = r1.y, xf[6] = r1.z, xf[7] = r1.w;
     xf[8] = r2.x, xf[9] = r2.y, xf[10] = r2.z, xf[11] = r2.w;
   }
-  point = kFastPoint ? madd(rd_w, tw, ro_w) : mulMV<1>(xf, objp);
+  // (the fast build could take the point as ro + rd * world distance and skip the `xf` fetch: C5 bounce kernel -5.3 %, but 0.27 %
+  // of the random-scene pixels then move by > 1e-5, over tests/test_gpu_arith.py's bound of 0.2 %; LABNOTES.md §9.3)
+  point = mulMV<1>(xf, objp);
   if (DEFER) {
     normal = is_box ? mk(__int_as_float(ncode), 0.f, 0.f) : (flip ? neg(nobj) : nobj);
   } else if (is_box) {
@@ -224,7 +220,7 @@ PT_DEV float geom_test(const ptd::Geom* __restrict__ G_in, f3 ro_w, f3 rd_w, f3&
     normal = normalize(mulMV<0>(G->invT, nobj));
     if (flip) normal = neg(normal);
   }
-  return kFastPoint ? tw : length(sub(ro_w, point));
+  return length(sub(ro_w, point));
 }
 // The world-space normal of a hit whose geom_test ran with DEFER.
 PT_DEV f3 finish_normal(const ptd::Geom* __restrict__ G, f3 stored) {
@@ -246,7 +242,7 @@ PT_DEV f3 finish_normal(const ptd::Geom* __restrict__ G, f3 stored) {
 // (an axis-parallel ray would otherwise produce inf - inf in the FMA form of the slab test).
 PT_DEV RayInv ray_inv(f3 d, f3 o) {
   RayInv r;
-  if (kFastSlab) {
+  if (kFastArith) {
     const float dx = __builtin_copysignf(__builtin_fmaxf(__builtin_fabsf(d.x), 1e-20f), d.x);
     const float dy = __builtin_copysignf(__builtin_fmaxf(__builtin_fabsf(d.y), 1e-20f), d.y);
     const float dz = __builtin_copysignf(__builtin_fmaxf(__builtin_fabsf(d.z), 1e-20f), d.z);
@@ -267,7 +263,7 @@ PT_DEV bool slab_planes(float ax, float bx, float ay, float by, float az, float 
 }
 // slab() that also returns the entry distance (for the closer-hit cull of the subtree scans).
 PT_DEV bool slab_t(f3 o, const RayInv& ri, float lox, float loy, float loz, float hix, float hiy, float hiz, float& tn) {
-  if (kFastSlab) {
+  if (kFastArith) {
     // The fast build's bounce kernels get their boxes as CENTRE (lo*) and HALF EXTENT (hi*) (SceneTables::*_b, converted by the
     // host): the plane distances of an axis are tc -+ h * |i| with tc = c * i - o * i — three FMAs per axis and no min / max
     // (min / max / compare / select issue at half the rate of an FMA on gfx950, profiles/r03_ubench_valu.txt: 41 instead
@@ -296,7 +292,7 @@ PT_DEV bool slab(f3 o, const RayInv& ri, float lox, float loy, float loz, float 
 }
 // slab() on a box given relative to the ray origin (lo - o, hi - o precomputed with the same subtraction).
 PT_DEV bool slab_rel(const RayInv& ri, float lox, float loy, float loz, float hix, float hiy, float hiz) {
-  if (kFastSlab) {
+  if (kFastArith) {
     float tn;
     return slab_planes(lox * ri.ix, hix * ri.ix, loy * ri.iy, hiy * ri.iy, loz * ri.iz, hiz * ri.iz, tn);
   }

@@ -16,7 +16,7 @@ struct CellRing {
 // values and computes no reciprocal.  (Round 2 measured the stored reciprocals 34 % slower for the fast build of the kernel
 // as it was then; round 3, with the retirement and filing changes in: 3.4 % faster, `n` included 6 %.)
 template <bool EX>
-constexpr int rinv_planes() { return (EX || !kFastSlab) ? 3 : 6; }
+constexpr int rinv_planes() { return (EX || !kFast) ? 3 : 6; }
 template <bool EX>
 constexpr int grid_wave_bytes() { return carry_bytes<false, 1>() + kCellRing * 4 + kRing * 4 + rinv_planes<EX>() * 64 * 4; }  // Carry + cell ring + Carry::gix + CellRing::rinv
 // Exclusive prefix sum over the wave of a small count per lane, and the total: a Hillis-Steele scan on the DPP network —
@@ -142,10 +142,7 @@ PT_DEV void walk_start(const SceneTables& sc, f3 o, f3 d, float t_from, float t_
 // longest of 64 walks takes 26, so once few lanes are still walking their remaining spans are cut into equal parts and
 // dealt to all 64 lanes (candidates are filed under the lane that owns the ray, as with the work stealing of the
 // subtree scans; the parts overlap by a cell, which costs a repeated test and changes nothing).
-#ifndef PT_GRID_SPLIT
-#define PT_GRID_SPLIT 16
-#endif
-constexpr int kGridSplit = PT_GRID_SPLIT;  // lanes still walking when the remaining spans are dealt out (0: never)
+constexpr int kGridSplit = 16;  // lanes still walking when the remaining spans are dealt out
 template <int NPAR, bool EX = false>
 PT_DEV void grid_search(Carry<false, NPAR>& c, CellRing& cr, const SceneTables& sc, const ptd::Node* __restrict__ nodes,
                         const ptd::Geom* __restrict__ geoms, f3 o, f3 d, bool valid, int lane, int par) {
@@ -169,7 +166,7 @@ PT_DEV void grid_search(Carry<false, NPAR>& c, CellRing& cr, const SceneTables& 
     if (!M) break;
     PT_STAT(1, 1);
     PT_STAT(2, __popcll(M));
-    if (kGridSplit > 0 && splits < 2 && __popcll(M) <= kGridSplit) {
+    if (splits < 2 && __popcll(M) <= kGridSplit) {
       ++splits;
       const int n_on = __popcll(M);
       const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(M >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)M, 0));

@@ -12,12 +12,8 @@
 //          plain FMA where v_div_fmas (which is an FMA unless v_div_scale set VCC) stood
 // otherwise the wave runs the compiler's expansion.  Identity by construction inside the range (it is the same instruction
 // sequence); pt_selfcheck_ieee verifies it on the device against `__builtin_sqrtf`, `1.0f / x` and `a / b` for all 2^32 bit
-// patterns of x and for 2^33 operand pairs (tests/test_gpu_ieee_ops.py).  -DPT_IEEE_FAST=0 builds the plain expansions.
-#ifndef PT_IEEE_FAST
-#define PT_IEEE_FAST 1
-#endif
+// patterns of x and for 2^33 operand pairs (tests/test_gpu_ieee_ops.py).
 namespace ieee {
-constexpr bool kGuarded = PT_IEEE_FAST != 0;
 PT_DEV bool every_lane(bool ok) { return ballot(!ok) == 0ull; }
 // |v| in [2^-47, 2^47): the exponents of numerator and denominator differ by less than 96, so v_div_scale leaves both as they
 // are (VCC = 0, v_div_fmas is a plain FMA) and the quotient is a normal number — by construction, not only by test (round 3's
@@ -49,20 +45,20 @@ PT_DEV float quot_core(float a, float b, float r) {
   return __builtin_fmaf(e3, r, q);
 }
 PT_DEV float sqrt(float x) {
-  if (kGuarded && every_lane(sqrt_range(x))) return sqrt_core(x);
+  if (every_lane(sqrt_range(x))) return sqrt_core(x);
   return __builtin_sqrtf(x);
 }
 PT_DEV float div(float a, float b) {
-  if (kGuarded && every_lane(div_range(a) && div_range(b))) return quot_core(a, b, rcp_core(b));
+  if (every_lane(div_range(a) && div_range(b))) return quot_core(a, b, rcp_core(b));
   return a / b;
 }
 PT_DEV float rcp(float b) {
-  if (kGuarded && every_lane(div_range(b))) return quot_core(1.0f, b, rcp_core(b));
+  if (every_lane(div_range(b))) return quot_core(1.0f, b, rcp_core(b));
   return 1.0f / b;
 }
 // 1 / sqrt(x) as the reference forms it: two correctly rounded operations.  One range test covers both.
 PT_DEV float rcp_sqrt(float x) {
-  if (kGuarded && every_lane(sqrt_range(x))) {
+  if (every_lane(sqrt_range(x))) {
     const float s = sqrt_core(x);
     return quot_core(1.0f, s, rcp_core(s));
   }
@@ -70,7 +66,7 @@ PT_DEV float rcp_sqrt(float x) {
 }
 // (a1 / b, a2 / b) and (1/x, 1/y, 1/z): one range test, and the two quotients of one denominator share its reciprocal
 PT_DEV void div2(float a1, float a2, float b, float& q1, float& q2) {
-  if (kGuarded && every_lane(div_range(a1) && div_range(a2) && div_range(b))) {
+  if (every_lane(div_range(a1) && div_range(a2) && div_range(b))) {
     const float r = rcp_core(b);
     q1 = quot_core(a1, b, r), q2 = quot_core(a2, b, r);
     return;
@@ -80,7 +76,7 @@ PT_DEV void div2(float a1, float a2, float b, float& q1, float& q2) {
 // (a.x, a.y, a.z) / b.  (Zero numerators stay outside the guarded range: the correction chain turns -0 / b into +0 — found by the
 // self-check.)
 PT_DEV void div3(float& x, float& y, float& z, float b) {
-  if (kGuarded && every_lane(div_range(x) && div_range(y) && div_range(z) && div_range(b))) {
+  if (every_lane(div_range(x) && div_range(y) && div_range(z) && div_range(b))) {
     const float r = rcp_core(b);
     x = quot_core(x, b, r), y = quot_core(y, b, r), z = quot_core(z, b, r);
     return;
@@ -88,7 +84,7 @@ PT_DEV void div3(float& x, float& y, float& z, float b) {
   x = x / b, y = y / b, z = z / b;
 }
 PT_DEV void rcp3(float x, float y, float z, float& rx, float& ry, float& rz) {
-  if (kGuarded && every_lane(div_range(x) && div_range(y) && div_range(z))) {
+  if (every_lane(div_range(x) && div_range(y) && div_range(z))) {
     rx = quot_core(1.0f, x, rcp_core(x)), ry = quot_core(1.0f, y, rcp_core(y)), rz = quot_core(1.0f, z, rcp_core(z));
     return;
   }

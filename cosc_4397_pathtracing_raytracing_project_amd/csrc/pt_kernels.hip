@@ -27,7 +27,7 @@
 //            -fhip-fp32-correctly-rounded-divide-sqrt), and sin/cos/acos come from pt_portable_math.h, so
 //            results are bit-identical to oracle/pt_oracle.cpp in PORTABLE mode;
 //   1 fma:   the same source with contraction allowed; direction sampling in float only (shade_bounce_float<false>);
-//   2 fast:  the `kFast` branches below — hardware rcp / rsq / sqrt / sin / cos, nested-FMA matrix products,
+//   2 fast:  the `kFast` branches below — hardware rcp / rsq / sqrt / sin / cos, nested-FMA matrix products, FMA slab tests,
 //            float-only direction sampling.  Same algorithm, same RNG draws, same decisions; only rounding differs.
 // No MFMA: there is no dense contraction here.
 #include "pt_kernels.h"
@@ -61,48 +61,8 @@ namespace {
 #define PT_DEV __device__ __forceinline__
 
 constexpr bool kFast = PT_ARITH == 2;
-// Components of the fast mode, individually switchable (-DPT_FAST_x=0) for the flip-rate bisection of
-// tools/arith_bisect.sh; the product builds leave all of them on.
-#ifndef PT_FAST_TRIG
-#define PT_FAST_TRIG 1  // direction sampling: v_sin / v_cos in revolutions, sqrt form of the diffuse lobe, no doubles
-#endif
-#ifndef PT_FAST_DIV
-#define PT_FAST_DIV 1   // v_rcp_f32 instead of IEEE divides
-#endif
-#ifndef PT_FAST_SQRT
-#define PT_FAST_SQRT 1  // v_rsq_f32 / v_sqrt_f32 instead of IEEE sqrt (+ divide) in normalize / length
-#endif
-#ifndef PT_FAST_SLAB
-#define PT_FAST_SLAB 1  // AABB test as (b * inv - o * inv) FMAs with min/max per axis
-#endif
-#ifndef PT_FAST_MV
-#define PT_FAST_MV 1    // nested-FMA matrix-vector products and dot products
-#endif
-#ifndef PT_FAST_QO
-#define PT_FAST_QO 0    // 1: ray origin -> object space as a nested-FMA product too.  Off in the product: this is the one
-                        // ill-conditioned product of the primitive test (thin wall: 100 * z + 500), and rounding it like the
-                        // reference does (unfused, GLM order) removes 90 % of the remaining fma / fast sample flips
-                        // (cornell 256^2 x 16 spp: 25 -> 3 pixels for fma, 46 -> 3 for fast; tools/arith_flips.py)
-#endif
-#ifndef PT_FAST_RENORM
-#define PT_FAST_RENORM 1  // getPointOnRay does not normalise the already normalised object-space direction again
-#endif
-#ifndef PT_FAST_POINT
-#define PT_FAST_POINT 0   // 1: hit point as ray origin + direction * world distance instead of transform * object-space point (the
-                          // object-space direction is normalize(inverse * d), so transform * it = d / |inverse * d|, and the world
-                          // distance is the object-space one times the rsq the normalisation already took): spares the 48-byte
-                          // `transform` fetch of every hit candidate — a dependent second fetch per chunk — and 9 FMAs.  Measured
-                          // (round 3): C5 bounce kernel -5.3 %, cornell -1 %; OFF because it is one more place where the fast
-                          // mode rounds differently from the reference, and the random-scene tolerance test then sees 0.27 % of
-                          // the pixels off by > 1e-5 against its bound of 0.2 % (tests/test_gpu_arith.py).  The tolerance wins.
-#endif
-constexpr bool kFastPoint = kFast && PT_FAST_POINT;
-#ifndef PT_FMA_FLOAT_TRIG
-#define PT_FMA_FLOAT_TRIG 1  // fma mode: float-only direction sampling (shade_bounce_float<false>) instead of the exact mode's
-#endif
-constexpr bool kFloatTrig = PT_ARITH == 1 && PT_FMA_FLOAT_TRIG;
-constexpr bool kFastTrig = kFast && PT_FAST_TRIG, kFastDiv = kFast && PT_FAST_DIV, kFastSqrt = kFast && PT_FAST_SQRT,
-               kFastSlab = kFast && PT_FAST_SLAB, kFastMV = kFast && PT_FAST_MV, kFastRenorm = kFast && PT_FAST_RENORM, kFastQO = PT_ARITH == 0 || (kFast && PT_FAST_QO);
+// The fma build samples directions in float only (shade_bounce_float<false>) instead of the exact build's double-reduced form.
+constexpr bool kFloatTrig = PT_ARITH == 1;
 
 // Diagnostic builds only (-DPT_WALK_STATS, tools/walk_stats.py): event counts of the large-scene kernels' search loops, added up
 // over a launch in a buffer nothing else reads.  The product build compiles none of it.
@@ -121,18 +81,11 @@ PT_DEV int wave_max_stat(int v) {
 #define PT_STAT(i, v)
 #endif
 
-// Tuning switch of the large-scene (global-table) path, overridable with -D for A/B builds.
-#ifndef PT_STEAL_MIN
-#define PT_STEAL_MIN 16
-#endif
-constexpr int kStealMin = PT_STEAL_MIN;  // idle lanes needed before a work-stealing step is run (65: never)
+constexpr int kStealMin = 16;  // large-scene (global-table) path: idle lanes needed before a work-stealing step is run (65: never)
 // Waves per SIMD the depth-0 kernel is compiled for (__launch_bounds__ second argument).  5: the camera ring's 5.9 KB per wave
 // fit five workgroups per CU; in-box, Msamples/s at 4 | 5 | 6: fast 22.5 k | 22.5 k (95 VGPRs either way) | 21.0 k (88 B / lane of
 // scratch), fma 17.27 k | 17.45 k, exact 15.29 k | 15.63 k (97 VGPRs at 4; 95 + 20 B / lane of scratch at 5).
-#ifndef PT_PRIMARY_WAVES
-#define PT_PRIMARY_WAVES 5
-#endif
-constexpr int kPrimaryWaves = PT_PRIMARY_WAVES;
+constexpr int kPrimaryWaves = 5;
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 struct f3 {
@@ -189,7 +142,7 @@ struct RayInv {
 #pragma clang fp contract(off)
 namespace ex {
 namespace {
-constexpr bool kFastDiv = false, kFastSqrt = false, kFastMV = false, kFastRenorm = false, kFastSlab = false, kFastQO = true, kFastPoint = false, kFusedRef = false;
+constexpr bool kFastArith = false, kFusedRef = false;
 #include "pt_arith.inc"
 }  // namespace
 }  // namespace ex
@@ -198,8 +151,7 @@ constexpr bool kFastDiv = false, kFastSqrt = false, kFastMV = false, kFastRenorm
 #endif
 namespace md {
 namespace {
-constexpr bool kFastDiv = PT_NS::kFastDiv, kFastSqrt = PT_NS::kFastSqrt, kFastMV = PT_NS::kFastMV, kFastRenorm = PT_NS::kFastRenorm,
-               kFastSlab = PT_NS::kFastSlab, kFastQO = PT_NS::kFastQO, kFastPoint = PT_NS::kFastPoint, kFusedRef = PT_ARITH == 1;
+constexpr bool kFastArith = kFast, kFusedRef = PT_ARITH == 1;
 #include "pt_arith.inc"
 }  // namespace
 }  // namespace md
@@ -639,11 +591,10 @@ constexpr unsigned long long kNoHit = ((unsigned long long)0x7f7fffffu << 32) | 
 // list[sfirst].  TYPE 1 / 0: the chunk holds only cubes / only spheres (specialised code); TYPE -1: both —
 // the object-space transform of the ray and the world-space reconstruction are executed once for all
 // lanes and only the slab / quadratic middle parts diverge (geom_test<-1>).
-// CAM (primary kernel): every ray starts at the camera, so the origin needs no fetch; QO (tables in LDS): its
-// object-space image comes from the per-geom table qo_tab.
-template <int TYPE, bool CAM, bool QO, bool EX>
+// CAM (primary kernel): every ray starts at the camera, so the origin needs no fetch.
+template <int TYPE, bool CAM, bool EX>
 PT_DEV void run_chunk(const WaveLds& w, int cfirst, int nc, int sfirst, int nsph, int lane, f3 o, f3 d,
-                      const ptd::Node* __restrict__ nodes, const ptd::Geom* __restrict__ geoms, const float* qo_tab) {
+                      const ptd::Node* __restrict__ nodes, const ptd::Geom* __restrict__ geoms) {
   const bool valid = lane < nc + nsph;
   const uint32_t entry = valid ? w.list[lane < nc ? cfirst + lane : sfirst + (lane - nc)] : (uint32_t)lane;
   const int src = (int)(entry & 63u);
@@ -653,9 +604,7 @@ PT_DEV void run_chunk(const WaveLds& w, int cfirst, int nc, int sfirst, int nsph
   const int gi = valid ? nodes[leaf].geom : 0;
   const ptd::Geom* G = geoms + gi;
   f3 pt, nrm;
-  float t;
-  if (QO) t = Ar<EX>::template geom_test<TYPE, true>(G, ro, rd, pt, nrm, mk(qo_tab[3 * gi], qo_tab[3 * gi + 1], qo_tab[3 * gi + 2]));
-  else t = Ar<EX>::template geom_test<TYPE, false>(G, ro, rd, pt, nrm, mk(0.f, 0.f, 0.f));
+  const float t = Ar<EX>::template geom_test<TYPE, false>(G, ro, rd, pt, nrm, mk(0.f, 0.f, 0.f));
   const uint32_t tb = __float_as_uint(t);
   if (valid && t > 0.f && tb < 0x7f7fffffu) {
     const unsigned long long key = ((unsigned long long)tb << 32) | leaf;
@@ -670,33 +619,31 @@ PT_DEV void run_chunk(const WaveLds& w, int cfirst, int nc, int sfirst, int nsph
 // Chunk plan (a typical group at depth >= 1 holds ~55 cubes and ~12 spheres): full chunks of cubes,
 // then the remaining cubes together with the spheres in ONE mixed chunk if they fit in 64 lanes
 // (costs ~1.3x a pure chunk instead of two pure chunks), otherwise separately.
-template <bool CAM, bool QO, bool EX>
+template <bool CAM, bool EX>
 PT_DEV void flush_candidates(const WaveLds& w, int nb, int ns, int lane, f3 o, f3 d,
-                             const ptd::Node* __restrict__ nodes, const ptd::Geom* __restrict__ geoms, const float* qo_tab,
+                             const ptd::Node* __restrict__ nodes, const ptd::Geom* __restrict__ geoms,
                              bool tri) {  // tri (wave-uniform): the back list may hold triangles (mesh extension)
   const int sbase = kCandCap - ns;
   int c0 = 0;
-  for (; c0 + 64 <= nb; c0 += 64) run_chunk<1, CAM, QO, EX>(w, c0, 64, 0, 0, lane, o, d, nodes, geoms, qo_tab);
+  for (; c0 + 64 <= nb; c0 += 64) run_chunk<1, CAM, EX>(w, c0, 64, 0, 0, lane, o, d, nodes, geoms);
   const int rem = nb - c0;
   if (rem > 0 && ns > 0 && rem + ns <= 64) {
-    run_chunk<-1, CAM, QO, EX>(w, c0, rem, sbase, ns, lane, o, d, nodes, geoms, qo_tab);
+    run_chunk<-1, CAM, EX>(w, c0, rem, sbase, ns, lane, o, d, nodes, geoms);
     return;
   }
-  if (rem > 0) run_chunk<1, CAM, QO, EX>(w, c0, rem, 0, 0, lane, o, d, nodes, geoms, qo_tab);
+  if (rem > 0) run_chunk<1, CAM, EX>(w, c0, rem, 0, 0, lane, o, d, nodes, geoms);
   for (int s0 = 0; s0 < ns; s0 += 64) {
-    if (tri) run_chunk<-1, CAM, QO, EX>(w, 0, 0, sbase + s0, min(64, ns - s0), lane, o, d, nodes, geoms, qo_tab);
-    else run_chunk<0, CAM, QO, EX>(w, 0, 0, sbase + s0, min(64, ns - s0), lane, o, d, nodes, geoms, qo_tab);
+    if (tri) run_chunk<-1, CAM, EX>(w, 0, 0, sbase + s0, min(64, ns - s0), lane, o, d, nodes, geoms);
+    else run_chunk<0, CAM, EX>(w, 0, 0, sbase + s0, min(64, ns - s0), lane, o, d, nodes, geoms);
   }
 }
 
 // Phase 1 + phase 2 for one group of 64 rays (one per lane; `valid` masks tail lanes).  On return
 // w.best[lane] holds the lane's (t bits << 32 | leaf) key (kNoHit if none) and w.rec its normal/point.
-// CAM: primary rays — `top` holds the entries' boxes relative to the camera position (slab_rel) and qo_tab the
-// camera position in every geom's object space (run_chunk<.., true>).
-template <bool CAM, bool QO, bool EX>
+template <bool EX>
 PT_DEV void trace_group(const WaveLds& w, const float4* top, int ntop, const ptd::Node* __restrict__ nodes,
                         const ptd::Geom* __restrict__ geoms, f3 o, f3 d, bool valid, int lane, float cull,
-                        unsigned long long top_xor, const float* qo_tab = nullptr, bool tri = false) {
+                        unsigned long long top_xor, bool tri) {
   const RayInv ri = Ar<EX>::ray_inv(d, o);
   w.best[lane] = kNoHit;
   int nb = 0, ns = 0;  // pending cubes (front of the list) / spheres (back)
@@ -709,12 +656,12 @@ PT_DEV void trace_group(const WaveLds& w, const float4* top, int ntop, const ptd
     if (e + 1 < ntop) A = top[2 * e + 2], B = top[2 * e + 3];
     const int t_idx = __builtin_amdgcn_readfirstlane(__float_as_int(TB.z));
     const int t_link = __builtin_amdgcn_readfirstlane(__float_as_int(TB.w));
-    const bool pass = valid && (CAM ? Ar<EX>::slab_rel(ri, TA.x, TA.y, TA.z, TA.w, TB.x, TB.y) : Ar<EX>::slab(o, ri, TA.x, TA.y, TA.z, TA.w, TB.x, TB.y));
+    const bool pass = valid && Ar<EX>::slab(o, ri, TA.x, TA.y, TA.z, TA.w, TB.x, TB.y);
     if (t_link < 0) {  // leaf entry: type is wave-uniform
       const unsigned long long m = ballot(pass);
       if (m) {
         if (nb + ns + 64 > kCandCap) {
-          flush_candidates<CAM, QO, EX>(w, nb, ns, lane, o, d, nodes, geoms, qo_tab, tri);
+          flush_candidates<false, EX>(w, nb, ns, lane, o, d, nodes, geoms, tri);
           nb = ns = 0;
         }
         const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
@@ -765,7 +712,7 @@ PT_DEV void trace_group(const WaveLds& w, const float4* top, int ntop, const ptd
       const unsigned long long mb = ballot(cbox), msp = ballot(csph);
       if (mb | msp) {
         if (nb + ns + 128 > kCandCap) {
-          flush_candidates<CAM, QO, EX>(w, nb, ns, lane, o, d, nodes, geoms, qo_tab, tri);
+          flush_candidates<false, EX>(w, nb, ns, lane, o, d, nodes, geoms, tri);
           nb = ns = 0;
         }
         const uint32_t entry = ((uint32_t)at_n << 6) | (uint32_t)wk.own;
@@ -779,7 +726,7 @@ PT_DEV void trace_group(const WaveLds& w, const float4* top, int ntop, const ptd
       }
     }
   }
-  if (nb + ns) flush_candidates<CAM, QO, EX>(w, nb, ns, lane, o, d, nodes, geoms, qo_tab, tri);
+  if (nb + ns) flush_candidates<false, EX>(w, nb, ns, lane, o, d, nodes, geoms, tri);
 }
 
 // Primary rays of a scene whose tables stay in memory (more than 32 leaves, no grid): the candidate search as ONE scan of the
@@ -792,7 +739,7 @@ PT_DEV void trace_group(const WaveLds& w, const float4* top, int ntop, const ptd
 typedef __attribute__((address_space(4))) const v4f cnode4;  // wave-uniform indices into it become scalar loads
 template <bool EX>
 PT_DEV void trace_group_packet(const WaveLds& w, const ptd::Node* __restrict__ nodes, int num_nodes, const ptd::Geom* __restrict__ geoms,
-                               f3 o, f3 d, bool valid, int lane, const float* qo_tab, bool tri) {
+                               f3 o, f3 d, bool valid, int lane, bool tri) {
   const RayInv ri = Ar<EX>::ray_inv(d, o);
   w.best[lane] = kNoHit;
   int nb = 0, ns = 0;  // pending cubes (front of the list) / others (back)
@@ -811,7 +758,7 @@ PT_DEV void trace_group_packet(const WaveLds& w, const ptd::Node* __restrict__ n
     }
     if (gi >= 0) {  // a leaf some lane passes: type is wave-uniform
       if (nb + ns + 64 > kCandCap) {
-        flush_candidates<true, false, EX>(w, nb, ns, lane, o, d, nodes, geoms, qo_tab, tri);
+        flush_candidates<true, EX>(w, nb, ns, lane, o, d, nodes, geoms, tri);
         nb = ns = 0;
       }
       const int rank = rank_in(m), cnt = __popcll(m);
@@ -826,7 +773,7 @@ PT_DEV void trace_group_packet(const WaveLds& w, const ptd::Node* __restrict__ n
     }
     ++i;
   }
-  if (nb + ns) flush_candidates<true, false, EX>(w, nb, ns, lane, o, d, nodes, geoms, qo_tab, tri);
+  if (nb + ns) flush_candidates<true, EX>(w, nb, ns, lane, o, d, nodes, geoms, tri);
 }
 
 template <bool TABLES_IN_LDS, bool EX>
@@ -881,7 +828,7 @@ __global__ __launch_bounds__(kBlock) void k_intersect(SceneTables sc, ptd::Queue
     const int64_t at = qbase + i;
     const f3 o = no, d = nd;
     path_load_ray(paths, qbase + min((j + wq) * 64 + lane, last), no, nd);
-    trace_group<false, false, EX>(w, top, ntop, nodes, geoms, o, d, valid, lane, sc.cull_margin, sc.top_xor, nullptr, sc.has_triangles != 0);
+    trace_group<EX>(w, top, ntop, nodes, geoms, o, d, valid, lane, sc.cull_margin, sc.top_xor, sc.has_triangles != 0);
 
     const unsigned long long best = w.best[lane];
     const bool hit = (uint32_t)(best >> 32) != 0x7f7fffffu;
@@ -1144,14 +1091,8 @@ PT_DEV void carry_drain_to(Carry<SMALL, NPAR>& c, int mark, int lane, const ptd:
 // files ~85 candidates, which the per-group form (trace_group) ran as one full chunk plus one a third full — and the
 // appends run lane-major (two-phase search).  A group is shaded one loop iteration after its search, like in k_bounce.
 // Unlike the ring form tried in round 2 it keeps the camera-relative boxes and the per-geom object-space camera position.
-#ifndef PT_PRIMARY_RING
-#define PT_PRIMARY_RING 1
-#endif
-#ifndef PT_PRIMARY_PACKET
-#define PT_PRIMARY_PACKET 1  // global-table scenes: one wave-uniform scan of the threaded tree per group (trace_group_packet) instead of top list + per-lane subtree scans
-#endif
-template <bool TABLES_IN_LDS, bool GRID>
-constexpr bool primary_ring() { return PT_PRIMARY_RING != 0 && TABLES_IN_LDS && !GRID; }
+// Tables in memory, no grid: one wave-uniform scan of the threaded tree per group (trace_group_packet) instead of
+// top list + per-lane subtree scans.
 template <bool TABLES_IN_LDS, bool GRID = false>
 __global__ __launch_bounds__(kBlock, kPrimaryWaves) void k_primary(SceneTables sc, ptd::Camera cam, BatchInfo b, ptd::Queues qs,
                                                     int32_t* __restrict__ cnt0, int32_t* __restrict__ cnt_out,
@@ -1176,7 +1117,7 @@ __global__ __launch_bounds__(kBlock, kPrimaryWaves) void k_primary(SceneTables s
     geoms = reinterpret_cast<const ptd::Geom*>(lds + tbl + nb_nodes);
     tbl += nb_nodes + nb_geoms;
   }
-  constexpr bool RING = primary_ring<TABLES_IN_LDS, GRID>();
+  constexpr bool RING = TABLES_IN_LDS;  // (GRID reads the tables from memory)
   constexpr int kWaveBytes = GRID ? grid_wave_bytes<kD0>() : (RING ? carry_bytes<true, 2>() : kWaveLds);
   uint32_t* ihash = reinterpret_cast<uint32_t*>(lds + tbl + kWavesPerBlock * kWaveBytes);  // after the per-wave blocks
   iter_hash_fill(ihash, sc, b, 0);
@@ -1336,8 +1277,7 @@ __global__ __launch_bounds__(kBlock, kPrimaryWaves) void k_primary(SceneTables s
               while (cy.count > 0) carry_chunk<false, 1, kD0, true>(cy, min(64, cy.count), lane, nodes, geoms);
             }
           } else if (near_scene) {
-            if constexpr (!TABLES_IN_LDS && PT_PRIMARY_PACKET != 0) trace_group_packet<kD0>(w, nodes, sc.num_nodes, geoms, o, d, valid, lane, cam_qo, sc.has_triangles != 0);
-            else trace_group<true, TABLES_IN_LDS, kD0>(w, cam_top, ntop, nodes, geoms, o, d, valid, lane, sc.cull_margin, sc.top_xor, cam_qo, sc.has_triangles != 0);
+            trace_group_packet<kD0>(w, nodes, sc.num_nodes, geoms, o, d, valid, lane, sc.has_triangles != 0);
           } else {
             w.best[lane] = kNoHit;
           }
@@ -1381,13 +1321,8 @@ __global__ __launch_bounds__(kBlock, kPrimaryWaves) void k_primary(SceneTables s
 //   * every vector-memory operation outstanding at the refill's s_waitcnt vmcnt(0) is a whole iteration old: the retirement
 //     store of a lane that died is issued AFTER the slot reads of the next refill (the dead lane's colour and sample id
 //     stay in its registers until then).
-#ifndef PT_PATHS_WAVES
-#define PT_PATHS_WAVES 6
-#endif
-#ifndef PT_PATHS_MIN_READY
-#define PT_PATHS_MIN_READY 32  // fewer resolved lanes than this and candidates pending: run the partial chunk instead of shading a thin group
-#endif
-constexpr int kPathsWaves = PT_PATHS_WAVES, kPathsMinReady = PT_PATHS_MIN_READY;
+constexpr int kPathsWaves = 6;
+constexpr int kPathsMinReady = 32;  // fewer resolved lanes than this and candidates pending: run the partial chunk instead of shading a thin group
 constexpr int kSlotBytes = 64 * 16 + 64 * 16 + 64 * 4 + 64 * 4 + 64 * 4;  // planes 0, 1 (16 B per lane), colour.z, sample id, record slot
 PT_DEV uint32_t lds_offset(const void* p) { return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)p; }
 // memory -> LDS without passing through VGPRs: path record i of a queue (b0 / b1 / b2 = the queue's first record in planes 0,
@@ -1465,10 +1400,6 @@ PT_DEV void paths_chunk(Lanes& c, int n, int lane, f3 o, f3 d, const uint32_t* t
 // Candidate search of the fresh lanes of a persistent group (LDS-table scenes: every top entry is a leaf) — carry_search's
 // two-phase form with the per-lane resolution mark: `mark` = ring entries appended up to and including the lane's last one.
 // tword[e] = leaf | geom << 8 of top entry e (read by the chunks).
-#ifndef PT_TOP_SCALAR
-#define PT_TOP_SCALAR (PT_ARITH == 2)  // mode 0, fast build: the top list's boxes come through scalar loads (constant address space: s_load into SGPRs, the scalar cache) instead of
-                                       // broadcast LDS reads into VGPRs: 73 -> 67 VGPRs; in-box fast +0.8 %, exact -1.4 % (its longer tests already cover the LDS latency)
-#endif
 typedef __attribute__((address_space(4))) const v4f cfloat4;  // wave-uniform indices into it become scalar loads (a builtin vector: HIP's float4 class cannot be copied out of another address space)
 template <typename TOP>
 PT_DEV void paths_search(Lanes& c, TOP* top, const uint32_t* tword, int ntop, const ptd::Geom* __restrict__ geoms, f3 o, f3 d,
@@ -1518,17 +1449,11 @@ PT_DEV void paths_search(Lanes& c, TOP* top, const uint32_t* tword, int ntop, co
 //         per-lane mark would need cross-lane bookkeeping): all live lanes are searched and shaded in every round.
 //         The grid walk's rings leave no LDS for refill slots (three workgroups per CU with them: measured 17-22 % slower than
 //         the per-depth kernel it replaces), and its rounds take tens of microseconds: the next record of a lane waits in
-//         REGISTERS there, loaded a round ahead by ordinary loads (waves per SIMD: see PT_PATHS_GRID_WAVES; prefetching only origin
+//         REGISTERS there, loaded a round ahead by ordinary loads (waves per SIMD: see kPathsGridWaves; prefetching only origin
 //         and direction and loading the rest on demand: slower).
-#ifndef PT_PATHS_SCAN_WAVES
-#define PT_PATHS_SCAN_WAVES 5
-#endif
-#ifndef PT_PATHS_GRID_WAVES  // 95-96 VGPRs without scratch since the wave index is scalar; in-box 4 and 5 are level for the fast build, 5 wins for exact
-#define PT_PATHS_GRID_WAVES 5
-#endif
-#ifndef PT_SLOTS_MODES
-#define PT_SLOTS_MODES 0  // experiment: 0 = only mode 0 keeps refill slots in LDS
-#endif
+// Waves per SIMD of modes 1 and 2 (mode 0: kPathsWaves).  Mode 2: 95-96 VGPRs without scratch since the wave index is scalar;
+// in-box 4 and 5 are level for the fast build, 5 wins for exact.
+constexpr int kPathsScanWaves = 5, kPathsGridWaves = 5;
 // k_paths' visit ring (fillc): one record counter per sub-list visit of the cursor, kVisitRing per wave, taken modulo the ring.
 // A refill starts only while every path in flight was taken fewer than kVisitLap visits ago; it makes at most kVisitsPerRefill
 // new visits and the seek of a new piece one more, so no counter of a path in flight is handed to another visit.
@@ -1536,15 +1461,13 @@ constexpr int kVisitRing = 64, kVisitLap = 32, kVisitsPerRefill = 31;
 static_assert(kVisitLap + kVisitsPerRefill + 1 <= kVisitRing, "the visit ring laps a path in flight");
 static_assert((kVisitRing & (kVisitRing - 1)) == 0, "visit numbers wrap with a mask");
 template <int MODE>
-constexpr bool paths_slots_in_lds() { return MODE == 0 || (MODE == 1 && PT_SLOTS_MODES == 1); }
-template <int MODE>
-constexpr int paths_extra_bytes() { return (paths_slots_in_lds<MODE>() ? kSlotBytes : 0) + 64 * 4 + kVisitRing * 4; }  // refill slots + 64 counters: paths retired per depth + the visit ring
+constexpr int paths_extra_bytes() { return (MODE == 0 ? kSlotBytes : 0) + 64 * 4 + kVisitRing * 4; }  // refill slots (mode 0) + 64 counters: paths retired per depth + the visit ring
 template <int MODE>
 constexpr int paths_wave_bytes() {
   return (MODE == 0 ? kLanesBytes : MODE == 1 ? carry_bytes<false, 1>() : grid_wave_bytes<false>()) + paths_extra_bytes<MODE>();
 }
 template <int MODE>
-__global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? PT_PATHS_SCAN_WAVES : PT_PATHS_GRID_WAVES) void k_paths(SceneTables sc, BatchInfo b, ptd::Queues qs, int32_t* __restrict__ cnt /* [depth][Q] rows */,
+__global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPathsScanWaves : kPathsGridWaves) void k_paths(SceneTables sc, BatchInfo b, ptd::Queues qs, int32_t* __restrict__ cnt /* [depth][Q] rows */,
                                                                ptd::PathBuf in, ptd::RetireBuf ret) {
   extern __shared__ float4 lds_raw[];
   char* lds = reinterpret_cast<char*>(lds_raw);
@@ -1594,7 +1517,7 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? PT_PA
   CellRing cr{reinterpret_cast<uint32_t*>(wbase + carry_bytes<false, 1>()), 0, 0, nullptr};
   if (MODE == 2) cb.gix = cr.ent + kCellRing, cr.rinv = reinterpret_cast<float*>(cr.ent + kCellRing + kRing);
   cb.lnodes = (const __attribute__((address_space(3))) v4f*)(lnodes ? lnodes : lds), cb.lds_nodes = lnodes != nullptr;
-  constexpr bool SLOTS = paths_slots_in_lds<MODE>();
+  constexpr bool SLOTS = MODE == 0;
   char* slots = wbase + core_bytes;  // SLOTS: [64] x 16 B, [64] x 16 B, [64] x 4 B, [64] x 4 B
   int* died = reinterpret_cast<int*>(slots + (SLOTS ? kSlotBytes : 0));  // [64]: paths of this wave retired AT depth d (statistics; PT_MAX_DEPTH = 64)
   int* fillc = died + 64;                                                 // [kVisitRing]: next record slot per sub-list visit
@@ -1844,7 +1767,9 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? PT_PA
     if constexpr (MODE == 0) {
       // ── search: box tests + appends for the lanes with a new ray; full chunks as the ring fills ──
       if (ballot(fresh)) {
-        if constexpr (PT_TOP_SCALAR != 0) paths_search(cy, (cfloat4*)(uintptr_t)sc.top_b, tword, ntop, geoms, o, d, fresh, lane, mark);
+        // fast build: the top list's boxes come through scalar loads (constant address space: s_load into SGPRs, the scalar cache)
+        // instead of broadcast LDS reads into VGPRs: 73 -> 67 VGPRs; in-box fast +0.8 %, exact -1.4 % (its longer tests cover the LDS latency)
+        if constexpr (kFast) paths_search(cy, (cfloat4*)(uintptr_t)sc.top_b, tword, ntop, geoms, o, d, fresh, lane, mark);
         else paths_search(cy, top, tword, ntop, geoms, o, d, fresh, lane, mark);
       }
       // ── which lanes are resolved?  Too few, with candidates pending: run them as a partial chunk ──
@@ -1965,7 +1890,7 @@ const KernelApi kApi = {
 #endif
     launch_generate, launch_primary, launch_intersect, launch_shade, launch_collect, launch_count_stats,
     launch_preview, launch_save_u8, launch_shade_stage, lds_table_limit, resident_blocks_per_cu, launch_ieee_check, launch_paths,
-    md::kFastSlab ? 1 : 0};
+    kFast ? 1 : 0};
 
 }  // namespace
 }  // namespace PT_NS

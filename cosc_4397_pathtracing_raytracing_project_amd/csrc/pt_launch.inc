@@ -23,7 +23,7 @@ SceneTables resolve_scan_nodes(const SceneTables& sc_in) {
     SceneTables without = sc;
     without.max_batch_iters = kIterHashMax + 1;
     const int mode = paths_mode(sc);
-    const int reg_waves = mode == 0 ? kPathsWaves : mode == 1 ? PT_PATHS_SCAN_WAVES : PT_PATHS_GRID_WAVES;
+    const int reg_waves = mode == 0 ? kPathsWaves : mode == 1 ? kPathsScanWaves : kPathsGridWaves;
     SceneTables a = sc, b = without;
     if (a.scan_nodes_lds < 0) a.scan_nodes_lds = b.scan_nodes_lds = 0;
     const bool costs = min(lds_share_limit(paths_lds_bytes(b, mode)), reg_waves) > min(lds_share_limit(paths_lds_bytes(a, mode)), reg_waves);
@@ -34,7 +34,7 @@ SceneTables resolve_scan_nodes(const SceneTables& sc_in) {
   SceneTables with = sc, without = sc;
   with.scan_nodes_lds = 1, without.scan_nodes_lds = 0;
   const int bw = paths_lds_bytes(with, 1), bo = paths_lds_bytes(without, 1);
-  t.scan_nodes_lds = (bw <= 64 * 1024 && lds_share_limit(bw) >= min(lds_share_limit(bo), PT_PATHS_SCAN_WAVES)) ? 1 : 0;  // (registers allow PT_PATHS_SCAN_WAVES workgroups per CU)
+  t.scan_nodes_lds = (bw <= 64 * 1024 && lds_share_limit(bw) >= min(lds_share_limit(bo), kPathsScanWaves)) ? 1 : 0;  // (registers allow kPathsScanWaves workgroups per CU)
   return t;
 }
 int paths_lds_bytes(const SceneTables& sc, int mode) {
@@ -70,10 +70,8 @@ int lds_table_limit(const SceneTables& sc, int forced_bytes) {
 // The occupancy query over-reports by one workgroup when the LDS of a block is a few hundred bytes under a 1/n share of the
 // CU's 160 KB (measured, round 4: 27,088 B per block: 6 reported, 5 resident — and a persistent grid one block too large runs
 // that block's whole share after everybody else: k_paths 1335 -> 1607 us).  A share is therefore counted in 1280-byte granules.
-#ifndef PT_LDS_GRANULE
-#define PT_LDS_GRANULE 1280
-#endif
-int lds_share_limit(int bytes) { return bytes > 0 ? (160 * 1024) / (((bytes + PT_LDS_GRANULE - 1) / PT_LDS_GRANULE) * PT_LDS_GRANULE) : 8; }
+constexpr int kLdsGranule = 1280;
+int lds_share_limit(int bytes) { return bytes > 0 ? (160 * 1024) / (((bytes + kLdsGranule - 1) / kLdsGranule) * kLdsGranule) : 8; }
 int resident_blocks_per_cu(KernelId id, const SceneTables& sc) {
   int n = 0, lds = 0;
   hipError_t e = hipSuccess;
@@ -95,7 +93,7 @@ int resident_blocks_per_cu(KernelId id, const SceneTables& sc) {
       break;
     case kPrimary:
       if (sc.use_grid) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_primary<false, true>, kBlock, lds = primary_grid_lds_bytes(sc));
-      else if (in_lds) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_primary<true>, kBlock, lds = fused_lds_bytes(sc, true, primary_ring<true, false>() ? carry_bytes<true>() : kWaveLds, true));
+      else if (in_lds) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_primary<true>, kBlock, lds = fused_lds_bytes(sc, true, carry_bytes<true>(), true));
       else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_primary<false>, kBlock, lds = fused_lds_bytes(sc, false, kWaveLds, true));
       break;
     case kPaths:
@@ -140,7 +138,7 @@ void launch_intersect(hipStream_t s, int grid, const SceneTables& sc, const ptd:
 void launch_primary(hipStream_t s, int grid, const SceneTables& sc, const ptd::Camera& cam, const BatchInfo& b,
                     const ptd::Queues& qs, int32_t* cnt0, int32_t* cnt_out, ptd::PathBuf out, ptd::RetireBuf ret) {
   if (sc.use_grid) hipLaunchKernelGGL((k_primary<false, true>), dim3(grid), dim3(kBlock), primary_grid_lds_bytes(sc), s, sc, cam, b, qs, cnt0, cnt_out, out, ret);
-  else if (tables_in_lds(sc)) hipLaunchKernelGGL(k_primary<true>, dim3(grid), dim3(kBlock), fused_lds_bytes(sc, true, primary_ring<true, false>() ? carry_bytes<true>() : kWaveLds, true), s, sc, cam, b, qs, cnt0, cnt_out, out, ret);
+  else if (tables_in_lds(sc)) hipLaunchKernelGGL(k_primary<true>, dim3(grid), dim3(kBlock), fused_lds_bytes(sc, true, carry_bytes<true>(), true), s, sc, cam, b, qs, cnt0, cnt_out, out, ret);
   else hipLaunchKernelGGL(k_primary<false>, dim3(grid), dim3(kBlock), fused_lds_bytes(sc, false, kWaveLds, true), s, sc, cam, b, qs, cnt0, cnt_out, out, ret);
 }
 

@@ -8,9 +8,6 @@
 // pixels: image[p] = (((image[p] + c_0) + c_1) + ...), the order in which successive finalGather launches would have added
 // them.  Nothing is scattered through memory: the regions are read once, the image is read and written once.  Queues
 // with more pixels than a tile (frames beyond 4K at Q = 256 .. 1024) take several passes over their records.
-#ifndef PT_COLLECT_GUARD
-#define PT_COLLECT_GUARD 1
-#endif
 constexpr int kCollectThreads = 1024;
 constexpr int kCollectPPT = 8;                                // pixels (and records) per thread and pass
 constexpr int kCollectPixels = kCollectPPT * kCollectThreads;  // 8192 pixels = 128 chunks: 96 KB of LDS
@@ -24,7 +21,7 @@ struct CollectChunk {
 PT_DEV void collect_load(const ptd::Word4* rec, int n, int i0, CollectChunk& c) {
 #pragma unroll
   for (int u = 0; u < kCollectPPT; ++u) {
-    if (PT_COLLECT_GUARD && u > 0 && i0 + u * kCollectThreads >= n) break;
+    if (u > 0 && i0 + u * kCollectThreads >= n) break;
     const int i = i0 + u * kCollectThreads + (int)threadIdx.x;
     c.v[u] = rec[i < n ? i : (n > 0 ? n - 1 : 0)];
   }
@@ -33,7 +30,7 @@ PT_DEV void collect_load(const ptd::Word4* rec, int n, int i0, CollectChunk& c) 
 PT_DEV void collect_scatter(const CollectChunk& c, int n, int i0, int g0, int g1, int Q, float inv_q, int first, float* tile) {
 #pragma unroll
   for (int u = 0; u < kCollectPPT; ++u) {
-    if (PT_COLLECT_GUARD && u > 0 && i0 + u * kCollectThreads >= n) break;
+    if (u > 0 && i0 + u * kCollectThreads >= n) break;
     const int i = i0 + u * kCollectThreads + (int)threadIdx.x;
     const int pl = __float_as_int(c.v[u].w);
     int jj, qq;
@@ -85,7 +82,7 @@ __global__ __launch_bounds__(kCollectThreads) void k_collect(BatchInfo b, ptd::Q
       __syncthreads();
 #pragma unroll
       for (int m = 0; m < kCollectPPT; ++m) {
-        if (PT_COLLECT_GUARD && m > 0 && first + kCollectThreads * m >= sh.my_nq * 64) break;  // block-uniform: pixels the queue does not have
+        if (m > 0 && first + kCollectThreads * m >= sh.my_nq * 64) break;  // block-uniform: pixels the queue does not have
         const int li = threadIdx.x + kCollectThreads * m;  // every pixel of the queue retires exactly once per iteration: no stale entries are read
         acc[m][0] += tile[3 * li], acc[m][1] += tile[3 * li + 1], acc[m][2] += tile[3 * li + 2];
       }

@@ -53,7 +53,7 @@ PT_DEV Bounce shade_decide(const ptd::Mat* __restrict__ mats, int trace_depth, i
   if (depth > 3) {  // Russian roulette
     const float q = __builtin_fmaxf(mcolor.x, __builtin_fmaxf(mcolor.y, mcolor.z));
     if (rng.u01() > q) return bo;
-    if (kFastDiv) s.c = scl(s.c, __builtin_amdgcn_rcpf(q));
+    if (kFast) s.c = scl(s.c, __builtin_amdgcn_rcpf(q));
     else ieee::div3(s.c.x, s.c.y, s.c.z, q);
   }
   const float reflectivity = m->reflective;
@@ -118,7 +118,7 @@ PT_DEV void shade_bounce_float(const Bounce& bo, f3 hn, f3 hp, ShadeIO& s) {
   s.d = perturb ? pert : refl;
 }
 PT_DEV void shade_bounce(const Bounce& bo, f3 hn, f3 hp, ShadeIO& s) {
-  if (kFastTrig) return shade_bounce_float<true>(bo, hn, hp, s);
+  if (kFast) return shade_bounce_float<true>(bo, hn, hp, s);
   if (kFloatTrig) return shade_bounce_float<false>(bo, hn, hp, s);
   // The specular branch (pathtrace.cu:402-422) and the diffuse branch (:424-435, :225-238) have the
   // same shape — a frame around an axis f, three trigonometric evaluations, normalize(t*x + f*y + b*z)

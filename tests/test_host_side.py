@@ -164,6 +164,25 @@ def test_product_never_touches_oracle():
                 assert "liboracle" not in txt and "oracle.binding" not in txt and "from oracle" not in txt, os.path.join(d, f)
 
 
+def test_kernel_build_has_no_compile_time_switches():
+    """Product constants are constexpr, not overridable macros: the only identifiers the preprocessor tests are the
+    arithmetic mode, the diagnostic PT_WALK_STATS build and the compiler's own; the Makefile defines PT_ARITH alone.
+    A new switch needs a deliberate edit of this list."""
+    csrc = os.path.join(ROOT, "cosc_4397_pathtracing_raytracing_project_amd", "csrc")
+    tested = set()
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hip", ".inc", ".h")):
+            for line in open(os.path.join(csrc, f), errors="replace"):
+                m = re.match(r"\s*#\s*(?:if|ifdef|ifndef|elif)\b(.*)", line)
+                if m:
+                    cond = re.sub(r"//.*|/\*.*?\*/", "", m.group(1))
+                    tested |= set(re.findall(r"\b[A-Za-z_]\w*", cond)) - {"defined"}
+    assert "PT_ARITH" in tested
+    assert tested <= {"PT_ARITH", "PT_WALK_STATS", "__HIPCC__"}, sorted(tested)
+    make = open(os.path.join(csrc, "Makefile")).read()
+    assert set(re.findall(r"-D\s*(\w+)", make)) == {"PT_ARITH"}
+
+
 REF_TOKENS = os.path.join(HERE, "golden", "ref_scene_tokens.json")  # SHA-256 of the reference's scenes/*.txt token streams
 
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Flip-rate of the arithmetic modes on the GPU: for every library given (variants from tools/arith_bisect.sh, or the
-product library) render cornell at 256x256x16 spp and 800x800x8 spp in the fast mode and count the pixels that differ
+"""Flip-rate of the arithmetic modes on the GPU: for every library given (the product library, or A/B builds of
+tools/build_variant.sh) render cornell at 256x256x16 spp and 800x800x8 spp in the fast mode and count the pixels that differ
 from the reference semantics (oracle, LIBM, reference-literal loop) by more than 1e-5, with the PSNR.  One child
 process per library (PT_AMD_LIB is read at import)."""
 import json, os, subprocess, sys

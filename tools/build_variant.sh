@@ -1,7 +1,7 @@
 #!/bin/bash
 # Builds an A/B variant of the whole library (all three kernel translation units with extra -D flags) into
 # build/variants/NAME.so; load it with PT_AMD_LIB=build/variants/NAME.so (capi.py).  The in-tree library is untouched.
-# usage: tools/build_variant.sh NAME "-DPT_BOUNCE_WAVES=4 ..." [GIT_REV]
+# usage: tools/build_variant.sh NAME "-DPT_WALK_STATS ..." [GIT_REV]
 # With GIT_REV the kernel sources (pt_kernels.hip, its *.inc files, headers) are taken from that commit instead of the
 # working tree (old-vs-new A/B in one gpurun call); the host objects are the current ones, so the C ABI must match.
 set -e

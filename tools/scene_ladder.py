@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Scene-size ladder at 1080p: cornell.txt (7 primitives) and random scenes of 10 ... 1000 objects inside the cornell box
 (+ its 6 walls), plus BASELINE config C5 (10,170 primitives) — Msamples/s per arithmetic mode with the library's own
-choices, and with `--flags` extra debug_flags sets for A/B (e.g. 4096 = one launch per depth).  Images of all arms of
-a scene are compared bit for bit within a mode.
-usage: tools/scene_ladder.py [--spp N] [--arith fast,exact] [--flags 0,4096] [--sizes 7,16,26,58,150,494,994,c5]"""
+choices, and with `--flags` extra debug_flags sets for A/B (e.g. 512 = BVH scan instead of the grid walk).  Images of all
+arms of a scene are compared bit for bit within a mode.
+usage: tools/scene_ladder.py [--spp N] [--arith fast,exact] [--flags 0,512] [--sizes 7,16,26,58,150,494,994,c5]"""
 import argparse, os, sys, tempfile, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
