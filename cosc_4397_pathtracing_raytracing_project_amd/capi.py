@@ -214,8 +214,9 @@ class Scene:
         return [self.desc.materials[i] for i in range(self.desc.num_materials)]
 
     def grid(self, forced: bool = False):
-        """The uniform grid over the leaf boxes the renderer would walk (pt_build_grid): (info, cell_start, records) or
-        None when the scene keeps the BVH scan."""
+        """The uniform grid of the cost model's resolution over the reference's leaf boxes, without the camera (pt_build_grid):
+        (info, cell_start, records), or None when the scene is no grid candidate.  A renderer builds its grids the same way
+        over its traversal boxes (tightened sphere leaves), so they need not equal this one byte for byte."""
         info = PtGridInfo()
         rc = lib().pt_build_grid(self.desc.geoms, self.desc.num_geoms, int(forced), C.byref(info), None, None)
         if rc < 0:

@@ -30,6 +30,7 @@ static_assert(sizeof(Node) == 32, "Node must be 32 B");
 // accepts.  Inner nodes are therefore pure acceleration, and the top of the tree is replaced
 // by a short list every ray tests with wave-uniform (scalar-loaded) box data; only subtrees
 // below the cut are walked per lane.  For cornell.txt the cut is the 7 leaves themselves.
+constexpr int kMaxTop = 32;  // entries in the flattened BVH top (per-lane 32-bit subtree mask)
 struct TopEntry {
   float bmin[3];
   float bmax[3];

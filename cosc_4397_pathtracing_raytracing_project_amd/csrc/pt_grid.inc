@@ -87,7 +87,7 @@ PT_DEV void grid_filter(Carry<false, NPAR>& c, CellRing& cr, int n, const SceneT
 // between boundaries, the current cell.  A walk ends by distance alone (te > t_end, the grid's far side): the boundary
 // distances accumulate rounding, so the decision at the exit face can come a step late — up to three steps at a corner of
 // the grid — and the cell index then leaves the grid by at most one cell per axis, i.e. by < rx * ry + rx + 2 entries of
-// the cell table: the host pads the table with that many empty cells on both sides (pt_api.cpp), and a wrapped index
+// the cell table: the host pads the table with that many empty cells on both sides (pt_tables.cpp), and a wrapped index
 // inside the table only adds records to test (round 2 counted the cells left per axis instead: 3 registers and 6
 // instructions per step).
 struct CellWalk {

@@ -9,7 +9,7 @@ namespace ptk {
 constexpr int kBlock = 256;        // 4 wave64 per workgroup
 constexpr int kWavesPerBlock = 4;
 constexpr int kLdsTableBytes = 64 * 1024;  // upper limit for staging the scene tables in LDS (see auto_lds_table_limit)
-constexpr int kMaxTop = 32;                // entries in the flattened BVH top (per-lane 32-bit subtree mask)
+constexpr int kMaxTop = ptd::kMaxTop;      // entries in the flattened BVH top (pt_device.h TopEntry)
 constexpr int kCandCap = 192;              // per-wave candidate list entries (LDS)
 constexpr int kWaveLds = 64 * 8 + 7 * 64 * 4 + kCandCap * 4;  // best keys + winner records + list = 3072 B
 
@@ -27,7 +27,7 @@ struct SceneTables {
   // by more than this margin cannot contain the closest hit.  The reported hit distance is measured to a point
   // pulled 1e-4 object units towards the ray origin (intersections.h:27-29) and carries the rounding of two
   // matrix products, so it can undershoot the true distance by 1e-4 * |transform| + O(1e-6 * |coordinates|); the
-  // host sets a margin an order of magnitude above that bound (pt_api.cpp).  Negative: culling disabled.
+  // host sets a margin an order of magnitude above that bound (pt_tables.cpp cull_margin).  Negative: culling disabled.
   float cull_margin;
   // Near-first subtree order: byte k = XOR mask for rays whose direction sign bits are k = sx | sy << 1 | sz << 2
   // (pt_kernels.hip permute_xor); 0 when the top list is not a complete level of the tree.
@@ -38,7 +38,7 @@ struct SceneTables {
   // Iterations per wavefront batch of the context (>= every BatchInfo::K it launches): sizes the per-iteration RNG hash
   // table in LDS (none beyond 256 iterations, those batches hash per ray).
   int32_t max_batch_iters;
-  // Uniform grid over the leaf boxes (pt_api.cpp build_grid; grid_search in pt_kernels.hip): the fused kernels of large
+  // Uniform grid over the leaf boxes (pt_tables.cpp build_grid; grid_search in pt_kernels.hip): the fused kernels of large
   // scenes walk it instead of the BVH when that is faster (measured by the host at init).  A cell lists every leaf whose box,
   // grown by grid_pad, overlaps it: cell c's records are grid_items[grid_start[c] .. grid_start[c + 1]), each a ptd::Node
   // with the leaf's box, `skip` = the leaf's threaded node index and `geom` = geom index << 8 | primitive type << 6 | bit a
@@ -55,7 +55,7 @@ struct SceneTables {
   // The box tables of the BOUNCE kernels (depths >= 1; depth 0 always reads the ones above with the reference's arithmetic).  The
   // same tables, except in the fast build (KernelApi::boxes_center_half), whose slab test takes a box as centre and half extent
   // (pt_arith.inc slab_t): there the host uploads converted copies — bmin = centre, bmax = half extent rounded up so that the
-  // box contains the original, inner nodes and subtree entries a little more (pt_api.cpp center_half_boxes).
+  // box contains the original, inner nodes and subtree entries a little more (pt_tables.cpp center_half_box).
   const ptd::Node* nodes_b;
   const ptd::TopEntry* top_b;
   const ptd::Node* grid_items_b;

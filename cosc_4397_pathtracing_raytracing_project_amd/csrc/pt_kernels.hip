@@ -407,7 +407,7 @@ struct HitRec {
 };
 
 // Near-first order of a ray's entered subtrees.  When the top list is a complete level of a balanced tree its
-// entries are laid out by path code (bit 4 = child taken at the root, ... bit 0 = at level 4; pt_api.cpp build_top),
+// entries are laid out by path code (bit 4 = child taken at the root, ... bit 0 = at level 4; pt_tables.cpp build_top),
 // so visiting the nearer child first at every level is visiting the entries in increasing (index XOR m) order,
 // where bit l of m says that the nearer child at that level is child 1 for this ray's direction signs
 // (SceneTables::top_xor, one mask per sign octant).  permute_xor returns the pending mask re-indexed by

@@ -1,0 +1,443 @@
+// pt_tables.cpp — the scene tables of the MI355X path tracer (pt_tables.h), pure host arithmetic.  Compiled with
+// -ffp-contract=off like the kernels' exact build: box_normal_table must round as the device does.
+#include "pt_tables.h"
+
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstring>
+
+#include "pt_scene.h"
+
+namespace pt {
+
+// Re-emit the reference-order BVH (node, left, right links) in visiting order with
+// skip links (see ptd::Node).  Visiting order of the reference's stack walk is:
+// node, then its RIGHT subtree, then its LEFT subtree (pathtrace.cu:321-322).
+static void thread_bvh(const std::vector<PtBVHNode>& in, int idx, std::vector<ptd::Node>& out, std::vector<int>& where) {
+  const PtBVHNode& n = in[idx];
+  const size_t self = out.size();
+  where[idx] = (int)self;
+  ptd::Node t{};
+  std::memcpy(t.bmin, n.bmin, 12);
+  std::memcpy(t.bmax, n.bmax, 12);
+  t.geom = n.left < 0 ? n.geomIndex : -1;
+  out.push_back(t);
+  if (n.left >= 0) {
+    thread_bvh(in, n.right, out, where);
+    thread_bvh(in, n.left, out, where);
+  }
+  out[self].skip = (int32_t)out.size();
+}
+ThreadedBvh threaded_bvh(const PtGeom* geoms, int num_geoms) {
+  ThreadedBvh t;
+  pt::buildBVH(geoms, num_geoms, t.ref);
+  t.nodes.reserve(t.ref.size());
+  t.where.assign(t.ref.size(), -1);
+  thread_bvh(t.ref, 0, t.nodes, t.where);
+  return t;
+}
+
+// Flatten the top of the tree into at most ptd::kMaxTop entries (see ptd::TopEntry): start from
+// the root and keep splitting the inner entry that covers the most nodes.  The entries are emitted in
+// path-code order (0 = left child, 1 = right child, root choice in the most significant bit); when
+// the cut is a complete level (every entry at the same depth, a power of two of them) `top_xor`
+// receives, per direction-sign octant, the XOR mask that turns list order into near-first order
+// (pt_kernels.hip permute_xor), otherwise 0.
+static void build_top(const std::vector<PtBVHNode>& ref, const std::vector<ptd::Node>& thr, const std::vector<int>& where,
+                      const PtGeom* geoms, std::vector<ptd::TopEntry>& top, unsigned long long* top_xor) {
+  struct Cut {
+    int ref_idx;
+    uint32_t code;
+    int len;
+  };
+  std::vector<Cut> cut{{0, 0u, 0}};
+  auto span = [&](int ref_idx) { return thr[where[ref_idx]].skip - where[ref_idx]; };
+  while ((int)cut.size() < ptd::kMaxTop) {
+    int best = -1;
+    for (size_t i = 0; i < cut.size(); ++i)
+      if (ref[cut[i].ref_idx].left >= 0 && cut[i].len < 24 && (best < 0 || span(cut[i].ref_idx) > span(cut[best].ref_idx)))
+        best = (int)i;
+    if (best < 0) break;
+    const Cut c = cut[best];
+    const PtBVHNode n = ref[c.ref_idx];
+    cut[best] = Cut{n.left, c.code << 1, c.len + 1};
+    cut.push_back(Cut{n.right, (c.code << 1) | 1u, c.len + 1});
+  }
+  std::sort(cut.begin(), cut.end(), [](const Cut& a, const Cut& b) {
+    return ((uint64_t)a.code << (32 - a.len)) < ((uint64_t)b.code << (32 - b.len));
+  });
+  top.clear();
+  for (const Cut& c : cut) {
+    const PtBVHNode& n = ref[c.ref_idx];
+    ptd::TopEntry e{};
+    std::memcpy(e.bmin, n.bmin, 12);
+    std::memcpy(e.bmax, n.bmax, 12);
+    e.idx = where[c.ref_idx];
+    e.link = n.left < 0 ? -1 - geoms[n.geomIndex].type : thr[where[c.ref_idx]].skip;
+    top.push_back(e);
+  }
+  *top_xor = 0;
+  const int levels = cut[0].len;
+  bool complete = levels >= 1 && levels <= 5 && (int)cut.size() == (1 << levels);
+  for (const Cut& c : cut) complete = complete && c.len == levels;
+  if (!complete) return;
+  // axis and polarity of each level, taken from the node on the all-left path
+  int axis[5] = {0, 0, 0, 0, 0};
+  bool left_lower[5] = {true, true, true, true, true};
+  int at = 0;
+  for (int l = 0; l < levels; ++l) {
+    const PtBVHNode &L = ref[ref[at].left], &R = ref[ref[at].right];
+    float sep = -1.f;
+    for (int a = 0; a < 3; ++a) {
+      const float d = fabsf((L.bmin[a] + L.bmax[a]) - (R.bmin[a] + R.bmax[a]));
+      if (d > sep) sep = d, axis[l] = a;
+    }
+    left_lower[l] = (L.bmin[axis[l]] + L.bmax[axis[l]]) <= (R.bmin[axis[l]] + R.bmax[axis[l]]);
+    at = ref[at].left;
+  }
+  for (int oct = 0; oct < 8; ++oct) {
+    uint32_t m = 0;
+    for (int l = 0; l < levels; ++l) {
+      const bool negative = (oct >> axis[l]) & 1;
+      const bool near_is_right = left_lower[l] == negative;  // positive direction: the lower child is nearer
+      if (near_is_right) m |= 1u << (levels - 1 - l);
+    }
+    *top_xor |= (unsigned long long)m << (8 * oct);
+  }
+}
+
+// normalize(vec3(invTranspose * vec4(n, 0))) in GLM operation order (same expressions as mulMV /
+// normalize in pt_kernels.hip; this file is compiled with -ffp-contract=off, sqrtf and / are IEEE on
+// the host as on the device), for the 7 object-space normals a cube test can produce.
+static void box_normal_table(const float invT12[12], float out[7][4]) {
+  for (int code = 0; code < 7; ++code) {
+    float n[3] = {0.f, 0.f, 0.f};
+    if (code > 0) n[(code - 1) / 2] = ((code - 1) & 1) ? 1.0f : -1.0f;
+    const float* m = invT12;
+    float v[3];
+    for (int r = 0; r < 3; ++r) v[r] = (m[0 + r] * n[0] + m[3 + r] * n[1]) + (m[6 + r] * n[2] + m[9 + r] * 0.0f);
+    const float inv = 1.0f / sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+    out[code][0] = v[0] * inv, out[code][1] = v[1] * inv, out[code][2] = v[2] * inv, out[code][3] = 0.f;
+  }
+}
+
+static void pack_rows(const float m16[16], float out12[12]) {
+  for (int c = 0; c < 4; ++c)
+    for (int r = 0; r < 3; ++r) out12[c * 3 + r] = m16[c * 4 + r];
+}
+
+// Tighter leaf boxes for spheres (large scenes only; result-neutral).  The reference's leaf box is the box of the
+// transformed unit CUBE (pathtrace.cu:36-50), which for a rotated sphere / ellipsoid is up to sqrt(3) wider per axis than
+// the primitive: rays pass the box, reach sphereIntersectionTest (intersections.h:102-144) and miss.  Our structures may
+// skip such a leaf exactly when its primitive test cannot report a hit, so the box our traversal tests is
+//     reference leaf box  INTERSECTED WITH  box of the ellipsoid { x : |A (x - c)| <= rho },  A = the geom's inverse transform,
+// where rho > 0.5 covers everything the reference's float arithmetic can still call a hit.  That test takes
+// radicand = v*v - (|ro|^2 - 0.25) >= 0 with ro = A o + t, rd = normalize(A d), v = ro . rd in float (u = 2^-24):
+//   * the two dot products, the square and the two subtractions:  <= 18 u |ro|^2,         |ro| <= |A|_F * D  =: D_obj
+//   * rounding of ro itself (4 products per component, cancelling against t when the object is far from the origin):
+//     |d ro| <= 14 u (|A|_F * M + |t|) =: 14 u M_obj, which moves the squared distance to the axis by <= 2 * 0.5 * |d ro|
+//   * rounding of rd (direction error <= 5 u cond(A)), which moves it by <= 5 u cond(A) * D_obj
+// with D = the largest distance from a ray origin to the sphere's centre and M = the largest coordinate magnitude of a ray
+// origin; ray origins of the renderer lie in the scene bounds (hit points) or at the camera.  rho^2 = 0.25 + 4 x that sum
+// (safety factor 3.5 on the dominant term), the box is rounded outward and padded by 32 float-eps of M for the slab test's
+// own rounding.  The tightened box lies inside the reference's, so a ray that passes it passes the reference's box and
+// every ancestor (the slab test is monotone under inclusion, DESIGN.md §9, LABNOTES.md §9.1): the leaves we test are a subset of the
+// reference's, and the ones we drop return "no hit" there.  Exact mode stays bit-identical (tests: stress scenes and the
+// random-scene fuzz against the oracle, which keeps the reference's boxes); debug_flags 2048 keeps the reference's boxes.
+// pt_stage_intersect on such a scene inherits the assumption about ray origins.
+// One sphere: ref_lo / ref_hi = the reference's leaf box; returns false when nothing could be tightened.
+static bool sphere_tight_box(const PtGeom& gm, const double origin_lo[3], const double origin_hi[3], const float ref_lo[3], const float ref_hi[3],
+                             float lo[3], float hi[3]) {
+  const double u = 1.0 / 16777216.0;
+  double M = 0.0;
+  for (int a = 0; a < 3; ++a) M = std::max({M, std::fabs(origin_lo[a]), std::fabs(origin_hi[a])});
+  M *= std::sqrt(3.0);
+  const float* inv = gm.inverseTransform;  // column-major 4x4, m[c*4+r]
+  double A[3][3], t[3], B[3][3];
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) A[r][c] = inv[c * 4 + r];
+    t[r] = inv[3 * 4 + r];
+  }
+  const double det = A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0]) +
+                     A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]);
+  if (!(std::fabs(det) > 0.0) || !std::isfinite(det)) return false;
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) {
+      const int r1 = (c + 1) % 3, r2 = (c + 2) % 3, c1 = (r + 1) % 3, c2 = (r + 2) % 3;  // B = A^-1: cofactor of A[c][r] over det
+      B[r][c] = (A[r1][c1] * A[r2][c2] - A[r1][c2] * A[r2][c1]) / det;
+    }
+  double nA = 0.0, nB = 0.0, nt = 0.0, ctr[3], D = 0.0;
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) nA += A[r][c] * A[r][c], nB += B[r][c] * B[r][c];
+    nt += t[r] * t[r];
+    ctr[r] = -(B[r][0] * t[0] + B[r][1] * t[1] + B[r][2] * t[2]);
+  }
+  nA = std::sqrt(nA), nB = std::sqrt(nB), nt = std::sqrt(nt);
+  for (int a = 0; a < 3; ++a) {
+    const double far = std::max(std::fabs(ctr[a] - origin_lo[a]), std::fabs(ctr[a] - origin_hi[a]));
+    D += far * far;
+  }
+  const double D_obj = nA * std::sqrt(D), M_obj = nA * M + nt;
+  const double rho = std::sqrt(0.25 + 4.0 * u * (18.0 * D_obj * D_obj + 14.0 * M_obj + 5.0 * nA * nB * D_obj));
+  if (!std::isfinite(rho)) return false;
+  const double slab = 32.0 * (double)FLT_EPSILON * M;
+  bool changed = false;
+  for (int a = 0; a < 3; ++a) {
+    const double half = rho * std::sqrt(B[a][0] * B[a][0] + B[a][1] * B[a][1] + B[a][2] * B[a][2]) + slab;
+    lo[a] = std::nextafterf((float)(ctr[a] - half), -INFINITY);
+    hi[a] = std::nextafterf((float)(ctr[a] + half), INFINITY);
+    if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) lo[a] = ref_lo[a], hi[a] = ref_hi[a];
+    lo[a] = std::max(lo[a], ref_lo[a]), hi[a] = std::min(hi[a], ref_hi[a]);
+    changed = changed || lo[a] != ref_lo[a] || hi[a] != ref_hi[a];
+  }
+  return changed && lo[0] < hi[0] && lo[1] < hi[1] && lo[2] < hi[2];
+}
+int tighten_sphere_leaves(std::vector<ptd::Node>& nodes, const PtGeom* geoms, const double origin_lo[3], const double origin_hi[3]) {
+  int tightened = 0;
+  for (ptd::Node& n : nodes) {
+    if (n.geom < 0 || geoms[n.geom].type != PT_GEOM_SPHERE) continue;
+    float lo[3], hi[3];
+    if (!sphere_tight_box(geoms[n.geom], origin_lo, origin_hi, n.bmin, n.bmax, lo, hi)) continue;
+    std::memcpy(n.bmin, lo, 12);
+    std::memcpy(n.bmax, hi, 12);
+    ++tightened;
+  }
+  return tightened;
+}
+// The region ray origins come from: hit points (inside the scene bounds; the shading offsets are <= 1e-3) and the camera.
+void origin_region(const float root_min[3], const float root_max[3], const float cam[3], double olo[3], double ohi[3]) {
+  for (int a = 0; a < 3; ++a) {
+    const double ext = (double)root_max[a] - (double)root_min[a];
+    olo[a] = std::min((double)root_min[a] - 0.01 * ext - 0.01, (double)cam[a]);
+    ohi[a] = std::max((double)root_max[a] + 0.01 * ext + 0.01, (double)cam[a]);
+  }
+}
+
+// Uniform grid over the leaf boxes — the traversal structure of our own for large scenes (SceneTables::grid_*).  The
+// reference's median-split BVH (pathtrace.cu:52-111) costs a bounce ray of a 10 000-primitive scene ~60 dependent node
+// fetches below the top list; a grid with about one cell per primitive is walked in ~6 cells.  Results cannot change: a
+// leaf is tested exactly when the ray passes the leaf's own box (pt_device.h), the grid only has to deliver a superset
+// of those leaves, and it does because every leaf is listed in all cells its box grown by `pad` touches — `pad` is orders
+// of magnitude above the rounding of the float cell walk.  Built for large scenes whose lists stay moderate; whether
+// the renderer walks it or the BVH is measured at init (choose_traversal).
+// `coord_mag`: the largest coordinate magnitude a ray of this scene is built from (scene bounds and, where known, the
+// camera position).  The float cell walk's error grows with eps * |coordinate| and eps * t_in, not with the extent, so
+// for a small scene far from the origin (|coordinate| / extent >~ 1e3) 1e-4 * extent alone would sink below the
+// walk's rounding; the pad therefore never goes below 64 ulps of that magnitude.
+bool build_grid(const std::vector<ptd::Node>& nodes, const PtGeom* geoms, int num_geoms, const float root_min[3], const float root_max[3],
+                double coord_mag, double density, bool forced, Grid& grid) {
+  std::vector<int> leaves;
+  for (size_t i = 0; i < nodes.size(); ++i)
+    if (nodes[i].geom >= 0) leaves.push_back((int)i);
+  if (leaves.empty()) return false;
+  double ext[3], maxext = 0.0;
+  for (int a = 0; a < 3; ++a) maxext = std::max(maxext, (double)root_max[a] - (double)root_min[a]);
+  if (!(maxext > 0.0) || !std::isfinite(maxext)) return false;
+  for (int a = 0; a < 3; ++a) coord_mag = std::max({coord_mag, std::fabs((double)root_min[a]), std::fabs((double)root_max[a])});
+  const double pad = std::max(1e-4 * maxext, 64.0 * (double)FLT_EPSILON * coord_mag);
+  if (!(pad < 0.05 * maxext)) return false;  // the scene is a speck at its distance from the origin: cells would be all padding
+  double lo[3], vol = 1.0;
+  for (int a = 0; a < 3; ++a) {
+    lo[a] = (double)root_min[a] - 2.0 * pad;
+    ext[a] = ((double)root_max[a] + 2.0 * pad) - lo[a];
+    vol *= ext[a];
+  }
+  // the cells [c0, c1] per axis that a leaf's box grown by `pad` touches, at resolution `res`
+  auto cell_range = [&](const ptd::Node& n, const int res[3], int c0[3], int c1[3]) {
+    for (int a = 0; a < 3; ++a) {
+      c0[a] = std::min(std::max((int)std::floor(((double)n.bmin[a] - pad - lo[a]) / ext[a] * res[a]), 0), res[a] - 1);
+      c1[a] = std::min(std::max((int)std::floor(((double)n.bmax[a] + pad - lo[a]) / ext[a] * res[a]), 0), res[a] - 1);
+    }
+  };
+  auto references = [&](const int res[3]) {
+    int64_t refs = 0;
+    for (int li : leaves) {
+      int c0[3], c1[3];
+      cell_range(nodes[li], res, c0, c1);
+      refs += (int64_t)(c1[0] - c0[0] + 1) * (c1[1] - c0[1] + 1) * (c1[2] - c0[2] + 1);
+    }
+    return refs;
+  };
+  // Resolution: about one cell per primitive (density <= 0: a search around that).  What a ray pays is one step per cell
+  // it crosses plus one box test per record it comes across, i.e. per unit length ~ r (cells) and ~ refs * r / ncell
+  // (records), r = mean resolution; measured on the 10 170-primitive scene a record costs about half a step (kernel
+  // time follows refs * r / ncell + 2 r over resolutions 15..31).  The search matters for primitives on a lattice —
+  // the resolution that matches the lattice pitch halves the references — and is harmless otherwise.
+  auto resolution = [&](double per_len, int res[3]) {
+    for (int a = 0; a < 3; ++a) res[a] = (int)std::min(512.0, std::max(1.0, std::floor(ext[a] * per_len + 0.5)));
+  };
+  GridShape& s = grid.shape;
+  const double base = std::cbrt((double)leaves.size() / vol);
+  if (density > 0.0) {
+    resolution(std::cbrt(density) * base, s.res);
+  } else {
+    double best_cost = INFINITY;
+    int last[3] = {0, 0, 0};
+    for (int i = 0; i <= 40; ++i) {
+      int res[3];
+      resolution(base * (0.6 + 0.025 * i), res);
+      if (res[0] == last[0] && res[1] == last[1] && res[2] == last[2]) continue;
+      std::memcpy(last, res, sizeof(last));
+      const double r = (res[0] + res[1] + res[2]) / 3.0, cells = (double)res[0] * res[1] * res[2];
+      const double cost = (double)references(res) * r / cells + 2.0 * r;
+      if (cost < best_cost) best_cost = cost, std::memcpy(s.res, res, sizeof(res));
+    }
+  }
+  int64_t ncell = 1;
+  for (int a = 0; a < 3; ++a) {
+    s.gmin[a] = (float)lo[a];
+    s.cs[a] = (float)(ext[a] / s.res[a]);
+    s.inv_cs[a] = (float)(s.res[a] / ext[a]);
+    ncell *= s.res[a];
+  }
+  s.pad = (float)pad;
+  if (ncell > (int64_t)64 * 1024 * 1024) return false;
+  const int64_t refs = references(s.res);
+  if (refs > (int64_t)1 << 22) return false;  // ring entries hold 22-bit record indices
+  if (num_geoms > (1 << 24)) return false;    // records hold 24-bit geom indices
+  // a candidate only while the lists stay moderate (whether it beats the BVH scan is measured, choose_traversal())
+  if (!forced && refs > 64 * (int64_t)leaves.size()) return false;
+  auto cell = [&](int x, int y, int z) { return (size_t)x + (size_t)s.res[0] * ((size_t)y + (size_t)s.res[1] * z); };
+  std::vector<uint32_t> count((size_t)ncell + 1, 0);
+  for (int li : leaves) {
+    int c0[3], c1[3];
+    cell_range(nodes[li], s.res, c0, c1);
+    for (int z = c0[2]; z <= c1[2]; ++z)
+      for (int y = c0[1]; y <= c1[1]; ++y)
+        for (int x = c0[0]; x <= c1[0]; ++x) ++count[cell(x, y, z)];
+  }
+  uint32_t longest = 0;
+  grid.start.assign((size_t)ncell + 1, 0);
+  for (int64_t c = 0; c < ncell; ++c) {
+    grid.start[c + 1] = grid.start[c] + count[c];
+    longest = std::max(longest, count[c]);
+  }
+  if (!forced && longest > 4096) return false;
+  grid.items.assign((size_t)refs, ptd::Node{});
+  std::vector<uint32_t> fill(grid.start.begin(), grid.start.end() - 1);
+  for (int li : leaves) {  // threaded (= reference visiting) order inside every cell
+    int c0[3], c1[3];
+    cell_range(nodes[li], s.res, c0, c1);
+    for (int z = c0[2]; z <= c1[2]; ++z)
+      for (int y = c0[1]; y <= c1[1]; ++y)
+        for (int x = c0[0]; x <= c1[0]; ++x) {
+          ptd::Node it = nodes[li];
+          it.skip = li;
+          it.geom = (x > c0[0] ? 1 : 0) | (x < c1[0] ? 2 : 0) | (y > c0[1] ? 4 : 0) | (y < c1[1] ? 8 : 0) | (z > c0[2] ? 16 : 0) |
+                    (z < c1[2] ? 32 : 0) | ((geoms[nodes[li].geom].type & 3) << 6) | (nodes[li].geom << 8);
+          grid.items[fill[cell(x, y, z)]++] = it;
+        }
+  }
+  return true;
+}
+
+// A box as centre and half extent for the fast build's slab test (pt_arith.inc slab_t): the centre rounded to float, the half
+// extent rounded UP from the distance to the farther face (so the converted box contains the original in real arithmetic), in
+// place in (bmin, bmax).  `inner` (inner nodes, subtree entries of the top list — pure acceleration): a little more, so that in the
+// test's float arithmetic a ray that passes a leaf's box still passes every box above it (1e-5 of the box and of the
+// coordinates: two orders of magnitude above the rounding of the three FMAs).
+void center_half_box(float bmin[3], float bmax[3], bool inner) {
+  for (int a = 0; a < 3; ++a) {
+    const double lo = bmin[a], hi = bmax[a];
+    const float c = (float)(0.5 * (lo + hi));
+    double h = std::max(hi - (double)c, (double)c - lo);
+    if (inner) h = h * (1.0 + 1e-5) + 1e-5 * std::max(std::fabs(lo), std::fabs(hi)) + 1e-30;
+    float hf = (float)h;
+    if ((double)hf < h) hf = std::nextafter(hf, INFINITY);
+    bmin[a] = c, bmax[a] = hf;
+  }
+}
+
+HostTables build_scene_tables(const PtSceneDesc& desc, int debug_flags, bool center_half) {
+  HostTables t;
+  ThreadedBvh bvh = threaded_bvh(desc.geoms, desc.num_geoms);
+  build_top(bvh.ref, bvh.nodes, bvh.where, desc.geoms, t.top, &t.top_xor);
+  t.nodes = std::move(bvh.nodes);
+  std::memcpy(t.root_min, bvh.ref[0].bmin, 12);
+  std::memcpy(t.root_max, bvh.ref[0].bmax, 12);
+  if ((int)t.nodes.size() >= kTightNodes && !(debug_flags & 2048)) {
+    double olo[3], ohi[3];
+    origin_region(t.root_min, t.root_max, desc.camera.position, olo, ohi);
+    t.tight_leaves = tighten_sphere_leaves(t.nodes, desc.geoms, olo, ohi);
+    for (ptd::TopEntry& e : t.top)
+      if (e.link < 0) std::memcpy(e.bmin, t.nodes[e.idx].bmin, 12), std::memcpy(e.bmax, t.nodes[e.idx].bmax, 12);
+  }
+  {
+    // SceneTables::cull_margin: >= 10x the worst undershoot of a reported hit distance (1e-4 object units mapped
+    // to world space + rounding of the transforms at the scene's coordinate magnitudes)
+    float max_xf = 1.0f, extent = 1.0f;
+    for (int i = 0; i < desc.num_geoms; ++i) {
+      const PtGeom& gm = desc.geoms[i];
+      if (gm.type == PT_GEOM_TRIANGLE) continue;  // world-space test: the pull-back is 1e-4 world units (max_xf >= 1 covers it)
+      float f = 0.f;
+      for (int c = 0; c < 3; ++c)
+        for (int r = 0; r < 3; ++r) f += gm.transform[c * 4 + r] * gm.transform[c * 4 + r];
+      max_xf = std::max(max_xf, sqrtf(f));
+    }
+    for (int a = 0; a < 3; ++a)
+      extent = std::max({extent, fabsf(t.root_min[a]), fabsf(t.root_max[a]), fabsf(desc.camera.position[a])});
+    t.cull_margin = 1e-3f * max_xf + 1e-4f * extent;
+  }
+  t.geoms.assign(desc.num_geoms, ptd::Geom{});
+  for (int i = 0; i < desc.num_geoms; ++i) {
+    const PtGeom& gm = desc.geoms[i];
+    ptd::Geom& dg = t.geoms[i];
+    dg.type = gm.type;
+    dg.material = gm.materialid;
+    if (gm.type == PT_GEOM_TRIANGLE) {  // mesh extension: the three world-space vertices where `inv` would be
+      std::memcpy(dg.inv, gm.transform, 9 * sizeof(float));
+      t.has_triangles = true;
+      continue;
+    }
+    pack_rows(gm.inverseTransform, dg.inv);
+    pack_rows(gm.transform, dg.xf);
+    pack_rows(gm.invTranspose, dg.invT);
+    box_normal_table(dg.invT, dg.box_normal);
+  }
+  t.mats.assign(desc.num_materials, ptd::Mat{});
+  for (int i = 0; i < desc.num_materials; ++i) {
+    const PtMaterial& m = desc.materials[i];
+    std::memcpy(t.mats[i].color, m.color, 12);
+    std::memcpy(t.mats[i].spec, m.specular_color, 12);
+    t.mats[i].reflective = m.hasReflective, t.mats[i].refractive = m.hasRefractive, t.mats[i].emittance = m.emittance;
+  }
+  if (center_half) {  // the fast build: converted copies for the bounce kernels
+    t.nodes_b = t.nodes;
+    for (ptd::Node& n : t.nodes_b) center_half_box(n.bmin, n.bmax, n.geom < 0);
+    t.top_b = t.top;
+    for (ptd::TopEntry& e : t.top_b) center_half_box(e.bmin, e.bmax, e.link >= 0);
+  }
+  if (((int)t.nodes.size() >= kGridNodes || (debug_flags & 256)) && !(debug_flags & 512)) {
+    double cam_mag = 0.0;
+    for (int a = 0; a < 3; ++a) cam_mag = std::max(cam_mag, std::fabs((double)desc.camera.position[a]));
+    // Candidates: the resolution the host's cost model finds (about one cell per primitive; build_grid) and two finer ones.
+    // The model prices a uniform spread of primitives and rays; where the primitives cluster, a finer grid pays (clustered 1500
+    // objects: 2319 Msamples/s at the model's resolution, 2931 at 8 cells per primitive; a lattice wants exactly its pitch),
+    // so choose_traversal() measures.  A forced grid (debug_flags 256) is the only candidate.
+    const bool forced = (debug_flags & 256) != 0;
+    std::vector<double> densities{0.0};
+    if (!forced) densities.insert(densities.end(), {4.0, 8.0});
+    for (double density : densities) {
+      Grid grid;
+      if (!build_grid(t.nodes, desc.geoms, desc.num_geoms, t.root_min, t.root_max, cam_mag, density, forced, grid)) continue;
+      bool repeat = false;
+      for (const Grid& o : t.grids) repeat = repeat || std::equal(o.shape.res, o.shape.res + 3, grid.shape.res);
+      if (repeat) continue;
+      // the cell table with empty cells before and after it: a walk may run up to one cell per axis past the grid's far side
+      // before its distance test ends it (pt_grid.inc CellWalk)
+      grid.guard = (size_t)grid.shape.res[0] * grid.shape.res[1] + grid.shape.res[0] + 2;
+      const uint32_t total = grid.start.back();
+      grid.start.insert(grid.start.begin(), grid.guard, 0u);
+      grid.start.resize(grid.start.size() + grid.guard, total);
+      if (center_half) {  // the grid's records are leaf boxes
+        grid.items_b = grid.items;
+        for (ptd::Node& n : grid.items_b) center_half_box(n.bmin, n.bmax, false);
+      }
+      t.grids.push_back(std::move(grid));
+    }
+  }
+  return t;
+}
+
+}  // namespace pt

@@ -189,9 +189,12 @@ int pt_build_bvh(const PtGeom* geoms, int num_geoms, PtBVHNode* out, int cap);
  * test, and every leaf is listed in all cells its box, grown by `pad`, touches.  A scene is a CANDIDATE when it has
  * >= 600 BVH nodes and its lists stay moderate (at most 64 cell references per primitive; `forced` skips both
  * conditions, as PtOptions.debug_flags 256 does); for a candidate pt_init / pt_ctx_create time a few iterations of the
- * tile with the BVH scan, with this grid and with two finer ones (4 and 8 cells per primitive) and keep the fastest
- * (PtStats.grid_cells > 0: a grid, with that many cells).  The device walks the same structure over the boxes of
- * pt_traversal_boxes, its cell table padded with empty guard cells.  This function is host-only (no GPU needed).  Returns 1 and fills `info` for a candidate, 0 otherwise, -1 on error; cell c's records
+ * tile with the BVH scan, with a grid of the cost model's resolution and with two finer ones (4 and 8 cells per
+ * primitive) and keep the fastest (PtStats.grid_cells > 0: a grid, with that many cells).  This function builds the grid
+ * of the cost model's resolution over the reference's leaf boxes, without the camera (csrc/pt_tables.cpp build_grid).  The
+ * renderer's grids cover its traversal boxes (pt_traversal_boxes: tightened sphere leaves), their pad also covers the
+ * camera's coordinates and their cell table carries empty guard cells: built the same way, but not byte for byte this grid.
+ * Host-only (no GPU needed).  Returns 1 and fills `info` for a candidate, 0 otherwise, -1 on error; cell c's records
  * are records[cell_start[c] .. cell_start[c + 1]), c = x + res[0] * (y + res[1] * z); either array may be NULL (sizes
  * are in `info`). */
 typedef struct PtGridInfo {
@@ -210,7 +213,7 @@ int pt_build_grid(const PtGeom* geoms, int num_geoms, int forced, PtGridInfo* in
 /* Host-only: the box our traversal structures test for each geom's leaf — the reference's leaf box (pathtrace.cu:36-50),
  * except for spheres of large scenes, where it is intersected with the box of the ellipsoid itself (grown by a bound on
  * what sphereIntersectionTest's float arithmetic, intersections.h:102-144, can still report as a hit for ray origins inside
- * the scene bounds or at `camera_position`; csrc/pt_api.cpp sphere_tight_box).  A ray that passes the tightened box passes the
+ * the scene bounds or at `camera_position`; csrc/pt_tables.cpp sphere_tight_box).  A ray that passes the tightened box passes the
  * reference's; a ray that passes only the reference's misses the sphere: same hits, fewer candidates.  boxes[g] = {min xyz, max xyz}.
  * Returns the number of tightened leaves (pt_init applies it from 64 BVH nodes on; PtOptions.debug_flags 2048 turns it off). */
 int pt_traversal_boxes(const PtGeom* geoms, int num_geoms, const float camera_position[3], float* boxes);

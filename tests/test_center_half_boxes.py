@@ -1,5 +1,5 @@
 """The centre / half-extent form of the traversal boxes the fast build's bounce kernels test (pt_center_half_box,
-csrc/pt_api.cpp center_half_box; csrc/pt_arith.inc slab_t): the converted box must CONTAIN the min / max box it came from
+csrc/pt_tables.cpp center_half_box; csrc/pt_arith.inc slab_t): the converted box must CONTAIN the min / max box it came from
 (a ray that passes the reference's box must not be lost to rounding of the conversion), inner boxes must be larger still,
 and both must stay tight.  Host-only."""
 import ctypes as C

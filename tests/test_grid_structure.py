@@ -1,5 +1,5 @@
 """The traversal structure of our own for large scenes: a uniform grid over the leaf boxes
-(pt_build_grid, include/pt_amd.h).  CPU-only checks of the two facts the GPU walk's bit-exactness rests on:
+(pt_build_grid, include/pt_amd.h; csrc/pt_tables.cpp build_grid, which also builds the renderer's grids).  CPU-only checks of the two facts the GPU walk's bit-exactness rests on:
   * the reference's float AABB test (pathtrace.cu:113-128) is monotone under box inclusion — a ray that passes a leaf's
     box passes the boxes of all its ancestors — so "the leaves the reference's walk tests" == "the leaves whose own box the
     ray passes", whatever structure finds them;
@@ -105,7 +105,7 @@ def test_reference_box_test_is_monotone_under_inclusion(test_scenes, name):
 @pytest.mark.parametrize("name", ["lattice", "random", "clustered", "mesh"])
 def test_grid_lists_every_leaf_in_every_cell_its_box_touches(test_scenes, name):
     sc, bmin, bmax, parent, geom = scene_nodes(test_scenes[name])
-    if len(geom) < 600:  # pt_api.cpp kGridNodes
+    if len(geom) < 600:  # pt_tables.h kGridNodes
         assert sc.grid() is None, "small scenes keep the BVH scan unless forced"
     info, start, recs = sc.grid(forced=True)
     res = np.array(info.res)

@@ -6,6 +6,7 @@ import json
 import os
 import re
 import struct
+import subprocess
 import zlib
 
 import numpy as np
@@ -181,6 +182,14 @@ def test_kernel_build_has_no_compile_time_switches():
     assert tested <= {"PT_ARITH", "PT_WALK_STATS", "__HIPCC__"}, sorted(tested)
     make = open(os.path.join(csrc, "Makefile")).read()
     assert set(re.findall(r"-D\s*(\w+)", make)) == {"PT_ARITH"}
+
+
+def test_scene_table_builder_needs_no_hip():
+    """csrc/pt_tables.cpp, everything the renderer uploads for a scene, is plain C++: the system compiler, without any
+    ROCm include path, accepts it, so no HIP header can creep into the builder."""
+    src = os.path.join(ROOT, "cosc_4397_pathtracing_raytracing_project_amd", "csrc", "pt_tables.cpp")
+    r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", src], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
 
 
 REF_TOKENS = os.path.join(HERE, "golden", "ref_scene_tokens.json")  # SHA-256 of the reference's scenes/*.txt token streams

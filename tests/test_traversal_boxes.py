@@ -1,4 +1,4 @@
-"""The tightened sphere leaf boxes of large scenes (pt_traversal_boxes, csrc/pt_api.cpp sphere_tight_box) must never
+"""The tightened sphere leaf boxes of large scenes (pt_traversal_boxes, csrc/pt_tables.cpp sphere_tight_box) must never
 reject a ray the reference's sphere test (intersections.h:102-144, restated by the oracle and pinned by the reference-compiled
 goldens) reports as a hit: the traversal may skip a leaf only when the primitive test could not hit anyway.  CPU only: the
 oracle says which rays hit which sphere, the box test is intersectAABB restated in numpy (tests/golden_io.py).  The GPU side

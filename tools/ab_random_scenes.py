@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Grid walk against BVH scan (PtOptions.debug_flags 512) on random scenes — the check that the host's choice of the grid
-(pt_api.cpp build_grid) does not hurt scenes that are not lattices.  usage: tools/ab_random_scenes.py [spp]"""
+(pt_tables.cpp build_grid) does not hurt scenes that are not lattices.  usage: tools/ab_random_scenes.py [spp]"""
 import os, sys, tempfile, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -26,6 +26,6 @@ $K -ffp-contract=fast-honor-pragmas -DPT_ARITH=1 -c $KSRC/pt_kernels.hip -o $OUT
 $K -ffp-contract=fast-honor-pragmas -DPT_ARITH=2 -c $KSRC/pt_kernels.hip -o $OUT/obj_$NAME/k2.o &
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $OUT/$NAME.so $OUT/obj_$NAME/k0.o $OUT/obj_$NAME/k1.o $OUT/obj_$NAME/k2.o $SRC/build/pt_api.o \
-  $SRC/build/pt_group.o $SRC/build/pt_scene.o $SRC/build/pt_image.o $SRC/build/pathtrace_shim.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+  $SRC/build/pt_group.o $SRC/build/pt_scene.o $SRC/build/pt_tables.o $SRC/build/pt_image.o $SRC/build/pathtrace_shim.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 rm -rf $OUT/obj_$NAME
 echo "$OUT/$NAME.so"
