@@ -20,6 +20,9 @@ LIB_PATH = os.environ.get("PT_AMD_LIB") or os.path.join(_PKG, "libpt_amd.so")
 PT_MAX_DEPTH = 64
 ARITH = {"exact": 0, "fma": 1, "fast": 2}  # PT_ARITH_* (include/pt_amd.h)
 ARITH_NAMES = {v: k for k, v in ARITH.items()}
+CONVERGENCE_WAVES = 16        # PT_CONVERGENCE_WAVES
+CONVERGENCE_CAPACITY = 65536  # PT_CONVERGENCE_CAPACITY: iterations the convergence metric keeps a value for
+FLT_MAX = float(np.finfo(np.float32).max)
 
 
 class PtGeom(C.Structure):
@@ -62,7 +65,7 @@ class PtOptions(C.Structure):
     _fields_ = [("device", C.c_int32), ("pixel_begin", C.c_int32), ("pixel_count", C.c_int32),
                 ("iters_per_batch", C.c_int32), ("num_queues", C.c_int32), ("blocks_per_cu", C.c_int32),
                 ("time_kernels", C.c_int32), ("legacy_traversal", C.c_int32), ("debug_flags", C.c_int32), ("unfused_primary", C.c_int32), ("unfused_bounces", C.c_int32), ("stripe_pixels", C.c_int32), ("stripe_stride", C.c_int32),
-                ("arith", C.c_int32), ("aa_jitter", C.c_int32), ("reserved", C.c_int32 * 1),
+                ("arith", C.c_int32), ("aa_jitter", C.c_int32), ("convergence", C.c_int32),
                 ("lds_table_kb", C.c_int32), ("primary_pieces", C.c_int32), ("paths_pieces", C.c_int32), ("paths_min_piece", C.c_int32)]
 
 
@@ -152,6 +155,19 @@ def lib() -> C.CDLL:
     L.pt_save_png.argtypes = [C.c_char_p, _fp, C.c_int, C.c_int, C.c_float]
     L.pt_save_hdr.argtypes = [C.c_char_p, _fp, C.c_int, C.c_int, C.c_float]
     L.pt_save_pfm.argtypes = [C.c_char_p, _fp, C.c_int, C.c_int, C.c_float]
+    L.pt_load_pfm.argtypes = [C.c_char_p, _fp, C.c_int, _ip, _ip, C.c_float]
+    _dp = C.POINTER(C.c_double)
+    L.pt_psnr_from_sse.argtypes = [C.c_double, C.c_int64]
+    L.pt_psnr_from_sse.restype = C.c_float
+    L.pt_set_reference.argtypes = [_fp]
+    L.pt_get_convergence.argtypes = [C.c_int, C.c_int, _dp]
+    L.pt_iterations_to_clean.argtypes = [C.c_float, _ip]
+    L.pt_ctx_set_reference.argtypes = [C.c_void_p, _fp]
+    L.pt_ctx_get_convergence.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
+    L.pt_ctx_iterations_to_clean.argtypes = [C.c_void_p, C.c_float, _ip]
+    L.pt_group_set_reference.argtypes = [C.c_void_p, _fp]
+    L.pt_group_get_convergence.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
+    L.pt_group_iterations_to_clean.argtypes = [C.c_void_p, C.c_float, _ip]
     _lib = L
     return L
 
@@ -264,7 +280,8 @@ def make_options(device: int = 0, pixel_begin: int = 0, pixel_count: int = 0, it
                  num_queues: int = 0, blocks_per_cu: int = 0, time_kernels: bool = False, legacy_traversal: bool = False,
                  debug_flags: int = 0, unfused_primary: bool = False, unfused_bounces: bool = False,
                  stripe_pixels: int = 0, stripe_stride: int = 0, arith="exact", aa_jitter: bool = False,
-                 lds_table_kb: int = 0, primary_pieces: int = 0, paths_pieces: int = 0, paths_min_piece: int = 0) -> PtOptions:
+                 lds_table_kb: int = 0, primary_pieces: int = 0, paths_pieces: int = 0, paths_min_piece: int = 0,
+                 convergence: int = 0) -> PtOptions:
     opt = PtOptions()
     opt.device = device
     opt.pixel_begin = pixel_begin
@@ -281,6 +298,7 @@ def make_options(device: int = 0, pixel_begin: int = 0, pixel_count: int = 0, it
     opt.stripe_stride = int(stripe_stride)
     opt.arith = ARITH[arith] if isinstance(arith, str) else int(arith)
     opt.aa_jitter = 1 if aa_jitter else 0
+    opt.convergence = int(convergence)  # 0 off, N > 0 reference frame captured at iteration N, -1 supplied (set_reference)
     opt.lds_table_kb = int(lds_table_kb)
     opt.primary_pieces = int(primary_pieces)
     opt.paths_pieces = int(paths_pieces)
@@ -339,6 +357,26 @@ class Renderer:
     def clear(self) -> None:
         """Restart the accumulation (SUM image and statistics zeroed) on the same, already touched buffers."""
         _check(lib().pt_clear())
+
+    # ---- convergence metric (make_options(convergence=...)) ----
+    def set_reference(self, rgb_avg: np.ndarray) -> None:
+        """The reference frame of convergence=-1: averaged radiance of the tile, float32 [n, 3]."""
+        a = np.ascontiguousarray(rgb_avg, np.float32).reshape(-1)
+        if a.size != 3 * self.n:
+            raise PtError(f"set_reference: {a.size} floats for a tile of {self.n} pixels")
+        _check(lib().pt_set_reference(_f(a)))
+
+    def convergence(self, first: int, count: int) -> np.ndarray:
+        """Sum of squared errors of iterations first .. first + count - 1 against the reference frame, float64 [count];
+        -1 where there is none.  psnr_from_sse(sse, pixels) gives the reference's PSNR."""
+        out = np.empty(max(int(count), 0), np.float64)
+        _check(lib().pt_get_convergence(int(first), out.size, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def iterations_to_clean(self, threshold_db: float = 35.0) -> int:
+        it = C.c_int32(-1)
+        _check(lib().pt_iterations_to_clean(C.c_float(threshold_db), C.byref(it)))
+        return int(it.value)
 
     def free(self) -> None:
         if self._live:
@@ -434,6 +472,25 @@ class Group:
         _check(lib().pt_ctx_get_stats(lib().pt_group_context(self._h, i), C.byref(st)))
         return st
 
+    def set_reference(self, rgb_avg: np.ndarray) -> None:
+        """The reference frame of convergence=-1 for the whole frame: averaged radiance, float32 [W*H, 3], raw orientation."""
+        w, h = self.scene.resolution
+        a = np.ascontiguousarray(rgb_avg, np.float32).reshape(-1)
+        if a.size != 3 * w * h:
+            raise PtError(f"set_reference: {a.size} floats for a frame of {w}x{h}")
+        _check(lib().pt_group_set_reference(self._h, _f(a)))
+
+    def convergence(self, first: int, count: int) -> np.ndarray:
+        """SSE of the whole frame per iteration (the contexts' sums added in context order); -1 where there is none."""
+        out = np.empty(max(int(count), 0), np.float64)
+        _check(lib().pt_group_get_convergence(self._h, int(first), out.size, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def iterations_to_clean(self, threshold_db: float = 35.0) -> int:
+        it = C.c_int32(-1)
+        _check(lib().pt_group_iterations_to_clean(self._h, C.c_float(threshold_db), C.byref(it)))
+        return int(it.value)
+
     def free(self) -> None:
         if self._h:
             lib().pt_group_destroy(self._h)
@@ -470,3 +527,19 @@ def save_pfm(path: str, rgb_sum: np.ndarray, w: int, h: int, samples: float) -> 
     a = np.ascontiguousarray(rgb_sum, np.float32)
     if lib().pt_save_pfm(os.fsencode(path), _f(a), w, h, C.c_float(samples)) != 0:
         raise PtError(f"cannot write {path}")
+
+
+def load_pfm(path: str, samples: float = 1.0) -> np.ndarray:
+    """The inverse of save_pfm: float32 [h, w, 3], raw orientation, file contents times `samples`."""
+    w, h = C.c_int32(0), C.c_int32(0)
+    if lib().pt_load_pfm(os.fsencode(path), None, 0, C.byref(w), C.byref(h), C.c_float(samples)) != 0:
+        raise PtError(f"cannot read {path}")
+    out = np.empty((h.value, w.value, 3), np.float32)
+    if lib().pt_load_pfm(os.fsencode(path), _f(out), w.value * h.value, C.byref(w), C.byref(h), C.c_float(samples)) != 0:
+        raise PtError(f"cannot read {path}")
+    return out
+
+
+def psnr_from_sse(sse: float, pixels: int) -> float:
+    """computePSNR's last lines (pt_psnr_from_sse): FLT_MAX where the reference prints "Inf"."""
+    return float(lib().pt_psnr_from_sse(C.c_double(sse), C.c_int64(pixels)))

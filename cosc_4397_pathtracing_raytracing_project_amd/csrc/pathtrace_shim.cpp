@@ -1,5 +1,6 @@
 // pathtrace_shim.cpp — the four reference entry points (src/pathtrace.h:6-9)
 // implemented over the C ABI.  See include/pathtrace_amd.hpp for the contract.
+#include <cfloat>
 #include <cstdio>
 #include <cstdlib>
 
@@ -15,6 +16,7 @@ int q_first = 0, q_count = 0;  // queued, not yet submitted iterations [q_first,
 int last_iter = 0;
 int arith_mode = PT_ARITH_EXACT;
 int aa_mode = 0;
+int conv_mode = 0;
 
 void check(int rc, const char* what) {  // pathtrace.cu:141-150
   if (rc == 0) return;
@@ -30,6 +32,7 @@ void flush() {
 void InitDataContainer(GuiDataContainer* imGuiData) { guiData = imGuiData; }
 void pathtraceSetArith(int pt_arith) { arith_mode = pt_arith; }
 void pathtraceSetAntialias(int on) { aa_mode = on ? 1 : 0; }
+void pathtraceSetConvergence(int n) { conv_mode = n; }
 
 void pathtraceInit(pt::Scene* scene) {
   hst_scene = scene;
@@ -37,6 +40,7 @@ void pathtraceInit(pt::Scene* scene) {
   PtOptions opt{};
   opt.arith = arith_mode;
   opt.aa_jitter = aa_mode;
+  opt.convergence = conv_mode;
   check(pt_init(&d, &opt), "pathtraceInit");
   q_count = 0;
   last_iter = 0;
@@ -75,4 +79,13 @@ void pathtrace(pt_uchar4* pbo, int /*frame*/, int iter) {
   }
   if (final_iter || q_count >= 64) flush();
   if (final_iter) pathtraceSyncImage();
+}
+
+float pathtracePSNR(int iter) {  // what pathtrace.cu:627-638 prints after iteration `iter`
+  if (!hst_scene) return FLT_MAX;
+  flush();
+  double sse = -1.0;
+  check(pt_get_convergence(iter, 1, &sse), "pathtracePSNR");
+  const PtCamera& c = hst_scene->state.camera;
+  return sse < 0.0 ? FLT_MAX : pt_psnr_from_sse(sse, (int64_t)c.resolution[0] * c.resolution[1]);
 }

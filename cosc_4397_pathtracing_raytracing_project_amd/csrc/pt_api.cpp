@@ -29,6 +29,7 @@ namespace {
 std::string g_err;
 constexpr int kDebugFlags = 16 | 32 | 64 | 256 | 512 | 2048;  // the PtOptions.debug_flags bits pt_init accepts
 static_assert(sizeof(PtOptions) == 80, "capi.PtOptions mirrors this layout");
+static_assert(PT_CONVERGENCE_WAVES == ptk::kConvWaves, "pt_amd.h documents the size of the convergence metric's partial sums");
 }  // namespace
 int pt_fail(const char* fmt, ...) {  // pt_internal.h: sets pt_last_error(), returns -1
   char buf[1024];
@@ -106,6 +107,14 @@ struct PtContext {
   ptd::HitBuf hits{};
   ptd::RetireBuf ret{};  // retirement records + fill levels (pt_device.h)
   float* d_image = nullptr;
+  // Convergence metric (PtOptions.convergence, pt_kernels.h ConvInfo): all of it absent when the option is 0
+  int conv = 0;                // the option: N > 0 capture the frame at iteration N, -1 supplied
+  bool conv_live = false;      // off while setup() renders its timing batches: they leave no trace in the curve or the frame
+  bool conv_have_ref = false;  // d_ref holds the frame (supplied, or the batch that captures it has been submitted)
+  int conv_last = 0;           // highest iteration submitted with the metric on
+  float* d_ref = nullptr;      // [N][3]
+  double* d_partial = nullptr;  // [K][Q][kConvWaves]
+  double* d_sse = nullptr;      // [PT_CONVERGENCE_CAPACITY], iteration i at i - 1; all bits set (a NaN) = no value
   uint8_t* d_rgb8 = nullptr;  // lazily allocated output of pt_ctx_save_u8
   int32_t* d_cnt = nullptr;
   unsigned long long* d_stats = nullptr;
@@ -274,7 +283,14 @@ int run_batch(Ctx& g, int iter_first, int kb) {
     src ^= 1;
   }
   k.count_stats(g.stream, g.qs, g.d_cnt, g.depth, g.d_stats);
-  k.collect(g.stream, b, g.qs, g.ret, g.d_image);
+  ptk::ConvInfo cv{g.d_ref, g.d_partial, -1, kb};
+  if (g.conv_live) {
+    if (g.conv_have_ref) cv.first_k = 0;
+    else if (g.conv >= iter_first && g.conv < iter_first + kb) cv.capture_k = g.conv - iter_first, cv.first_k = cv.capture_k + 1, g.conv_have_ref = true;
+    g.conv_last = std::max(g.conv_last, iter_first + kb - 1);
+  }
+  if (cv.capture_k >= 0 || cv.first_k < kb) k.collect_conv(g.stream, b, g.qs, g.ret, g.d_image, cv, g.d_sse);
+  else k.collect(g.stream, b, g.qs, g.ret, g.d_image);
   HIP_OK(hipGetLastError());
   g.samples += (int64_t)kb * g.N;
   if (g.pending_isect.size() > 16384) {
@@ -407,6 +423,8 @@ int open_device(Ctx& g, const PtOptions& opt) {
   g.arith = opt.arith;
   g.k = ptk::api_for(opt.arith);
   if (!g.k) return fail("pt_init: arith %d is not one of PT_ARITH_EXACT / PT_ARITH_FMA / PT_ARITH_FAST", opt.arith);
+  if (opt.convergence < -1) return fail("pt_init: convergence %d is not 0 (off), N > 0 (frame captured at iteration N) or -1 (frame supplied)", opt.convergence);
+  if (opt.convergence > PT_CONVERGENCE_CAPACITY) return fail("pt_init: convergence %d exceeds PT_CONVERGENCE_CAPACITY (%d iterations)", opt.convergence, PT_CONVERGENCE_CAPACITY);
   if (opt.debug_flags & ~kDebugFlags) return fail("pt_init: debug_flags 0x%x: bits 0x%x are not defined", opt.debug_flags, opt.debug_flags & ~kDebugFlags);
   int ndev = 0;
   HIP_OK(hipGetDeviceCount(&ndev));
@@ -434,6 +452,7 @@ void take_scene_and_options(Ctx& g, const PtSceneDesc* sc, const PtOptions& opt)
   g.legacy = opt.legacy_traversal != 0;
   g.aa_jitter = opt.aa_jitter != 0;
   g.debug_flags = opt.debug_flags;
+  g.conv = opt.convergence;
   auto pieces = [](int v, int automatic) { return v ? std::clamp(v, 1, 0x7fff) : automatic; };
   g.lds_table_forced = opt.lds_table_kb ? std::clamp(opt.lds_table_kb, 0, ptk::kLdsTableBytes / 1024) * 1024 : -1;
   g.primary_pieces = pieces(opt.primary_pieces, 0);
@@ -553,6 +572,13 @@ int alloc_batch_buffers(Ctx& g) {
     if (dalloc(g, &g.qs.deal, 4 * (size_t)Q + 2)) return -1;
     HIP_OK(hipMemset(g.qs.deal, 0, (4 * (size_t)Q + 2) * sizeof(int32_t)));  // nothing measured yet: W / Q each
   }
+  if (g.conv) {
+    const size_t partials = (size_t)g.K * Q * ptk::kConvWaves;
+    if (dalloc(g, &g.d_ref, 3 * (size_t)g.N) || dalloc(g, &g.d_partial, partials) || dalloc(g, &g.d_sse, (size_t)PT_CONVERGENCE_CAPACITY)) return -1;
+    HIP_OK(hipMemset(g.d_ref, 0, 3 * (size_t)g.N * sizeof(float)));
+    HIP_OK(hipMemset(g.d_partial, 0, partials * sizeof(double)));  // queues without pixels never write theirs
+    HIP_OK(hipMemset(g.d_sse, 0xff, (size_t)PT_CONVERGENCE_CAPACITY * sizeof(double)));
+  }
   HIP_OK(hipMemset(g.d_image, 0, 3 * (size_t)g.N * sizeof(float)));
   HIP_OK(hipMemset(g.d_stats, 0, PT_MAX_DEPTH * sizeof(unsigned long long)));
   HIP_OK(hipDeviceSynchronize());
@@ -570,6 +596,7 @@ int setup(Ctx& g, const PtSceneDesc* sc, const PtOptions& opt) {
   plan_launch(g);
   if (alloc_batch_buffers(g) || choose_traversal(g)) return -1;
   g.time_kernels = opt.time_kernels != 0;
+  g.conv_live = g.conv != 0;
   return 0;
 }
 
@@ -716,6 +743,12 @@ int pt_ctx_render(PtContext* c, int iter_first, int iter_count) {
   if (iter_count <= 0) return 0;
   Ctx& g = *c;
   if (g.failed) return fail("pt_render: an earlier batch of this context failed (%s); free it and create a new one", g_err.c_str());
+  if (g.conv_live) {
+    if (iter_first < 1 || (int64_t)iter_first + iter_count - 1 > PT_CONVERGENCE_CAPACITY)
+      return fail("pt_render: iterations %d .. %lld outside 1 .. %d (PT_CONVERGENCE_CAPACITY) with the convergence metric on", iter_first,
+                  (long long)iter_first + iter_count - 1, PT_CONVERGENCE_CAPACITY);
+    if (g.conv < 0 && !g.conv_have_ref) return fail("pt_render: PtOptions.convergence is -1 but no reference frame has been supplied (pt_set_reference)");
+  }
   HIP_OK(hipSetDevice(g.device));
   EventPair ev{};
   if (get_events(g, &ev)) return -1;
@@ -862,7 +895,53 @@ int pt_ctx_clear(PtContext* c) {
   if (need(c, "pt_clear")) return -1;
   if (pt_ctx_sync(c)) return -1;
   HIP_OK(hipMemsetAsync(c->d_image, 0, 3 * (size_t)c->N * sizeof(float), c->stream));
+  if (c->conv) {  // forget the curve, re-arm the capture (a supplied frame stays)
+    HIP_OK(hipMemsetAsync(c->d_sse, 0xff, (size_t)PT_CONVERGENCE_CAPACITY * sizeof(double), c->stream));
+    c->conv_last = 0;
+    if (c->conv > 0) c->conv_have_ref = false;
+  }
   return pt_ctx_reset_stats(c);
+}
+
+// ---- convergence metric ---------------------------------------------------------------------
+int pt_ctx_set_reference(PtContext* c, const float* rgb_avg_host) {
+  if (need(c, "pt_set_reference")) return -1;
+  if (!rgb_avg_host) return fail("pt_set_reference: null image");
+  if (c->conv != -1) return fail("pt_set_reference: the renderer was created with PtOptions.convergence = %d, not -1", c->conv);
+  if (pt_ctx_sync(c)) return -1;
+  HIP_OK(hipMemcpyAsync(c->d_ref, rgb_avg_host, 3 * (size_t)c->N * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIP_OK(hipStreamSynchronize(c->stream));
+  c->conv_have_ref = true;
+  return 0;
+}
+
+int pt_ctx_get_convergence(PtContext* c, int iter_first, int iter_count, double* sse) {
+  if (need(c, "pt_get_convergence")) return -1;
+  if (!c->conv) return fail("pt_get_convergence: the renderer was created with PtOptions.convergence = 0 (metric off)");
+  if (iter_count < 0 || (iter_count > 0 && !sse)) return fail("pt_get_convergence: bad argument");
+  if (pt_ctx_sync(c)) return -1;
+  for (int j = 0; j < iter_count; ++j) sse[j] = -1.0;
+  const int64_t lo = std::max<int64_t>(iter_first, 1), hi = std::min<int64_t>((int64_t)iter_first + iter_count, (int64_t)PT_CONVERGENCE_CAPACITY + 1);
+  if (lo >= hi) return 0;
+  double* dst = sse + (lo - iter_first);
+  HIP_OK(hipMemcpy(dst, c->d_sse + (lo - 1), (size_t)(hi - lo) * sizeof(double), hipMemcpyDeviceToHost));
+  for (int64_t j = 0; j < hi - lo; ++j)
+    if (!(dst[j] >= 0.0)) dst[j] = -1.0;  // the "no value" pattern is a NaN
+  return 0;
+}
+
+int pt_ctx_iterations_to_clean(PtContext* c, float threshold_db, int* iteration) {
+  if (need(c, "pt_iterations_to_clean")) return -1;
+  if (!iteration) return fail("pt_iterations_to_clean: null output");
+  std::vector<double> sse((size_t)std::max(c->conv_last, 0));
+  if (pt_ctx_get_convergence(c, 1, (int)sse.size(), sse.data())) return -1;
+  *iteration = -1;
+  for (size_t i = 0; i < sse.size(); ++i)
+    if (sse[i] >= 0.0 && pt_psnr_from_sse(sse[i], c->N) > threshold_db) {
+      *iteration = (int)i + 1;
+      break;
+    }
+  return 0;
 }
 
 // ---- the reference's single-instance API (pathtrace.h) on a default context -------------
@@ -886,6 +965,9 @@ int pt_preview_rgba8_device(int iterations, void* rgba_dev) { return pt_ctx_prev
 int pt_get_stats(PtStats* out) { return pt_ctx_get_stats(g_default, out); }
 int pt_reset_stats(void) { return pt_ctx_reset_stats(g_default); }
 int pt_clear(void) { return pt_ctx_clear(g_default); }
+int pt_set_reference(const float* rgb_avg_host) { return pt_ctx_set_reference(g_default, rgb_avg_host); }
+int pt_get_convergence(int iter_first, int iter_count, double* sse) { return pt_ctx_get_convergence(g_default, iter_first, iter_count, sse); }
+int pt_iterations_to_clean(float threshold_db, int* iteration) { return pt_ctx_iterations_to_clean(g_default, threshold_db, iteration); }
 
 // ---- stage entry points (tests; default context) ------------------------------------------------
 // The C ABI of the stages takes plain SoA float arrays ([3][n]); the kernels stream three planes of 16-byte path records

@@ -276,6 +276,51 @@ int pt_group_gather_u8(PtGroup* g, float samples, uint8_t* rgb8_host) {
   return pt_group_sync(g);
 }
 
+// Convergence metric of the whole frame (PtOptions.convergence in `base`): every context keeps the sums of its own rows; they
+// meet on the host, one double per iteration and context.
+int pt_group_set_reference(PtGroup* g, const float* rgb_avg_host) {
+  if (!g || !rgb_avg_host) return pt_fail("pt_group_set_reference: bad argument");
+  const size_t row = 3 * (size_t)g->W;
+  std::vector<float> tile;
+  for (int i = 0; i < g->n; ++i) {  // context i owns rows i, i + n, ... in that order
+    tile.resize(row * (size_t)g->rows[i]);
+    for (int r = 0; r < g->rows[i]; ++r) std::memcpy(tile.data() + row * r, rgb_avg_host + row * ((size_t)i + (size_t)r * g->n), row * sizeof(float));
+    if (pt_ctx_set_reference(g->ctx[i], tile.data())) return -1;
+  }
+  return 0;
+}
+
+int pt_group_get_convergence(PtGroup* g, int iter_first, int iter_count, double* sse) {
+  if (!g || iter_count < 0 || (iter_count > 0 && !sse)) return pt_fail("pt_group_get_convergence: bad argument");
+  std::vector<double> part((size_t)iter_count);
+  for (int i = 0; i < g->n; ++i) {
+    if (pt_ctx_get_convergence(g->ctx[i], iter_first, iter_count, i == 0 ? sse : part.data())) return -1;
+    for (int j = 0; j < iter_count && i > 0; ++j) sse[j] = (sse[j] < 0.0 || part[j] < 0.0) ? -1.0 : sse[j] + part[j];  // context order
+  }
+  return 0;
+}
+
+int pt_group_iterations_to_clean(PtGroup* g, float threshold_db, int* iteration) {
+  if (!g || !iteration) return pt_fail("pt_group_iterations_to_clean: bad argument");
+  *iteration = -1;
+  const int chunk = 1024;
+  std::vector<double> sse((size_t)chunk);
+  for (int first = 1; first <= PT_CONVERGENCE_CAPACITY; first += chunk) {
+    if (pt_group_get_convergence(g, first, chunk, sse.data())) return -1;
+    bool any = false;
+    for (int j = 0; j < chunk; ++j) {
+      if (sse[j] < 0.0) continue;
+      any = true;
+      if (pt_psnr_from_sse(sse[j], (int64_t)g->W * g->H) > threshold_db) {
+        *iteration = first + j;
+        return 0;
+      }
+    }
+    if (!any && first > 1) break;  // past the rendered iterations
+  }
+  return 0;
+}
+
 // Progressive preview (the reference converts and shows the running average after EVERY iteration: sendImageToPBO,
 // src/pathtrace.cu:250-268,618): every device converts its own rows (average over `iterations`, gamma 1/2.2, clamp,
 // RGBA8), then the same single exchange + row placement as the write-out, 4 B per pixel.  Meant to be called every N

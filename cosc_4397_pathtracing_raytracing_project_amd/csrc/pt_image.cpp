@@ -2,6 +2,7 @@
 // saveImage() (src/main.cpp:86-107) + image::savePNG (src/image.cpp:22-39) produce,
 // without stb: a self-contained PNG encoder (zlib "stored" deflate blocks) and a
 // PFM writer for lossless float output.
+#include <cfloat>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -223,6 +224,57 @@ int pt_save_pfm(const char* path, const float* rgb_sum, int w, int h, float samp
   }
   fclose(f);
   return 0;
+}
+
+int pt_load_pfm(const char* path, float* rgb_sum, int cap_pixels, int* w_out, int* h_out, float samples) {
+  if (!path || !w_out || !h_out) return -1;
+  FILE* f = fopen(path, "rb");
+  if (!f) return -1;
+  char magic[3] = {0, 0, 0};
+  int w = 0, h = 0;
+  double scale = 0.0;
+  // header: "PF", width, height, scale (negative: little-endian), then exactly one white-space byte
+  const bool head = fscanf(f, "%2s %d %d %lf", magic, &w, &h, &scale) == 4 && !strcmp(magic, "PF") && w > 0 && h > 0 && scale != 0.0 &&
+                    (int64_t)w * h <= (1ll << 30) && fgetc(f) != EOF;
+  if (!head) {
+    fclose(f);
+    return -1;
+  }
+  *w_out = w, *h_out = h;
+  if (!rgb_sum) {
+    fclose(f);
+    return 0;
+  }
+  if ((int64_t)cap_pixels < (int64_t)w * h) {
+    fclose(f);
+    return -1;
+  }
+  std::vector<float> row(3 * (size_t)w);
+  for (int y = h - 1; y >= 0; --y) {  // rows bottom-to-top, as pt_save_pfm writes them
+    if (fread(row.data(), sizeof(float), row.size(), f) != row.size()) {
+      fclose(f);
+      return -1;
+    }
+    for (size_t i = 0; i < row.size(); ++i) {
+      float v = row[i];
+      if (scale > 0.0) {  // big-endian file
+        uint32_t u;
+        memcpy(&u, &v, 4);
+        u = (u >> 24) | ((u >> 8) & 0xff00u) | ((u << 8) & 0xff0000u) | (u << 24);
+        memcpy(&v, &u, 4);
+      }
+      rgb_sum[(size_t)y * w * 3 + i] = v * samples;
+    }
+  }
+  fclose(f);
+  return 0;
+}
+
+// computePSNR's last lines (pathtrace.cu:198-200)
+float pt_psnr_from_sse(double sse, int64_t pixels) {
+  const double mse = sse / ((double)pixels * 3.0);
+  if (mse <= 1e-12) return FLT_MAX;
+  return 10.0f * log10f(1.0f / float(mse));
 }
 
 }  // extern "C"

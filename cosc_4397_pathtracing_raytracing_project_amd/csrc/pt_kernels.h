@@ -83,6 +83,18 @@ struct BatchInfo {
                            // come, first served (counters behind ptd::Queues::deal); <= 1: one piece per wave; high 16 bits: fewest paths in a piece
 };
 
+// Convergence metric of the gather (PtOptions.convergence; k_collect_conv in pt_output.inc).  Iteration iter_first + k of a batch gets
+// a sum of squared errors against the reference frame when k >= first_k; the frame is either there before the batch (first_k == 0)
+// or is the average after iteration iter_first + capture_k of this batch, which the gather stores as it passes it
+// (first_k == capture_k + 1).
+constexpr int kConvWaves = 16;  // waves of a k_collect workgroup: partial sums per (iteration, queue)
+struct ConvInfo {
+  float* ref;         // [N][3] reference frame, averaged radiance
+  double* partial;    // [iterations per batch][Q][kConvWaves]
+  int32_t capture_k;  // -1: no capture in this batch
+  int32_t first_k;    // first k with a value; K: none
+};
+
 // Resident workgroups per CU for each persistent kernel (hipOccupancyMaxActiveBlocksPerMultiprocessor),
 // so that grid = CUs * blocks never exceeds what is co-resident: work is dealt statically to waves,
 // a workgroup that has to wait for a free slot would run its whole share after everybody else.
@@ -142,6 +154,9 @@ struct KernelApi {
   // queue, survivors never leave their registers (pt_kernels.hip k_paths; LDS-table scenes).  cnt = the counter rows [depth][Q]:
   // row 1 is read (the queues' depth-1 rays), rows >= 2 receive the rays traced per depth.
   void (*paths)(hipStream_t s, int grid, const SceneTables& sc, const BatchInfo& b, const ptd::Queues& qs, int32_t* cnt, ptd::PathBuf in, ptd::RetireBuf ret);
+  // `collect` with the convergence metric: additionally sse[iter_first + k - 1] = sum over the tile's pixels of the squared error of
+  // iteration iter_first + k against the reference frame, for first_k <= k < K (a second, small launch adds the gather's partial sums).
+  void (*collect_conv)(hipStream_t s, const BatchInfo& b, const ptd::Queues& qs, ptd::RetireBuf ret, float* image_rgb, const ConvInfo& cv, double* sse);
   int boxes_center_half;  // 1: the bounce kernels of this build expect SceneTables::*_b as centre / half extent (the fast build)
 };
 const KernelApi* api_exact();

@@ -1890,7 +1890,7 @@ const KernelApi kApi = {
 #endif
     launch_generate, launch_primary, launch_intersect, launch_shade, launch_collect, launch_count_stats,
     launch_preview, launch_save_u8, launch_shade_stage, lds_table_limit, resident_blocks_per_cu, launch_ieee_check, launch_paths,
-    kFast ? 1 : 0};
+    launch_collect_conv, kFast ? 1 : 0};
 
 }  // namespace
 }  // namespace PT_NS

@@ -166,6 +166,11 @@ void launch_collect(hipStream_t s, const BatchInfo& b, const ptd::Queues& qs, pt
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_collect), hipFuncAttributeMaxDynamicSharedMemorySize, collect_lds_bytes());
   hipLaunchKernelGGL(k_collect, dim3(qs.Q), dim3(kCollectThreads), collect_lds_bytes(), s, b, qs, ret, image_rgb);
 }
+void launch_collect_conv(hipStream_t s, const BatchInfo& b, const ptd::Queues& qs, ptd::RetireBuf ret, float* image_rgb, const ConvInfo& cv, double* sse) {
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_collect_conv), hipFuncAttributeMaxDynamicSharedMemorySize, collect_lds_bytes());
+  hipLaunchKernelGGL(k_collect_conv, dim3(qs.Q), dim3(kCollectThreads), collect_lds_bytes(), s, b, qs, ret, image_rgb, cv);
+  if (cv.first_k < b.K) hipLaunchKernelGGL(k_conv_reduce, dim3(b.K - cv.first_k), dim3(kBlock), 0, s, b.iter_first, cv.first_k, qs.Q * kCollectWaves, cv.partial, sse);
+}
 
 #include "pt_ieee_check.inc"
 

@@ -18,11 +18,16 @@ struct CollectChunk {
 };
 // (the u-th record of a thread exists only while i0 + u * 1024 < n — block-uniform: a queue of a small tile, e.g. 1024 pixels when
 // eight GPUs share a 1080p frame, pays for one record per thread and iteration, not for eight)
+// (FRESH: the record indices are formed anew at every call instead of living in sixteen registers across the iteration loop — the
+// convergence variant needs those for the reference frame)
+template <bool FRESH = false>
 PT_DEV void collect_load(const ptd::Word4* rec, int n, int i0, CollectChunk& c) {
+  int t = (int)threadIdx.x;
+  if constexpr (FRESH) asm volatile("" : "+v"(t));
 #pragma unroll
   for (int u = 0; u < kCollectPPT; ++u) {
     if (u > 0 && i0 + u * kCollectThreads >= n) break;
-    const int i = i0 + u * kCollectThreads + (int)threadIdx.x;
+    const int i = i0 + u * kCollectThreads + t;
     c.v[u] = rec[i < n ? i : (n > 0 ? n - 1 : 0)];
   }
 }
@@ -39,7 +44,49 @@ PT_DEV void collect_scatter(const CollectChunk& c, int n, int i0, int g0, int g1
     if (i < n && !(i >= g0 && i < g1) && li >= 0 && li < kCollectPixels) tile[3 * li] = c.v[u].x, tile[3 * li + 1] = c.v[u].y, tile[3 * li + 2] = c.v[u].z;
   }
 }
-__global__ __launch_bounds__(kCollectThreads) void k_collect(BatchInfo b, ptd::Queues qs, ptd::RetireBuf ret, float* __restrict__ image) {
+// Convergence metric (PtOptions.convergence, ConvInfo in pt_kernels.h): after the adds of iteration k a thread holds the SUM image the
+// reference has after iteration iter_first + k, so the squared error of computePSNR (pathtrace.cu:184-201) against the reference
+// frame is taken right here — cur = sum / float(iteration) correctly rounded, d = cur - ref, d.x d.x + d.y d.y + d.z d.z without
+// contraction in every build (namespace ex), added up in double.  The frame's values of a thread's pixels are loaded once per pass
+// (or, when the frame is iteration capture_k of this very batch, taken from `cur` as it passes and stored); a wave adds its lanes'
+// sums with cross-lane operations (wave_sum_f64) and one lane writes partial[k][queue][wave] — plain stores, a fixed order, no atomics, no barrier
+// of its own.  k_conv_reduce adds the partials of an iteration.
+constexpr int kCollectWaves = kCollectThreads / 64;
+static_assert(kCollectWaves == kConvWaves, "the host sizes the partial sums with pt_kernels.h kConvWaves");
+// Every one of three sums is +0 or lies in ieee::div_range (2^-47 <= v < 2^47): operands for which ieee::quot_core is the compiler's
+// correctly rounded quotient (a sum of radiance is +0 before the first light reaches the pixel; 0 * r and the residuals stay +0).
+// On the bit patterns, as unsigned numbers: the largest is below the pattern of 2^47 (which no negative number is) and the smallest
+// of (pattern - 1) is at least the pattern of 2^-47 minus one (0 - 1 wraps to the top).  Denormal, huge, negative or non-finite
+// sums send the wave through the compiler's divide.
+PT_DEV bool conv_div_ok(float x, float y, float z) {
+  const uint32_t a = __float_as_uint(x), b = __float_as_uint(y), c = __float_as_uint(z);
+  return max(max(a, b), c) < 0x57000000u && min(min(a - 1u, b - 1u), c - 1u) >= 0x28000000u - 1u;
+}
+// The sum of a double over the wave's 64 lanes, wave-uniform, in a fixed order: four DPP steps leave the sum of each 16-lane row in
+// all of its lanes (both partners of a step add the same two values), the four row sums are read into scalar registers and added
+// front to back.  (~20 instructions; six dependent rounds of ds_bpermute pairs, as __shfl_xor would issue them, cost the gather of a
+// small tile — one pixel per thread, 195 iterations per batch — more than everything else the metric does.)
+template <int CTRL>
+PT_DEV double dpp_f64(double v) {
+  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)u, CTRL, 0xf, 0xf, false);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), CTRL, 0xf, 0xf, false);
+  return __longlong_as_double((long long)((unsigned long long)hi << 32 | lo));
+}
+PT_DEV double readlane_f64(double v, int lane) {
+  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, lane), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), lane);
+  return __longlong_as_double((long long)((unsigned long long)hi << 32 | lo));
+}
+PT_DEV double wave_sum_f64(double v) {
+  v += dpp_f64<0xb1>(v);   // quad_perm [1, 0, 3, 2]
+  v += dpp_f64<0x4e>(v);   // quad_perm [2, 3, 0, 1]
+  v += dpp_f64<0x141>(v);  // row_half_mirror
+  v += dpp_f64<0x140>(v);  // row_mirror
+  return ((readlane_f64(v, 0) + readlane_f64(v, 16)) + readlane_f64(v, 32)) + readlane_f64(v, 48);
+}
+template <bool CONV>
+PT_DEV void collect_body(BatchInfo b, ptd::Queues qs, ptd::RetireBuf ret, float* __restrict__ image, ConvInfo cv) {
   extern __shared__ float4 lds_raw[];
   float* tile = reinterpret_cast<float*>(lds_raw);  // [kCollectPixels][3]
   const int q = blockIdx.x;
@@ -60,6 +107,8 @@ __global__ __launch_bounds__(kCollectThreads) void k_collect(BatchInfo b, ptd::Q
   }
   for (int first = 0; first < sh.my_nq * 64; first += kCollectPixels) {  // one pass per kCollectPixels of the queue's pixels
     float acc[kCollectPPT][3];
+    float rf[CONV ? kCollectPPT : 1][3];  // the reference frame's values of this thread's pixels
+    uint32_t mine_bits = 0;               // bit m: pixel m of this thread exists
     // thread t owns the queue pixels first + t + kCollectThreads * m: chunk jj = index >> 6 is tile chunk q + jj * Q
 #pragma unroll
     for (int m = 0; m < kCollectPPT; ++m) {
@@ -67,18 +116,23 @@ __global__ __launch_bounds__(kCollectThreads) void k_collect(BatchInfo b, ptd::Q
       const int pl = (q + (li >> 6) * qs.Q) * 64 + (li & 63);
       const bool mine = li < sh.my_nq * 64 && pl < b.N;
       acc[m][0] = mine ? image[3 * (int64_t)pl] : 0.f, acc[m][1] = mine ? image[3 * (int64_t)pl + 1] : 0.f, acc[m][2] = mine ? image[3 * (int64_t)pl + 2] : 0.f;
+      if constexpr (CONV) {
+        const bool have = mine && cv.first_k == 0;  // the frame exists before this batch
+        mine_bits |= (mine ? 1u : 0u) << m;
+        rf[m][0] = have ? cv.ref[3 * (int64_t)pl] : 0.f, rf[m][1] = have ? cv.ref[3 * (int64_t)pl + 1] : 0.f, rf[m][2] = have ? cv.ref[3 * (int64_t)pl + 2] : 0.f;
+      }
     }
     // software pipeline: the first 8192 records of iteration k + 1 are in flight while iteration k is summed (the tile is
     // reused every iteration, so the two barriers per iteration stay)
     CollectChunk c;
-    collect_load(rec, n, 0, c);
+    collect_load<CONV>(rec, n, 0, c);
     for (int k = 0; k < b.K; ++k) {
       collect_scatter(c, n, 0, g0, g1, qs.Q, inv_q, first, tile);
       for (int i0 = kCollectPixels; i0 < n; i0 += kCollectPixels) {  // regions longer than one chunk (several passes only)
-        collect_load(rec + (int64_t)k * ret.seg_cap, n, i0, c);
+        collect_load<CONV>(rec + (int64_t)k * ret.seg_cap, n, i0, c);
         collect_scatter(c, n, i0, g0, g1, qs.Q, inv_q, first, tile);
       }
-      if (k + 1 < b.K) collect_load(rec + (int64_t)(k + 1) * ret.seg_cap, n, 0, c);
+      if (k + 1 < b.K) collect_load<CONV>(rec + (int64_t)(k + 1) * ret.seg_cap, n, 0, c);
       __syncthreads();
 #pragma unroll
       for (int m = 0; m < kCollectPPT; ++m) {
@@ -86,17 +140,82 @@ __global__ __launch_bounds__(kCollectThreads) void k_collect(BatchInfo b, ptd::Q
         const int li = threadIdx.x + kCollectThreads * m;  // every pixel of the queue retires exactly once per iteration: no stale entries are read
         acc[m][0] += tile[3 * li], acc[m][1] += tile[3 * li + 1], acc[m][2] += tile[3 * li + 2];
       }
+      if constexpr (CONV) {
+        if (k == cv.capture_k || k >= cv.first_k) {  // block-uniform
+          // 1 .. 2^24: inside ieee::div_range; divisor and refined reciprocal are the same in every lane: scalar registers
+          const float n_it = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint((float)(b.iter_first + k))));
+          uint32_t ok = 1u;
+#pragma unroll
+          for (int m = 0; m < kCollectPPT; ++m) {
+            if (m > 0 && first + kCollectThreads * m >= sh.my_nq * 64) break;
+            ok &= (~mine_bits >> m & 1u) | (uint32_t)conv_div_ok(acc[m][0], acc[m][1], acc[m][2]);
+          }
+          const bool short_div = ieee::every_lane(ok != 0u);
+          const float r_it = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(ieee::rcp_core(n_it))));
+          double sum = 0.0;
+#pragma unroll
+          for (int m = 0; m < kCollectPPT; ++m) {
+            if (m > 0 && first + kCollectThreads * m >= sh.my_nq * 64) break;
+            const bool mine = mine_bits >> m & 1u;
+            f3 cur;
+            if (short_div) cur = mk(ieee::quot_core(acc[m][0], n_it, r_it), ieee::quot_core(acc[m][1], n_it, r_it), ieee::quot_core(acc[m][2], n_it, r_it));
+            else cur = mk(acc[m][0] / n_it, acc[m][1] / n_it, acc[m][2] / n_it);
+            if (k == cv.capture_k) {
+              rf[m][0] = cur.x, rf[m][1] = cur.y, rf[m][2] = cur.z;
+              int t_cap = (int)threadIdx.x;
+              asm volatile("" : "+v"(t_cap));  // the frame's addresses are formed here, once per render, not kept across the iteration loop
+              const int li = first + t_cap + kCollectThreads * m;
+              const int pl = (q + (li >> 6) * qs.Q) * 64 + (li & 63);
+              if (mine) cv.ref[3 * (int64_t)pl] = cur.x, cv.ref[3 * (int64_t)pl + 1] = cur.y, cv.ref[3 * (int64_t)pl + 2] = cur.z;
+            } else {
+              const f3 d = ex::sub(cur, mk(rf[m][0], rf[m][1], rf[m][2]));
+              sum += mine ? (double)ex::dot(d, d) : 0.0;
+            }
+          }
+          if (k >= cv.first_k) {
+            sum = wave_sum_f64(sum);
+            double* slot = cv.partial + ((int64_t)k * qs.Q + q) * kCollectWaves + (threadIdx.x >> 6);
+            if ((threadIdx.x & 63) == 0) *slot = first == 0 ? sum : *slot + sum;  // (a later pass: this lane wrote the slot itself)
+          }
+        }
+      }
       __syncthreads();
     }
+    int t_out = (int)threadIdx.x;
+    if constexpr (CONV) asm volatile("" : "+v"(t_out));  // the pixels' addresses are formed anew instead of living across the iteration loop
 #pragma unroll
     for (int m = 0; m < kCollectPPT; ++m) {
-      const int li = first + threadIdx.x + kCollectThreads * m;
+      const int li = first + t_out + kCollectThreads * m;
       const int pl = (q + (li >> 6) * qs.Q) * 64 + (li & 63);
       if (li < sh.my_nq * 64 && pl < b.N) image[3 * (int64_t)pl] = acc[m][0], image[3 * (int64_t)pl + 1] = acc[m][1], image[3 * (int64_t)pl + 2] = acc[m][2];
     }
   }
   // the records are consumed: zero counters for the next batch
   for (int i = threadIdx.x; i < ret.kmax; i += kCollectThreads) ret.cnt[(int64_t)q * ret.kmax + i] = 0ull;
+}
+__global__ __launch_bounds__(kCollectThreads) void k_collect(BatchInfo b, ptd::Queues qs, ptd::RetireBuf ret, float* __restrict__ image) {
+  collect_body<false>(b, qs, ret, image, ConvInfo{});
+}
+// the same gather with the convergence metric: 4 waves per SIMD as well, i.e. at most 128 VGPRs
+__global__ __launch_bounds__(kCollectThreads) void k_collect_conv(BatchInfo b, ptd::Queues qs, ptd::RetireBuf ret, float* __restrict__ image, ConvInfo cv) {
+  collect_body<true>(b, qs, ret, image, cv);
+}
+// sse[iteration - 1] = the partial sums of iteration iter_first + k, k = first_k + blockIdx.x, in a fixed order: thread t adds
+// elements t, t + 256, ... of the Q * kCollectWaves values, a wave its lanes, thread 0 the four waves.
+__global__ __launch_bounds__(kBlock) void k_conv_reduce(int iter_first, int first_k, int count, const double* __restrict__ partial, double* __restrict__ sse) {
+  const int k = first_k + blockIdx.x;
+  const double* p = partial + (int64_t)k * count;
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < count; i += kBlock) acc += p[i];
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  __shared__ double part[kWavesPerBlock];
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = part[0];
+    for (int w = 1; w < kWavesPerBlock; ++w) t += part[w];
+    sse[iter_first + k - 1] = t;
+  }
 }
 
 // k_paths' waves for the next batch (ptd::Queues::deal): queue q gets one wave plus its share of the other W - Q by the time

@@ -5,7 +5,7 @@
 //
 //   pt_render SCENE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr]
 //                       [--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa]
-//                       [--preview N]
+//                       [--preview N] [--convergence N | --reference FILE.pfm] [--clean-db X]
 //
 // Without --gpus the run goes through the pathtrace.h-compatible shim (pathtraceInit / pathtrace per
 // iteration / pathtraceFree), i.e. the code path a reference main.cpp would take.  With --gpus K (K >= 1;
@@ -15,11 +15,16 @@
 // exchange then uses peer / device copies instead of RCCL, PT_GROUP_TRANSPORT_COPY; --transport forces either).
 // --preview N (with --gpus): every N iterations the running average is converted on the devices and gathered
 // (pt_group_preview_rgba8 — the reference shows it after every iteration, pathtrace.cu:618) into PREFIX.preview.png.
+// --convergence N / --reference FILE.pfm: the convergence metric (PtOptions.convergence) against the average after iteration N
+// (the reference's computePSNR: N = 10) or against an averaged-radiance image as --pfm writes it (e.g. a 5000-spp render): after
+// the render one line `iteration psnr_db` per iteration ("Inf" where the reference prints it) and "Iterations to clean: n", the
+// first iteration above --clean-db (default 35; -1 when there is none).  Works with --gpus / --devices.
 // Output name: PREFIX.<spp>samp.png, or with --stamp the reference's own
 // <FILE>.<UTC start time>.<spp>samp.png (main.cpp:99-102).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -33,13 +38,16 @@
 int main(int argc, char** argv) {
   if (argc < 2) {
     std::printf("Usage: %s SCENEFILE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] "
-                "[--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa] [--preview N]\n", argv[0]);
+                "[--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa] [--preview N] "
+                "[--convergence N | --reference FILE.pfm] [--clean-db X]\n", argv[0]);
     return 1;
   }
   int rw = 0, rh = 0, spp = 0, depth = 0, gpus = -1, arith = PT_ARITH_EXACT, preview = 0, transport = PT_GROUP_TRANSPORT_AUTO;
   std::vector<int> device_list;
   bool pfm = false, hdr = false, stamp = false, aa = false;
-  std::string out;
+  int convergence = 0;
+  float clean_db = 35.0f;
+  std::string out, reference;
   for (int i = 2; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--res") && i + 1 < argc) std::sscanf(argv[++i], "%dx%d", &rw, &rh);
     else if (!std::strcmp(argv[i], "--spp") && i + 1 < argc) spp = std::atoi(argv[++i]);
@@ -47,6 +55,14 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) out = argv[++i];
     else if (!std::strcmp(argv[i], "--gpus") && i + 1 < argc) gpus = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--preview") && i + 1 < argc) preview = std::atoi(argv[++i]);
+    else if (!std::strcmp(argv[i], "--convergence") && i + 1 < argc) {
+      convergence = std::atoi(argv[++i]);
+      if (convergence <= 0) {
+        std::fprintf(stderr, "--convergence wants the iteration (>= 1) whose average becomes the reference frame\n");
+        return 1;
+      }
+    } else if (!std::strcmp(argv[i], "--reference") && i + 1 < argc) reference = argv[++i];
+    else if (!std::strcmp(argv[i], "--clean-db") && i + 1 < argc) clean_db = (float)std::atof(argv[++i]);
     else if (!std::strcmp(argv[i], "--devices") && i + 1 < argc) {
       for (const char* q = argv[++i]; *q;) {
         char* end = nullptr;
@@ -85,6 +101,11 @@ int main(int argc, char** argv) {
       return 1;
     }
   }
+  if (convergence > 0 && !reference.empty()) {
+    std::fprintf(stderr, "--convergence and --reference exclude each other (one reference frame)\n");
+    return 1;
+  }
+  if (!reference.empty()) convergence = -1;
   pt::Scene* scene = nullptr;
   try {
     scene = new pt::Scene(argv[1]);
@@ -106,6 +127,28 @@ int main(int argc, char** argv) {
     base = buf;
   }
 
+  std::vector<float> ref_frame;  // --reference: W * H averaged radiance
+  if (!reference.empty()) {
+    int fw = 0, fh = 0;
+    if (pt_load_pfm(reference.c_str(), nullptr, 0, &fw, &fh, 1.0f) || fw != W || fh != H) {
+      std::fprintf(stderr, "--reference %s: not a PFM image of %dx%d\n", reference.c_str(), W, H);
+      return 1;
+    }
+    ref_frame.resize((size_t)W * H * 3);
+    if (pt_load_pfm(reference.c_str(), ref_frame.data(), W * H, &fw, &fh, 1.0f)) {
+      std::fprintf(stderr, "--reference %s: cannot read the pixels\n", reference.c_str());
+      return 1;
+    }
+  }
+  // the curve after the render: `iteration psnr_db` per line, then the iterations to clean
+  auto print_curve = [&](const std::vector<float>& psnr, int clean) {
+    for (int it = 1; it <= iters; ++it) {
+      if (psnr[it - 1] == FLT_MAX) std::printf("%d Inf\n", it);
+      else std::printf("%d %.9g\n", it, psnr[it - 1]);
+    }
+    std::printf("Iterations to clean: %d\n", clean);
+  };
+
   double secs = 0;
   if (gpus < 0) {
     // the reference's call sequence (main.cpp:133-152) through the pathtrace.h shim
@@ -114,7 +157,12 @@ int main(int argc, char** argv) {
     pathtraceFree();  // main.cpp:134 frees before the first init
     pathtraceSetArith(arith);
     pathtraceSetAntialias(aa);
+    pathtraceSetConvergence(convergence);
     pathtraceInit(scene);
+    if (!ref_frame.empty() && pt_set_reference(ref_frame.data())) {
+      std::fprintf(stderr, "HIP error (pt_set_reference): %s\n", pt_last_error());
+      return EXIT_FAILURE;
+    }
     const auto t0 = std::chrono::high_resolution_clock::now();
     for (int it = 1; it <= iters; ++it) pathtrace(nullptr, 0, it);  // main.cpp:138-149
     pathtraceSyncImage();
@@ -127,6 +175,16 @@ int main(int argc, char** argv) {
       std::printf("Saved %s.pfm.\n", base.c_str());
     if (hdr && pt_save_hdr((base + ".hdr").c_str(), scene->state.image.data(), W, H, (float)iters) == 0)
       std::printf("Saved %s.hdr.\n", base.c_str());
+    if (convergence) {
+      std::vector<float> psnr((size_t)iters);
+      for (int it = 1; it <= iters; ++it) psnr[it - 1] = pathtracePSNR(it);  // what the reference prints after every iteration
+      int clean = -1;
+      if (pt_iterations_to_clean(clean_db, &clean)) {
+        std::fprintf(stderr, "HIP error (pt_iterations_to_clean): %s\n", pt_last_error());
+        return EXIT_FAILURE;
+      }
+      print_curve(psnr, clean);
+    }
     pathtraceFree();
   } else {
     int ndev = 0;
@@ -149,10 +207,15 @@ int main(int argc, char** argv) {
     PtOptions opt{};
     opt.arith = arith;
     opt.aa_jitter = aa ? 1 : 0;
+    opt.convergence = convergence;
     const PtSceneDesc desc = scene->desc();
     PtGroup* grp = nullptr;
     if (pt_group_create_ex(&desc, &opt, devices.data(), gpus, transport, &grp)) {
       std::fprintf(stderr, "HIP error (pt_group_create): %s\n", pt_last_error());
+      return EXIT_FAILURE;
+    }
+    if (!ref_frame.empty() && pt_group_set_reference(grp, ref_frame.data())) {
+      std::fprintf(stderr, "HIP error (pt_group_set_reference): %s\n", pt_last_error());
       return EXIT_FAILURE;
     }
     std::vector<uint8_t> rgb8((size_t)W * H * 3);
@@ -191,6 +254,17 @@ int main(int argc, char** argv) {
         std::printf("Saved %s.pfm.\n", base.c_str());
       if (hdr && pt_save_hdr((base + ".hdr").c_str(), scene->state.image.data(), W, H, (float)iters) == 0)
         std::printf("Saved %s.hdr.\n", base.c_str());
+    }
+    if (convergence) {
+      std::vector<double> sse((size_t)iters);
+      int clean = -1;
+      if (pt_group_get_convergence(grp, 1, iters, sse.data()) || pt_group_iterations_to_clean(grp, clean_db, &clean)) {
+        std::fprintf(stderr, "HIP error (pt_group_get_convergence): %s\n", pt_last_error());
+        return EXIT_FAILURE;
+      }
+      std::vector<float> psnr((size_t)iters);
+      for (int it = 1; it <= iters; ++it) psnr[it - 1] = sse[it - 1] < 0.0 ? FLT_MAX : pt_psnr_from_sse(sse[it - 1], (int64_t)W * H);
+      print_curve(psnr, clean);
     }
     pt_group_destroy(grp);
   }

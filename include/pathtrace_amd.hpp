@@ -43,3 +43,9 @@ void pathtraceSyncImage();
 void pathtraceSetArith(int pt_arith);
 // extension: stochastic anti-aliasing (PtOptions.aa_jitter) of the next pathtraceInit; default off = reference semantics
 void pathtraceSetAntialias(int on);
+// extension: convergence metric (PtOptions.convergence) of the next pathtraceInit: 0 off (default), N > 0 the reference frame is
+// the average after iteration N (the reference's computePSNR uses 10)
+void pathtraceSetConvergence(int n);
+// extension: flushes queued iterations and returns what the reference prints as "PSNR" after iteration `iter`
+// (pathtrace.cu:627-638): FLT_MAX where it prints "Inf" (no reference frame yet, or mse <= 1e-12)
+float pathtracePSNR(int iter);

@@ -118,7 +118,12 @@ typedef struct PtOptions {
                                (pathtrace.cu:270-286) although its assignment text asks for this (INSTRUCTION.md:96).
                                u1, u2 come from a hash domain of their own, every other random stream is unchanged.
                                Parity unpinned (nothing in the reference to compare with): tested GPU == oracle. */
-  int32_t reserved[1];
+  int32_t convergence;      /* convergence metric (computePSNR, pathtrace.cu:184-201), computed inside the gather: 0 off (default;
+                               nothing is allocated, the kernels are the ones that run without this field); N > 0: the frame
+                               every iteration is compared with is the average after iteration N (the reference's N is 10), kept
+                               on the device, and iterations <= N have no value; -1: the frame is supplied with
+                               pt_set_reference before the first pt_render.  pt_init fails on any other value.  See
+                               pt_get_convergence. */
   /* Overrides of automatic choices (tests, A/B): 0 = automatic; no value changes the image. */
   int32_t lds_table_kb;     /* LDS staging limit of the scene tables: N > 0 forces N KB (at most 64), < 0 keeps the tables
                                in memory (automatic: staged when every leaf is a top-list entry and staging costs the fused
@@ -264,6 +269,34 @@ const char* pt_last_error(void);
  * `count` bit patterns starting at `first` (2^32 patterns = every float); kind 3 a/b, 4 the shared-reciprocal forms over
  * `count` pseudo-random operand sets derived from `seed` and the set's index first + i.  `arith` selects the kernel build. */
 int pt_selfcheck_ieee(int arith, int kind, uint64_t first, uint64_t count, uint32_t seed, uint64_t* mismatches);
+/* ---- convergence metric (PtOptions.convergence != 0).  For a tile pixel p after iteration i, with S the running SUM image and R
+ * the reference frame (averaged radiance), computePSNR's terms (pathtrace.cu:184-201) in float32: cur = S[p] / float(i) per
+ * component (correctly rounded), d = cur - R[p], term = d.x*d.x + d.y*d.y + d.z*d.z left to right without FMA contraction in
+ * every arithmetic mode; SSE_i = sum over the tile's pixels of (double)term, added in a fixed order (no atomics: equal options give
+ * equal bits).  The sums stay on the device until they are asked for; pt_render gains no synchronisation and no allocation.
+ * Device memory the metric adds (PtStats.device_bytes), all allocated by pt_init:
+ *     12 * pixel_count                                                   the reference frame
+ *   +  8 * iters_per_batch * num_queues * PT_CONVERGENCE_WAVES           partial sums of one batch (PtStats has both factors)
+ *   +  8 * PT_CONVERGENCE_CAPACITY                                       one SSE per iteration
+ * pt_render fails for iterations outside 1 .. PT_CONVERGENCE_CAPACITY while the metric is on.
+ * pt_clear (and a new pt_init) forget the curve and re-arm the capture of iteration N; a supplied frame survives pt_clear.
+ * Unlike the reference, whose frame is a file-scope static that survives pathtraceInit, the frame belongs to the renderer. */
+#define PT_CONVERGENCE_WAVES 16
+#define PT_CONVERGENCE_CAPACITY 65536
+/* The frame of PtOptions.convergence == -1: pixel_count * 3 floats of averaged radiance in tile order (pt_readback's layout
+ * divided by the sample count), e.g. a 5000-spp render.  Synchronises. */
+int pt_set_reference(const float* rgb_avg_host);
+/* sse[j] = SSE of iteration iter_first + j, or -1 where there is none: the iteration was not rendered, lies outside the capacity,
+ * or the frame did not exist yet (captured frame: iterations <= N).  Synchronises. */
+int pt_get_convergence(int iter_first, int iter_count, double* sse);
+/* "Iterations to clean image" (the reference's README metric): the smallest rendered iteration that has a PSNR above
+ * threshold_db (the reference uses 35), or -1.  The reference's own code always reports 1, because iteration 1's FLT_MAX
+ * placeholder passes `psnr > 35.0f` (pathtrace.cu:629); this is the README's meaning.  Synchronises. */
+int pt_iterations_to_clean(float threshold_db, int* iteration);
+/* Host-only: computePSNR's last lines.  mse = sse / (pixels * 3.0); FLT_MAX (the reference prints "Inf") when mse <= 1e-12,
+ * else 10.0f * log10f(1.0f / float(mse)). */
+float pt_psnr_from_sse(double sse, int64_t pixels);
+
 /* saveImage()'s per-pixel conversion (main.cpp:91-97 x mirror, image.cpp:26-30 clamp * 255 truncated) on the
  * device: pixel_count*3 bytes, row-major, x mirrored inside each row; the tile must consist of whole rows.
  * Reads back 3 B per pixel instead of 12. */
@@ -284,6 +317,9 @@ int pt_ctx_preview_rgba8_device(PtContext* c, int iterations, void* rgba_dev);
 int pt_ctx_get_stats(PtContext* c, PtStats* out);
 int pt_ctx_reset_stats(PtContext* c);
 int pt_ctx_clear(PtContext* c);
+int pt_ctx_set_reference(PtContext* c, const float* rgb_avg_host);
+int pt_ctx_get_convergence(PtContext* c, int iter_first, int iter_count, double* sse);
+int pt_ctx_iterations_to_clean(PtContext* c, float threshold_db, int* iteration);
 const float* pt_ctx_device_image(PtContext* c); /* device pointer of the tile SUM image */
 void* pt_ctx_stream(PtContext* c);              /* the context's hipStream_t */
 int pt_ctx_pixel_count(const PtContext* c);
@@ -320,6 +356,13 @@ int pt_group_gather_u8(PtGroup* g, float samples, uint8_t* rgb8_host); /* W*H*3 
  * iteration): W*H RGBA8 bytes, raw orientation, converted on each device, one exchange of 4 B per pixel. */
 int pt_group_preview_rgba8(PtGroup* g, int iterations, uint8_t* rgba_host);
 
+/* The convergence metric of the whole frame: the reference frame is a W*H image (raw orientation, averaged radiance) of which
+ * every context receives its rows; the contexts' SSEs are added in context order (one double per iteration and context crosses to
+ * the host, nothing goes on the data path); the PSNR of pt_group_iterations_to_clean is over all W*H pixels. */
+int pt_group_set_reference(PtGroup* g, const float* rgb_avg_host);
+int pt_group_get_convergence(PtGroup* g, int iter_first, int iter_count, double* sse);
+int pt_group_iterations_to_clean(PtGroup* g, float threshold_db, int* iteration);
+
 /* ---- stage-level entry points (same kernels, caller-supplied HOST arrays, SoA:
  * vec3 arrays are [3][n]).  Used by the parity tests; each uploads, launches the
  * production kernel, downloads. ----------------------------------------------- */
@@ -349,6 +392,11 @@ int pt_write_png_rgb8(const char* path, const uint8_t* rgb8, int w, int h);
  * the reference's); writes at most cap bytes incl. the terminator, returns the full length. */
 int pt_output_basename(const char* name, int samples, char* out, int cap);
 int pt_save_pfm(const char* path, const float* rgb_sum, int w, int h, float samples);
+/* The inverse of pt_save_pfm: *w, *h receive the size; rgb_sum (may be NULL to ask for the size only; else cap_pixels * 3 floats,
+ * cap_pixels >= w * h) receives the raw-orientation image times `samples` — the SUM image bit for bit when the file was written
+ * with samples = 1, and the averaged radiance pt_set_reference wants when read with samples = 1.  Three-channel "PF" files of
+ * either byte order. */
+int pt_load_pfm(const char* path, float* rgb_sum, int cap_pixels, int* w, int* h, float samples);
 /* image::saveHDR (src/image.cpp:41-45, stbi_write_hdr; main.cpp:106 keeps the call commented out) with saveImage()'s x
  * mirror and division by `samples`: Radiance RGBE, run-length coded, byte for byte what the reference's writer emits
  * (tests/golden/ref_hdr.json, made by the reference's image.cpp + stb.cpp compiled in place). */
