@@ -4,9 +4,8 @@
 // Second ring of a wave: cell records a ray came across, waiting for their leaf-box test.  Entry: record index << 10 |
 // direction the ray entered the cell from (0..5 = through its -x, +x, -y, +y, -z, +z face, 7 = first cell) << 7 |
 // group parity << 6 | owner lane.
-constexpr int kCellRing = 256;  // entries (power of two): what is left of a step (< 64) + what a step files (<= 192 at once)
 struct CellRing {
-  uint32_t* ent;  // [kCellRing]
+  uint32_t* ent;  // [kCellRing] (pt_lds.h)
   int head, count;
   float* rinv;    // [rinv_planes][64] reciprocal direction of each lane's ray in the mode's arithmetic (+ -o * that: fast)
 };
@@ -15,10 +14,17 @@ struct CellRing {
 // and, where the slab test has the FMA form t = plane * i + n (fast), n = -o * i as well, so that a record's test reads six
 // values and computes no reciprocal.  (Round 2 measured the stored reciprocals 34 % slower for the fast build of the kernel
 // as it was then; round 3, with the retirement and filing changes in: 3.4 % faster, `n` included 6 %.)
+struct GridRings {
+  Carry<false, 1> cy;  // with gix
+  CellRing cr;
+};
 template <bool EX>
-constexpr int rinv_planes() { return (EX || !kFast) ? 3 : 6; }
-template <bool EX>
-constexpr int grid_wave_bytes() { return carry_bytes<false, 1>() + kCellRing * 4 + kRing * 4 + rinv_planes<EX>() * 64 * 4; }  // Carry + cell ring + Carry::gix + CellRing::rinv
+PT_DEV GridRings grid_rings_init(char* base) {  // on a GridMap<kFast, EX>::bytes block
+  using M = GridMap<kFast, EX>;
+  GridRings g{carry_init<false, 1>(base), CellRing{reinterpret_cast<uint32_t*>(base + M::cells), 0, 0, reinterpret_cast<float*>(base + M::rinv)}};
+  g.cy.gix = reinterpret_cast<uint32_t*>(base + M::gix);
+  return g;
+}
 // Exclusive prefix sum over the wave of a small count per lane, and the total: a Hillis-Steele scan on the DPP network —
 // four row_shr steps scan each row of 16 lanes, row_bcast:15 / :31 carry the row totals over — six v_add_u32_dpp instead of
 // the six ballots + twelve mbcnt + six shift-adds of a bit-sliced count (round 2; the walk loop runs this once per cell step).
@@ -56,7 +62,7 @@ PT_DEV void grid_filter(Carry<false, NPAR>& c, CellRing& cr, int n, const SceneT
   f3 ro = mk(0.f, 0.f, 0.f);
   ri.ix = cr.rinv[0 * 64 + src], ri.iy = cr.rinv[1 * 64 + src], ri.iz = cr.rinv[2 * 64 + src];
   ri.sx = ri.ix < 0.0f, ri.sy = ri.iy < 0.0f, ri.sz = ri.iz < 0.0f;
-  if (rinv_planes<EX>() == 6) {  // FMA form: the origin itself is not needed
+  if (rinv_planes<kFast, EX>() == 6) {  // FMA form: the origin itself is not needed
     ri.nx = cr.rinv[3 * 64 + src], ri.ny = cr.rinv[4 * 64 + src], ri.nz = cr.rinv[5 * 64 + src];
   } else {
     const float* ray = c.ray + par * 6 * 64 + src;
@@ -152,7 +158,7 @@ PT_DEV void grid_search(Carry<false, NPAR>& c, CellRing& cr, const SceneTables& 
   {
     const RayInv ri = Ar<EX>::ray_inv(d, o);
     cr.rinv[0 * 64 + lane] = ri.ix, cr.rinv[1 * 64 + lane] = ri.iy, cr.rinv[2 * 64 + lane] = ri.iz;
-    if (rinv_planes<EX>() == 6) cr.rinv[3 * 64 + lane] = ri.nx, cr.rinv[4 * 64 + lane] = ri.ny, cr.rinv[5 * 64 + lane] = ri.nz;
+    if (rinv_planes<kFast, EX>() == 6) cr.rinv[3 * 64 + lane] = ri.nx, cr.rinv[4 * 64 + lane] = ri.ny, cr.rinv[5 * 64 + lane] = ri.nz;
   }
   CellWalk w;
   PT_STAT(0, 1);

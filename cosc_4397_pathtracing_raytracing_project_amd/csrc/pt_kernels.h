@@ -8,10 +8,8 @@ namespace ptk {
 
 constexpr int kBlock = 256;        // 4 wave64 per workgroup
 constexpr int kWavesPerBlock = 4;
-constexpr int kLdsTableBytes = 64 * 1024;  // upper limit for staging the scene tables in LDS (see auto_lds_table_limit)
+constexpr int kLdsTableBytes = 64 * 1024;  // upper limit for staging the scene tables in LDS (see KernelApi::lds_table_limit)
 constexpr int kMaxTop = ptd::kMaxTop;      // entries in the flattened BVH top (pt_device.h TopEntry)
-constexpr int kCandCap = 192;              // per-wave candidate list entries (LDS)
-constexpr int kWaveLds = 64 * 8 + 7 * 64 * 4 + kCandCap * 4;  // best keys + winner records + list = 3072 B
 
 struct SceneTables {
   const ptd::Node* nodes;  // threaded DFS order
@@ -32,7 +30,7 @@ struct SceneTables {
   // Near-first subtree order: byte k = XOR mask for rays whose direction sign bits are k = sx | sy << 1 | sz << 2
   // (pt_kernels.hip permute_xor); 0 when the top list is not a complete level of the tree.
   unsigned long long top_xor;
-  // Host-side decision (KernelApi::auto_lds_table_limit): nodes + geoms up to this many bytes are staged in LDS by
+  // Host-side decision (KernelApi::lds_table_limit): nodes + geoms up to this many bytes are staged in LDS by
   // the traversal kernels; -1: never.  Part of the tables so that several renderer contexts can differ.
   int32_t lds_table_bytes;
   // Iterations per wavefront batch of the context (>= every BatchInfo::K it launches): sizes the per-iteration RNG hash
@@ -151,7 +149,7 @@ struct KernelApi {
   // compiler's expansions on `count` operands starting at `first`; adds the number of mismatching results to *bad.
   void (*ieee_check)(hipStream_t s, int kind, unsigned long long first, unsigned long long count, uint32_t seed, unsigned long long* bad);
   // ALL depths >= 1 of a batch in ONE launch — persistent lanes with their own depth, a dead lane takes the next depth-1 ray of its
-  // queue, survivors never leave their registers (pt_kernels.hip k_paths; LDS-table scenes).  cnt = the counter rows [depth][Q]:
+  // queue, survivors never leave their registers (pt_kernels.hip k_paths; every search form, pt_lds.h Search).  cnt = the counter rows [depth][Q]:
   // row 1 is read (the queues' depth-1 rays), rows >= 2 receive the rays traced per depth.
   void (*paths)(hipStream_t s, int grid, const SceneTables& sc, const BatchInfo& b, const ptd::Queues& qs, int32_t* cnt, ptd::PathBuf in, ptd::RetireBuf ret);
   // `collect` with the convergence metric: additionally sse[iter_first + k - 1] = sum over the tile's pixels of the squared error of

@@ -36,6 +36,7 @@
 
 #include <type_traits>
 
+#include "pt_lds.h"
 #include "pt_portable_math.h"
 
 #ifndef PT_ARITH
@@ -223,13 +224,8 @@ struct MinStd {
 };
 // makeSeededRandomEngine (pathtrace.cu:203-207): seed = utilhash((1 << 31) | (depth << 22) | iter) ^ utilhash(index).
 // The first factor depends only on (iteration, depth): the kernels compute it once per iteration of the batch into
-// a small LDS table instead of once per ray (same values, ~18 VALU less per ray).
+// a small LDS table (pt_lds.h iter_hash_entries) instead of once per ray (same values, ~18 VALU less per ray).
 PT_DEV uint32_t iter_hash(int iter, int depth) { return utilhash((1u << 31) | ((uint32_t)depth << 22) | (uint32_t)iter); }
-constexpr int kIterHashMax = 256;  // most table entries (iterations per batch it covers; larger batches hash per ray)
-// LDS entries of the table: the context's iterations per batch (SceneTables::max_batch_iters), none beyond kIterHashMax
-__host__ __device__ inline int iter_hash_entries(const SceneTables& sc) {
-  return sc.max_batch_iters <= kIterHashMax ? (sc.max_batch_iters + 3) & ~3 : 0;
-}
 PT_DEV void iter_hash_fill(uint32_t* tab, const SceneTables& sc, const BatchInfo& b, int depth) {  // before the kernel's __syncthreads()
   if (iter_hash_entries(sc) > 0)
     for (int i = threadIdx.x; i < b.K; i += blockDim.x) tab[i] = iter_hash(b.iter_first + i, depth);
@@ -533,12 +529,13 @@ __global__ __launch_bounds__(kBlock) void k_intersect_legacy(SceneTables sc, ptd
   const ptd::Node* nodes = EX ? sc.nodes : sc.nodes_b;  // EX: primary rays, the reference's arithmetic on the reference's boxes; else the build's bounce tables
   const ptd::Geom* geoms = sc.geoms;
   if (TABLES_IN_LDS) {
-    char* base = reinterpret_cast<char*>(lds_raw);
-    stage16(base, nodes, sc.num_nodes * (int)sizeof(ptd::Node));
-    stage16(base + sc.num_nodes * sizeof(ptd::Node), sc.geoms, sc.num_geoms * (int)sizeof(ptd::Geom));
+    char* lds = reinterpret_cast<char*>(lds_raw);
+    const LegacyLds L = legacy_lds<TABLES_IN_LDS>(sc);
+    stage16(lds + L.nodes, nodes, node_bytes(sc));
+    stage16(lds + L.geoms, sc.geoms, geom_bytes(sc));
     __syncthreads();
-    nodes = reinterpret_cast<const ptd::Node*>(base);
-    geoms = reinterpret_cast<const ptd::Geom*>(base + sc.num_nodes * sizeof(ptd::Node));
+    nodes = reinterpret_cast<const ptd::Node*>(lds + L.nodes);
+    geoms = reinterpret_cast<const ptd::Geom*>(lds + L.geoms);
   }
   const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
   const int lane = lane_id();
@@ -583,6 +580,13 @@ struct WaveLds {
   float* rec;                // [7][64]: normal xyz, point xyz; row 6: donor table of the work-stealing step
   uint32_t* list;            // [kCandCap]: (leaf index << 6) | owner lane
 };
+PT_DEV WaveLds wave_lds_init(char* base) {  // on a WaveMap::bytes block
+  WaveLds w;
+  w.best = reinterpret_cast<unsigned long long*>(base + WaveMap::best);
+  w.rec = reinterpret_cast<float*>(base + WaveMap::rec);
+  w.list = reinterpret_cast<uint32_t*>(base + WaveMap::list);
+  return w;
+}
 constexpr unsigned long long kNoHit = ((unsigned long long)0x7f7fffffu << 32) | 0xffffffffull;  // t_min = FLT_MAX
 
 
@@ -781,31 +785,20 @@ __global__ __launch_bounds__(kBlock) void k_intersect(SceneTables sc, ptd::Queue
                                                       ptd::PathBuf paths, ptd::HitBuf hits) {
   extern __shared__ float4 lds_raw[];
   char* lds = reinterpret_cast<char*>(lds_raw);
-  // LDS map: [top list][nodes][geoms] (tables, if they fit) then one WaveLds block per wave
-  const int nb_top = sc.num_top * (int)sizeof(ptd::TopEntry);
-  stage16(lds, EX ? sc.top : sc.top_b, nb_top);  // EX: primary rays, the reference's arithmetic on the reference's boxes; else the build's bounce tables
-  const float4* top = reinterpret_cast<const float4*>(lds);
+  const IntersectLds L = intersect_lds<TABLES_IN_LDS>(sc);  // [top list][nodes][geoms] (tables, if they fit) then one WaveLds block per wave
+  stage16(lds + L.top, EX ? sc.top : sc.top_b, top_bytes(sc));  // EX: primary rays, the reference's arithmetic on the reference's boxes; else the build's bounce tables
+  const float4* top = reinterpret_cast<const float4*>(lds + L.top);
   const ptd::Node* nodes = EX ? sc.nodes : sc.nodes_b;
   const ptd::Geom* geoms = sc.geoms;
-  int tbl = nb_top;
   if (TABLES_IN_LDS) {
-    const int nb_nodes = sc.num_nodes * (int)sizeof(ptd::Node);
-    const int nb_geoms = sc.num_geoms * (int)sizeof(ptd::Geom);
-    stage16(lds + nb_top, nodes, nb_nodes);
-    stage16(lds + nb_top + nb_nodes, sc.geoms, nb_geoms);
-    nodes = reinterpret_cast<const ptd::Node*>(lds + nb_top);
-    geoms = reinterpret_cast<const ptd::Geom*>(lds + nb_top + nb_nodes);
-    tbl += nb_nodes + nb_geoms;
+    stage16(lds + L.nodes, nodes, node_bytes(sc));
+    stage16(lds + L.geoms, sc.geoms, geom_bytes(sc));
+    nodes = reinterpret_cast<const ptd::Node*>(lds + L.nodes);
+    geoms = reinterpret_cast<const ptd::Geom*>(lds + L.geoms);
   }
   __syncthreads();
   const int wib = threadIdx.x >> 6;
-  WaveLds w;
-  {
-    char* base = lds + tbl + wib * kWaveLds;
-    w.best = reinterpret_cast<unsigned long long*>(base);
-    w.rec = reinterpret_cast<float*>(base + 64 * 8);
-    w.list = reinterpret_cast<uint32_t*>(base + 64 * 8 + 7 * 64 * 4);
-  }
+  WaveLds w = wave_lds_init(lds + L.waves + wib * L.wave_bytes);
   const int ntop = sc.num_top;
 
   const int wave = blockIdx.x * kWavesPerBlock + wib;
@@ -858,13 +851,12 @@ __global__ __launch_bounds__(kBlock) void k_intersect(SceneTables sc, ptd::Queue
 // entry appended during its search has been processed (forced partial chunk only if the ring never
 // filled up in between).  Order of evaluation still does not matter: the (t, leaf) key minimum is the
 // reference's choice.
-constexpr int kRing = 128;  // ring entries per wave (power of two; <= 63 pending + <= 64 appended at once)
 // SMALL: the primary kernel's ring for LDS-table scenes (every leaf is one of <= 32 top entries, so leaf indices are < 64; every
 // ray starts at the camera): 16-bit ring entries, no work-stealing table, and only the rays' DIRECTIONS kept — 5888 B per
 // wave, which lets a fifth workgroup of k_primary fit a CU.
 // NPAR: 2 = keys / records / rays double-buffered by group parity (k_primary's ring: a group is shaded while the next one is
 // searched); 1 = one group at a time (k_paths modes 1 and 2, k_primary on the grid).
-template <bool SMALL, int NPAR = 2>
+template <bool SMALL, int NPAR>
 struct Carry {
   using Ent = typename std::conditional<SMALL, uint16_t, uint32_t>::type;
   unsigned long long* best;  // [NPAR][64]
@@ -881,19 +873,15 @@ struct Carry {
   const __attribute__((address_space(3))) v4f* lnodes;  // the threaded nodes in LDS (k_paths mode 1 on scenes of a few hundred nodes) when lds_nodes
   bool lds_nodes;
 };
-template <bool SMALL, int NPAR = 2>
-__host__ __device__ constexpr int carry_bytes() {
-  return NPAR * 64 * 8 + NPAR * 6 * 64 * 4 + kRing * (SMALL ? 2 : 4) + NPAR * (SMALL ? 3 : 6) * 64 * 4 + (SMALL ? 0 : 64 * 4);
-}
-template <bool SMALL, int NPAR = 2>
-PT_DEV Carry<SMALL, NPAR> carry_init(char* base) {
+template <bool SMALL, int NPAR>
+PT_DEV Carry<SMALL, NPAR> carry_init(char* base) {  // on a CarryMap<SMALL, NPAR>::bytes block
+  using M = CarryMap<SMALL, NPAR>;
   Carry<SMALL, NPAR> c;
-  c.best = reinterpret_cast<unsigned long long*>(base);
-  c.rec = reinterpret_cast<float*>(base + NPAR * 64 * 8);
-  c.ray = reinterpret_cast<float*>(base + NPAR * 64 * 8 + NPAR * 6 * 64 * 4);
-  constexpr int ray_bytes = NPAR * Carry<SMALL, NPAR>::kRayPlanes * 64 * 4;
-  c.ent = reinterpret_cast<typename Carry<SMALL, NPAR>::Ent*>(base + NPAR * 64 * 8 + NPAR * 6 * 64 * 4 + ray_bytes);
-  c.slot = reinterpret_cast<int*>(base + NPAR * 64 * 8 + NPAR * 6 * 64 * 4 + ray_bytes + kRing * 4);
+  c.best = reinterpret_cast<unsigned long long*>(base + M::best);
+  c.rec = reinterpret_cast<float*>(base + M::rec);
+  c.ray = reinterpret_cast<float*>(base + M::ray);
+  c.ent = reinterpret_cast<typename Carry<SMALL, NPAR>::Ent*>(base + M::ent);
+  c.slot = reinterpret_cast<int*>(base + M::slot);
   c.cam_o = mk(0.f, 0.f, 0.f);
   c.head = c.count = c.appended = c.processed = 0;
   c.gix = nullptr;
@@ -966,7 +954,7 @@ PT_DEV void carry_append(Carry<SMALL, NPAR>& c, bool pass, uint32_t leaf, int pa
 }
 // Candidate search of one group (phase 1 of trace_group) feeding the ring.
 // SUB: the scene has subtrees below the top list.  The LDS-table kernels are only used for scenes whose leaves all
-// fit the top list (auto_lds_table_limit), so their instantiation drops the subtree scan.
+// fit the top list (lds_table_limit), so their instantiation drops the subtree scan.
 // CAM (primary rays, !SUB only): `top` holds the boxes relative to the camera position (slab_rel), EX selects the
 // reference's exact arithmetic, and the chunks take the object-space origin from Carry::qo_tab.
 template <bool SUB, int NPAR, bool CAM = false, bool EX = false>
@@ -1036,7 +1024,7 @@ PT_DEV void carry_search(Carry<!SUB, NPAR>& c, const float4* top, int ntop, cons
     else if (pass) pend |= 1u << e;
   }
   // Subtrees below the cut (large scenes only): per-lane stackless scans, nearest subtree first, with work stealing
-  // (scan_next / steal_step); candidates are filed under the lane that owns the ray, so nothing downstream changes.
+  // (scan_step / steal_step); candidates are filed under the lane that owns the ray, so nothing downstream changes.
   if (SUB && ballot(pend != 0)) {
     Walker wk{0, 0, lane, o, ri};
     const uint32_t xm = octant_mask(ri, top_xor);
@@ -1084,47 +1072,40 @@ PT_DEV void carry_drain_to(Carry<SMALL, NPAR>& c, int mark, int lane, const ptd:
 // colour.  That removes the generate launch and ~190 B/sample of HBM round trips (40 B ray state
 // written + 24 B read, 32 B hit record written + read, 28 B path state re-read) at the one depth
 // where every sample is alive.  Also writes the per-queue sample counts of depth 0 (statistics).
-// GRID: large scenes with a uniform grid over the leaf boxes (SceneTables::use_grid): the primary rays walk it like the
+// kGrid: large scenes with a uniform grid over the leaf boxes (SceneTables::use_grid): the primary rays walk it like the
 // bounce rays do (grid_search) instead of testing the top list and scanning subtrees; exact arithmetic as in every depth-0 path.
-// RING (the LDS-table scenes, e.g. cornell.txt): the candidates go through the bounce kernel's ring with carry-over
+// kLdsTables (e.g. cornell.txt): the candidates go through the bounce kernel's ring with carry-over
 // (carry_search / carry_chunk), so that primitive tests only ever run as full 64-entry chunks — a group of primary rays
 // files ~85 candidates, which the per-group form (trace_group) ran as one full chunk plus one a third full — and the
-// appends run lane-major (two-phase search).  A group is shaded one loop iteration after its search, like in k_bounce.
+// appends run lane-major (two-phase search).  A group is shaded one loop iteration after its search.
 // Unlike the ring form tried in round 2 it keeps the camera-relative boxes and the per-geom object-space camera position.
-// Tables in memory, no grid: one wave-uniform scan of the threaded tree per group (trace_group_packet) instead of
+// kTopScan (tables in memory, no grid): one wave-uniform scan of the threaded tree per group (trace_group_packet) instead of
 // top list + per-lane subtree scans.
-template <bool TABLES_IN_LDS, bool GRID = false>
+template <Search F>
 __global__ __launch_bounds__(kBlock, kPrimaryWaves) void k_primary(SceneTables sc, ptd::Camera cam, BatchInfo b, ptd::Queues qs,
                                                     int32_t* __restrict__ cnt0, int32_t* __restrict__ cnt_out,
                                                     ptd::PathBuf out, ptd::RetireBuf ret) {
   extern __shared__ float4 lds_raw[];
   char* lds = reinterpret_cast<char*>(lds_raw);
-  static_assert(!(GRID && TABLES_IN_LDS), "the grid walk reads the tables from memory");
-  const int nb_top = GRID ? 0 : sc.num_top * (int)sizeof(ptd::TopEntry);
-  const int nb_mats = (sc.num_mats * (int)sizeof(ptd::Mat) + 15) & ~15;
-  stage16(lds, sc.top, nb_top);
-  stage16(lds + nb_top, sc.mats, nb_mats);
-  const ptd::Mat* mats = reinterpret_cast<const ptd::Mat*>(lds + nb_top);
+  constexpr bool GRID = F == kGrid, TABLES_IN_LDS = F == kLdsTables, RING = TABLES_IN_LDS;
+  const PrimaryLds L = primary_lds<F, kFast, kD0>(sc);
+  stage16(lds + L.top, sc.top, GRID ? 0 : top_bytes(sc));
+  stage16(lds + L.mats, sc.mats, mat_bytes(sc));
+  const ptd::Mat* mats = reinterpret_cast<const ptd::Mat*>(lds + L.mats);
   const ptd::Node* nodes = sc.nodes;
   const ptd::Geom* geoms = sc.geoms;
-  int tbl = nb_top + nb_mats;
   if (TABLES_IN_LDS) {
-    const int nb_nodes = sc.num_nodes * (int)sizeof(ptd::Node);
-    const int nb_geoms = sc.num_geoms * (int)sizeof(ptd::Geom);
-    stage16(lds + tbl, sc.nodes, nb_nodes);
-    stage16(lds + tbl + nb_nodes, sc.geoms, nb_geoms);
-    nodes = reinterpret_cast<const ptd::Node*>(lds + tbl);
-    geoms = reinterpret_cast<const ptd::Geom*>(lds + tbl + nb_nodes);
-    tbl += nb_nodes + nb_geoms;
+    stage16(lds + L.nodes, sc.nodes, node_bytes(sc));
+    stage16(lds + L.geoms, sc.geoms, geom_bytes(sc));
+    nodes = reinterpret_cast<const ptd::Node*>(lds + L.nodes);
+    geoms = reinterpret_cast<const ptd::Geom*>(lds + L.geoms);
   }
-  constexpr bool RING = TABLES_IN_LDS;  // (GRID reads the tables from memory)
-  constexpr int kWaveBytes = GRID ? grid_wave_bytes<kD0>() : (RING ? carry_bytes<true, 2>() : kWaveLds);
-  uint32_t* ihash = reinterpret_cast<uint32_t*>(lds + tbl + kWavesPerBlock * kWaveBytes);  // after the per-wave blocks
+  uint32_t* ihash = reinterpret_cast<uint32_t*>(lds + L.ihash);
   iter_hash_fill(ihash, sc, b, 0);
   // camera-relative copies for the primary rays: top-list boxes minus the camera position and (tables in LDS only)
   // the camera position in each geom's object space — the same float operations the per-ray code would execute
-  float4* cam_top = reinterpret_cast<float4*>(ihash + iter_hash_entries(sc));
-  float* cam_qo = reinterpret_cast<float*>(cam_top + 2 * sc.num_top);
+  float4* cam_top = reinterpret_cast<float4*>(lds + L.cam_top);
+  float* cam_qo = reinterpret_cast<float*>(lds + L.cam_qo);
   {
     const f3 cp = mk(cam.pos[0], cam.pos[1], cam.pos[2]);
     for (int e = threadIdx.x; !GRID && e < sc.num_top; e += blockDim.x) {
@@ -1139,21 +1120,13 @@ __global__ __launch_bounds__(kBlock, kPrimaryWaves) void k_primary(SceneTables s
   }
   __syncthreads();
   const int wib = threadIdx.x >> 6;
-  WaveLds w;
-  Carry<false, 1> cy = carry_init<false, 1>(lds + tbl + wib * kWaveBytes);  // GRID: the bounce kernel's rings
-  CellRing cr{reinterpret_cast<uint32_t*>(lds + tbl + wib * kWaveBytes + carry_bytes<false, 1>()), 0, 0, nullptr};
-  if (GRID) {
-    cy.gix = cr.ent + kCellRing;
-    cr.rinv = reinterpret_cast<float*>(cr.ent + kCellRing + kRing);
-    w.best = cy.best;
-    w.rec = cy.rec;
-    w.list = nullptr;
-  } else {
-    char* base = lds + tbl + wib * kWaveBytes;
-    w.best = reinterpret_cast<unsigned long long*>(base);
-    w.rec = reinterpret_cast<float*>(base + 64 * 8);
-    w.list = reinterpret_cast<uint32_t*>(base + 64 * 8 + 7 * 64 * 4);
-  }
+  // the form's per-wave state: the camera ring (kLdsTables), the bounce kernel's rings (kGrid) or one group's candidate list
+  char* wbase = lds + L.waves + wib * L.wave_bytes;
+  auto ws = [wbase] {
+    if constexpr (RING) return carry_init<true, 2>(wbase);
+    else if constexpr (GRID) return grid_rings_init<kD0>(wbase);
+    else return wave_lds_init(wbase);
+  }();
   const int ntop = sc.num_top;
   const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + wib);  // (the compiler cannot see that threadIdx.x >> 6 is wave-uniform)
   const int lane = lane_id();
@@ -1242,9 +1215,7 @@ __global__ __launch_bounds__(kBlock, kPrimaryWaves) void k_primary(SceneTables s
       bool any;
     } pp;
     pp.any = false;
-    Carry<true, 2> rc = carry_init<true, 2>(lds + tbl + wib * kWaveBytes);  // RING only (the same bytes as `w` otherwise)
-    rc.qo_tab = cam_qo;
-    rc.cam_o = o;
+    if constexpr (RING) ws = carry_init<true, 2>(wbase), ws.qo_tab = cam_qo, ws.cam_o = o;  // every strand starts with an empty ring
     int it = 0;
     for (int k = k0, rho = (r + k0) % wq; k < k1; ++k, rho = rho + 1 == wq ? 0 : rho + 1) {
       for (int jj = rho; jj < sh.my_nq; jj += wq, ++it) {
@@ -1264,31 +1235,29 @@ __global__ __launch_bounds__(kBlock, kPrimaryWaves) void k_primary(SceneTables s
                                                        sc.root_max[0], sc.root_max[1], sc.root_max[2])) != 0;
         if constexpr (RING) {
           const int par = it & 1;
-          rc.best[par * 64 + lane] = kNoHit;
-          if (near_scene) carry_search<false, 2, true, kD0>(rc, cam_top, ntop, nodes, geoms, o, d, valid, lane, par, sc.cull_margin, sc.top_xor);
-          if (pp.any) carry_drain_to<true, 2, kD0, true>(rc, pp.mark, lane, nodes, geoms);  // the previous group's candidates are now all resolved
-          if (pp.any) shade_group(rc.best[pp.par * 64 + lane], rc.rec + pp.par * 6 * 64 + lane, pp.valid, pp.k, pp.pl, pp.slot, pp.phash, pp.d);
-          pp.d = d, pp.k = k, pp.pl = pl, pp.slot = slot, pp.phash = phash, pp.valid = valid, pp.par = par, pp.mark = rc.appended, pp.any = true;
-        } else {
-          if (GRID) {
-            w.best[lane] = kNoHit;
-            if (near_scene) {
-              grid_search<1, kD0>(cy, cr, sc, nodes, geoms, o, d, valid, lane, 0);
-              while (cy.count > 0) carry_chunk<false, 1, kD0, true>(cy, min(64, cy.count), lane, nodes, geoms);
-            }
-          } else if (near_scene) {
-            trace_group_packet<kD0>(w, nodes, sc.num_nodes, geoms, o, d, valid, lane, sc.has_triangles != 0);
-          } else {
-            w.best[lane] = kNoHit;
+          ws.best[par * 64 + lane] = kNoHit;
+          if (near_scene) carry_search<false, 2, true, kD0>(ws, cam_top, ntop, nodes, geoms, o, d, valid, lane, par, sc.cull_margin, sc.top_xor);
+          if (pp.any) carry_drain_to<true, 2, kD0, true>(ws, pp.mark, lane, nodes, geoms);  // the previous group's candidates are now all resolved
+          if (pp.any) shade_group(ws.best[pp.par * 64 + lane], ws.rec + pp.par * 6 * 64 + lane, pp.valid, pp.k, pp.pl, pp.slot, pp.phash, pp.d);
+          pp.d = d, pp.k = k, pp.pl = pl, pp.slot = slot, pp.phash = phash, pp.valid = valid, pp.par = par, pp.mark = ws.appended, pp.any = true;
+        } else if constexpr (GRID) {
+          ws.cy.best[lane] = kNoHit;
+          if (near_scene) {
+            grid_search<1, kD0>(ws.cy, ws.cr, sc, nodes, geoms, o, d, valid, lane, 0);
+            while (ws.cy.count > 0) carry_chunk<false, 1, kD0, true>(ws.cy, min(64, ws.cy.count), lane, nodes, geoms);
           }
-          shade_group(w.best[lane], w.rec + lane, valid, k, pl, slot, phash, d);
+          shade_group(ws.cy.best[lane], ws.cy.rec + lane, valid, k, pl, slot, phash, d);
+        } else {
+          if (near_scene) trace_group_packet<kD0>(ws, nodes, sc.num_nodes, geoms, o, d, valid, lane, sc.has_triangles != 0);
+          else ws.best[lane] = kNoHit;
+          shade_group(ws.best[lane], ws.rec + lane, valid, k, pl, slot, phash, d);
         }
       }
     }
     if constexpr (RING) {
       if (pp.any) {
-        carry_drain_to<true, 2, kD0, true>(rc, pp.mark, lane, nodes, geoms);
-        shade_group(rc.best[pp.par * 64 + lane], rc.rec + pp.par * 6 * 64 + lane, pp.valid, pp.k, pp.pl, pp.slot, pp.phash, pp.d);
+        carry_drain_to<true, 2, kD0, true>(ws, pp.mark, lane, nodes, geoms);
+        shade_group(ws.best[pp.par * 64 + lane], ws.rec + pp.par * 6 * 64 + lane, pp.valid, pp.k, pp.pl, pp.slot, pp.phash, pp.d);
       }
     }
     if (!b.flat)
@@ -1323,11 +1292,10 @@ __global__ __launch_bounds__(kBlock, kPrimaryWaves) void k_primary(SceneTables s
 //     stay in its registers until then).
 constexpr int kPathsWaves = 6;
 constexpr int kPathsMinReady = 32;  // fewer resolved lanes than this and candidates pending: run the partial chunk instead of shading a thin group
-constexpr int kSlotBytes = 64 * 16 + 64 * 16 + 64 * 4 + 64 * 4 + 64 * 4;  // planes 0, 1 (16 B per lane), colour.z, sample id, record slot
 PT_DEV uint32_t lds_offset(const void* p) { return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)p; }
 // memory -> LDS without passing through VGPRs: path record i of a queue (b0 / b1 / b2 = the queue's first record in planes 0,
 // 1, 2; wave-uniform, so they are scalar bases and a lane supplies 32-bit byte offsets only) of every active lane to lds_base
-// (wave-uniform) + {0, 1024} + lane * 16 (planes 0 and 1) and + {2048, 2304} + lane * 4 (colour.z, sample id).  The
+// (wave-uniform) + {0, 1024} + lane * 16 (planes 0 and 1) and + {2048, 2304} + lane * 4 (colour.z, sample id; pt_lds.h kSlotTail).  The
 // instruction's immediate offset moves BOTH addresses, hence M0 + 0xfc for the last transfer.  M0 (the transfers' LDS base)
 // belongs to the compiler: saved and restored.
 template <typename T>
@@ -1369,7 +1337,14 @@ struct Lanes {
   int head, count;           // wave-uniform
   int appended, processed;   // running totals (wave-uniform)
 };
-constexpr int kLanesBytes = 64 * 8 + 6 * 64 * 4 + kRing * 2;
+PT_DEV Lanes lanes_init(char* base) {  // on a LanesMap::bytes block
+  Lanes c;
+  c.best = reinterpret_cast<unsigned long long*>(base + LanesMap::best);
+  c.rec = reinterpret_cast<float*>(base + LanesMap::rec);
+  c.ent = reinterpret_cast<uint16_t*>(base + LanesMap::ent);
+  c.head = c.count = c.appended = c.processed = 0;
+  return c;
+}
 // Primitive tests for the first n (<= 64) pending entries; wave-uniform control flow, all 64 lanes active.
 PT_DEV void paths_chunk(Lanes& c, int n, int lane, f3 o, f3 d, const uint32_t* tword, const ptd::Geom* __restrict__ geoms) {
   const bool valid = lane < n;
@@ -1442,9 +1417,9 @@ PT_DEV void paths_search(Lanes& c, TOP* top, const uint32_t* tword, int ntop, co
     if (c.count >= 64) paths_chunk(c, 64, lane, o, d, tword, geoms);
   }
 }
-// MODE 0: scene tables in LDS, every leaf a top entry (cornell.txt: the form described above).
-// MODE 1: tables in memory, top list + per-lane subtree scans with work stealing (carry_search<true>);
-// MODE 2: tables in memory, uniform grid walk (grid_search).  Modes 1 and 2 run every pending candidate before they shade
+// kLdsTables (mode 0): scene tables in LDS, every leaf a top entry (cornell.txt: the form described above).
+// kTopScan (mode 1): tables in memory, top list + per-lane subtree scans with work stealing (carry_search<true>);
+// kGrid (mode 2): tables in memory, uniform grid walk (grid_search).  Modes 1 and 2 run every pending candidate before they shade
 //         (a search of theirs files several chunks' worth, and stolen work files candidates under other lanes' names, so a
 //         per-lane mark would need cross-lane bookkeeping): all live lanes are searched and shaded in every round.
 //         The grid walk's rings leave no LDS for refill slots (three workgroups per CU with them: measured 17-22 % slower than
@@ -1457,48 +1432,35 @@ constexpr int kPathsScanWaves = 5, kPathsGridWaves = 5;
 // k_paths' visit ring (fillc): one record counter per sub-list visit of the cursor, kVisitRing per wave, taken modulo the ring.
 // A refill starts only while every path in flight was taken fewer than kVisitLap visits ago; it makes at most kVisitsPerRefill
 // new visits and the seek of a new piece one more, so no counter of a path in flight is handed to another visit.
-constexpr int kVisitRing = 64, kVisitLap = 32, kVisitsPerRefill = 31;
+constexpr int kVisitLap = 32, kVisitsPerRefill = 31;
 static_assert(kVisitLap + kVisitsPerRefill + 1 <= kVisitRing, "the visit ring laps a path in flight");
 static_assert((kVisitRing & (kVisitRing - 1)) == 0, "visit numbers wrap with a mask");
-template <int MODE>
-constexpr int paths_extra_bytes() { return (MODE == 0 ? kSlotBytes : 0) + 64 * 4 + kVisitRing * 4; }  // refill slots (mode 0) + 64 counters: paths retired per depth + the visit ring
-template <int MODE>
-constexpr int paths_wave_bytes() {
-  return (MODE == 0 ? kLanesBytes : MODE == 1 ? carry_bytes<false, 1>() : grid_wave_bytes<false>()) + paths_extra_bytes<MODE>();
-}
-template <int MODE>
+template <Search MODE>
 __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPathsScanWaves : kPathsGridWaves) void k_paths(SceneTables sc, BatchInfo b, ptd::Queues qs, int32_t* __restrict__ cnt /* [depth][Q] rows */,
                                                                ptd::PathBuf in, ptd::RetireBuf ret) {
   extern __shared__ float4 lds_raw[];
   char* lds = reinterpret_cast<char*>(lds_raw);
-  const int nb_top = MODE == 2 ? 0 : sc.num_top * (int)sizeof(ptd::TopEntry);  // the grid walk replaces top list and subtrees
-  const int nb_mats = (sc.num_mats * (int)sizeof(ptd::Mat) + 15) & ~15;
-  stage16(lds, sc.top_b, nb_top);  // the bounce kernels' box tables (SceneTables::*_b)
-  stage16(lds + nb_top, sc.mats, nb_mats);
-  const float4* top = reinterpret_cast<const float4*>(lds);
-  const ptd::Mat* mats = reinterpret_cast<const ptd::Mat*>(lds + nb_top);
-  int tbl = nb_top + nb_mats;
+  const PathsLds L = paths_lds<MODE, kFast>(sc);
+  stage16(lds + L.top, sc.top_b, MODE == 2 ? 0 : top_bytes(sc));  // the bounce kernels' box tables (SceneTables::*_b); the grid walk replaces top list and subtrees
+  stage16(lds + L.mats, sc.mats, mat_bytes(sc));
+  const float4* top = reinterpret_cast<const float4*>(lds + L.top);
+  const ptd::Mat* mats = reinterpret_cast<const ptd::Mat*>(lds + L.mats);
   const ptd::Node* nodes = sc.nodes_b;
   const ptd::Geom* geoms = sc.geoms;
   if (MODE == 0) {  // the geometry records; of the nodes only tword / lmat below are needed (every leaf is a top entry)
-    const int nb_geoms = sc.num_geoms * (int)sizeof(ptd::Geom);
-    stage16(lds + tbl, sc.geoms, nb_geoms);
-    geoms = reinterpret_cast<const ptd::Geom*>(lds + tbl);
-    tbl += nb_geoms;
+    stage16(lds + L.geoms, sc.geoms, geom_bytes(sc));
+    geoms = reinterpret_cast<const ptd::Geom*>(lds + L.geoms);
   }
   const char* lnodes = nullptr;
   if (MODE == 1 && sc.scan_nodes_lds > 0) {
-    const int nb_nodes = sc.num_nodes * (int)sizeof(ptd::Node);
-    stage16(lds + tbl, sc.nodes_b, nb_nodes);
-    lnodes = lds + tbl;
-    tbl += nb_nodes;
+    stage16(lds + L.nodes, sc.nodes_b, node_bytes(sc));
+    lnodes = lds + L.nodes;
   }
-  constexpr int wave_bytes = paths_wave_bytes<MODE>();
-  constexpr int core_bytes = wave_bytes - paths_extra_bytes<MODE>();
+  using WM = PathsWaveMap<MODE, kFast>;
   const int he = iter_hash_entries(sc);
-  uint32_t* tword = reinterpret_cast<uint32_t*>(lds + tbl + kWavesPerBlock * wave_bytes);  // MODE 0: [kMaxTop] leaf | geom << 8 per top entry
-  int* lmat = reinterpret_cast<int*>(tword + (MODE == 0 ? kMaxTop : 0));                    // MODE 0: [64] material of the leaf at threaded node index i
-  uint32_t* ihash = reinterpret_cast<uint32_t*>(lmat + (MODE == 0 ? 64 : 0));               // rows of the depths 1 .. trace_depth - 1
+  uint32_t* tword = reinterpret_cast<uint32_t*>(lds + L.tword);  // MODE 0: [kMaxTop] leaf | geom << 8 per top entry
+  int* lmat = reinterpret_cast<int*>(lds + L.lmat);              // MODE 0: [64] material of the leaf at threaded node index i
+  uint32_t* ihash = reinterpret_cast<uint32_t*>(lds + L.ihash);  // rows of the depths 1 .. trace_depth - 1
   for (int d = 1; d < b.trace_depth; ++d) iter_hash_fill(ihash + (d - 1) * he, sc, b, d);
   for (int e = threadIdx.x; MODE == 0 && e < sc.num_top; e += blockDim.x) {
     const int leaf = sc.top[e].idx, gi = sc.nodes[leaf].geom;
@@ -1507,20 +1469,16 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
   }
   __syncthreads();
   const int wib = threadIdx.x >> 6;
-  char* wbase = lds + tbl + wib * wave_bytes;
-  Lanes cy;  // MODE 0
-  cy.best = reinterpret_cast<unsigned long long*>(wbase);
-  cy.rec = reinterpret_cast<float*>(wbase + 64 * 8);
-  cy.ent = reinterpret_cast<uint16_t*>(wbase + 64 * 8 + 6 * 64 * 4);
-  cy.head = cy.count = cy.appended = cy.processed = 0;
-  Carry<false, 1> cb = carry_init<false, 1>(wbase);  // MODES 1, 2 (the same bytes)
-  CellRing cr{reinterpret_cast<uint32_t*>(wbase + carry_bytes<false, 1>()), 0, 0, nullptr};
-  if (MODE == 2) cb.gix = cr.ent + kCellRing, cr.rinv = reinterpret_cast<float*>(cr.ent + kCellRing + kRing);
+  char* wbase = lds + L.waves + wib * L.wave_bytes;
+  Lanes cy = lanes_init(wbase);  // MODE 0; its keys and records are where the other modes' Carry has them
+  GridRings gr = grid_rings_init<false>(wbase);  // MODES 1, 2 (the same bytes; mode 1 uses the Carry alone)
+  Carry<false, 1>& cb = gr.cy;
+  CellRing& cr = gr.cr;
   cb.lnodes = (const __attribute__((address_space(3))) v4f*)(lnodes ? lnodes : lds), cb.lds_nodes = lnodes != nullptr;
   constexpr bool SLOTS = MODE == 0;
-  char* slots = wbase + core_bytes;  // SLOTS: [64] x 16 B, [64] x 16 B, [64] x 4 B, [64] x 4 B
-  int* died = reinterpret_cast<int*>(slots + (SLOTS ? kSlotBytes : 0));  // [64]: paths of this wave retired AT depth d (statistics; PT_MAX_DEPTH = 64)
-  int* fillc = died + 64;                                                 // [kVisitRing]: next record slot per sub-list visit
+  char* slots = wbase + WM::slots;  // SLOTS: [64] x 16 B, [64] x 16 B, [64] x 4 B, [64] x 4 B, [64] x 4 B
+  int* died = reinterpret_cast<int*>(wbase + WM::died);    // [64]: paths of this wave retired AT depth d (statistics; PT_MAX_DEPTH = 64)
+  int* fillc = reinterpret_cast<int*>(wbase + WM::fillc);  // [kVisitRing]: next record slot per sub-list visit
   const int ntop = sc.num_top;
   const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + wib);  // (the compiler cannot see that threadIdx.x >> 6 is wave-uniform)
   const int lane = lane_id();
@@ -1667,14 +1625,14 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
     return want && !pending;
   };
   const uint32_t s_base = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_offset(slots));
-  const uint32_t s16 = s_base + (uint32_t)lane * 16u, s4 = s_base + 2048u + (uint32_t)lane * 4u;
+  const uint32_t s16 = s_base + (uint32_t)lane * 16u, s4 = s_base + (uint32_t)kSlotTail + (uint32_t)lane * 4u;
   // issue the transfer of path record `i` of the queue into this lane's slot
   const ptd::Word4 *in0 = uniform_ptr(in.r + qbase), *in1 = uniform_ptr(in.r + in.stride + qbase);
   const float* in2 = uniform_ptr(reinterpret_cast<const float*>(in.r + 2 * in.stride) + 2 * qbase);
   PathRec nx;  // !SLOTS: the lane's next record, in registers
   nx.o = nx.d = nx.c = mk(0.f, 0.f, 0.f), nx.tag = PathTag{0, 0u, 0};
   int nx_rs = 0;  // !SLOTS: ... and its visit
-  int* slot_rs = reinterpret_cast<int*>(slots + 2560) + lane;  // SLOTS: the visit of the record waiting in the lane's slot
+  int* slot_rs = reinterpret_cast<int*>(slots + kSlotVisit) + lane;  // SLOTS: the visit of the record waiting in the lane's slot
   auto fetch = [&](int at, int rs) {
     if constexpr (SLOTS) fetch_record_to_lds(in0, in1, in2, at, s_base), *slot_rs = rs;
     else nx = path_load(in, qbase + at), nx_rs = rs;
@@ -1858,9 +1816,11 @@ __global__ __launch_bounds__(kBlock) void k_shade_stage(SceneTables sc, int trac
                                                         const int32_t* __restrict__ pixel, ptd::HitBuf hits,
                                                         ptd::PathBuf paths, int32_t* __restrict__ alive) {
   extern __shared__ float4 lds_raw[];
-  stage16(lds_raw, sc.mats, sc.num_mats * (int)sizeof(ptd::Mat));
+  char* lds = reinterpret_cast<char*>(lds_raw);
+  const ShadeLds L = shade_lds<false>(sc);
+  stage16(lds + L.mats, sc.mats, mat_bytes(sc));
   __syncthreads();
-  const ptd::Mat* mats = reinterpret_cast<const ptd::Mat*>(lds_raw);
+  const ptd::Mat* mats = reinterpret_cast<const ptd::Mat*>(lds + L.mats);
   const int64_t HS = hits.stride;
   for (int at = blockIdx.x * blockDim.x + threadIdx.x; at < n; at += gridDim.x * blockDim.x) {
     const PathRec pr = path_load(paths, at);

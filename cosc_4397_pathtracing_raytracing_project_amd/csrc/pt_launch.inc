@@ -1,18 +1,42 @@
-// pt_launch.inc — LDS sizing, residency queries and launch wrappers behind ptk::KernelApi.
+// pt_launch.inc — kernel selection, residency queries and launch wrappers behind ptk::KernelApi (LDS sizes: pt_lds.h).
 // Included by pt_kernels.hip inside ptk::<arith>::(anonymous), after every kernel.
 // ───────────────────────────── launch wrappers ─────────────────────────────
-int fused_lds_bytes(const SceneTables& sc, bool in_lds, int wave_lds, bool primary = false) {
-  int bytes = sc.num_top * (int)sizeof(ptd::TopEntry) + round16(sc.num_mats * (int)sizeof(ptd::Mat)) + kWavesPerBlock * wave_lds + iter_hash_entries(sc) * 4;
-  if (in_lds) bytes += round16(sc.num_nodes * (int)sizeof(ptd::Node) + sc.num_geoms * (int)sizeof(ptd::Geom));
-  if (primary) bytes += sc.num_top * (int)sizeof(ptd::TopEntry) + (in_lds ? round16(sc.num_geoms * 12) : 0);  // camera-relative copies
+// One selector per kernel family: hands `f` the kernel instance that runs `sc` and the dynamic LDS it needs (pt_lds.h).  The
+// occupancy queries and the launches both go through it — a persistent grid is only right when both name the same
+// instance with the same byte count.
+template <bool EX, typename F>
+void with_intersect_of(const SceneTables& sc, bool legacy, F&& f) {
+  const bool in_lds = tables_in_lds(sc);
+  if (legacy) in_lds ? f(k_intersect_legacy<true, EX>, legacy_lds<true>(sc).total) : f(k_intersect_legacy<false, EX>, legacy_lds<false>(sc).total);
+  else in_lds ? f(k_intersect<true, EX>, intersect_lds<true>(sc).total) : f(k_intersect<false, EX>, intersect_lds<false>(sc).total);
+}
+// exact: the rays are primary rays (depth 0), traced with the reference's exact arithmetic in every mode
+template <typename F>
+void with_intersect(const SceneTables& sc, bool legacy, bool exact, F&& f) {
+  exact ? with_intersect_of<kD0>(sc, legacy, f) : with_intersect_of<false>(sc, legacy, f);
+}
+template <typename F>
+void with_primary(const SceneTables& sc, F&& f) {
+  switch (search_form(sc)) {
+    case kLdsTables: return f(k_primary<kLdsTables>, primary_lds<kLdsTables, kFast, kD0>(sc).total);
+    case kTopScan: return f(k_primary<kTopScan>, primary_lds<kTopScan, kFast, kD0>(sc).total);
+    case kGrid: return f(k_primary<kGrid>, primary_lds<kGrid, kFast, kD0>(sc).total);
+  }
+}
+template <typename F>
+void with_paths(const SceneTables& sc, Search form, F&& f) {  // (SceneTables::scan_nodes_lds resolved by the caller)
+  switch (form) {
+    case kLdsTables: return f(k_paths<kLdsTables>, paths_lds<kLdsTables, kFast>(sc).total);
+    case kTopScan: return f(k_paths<kTopScan>, paths_lds<kTopScan, kFast>(sc).total);
+    case kGrid: return f(k_paths<kGrid>, paths_lds<kGrid, kFast>(sc).total);
+  }
+}
+int paths_lds_bytes(const SceneTables& sc, Search form) {
+  int bytes = 0;
+  with_paths(sc, form, [&](auto, int lds) { bytes = lds; });
   return bytes;
 }
-int table_bytes(const SceneTables& sc) { return sc.num_nodes * (int)sizeof(ptd::Node) + sc.num_geoms * (int)sizeof(ptd::Geom); }
-bool tables_in_lds(const SceneTables& sc) { return table_bytes(sc) <= sc.lds_table_bytes; }
-// k_paths' search form: 2 = uniform grid walk, 0 = scene tables in LDS (every leaf a top entry), 1 = top list + subtree scans
-int paths_mode(const SceneTables& sc) { return sc.use_grid ? 2 : (tables_in_lds(sc) ? 0 : 1); }
 int lds_share_limit(int bytes);
-int paths_lds_bytes(const SceneTables& sc, int mode);
 // SceneTables::scan_nodes_lds == -1 resolved: the nodes go to LDS when the scan form's workgroups per CU (LDS share) stay the same
 SceneTables resolve_scan_nodes(const SceneTables& sc_in) {
   SceneTables sc = sc_in;
@@ -22,32 +46,26 @@ SceneTables resolve_scan_nodes(const SceneTables& sc_in) {
   if (iter_hash_entries(sc) > 0) {
     SceneTables without = sc;
     without.max_batch_iters = kIterHashMax + 1;
-    const int mode = paths_mode(sc);
-    const int reg_waves = mode == 0 ? kPathsWaves : mode == 1 ? kPathsScanWaves : kPathsGridWaves;
+    const Search form = search_form(sc);
+    const int reg_waves = form == kLdsTables ? kPathsWaves : form == kTopScan ? kPathsScanWaves : kPathsGridWaves;
     SceneTables a = sc, b = without;
     if (a.scan_nodes_lds < 0) a.scan_nodes_lds = b.scan_nodes_lds = 0;
-    const bool costs = min(lds_share_limit(paths_lds_bytes(b, mode)), reg_waves) > min(lds_share_limit(paths_lds_bytes(a, mode)), reg_waves);
+    const bool costs = min(lds_share_limit(paths_lds_bytes(b, form)), reg_waves) > min(lds_share_limit(paths_lds_bytes(a, form)), reg_waves);
     if (costs) sc = without;
   }
   SceneTables t = sc;
   if (t.scan_nodes_lds >= 0) return t;
   SceneTables with = sc, without = sc;
   with.scan_nodes_lds = 1, without.scan_nodes_lds = 0;
-  const int bw = paths_lds_bytes(with, 1), bo = paths_lds_bytes(without, 1);
+  const int bw = paths_lds_bytes(with, kTopScan), bo = paths_lds_bytes(without, kTopScan);
   t.scan_nodes_lds = (bw <= 64 * 1024 && lds_share_limit(bw) >= min(lds_share_limit(bo), kPathsScanWaves)) ? 1 : 0;  // (registers allow kPathsScanWaves workgroups per CU)
   return t;
 }
-int paths_lds_bytes(const SceneTables& sc, int mode) {
-  const int rows = iter_hash_entries(sc) * 4 * max(0, sc.trace_depth - 1), common = round16(sc.num_mats * (int)sizeof(ptd::Mat)) + rows;
-  const int top = sc.num_top * (int)sizeof(ptd::TopEntry);
-  switch (mode) {
-    case 0: return common + top + sc.num_geoms * (int)sizeof(ptd::Geom) + kWavesPerBlock * paths_wave_bytes<0>() + kMaxTop * 4 + 64 * 4;
-    case 1: return common + top + kWavesPerBlock * paths_wave_bytes<1>() + (sc.scan_nodes_lds > 0 ? sc.num_nodes * (int)sizeof(ptd::Node) : 0);
-    default: return common + kWavesPerBlock * paths_wave_bytes<2>();
-  }
-}
-int primary_grid_lds_bytes(const SceneTables& sc) {
-  return round16(sc.num_mats * (int)sizeof(ptd::Mat)) + kWavesPerBlock * grid_wave_bytes<kD0>() + iter_hash_entries(sc) * 4;
+// Resident workgroups per CU by the runtime's count, for a selector's callback; `fallback` when the query fails.
+auto occupancy_into(int& n, int fallback) {
+  return [&n, fallback](auto kernel, int lds) {
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, kBlock, lds) != hipSuccess) n = fallback;
+  };
 }
 // The LDS-table kernel variants assume that every leaf is a top-list entry (no subtrees).
 bool leaves_fit_top(const SceneTables& sc) { return (sc.num_nodes + 1) / 2 <= kMaxTop; }
@@ -60,9 +78,9 @@ int lds_table_limit(const SceneTables& sc, int forced_bytes) {
   if (tbl <= kLdsTableBytes && leaves_fit_top(sc)) {
     SceneTables in = sc;
     in.lds_table_bytes = tbl;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&with, k_paths<0>, kBlock, paths_lds_bytes(in, 0)) != hipSuccess) with = 0;
+    with_paths(in, kLdsTables, occupancy_into(with, 0));
   }
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&without, k_paths<1>, kBlock, paths_lds_bytes(sc, 1)) != hipSuccess) without = 1;
+  with_paths(sc, kTopScan, occupancy_into(without, 1));
   (void)hipGetLastError();
   return (with >= without && with > 0) ? tbl : -1;
 }
@@ -73,40 +91,18 @@ int lds_table_limit(const SceneTables& sc, int forced_bytes) {
 constexpr int kLdsGranule = 1280;
 int lds_share_limit(int bytes) { return bytes > 0 ? (160 * 1024) / (((bytes + kLdsGranule - 1) / kLdsGranule) * kLdsGranule) : 8; }
 int resident_blocks_per_cu(KernelId id, const SceneTables& sc) {
-  int n = 0, lds = 0;
-  hipError_t e = hipSuccess;
-  const int tbl = table_bytes(sc);
-  const bool in_lds = tables_in_lds(sc);
+  int n = 0, lds = 0;  // lds: the fused kernels' blocks are also held to their granule share of the CU's LDS
+  const auto query = occupancy_into(n, 1);
+  const auto query_share = [&](auto kernel, int bytes) { query(kernel, bytes), lds = bytes; };
   switch (id) {
-    case kGenerate:
-      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_generate, kBlock, 0);
-      break;
-    case kIntersect:
-      if (in_lds)
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_intersect<true, false>, kBlock, round16(tbl) + kWavesPerBlock * kWaveLds + sc.num_top * (int)sizeof(ptd::TopEntry));
-      else
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_intersect<false, false>, kBlock, kWavesPerBlock * kWaveLds + sc.num_top * (int)sizeof(ptd::TopEntry));
-      break;
-    case kIntersectLegacy:
-      if (in_lds) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_intersect_legacy<true, false>, kBlock, round16(tbl));
-      else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_intersect_legacy<false, false>, kBlock, 0);
-      break;
-    case kPrimary:
-      if (sc.use_grid) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_primary<false, true>, kBlock, lds = primary_grid_lds_bytes(sc));
-      else if (in_lds) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_primary<true>, kBlock, lds = fused_lds_bytes(sc, true, carry_bytes<true>(), true));
-      else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_primary<false>, kBlock, lds = fused_lds_bytes(sc, false, kWaveLds, true));
-      break;
-    case kPaths:
-      lds = paths_lds_bytes(resolve_scan_nodes(sc), paths_mode(sc));
-      if (paths_mode(sc) == 0) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_paths<0>, kBlock, lds);
-      else if (paths_mode(sc) == 1) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_paths<1>, kBlock, lds);
-      else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_paths<2>, kBlock, lds);
-      break;
-    case kShade:
-      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_shade, kBlock, round16(sc.num_mats * (int)sizeof(ptd::Mat)) + iter_hash_entries(sc) * 4);
-      break;
+    case kGenerate: query(k_generate, 0); break;
+    case kIntersect: with_intersect(sc, false, false, query); break;
+    case kIntersectLegacy: with_intersect(sc, true, false, query); break;
+    case kPrimary: with_primary(sc, query_share); break;
+    case kPaths: with_paths(resolve_scan_nodes(sc), search_form(sc), query_share); break;
+    case kShade: query(k_shade, shade_lds<true>(sc).total); break;
   }
-  if (e != hipSuccess || n < 1) n = 1;
+  if (n < 1) n = 1;
   n = min(n, max(1, lds_share_limit(lds)));
   return n > 8 ? 8 : n;
 }
@@ -116,44 +112,24 @@ void launch_generate(hipStream_t s, int grid, const ptd::Camera& cam, const Batc
   hipLaunchKernelGGL(k_generate, dim3(grid), dim3(kBlock), 0, s, cam, b, qs, out, cnt0);
 }
 
-// exact_arith: the rays are primary rays (depth 0), traced with the reference's exact arithmetic in every mode
 void launch_intersect(hipStream_t s, int grid, const SceneTables& sc, const ptd::Queues& qs, const int32_t* cnt_in,
                       ptd::PathBuf paths, ptd::HitBuf hits, bool legacy, bool exact_arith) {
-  const int bytes = table_bytes(sc);
-  const bool in_lds = tables_in_lds(sc);
-  const bool ex = kD0 && exact_arith;
-  const int wave_lds = kWavesPerBlock * kWaveLds + sc.num_top * (int)sizeof(ptd::TopEntry);
-  const int lds = legacy ? (in_lds ? round16(bytes) : 0) : (in_lds ? round16(bytes) : 0) + wave_lds;
-#define PT_LAUNCH_ISECT(K) hipLaunchKernelGGL(K, dim3(grid), dim3(kBlock), lds, s, sc, qs, cnt_in, paths, hits)
-  if (legacy) {
-    if (in_lds) { if (ex) PT_LAUNCH_ISECT((k_intersect_legacy<true, kD0>)); else PT_LAUNCH_ISECT((k_intersect_legacy<true, false>)); }
-    else { if (ex) PT_LAUNCH_ISECT((k_intersect_legacy<false, kD0>)); else PT_LAUNCH_ISECT((k_intersect_legacy<false, false>)); }
-  } else {
-    if (in_lds) { if (ex) PT_LAUNCH_ISECT((k_intersect<true, kD0>)); else PT_LAUNCH_ISECT((k_intersect<true, false>)); }
-    else { if (ex) PT_LAUNCH_ISECT((k_intersect<false, kD0>)); else PT_LAUNCH_ISECT((k_intersect<false, false>)); }
-  }
-#undef PT_LAUNCH_ISECT
+  with_intersect(sc, legacy, exact_arith, [&](auto kernel, int lds) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, sc, qs, cnt_in, paths, hits); });
 }
 
 void launch_primary(hipStream_t s, int grid, const SceneTables& sc, const ptd::Camera& cam, const BatchInfo& b,
                     const ptd::Queues& qs, int32_t* cnt0, int32_t* cnt_out, ptd::PathBuf out, ptd::RetireBuf ret) {
-  if (sc.use_grid) hipLaunchKernelGGL((k_primary<false, true>), dim3(grid), dim3(kBlock), primary_grid_lds_bytes(sc), s, sc, cam, b, qs, cnt0, cnt_out, out, ret);
-  else if (tables_in_lds(sc)) hipLaunchKernelGGL(k_primary<true>, dim3(grid), dim3(kBlock), fused_lds_bytes(sc, true, carry_bytes<true>(), true), s, sc, cam, b, qs, cnt0, cnt_out, out, ret);
-  else hipLaunchKernelGGL(k_primary<false>, dim3(grid), dim3(kBlock), fused_lds_bytes(sc, false, kWaveLds, true), s, sc, cam, b, qs, cnt0, cnt_out, out, ret);
+  with_primary(sc, [&](auto kernel, int lds) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, sc, cam, b, qs, cnt0, cnt_out, out, ret); });
 }
 
 void launch_paths(hipStream_t s, int grid, const SceneTables& sc_in, const BatchInfo& b, const ptd::Queues& qs, int32_t* cnt, ptd::PathBuf in, ptd::RetireBuf ret) {
   const SceneTables sc = resolve_scan_nodes(sc_in);
-  const int bytes = paths_lds_bytes(sc, paths_mode(sc));
-  if (paths_mode(sc) == 0) hipLaunchKernelGGL(k_paths<0>, dim3(grid), dim3(kBlock), bytes, s, sc, b, qs, cnt, in, ret);
-  else if (paths_mode(sc) == 1) hipLaunchKernelGGL(k_paths<1>, dim3(grid), dim3(kBlock), bytes, s, sc, b, qs, cnt, in, ret);
-  else hipLaunchKernelGGL(k_paths<2>, dim3(grid), dim3(kBlock), bytes, s, sc, b, qs, cnt, in, ret);
+  with_paths(sc, search_form(sc), [&](auto kernel, int lds) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, sc, b, qs, cnt, in, ret); });
 }
 void launch_shade(hipStream_t s, int grid, const SceneTables& sc, const BatchInfo& b, int depth, const ptd::Queues& qs,
                   const int32_t* cnt_in, int32_t* cnt_out, ptd::PathBuf in, ptd::HitBuf hits, ptd::PathBuf out,
                   ptd::RetireBuf ret) {
-  const int bytes = round16(sc.num_mats * (int)sizeof(ptd::Mat)) + iter_hash_entries(sc) * 4;
-  hipLaunchKernelGGL(k_shade, dim3(grid), dim3(kBlock), bytes, s, sc, b, depth, qs, cnt_in, cnt_out, in, hits, out,
+  hipLaunchKernelGGL(k_shade, dim3(grid), dim3(kBlock), shade_lds<true>(sc).total, s, sc, b, depth, qs, cnt_in, cnt_out, in, hits, out,
                      ret);
 }
 
@@ -189,7 +165,6 @@ void launch_save_u8(hipStream_t s, int n, int width, float samples, const float*
 
 void launch_shade_stage(hipStream_t s, const SceneTables& sc, int trace_depth, int depth, int n, const int32_t* iter,
                         const int32_t* pixel, ptd::HitBuf hits, ptd::PathBuf paths, int32_t* alive) {
-  const int bytes = round16(sc.num_mats * (int)sizeof(ptd::Mat));
-  hipLaunchKernelGGL(k_shade_stage, dim3(flat_grid(n, 2048)), dim3(kBlock), bytes, s, sc, trace_depth, depth, n, iter, pixel, hits,
+  hipLaunchKernelGGL(k_shade_stage, dim3(flat_grid(n, 2048)), dim3(kBlock), shade_lds<false>(sc).total, s, sc, trace_depth, depth, n, iter, pixel, hits,
                      paths, alive);
 }

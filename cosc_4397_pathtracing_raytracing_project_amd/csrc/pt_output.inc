@@ -340,5 +340,3 @@ __global__ __launch_bounds__(kBlock) void k_save_u8(int n, int width, float samp
     }
   }
 }
-
-inline int round16(int x) { return (x + 15) & ~15; }

@@ -166,12 +166,13 @@ __global__ __launch_bounds__(kBlock) void k_shade(SceneTables sc, BatchInfo b, i
                                                   ptd::PathBuf in, ptd::HitBuf hits, ptd::PathBuf out,
                                                   ptd::RetireBuf ret) {
   extern __shared__ float4 lds_raw[];
-  char* lds = reinterpret_cast<char*>(lds_raw);  // [materials][iteration hashes]
-  stage16(lds, sc.mats, sc.num_mats * (int)sizeof(ptd::Mat));
-  uint32_t* ihash = reinterpret_cast<uint32_t*>(lds + ((sc.num_mats * (int)sizeof(ptd::Mat) + 15) & ~15));
+  char* lds = reinterpret_cast<char*>(lds_raw);
+  const ShadeLds L = shade_lds<true>(sc);
+  stage16(lds + L.mats, sc.mats, mat_bytes(sc));
+  uint32_t* ihash = reinterpret_cast<uint32_t*>(lds + L.ihash);
   iter_hash_fill(ihash, sc, b, depth);
   __syncthreads();
-  const ptd::Mat* mats = reinterpret_cast<const ptd::Mat*>(lds);
+  const ptd::Mat* mats = reinterpret_cast<const ptd::Mat*>(lds + L.mats);
 
   const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
   const int lane = lane_id();
