@@ -692,9 +692,9 @@ int pt_build_grid(const PtGeom* geoms, int num_geoms, int forced, PtGridInfo* in
   return 1;
 }
 
-void pt_center_half_box(const float lo[3], const float hi[3], int inner, float center[3], float half_extent[3]) {
+void pt_center_half_box(const float lo[3], const float hi[3], int inner, float magnitude, float center[3], float half_extent[3]) {
   float a[3] = {lo[0], lo[1], lo[2]}, b[3] = {hi[0], hi[1], hi[2]};
-  pt::center_half_box(a, b, inner != 0);
+  pt::center_half_box(a, b, inner != 0, (double)magnitude);
   std::memcpy(center, a, 12);
   std::memcpy(half_extent, b, 12);
 }

@@ -53,7 +53,8 @@ struct SceneTables {
   // The box tables of the BOUNCE kernels (depths >= 1; depth 0 always reads the ones above with the reference's arithmetic).  The
   // same tables, except in the fast build (KernelApi::boxes_center_half), whose slab test takes a box as centre and half extent
   // (pt_arith.inc slab_t): there the host uploads converted copies — bmin = centre, bmax = half extent rounded up so that the
-  // box contains the original, inner nodes and subtree entries a little more (pt_tables.cpp center_half_box).
+  // box contains the original, inner nodes and subtree entries more by 1e-5 of the SCENE's coordinate magnitude (the rounding of the
+  // test follows the ray origin, not the box), so that a ray passing a leaf's box passes every box above it (pt_tables.cpp center_half_box).
   const ptd::Node* nodes_b;
   const ptd::TopEntry* top_b;
   const ptd::Node* grid_items_b;

@@ -335,18 +335,32 @@ bool build_grid(const std::vector<ptd::Node>& nodes, const PtGeom* geoms, int nu
 // A box as centre and half extent for the fast build's slab test (pt_arith.inc slab_t): the centre rounded to float, the half
 // extent rounded UP from the distance to the farther face (so the converted box contains the original in real arithmetic), in
 // place in (bmin, bmax).  `inner` (inner nodes, subtree entries of the top list — pure acceleration): a little more, so that in the
-// test's float arithmetic a ray that passes a leaf's box still passes every box above it (1e-5 of the box and of the
-// coordinates: two orders of magnitude above the rounding of the three FMAs).
-void center_half_box(float bmin[3], float bmax[3], bool inner) {
+// test's float arithmetic a ray that passes a leaf's box still passes every box above it.  How much more, with u = 2^-24, i the
+// reciprocal direction and n = -o * i of the ray (both computed once per ray: the same values for the leaf and its ancestor),
+// per plane and per box:
+//   * tc = fma(c, i, n) is off by <= u |tc| <= u (|c| + |o|) |i|, the plane fma(-+h, |i|, tc) by <= u (|c| + |o| + h) |i| more;
+//   * the converted LEAF reaches <= 2 u (|c| + h) beyond its min / max box (centre rounded, half extent rounded up), and only
+//     that min / max box is known to lie inside the ancestor's.
+// Leaf plus ancestor: <= (4 (|o| + |c| + h) + 2 (|c| + h)) u |i| <= 10 u M |i| for |o|, |c| + h <= M.  The error follows the ray
+// ORIGIN, not the box: a small node next to the world origin of a wide scene needs the margin of the whole scene.  So the slack is
+// 1e-5 of the half extent plus 1e-5 * `magnitude`, M = scene_magnitude() (where ray origins lie: the scene bounds, the camera):
+// 1e-5 / (10 u) = 16.7 times the bound.
+void center_half_box(float bmin[3], float bmax[3], bool inner, double magnitude) {
   for (int a = 0; a < 3; ++a) {
     const double lo = bmin[a], hi = bmax[a];
     const float c = (float)(0.5 * (lo + hi));
     double h = std::max(hi - (double)c, (double)c - lo);
-    if (inner) h = h * (1.0 + 1e-5) + 1e-5 * std::max(std::fabs(lo), std::fabs(hi)) + 1e-30;
+    if (inner) h = h * (1.0 + 1e-5) + 1e-5 * magnitude + 1e-30;
     float hf = (float)h;
     if ((double)hf < h) hf = std::nextafter(hf, INFINITY);
     bmin[a] = c, bmax[a] = hf;
   }
+}
+// The largest coordinate magnitude a ray origin of the scene has: hit points lie in the scene bounds, depth 0 starts at the camera.
+double scene_magnitude(const float root_min[3], const float root_max[3], const float cam[3]) {
+  double m = 0.0;
+  for (int a = 0; a < 3; ++a) m = std::max({m, std::fabs((double)root_min[a]), std::fabs((double)root_max[a]), std::fabs((double)cam[a])});
+  return m;
 }
 
 HostTables build_scene_tables(const PtSceneDesc& desc, int debug_flags, bool center_half) {
@@ -366,7 +380,7 @@ HostTables build_scene_tables(const PtSceneDesc& desc, int debug_flags, bool cen
   {
     // SceneTables::cull_margin: >= 10x the worst undershoot of a reported hit distance (1e-4 object units mapped
     // to world space + rounding of the transforms at the scene's coordinate magnitudes)
-    float max_xf = 1.0f, extent = 1.0f;
+    float max_xf = 1.0f;
     for (int i = 0; i < desc.num_geoms; ++i) {
       const PtGeom& gm = desc.geoms[i];
       if (gm.type == PT_GEOM_TRIANGLE) continue;  // world-space test: the pull-back is 1e-4 world units (max_xf >= 1 covers it)
@@ -375,8 +389,7 @@ HostTables build_scene_tables(const PtSceneDesc& desc, int debug_flags, bool cen
         for (int r = 0; r < 3; ++r) f += gm.transform[c * 4 + r] * gm.transform[c * 4 + r];
       max_xf = std::max(max_xf, sqrtf(f));
     }
-    for (int a = 0; a < 3; ++a)
-      extent = std::max({extent, fabsf(t.root_min[a]), fabsf(t.root_max[a]), fabsf(desc.camera.position[a])});
+    const float extent = std::max(1.0f, (float)scene_magnitude(t.root_min, t.root_max, desc.camera.position));
     t.cull_margin = 1e-3f * max_xf + 1e-4f * extent;
   }
   t.geoms.assign(desc.num_geoms, ptd::Geom{});
@@ -403,10 +416,11 @@ HostTables build_scene_tables(const PtSceneDesc& desc, int debug_flags, bool cen
     t.mats[i].reflective = m.hasReflective, t.mats[i].refractive = m.hasRefractive, t.mats[i].emittance = m.emittance;
   }
   if (center_half) {  // the fast build: converted copies for the bounce kernels
+    const double mag = scene_magnitude(t.root_min, t.root_max, desc.camera.position);
     t.nodes_b = t.nodes;
-    for (ptd::Node& n : t.nodes_b) center_half_box(n.bmin, n.bmax, n.geom < 0);
+    for (ptd::Node& n : t.nodes_b) center_half_box(n.bmin, n.bmax, n.geom < 0, mag);
     t.top_b = t.top;
-    for (ptd::TopEntry& e : t.top_b) center_half_box(e.bmin, e.bmax, e.link >= 0);
+    for (ptd::TopEntry& e : t.top_b) center_half_box(e.bmin, e.bmax, e.link >= 0, mag);
   }
   if (((int)t.nodes.size() >= kGridNodes || (debug_flags & 256)) && !(debug_flags & 512)) {
     double cam_mag = 0.0;
@@ -432,7 +446,7 @@ HostTables build_scene_tables(const PtSceneDesc& desc, int debug_flags, bool cen
       grid.start.resize(grid.start.size() + grid.guard, total);
       if (center_half) {  // the grid's records are leaf boxes
         grid.items_b = grid.items;
-        for (ptd::Node& n : grid.items_b) center_half_box(n.bmin, n.bmax, false);
+        for (ptd::Node& n : grid.items_b) center_half_box(n.bmin, n.bmax, false, 0.0);
       }
       t.grids.push_back(std::move(grid));
     }

@@ -36,7 +36,8 @@ bool build_grid(const std::vector<ptd::Node>& nodes, const PtGeom* geoms, int nu
                 double coord_mag, double density, bool forced, Grid& grid);
 void origin_region(const float root_min[3], const float root_max[3], const float cam[3], double olo[3], double ohi[3]);
 int tighten_sphere_leaves(std::vector<ptd::Node>& nodes, const PtGeom* geoms, const double origin_lo[3], const double origin_hi[3]);
-void center_half_box(float bmin[3], float bmax[3], bool inner);
+double scene_magnitude(const float root_min[3], const float root_max[3], const float cam[3]);
+void center_half_box(float bmin[3], float bmax[3], bool inner, double magnitude);  // magnitude: scene_magnitude(), used for inner boxes only
 
 struct HostTables {              // what ptk::SceneTables points to, on the host
   std::vector<ptd::Node> nodes, nodes_b;  // *_b: centre / half extent copies (`center_half`), else empty

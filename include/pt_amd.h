@@ -227,9 +227,11 @@ int pt_traversal_boxes(const PtGeom* geoms, int num_geoms, const float camera_po
  * the slab test is three FMAs per axis (csrc/pt_arith.inc slab_t; min / max issue at half the rate of an FMA on gfx950).  The
  * half extent is rounded up from the distance between the float centre and the farther face, so [c - h, c + h] contains
  * [lo, hi] in real arithmetic; `inner` != 0 (inner nodes, subtree entries of the top list: pure acceleration) adds 1e-5 of the
- * extent and of the coordinates, so that a ray passing a leaf's box in the test's float arithmetic passes every box above it.
+ * extent and 1e-5 * `magnitude`, the largest coordinate magnitude of the scene bounds and the camera position (what pt_init passes: the
+ * test's rounding follows the ray origin), so that a ray passing a leaf's box in the test's float arithmetic passes every box
+ * above it (the bound is derived at csrc/pt_tables.cpp center_half_box).  `magnitude` is not used for leaves.
  * Depth 0 and the exact / fma builds test the reference's min / max boxes with the reference's arithmetic. */
-void pt_center_half_box(const float lo[3], const float hi[3], int inner, float center[3], float half_extent[3]);
+void pt_center_half_box(const float lo[3], const float hi[3], int inner, float magnitude, float center[3], float half_extent[3]);
 
 /* transform / inverse / inverse-transpose of an OBJECT block's TRANS ROTAT SCALE
  * (trs[9]), as utilityCore::buildTransformationMatrix + glm::inverse +

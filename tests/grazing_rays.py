@@ -1,0 +1,237 @@
+"""Scenes and rays for the tests of the contract "the structure never changes which leaves pass their own box test"
+(DESIGN.md sections 4, 5, 9): test_center_half_boxes.py restates the fast build's slab test on the host,
+test_gpu_traversal_consistency.py compares the hierarchical searches with flat leaf tests on the GPU.
+
+Scenes: six wall cubes and a cluster of small primitives around the world origin (a third axis-aligned cubes, a third
+rotated cubes, a third rotated, non-uniformly scaled spheres) — small boxes next to the origin of a wide scene are where
+the rounding of the centre / half-extent slab test, which follows the ray ORIGIN, is largest against the boxes' own size.
+Rays: built to graze the edges and corners of the reference's leaf boxes (capi.Scene.bvh()), deterministic."""
+import numpy as np
+
+from cosc_4397_pathtracing_raytracing_project_amd import scenes
+
+SCENES = {
+    "room": dict(wall=5.0, n=90, scale=(0.02, 0.1), spread=0.5, seed=11),    # 96 leaves: top list plus subtree scans
+    "hall": dict(wall=100.0, n=90, scale=(0.02, 0.1), spread=0.5, seed=11),  # the same cluster, ray origins up to 100 away
+    "big": dict(wall=10.0, n=400, scale=(0.02, 0.3), spread=3.0, seed=12),   # 811 nodes: the kernels' global-memory tables
+}
+WALLS = 6
+FLAT_CHUNK = 26  # cluster primitives per flat sub-scene: 6 + 26 = 32 leaves, every leaf a top entry (leaves_fit_top)
+FAMILIES = ("edge", "corner", "zero", "face", "uniform")
+DELTAS = np.array([0.0] + [s * m for m in (1e-8, 3e-8, 1e-7, 3e-7, 1e-6, 1e-5) for s in (1.0, -1.0)])
+# the 12 edges of a box: (axis the edge runs along, the two other axes, which face of each)
+EDGES = [(a, (a + 1) % 3, (a + 2) % 3, sb, sc) for a in range(3) for sb in (0, 1) for sc in (0, 1)]
+CORNERS = [(sx, sy, sz) for sx in (0, 1) for sy in (0, 1) for sz in (0, 1)]
+
+
+def objects(name):
+    """(walls, cluster) as (kind, material, TRANS, ROTAT, SCALE) rows."""
+    p = SCENES[name]
+    w, th = p["wall"], p["wall"] / 500.0
+    walls = []
+    for a in range(3):
+        for s in (1, -1):
+            # every wall a little longer than the room and than the walls before it: where walls overlap (the room's edges) no
+            # two of them share a face plane, so a ray inside the overlap does not leave two walls at the same distance (a
+            # tie between two primitives is resolved by visiting order, which differs between a scene and its sub-scenes)
+            long = 2 * w + th * (1 + len(walls)) / 4
+            t, sc = [0.0, 0.0, 0.0], [long, long, long]
+            t[a], sc[a] = s * w, th
+            walls.append(("cube", 0 if (a, s) == (1, 1) else 1 + a, tuple(t), (0, 0, 0), tuple(sc)))  # the ceiling is the light
+    rs = np.random.RandomState(p["seed"])
+    cluster = []
+    for k in range(p["n"]):
+        pos = tuple(float(v) for v in np.round(rs.uniform(-p["spread"], p["spread"], 3), 4))
+        scl = tuple(float(v) for v in np.round(rs.uniform(p["scale"][0], p["scale"][1], 3), 4))
+        rot = tuple(int(v) for v in rs.randint(0, 180, 3))
+        cluster.append((("cube", "cube", "sphere")[k % 3], 1 + k % 4, pos, rot if k % 3 else (0, 0, 0), scl))
+    return walls, cluster
+
+
+def scene_text(name, rows=None, res=(64, 48), depth=8):
+    walls, cluster = objects(name)
+    rows = walls + cluster if rows is None else rows
+    out = [scenes._material(i, **m) for i, m in enumerate(scenes._CORNELL_MATERIALS)]
+    w = SCENES[name]["wall"]
+    out.append(scenes._camera(res, 45, 8, depth, name, (0, 0, 0.8 * w), (0, 0, 0), (0, 1, 0)))
+    for i, (kind, mat, t, r, s) in enumerate(rows):
+        out.append(scenes._object(i, kind, mat, t, r, s))
+    return "".join(out)
+
+
+def flat_scene_texts(name, **kw):
+    """The same primitives as sub-scenes of the six walls plus at most FLAT_CHUNK cluster primitives each."""
+    walls, cluster = objects(name)
+    return [scene_text(name, walls + cluster[k:k + FLAT_CHUNK], **kw) for k in range(0, len(cluster), FLAT_CHUNK)]
+
+
+def tree(bvh):
+    """The reference's BVH (capi.Scene.bvh()) as arrays: node boxes [n, 6] float32, the leaves' node indices in geom order
+    (leaf_of[g]), and each node's parent (-1 for the root)."""
+    n = len(bvh)
+    boxes = np.array([list(b.bmin) + list(b.bmax) for b in bvh], np.float32)
+    parent = np.full(n, -1, np.int64)
+    leaves = {}
+    for i, b in enumerate(bvh):
+        if b.left >= 0:
+            parent[b.left] = parent[b.right] = i
+        else:
+            leaves[b.geomIndex] = i
+    return boxes, np.array([leaves[g] for g in range(len(leaves))], np.int64), parent
+
+
+def _unit(rs, n):
+    u = rs.normal(size=(n, 3))
+    return u / np.linalg.norm(u, axis=1, keepdims=True)
+
+
+def _origins(rs, n, leaf_boxes, root):
+    """A third uniform in the scene bounds, a third exactly on a face of a wall's box, a third inside the box of a cluster leaf."""
+    lo, hi = root[:3].astype(np.float64), root[3:].astype(np.float64)
+    o = rs.uniform(lo, hi, (n, 3))
+    kind = rs.randint(0, 3, n)
+    j = np.where(kind == 1, rs.randint(0, WALLS, n), rs.randint(WALLS, len(leaf_boxes), n))
+    b = leaf_boxes[j].astype(np.float64)
+    inside = b[:, :3] + rs.rand(n, 3) * (b[:, 3:] - b[:, :3])
+    thin = np.argmin(b[:, 3:] - b[:, :3], axis=1)
+    face = np.where(rs.rand(n) < 0.5, b[np.arange(n), thin], b[np.arange(n), 3 + thin])
+    on_wall = inside.copy()
+    on_wall[np.arange(n), thin] = face
+    o = np.where((kind == 1)[:, None], on_wall, np.where((kind == 2)[:, None], inside, o))
+    return np.clip(o.astype(np.float32), root[:3], root[3:])  # float32, inside the bounds
+
+
+def _aim(o32, q):
+    """Direction from the float32 origin towards q: normalised in float64, then rounded to float32."""
+    d = q - o32.astype(np.float64)
+    n = np.linalg.norm(d, axis=1, keepdims=True)
+    d = np.where(n > 0, d / np.where(n > 0, n, 1.0), np.array([1.0, 0.0, 0.0]))
+    return d.astype(np.float32)
+
+
+def _edge_points(rs, b, e):
+    """A uniform point on edge EDGES[e] of the boxes b [n, 6] (float64; the two fixed coordinates are exact face values)."""
+    n = len(b)
+    ed = np.array(EDGES)[e]
+    r = np.arange(n)
+    p = np.zeros((n, 3))
+    a = ed[:, 0]
+    p[r, a] = b[r, a] + rs.rand(n) * (b[r, 3 + a] - b[r, a])
+    p[r, ed[:, 1]] = b[r, ed[:, 1] + 3 * ed[:, 3]]
+    p[r, ed[:, 2]] = b[r, ed[:, 2] + 3 * ed[:, 4]]
+    return p
+
+
+def rays(leaf_boxes, root, total=300000, families=FAMILIES, seed=1):
+    """About `total` rays against the leaf boxes [leaves, 6] (float32, walls first) with every origin inside `root` (lo, hi):
+    dict(o, d: float32 [3, n]; leaf, family, feature: which box, which family (index into FAMILIES), which edge / corner /
+    face it aims at; delta: the displacement of the aim point, as a multiple of 1 + |p|)."""
+    rs = np.random.RandomState(seed)
+    nl = len(leaf_boxes)
+    b64 = leaf_boxes.astype(np.float64)
+    share = {"edge": 0.62, "corner": 0.14, "zero": 0.07, "face": 0.04, "uniform": 0.13}
+    scale = total / sum(share[f] for f in families)
+    out = []
+
+    def emit(fam, leaf, feature, delta, o, d):
+        out.append((np.full(len(leaf), FAMILIES.index(fam), np.int8), leaf.astype(np.int32), feature.astype(np.int32), delta, o, d))
+
+    def displaced(fam, leaf, feature, delta, p):
+        n = len(leaf)
+        q = p + (delta * (1.0 + np.linalg.norm(p, axis=1)))[:, None] * _unit(rs, n)
+        o = _origins(rs, n, leaf_boxes, root)
+        emit(fam, leaf, feature, delta, o, _aim(o, q))
+
+    if "edge" in families:
+        k = max(1, int(round(scale * share["edge"] / (nl * 12 * len(DELTAS)))))
+        leaf, e, dl = (a.reshape(-1) for a in np.meshgrid(np.arange(nl), np.arange(12), np.arange(len(DELTAS)), indexing="ij"))
+        leaf, e, dl = np.repeat(leaf, k), np.repeat(e, k), np.repeat(dl, k)
+        displaced("edge", leaf, e, DELTAS[dl], _edge_points(rs, b64[leaf], e))
+    if "corner" in families:
+        k = max(1, int(round(scale * share["corner"] / (nl * 8 * len(DELTAS)))))
+        leaf, c, dl = (a.reshape(-1) for a in np.meshgrid(np.arange(nl), np.arange(8), np.arange(len(DELTAS)), indexing="ij"))
+        leaf, c, dl = np.repeat(leaf, k), np.repeat(c, k), np.repeat(dl, k)
+        side = np.array(CORNERS)[c]
+        p = np.where(side == 1, b64[leaf][:, 3:], b64[leaf][:, :3])
+        displaced("corner", leaf, c, DELTAS[dl], p)
+    if "zero" in families:
+        # through a point of an edge with one or two direction components exactly +0.0 / -0.0: the origin shares those
+        # coordinates with the point (for one zero component sometimes one float beside it: the ray runs IN or just beside
+        # the plane of a face).  In the fast build these components meet ray_inv's clamp to 1e-20.
+        k = max(1, int(round(scale * share["zero"] / (nl * 12))))
+        leaf, e = (a.reshape(-1) for a in np.meshgrid(np.arange(nl), np.arange(12), indexing="ij"))
+        leaf, e = np.repeat(leaf, k), np.repeat(e, k)
+        n = len(leaf)
+        p = _edge_points(rs, b64[leaf], e).astype(np.float32)
+        ed = np.array(EDGES)[e]
+        o = _origins(rs, n, leaf_boxes, root)
+        r = np.arange(n)
+        mode = rs.randint(0, 3, n)  # 0: one zero component (a fixed axis of the edge); 1: along the edge; 2: across it
+        z1 = np.where(mode == 1, ed[:, 1], np.where(rs.rand(n) < 0.5, ed[:, 1], ed[:, 2]))
+        z2 = np.where(mode == 1, ed[:, 2], np.where(mode == 2, ed[:, 0], -1))
+        nudge = np.where(mode == 0, rs.randint(-1, 3, n), 0)  # -1, 0, 1, 2 -> one float below, on, one float above, on
+        c1 = p[r, z1]
+        c1 = np.where(nudge == -1, np.nextafter(c1, np.float32(-np.inf)), np.where(nudge == 1, np.nextafter(c1, np.float32(np.inf)), c1))
+        o[r, z1] = c1
+        has2 = z2 >= 0
+        o[r[has2], z2[has2]] = p[r[has2], z2[has2]]
+        o = np.clip(o, root[:3], root[3:])
+        q = p.astype(np.float64)
+        q[r, z1] = o[r, z1]
+        d = _aim(o, q)
+        zero = np.where(rs.rand(n, 2) < 0.5, np.float32(0.0), np.float32(-0.0)).astype(np.float32)
+        d[r, z1] = zero[:, 0]
+        d[r[has2], z2[has2]] = zero[has2, 1]
+        emit("zero", leaf, e, np.zeros(n), o, d)
+    if "face" in families:
+        k = max(1, int(round(scale * share["face"] / (nl * 6))))
+        leaf, f = (a.reshape(-1) for a in np.meshgrid(np.arange(nl), np.arange(6), indexing="ij"))
+        leaf, f = np.repeat(leaf, k), np.repeat(f, k)
+        p = 0.5 * (b64[leaf][:, :3] + b64[leaf][:, 3:])
+        p[np.arange(len(leaf)), f % 3] = b64[leaf][np.arange(len(leaf)), f]
+        displaced("face", leaf, f, np.zeros(len(leaf)), p)
+    if "uniform" in families:
+        n = int(round(scale * share["uniform"]))
+        o = _origins(rs, n, leaf_boxes, root)
+        emit("uniform", np.full(n, -1), np.full(n, -1), np.zeros(n), o, _unit(rs, n).astype(np.float32))
+    fam, leaf, feature, delta, o, d = (np.concatenate(c) for c in zip(*out))
+    return dict(family=fam, leaf=leaf, feature=feature, delta=delta, o=np.ascontiguousarray(o.T, np.float32), d=np.ascontiguousarray(d.T, np.float32))
+
+
+def describe(r, i, leaf_boxes):
+    """One ray for a failure message: the ray, what it aims at, the target leaf's box."""
+    fam = FAMILIES[r["family"][i]]
+    what = {"edge": lambda f: f"edge {f} (along axis {EDGES[f][0]})", "corner": lambda f: f"corner {CORNERS[f]}", "zero": lambda f: f"edge {f}, zero components",
+            "face": lambda f: f"face {f}", "uniform": lambda f: "nothing"}[fam](int(r["feature"][i]))
+    box = leaf_boxes[r["leaf"][i]].tolist() if r["leaf"][i] >= 0 else None
+    return (f"ray {i} [{fam}] o={r['o'][:, i].tolist()} d={r['d'][:, i].tolist()} aims at {what} of leaf {int(r['leaf'][i])} box {box}, "
+            f"delta {r['delta'][i]:g}")
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def combine_flat(results):
+    """The flat result of every ray from the sub-scenes' hit records (dicts t [n], mat [n], nrm, pt [3, n]): the sub-scene
+    result with the smallest t >= 0, the first sub-scene on ties, a miss where all miss.  Also `agree` [n]: the sub-scenes
+    that attain the minimum (all of them for a miss) report the same mat / nrm / pt bit for bit."""
+    t = np.stack([r["t"] for r in results])
+    key = np.where(t >= 0, t, np.float32(np.inf))
+    best = np.argmin(key, axis=0)
+    cols = np.arange(t.shape[1])
+    out = dict(t=t[best, cols].copy(), mat=np.stack([r["mat"] for r in results])[best, cols].copy(),
+               nrm=np.stack([r["nrm"] for r in results])[best, :, cols].T.copy(), pt=np.stack([r["pt"] for r in results])[best, :, cols].T.copy())
+    agree = np.ones(t.shape[1], bool)
+    for r in results:
+        attains = bits(r["t"]) == bits(out["t"])
+        same = (bits(r["mat"].view(np.float32)) == bits(out["mat"].view(np.float32))) & (bits(r["nrm"]) == bits(out["nrm"])).all(axis=0) & \
+               (bits(r["pt"]) == bits(out["pt"])).all(axis=0)
+        agree &= ~attains | same
+    return out, agree
+
+
+def reports_cluster(name, hit):
+    """Rays whose hit lies in the cluster (far inside the walls)."""
+    p = SCENES[name]
+    return (hit["t"] >= 0) & (np.abs(hit["pt"]).max(axis=0) < 0.5 * (p["spread"] + p["wall"]))

@@ -90,12 +90,26 @@ def test_forced_grid_on_unusual_layouts(oracle, tmp_path, name):
     assert (imgs[256].sum(axis=1) > 0).mean() > 0.05, "the camera sees the scene"
 
 
+@pytest.mark.parametrize("layout", ["lattice", "mixed_sizes", "offset", "room"])
 @pytest.mark.parametrize("arith", ["fma", "fast"])
-def test_grid_and_scan_give_the_same_image_in_every_mode(tmp_path, arith):
+def test_grid_and_scan_give_the_same_image_in_every_mode(tmp_path, arith, layout):
     """The structure only changes which leaves are LOOKED AT, never which pass their box test: the fma / fast images are
-    identical with either structure too (same kernels' arithmetic on the same candidates)."""
-    res, spp = (160, 90), 6
-    path = scenes.write_scene(scenes.stress_scene_text((10, 10, 8), res=res), str(tmp_path / "s.txt"))
+    identical with either structure too (same kernels' arithmetic on the same candidates).  The grid tests leaf boxes only, so
+    it is the flat side of the fused kernels; the scan tests inner boxes on the way — in the fast build with the slack of
+    center_half_box, which has to cover primitives far smaller than the scene (mixed_sizes, room: grazing_rays.py) and
+    coordinates far larger than it (offset)."""
+    if layout == "lattice":
+        res, spp = (160, 90), 6
+        text = scenes.stress_scene_text((10, 10, 8), res=res)
+    elif layout == "room":
+        import grazing_rays
+        res, spp = (128, 96), 4
+        text = grazing_rays.scene_text("room", res=res)
+    else:
+        res, spp = (128, 96), 4
+        objects, eye, lookat = layouts()[layout]
+        text = scene_text(objects, res, eye, lookat)
+    path = scenes.write_scene(text, str(tmp_path / "s.txt"))
     sc = capi.Scene(path, res=res)
     imgs = []
     for flags in (256, 512):
@@ -103,8 +117,10 @@ def test_grid_and_scan_give_the_same_image_in_every_mode(tmp_path, arith):
         try:
             r.render(1, spp)
             imgs.append(r.readback())
+            assert (r.stats().grid_cells > 0) == (flags == 256)
         finally:
             r.free()
+    assert np.isfinite(imgs[0]).all() and (imgs[0].sum(axis=1) > 0).mean() > 0.05, "the camera sees the scene"
     assert np.array_equal(bits(imgs[0]), bits(imgs[1]))
 
 
