@@ -22,6 +22,7 @@
 #include "pt_internal.h"
 #include "pt_kernels.h"
 #include "pt_scene.h"
+#include "pt_sched.h"
 #include "pt_tables.h"
 
 namespace {
@@ -228,27 +229,22 @@ int run_batch(Ctx& g, int iter_first, int kb) {
   b.slot_shift = g.slot_shift;
   b.aa_jitter = g.aa_jitter ? 1 : 0;
   b.flat = g.fuse_bounces ? 0 : 1;
-  {
-    // k_primary's strands in pieces (BatchInfo::primary_pieces): a piece pays for its own pipeline drain, so it should hold a
-    // few dozen 64-sample groups; a wave's strand has K * nq / (waves per queue) of them
-    const int64_t groups = (int64_t)kb * g.qs.nq / std::max(1, g.ret.wq0);
-    b.primary_pieces = g.primary_pieces ? g.primary_pieces : (int)std::min<int64_t>(4, std::max<int64_t>(1, groups / 48));
-  }
+  b.primary_pieces = g.primary_pieces ? g.primary_pieces : ptk::auto_primary_pieces(kb, g.qs.nq, g.ret.wq0);
   b.paths_pieces = g.paths_pieces;
   b.stripe = g.stripe;
   b.gap = g.stripe ? g.stripe_stride - g.stripe : 0;
   b.inv_stripe = g.stripe ? 1.0f / (float)g.stripe : 0.0f;
   const ptk::SceneTables sc = tables(g);
   const ptk::KernelApi& k = *g.k;
-  const size_t per_depth = (size_t)g.qs.Q * g.qs.cnt_stride;
+  auto cnt_row = [&](int d) { return g.d_cnt + ptk::cnt_index(g.qs, d, 0); };  // the counter row of depth d
   int d0 = 0;
   if (g.fuse_primary) {
     // depth 0 in one launch; its survivors are the depth-1 input (buf[1], cnt[1])
-    k.primary(g.stream, g.grid_primary, sc, g.dcam, b, queues_for(g, g.grid_primary), g.d_cnt, g.d_cnt + per_depth, g.buf[1],
+    k.primary(g.stream, g.grid_primary, sc, g.dcam, b, queues_for(g, g.grid_primary), cnt_row(0), cnt_row(1), g.buf[1],
               g.ret);
     d0 = 1;
   } else {
-    k.generate(g.stream, g.grid_gen, g.dcam, b, queues_for(g, g.grid_gen), g.buf[0], g.d_cnt);
+    k.generate(g.stream, g.grid_gen, g.dcam, b, queues_for(g, g.grid_gen), g.buf[0], cnt_row(0));
   }
   int src = d0 & 1;
   // Depths >= 1, fused: ONE launch of k_paths — persistent lanes with their own depth, no path state through HBM after depth 0
@@ -267,8 +263,8 @@ int run_batch(Ctx& g, int iter_first, int kb) {
   }
   // ... unfused (tests, A/B): computeIntersections and shadeAndExtendRays as separate launches per depth
   for (int d = d0; d < g.depth && !all_depths; ++d) {
-    const int32_t* cin = g.d_cnt + per_depth * d;
-    int32_t* cout = g.d_cnt + per_depth * (d + 1);
+    const int32_t* cin = cnt_row(d);
+    int32_t* cout = cnt_row(d + 1);
     EventPair ev{};
     if (g.time_kernels) {  // brackets the dominant kernel of this depth
       if (get_events(g, &ev)) return -1;
@@ -308,7 +304,7 @@ void plan_launch(Ctx& g) {
   g.grid_isect = g.num_cus * std::min(g.cap_bpc, g.k->resident_blocks_per_cu(g.legacy ? ptk::kIntersectLegacy : ptk::kIntersect, t));
   g.grid_shade = g.num_cus * std::min(g.cap_bpc, g.k->resident_blocks_per_cu(ptk::kShade, t));
   g.grid_primary = g.num_cus * std::min(g.cap_bpc, g.k->resident_blocks_per_cu(ptk::kPrimary, t));
-  g.ret.wq0 = g.grid_primary * ptk::kWavesPerBlock / g.qs.Q;  // the sub-lists' residue count (pt_device.h RetireBuf)
+  g.ret.wq0 = ptk::wave_slot(0, g.qs.Q, g.grid_primary * ptk::kWavesPerBlock).wq;  // the sub-lists' residue count (pt_device.h RetireBuf)
   g.grid_paths = (g.fuse_bounces && g.depth > 1) ? g.num_cus * std::min(g.cap_bpc, g.k->resident_blocks_per_cu(ptk::kPaths, t)) : 0;
   g.qs.paths_W = g.grid_paths * ptk::kWavesPerBlock;  // what k_count_stats deals to the queues (a table made for another width is ignored)
 }
@@ -391,10 +387,11 @@ struct Scratch {  // frees on scope exit
 ptd::Queues single_queue(const Ctx& g, int n) {
   ptd::Queues qs{};
   qs.Q = 1;
-  qs.cap = ((n + 63) / 64) * 64;
+  const ptk::QueuePlan p = ptk::queue_plan(n, 1, 1);
+  qs.cap = p.cap;
   qs.W = g.grid * ptk::kWavesPerBlock;
   qs.cnt_stride = 16;
-  qs.nq = (n + 63) / 64;
+  qs.nq = p.nq;
   qs.inv_nq = 1.0f / (float)qs.nq;
   return qs;
 }
@@ -456,7 +453,7 @@ void take_scene_and_options(Ctx& g, const PtSceneDesc* sc, const PtOptions& opt)
   auto pieces = [](int v, int automatic) { return v ? std::clamp(v, 1, 0x7fff) : automatic; };
   g.lds_table_forced = opt.lds_table_kb ? std::clamp(opt.lds_table_kb, 0, ptk::kLdsTableBytes / 1024) * 1024 : -1;
   g.primary_pieces = pieces(opt.primary_pieces, 0);
-  g.paths_pieces = pieces(opt.paths_pieces, 2) | pieces(opt.paths_min_piece, 64) << 16;
+  g.paths_pieces = ptk::pack_paths_pieces(pieces(opt.paths_pieces, 2), pieces(opt.paths_min_piece, 64));
   g.fuse_primary = !g.legacy && !opt.unfused_primary;
   g.fuse_bounces = g.fuse_primary && !opt.unfused_bounces;
   g.cap_bpc = opt.blocks_per_cu > 0 ? std::min(opt.blocks_per_cu, 8) : 8;
@@ -499,10 +496,9 @@ int plan_batches(Ctx& g, const PtOptions& opt) {
   const int cu_waves = g.num_cus * ptk::kWavesPerBlock;
   if (Q > cu_waves) Q = cu_waves;
   while (cu_waves % Q) --Q;
-  const int64_t chunks = ((int64_t)g.N + 63) / 64;  // per iteration
   if (opt.num_queues <= 0)
-    while ((chunks + Q - 1) / Q > 128 && 2 * Q <= cu_waves && cu_waves % (2 * Q) == 0) Q *= 2;
-  const int nq = (int)((chunks + Q - 1) / Q);
+    while (ptk::chunks_per_queue(g.N, Q) > 128 && 2 * Q <= cu_waves && cu_waves % (2 * Q) == 0) Q *= 2;
+  const ptk::QueuePlan plan = ptk::queue_plan(g.N, Q, K);
   const int grid = g.num_cus * 8;
   // Retirement records: one slot per (iteration of the batch, pixel) — regions (queue, iteration) of nq * 64 slots, exactly
   // full at the end of a batch (pt_device.h RetireBuf): 16 bytes per sample and batch.
@@ -511,11 +507,11 @@ int plan_batches(Ctx& g, const PtOptions& opt) {
   g.qs.Q = Q;
   g.qs.W = grid * ptk::kWavesPerBlock;
   g.qs.cnt_stride = 16;
-  g.qs.nq = nq;
-  g.qs.inv_nq = 1.0f / (float)nq;
-  g.qs.cap = K * nq * 64;
+  g.qs.nq = plan.nq;
+  g.qs.inv_nq = 1.0f / (float)plan.nq;
+  g.qs.cap = plan.cap;
   g.stride = (int64_t)Q * g.qs.cap;
-  g.ret.seg_cap = nq * 64;
+  g.ret.seg_cap = plan.seg_cap;
   g.ret.kmax = K;
   return 0;
 }
@@ -559,18 +555,20 @@ int alloc_batch_buffers(Ctx& g) {
   if (!g.fuse_bounces && alloc_hitbuf(g, &g.hits, g.stride)) return -1;  // hit records reach HBM only in the unfused form
   {
     const size_t regions = (size_t)Q * g.ret.kmax;
-    const size_t wq_max = (size_t)g.num_cus * 8 * ptk::kWavesPerBlock / Q;  // waves per queue of the widest k_primary grid
+    const size_t wq_max = ptk::sub_stride(g.num_cus * 8 * ptk::kWavesPerBlock, Q);  // (8 resident workgroups per CU at the most)
     if (dalloc(g, &g.ret.rec, regions * g.ret.seg_cap) || dalloc(g, &g.ret.cnt, regions) || dalloc(g, &g.ret.sub, regions * wq_max)) return -1;
     HIP_OK(hipMemset(g.ret.cnt, 0, regions * sizeof(unsigned long long)));  // k_collect re-zeroes them after every batch
     HIP_OK(hipMemset(g.ret.sub, 0, regions * wq_max * sizeof(unsigned long long)));
   }
   if (dalloc(g, &g.d_image, 3 * (size_t)g.N)) return -1;
-  if (dalloc(g, &g.d_cnt, (size_t)(g.depth + 1) * Q * g.qs.cnt_stride)) return -1;
-  HIP_OK(hipMemset(g.d_cnt, 0, (size_t)(g.depth + 1) * Q * g.qs.cnt_stride * sizeof(int32_t)));  // k_count_stats re-zeroes it after every batch
+  const size_t cnt_words = ptk::cnt_index(g.qs, g.depth + 1, 0);  // rows 0 .. depth
+  if (dalloc(g, &g.d_cnt, cnt_words)) return -1;
+  HIP_OK(hipMemset(g.d_cnt, 0, cnt_words * sizeof(int32_t)));  // k_count_stats re-zeroes it after every batch
   if (dalloc(g, &g.d_stats, PT_MAX_DEPTH)) return -1;
   if (!(g.debug_flags & 64)) {  // (64: W / Q waves per queue in every batch; same image)
-    if (dalloc(g, &g.qs.deal, 4 * (size_t)Q + 2)) return -1;
-    HIP_OK(hipMemset(g.qs.deal, 0, (4 * (size_t)Q + 2) * sizeof(int32_t)));  // nothing measured yet: W / Q each
+    const size_t deal_words = (size_t)ptk::deal_map(g.qs).words();
+    if (dalloc(g, &g.qs.deal, deal_words)) return -1;
+    HIP_OK(hipMemset(g.qs.deal, 0, deal_words * sizeof(int32_t)));  // nothing measured yet: W / Q each
   }
   if (g.conv) {
     const size_t partials = (size_t)g.K * Q * ptk::kConvWaves;
@@ -867,9 +865,10 @@ int pt_ctx_get_stats(PtContext* c, PtStats* out) {
   out->tight_leaves = g.tight_leaves;
   out->paths_waves = 0;
   if (g.qs.deal && g.grid_paths > 0) {  // the table the NEXT batch's k_paths launch will read (ptd::Queues::deal)
-    std::vector<int32_t> first((size_t)g.qs.Q + 1);
-    HIP_OK(hipMemcpy(first.data(), g.qs.deal, first.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (first[g.qs.Q] == g.qs.paths_W) {
+    const ptk::DealMap dm = ptk::deal_map(g.qs);
+    std::vector<int32_t> first((size_t)dm.made_for() + 1);  // first(0 .. Q)
+    HIP_OK(hipMemcpy(first.data(), g.qs.deal + dm.first(0), first.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (first[dm.made_for()] == g.qs.paths_W) {
       int lo = first[1] - first[0], hi = lo;
       for (int q = 1; q < g.qs.Q; ++q) lo = std::min(lo, first[q + 1] - first[q]), hi = std::max(hi, first[q + 1] - first[q]);
       out->paths_waves = std::min(lo, 0xffff) << 16 | std::min(hi, 0xffff);

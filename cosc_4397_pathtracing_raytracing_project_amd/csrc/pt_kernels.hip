@@ -37,6 +37,7 @@
 #include <type_traits>
 
 #include "pt_lds.h"
+#include "pt_sched.h"
 #include "pt_portable_math.h"
 
 #ifndef PT_ARITH
@@ -339,11 +340,6 @@ PT_DEV Retire retire_of(const ptd::RetireBuf& rb, int q) {
   rt.seg_cap = rb.seg_cap, rt.wq0 = rb.wq0;
   return rt;
 }
-// Sub-list / sub-region (q, k, rho) of a queue with my_nq chunks per iteration dealt to wq0 residues: c(rho) chunks, the first
-// of them off(rho) chunks into list / region (q, k)  (residue rho owns the chunks jj = rho, rho + wq0, ...).
-// (quo = my_nq / wq0, rem = my_nq % wq0, computed once per kernel)
-PT_DEV int sub_chunks(int quo, int rem, int rho) { return quo + (rho < rem ? 1 : 0); }
-PT_DEV int sub_offset(int quo, int rem, int rho) { return rho * quo + min(rho, rem); }
 PT_DEV void retire_store(const Retire& rt, bool dead, int k, int pos, int pl, f3 c) {
   if (dead) rt.rec[(int64_t)k * rt.seg_cap + pos] = ptd::Word4{c.x, c.y, c.z, __int_as_float(pl)};
 }
@@ -352,37 +348,21 @@ PT_DEV void retire_store(const Retire& rt, bool dead, int k, int pos, int pl, f3
 PT_DEV void retire_append(const Retire& rt, bool dead, int k, int pl, f3 c) {
   if (dead) retire_store(rt, true, k, (int)(atomicAdd(&rt.cnt[k], 1ull << 32) >> 32), pl, c);
 }
-// Queue q's share of an iteration (ptd::Queues): chunks q, q + Q, ... of the tile's ceil(N / 64); only the tile's last
-// chunk can be partial, and it is the last chunk of the queue that owns it.
-struct QueueShare {
-  int my_nq;      // chunks of this queue per iteration
-  int my_pixels;  // pixels of this queue per iteration
-  float inv_my_nq;
-};
-PT_DEV QueueShare queue_share(const BatchInfo& b, const ptd::Queues& qs, int q) {
-  const int chunks = (b.N + 63) >> 6;
-  QueueShare sh;
-  sh.my_nq = q < chunks ? (chunks - q + qs.Q - 1) / qs.Q : 0;
-  const int last_q = (chunks - 1) % qs.Q;
-  sh.my_pixels = sh.my_nq * 64 - ((q == last_q && (b.N & 63)) ? 64 - (b.N & 63) : 0);
-  sh.inv_my_nq = sh.my_nq > 0 ? 1.0f / (float)sh.my_nq : 0.0f;
-  return sh;
-}
 
 // ───────────────────────────── generate ────────────────────────────────────
 __global__ __launch_bounds__(kBlock) void k_generate(ptd::Camera cam, BatchInfo b, ptd::Queues qs, ptd::PathBuf out,
                                                      int32_t* __restrict__ cnt0) {
   const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
   const int lane = lane_id();
-  const int q = wave % qs.Q, r = wave / qs.Q, wq = qs.W / qs.Q;
+  const auto [q, r, wq] = wave_slot(wave, qs.Q, qs.W);
   const float inv_w = 1.0f / (float)cam.res_x;
   const QueueShare sh = queue_share(b, qs, q);
-  if (r == 0 && lane == 0) cnt0[(size_t)q * qs.cnt_stride] = b.K * sh.my_pixels;
+  if (r == 0 && lane == 0) cnt0[cnt_index(qs, 0, q)] = b.K * sh.my_pixels;
   const int entries = b.K * sh.my_nq;  // iteration-major: entry j = k * my_nq + jj is chunk q + jj * Q of iteration k
   for (int j = r; j < entries; j += wq) {
     int k, jj;
     divmod(j, sh.my_nq, sh.inv_my_nq, k, jj);
-    const int pl = (q + jj * qs.Q) * 64 + lane;  // tile pixel
+    const int pl = chunk_pixel(q, jj, qs.Q) + lane;  // tile pixel
     if (pl < b.N) {
       const int p = global_pixel(b, pl);  // global pixel index
       float jx = 0.f, jy = 0.f;
@@ -539,8 +519,8 @@ __global__ __launch_bounds__(kBlock) void k_intersect_legacy(SceneTables sc, ptd
   }
   const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
   const int lane = lane_id();
-  const int q = wave % qs.Q, r = wave / qs.Q, wq = qs.W / qs.Q;
-  const int n_q = cnt_in[(size_t)q * qs.cnt_stride];
+  const auto [q, r, wq] = wave_slot(wave, qs.Q, qs.W);
+  const int n_q = cnt_in[cnt_index(qs, 0, q)];
   const int64_t HS = hits.stride;
   for (int j = r; j * 64 < n_q; j += wq) {
     const int i = j * 64 + lane;
@@ -803,8 +783,8 @@ __global__ __launch_bounds__(kBlock) void k_intersect(SceneTables sc, ptd::Queue
 
   const int wave = blockIdx.x * kWavesPerBlock + wib;
   const int lane = lane_id();
-  const int q = wave % qs.Q, r = wave / qs.Q, wq = qs.W / qs.Q;
-  const int n_q = cnt_in[(size_t)q * qs.cnt_stride];
+  const auto [q, r, wq] = wave_slot(wave, qs.Q, qs.W);
+  const int n_q = cnt_in[cnt_index(qs, 0, q)];
   const int64_t HS = hits.stride;
   const int64_t qbase = (int64_t)q * qs.cap;
   // Memory operations are kept branch-free so that the compiler can count them (s_waitcnt vmcnt(N)
@@ -1135,24 +1115,22 @@ __global__ __launch_bounds__(kBlock, kPrimaryWaves) void k_primary(SceneTables s
   // which cost a bounds test) the strands differ by +-20 %: they are then cut into `pieces` runs of iterations — every
   // (queue, iteration, residue) still has ONE owner, which is all the sub-lists ask for — piece 0 stays with wave w and the
   // others go to whoever is free, in the order of a counter (zeroed by k_count_stats).
-  const int kp = b.primary_pieces > 1 && qs.deal != nullptr && !b.flat ? (b.K + b.primary_pieces - 1) / b.primary_pieces : b.K;
-  const int pieces = (b.K + kp - 1) / kp;
-  for (int strand = wave; strand < qs.W * pieces;) {
-    const int piece = strand / qs.W, sw = strand - piece * qs.W;
-    const int k0 = piece * kp, k1 = min(b.K, k0 + kp);
-    const int q = sw % qs.Q, r = sw / qs.Q, wq = qs.W / qs.Q;
+  const StrandPlan plan = strand_plan(b.K, b.primary_pieces, qs.deal != nullptr, b.flat != 0);
+  for (int strand = wave; strand < qs.W * plan.pieces;) {
+    const Strand st = strand_of(strand, plan, b.K, qs.Q, qs.W);
+    const int piece = st.piece, q = st.q, r = st.r, wq = st.wq, k0 = st.k0, k1 = st.k1;  // (lambdas below capture them)
     const Retire rt = retire_of(ret, q);
     // The wave's samples: in iteration k the chunks jj = rho, rho + wq, ... of the queue's my_nq (chunk jj = tile chunk q + jj * Q),
     // rho = (r + k) mod wq — its own sub-list and sub-region of (q, k) (pt_device.h RetireBuf): positions come from the two
     // counters below, nothing is reserved with atomics and every store is issued where its group is shaded.
     const QueueShare sh = queue_share(b, qs, q);
-    if (piece == 0 && r == 0 && lane == 0) cnt0[(size_t)q * qs.cnt_stride] = b.K * sh.my_pixels;
+    if (piece == 0 && r == 0 && lane == 0) cnt0[cnt_index(qs, 0, q)] = b.K * sh.my_pixels;
     const int64_t qbase = (int64_t)q * qs.cap;
     const float inv_w = 1.0f / (float)cam.res_x;
     const f3 o = mk(cam.pos[0], cam.pos[1], cam.pos[2]);
-    int32_t* counter = &cnt_out[(size_t)q * qs.cnt_stride];  // flat form: the queue's ONE depth-1 list
+    int32_t* counter = &cnt_out[cnt_index(qs, 0, q)];  // flat form: the queue's ONE depth-1 list
     const int quo = sh.my_nq / wq, rem = sh.my_nq % wq;
-    int ck = k0 - 1, crho = (r + k0 + wq - 1) % wq, nl = 0, nd = 0;  // iteration the counters belong to, its residue (r + ck) mod wq; survivors / retirees of the wave in it so far
+    int ck = k0 - 1, crho = strand_rho_before(r, k0, wq), nl = 0, nd = 0;  // iteration the counters belong to, its residue (r + ck) mod wq; survivors / retirees of the wave in it so far
     auto publish = [&]() {  // the finished iteration's counts (also when the wave had no chunk in it: zeros)
       if (ck >= k0 && lane == 0) rt.sub[ck * rt.wq0 + crho] = ((unsigned long long)(uint32_t)nd << 32) | (uint32_t)nl;
     };
@@ -1217,9 +1195,9 @@ __global__ __launch_bounds__(kBlock, kPrimaryWaves) void k_primary(SceneTables s
     pp.any = false;
     if constexpr (RING) ws = carry_init<true, 2>(wbase), ws.qo_tab = cam_qo, ws.cam_o = o;  // every strand starts with an empty ring
     int it = 0;
-    for (int k = k0, rho = (r + k0) % wq; k < k1; ++k, rho = rho + 1 == wq ? 0 : rho + 1) {
+    for (int k = k0, rho = strand_rho(r, k0, wq); k < k1; ++k, rho = rho + 1 == wq ? 0 : rho + 1) {
       for (int jj = rho; jj < sh.my_nq; jj += wq, ++it) {
-        const int pl_raw = (q + jj * qs.Q) * 64 + lane;
+        const int pl_raw = chunk_pixel(q, jj, qs.Q) + lane;
         const bool valid = pl_raw < b.N;
         const int pl = valid ? pl_raw : b.N - 1;  // tile pixel
         const int slot = make_slot(b, k, pl);
@@ -1262,9 +1240,9 @@ __global__ __launch_bounds__(kBlock, kPrimaryWaves) void k_primary(SceneTables s
     }
     if (!b.flat)
       while (ck < k1) next_iteration();  // the last iteration's counts, and zeros for trailing iterations without a chunk
-    if (pieces == 1) break;
+    if (plan.pieces == 1) break;
     int nx = 0;
-    if (lane == 0) nx = atomicAdd(&qs.deal[2 * qs.Q + 1], 1);
+    if (lane == 0) nx = atomicAdd(&qs.deal[deal_map(qs).strand_counter()], 1);
     strand = qs.W + __builtin_amdgcn_readfirstlane(nx);
   }
 }
@@ -1486,16 +1464,17 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
   const uint64_t t_begin = __builtin_amdgcn_s_memrealtime();  // (100 MHz, whatever the shader clock does)
   // Which queue the wave serves, as which of how many: W / Q waves per queue, or — once a batch has been measured — the
   // queue's share of the W waves by the time its waves took in the previous batch (ptd::Queues::deal).
-  int q = wave % qs.Q, r = wave / qs.Q, wq = qs.W / qs.Q;
-  if (qs.deal != nullptr && qs.deal[qs.Q] == qs.W) {
+  const DealMap dm = deal_map(qs);
+  const WaveSlot even = wave_slot(wave, qs.Q, qs.W);
+  int q = even.q, r = even.r, wq = even.wq;
+  if (qs.deal != nullptr && qs.deal[dm.made_for()] == qs.W) {
     int at_or_before = 0;  // first[] is strictly increasing: the queues whose first wave is <= this wave
-    for (int e0 = 0; e0 < qs.Q; e0 += 64) at_or_before += (int)__popcll(ballot(e0 + lane < qs.Q && qs.deal[e0 + lane] <= wave));
+    for (int e0 = 0; e0 < qs.Q; e0 += 64) at_or_before += (int)__popcll(ballot(e0 + lane < qs.Q && qs.deal[dm.first(e0 + lane)] <= wave));
     q = at_or_before - 1;
-    const int first = qs.deal[q];
-    r = wave - first, wq = qs.deal[q + 1] - first;
+    const int first = qs.deal[dm.first(q)];
+    r = wave - first, wq = qs.deal[dm.first(q + 1)] - first;
   }
   const Retire rt = retire_of(ret, q);
-  const size_t per_depth = (size_t)qs.Q * qs.cnt_stride;
   const int64_t qbase = (int64_t)q * qs.cap;
   // The queue's depth-1 rays: k_primary's sub-lists (k, rho), e = k * wq0 + rho, concatenated in that order (their survivor
   // counts — the low words of sub[e] — are final before this launch).  A wave takes pieces [p * ps, (p + 1) * ps) of the global
@@ -1522,7 +1501,7 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
       if (lane == (e0 >> 6) + j) csum = sum;
     }
   }
-  if (r == 0 && lane == 0) cnt[per_depth * 1 + (size_t)q * qs.cnt_stride] = total;  // statistics: rays traced at depth 1
+  if (r == 0 && lane == 0) cnt[cnt_index(qs, 1, q)] = total;  // statistics: rays traced at depth 1
   // The queue's ranks [0, total) are cut into pieces of `ps` paths.  Piece r is the wave's own; the pieces from wq on go, in
   // order, to whichever wave of the queue has finished what it had (a counter per queue behind ptd::Queues::deal, zeroed by
   // k_count_stats): equal numbers of depth-1 rays are not equal work — a piece's paths come from a few dozen pixel chunks, and
@@ -1532,9 +1511,7 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
   // Piece sizes fall: the pieces of level l = p / wq hold ps0 (1 - 1 / P)^l paths (not fewer than a refill's worth; tests: fewer),
   // ps0 = total / (wq P), P = paths_pieces, so that the levels add up to the queue — large pieces while everybody is busy, small
   // ones at the end, where a launch waits for the last piece (pieces of one size left half a piece of idle time per wave).
-  const int pieces_per_wave = qs.deal != nullptr && chunk_sums && (b.paths_pieces & 0xffff) > 1 ? (b.paths_pieces & 0xffff) : 1;
-  const int ps_min = b.paths_pieces >> 16;
-  const int ps0 = max((total + wq * pieces_per_wave - 1) / (wq * pieces_per_wave), ps_min);
+  const PiecePlan pieces = piece_plan(total, wq, b.paths_pieces, qs.deal != nullptr, chunk_sums);
   int ce = ne, cstart = total, ccnt = 0, clist = 0;  // cursor (wave-uniform): sub-list e = k * wq0 + rho; nothing to stream leaves it at the end
   int cord = 0;  // sub-list visits of the cursor so far
   // A window of 64 consecutive sub[] words in registers (lane l holds sub[win0 + l]): the cursor reads counts and retiree numbers
@@ -1649,21 +1626,14 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
     if (streamed >= p_hi && p_hi >= 0) {
       int nextp = -1;
       if (cord == 0) nextp = r;  // (every piece starts with a visit)
-      else if (ps0 * wq < total) {  // (level 0 does not cover the queue: there is a counter)
+      else if (pieces.needs_counter()) {
         int v = 0;
-        if (lane == 0) v = atomicAdd(&qs.deal[2 * qs.Q + 2 + q], 1);
+        if (lane == 0) v = atomicAdd(&qs.deal[dm.piece_counter(q)], 1);
         nextp = wq + __builtin_amdgcn_readfirstlane(v);
       }
-      int start = total, sz = ps0;
-      if (nextp >= 0) {
-        start = 0;
-        int level = nextp / wq;
-        const int idx = nextp - level * wq;
-        for (; level > 0 && start < total; --level) start += wq * sz, sz = max(sz - sz / pieces_per_wave, ps_min);
-        start += idx * sz;
-      }
-      if (start < total) {
-        streamed = start, p_hi = min(start + sz, total);
+      const PieceRange pr = pieces.piece_range(nextp);
+      if (pr.some) {
+        streamed = pr.start, p_hi = pr.end;
         seek(streamed);
       } else {
         p_hi = -1;
@@ -1798,7 +1768,7 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
     for (int dd = min(b.trace_depth - 1, 63); dd >= 2; --dd) {
       reached += died[dd];
       rays += reached;
-      if (reached) atomicAdd(&cnt[per_depth * dd + (size_t)q * qs.cnt_stride], reached);
+      if (reached) atomicAdd(&cnt[cnt_index(qs, dd, q)], reached);
     }
     // What this queue's paths cost, for the next batch's deal: the TIME its waves spent on them (the waves of a queue finish together
     // — they share its pieces — so the sum is waves x the queue's finishing time, and dealing in proportion to it moves the
@@ -1806,7 +1776,7 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
     // resident for 73 % of the launch with it.
     rays += reached + died[1];  // (the wave's rays: every path it took has retired somewhere)
     const int ticks = (int)min((uint64_t)(__builtin_amdgcn_s_memrealtime() - t_begin) >> 6, (uint64_t)0x3ffff);  // units of 0.64 us; a queue's sum stays below 2^31
-    if (qs.deal != nullptr && rays) atomicAdd(&qs.deal[qs.Q + 1 + q], ticks), atomicAdd(&qs.deal[3 * qs.Q + 2 + q], rays);
+    if (qs.deal != nullptr && rays) atomicAdd(&qs.deal[dm.time(q)], ticks), atomicAdd(&qs.deal[dm.rays(q)], rays);
   }
 }
 

@@ -95,16 +95,8 @@ PT_DEV void collect_body(BatchInfo b, ptd::Queues qs, ptd::RetireBuf ret, float*
   const ptd::Word4* rec = ret.rec + (int64_t)q * ret.kmax * ret.seg_cap;  // region (q, 0)
   // Records per region: flat form — my_pixels, appended from the front; otherwise one slot per pixel of the queue's my_nq chunks,
   // every one filled except the last (64 - N % 64) slots of the sub-region that holds the tile's partial last chunk.
-  int n = sh.my_pixels, g0 = 0, g1 = 0;
-  if (!b.flat) {
-    n = sh.my_nq * 64;
-    const int missing = n - sh.my_pixels;
-    if (missing > 0) {
-      const int quo = sh.my_nq / ret.wq0, rem = sh.my_nq % ret.wq0, rho = (sh.my_nq - 1) % ret.wq0;
-      g1 = (sub_offset(quo, rem, rho) + sub_chunks(quo, rem, rho)) * 64;
-      g0 = g1 - missing;
-    }
-  }
+  const int n = b.flat ? sh.my_pixels : sh.my_nq * 64;
+  const auto [g0, g1] = b.flat ? Gap{0, 0} : region_gap(sh, ret.wq0);
   for (int first = 0; first < sh.my_nq * 64; first += kCollectPixels) {  // one pass per kCollectPixels of the queue's pixels
     float acc[kCollectPPT][3];
     float rf[CONV ? kCollectPPT : 1][3];  // the reference frame's values of this thread's pixels
@@ -113,7 +105,7 @@ PT_DEV void collect_body(BatchInfo b, ptd::Queues qs, ptd::RetireBuf ret, float*
 #pragma unroll
     for (int m = 0; m < kCollectPPT; ++m) {
       const int li = first + threadIdx.x + kCollectThreads * m;
-      const int pl = (q + (li >> 6) * qs.Q) * 64 + (li & 63);
+      const int pl = slot_pixel(q, li, qs.Q);
       const bool mine = li < sh.my_nq * 64 && pl < b.N;
       acc[m][0] = mine ? image[3 * (int64_t)pl] : 0.f, acc[m][1] = mine ? image[3 * (int64_t)pl + 1] : 0.f, acc[m][2] = mine ? image[3 * (int64_t)pl + 2] : 0.f;
       if constexpr (CONV) {
@@ -165,7 +157,7 @@ PT_DEV void collect_body(BatchInfo b, ptd::Queues qs, ptd::RetireBuf ret, float*
               int t_cap = (int)threadIdx.x;
               asm volatile("" : "+v"(t_cap));  // the frame's addresses are formed here, once per render, not kept across the iteration loop
               const int li = first + t_cap + kCollectThreads * m;
-              const int pl = (q + (li >> 6) * qs.Q) * 64 + (li & 63);
+              const int pl = slot_pixel(q, li, qs.Q);
               if (mine) cv.ref[3 * (int64_t)pl] = cur.x, cv.ref[3 * (int64_t)pl + 1] = cur.y, cv.ref[3 * (int64_t)pl + 2] = cur.z;
             } else {
               const f3 d = ex::sub(cur, mk(rf[m][0], rf[m][1], rf[m][2]));
@@ -186,7 +178,7 @@ PT_DEV void collect_body(BatchInfo b, ptd::Queues qs, ptd::RetireBuf ret, float*
 #pragma unroll
     for (int m = 0; m < kCollectPPT; ++m) {
       const int li = first + t_out + kCollectThreads * m;
-      const int pl = (q + (li >> 6) * qs.Q) * 64 + (li & 63);
+      const int pl = slot_pixel(q, li, qs.Q);
       if (li < sh.my_nq * 64 && pl < b.N) image[3 * (int64_t)pl] = acc[m][0], image[3 * (int64_t)pl + 1] = acc[m][1], image[3 * (int64_t)pl + 2] = acc[m][2];
     }
   }
@@ -226,14 +218,15 @@ constexpr int kDealMaxQ = 2048;
 PT_DEV void deal_waves(const ptd::Queues& qs) {
   __shared__ int work[kDealMaxQ];
   if (qs.deal == nullptr) return;
-  if (threadIdx.x == 0) qs.deal[2 * qs.Q + 1] = 0;  // k_primary's strand counter
-  for (int q = threadIdx.x; q < qs.Q; q += blockDim.x) qs.deal[2 * qs.Q + 2 + q] = 0;  // k_paths' piece counters
-  int32_t* first = qs.deal;
-  int32_t* wk = qs.deal + qs.Q + 1;
+  const DealMap dm = deal_map(qs);
+  if (threadIdx.x == 0) qs.deal[dm.strand_counter()] = 0;
+  for (int q = threadIdx.x; q < qs.Q; q += blockDim.x) qs.deal[dm.piece_counter(q)] = 0;
+  int32_t* first = qs.deal + dm.first(0);
+  int32_t* wk = qs.deal + dm.time(0);
   const int Q = qs.Q, W = qs.paths_W;
   if (Q > kDealMaxQ || W < Q) {
-    if (threadIdx.x == 0) first[Q] = 0;
-    for (int q = threadIdx.x; q < Q; q += blockDim.x) wk[q] = 0, qs.deal[3 * Q + 2 + q] = 0;
+    if (threadIdx.x == 0) qs.deal[dm.made_for()] = 0;
+    for (int q = threadIdx.x; q < Q; q += blockDim.x) wk[q] = 0, qs.deal[dm.rays(q)] = 0;
     return;
   }
   // Whether to deal at all is decided by the RAYS the queues' paths cost (a property of the tile: the same in every batch), how by
@@ -244,7 +237,7 @@ PT_DEV void deal_waves(const ptd::Queues& qs) {
   if (threadIdx.x == 0) ray_total_s = 0ull, ray_heaviest_s = 0;
   __syncthreads();
   {
-    int32_t* rays = qs.deal + 3 * Q + 2;
+    int32_t* rays = qs.deal + dm.rays(0);
     unsigned long long sum = 0;
     int hv = 0;
     for (int q = threadIdx.x; q < Q; q += blockDim.x) sum += (unsigned long long)rays[q], hv = max(hv, rays[q]), rays[q] = 0;
@@ -253,7 +246,7 @@ PT_DEV void deal_waves(const ptd::Queues& qs) {
   }
   for (int q = threadIdx.x; q < Q; q += blockDim.x) work[q] = wk[q], wk[q] = 0;
   __syncthreads();
-  const bool close_together = (unsigned long long)ray_heaviest_s * W * Q <= ray_total_s * ((unsigned long long)W + Q);
+  const bool close_together = queues_close_together(ray_heaviest_s, ray_total_s, W, Q);
   if (threadIdx.x < 64) {
     const int lane = threadIdx.x;
     unsigned long long total = 0;
@@ -271,10 +264,10 @@ PT_DEV void deal_waves(const ptd::Queues& qs) {
         const unsigned long long up = __shfl_up(incl, off, 64);
         if (lane >= off) incl += up;
       }
-      if (e0 + lane < Q) first[e0 + lane] = e0 + lane + (int)((unsigned long long)(W - Q) * (before + incl - mine) / total);
+      if (e0 + lane < Q) first[e0 + lane] = dealt_first(e0 + lane, W, Q, before + incl - mine, total);
       before += __shfl(incl, 63, 64);
     }
-    if (lane == 0) first[Q] = total > 0 ? W : 0;
+    if (lane == 0) qs.deal[dm.made_for()] = total > 0 ? W : 0;
   }
 }
 
@@ -290,7 +283,7 @@ __global__ void k_count_stats(ptd::Queues qs, int32_t* __restrict__ cnt, int dep
   if (d > depth_count) return;
   unsigned long long acc = 0;
   for (int q = threadIdx.x; q < qs.Q; q += blockDim.x) {
-    int32_t* c = &cnt[((size_t)d * qs.Q + q) * qs.cnt_stride];
+    int32_t* c = &cnt[cnt_index(qs, d, q)];
     acc += (unsigned long long)*c;
     *c = 0;
   }

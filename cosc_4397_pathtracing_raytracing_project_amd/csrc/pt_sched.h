@@ -1,0 +1,186 @@
+// pt_sched.h — how work is dealt out: which wave traces which sample, and where a record or a counter lives.
+//
+// The kernels (pt_kernels.hip, pt_shade.inc, pt_output.inc) and the host (pt_api.cpp) take these numbers from here, so the
+// two cannot disagree.  Plain C++ (the system compiler accepts it; tests/test_sched.py sweeps every function by enumeration):
+// integer arithmetic on (N, Q, W, K, wq0, pieces) only, no pointers into device memory and no runtime calls — the structs
+// that hold device pointers (Retire, the k_paths cursor) stay in pt_kernels.hip and take their offsets from here.
+#pragma once
+#include "pt_kernels.h"
+
+#define PT_SCHED __host__ __device__ inline __attribute__((always_inline))
+
+namespace ptk {
+
+PT_SCHED int sched_min(int a, int b) { return a < b ? a : b; }
+PT_SCHED int sched_max(int a, int b) { return a > b ? a : b; }
+
+// ── ptd::Queues::deal: five regions of int32 words, back to back ──────────────────────────────────────────────────────────
+//   first(0 .. Q)      first k_paths wave of queue q; word Q (= made_for()) holds the launch width W the table was made for
+//                      (0: nothing measured, or queues close together) — any other launch width gets W / Q waves per queue
+//   time(q)            time the waves of queue q spent in this batch's k_paths launch, 0.64-us units
+//   strand_counter()   where k_primary's waves take the later pieces of the strands from
+//   piece_counter(q)   where the waves of queue q take pieces of its depth-1 rays from in k_paths
+//   rays(q)            rays the waves of queue q traced in k_paths
+// k_count_stats (deal_waves) turns time / rays into the next batch's first[] and leaves everything else zeroed.
+struct DealMap {
+  int Q;
+  PT_SCHED int first(int q) const { return q; }
+  PT_SCHED int made_for() const { return Q; }
+  PT_SCHED int time(int q) const { return Q + 1 + q; }
+  PT_SCHED int strand_counter() const { return 2 * Q + 1; }
+  PT_SCHED int piece_counter(int q) const { return 2 * Q + 2 + q; }
+  PT_SCHED int rays(int q) const { return 3 * Q + 2 + q; }
+  PT_SCHED int words() const { return 4 * Q + 2; }
+};
+PT_SCHED DealMap deal_map(const ptd::Queues& qs) { return DealMap{qs.Q}; }
+
+// first[q] of the next batch: queue q gets one wave plus its share of the other W - Q by the work of the queues in front of
+// it, so first[] is strictly increasing (every queue keeps a wave), first[0] = 0 and first[Q] = W.  (W >= Q, work_total > 0)
+PT_SCHED int dealt_first(int q, int W, int Q, unsigned long long work_before, unsigned long long work_total) {
+  return q + (int)((unsigned long long)(W - Q) * work_before / work_total);
+}
+// Queues closer together in rays than the rounding of whole waves (heaviest / mean <= 1 + Q / W) keep W / Q waves each.
+PT_SCHED bool queues_close_together(int heaviest_rays, unsigned long long total_rays, int W, int Q) {
+  return (unsigned long long)heaviest_rays * W * Q <= total_rays * ((unsigned long long)W + Q);
+}
+
+// ── queue geometry (pt_device.h Queues, RetireBuf) ────────────────────────────────────────────────────────────────────────
+// Wave `wave` of a grid of W waves (a multiple of Q) serves queue q as the r-th of its wq waves.
+struct WaveSlot {
+  int q, r, wq;
+};
+PT_SCHED WaveSlot wave_slot(int wave, int Q, int W) { return WaveSlot{wave % Q, wave / Q, W / Q}; }
+
+// Queue q's share of an iteration: chunks q, q + Q, ... of the tile's ceil(N / 64); only the tile's last chunk can be
+// partial, and it is the last chunk of the queue that owns it.
+struct QueueShare {
+  int my_nq;      // chunks of this queue per iteration
+  int my_pixels;  // pixels of this queue per iteration
+  float inv_my_nq;
+};
+PT_SCHED QueueShare queue_share(const BatchInfo& b, const ptd::Queues& qs, int q) {
+  const int chunks = (b.N + 63) >> 6;
+  QueueShare sh;
+  sh.my_nq = q < chunks ? (chunks - q + qs.Q - 1) / qs.Q : 0;
+  const int last_q = (chunks - 1) % qs.Q;
+  sh.my_pixels = sh.my_nq * 64 - ((q == last_q && (b.N & 63)) ? 64 - (b.N & 63) : 0);
+  sh.inv_my_nq = sh.my_nq > 0 ? 1.0f / (float)sh.my_nq : 0.0f;
+  return sh;
+}
+// First tile pixel of the queue's chunk jj (tile chunk q + jj * Q); lane l of a wave has pixel + l.
+PT_SCHED int chunk_pixel(int q, int jj, int Q) { return (q + jj * Q) * 64; }
+// Tile pixel of the queue's pixel slot li = jj * 64 + lane.
+PT_SCHED int slot_pixel(int q, int li, int Q) { return chunk_pixel(q, li >> 6, Q) + (li & 63); }
+
+// Sub-list / sub-region (q, k, rho) of a queue with my_nq chunks per iteration dealt to wq0 residues: c(rho) chunks, the first
+// of them off(rho) chunks into list / region (q, k)  (residue rho owns the chunks jj = rho, rho + wq0, ...).
+// (quo = my_nq / wq0, rem = my_nq % wq0, computed once per kernel)
+PT_SCHED int sub_chunks(int quo, int rem, int rho) { return quo + (rho < rem ? 1 : 0); }
+PT_SCHED int sub_offset(int quo, int rem, int rho) { return rho * quo + sched_min(rho, rem); }
+// The record slots [g0, g1) of a region that stay unused: none when the queue's chunks are whole, otherwise the last
+// 64 - N % 64 slots of the sub-region that holds the tile's partial last chunk (the queue's last chunk, my_nq - 1).
+struct Gap {
+  int g0, g1;
+};
+PT_SCHED Gap region_gap(const QueueShare& sh, int wq0) {
+  Gap g{0, 0};
+  const int missing = sh.my_nq * 64 - sh.my_pixels;
+  if (missing > 0) {
+    const int quo = sh.my_nq / wq0, rem = sh.my_nq % wq0, rho = (sh.my_nq - 1) % wq0;
+    g.g1 = (sub_offset(quo, rem, rho) + sub_chunks(quo, rem, rho)) * 64;
+    g.g0 = g.g1 - missing;
+  }
+  return g;
+}
+
+// The counter rows cnt[depth][Q], cnt_stride ints apart: the index of queue q's counter in row d, and the rows' words.
+PT_SCHED size_t cnt_index(const ptd::Queues& qs, int d, int q) { return (size_t)qs.Q * qs.cnt_stride * d + (size_t)q * qs.cnt_stride; }
+
+// What the host sizes the queues with: chunks per queue and iteration, record slots per region (queue, iteration), paths
+// per queue and batch.
+struct QueuePlan {
+  int nq, seg_cap, cap;
+};
+PT_SCHED int chunks_per_queue(int64_t N, int Q) { return (int)(((N + 63) / 64 + Q - 1) / Q); }
+PT_SCHED QueuePlan queue_plan(int64_t N, int Q, int K) {
+  QueuePlan p;
+  p.nq = chunks_per_queue(N, Q);
+  p.seg_cap = p.nq * 64;
+  p.cap = K * p.seg_cap;
+  return p;
+}
+// Entries of RetireBuf::sub per region: the waves per queue of the widest k_primary grid.
+PT_SCHED size_t sub_stride(int widest_grid_waves, int Q) { return (size_t)widest_grid_waves / Q; }
+
+// ── k_primary: strands ────────────────────────────────────────────────────────────────────────────────────────────────────
+// A strand = what one wave of one queue traces at depth 0: in iteration k the queue's chunks jj = rho, rho + wq, ... of
+// residue rho = (r + k) mod wq.  The strands are cut into `pieces` runs of kp iterations; strand index s < W is piece 0 of
+// wave s, the indices from W on (piece by piece, W each) go to whoever is free.  Every (queue, iteration, residue) has ONE owner.
+struct StrandPlan {
+  int kp, pieces;
+};
+PT_SCHED StrandPlan strand_plan(int K, int primary_pieces, bool deal_present, bool flat) {
+  StrandPlan p;
+  p.kp = primary_pieces > 1 && deal_present && !flat ? (K + primary_pieces - 1) / primary_pieces : K;
+  p.pieces = (K + p.kp - 1) / p.kp;
+  return p;
+}
+struct Strand {
+  int piece, q, r, wq, k0, k1;  // iterations [k0, k1) of wave r of queue q's wq
+};
+PT_SCHED Strand strand_of(int strand, const StrandPlan& p, int K, int Q, int W) {
+  Strand s;
+  s.piece = strand / W;
+  const WaveSlot w = wave_slot(strand - s.piece * W, Q, W);
+  s.q = w.q, s.r = w.r, s.wq = w.wq;
+  s.k0 = s.piece * p.kp, s.k1 = sched_min(K, s.k0 + p.kp);
+  return s;
+}
+PT_SCHED int strand_rho(int r, int k, int wq) { return (r + k) % wq; }
+PT_SCHED int strand_rho_before(int r, int k, int wq) { return (r + k + wq - 1) % wq; }  // rho of iteration k - 1 (k >= 0)
+// The host's choice of primary_pieces: a piece pays for its own pipeline drain, so it should hold a few dozen 64-sample
+// groups; a wave's strand has K * nq / (waves per queue) of them.
+PT_SCHED int auto_primary_pieces(int K, int nq, int wq0) {
+  const int64_t want = (int64_t)K * nq / sched_max(1, wq0) / 48;
+  return want < 1 ? 1 : want > 4 ? 4 : (int)want;
+}
+
+// ── k_paths: falling pieces ───────────────────────────────────────────────────────────────────────────────────────────────
+// BatchInfo::paths_pieces: pieces per wave | fewest paths in a piece << 16.
+PT_SCHED int pack_paths_pieces(int count, int min_piece) { return count | min_piece << 16; }
+PT_SCHED int paths_pieces_count(int word) { return word & 0xffff; }
+PT_SCHED int paths_pieces_min(int word) { return word >> 16; }
+// A queue's depth-1 ranks [0, total) cut into pieces for its wq waves.  Piece p belongs to level p / wq; a level has wq pieces
+// of one size, ps0 at level 0 and (1 - 1 / P) of the previous level's after that, never below ps_min (P = pieces_per_wave).
+// Pieces 0 .. wq - 1 are the waves' own; the later ones are handed out by the queue's counter, which exists only when
+// level 0 does not cover the queue.
+struct PieceRange {
+  int start, end;
+  bool some;  // false: no such piece (and start == end == total)
+};
+struct PiecePlan {
+  int total, wq, pieces_per_wave, ps_min, ps0;
+  PT_SCHED bool needs_counter() const { return ps0 * wq < total; }
+  PT_SCHED PieceRange piece_range(int nextp) const {  // nextp < 0: none
+    int start = total, sz = ps0;
+    if (nextp >= 0) {
+      start = 0;
+      int level = nextp / wq;
+      const int idx = nextp - level * wq;
+      for (; level > 0 && start < total; --level) start += wq * sz, sz = sched_max(sz - sz / pieces_per_wave, ps_min);
+      start += idx * sz;
+    }
+    return start < total ? PieceRange{start, sched_min(start + sz, total), true} : PieceRange{total, total, false};
+  }
+};
+// (pieces only with a deal table behind the counters and with k_paths' chunk sums, i.e. at most 4096 sub-lists)
+PT_SCHED PiecePlan piece_plan(int total, int wq, int paths_pieces, bool deal_present, bool chunk_sums) {
+  PiecePlan p;
+  p.total = total, p.wq = wq;
+  p.pieces_per_wave = deal_present && chunk_sums && paths_pieces_count(paths_pieces) > 1 ? paths_pieces_count(paths_pieces) : 1;
+  p.ps_min = paths_pieces_min(paths_pieces);
+  p.ps0 = sched_max((total + wq * p.pieces_per_wave - 1) / (wq * p.pieces_per_wave), p.ps_min);
+  return p;
+}
+
+}  // namespace ptk

@@ -176,9 +176,9 @@ __global__ __launch_bounds__(kBlock) void k_shade(SceneTables sc, BatchInfo b, i
 
   const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
   const int lane = lane_id();
-  const int q = wave % qs.Q, r = wave / qs.Q, wq = qs.W / qs.Q;
+  const auto [q, r, wq] = wave_slot(wave, qs.Q, qs.W);
   const Retire rt = retire_of(ret, q);
-  const int n_q = cnt_in[(size_t)q * qs.cnt_stride];
+  const int n_q = cnt_in[cnt_index(qs, 0, q)];
   const int64_t HS = hits.stride;
   const int64_t qbase = (int64_t)q * qs.cap;
   // inputs of one path; the next group's are loaded (branch-free, index clamped into the queue's own
@@ -222,7 +222,7 @@ __global__ __launch_bounds__(kBlock) void k_shade(SceneTables sc, BatchInfo b, i
     const bool alive = valid && s.alive;
     const unsigned long long live = ballot(alive);
     int base = 0;
-    if (live && lane == 0) base = atomicAdd(&cnt_out[(size_t)q * qs.cnt_stride], (int)__popcll(live));
+    if (live && lane == 0) base = atomicAdd(&cnt_out[cnt_index(qs, 0, q)], (int)__popcll(live));
     if (alive) shade_bounce(bo, cur.hn, cur.hp, s);
     if (live) {
       base = __builtin_amdgcn_readfirstlane(base);

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Static instruction counts and register use of the traversal kernels and the gather (k_collect, k_collect_conv) in gfx950 assembly files.
+"""Static instruction counts and register use of the traversal kernels, the gather (k_collect, k_collect_conv) and the kernels that only
+deal work out (k_generate, k_shade, k_count_stats) in gfx950 assembly files.
 usage: tools/isa_counts.py file.s [file.s ...]"""
 import re, sys
 for path in sys.argv[1:]:
@@ -31,6 +32,6 @@ for path in sys.argv[1:]:
         regs[m.group(1)] = (v.group(1) if v else "?", sp.group(1) if sp else "?")
     print(path)
     for k, v in cnt.items():
-        if any(w in k for w in ("k_paths", "k_primary", "k_intersect", "k_collect")):
+        if any(w in k for w in ("k_paths", "k_primary", "k_intersect", "k_collect", "k_generate", "k_shade", "k_count_stats")):
             short = re.sub(r"^_ZN3ptk\d+\w+?_GLOBAL__N_1\d+", "", k)[:34]
             print(f"  {short:36s} VALU {v[0]:5d} SALU {v[1]:5d} LDS {v[2]:4d} VMEM {v[3]:4d}  vgpr/spill {regs.get(k)}")
