@@ -20,6 +20,7 @@ LIB_PATH = os.environ.get("PT_AMD_LIB") or os.path.join(_PKG, "libpt_amd.so")
 PT_MAX_DEPTH = 64
 ARITH = {"exact": 0, "fma": 1, "fast": 2}  # PT_ARITH_* (include/pt_amd.h)
 ARITH_NAMES = {v: k for k, v in ARITH.items()}
+FEATURE_PLANES = 3            # PT_FEATURE_PLANES
 CONVERGENCE_WAVES = 16        # PT_CONVERGENCE_WAVES
 CONVERGENCE_CAPACITY = 65536  # PT_CONVERGENCE_CAPACITY: iterations the convergence metric keeps a value for
 FLT_MAX = float(np.finfo(np.float32).max)
@@ -168,6 +169,15 @@ def lib() -> C.CDLL:
     L.pt_group_set_reference.argtypes = [C.c_void_p, _fp]
     L.pt_group_get_convergence.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
     L.pt_group_iterations_to_clean.argtypes = [C.c_void_p, C.c_float, _ip]
+    if hasattr(L, "pt_render_features"):  # absent from older A/B builds of the library (tools/build_rev.sh)
+        L.pt_render_features.argtypes = [C.c_int, C.c_int]
+        L.pt_readback_features.argtypes = [_fp]
+        L.pt_ctx_render_features.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.pt_ctx_readback_features.argtypes = [C.c_void_p, _fp]
+        L.pt_ctx_device_features.argtypes = [C.c_void_p]
+        L.pt_ctx_device_features.restype = C.c_void_p
+        L.pt_group_render_features.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.pt_group_gather_features.argtypes = [C.c_void_p, _fp]
     _lib = L
     return L
 
@@ -306,6 +316,15 @@ def make_options(device: int = 0, pixel_begin: int = 0, pixel_count: int = 0, it
     return opt
 
 
+def split_features(planes: np.ndarray) -> dict:
+    """The feature SUM planes [PT_FEATURE_PLANES, n, 4] (pt_readback_features) by name: normal [n, 3], depth [n] (sum of t),
+    albedo [n, 3], hits [n], position [n, 3], object_id [n] int32 (1 + geom index of the last iteration, 0 = miss)."""
+    p = planes.reshape(FEATURE_PLANES, -1, 4)
+    return dict(normal=np.ascontiguousarray(p[0, :, :3]), depth=np.ascontiguousarray(p[0, :, 3]),
+                albedo=np.ascontiguousarray(p[1, :, :3]), hits=np.ascontiguousarray(p[1, :, 3]),
+                position=np.ascontiguousarray(p[2, :, :3]), object_id=np.ascontiguousarray(p[2, :, 3]).view(np.int32))
+
+
 class Renderer:
     """pathtraceInit / pathtrace / pathtraceFree over the C ABI (the default instance, like the reference's
     file-scope renderer state).  `arith`: "exact" (bit-identical to the oracle), "fma" or "fast" (PT_ARITH_*)."""
@@ -357,6 +376,17 @@ class Renderer:
     def clear(self) -> None:
         """Restart the accumulation (SUM image and statistics zeroed) on the same, already touched buffers."""
         _check(lib().pt_clear())
+
+    # ---- first-hit feature buffers (include/pt_amd.h: pt_render_features) ----
+    def render_features(self, iter_first: int, iter_count: int) -> None:
+        """Adds what the camera rays of iterations iter_first .. iter_first + iter_count - 1 see to the feature SUM buffers."""
+        _check(lib().pt_render_features(int(iter_first), int(iter_count)))
+
+    def readback_features(self) -> dict:
+        """The feature SUM buffers of the tile by name (split_features)."""
+        out = np.empty((FEATURE_PLANES, self.n, 4), np.float32)
+        _check(lib().pt_readback_features(_f(out)))
+        return split_features(out)
 
     # ---- convergence metric (make_options(convergence=...)) ----
     def set_reference(self, rgb_avg: np.ndarray) -> None:
@@ -453,6 +483,16 @@ class Group:
         out = np.empty((w * h, 3), np.float32)
         _check(lib().pt_group_gather(self._h, _f(out)))
         return out
+
+    def render_features(self, iter_first: int, iter_count: int) -> None:
+        _check(lib().pt_group_render_features(self._h, int(iter_first), int(iter_count)))
+
+    def gather_features(self) -> dict:
+        """The feature SUM buffers of the whole frame by name (split_features), raw orientation."""
+        w, h = self.scene.resolution
+        out = np.empty((FEATURE_PLANES, w * h, 4), np.float32)
+        _check(lib().pt_group_gather_features(self._h, _f(out)))
+        return split_features(out)
 
     def gather_u8(self, samples: float) -> np.ndarray:
         w, h = self.scene.resolution

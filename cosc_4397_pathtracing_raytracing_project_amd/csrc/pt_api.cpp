@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -108,6 +109,9 @@ struct PtContext {
   ptd::HitBuf hits{};
   ptd::RetireBuf ret{};  // retirement records + fill levels (pt_device.h)
   float* d_image = nullptr;
+  // First-hit feature buffers (pt_ctx_render_features): PT_FEATURE_PLANES planes of N float4 sums; absent until the first feature pass
+  float4* d_feat = nullptr;
+  int grid_features = 0;
   // Convergence metric (PtOptions.convergence, pt_kernels.h ConvInfo): all of it absent when the option is 0
   int conv = 0;                // the option: N > 0 capture the frame at iteration N, -1 supplied
   bool conv_live = false;      // off while setup() renders its timing batches: they leave no trace in the curve or the frame
@@ -763,6 +767,51 @@ int pt_ctx_render(PtContext* c, int iter_first, int iter_count) {
   return 0;
 }
 
+// ---- first-hit feature buffers (csrc/pt_features.inc) --------------------------------------------
+int pt_ctx_render_features(PtContext* c, int iter_first, int iter_count) {
+  if (need(c, "pt_render_features")) return -1;
+  Ctx& g = *c;
+  if (iter_first < 1 || iter_count < 0 || (int64_t)iter_first + iter_count - 1 > INT32_MAX)
+    return fail("pt_render_features: iterations %d, +%d: the first is >= 1, the count >= 0", iter_first, iter_count);
+  if (g.failed) return fail("pt_render_features: an earlier batch of this context failed (%s); free it and create a new one", g_err.c_str());
+  HIP_OK(hipSetDevice(g.device));
+  const ptk::SceneTables sc = tables(g);
+  if (!g.d_feat) {  // first feature pass of the context: the buffer, zeroed, and the launch width
+    static_assert(sizeof(float4) == 16, "a feature plane holds 16 bytes per pixel");
+    if (dalloc(g, &g.d_feat, (size_t)PT_FEATURE_PLANES * g.N)) return -1;
+    HIP_OK(hipMemsetAsync(g.d_feat, 0, (size_t)PT_FEATURE_PLANES * g.N * sizeof(float4), g.stream));
+  }
+  if (iter_count == 0) return 0;
+  // one wave per group of 64 pixels, no more workgroups than are resident (the table placement can differ between calls: debug grids)
+  const int groups = (g.N + 63) / 64;
+  g.grid_features = std::min((groups + ptk::kWavesPerBlock - 1) / ptk::kWavesPerBlock,
+                             g.num_cus * std::min(g.cap_bpc, g.k->resident_blocks_per_cu(ptk::kFeatures, sc)));
+  ptk::BatchInfo b{};
+  b.iter_first = iter_first;
+  b.K = iter_count;
+  b.N = g.N;
+  b.pixel_begin = g.pixel_begin;
+  b.trace_depth = g.depth;
+  b.aa_jitter = g.aa_jitter ? 1 : 0;
+  b.stripe = g.stripe;
+  b.gap = g.stripe ? g.stripe_stride - g.stripe : 0;
+  b.inv_stripe = g.stripe ? 1.0f / (float)g.stripe : 0.0f;
+  g.k->features(g.stream, g.grid_features, sc, g.dcam, b, g.d_feat);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int pt_ctx_readback_features(PtContext* c, float* planes_host) {
+  if (need(c, "pt_readback_features")) return -1;
+  if (!planes_host) return fail("pt_readback_features: null buffer");
+  if (!c->d_feat) return fail("pt_readback_features: no feature pass has been rendered (pt_render_features)");
+  HIP_OK(hipSetDevice(c->device));
+  HIP_OK(hipMemcpyAsync(planes_host, c->d_feat, (size_t)PT_FEATURE_PLANES * c->N * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+  return pt_ctx_sync(c);
+}
+
+const float* pt_ctx_device_features(PtContext* c) { return c ? reinterpret_cast<const float*>(c->d_feat) : nullptr; }
+
 int pt_ctx_sync(PtContext* c) {
   if (need(c, "pt_sync")) return -1;
   HIP_OK(hipSetDevice(c->device));
@@ -894,6 +943,7 @@ int pt_ctx_clear(PtContext* c) {
   if (need(c, "pt_clear")) return -1;
   if (pt_ctx_sync(c)) return -1;
   HIP_OK(hipMemsetAsync(c->d_image, 0, 3 * (size_t)c->N * sizeof(float), c->stream));
+  if (c->d_feat) HIP_OK(hipMemsetAsync(c->d_feat, 0, (size_t)PT_FEATURE_PLANES * c->N * sizeof(float4), c->stream));  // sums and object ids
   if (c->conv) {  // forget the curve, re-arm the capture (a supplied frame stays)
     HIP_OK(hipMemsetAsync(c->d_sse, 0xff, (size_t)PT_CONVERGENCE_CAPACITY * sizeof(double), c->stream));
     c->conv_last = 0;
@@ -964,6 +1014,8 @@ int pt_preview_rgba8_device(int iterations, void* rgba_dev) { return pt_ctx_prev
 int pt_get_stats(PtStats* out) { return pt_ctx_get_stats(g_default, out); }
 int pt_reset_stats(void) { return pt_ctx_reset_stats(g_default); }
 int pt_clear(void) { return pt_ctx_clear(g_default); }
+int pt_render_features(int iter_first, int iter_count) { return pt_ctx_render_features(g_default, iter_first, iter_count); }
+int pt_readback_features(float* planes_host) { return pt_ctx_readback_features(g_default, planes_host); }
 int pt_set_reference(const float* rgb_avg_host) { return pt_ctx_set_reference(g_default, rgb_avg_host); }
 int pt_get_convergence(int iter_first, int iter_count, double* sse) { return pt_ctx_get_convergence(g_default, iter_first, iter_count, sse); }
 int pt_iterations_to_clean(float threshold_db, int* iteration) { return pt_ctx_iterations_to_clean(g_default, threshold_db, iteration); }

@@ -57,6 +57,8 @@ struct PtGroup {
   std::vector<uint8_t*> d_prev;  // per device: RGBA8 preview of its tile (sendImageToPBO)
   uint8_t* d_recv_prev = nullptr;  // root: preview tiles of devices 1..n-1 / assembled preview (kept: previews recur)
   uint8_t* d_full_prev = nullptr;
+  float* d_recv_feat = nullptr;  // root: one feature plane of the tiles of devices 1..n-1 (16 B per pixel) / the assembled planes
+  float* d_full_feat = nullptr;
 };
 
 namespace {
@@ -75,7 +77,7 @@ void release(PtGroup* g) {
     }
   if (!g->devices.empty()) (void)hipSetDevice(g->devices[0]);
   for (void* p : {(void*)g->d_recv, (void*)g->d_full, (void*)g->d_recv8, (void*)g->d_full8, (void*)g->d_recv_prev,
-                  (void*)g->d_full_prev})
+                  (void*)g->d_full_prev, (void*)g->d_recv_feat, (void*)g->d_full_feat})
     if (p) (void)hipFree(p);
   for (size_t i = 0; i < g->d_prev.size(); ++i)
     if (g->d_prev[i]) {
@@ -252,6 +254,35 @@ int pt_group_gather(PtGroup* g, float* rgb_sum_host) {
     if (place_rows(g, i, i == 0 ? pt_ctx_device_image(g->ctx[0]) : g->d_recv + 3 * g->recv_off[i], g->d_full, 12))
       return fail_after_drain(g);
   HIP_OK(hipMemcpyAsync(rgb_sum_host, g->d_full, frame * 12, hipMemcpyDeviceToHost, (hipStream_t)pt_ctx_stream(g->ctx[0])));
+  return pt_group_sync(g);
+}
+
+// First-hit feature buffers (pt_ctx_render_features) of the whole frame: every context sums its own rows; the planes meet like
+// the image, one exchange + row placement per plane with 16 bytes per pixel.
+int pt_group_render_features(PtGroup* g, int iter_first, int iter_count) {
+  if (!g) return pt_fail("pt_group_render_features: null group");
+  for (PtContext* c : g->ctx)
+    if (pt_ctx_render_features(c, iter_first, iter_count)) return -1;
+  return 0;
+}
+
+int pt_group_gather_features(PtGroup* g, float* planes_host) {
+  if (!g || !planes_host) return pt_fail("pt_group_gather_features: bad argument");
+  const size_t frame = (size_t)g->W * g->H;
+  for (PtContext* c : g->ctx)
+    if (!pt_ctx_device_features(c)) return pt_fail("pt_group_gather_features: no feature pass has been rendered (pt_group_render_features)");
+  HIP_OK(hipSetDevice(g->devices[0]));
+  if (g->n == 1) return pt_ctx_readback_features(g->ctx[0], planes_host);
+  if (!g->d_full_feat) HIP_OK(hipMalloc((void**)&g->d_full_feat, PT_FEATURE_PLANES * frame * 16));
+  if (!g->d_recv_feat) HIP_OK(hipMalloc((void**)&g->d_recv_feat, g->recv_pixels * 16));
+  for (int pl = 0; pl < PT_FEATURE_PLANES; ++pl) {  // the root's stream orders plane pl + 1's receives behind plane pl's placement
+    auto tile = [&](int i) { return pt_ctx_device_features(g->ctx[i]) + 4 * (size_t)pl * pt_ctx_pixel_count(g->ctx[i]); };
+    if (exchange(g, ncclFloat, 4, g->d_recv_feat, tile)) return fail_after_drain(g);
+    HIP_OK(hipSetDevice(g->devices[0]));
+    for (int i = 0; i < g->n; ++i)
+      if (place_rows(g, i, i == 0 ? tile(0) : g->d_recv_feat + 4 * g->recv_off[i], g->d_full_feat + 4 * pl * frame, 16)) return fail_after_drain(g);
+  }
+  HIP_OK(hipMemcpyAsync(planes_host, g->d_full_feat, PT_FEATURE_PLANES * frame * 16, hipMemcpyDeviceToHost, (hipStream_t)pt_ctx_stream(g->ctx[0])));
   return pt_group_sync(g);
 }
 

@@ -97,7 +97,7 @@ struct ConvInfo {
 // Resident workgroups per CU for each persistent kernel (hipOccupancyMaxActiveBlocksPerMultiprocessor),
 // so that grid = CUs * blocks never exceeds what is co-resident: work is dealt statically to waves,
 // a workgroup that has to wait for a free slot would run its whole share after everybody else.
-enum KernelId { kGenerate = 0, kIntersect = 1, kShade = 2, kIntersectLegacy = 3, kPrimary = 4, kPaths = 5 };
+enum KernelId { kGenerate = 0, kIntersect = 1, kShade = 2, kIntersectLegacy = 3, kPrimary = 4, kPaths = 5, kFeatures = 6 };
 
 // pt_kernels.hip is compiled once per arithmetic mode (PtOptions.arith, include/pt_amd.h):
 //   0 exact  -ffp-contract=off, every operation in the reference's order: bit-identical to oracle/pt_oracle.cpp
@@ -156,6 +156,10 @@ struct KernelApi {
   // `collect` with the convergence metric: additionally sse[iter_first + k - 1] = sum over the tile's pixels of the squared error of
   // iteration iter_first + k against the reference frame, for first_k <= k < K (a second, small launch adds the gather's partial sums).
   void (*collect_conv)(hipStream_t s, const BatchInfo& b, const ptd::Queues& qs, ptd::RetireBuf ret, float* image_rgb, const ConvInfo& cv, double* sse);
+  // First-hit feature buffers (pt_features.inc; include/pt_amd.h pt_render_features): for the b.K iterations from b.iter_first, the
+  // camera ray of every tile pixel as depth 0 generates it, its closest hit in the depth-0 arithmetic, added to the three planes
+  // of b.N float4 behind `feat` (normal + t | material colour + hit count | point + object id of the last iteration).
+  void (*features)(hipStream_t s, int grid, const SceneTables& sc, const ptd::Camera& cam, const BatchInfo& b, float4* feat);
   int boxes_center_half;  // 1: the bounce kernels of this build expect SceneTables::*_b as centre / half extent (the fast build)
 };
 const KernelApi* api_exact();

@@ -13,6 +13,7 @@
 //                into the image in iteration order)
 //   k_preview    sendImageToPBO          src/pathtrace.cu:250-268
 //   k_save_u8    saveImage + savePNG     src/main.cpp:86-107, src/image.cpp:22-39
+//   k_features   (no counterpart) first-hit feature buffers: generate + intersect of depth 0 summed per pixel (pt_features.inc)
 // and the two kernels the default pipeline actually runs, which fuse the above so that neither the primary ray nor the
 // hit record ever goes through HBM, and no path state after depth 0:
 //   k_primary    depth 0:  generate + intersect + shade + compaction into one depth-1 list per (queue, iteration)
@@ -1808,6 +1809,7 @@ __global__ __launch_bounds__(kBlock) void k_shade_stage(SceneTables sc, int trac
   }
 }
 
+#include "pt_features.inc"
 #include "pt_output.inc"
 #include "pt_launch.inc"
 const KernelApi kApi = {
@@ -1820,7 +1822,7 @@ const KernelApi kApi = {
 #endif
     launch_generate, launch_primary, launch_intersect, launch_shade, launch_collect, launch_count_stats,
     launch_preview, launch_save_u8, launch_shade_stage, lds_table_limit, resident_blocks_per_cu, launch_ieee_check, launch_paths,
-    launch_collect_conv, kFast ? 1 : 0};
+    launch_collect_conv, launch_features, kFast ? 1 : 0};
 
 }  // namespace
 }  // namespace PT_NS

@@ -15,6 +15,16 @@ template <typename F>
 void with_intersect(const SceneTables& sc, bool legacy, bool exact, F&& f) {
   exact ? with_intersect_of<kD0>(sc, legacy, f) : with_intersect_of<false>(sc, legacy, f);
 }
+// The LDS-table kernel variants assume that every leaf is a top-list entry (no subtrees).
+bool leaves_fit_top(const SceneTables& sc) { return (sc.num_nodes + 1) / 2 <= kMaxTop; }
+// k_features: k_intersect's LDS map; scenes whose tables stay in memory and whose leaves do not all fit the top list take the
+// packet scan (every ray of a group starts at the camera), the others the top list
+template <typename F>
+void with_features(const SceneTables& sc, F&& f) {
+  if (tables_in_lds(sc)) return f(k_features<true, false>, intersect_lds<true>(sc).total);
+  if (leaves_fit_top(sc)) return f(k_features<false, false>, intersect_lds<false>(sc).total);
+  return f(k_features<false, true>, intersect_lds<false>(sc).total);
+}
 template <typename F>
 void with_primary(const SceneTables& sc, F&& f) {
   switch (search_form(sc)) {
@@ -67,8 +77,6 @@ auto occupancy_into(int& n, int fallback) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, kBlock, lds) != hipSuccess) n = fallback;
   };
 }
-// The LDS-table kernel variants assume that every leaf is a top-list entry (no subtrees).
-bool leaves_fit_top(const SceneTables& sc) { return (sc.num_nodes + 1) / 2 <= kMaxTop; }
 // Stage the scene tables in LDS only if every leaf is a top-list entry and staging does not cost the dominant kernel
 // (k_paths) a resident block per CU against its form with the tables in memory.
 int lds_table_limit(const SceneTables& sc, int forced_bytes) {
@@ -101,6 +109,7 @@ int resident_blocks_per_cu(KernelId id, const SceneTables& sc) {
     case kPrimary: with_primary(sc, query_share); break;
     case kPaths: with_paths(resolve_scan_nodes(sc), search_form(sc), query_share); break;
     case kShade: query(k_shade, shade_lds<true>(sc).total); break;
+    case kFeatures: with_features(sc, query); break;
   }
   if (n < 1) n = 1;
   n = min(n, max(1, lds_share_limit(lds)));
@@ -120,6 +129,14 @@ void launch_intersect(hipStream_t s, int grid, const SceneTables& sc, const ptd:
 void launch_primary(hipStream_t s, int grid, const SceneTables& sc, const ptd::Camera& cam, const BatchInfo& b,
                     const ptd::Queues& qs, int32_t* cnt0, int32_t* cnt_out, ptd::PathBuf out, ptd::RetireBuf ret) {
   with_primary(sc, [&](auto kernel, int lds) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, sc, cam, b, qs, cnt0, cnt_out, out, ret); });
+}
+
+void launch_features(hipStream_t s, int grid, const SceneTables& sc, const ptd::Camera& cam, const BatchInfo& b, float4* feat) {
+  with_features(sc, [&](auto kernel, int lds) {
+    // tables of up to kLdsTableBytes plus the waves' blocks: above the 64 KB a kernel gets without asking
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, sc, cam, b, feat);
+  });
 }
 
 void launch_paths(hipStream_t s, int grid, const SceneTables& sc_in, const BatchInfo& b, const ptd::Queues& qs, int32_t* cnt, ptd::PathBuf in, ptd::RetireBuf ret) {

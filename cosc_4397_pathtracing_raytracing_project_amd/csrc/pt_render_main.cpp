@@ -5,7 +5,7 @@
 //
 //   pt_render SCENE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr]
 //                       [--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa]
-//                       [--preview N] [--convergence N | --reference FILE.pfm] [--clean-db X]
+//                       [--preview N] [--convergence N | --reference FILE.pfm] [--clean-db X] [--features]
 //
 // Without --gpus the run goes through the pathtrace.h-compatible shim (pathtraceInit / pathtrace per
 // iteration / pathtraceFree), i.e. the code path a reference main.cpp would take.  With --gpus K (K >= 1;
@@ -19,6 +19,9 @@
 // (the reference's computePSNR: N = 10) or against an averaged-radiance image as --pfm writes it (e.g. a 5000-spp render): after
 // the render one line `iteration psnr_db` per iteration ("Inf" where the reference prints it) and "Iterations to clean: n", the
 // first iteration above --clean-db (default 35; -1 when there is none).  Works with --gpus / --devices.
+// --features: after the render a first-hit feature pass over the same iterations (pt_render_features / pt_group_render_features);
+// the averages go to <base>.normal.pfm, <base>.albedo.pfm, <base>.position.pfm and <base>.depth.pfm (depth in all three
+// channels) next to the image, written like --pfm writes the image (sums / spp).
 // Output name: PREFIX.<spp>samp.png, or with --stamp the reference's own
 // <FILE>.<UTC start time>.<spp>samp.png (main.cpp:99-102).
 #include <hip/hip_runtime.h>
@@ -39,12 +42,12 @@ int main(int argc, char** argv) {
   if (argc < 2) {
     std::printf("Usage: %s SCENEFILE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] "
                 "[--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa] [--preview N] "
-                "[--convergence N | --reference FILE.pfm] [--clean-db X]\n", argv[0]);
+                "[--convergence N | --reference FILE.pfm] [--clean-db X] [--features]\n", argv[0]);
     return 1;
   }
   int rw = 0, rh = 0, spp = 0, depth = 0, gpus = -1, arith = PT_ARITH_EXACT, preview = 0, transport = PT_GROUP_TRANSPORT_AUTO;
   std::vector<int> device_list;
-  bool pfm = false, hdr = false, stamp = false, aa = false;
+  bool pfm = false, hdr = false, stamp = false, aa = false, features = false;
   int convergence = 0;
   float clean_db = 35.0f;
   std::string out, reference;
@@ -86,6 +89,7 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[i], "--pfm")) pfm = true;
     else if (!std::strcmp(argv[i], "--hdr")) hdr = true;  // the Radiance file of image::saveHDR (main.cpp:106, commented out there)
     else if (!std::strcmp(argv[i], "--stamp")) stamp = true;
+    else if (!std::strcmp(argv[i], "--features")) features = true;  // first-hit feature buffers next to the image
     else if (!std::strcmp(argv[i], "--aa")) aa = true;  // extension: stochastic anti-aliasing (PtOptions.aa_jitter)
     else if (!std::strcmp(argv[i], "--arith") && i + 1 < argc) {
       const char* a = argv[++i];
@@ -149,6 +153,20 @@ int main(int argc, char** argv) {
     std::printf("Iterations to clean: %d\n", clean);
   };
 
+  // --features: the SUM planes (pt_readback_features' layout for the whole frame) as four three-channel PFM files
+  auto save_features = [&](const std::vector<float>& planes) {
+    const size_t n = (size_t)W * H;
+    std::vector<float> rgb(3 * n);
+    const struct { const char* name; int plane; bool w_only; } files[] = {{"normal", 0, false}, {"albedo", 1, false}, {"position", 2, false}, {"depth", 0, true}};
+    for (const auto& f : files) {
+      const float* src = planes.data() + 4 * n * f.plane;
+      for (size_t p = 0; p < n; ++p)
+        for (int c = 0; c < 3; ++c) rgb[3 * p + c] = src[4 * p + (f.w_only ? 3 : c)];
+      const std::string path = base + "." + f.name + ".pfm";
+      if (pt_save_pfm(path.c_str(), rgb.data(), W, H, (float)iters) == 0) std::printf("Saved %s.\n", path.c_str());
+    }
+  };
+
   double secs = 0;
   if (gpus < 0) {
     // the reference's call sequence (main.cpp:133-152) through the pathtrace.h shim
@@ -175,6 +193,14 @@ int main(int argc, char** argv) {
       std::printf("Saved %s.pfm.\n", base.c_str());
     if (hdr && pt_save_hdr((base + ".hdr").c_str(), scene->state.image.data(), W, H, (float)iters) == 0)
       std::printf("Saved %s.hdr.\n", base.c_str());
+    if (features) {
+      std::vector<float> planes((size_t)PT_FEATURE_PLANES * W * H * 4);
+      if (pt_render_features(1, iters) || pt_readback_features(planes.data())) {
+        std::fprintf(stderr, "HIP error (pt_render_features): %s\n", pt_last_error());
+        return EXIT_FAILURE;
+      }
+      save_features(planes);
+    }
     if (convergence) {
       std::vector<float> psnr((size_t)iters);
       for (int it = 1; it <= iters; ++it) psnr[it - 1] = pathtracePSNR(it);  // what the reference prints after every iteration
@@ -254,6 +280,14 @@ int main(int argc, char** argv) {
         std::printf("Saved %s.pfm.\n", base.c_str());
       if (hdr && pt_save_hdr((base + ".hdr").c_str(), scene->state.image.data(), W, H, (float)iters) == 0)
         std::printf("Saved %s.hdr.\n", base.c_str());
+    }
+    if (features) {
+      std::vector<float> planes((size_t)PT_FEATURE_PLANES * W * H * 4);
+      if (pt_group_render_features(grp, 1, iters) || pt_group_gather_features(grp, planes.data())) {
+        std::fprintf(stderr, "HIP error (pt_group_render_features): %s\n", pt_last_error());
+        return EXIT_FAILURE;
+      }
+      save_features(planes);
     }
     if (convergence) {
       std::vector<double> sse((size_t)iters);

@@ -299,6 +299,30 @@ int pt_iterations_to_clean(float threshold_db, int* iteration);
  * else 10.0f * log10f(1.0f / float(mse)). */
 float pt_psnr_from_sse(double sse, int64_t pixels);
 
+/* ---- first-hit feature buffers: what the camera ray of every sample sees, summed per tile pixel (for a denoiser, an edge-avoiding
+ * filter, per-object decisions, compositing).  For tile pixel p and iteration i the camera ray is the one depth 0 of pt_render
+ * traces for sample (i, global pixel) — generateRayFromCamera, plus PtOptions.aa_jitter when the renderer has it on — and its
+ * closest hit is computeIntersections' record: t, world normal, intersection point, geom.  The renderer keeps a SUM buffer of
+ * PT_FEATURE_PLANES planes, each pixel_count float4 in tile order:
+ *     plane   .x .y .z                                                   .w
+ *     0       sum of the normals                                         sum of t over the iterations that hit
+ *     1       sum of materials[geoms[g].materialid].color                number of iterations that hit (a float)
+ *             (any material, emitters too)
+ *     2       sum of the intersection points                             object id of the LAST iteration added: the int32 bit
+ *                                                                        pattern of 1 + index in PtSceneDesc.geoms, 0 = miss
+ *                                                                        (or nothing rendered yet)
+ * A miss adds +0 to every sum.  Every sum is a float32 running sum in iteration order, ((s + v_a) + v_a+1) + ..., plain adds:
+ * without anti-aliasing the same value is added iter_count times (not multiplied).  Depth 0 runs the reference's arithmetic in
+ * every PT_ARITH_* mode, so the buffers are the same bit for bit in all three.  They accumulate across calls like the image and
+ * independently of it (pt_render neither reads nor writes them, PtStats.samples / live_rays do not count feature passes);
+ * pt_clear zeroes them, ids included.  Memory: 48 bytes per tile pixel, allocated and zeroed by the first pt_render_features
+ * call (iter_count == 0 allocates and does nothing else) and part of PtStats.device_bytes from then on; pt_init and pt_render
+ * allocate and launch nothing for them.  A call reads and writes the buffer once (96 B per pixel) whatever iter_count is.
+ * iter_first < 1 or iter_count < 0 is an error, as is a readback before the first feature pass. */
+#define PT_FEATURE_PLANES 3
+int pt_render_features(int iter_first, int iter_count); /* asynchronous on the renderer's stream, like pt_render */
+int pt_readback_features(float* planes_host);          /* PT_FEATURE_PLANES * pixel_count * 4 floats; synchronises */
+
 /* saveImage()'s per-pixel conversion (main.cpp:91-97 x mirror, image.cpp:26-30 clamp * 255 truncated) on the
  * device: pixel_count*3 bytes, row-major, x mirrored inside each row; the tile must consist of whole rows.
  * Reads back 3 B per pixel instead of 12. */
@@ -322,6 +346,9 @@ int pt_ctx_clear(PtContext* c);
 int pt_ctx_set_reference(PtContext* c, const float* rgb_avg_host);
 int pt_ctx_get_convergence(PtContext* c, int iter_first, int iter_count, double* sse);
 int pt_ctx_iterations_to_clean(PtContext* c, float threshold_db, int* iteration);
+int pt_ctx_render_features(PtContext* c, int iter_first, int iter_count);
+int pt_ctx_readback_features(PtContext* c, float* planes_host);
+const float* pt_ctx_device_features(PtContext* c); /* device pointer of plane 0; the planes are contiguous; NULL before the first pt_ctx_render_features */
 const float* pt_ctx_device_image(PtContext* c); /* device pointer of the tile SUM image */
 void* pt_ctx_stream(PtContext* c);              /* the context's hipStream_t */
 int pt_ctx_pixel_count(const PtContext* c);
@@ -354,6 +381,10 @@ int pt_group_render(PtGroup* g, int iter_first, int iter_count); /* asynchronous
 int pt_group_sync(PtGroup* g);
 int pt_group_gather(PtGroup* g, float* rgb_sum_host);             /* W*H*3 floats, raw orientation */
 int pt_group_gather_u8(PtGroup* g, float samples, uint8_t* rgb8_host); /* W*H*3 bytes as pt_save_u8, converted on each device */
+/* The feature buffers of the whole frame: every context sums its own rows, the planes meet at the root like the image (one
+ * exchange of 16 B per pixel and plane, either transport; the root's buffers are allocated on first use). */
+int pt_group_render_features(PtGroup* g, int iter_first, int iter_count); /* asynchronous on every device */
+int pt_group_gather_features(PtGroup* g, float* planes_host);            /* PT_FEATURE_PLANES * W*H * 4 floats, raw orientation */
 /* Progressive preview of the running average (sendImageToPBO, pathtrace.cu:250-268, which the reference runs after every
  * iteration): W*H RGBA8 bytes, raw orientation, converted on each device, one exchange of 4 B per pixel. */
 int pt_group_preview_rgba8(PtGroup* g, int iterations, uint8_t* rgba_host);
