@@ -78,6 +78,12 @@ class PtStats(C.Structure):
                 ("arith", C.c_int32), ("grid_cells", C.c_int32), ("tight_leaves", C.c_int32), ("paths_waves", C.c_int32)]
 
 
+class PtDenoiseOptions(C.Structure):
+    """Options of the edge-avoiding filter (include/pt_amd.h); 0 in a field = its default (5 levels, sigmas 4 / 0.5 / 1, demodulate)."""
+    _fields_ = [("levels", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_position", C.c_float),
+                ("keep_albedo", C.c_int32)]
+
+
 class PtError(RuntimeError):
     pass
 
@@ -178,6 +184,14 @@ def lib() -> C.CDLL:
         L.pt_ctx_device_features.restype = C.c_void_p
         L.pt_group_render_features.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.pt_group_gather_features.argtypes = [C.c_void_p, _fp]
+    if hasattr(L, "pt_denoise"):  # absent from older A/B builds of the library (tools/build_rev.sh)
+        _dno = C.POINTER(PtDenoiseOptions)
+        L.pt_denoise.argtypes = [C.c_float, _dno, _fp]
+        L.pt_ctx_denoise.argtypes = [C.c_void_p, C.c_float, _dno, _fp]
+        L.pt_ctx_denoise_device.argtypes = [C.c_void_p, C.c_float, _dno, C.POINTER(C.c_void_p)]
+        L.pt_group_denoise.argtypes = [C.c_void_p, C.c_float, _dno, _fp]
+        L.pt_stage_denoise.argtypes = [C.c_int, C.c_int, _fp, _fp, C.c_float, _dno, _fp]
+        L.pt_denoise_host.argtypes = [C.c_int, C.c_int, _fp, _fp, C.c_float, _dno, _fp]
     _lib = L
     return L
 
@@ -325,6 +339,29 @@ def split_features(planes: np.ndarray) -> dict:
                 position=np.ascontiguousarray(p[2, :, :3]), object_id=np.ascontiguousarray(p[2, :, 3]).view(np.int32))
 
 
+def denoise_options(levels: int = 0, sigma_color: float = 0.0, sigma_normal: float = 0.0, sigma_position: float = 0.0,
+                    keep_albedo: bool = False) -> PtDenoiseOptions:
+    """PtDenoiseOptions; 0 = the default of a field, a negative sigma switches its term off."""
+    return PtDenoiseOptions(int(levels), float(sigma_color), float(sigma_normal), float(sigma_position), 1 if keep_albedo else 0)
+
+
+def _denoise_arrays(rgb_sum: np.ndarray, planes: np.ndarray, w: int, rows: int):
+    s = np.ascontiguousarray(rgb_sum, np.float32).reshape(-1)
+    p = np.ascontiguousarray(planes, np.float32).reshape(-1)
+    if s.size != 3 * w * rows or p.size != 4 * FEATURE_PLANES * w * rows:
+        raise PtError(f"denoise: {s.size} image and {p.size} plane floats for a frame of {w}x{rows}")
+    return s, p, np.empty((w * rows, 3), np.float32)
+
+
+def denoise_host(rgb_sum: np.ndarray, planes: np.ndarray, w: int, rows: int, samples: float, **opts) -> np.ndarray:
+    """The edge-avoiding filter on the host (pt_denoise_host; no GPU): SUM image [w*rows, 3] and feature SUM planes
+    [PT_FEATURE_PLANES, w*rows, 4] in, averaged radiance [w*rows, 3] out.  The device result equals it bit for bit."""
+    s, p, out = _denoise_arrays(rgb_sum, planes, w, rows)
+    opt = denoise_options(**opts)
+    _check(lib().pt_denoise_host(int(w), int(rows), _f(s), _f(p), C.c_float(samples), C.byref(opt), _f(out)))
+    return out
+
+
 class Renderer:
     """pathtraceInit / pathtrace / pathtraceFree over the C ABI (the default instance, like the reference's
     file-scope renderer state).  `arith`: "exact" (bit-identical to the oracle), "fma" or "fast" (PT_ARITH_*)."""
@@ -388,6 +425,14 @@ class Renderer:
         _check(lib().pt_readback_features(_f(out)))
         return split_features(out)
 
+    def denoise(self, samples: float, **opts) -> np.ndarray:
+        """The image filtered by the edge-avoiding filter over the feature buffers (pt_denoise; options: denoise_options):
+        averaged radiance of the tile, float32 [n, 3].  The tile is whole contiguous rows; a feature pass must have run."""
+        out = np.empty((self.n, 3), np.float32)
+        opt = denoise_options(**opts)
+        _check(lib().pt_denoise(C.c_float(samples), C.byref(opt), _f(out)))
+        return out
+
     # ---- convergence metric (make_options(convergence=...)) ----
     def set_reference(self, rgb_avg: np.ndarray) -> None:
         """The reference frame of convergence=-1: averaged radiance of the tile, float32 [n, 3]."""
@@ -438,6 +483,14 @@ class Renderer:
         a = np.ascontiguousarray(rgb_sum, np.float32)
         out = np.empty((h, w, 3), np.uint8)
         _check(lib().pt_stage_save_u8(w, h, C.c_float(samples), _f(a), out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    @staticmethod
+    def stage_denoise(rgb_sum: np.ndarray, planes: np.ndarray, w: int, rows: int, samples: float, **opts) -> np.ndarray:
+        """denoise_host's arguments through the filter kernels (pt_stage_denoise)."""
+        s, p, out = _denoise_arrays(rgb_sum, planes, w, rows)
+        opt = denoise_options(**opts)
+        _check(lib().pt_stage_denoise(int(w), int(rows), _f(s), _f(p), C.c_float(samples), C.byref(opt), _f(out)))
         return out
 
     @staticmethod
@@ -493,6 +546,14 @@ class Group:
         out = np.empty((FEATURE_PLANES, w * h, 4), np.float32)
         _check(lib().pt_group_gather_features(self._h, _f(out)))
         return split_features(out)
+
+    def denoise(self, samples: float, **opts) -> np.ndarray:
+        """Renderer.denoise of the whole frame (pt_group_denoise): float32 [W*H, 3], raw orientation."""
+        w, h = self.scene.resolution
+        out = np.empty((w * h, 3), np.float32)
+        opt = denoise_options(**opts)
+        _check(lib().pt_group_denoise(self._h, C.c_float(samples), C.byref(opt), _f(out)))
+        return out
 
     def gather_u8(self, samples: float) -> np.ndarray:
         w, h = self.scene.resolution

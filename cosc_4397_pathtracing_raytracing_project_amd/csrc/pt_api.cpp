@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/pt_amd.h"
+#include "pt_denoise.h"
 #include "pt_device.h"
 #include "pt_internal.h"
 #include "pt_kernels.h"
@@ -112,6 +113,7 @@ struct PtContext {
   // First-hit feature buffers (pt_ctx_render_features): PT_FEATURE_PLANES planes of N float4 sums; absent until the first feature pass
   float4* d_feat = nullptr;
   int grid_features = 0;
+  void* d_denoise = nullptr;  // workspace of pt_ctx_denoise (pt_denoise_workspace_bytes(N)); absent until the first denoise call
   // Convergence metric (PtOptions.convergence, pt_kernels.h ConvInfo): all of it absent when the option is 0
   int conv = 0;                // the option: N > 0 capture the frame at iteration N, -1 supplied
   bool conv_live = false;      // off while setup() renders its timing batches: they leave no trace in the curve or the frame
@@ -812,6 +814,33 @@ int pt_ctx_readback_features(PtContext* c, float* planes_host) {
 
 const float* pt_ctx_device_features(PtContext* c) { return c ? reinterpret_cast<const float*>(c->d_feat) : nullptr; }
 
+// ---- edge-avoiding filter over the image and the feature buffers (csrc/pt_denoise.hip) ------------------------
+int pt_ctx_denoise_device(PtContext* c, float samples, const PtDenoiseOptions* opt, const float** rgb_dev) {
+  if (need(c, "pt_denoise")) return -1;
+  Ctx& g = *c;
+  if (g.failed) return fail("pt_denoise: an earlier batch of this context failed (%s); free it and create a new one", g_err.c_str());
+  const int W = g.cam.resolution[0];
+  if (g.stripe || g.pixel_begin % W || g.N % W)
+    return fail("pt_denoise: the tile must consist of whole contiguous image rows (begin %d, count %d, stripe %d, width %d)", g.pixel_begin, g.N, g.stripe, W);
+  if (!g.d_feat) return fail("pt_denoise: no feature pass has been rendered (pt_render_features)");
+  ptdn::Params P{};
+  if (pt_denoise_resolve("pt_denoise", samples, opt, &P)) return -1;
+  HIP_OK(hipSetDevice(g.device));
+  if (!g.d_denoise) {  // first denoise call of the context
+    char* ws = nullptr;
+    if (dalloc(g, &ws, pt_denoise_workspace_bytes((size_t)g.N))) return -1;
+    g.d_denoise = ws;
+  }
+  return pt_denoise_launch(g.stream, W, g.N / W, g.d_image, reinterpret_cast<const float*>(g.d_feat), samples, P, g.d_denoise, rgb_dev);
+}
+int pt_ctx_denoise(PtContext* c, float samples, const PtDenoiseOptions* opt, float* rgb_avg_host) {
+  if (!rgb_avg_host) return fail("pt_denoise: null buffer");
+  const float* d = nullptr;
+  if (pt_ctx_denoise_device(c, samples, opt, &d)) return -1;
+  HIP_OK(hipMemcpyAsync(rgb_avg_host, d, 3 * (size_t)c->N * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  return pt_ctx_sync(c);
+}
+
 int pt_ctx_sync(PtContext* c) {
   if (need(c, "pt_sync")) return -1;
   HIP_OK(hipSetDevice(c->device));
@@ -1016,6 +1045,7 @@ int pt_reset_stats(void) { return pt_ctx_reset_stats(g_default); }
 int pt_clear(void) { return pt_ctx_clear(g_default); }
 int pt_render_features(int iter_first, int iter_count) { return pt_ctx_render_features(g_default, iter_first, iter_count); }
 int pt_readback_features(float* planes_host) { return pt_ctx_readback_features(g_default, planes_host); }
+int pt_denoise(float samples, const PtDenoiseOptions* opt, float* rgb_avg_host) { return pt_ctx_denoise(g_default, samples, opt, rgb_avg_host); }
 int pt_set_reference(const float* rgb_avg_host) { return pt_ctx_set_reference(g_default, rgb_avg_host); }
 int pt_get_convergence(int iter_first, int iter_count, double* sse) { return pt_ctx_get_convergence(g_default, iter_first, iter_count, sse); }
 int pt_iterations_to_clean(float threshold_db, int* iteration) { return pt_ctx_iterations_to_clean(g_default, threshold_db, iteration); }
@@ -1185,6 +1215,29 @@ int pt_stage_save_u8(int w, int h, float samples, const float* rgb_sum, uint8_t*
   g.k->save_u8(g.stream, (int)n, w, samples, d_img, d_u8);
   HIP_OK(hipStreamSynchronize(g.stream));
   HIP_OK(hipMemcpy(rgb8, d_u8, 3 * n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// The filter kernels on caller-supplied host arrays (tests: frames a renderer would never produce)
+int pt_stage_denoise(int w, int rows, const float* rgb_sum, const float* planes, float samples, const PtDenoiseOptions* opt, float* rgb_avg) {
+  if (need(g_default, "pt_stage_denoise")) return -1;
+  Ctx& g = *g_default;
+  if (w <= 0 || rows <= 0 || rows >= 32768 || (int64_t)w * rows > (1ll << 30) || !rgb_sum || !planes || !rgb_avg) return fail("pt_stage_denoise: bad argument");
+  ptdn::Params P{};
+  if (pt_denoise_resolve("pt_stage_denoise", samples, opt, &P)) return -1;
+  HIP_OK(hipSetDevice(g.device));
+  Scratch sc;
+  const size_t n = (size_t)w * rows;
+  float* d_img = sc.get<float>(3 * n);
+  float* d_planes = sc.get<float>(4 * PT_FEATURE_PLANES * n);
+  char* d_ws = sc.get<char>(pt_denoise_workspace_bytes(n));
+  if (!d_img || !d_planes || !d_ws) return fail("pt_stage_denoise: out of device memory");
+  HIP_OK(hipMemcpy(d_img, rgb_sum, 3 * n * sizeof(float), hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(d_planes, planes, 4 * PT_FEATURE_PLANES * n * sizeof(float), hipMemcpyHostToDevice));
+  const float* d_out = nullptr;
+  if (pt_denoise_launch(g.stream, w, rows, d_img, d_planes, samples, P, d_ws, &d_out)) return -1;
+  HIP_OK(hipStreamSynchronize(g.stream));
+  HIP_OK(hipMemcpy(rgb_avg, d_out, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
   return 0;
 }
 

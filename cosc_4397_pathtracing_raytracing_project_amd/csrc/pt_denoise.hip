@@ -1,0 +1,82 @@
+// pt_denoise.hip — the kernels of the edge-avoiding à-trous filter (include/pt_amd.h pt_denoise) and their launcher.
+//
+// A translation unit of its own, compiled ONCE with -ffp-contract=off: the filter is specified as separate IEEE float32 operations
+// (pt_denoise.h), so there is nothing an arithmetic mode could change, and the path tracer's kernels (pt_kernels.hip) are not
+// rebuilt differently because of it.  The kernels are thin: thread indices in, the PT_HD bodies of pt_denoise.h, which the host
+// loop pt_denoise_host runs too.
+//
+//   k_denoise_prepare   one thread per pixel: SUM image + feature SUM planes -> normal | hit, position, albedo, colour (4 x 16 B)
+//   k_denoise_level     the hot path, once per level: a 64 x 4 workgroup, lanes along x (at every step consecutive lanes read
+//                       consecutive pixels: 1 KiB per wave and load), each thread kRows pixels of its column, rows s apart
+//                       (pt_denoise.h level_column); no LDS, the reuse left between neighbouring columns is L1's and L2's
+//   k_denoise_finish    one thread per pixel: remodulation, 12 B per pixel
+#include <hip/hip_runtime.h>
+
+#include "pt_denoise.h"
+#include "pt_internal.h"
+
+namespace {
+using ptdn::Params;
+using ptdn::V4;
+constexpr int kBlock = 256;
+constexpr int kLevelX = 64, kLevelY = kBlock / kLevelX;  // a wave is 64 pixels of one row slot
+
+__global__ __launch_bounds__(kBlock) void k_denoise_prepare(int npix, const float* __restrict__ S, const V4* __restrict__ planes, float samples,
+                                                            int keep_albedo, V4* __restrict__ n, V4* __restrict__ p, V4* __restrict__ a,
+                                                            V4* __restrict__ c) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < npix) ptdn::prepare_pixel((size_t)i, (size_t)npix, S, planes, samples, keep_albedo, n, p, a, c);
+}
+
+__global__ __launch_bounds__(kBlock) void k_denoise_level(int W, int R, int l, Params P, const V4* __restrict__ c, const V4* __restrict__ n,
+                                                          const V4* __restrict__ p, V4* __restrict__ out) {
+  const int x = blockIdx.x * kLevelX + (threadIdx.x & (kLevelX - 1));
+  const int ty = blockIdx.y * kLevelY + threadIdx.x / kLevelX;
+  if (x < W && ty < ptdn::level_slots(R, l)) ptdn::level_column(W, R, x, ty, l, P, c, n, p, out);
+}
+
+__global__ __launch_bounds__(kBlock) void k_denoise_finish(int npix, int keep_albedo, const V4* __restrict__ c, const V4* __restrict__ a,
+                                                           float* __restrict__ out) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < npix) ptdn::finish_pixel((size_t)i, keep_albedo, c, a, out);
+}
+
+}  // namespace
+
+// pt_internal.h.  Everything is checked before the first launch; no allocation, no synchronisation.
+int pt_denoise_launch(hipStream_t stream, int w, int rows, const float* rgb_sum_dev, const float* planes_dev, float samples,
+                      const ptdn::Params& P, void* workspace_dev, const float** rgb_avg_dev) {
+  if (w <= 0 || rows <= 0 || rows >= 32768 || (int64_t)w * rows > (1ll << 30)) return pt_fail("pt_denoise: a frame of %d x %d pixels is not supported", w, rows);
+  if (!rgb_sum_dev || !planes_dev || !workspace_dev || !(samples > 0.0f) || P.levels < 1 || P.levels > ptdn::kMaxLevels)
+    return pt_fail("pt_denoise: bad argument");
+  const int npix = w * rows;
+  V4* n = static_cast<V4*>(workspace_dev);
+  V4 *p = n + npix, *a = p + npix, *col[2] = {a + npix, a + 2 * (size_t)npix};
+  const int flat = (npix + kBlock - 1) / kBlock;
+  hipLaunchKernelGGL(k_denoise_prepare, dim3(flat), dim3(kBlock), 0, stream, npix, rgb_sum_dev, reinterpret_cast<const V4*>(planes_dev), samples,
+                     P.keep_albedo, n, p, a, col[0]);
+  for (int l = 0; l < P.levels; ++l) {
+    const dim3 grid((w + kLevelX - 1) / kLevelX, (ptdn::level_slots(rows, l) + kLevelY - 1) / kLevelY);
+    hipLaunchKernelGGL(k_denoise_level, grid, dim3(kBlock), 0, stream, w, rows, l, P, col[ptdn::color_buffer(l)], n, p, col[ptdn::color_buffer(l + 1)]);
+  }
+  float* out = reinterpret_cast<float*>(col[ptdn::color_buffer(P.levels + 1)]);
+  hipLaunchKernelGGL(k_denoise_finish, dim3(flat), dim3(kBlock), 0, stream, npix, P.keep_albedo, col[ptdn::color_buffer(P.levels)], a, out);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return pt_fail("pt_denoise: launch failed: %s", hipGetErrorString(e));
+  if (rgb_avg_dev) *rgb_avg_dev = out;
+  return 0;
+}
+
+int pt_denoise_resolve(const char* who, float samples, const PtDenoiseOptions* opt, ptdn::Params* P) {
+  if (!(samples > 0.0f)) return pt_fail("%s: samples must be positive", who);
+  if (const char* msg = ptdn::resolve(opt, P)) return pt_fail("%s: %s", who, msg);
+  return 0;
+}
+
+extern "C" int pt_denoise_host(int w, int rows, const float* rgb_sum, const float* planes, float samples, const PtDenoiseOptions* opt, float* rgb_avg) {
+  if (w <= 0 || rows <= 0 || (int64_t)w * rows > (1ll << 30) || !rgb_sum || !planes || !rgb_avg) return pt_fail("pt_denoise_host: bad argument");
+  ptdn::Params P{};
+  if (pt_denoise_resolve("pt_denoise_host", samples, opt, &P)) return -1;
+  ptdn::denoise_host(w, rows, rgb_sum, planes, samples, P, rgb_avg);
+  return 0;
+}

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/pt_amd.h"
+#include "pt_denoise.h"
 #include "pt_internal.h"
 
 #define HIP_OK(expr)                                                                                      \
@@ -59,6 +60,7 @@ struct PtGroup {
   uint8_t* d_full_prev = nullptr;
   float* d_recv_feat = nullptr;  // root: one feature plane of the tiles of devices 1..n-1 (16 B per pixel) / the assembled planes
   float* d_full_feat = nullptr;
+  void* d_denoise = nullptr;  // root: workspace of pt_group_denoise over the whole frame
 };
 
 namespace {
@@ -77,7 +79,7 @@ void release(PtGroup* g) {
     }
   if (!g->devices.empty()) (void)hipSetDevice(g->devices[0]);
   for (void* p : {(void*)g->d_recv, (void*)g->d_full, (void*)g->d_recv8, (void*)g->d_full8, (void*)g->d_recv_prev,
-                  (void*)g->d_full_prev, (void*)g->d_recv_feat, (void*)g->d_full_feat})
+                  (void*)g->d_full_prev, (void*)g->d_recv_feat, (void*)g->d_full_feat, g->d_denoise})
     if (p) (void)hipFree(p);
   for (size_t i = 0; i < g->d_prev.size(); ++i)
     if (g->d_prev[i]) {
@@ -147,6 +149,39 @@ int place_rows(PtGroup* g, int i, const T* tile, T* full, size_t bytes_per_pixel
   const size_t row = (size_t)g->W * bytes_per_pixel;
   HIP_OK(hipMemcpy2DAsync(reinterpret_cast<char*>(full) + (size_t)i * row, (size_t)g->n * row, tile, row, row, (size_t)g->rows[i],
                           hipMemcpyDeviceToDevice, (hipStream_t)pt_ctx_stream(g->ctx[0])));
+  return 0;
+}
+
+// The device side of the two write-out gathers (n > 1; the root device is current), on the root's stream: the tiles' exchange into
+// the receive buffer and the placement of everybody's rows in the frame buffer.  What follows — a copy to the host, the filter —
+// is queued behind them on the same stream.
+int assemble_image(PtGroup* g) {  // -> g->d_full: W*H*3 floats
+  const size_t frame = (size_t)g->W * g->H;
+  if (!g->d_full) HIP_OK(hipMalloc((void**)&g->d_full, frame * 12));
+  if (!g->d_recv) HIP_OK(hipMalloc((void**)&g->d_recv, g->recv_pixels * 12));
+  if (exchange(g, ncclFloat, 3, g->d_recv, [&](int i) { return pt_ctx_device_image(g->ctx[i]); })) return fail_after_drain(g);
+  HIP_OK(hipSetDevice(g->devices[0]));
+  for (int i = 0; i < g->n; ++i)
+    if (place_rows(g, i, i == 0 ? pt_ctx_device_image(g->ctx[0]) : g->d_recv + 3 * g->recv_off[i], g->d_full, 12))
+      return fail_after_drain(g);
+  return 0;
+}
+int need_features(PtGroup* g, const char* who) {
+  for (PtContext* c : g->ctx)
+    if (!pt_ctx_device_features(c)) return pt_fail("%s: no feature pass has been rendered (pt_group_render_features)", who);
+  return 0;
+}
+int assemble_features(PtGroup* g) {  // -> g->d_full_feat: PT_FEATURE_PLANES planes of W*H float4
+  const size_t frame = (size_t)g->W * g->H;
+  if (!g->d_full_feat) HIP_OK(hipMalloc((void**)&g->d_full_feat, PT_FEATURE_PLANES * frame * 16));
+  if (!g->d_recv_feat) HIP_OK(hipMalloc((void**)&g->d_recv_feat, g->recv_pixels * 16));
+  for (int pl = 0; pl < PT_FEATURE_PLANES; ++pl) {  // the root's stream orders plane pl + 1's receives behind plane pl's placement
+    auto tile = [&](int i) { return pt_ctx_device_features(g->ctx[i]) + 4 * (size_t)pl * pt_ctx_pixel_count(g->ctx[i]); };
+    if (exchange(g, ncclFloat, 4, g->d_recv_feat, tile)) return fail_after_drain(g);
+    HIP_OK(hipSetDevice(g->devices[0]));
+    for (int i = 0; i < g->n; ++i)
+      if (place_rows(g, i, i == 0 ? tile(0) : g->d_recv_feat + 4 * g->recv_off[i], g->d_full_feat + 4 * pl * frame, 16)) return fail_after_drain(g);
+  }
   return 0;
 }
 
@@ -246,13 +281,7 @@ int pt_group_gather(PtGroup* g, float* rgb_sum_host) {
   const size_t frame = (size_t)g->W * g->H;
   HIP_OK(hipSetDevice(g->devices[0]));
   if (g->n == 1) return pt_ctx_readback(g->ctx[0], rgb_sum_host);
-  if (!g->d_full) HIP_OK(hipMalloc((void**)&g->d_full, frame * 12));
-  if (!g->d_recv) HIP_OK(hipMalloc((void**)&g->d_recv, g->recv_pixels * 12));
-  if (exchange(g, ncclFloat, 3, g->d_recv, [&](int i) { return pt_ctx_device_image(g->ctx[i]); })) return fail_after_drain(g);
-  HIP_OK(hipSetDevice(g->devices[0]));
-  for (int i = 0; i < g->n; ++i)
-    if (place_rows(g, i, i == 0 ? pt_ctx_device_image(g->ctx[0]) : g->d_recv + 3 * g->recv_off[i], g->d_full, 12))
-      return fail_after_drain(g);
+  if (assemble_image(g)) return -1;
   HIP_OK(hipMemcpyAsync(rgb_sum_host, g->d_full, frame * 12, hipMemcpyDeviceToHost, (hipStream_t)pt_ctx_stream(g->ctx[0])));
   return pt_group_sync(g);
 }
@@ -269,20 +298,30 @@ int pt_group_render_features(PtGroup* g, int iter_first, int iter_count) {
 int pt_group_gather_features(PtGroup* g, float* planes_host) {
   if (!g || !planes_host) return pt_fail("pt_group_gather_features: bad argument");
   const size_t frame = (size_t)g->W * g->H;
-  for (PtContext* c : g->ctx)
-    if (!pt_ctx_device_features(c)) return pt_fail("pt_group_gather_features: no feature pass has been rendered (pt_group_render_features)");
+  if (need_features(g, "pt_group_gather_features")) return -1;
   HIP_OK(hipSetDevice(g->devices[0]));
   if (g->n == 1) return pt_ctx_readback_features(g->ctx[0], planes_host);
-  if (!g->d_full_feat) HIP_OK(hipMalloc((void**)&g->d_full_feat, PT_FEATURE_PLANES * frame * 16));
-  if (!g->d_recv_feat) HIP_OK(hipMalloc((void**)&g->d_recv_feat, g->recv_pixels * 16));
-  for (int pl = 0; pl < PT_FEATURE_PLANES; ++pl) {  // the root's stream orders plane pl + 1's receives behind plane pl's placement
-    auto tile = [&](int i) { return pt_ctx_device_features(g->ctx[i]) + 4 * (size_t)pl * pt_ctx_pixel_count(g->ctx[i]); };
-    if (exchange(g, ncclFloat, 4, g->d_recv_feat, tile)) return fail_after_drain(g);
-    HIP_OK(hipSetDevice(g->devices[0]));
-    for (int i = 0; i < g->n; ++i)
-      if (place_rows(g, i, i == 0 ? tile(0) : g->d_recv_feat + 4 * g->recv_off[i], g->d_full_feat + 4 * pl * frame, 16)) return fail_after_drain(g);
-  }
+  if (assemble_features(g)) return -1;
   HIP_OK(hipMemcpyAsync(planes_host, g->d_full_feat, PT_FEATURE_PLANES * frame * 16, hipMemcpyDeviceToHost, (hipStream_t)pt_ctx_stream(g->ctx[0])));
+  return pt_group_sync(g);
+}
+
+// pt_denoise of the whole frame: a context owns interleaved rows and cannot filter its own tile, so the SUM image and the planes
+// meet on the root device as for the two gathers, and the launcher every context uses runs there on the root's stream.
+int pt_group_denoise(PtGroup* g, float samples, const PtDenoiseOptions* opt, float* rgb_avg_host) {
+  if (!g || !rgb_avg_host) return pt_fail("pt_group_denoise: bad argument");
+  if (g->n == 1) return pt_ctx_denoise(g->ctx[0], samples, opt, rgb_avg_host);
+  const size_t frame = (size_t)g->W * g->H;
+  if (need_features(g, "pt_group_denoise")) return -1;
+  ptdn::Params P{};
+  if (pt_denoise_resolve("pt_group_denoise", samples, opt, &P)) return -1;
+  HIP_OK(hipSetDevice(g->devices[0]));
+  if (!g->d_denoise) HIP_OK(hipMalloc(&g->d_denoise, pt_denoise_workspace_bytes(frame)));
+  if (assemble_image(g) || assemble_features(g)) return -1;
+  hipStream_t root = (hipStream_t)pt_ctx_stream(g->ctx[0]);
+  const float* d_out = nullptr;
+  if (pt_denoise_launch(root, g->W, g->H, g->d_full, g->d_full_feat, samples, P, g->d_denoise, &d_out)) return fail_after_drain(g);
+  HIP_OK(hipMemcpyAsync(rgb_avg_host, d_out, frame * 12, hipMemcpyDeviceToHost, root));
   return pt_group_sync(g);
 }
 

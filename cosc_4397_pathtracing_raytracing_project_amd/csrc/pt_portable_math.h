@@ -162,6 +162,27 @@ PT_HD void sincos_rev(float u, float* s_out, float* c_out) {
   *c_out = ((q + 1) & 2) ? -vc : vc;
 }
 
+// exp(x) for x <= 0 in float32 operations only — the weight function of the edge-avoiding filter (pt_denoise.h), which evaluates it
+// 25 times per pixel and level: a double-precision polynomial would bind that kernel at the FP64 rate.  The Cephes expf scheme:
+// k = rint(x * log2(e)), r = x - k * ln 2 with ln 2 split so that k * 0.693359375 is exact for |k| <= 2^15, a degree-5 polynomial
+// for (exp(r) - 1 - r) / r^2 on |r| <= ln(2) / 2, scaled by 2^k.  Every operation is a separate, correctly rounded IEEE operation
+// in the order written — its callers are compiled with -ffp-contract=off (csrc/Makefile: pt_denoise.hip, the host code) —, so host, device and a numpy restatement
+// agree bit for bit (tests/test_denoise_host.py; <= 0.98 ulp against exp in double on the sample there).  Below -80 the result
+// is +0: every value returned is zero or a normal number (exp(-80) ~ 1.8e-35).
+PT_HD float exp32(float x) {
+  if (x < -80.0f) return 0.0f;
+  const float k = __builtin_rintf(x * 1.44269504f);
+  const float r = (x - k * 0.693359375f) - k * (-2.12194440e-4f);
+  float y = 1.9875691500e-4f;
+  y = y * r + 1.3981999507e-3f;
+  y = y * r + 8.3334519073e-3f;
+  y = y * r + 4.1665795894e-2f;
+  y = y * r + 1.6666665459e-1f;
+  y = y * r + 5.0000001201e-1f;
+  y = (y * (r * r) + r) + 1.0f;
+  return __builtin_ldexpf(y, (int)k);
+}
+
 // float wrappers (what the renderer calls where the reference calls the float overloads)
 PT_HD float sinf32(float x) { return sin_r((double)x); }
 PT_HD float cosf32(float x) { return cos_r((double)x); }

@@ -6,6 +6,7 @@
 //   pt_render SCENE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr]
 //                       [--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa]
 //                       [--preview N] [--convergence N | --reference FILE.pfm] [--clean-db X] [--features]
+//                       [--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]]
 //
 // Without --gpus the run goes through the pathtrace.h-compatible shim (pathtraceInit / pathtrace per
 // iteration / pathtraceFree), i.e. the code path a reference main.cpp would take.  With --gpus K (K >= 1;
@@ -22,6 +23,10 @@
 // --features: after the render a first-hit feature pass over the same iterations (pt_render_features / pt_group_render_features);
 // the averages go to <base>.normal.pfm, <base>.albedo.pfm, <base>.position.pfm and <base>.depth.pfm (depth in all three
 // channels) next to the image, written like --pfm writes the image (sums / spp).
+// --denoise (implies --features): the edge-avoiding filter over the image and the feature buffers (pt_denoise / pt_group_denoise);
+// the averaged result goes to <base>.denoised.png and, with --pfm, <base>.denoised.pfm.  --denoise-levels N (1 .. 8, default 5),
+// --denoise-sigma C,N,P (colour, normal, position; 0 = the default 4, 0.5, 1; negative = that term off), --denoise-keep-albedo
+// (no demodulation by the first-hit albedo) are PtDenoiseOptions' fields.
 // Output name: PREFIX.<spp>samp.png, or with --stamp the reference's own
 // <FILE>.<UTC start time>.<spp>samp.png (main.cpp:99-102).
 #include <hip/hip_runtime.h>
@@ -29,6 +34,7 @@
 #include <algorithm>
 #include <cfloat>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -42,12 +48,14 @@ int main(int argc, char** argv) {
   if (argc < 2) {
     std::printf("Usage: %s SCENEFILE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] "
                 "[--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa] [--preview N] "
-                "[--convergence N | --reference FILE.pfm] [--clean-db X] [--features]\n", argv[0]);
+                "[--convergence N | --reference FILE.pfm] [--clean-db X] [--features] "
+                "[--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]]\n", argv[0]);
     return 1;
   }
   int rw = 0, rh = 0, spp = 0, depth = 0, gpus = -1, arith = PT_ARITH_EXACT, preview = 0, transport = PT_GROUP_TRANSPORT_AUTO;
   std::vector<int> device_list;
-  bool pfm = false, hdr = false, stamp = false, aa = false, features = false;
+  bool pfm = false, hdr = false, stamp = false, aa = false, features = false, denoise = false;
+  PtDenoiseOptions dn_opt{};
   int convergence = 0;
   float clean_db = 35.0f;
   std::string out, reference;
@@ -90,6 +98,24 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[i], "--hdr")) hdr = true;  // the Radiance file of image::saveHDR (main.cpp:106, commented out there)
     else if (!std::strcmp(argv[i], "--stamp")) stamp = true;
     else if (!std::strcmp(argv[i], "--features")) features = true;  // first-hit feature buffers next to the image
+    else if (!std::strcmp(argv[i], "--denoise")) denoise = true;    // the filtered image next to the image
+    else if (!std::strcmp(argv[i], "--denoise-keep-albedo")) dn_opt.keep_albedo = 1;
+    else if (!std::strcmp(argv[i], "--denoise-levels") && i + 1 < argc) {
+      char* end = nullptr;
+      const long v = std::strtol(argv[++i], &end, 10);
+      if (end == argv[i] || *end || v < 1 || v > 8) {
+        std::fprintf(stderr, "--denoise-levels wants a number of levels from 1 to 8\n");
+        return 1;
+      }
+      dn_opt.levels = (int)v;
+    } else if (!std::strcmp(argv[i], "--denoise-sigma") && i + 1 < argc) {
+      char tail = 0;
+      const int got = std::sscanf(argv[++i], "%f,%f,%f%c", &dn_opt.sigma_color, &dn_opt.sigma_normal, &dn_opt.sigma_position, &tail);
+      if (got != 3 || !std::isfinite(dn_opt.sigma_color) || !std::isfinite(dn_opt.sigma_normal) || !std::isfinite(dn_opt.sigma_position)) {
+        std::fprintf(stderr, "--denoise-sigma wants three finite numbers C,N,P (colour, normal, position; 0 = default, negative = off)\n");
+        return 1;
+      }
+    }
     else if (!std::strcmp(argv[i], "--aa")) aa = true;  // extension: stochastic anti-aliasing (PtOptions.aa_jitter)
     else if (!std::strcmp(argv[i], "--arith") && i + 1 < argc) {
       const char* a = argv[++i];
@@ -110,6 +136,11 @@ int main(int argc, char** argv) {
     return 1;
   }
   if (!reference.empty()) convergence = -1;
+  if (!denoise && (dn_opt.levels || dn_opt.keep_albedo || dn_opt.sigma_color != 0.0f || dn_opt.sigma_normal != 0.0f || dn_opt.sigma_position != 0.0f)) {
+    std::fprintf(stderr, "--denoise-levels, --denoise-sigma and --denoise-keep-albedo want --denoise\n");
+    return 1;
+  }
+  if (denoise) features = true;
   pt::Scene* scene = nullptr;
   try {
     scene = new pt::Scene(argv[1]);
@@ -167,6 +198,12 @@ int main(int argc, char** argv) {
     }
   };
 
+  // --denoise: the averaged, filtered frame through the writers of the image (samples = 1: it is no SUM)
+  auto save_denoised = [&](const std::vector<float>& rgb) {
+    if (pt_save_png((base + ".denoised.png").c_str(), rgb.data(), W, H, 1.0f) == 0) std::printf("Saved %s.denoised.png.\n", base.c_str());
+    if (pfm && pt_save_pfm((base + ".denoised.pfm").c_str(), rgb.data(), W, H, 1.0f) == 0) std::printf("Saved %s.denoised.pfm.\n", base.c_str());
+  };
+
   double secs = 0;
   if (gpus < 0) {
     // the reference's call sequence (main.cpp:133-152) through the pathtrace.h shim
@@ -200,6 +237,14 @@ int main(int argc, char** argv) {
         return EXIT_FAILURE;
       }
       save_features(planes);
+    }
+    if (denoise) {
+      std::vector<float> rgb((size_t)W * H * 3);
+      if (pt_denoise((float)iters, &dn_opt, rgb.data())) {
+        std::fprintf(stderr, "HIP error (pt_denoise): %s\n", pt_last_error());
+        return EXIT_FAILURE;
+      }
+      save_denoised(rgb);
     }
     if (convergence) {
       std::vector<float> psnr((size_t)iters);
@@ -288,6 +333,14 @@ int main(int argc, char** argv) {
         return EXIT_FAILURE;
       }
       save_features(planes);
+    }
+    if (denoise) {
+      std::vector<float> rgb((size_t)W * H * 3);
+      if (pt_group_denoise(grp, (float)iters, &dn_opt, rgb.data())) {
+        std::fprintf(stderr, "HIP error (pt_group_denoise): %s\n", pt_last_error());
+        return EXIT_FAILURE;
+      }
+      save_denoised(rgb);
     }
     if (convergence) {
       std::vector<double> sse((size_t)iters);

@@ -323,6 +323,40 @@ float pt_psnr_from_sse(double sse, int64_t pixels);
 int pt_render_features(int iter_first, int iter_count); /* asynchronous on the renderer's stream, like pt_render */
 int pt_readback_features(float* planes_host);          /* PT_FEATURE_PLANES * pixel_count * 4 floats; synchronises */
 
+/* ---- edge-avoiding à-trous wavelet filter (Dammertz et al. 2010) over the image and the first-hit feature buffers: a low-spp image
+ * made usable on the device.  Specified to the bit: float32 throughout, every operation a separate IEEE operation in the order written
+ * (no FMA contraction, correctly rounded division, denormals kept, no library transcendentals), so the result is the same in all
+ * three PT_ARITH_* builds, on the host (pt_denoise_host) and on the device.  The tile must be whole contiguous rows (W x R); the filter
+ * treats them as an image of their own.  With S the SUM image, s0 s1 s2 the feature SUM planes:
+ *   prepare  hit = s1.w > 0;  c = S / samples;  hit: n = s0.xyz / s1.w, a = s1.xyz / s1.w, p = s2.xyz / s1.w;  miss: n = a = p = 0;
+ *            unless keep_albedo: c_k = a_k > 0 ? c_k / a_k : c_k  (the filter then runs on irradiance-like values, textures stay sharp)
+ *   level l = 0 .. levels - 1, step s = 1 << l, pixel (x, y):  acc = 0, wsum = 0; for j = -2 .. 2 (rows, outer), i = -2 .. 2:
+ *            q = (x + i s, y + j s); the tap is skipped when q is outside the W x R rectangle or hit(q) != hit(x, y);
+ *            dc = |c_l(q) - c_l(x, y)|^2, dn = |n(q) - n(x, y)|^2, dp = |p(q) - p(x, y)|^2, each (d.x d.x + d.y d.y) + d.z d.z;
+ *            e = (dc * (inv_c * 4^l) + dn * inv_n) + dp * inv_p;  w = (H[j + 2] * H[i + 2]) * exp32(-e), H = 1/16 1/4 3/8 1/4 1/16;
+ *            acc += w * c_l(q) per component (multiply, then add);  wsum += w;   c_l+1(x, y) = acc / wsum   (wsum >= 9/64: the centre)
+ *   finish   out_k = a_k > 0 ? c_levels,k * a_k : c_levels,k unless keep_albedo, else c_levels
+ * inv_* = 1.0f / (sigma * sigma) in float32, 0 for a term that is switched off; exp32 is ptmath::exp32 (csrc/pt_portable_math.h: +0
+ * below -80, else a float32 polynomial).  The output is AVERAGED radiance (not a SUM), 3 floats per pixel, tile order, raw orientation.
+ * Every field of the options: 0 = the default; the defaults were tuned on the cornell box at 4 spp (mean squared error against a
+ * 1024-spp render 0.085 of the unfiltered image's). */
+typedef struct PtDenoiseOptions {
+  int32_t levels;       /* 1 .. 8; default 5 (reach 2 * 2^levels - 2 = 62 pixels)                               */
+  float sigma_color;    /* default 4.0; < 0 switches the colour term off.  Tightens by 2 per level (4^l above)  */
+  float sigma_normal;   /* default 0.5; < 0 switches the normal term off                                        */
+  float sigma_position; /* default 1.0, scene units; < 0 switches the position term off                         */
+  int32_t keep_albedo;  /* 0 = demodulate by the first-hit albedo (default); 1 = filter the radiance as it is   */
+} PtDenoiseOptions;
+/* Reads the image and the feature buffers (pt_render_features must have run) and changes neither, nor PtStats.samples.  Errors with a
+ * message, allocating nothing: a striped or ragged tile, no feature pass yet, samples <= 0, levels outside 1 .. 8, a sigma that is
+ * not finite, a failed context.  Workspace: 80 bytes per tile pixel (normal + hit flag, position, albedo, two colour buffers, float4
+ * each), allocated by the first denoise call of a renderer, part of PtStats.device_bytes from then on, kept across pt_clear.
+ * opt == NULL: all defaults.  rgb_avg_host receives pixel_count * 3 floats.  Synchronises. */
+int pt_denoise(float samples, const PtDenoiseOptions* opt, float* rgb_avg_host);
+/* The same filter on the host, for a frame of w x rows pixels: S w*rows*3 floats, planes PT_FEATURE_PLANES * w*rows * 4 floats
+ * (pt_readback_features' layout), out w*rows*3 floats.  Needs no GPU; the device result equals it bit for bit. */
+int pt_denoise_host(int w, int rows, const float* rgb_sum, const float* planes, float samples, const PtDenoiseOptions* opt, float* rgb_avg);
+
 /* saveImage()'s per-pixel conversion (main.cpp:91-97 x mirror, image.cpp:26-30 clamp * 255 truncated) on the
  * device: pixel_count*3 bytes, row-major, x mirrored inside each row; the tile must consist of whole rows.
  * Reads back 3 B per pixel instead of 12. */
@@ -348,6 +382,9 @@ int pt_ctx_get_convergence(PtContext* c, int iter_first, int iter_count, double*
 int pt_ctx_iterations_to_clean(PtContext* c, float threshold_db, int* iteration);
 int pt_ctx_render_features(PtContext* c, int iter_first, int iter_count);
 int pt_ctx_readback_features(PtContext* c, float* planes_host);
+int pt_ctx_denoise(PtContext* c, float samples, const PtDenoiseOptions* opt, float* rgb_avg_host);
+/* Asynchronous on the context's stream; *rgb_dev (pixel_count * 3 floats, inside the workspace) stays valid until the next denoise call. */
+int pt_ctx_denoise_device(PtContext* c, float samples, const PtDenoiseOptions* opt, const float** rgb_dev);
 const float* pt_ctx_device_features(PtContext* c); /* device pointer of plane 0; the planes are contiguous; NULL before the first pt_ctx_render_features */
 const float* pt_ctx_device_image(PtContext* c); /* device pointer of the tile SUM image */
 void* pt_ctx_stream(PtContext* c);              /* the context's hipStream_t */
@@ -385,6 +422,11 @@ int pt_group_gather_u8(PtGroup* g, float samples, uint8_t* rgb8_host); /* W*H*3 
  * exchange of 16 B per pixel and plane, either transport; the root's buffers are allocated on first use). */
 int pt_group_render_features(PtGroup* g, int iter_first, int iter_count); /* asynchronous on every device */
 int pt_group_gather_features(PtGroup* g, float* planes_host);            /* PT_FEATURE_PLANES * W*H * 4 floats, raw orientation */
+/* pt_denoise of the whole frame (W*H*3 floats of averaged radiance, raw orientation), bit-identical to a single context's.  A
+ * context of a group owns interleaved rows and cannot filter its own tile: the SUM image and the three planes are assembled on the
+ * root device as for the two gathers above, and the filter runs there, on the root's stream, with a workspace of 80 B per frame
+ * pixel owned by the group.  Errors as pt_denoise (before a feature pass: an error). */
+int pt_group_denoise(PtGroup* g, float samples, const PtDenoiseOptions* opt, float* rgb_avg_host);
 /* Progressive preview of the running average (sendImageToPBO, pathtrace.cu:250-268, which the reference runs after every
  * iteration): W*H RGBA8 bytes, raw orientation, converted on each device, one exchange of 4 B per pixel. */
 int pt_group_preview_rgba8(PtGroup* g, int iterations, uint8_t* rgba_host);
@@ -413,6 +455,9 @@ int pt_stage_shade(int n, int depth, const int32_t* iter, const int32_t* pixel, 
 
 /* saveImage + savePNG conversion kernel (pt_save_u8) on a caller-supplied SUM image of w*h pixels (tests). */
 int pt_stage_save_u8(int w, int h, float samples, const float* rgb_sum, uint8_t* rgb8);
+
+/* The filter kernels of pt_denoise on caller-supplied host arrays (pt_denoise_host's arguments; rows < 32768). */
+int pt_stage_denoise(int w, int rows, const float* rgb_sum, const float* planes, float samples, const PtDenoiseOptions* opt, float* rgb_avg);
 
 /* ---- image output (src/image.cpp:22-45, src/main.cpp:86-107) ------------- */
 /* rgb_sum: W*H*3 floats (raw orientation); writes <path> as 8-bit PNG of
