@@ -21,6 +21,8 @@ PT_MAX_DEPTH = 64
 ARITH = {"exact": 0, "fma": 1, "fast": 2}  # PT_ARITH_* (include/pt_amd.h)
 ARITH_NAMES = {v: k for k, v in ARITH.items()}
 FEATURE_PLANES = 3            # PT_FEATURE_PLANES
+NOISE_PLANES = 2              # PT_NOISE_PLANES
+NOISE_PIXELS_PER_PARTIAL = 1024  # PT_NOISE_PIXELS_PER_PARTIAL
 CONVERGENCE_WAVES = 16        # PT_CONVERGENCE_WAVES
 CONVERGENCE_CAPACITY = 65536  # PT_CONVERGENCE_CAPACITY: iterations the convergence metric keeps a value for
 FLT_MAX = float(np.finfo(np.float32).max)
@@ -192,6 +194,22 @@ def lib() -> C.CDLL:
         L.pt_group_denoise.argtypes = [C.c_void_p, C.c_float, _dno, _fp]
         L.pt_stage_denoise.argtypes = [C.c_int, C.c_int, _fp, _fp, C.c_float, _dno, _fp]
         L.pt_denoise_host.argtypes = [C.c_int, C.c_int, _fp, _fp, C.c_float, _dno, _fp]
+    if hasattr(L, "pt_noise_fold"):  # absent from older A/B builds of the library (tools/build_rev.sh)
+        _until = [C.c_int, C.c_int, C.c_int, C.c_float, _ip, _fp]
+        L.pt_noise_fold.argtypes = []
+        L.pt_get_noise.argtypes = [_dp, _ip, _ip]
+        L.pt_readback_noise.argtypes = [_fp]
+        L.pt_render_until.argtypes = _until
+        L.pt_ctx_noise_fold.argtypes = [C.c_void_p]
+        L.pt_ctx_get_noise.argtypes = [C.c_void_p, _dp, _ip, _ip]
+        L.pt_ctx_readback_noise.argtypes = [C.c_void_p, _fp]
+        L.pt_ctx_render_until.argtypes = [C.c_void_p] + _until
+        L.pt_ctx_device_noise.argtypes = [C.c_void_p]
+        L.pt_ctx_device_noise.restype = C.c_void_p
+        L.pt_group_noise_fold.argtypes = [C.c_void_p]
+        L.pt_group_get_noise.argtypes = [C.c_void_p, _dp, _ip, _ip]
+        L.pt_group_render_until.argtypes = [C.c_void_p] + _until
+        L.pt_noise_fold_host.argtypes = [C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int64, _dp]
     _lib = L
     return L
 
@@ -362,6 +380,36 @@ def denoise_host(rgb_sum: np.ndarray, planes: np.ndarray, w: int, rows: int, sam
     return out
 
 
+def split_noise(planes: np.ndarray) -> dict:
+    """The noise planes [PT_NOISE_PLANES, n, 4] (pt_readback_noise) by name: prev [n, 3] (the SUM image at the last fold),
+    q [n, 3] (sum over the groups of B^2 / n), variance [n] (w: estimated variance of the averaged radiance, channels added)."""
+    p = planes.reshape(NOISE_PLANES, -1, 4)
+    return dict(prev=np.ascontiguousarray(p[0, :, :3]), q=np.ascontiguousarray(p[1, :, :3]), variance=np.ascontiguousarray(p[0, :, 3]))
+
+
+def noise_fold_host(rgb_sum: np.ndarray, planes: np.ndarray, group_iters: int, groups_after: int, iters_after: int) -> float:
+    """One fold of the noise estimate on the host (pt_noise_fold_host; no GPU): SUM image [n, 3], planes float32
+    [PT_NOISE_PLANES, n, 4] updated IN PLACE; returns SSE_est (-1 while groups_after < 2).  The device's planes equal it bit for bit."""
+    s = np.ascontiguousarray(rgb_sum, np.float32).reshape(-1)
+    if planes.dtype != np.float32 or not planes.flags.c_contiguous or planes.size != 4 * NOISE_PLANES * (s.size // 3) or s.size % 3:
+        raise PtError(f"noise_fold_host: {s.size} image floats and {planes.size} plane floats (contiguous float32 [{NOISE_PLANES}, n, 4])")
+    sse = C.c_double(-1.0)
+    _check(lib().pt_noise_fold_host(s.size // 3, _f(s), _f(planes), int(group_iters), int(groups_after), int(iters_after), C.byref(sse)))
+    return float(sse.value)
+
+
+def _noise(call, *handle) -> dict:
+    sse, groups, iters = C.c_double(-1.0), C.c_int32(0), C.c_int32(0)
+    _check(call(*handle, C.byref(sse), C.byref(groups), C.byref(iters)))
+    return dict(sse=float(sse.value), groups=int(groups.value), iterations=int(iters.value))
+
+
+def _render_until(call, handle, iter_first, max_iters, group_iters, target_db):
+    done, psnr = C.c_int32(0), C.c_float(-1.0)
+    _check(call(*handle, int(iter_first), int(max_iters), int(group_iters), C.c_float(target_db), C.byref(done), C.byref(psnr)))
+    return int(done.value), float(psnr.value)
+
+
 class Renderer:
     """pathtraceInit / pathtrace / pathtraceFree over the C ABI (the default instance, like the reference's
     file-scope renderer state).  `arith`: "exact" (bit-identical to the oracle), "fma" or "fast" (PT_ARITH_*)."""
@@ -432,6 +480,27 @@ class Renderer:
         opt = denoise_options(**opts)
         _check(lib().pt_denoise(C.c_float(samples), C.byref(opt), _f(out)))
         return out
+
+    # ---- noise estimate from batch sums (include/pt_amd.h: pt_noise_fold) ----
+    def noise_fold(self) -> None:
+        """Folds the iterations rendered since the last fold into the noise estimate as one group (asynchronous)."""
+        _check(lib().pt_noise_fold())
+
+    def noise(self) -> dict:
+        """sse (SSE_est of the last fold, -1 before two groups), groups, iterations folded so far; psnr_from_sse(sse, n) is
+        the estimated PSNR of the tile."""
+        return _noise(lib().pt_get_noise)
+
+    def readback_noise(self) -> dict:
+        """The noise planes of the tile by name (split_noise): prev, q, variance."""
+        out = np.empty((NOISE_PLANES, self.n, 4), np.float32)
+        _check(lib().pt_readback_noise(_f(out)))
+        return split_noise(out)
+
+    def render_until(self, iter_first: int, max_iters: int, target_db: float, group_iters: int = 0):
+        """Renders groups of group_iters iterations (0 = a batch) until the estimated PSNR is above target_db or max_iters
+        are done (pt_render_until): (iterations rendered, last estimated PSNR in dB or -1)."""
+        return _render_until(lib().pt_render_until, (), iter_first, max_iters, group_iters, target_db)
 
     # ---- convergence metric (make_options(convergence=...)) ----
     def set_reference(self, rgb_avg: np.ndarray) -> None:
@@ -554,6 +623,18 @@ class Group:
         opt = denoise_options(**opts)
         _check(lib().pt_group_denoise(self._h, C.c_float(samples), C.byref(opt), _f(out)))
         return out
+
+    def noise_fold(self) -> None:
+        """Renderer.noise_fold on every context (pt_group_noise_fold)."""
+        _check(lib().pt_group_noise_fold(self._h))
+
+    def noise(self) -> dict:
+        """Renderer.noise of the whole frame: the contexts' SSE_est added in context order (pt_group_get_noise)."""
+        return _noise(lib().pt_group_get_noise, self._h)
+
+    def render_until(self, iter_first: int, max_iters: int, target_db: float, group_iters: int = 0):
+        """Renderer.render_until of the whole frame (pt_group_render_until); the PSNR is taken over W*H pixels."""
+        return _render_until(lib().pt_group_render_until, (self._h,), iter_first, max_iters, group_iters, target_db)
 
     def gather_u8(self, samples: float) -> np.ndarray:
         w, h = self.scene.resolution

@@ -23,6 +23,7 @@
 #include "pt_device.h"
 #include "pt_internal.h"
 #include "pt_kernels.h"
+#include "pt_noise.h"
 #include "pt_scene.h"
 #include "pt_sched.h"
 #include "pt_tables.h"
@@ -114,6 +115,11 @@ struct PtContext {
   float4* d_feat = nullptr;
   int grid_features = 0;
   void* d_denoise = nullptr;  // workspace of pt_ctx_denoise (pt_denoise_workspace_bytes(N)); absent until the first denoise call
+  // Noise estimate (pt_ctx_noise_fold, csrc/pt_noise.hip): planes, partial sums and their sum (pt_noise_state_bytes(N)); absent until the first fold
+  void* d_noise = nullptr;
+  int noise_groups = 0;      // M: folds since pt_init / pt_clear that had something to fold
+  int64_t noise_iters = 0;   // T: iterations those folds took
+  int64_t rendered = 0;      // iterations handed to pt_ctx_render since pt_init / pt_clear (samples is zeroed by pt_reset_stats; setup()'s timing batches never count)
   // Convergence metric (PtOptions.convergence, pt_kernels.h ConvInfo): all of it absent when the option is 0
   int conv = 0;                // the option: N > 0 capture the frame at iteration N, -1 supplied
   bool conv_live = false;      // off while setup() renders its timing batches: they leave no trace in the curve or the frame
@@ -766,6 +772,7 @@ int pt_ctx_render(PtContext* c, int iter_first, int iter_count) {
     }
   HIP_OK(hipEventRecord(ev.b, g.stream));
   g.pending_render.push_back(ev);
+  g.rendered += iter_count;
   return 0;
 }
 
@@ -839,6 +846,78 @@ int pt_ctx_denoise(PtContext* c, float samples, const PtDenoiseOptions* opt, flo
   if (pt_ctx_denoise_device(c, samples, opt, &d)) return -1;
   HIP_OK(hipMemcpyAsync(rgb_avg_host, d, 3 * (size_t)c->N * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   return pt_ctx_sync(c);
+}
+
+// ---- noise estimate from batch sums, render until a target PSNR (csrc/pt_noise.hip) ----------------------------
+int pt_ctx_noise_fold(PtContext* c) {
+  if (need(c, "pt_noise_fold")) return -1;
+  Ctx& g = *c;
+  if (g.failed) return fail("pt_noise_fold: an earlier batch of this context failed (%s); free it and create a new one", g_err.c_str());
+  const int64_t n = g.rendered - g.noise_iters;
+  if (n <= 0) return 0;  // nothing rendered since the last fold
+  HIP_OK(hipSetDevice(g.device));
+  if (!g.d_noise) {  // first fold of the context: the state, zeroed like the image it starts from
+    char* st = nullptr;
+    if (dalloc(g, &st, pt_noise_state_bytes((size_t)g.N))) return -1;
+    g.d_noise = st;
+    HIP_OK(hipMemsetAsync(g.d_noise, 0, pt_noise_state_bytes((size_t)g.N), g.stream));
+  }
+  if (pt_noise_launch(g.stream, g.N, g.d_image, g.d_noise, ptnz::fold_scalars(n, g.noise_groups + 1, g.noise_iters + n))) return -1;
+  g.noise_groups += 1;
+  g.noise_iters += n;
+  return 0;
+}
+
+int pt_ctx_get_noise(PtContext* c, double* sse, int* groups, int* iterations) {
+  if (need(c, "pt_get_noise")) return -1;
+  if (pt_ctx_sync(c)) return -1;
+  Ctx& g = *c;
+  if (sse) {
+    *sse = -1.0;
+    if (g.d_noise && g.noise_groups >= 2) {
+      const char* result = static_cast<const char*>(g.d_noise) + pt_noise_state_bytes((size_t)g.N) - sizeof(double);
+      HIP_OK(hipMemcpy(sse, result, sizeof(double), hipMemcpyDeviceToHost));
+    }
+  }
+  if (groups) *groups = g.noise_groups;
+  if (iterations) *iterations = (int)std::min<int64_t>(g.noise_iters, INT32_MAX);
+  return 0;
+}
+
+int pt_ctx_readback_noise(PtContext* c, float* planes_host) {
+  if (need(c, "pt_readback_noise")) return -1;
+  if (!planes_host) return fail("pt_readback_noise: null buffer");
+  if (!c->d_noise) return fail("pt_readback_noise: nothing has been folded (pt_noise_fold)");
+  HIP_OK(hipSetDevice(c->device));
+  HIP_OK(hipMemcpyAsync(planes_host, c->d_noise, (size_t)PT_NOISE_PLANES * c->N * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+  return pt_ctx_sync(c);
+}
+
+const float* pt_ctx_device_noise(PtContext* c) { return c ? static_cast<const float*>(c->d_noise) : nullptr; }
+
+int pt_ctx_render_until(PtContext* c, int iter_first, int max_iters, int group_iters, float target_db, int* iters_done, float* psnr_db) {
+  if (need(c, "pt_render_until")) return -1;
+  Ctx& g = *c;
+  if (iter_first < 1 || max_iters < 1 || (int64_t)iter_first + max_iters - 1 > INT32_MAX || group_iters < 0 || !std::isfinite(target_db))
+    return fail("pt_render_until: iterations %d, +%d in groups of %d until %g dB: the first is >= 1, the count >= 1, the group >= 0 (0 = a batch), the target finite",
+                iter_first, max_iters, group_iters, (double)target_db);
+  if (g.failed) return fail("pt_render_until: an earlier batch of this context failed (%s); free it and create a new one", g_err.c_str());
+  const int group = group_iters ? group_iters : g.K;
+  int done = 0;
+  float psnr = -1.0f;
+  while (done < max_iters) {
+    const int n = std::min(group, max_iters - done);
+    if (pt_ctx_render(c, iter_first + done, n)) return -1;
+    done += n;
+    double sse = -1.0;
+    if (pt_ctx_noise_fold(c) || pt_ctx_get_noise(c, &sse, nullptr, nullptr)) return -1;
+    if (sse < 0.0) continue;  // one group says nothing about the spread
+    psnr = pt_psnr_from_sse(sse, g.N);
+    if (psnr > target_db) break;
+  }
+  if (iters_done) *iters_done = done;
+  if (psnr_db) *psnr_db = psnr;
+  return 0;
 }
 
 int pt_ctx_sync(PtContext* c) {
@@ -973,6 +1052,9 @@ int pt_ctx_clear(PtContext* c) {
   if (pt_ctx_sync(c)) return -1;
   HIP_OK(hipMemsetAsync(c->d_image, 0, 3 * (size_t)c->N * sizeof(float), c->stream));
   if (c->d_feat) HIP_OK(hipMemsetAsync(c->d_feat, 0, (size_t)PT_FEATURE_PLANES * c->N * sizeof(float4), c->stream));  // sums and object ids
+  if (c->d_noise) HIP_OK(hipMemsetAsync(c->d_noise, 0, pt_noise_state_bytes((size_t)c->N), c->stream));
+  c->noise_groups = 0;
+  c->noise_iters = c->rendered = 0;
   if (c->conv) {  // forget the curve, re-arm the capture (a supplied frame stays)
     HIP_OK(hipMemsetAsync(c->d_sse, 0xff, (size_t)PT_CONVERGENCE_CAPACITY * sizeof(double), c->stream));
     c->conv_last = 0;
@@ -1046,6 +1128,12 @@ int pt_clear(void) { return pt_ctx_clear(g_default); }
 int pt_render_features(int iter_first, int iter_count) { return pt_ctx_render_features(g_default, iter_first, iter_count); }
 int pt_readback_features(float* planes_host) { return pt_ctx_readback_features(g_default, planes_host); }
 int pt_denoise(float samples, const PtDenoiseOptions* opt, float* rgb_avg_host) { return pt_ctx_denoise(g_default, samples, opt, rgb_avg_host); }
+int pt_noise_fold(void) { return pt_ctx_noise_fold(g_default); }
+int pt_get_noise(double* sse, int* groups, int* iterations) { return pt_ctx_get_noise(g_default, sse, groups, iterations); }
+int pt_readback_noise(float* planes_host) { return pt_ctx_readback_noise(g_default, planes_host); }
+int pt_render_until(int iter_first, int max_iters, int group_iters, float target_db, int* iters_done, float* psnr_db) {
+  return pt_ctx_render_until(g_default, iter_first, max_iters, group_iters, target_db, iters_done, psnr_db);
+}
 int pt_set_reference(const float* rgb_avg_host) { return pt_ctx_set_reference(g_default, rgb_avg_host); }
 int pt_get_convergence(int iter_first, int iter_count, double* sse) { return pt_ctx_get_convergence(g_default, iter_first, iter_count, sse); }
 int pt_iterations_to_clean(float threshold_db, int* iteration) { return pt_ctx_iterations_to_clean(g_default, threshold_db, iteration); }

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -323,6 +324,55 @@ int pt_group_denoise(PtGroup* g, float samples, const PtDenoiseOptions* opt, flo
   if (pt_denoise_launch(root, g->W, g->H, g->d_full, g->d_full_feat, samples, P, g->d_denoise, &d_out)) return fail_after_drain(g);
   HIP_OK(hipMemcpyAsync(rgb_avg_host, d_out, frame * 12, hipMemcpyDeviceToHost, root));
   return pt_group_sync(g);
+}
+
+// The noise estimate of the whole frame (pt_ctx_noise_fold): every context folds its own rows on its own stream, nothing is exchanged;
+// the estimates meet on the host, one double per context.
+int pt_group_noise_fold(PtGroup* g) {
+  if (!g) return pt_fail("pt_group_noise_fold: null group");
+  for (PtContext* c : g->ctx)
+    if (pt_ctx_noise_fold(c)) return -1;
+  return 0;
+}
+
+int pt_group_get_noise(PtGroup* g, double* sse, int* groups, int* iterations) {
+  if (!g) return pt_fail("pt_group_get_noise: null group");
+  double total = 0.0;
+  for (int i = 0; i < g->n; ++i) {  // context order
+    double part = -1.0;
+    if (pt_ctx_get_noise(g->ctx[i], &part, i == 0 ? groups : nullptr, i == 0 ? iterations : nullptr)) return -1;
+    total = (total < 0.0 || part < 0.0) ? -1.0 : total + part;
+  }
+  if (sse) *sse = total;
+  return 0;
+}
+
+int pt_group_render_until(PtGroup* g, int iter_first, int max_iters, int group_iters, float target_db, int* iters_done, float* psnr_db) {
+  if (!g) return pt_fail("pt_group_render_until: null group");
+  if (iter_first < 1 || max_iters < 1 || (int64_t)iter_first + max_iters - 1 > INT32_MAX || group_iters < 0 || !std::isfinite(target_db))
+    return pt_fail("pt_group_render_until: iterations %d, +%d in groups of %d until %g dB: the first is >= 1, the count >= 1, the group >= 0 (0 = a batch), the target finite",
+                   iter_first, max_iters, group_iters, (double)target_db);
+  int group = group_iters;
+  if (!group) {
+    PtStats st;
+    if (pt_ctx_get_stats(g->ctx[0], &st)) return -1;
+    group = st.iters_per_batch;
+  }
+  int done = 0;
+  float psnr = -1.0f;
+  while (done < max_iters) {
+    const int n = group < max_iters - done ? group : max_iters - done;
+    if (pt_group_render(g, iter_first + done, n)) return -1;
+    done += n;
+    double sse = -1.0;
+    if (pt_group_noise_fold(g) || pt_group_get_noise(g, &sse, nullptr, nullptr)) return -1;
+    if (sse < 0.0) continue;
+    psnr = pt_psnr_from_sse(sse, (int64_t)g->W * g->H);
+    if (psnr > target_db) break;
+  }
+  if (iters_done) *iters_done = done;
+  if (psnr_db) *psnr_db = psnr;
+  return 0;
 }
 
 int pt_group_gather_u8(PtGroup* g, float samples, uint8_t* rgb8_host) {

@@ -17,3 +17,14 @@ inline size_t pt_denoise_workspace_bytes(size_t pixels) { return 80 * pixels; }
 int pt_denoise_resolve(const char* who, float samples, const PtDenoiseOptions* opt, ptdn::Params* P);
 int pt_denoise_launch(hipStream_t stream, int w, int rows, const float* rgb_sum_dev, const float* planes_dev, float samples, const ptdn::Params& P,
                       void* workspace_dev, const float** rgb_avg_dev);
+
+// The noise estimate (pt_noise.hip), on raw device pointers and a stream.  state_dev holds pt_noise_state_bytes(pixels) bytes:
+// PT_NOISE_PLANES planes of `pixels` float4, then one double per PT_NOISE_PIXELS_PER_PARTIAL pixels (k_noise_fold's partial sums),
+// then the double they add up to (k_noise_reduce).  pt_noise_launch: one fold of the SUM image rgb_sum_dev (pixels * 3 floats) with the
+// scalars of ptnz::fold_scalars; asynchronous on `stream`.
+namespace ptnz {
+struct Fold;
+}
+inline size_t pt_noise_partials(size_t pixels) { return (pixels + 1023) / 1024; }
+inline size_t pt_noise_state_bytes(size_t pixels) { return 32 * pixels + 8 * (pt_noise_partials(pixels) + 1); }
+int pt_noise_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, void* state_dev, const ptnz::Fold& f);

@@ -7,6 +7,7 @@
 //                       [--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa]
 //                       [--preview N] [--convergence N | --reference FILE.pfm] [--clean-db X] [--features]
 //                       [--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]]
+//                       [--until-db X [--until-group G]]
 //
 // Without --gpus the run goes through the pathtrace.h-compatible shim (pathtraceInit / pathtrace per
 // iteration / pathtraceFree), i.e. the code path a reference main.cpp would take.  With --gpus K (K >= 1;
@@ -27,6 +28,10 @@
 // the averaged result goes to <base>.denoised.png and, with --pfm, <base>.denoised.pfm.  --denoise-levels N (1 .. 8, default 5),
 // --denoise-sigma C,N,P (colour, normal, position; 0 = the default 4, 0.5, 1; negative = that term off), --denoise-keep-albedo
 // (no demodulation by the first-hit albedo) are PtDenoiseOptions' fields.
+// --until-db X: render until the image's own noise estimate says it is clean (pt_render_until / pt_group_render_until): groups of G
+// iterations (--until-group, default 0 = one batch), a fold after each, until the estimated PSNR is above X dB; --spp becomes the cap.
+// Prints `noise: <iterations> iterations, <groups> groups, estimated PSNR <x> dB`; the file names, --features, --denoise and the
+// curves carry the iterations actually rendered.
 // Output name: PREFIX.<spp>samp.png, or with --stamp the reference's own
 // <FILE>.<UTC start time>.<spp>samp.png (main.cpp:99-102).
 #include <hip/hip_runtime.h>
@@ -35,6 +40,7 @@
 #include <cfloat>
 #include <chrono>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -49,15 +55,16 @@ int main(int argc, char** argv) {
     std::printf("Usage: %s SCENEFILE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] "
                 "[--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa] [--preview N] "
                 "[--convergence N | --reference FILE.pfm] [--clean-db X] [--features] "
-                "[--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]]\n", argv[0]);
+                "[--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]] [--until-db X [--until-group G]]\n", argv[0]);
     return 1;
   }
   int rw = 0, rh = 0, spp = 0, depth = 0, gpus = -1, arith = PT_ARITH_EXACT, preview = 0, transport = PT_GROUP_TRANSPORT_AUTO;
   std::vector<int> device_list;
   bool pfm = false, hdr = false, stamp = false, aa = false, features = false, denoise = false;
   PtDenoiseOptions dn_opt{};
-  int convergence = 0;
-  float clean_db = 35.0f;
+  int convergence = 0, until_group = 0;
+  bool until = false, until_group_given = false;
+  float clean_db = 35.0f, until_db = 0.0f;
   std::string out, reference;
   for (int i = 2; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--res") && i + 1 < argc) std::sscanf(argv[++i], "%dx%d", &rw, &rh);
@@ -116,6 +123,23 @@ int main(int argc, char** argv) {
         return 1;
       }
     }
+    else if (!std::strcmp(argv[i], "--until-db") && i + 1 < argc) {
+      char* end = nullptr;
+      until_db = std::strtof(argv[++i], &end);
+      if (end == argv[i] || *end || !std::isfinite(until_db)) {
+        std::fprintf(stderr, "--until-db wants the estimated PSNR in dB at which to stop, a finite number\n");
+        return 1;
+      }
+      until = true;
+    } else if (!std::strcmp(argv[i], "--until-group") && i + 1 < argc) {
+      char* end = nullptr;
+      const long v = std::strtol(argv[++i], &end, 10);
+      if (end == argv[i] || *end || v < 0 || v > INT32_MAX) {
+        std::fprintf(stderr, "--until-group wants the iterations per group of --until-db (0 = one batch)\n");
+        return 1;
+      }
+      until_group = (int)v, until_group_given = true;
+    }
     else if (!std::strcmp(argv[i], "--aa")) aa = true;  // extension: stochastic anti-aliasing (PtOptions.aa_jitter)
     else if (!std::strcmp(argv[i], "--arith") && i + 1 < argc) {
       const char* a = argv[++i];
@@ -141,6 +165,14 @@ int main(int argc, char** argv) {
     return 1;
   }
   if (denoise) features = true;
+  if (until_group_given && !until) {
+    std::fprintf(stderr, "--until-group wants --until-db\n");
+    return 1;
+  }
+  if (until && preview > 0) {
+    std::fprintf(stderr, "--until-db and --preview exclude each other (one loop over the iterations)\n");
+    return 1;
+  }
   pt::Scene* scene = nullptr;
   try {
     scene = new pt::Scene(argv[1]);
@@ -153,14 +185,25 @@ int main(int argc, char** argv) {
   if (depth > 0) scene->state.traceDepth = depth;
   scene->applyInitialCameraState();
   const int W = scene->state.camera.resolution[0], H = scene->state.camera.resolution[1];
-  const int iters = (int)scene->state.iterations;
+  int iters = (int)scene->state.iterations;  // with --until-db the cap, until the render has said how many it took
   if (out.empty()) out = scene->state.imageName;
-  std::string base = out + "." + std::to_string(iters) + "samp";
-  if (stamp) {
-    char buf[1024];
-    pt_output_basename(out.c_str(), iters, buf, sizeof buf);
-    base = buf;
-  }
+  std::string base;
+  auto name_outputs = [&]() {
+    base = out + "." + std::to_string(iters) + "samp";
+    if (stamp) {
+      char buf[1024];
+      pt_output_basename(out.c_str(), iters, buf, sizeof buf);  // (one start time per process)
+      base = buf;
+    }
+  };
+  name_outputs();
+  // --until-db: what the render took and what it reached; everything after it speaks of the iterations actually rendered
+  auto report_noise = [&](int done, int groups, float psnr) {
+    std::printf("noise: %d iterations, %d groups, estimated PSNR %.9g dB\n", done, groups, (double)psnr);
+    iters = done;
+    scene->state.iterations = done;
+    name_outputs();
+  };
 
   std::vector<float> ref_frame;  // --reference: W * H averaged radiance
   if (!reference.empty()) {
@@ -219,7 +262,17 @@ int main(int argc, char** argv) {
       return EXIT_FAILURE;
     }
     const auto t0 = std::chrono::high_resolution_clock::now();
-    for (int it = 1; it <= iters; ++it) pathtrace(nullptr, 0, it);  // main.cpp:138-149
+    if (until) {
+      int done = 0, groups = 0;
+      float psnr = -1.0f;
+      if (pt_render_until(1, iters, until_group, until_db, &done, &psnr) || pt_get_noise(nullptr, &groups, nullptr)) {
+        std::fprintf(stderr, "HIP error (pt_render_until): %s\n", pt_last_error());
+        return EXIT_FAILURE;
+      }
+      report_noise(done, groups, psnr);
+    } else {
+      for (int it = 1; it <= iters; ++it) pathtrace(nullptr, 0, it);  // main.cpp:138-149
+    }
     pathtraceSyncImage();
     secs = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
     std::printf("%dx%d, %d spp, depth %d: %.3f s, %.2f Msamples/s\n", W, H, iters, scene->state.traceDepth, secs,
@@ -303,6 +356,11 @@ int main(int argc, char** argv) {
           if (!rc) pt_write_png_rgb8((out + ".preview.png").c_str(), rgb.data(), W, H);
         }
       }
+    } else if (until) {
+      int done = 0, groups = 0;
+      float psnr = -1.0f;
+      rc = pt_group_render_until(grp, 1, iters, until_group, until_db, &done, &psnr) || pt_group_get_noise(grp, nullptr, &groups, nullptr);
+      if (!rc) report_noise(done, groups, psnr);
     } else {
       rc = pt_group_render(grp, 1, iters);
     }

@@ -357,6 +357,49 @@ int pt_denoise(float samples, const PtDenoiseOptions* opt, float* rgb_avg_host);
  * (pt_readback_features' layout), out w*rows*3 floats.  Needs no GPU; the device result equals it bit for bit. */
 int pt_denoise_host(int w, int rows, const float* rgb_sum, const float* planes, float samples, const PtDenoiseOptions* opt, float* rgb_avg);
 
+/* ---- noise estimate from batch sums, and rendering until a target PSNR.  pt_get_convergence says how far the image is from a given
+ * frame; this says how noisy the image is when there is no such frame, so that a renderer can stop by itself.  The SUM image S is
+ * looked at only at group boundaries (batches of iterations, never single samples) by a streaming kernel of its own
+ * (csrc/pt_noise.hip); pt_render and its kernels know nothing of it.  Specified to the bit, like the filter above: float32 throughout,
+ * every operation a separate IEEE operation in the order written (no FMA contraction, correctly rounded division, denormals kept),
+ * so the planes are the same in all three PT_ARITH_* builds, on the host (pt_noise_fold_host) and on the device.
+ * State: PT_NOISE_PLANES planes, each pixel_count float4 in tile order:
+ *   plane 0  prev.xyz (S at the last fold), w   (the estimate, below)
+ *   plane 1  q.xyz,                          +0
+ * all zero at allocation and after pt_clear (S is zero then too).  Per renderer: groups M, iterations T folded so far, and `rendered`,
+ * the iterations handed to pt_render since pt_init or pt_clear (pt_reset_stats leaves it alone).
+ * A fold takes all iterations rendered since the last fold as ONE group of n = rendered - T iterations; n == 0: nothing happens.
+ * Then M += 1, T += n and, with nf = (float)n, Tf = (float)T, Df = (float)(M - 1) * Tf, per pixel and component k = x, y, z:
+ *   b = S_k - prev_k;   q_k = q_k + (b * b) / nf;   prev_k = S_k
+ *   M >= 2:  d = q_k - (S_k * S_k) / Tf;   v_k = (d > 0 ? d : 0) / Df
+ *   w = M >= 2 ? (v_x + v_y) + v_z : +0
+ * w estimates the variance of the pixel's AVERAGED radiance, summed over the channels: with group sums B_j of n_j samples,
+ * sum_j B_j^2 / n_j - S^2 / T has expectation (M - 1) sigma^2 for any group sizes, and sigma^2 / T is the variance of the mean.
+ * Frame statistic: SSE_est = sum over the tile pixels of (double)w, in the unit of pt_get_convergence's SSE against a converged
+ * frame; estimated PSNR = pt_psnr_from_sse(SSE_est, pixel_count).  On the device every PT_NOISE_PIXELS_PER_PARTIAL consecutive tile
+ * pixels give one double, and a second launch adds those in index order: no atomics, equal tiles and equal folds give equal bits.
+ * The host function adds in pixel order; the two may differ in the last bits.
+ * Memory: 32 * N + 8 * (ceil(N / PT_NOISE_PIXELS_PER_PARTIAL) + 1) bytes for a tile of N pixels, allocated and zeroed by the first
+ * fold that has something to fold, part of PtStats.device_bytes from then on, kept across pt_clear, which zeroes it and M, T. */
+#define PT_NOISE_PLANES 2
+#define PT_NOISE_PIXELS_PER_PARTIAL 1024
+int pt_noise_fold(void); /* asynchronous on the renderer's stream; changes neither the image nor PtStats.samples */
+/* Synchronises.  *sse = SSE_est of the last fold, -1 while groups < 2 (or nothing has been folded); any pointer may be NULL. */
+int pt_get_noise(double* sse, int* groups, int* iterations);
+int pt_readback_noise(float* planes_host); /* PT_NOISE_PLANES * pixel_count * 4 floats; synchronises; an error before the first fold */
+/* Render until the image is clean: groups of group_iters iterations (0 = PtStats.iters_per_batch; the last one is cut so that no
+ * more than max_iters are rendered) from iteration iter_first on, a fold after each, then the one double is read (one synchronise
+ * per group).  Stops after the first fold with groups >= 2 whose estimated PSNR is above target_db (`>`, like
+ * pt_iterations_to_clean), or at max_iters; returns 0 either way.  *iters_done: iterations rendered by this call; *psnr_db: the
+ * last estimate, -1 when there is none (either may be NULL).  Groups folded before the call count; iterations rendered but not
+ * yet folded join the first group.  Errors, with nothing rendered or allocated: iter_first < 1, max_iters < 1 (or iterations past
+ * 2^31 - 1), group_iters < 0, a target that is not finite, a failed context. */
+int pt_render_until(int iter_first, int max_iters, int group_iters, float target_db, int* iters_done, float* psnr_db);
+/* One fold on the host (no GPU): rgb_sum pixels*3 floats (S), planes PT_NOISE_PLANES * pixels * 4 floats, updated in place;
+ * group_iters = n, groups_after = M and iters_after = T after this fold; *sse (may be NULL) = the estimates added in pixel order, -1
+ * while groups_after < 2.  The device's planes equal it bit for bit. */
+int pt_noise_fold_host(int pixels, const float* rgb_sum, float* planes, int group_iters, int groups_after, int64_t iters_after, double* sse);
+
 /* saveImage()'s per-pixel conversion (main.cpp:91-97 x mirror, image.cpp:26-30 clamp * 255 truncated) on the
  * device: pixel_count*3 bytes, row-major, x mirrored inside each row; the tile must consist of whole rows.
  * Reads back 3 B per pixel instead of 12. */
@@ -385,6 +428,11 @@ int pt_ctx_readback_features(PtContext* c, float* planes_host);
 int pt_ctx_denoise(PtContext* c, float samples, const PtDenoiseOptions* opt, float* rgb_avg_host);
 /* Asynchronous on the context's stream; *rgb_dev (pixel_count * 3 floats, inside the workspace) stays valid until the next denoise call. */
 int pt_ctx_denoise_device(PtContext* c, float samples, const PtDenoiseOptions* opt, const float** rgb_dev);
+int pt_ctx_noise_fold(PtContext* c);
+int pt_ctx_get_noise(PtContext* c, double* sse, int* groups, int* iterations);
+int pt_ctx_readback_noise(PtContext* c, float* planes_host);
+int pt_ctx_render_until(PtContext* c, int iter_first, int max_iters, int group_iters, float target_db, int* iters_done, float* psnr_db);
+const float* pt_ctx_device_noise(PtContext* c); /* device pointer of plane 0; the planes are contiguous; NULL before the first fold */
 const float* pt_ctx_device_features(PtContext* c); /* device pointer of plane 0; the planes are contiguous; NULL before the first pt_ctx_render_features */
 const float* pt_ctx_device_image(PtContext* c); /* device pointer of the tile SUM image */
 void* pt_ctx_stream(PtContext* c);              /* the context's hipStream_t */
@@ -427,6 +475,13 @@ int pt_group_gather_features(PtGroup* g, float* planes_host);            /* PT_F
  * root device as for the two gathers above, and the filter runs there, on the root's stream, with a workspace of 80 B per frame
  * pixel owned by the group.  Errors as pt_denoise (before a feature pass: an error). */
 int pt_group_denoise(PtGroup* g, float samples, const PtDenoiseOptions* opt, float* rgb_avg_host);
+/* The noise estimate of the whole frame: every context folds its own rows (nothing is exchanged), the contexts' SSE_est are added
+ * in context order on the host, and the estimated PSNR is taken over W*H pixels.  pt_group_render_until is pt_render_until with
+ * pt_group_render, one synchronise of every device per group; group_iters 0 = the first context's iters_per_batch.  Gathering the
+ * planes of a group is not offered (pt_ctx_readback_noise of pt_group_context(g, i) gives a context's rows). */
+int pt_group_noise_fold(PtGroup* g);
+int pt_group_get_noise(PtGroup* g, double* sse, int* groups, int* iterations);
+int pt_group_render_until(PtGroup* g, int iter_first, int max_iters, int group_iters, float target_db, int* iters_done, float* psnr_db);
 /* Progressive preview of the running average (sendImageToPBO, pathtrace.cu:250-268, which the reference runs after every
  * iteration): W*H RGBA8 bytes, raw orientation, converted on each device, one exchange of 4 B per pixel. */
 int pt_group_preview_rgba8(PtGroup* g, int iterations, uint8_t* rgba_host);
