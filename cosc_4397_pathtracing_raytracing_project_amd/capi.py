@@ -322,7 +322,7 @@ def make_options(device: int = 0, pixel_begin: int = 0, pixel_count: int = 0, it
                  num_queues: int = 0, blocks_per_cu: int = 0, time_kernels: bool = False, legacy_traversal: bool = False,
                  debug_flags: int = 0, unfused_primary: bool = False, unfused_bounces: bool = False,
                  stripe_pixels: int = 0, stripe_stride: int = 0, arith="exact", aa_jitter: bool = False,
-                 lds_table_kb: int = 0, primary_pieces: int = 0, paths_pieces: int = 0, paths_min_piece: int = 0,
+                 lds_table_kb: int = 0, primary_pieces: int = 0, paths_pieces: int = 0, paths_min_piece: int = 0, primary_share: int = 0,
                  convergence: int = 0) -> PtOptions:
     opt = PtOptions()
     opt.device = device
@@ -342,7 +342,9 @@ def make_options(device: int = 0, pixel_begin: int = 0, pixel_count: int = 0, it
     opt.aa_jitter = 1 if aa_jitter else 0
     opt.convergence = int(convergence)  # 0 off, N > 0 reference frame captured at iteration N, -1 supplied (set_reference)
     opt.lds_table_kb = int(lds_table_kb)
-    opt.primary_pieces = int(primary_pieces)
+    # PT_PRIMARY_PIECES (include/pt_amd.h): primary_share (0 automatic, 1 a trace per iteration, up to 64) rides in bits 16-22
+    pp = int(primary_pieces)  # negative: passed on as it is (pt_init clamps it to one piece)
+    opt.primary_pieces = pp if pp < 0 else min(pp, 0x7fff) | max(0, min(int(primary_share), 64)) << 16
     opt.paths_pieces = int(paths_pieces)
     opt.paths_min_piece = int(paths_min_piece)
     return opt

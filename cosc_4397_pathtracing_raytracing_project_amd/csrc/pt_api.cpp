@@ -31,7 +31,7 @@
 namespace {
 
 std::string g_err;
-constexpr int kDebugFlags = 16 | 32 | 64 | 256 | 512 | 2048;  // the PtOptions.debug_flags bits pt_init accepts
+constexpr int kDebugFlags = 16 | 32 | 64 | 128 | 256 | 512 | 2048;  // the PtOptions.debug_flags bits pt_init accepts
 static_assert(sizeof(PtOptions) == 80, "capi.PtOptions mirrors this layout");
 static_assert(PT_CONVERGENCE_WAVES == ptk::kConvWaves, "pt_amd.h documents the size of the convergence metric's partial sums");
 }  // namespace
@@ -85,6 +85,7 @@ struct PtContext {
   int lds_table_bytes = -1;        // SceneTables::lds_table_bytes
   int lds_table_forced = -1;       // PtOptions.lds_table_kb in bytes; -1: KernelApi::lds_table_limit decides
   int primary_pieces = 0;          // BatchInfo::primary_pieces forced by PtOptions.primary_pieces; 0: run_batch decides
+  int primary_share = 0;           // BatchInfo::primary_share forced through PT_PRIMARY_PIECES; 0: automatic (primary_share_of)
   int paths_pieces = 0;            // BatchInfo::paths_pieces (PtOptions.paths_pieces, paths_min_piece)
   // Uniform grids over the leaf boxes (pt::build_grid; SceneTables::grid_*), large scenes where one beats the BVH scan: setup()
   // uploads the candidates of pt::build_scene_tables, choose_traversal() times them, keeps the fastest and frees the rest.
@@ -231,6 +232,12 @@ ptd::Queues queues_for(const Ctx& g, int grid) {
   return q;
 }
 
+// BatchInfo::primary_share of the context's batches: debug_flags 128 and a primary_share of 1 both mean a trace per iteration;
+// automatic: the longest run, a whole piece per trace (on the whole frame caps of 8 to 64 iterations measure alike, 4 is 0.5 %
+// slower: profiles/first_hit_sharing.log section 2b).
+int primary_share_of(const Ctx& g) { return (g.debug_flags & 128) ? 1 : g.primary_share ? g.primary_share : ptk::kShareMax; }
+bool shares_first_hit(const Ctx& g) { return ptk::primary_shares(primary_share_of(g), g.aa_jitter, !g.fuse_bounces); }
+
 int run_batch(Ctx& g, int iter_first, int kb) {
   ptk::BatchInfo b{};
   b.iter_first = iter_first;
@@ -241,7 +248,9 @@ int run_batch(Ctx& g, int iter_first, int kb) {
   b.slot_shift = g.slot_shift;
   b.aa_jitter = g.aa_jitter ? 1 : 0;
   b.flat = g.fuse_bounces ? 0 : 1;
-  b.primary_pieces = g.primary_pieces ? g.primary_pieces : ptk::auto_primary_pieces(kb, g.qs.nq, g.ret.wq0);
+  b.primary_share = primary_share_of(g);
+  b.primary_pieces = g.primary_pieces ? g.primary_pieces
+                     : ptk::primary_shares(b) ? ptk::auto_shared_pieces(kb, g.qs.nq, g.ret.wq0) : ptk::auto_primary_pieces(kb, g.qs.nq, g.ret.wq0);
   b.paths_pieces = g.paths_pieces;
   b.stripe = g.stripe;
   b.gap = g.stripe ? g.stripe_stride - g.stripe : 0;
@@ -315,7 +324,7 @@ void plan_launch(Ctx& g) {
   g.grid_gen = g.num_cus * std::min(g.cap_bpc, g.k->resident_blocks_per_cu(ptk::kGenerate, t));
   g.grid_isect = g.num_cus * std::min(g.cap_bpc, g.k->resident_blocks_per_cu(g.legacy ? ptk::kIntersectLegacy : ptk::kIntersect, t));
   g.grid_shade = g.num_cus * std::min(g.cap_bpc, g.k->resident_blocks_per_cu(ptk::kShade, t));
-  g.grid_primary = g.num_cus * std::min(g.cap_bpc, g.k->resident_blocks_per_cu(ptk::kPrimary, t));
+  g.grid_primary = g.num_cus * std::min(g.cap_bpc, g.k->resident_blocks_per_cu(shares_first_hit(g) ? ptk::kPrimaryShared : ptk::kPrimary, t));
   g.ret.wq0 = ptk::wave_slot(0, g.qs.Q, g.grid_primary * ptk::kWavesPerBlock).wq;  // the sub-lists' residue count (pt_device.h RetireBuf)
   g.grid_paths = (g.fuse_bounces && g.depth > 1) ? g.num_cus * std::min(g.cap_bpc, g.k->resident_blocks_per_cu(ptk::kPaths, t)) : 0;
   g.qs.paths_W = g.grid_paths * ptk::kWavesPerBlock;  // what k_count_stats deals to the queues (a table made for another width is ignored)
@@ -434,6 +443,7 @@ int open_device(Ctx& g, const PtOptions& opt) {
   if (!g.k) return fail("pt_init: arith %d is not one of PT_ARITH_EXACT / PT_ARITH_FMA / PT_ARITH_FAST", opt.arith);
   if (opt.convergence < -1) return fail("pt_init: convergence %d is not 0 (off), N > 0 (frame captured at iteration N) or -1 (frame supplied)", opt.convergence);
   if (opt.convergence > PT_CONVERGENCE_CAPACITY) return fail("pt_init: convergence %d exceeds PT_CONVERGENCE_CAPACITY (%d iterations)", opt.convergence, PT_CONVERGENCE_CAPACITY);
+  if (opt.primary_pieces > 0 && (opt.primary_pieces >> 16) > ptk::kShareMax) return fail("pt_init: primary_pieces 0x%x: primary_share %d exceeds %d (PT_PRIMARY_PIECES)", opt.primary_pieces, opt.primary_pieces >> 16, ptk::kShareMax);
   if (opt.debug_flags & ~kDebugFlags) return fail("pt_init: debug_flags 0x%x: bits 0x%x are not defined", opt.debug_flags, opt.debug_flags & ~kDebugFlags);
   int ndev = 0;
   HIP_OK(hipGetDeviceCount(&ndev));
@@ -464,7 +474,8 @@ void take_scene_and_options(Ctx& g, const PtSceneDesc* sc, const PtOptions& opt)
   g.conv = opt.convergence;
   auto pieces = [](int v, int automatic) { return v ? std::clamp(v, 1, 0x7fff) : automatic; };
   g.lds_table_forced = opt.lds_table_kb ? std::clamp(opt.lds_table_kb, 0, ptk::kLdsTableBytes / 1024) * 1024 : -1;
-  g.primary_pieces = pieces(opt.primary_pieces, 0);
+  g.primary_pieces = pieces(opt.primary_pieces < 0 ? opt.primary_pieces : opt.primary_pieces & 0xffff, 0);
+  g.primary_share = opt.primary_pieces < 0 ? 0 : std::min(opt.primary_pieces >> 16 & 0x7f, ptk::kShareMax);  // PT_PRIMARY_PIECES
   g.paths_pieces = ptk::pack_paths_pieces(pieces(opt.paths_pieces, 2), pieces(opt.paths_min_piece, 64));
   g.fuse_primary = !g.legacy && !opt.unfused_primary;
   g.fuse_bounces = g.fuse_primary && !opt.unfused_bounces;

@@ -108,7 +108,9 @@ struct HitBuf {
 //     queue q, seg_cap = nq * 64 of them, and the depth-1 list (q, k) — the survivors of depth 0 — lives at path index
 //     q * cap + k * seg_cap, also seg_cap long;
 //   * depth 0 (k_primary): in iteration k wave r of the queue's wq0 waves traces the chunks jj = rho, rho + wq0, ... with
-//     rho = (r + k) mod wq0 (the residue rotates so that chunk counts even out over a batch).  Those are c(rho) chunks, and
+//     rho = (r + k) mod wq0 (the residue rotates so that chunk counts even out over a batch) — or, when the camera rays are the
+//     same in every iteration (no aa_jitter), rho = r throughout, each chunk traced once per run of iterations and shaded in
+//     every one of them (pt_sched.h, shared form: same owner rule, same contents).  Those are c(rho) chunks, and
 //     off(rho) chunks belong to smaller residues, so SUB-list / SUB-region (q, k, rho) = slots [off(rho) * 64, (off(rho) +
 //     c(rho)) * 64) of list / region (q, k) is the wave's own: it appends survivors to the sub-list and retirees to the front
 //     of the sub-region from counters in its registers, stores at once, and leaves the two counts in sub[q][k][rho];

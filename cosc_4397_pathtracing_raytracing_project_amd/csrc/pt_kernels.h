@@ -78,6 +78,8 @@ struct BatchInfo {
                   // reads that); 0: to one list per (queue, iteration) (k_paths, pt_device.h RetireBuf)
   int32_t primary_pieces;  // k_primary: a (queue, wave) strand's iterations cut into this many pieces, the first taken by the wave
                            // itself, the others by whoever is free (an atomic counter behind ptd::Queues::deal); <= 1: one piece
+  int32_t primary_share;   // k_primary: > 1 (and no aa_jitter, not flat): the shared form — a chunk's camera rays are traced once per run of
+                           // at most this many iterations (and 64) and shaded in each of them; <= 1: traced in every iteration
   int32_t paths_pieces;    // k_paths: low 16 bits: a queue's depth-1 rays cut into this many pieces per wave, one its own, the others first
                            // come, first served (counters behind ptd::Queues::deal); <= 1: one piece per wave; high 16 bits: fewest paths in a piece
 };
@@ -97,7 +99,7 @@ struct ConvInfo {
 // Resident workgroups per CU for each persistent kernel (hipOccupancyMaxActiveBlocksPerMultiprocessor),
 // so that grid = CUs * blocks never exceeds what is co-resident: work is dealt statically to waves,
 // a workgroup that has to wait for a free slot would run its whole share after everybody else.
-enum KernelId { kGenerate = 0, kIntersect = 1, kShade = 2, kIntersectLegacy = 3, kPrimary = 4, kPaths = 5, kFeatures = 6 };
+enum KernelId { kGenerate = 0, kIntersect = 1, kShade = 2, kIntersectLegacy = 3, kPrimary = 4, kPaths = 5, kFeatures = 6, kPrimaryShared = 7 };
 
 // pt_kernels.hip is compiled once per arithmetic mode (PtOptions.arith, include/pt_amd.h):
 //   0 exact  -ffp-contract=off, every operation in the reference's order: bit-identical to oracle/pt_oracle.cpp

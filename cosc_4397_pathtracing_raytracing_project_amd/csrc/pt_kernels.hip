@@ -1062,7 +1062,12 @@ PT_DEV void carry_drain_to(Carry<SMALL, NPAR>& c, int mark, int lane, const ptd:
 // Unlike the ring form tried in round 2 it keeps the camera-relative boxes and the per-geom object-space camera position.
 // kTopScan (tables in memory, no grid): one wave-uniform scan of the threaded tree per group (trace_group_packet) instead of
 // top list + per-lane subtree scans.
-template <Search F>
+// SHARE (BatchInfo::primary_share > 1, no aa_jitter, not flat; pt_sched.h): the camera ray of a pixel, and so its hit key, normal
+// and point, do not depend on the iteration — the loop nest is chunk outer, iteration inner: a chunk is generated, searched and
+// resolved ONCE per run of iterations and shaded in each of them with that iteration's seed (every sample is still drawn, shaded,
+// bounced and stored; the records, their order and the image are those of the per-iteration form, which stays for jittered
+// rays, the flat lists and as the A/B switch PtOptions.debug_flags 128).  The search sits above the shading in all three forms.
+template <Search F, bool SHARE = false>
 __global__ __launch_bounds__(kBlock, kPrimaryWaves) void k_primary(SceneTables sc, ptd::Camera cam, BatchInfo b, ptd::Queues qs,
                                                     int32_t* __restrict__ cnt0, int32_t* __restrict__ cnt_out,
                                                     ptd::PathBuf out, ptd::RetireBuf ret) {
@@ -1195,52 +1200,141 @@ __global__ __launch_bounds__(kBlock, kPrimaryWaves) void k_primary(SceneTables s
     } pp;
     pp.any = false;
     if constexpr (RING) ws = carry_init<true, 2>(wbase), ws.qo_tab = cam_qo, ws.cam_o = o;  // every strand starts with an empty ring
-    int it = 0;
-    for (int k = k0, rho = strand_rho(r, k0, wq); k < k1; ++k, rho = rho + 1 == wq ? 0 : rho + 1) {
-      for (int jj = rho; jj < sh.my_nq; jj += wq, ++it) {
-        const int pl_raw = chunk_pixel(q, jj, qs.Q) + lane;
-        const bool valid = pl_raw < b.N;
-        const int pl = valid ? pl_raw : b.N - 1;  // tile pixel
-        const int slot = make_slot(b, k, pl);
-        const int p = global_pixel(b, pl);  // global pixel index
-        const uint32_t phash = utilhash((uint32_t)p);
-        float jx = 0.f, jy = 0.f;
-        if (b.aa_jitter) aa_jitter(b.iter_first + k, p, jx, jy);
-        const f3 d = Ar<kD0>::camera_dir(cam, inv_w, p, b.aa_jitter != 0, jx, jy);
-        // Primary rays come in bundles of 64 neighbouring pixels and half of the 16:9 frame looks past the scene:
-        // one test against the bounds of the whole tree per lane, and if no lane passes (a parent box rejects
-        // whatever its children would, the slab arithmetic being monotone) the 7 leaf-box tests are skipped.
-        const bool near_scene = ballot(valid && Ar<kD0>::slab(o, Ar<kD0>::ray_inv(d, o), sc.root_min[0], sc.root_min[1], sc.root_min[2],
-                                                       sc.root_max[0], sc.root_max[1], sc.root_max[2])) != 0;
-        if constexpr (RING) {
-          const int par = it & 1;
-          ws.best[par * 64 + lane] = kNoHit;
-          if (near_scene) carry_search<false, 2, true, kD0>(ws, cam_top, ntop, nodes, geoms, o, d, valid, lane, par, sc.cull_margin, sc.top_xor);
-          if (pp.any) carry_drain_to<true, 2, kD0, true>(ws, pp.mark, lane, nodes, geoms);  // the previous group's candidates are now all resolved
-          if (pp.any) shade_group(ws.best[pp.par * 64 + lane], ws.rec + pp.par * 6 * 64 + lane, pp.valid, pp.k, pp.pl, pp.slot, pp.phash, pp.d);
-          pp.d = d, pp.k = k, pp.pl = pl, pp.slot = slot, pp.phash = phash, pp.valid = valid, pp.par = par, pp.mark = ws.appended, pp.any = true;
-        } else if constexpr (GRID) {
-          ws.cy.best[lane] = kNoHit;
-          if (near_scene) {
-            grid_search<1, kD0>(ws.cy, ws.cr, sc, nodes, geoms, o, d, valid, lane, 0);
-            while (ws.cy.count > 0) carry_chunk<false, 1, kD0, true>(ws.cy, min(64, ws.cy.count), lane, nodes, geoms);
+    if constexpr (SHARE) {
+      // (The per-group search dispatch below and shade_run restate the per-iteration loop and shade_group of the else branch, kept
+      // apart so that the per-iteration instance compiles to the code it had: a fix to one copy has to be made in the other.)
+      // Shared form (pt_sched.h): the wave keeps residue r through the piece, so chunk jj is traced ONCE per run of iterations
+      // [s0, s1) and shaded s1 - s0 times from the same hit; lane l of vnl / vnd counts the survivors / retirees of iteration s0 + l.
+      const int cap = shared_run_cap(b.primary_share), sub_off = sub_offset(quo, rem, shared_rho(r, k0, wq)) * 64;
+      for (int run = 0, runs = shared_runs(k0, k1, cap); run < runs; ++run) {
+        const Run sr = shared_run(k0, k1, cap, run);
+        const int s0 = sr.k0, s1 = sr.k1;
+        int vnl = 0, vnd = 0;
+        // shading + retirement + compaction of one group of primary rays in every iteration of the run
+        auto shade_run = [&](unsigned long long best, const float* rec, bool valid, int pl, uint32_t phash, f3 d) {
+          const bool hit = (uint32_t)(best >> 32) != 0x7f7fffffu;
+          f3 hn = mk(0.f, 0.f, 0.f), hp = mk(0.f, 0.f, 0.f);
+          float ht = -1.0f;
+          int hmat = 0;
+          if (valid && hit) {
+            ht = __uint_as_float((uint32_t)(best >> 32));
+            const ptd::Geom* G = geoms + nodes[(uint32_t)best].geom;
+            hmat = G->material;
+            hn = mk(rec[0 * 64], rec[1 * 64], rec[2 * 64]);
+            hp = mk(rec[3 * 64], rec[4 * 64], rec[5 * 64]);
+            if (GRID) hn = Ar<kD0>::finish_normal(G, hn);
           }
-          shade_group(ws.cy.best[lane], ws.cy.rec + lane, valid, k, pl, slot, phash, d);
-        } else {
-          if (near_scene) trace_group_packet<kD0>(ws, nodes, sc.num_nodes, geoms, o, d, valid, lane, sc.has_triangles != 0);
-          else ws.best[lane] = kNoHit;
-          shade_group(ws.best[lane], ws.rec + lane, valid, k, pl, slot, phash, d);
+          for (int k = s0; k < s1; ++k) {
+            ShadeIO s;
+            s.o = o;
+            s.d = d;
+            s.c = mk(1.0f, 1.0f, 1.0f);
+            s.alive = false;
+            Bounce bo;
+            bo.kind = 0;
+            if (valid) bo = shade_decide(mats, b.trace_depth, 0, iter_hash_of(ihash, sc, b, 0, k) ^ phash, ht, hmat, s);
+            const bool alive = valid && s.alive, dead = valid && !s.alive;
+            if (alive) shade_bounce(bo, hn, hp, s);
+            const unsigned long long live = ballot(alive), deadm = ballot(dead);
+            const int nl = __builtin_amdgcn_readlane(vnl, k - s0), nd = __builtin_amdgcn_readlane(vnd, k - s0);
+            const int sub0 = k * rt.seg_cap + sub_off;  // first slot of sub-list / sub-region (q, k, r)
+            const PathTag tag{make_slot(b, k, pl), phash, k};
+            if (alive) path_store(out, qbase + sub0 + nl + rank_in(live), s.o, s.d, s.c, tag);
+            if (dead) rt.rec[sub0 + nd + rank_in(deadm)] = ptd::Word4{s.c.x, s.c.y, s.c.z, __int_as_float(pl)};
+            if (lane == k - s0) vnl += (int)__popcll(live), vnd += (int)__popcll(deadm);
+          }
+        };
+        if constexpr (RING) ws = carry_init<true, 2>(wbase), ws.qo_tab = cam_qo, ws.cam_o = o;  // every run starts with an empty ring
+        pp.any = false;
+        int it = 0;
+        for (int jj = shared_rho(r, s0, wq); jj < sh.my_nq; jj += wq, ++it) {
+          const int pl_raw = chunk_pixel(q, jj, qs.Q) + lane;
+          const bool valid = pl_raw < b.N;
+          const int pl = valid ? pl_raw : b.N - 1;  // tile pixel
+          const int p = global_pixel(b, pl);        // global pixel index
+          const uint32_t phash = utilhash((uint32_t)p);
+          const f3 d = Ar<kD0>::camera_dir(cam, inv_w, p, false, 0.f, 0.f);
+          const bool near_scene = ballot(valid && Ar<kD0>::slab(o, Ar<kD0>::ray_inv(d, o), sc.root_min[0], sc.root_min[1], sc.root_min[2],
+                                                         sc.root_max[0], sc.root_max[1], sc.root_max[2])) != 0;
+          if constexpr (RING) {
+            const int par = it & 1;
+            ws.best[par * 64 + lane] = kNoHit;
+            if (near_scene) carry_search<false, 2, true, kD0>(ws, cam_top, ntop, nodes, geoms, o, d, valid, lane, par, sc.cull_margin, sc.top_xor);
+            if (pp.any) {  // the previous group's candidates are now all resolved; its key and record stay in its parity's half while it is shaded
+              carry_drain_to<true, 2, kD0, true>(ws, pp.mark, lane, nodes, geoms);
+              shade_run(ws.best[pp.par * 64 + lane], ws.rec + pp.par * 6 * 64 + lane, pp.valid, pp.pl, pp.phash, pp.d);
+            }
+            pp.d = d, pp.pl = pl, pp.phash = phash, pp.valid = valid, pp.par = par, pp.mark = ws.appended, pp.any = true;
+          } else if constexpr (GRID) {
+            ws.cy.best[lane] = kNoHit;
+            if (near_scene) {
+              grid_search<1, kD0>(ws.cy, ws.cr, sc, nodes, geoms, o, d, valid, lane, 0);
+              while (ws.cy.count > 0) carry_chunk<false, 1, kD0, true>(ws.cy, min(64, ws.cy.count), lane, nodes, geoms);
+            }
+            shade_run(ws.cy.best[lane], ws.cy.rec + lane, valid, pl, phash, d);
+          } else {
+            if (near_scene) trace_group_packet<kD0>(ws, nodes, sc.num_nodes, geoms, o, d, valid, lane, sc.has_triangles != 0);
+            else ws.best[lane] = kNoHit;
+            shade_run(ws.best[lane], ws.rec + lane, valid, pl, phash, d);
+          }
+        }
+        if constexpr (RING) {
+          if (pp.any) {
+            carry_drain_to<true, 2, kD0, true>(ws, pp.mark, lane, nodes, geoms);
+            shade_run(ws.best[pp.par * 64 + lane], ws.rec + pp.par * 6 * 64 + lane, pp.valid, pp.pl, pp.phash, pp.d);
+          }
+        }
+        // the run's counts, one lane per iteration (zeros where the wave had no chunk)
+        if (lane < s1 - s0) rt.sub[(s0 + lane) * rt.wq0 + shared_rho(r, s0 + lane, wq)] = ((unsigned long long)(uint32_t)vnd << 32) | (uint32_t)vnl;
+      }
+    } else {
+      int it = 0;
+      for (int k = k0, rho = strand_rho(r, k0, wq); k < k1; ++k, rho = rho + 1 == wq ? 0 : rho + 1) {
+        for (int jj = rho; jj < sh.my_nq; jj += wq, ++it) {
+          const int pl_raw = chunk_pixel(q, jj, qs.Q) + lane;
+          const bool valid = pl_raw < b.N;
+          const int pl = valid ? pl_raw : b.N - 1;  // tile pixel
+          const int slot = make_slot(b, k, pl);
+          const int p = global_pixel(b, pl);  // global pixel index
+          const uint32_t phash = utilhash((uint32_t)p);
+          float jx = 0.f, jy = 0.f;
+          if (b.aa_jitter) aa_jitter(b.iter_first + k, p, jx, jy);
+          const f3 d = Ar<kD0>::camera_dir(cam, inv_w, p, b.aa_jitter != 0, jx, jy);
+          // Primary rays come in bundles of 64 neighbouring pixels and half of the 16:9 frame looks past the scene:
+          // one test against the bounds of the whole tree per lane, and if no lane passes (a parent box rejects
+          // whatever its children would, the slab arithmetic being monotone) the 7 leaf-box tests are skipped.
+          const bool near_scene = ballot(valid && Ar<kD0>::slab(o, Ar<kD0>::ray_inv(d, o), sc.root_min[0], sc.root_min[1], sc.root_min[2],
+                                                         sc.root_max[0], sc.root_max[1], sc.root_max[2])) != 0;
+          if constexpr (RING) {
+            const int par = it & 1;
+            ws.best[par * 64 + lane] = kNoHit;
+            if (near_scene) carry_search<false, 2, true, kD0>(ws, cam_top, ntop, nodes, geoms, o, d, valid, lane, par, sc.cull_margin, sc.top_xor);
+            if (pp.any) carry_drain_to<true, 2, kD0, true>(ws, pp.mark, lane, nodes, geoms);  // the previous group's candidates are now all resolved
+            if (pp.any) shade_group(ws.best[pp.par * 64 + lane], ws.rec + pp.par * 6 * 64 + lane, pp.valid, pp.k, pp.pl, pp.slot, pp.phash, pp.d);
+            pp.d = d, pp.k = k, pp.pl = pl, pp.slot = slot, pp.phash = phash, pp.valid = valid, pp.par = par, pp.mark = ws.appended, pp.any = true;
+          } else if constexpr (GRID) {
+            ws.cy.best[lane] = kNoHit;
+            if (near_scene) {
+              grid_search<1, kD0>(ws.cy, ws.cr, sc, nodes, geoms, o, d, valid, lane, 0);
+              while (ws.cy.count > 0) carry_chunk<false, 1, kD0, true>(ws.cy, min(64, ws.cy.count), lane, nodes, geoms);
+            }
+            shade_group(ws.cy.best[lane], ws.cy.rec + lane, valid, k, pl, slot, phash, d);
+          } else {
+            if (near_scene) trace_group_packet<kD0>(ws, nodes, sc.num_nodes, geoms, o, d, valid, lane, sc.has_triangles != 0);
+            else ws.best[lane] = kNoHit;
+            shade_group(ws.best[lane], ws.rec + lane, valid, k, pl, slot, phash, d);
+          }
         }
       }
-    }
-    if constexpr (RING) {
-      if (pp.any) {
-        carry_drain_to<true, 2, kD0, true>(ws, pp.mark, lane, nodes, geoms);
-        shade_group(ws.best[pp.par * 64 + lane], ws.rec + pp.par * 6 * 64 + lane, pp.valid, pp.k, pp.pl, pp.slot, pp.phash, pp.d);
+      if constexpr (RING) {
+        if (pp.any) {
+          carry_drain_to<true, 2, kD0, true>(ws, pp.mark, lane, nodes, geoms);
+          shade_group(ws.best[pp.par * 64 + lane], ws.rec + pp.par * 6 * 64 + lane, pp.valid, pp.k, pp.pl, pp.slot, pp.phash, pp.d);
+        }
       }
+      if (!b.flat)
+        while (ck < k1) next_iteration();  // the last iteration's counts, and zeros for trailing iterations without a chunk
     }
-    if (!b.flat)
-      while (ck < k1) next_iteration();  // the last iteration's counts, and zeros for trailing iterations without a chunk
     if (plan.pieces == 1) break;
     int nx = 0;
     if (lane == 0) nx = atomicAdd(&qs.deal[deal_map(qs).strand_counter()], 1);

@@ -25,14 +25,16 @@ void with_features(const SceneTables& sc, F&& f) {
   if (leaves_fit_top(sc)) return f(k_features<false, false>, intersect_lds<false>(sc).total);
   return f(k_features<false, true>, intersect_lds<false>(sc).total);
 }
+// share: the shared loop form (one trace per chunk and run of iterations, pt_sched.h) — both forms use the same LDS map
 template <typename F>
-void with_primary(const SceneTables& sc, F&& f) {
+void with_primary(const SceneTables& sc, bool share, F&& f) {
   switch (search_form(sc)) {
-    case kLdsTables: return f(k_primary<kLdsTables>, primary_lds<kLdsTables, kFast, kD0>(sc).total);
-    case kTopScan: return f(k_primary<kTopScan>, primary_lds<kTopScan, kFast, kD0>(sc).total);
-    case kGrid: return f(k_primary<kGrid>, primary_lds<kGrid, kFast, kD0>(sc).total);
+    case kLdsTables: return share ? f(k_primary<kLdsTables, true>, primary_lds<kLdsTables, kFast, kD0>(sc).total) : f(k_primary<kLdsTables>, primary_lds<kLdsTables, kFast, kD0>(sc).total);
+    case kTopScan: return share ? f(k_primary<kTopScan, true>, primary_lds<kTopScan, kFast, kD0>(sc).total) : f(k_primary<kTopScan>, primary_lds<kTopScan, kFast, kD0>(sc).total);
+    case kGrid: return share ? f(k_primary<kGrid, true>, primary_lds<kGrid, kFast, kD0>(sc).total) : f(k_primary<kGrid>, primary_lds<kGrid, kFast, kD0>(sc).total);
   }
 }
+
 template <typename F>
 void with_paths(const SceneTables& sc, Search form, F&& f) {  // (SceneTables::scan_nodes_lds resolved by the caller)
   switch (form) {
@@ -106,7 +108,8 @@ int resident_blocks_per_cu(KernelId id, const SceneTables& sc) {
     case kGenerate: query(k_generate, 0); break;
     case kIntersect: with_intersect(sc, false, false, query); break;
     case kIntersectLegacy: with_intersect(sc, true, false, query); break;
-    case kPrimary: with_primary(sc, query_share); break;
+    case kPrimary: with_primary(sc, false, query_share); break;
+    case kPrimaryShared: with_primary(sc, true, query_share); break;
     case kPaths: with_paths(resolve_scan_nodes(sc), search_form(sc), query_share); break;
     case kShade: query(k_shade, shade_lds<true>(sc).total); break;
     case kFeatures: with_features(sc, query); break;
@@ -128,7 +131,7 @@ void launch_intersect(hipStream_t s, int grid, const SceneTables& sc, const ptd:
 
 void launch_primary(hipStream_t s, int grid, const SceneTables& sc, const ptd::Camera& cam, const BatchInfo& b,
                     const ptd::Queues& qs, int32_t* cnt0, int32_t* cnt_out, ptd::PathBuf out, ptd::RetireBuf ret) {
-  with_primary(sc, [&](auto kernel, int lds) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, sc, cam, b, qs, cnt0, cnt_out, out, ret); });
+  with_primary(sc, primary_shares(b), [&](auto kernel, int lds) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, sc, cam, b, qs, cnt0, cnt_out, out, ret); });
 }
 
 void launch_features(hipStream_t s, int grid, const SceneTables& sc, const ptd::Camera& cam, const BatchInfo& b, float4* feat) {

@@ -145,6 +145,39 @@ PT_SCHED int auto_primary_pieces(int K, int nq, int wq0) {
   return want < 1 ? 1 : want > 4 ? 4 : (int)want;
 }
 
+// ── k_primary, shared form: one trace per chunk and run of iterations ──────────────────────────────────────────────────────
+// Without anti-aliasing jitter a pixel's camera ray, and so its first hit, is the same in every iteration.  In the shared
+// form a strand keeps ONE residue, rho = r in every iteration of its piece, so the wave meets the same chunks jj = r, r + wq,
+// ... in all of them: it traces a chunk once and shades it for a run of iterations.  (queue, iteration k, residue rho) is
+// then owned by (wave rho, piece containing k): still one owner, and for a fixed k the owner still appends its chunks in
+// ascending jj, so every sub-list and sub-region holds what the per-iteration form puts there, in the same order.
+// A run is at most kShareMax iterations (the per-iteration counters of a run live in the 64 lanes of two registers); a
+// longer piece is walked as sub-runs, each tracing the chunks again.
+constexpr int kShareMax = 64;
+// Which form a batch runs: the shared one needs the camera rays to be the same in every iteration (no jitter) and the
+// per-(queue, iteration) sub-lists (not flat); BatchInfo::primary_share <= 1 asks for a trace per iteration.
+PT_SCHED bool primary_shares(int primary_share, bool aa_jitter, bool flat) { return primary_share > 1 && !aa_jitter && !flat; }
+PT_SCHED bool primary_shares(const BatchInfo& b) { return primary_shares(b.primary_share, b.aa_jitter != 0, b.flat != 0); }
+PT_SCHED int shared_rho(int r, int /*k*/, int /*wq*/) { return r; }  // the strand's residue in iteration k: the same in all of them (beside strand_rho)
+// Longest run per trace from BatchInfo::primary_share (<= 1: the per-iteration form, not this one).
+PT_SCHED int shared_run_cap(int primary_share) { return primary_share < 1 ? 1 : sched_min(primary_share, kShareMax); }
+// Sub-runs of the piece [k0, k1): i = 0 .. shared_runs() - 1 cover [k0 + i * cap, min(k1, k0 + (i + 1) * cap)).
+struct Run {
+  int k0, k1;
+};
+PT_SCHED int shared_runs(int k0, int k1, int cap) { return (k1 - k0 + cap - 1) / cap; }
+PT_SCHED Run shared_run(int k0, int k1, int cap, int i) { return Run{k0 + i * cap, sched_min(k1, k0 + (i + 1) * cap)}; }
+// The host's choice of primary_pieces for the shared form.  A wave with a fixed residue has quo or quo + 1 chunks in EVERY
+// iteration (the per-iteration form's rotation evened that out over the batch), so the pieces behind the counter are what
+// levels the waves, and each piece pays one trace per chunk.  Swept on the whole 1080p frame (K = 25) and on an eighth of it
+// (K = 195), profiles/first_hit_sharing.log section 2b: 2 pieces win on the frame (1 / 2 / 4 / 8: 31.3 / 31.9 / 31.4 / 28.5 k
+// Msamples/s), 4 on the eighth (29.5 / 29.9 / 30.2 / 26.8 k), where a piece of K / 4 = 49 iterations is still ONE run — a
+// piece longer than kShareMax traces its chunks again anyway, so it may as well be a piece of its own: max(2, ceil(K / 64)).
+PT_SCHED int auto_shared_pieces(int K, int /*nq*/, int /*wq0*/) {
+  const int want = sched_max(2, (K + kShareMax - 1) / kShareMax);
+  return sched_max(1, sched_min(want, K));
+}
+
 // ── k_paths: falling pieces ───────────────────────────────────────────────────────────────────────────────────────────────
 // BatchInfo::paths_pieces: pieces per wave | fewest paths in a piece << 16.
 PT_SCHED int pack_paths_pieces(int count, int min_piece) { return count | min_piece << 16; }

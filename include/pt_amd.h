@@ -98,7 +98,9 @@ typedef struct PtOptions {
   int32_t legacy_traversal; /* 1: per-lane BVH walk kernel instead of the wave-cooperative one (A/B) */
   int32_t debug_flags;      /* A-B switches with UNCHANGED results: 16 no closer-hit cull in the subtree scans, 32 no
                                near-first subtree order, 64 W / Q waves per queue in every batch of the fused bounce kernel
-                               (default: dealt by the time the queues' waves took, PtStats.paths_waves), 256 / 512 force /
+                               (default: dealt by the time the queues' waves took, PtStats.paths_waves), 128 the fused primary
+                               kernel traces its camera rays in every iteration (default without aa_jitter: once per run of
+                               iterations, see primary_share), 256 / 512 force /
                                forbid the uniform-grid walk of the fused kernels (default: for large scenes, whichever of the
                                BVH scan and up to three grid resolutions renders a few iterations fastest at pt_init), 2048
                                keep the reference's leaf boxes for spheres (default for large scenes: tightened to the
@@ -129,11 +131,19 @@ typedef struct PtOptions {
                                in memory (automatic: staged when every leaf is a top-list entry and staging costs the fused
                                bounce kernel no resident workgroup) */
   int32_t primary_pieces;   /* the fused primary kernel's per-wave strands cut into this many pieces (automatic:
-                               min(4, max(1, strand groups / 48))) */
+                               max(2, iterations per batch / 64 rounded up) when it traces once per run of iterations; with a trace per
+                               iteration min(4, max(1, strand groups / 48))).  Bits 16-22 of the same word hold primary_share
+                               (PT_PRIMARY_PIECES below; the struct keeps its 20 words): the kernel traces a group of camera
+                               rays once for at most that many iterations of a batch and shades it in each of them (0 =
+                               automatic: a whole piece, at most 64; 1: a trace per iteration, as debug_flags 128; always a
+                               trace per iteration with aa_jitter, whose rays differ from iteration to iteration) */
   int32_t paths_pieces;     /* the fused bounce kernel's depth-1 rays cut into this many pieces per wave (automatic: 2) */
   int32_t paths_min_piece;  /* fewest paths in one of those pieces (automatic: 64; small values send small images through
-                               the piece switches).  The three piece counts are clamped to 1..0x7fff. */
+                               the piece switches).  The three piece counts are clamped to 1..0x7fff (of primary_pieces: its low 16
+                               bits; a negative word counts as 1 piece; pt_init fails when bits 16 and up hold more than 64). */
 } PtOptions;
+/* PtOptions.primary_pieces from a piece count (0 .. 0x7fff) and primary_share (0 .. 64). */
+#define PT_PRIMARY_PIECES(pieces, share) ((int32_t)((pieces) | (share) << 16))
 
 /* Arithmetic modes (PtOptions.arith).  All modes run the same algorithm with the same random draws and decisions;
  * they differ in how float expressions are rounded.

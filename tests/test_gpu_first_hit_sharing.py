@@ -1,0 +1,132 @@
+"""k_primary's shared form: a chunk's camera rays are traced once per run of iterations and shaded in each of them
+(csrc/pt_sched.h).  Without aa_jitter the first hit of a pixel is the same in every iteration, so the
+image, the live-ray counts and the sample count must be those of the per-iteration form (PtOptions.debug_flags 128), bit for
+bit, in every search form of depth 0 (LDS tables with the candidate ring, packet scan, grid walk), on whole frames, partial
+last chunks and a rank's striped tile, with runs cut by short last batches, by pieces, by the 64-iteration limit and by
+primary_share — and in exact mode both must be the oracle's image (PORTABLE math, RETIRE loop)."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+PER_ITERATION = 128  # PtOptions.debug_flags: depth 0 traced in every iteration
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def gpu_render(scene_path, res, spp, **kw):
+    from cosc_4397_pathtracing_raytracing_project_amd import capi
+    r = capi.Renderer(capi.Scene(scene_path, res=res), **kw)
+    try:
+        r.render(1, spp)
+        return r.readback(), r.stats()
+    finally:
+        r.free()
+
+
+def both_forms(scene_path, res, spp, arith="exact", **kw):
+    """(image, stats) of the default form and of the per-iteration form; asserts that the two agree."""
+    flags = kw.pop("debug_flags", 0)
+    shared, st_s = gpu_render(scene_path, res, spp, arith=arith, debug_flags=flags, **kw)
+    per_it, st_p = gpu_render(scene_path, res, spp, arith=arith, debug_flags=flags | PER_ITERATION, **kw)
+    assert np.isfinite(shared).all()
+    diff = (bits(shared) != bits(per_it)).any(axis=1)
+    assert not diff.any(), f"{arith}: {diff.sum()} pixels differ between the forms, first {np.flatnonzero(diff)[:8]}"
+    assert st_s.samples == st_p.samples == shared.shape[0] * spp
+    assert list(st_s.live_rays) == list(st_p.live_rays)
+    return shared, per_it
+
+
+def oracle_image(oracle, scene_path, res, spp, aa=False):
+    oracle.set_math_mode(oracle.PORTABLE)
+    oracle.load_scene(scene_path, res=res)
+    try:
+        oracle.set_aa_jitter(aa)
+        return oracle.render(1, spp, depth=8, variant=oracle.RETIRE, nthreads=16)
+    finally:
+        oracle.set_aa_jitter(False)
+
+
+def assert_is_oracle(imgs, ref):
+    for img in imgs:
+        diff = (bits(img) != bits(ref)).any(axis=1)
+        assert not diff.any(), f"{diff.sum()} pixels differ from the oracle, first {np.flatnonzero(diff)[:8]}"
+
+
+@pytest.fixture(scope="module")
+def cornell_ref(scene_dir):
+    """The oracle's 200x120, 7 spp cornell image: computed once for the three arithmetic modes' case."""
+    from oracle import binding as ob
+    try:
+        return oracle_image(ob, scene_dir["cornell"], (200, 120), 7)
+    finally:
+        ob.set_math_mode(ob.LIBM)
+
+
+@pytest.mark.parametrize("arith", ["exact", "fma", "fast"])
+def test_cornell_short_last_batch_every_mode(scene_dir, cornell_ref, arith):
+    """LDS tables, candidate ring; 7 iterations in batches of 3, so the last batch has one.  fma / fast: the shading of the two
+    loop forms must round alike (explicit contractions); exact: and both are the oracle's image."""
+    imgs = both_forms(scene_dir["cornell"], (200, 120), 7, arith=arith, iters_per_batch=3)
+    if arith == "exact":
+        assert_is_oracle(imgs, cornell_ref)
+
+
+@pytest.mark.parametrize("name,res,spp,kw", [
+    ("partial last chunk", (201, 119), 3, {}),                                      # 23919 pixels: the tile's last chunk has 47
+    ("long batch in one piece", (64, 48), 70, dict(iters_per_batch=70, primary_pieces=1)),  # a run of 70: sub-runs of 64 and 6
+    ("primary_share 2", (96, 64), 7, dict(iters_per_batch=5, primary_share=2)),     # sub-runs 2 + 2 + 1, then a batch of 2
+    ("primary_share 2 in pieces", (96, 64), 7, dict(iters_per_batch=5, primary_share=2, primary_pieces=2)),  # pieces 3 + 2: runs 2 + 1, 2
+])
+def test_cornell_runs_cut_every_way(scene_dir, oracle, name, res, spp, kw):
+    imgs = both_forms(scene_dir["cornell"], res, spp, **kw)
+    assert_is_oracle(imgs, oracle_image(oracle, scene_dir["cornell"], res, spp))
+
+
+@pytest.mark.parametrize("pieces", [1, 3])
+def test_rank_tile_in_pieces(scene_dir, oracle, pieces):
+    """Rank 0's striped tile of an eight-way split: a queue owns a few chunks, some beside the box; strands in one piece and in
+    three, the later ones behind the counter."""
+    from cosc_4397_pathtracing_raytracing_project_amd import parallel
+    res, spp = (640, 360), 5
+    w, h = res
+    o = parallel.striped_tile_for_rank(w, h, 0, 8)
+    shared, _ = both_forms(scene_dir["cornell"], res, spp, iters_per_batch=3, primary_pieces=pieces, **o)
+    oracle.set_math_mode(oracle.PORTABLE)
+    oracle.load_scene(scene_dir["cornell"], res=res)
+    for row in list(range(0, h, 8))[12:30:3]:  # rows that look into the box
+        ref = oracle.render(1, spp, depth=8, variant=oracle.RETIRE, nthreads=8, pix_begin=row * w, pix_count=w)
+        assert np.array_equal(bits(shared.reshape(-1, w, 3)[row // 8]), bits(ref.reshape(-1, 3))), row
+
+
+def test_packet_scan_on_a_random_scene(oracle, tmp_path):
+    """33 leaves: more than the top list holds, tables in memory, no grid — depth 0 is one wave-uniform scan per group."""
+    from cosc_4397_pathtracing_raytracing_project_amd import scenes
+    res, spp = (96, 64), 6
+    from cosc_4397_pathtracing_raytracing_project_amd import capi
+    path = scenes.write_scene(scenes.random_scene_text(2, 27, res=res), str(tmp_path / "rnd.txt"))
+    # the packet scan is what runs when the tables stay in memory and no grid is walked: more leaves than the top list's 32
+    # keep them out of LDS; lds_table_kb < 0 and debug_flags 512 (grid forbidden) hold that whatever the limits become
+    assert (len(capi.Scene(path, res=res).bvh()) + 1) // 2 > 32
+    imgs = both_forms(path, res, spp, iters_per_batch=4, lds_table_kb=-1, debug_flags=512)
+    assert gpu_render(path, res, 1, lds_table_kb=-1, debug_flags=512)[1].grid_cells == 0
+    assert_is_oracle(imgs, oracle_image(oracle, path, res, spp))
+
+
+def test_grid_walk_on_stress_big(scene_dir, oracle):
+    res, spp = (160, 90), 4
+    flags = 256  # the uniform-grid walk forced
+    imgs = both_forms(scene_dir["stress_big"], res, spp, debug_flags=flags)
+    assert gpu_render(scene_dir["stress_big"], res, 1, debug_flags=flags)[1].grid_cells > 0  # the grid is what was walked
+    assert_is_oracle(imgs, oracle_image(oracle, scene_dir["stress_big"], res, spp))
+
+
+def test_jittered_rays_are_traced_in_every_iteration(scene_dir, oracle):
+    """aa_jitter: the camera rays differ from iteration to iteration, nothing can be shared — the per-iteration form runs with
+    and without the switch (pt_sched.h primary_shares; tests/test_sched_shared.py), and the image is the oracle's jittered one."""
+    res, spp = (96, 64), 5
+    imgs = both_forms(scene_dir["cornell"], res, spp, aa_jitter=True, iters_per_batch=3)
+    assert_is_oracle(imgs, oracle_image(oracle, scene_dir["cornell"], res, spp, aa=True))
+    plain, _ = gpu_render(scene_dir["cornell"], res, spp, iters_per_batch=3)
+    assert not np.array_equal(bits(plain), bits(imgs[0]))
