@@ -31,7 +31,7 @@
 namespace {
 
 std::string g_err;
-constexpr int kDebugFlags = 16 | 32 | 64 | 128 | 256 | 512 | 2048;  // the PtOptions.debug_flags bits pt_init accepts
+constexpr int kDebugFlags = 16 | 32 | 64 | 128 | 256 | 512 | ptk::kRetireEveryIteration | 2048;  // the PtOptions.debug_flags bits pt_init accepts
 static_assert(sizeof(PtOptions) == 80, "capi.PtOptions mirrors this layout");
 static_assert(PT_CONVERGENCE_WAVES == ptk::kConvWaves, "pt_amd.h documents the size of the convergence metric's partial sums");
 }  // namespace
@@ -252,6 +252,7 @@ int run_batch(Ctx& g, int iter_first, int kb) {
   b.primary_pieces = g.primary_pieces ? g.primary_pieces
                      : ptk::primary_shares(b) ? ptk::auto_shared_pieces(kb, g.qs.nq, g.ret.wq0) : ptk::auto_primary_pieces(kb, g.qs.nq, g.ret.wq0);
   b.paths_pieces = g.paths_pieces;
+  b.retire_once = ptk::retires_once(b, g.debug_flags) ? 1 : 0;  // (every batch of the context, the timing batches of choose_traversal among them)
   b.stripe = g.stripe;
   b.gap = g.stripe ? g.stripe_stride - g.stripe : 0;
   b.inv_stripe = g.stripe ? 1.0f / (float)g.stripe : 0.0f;
@@ -571,6 +572,13 @@ int upload_tables(Ctx& g, const pt::HostTables& t) {
   return 0;
 }
 
+// Every retirement record slot := (quiet NaN, NaN, NaN, tile pixel chunk_pixel(q, 0, Q) of the slot's queue q); see alloc_batch_buffers.
+__global__ void k_poison_records(ptd::Word4* rec, unsigned long long per_queue, unsigned long long total, int Q) {
+  const float nan = __builtin_nanf("");
+  for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (unsigned long long)gridDim.x * blockDim.x)
+    rec[i] = ptd::Word4{nan, nan, nan, __int_as_float(ptk::chunk_pixel((int)(i / per_queue), 0, Q))};
+}
+
 // Path state, hit records, retirement records, image, counters.
 int alloc_batch_buffers(Ctx& g) {
   const int Q = g.qs.Q;
@@ -580,6 +588,15 @@ int alloc_batch_buffers(Ctx& g) {
     const size_t regions = (size_t)Q * g.ret.kmax;
     const size_t wq_max = ptk::sub_stride(g.num_cus * 8 * ptk::kWavesPerBlock, Q);  // (8 resident workgroups per CU at the most)
     if (dalloc(g, &g.ret.rec, regions * g.ret.seg_cap) || dalloc(g, &g.ret.cnt, regions) || dalloc(g, &g.ret.sub, regions * wq_max)) return -1;
+    // In a BatchInfo::retire_once batch nobody writes the retiree slots at the front of the regions k >= 1, and later they hold an older
+    // batch's identical records: a gather that wrongly read them would still produce the right image.  So every slot starts as
+    // (NaN, NaN, NaN, first pixel of the slot's queue) — a wrongly gathered slot then shows in the first batch of a context.
+    {
+      const size_t per_queue = (size_t)g.ret.kmax * g.ret.seg_cap;
+      hipLaunchKernelGGL(k_poison_records, dim3((unsigned)std::min<size_t>((regions * g.ret.seg_cap + 255) / 256, 65536)), dim3(256), 0, g.stream, g.ret.rec,
+                         (unsigned long long)per_queue, (unsigned long long)(regions * g.ret.seg_cap), Q);
+      HIP_OK(hipGetLastError());
+    }
     HIP_OK(hipMemset(g.ret.cnt, 0, regions * sizeof(unsigned long long)));  // k_collect re-zeroes them after every batch
     HIP_OK(hipMemset(g.ret.sub, 0, regions * wq_max * sizeof(unsigned long long)));
   }

@@ -82,6 +82,8 @@ struct BatchInfo {
                            // at most this many iterations (and 64) and shaded in each of them; <= 1: traced in every iteration
   int32_t paths_pieces;    // k_paths: low 16 bits: a queue's depth-1 rays cut into this many pieces per wave, one its own, the others first
                            // come, first served (counters behind ptd::Queues::deal); <= 1: one piece per wave; high 16 bits: fewest paths in a piece
+  int32_t retire_once;     // 1 (the host sets it from pt_sched.h retires_once): a sample that retires at depth 0 does so in every iteration, with the
+                           // same colour — k_primary stores its record in iteration 0 of the batch only, k_collect gathers it there only
 };
 
 // Convergence metric of the gather (PtOptions.convergence; k_collect_conv in pt_output.inc).  Iteration iter_first + k of a batch gets

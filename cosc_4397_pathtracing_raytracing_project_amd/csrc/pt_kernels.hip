@@ -1067,6 +1067,8 @@ PT_DEV void carry_drain_to(Carry<SMALL, NPAR>& c, int mark, int lane, const ptd:
 // resolved ONCE per run of iterations and shaded in each of them with that iteration's seed (every sample is still drawn, shaded,
 // bounced and stored; the records, their order and the image are those of the per-iteration form, which stays for jittered
 // rays, the flat lists and as the A/B switch PtOptions.debug_flags 128).  The search sits above the shading in all three forms.
+// BatchInfo::retire_once (pt_sched.h): the records of the lanes that retire here — the same lanes with the same colour in every
+// iteration — are stored in iteration 0 of the batch only, and a group that holds nothing else skips the iteration loop.
 template <Search F, bool SHARE = false>
 __global__ __launch_bounds__(kBlock, kPrimaryWaves) void k_primary(SceneTables sc, ptd::Camera cam, BatchInfo b, ptd::Queues qs,
                                                     int32_t* __restrict__ cnt0, int32_t* __restrict__ cnt_out,
@@ -1206,6 +1208,7 @@ __global__ __launch_bounds__(kBlock, kPrimaryWaves) void k_primary(SceneTables s
       // Shared form (pt_sched.h): the wave keeps residue r through the piece, so chunk jj is traced ONCE per run of iterations
       // [s0, s1) and shaded s1 - s0 times from the same hit; lane l of vnl / vnd counts the survivors / retirees of iteration s0 + l.
       const int cap = shared_run_cap(b.primary_share), sub_off = sub_offset(quo, rem, shared_rho(r, k0, wq)) * 64;
+      const bool once = b.retire_once != 0;
       for (int run = 0, runs = shared_runs(k0, k1, cap); run < runs; ++run) {
         const Run sr = shared_run(k0, k1, cap, run);
         const int s0 = sr.k0, s1 = sr.k1;
@@ -1224,6 +1227,29 @@ __global__ __launch_bounds__(kBlock, kPrimaryWaves) void k_primary(SceneTables s
             hp = mk(rec[3 * 64], rec[4 * 64], rec[5 * 64]);
             if (GRID) hn = Ar<kD0>::finish_normal(G, hn);
           }
+          // BatchInfo::retire_once (pt_sched.h): a miss or an emitter hit retires here in every iteration with the same colour — the
+          // tests are shade_decide's own, which returns for both before it uses a draw — and every other hit survives.  Those lanes'
+          // records are written in iteration 0 of the batch only, to the slots they have always had; vnd still advances in every
+          // iteration, so sub[], k_paths' slots and the statistics are what they were.
+          const bool cdead = once && valid && (ht < 0.0f || mats[hmat].emittance > 0.0f);
+          const unsigned long long cdeadm = once ? ballot(cdead) : 0ull;
+          if (once) {
+            if (s0 == 0 && cdeadm) {  // this run holds iteration 0 of the batch
+              ShadeIO s;
+              s.o = o;
+              s.d = d;
+              s.c = mk(1.0f, 1.0f, 1.0f);
+              s.alive = false;
+              if (cdead) {
+                shade_decide(mats, b.trace_depth, 0, iter_hash_of(ihash, sc, b, 0, 0) ^ phash, ht, hmat, s);
+                rt.rec[sub_off + __builtin_amdgcn_readlane(vnd, 0) + rank_in(cdeadm)] = ptd::Word4{s.c.x, s.c.y, s.c.z, __int_as_float(pl)};
+              }
+            }
+            if (ballot(valid && !cdead) == 0) {  // nobody survives, in any iteration: only the counts move
+              if (lane < s1 - s0) vnd += (int)__popcll(cdeadm);
+              return;
+            }
+          }
           for (int k = s0; k < s1; ++k) {
             ShadeIO s;
             s.o = o;
@@ -1235,12 +1261,12 @@ __global__ __launch_bounds__(kBlock, kPrimaryWaves) void k_primary(SceneTables s
             if (valid) bo = shade_decide(mats, b.trace_depth, 0, iter_hash_of(ihash, sc, b, 0, k) ^ phash, ht, hmat, s);
             const bool alive = valid && s.alive, dead = valid && !s.alive;
             if (alive) shade_bounce(bo, hn, hp, s);
-            const unsigned long long live = ballot(alive), deadm = ballot(dead);
+            const unsigned long long live = ballot(alive), deadm = once ? cdeadm : ballot(dead);
             const int nl = __builtin_amdgcn_readlane(vnl, k - s0), nd = __builtin_amdgcn_readlane(vnd, k - s0);
             const int sub0 = k * rt.seg_cap + sub_off;  // first slot of sub-list / sub-region (q, k, r)
             const PathTag tag{make_slot(b, k, pl), phash, k};
             if (alive) path_store(out, qbase + sub0 + nl + rank_in(live), s.o, s.d, s.c, tag);
-            if (dead) rt.rec[sub0 + nd + rank_in(deadm)] = ptd::Word4{s.c.x, s.c.y, s.c.z, __int_as_float(pl)};
+            if (dead && !once) rt.rec[sub0 + nd + rank_in(deadm)] = ptd::Word4{s.c.x, s.c.y, s.c.z, __int_as_float(pl)};
             if (lane == k - s0) vnl += (int)__popcll(live), vnd += (int)__popcll(deadm);
           }
         };

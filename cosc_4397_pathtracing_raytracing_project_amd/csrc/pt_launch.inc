@@ -158,13 +158,13 @@ int flat_grid(int n, int cap) {
   return grid > cap ? cap : (grid < 1 ? 1 : grid);
 }
 void launch_collect(hipStream_t s, const BatchInfo& b, const ptd::Queues& qs, ptd::RetireBuf ret, float* image_rgb) {
-  // 96 KB of dynamic LDS: above the 64 KB a kernel gets without asking (per device: set on every launch, it is cheap)
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_collect), hipFuncAttributeMaxDynamicSharedMemorySize, collect_lds_bytes());
-  hipLaunchKernelGGL(k_collect, dim3(qs.Q), dim3(kCollectThreads), collect_lds_bytes(), s, b, qs, ret, image_rgb);
+  // 96 KB of dynamic LDS (and the residues' retiree counts): above the 64 KB a kernel gets without asking (per device: set on every launch, it is cheap)
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_collect), hipFuncAttributeMaxDynamicSharedMemorySize, collect_lds_bytes(ret.wq0));
+  hipLaunchKernelGGL(k_collect, dim3(qs.Q), dim3(kCollectThreads), collect_lds_bytes(ret.wq0), s, b, qs, ret, image_rgb);
 }
 void launch_collect_conv(hipStream_t s, const BatchInfo& b, const ptd::Queues& qs, ptd::RetireBuf ret, float* image_rgb, const ConvInfo& cv, double* sse) {
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_collect_conv), hipFuncAttributeMaxDynamicSharedMemorySize, collect_lds_bytes());
-  hipLaunchKernelGGL(k_collect_conv, dim3(qs.Q), dim3(kCollectThreads), collect_lds_bytes(), s, b, qs, ret, image_rgb, cv);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_collect_conv), hipFuncAttributeMaxDynamicSharedMemorySize, collect_lds_bytes(ret.wq0));
+  hipLaunchKernelGGL(k_collect_conv, dim3(qs.Q), dim3(kCollectThreads), collect_lds_bytes(ret.wq0), s, b, qs, ret, image_rgb, cv);
   if (cv.first_k < b.K) hipLaunchKernelGGL(k_conv_reduce, dim3(b.K - cv.first_k), dim3(kBlock), 0, s, b.iter_first, cv.first_k, qs.Q * kCollectWaves, cv.partial, sse);
 }
 

@@ -11,7 +11,8 @@
 constexpr int kCollectThreads = 1024;
 constexpr int kCollectPPT = 8;                                // pixels (and records) per thread and pass
 constexpr int kCollectPixels = kCollectPPT * kCollectThreads;  // 8192 pixels = 128 chunks: 96 KB of LDS
-__host__ __device__ inline int collect_lds_bytes() { return kCollectPixels * 12; }
+// (+ one int per residue: the sub-regions' depth-0 retiree counts of a BatchInfo::retire_once batch, collect_front_bits)
+__host__ __device__ inline int collect_lds_bytes(int wq0) { return kCollectPixels * 12 + wq0 * 4; }
 // records i0 + t, i0 + t + 1024, ... of a region, eight per thread
 struct CollectChunk {
   ptd::Word4 v[kCollectPPT];
@@ -20,19 +21,37 @@ struct CollectChunk {
 // eight GPUs share a 1080p frame, pays for one record per thread and iteration, not for eight)
 // (FRESH: the record indices are formed anew at every call instead of living in sixteen registers across the iteration loop — the
 // convergence variant needs those for the reference frame)
+// (skip: bit u set — the thread's u-th record is neither loaded nor scattered, c.v[u] keeps whatever it held)
 template <bool FRESH = false>
-PT_DEV void collect_load(const ptd::Word4* rec, int n, int i0, CollectChunk& c) {
+PT_DEV void collect_load(const ptd::Word4* rec, int n, int i0, uint32_t skip, CollectChunk& c) {
   int t = (int)threadIdx.x;
   if constexpr (FRESH) asm volatile("" : "+v"(t));
 #pragma unroll
   for (int u = 0; u < kCollectPPT; ++u) {
     if (u > 0 && i0 + u * kCollectThreads >= n) break;
     const int i = i0 + u * kCollectThreads + t;
-    c.v[u] = rec[i < n ? i : (n > 0 ? n - 1 : 0)];
+    if (!(skip >> u & 1u)) c.v[u] = rec[i < n ? i : (n > 0 ? n - 1 : 0)];
   }
 }
+// BatchInfo::retire_once (pt_sched.h): bit u set — the thread's u-th record of the chunk at i0 lies in a depth-0 retiree slot, the
+// front of its sub-region.  In such a batch the slot holds the same colour for the same pixel in every iteration and is written in
+// iteration 0 only: from iteration 1 on it is skipped and the tile keeps the pixel's value.  front[rho]: retirees of sub-region
+// (q, 0, rho), in LDS; quo, rem: the queue's chunks over the residues (sub_slot).
+PT_DEV uint32_t collect_front_bits(const int* front, int quo, int rem, int n, int i0) {
+  uint32_t bits = 0;
+#pragma unroll 1  // (two divisions per record: one after the other, their temporaries in the same registers)
+  for (int u = 0; u < kCollectPPT; ++u) {
+    if (u > 0 && i0 + u * kCollectThreads >= n) break;
+    const int i = i0 + u * kCollectThreads + (int)threadIdx.x;
+    if (i < n) {
+      const SubSlot s = sub_slot(quo, rem, i);
+      bits |= (retiree_slot(s, front[s.rho]) ? 1u : 0u) << u;
+    }
+  }
+  return bits;
+}
 // (g0, g1: slots of the region that hold no record — the unused tail of the sub-region with the tile's partial last chunk)
-PT_DEV void collect_scatter(const CollectChunk& c, int n, int i0, int g0, int g1, int Q, float inv_q, int first, float* tile) {
+PT_DEV void collect_scatter(const CollectChunk& c, int n, int i0, uint32_t skip, int g0, int g1, int Q, float inv_q, int first, float* tile) {
 #pragma unroll
   for (int u = 0; u < kCollectPPT; ++u) {
     if (u > 0 && i0 + u * kCollectThreads >= n) break;
@@ -41,7 +60,7 @@ PT_DEV void collect_scatter(const CollectChunk& c, int n, int i0, int g0, int g1
     int jj, qq;
     divmod(pl >> 6, Q, inv_q, jj, qq);
     const int li = jj * 64 + (pl & 63) - first;
-    if (i < n && !(i >= g0 && i < g1) && li >= 0 && li < kCollectPixels) tile[3 * li] = c.v[u].x, tile[3 * li + 1] = c.v[u].y, tile[3 * li + 2] = c.v[u].z;
+    if (i < n && !(skip >> u & 1u) && !(i >= g0 && i < g1) && li >= 0 && li < kCollectPixels) tile[3 * li] = c.v[u].x, tile[3 * li + 1] = c.v[u].y, tile[3 * li + 2] = c.v[u].z;
   }
 }
 // Convergence metric (PtOptions.convergence, ConvInfo in pt_kernels.h): after the adds of iteration k a thread holds the SUM image the
@@ -85,7 +104,8 @@ PT_DEV double wave_sum_f64(double v) {
   v += dpp_f64<0x140>(v);  // row_mirror
   return ((readlane_f64(v, 0) + readlane_f64(v, 16)) + readlane_f64(v, 32)) + readlane_f64(v, 48);
 }
-template <bool CONV>
+// (ONCE: a BatchInfo::retire_once batch; a template parameter, so that every other batch runs the gather without the skip tests)
+template <bool CONV, bool ONCE>
 PT_DEV void collect_body(BatchInfo b, ptd::Queues qs, ptd::RetireBuf ret, float* __restrict__ image, ConvInfo cv) {
   extern __shared__ float4 lds_raw[];
   float* tile = reinterpret_cast<float*>(lds_raw);  // [kCollectPixels][3]
@@ -97,10 +117,21 @@ PT_DEV void collect_body(BatchInfo b, ptd::Queues qs, ptd::RetireBuf ret, float*
   // every one filled except the last (64 - N % 64) slots of the sub-region that holds the tile's partial last chunk.
   const int n = b.flat ? sh.my_pixels : sh.my_nq * 64;
   const auto [g0, g1] = b.flat ? Gap{0, 0} : region_gap(sh, ret.wq0);
+  // BatchInfo::retire_once: the depth-0 retiree counts of the queue's sub-regions, row k = 0 of its sub[] (the rows of such a batch
+  // are equal by construction), staged once per block behind the tile
+  constexpr bool once = ONCE;
+  int* front = reinterpret_cast<int*>(tile + 3 * kCollectPixels);  // [wq0]
+  const int quo = once ? sh.my_nq / ret.wq0 : 0, rem = once ? sh.my_nq % ret.wq0 : 0;
+  if (once) {
+    for (int rho = threadIdx.x; rho < ret.wq0; rho += kCollectThreads) front[rho] = (int)(ret.sub[(int64_t)q * ret.kmax * ret.wq0 + rho] >> 32);
+    __syncthreads();
+  }
   for (int first = 0; first < sh.my_nq * 64; first += kCollectPixels) {  // one pass per kCollectPixels of the queue's pixels
     float acc[kCollectPPT][3];
     float rf[CONV ? kCollectPPT : 1][3];  // the reference frame's values of this thread's pixels
-    uint32_t mine_bits = 0;               // bit m: pixel m of this thread exists
+    uint32_t mine_bits = 0;               // bit m: pixel m of this thread exists (CONV); bit 8 + u: its u-th record of a region's first chunk is a
+                                          // depth-0 retiree slot of a retire_once batch — formed once per pass, one register for both
+    if (once) mine_bits = collect_front_bits(front, quo, rem, n, 0) << 8;
     // thread t owns the queue pixels first + t + kCollectThreads * m: chunk jj = index >> 6 is tile chunk q + jj * Q
 #pragma unroll
     for (int m = 0; m < kCollectPPT; ++m) {
@@ -117,14 +148,18 @@ PT_DEV void collect_body(BatchInfo b, ptd::Queues qs, ptd::RetireBuf ret, float*
     // software pipeline: the first 8192 records of iteration k + 1 are in flight while iteration k is summed (the tile is
     // reused every iteration, so the two barriers per iteration stay)
     CollectChunk c;
-    collect_load<CONV>(rec, n, 0, c);
+    // Iteration 0 of a pass loads and scatters the whole region, so every pixel of the window has its value in the tile and nothing
+    // of an earlier pass or batch is used; the later iterations leave out the retiree slots (all of them: nothing is left out
+    // unless retire_once).  acc += tile runs for every pixel in every iteration: the summation order is the same.
+    collect_load<CONV>(rec, n, 0, 0u, c);
     for (int k = 0; k < b.K; ++k) {
-      collect_scatter(c, n, 0, g0, g1, qs.Q, inv_q, first, tile);
+      collect_scatter(c, n, 0, once && k > 0 ? mine_bits >> 8 : 0u, g0, g1, qs.Q, inv_q, first, tile);
       for (int i0 = kCollectPixels; i0 < n; i0 += kCollectPixels) {  // regions longer than one chunk (several passes only)
-        collect_load<CONV>(rec + (int64_t)k * ret.seg_cap, n, i0, c);
-        collect_scatter(c, n, i0, g0, g1, qs.Q, inv_q, first, tile);
+        const uint32_t skip = once && k > 0 ? collect_front_bits(front, quo, rem, n, i0) : 0u;  // (formed afresh: a rare form)
+        collect_load<CONV>(rec + (int64_t)k * ret.seg_cap, n, i0, skip, c);
+        collect_scatter(c, n, i0, skip, g0, g1, qs.Q, inv_q, first, tile);
       }
-      if (k + 1 < b.K) collect_load<CONV>(rec + (int64_t)(k + 1) * ret.seg_cap, n, 0, c);
+      if (k + 1 < b.K) collect_load<CONV>(rec + (int64_t)(k + 1) * ret.seg_cap, n, 0, once ? mine_bits >> 8 : 0u, c);
       __syncthreads();
 #pragma unroll
       for (int m = 0; m < kCollectPPT; ++m) {
@@ -186,11 +221,13 @@ PT_DEV void collect_body(BatchInfo b, ptd::Queues qs, ptd::RetireBuf ret, float*
   for (int i = threadIdx.x; i < ret.kmax; i += kCollectThreads) ret.cnt[(int64_t)q * ret.kmax + i] = 0ull;
 }
 __global__ __launch_bounds__(kCollectThreads) void k_collect(BatchInfo b, ptd::Queues qs, ptd::RetireBuf ret, float* __restrict__ image) {
-  collect_body<false>(b, qs, ret, image, ConvInfo{});
+  if (b.retire_once && !b.flat) collect_body<false, true>(b, qs, ret, image, ConvInfo{});
+  else collect_body<false, false>(b, qs, ret, image, ConvInfo{});
 }
 // the same gather with the convergence metric: 4 waves per SIMD as well, i.e. at most 128 VGPRs
 __global__ __launch_bounds__(kCollectThreads) void k_collect_conv(BatchInfo b, ptd::Queues qs, ptd::RetireBuf ret, float* __restrict__ image, ConvInfo cv) {
-  collect_body<true>(b, qs, ret, image, cv);
+  if (b.retire_once && !b.flat) collect_body<true, true>(b, qs, ret, image, cv);
+  else collect_body<true, false>(b, qs, ret, image, cv);
 }
 // sse[iteration - 1] = the partial sums of iteration iter_first + k, k = first_k + blockIdx.x, in a fixed order: thread t adds
 // elements t, t + 256, ... of the Q * kCollectWaves values, a wave its lanes, thread 0 the four waves.

@@ -178,6 +178,37 @@ PT_SCHED int auto_shared_pieces(int K, int /*nq*/, int /*wq0*/) {
   return sched_max(1, sched_min(want, K));
 }
 
+// ── depth-0 retirees: stored and gathered once per batch ──────────────────────────────────────────────────────────────────
+// A sample that retires at depth 0 of a path with trace_depth >= 2 is a miss or an emitter hit: shade_decide (pt_shade.inc)
+// returns for both before any draw of the iteration's RNG is used, roulette starts at depth 4, and every other hit survives
+// while 1 < trace_depth.  With the same camera ray in every iteration (the shared form) WHETHER a pixel retires at depth 0, and
+// the colour it retires with, are therefore functions of the pixel alone: the K records of a pixel are equal.  Such a batch
+// (BatchInfo::retire_once) writes them in iteration 0 only and k_collect, whose LDS tile is indexed by pixel and survives from
+// iteration to iteration, gathers them there only.  The layout is untouched: slots, counts and RetireBuf::sub stay what
+// they are (so k_paths sees the same buffers); the retiree slots at the front of the sub-regions of iterations >= 1 are
+// simply neither written nor read.  With trace_depth == 1 EVERY sample retires at depth 0, with a colour that depends on the
+// iteration's specular / diffuse draw: the rule is off.  PtOptions.debug_flags kRetireEveryIteration: off as an A/B switch.
+constexpr int kRetireEveryIteration = 1024;
+PT_SCHED bool retires_once(int primary_share, bool aa_jitter, bool flat, int trace_depth, int debug_flags) {
+  return primary_shares(primary_share, aa_jitter, flat) && trace_depth >= 2 && !(debug_flags & kRetireEveryIteration);
+}
+PT_SCHED bool retires_once(const BatchInfo& b, int debug_flags) {
+  return retires_once(b.primary_share, b.aa_jitter != 0, b.flat != 0, b.trace_depth, debug_flags);
+}
+// Slot i of a region (q, k) -> the sub-region (q, k, rho) that holds it and its position there: the inverse of sub_offset /
+// sub_chunks.  Residues below rem own quo + 1 chunks each, the others quo; slots behind the last sub-region
+// (i >= my_nq * 64) do not exist.  (quo = my_nq / wq0, rem = my_nq % wq0)
+struct SubSlot {
+  int rho, pos;
+};
+PT_SCHED SubSlot sub_slot(int quo, int rem, int i) {
+  const int c = i >> 6, big = rem * (quo + 1);  // chunks of the residues that own quo + 1
+  const int rho = c < big ? c / (quo + 1) : rem + (c - big) / sched_max(quo, 1);
+  return SubSlot{rho, i - sub_offset(quo, rem, rho) * 64};
+}
+// Slot i is a depth-0 retiree slot: it lies in the front of its sub-region, among the `retirees` records k_primary puts there.
+PT_SCHED bool retiree_slot(const SubSlot& s, int retirees) { return s.pos < retirees; }
+
 // ── k_paths: falling pieces ───────────────────────────────────────────────────────────────────────────────────────────────
 // BatchInfo::paths_pieces: pieces per wave | fewest paths in a piece << 16.
 PT_SCHED int pack_paths_pieces(int count, int min_piece) { return count | min_piece << 16; }

@@ -102,7 +102,10 @@ typedef struct PtOptions {
                                kernel traces its camera rays in every iteration (default without aa_jitter: once per run of
                                iterations, see primary_share), 256 / 512 force /
                                forbid the uniform-grid walk of the fused kernels (default: for large scenes, whichever of the
-                               BVH scan and up to three grid resolutions renders a few iterations fastest at pt_init), 2048
+                               BVH scan and up to three grid resolutions renders a few iterations fastest at pt_init), 1024
+                               depth-0 retirees stored and gathered in every iteration (default in the shared form with
+                               depth >= 2: a miss or an emitter hit of a camera ray has the same colour in every iteration
+                               and is stored and gathered in iteration 0 of a batch only), 2048
                                keep the reference's leaf boxes for spheres (default for large scenes: tightened to the
                                ellipsoid's box, PtStats.tight_leaves; pt_stage_intersect on such a scene then expects ray
                                origins inside the scene bounds or at the camera).  pt_init fails on any other bit. */
