@@ -194,6 +194,16 @@ def lib() -> C.CDLL:
         L.pt_group_denoise.argtypes = [C.c_void_p, C.c_float, _dno, _fp]
         L.pt_stage_denoise.argtypes = [C.c_int, C.c_int, _fp, _fp, C.c_float, _dno, _fp]
         L.pt_denoise_host.argtypes = [C.c_int, C.c_int, _fp, _fp, C.c_float, _dno, _fp]
+    if hasattr(L, "pt_denoise_guided"):  # absent from older A/B builds of the library (tools/build_rev.sh)
+        _dno = C.POINTER(PtDenoiseOptions)
+        _guided = [C.c_int, C.c_int, _fp, _fp, _fp, C.c_int, C.c_int64, _dno]
+        L.pt_denoise_guided.argtypes = [_dno, _fp]
+        L.pt_ctx_denoise_guided.argtypes = [C.c_void_p, _dno, _fp]
+        L.pt_ctx_denoise_guided_device.argtypes = [C.c_void_p, _dno, C.POINTER(C.c_void_p)]
+        L.pt_group_denoise_guided.argtypes = [C.c_void_p, _dno, _fp]
+        L.pt_stage_denoise_guided.argtypes = _guided + [_fp]
+        L.pt_denoise_guided_host.argtypes = _guided + [_fp]
+        L.pt_denoise_guided_variance_host.argtypes = _guided + [_fp, _fp]
     if hasattr(L, "pt_noise_fold"):  # absent from older A/B builds of the library (tools/build_rev.sh)
         _until = [C.c_int, C.c_int, C.c_int, C.c_float, _ip, _fp]
         L.pt_noise_fold.argtypes = []
@@ -400,6 +410,42 @@ def noise_fold_host(rgb_sum: np.ndarray, planes: np.ndarray, group_iters: int, g
     return float(sse.value)
 
 
+def join_noise(noise: dict) -> np.ndarray:
+    """split_noise's dict (Renderer.readback_noise) back into the planes [PT_NOISE_PLANES, n, 4] the guided filter reads."""
+    n = noise["variance"].shape[0]
+    planes = np.zeros((NOISE_PLANES, n, 4), np.float32)
+    planes[0, :, :3], planes[0, :, 3], planes[1, :, :3] = noise["prev"], noise["variance"], noise["q"]
+    return planes
+
+
+def _denoise_guided_arrays(rgb_sum, planes, noise_planes, w: int, rows: int):
+    s, p, out = _denoise_arrays(rgb_sum, planes, w, rows)
+    z = np.ascontiguousarray(noise_planes, np.float32).reshape(-1)
+    if z.size != 4 * NOISE_PLANES * w * rows:
+        raise PtError(f"denoise_guided: {z.size} noise plane floats for a frame of {w}x{rows}")
+    return s, p, z, out
+
+
+def denoise_guided_host(rgb_sum: np.ndarray, planes: np.ndarray, noise_planes: np.ndarray, w: int, rows: int, groups: int, iters: int,
+                        **opts) -> np.ndarray:
+    """The variance-guided filter on the host (pt_denoise_guided_host; no GPU): denoise_host's arrays, the noise planes
+    [PT_NOISE_PLANES, w*rows, 4] and the counters M, T of the folds that made them.  The device result equals it bit for bit."""
+    s, p, z, out = _denoise_guided_arrays(rgb_sum, planes, noise_planes, w, rows)
+    opt = denoise_options(**opts)
+    _check(lib().pt_denoise_guided_host(int(w), int(rows), _f(s), _f(p), _f(z), int(groups), int(iters), C.byref(opt), _f(out)))
+    return out
+
+
+def denoise_guided_variance_host(rgb_sum: np.ndarray, planes: np.ndarray, noise_planes: np.ndarray, w: int, rows: int, groups: int, iters: int,
+                                 **opts):
+    """The two variances the guided filter's levels start from (pt_denoise_guided_variance_host): (var_raw, var_0), [w*rows] each."""
+    s, p, z, _ = _denoise_guided_arrays(rgb_sum, planes, noise_planes, w, rows)
+    raw, pre = np.empty(w * rows, np.float32), np.empty(w * rows, np.float32)
+    opt = denoise_options(**opts)
+    _check(lib().pt_denoise_guided_variance_host(int(w), int(rows), _f(s), _f(p), _f(z), int(groups), int(iters), C.byref(opt), _f(raw), _f(pre)))
+    return raw, pre
+
+
 def _noise(call, *handle) -> dict:
     sse, groups, iters = C.c_double(-1.0), C.c_int32(0), C.c_int32(0)
     _check(call(*handle, C.byref(sse), C.byref(groups), C.byref(iters)))
@@ -481,6 +527,14 @@ class Renderer:
         out = np.empty((self.n, 3), np.float32)
         opt = denoise_options(**opts)
         _check(lib().pt_denoise(C.c_float(samples), C.byref(opt), _f(out)))
+        return out
+
+    def denoise_guided(self, **opts) -> np.ndarray:
+        """The image filtered by the variance-guided form of the filter (pt_denoise_guided): as denoise, the colour term following
+        the noise estimate.  At least two groups must have been folded and nothing rendered since the last fold."""
+        out = np.empty((self.n, 3), np.float32)
+        opt = denoise_options(**opts)
+        _check(lib().pt_denoise_guided(C.byref(opt), _f(out)))
         return out
 
     # ---- noise estimate from batch sums (include/pt_amd.h: pt_noise_fold) ----
@@ -565,6 +619,15 @@ class Renderer:
         return out
 
     @staticmethod
+    def stage_denoise_guided(rgb_sum: np.ndarray, planes: np.ndarray, noise_planes: np.ndarray, w: int, rows: int, groups: int, iters: int,
+                             **opts) -> np.ndarray:
+        """denoise_guided_host's arguments through the guided filter's kernels (pt_stage_denoise_guided)."""
+        s, p, z, out = _denoise_guided_arrays(rgb_sum, planes, noise_planes, w, rows)
+        opt = denoise_options(**opts)
+        _check(lib().pt_stage_denoise_guided(int(w), int(rows), _f(s), _f(p), _f(z), int(groups), int(iters), C.byref(opt), _f(out)))
+        return out
+
+    @staticmethod
     def stage_shade(depth: int, it, pixel, hit: dict, o, d, color):
         n = o.shape[1]
         o, d, color = (np.ascontiguousarray(a, np.float32).copy() for a in (o, d, color))
@@ -624,6 +687,14 @@ class Group:
         out = np.empty((w * h, 3), np.float32)
         opt = denoise_options(**opts)
         _check(lib().pt_group_denoise(self._h, C.c_float(samples), C.byref(opt), _f(out)))
+        return out
+
+    def denoise_guided(self, **opts) -> np.ndarray:
+        """Renderer.denoise_guided of the whole frame (pt_group_denoise_guided): float32 [W*H, 3], raw orientation."""
+        w, h = self.scene.resolution
+        out = np.empty((w * h, 3), np.float32)
+        opt = denoise_options(**opts)
+        _check(lib().pt_group_denoise_guided(self._h, C.byref(opt), _f(out)))
         return out
 
     def noise_fold(self) -> None:

@@ -645,6 +645,9 @@ int need(const PtContext* c, const char* who) {
 
 }  // namespace
 
+// pt_internal.h (pt_group_denoise_guided: the group refuses what its contexts would refuse, before anything is exchanged)
+int64_t pt_ctx_unfolded_iterations(const PtContext* c) { return c ? c->rendered - c->noise_iters : 0; }
+
 extern "C" {
 
 const char* pt_last_error(void) { return g_err.c_str(); }
@@ -872,6 +875,39 @@ int pt_ctx_denoise(PtContext* c, float samples, const PtDenoiseOptions* opt, flo
   if (!rgb_avg_host) return fail("pt_denoise: null buffer");
   const float* d = nullptr;
   if (pt_ctx_denoise_device(c, samples, opt, &d)) return -1;
+  HIP_OK(hipMemcpyAsync(rgb_avg_host, d, 3 * (size_t)c->N * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  return pt_ctx_sync(c);
+}
+
+// The variance-guided form: the same tile, the same workspace, plus the planes of the noise estimate — which must describe the image
+// as it is, so iterations rendered since the last fold are refused rather than filtered with a stale variance.
+int pt_ctx_denoise_guided_device(PtContext* c, const PtDenoiseOptions* opt, const float** rgb_dev) {
+  if (need(c, "pt_denoise_guided")) return -1;
+  Ctx& g = *c;
+  if (g.failed) return fail("pt_denoise_guided: an earlier batch of this context failed (%s); free it and create a new one", g_err.c_str());
+  const int W = g.cam.resolution[0];
+  if (g.stripe || g.pixel_begin % W || g.N % W)
+    return fail("pt_denoise_guided: the tile must consist of whole contiguous image rows (begin %d, count %d, stripe %d, width %d)", g.pixel_begin, g.N, g.stripe, W);
+  if (!g.d_feat) return fail("pt_denoise_guided: no feature pass has been rendered (pt_render_features)");
+  if (!g.d_noise || g.noise_groups < 1) return fail("pt_denoise_guided: nothing has been folded (pt_noise_fold)");
+  if (g.rendered != g.noise_iters)
+    return fail("pt_denoise_guided: %lld iteration(s) rendered since the last fold; fold first (pt_noise_fold)", (long long)(g.rendered - g.noise_iters));
+  ptdn::Params P{};
+  float Tf = 0.0f, Df = 0.0f;
+  if (pt_denoise_guided_resolve("pt_denoise_guided", g.noise_groups, g.noise_iters, opt, &P, &Tf, &Df)) return -1;
+  HIP_OK(hipSetDevice(g.device));
+  if (!g.d_denoise) {  // first denoise call of the context, of either kind
+    char* ws = nullptr;
+    if (dalloc(g, &ws, pt_denoise_workspace_bytes((size_t)g.N))) return -1;
+    g.d_denoise = ws;
+  }
+  return pt_denoise_guided_launch(g.stream, W, g.N / W, g.d_image, reinterpret_cast<const float*>(g.d_feat), static_cast<const float*>(g.d_noise), Tf, Df, P,
+                                  g.d_denoise, rgb_dev);
+}
+int pt_ctx_denoise_guided(PtContext* c, const PtDenoiseOptions* opt, float* rgb_avg_host) {
+  if (!rgb_avg_host) return fail("pt_denoise_guided: null buffer");
+  const float* d = nullptr;
+  if (pt_ctx_denoise_guided_device(c, opt, &d)) return -1;
   HIP_OK(hipMemcpyAsync(rgb_avg_host, d, 3 * (size_t)c->N * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   return pt_ctx_sync(c);
 }
@@ -1156,6 +1192,7 @@ int pt_clear(void) { return pt_ctx_clear(g_default); }
 int pt_render_features(int iter_first, int iter_count) { return pt_ctx_render_features(g_default, iter_first, iter_count); }
 int pt_readback_features(float* planes_host) { return pt_ctx_readback_features(g_default, planes_host); }
 int pt_denoise(float samples, const PtDenoiseOptions* opt, float* rgb_avg_host) { return pt_ctx_denoise(g_default, samples, opt, rgb_avg_host); }
+int pt_denoise_guided(const PtDenoiseOptions* opt, float* rgb_avg_host) { return pt_ctx_denoise_guided(g_default, opt, rgb_avg_host); }
 int pt_noise_fold(void) { return pt_ctx_noise_fold(g_default); }
 int pt_get_noise(double* sse, int* groups, int* iterations) { return pt_ctx_get_noise(g_default, sse, groups, iterations); }
 int pt_readback_noise(float* planes_host) { return pt_ctx_readback_noise(g_default, planes_host); }
@@ -1352,6 +1389,34 @@ int pt_stage_denoise(int w, int rows, const float* rgb_sum, const float* planes,
   HIP_OK(hipMemcpy(d_planes, planes, 4 * PT_FEATURE_PLANES * n * sizeof(float), hipMemcpyHostToDevice));
   const float* d_out = nullptr;
   if (pt_denoise_launch(g.stream, w, rows, d_img, d_planes, samples, P, d_ws, &d_out)) return -1;
+  HIP_OK(hipStreamSynchronize(g.stream));
+  HIP_OK(hipMemcpy(rgb_avg, d_out, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// The guided filter's kernels on caller-supplied host arrays
+int pt_stage_denoise_guided(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, int groups, int64_t iters,
+                            const PtDenoiseOptions* opt, float* rgb_avg) {
+  if (need(g_default, "pt_stage_denoise_guided")) return -1;
+  Ctx& g = *g_default;
+  if (w <= 0 || rows <= 0 || rows >= 32768 || (int64_t)w * rows > (1ll << 30) || !rgb_sum || !planes || !noise_planes || !rgb_avg)
+    return fail("pt_stage_denoise_guided: bad argument");
+  ptdn::Params P{};
+  float Tf = 0.0f, Df = 0.0f;
+  if (pt_denoise_guided_resolve("pt_stage_denoise_guided", groups, iters, opt, &P, &Tf, &Df)) return -1;
+  HIP_OK(hipSetDevice(g.device));
+  Scratch sc;
+  const size_t n = (size_t)w * rows;
+  float* d_img = sc.get<float>(3 * n);
+  float* d_planes = sc.get<float>(4 * PT_FEATURE_PLANES * n);
+  float* d_noise = sc.get<float>(4 * PT_NOISE_PLANES * n);
+  char* d_ws = sc.get<char>(pt_denoise_workspace_bytes(n));
+  if (!d_img || !d_planes || !d_noise || !d_ws) return fail("pt_stage_denoise_guided: out of device memory");
+  HIP_OK(hipMemcpy(d_img, rgb_sum, 3 * n * sizeof(float), hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(d_planes, planes, 4 * PT_FEATURE_PLANES * n * sizeof(float), hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(d_noise, noise_planes, 4 * PT_NOISE_PLANES * n * sizeof(float), hipMemcpyHostToDevice));
+  const float* d_out = nullptr;
+  if (pt_denoise_guided_launch(g.stream, w, rows, d_img, d_planes, d_noise, Tf, Df, P, d_ws, &d_out)) return -1;
   HIP_OK(hipStreamSynchronize(g.stream));
   HIP_OK(hipMemcpy(rgb_avg, d_out, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
   return 0;

@@ -2,6 +2,8 @@
 //
 // The per-pixel prepare / level / finish bodies below are what the HIP kernels (pt_denoise.hip) and the host loop
 // (denoise_host, exported as pt_denoise_host) both run, so the two cannot disagree; tests/denoise_ref.py restates them in numpy.
+// The variance-guided form (pt_denoise_guided; tests/denoise_guided_ref.py) is the same code with kGuided = true: the colour term is
+// scaled by the centre's variance, which is prepared from the noise planes, prefiltered once and filtered along with the colour.
 // Every float operation is a separate IEEE operation in the order pt_amd.h states (`#pragma clang fp contract(off)` in every body, correctly
 // rounded division, denormals kept), so the result does not depend on the arithmetic mode of the build or on the side it runs on.
 // Plain C++ apart from PT_HD: the system compiler accepts it (a host sanitizer run needs nothing else).
@@ -14,6 +16,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/pt_amd.h"
@@ -37,14 +40,16 @@ struct Params {
 };
 
 // PtDenoiseOptions -> Params (0 = the default in every field, NULL = all defaults); the message of a refusal, or nullptr.
-inline const char* resolve(const PtDenoiseOptions* opt, Params* out) {
+// default_color: sigma_color's default, 4 for pt_denoise, kGuidedSigmaColor for the guided form.
+constexpr float kGuidedSigmaColor = 8.0f;
+inline const char* resolve(const PtDenoiseOptions* opt, Params* out, float default_color = 4.0f) {
 #pragma clang fp contract(off)
   PtDenoiseOptions o{};
   if (opt) o = *opt;
   if (o.levels == 0) o.levels = 5;
   if (o.levels < 1 || o.levels > kMaxLevels) return "levels outside 1 .. 8";
   const float sig[3] = {o.sigma_color, o.sigma_normal, o.sigma_position};
-  const float def[3] = {4.0f, 0.5f, 1.0f};
+  const float def[3] = {default_color, 0.5f, 1.0f};
   float inv[3];
   for (int k = 0; k < 3; ++k) {
     if (!(sig[k] - sig[k] == 0.0f)) return "a sigma is not finite";
@@ -81,6 +86,67 @@ PT_HD void prepare_pixel(size_t i, size_t npix, const float* S, const V4* planes
   n[i] = vn, p[i] = vp, a[i] = va, c[i] = vc;
 }
 
+// guided: the fold's own estimate of one component (pt_noise.h fold_component's last two lines, on the planes it left), demodulated
+// like the colour it belongs to
+PT_HD float guided_variance(float prev, float q, float albedo, float Tf, float Df, int keep_albedo) {
+#pragma clang fp contract(off)
+  const float d = q - (prev * prev) / Tf;
+  const float v = (d > 0.0f ? d : 0.0f) / Df;
+  return !keep_albedo && albedo > 0.0f ? v / (albedo * albedo) : v;
+}
+// guided prepare: prepare_pixel with samples = Tf (its twin, so that the kernel above stays the code it was), and var_raw into the
+// albedo buffer's spare word.  noise: the fold's two planes.
+PT_HD void prepare_pixel_guided(size_t i, size_t npix, const float* S, const V4* planes, const V4* noise, float Tf, float Df, int keep_albedo, V4* n,
+                                V4* p, V4* a, V4* c) {
+#pragma clang fp contract(off)
+  const V4 s0 = planes[i], s1 = planes[npix + i], s2 = planes[2 * npix + i];
+  const bool hit = s1.w > 0.0f;
+  V4 vn{0.0f, 0.0f, 0.0f, hit ? 1.0f : 0.0f}, va{0.0f, 0.0f, 0.0f, 0.0f}, vp{0.0f, 0.0f, 0.0f, 0.0f};
+  if (hit) {
+    vn.x = s0.x / s1.w, vn.y = s0.y / s1.w, vn.z = s0.z / s1.w;
+    va.x = s1.x / s1.w, va.y = s1.y / s1.w, va.z = s1.z / s1.w;
+    vp.x = s2.x / s1.w, vp.y = s2.y / s1.w, vp.z = s2.z / s1.w;
+  }
+  V4 vc{S[3 * i] / Tf, S[3 * i + 1] / Tf, S[3 * i + 2] / Tf, 0.0f};
+  if (!keep_albedo) {
+    vc.x = va.x > 0.0f ? vc.x / va.x : vc.x;
+    vc.y = va.y > 0.0f ? vc.y / va.y : vc.y;
+    vc.z = va.z > 0.0f ? vc.z / va.z : vc.z;
+  }
+  const V4 prev = noise[i], q = noise[npix + i];
+  const float vx = guided_variance(prev.x, q.x, va.x, Tf, Df, keep_albedo);
+  const float vy = guided_variance(prev.y, q.y, va.y, Tf, Df, keep_albedo);
+  const float vz = guided_variance(prev.z, q.z, va.z, Tf, Df, keep_albedo);
+  va.w = (vx + vy) + vz;
+  n[i] = vn, p[i] = vp, a[i] = va, c[i] = vc;
+}
+
+// guided variance prefilter: pixel (x, y); 3 x 3, binomial, over the pixels on the centre's side of hit / miss.  Reads the hit flags
+// and var_raw (a.w), writes var_0 into the spare word of colour buffer 0 (4 bytes each: 24 B per pixel with the eight neighbours in cache).
+PT_HD void var_prefilter_pixel(int W, int R, int x, int y, const V4* n, const V4* a, V4* c0) {
+#pragma clang fp contract(off)
+  constexpr float G[3] = {1.0f / 4.0f, 1.0f / 2.0f, 1.0f / 4.0f};
+  const size_t i0 = (size_t)y * W + x;
+  const float hit = n[i0].w;
+  float acc = 0.0f, gsum = 0.0f;
+#pragma unroll
+  for (int j = -1; j <= 1; ++j) {
+    const int yt = y + j;
+    if (yt < 0 || yt >= R) continue;
+#pragma unroll
+    for (int i = -1; i <= 1; ++i) {
+      const int xt = x + i;
+      if (xt < 0 || xt >= W) continue;
+      const size_t q = (size_t)yt * W + xt;
+      if (n[q].w != hit) continue;
+      const float g = G[j + 1] * G[i + 1];
+      acc = acc + g * a[q].w;
+      gsum = gsum + g;
+    }
+  }
+  c0[i0].w = acc / gsum;
+}
+
 // ── level: one tap against one centre ────────────────────────────────────────────────────────────────────────────────────
 struct Centre {
   V4 c, n, p;  // n.w: the hit flag (1 / 0), or -1: no such pixel (no tap matches it)
@@ -103,6 +169,29 @@ PT_HD void tap(Centre& ce, float h, float cf, const Params& P, const V4& qc, con
   ce.wsum = ce.wsum + w;
 }
 
+// guided: the centre carries its own colour factor (set once from its variance) and the sum of w^2 var(q); qc.w is var_l(q)
+struct CentreGuided : Centre {
+  float cf, vsum;
+};
+template <bool kGuided>
+using CentreOf = typename std::conditional<kGuided, CentreGuided, Centre>::type;
+PT_HD float guided_color_factor(const Params& P, float var) {
+#pragma clang fp contract(off)
+  return P.inv_c / (var + PT_DENOISE_VARIANCE_FLOOR);
+}
+PT_HD void tap_guided(CentreGuided& ce, float h, const Params& P, const V4& qc, const V4& qn, const V4& qp) {
+#pragma clang fp contract(off)
+  if (qn.w != ce.n.w) return;
+  const float dc = dist2(qc, ce.c), dn = dist2(qn, ce.n), dp = dist2(qp, ce.p);
+  const float e = (dc * ce.cf + dn * P.inv_n) + dp * P.inv_p;
+  const float w = h * ptmath::exp32(-e);
+  ce.ax = ce.ax + w * qc.x;
+  ce.ay = ce.ay + w * qc.y;
+  ce.az = ce.az + w * qc.z;
+  ce.wsum = ce.wsum + w;
+  ce.vsum = ce.vsum + (w * w) * qc.w;
+}
+
 // Threads of a level over a frame of R rows: column x, row slot ty < level_slots(R, l); slot ty filters the rows
 // first_row(ty, l) + k * s, k < kRows, that exist.  (Groups of kRows * s rows, one slot per residue of the step.)
 PT_HD int level_slots(int R, int l) {
@@ -111,15 +200,17 @@ PT_HD int level_slots(int R, int l) {
 }
 PT_HD int first_row(int ty, int l) { return (ty >> l) * (kRows << l) + (ty & ((1 << l) - 1)); }
 
-// Level l for the pixels of column x in slot ty: reads c, n, p, writes `out` (the other colour buffer).
-PT_HD void level_column(int W, int R, int x, int ty, int l, const Params& P, const V4* c, const V4* n, const V4* p, V4* out) {
+// Level l for the pixels of column x in slot ty: reads c, n, p, writes `out` (the other colour buffer).  kGuided: c.w is the variance
+// that belongs to c.xyz, and out.w the variance of what is written.
+template <bool kGuided>
+PT_HD void level_column_of(int W, int R, int x, int ty, int l, const Params& P, const V4* c, const V4* n, const V4* p, V4* out) {
 #pragma clang fp contract(off)
   constexpr float H[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
   const int s = 1 << l;
   const int y0 = first_row(ty, l);
   if (y0 >= R) return;  // (a slot of the last, partial group of rows)
-  const float cf = color_factor(P, l);
-  Centre ce[kRows];
+  const float cf = kGuided ? 0.0f : color_factor(P, l);
+  CentreOf<kGuided> ce[kRows];
 #pragma unroll
   for (int k = 0; k < kRows; ++k) {
     const int y = y0 + k * s;
@@ -131,6 +222,7 @@ PT_HD void level_column(int W, int R, int x, int ty, int l, const Params& P, con
       ce[k].c = ce[k].p = V4{0.0f, 0.0f, 0.0f, 0.0f};
       ce[k].n = V4{0.0f, 0.0f, 0.0f, -1.0f};
     }
+    if constexpr (kGuided) ce[k].cf = guided_color_factor(P, ce[k].c.w), ce[k].vsum = 0.0f;
   }
 #pragma unroll
   for (int m = 0; m < kRows + 4; ++m) {  // lattice row m - 2 relative to y0: the tap row j = m - 2 - k of centre k
@@ -145,15 +237,27 @@ PT_HD void level_column(int W, int R, int x, int ty, int l, const Params& P, con
 #pragma unroll
       for (int k = 0; k < kRows; ++k) {
         const int j = m - 2 - k;
-        if (j >= -2 && j <= 2) tap(ce[k], H[j + 2] * H[i + 2], cf, P, qc, qn, qp);
+        if (j >= -2 && j <= 2) {
+          if constexpr (kGuided) tap_guided(ce[k], H[j + 2] * H[i + 2], P, qc, qn, qp);
+          else tap(ce[k], H[j + 2] * H[i + 2], cf, P, qc, qn, qp);
+        }
       }
     }
   }
 #pragma unroll
   for (int k = 0; k < kRows; ++k) {
     const int y = y0 + k * s;
-    if (y < R) out[(size_t)y * W + x] = V4{ce[k].ax / ce[k].wsum, ce[k].ay / ce[k].wsum, ce[k].az / ce[k].wsum, 0.0f};
+    if (y >= R) continue;
+    float var = 0.0f;
+    if constexpr (kGuided) var = ce[k].vsum / (ce[k].wsum * ce[k].wsum);
+    out[(size_t)y * W + x] = V4{ce[k].ax / ce[k].wsum, ce[k].ay / ce[k].wsum, ce[k].az / ce[k].wsum, var};
   }
+}
+PT_HD void level_column(int W, int R, int x, int ty, int l, const Params& P, const V4* c, const V4* n, const V4* p, V4* out) {
+  level_column_of<false>(W, R, x, ty, l, P, c, n, p, out);
+}
+PT_HD void level_column_guided(int W, int R, int x, int ty, int l, const Params& P, const V4* c, const V4* n, const V4* p, V4* out) {
+  level_column_of<true>(W, R, x, ty, l, P, c, n, p, out);
 }
 
 // ── finish: pixel i ──────────────────────────────────────────────────────────────────────────────────────────────────────
@@ -181,6 +285,29 @@ inline void denoise_host(int W, int R, const float* S, const float* planes, floa
   for (int l = 0; l < P.levels; ++l)
     for (int ty = 0; ty < level_slots(R, l); ++ty)
       for (int x = 0; x < W; ++x) level_column(W, R, x, ty, l, P, col[color_buffer(l)], n, p, col[color_buffer(l + 1)]);
+  for (size_t i = 0; i < npix; ++i) finish_pixel(i, P.keep_albedo, col[color_buffer(P.levels)], a, out);
+}
+
+// The guided filter on the host: noise holds the fold's PT_NOISE_PLANES planes, Tf and Df are ptnz::fold_scalars' of the folds so far.
+// var_raw / var_0 (npix floats each, or null) receive the prepared and the prefiltered variance.
+inline void denoise_guided_host(int W, int R, const float* S, const float* planes, const float* noise, float Tf, float Df, const Params& P, float* out,
+                                float* var_raw = nullptr, float* var_0 = nullptr) {
+  const size_t npix = (size_t)W * R;
+  std::vector<V4> ws(kWorkspaceV4 * npix);
+  V4 *n = ws.data(), *p = n + npix, *a = p + npix, *col[2] = {a + npix, a + 2 * npix};
+  std::vector<V4> pl((PT_FEATURE_PLANES + PT_NOISE_PLANES) * npix);
+  for (size_t i = 0; i < PT_FEATURE_PLANES * npix; ++i) pl[i] = V4{planes[4 * i], planes[4 * i + 1], planes[4 * i + 2], planes[4 * i + 3]};
+  V4* nz = pl.data() + PT_FEATURE_PLANES * npix;
+  for (size_t i = 0; i < PT_NOISE_PLANES * npix; ++i) nz[i] = V4{noise[4 * i], noise[4 * i + 1], noise[4 * i + 2], noise[4 * i + 3]};
+  for (size_t i = 0; i < npix; ++i) prepare_pixel_guided(i, npix, S, pl.data(), nz, Tf, Df, P.keep_albedo, n, p, a, col[0]);
+  for (int y = 0; y < R; ++y)
+    for (int x = 0; x < W; ++x) var_prefilter_pixel(W, R, x, y, n, a, col[0]);
+  for (size_t i = 0; i < npix && var_raw; ++i) var_raw[i] = a[i].w;
+  for (size_t i = 0; i < npix && var_0; ++i) var_0[i] = col[0][i].w;
+  if (!out) return;
+  for (int l = 0; l < P.levels; ++l)
+    for (int ty = 0; ty < level_slots(R, l); ++ty)
+      for (int x = 0; x < W; ++x) level_column_guided(W, R, x, ty, l, P, col[color_buffer(l)], n, p, col[color_buffer(l + 1)]);
   for (size_t i = 0; i < npix; ++i) finish_pixel(i, P.keep_albedo, col[color_buffer(P.levels)], a, out);
 }
 

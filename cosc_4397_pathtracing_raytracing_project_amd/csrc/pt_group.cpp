@@ -61,6 +61,7 @@ struct PtGroup {
   uint8_t* d_full_prev = nullptr;
   float* d_recv_feat = nullptr;  // root: one feature plane of the tiles of devices 1..n-1 (16 B per pixel) / the assembled planes
   float* d_full_feat = nullptr;
+  float* d_full_noise = nullptr;  // root: the assembled noise planes (pt_group_denoise_guided; the receive buffer is d_recv_feat)
   void* d_denoise = nullptr;  // root: workspace of pt_group_denoise over the whole frame
 };
 
@@ -80,7 +81,7 @@ void release(PtGroup* g) {
     }
   if (!g->devices.empty()) (void)hipSetDevice(g->devices[0]);
   for (void* p : {(void*)g->d_recv, (void*)g->d_full, (void*)g->d_recv8, (void*)g->d_full8, (void*)g->d_recv_prev,
-                  (void*)g->d_full_prev, (void*)g->d_recv_feat, (void*)g->d_full_feat, g->d_denoise})
+                  (void*)g->d_full_prev, (void*)g->d_recv_feat, (void*)g->d_full_feat, (void*)g->d_full_noise, g->d_denoise})
     if (p) (void)hipFree(p);
   for (size_t i = 0; i < g->d_prev.size(); ++i)
     if (g->d_prev[i]) {
@@ -172,18 +173,26 @@ int need_features(PtGroup* g, const char* who) {
     if (!pt_ctx_device_features(c)) return pt_fail("%s: no feature pass has been rendered (pt_group_render_features)", who);
   return 0;
 }
-int assemble_features(PtGroup* g) {  // -> g->d_full_feat: PT_FEATURE_PLANES planes of W*H float4
+// `count` float4 planes of every context (planes(c): plane 0 of context c, the planes contiguous) -> *full: the planes of the frame
+template <typename PlanesFn>
+int assemble_planes(PtGroup* g, int count, float** full, PlanesFn planes) {
   const size_t frame = (size_t)g->W * g->H;
-  if (!g->d_full_feat) HIP_OK(hipMalloc((void**)&g->d_full_feat, PT_FEATURE_PLANES * frame * 16));
+  if (!*full) HIP_OK(hipMalloc((void**)full, count * frame * 16));
   if (!g->d_recv_feat) HIP_OK(hipMalloc((void**)&g->d_recv_feat, g->recv_pixels * 16));
-  for (int pl = 0; pl < PT_FEATURE_PLANES; ++pl) {  // the root's stream orders plane pl + 1's receives behind plane pl's placement
-    auto tile = [&](int i) { return pt_ctx_device_features(g->ctx[i]) + 4 * (size_t)pl * pt_ctx_pixel_count(g->ctx[i]); };
+  for (int pl = 0; pl < count; ++pl) {  // the root's stream orders plane pl + 1's receives behind plane pl's placement
+    auto tile = [&](int i) { return planes(g->ctx[i]) + 4 * (size_t)pl * pt_ctx_pixel_count(g->ctx[i]); };
     if (exchange(g, ncclFloat, 4, g->d_recv_feat, tile)) return fail_after_drain(g);
     HIP_OK(hipSetDevice(g->devices[0]));
     for (int i = 0; i < g->n; ++i)
-      if (place_rows(g, i, i == 0 ? tile(0) : g->d_recv_feat + 4 * g->recv_off[i], g->d_full_feat + 4 * pl * frame, 16)) return fail_after_drain(g);
+      if (place_rows(g, i, i == 0 ? tile(0) : g->d_recv_feat + 4 * g->recv_off[i], *full + 4 * pl * frame, 16)) return fail_after_drain(g);
   }
   return 0;
+}
+int assemble_features(PtGroup* g) {  // -> g->d_full_feat: PT_FEATURE_PLANES planes of W*H float4
+  return assemble_planes(g, PT_FEATURE_PLANES, &g->d_full_feat, [](PtContext* c) { return pt_ctx_device_features(c); });
+}
+int assemble_noise(PtGroup* g) {  // -> g->d_full_noise: PT_NOISE_PLANES planes of W*H float4
+  return assemble_planes(g, PT_NOISE_PLANES, &g->d_full_noise, [](PtContext* c) { return pt_ctx_device_noise(c); });
 }
 
 }  // namespace
@@ -322,6 +331,36 @@ int pt_group_denoise(PtGroup* g, float samples, const PtDenoiseOptions* opt, flo
   hipStream_t root = (hipStream_t)pt_ctx_stream(g->ctx[0]);
   const float* d_out = nullptr;
   if (pt_denoise_launch(root, g->W, g->H, g->d_full, g->d_full_feat, samples, P, g->d_denoise, &d_out)) return fail_after_drain(g);
+  HIP_OK(hipMemcpyAsync(rgb_avg_host, d_out, frame * 12, hipMemcpyDeviceToHost, root));
+  return pt_group_sync(g);
+}
+
+// pt_denoise_guided of the whole frame: as above, and the noise planes meet on the root like the feature planes.  The filter has ONE
+// M and T, so the contexts must agree on them (and none may hold unfolded iterations: its own call would be refused).
+int pt_group_denoise_guided(PtGroup* g, const PtDenoiseOptions* opt, float* rgb_avg_host) {
+  if (!g || !rgb_avg_host) return pt_fail("pt_group_denoise_guided: bad argument");
+  if (g->n == 1) return pt_ctx_denoise_guided(g->ctx[0], opt, rgb_avg_host);
+  const size_t frame = (size_t)g->W * g->H;
+  if (need_features(g, "pt_group_denoise_guided")) return -1;
+  int groups = 0, iters = 0;
+  for (int i = 0; i < g->n; ++i) {
+    int m = 0, t = 0;
+    if (pt_ctx_get_noise(g->ctx[i], nullptr, &m, &t)) return -1;
+    if (!pt_ctx_device_noise(g->ctx[i]) || m < 1) return pt_fail("pt_group_denoise_guided: nothing has been folded (pt_group_noise_fold)");
+    if (pt_ctx_unfolded_iterations(g->ctx[i]) != 0) return pt_fail("pt_group_denoise_guided: context %d has iterations rendered since its last fold; fold first (pt_group_noise_fold)", i);
+    if (i == 0) groups = m, iters = t;
+    else if (m != groups || t != iters)
+      return pt_fail("pt_group_denoise_guided: context %d folded %d groups of %d iterations, context 0 %d of %d; the contexts of a group share them", i, m, t, groups, iters);
+  }
+  ptdn::Params P{};
+  float Tf = 0.0f, Df = 0.0f;
+  if (pt_denoise_guided_resolve("pt_group_denoise_guided", groups, iters, opt, &P, &Tf, &Df)) return -1;
+  HIP_OK(hipSetDevice(g->devices[0]));
+  if (!g->d_denoise) HIP_OK(hipMalloc(&g->d_denoise, pt_denoise_workspace_bytes(frame)));
+  if (assemble_image(g) || assemble_features(g) || assemble_noise(g)) return -1;
+  hipStream_t root = (hipStream_t)pt_ctx_stream(g->ctx[0]);
+  const float* d_out = nullptr;
+  if (pt_denoise_guided_launch(root, g->W, g->H, g->d_full, g->d_full_feat, g->d_full_noise, Tf, Df, P, g->d_denoise, &d_out)) return fail_after_drain(g);
   HIP_OK(hipMemcpyAsync(rgb_avg_host, d_out, frame * 12, hipMemcpyDeviceToHost, root));
   return pt_group_sync(g);
 }

@@ -7,7 +7,7 @@
 //                       [--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa]
 //                       [--preview N] [--convergence N | --reference FILE.pfm] [--clean-db X] [--features]
 //                       [--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]]
-//                       [--until-db X [--until-group G]]
+//                       [--denoise-guided] [--until-db X [--until-group G]]
 //
 // Without --gpus the run goes through the pathtrace.h-compatible shim (pathtraceInit / pathtrace per
 // iteration / pathtraceFree), i.e. the code path a reference main.cpp would take.  With --gpus K (K >= 1;
@@ -28,6 +28,10 @@
 // the averaged result goes to <base>.denoised.png and, with --pfm, <base>.denoised.pfm.  --denoise-levels N (1 .. 8, default 5),
 // --denoise-sigma C,N,P (colour, normal, position; 0 = the default 4, 0.5, 1; negative = that term off), --denoise-keep-albedo
 // (no demodulation by the first-hit albedo) are PtDenoiseOptions' fields.
+// --denoise-guided (implies --features; excludes --denoise, takes the --denoise-* options, sigma C's default then being 8): the
+// variance-guided form of the filter (pt_denoise_guided / pt_group_denoise_guided), whose colour term follows the per-pixel noise
+// estimate.  It needs at least two folded groups: with --until-db it filters what that render left; without it the --spp iterations
+// (at least 2) are rendered in groups of --until-group G (default ceil(spp / 4)) with a fold after each.  Same output files as --denoise.
 // --until-db X: render until the image's own noise estimate says it is clean (pt_render_until / pt_group_render_until): groups of G
 // iterations (--until-group, default 0 = one batch), a fold after each, until the estimated PSNR is above X dB; --spp becomes the cap.
 // Prints `noise: <iterations> iterations, <groups> groups, estimated PSNR <x> dB`; the file names, --features, --denoise and the
@@ -55,12 +59,12 @@ int main(int argc, char** argv) {
     std::printf("Usage: %s SCENEFILE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] "
                 "[--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa] [--preview N] "
                 "[--convergence N | --reference FILE.pfm] [--clean-db X] [--features] "
-                "[--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]] [--until-db X [--until-group G]]\n", argv[0]);
+                "[--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]] [--denoise-guided] [--until-db X [--until-group G]]\n", argv[0]);
     return 1;
   }
   int rw = 0, rh = 0, spp = 0, depth = 0, gpus = -1, arith = PT_ARITH_EXACT, preview = 0, transport = PT_GROUP_TRANSPORT_AUTO;
   std::vector<int> device_list;
-  bool pfm = false, hdr = false, stamp = false, aa = false, features = false, denoise = false;
+  bool pfm = false, hdr = false, stamp = false, aa = false, features = false, denoise = false, guided = false;
   PtDenoiseOptions dn_opt{};
   int convergence = 0, until_group = 0;
   bool until = false, until_group_given = false;
@@ -106,6 +110,7 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[i], "--stamp")) stamp = true;
     else if (!std::strcmp(argv[i], "--features")) features = true;  // first-hit feature buffers next to the image
     else if (!std::strcmp(argv[i], "--denoise")) denoise = true;    // the filtered image next to the image
+    else if (!std::strcmp(argv[i], "--denoise-guided")) guided = true;  // ... by the variance-guided form of the filter
     else if (!std::strcmp(argv[i], "--denoise-keep-albedo")) dn_opt.keep_albedo = 1;
     else if (!std::strcmp(argv[i], "--denoise-levels") && i + 1 < argc) {
       char* end = nullptr;
@@ -160,13 +165,21 @@ int main(int argc, char** argv) {
     return 1;
   }
   if (!reference.empty()) convergence = -1;
-  if (!denoise && (dn_opt.levels || dn_opt.keep_albedo || dn_opt.sigma_color != 0.0f || dn_opt.sigma_normal != 0.0f || dn_opt.sigma_position != 0.0f)) {
-    std::fprintf(stderr, "--denoise-levels, --denoise-sigma and --denoise-keep-albedo want --denoise\n");
+  if (denoise && guided) {
+    std::fprintf(stderr, "--denoise and --denoise-guided exclude each other (one filtered image)\n");
     return 1;
   }
-  if (denoise) features = true;
-  if (until_group_given && !until) {
-    std::fprintf(stderr, "--until-group wants --until-db\n");
+  if (!denoise && !guided && (dn_opt.levels || dn_opt.keep_albedo || dn_opt.sigma_color != 0.0f || dn_opt.sigma_normal != 0.0f || dn_opt.sigma_position != 0.0f)) {
+    std::fprintf(stderr, "--denoise-levels, --denoise-sigma and --denoise-keep-albedo want --denoise or --denoise-guided\n");
+    return 1;
+  }
+  if (denoise || guided) features = true;
+  if (until_group_given && !until && !guided) {
+    std::fprintf(stderr, "--until-group wants --until-db or --denoise-guided\n");
+    return 1;
+  }
+  if (guided && preview > 0) {
+    std::fprintf(stderr, "--denoise-guided and --preview exclude each other (one loop over the iterations)\n");
     return 1;
   }
   if (until && preview > 0) {
@@ -186,6 +199,12 @@ int main(int argc, char** argv) {
   scene->applyInitialCameraState();
   const int W = scene->state.camera.resolution[0], H = scene->state.camera.resolution[1];
   int iters = (int)scene->state.iterations;  // with --until-db the cap, until the render has said how many it took
+  if (guided && iters < 2) {
+    std::fprintf(stderr, "--denoise-guided wants at least 2 iterations (--spp): a variance needs two groups\n");
+    return 1;
+  }
+  // --denoise-guided without --until-db: the iterations in groups of G (default ceil(spp / 4)), a fold after each
+  const int fold_group = until_group > 0 ? until_group : (iters + 3) / 4;
   if (out.empty()) out = scene->state.imageName;
   std::string base;
   auto name_outputs = [&]() {
@@ -270,6 +289,12 @@ int main(int argc, char** argv) {
         return EXIT_FAILURE;
       }
       report_noise(done, groups, psnr);
+    } else if (guided) {
+      for (int it = 1; it <= iters; it += fold_group)
+        if (pt_render(it, std::min(fold_group, iters - it + 1)) || pt_noise_fold()) {
+          std::fprintf(stderr, "HIP error (pt_noise_fold): %s\n", pt_last_error());
+          return EXIT_FAILURE;
+        }
     } else {
       for (int it = 1; it <= iters; ++it) pathtrace(nullptr, 0, it);  // main.cpp:138-149
     }
@@ -295,6 +320,14 @@ int main(int argc, char** argv) {
       std::vector<float> rgb((size_t)W * H * 3);
       if (pt_denoise((float)iters, &dn_opt, rgb.data())) {
         std::fprintf(stderr, "HIP error (pt_denoise): %s\n", pt_last_error());
+        return EXIT_FAILURE;
+      }
+      save_denoised(rgb);
+    }
+    if (guided) {
+      std::vector<float> rgb((size_t)W * H * 3);
+      if (pt_denoise_guided(&dn_opt, rgb.data())) {
+        std::fprintf(stderr, "HIP error (pt_denoise_guided): %s\n", pt_last_error());
         return EXIT_FAILURE;
       }
       save_denoised(rgb);
@@ -361,6 +394,8 @@ int main(int argc, char** argv) {
       float psnr = -1.0f;
       rc = pt_group_render_until(grp, 1, iters, until_group, until_db, &done, &psnr) || pt_group_get_noise(grp, nullptr, &groups, nullptr);
       if (!rc) report_noise(done, groups, psnr);
+    } else if (guided) {
+      for (int it = 1; it <= iters && !rc; it += fold_group) rc = pt_group_render(grp, it, std::min(fold_group, iters - it + 1)) || pt_group_noise_fold(grp);
     } else {
       rc = pt_group_render(grp, 1, iters);
     }
@@ -396,6 +431,14 @@ int main(int argc, char** argv) {
       std::vector<float> rgb((size_t)W * H * 3);
       if (pt_group_denoise(grp, (float)iters, &dn_opt, rgb.data())) {
         std::fprintf(stderr, "HIP error (pt_group_denoise): %s\n", pt_last_error());
+        return EXIT_FAILURE;
+      }
+      save_denoised(rgb);
+    }
+    if (guided) {
+      std::vector<float> rgb((size_t)W * H * 3);
+      if (pt_group_denoise_guided(grp, &dn_opt, rgb.data())) {
+        std::fprintf(stderr, "HIP error (pt_group_denoise_guided): %s\n", pt_last_error());
         return EXIT_FAILURE;
       }
       save_denoised(rgb);

@@ -413,6 +413,42 @@ int pt_render_until(int iter_first, int max_iters, int group_iters, float target
  * while groups_after < 2.  The device's planes equal it bit for bit. */
 int pt_noise_fold_host(int pixels, const float* rgb_sum, float* planes, int group_iters, int groups_after, int64_t iters_after, double* sse);
 
+/* ---- variance-guided form of the filter above (the step from Dammertz-style a-trous to SVGF-style filtering): the colour term of a
+ * pixel is scaled by that pixel's own variance, taken from the noise estimate, instead of one global sigma_color tightened by 4^l.
+ * Clean pixels keep their detail, noisy ones are smoothed, and the variance is filtered along with the colour, so it shrinks by
+ * itself from level to level.  pt_denoise keeps its specification and its results.  Same rules: float32 throughout, every operation
+ * a separate IEEE operation in the order written, no contraction, correctly rounded division, denormals kept.  Everything not
+ * mentioned is pt_denoise's specification (skipped taps, dn, dp, H, exp32, rows outer and columns inner, finish).
+ * Inputs: S, s0 s1 s2 as above; the noise planes prev.xyz | w and q.xyz | 0; the fold counters M >= 2 and T;
+ * Tf = (float)T, Df = (float)(M - 1) * Tf.  `samples` is no parameter: c = S / Tf.
+ *   prepare  as pt_denoise with samples = Tf, plus per component k:  d = q_k - (prev_k * prev_k) / Tf;  v_k = (d > 0 ? d : 0) / Df
+ *            (the fold's own v_k, bit for bit, when nothing was rendered since the last fold);
+ *            unless keep_albedo: v_k = a_k > 0 ? v_k / (a_k * a_k) : v_k;    var_raw = (v_x + v_y) + v_z
+ *   variance prefilter, once:  var_0(x, y) = (sum g var_raw(q)) / (sum g)  over j = -1 .. 1 (rows, outer), i = -1 .. 1, q = (x + i, y + j),
+ *            g = G[j + 1] * G[i + 1], G = 1/4 1/2 1/4, both sums started at 0 and added to in that order (multiply, then add); a tap is
+ *            skipped when q is outside the rectangle or hit(q) != hit(x, y).  (A batch estimate from M - 1 = 1 .. 3 degrees of freedom
+ *            is too noisy to guide a filter raw.)
+ *   level l  per centre, once:  cf = inv_c / (var_l(x, y) + PT_DENOISE_VARIANCE_FLOOR)   (no 4^l);  vsum = 0
+ *            per tap:  e = (dc * cf + dn * inv_n) + dp * inv_p;  w = h * exp32(-e);  the colour sums as in pt_denoise;
+ *                      vsum = vsum + (w * w) * var_l(q)
+ *            c_l+1 = acc / wsum;   var_l+1 = vsum / (wsum * wsum)
+ * A centre of variance 0 (a miss, an emitter, a pixel whose groups agree) accepts only taps of its own colour: intended.
+ * PtDenoiseOptions is reused; here sigma_color == 0 means 8.0, and sigma_color < 0 switches the colour term off (inv_c = 0, cf = +0):
+ * the result then equals pt_denoise's with the colour term off and samples = T, bit for bit.
+ * Errors with a message, allocating nothing: everything pt_denoise refuses, nothing folded yet, fewer than 2 groups folded, iterations
+ * rendered since the last fold ("fold first": the planes would not belong to the image).  The workspace is pt_denoise's 80 bytes per
+ * pixel, shared with it (var_raw lives in the albedo buffer's spare word, var_l in the colour buffers'); neither the image, the
+ * feature buffers, the noise planes nor any counter changes.  Synchronises. */
+#define PT_DENOISE_VARIANCE_FLOOR 1e-8f
+int pt_denoise_guided(const PtDenoiseOptions* opt, float* rgb_avg_host);
+/* The same on the host (no GPU): pt_denoise_host's arrays, noise_planes PT_NOISE_PLANES * w*rows * 4 floats (pt_readback_noise's
+ * layout), groups = M and iters = T of the folds that made them.  The device result equals it bit for bit. */
+int pt_denoise_guided_host(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, int groups, int64_t iters,
+                           const PtDenoiseOptions* opt, float* rgb_avg);
+/* Host-only, for tests and tuning: the two variances the levels start from, w*rows floats each (either may be NULL). */
+int pt_denoise_guided_variance_host(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, int groups, int64_t iters,
+                                    const PtDenoiseOptions* opt, float* var_raw, float* var_0);
+
 /* saveImage()'s per-pixel conversion (main.cpp:91-97 x mirror, image.cpp:26-30 clamp * 255 truncated) on the
  * device: pixel_count*3 bytes, row-major, x mirrored inside each row; the tile must consist of whole rows.
  * Reads back 3 B per pixel instead of 12. */
@@ -441,6 +477,8 @@ int pt_ctx_readback_features(PtContext* c, float* planes_host);
 int pt_ctx_denoise(PtContext* c, float samples, const PtDenoiseOptions* opt, float* rgb_avg_host);
 /* Asynchronous on the context's stream; *rgb_dev (pixel_count * 3 floats, inside the workspace) stays valid until the next denoise call. */
 int pt_ctx_denoise_device(PtContext* c, float samples, const PtDenoiseOptions* opt, const float** rgb_dev);
+int pt_ctx_denoise_guided(PtContext* c, const PtDenoiseOptions* opt, float* rgb_avg_host);
+int pt_ctx_denoise_guided_device(PtContext* c, const PtDenoiseOptions* opt, const float** rgb_dev); /* as pt_ctx_denoise_device */
 int pt_ctx_noise_fold(PtContext* c);
 int pt_ctx_get_noise(PtContext* c, double* sse, int* groups, int* iterations);
 int pt_ctx_readback_noise(PtContext* c, float* planes_host);
@@ -488,6 +526,10 @@ int pt_group_gather_features(PtGroup* g, float* planes_host);            /* PT_F
  * root device as for the two gathers above, and the filter runs there, on the root's stream, with a workspace of 80 B per frame
  * pixel owned by the group.  Errors as pt_denoise (before a feature pass: an error). */
 int pt_group_denoise(PtGroup* g, float samples, const PtDenoiseOptions* opt, float* rgb_avg_host);
+/* pt_denoise_guided of the whole frame, bit-identical to a single context's: as pt_group_denoise, and the two noise planes of every
+ * context meet on the root like the feature planes (16 B per pixel and plane, either transport; the root's buffers are allocated on
+ * first use).  The contexts of a group share M and T (pt_group_noise_fold keeps them so); a group whose contexts do not is refused. */
+int pt_group_denoise_guided(PtGroup* g, const PtDenoiseOptions* opt, float* rgb_avg_host);
 /* The noise estimate of the whole frame: every context folds its own rows (nothing is exchanged), the contexts' SSE_est are added
  * in context order on the host, and the estimated PSNR is taken over W*H pixels.  pt_group_render_until is pt_render_until with
  * pt_group_render, one synchronise of every device per group; group_iters 0 = the first context's iters_per_batch.  Gathering the
@@ -526,6 +568,9 @@ int pt_stage_save_u8(int w, int h, float samples, const float* rgb_sum, uint8_t*
 
 /* The filter kernels of pt_denoise on caller-supplied host arrays (pt_denoise_host's arguments; rows < 32768). */
 int pt_stage_denoise(int w, int rows, const float* rgb_sum, const float* planes, float samples, const PtDenoiseOptions* opt, float* rgb_avg);
+/* The kernels of pt_denoise_guided on caller-supplied host arrays (pt_denoise_guided_host's arguments; rows < 32768). */
+int pt_stage_denoise_guided(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, int groups, int64_t iters,
+                            const PtDenoiseOptions* opt, float* rgb_avg);
 
 /* ---- image output (src/image.cpp:22-45, src/main.cpp:86-107) ------------- */
 /* rgb_sum: W*H*3 floats (raw orientation); writes <path> as 8-bit PNG of
