@@ -31,7 +31,7 @@
 namespace {
 
 std::string g_err;
-constexpr int kDebugFlags = 16 | 32 | 64 | 128 | 256 | 512 | ptk::kRetireEveryIteration | 2048;  // the PtOptions.debug_flags bits pt_init accepts
+constexpr int kDebugFlags = 16 | 32 | 64 | 128 | 256 | 512 | ptk::kRetireEveryIteration | 2048 | ptk::kWholeRecords;  // the PtOptions.debug_flags bits pt_init accepts
 static_assert(sizeof(PtOptions) == 80, "capi.PtOptions mirrors this layout");
 static_assert(PT_CONVERGENCE_WAVES == ptk::kConvWaves, "pt_amd.h documents the size of the convergence metric's partial sums");
 }  // namespace
@@ -211,10 +211,11 @@ ptk::SceneTables tables(const Ctx& g) {
   return t;
 }
 
+size_t pathbuf_words(int64_t stride) { return (size_t)(2 * stride + (stride * ptd::kPathPlane2Bytes + 15) / 16); }
 int alloc_pathbuf(Ctx& g, ptd::PathBuf* b, int64_t stride) {
   b->stride = stride;
   // planes 0 and 1: 16 bytes per path, plane 2: kPathPlane2Bytes (pt_device.h); allocated in 16-byte words
-  return dalloc(g, &b->r, 2 * stride + (stride * ptd::kPathPlane2Bytes + 15) / 16);
+  return dalloc(g, &b->r, pathbuf_words(stride));
 }
 int alloc_hitbuf(Ctx& g, ptd::HitBuf* h, int64_t stride) {
   h->stride = stride;
@@ -253,6 +254,7 @@ int run_batch(Ctx& g, int iter_first, int kb) {
                      : ptk::primary_shares(b) ? ptk::auto_shared_pieces(kb, g.qs.nq, g.ret.wq0) : ptk::auto_primary_pieces(kb, g.qs.nq, g.ret.wq0);
   b.paths_pieces = g.paths_pieces;
   b.retire_once = ptk::retires_once(b, g.debug_flags) ? 1 : 0;  // (every batch of the context, the timing batches of choose_traversal among them)
+  b.split_records = ptk::splits_records(b, g.debug_flags) ? 1 : 0;  // (likewise; the unfused kernels' batches are flat: whole records)
   b.stripe = g.stripe;
   b.gap = g.stripe ? g.stripe_stride - g.stripe : 0;
   b.inv_stripe = g.stripe ? 1.0f / (float)g.stripe : 0.0f;
@@ -583,6 +585,10 @@ __global__ void k_poison_records(ptd::Word4* rec, unsigned long long per_queue, 
 int alloc_batch_buffers(Ctx& g) {
   const int Q = g.qs.Q;
   if (alloc_pathbuf(g, &g.buf[0], g.stride) || alloc_pathbuf(g, &g.buf[1], g.stride)) return -1;
+  // In a BatchInfo::split_records batch the invariant half of a depth-1 record is written by ONE run of k_primary and read in every
+  // iteration; a later batch finds an older batch's identical words there.  So the path buffers start as NaN (all bits set) in every
+  // word, like the retirement records below: a slot nobody wrote in this batch then shows in the first batch of a context.
+  for (const ptd::PathBuf& pb : g.buf) HIP_OK(hipMemset(pb.r, 0xff, pathbuf_words(pb.stride) * sizeof(ptd::Word4)));
   if (!g.fuse_bounces && alloc_hitbuf(g, &g.hits, g.stride)) return -1;  // hit records reach HBM only in the unfused form
   {
     const size_t regions = (size_t)Q * g.ret.kmax;

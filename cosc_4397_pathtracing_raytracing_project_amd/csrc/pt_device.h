@@ -81,6 +81,8 @@ struct Camera {
 //   plane 1   direction.yz, colour.xy
 //   plane 2   colour.z | sample id inside the batch: k << slot_shift | tile pixel (BatchInfo::slot_shift), 8 B per path
 // 40 B per path, the algorithmic minimum of SURVEY §8(d) (+ 0: the id replaces the reference's pixelIndex).
+// A batch that splits its records (BatchInfo::split_records, pt_sched.h) keeps (direction.xyz, sample id | specular bit << 31) in plane 0 and,
+// at the path's slot of ITERATION 0, (origin.xyz, material index) in plane 1, written once per batch; plane 2 is not touched.
 struct alignas(16) Word4 {
   float x, y, z, w;
 };

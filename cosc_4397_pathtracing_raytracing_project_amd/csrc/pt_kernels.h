@@ -84,6 +84,8 @@ struct BatchInfo {
                            // come, first served (counters behind ptd::Queues::deal); <= 1: one piece per wave; high 16 bits: fewest paths in a piece
   int32_t retire_once;     // 1 (the host sets it from pt_sched.h retires_once): a sample that retires at depth 0 does so in every iteration, with the
                            // same colour — k_primary stores its record in iteration 0 of the batch only, k_collect gathers it there only
+  int32_t split_records;   // 1 (the host sets it from pt_sched.h splits_records): a depth-1 record's origin and material index are stored once per
+                           // batch, in plane 1 at the slot of iteration 0; plane 0 holds direction, sample id and the specular / diffuse bit
 };
 
 // Convergence metric of the gather (PtOptions.convergence; k_collect_conv in pt_output.inc).  Iteration iter_first + k of a batch gets

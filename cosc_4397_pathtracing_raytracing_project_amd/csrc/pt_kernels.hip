@@ -1046,6 +1046,13 @@ PT_DEV void carry_drain_to(Carry<SMALL, NPAR>& c, int mark, int lane, const ptd:
 }
 
 #include "pt_grid.inc"
+// Waves per SIMD a k_primary instance is compiled for.  Two shared instances end at 72 VGPRs — seven waves, which the persistent
+// grid of a scene with little LDS per block uses — by the allocator's choice, not by the bound; their SPLIT forms came out at 74
+// under the same bound and are asked for the seven outright (72 VGPRs, no scratch; exact / kTopScan would spill, and has six either way).
+template <Search F, bool SPLIT>
+constexpr int primary_waves() {
+  return SPLIT && ((PT_ARITH == 2 && F == kTopScan) || (PT_ARITH == 0 && F == kLdsTables)) ? 7 : kPrimaryWaves;
+}
 // ── depth 0 fused: generateRayFromCamera + computeIntersections + shadeAndExtendRays ────────
 // Primary rays are a pure function of the sample id, so depth 0 needs no path state in memory at
 // all: the ray is built in registers, traced with the same wave-cooperative search, shaded, and
@@ -1069,8 +1076,11 @@ PT_DEV void carry_drain_to(Carry<SMALL, NPAR>& c, int mark, int lane, const ptd:
 // rays, the flat lists and as the A/B switch PtOptions.debug_flags 128).  The search sits above the shading in all three forms.
 // BatchInfo::retire_once (pt_sched.h): the records of the lanes that retire here — the same lanes with the same colour in every
 // iteration — are stored in iteration 0 of the batch only, and a group that holds nothing else skips the iteration loop.
-template <Search F, bool SHARE = false>
-__global__ __launch_bounds__(kBlock, kPrimaryWaves) void k_primary(SceneTables sc, ptd::Camera cam, BatchInfo b, ptd::Queues qs,
+// SPLIT (BatchInfo::split_records, shared form only; pt_sched.h): a survivor's record is the 16-byte per-iteration word (direction,
+// sample id | specular bit) in plane 0 and, from the run that holds iteration 0 of the batch only, the 16-byte invariant word
+// (origin, material index) in plane 1 at the slot of iteration 0; its throughput is not stored at all.
+template <Search F, bool SHARE = false, bool SPLIT = false>
+__global__ __launch_bounds__(kBlock, (primary_waves<F, SPLIT>())) void k_primary(SceneTables sc, ptd::Camera cam, BatchInfo b, ptd::Queues qs,
                                                     int32_t* __restrict__ cnt0, int32_t* __restrict__ cnt_out,
                                                     ptd::PathBuf out, ptd::RetireBuf ret) {
   extern __shared__ float4 lds_raw[];
@@ -1227,6 +1237,17 @@ __global__ __launch_bounds__(kBlock, kPrimaryWaves) void k_primary(SceneTables s
             hp = mk(rec[3 * 64], rec[4 * 64], rec[5 * 64]);
             if (GRID) hn = Ar<kD0>::finish_normal(G, hn);
           }
+          if constexpr (SPLIT) {
+            // BatchInfo::split_records (pt_sched.h): the lanes that survive — every hit but an emitter's, in every iteration — get their
+            // invariant word (shade_bounce's origin, the material) from the run that holds iteration 0 of the batch, at the slot their
+            // records have in that iteration (invariant_slot of every other iteration's).
+            if (s0 == 0) {
+              const bool lives = valid && !(ht < 0.0f || mats[hmat].emittance > 0.0f);
+              const unsigned long long livem = ballot(lives);
+              const f3 o1 = bounce_origin(hn, hp);
+              if (lives) out.r[out.stride + qbase + sub_off + __builtin_amdgcn_readlane(vnl, 0) + rank_in(livem)] = ptd::Word4{o1.x, o1.y, o1.z, __int_as_float(hmat)};
+            }
+          }
           // BatchInfo::retire_once (pt_sched.h): a miss or an emitter hit retires here in every iteration with the same colour — the
           // tests are shade_decide's own, which returns for both before it uses a draw — and every other hit survives.  Those lanes'
           // records are written in iteration 0 of the batch only, to the slots they have always had; vnd still advances in every
@@ -1265,7 +1286,9 @@ __global__ __launch_bounds__(kBlock, kPrimaryWaves) void k_primary(SceneTables s
             const int nl = __builtin_amdgcn_readlane(vnl, k - s0), nd = __builtin_amdgcn_readlane(vnd, k - s0);
             const int sub0 = k * rt.seg_cap + sub_off;  // first slot of sub-list / sub-region (q, k, r)
             const PathTag tag{make_slot(b, k, pl), phash, k};
-            if (alive) path_store(out, qbase + sub0 + nl + rank_in(live), s.o, s.d, s.c, tag);
+            if constexpr (SPLIT) {
+              if (alive) out.r[qbase + sub0 + nl + rank_in(live)] = ptd::Word4{s.d.x, s.d.y, s.d.z, __uint_as_float(pack_kind(tag.slot, bo.kind == 1))};
+            } else if (alive) path_store(out, qbase + sub0 + nl + rank_in(live), s.o, s.d, s.c, tag);
             if (dead && !once) rt.rec[sub0 + nd + rank_in(deadm)] = ptd::Word4{s.c.x, s.c.y, s.c.z, __int_as_float(pl)};
             if (lane == k - s0) vnl += (int)__popcll(live), vnd += (int)__popcll(deadm);
           }
@@ -1425,6 +1448,24 @@ PT_DEV void fetch_record_to_lds(const void* b0, const void* b1, const void* b2, 
       : [base] "s"(lds_base), [b0] "s"(b0), [b1] "s"(b1), [b2] "s"(b2), [o16] "v"(off16), [o8] "v"(off8)
       : "memory", "scc");
 }
+// A split record (BatchInfo::split_records, pt_sched.h): the per-iteration word of path slot i from plane 0 and the invariant word
+// of slot i0 from plane 1, to the same two 16-byte slot planes; the slot's 4-byte tail stays unused.
+PT_DEV void fetch_split_to_lds(const void* b0, const void* b1, int i, int i0, uint32_t lds_base) {
+  uint32_t keep;
+  const uint32_t off = (uint32_t)i << 4, off0 = (uint32_t)i0 << 4;
+  asm volatile(
+      "s_mov_b32 %[keep], m0\n\t"
+      "s_mov_b32 m0, %[base]\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dwordx4 %[o], %[b0]\n\t"
+      "s_add_u32 m0, m0, 0x400\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dwordx4 %[o0], %[b1]\n\t"
+      "s_mov_b32 m0, %[keep]"
+      : [keep] "=&s"(keep)
+      : [base] "s"(lds_base), [b0] "s"(b0), [b1] "s"(b1), [o] "v"(off), [o0] "v"(off0)
+      : "memory", "scc");
+}
 // Per-wave LDS of k_paths: closest-hit keys, winner records, the candidate ring (16-bit entries: top entry << 6 | owner lane;
 // the chunk looks leaf and geom index up in tword[top entry] = leaf | geom << 8, so it does not go through nodes[leaf]) and the
 // running totals.  The rays are NOT kept in LDS: the lanes are persistent, a chunk fetches a candidate's ray from its owner's
@@ -1534,7 +1575,10 @@ constexpr int kPathsScanWaves = 5, kPathsGridWaves = 5;
 constexpr int kVisitLap = 32, kVisitsPerRefill = 31;
 static_assert(kVisitLap + kVisitsPerRefill + 1 <= kVisitRing, "the visit ring laps a path in flight");
 static_assert((kVisitRing & (kVisitRing - 1)) == 0, "visit numbers wrap with a mask");
-template <Search MODE>
+// SPLIT (BatchInfo::split_records, pt_sched.h): a path's record is the per-iteration word (direction, sample id | specular bit) at its
+// own slot of plane 0 and the invariant word (origin, material index) at the same slot of ITERATION 0 in plane 1 — the cursor
+// keeps both bases — and its throughput is (1, 1, 1) times the material's spec or color, formed when the lane takes the path.
+template <Search MODE, bool SPLIT = false>
 __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPathsScanWaves : kPathsGridWaves) void k_paths(SceneTables sc, BatchInfo b, ptd::Queues qs, int32_t* __restrict__ cnt /* [depth][Q] rows */,
                                                                ptd::PathBuf in, ptd::RetireBuf ret) {
   extern __shared__ float4 lds_raw[];
@@ -1633,6 +1677,7 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
   // ps0 = total / (wq P), P = paths_pieces, so that the levels add up to the queue — large pieces while everybody is busy, small
   // ones at the end, where a launch waits for the last piece (pieces of one size left half a piece of idle time per wave).
   const PiecePlan pieces = piece_plan(total, wq, b.paths_pieces, qs.deal != nullptr, chunk_sums);
+  [[maybe_unused]] int clist0 = 0;  // SPLIT: clist without its iteration's k * seg_cap — where the sub-list of iteration 0 starts
   int ce = ne, cstart = total, ccnt = 0, clist = 0;  // cursor (wave-uniform): sub-list e = k * wq0 + rho; nothing to stream leaves it at the end
   int cord = 0;  // sub-list visits of the cursor so far
   // A window of 64 consecutive sub[] words in registers (lane l holds sub[win0 + l]): the cursor reads counts and retiree numbers
@@ -1660,6 +1705,7 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
   auto cursor_bases = [&](int first_rank) {
     const int ec = min(ce, ne - 1), ck = ec / wq0, crho = ec - ck * wq0;  // (wave-uniform: scalar instructions)
     clist = ck * rt.seg_cap + sub_offset(quo, rem, crho) * 64;
+    if constexpr (SPLIT) clist0 = invariant_slot(clist, ck, rt.seg_cap);
     window_to(ec);
     const int crec = clist + (int)(uint32_t)(sub_word(ec) >> 32);
     if (lane == 0) fillc[cord & (kVisitRing - 1)] = crec + (first_rank - cstart);  // where this wave's first record of the visit goes
@@ -1694,13 +1740,15 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
   // Path index (inside the queue's region) of the rays of global rank `rank`, for the lanes that `want` one (consecutive ranks in
   // lane order), and the visit their retirement records are counted under.  Ranks only grow inside a piece, so the cursor only
   // moves forward; it stops after kVisitsPerRefill new visits (sub-lists of a path or two: tiles of a few pixels per wave) — the lanes behind
-  // that are served by a later refill.  Returns whether the lane was served.  Wave-uniform control flow.
-  auto assign = [&](bool want, int rank, int& at, int& rs) -> bool {
+  // that are served by a later refill.  Returns whether the lane was served.  Wave-uniform control flow.  (at0, SPLIT: the same index in iteration 0)
+  auto assign = [&](bool want, int rank, int& at, [[maybe_unused]] int& at0, int& rs) -> bool {
     bool pending = want;
     const int cord0 = cord;
     while (true) {
       const bool in = pending && rank < cstart + ccnt;
       if (in) at = clist + (rank - cstart), rs = cord;
+      if constexpr (SPLIT)
+        if (in) at0 = clist0 + (rank - cstart);
       pending = pending && !in;
       if (!ballot(pending) || ce >= ne || cord - cord0 >= kVisitsPerRefill) break;
       cstart += ccnt;  // on to the next sub-list that holds anything: the first non-empty one behind ce in the window, else the window moves on
@@ -1731,9 +1779,13 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
   nx.o = nx.d = nx.c = mk(0.f, 0.f, 0.f), nx.tag = PathTag{0, 0u, 0};
   int nx_rs = 0;  // !SLOTS: ... and its visit
   int* slot_rs = reinterpret_cast<int*>(slots + kSlotVisit) + lane;  // SLOTS: the visit of the record waiting in the lane's slot
-  auto fetch = [&](int at, int rs) {
-    if constexpr (SLOTS) fetch_record_to_lds(in0, in1, in2, at, s_base), *slot_rs = rs;
-    else nx = path_load(in, qbase + at), nx_rs = rs;
+  auto fetch = [&](int at, [[maybe_unused]] int at0, int rs) {
+    if constexpr (SLOTS && SPLIT) fetch_split_to_lds(in0, in1, at, at0, s_base), *slot_rs = rs;
+    else if constexpr (SLOTS) fetch_record_to_lds(in0, in1, in2, at, s_base), *slot_rs = rs;
+    else if constexpr (SPLIT) {  // the two words as they lie in memory: unpacked when the lane takes them
+      const ptd::Word4 w0 = in.r[qbase + at], w1 = in.r[in.stride + qbase + at0];
+      nx.o = mk(w0.x, w0.y, w0.z), nx.d = mk(w0.w, w1.x, w1.y), nx.c = mk(w1.z, w1.w, 0.f), nx_rs = rs;
+    } else nx = path_load(in, qbase + at), nx_rs = rs;
   };
   // lane state
   f3 o = mk(0.f, 0.f, 0.f), d = o, c = o;
@@ -1766,7 +1818,18 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
       v4f w0, w1;
       float cz;
       int nslot, nrs;
-      if constexpr (SLOTS) {
+      if constexpr (SLOTS && SPLIT) {
+        asm volatile(
+            "s_waitcnt vmcnt(0)\n\t"
+            "ds_read_b128 %0, %3\n\t"
+            "ds_read_b128 %1, %3 offset:1024\n\t"
+            "ds_read_b32 %2, %4 offset:512\n\t"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&v"(w0), "=&v"(w1), "=&v"(nrs)
+            : "v"(s16), "v"(s4)
+            : "memory");
+        cz = 0.f, nslot = 0;
+      } else if constexpr (SLOTS) {
         // everything outstanding here (last refill's transfers, last refill's retirement stores) is a whole iteration old
         asm volatile(
             "s_waitcnt vmcnt(0)\n\t"
@@ -1786,8 +1849,16 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
         rt.rec[rslot] = ptd::Word4{c.x, c.y, c.z, __int_as_float(slot & ((1 << b.slot_shift) - 1))};
         owes = false;
       }
+      if constexpr (SPLIT) {  // (per-iteration word, invariant word)
+        if (take) {
+          const uint32_t word = __float_as_uint(w0.w);
+          const ptd::Mat* m = mats + __float_as_int(w1.w);
+          nslot = kind_sample_id(word);
+          o = mk(w1.x, w1.y, w1.z), d = mk(w0.x, w0.y, w0.z);
+          c = mul(mk(1.0f, 1.0f, 1.0f), kind_specular(word) ? mk(m->spec[0], m->spec[1], m->spec[2]) : mk(m->color[0], m->color[1], m->color[2]));
+        }
+      } else if (take) o = mk(w0.x, w0.y, w0.z), d = mk(w0.w, w1.x, w1.y), c = mk(w1.z, w1.w, cz);
       if (take) {
-        o = mk(w0.x, w0.y, w0.z), d = mk(w0.w, w1.x, w1.y), c = mk(w1.z, w1.w, cz);
         slot = nslot, rslot = nrs;
         phash = utilhash((uint32_t)global_pixel(b, nslot & ((1 << b.slot_shift) - 1)));
         depth = 1;
@@ -1801,11 +1872,11 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
       const unsigned long long em = ballot(empty);
       const int rank = rank_in(em);
       const bool more = empty && streamed + rank < p_hi;
-      int at = 0, rs = 0;
-      const bool served = assign(more, streamed + rank, at, rs);
+      int at = 0, at0 = 0, rs = 0;
+      const bool served = assign(more, streamed + rank, at, at0, rs);
       if (served) {
         has_next = true;
-        fetch(at, rs);
+        fetch(at, at0, rs);
       }
       streamed += (int)__popcll(ballot(served));
     }

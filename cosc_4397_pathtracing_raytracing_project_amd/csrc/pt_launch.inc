@@ -25,27 +25,34 @@ void with_features(const SceneTables& sc, F&& f) {
   if (leaves_fit_top(sc)) return f(k_features<false, false>, intersect_lds<false>(sc).total);
   return f(k_features<false, true>, intersect_lds<false>(sc).total);
 }
-// share: the shared loop form (one trace per chunk and run of iterations, pt_sched.h) — both forms use the same LDS map
+// share: the shared loop form (one trace per chunk and run of iterations, pt_sched.h) — both forms use the same LDS map;
+// split (shared form only): BatchInfo::split_records
+template <Search S, typename F>
+void with_primary_of(const SceneTables& sc, bool share, bool split, F&& f) {
+  const int lds = primary_lds<S, kFast, kD0>(sc).total;
+  return !share ? f(k_primary<S>, lds) : split ? f(k_primary<S, true, true>, lds) : f(k_primary<S, true>, lds);
+}
 template <typename F>
-void with_primary(const SceneTables& sc, bool share, F&& f) {
+void with_primary(const SceneTables& sc, bool share, bool split, F&& f) {
   switch (search_form(sc)) {
-    case kLdsTables: return share ? f(k_primary<kLdsTables, true>, primary_lds<kLdsTables, kFast, kD0>(sc).total) : f(k_primary<kLdsTables>, primary_lds<kLdsTables, kFast, kD0>(sc).total);
-    case kTopScan: return share ? f(k_primary<kTopScan, true>, primary_lds<kTopScan, kFast, kD0>(sc).total) : f(k_primary<kTopScan>, primary_lds<kTopScan, kFast, kD0>(sc).total);
-    case kGrid: return share ? f(k_primary<kGrid, true>, primary_lds<kGrid, kFast, kD0>(sc).total) : f(k_primary<kGrid>, primary_lds<kGrid, kFast, kD0>(sc).total);
+    case kLdsTables: return with_primary_of<kLdsTables>(sc, share, split, f);
+    case kTopScan: return with_primary_of<kTopScan>(sc, share, split, f);
+    case kGrid: return with_primary_of<kGrid>(sc, share, split, f);
   }
 }
 
+// split: BatchInfo::split_records — the same LDS map
 template <typename F>
-void with_paths(const SceneTables& sc, Search form, F&& f) {  // (SceneTables::scan_nodes_lds resolved by the caller)
+void with_paths(const SceneTables& sc, Search form, bool split, F&& f) {  // (SceneTables::scan_nodes_lds resolved by the caller)
   switch (form) {
-    case kLdsTables: return f(k_paths<kLdsTables>, paths_lds<kLdsTables, kFast>(sc).total);
-    case kTopScan: return f(k_paths<kTopScan>, paths_lds<kTopScan, kFast>(sc).total);
-    case kGrid: return f(k_paths<kGrid>, paths_lds<kGrid, kFast>(sc).total);
+    case kLdsTables: return split ? f(k_paths<kLdsTables, true>, paths_lds<kLdsTables, kFast>(sc).total) : f(k_paths<kLdsTables>, paths_lds<kLdsTables, kFast>(sc).total);
+    case kTopScan: return split ? f(k_paths<kTopScan, true>, paths_lds<kTopScan, kFast>(sc).total) : f(k_paths<kTopScan>, paths_lds<kTopScan, kFast>(sc).total);
+    case kGrid: return split ? f(k_paths<kGrid, true>, paths_lds<kGrid, kFast>(sc).total) : f(k_paths<kGrid>, paths_lds<kGrid, kFast>(sc).total);
   }
 }
 int paths_lds_bytes(const SceneTables& sc, Search form) {
   int bytes = 0;
-  with_paths(sc, form, [&](auto, int lds) { bytes = lds; });
+  with_paths(sc, form, false, [&](auto, int lds) { bytes = lds; });
   return bytes;
 }
 int lds_share_limit(int bytes);
@@ -88,9 +95,9 @@ int lds_table_limit(const SceneTables& sc, int forced_bytes) {
   if (tbl <= kLdsTableBytes && leaves_fit_top(sc)) {
     SceneTables in = sc;
     in.lds_table_bytes = tbl;
-    with_paths(in, kLdsTables, occupancy_into(with, 0));
+    with_paths(in, kLdsTables, false, occupancy_into(with, 0));
   }
-  with_paths(sc, kTopScan, occupancy_into(without, 1));
+  with_paths(sc, kTopScan, false, occupancy_into(without, 1));
   (void)hipGetLastError();
   return (with >= without && with > 0) ? tbl : -1;
 }
@@ -101,16 +108,17 @@ int lds_table_limit(const SceneTables& sc, int forced_bytes) {
 constexpr int kLdsGranule = 1280;
 int lds_share_limit(int bytes) { return bytes > 0 ? (160 * 1024) / (((bytes + kLdsGranule - 1) / kLdsGranule) * kLdsGranule) : 8; }
 int resident_blocks_per_cu(KernelId id, const SceneTables& sc) {
-  int n = 0, lds = 0;  // lds: the fused kernels' blocks are also held to their granule share of the CU's LDS
+  int n = 0, m = 0, lds = 0;  // lds: the fused kernels' blocks are also held to their granule share of the CU's LDS
   const auto query = occupancy_into(n, 1);
   const auto query_share = [&](auto kernel, int bytes) { query(kernel, bytes), lds = bytes; };
   switch (id) {
     case kGenerate: query(k_generate, 0); break;
     case kIntersect: with_intersect(sc, false, false, query); break;
     case kIntersectLegacy: with_intersect(sc, true, false, query); break;
-    case kPrimary: with_primary(sc, false, query_share); break;
-    case kPrimaryShared: with_primary(sc, true, query_share); break;
-    case kPaths: with_paths(resolve_scan_nodes(sc), search_form(sc), query_share); break;
+    case kPrimary: with_primary(sc, false, false, query_share); break;
+    // (a context's batches run either record form of these two, BatchInfo::split_records: same launch bounds and LDS; the smaller count serves both)
+    case kPrimaryShared: with_primary(sc, true, false, query_share), m = n, with_primary(sc, true, true, query_share), n = min(n, m); break;
+    case kPaths: with_paths(resolve_scan_nodes(sc), search_form(sc), false, query_share), m = n, with_paths(resolve_scan_nodes(sc), search_form(sc), true, query_share), n = min(n, m); break;
     case kShade: query(k_shade, shade_lds<true>(sc).total); break;
     case kFeatures: with_features(sc, query); break;
   }
@@ -131,7 +139,7 @@ void launch_intersect(hipStream_t s, int grid, const SceneTables& sc, const ptd:
 
 void launch_primary(hipStream_t s, int grid, const SceneTables& sc, const ptd::Camera& cam, const BatchInfo& b,
                     const ptd::Queues& qs, int32_t* cnt0, int32_t* cnt_out, ptd::PathBuf out, ptd::RetireBuf ret) {
-  with_primary(sc, primary_shares(b), [&](auto kernel, int lds) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, sc, cam, b, qs, cnt0, cnt_out, out, ret); });
+  with_primary(sc, primary_shares(b), primary_shares(b) && b.split_records != 0, [&](auto kernel, int lds) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, sc, cam, b, qs, cnt0, cnt_out, out, ret); });
 }
 
 void launch_features(hipStream_t s, int grid, const SceneTables& sc, const ptd::Camera& cam, const BatchInfo& b, float4* feat) {
@@ -144,7 +152,7 @@ void launch_features(hipStream_t s, int grid, const SceneTables& sc, const ptd::
 
 void launch_paths(hipStream_t s, int grid, const SceneTables& sc_in, const BatchInfo& b, const ptd::Queues& qs, int32_t* cnt, ptd::PathBuf in, ptd::RetireBuf ret) {
   const SceneTables sc = resolve_scan_nodes(sc_in);
-  with_paths(sc, search_form(sc), [&](auto kernel, int lds) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, sc, b, qs, cnt, in, ret); });
+  with_paths(sc, search_form(sc), b.split_records != 0, [&](auto kernel, int lds) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, sc, b, qs, cnt, in, ret); });
 }
 void launch_shade(hipStream_t s, int grid, const SceneTables& sc, const BatchInfo& b, int depth, const ptd::Queues& qs,
                   const int32_t* cnt_in, int32_t* cnt_out, ptd::PathBuf in, ptd::HitBuf hits, ptd::PathBuf out,

@@ -209,6 +209,34 @@ PT_SCHED SubSlot sub_slot(int quo, int rem, int i) {
 // Slot i is a depth-0 retiree slot: it lies in the front of its sub-region, among the `retirees` records k_primary puts there.
 PT_SCHED bool retiree_slot(const SubSlot& s, int retirees) { return s.pos < retirees; }
 
+// ── depth-1 records: the iteration-invariant half written once per batch ──────────────────────────────────────────────────
+// In a batch that retires once (above) the lanes that SURVIVE depth 0 are the same in every iteration too, so with
+// shared_rho(r, k, wq) = r record i of sub-list (q, k, r) belongs to the same pixel for every k.  Of its 40 bytes the origin
+// hp + 0.001 * hn is a function of the first hit alone, and the throughput — depth 0 has no roulette — is (1, 1, 1) times the
+// hit material's spec or color, whichever the iteration's specular / diffuse draw chose: only the direction, the sample id
+// and that one bit differ between iterations.  Such a batch (BatchInfo::split_records) keeps, in the same buffers at the
+// same strides,
+//   plane 0, slot at                   (direction.xyz, sample id | kind << 31)   per iteration, as before
+//   plane 1, slot at - k * seg_cap     (origin.xyz, material index)              once, by the run that holds iteration 0
+// and leaves plane 2 alone; k_paths forms the throughput from its material table.  The conditions are those of retires_once
+// (trace_depth 1: nobody survives; jitter, flat lists, a trace per iteration: whole records).  PtOptions.debug_flags
+// kWholeRecords: off as an A/B switch.
+constexpr int kWholeRecords = 4096;
+PT_SCHED bool splits_records(int primary_share, bool aa_jitter, bool flat, int trace_depth, int debug_flags) {
+  return primary_shares(primary_share, aa_jitter, flat) && trace_depth >= 2 && !(debug_flags & kWholeRecords);
+}
+PT_SCHED bool splits_records(const BatchInfo& b, int debug_flags) {
+  return splits_records(b.primary_share, b.aa_jitter != 0, b.flat != 0, b.trace_depth, debug_flags);
+}
+// Where the invariant half of the record at path slot `at` = k * seg_cap + sub_offset(quo, rem, rho) * 64 + i of a queue lives:
+// the same slot of iteration 0.
+PT_SCHED int invariant_slot(int at, int k, int seg_cap) { return at - k * seg_cap; }
+// The per-iteration word's last lane: sample ids k << slot_shift | pl use 31 bits (k < 2^(31 - slot_shift), pt_init), bit 31
+// carries what shade_decide decided at depth 0: 1 specular (throughput = spec), 0 diffuse (throughput = color).
+PT_SCHED uint32_t pack_kind(int sample_id, bool specular) { return (uint32_t)sample_id | (specular ? 0x80000000u : 0u); }
+PT_SCHED int kind_sample_id(uint32_t word) { return (int)(word & 0x7fffffffu); }
+PT_SCHED bool kind_specular(uint32_t word) { return (word >> 31) != 0u; }
+
 // ── k_paths: falling pieces ───────────────────────────────────────────────────────────────────────────────────────────────
 // BatchInfo::paths_pieces: pieces per wave | fewest paths in a piece << 16.
 PT_SCHED int pack_paths_pieces(int count, int min_piece) { return count | min_piece << 16; }

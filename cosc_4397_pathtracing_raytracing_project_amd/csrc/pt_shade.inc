@@ -81,6 +81,11 @@ PT_DEV Bounce shade_decide(const ptd::Mat* __restrict__ mats, int trace_depth, i
 //   reference runs on under nvcc, which documents 2 ulp); the specular evaluations only when the wave holds a specular lane.
 //   Round 3: the fma mode used to share the exact mode's sampling (fdlibm acosf + three double-reduced sincos, 900 issue cycles a
 //   group); it is held to the tolerance, not to bit-equality, and the tolerance does not see the difference (tests/test_gpu_arith.py).
+// Origin of the new ray (pathtrace.cu:420, :433): the hit point pushed 0.001 along the normal, in the build's arithmetic.
+PT_DEV f3 bounce_origin(f3 hn, f3 hp) {
+  if (kFast || kFloatTrig) return madd(hn, 0.001f, hp);
+  return add(hp, scl(hn, 0.001f));
+}
 template <bool HW>
 PT_DEV void shade_bounce_float(const Bounce& bo, f3 hn, f3 hp, ShadeIO& s) {
   MinStd rng(1u);
@@ -114,7 +119,7 @@ PT_DEV void shade_bounce_float(const Bounce& bo, f3 hn, f3 hp, ShadeIO& s) {
   local_frame(f, tangent, bitangent);
   const f3 pert = normalize(madd(tangent, x, madd(f, y, scl(bitangent, z))));
   const bool perturb = !spec || bo.roughness > 0.0f;
-  s.o = madd(hn, 0.001f, hp);
+  s.o = bounce_origin(hn, hp);
   s.d = perturb ? pert : refl;
 }
 PT_DEV void shade_bounce(const Bounce& bo, f3 hn, f3 hp, ShadeIO& s) {
@@ -156,7 +161,7 @@ PT_DEV void shade_bounce(const Bounce& bo, f3 hn, f3 hp, ShadeIO& s) {
   local_frame(f, tangent, bitangent);
   const f3 pert = normalize(add(add(scl(tangent, x), scl(f, y)), scl(bitangent, z)));
   const bool perturb = !spec || bo.roughness > 0.0f;  // a perfect mirror keeps the reflected direction
-  s.o = add(hp, scl(hn, 0.001f));
+  s.o = bounce_origin(hn, hp);
   s.d = perturb ? pert : refl;
 }
 

@@ -105,7 +105,10 @@ typedef struct PtOptions {
                                BVH scan and up to three grid resolutions renders a few iterations fastest at pt_init), 1024
                                depth-0 retirees stored and gathered in every iteration (default in the shared form with
                                depth >= 2: a miss or an emitter hit of a camera ray has the same colour in every iteration
-                               and is stored and gathered in iteration 0 of a batch only), 2048
+                               and is stored and gathered in iteration 0 of a batch only), 4096
+                               whole 40-byte depth-1 records in every iteration (default under the same conditions: origin and
+                               material of a surviving pixel are stored once per batch, direction, sample id and the
+                               specular / diffuse choice per iteration, and the throughput is formed where the path is taken), 2048
                                keep the reference's leaf boxes for spheres (default for large scenes: tightened to the
                                ellipsoid's box, PtStats.tight_leaves; pt_stage_intersect on such a scene then expects ray
                                origins inside the scene bounds or at the camera).  pt_init fails on any other bit. */
