@@ -220,6 +220,22 @@ def lib() -> C.CDLL:
         L.pt_group_get_noise.argtypes = [C.c_void_p, _dp, _ip, _ip]
         L.pt_group_render_until.argtypes = [C.c_void_p] + _until
         L.pt_noise_fold_host.argtypes = [C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int64, _dp]
+    if hasattr(L, "pt_adaptive_round"):  # absent from older A/B builds of the library (tools/build_rev.sh)
+        _i64p = C.POINTER(C.c_int64)
+        _adaptive = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _ip, _i64p, _fp]
+        L.pt_adaptive_round.argtypes = [C.c_int, C.c_int, C.c_float]
+        L.pt_render_adaptive.argtypes = _adaptive
+        L.pt_readback_adaptive.argtypes = [_ip]
+        L.pt_resolve.argtypes = [_fp]
+        L.pt_ctx_adaptive_round.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float]
+        L.pt_ctx_render_adaptive.argtypes = [C.c_void_p] + _adaptive
+        L.pt_ctx_readback_adaptive.argtypes = [C.c_void_p, _ip]
+        L.pt_ctx_resolve.argtypes = [C.c_void_p, _fp]
+        L.pt_ctx_resolve_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        L.pt_adaptive_select_host.argtypes = [C.c_int, C.c_int, _fp, _ip, C.c_int, _ip]
+        L.pt_stage_adaptive_select.argtypes = [C.c_int, C.c_int, _fp, _ip, C.c_int, _ip]
+        L.pt_adaptive_merge_host.argtypes = [C.c_int, _fp, _fp, _ip, _ip, C.c_int, _fp, C.c_int, _dp]
+        L.pt_stage_render_list.argtypes = [_ip, C.c_int, C.c_int, C.c_int, _fp]
     _lib = L
     return L
 
@@ -446,6 +462,60 @@ def denoise_guided_variance_host(rgb_sum: np.ndarray, planes: np.ndarray, noise_
     return raw, pre
 
 
+def _select_arrays(noise_planes: np.ndarray, counts: np.ndarray, w: int, rows: int, m: int):
+    z = np.ascontiguousarray(noise_planes, np.float32).reshape(-1)
+    c = np.ascontiguousarray(counts, np.int32).reshape(-1)
+    n = int(w) * int(rows)
+    if z.size != NOISE_PLANES * n * 4 or c.size != 2 * n:
+        raise PtError(f"adaptive_select: {z.size} noise plane floats and {c.size} counts for a tile of {w}x{rows}")
+    if not 1 <= int(m) <= n:
+        raise PtError(f"adaptive_select: a list of {m} out of {n} pixels")
+    return z, c, np.full(int(m), -1, np.int32)
+
+
+def adaptive_select_host(noise_planes: np.ndarray, counts: np.ndarray, w: int, rows: int, m: int) -> np.ndarray:
+    """The selection of an adaptive round on the host (pt_adaptive_select_host; no GPU): noise planes [PT_NOISE_PLANES, n, 4], counts
+    int32 [n, 2] (T_p, M_p) of a tile of w x rows -> the m tile indices with the largest key, ascending (int32 [m])."""
+    z, c, out = _select_arrays(noise_planes, counts, w, rows, m)
+    _check(lib().pt_adaptive_select_host(int(w), int(rows), _f(z), _i(c), int(m), _i(out)))
+    return out
+
+
+def stage_adaptive_select(noise_planes: np.ndarray, counts: np.ndarray, w: int, rows: int, m: int) -> np.ndarray:
+    """adaptive_select_host's arguments through the selection's kernels (pt_stage_adaptive_select; needs a Renderer)."""
+    z, c, out = _select_arrays(noise_planes, counts, w, rows, m)
+    _check(lib().pt_stage_adaptive_select(int(w), int(rows), _f(z), _i(c), int(m), _i(out)))
+    return out
+
+
+def adaptive_merge_host(rgb_sum: np.ndarray, planes: np.ndarray, counts: np.ndarray, pixel_list: np.ndarray, group_sum: np.ndarray,
+                        group_iters: int) -> float:
+    """The merge of an adaptive round on the host (pt_adaptive_merge_host; no GPU): SUM image float32 [n, 3], planes float32
+    [PT_NOISE_PLANES, n, 4] and counts int32 [n, 2], all contiguous and updated IN PLACE, from the group sums [m, 3] of the listed
+    pixels.  Returns SSE_est, the estimates of all pixels added in pixel order."""
+    lst = np.ascontiguousarray(pixel_list, np.int32).reshape(-1)
+    sw = np.ascontiguousarray(group_sum, np.float32).reshape(-1)
+    n = rgb_sum.size // 3
+    for a, dt, size in ((rgb_sum, np.float32, 3 * n), (planes, np.float32, NOISE_PLANES * n * 4), (counts, np.int32, 2 * n)):
+        if a.dtype != dt or not a.flags.c_contiguous or a.size != size:
+            raise PtError(f"adaptive_merge_host: contiguous float32 [n, 3], float32 [{NOISE_PLANES}, n, 4] and int32 [n, 2] wanted")
+    if sw.size != 3 * lst.size:
+        raise PtError(f"adaptive_merge_host: {sw.size} group sum floats for a list of {lst.size}")
+    sse = C.c_double(-1.0)
+    _check(lib().pt_adaptive_merge_host(n, _f(rgb_sum.reshape(-1)), _f(planes.reshape(-1)), _i(counts.reshape(-1)), _i(lst), lst.size, _f(sw),
+                                        int(group_iters), C.byref(sse)))
+    return float(sse.value)
+
+
+def stage_render_list(pixel_list: np.ndarray, iter_first: int, iter_count: int) -> np.ndarray:
+    """The worker context of an adaptive round alone (pt_stage_render_list; needs a Renderer): the group sum float32 [m, 3] of the
+    iterations for the listed tile pixels (distinct, any order)."""
+    lst = np.ascontiguousarray(pixel_list, np.int32).reshape(-1)
+    out = np.empty((lst.size, 3), np.float32)
+    _check(lib().pt_stage_render_list(_i(lst), lst.size, int(iter_first), int(iter_count), _f(out)))
+    return out
+
+
 def _noise(call, *handle) -> dict:
     sse, groups, iters = C.c_double(-1.0), C.c_int32(0), C.c_int32(0)
     _check(call(*handle, C.byref(sse), C.byref(groups), C.byref(iters)))
@@ -557,6 +627,30 @@ class Renderer:
         """Renders groups of group_iters iterations (0 = a batch) until the estimated PSNR is above target_db or max_iters
         are done (pt_render_until): (iterations rendered, last estimated PSNR in dB or -1)."""
         return _render_until(lib().pt_render_until, (), iter_first, max_iters, group_iters, target_db)
+
+    # ---- adaptive sampling (include/pt_amd.h: pt_adaptive_round) ----
+    def adaptive_round(self, iter_first: int, group_iters: int, fraction: float) -> None:
+        """One round: the noisiest `fraction` of the pixels get iterations iter_first .. iter_first + group_iters - 1 (asynchronous)."""
+        _check(lib().pt_adaptive_round(int(iter_first), int(group_iters), C.c_float(fraction)))
+
+    def render_adaptive(self, iter_first: int, max_iters: int, target_db: float, fraction: float, group_iters: int = 0):
+        """render_until with rounds (pt_render_adaptive): (iteration numbers used, pixel-samples rendered, last estimated PSNR or -1)."""
+        done, samples, psnr = C.c_int32(0), C.c_int64(0), C.c_float(-1.0)
+        _check(lib().pt_render_adaptive(int(iter_first), int(max_iters), int(group_iters), C.c_float(fraction), C.c_float(target_db), C.byref(done),
+                                        C.byref(samples), C.byref(psnr)))
+        return int(done.value), int(samples.value), float(psnr.value)
+
+    def readback_adaptive(self) -> np.ndarray:
+        """The per-pixel counts int32 [n, 2]: iterations T_p, groups M_p."""
+        out = np.empty((self.n, 2), np.int32)
+        _check(lib().pt_readback_adaptive(_i(out)))
+        return out
+
+    def resolve(self) -> np.ndarray:
+        """Averaged radiance float32 [n, 3]: the SUM image over every pixel's own iterations (pt_resolve)."""
+        out = np.empty((self.n, 3), np.float32)
+        _check(lib().pt_resolve(_f(out)))
+        return out
 
     # ---- convergence metric (make_options(convergence=...)) ----
     def set_reference(self, rgb_avg: np.ndarray) -> None:

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/pt_amd.h"
+#include "pt_adaptive.h"
 #include "pt_denoise.h"
 #include "pt_device.h"
 #include "pt_internal.h"
@@ -141,6 +142,19 @@ struct PtContext {
   // A batch that failed half-way (a launch or an event call returned an error) leaves counters and record regions in an
   // undefined state: the context refuses further renders instead of appending past them.
   bool failed = false;
+  // Adaptive sampling (pt_ctx_adaptive_round, csrc/pt_adaptive.hip): all of it absent until the first round (d_list and the worker: or
+  // until pt_stage_render_list)
+  int opt_iters_per_batch = 0, opt_num_queues = 0;  // PtOptions, as given: a worker plans its own batches from them
+  bool borrowed = false;           // a worker context: device, stream, scene tables and grids belong to its parent
+  const int32_t* list = nullptr;   // BatchInfo::list of this context's batches (a worker's: the parent's d_list)
+  PtContext* worker = nullptr;     // the context that renders the pixel list; its tile is the list's m pixels, its d_image the group sum Sw
+  int32_t* d_list = nullptr;       // N entries, the first worker->N in use
+  void* d_acnt = nullptr;          // the plane cnt: N * ptad::Cnt
+  void* d_select = nullptr;        // pt_adaptive_select_bytes(N)
+  float* d_resolved = nullptr;     // [N][3], output of pt_ctx_resolve_device; absent until the first resolve
+  bool adaptive = false;           // the adaptive state: from the first round to pt_clear
+  int adaptive_rounds = 0;
+  int64_t adaptive_last = 0;       // highest iteration number folded or merged
 };
 
 namespace {
@@ -258,6 +272,8 @@ int run_batch(Ctx& g, int iter_first, int kb) {
   b.stripe = g.stripe;
   b.gap = g.stripe ? g.stripe_stride - g.stripe : 0;
   b.inv_stripe = g.stripe ? 1.0f / (float)g.stripe : 0.0f;
+  b.list = g.list;
+  if (b.list) b.stripe = 1, b.gap = 0, b.inv_stripe = 1.0f;  // (BatchInfo::list: the list form sits behind the stripe test)
   const ptk::SceneTables sc = tables(g);
   const ptk::KernelApi& k = *g.k;
   auto cnt_row = [&](int d) { return g.d_cnt + ptk::cnt_index(g.qs, d, 0); };  // the counter row of depth d
@@ -322,7 +338,7 @@ int run_batch(Ctx& g, int iter_first, int kb) {
 
 // Launch geometry (persistent grids = resident workgroups) for the kernels the current tables select.
 void plan_launch(Ctx& g) {
-  g.lds_table_bytes = g.k->lds_table_limit(tables(g), g.lds_table_forced);
+  if (!g.borrowed) g.lds_table_bytes = g.k->lds_table_limit(tables(g), g.lds_table_forced);  // (a worker keeps its parent's decision)
   const ptk::SceneTables t = tables(g);
   g.grid_gen = g.num_cus * std::min(g.cap_bpc, g.k->resident_blocks_per_cu(ptk::kGenerate, t));
   g.grid_isect = g.num_cus * std::min(g.cap_bpc, g.k->resident_blocks_per_cu(g.legacy ? ptk::kIntersectLegacy : ptk::kIntersect, t));
@@ -422,6 +438,7 @@ ptd::Queues single_queue(const Ctx& g, int n) {
 
 void destroy(Ctx* c) {
   if (!c) return;
+  destroy(c->worker);
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   for (void* p : c->allocs) (void)hipFree(p);
@@ -435,7 +452,7 @@ void destroy(Ctx* c) {
   kill(c->free_events);
   kill(c->pending_isect);
   kill(c->pending_render);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
+  if (c->stream && !c->borrowed) (void)hipStreamDestroy(c->stream);
   delete c;
 }
 
@@ -485,9 +502,29 @@ void take_scene_and_options(Ctx& g, const PtSceneDesc* sc, const PtOptions& opt)
   g.cap_bpc = opt.blocks_per_cu > 0 ? std::min(opt.blocks_per_cu, 8) : 8;
 }
 
+// Iterations per batch of a tile of N pixels (iters_per_batch <= 0: automatic) and its BatchInfo::slot_shift; -1 after a failure.
+// One function for a context's own plan and for what a worker of pt_render_adaptive WOULD plan before it exists.
+int batch_iters_for(int iters_per_batch, int N, int* slot_shift) {
+  // batch size: enough paths in flight to fill the chip a few times over; slots are int32
+  int K = iters_per_batch;
+  if (K <= 0) {
+    const int64_t target = 48ll << 20;  // ~50 M paths per batch (24 iterations of 1920x1080, ~5 GB of path state):
+                                        // launch boundaries drop below 1 % of a batch (measured K=6 → 48: +8 %)
+    K = (int)std::max<int64_t>(1, std::min<int64_t>(256, (target + N - 1) / N));
+  }
+  // sample ids are k << slot_shift | tile pixel in 31 bits (BatchInfo::slot_shift)
+  int shift = 1;
+  while ((1ll << shift) < N) ++shift;
+  if (shift > 30) return fail("pt_init: tiles of more than 2^30 pixels are not supported");
+  while (K > 1 && K > (1 << (31 - shift))) --K;
+  if (slot_shift) *slot_shift = shift;
+  return K;
+}
+
 // The tile, the iterations per batch and the compaction queues.
 int plan_batches(Ctx& g, const PtOptions& opt) {
   const int W = g.cam.resolution[0], H = g.cam.resolution[1];
+  g.opt_iters_per_batch = opt.iters_per_batch, g.opt_num_queues = opt.num_queues;
   g.pixel_begin = opt.pixel_begin;
   g.N = opt.pixel_count > 0 ? opt.pixel_count : W * H - opt.pixel_begin;
   g.stripe = opt.stripe_pixels;
@@ -502,18 +539,8 @@ int plan_batches(Ctx& g, const PtOptions& opt) {
     if (g.stripe > 0 && g.N / g.stripe >= 32768) return fail("pt_init: more than 32767 stripes");
     if (H >= 32768) return fail("pt_init: image height %d not supported (>= 32768)", H);
   }
-  // batch size: enough paths in flight to fill the chip a few times over; slots are int32
-  int K = opt.iters_per_batch;
-  if (K <= 0) {
-    const int64_t target = 48ll << 20;  // ~50 M paths per batch (24 iterations of 1920x1080, ~5 GB of path state):
-                                        // launch boundaries drop below 1 % of a batch (measured K=6 → 48: +8 %)
-    K = (int)std::max<int64_t>(1, std::min<int64_t>(256, (target + g.N - 1) / g.N));
-  }
-  // sample ids are k << slot_shift | tile pixel in 31 bits (BatchInfo::slot_shift)
-  g.slot_shift = 1;
-  while ((1ll << g.slot_shift) < g.N) ++g.slot_shift;
-  if (g.slot_shift > 30) return fail("pt_init: tiles of more than 2^30 pixels are not supported");
-  while (K > 1 && K > (1 << (31 - g.slot_shift))) --K;
+  const int K = batch_iters_for(opt.iters_per_batch, g.N, &g.slot_shift);
+  if (K < 0) return -1;
 
   // Compaction queues: every launch needs (waves % Q) == 0, so Q divides 4 * CUs.  A queue owns every Q-th 64-pixel
   // chunk of the tile in every iteration (pt_device.h); k_collect wants at most 128 chunks per queue (one LDS tile per
@@ -647,6 +674,13 @@ int setup(Ctx& g, const PtSceneDesc* sc, const PtOptions& opt) {
 int need(const PtContext* c, const char* who) {
   if (!c) return fail("%s: pt_init has not been called", who);
   return 0;
+}
+
+// What reads the image as "SUM over one number of samples" has no meaning once pixels differ in their sample counts.
+int refuse_adaptive(const PtContext& g, const char* who) {
+  if (!g.adaptive) return 0;
+  return fail("%s: the renderer is in the adaptive state (pt_adaptive_round): one sample count no longer describes the image; read it with pt_resolve, or "
+              "return to the uniform state with pt_clear", who);
 }
 
 }  // namespace
@@ -790,6 +824,7 @@ int pt_ctx_render(PtContext* c, int iter_first, int iter_count) {
   if (iter_count <= 0) return 0;
   Ctx& g = *c;
   if (g.failed) return fail("pt_render: an earlier batch of this context failed (%s); free it and create a new one", g_err.c_str());
+  if (refuse_adaptive(g, "pt_render")) return -1;
   if (g.conv_live) {
     if (iter_first < 1 || (int64_t)iter_first + iter_count - 1 > PT_CONVERGENCE_CAPACITY)
       return fail("pt_render: iterations %d .. %lld outside 1 .. %d (PT_CONVERGENCE_CAPACITY) with the convergence metric on", iter_first,
@@ -863,6 +898,7 @@ int pt_ctx_denoise_device(PtContext* c, float samples, const PtDenoiseOptions* o
   if (need(c, "pt_denoise")) return -1;
   Ctx& g = *c;
   if (g.failed) return fail("pt_denoise: an earlier batch of this context failed (%s); free it and create a new one", g_err.c_str());
+  if (refuse_adaptive(g, "pt_denoise")) return -1;
   const int W = g.cam.resolution[0];
   if (g.stripe || g.pixel_begin % W || g.N % W)
     return fail("pt_denoise: the tile must consist of whole contiguous image rows (begin %d, count %d, stripe %d, width %d)", g.pixel_begin, g.N, g.stripe, W);
@@ -891,6 +927,7 @@ int pt_ctx_denoise_guided_device(PtContext* c, const PtDenoiseOptions* opt, cons
   if (need(c, "pt_denoise_guided")) return -1;
   Ctx& g = *c;
   if (g.failed) return fail("pt_denoise_guided: an earlier batch of this context failed (%s); free it and create a new one", g_err.c_str());
+  if (refuse_adaptive(g, "pt_denoise_guided")) return -1;
   const int W = g.cam.resolution[0];
   if (g.stripe || g.pixel_begin % W || g.N % W)
     return fail("pt_denoise_guided: the tile must consist of whole contiguous image rows (begin %d, count %d, stripe %d, width %d)", g.pixel_begin, g.N, g.stripe, W);
@@ -923,6 +960,7 @@ int pt_ctx_noise_fold(PtContext* c) {
   if (need(c, "pt_noise_fold")) return -1;
   Ctx& g = *c;
   if (g.failed) return fail("pt_noise_fold: an earlier batch of this context failed (%s); free it and create a new one", g_err.c_str());
+  if (refuse_adaptive(g, "pt_noise_fold")) return -1;
   const int64_t n = g.rendered - g.noise_iters;
   if (n <= 0) return 0;  // nothing rendered since the last fold
   HIP_OK(hipSetDevice(g.device));
@@ -949,8 +987,9 @@ int pt_ctx_get_noise(PtContext* c, double* sse, int* groups, int* iterations) {
       HIP_OK(hipMemcpy(sse, result, sizeof(double), hipMemcpyDeviceToHost));
     }
   }
-  if (groups) *groups = g.noise_groups;
-  if (iterations) *iterations = (int)std::min<int64_t>(g.noise_iters, INT32_MAX);
+  // (the adaptive state: the last merge's SSE_est lies where a fold's does; every round counts as a group)
+  if (groups) *groups = g.noise_groups + g.adaptive_rounds;
+  if (iterations) *iterations = (int)std::min<int64_t>(g.adaptive ? g.adaptive_last : g.noise_iters, INT32_MAX);
   return 0;
 }
 
@@ -972,6 +1011,7 @@ int pt_ctx_render_until(PtContext* c, int iter_first, int max_iters, int group_i
     return fail("pt_render_until: iterations %d, +%d in groups of %d until %g dB: the first is >= 1, the count >= 1, the group >= 0 (0 = a batch), the target finite",
                 iter_first, max_iters, group_iters, (double)target_db);
   if (g.failed) return fail("pt_render_until: an earlier batch of this context failed (%s); free it and create a new one", g_err.c_str());
+  if (refuse_adaptive(g, "pt_render_until")) return -1;
   const int group = group_iters ? group_iters : g.K;
   int done = 0;
   float psnr = -1.0f;
@@ -988,6 +1028,192 @@ int pt_ctx_render_until(PtContext* c, int iter_first, int max_iters, int group_i
   if (iters_done) *iters_done = done;
   if (psnr_db) *psnr_db = psnr;
   return 0;
+}
+
+
+// ---- adaptive sampling: further groups over the noisiest pixels only (csrc/pt_adaptive.hip) -------------------------------
+namespace {
+int ensure_list(Ctx& g) {
+  if (g.d_list) return 0;
+  if (dalloc(g, &g.d_list, (size_t)g.N)) return -1;
+  HIP_OK(hipMemset(g.d_list, 0, (size_t)g.N * sizeof(int32_t)));  // every entry a tile pixel from the start
+  return 0;
+}
+
+void drop_worker(Ctx& g) {
+  if (!g.worker) return;
+  g.device_bytes -= g.worker->device_bytes;
+  destroy(g.worker);
+  g.worker = nullptr;
+}
+
+// The worker context for a list of m pixels: batches, queues, buffers and launch widths planned for N = m like any context's; the
+// scene tables, the grid or BVH choice and the LDS-table decision are the parent's (neither uploaded nor measured again, not owned).
+int ensure_worker(Ctx& g, int m) {
+  if (g.worker && g.worker->N == m) return 0;
+  drop_worker(g);
+  if (ensure_list(g)) return -1;
+  Ctx* w = new Ctx();
+  w->borrowed = true;
+  w->device = g.device, w->stream = g.stream, w->k = g.k, w->arith = g.arith, w->num_cus = g.num_cus;
+  w->cam = g.cam, w->dcam = g.dcam, w->depth = g.depth;
+  w->scene = g.scene, w->grids = g.grids, w->grid_pick = g.grid_pick, w->grid_enabled = g.grid_enabled, w->tight_leaves = g.tight_leaves;
+  w->lds_table_bytes = g.lds_table_bytes, w->lds_table_forced = g.lds_table_forced;
+  w->primary_pieces = g.primary_pieces, w->primary_share = g.primary_share, w->paths_pieces = g.paths_pieces;
+  w->cap_bpc = g.cap_bpc, w->legacy = g.legacy, w->debug_flags = g.debug_flags, w->aa_jitter = g.aa_jitter;
+  w->fuse_primary = g.fuse_primary, w->fuse_bounces = g.fuse_bounces;
+  PtOptions o{};
+  o.pixel_begin = g.pixel_begin, o.pixel_count = m;
+  o.iters_per_batch = g.opt_iters_per_batch, o.num_queues = g.opt_num_queues;  // 0: automatic for m pixels
+  if (plan_batches(*w, o)) return destroy(w), -1;
+  plan_launch(*w);
+  if (alloc_batch_buffers(*w)) return destroy(w), -1;
+  w->list = g.d_list;
+  g.worker = w;
+  g.device_bytes += w->device_bytes;
+  return 0;
+}
+
+// Iterations iter_first .. iter_first + iter_count - 1 of the listed pixels into the worker's cleared group sum.
+int render_list(Ctx& g, int iter_first, int iter_count) {
+  Ctx& w = *g.worker;
+  HIP_OK(hipMemsetAsync(w.d_image, 0, 3 * (size_t)w.N * sizeof(float), g.stream));
+  const int end = iter_first + iter_count;
+  for (int it = iter_first; it < end; it += w.K)
+    if (run_batch(w, it, std::min(w.K, end - it))) {
+      g.failed = true;
+      return -1;
+    }
+  return 0;
+}
+
+// Everything a round refuses, before anything is allocated or launched.
+int adaptive_refusal(const Ctx& g, const char* who, int iter_first, int group_iters, float fraction) {
+  if (g.failed) return fail("%s: an earlier batch of this context failed (%s); free it and create a new one", who, g_err.c_str());
+  if (iter_first < 1 || group_iters < 1 || (int64_t)iter_first + group_iters - 1 > INT32_MAX)
+    return fail("%s: iterations %d, +%d: the first is >= 1, the group holds at least one", who, iter_first, group_iters);
+  if (!(fraction > 0.0f && fraction <= 1.0f)) return fail("%s: fraction %g is not in (0, 1]", who, (double)fraction);
+  if (g.conv) return fail("%s: the renderer was created with PtOptions.convergence = %d; the convergence metric follows whole iterations", who, g.conv);
+  const int W = g.cam.resolution[0];
+  if (g.stripe || g.pixel_begin % W || g.N % W)
+    return fail("%s: the tile must consist of whole contiguous image rows (begin %d, count %d, stripe %d, width %d)", who, g.pixel_begin, g.N, g.stripe, W);
+  if (g.adaptive) return 0;
+  if (g.noise_groups < 2) return fail("%s: %d group(s) folded; the selection needs the noise estimate of at least 2 (pt_noise_fold)", who, g.noise_groups);
+  if (g.rendered != g.noise_iters)
+    return fail("%s: %lld iteration(s) rendered since the last fold; fold first (pt_noise_fold)", who, (long long)(g.rendered - g.noise_iters));
+  if (g.noise_iters > INT32_MAX / 2) return fail("%s: %lld iterations folded: the per-pixel counts are int32", who, (long long)g.noise_iters);
+  return 0;
+}
+
+// group_iters == 0 of pt_render_adaptive: the iterations per batch a worker for m pixels plans (plan_batches' own function)
+int worker_batch_iters(const Ctx& g, int m) { return g.worker && g.worker->N == m ? g.worker->K : batch_iters_for(g.opt_iters_per_batch, m, nullptr); }
+}  // namespace
+
+int pt_ctx_adaptive_round(PtContext* c, int iter_first, int group_iters, float fraction) {
+  if (need(c, "pt_adaptive_round")) return -1;
+  Ctx& g = *c;
+  if (adaptive_refusal(g, "pt_adaptive_round", iter_first, group_iters, fraction)) return -1;
+  HIP_OK(hipSetDevice(g.device));
+  const int W = g.cam.resolution[0];
+  if (!g.adaptive) {  // the first round since pt_init / pt_clear: every pixel has the fold's T and M
+    if (!g.d_acnt) {
+      char *cnt = nullptr, *ws = nullptr;
+      if (dalloc(g, &cnt, (size_t)g.N * sizeof(ptad::Cnt)) || dalloc(g, &ws, pt_adaptive_select_bytes((size_t)g.N)) || ensure_list(g)) return -1;
+      g.d_acnt = cnt, g.d_select = ws;
+    }
+    if (pt_adaptive_init_counts_launch(g.stream, g.N, g.d_acnt, (int)g.noise_iters, g.noise_groups)) return -1;
+    g.adaptive = true;
+    g.adaptive_rounds = 0;
+    g.adaptive_last = g.noise_iters;
+  }
+  const int m = ptad::list_length((double)fraction, g.N);
+  if (ensure_worker(g, m)) return -1;
+  if (pt_adaptive_select_launch(g.stream, W, g.N / W, static_cast<const float*>(g.d_noise), g.d_acnt, m, g.d_select, g.d_list)) return -1;
+  if (render_list(g, iter_first, group_iters)) return -1;
+  if (pt_adaptive_merge_launch(g.stream, g.N, g.d_image, g.d_noise, g.d_acnt, g.d_list, m, g.worker->d_image, group_iters)) return -1;
+  g.adaptive_rounds += 1;
+  g.adaptive_last = std::max<int64_t>(g.adaptive_last, (int64_t)iter_first + group_iters - 1);
+  g.samples += (int64_t)group_iters * m;  // (live_rays and the kernel timings stay the parent's own launches')
+  return 0;
+}
+
+int pt_ctx_render_adaptive(PtContext* c, int iter_first, int max_iters, int group_iters, float fraction, float target_db, int* iters_done,
+                           int64_t* samples_done, float* psnr_db) {
+  if (need(c, "pt_render_adaptive")) return -1;
+  Ctx& g = *c;
+  if (max_iters < 1 || (int64_t)iter_first + max_iters - 1 > INT32_MAX || group_iters < 0 || !std::isfinite(target_db))
+    return fail("pt_render_adaptive: iterations %d, +%d in groups of %d until %g dB: the count is >= 1, the group >= 0 (0 = a batch of the worker), the target finite",
+                iter_first, max_iters, group_iters, (double)target_db);
+  // what a round would refuse, apart from the state of the folds, which the uniform groups below establish
+  if (g.failed) return fail("pt_render_adaptive: an earlier batch of this context failed (%s); free it and create a new one", g_err.c_str());
+  if (iter_first < 1) return fail("pt_render_adaptive: the first iteration %d is not >= 1", iter_first);
+  if (!(fraction > 0.0f && fraction <= 1.0f)) return fail("pt_render_adaptive: fraction %g is not in (0, 1]", (double)fraction);
+  if (g.conv) return fail("pt_render_adaptive: the renderer was created with PtOptions.convergence = %d; the convergence metric follows whole iterations", g.conv);
+  const int W = g.cam.resolution[0];
+  if (g.stripe || g.pixel_begin % W || g.N % W)
+    return fail("pt_render_adaptive: the tile must consist of whole contiguous image rows (begin %d, count %d, stripe %d, width %d)", g.pixel_begin, g.N, g.stripe, W);
+  const int m = ptad::list_length((double)fraction, g.N);
+  const int group = group_iters ? group_iters : worker_batch_iters(g, m);
+  int done = 0;
+  int64_t samples = 0;
+  float psnr = -1.0f;
+  while (done < max_iters) {
+    const int n = std::min(group, max_iters - done);
+    if (!g.adaptive && g.noise_groups < 2) {  // a uniform group and its fold, as pt_render_until
+      if (pt_ctx_render(c, iter_first + done, n) || pt_ctx_noise_fold(c)) return -1;
+      samples += (int64_t)n * g.N;
+    } else {
+      if (!g.adaptive && g.rendered != g.noise_iters && pt_ctx_noise_fold(c)) return -1;  // iterations of the caller's, not yet folded
+      if (pt_ctx_adaptive_round(c, iter_first + done, n, fraction)) return -1;
+      samples += (int64_t)n * m;
+    }
+    done += n;
+    double sse = -1.0;
+    if (pt_ctx_get_noise(c, &sse, nullptr, nullptr)) return -1;
+    if (sse < 0.0) continue;  // one group says nothing about the spread
+    psnr = pt_psnr_from_sse(sse, g.N);
+    if (psnr > target_db) break;
+  }
+  if (iters_done) *iters_done = done;
+  if (samples_done) *samples_done = samples;
+  if (psnr_db) *psnr_db = psnr;
+  return 0;
+}
+
+int pt_ctx_readback_adaptive(PtContext* c, int32_t* counts) {
+  if (need(c, "pt_readback_adaptive")) return -1;
+  if (!counts) return fail("pt_readback_adaptive: null buffer");
+  Ctx& g = *c;
+  if (!g.adaptive) {  // the uniform state: the fold's T and M for every pixel
+    if (pt_ctx_sync(c)) return -1;
+    for (size_t p = 0; p < (size_t)g.N; ++p) counts[2 * p] = (int32_t)std::min<int64_t>(g.noise_iters, INT32_MAX), counts[2 * p + 1] = g.noise_groups;
+    return 0;
+  }
+  HIP_OK(hipSetDevice(g.device));
+  HIP_OK(hipMemcpyAsync(counts, g.d_acnt, (size_t)g.N * sizeof(ptad::Cnt), hipMemcpyDeviceToHost, g.stream));
+  return pt_ctx_sync(c);
+}
+
+int pt_ctx_resolve_device(PtContext* c, const float** rgb_dev) {
+  if (need(c, "pt_resolve")) return -1;
+  Ctx& g = *c;
+  if (g.failed) return fail("pt_resolve: an earlier batch of this context failed (%s); free it and create a new one", g_err.c_str());
+  if (g.noise_groups < 1) return fail("pt_resolve: nothing has been folded (pt_noise_fold): the sample counts are the folds'");
+  if (g.rendered != g.noise_iters)
+    return fail("pt_resolve: %lld iteration(s) rendered since the last fold; fold first (pt_noise_fold)", (long long)(g.rendered - g.noise_iters));
+  if (g.noise_iters > INT32_MAX) return fail("pt_resolve: %lld iterations folded", (long long)g.noise_iters);
+  HIP_OK(hipSetDevice(g.device));
+  if (!g.d_resolved && dalloc(g, &g.d_resolved, 3 * (size_t)g.N)) return -1;
+  if (pt_adaptive_resolve_launch(g.stream, g.N, g.d_image, g.adaptive ? g.d_acnt : nullptr, (int)g.noise_iters, g.d_resolved)) return -1;
+  if (rgb_dev) *rgb_dev = g.d_resolved;
+  return 0;
+}
+int pt_ctx_resolve(PtContext* c, float* rgb_avg_host) {
+  if (!rgb_avg_host) return fail("pt_resolve: null buffer");
+  const float* d = nullptr;
+  if (pt_ctx_resolve_device(c, &d)) return -1;
+  HIP_OK(hipMemcpyAsync(rgb_avg_host, d, 3 * (size_t)c->N * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  return pt_ctx_sync(c);
 }
 
 int pt_ctx_sync(PtContext* c) {
@@ -1024,6 +1250,7 @@ int pt_ctx_save_u8_device(PtContext* c, float samples, const uint8_t** rgb8_dev)
   Ctx& g = *c;
   const int W = g.cam.resolution[0];
   if (!(samples > 0.0f)) return fail("pt_save_u8: samples must be positive");
+  if (refuse_adaptive(g, "pt_save_u8")) return -1;
   if (g.pixel_begin % W || g.N % W || (g.stripe && g.stripe != W))
     return fail("pt_save_u8: the tile must consist of whole image rows (begin %d, count %d, stripe %d, width %d)", g.pixel_begin, g.N, g.stripe, W);
   HIP_OK(hipSetDevice(g.device));
@@ -1044,6 +1271,7 @@ int pt_ctx_save_u8(PtContext* c, float samples, uint8_t* rgb8_host) {
 int pt_ctx_preview_rgba8_device(PtContext* c, int iterations, void* rgba_dev) {
   if (need(c, "pt_preview_rgba8_device")) return -1;
   if (!rgba_dev || iterations <= 0) return fail("pt_preview_rgba8_device: bad argument");
+  if (refuse_adaptive(*c, "pt_preview_rgba8_device")) return -1;
   HIP_OK(hipSetDevice(c->device));
   c->k->preview(c->stream, c->N, iterations, c->d_image, reinterpret_cast<uchar4*>(rgba_dev));
   HIP_OK(hipStreamSynchronize(c->stream));
@@ -1053,6 +1281,7 @@ int pt_ctx_preview_rgba8_device(PtContext* c, int iterations, void* rgba_dev) {
 int pt_ctx_preview_rgba8(PtContext* c, int iterations, uint8_t* rgba_host) {
   if (need(c, "pt_preview_rgba8")) return -1;
   if (!rgba_host || iterations <= 0) return fail("pt_preview_rgba8: bad argument");
+  if (refuse_adaptive(*c, "pt_preview_rgba8")) return -1;
   HIP_OK(hipSetDevice(c->device));
   uchar4* d = nullptr;
   HIP_OK(hipMalloc((void**)&d, (size_t)c->N * 4));
@@ -1125,6 +1354,10 @@ int pt_ctx_clear(PtContext* c) {
   if (c->d_noise) HIP_OK(hipMemsetAsync(c->d_noise, 0, pt_noise_state_bytes((size_t)c->N), c->stream));
   c->noise_groups = 0;
   c->noise_iters = c->rendered = 0;
+  if (c->d_acnt) HIP_OK(hipMemsetAsync(c->d_acnt, 0, (size_t)c->N * sizeof(ptad::Cnt), c->stream));  // back to the uniform state; nothing is freed
+  c->adaptive = false;
+  c->adaptive_rounds = 0;
+  c->adaptive_last = 0;
   if (c->conv) {  // forget the curve, re-arm the capture (a supplied frame stays)
     HIP_OK(hipMemsetAsync(c->d_sse, 0xff, (size_t)PT_CONVERGENCE_CAPACITY * sizeof(double), c->stream));
     c->conv_last = 0;
@@ -1205,6 +1438,13 @@ int pt_readback_noise(float* planes_host) { return pt_ctx_readback_noise(g_defau
 int pt_render_until(int iter_first, int max_iters, int group_iters, float target_db, int* iters_done, float* psnr_db) {
   return pt_ctx_render_until(g_default, iter_first, max_iters, group_iters, target_db, iters_done, psnr_db);
 }
+int pt_adaptive_round(int iter_first, int group_iters, float fraction) { return pt_ctx_adaptive_round(g_default, iter_first, group_iters, fraction); }
+int pt_render_adaptive(int iter_first, int max_iters, int group_iters, float fraction, float target_db, int* iters_done, int64_t* samples_done,
+                       float* psnr_db) {
+  return pt_ctx_render_adaptive(g_default, iter_first, max_iters, group_iters, fraction, target_db, iters_done, samples_done, psnr_db);
+}
+int pt_readback_adaptive(int32_t* counts) { return pt_ctx_readback_adaptive(g_default, counts); }
+int pt_resolve(float* rgb_avg_host) { return pt_ctx_resolve(g_default, rgb_avg_host); }
 int pt_set_reference(const float* rgb_avg_host) { return pt_ctx_set_reference(g_default, rgb_avg_host); }
 int pt_get_convergence(int iter_first, int iter_count, double* sse) { return pt_ctx_get_convergence(g_default, iter_first, iter_count, sse); }
 int pt_iterations_to_clean(float threshold_db, int* iteration) { return pt_ctx_iterations_to_clean(g_default, threshold_db, iteration); }
@@ -1426,6 +1666,53 @@ int pt_stage_denoise_guided(int w, int rows, const float* rgb_sum, const float* 
   HIP_OK(hipStreamSynchronize(g.stream));
   HIP_OK(hipMemcpy(rgb_avg, d_out, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
   return 0;
+}
+
+// The selection's kernels on caller-supplied host arrays (pt_adaptive_select_host's arguments)
+int pt_stage_adaptive_select(int w, int rows, const float* noise_planes, const int32_t* counts, int m, int32_t* list) {
+  if (need(g_default, "pt_stage_adaptive_select")) return -1;
+  Ctx& g = *g_default;
+  if (pt_adaptive_check_select("pt_stage_adaptive_select", w, rows, noise_planes, counts, m, list)) return -1;
+  HIP_OK(hipSetDevice(g.device));
+  Scratch sc;
+  const size_t n = (size_t)w * rows;
+  float* d_plane0 = sc.get<float>(4 * n);  // the selection reads plane 0 only
+  int32_t* d_counts = sc.get<int32_t>(2 * n);
+  char* d_ws = sc.get<char>(pt_adaptive_select_bytes(n));
+  int32_t* d_list = sc.get<int32_t>((size_t)m);
+  if (!d_plane0 || !d_counts || !d_ws || !d_list) return fail("pt_stage_adaptive_select: out of device memory");
+  HIP_OK(hipMemcpy(d_plane0, noise_planes, 4 * n * sizeof(float), hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(d_counts, counts, 2 * n * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_OK(hipMemset(d_list, 0xff, (size_t)m * sizeof(int32_t)));  // an entry nobody wrote shows as -1
+  if (pt_adaptive_select_launch(g.stream, w, rows, d_plane0, d_counts, m, d_ws, d_list)) return -1;
+  HIP_OK(hipStreamSynchronize(g.stream));
+  HIP_OK(hipMemcpy(list, d_list, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// The worker context alone: iterations iter_first .. iter_first + iter_count - 1 of the m listed tile pixels (distinct, any order);
+// rgb_sum_host receives the group sum, m * 3 floats in list order.  Leaves image, folds and state of the renderer alone.
+int pt_stage_render_list(const int32_t* list, int m, int iter_first, int iter_count, float* rgb_sum_host) {
+  if (need(g_default, "pt_stage_render_list")) return -1;
+  Ctx& g = *g_default;
+  if (!list || !rgb_sum_host || m < 1 || m > g.N || iter_first < 1 || iter_count < 0 || (int64_t)iter_first + iter_count - 1 > INT32_MAX)
+    return fail("pt_stage_render_list: bad argument (a list of %d out of %d pixels, iterations %d, +%d)", m, g.N, iter_first, iter_count);
+  if (g.failed) return fail("pt_stage_render_list: an earlier batch of this context failed (%s); free it and create a new one", g_err.c_str());
+  if (g.stripe) return fail("pt_stage_render_list: a striped tile has no list form");
+  {
+    std::vector<uint8_t> seen((size_t)g.N, 0);
+    for (int i = 0; i < m; ++i) {
+      if (list[i] < 0 || list[i] >= g.N || seen[(size_t)list[i]]) return fail("pt_stage_render_list: list[%d] = %d is outside the tile or repeated", i, list[i]);
+      seen[(size_t)list[i]] = 1;
+    }
+  }
+  HIP_OK(hipSetDevice(g.device));
+  if (ensure_worker(g, m)) return -1;
+  HIP_OK(hipStreamSynchronize(g.stream));  // (the list may still be read by an earlier round)
+  HIP_OK(hipMemcpy(g.d_list, list, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice));
+  if (render_list(g, iter_first, iter_count)) return -1;
+  HIP_OK(hipMemcpyAsync(rgb_sum_host, g.worker->d_image, 3 * (size_t)m * sizeof(float), hipMemcpyDeviceToHost, g.stream));
+  return pt_ctx_sync(&g);
 }
 
 }  // extern "C"

@@ -37,3 +37,20 @@ inline size_t pt_noise_state_bytes(size_t pixels) { return 32 * pixels + 8 * (pt
 struct PtContext;
 int64_t pt_ctx_unfolded_iterations(const PtContext* c);  // iterations rendered since the context's last fold
 int pt_noise_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, void* state_dev, const ptnz::Fold& f);
+// k_noise_reduce alone: *sse_dev = partial_dev[0] + ... + partial_dev[count - 1] in index order (one thread adds).
+int pt_noise_reduce_launch(hipStream_t stream, int count, const double* partial_dev, double* sse_dev);
+
+// Adaptive sampling (pt_adaptive.hip), on raw device pointers and a stream; everything asynchronous, nothing allocated.
+// counts_dev: the plane `cnt`, pixels * {int32 T_p, int32 M_p}.  noise_dev / noise_state_dev: the fold's state (pt_noise_state_bytes).
+// pt_adaptive_select_launch: the m pixels of a tile of w x rows with the largest key -> list_dev (m entries, ascending tile index);
+// workspace_dev holds pt_adaptive_select_bytes(pixels) bytes.  pt_adaptive_merge_launch: group_sum_dev (m * 3 floats, the worker's
+// sums of group_iters iterations for the pixels of list_dev) joins the image, the planes and the counts; leaves SSE_est where a
+// fold leaves it.  pt_adaptive_resolve_launch: rgb_avg_dev = S / (float)T_p (counts_dev == nullptr: T_p = iters for every pixel).
+size_t pt_adaptive_select_bytes(size_t pixels);
+int pt_adaptive_check_select(const char* who, int w, int rows, const float* noise_planes, const int32_t* counts, int m, const int32_t* list);
+int pt_adaptive_init_counts_launch(hipStream_t stream, int pixels, void* counts_dev, int iters, int groups);
+int pt_adaptive_select_launch(hipStream_t stream, int w, int rows, const float* noise_dev, const void* counts_dev, int m, void* workspace_dev,
+                              int32_t* list_dev);
+int pt_adaptive_merge_launch(hipStream_t stream, int pixels, float* rgb_sum_dev, void* noise_state_dev, void* counts_dev, const int32_t* list_dev, int m,
+                             const float* group_sum_dev, int group_iters);
+int pt_adaptive_resolve_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, const void* counts_dev, int iters, float* rgb_avg_dev);

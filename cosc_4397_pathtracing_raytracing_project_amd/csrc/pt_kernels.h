@@ -69,6 +69,7 @@ struct BatchInfo {
   int32_t pixel_begin;  // global index of tile pixel 0
   // Striped tiles (multi-GPU load balance): the tile is every `stripe`-pixel run out of `stripe + gap`;
   // tile pixel p is global pixel pixel_begin + p + (p / stripe) * gap.  stripe == 0: contiguous tile.
+  // Kernels read these three ONLY through global_pixel (pt_kernels.hip): a list batch (`list` below) carries stripe = 1 as a marker.
   int32_t stripe, gap;
   float inv_stripe;
   int32_t trace_depth;
@@ -84,6 +85,10 @@ struct BatchInfo {
                            // come, first served (counters behind ptd::Queues::deal); <= 1: one piece per wave; high 16 bits: fewest paths in a piece
   int32_t retire_once;     // 1 (the host sets it from pt_sched.h retires_once): a sample that retires at depth 0 does so in every iteration, with the
                            // same colour — k_primary stores its record in iteration 0 of the batch only, k_collect gathers it there only
+  // Pixel list (adaptive sampling, pt_adaptive.hip): not nullptr, with stripe != 0 (any value: the list is looked at behind the
+  // stripe test, so that contiguous tiles run the code they always ran): tile pixel p is global pixel pixel_begin + list[p] —
+  // N entries, distinct, in any order.  Queues, slots, records and the gather work on tile pixels and never look at it.
+  const int32_t* list;
   int32_t split_records;   // 1 (the host sets it from pt_sched.h splits_records): a depth-1 record's origin and material index are stored once per
                            // batch, in plane 1 at the slot of iteration 0; plane 0 holds direction, sample id and the specular / diffuse bit
 };

@@ -252,9 +252,10 @@ PT_DEV void stage16(void* lds, const void* g, int bytes) {
   for (int i = threadIdx.x; i < bytes / 16; i += blockDim.x) dst[i] = src[i];
 }
 
-// Tile pixel → global pixel index (what keys the RNG and the camera ray), see BatchInfo::stripe.
+// Tile pixel → global pixel index (what keys the RNG and the camera ray), see BatchInfo::stripe and BatchInfo::list (p < b.N).
 PT_DEV int global_pixel(const BatchInfo& b, int p) {
   if (b.stripe == 0) return b.pixel_begin + p;
+  if (b.list) return b.pixel_begin + b.list[p];  // (the host gives a list batch stripe != 0, so the contiguous form pays nothing for this test)
   int i, r;
   divmod(p, b.stripe, b.inv_stripe, i, r);
   return b.pixel_begin + p + i * b.gap;

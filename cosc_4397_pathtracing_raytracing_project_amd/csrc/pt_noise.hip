@@ -75,7 +75,12 @@ int pt_noise_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, vo
   double* partial = reinterpret_cast<double*>(planes + (size_t)PT_NOISE_PLANES * pixels);
   const int blocks = (int)pt_noise_partials((size_t)pixels);
   hipLaunchKernelGGL(k_noise_fold, dim3(blocks), dim3(kBlock), 0, stream, pixels, rgb_sum_dev, planes, f, partial);
-  hipLaunchKernelGGL(k_noise_reduce, dim3(1), dim3(kReduce), 0, stream, blocks, partial, partial + blocks);
+  return pt_noise_reduce_launch(stream, blocks, partial, partial + blocks);
+}
+
+// pt_internal.h: the second half of a fold on its own (the merge of pt_adaptive_round produces partial sums of the same kind)
+int pt_noise_reduce_launch(hipStream_t stream, int count, const double* partial_dev, double* sse_dev) {
+  hipLaunchKernelGGL(k_noise_reduce, dim3(1), dim3(kReduce), 0, stream, count, partial_dev, sse_dev);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return pt_fail("pt_noise_fold: launch failed: %s", hipGetErrorString(e));
   return 0;

@@ -7,7 +7,7 @@
 //                       [--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa]
 //                       [--preview N] [--convergence N | --reference FILE.pfm] [--clean-db X] [--features]
 //                       [--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]]
-//                       [--denoise-guided] [--until-db X [--until-group G]]
+//                       [--denoise-guided] [--until-db X [--until-group G] [--adaptive F]]
 //
 // Without --gpus the run goes through the pathtrace.h-compatible shim (pathtraceInit / pathtrace per
 // iteration / pathtraceFree), i.e. the code path a reference main.cpp would take.  With --gpus K (K >= 1;
@@ -36,6 +36,12 @@
 // iterations (--until-group, default 0 = one batch), a fold after each, until the estimated PSNR is above X dB; --spp becomes the cap.
 // Prints `noise: <iterations> iterations, <groups> groups, estimated PSNR <x> dB`; the file names, --features, --denoise and the
 // curves carry the iterations actually rendered.
+// --adaptive F (needs --until-db X, takes --until-group; excludes --gpus / --devices, --denoise*, --convergence, --reference and
+// --preview): adaptive sampling (pt_render_adaptive) — two uniform groups of G iterations, then rounds of G iterations over the
+// noisiest fraction F (0 < F <= 1) of the pixels, until the estimated PSNR is above X dB or --spp iteration numbers are used up.
+// Prints `adaptive: <iterations> iterations, <rounds> rounds, <samples> samples (<x> of uniform), estimated PSNR <y> dB`, x being
+// the samples over iterations * pixels; the PNG / PFM / HDR hold the resolved image (pt_resolve: every pixel's sum over its own
+// sample count) and the file name carries ceil(samples / pixels).
 // Output name: PREFIX.<spp>samp.png, or with --stamp the reference's own
 // <FILE>.<UTC start time>.<spp>samp.png (main.cpp:99-102).
 #include <hip/hip_runtime.h>
@@ -59,7 +65,7 @@ int main(int argc, char** argv) {
     std::printf("Usage: %s SCENEFILE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] "
                 "[--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa] [--preview N] "
                 "[--convergence N | --reference FILE.pfm] [--clean-db X] [--features] "
-                "[--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]] [--denoise-guided] [--until-db X [--until-group G]]\n", argv[0]);
+                "[--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]] [--denoise-guided] [--until-db X [--until-group G] [--adaptive F]]\n", argv[0]);
     return 1;
   }
   int rw = 0, rh = 0, spp = 0, depth = 0, gpus = -1, arith = PT_ARITH_EXACT, preview = 0, transport = PT_GROUP_TRANSPORT_AUTO;
@@ -68,7 +74,7 @@ int main(int argc, char** argv) {
   PtDenoiseOptions dn_opt{};
   int convergence = 0, until_group = 0;
   bool until = false, until_group_given = false;
-  float clean_db = 35.0f, until_db = 0.0f;
+  float clean_db = 35.0f, until_db = 0.0f, adaptive = 0.0f;  // adaptive > 0: --adaptive F
   std::string out, reference;
   for (int i = 2; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--res") && i + 1 < argc) std::sscanf(argv[++i], "%dx%d", &rw, &rh);
@@ -145,6 +151,14 @@ int main(int argc, char** argv) {
       }
       until_group = (int)v, until_group_given = true;
     }
+    else if (!std::strcmp(argv[i], "--adaptive") && i + 1 < argc) {
+      char* end = nullptr;
+      adaptive = std::strtof(argv[++i], &end);
+      if (end == argv[i] || *end || !(adaptive > 0.0f && adaptive <= 1.0f)) {
+        std::fprintf(stderr, "--adaptive wants the fraction of the pixels a round samples, 0 < F <= 1\n");
+        return 1;
+      }
+    }
     else if (!std::strcmp(argv[i], "--aa")) aa = true;  // extension: stochastic anti-aliasing (PtOptions.aa_jitter)
     else if (!std::strcmp(argv[i], "--arith") && i + 1 < argc) {
       const char* a = argv[++i];
@@ -181,6 +195,16 @@ int main(int argc, char** argv) {
   if (guided && preview > 0) {
     std::fprintf(stderr, "--denoise-guided and --preview exclude each other (one loop over the iterations)\n");
     return 1;
+  }
+  if (adaptive > 0.0f) {
+    if (!until) {
+      std::fprintf(stderr, "--adaptive wants --until-db (the estimated PSNR at which to stop)\n");
+      return 1;
+    }
+    if (gpus >= 0 || denoise || guided || convergence != 0 || preview > 0) {
+      std::fprintf(stderr, "--adaptive excludes --gpus / --devices, --denoise, --denoise-guided, --convergence, --reference and --preview\n");
+      return 1;
+    }
   }
   if (until && preview > 0) {
     std::fprintf(stderr, "--until-db and --preview exclude each other (one loop over the iterations)\n");
@@ -281,7 +305,24 @@ int main(int argc, char** argv) {
       return EXIT_FAILURE;
     }
     const auto t0 = std::chrono::high_resolution_clock::now();
-    if (until) {
+    int64_t adaptive_samples = 0;
+    if (adaptive > 0.0f) {
+      int done = 0, groups = 0;
+      float psnr = -1.0f;
+      scene->state.image.resize((size_t)W * H * 3);
+      if (pt_render_adaptive(1, iters, until_group, adaptive, until_db, &done, &adaptive_samples, &psnr) || pt_get_noise(nullptr, &groups, nullptr) ||
+          pt_resolve(scene->state.image.data())) {
+        std::fprintf(stderr, "HIP error (pt_render_adaptive): %s\n", pt_last_error());
+        return EXIT_FAILURE;
+      }
+      const int64_t pixels = (int64_t)W * H;
+      std::printf("adaptive: %d iterations, %d rounds, %lld samples (%.4f of uniform), estimated PSNR %.9g dB\n", done, std::max(0, groups - 2),
+                  (long long)adaptive_samples, (double)adaptive_samples / ((double)done * (double)pixels), (double)psnr);
+      scene->state.iterations = done;
+      iters = (int)((adaptive_samples + pixels - 1) / pixels);  // what the file names carry
+      name_outputs();
+      iters = done;  // (the feature pass covers the iteration numbers used)
+    } else if (until) {
       int done = 0, groups = 0;
       float psnr = -1.0f;
       if (pt_render_until(1, iters, until_group, until_db, &done, &psnr) || pt_get_noise(nullptr, &groups, nullptr)) {
@@ -298,15 +339,19 @@ int main(int argc, char** argv) {
     } else {
       for (int it = 1; it <= iters; ++it) pathtrace(nullptr, 0, it);  // main.cpp:138-149
     }
-    pathtraceSyncImage();
+    if (adaptive > 0.0f) pt_sync();  // (the resolved image is already in scene->state.image; the SUM image alone means nothing)
+    else pathtraceSyncImage();
     secs = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
-    std::printf("%dx%d, %d spp, depth %d: %.3f s, %.2f Msamples/s\n", W, H, iters, scene->state.traceDepth, secs,
-                (double)W * H * iters / secs / 1e6);
-    if (pt_save_png((base + ".png").c_str(), scene->state.image.data(), W, H, (float)iters) == 0)
+    const double samples_done = adaptive > 0.0f ? (double)adaptive_samples : (double)W * H * iters;
+    // (adaptive: the spp of the file names, ceil(samples / pixels), beside the rate of the samples actually rendered)
+    const int spp_done = adaptive > 0.0f ? (int)((adaptive_samples + (int64_t)W * H - 1) / ((int64_t)W * H)) : iters;
+    std::printf("%dx%d, %d spp, depth %d: %.3f s, %.2f Msamples/s\n", W, H, spp_done, scene->state.traceDepth, secs, samples_done / secs / 1e6);
+    const float image_samples = adaptive > 0.0f ? 1.0f : (float)iters;  // the resolved image is averaged radiance already
+    if (pt_save_png((base + ".png").c_str(), scene->state.image.data(), W, H, image_samples) == 0)
       std::printf("Saved %s.png.\n", base.c_str());
-    if (pfm && pt_save_pfm((base + ".pfm").c_str(), scene->state.image.data(), W, H, (float)iters) == 0)
+    if (pfm && pt_save_pfm((base + ".pfm").c_str(), scene->state.image.data(), W, H, image_samples) == 0)
       std::printf("Saved %s.pfm.\n", base.c_str());
-    if (hdr && pt_save_hdr((base + ".hdr").c_str(), scene->state.image.data(), W, H, (float)iters) == 0)
+    if (hdr && pt_save_hdr((base + ".hdr").c_str(), scene->state.image.data(), W, H, image_samples) == 0)
       std::printf("Saved %s.hdr.\n", base.c_str());
     if (features) {
       std::vector<float> planes((size_t)PT_FEATURE_PLANES * W * H * 4);

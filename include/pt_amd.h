@@ -452,6 +452,83 @@ int pt_denoise_guided_host(int w, int rows, const float* rgb_sum, const float* p
 int pt_denoise_guided_variance_host(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, int groups, int64_t iters,
                                     const PtDenoiseOptions* opt, float* var_raw, float* var_0);
 
+/* ---- adaptive sampling: after a uniform warm-up, further groups of iterations are rendered over the noisiest pixels only.  The
+ * noise estimate above says where the variance is; a ROUND picks the m pixels with the largest (prefiltered) estimate, renders a
+ * group of iterations for those pixels alone and merges the group into the image and the estimate.  From the first round on the
+ * renderer is in the ADAPTIVE STATE (until pt_clear): pixels differ in their sample counts, the SUM image S means something only
+ * together with the per-pixel counts, and pt_resolve gives the averaged radiance.  Selection, merge and resolve are kernels of
+ * their own (csrc/pt_adaptive.hip), specified to the bit like the fold: float32 throughout, every operation a separate IEEE
+ * operation in the order written (no FMA contraction, correctly rounded division, denormals kept), the same in all three PT_ARITH_*
+ * builds, on the host (pt_adaptive_select_host, pt_adaptive_merge_host) and on the device.  The tile must be whole contiguous rows
+ * (W x R), as for pt_denoise.
+ * State: the plane cnt, N x {int32 T_p, int32 M_p} (iterations and groups of pixel p; 8 bytes per pixel), allocated by the first
+ * round together with the selection's workspace (4 B per pixel of keys, 4 B per pixel of list, 24 KiB of histograms, 8 B per 1024
+ * pixels), set to the fold's (T, M) for every pixel by the first round since pt_init / pt_clear; pt_clear frees nothing and zeroes it.
+ * Key, per pixel p before every round, with w_p the estimate in noise plane 0:
+ *   Tf_p = (float)T_p;   s_p = w_p * Tf_p                      (the per-sample variance)
+ *   num = 0, den = 0;  for j = -1, 0, 1 (rows, outer) and i = -1, 0, 1, skipping only taps outside the W x R rectangle:
+ *       g = G[j + 1] * G[i + 1]  with G = 1/4, 1/2, 1/4;   num = num + g * s(q);   den = den + g        (multiply, then add)
+ *   f_p = num / den;   key_p = f_p / Tf_p
+ * The sort key is the uint32 bit pattern of key_p (every value is >= +0, so the order is the float order); a NaN of any sign and
+ * payload becomes 0xffffffff and so sorts first.  The raw w_p, with one to three degrees of freedom behind it, must not be the key:
+ * pixels whose first groups happen to agree would be starved for good (simulated: worse than uniform sampling by 1.2x to 3.7x in MSE);
+ * the 3x3 binomial prefilter is the one pt_denoise_guided applies to its variance for the same reason.
+ * Select: m = clamp(ceil((double)fraction * N), 1, N).  The list holds the m pixels with the largest key, equal keys resolved by
+ * the smaller tile index, stored in ascending tile index.  On the device a radix select (11 / 11 / 10 bits, integer atomics on
+ * histogram bins only) finds the threshold key and the number of pixels equal to it to take, and a counting pass, a scan and a
+ * scatter write the list; no host synchronisation, equal inputs give an equal list.
+ * Render: a worker context owned by the renderer, whose tile is the list (created by the first round, recreated when m changes,
+ * its memory part of PtStats.device_bytes), renders iterations iter_first .. iter_first + G - 1 (global iteration numbers, the RNG
+ * keyed by the global pixel as everywhere) for the listed pixels into a cleared group sum Sw[m][3], with the renderer's arithmetic
+ * mode, scene tables, traversal choice and options; iters_per_batch and num_queues of 0 are automatic for m pixels.  Pixels outside
+ * the list have no sample in those iterations.  PtStats.samples counts the worker's samples; live_rays, the kernel timings and
+ * iters_per_batch stay those of the renderer's own whole-tile launches.
+ * Merge, for i < m with p = list[i], nf = (float)G, per component k:
+ *   b = Sw[i].k;   S_p.k = S_p.k + b;   q_k = q_k + (b * b) / nf;   prev_k = S_p.k
+ * then  T_p += G;  M_p += 1;  Tf = (float)T_p;  Df = (float)(M_p - 1) * Tf;
+ *   d = q_k - (S_k * S_k) / Tf;   v_k = (d > 0 ? d : 0) / Df;   w = (v_x + v_y) + v_z
+ * Pixels outside the list keep every word.  SSE_est = sum of (double)w over ALL tile pixels in the fold's order (one double per
+ * PT_NOISE_PIXELS_PER_PARTIAL consecutive pixels, those in index order), left where a fold leaves it.
+ * Resolve: c_p = S_p / (float)T_p per component, averaged radiance.  Valid in the uniform state too (T_p = T for every pixel);
+ * needs at least one fold and nothing rendered since the last fold.
+ * What to know before relying on it:
+ *   - Sampling by an ESTIMATED variance makes the image a biased estimator: whether a pixel receives more samples depends on the
+ *     samples it already has.  The bias falls with the warm-up length; it is not corrected.
+ *   - The frame statistic turns optimistic under selection: the pixels that underestimate their variance are the ones skipped.
+ *     Simulated on the CPU (cornell 96x54, depth 8, two uniform groups of 4, rounds of 4 over a quarter of the pixels, 32 iterations'
+ *     worth of samples): SSE_est is 0.80 to 0.90 of the actual squared error, 0.5 to 1 dB in the estimated PSNR; measured on an
+ *     MI355X in that configuration (tests/test_gpu_adaptive.py): 0.843, the estimate reading 33.84 dB where the image has 33.10 dB.
+ *   - A pixel whose first two groups agree exactly has w = 0 and is sampled again only through its neighbours' variance (the
+ *     prefilter).  For background and emitter pixels that is the point; a pixel that is noisy but unlucky twice is reached the same way.
+ * Out of scope: pt_group_* (a rank's top m is not the frame's), filtering an adaptive image on the device (pt_ctx_resolve_device is
+ * the hook: pt_denoise and pt_denoise_guided refuse the adaptive state), a list length that varies from round to round, and any
+ * tuning of the path-tracing kernels for incoherent lists.
+ * In the adaptive state pt_readback (S), pt_get_noise (sse = the last merge's, groups = M + rounds, iterations = the highest
+ * iteration number folded or merged), pt_readback_noise, pt_render_features and pt_get_stats still work; pt_render, pt_noise_fold,
+ * pt_render_until, pt_denoise, pt_denoise_guided, pt_save_u8 and pt_preview_rgba8* fail with a message that names pt_resolve and
+ * pt_clear.  A renderer that never calls the functions below behaves, allocates and launches as before. */
+/* One round: key, select, render, merge; asynchronous on the renderer's stream.  Errors, with nothing rendered or allocated: fewer
+ * than 2 groups folded, iterations rendered since the last fold ("fold first"), a striped or ragged tile, PtOptions.convergence != 0,
+ * fraction outside (0, 1], group_iters < 1, iter_first < 1, a failed context. */
+int pt_adaptive_round(int iter_first, int group_iters, float fraction);
+/* pt_render_until with rounds: while fewer than 2 groups are folded, uniform groups of group_iters iterations with a fold each,
+ * exactly as pt_render_until; then rounds of group_iters iterations over the fraction.  group_iters == 0: the worker's iterations
+ * per batch.  One synchronise per group or round; stops after the first estimate above target_db or when max_iters iteration
+ * numbers are used up (the last group is cut).  *iters_done: iteration numbers used; *samples_done: pixel-samples rendered by this
+ * call; *psnr_db: the last estimate, -1 when there is none (any may be NULL). */
+int pt_render_adaptive(int iter_first, int max_iters, int group_iters, float fraction, float target_db, int* iters_done, int64_t* samples_done,
+                       float* psnr_db);
+int pt_readback_adaptive(int32_t* counts); /* pixel_count * 2 int32: T_p, M_p (the uniform state: the fold's T, M); synchronises */
+int pt_resolve(float* rgb_avg_host);       /* pixel_count * 3 floats of averaged radiance; synchronises */
+/* The selection on the host (no GPU): noise_planes as pt_readback_noise gives them (plane 0 is read), counts w*rows * 2 int32 with
+ * every T_p >= 1, 1 <= m <= w*rows; list receives m tile indices.  The device's list equals it. */
+int pt_adaptive_select_host(int w, int rows, const float* noise_planes, const int32_t* counts, int m, int32_t* list);
+/* A merge on the host (no GPU): rgb_sum (S), planes and counts of `pixels` tile pixels are updated in place from group_sum (m * 3
+ * floats, the sums of group_iters iterations of the pixels list[0 .. m), distinct); *sse (may be NULL) = the estimates of all
+ * pixels added in pixel order.  The device's image, planes and counts equal it bit for bit. */
+int pt_adaptive_merge_host(int pixels, float* rgb_sum, float* planes, int32_t* counts, const int32_t* list, int m, const float* group_sum,
+                           int group_iters, double* sse);
+
 /* saveImage()'s per-pixel conversion (main.cpp:91-97 x mirror, image.cpp:26-30 clamp * 255 truncated) on the
  * device: pixel_count*3 bytes, row-major, x mirrored inside each row; the tile must consist of whole rows.
  * Reads back 3 B per pixel instead of 12. */
@@ -486,6 +563,14 @@ int pt_ctx_noise_fold(PtContext* c);
 int pt_ctx_get_noise(PtContext* c, double* sse, int* groups, int* iterations);
 int pt_ctx_readback_noise(PtContext* c, float* planes_host);
 int pt_ctx_render_until(PtContext* c, int iter_first, int max_iters, int group_iters, float target_db, int* iters_done, float* psnr_db);
+int pt_ctx_adaptive_round(PtContext* c, int iter_first, int group_iters, float fraction);
+int pt_ctx_render_adaptive(PtContext* c, int iter_first, int max_iters, int group_iters, float fraction, float target_db, int* iters_done,
+                           int64_t* samples_done, float* psnr_db);
+int pt_ctx_readback_adaptive(PtContext* c, int32_t* counts);
+int pt_ctx_resolve(PtContext* c, float* rgb_avg_host);
+/* Asynchronous on the context's stream; *rgb_dev (pixel_count * 3 floats, owned by the context, allocated by the first resolve) stays
+ * valid until the next resolve: where a later filter of the resolved image can start from. */
+int pt_ctx_resolve_device(PtContext* c, const float** rgb_dev);
 const float* pt_ctx_device_noise(PtContext* c); /* device pointer of plane 0; the planes are contiguous; NULL before the first fold */
 const float* pt_ctx_device_features(PtContext* c); /* device pointer of plane 0; the planes are contiguous; NULL before the first pt_ctx_render_features */
 const float* pt_ctx_device_image(PtContext* c); /* device pointer of the tile SUM image */
@@ -574,6 +659,13 @@ int pt_stage_denoise(int w, int rows, const float* rgb_sum, const float* planes,
 /* The kernels of pt_denoise_guided on caller-supplied host arrays (pt_denoise_guided_host's arguments; rows < 32768). */
 int pt_stage_denoise_guided(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, int groups, int64_t iters,
                             const PtDenoiseOptions* opt, float* rgb_avg);
+
+/* The selection's kernels on caller-supplied host arrays (pt_adaptive_select_host's arguments; rows < 32768). */
+int pt_stage_adaptive_select(int w, int rows, const float* noise_planes, const int32_t* counts, int m, int32_t* list);
+/* The worker context of pt_adaptive_round alone: iterations iter_first .. iter_first + iter_count - 1 of the m listed tile pixels
+ * (distinct, in any order) — rgb_sum_host receives their group sum, m * 3 floats in list order: bit for bit the listed rows of what
+ * pt_render adds to the image for the same iterations.  Changes neither the image nor the folds nor the state of the renderer. */
+int pt_stage_render_list(const int32_t* list, int m, int iter_first, int iter_count, float* rgb_sum_host);
 
 /* ---- image output (src/image.cpp:22-45, src/main.cpp:86-107) ------------- */
 /* rgb_sum: W*H*3 floats (raw orientation); writes <path> as 8-bit PNG of
