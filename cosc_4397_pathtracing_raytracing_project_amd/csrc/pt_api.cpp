@@ -1,33 +1,24 @@
 // pt_api.cpp — C ABI (include/pt_amd.h) and device-state owner of the MI355X
 // wavefront path tracer.  Host C++ calling the HIP runtime directly; replaces the
 // reference's pathtraceInit / pathtrace / pathtraceFree (src/pathtrace.cu:446-653).
+// Here: the error state, a context's lifecycle, run_batch, readback, the scene functions and the single-instance API; pt_post.cpp is
+// what reads or extends a rendered image, pt_stage.cpp the tests' stages, pt_context.h the context and the helpers the three share.
 //
 // Differences from the reference's host loop by design:
 //   * no host<->device synchronisation inside an iteration (the reference does ~38),
 //     no per-iteration malloc/free, no per-iteration D2H frame copies or printf;
 //   * K iterations are traced as one wavefront batch so each launch has enough rays;
 //   * kernel sizes are fixed (persistent grid), live counts stay on the device.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
 #include <cmath>
 #include <cstdarg>
-#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <string>
-#include <vector>
 
-#include "../../include/pt_amd.h"
 #include "pt_adaptive.h"
-#include "pt_denoise.h"
-#include "pt_device.h"
-#include "pt_internal.h"
-#include "pt_kernels.h"
-#include "pt_noise.h"
+#include "pt_context.h"
 #include "pt_scene.h"
 #include "pt_sched.h"
-#include "pt_tables.h"
 
 namespace {
 
@@ -45,133 +36,10 @@ int pt_fail(const char* fmt, ...) {  // pt_internal.h: sets pt_last_error(), ret
   g_err = buf;
   return -1;
 }
-namespace {
-#define fail pt_fail
-#define HIP_OK(expr)                                                                                   \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) return fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
 
-struct EventPair {
-  hipEvent_t a, b;
-};
-
-}  // namespace
-
-// One renderer instance = one device, one stream, one tile of the framebuffer.  The reference keeps this state in
-// file-scope statics (pathtrace.cu:446-456); here it is an object so that one process can drive several GPUs
-// (pt_group_*, pt_group.cpp) — the old single-instance entry points act on a default context.
-struct PtContext {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  const ptk::KernelApi* k = nullptr;  // kernels of the selected arithmetic mode
-  int arith = 0;
-  // scene
-  PtCamera cam{};
-  ptd::Camera dcam{};
-  int depth = 0;
-  // tile / batch geometry
-  int N = 0, pixel_begin = 0, K = 1;
-  int slot_shift = 0;  // BatchInfo::slot_shift
-  int stripe = 0, stripe_stride = 0;
-  int num_cus = 0, grid = 0;  // grid: widest persistent grid (stats / test stages)
-  int grid_gen = 0, grid_isect = 0, grid_shade = 0;
-  ptd::Queues qs{};
-  int64_t stride = 0;  // plane stride = Q*cap
-  // device memory
-  std::vector<void*> allocs;
-  int64_t device_bytes = 0;
-  ptk::SceneTables scene{};  // what upload_tables() put on the device; tables() adds the fields that options and launches decide
-  int lds_table_bytes = -1;        // SceneTables::lds_table_bytes
-  int lds_table_forced = -1;       // PtOptions.lds_table_kb in bytes; -1: KernelApi::lds_table_limit decides
-  int primary_pieces = 0;          // BatchInfo::primary_pieces forced by PtOptions.primary_pieces; 0: run_batch decides
-  int primary_share = 0;           // BatchInfo::primary_share forced through PT_PRIMARY_PIECES; 0: automatic (primary_share_of)
-  int paths_pieces = 0;            // BatchInfo::paths_pieces (PtOptions.paths_pieces, paths_min_piece)
-  // Uniform grids over the leaf boxes (pt::build_grid; SceneTables::grid_*), large scenes where one beats the BVH scan: setup()
-  // uploads the candidates of pt::build_scene_tables, choose_traversal() times them, keeps the fastest and frees the rest.
-  struct DeviceGrid {
-    pt::GridShape shape;
-    size_t guard;  // empty cells in front of (and behind) the cell table proper
-    const uint32_t* d_start;
-    const ptd::Node* d_items;
-    const ptd::Node* d_items_b;  // == d_items unless the build wants centre / half extent
-    size_t bytes;
-  };
-  std::vector<DeviceGrid> grids;
-  size_t grid_pick = 0;  // grids[grid_pick] is the one the kernels walk (when grids is not empty)
-  int tight_leaves = 0;  // sphere leaves with a tightened traversal box (pt::tighten_sphere_leaves)
-  bool grid_enabled = true;      // the outcome of choose_traversal()
-  float probe_ms[2] = {0.f, 0.f};  // a few iterations with the BVH scan / with the (fastest) grid, as timed by choose_traversal()
-  int cap_bpc = 8;
-  bool legacy = false;
-  int debug_flags = 0;
-  bool fuse_primary = true, fuse_bounces = true;
-  bool aa_jitter = false;
-  int grid_primary = 0, grid_paths = 0;
-  ptd::PathBuf buf[2]{};
-  ptd::HitBuf hits{};
-  ptd::RetireBuf ret{};  // retirement records + fill levels (pt_device.h)
-  float* d_image = nullptr;
-  // First-hit feature buffers (pt_ctx_render_features): PT_FEATURE_PLANES planes of N float4 sums; absent until the first feature pass
-  float4* d_feat = nullptr;
-  int grid_features = 0;
-  void* d_denoise = nullptr;  // workspace of pt_ctx_denoise (pt_denoise_workspace_bytes(N)); absent until the first denoise call
-  // Noise estimate (pt_ctx_noise_fold, csrc/pt_noise.hip): planes, partial sums and their sum (pt_noise_state_bytes(N)); absent until the first fold
-  void* d_noise = nullptr;
-  int noise_groups = 0;      // M: folds since pt_init / pt_clear that had something to fold
-  int64_t noise_iters = 0;   // T: iterations those folds took
-  int64_t rendered = 0;      // iterations handed to pt_ctx_render since pt_init / pt_clear (samples is zeroed by pt_reset_stats; setup()'s timing batches never count)
-  // Convergence metric (PtOptions.convergence, pt_kernels.h ConvInfo): all of it absent when the option is 0
-  int conv = 0;                // the option: N > 0 capture the frame at iteration N, -1 supplied
-  bool conv_live = false;      // off while setup() renders its timing batches: they leave no trace in the curve or the frame
-  bool conv_have_ref = false;  // d_ref holds the frame (supplied, or the batch that captures it has been submitted)
-  int conv_last = 0;           // highest iteration submitted with the metric on
-  float* d_ref = nullptr;      // [N][3]
-  double* d_partial = nullptr;  // [K][Q][kConvWaves]
-  double* d_sse = nullptr;      // [PT_CONVERGENCE_CAPACITY], iteration i at i - 1; all bits set (a NaN) = no value
-  uint8_t* d_rgb8 = nullptr;  // lazily allocated output of pt_ctx_save_u8
-  int32_t* d_cnt = nullptr;
-  unsigned long long* d_stats = nullptr;
-  // timing
-  bool time_kernels = false;
-  std::vector<EventPair> free_events, pending_isect, pending_render;
-  double isect_ms = 0, render_ms = 0;
-  int64_t isect_launches = 0;
-  int64_t samples = 0;
-  // A batch that failed half-way (a launch or an event call returned an error) leaves counters and record regions in an
-  // undefined state: the context refuses further renders instead of appending past them.
-  bool failed = false;
-  // Adaptive sampling (pt_ctx_adaptive_round, csrc/pt_adaptive.hip): all of it absent until the first round (d_list and the worker: or
-  // until pt_stage_render_list)
-  int opt_iters_per_batch = 0, opt_num_queues = 0;  // PtOptions, as given: a worker plans its own batches from them
-  bool borrowed = false;           // a worker context: device, stream, scene tables and grids belong to its parent
-  const int32_t* list = nullptr;   // BatchInfo::list of this context's batches (a worker's: the parent's d_list)
-  PtContext* worker = nullptr;     // the context that renders the pixel list; its tile is the list's m pixels, its d_image the group sum Sw
-  int32_t* d_list = nullptr;       // N entries, the first worker->N in use
-  void* d_acnt = nullptr;          // the plane cnt: N * ptad::Cnt
-  void* d_select = nullptr;        // pt_adaptive_select_bytes(N)
-  float* d_resolved = nullptr;     // [N][3], output of pt_ctx_resolve_device; absent until the first resolve
-  bool adaptive = false;           // the adaptive state: from the first round to pt_clear
-  int adaptive_rounds = 0;
-  int64_t adaptive_last = 0;       // highest iteration number folded or merged
-};
-
-namespace {
-using Ctx = PtContext;
-Ctx* g_default = nullptr;  // the instance behind pt_init / pt_render / pt_free
-
-template <typename T>
-int dalloc(Ctx& g, T** out, size_t count) {
-  void* p = nullptr;
-  size_t bytes = std::max<size_t>(count * sizeof(T), 16);
-  hipError_t e = hipMalloc(&p, bytes);
-  if (e != hipSuccess) return fail("hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
-  g.allocs.push_back(p);
-  g.device_bytes += (int64_t)bytes;
-  *out = reinterpret_cast<T*>(p);
-  return 0;
-}
+namespace ptc {
+static PtContext* g_default = nullptr;
+PtContext* default_context() { return g_default; }
 
 int get_events(Ctx& g, EventPair* ev) {
   if (!g.free_events.empty()) {
@@ -183,23 +51,19 @@ int get_events(Ctx& g, EventPair* ev) {
   HIP_OK(hipEventCreate(&ev->b));
   return 0;
 }
-int resolve_events(Ctx& g) {  // requires the stream to be idle
-  for (auto& e : g.pending_isect) {
-    float ms = 0;
-    HIP_OK(hipEventElapsedTime(&ms, e.a, e.b));
-    g.isect_ms += ms;
-    g.isect_launches++;
-    g.free_events.push_back(e);
-  }
-  g.pending_isect.clear();
-  for (auto& e : g.pending_render) {
-    float ms = 0;
-    HIP_OK(hipEventElapsedTime(&ms, e.a, e.b));
-    g.render_ms += ms;
-    g.free_events.push_back(e);
-  }
-  g.pending_render.clear();
-  return 0;
+static int resolve_events(Ctx& g) {  // requires the stream to be idle
+  auto drain = [&](std::vector<EventPair>& pending, double& total_ms) -> int {
+    for (auto& e : pending) {
+      float ms = 0;
+      HIP_OK(hipEventElapsedTime(&ms, e.a, e.b));
+      total_ms += ms;
+      g.free_events.push_back(e);
+    }
+    pending.clear();
+    return 0;
+  };
+  g.isect_launches += (int64_t)g.pending_isect.size();
+  return drain(g.pending_isect, g.isect_ms) || drain(g.pending_render, g.render_ms) ? -1 : 0;
 }
 
 ptk::SceneTables tables(const Ctx& g) {
@@ -225,23 +89,19 @@ ptk::SceneTables tables(const Ctx& g) {
   return t;
 }
 
-size_t pathbuf_words(int64_t stride) { return (size_t)(2 * stride + (stride * ptd::kPathPlane2Bytes + 15) / 16); }
-int alloc_pathbuf(Ctx& g, ptd::PathBuf* b, int64_t stride) {
+static size_t pathbuf_words(int64_t stride) { return (size_t)(2 * stride + (stride * ptd::kPathPlane2Bytes + 15) / 16); }
+static int alloc_pathbuf(Ctx& g, ptd::PathBuf* b, int64_t stride) {
   b->stride = stride;
   // planes 0 and 1: 16 bytes per path, plane 2: kPathPlane2Bytes (pt_device.h); allocated in 16-byte words
   return dalloc(g, &b->r, pathbuf_words(stride));
 }
-int alloc_hitbuf(Ctx& g, ptd::HitBuf* h, int64_t stride) {
+static int alloc_hitbuf(Ctx& g, ptd::HitBuf* h, int64_t stride) {
   h->stride = stride;
-  if (dalloc(g, &h->t, stride)) return -1;
-  if (dalloc(g, &h->n, 3 * stride)) return -1;
-  if (dalloc(g, &h->mat, stride)) return -1;
-  if (dalloc(g, &h->p, 3 * stride)) return -1;
-  return 0;
+  return dalloc(g, &h->t, stride) || dalloc(g, &h->n, 3 * stride) || dalloc(g, &h->mat, stride) || dalloc(g, &h->p, 3 * stride) ? -1 : 0;
 }
 
 // Queue descriptor for a launch of `grid` workgroups (W = waves of THAT launch; Q, cap shared).
-ptd::Queues queues_for(const Ctx& g, int grid) {
+static ptd::Queues queues_for(const Ctx& g, int grid) {
   ptd::Queues q = g.qs;
   q.W = grid * ptk::kWavesPerBlock;
   return q;
@@ -250,18 +110,26 @@ ptd::Queues queues_for(const Ctx& g, int grid) {
 // BatchInfo::primary_share of the context's batches: debug_flags 128 and a primary_share of 1 both mean a trace per iteration;
 // automatic: the longest run, a whole piece per trace (on the whole frame caps of 8 to 64 iterations measure alike, 4 is 0.5 %
 // slower: profiles/first_hit_sharing.log section 2b).
-int primary_share_of(const Ctx& g) { return (g.debug_flags & 128) ? 1 : g.primary_share ? g.primary_share : ptk::kShareMax; }
-bool shares_first_hit(const Ctx& g) { return ptk::primary_shares(primary_share_of(g), g.aa_jitter, !g.fuse_bounces); }
+static int primary_share_of(const Ctx& g) { return (g.debug_flags & 128) ? 1 : g.primary_share ? g.primary_share : ptk::kShareMax; }
+static bool shares_first_hit(const Ctx& g) { return ptk::primary_shares(primary_share_of(g), g.aa_jitter, !g.fuse_bounces); }
 
-int run_batch(Ctx& g, int iter_first, int kb) {
+ptk::BatchInfo tile_batch(const Ctx& g, int iter_first, int K) {
   ptk::BatchInfo b{};
   b.iter_first = iter_first;
-  b.K = kb;
+  b.K = K;
   b.N = g.N;
   b.pixel_begin = g.pixel_begin;
   b.trace_depth = g.depth;
-  b.slot_shift = g.slot_shift;
   b.aa_jitter = g.aa_jitter ? 1 : 0;
+  b.stripe = g.stripe;
+  b.gap = g.stripe ? g.stripe_stride - g.stripe : 0;
+  b.inv_stripe = g.stripe ? 1.0f / (float)g.stripe : 0.0f;
+  return b;
+}
+
+int run_batch(Ctx& g, int iter_first, int kb) {
+  ptk::BatchInfo b = tile_batch(g, iter_first, kb);
+  b.slot_shift = g.slot_shift;
   b.flat = g.fuse_bounces ? 0 : 1;
   b.primary_share = primary_share_of(g);
   b.primary_pieces = g.primary_pieces ? g.primary_pieces
@@ -269,9 +137,6 @@ int run_batch(Ctx& g, int iter_first, int kb) {
   b.paths_pieces = g.paths_pieces;
   b.retire_once = ptk::retires_once(b, g.debug_flags) ? 1 : 0;  // (every batch of the context, the timing batches of choose_traversal among them)
   b.split_records = ptk::splits_records(b, g.debug_flags) ? 1 : 0;  // (likewise; the unfused kernels' batches are flat: whole records)
-  b.stripe = g.stripe;
-  b.gap = g.stripe ? g.stripe_stride - g.stripe : 0;
-  b.inv_stripe = g.stripe ? 1.0f / (float)g.stripe : 0.0f;
   b.list = g.list;
   if (b.list) b.stripe = 1, b.gap = 0, b.inv_stripe = 1.0f;  // (BatchInfo::list: the list form sits behind the stripe test)
   const ptk::SceneTables sc = tables(g);
@@ -289,32 +154,31 @@ int run_batch(Ctx& g, int iter_first, int kb) {
   int src = d0 & 1;
   // Depths >= 1, fused: ONE launch of k_paths — persistent lanes with their own depth, no path state through HBM after depth 0
   const bool all_depths = g.grid_paths > 0;
+  EventPair ev{};  // brackets the dominant kernel of a depth (fused: of all depths) when the context times its kernels
+  auto timed_from = [&]() -> int {
+    if (!g.time_kernels) return 0;
+    if (get_events(g, &ev)) return -1;
+    HIP_OK(hipEventRecord(ev.a, g.stream));
+    return 0;
+  };
+  auto timed_to = [&]() -> int {
+    if (!g.time_kernels) return 0;
+    HIP_OK(hipEventRecord(ev.b, g.stream));
+    g.pending_isect.push_back(ev);
+    return 0;
+  };
   if (all_depths) {
-    EventPair ev{};
-    if (g.time_kernels) {
-      if (get_events(g, &ev)) return -1;
-      HIP_OK(hipEventRecord(ev.a, g.stream));
-    }
+    if (timed_from()) return -1;
     k.paths(g.stream, g.grid_paths, sc, b, queues_for(g, g.grid_paths), g.d_cnt, g.buf[1], g.ret);
-    if (g.time_kernels) {
-      HIP_OK(hipEventRecord(ev.b, g.stream));
-      g.pending_isect.push_back(ev);
-    }
+    if (timed_to()) return -1;
   }
   // ... unfused (tests, A/B): computeIntersections and shadeAndExtendRays as separate launches per depth
   for (int d = d0; d < g.depth && !all_depths; ++d) {
     const int32_t* cin = cnt_row(d);
     int32_t* cout = cnt_row(d + 1);
-    EventPair ev{};
-    if (g.time_kernels) {  // brackets the dominant kernel of this depth
-      if (get_events(g, &ev)) return -1;
-      HIP_OK(hipEventRecord(ev.a, g.stream));
-    }
+    if (timed_from()) return -1;
     k.intersect(g.stream, g.grid_isect, sc, queues_for(g, g.grid_isect), cin, g.buf[src], g.hits, g.legacy, d == 0);
-    if (g.time_kernels) {
-      HIP_OK(hipEventRecord(ev.b, g.stream));
-      g.pending_isect.push_back(ev);
-    }
+    if (timed_to()) return -1;
     k.shade(g.stream, g.grid_shade, sc, b, d, queues_for(g, g.grid_shade), cin, cout, g.buf[src], g.hits, g.buf[src ^ 1], g.ret);
     src ^= 1;
   }
@@ -354,7 +218,7 @@ void plan_launch(Ctx& g) {
 // scenes — so it is measured: up to 8 iterations of the context's own tile with each (the second of two runs counts), before
 // the first sample is rendered.  Costs a few tens of milliseconds per candidate for a 1080p tile.  debug_flags 256 / 512 skip
 // the measurement.
-int choose_traversal(Ctx& g) {
+static int choose_traversal(Ctx& g) {
   auto drop_unused_grids = [&](size_t keep) {
     for (size_t i = 0; i < g.grids.size(); ++i) {
       const Ctx::DeviceGrid& d = g.grids[i];
@@ -411,19 +275,6 @@ int choose_traversal(Ctx& g) {
   return 0;
 }
 
-struct Scratch {  // frees on scope exit
-  std::vector<void*> p;
-  ~Scratch() {
-    for (void* q : p) (void)hipFree(q);
-  }
-  template <typename T>
-  T* get(size_t n) {
-    void* q = nullptr;
-    if (hipMalloc(&q, std::max<size_t>(n * sizeof(T), 16)) != hipSuccess) return nullptr;
-    p.push_back(q);
-    return reinterpret_cast<T*>(q);
-  }
-};
 ptd::Queues single_queue(const Ctx& g, int n) {
   ptd::Queues qs{};
   qs.Q = 1;
@@ -457,18 +308,18 @@ void destroy(Ctx* c) {
 }
 
 // The device, its stream and the kernels of the arithmetic mode.
-int open_device(Ctx& g, const PtOptions& opt) {
+static int open_device(Ctx& g, const PtOptions& opt) {
   g.arith = opt.arith;
   g.k = ptk::api_for(opt.arith);
-  if (!g.k) return fail("pt_init: arith %d is not one of PT_ARITH_EXACT / PT_ARITH_FMA / PT_ARITH_FAST", opt.arith);
-  if (opt.convergence < -1) return fail("pt_init: convergence %d is not 0 (off), N > 0 (frame captured at iteration N) or -1 (frame supplied)", opt.convergence);
-  if (opt.convergence > PT_CONVERGENCE_CAPACITY) return fail("pt_init: convergence %d exceeds PT_CONVERGENCE_CAPACITY (%d iterations)", opt.convergence, PT_CONVERGENCE_CAPACITY);
-  if (opt.primary_pieces > 0 && (opt.primary_pieces >> 16) > ptk::kShareMax) return fail("pt_init: primary_pieces 0x%x: primary_share %d exceeds %d (PT_PRIMARY_PIECES)", opt.primary_pieces, opt.primary_pieces >> 16, ptk::kShareMax);
-  if (opt.debug_flags & ~kDebugFlags) return fail("pt_init: debug_flags 0x%x: bits 0x%x are not defined", opt.debug_flags, opt.debug_flags & ~kDebugFlags);
+  if (!g.k) return pt_fail("pt_init: arith %d is not one of PT_ARITH_EXACT / PT_ARITH_FMA / PT_ARITH_FAST", opt.arith);
+  if (opt.convergence < -1) return pt_fail("pt_init: convergence %d is not 0 (off), N > 0 (frame captured at iteration N) or -1 (frame supplied)", opt.convergence);
+  if (opt.convergence > PT_CONVERGENCE_CAPACITY) return pt_fail("pt_init: convergence %d exceeds PT_CONVERGENCE_CAPACITY (%d iterations)", opt.convergence, PT_CONVERGENCE_CAPACITY);
+  if (opt.primary_pieces > 0 && (opt.primary_pieces >> 16) > ptk::kShareMax) return pt_fail("pt_init: primary_pieces 0x%x: primary_share %d exceeds %d (PT_PRIMARY_PIECES)", opt.primary_pieces, opt.primary_pieces >> 16, ptk::kShareMax);
+  if (opt.debug_flags & ~kDebugFlags) return pt_fail("pt_init: debug_flags 0x%x: bits 0x%x are not defined", opt.debug_flags, opt.debug_flags & ~kDebugFlags);
   int ndev = 0;
   HIP_OK(hipGetDeviceCount(&ndev));
-  if (ndev <= 0) return fail("pt_init: no HIP device (this library has no CPU fallback)");
-  if (opt.device < 0 || opt.device >= ndev) return fail("pt_init: device %d of %d", opt.device, ndev);
+  if (ndev <= 0) return pt_fail("pt_init: no HIP device (this library has no CPU fallback)");
+  if (opt.device < 0 || opt.device >= ndev) return pt_fail("pt_init: device %d of %d", opt.device, ndev);
   g.device = opt.device;
   HIP_OK(hipSetDevice(g.device));
   hipDeviceProp_t prop;
@@ -479,7 +330,7 @@ int open_device(Ctx& g, const PtOptions& opt) {
 }
 
 // The camera, the scene's sizes and the options that choose kernels and schedules.
-void take_scene_and_options(Ctx& g, const PtSceneDesc* sc, const PtOptions& opt) {
+static void take_scene_and_options(Ctx& g, const PtSceneDesc* sc, const PtOptions& opt) {
   g.cam = sc->camera;
   g.depth = sc->trace_depth;
   g.dcam.res_x = g.cam.resolution[0], g.dcam.res_y = g.cam.resolution[1];
@@ -515,7 +366,7 @@ int batch_iters_for(int iters_per_batch, int N, int* slot_shift) {
   // sample ids are k << slot_shift | tile pixel in 31 bits (BatchInfo::slot_shift)
   int shift = 1;
   while ((1ll << shift) < N) ++shift;
-  if (shift > 30) return fail("pt_init: tiles of more than 2^30 pixels are not supported");
+  if (shift > 30) return pt_fail("pt_init: tiles of more than 2^30 pixels are not supported");
   while (K > 1 && K > (1 << (31 - shift))) --K;
   if (slot_shift) *slot_shift = shift;
   return K;
@@ -529,15 +380,15 @@ int plan_batches(Ctx& g, const PtOptions& opt) {
   g.N = opt.pixel_count > 0 ? opt.pixel_count : W * H - opt.pixel_begin;
   g.stripe = opt.stripe_pixels;
   g.stripe_stride = opt.stripe_stride;
-  if (g.stripe < 0 || (g.stripe > 0 && g.stripe_stride < g.stripe)) return fail("pt_init: bad stripe %d / stride %d", g.stripe, g.stripe_stride);
+  if (g.stripe < 0 || (g.stripe > 0 && g.stripe_stride < g.stripe)) return pt_fail("pt_init: bad stripe %d / stride %d", g.stripe, g.stripe_stride);
   {
     // last global pixel the tile touches
     int64_t last = (int64_t)g.pixel_begin + g.N - 1;
     if (g.stripe > 0) last = (int64_t)g.pixel_begin + (g.N - 1) + (int64_t)((g.N - 1) / g.stripe) * (g.stripe_stride - g.stripe);
     if (g.pixel_begin < 0 || g.N <= 0 || last >= (int64_t)W * H)
-      return fail("pt_init: tile [%d, +%d, stripe %d/%d) outside %dx%d", opt.pixel_begin, opt.pixel_count, g.stripe, g.stripe_stride, W, H);
-    if (g.stripe > 0 && g.N / g.stripe >= 32768) return fail("pt_init: more than 32767 stripes");
-    if (H >= 32768) return fail("pt_init: image height %d not supported (>= 32768)", H);
+      return pt_fail("pt_init: tile [%d, +%d, stripe %d/%d) outside %dx%d", opt.pixel_begin, opt.pixel_count, g.stripe, g.stripe_stride, W, H);
+    if (g.stripe > 0 && g.N / g.stripe >= 32768) return pt_fail("pt_init: more than 32767 stripes");
+    if (H >= 32768) return pt_fail("pt_init: image height %d not supported (>= 32768)", H);
   }
   const int K = batch_iters_for(opt.iters_per_batch, g.N, &g.slot_shift);
   if (K < 0) return -1;
@@ -571,14 +422,14 @@ int plan_batches(Ctx& g, const PtOptions& opt) {
 
 // A device copy of `v`; nullptr after a failure.
 template <typename T>
-const T* upload(Ctx& g, const std::vector<T>& v) {
+static const T* upload(Ctx& g, const std::vector<T>& v) {
   T* p = nullptr;
   if (dalloc(g, &p, v.size())) return nullptr;
   const hipError_t e = hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-  return e == hipSuccess ? p : (fail("hipMemcpy(%zu bytes) failed: %s", v.size() * sizeof(T), hipGetErrorString(e)), nullptr);
+  return e == hipSuccess ? p : (pt_fail("hipMemcpy(%zu bytes) failed: %s", v.size() * sizeof(T), hipGetErrorString(e)), nullptr);
 }
 // What pt::build_scene_tables built, on the device (g.scene), the grids as candidates for choose_traversal().
-int upload_tables(Ctx& g, const pt::HostTables& t) {
+static int upload_tables(Ctx& g, const pt::HostTables& t) {
   ptk::SceneTables& s = g.scene;
   s.num_nodes = (int)t.nodes.size(), s.num_geoms = (int)t.geoms.size(), s.num_mats = (int)t.mats.size(), s.num_top = (int)t.top.size();
   std::memcpy(s.root_min, t.root_min, 12);
@@ -602,7 +453,7 @@ int upload_tables(Ctx& g, const pt::HostTables& t) {
 }
 
 // Every retirement record slot := (quiet NaN, NaN, NaN, tile pixel chunk_pixel(q, 0, Q) of the slot's queue q); see alloc_batch_buffers.
-__global__ void k_poison_records(ptd::Word4* rec, unsigned long long per_queue, unsigned long long total, int Q) {
+static __global__ void k_poison_records(ptd::Word4* rec, unsigned long long per_queue, unsigned long long total, int Q) {
   const float nan = __builtin_nanf("");
   for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (unsigned long long)gridDim.x * blockDim.x)
     rec[i] = ptd::Word4{nan, nan, nan, __int_as_float(ptk::chunk_pixel((int)(i / per_queue), 0, Q))};
@@ -620,7 +471,9 @@ int alloc_batch_buffers(Ctx& g) {
   {
     const size_t regions = (size_t)Q * g.ret.kmax;
     const size_t wq_max = ptk::sub_stride(g.num_cus * 8 * ptk::kWavesPerBlock, Q);  // (8 resident workgroups per CU at the most)
-    if (dalloc(g, &g.ret.rec, regions * g.ret.seg_cap) || dalloc(g, &g.ret.cnt, regions) || dalloc(g, &g.ret.sub, regions * wq_max)) return -1;
+    if (dalloc(g, &g.ret.rec, regions * g.ret.seg_cap)) return -1;
+    // the fill levels start at zero; k_collect re-zeroes them after every batch
+    if (ensure(g, g.ret.cnt, regions * sizeof(*g.ret.cnt), Zero::blocking) || ensure(g, g.ret.sub, regions * wq_max * sizeof(*g.ret.sub), Zero::blocking)) return -1;
     // In a BatchInfo::retire_once batch nobody writes the retiree slots at the front of the regions k >= 1, and later they hold an older
     // batch's identical records: a gather that wrongly read them would still produce the right image.  So every slot starts as
     // (NaN, NaN, NaN, first pixel of the slot's queue) — a wrongly gathered slot then shows in the first batch of a context.
@@ -630,38 +483,30 @@ int alloc_batch_buffers(Ctx& g) {
                          (unsigned long long)per_queue, (unsigned long long)(regions * g.ret.seg_cap), Q);
       HIP_OK(hipGetLastError());
     }
-    HIP_OK(hipMemset(g.ret.cnt, 0, regions * sizeof(unsigned long long)));  // k_collect re-zeroes them after every batch
-    HIP_OK(hipMemset(g.ret.sub, 0, regions * wq_max * sizeof(unsigned long long)));
   }
-  if (dalloc(g, &g.d_image, 3 * (size_t)g.N)) return -1;
-  const size_t cnt_words = ptk::cnt_index(g.qs, g.depth + 1, 0);  // rows 0 .. depth
-  if (dalloc(g, &g.d_cnt, cnt_words)) return -1;
-  HIP_OK(hipMemset(g.d_cnt, 0, cnt_words * sizeof(int32_t)));  // k_count_stats re-zeroes it after every batch
-  if (dalloc(g, &g.d_stats, PT_MAX_DEPTH)) return -1;
-  if (!(g.debug_flags & 64)) {  // (64: W / Q waves per queue in every batch; same image)
-    const size_t deal_words = (size_t)ptk::deal_map(g.qs).words();
-    if (dalloc(g, &g.qs.deal, deal_words)) return -1;
-    HIP_OK(hipMemset(g.qs.deal, 0, deal_words * sizeof(int32_t)));  // nothing measured yet: W / Q each
-  }
+  const size_t image_bytes = 3 * (size_t)g.N * sizeof(float);
+  const size_t cnt_words = ptk::cnt_index(g.qs, g.depth + 1, 0);  // rows 0 .. depth; k_count_stats re-zeroes them after every batch
+  if (ensure(g, g.d_image, image_bytes, Zero::blocking) || ensure(g, g.d_cnt, cnt_words * sizeof(int32_t), Zero::blocking) ||
+      ensure(g, g.d_stats, PT_MAX_DEPTH * sizeof(*g.d_stats), Zero::blocking))
+    return -1;
+  // (debug_flags 64: W / Q waves per queue in every batch; same image)  zero: nothing measured yet, W / Q each
+  if (!(g.debug_flags & 64) && ensure(g, g.qs.deal, (size_t)ptk::deal_map(g.qs).words() * sizeof(int32_t), Zero::blocking)) return -1;
   if (g.conv) {
-    const size_t partials = (size_t)g.K * Q * ptk::kConvWaves;
-    if (dalloc(g, &g.d_ref, 3 * (size_t)g.N) || dalloc(g, &g.d_partial, partials) || dalloc(g, &g.d_sse, (size_t)PT_CONVERGENCE_CAPACITY)) return -1;
-    HIP_OK(hipMemset(g.d_ref, 0, 3 * (size_t)g.N * sizeof(float)));
-    HIP_OK(hipMemset(g.d_partial, 0, partials * sizeof(double)));  // queues without pixels never write theirs
+    const size_t partials = (size_t)g.K * Q * ptk::kConvWaves;  // zero: queues without pixels never write theirs
+    if (ensure(g, g.d_ref, image_bytes, Zero::blocking) || ensure(g, g.d_partial, partials * sizeof(double), Zero::blocking)) return -1;
+    if (dalloc(g, &g.d_sse, (size_t)PT_CONVERGENCE_CAPACITY)) return -1;
     HIP_OK(hipMemset(g.d_sse, 0xff, (size_t)PT_CONVERGENCE_CAPACITY * sizeof(double)));
   }
-  HIP_OK(hipMemset(g.d_image, 0, 3 * (size_t)g.N * sizeof(float)));
-  HIP_OK(hipMemset(g.d_stats, 0, PT_MAX_DEPTH * sizeof(unsigned long long)));
   HIP_OK(hipDeviceSynchronize());
   return 0;
 }
 
 // pathtraceInit (pathtrace.cu:462-516) for one context.  Any failure leaves nothing behind: the caller destroys `g`.
-int setup(Ctx& g, const PtSceneDesc* sc, const PtOptions& opt) {
+static int setup(Ctx& g, const PtSceneDesc* sc, const PtOptions& opt) {
   if (open_device(g, opt)) return -1;
   take_scene_and_options(g, sc, opt);
   if (plan_batches(g, opt)) return -1;
-  if ((size_t)sc->num_materials * sizeof(ptd::Mat) > 60 * 1024) return fail("pt_init: %zu materials exceed the LDS table", (size_t)sc->num_materials);
+  if ((size_t)sc->num_materials * sizeof(ptd::Mat) > 60 * 1024) return pt_fail("pt_init: %zu materials exceed the LDS table", (size_t)sc->num_materials);
   const pt::HostTables host = pt::build_scene_tables(*sc, g.debug_flags, g.k->boxes_center_half != 0);
   if (upload_tables(g, host)) return -1;
   plan_launch(g);
@@ -671,22 +516,25 @@ int setup(Ctx& g, const PtSceneDesc* sc, const PtOptions& opt) {
   return 0;
 }
 
-int need(const PtContext* c, const char* who) {
-  if (!c) return fail("%s: pt_init has not been called", who);
+int need(const PtContext* c, const char* who) { return c ? 0 : pt_fail("%s: pt_init has not been called", who); }
+
+int admit(const PtContext& g, const char* who, unsigned req) {
+  if ((req & kNotFailed) && g.failed) return pt_fail("%s: an earlier batch of this context failed (%s); free it and create a new one", who, g_err.c_str());
+  // what reads the image as "SUM over one number of samples" has no meaning once pixels differ in their sample counts
+  if ((req & kUniform) && g.adaptive)
+    return pt_fail("%s: the renderer is in the adaptive state (pt_adaptive_round): one sample count no longer describes the image; read it with pt_resolve, or "
+                   "return to the uniform state with pt_clear", who);
+  const int W = g.cam.resolution[0];
+  if ((req & kWholeRows) && (g.stripe || g.pixel_begin % W || g.N % W))
+    return pt_fail("%s: the tile must consist of whole contiguous image rows (begin %d, count %d, stripe %d, width %d)", who, g.pixel_begin, g.N, g.stripe, W);
+  if ((req & kFoldedAll) && g.rendered != g.noise_iters)
+    return pt_fail("%s: %lld iteration(s) rendered since the last fold; fold first (pt_noise_fold)", who, (long long)(g.rendered - g.noise_iters));
+  if (req & kOnDevice) HIP_OK(hipSetDevice(g.device));
   return 0;
 }
 
-// What reads the image as "SUM over one number of samples" has no meaning once pixels differ in their sample counts.
-int refuse_adaptive(const PtContext& g, const char* who) {
-  if (!g.adaptive) return 0;
-  return fail("%s: the renderer is in the adaptive state (pt_adaptive_round): one sample count no longer describes the image; read it with pt_resolve, or "
-              "return to the uniform state with pt_clear", who);
-}
-
-}  // namespace
-
-// pt_internal.h (pt_group_denoise_guided: the group refuses what its contexts would refuse, before anything is exchanged)
-int64_t pt_ctx_unfolded_iterations(const PtContext* c) { return c ? c->rendered - c->noise_iters : 0; }
+}  // namespace ptc
+using namespace ptc;
 
 extern "C" {
 
@@ -694,7 +542,7 @@ const char* pt_last_error(void) { return g_err.c_str(); }
 
 int pt_selfcheck_ieee(int arith, int kind, uint64_t first, uint64_t count, uint32_t seed, uint64_t* mismatches) {
   const ptk::KernelApi* k = ptk::api_for(arith);
-  if (!k || kind < 0 || kind > 4 || !mismatches) return fail("pt_selfcheck_ieee: bad argument");
+  if (!k || kind < 0 || kind > 4 || !mismatches) return pt_fail("pt_selfcheck_ieee: bad argument");
   unsigned long long* d = nullptr;
   HIP_OK(hipMalloc(&d, sizeof(*d)));
   hipError_t e = hipMemset(d, 0, sizeof(*d));
@@ -705,7 +553,7 @@ int pt_selfcheck_ieee(int arith, int kind, uint64_t first, uint64_t count, uint3
   unsigned long long h = 0;
   if (e == hipSuccess) e = hipMemcpy(&h, d, sizeof(h), hipMemcpyDeviceToHost);
   (void)hipFree(d);
-  if (e != hipSuccess) return fail("pt_selfcheck_ieee: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return pt_fail("pt_selfcheck_ieee: %s", hipGetErrorString(e));
   *mismatches = h;
   return 0;
 }
@@ -717,7 +565,7 @@ struct PtScene {
 };
 
 int pt_scene_load(const char* path, int res_w, int res_h, PtScene** out) {
-  if (!path || !out) return fail("pt_scene_load: null argument");
+  if (!path || !out) return pt_fail("pt_scene_load: null argument");
   try {
     PtScene* s = new PtScene(path);
     if (res_w > 0 && res_h > 0) s->scene.overrideResolution(res_w, res_h);
@@ -725,12 +573,12 @@ int pt_scene_load(const char* path, int res_w, int res_h, PtScene** out) {
     *out = s;
     return 0;
   } catch (const std::exception& e) {
-    return fail("pt_scene_load: %s", e.what());
+    return pt_fail("pt_scene_load: %s", e.what());
   }
 }
 void pt_scene_free(PtScene* s) { delete s; }
 int pt_scene_desc(const PtScene* s, PtSceneDesc* out) {
-  if (!s || !out) return fail("pt_scene_desc: null argument");
+  if (!s || !out) return pt_fail("pt_scene_desc: null argument");
   *out = s->scene.desc();
   return 0;
 }
@@ -745,7 +593,7 @@ int pt_build_bvh(const PtGeom* geoms, int num_geoms, PtBVHNode* out, int cap) {
 }
 
 int pt_traversal_boxes(const PtGeom* geoms, int num_geoms, const float camera_position[3], float* boxes) {
-  if (!geoms || num_geoms <= 0 || !camera_position || !boxes) return fail("pt_traversal_boxes: null argument");
+  if (!geoms || num_geoms <= 0 || !camera_position || !boxes) return pt_fail("pt_traversal_boxes: null argument");
   pt::ThreadedBvh bvh = pt::threaded_bvh(geoms, num_geoms);
   double olo[3], ohi[3];
   pt::origin_region(bvh.ref[0].bmin, bvh.ref[0].bmax, camera_position, olo, ohi);
@@ -756,7 +604,7 @@ int pt_traversal_boxes(const PtGeom* geoms, int num_geoms, const float camera_po
 }
 
 int pt_build_grid(const PtGeom* geoms, int num_geoms, int forced, PtGridInfo* info, uint32_t* cell_start, PtGridRecord* records) {
-  if (!geoms || num_geoms <= 0 || !info) return fail("pt_build_grid: null argument");
+  if (!geoms || num_geoms <= 0 || !info) return pt_fail("pt_build_grid: null argument");
   const pt::ThreadedBvh bvh = pt::threaded_bvh(geoms, num_geoms);
   std::memset(info, 0, sizeof(*info));
   info->num_leaves = num_geoms;
@@ -781,26 +629,26 @@ void pt_center_half_box(const float lo[3], const float hi[3], int inner, float m
 }
 
 int pt_build_transform(const float* trs, float* transform, float* inverse, float* invTranspose) {
-  if (!trs || !transform || !inverse || !invTranspose) return fail("pt_build_transform: null argument");
+  if (!trs || !transform || !inverse || !invTranspose) return pt_fail("pt_build_transform: null argument");
   pt::buildTransform(trs, transform, inverse, invTranspose);
   return 0;
 }
 
 // ---- renderer contexts ---------------------------------------------------------
 int pt_ctx_create(const PtSceneDesc* sc, const PtOptions* opt_in, PtContext** out) {
-  if (!out) return fail("pt_ctx_create: null output");
+  if (!out) return pt_fail("pt_ctx_create: null output");
   *out = nullptr;
-  if (!sc) return fail("pt_init: null scene");
-  if (sc->num_geoms <= 0 || !sc->geoms) return fail("pt_init: scene has no geometry");
-  if (sc->num_materials <= 0 || !sc->materials) return fail("pt_init: scene has no materials");
-  if (sc->trace_depth <= 0 || sc->trace_depth > PT_MAX_DEPTH) return fail("pt_init: trace_depth %d out of range", sc->trace_depth);
+  if (!sc) return pt_fail("pt_init: null scene");
+  if (sc->num_geoms <= 0 || !sc->geoms) return pt_fail("pt_init: scene has no geometry");
+  if (sc->num_materials <= 0 || !sc->materials) return pt_fail("pt_init: scene has no materials");
+  if (sc->trace_depth <= 0 || sc->trace_depth > PT_MAX_DEPTH) return pt_fail("pt_init: trace_depth %d out of range", sc->trace_depth);
   const int W = sc->camera.resolution[0], H = sc->camera.resolution[1];
-  if (W <= 0 || H <= 0 || (int64_t)W * H > (1ll << 30)) return fail("pt_init: bad resolution %dx%d", W, H);
+  if (W <= 0 || H <= 0 || (int64_t)W * H > (1ll << 30)) return pt_fail("pt_init: bad resolution %dx%d", W, H);
   for (int i = 0; i < sc->num_geoms; ++i) {
     if (sc->geoms[i].materialid < 0 || sc->geoms[i].materialid >= sc->num_materials)
-      return fail("pt_init: geom %d references material %d of %d", i, sc->geoms[i].materialid, sc->num_materials);
+      return pt_fail("pt_init: geom %d references material %d of %d", i, sc->geoms[i].materialid, sc->num_materials);
     if (sc->geoms[i].type < PT_GEOM_SPHERE || sc->geoms[i].type > PT_GEOM_TRIANGLE)
-      return fail("pt_init: geom %d has unknown type %d", i, sc->geoms[i].type);
+      return pt_fail("pt_init: geom %d has unknown type %d", i, sc->geoms[i].type);
   }
   PtOptions opt{};
   if (opt_in) opt = *opt_in;
@@ -823,13 +671,12 @@ int pt_ctx_render(PtContext* c, int iter_first, int iter_count) {
   if (need(c, "pt_render")) return -1;
   if (iter_count <= 0) return 0;
   Ctx& g = *c;
-  if (g.failed) return fail("pt_render: an earlier batch of this context failed (%s); free it and create a new one", g_err.c_str());
-  if (refuse_adaptive(g, "pt_render")) return -1;
+  if (admit(g, "pt_render", kNotFailed | kUniform)) return -1;
   if (g.conv_live) {
     if (iter_first < 1 || (int64_t)iter_first + iter_count - 1 > PT_CONVERGENCE_CAPACITY)
-      return fail("pt_render: iterations %d .. %lld outside 1 .. %d (PT_CONVERGENCE_CAPACITY) with the convergence metric on", iter_first,
+      return pt_fail("pt_render: iterations %d .. %lld outside 1 .. %d (PT_CONVERGENCE_CAPACITY) with the convergence metric on", iter_first,
                   (long long)iter_first + iter_count - 1, PT_CONVERGENCE_CAPACITY);
-    if (g.conv < 0 && !g.conv_have_ref) return fail("pt_render: PtOptions.convergence is -1 but no reference frame has been supplied (pt_set_reference)");
+    if (g.conv < 0 && !g.conv_have_ref) return pt_fail("pt_render: PtOptions.convergence is -1 but no reference frame has been supplied (pt_set_reference)");
   }
   HIP_OK(hipSetDevice(g.device));
   EventPair ev{};
@@ -848,374 +695,6 @@ int pt_ctx_render(PtContext* c, int iter_first, int iter_count) {
   return 0;
 }
 
-// ---- first-hit feature buffers (csrc/pt_features.inc) --------------------------------------------
-int pt_ctx_render_features(PtContext* c, int iter_first, int iter_count) {
-  if (need(c, "pt_render_features")) return -1;
-  Ctx& g = *c;
-  if (iter_first < 1 || iter_count < 0 || (int64_t)iter_first + iter_count - 1 > INT32_MAX)
-    return fail("pt_render_features: iterations %d, +%d: the first is >= 1, the count >= 0", iter_first, iter_count);
-  if (g.failed) return fail("pt_render_features: an earlier batch of this context failed (%s); free it and create a new one", g_err.c_str());
-  HIP_OK(hipSetDevice(g.device));
-  const ptk::SceneTables sc = tables(g);
-  if (!g.d_feat) {  // first feature pass of the context: the buffer, zeroed, and the launch width
-    static_assert(sizeof(float4) == 16, "a feature plane holds 16 bytes per pixel");
-    if (dalloc(g, &g.d_feat, (size_t)PT_FEATURE_PLANES * g.N)) return -1;
-    HIP_OK(hipMemsetAsync(g.d_feat, 0, (size_t)PT_FEATURE_PLANES * g.N * sizeof(float4), g.stream));
-  }
-  if (iter_count == 0) return 0;
-  // one wave per group of 64 pixels, no more workgroups than are resident (the table placement can differ between calls: debug grids)
-  const int groups = (g.N + 63) / 64;
-  g.grid_features = std::min((groups + ptk::kWavesPerBlock - 1) / ptk::kWavesPerBlock,
-                             g.num_cus * std::min(g.cap_bpc, g.k->resident_blocks_per_cu(ptk::kFeatures, sc)));
-  ptk::BatchInfo b{};
-  b.iter_first = iter_first;
-  b.K = iter_count;
-  b.N = g.N;
-  b.pixel_begin = g.pixel_begin;
-  b.trace_depth = g.depth;
-  b.aa_jitter = g.aa_jitter ? 1 : 0;
-  b.stripe = g.stripe;
-  b.gap = g.stripe ? g.stripe_stride - g.stripe : 0;
-  b.inv_stripe = g.stripe ? 1.0f / (float)g.stripe : 0.0f;
-  g.k->features(g.stream, g.grid_features, sc, g.dcam, b, g.d_feat);
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-int pt_ctx_readback_features(PtContext* c, float* planes_host) {
-  if (need(c, "pt_readback_features")) return -1;
-  if (!planes_host) return fail("pt_readback_features: null buffer");
-  if (!c->d_feat) return fail("pt_readback_features: no feature pass has been rendered (pt_render_features)");
-  HIP_OK(hipSetDevice(c->device));
-  HIP_OK(hipMemcpyAsync(planes_host, c->d_feat, (size_t)PT_FEATURE_PLANES * c->N * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-  return pt_ctx_sync(c);
-}
-
-const float* pt_ctx_device_features(PtContext* c) { return c ? reinterpret_cast<const float*>(c->d_feat) : nullptr; }
-
-// ---- edge-avoiding filter over the image and the feature buffers (csrc/pt_denoise.hip) ------------------------
-int pt_ctx_denoise_device(PtContext* c, float samples, const PtDenoiseOptions* opt, const float** rgb_dev) {
-  if (need(c, "pt_denoise")) return -1;
-  Ctx& g = *c;
-  if (g.failed) return fail("pt_denoise: an earlier batch of this context failed (%s); free it and create a new one", g_err.c_str());
-  if (refuse_adaptive(g, "pt_denoise")) return -1;
-  const int W = g.cam.resolution[0];
-  if (g.stripe || g.pixel_begin % W || g.N % W)
-    return fail("pt_denoise: the tile must consist of whole contiguous image rows (begin %d, count %d, stripe %d, width %d)", g.pixel_begin, g.N, g.stripe, W);
-  if (!g.d_feat) return fail("pt_denoise: no feature pass has been rendered (pt_render_features)");
-  ptdn::Params P{};
-  if (pt_denoise_resolve("pt_denoise", samples, opt, &P)) return -1;
-  HIP_OK(hipSetDevice(g.device));
-  if (!g.d_denoise) {  // first denoise call of the context
-    char* ws = nullptr;
-    if (dalloc(g, &ws, pt_denoise_workspace_bytes((size_t)g.N))) return -1;
-    g.d_denoise = ws;
-  }
-  return pt_denoise_launch(g.stream, W, g.N / W, g.d_image, reinterpret_cast<const float*>(g.d_feat), samples, P, g.d_denoise, rgb_dev);
-}
-int pt_ctx_denoise(PtContext* c, float samples, const PtDenoiseOptions* opt, float* rgb_avg_host) {
-  if (!rgb_avg_host) return fail("pt_denoise: null buffer");
-  const float* d = nullptr;
-  if (pt_ctx_denoise_device(c, samples, opt, &d)) return -1;
-  HIP_OK(hipMemcpyAsync(rgb_avg_host, d, 3 * (size_t)c->N * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  return pt_ctx_sync(c);
-}
-
-// The variance-guided form: the same tile, the same workspace, plus the planes of the noise estimate — which must describe the image
-// as it is, so iterations rendered since the last fold are refused rather than filtered with a stale variance.
-int pt_ctx_denoise_guided_device(PtContext* c, const PtDenoiseOptions* opt, const float** rgb_dev) {
-  if (need(c, "pt_denoise_guided")) return -1;
-  Ctx& g = *c;
-  if (g.failed) return fail("pt_denoise_guided: an earlier batch of this context failed (%s); free it and create a new one", g_err.c_str());
-  if (refuse_adaptive(g, "pt_denoise_guided")) return -1;
-  const int W = g.cam.resolution[0];
-  if (g.stripe || g.pixel_begin % W || g.N % W)
-    return fail("pt_denoise_guided: the tile must consist of whole contiguous image rows (begin %d, count %d, stripe %d, width %d)", g.pixel_begin, g.N, g.stripe, W);
-  if (!g.d_feat) return fail("pt_denoise_guided: no feature pass has been rendered (pt_render_features)");
-  if (!g.d_noise || g.noise_groups < 1) return fail("pt_denoise_guided: nothing has been folded (pt_noise_fold)");
-  if (g.rendered != g.noise_iters)
-    return fail("pt_denoise_guided: %lld iteration(s) rendered since the last fold; fold first (pt_noise_fold)", (long long)(g.rendered - g.noise_iters));
-  ptdn::Params P{};
-  float Tf = 0.0f, Df = 0.0f;
-  if (pt_denoise_guided_resolve("pt_denoise_guided", g.noise_groups, g.noise_iters, opt, &P, &Tf, &Df)) return -1;
-  HIP_OK(hipSetDevice(g.device));
-  if (!g.d_denoise) {  // first denoise call of the context, of either kind
-    char* ws = nullptr;
-    if (dalloc(g, &ws, pt_denoise_workspace_bytes((size_t)g.N))) return -1;
-    g.d_denoise = ws;
-  }
-  return pt_denoise_guided_launch(g.stream, W, g.N / W, g.d_image, reinterpret_cast<const float*>(g.d_feat), static_cast<const float*>(g.d_noise), Tf, Df, P,
-                                  g.d_denoise, rgb_dev);
-}
-int pt_ctx_denoise_guided(PtContext* c, const PtDenoiseOptions* opt, float* rgb_avg_host) {
-  if (!rgb_avg_host) return fail("pt_denoise_guided: null buffer");
-  const float* d = nullptr;
-  if (pt_ctx_denoise_guided_device(c, opt, &d)) return -1;
-  HIP_OK(hipMemcpyAsync(rgb_avg_host, d, 3 * (size_t)c->N * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  return pt_ctx_sync(c);
-}
-
-// ---- noise estimate from batch sums, render until a target PSNR (csrc/pt_noise.hip) ----------------------------
-int pt_ctx_noise_fold(PtContext* c) {
-  if (need(c, "pt_noise_fold")) return -1;
-  Ctx& g = *c;
-  if (g.failed) return fail("pt_noise_fold: an earlier batch of this context failed (%s); free it and create a new one", g_err.c_str());
-  if (refuse_adaptive(g, "pt_noise_fold")) return -1;
-  const int64_t n = g.rendered - g.noise_iters;
-  if (n <= 0) return 0;  // nothing rendered since the last fold
-  HIP_OK(hipSetDevice(g.device));
-  if (!g.d_noise) {  // first fold of the context: the state, zeroed like the image it starts from
-    char* st = nullptr;
-    if (dalloc(g, &st, pt_noise_state_bytes((size_t)g.N))) return -1;
-    g.d_noise = st;
-    HIP_OK(hipMemsetAsync(g.d_noise, 0, pt_noise_state_bytes((size_t)g.N), g.stream));
-  }
-  if (pt_noise_launch(g.stream, g.N, g.d_image, g.d_noise, ptnz::fold_scalars(n, g.noise_groups + 1, g.noise_iters + n))) return -1;
-  g.noise_groups += 1;
-  g.noise_iters += n;
-  return 0;
-}
-
-int pt_ctx_get_noise(PtContext* c, double* sse, int* groups, int* iterations) {
-  if (need(c, "pt_get_noise")) return -1;
-  if (pt_ctx_sync(c)) return -1;
-  Ctx& g = *c;
-  if (sse) {
-    *sse = -1.0;
-    if (g.d_noise && g.noise_groups >= 2) {
-      const char* result = static_cast<const char*>(g.d_noise) + pt_noise_state_bytes((size_t)g.N) - sizeof(double);
-      HIP_OK(hipMemcpy(sse, result, sizeof(double), hipMemcpyDeviceToHost));
-    }
-  }
-  // (the adaptive state: the last merge's SSE_est lies where a fold's does; every round counts as a group)
-  if (groups) *groups = g.noise_groups + g.adaptive_rounds;
-  if (iterations) *iterations = (int)std::min<int64_t>(g.adaptive ? g.adaptive_last : g.noise_iters, INT32_MAX);
-  return 0;
-}
-
-int pt_ctx_readback_noise(PtContext* c, float* planes_host) {
-  if (need(c, "pt_readback_noise")) return -1;
-  if (!planes_host) return fail("pt_readback_noise: null buffer");
-  if (!c->d_noise) return fail("pt_readback_noise: nothing has been folded (pt_noise_fold)");
-  HIP_OK(hipSetDevice(c->device));
-  HIP_OK(hipMemcpyAsync(planes_host, c->d_noise, (size_t)PT_NOISE_PLANES * c->N * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-  return pt_ctx_sync(c);
-}
-
-const float* pt_ctx_device_noise(PtContext* c) { return c ? static_cast<const float*>(c->d_noise) : nullptr; }
-
-int pt_ctx_render_until(PtContext* c, int iter_first, int max_iters, int group_iters, float target_db, int* iters_done, float* psnr_db) {
-  if (need(c, "pt_render_until")) return -1;
-  Ctx& g = *c;
-  if (iter_first < 1 || max_iters < 1 || (int64_t)iter_first + max_iters - 1 > INT32_MAX || group_iters < 0 || !std::isfinite(target_db))
-    return fail("pt_render_until: iterations %d, +%d in groups of %d until %g dB: the first is >= 1, the count >= 1, the group >= 0 (0 = a batch), the target finite",
-                iter_first, max_iters, group_iters, (double)target_db);
-  if (g.failed) return fail("pt_render_until: an earlier batch of this context failed (%s); free it and create a new one", g_err.c_str());
-  if (refuse_adaptive(g, "pt_render_until")) return -1;
-  const int group = group_iters ? group_iters : g.K;
-  int done = 0;
-  float psnr = -1.0f;
-  while (done < max_iters) {
-    const int n = std::min(group, max_iters - done);
-    if (pt_ctx_render(c, iter_first + done, n)) return -1;
-    done += n;
-    double sse = -1.0;
-    if (pt_ctx_noise_fold(c) || pt_ctx_get_noise(c, &sse, nullptr, nullptr)) return -1;
-    if (sse < 0.0) continue;  // one group says nothing about the spread
-    psnr = pt_psnr_from_sse(sse, g.N);
-    if (psnr > target_db) break;
-  }
-  if (iters_done) *iters_done = done;
-  if (psnr_db) *psnr_db = psnr;
-  return 0;
-}
-
-
-// ---- adaptive sampling: further groups over the noisiest pixels only (csrc/pt_adaptive.hip) -------------------------------
-namespace {
-int ensure_list(Ctx& g) {
-  if (g.d_list) return 0;
-  if (dalloc(g, &g.d_list, (size_t)g.N)) return -1;
-  HIP_OK(hipMemset(g.d_list, 0, (size_t)g.N * sizeof(int32_t)));  // every entry a tile pixel from the start
-  return 0;
-}
-
-void drop_worker(Ctx& g) {
-  if (!g.worker) return;
-  g.device_bytes -= g.worker->device_bytes;
-  destroy(g.worker);
-  g.worker = nullptr;
-}
-
-// The worker context for a list of m pixels: batches, queues, buffers and launch widths planned for N = m like any context's; the
-// scene tables, the grid or BVH choice and the LDS-table decision are the parent's (neither uploaded nor measured again, not owned).
-int ensure_worker(Ctx& g, int m) {
-  if (g.worker && g.worker->N == m) return 0;
-  drop_worker(g);
-  if (ensure_list(g)) return -1;
-  Ctx* w = new Ctx();
-  w->borrowed = true;
-  w->device = g.device, w->stream = g.stream, w->k = g.k, w->arith = g.arith, w->num_cus = g.num_cus;
-  w->cam = g.cam, w->dcam = g.dcam, w->depth = g.depth;
-  w->scene = g.scene, w->grids = g.grids, w->grid_pick = g.grid_pick, w->grid_enabled = g.grid_enabled, w->tight_leaves = g.tight_leaves;
-  w->lds_table_bytes = g.lds_table_bytes, w->lds_table_forced = g.lds_table_forced;
-  w->primary_pieces = g.primary_pieces, w->primary_share = g.primary_share, w->paths_pieces = g.paths_pieces;
-  w->cap_bpc = g.cap_bpc, w->legacy = g.legacy, w->debug_flags = g.debug_flags, w->aa_jitter = g.aa_jitter;
-  w->fuse_primary = g.fuse_primary, w->fuse_bounces = g.fuse_bounces;
-  PtOptions o{};
-  o.pixel_begin = g.pixel_begin, o.pixel_count = m;
-  o.iters_per_batch = g.opt_iters_per_batch, o.num_queues = g.opt_num_queues;  // 0: automatic for m pixels
-  if (plan_batches(*w, o)) return destroy(w), -1;
-  plan_launch(*w);
-  if (alloc_batch_buffers(*w)) return destroy(w), -1;
-  w->list = g.d_list;
-  g.worker = w;
-  g.device_bytes += w->device_bytes;
-  return 0;
-}
-
-// Iterations iter_first .. iter_first + iter_count - 1 of the listed pixels into the worker's cleared group sum.
-int render_list(Ctx& g, int iter_first, int iter_count) {
-  Ctx& w = *g.worker;
-  HIP_OK(hipMemsetAsync(w.d_image, 0, 3 * (size_t)w.N * sizeof(float), g.stream));
-  const int end = iter_first + iter_count;
-  for (int it = iter_first; it < end; it += w.K)
-    if (run_batch(w, it, std::min(w.K, end - it))) {
-      g.failed = true;
-      return -1;
-    }
-  return 0;
-}
-
-// Everything a round refuses, before anything is allocated or launched.
-int adaptive_refusal(const Ctx& g, const char* who, int iter_first, int group_iters, float fraction) {
-  if (g.failed) return fail("%s: an earlier batch of this context failed (%s); free it and create a new one", who, g_err.c_str());
-  if (iter_first < 1 || group_iters < 1 || (int64_t)iter_first + group_iters - 1 > INT32_MAX)
-    return fail("%s: iterations %d, +%d: the first is >= 1, the group holds at least one", who, iter_first, group_iters);
-  if (!(fraction > 0.0f && fraction <= 1.0f)) return fail("%s: fraction %g is not in (0, 1]", who, (double)fraction);
-  if (g.conv) return fail("%s: the renderer was created with PtOptions.convergence = %d; the convergence metric follows whole iterations", who, g.conv);
-  const int W = g.cam.resolution[0];
-  if (g.stripe || g.pixel_begin % W || g.N % W)
-    return fail("%s: the tile must consist of whole contiguous image rows (begin %d, count %d, stripe %d, width %d)", who, g.pixel_begin, g.N, g.stripe, W);
-  if (g.adaptive) return 0;
-  if (g.noise_groups < 2) return fail("%s: %d group(s) folded; the selection needs the noise estimate of at least 2 (pt_noise_fold)", who, g.noise_groups);
-  if (g.rendered != g.noise_iters)
-    return fail("%s: %lld iteration(s) rendered since the last fold; fold first (pt_noise_fold)", who, (long long)(g.rendered - g.noise_iters));
-  if (g.noise_iters > INT32_MAX / 2) return fail("%s: %lld iterations folded: the per-pixel counts are int32", who, (long long)g.noise_iters);
-  return 0;
-}
-
-// group_iters == 0 of pt_render_adaptive: the iterations per batch a worker for m pixels plans (plan_batches' own function)
-int worker_batch_iters(const Ctx& g, int m) { return g.worker && g.worker->N == m ? g.worker->K : batch_iters_for(g.opt_iters_per_batch, m, nullptr); }
-}  // namespace
-
-int pt_ctx_adaptive_round(PtContext* c, int iter_first, int group_iters, float fraction) {
-  if (need(c, "pt_adaptive_round")) return -1;
-  Ctx& g = *c;
-  if (adaptive_refusal(g, "pt_adaptive_round", iter_first, group_iters, fraction)) return -1;
-  HIP_OK(hipSetDevice(g.device));
-  const int W = g.cam.resolution[0];
-  if (!g.adaptive) {  // the first round since pt_init / pt_clear: every pixel has the fold's T and M
-    if (!g.d_acnt) {
-      char *cnt = nullptr, *ws = nullptr;
-      if (dalloc(g, &cnt, (size_t)g.N * sizeof(ptad::Cnt)) || dalloc(g, &ws, pt_adaptive_select_bytes((size_t)g.N)) || ensure_list(g)) return -1;
-      g.d_acnt = cnt, g.d_select = ws;
-    }
-    if (pt_adaptive_init_counts_launch(g.stream, g.N, g.d_acnt, (int)g.noise_iters, g.noise_groups)) return -1;
-    g.adaptive = true;
-    g.adaptive_rounds = 0;
-    g.adaptive_last = g.noise_iters;
-  }
-  const int m = ptad::list_length((double)fraction, g.N);
-  if (ensure_worker(g, m)) return -1;
-  if (pt_adaptive_select_launch(g.stream, W, g.N / W, static_cast<const float*>(g.d_noise), g.d_acnt, m, g.d_select, g.d_list)) return -1;
-  if (render_list(g, iter_first, group_iters)) return -1;
-  if (pt_adaptive_merge_launch(g.stream, g.N, g.d_image, g.d_noise, g.d_acnt, g.d_list, m, g.worker->d_image, group_iters)) return -1;
-  g.adaptive_rounds += 1;
-  g.adaptive_last = std::max<int64_t>(g.adaptive_last, (int64_t)iter_first + group_iters - 1);
-  g.samples += (int64_t)group_iters * m;  // (live_rays and the kernel timings stay the parent's own launches')
-  return 0;
-}
-
-int pt_ctx_render_adaptive(PtContext* c, int iter_first, int max_iters, int group_iters, float fraction, float target_db, int* iters_done,
-                           int64_t* samples_done, float* psnr_db) {
-  if (need(c, "pt_render_adaptive")) return -1;
-  Ctx& g = *c;
-  if (max_iters < 1 || (int64_t)iter_first + max_iters - 1 > INT32_MAX || group_iters < 0 || !std::isfinite(target_db))
-    return fail("pt_render_adaptive: iterations %d, +%d in groups of %d until %g dB: the count is >= 1, the group >= 0 (0 = a batch of the worker), the target finite",
-                iter_first, max_iters, group_iters, (double)target_db);
-  // what a round would refuse, apart from the state of the folds, which the uniform groups below establish
-  if (g.failed) return fail("pt_render_adaptive: an earlier batch of this context failed (%s); free it and create a new one", g_err.c_str());
-  if (iter_first < 1) return fail("pt_render_adaptive: the first iteration %d is not >= 1", iter_first);
-  if (!(fraction > 0.0f && fraction <= 1.0f)) return fail("pt_render_adaptive: fraction %g is not in (0, 1]", (double)fraction);
-  if (g.conv) return fail("pt_render_adaptive: the renderer was created with PtOptions.convergence = %d; the convergence metric follows whole iterations", g.conv);
-  const int W = g.cam.resolution[0];
-  if (g.stripe || g.pixel_begin % W || g.N % W)
-    return fail("pt_render_adaptive: the tile must consist of whole contiguous image rows (begin %d, count %d, stripe %d, width %d)", g.pixel_begin, g.N, g.stripe, W);
-  const int m = ptad::list_length((double)fraction, g.N);
-  const int group = group_iters ? group_iters : worker_batch_iters(g, m);
-  int done = 0;
-  int64_t samples = 0;
-  float psnr = -1.0f;
-  while (done < max_iters) {
-    const int n = std::min(group, max_iters - done);
-    if (!g.adaptive && g.noise_groups < 2) {  // a uniform group and its fold, as pt_render_until
-      if (pt_ctx_render(c, iter_first + done, n) || pt_ctx_noise_fold(c)) return -1;
-      samples += (int64_t)n * g.N;
-    } else {
-      if (!g.adaptive && g.rendered != g.noise_iters && pt_ctx_noise_fold(c)) return -1;  // iterations of the caller's, not yet folded
-      if (pt_ctx_adaptive_round(c, iter_first + done, n, fraction)) return -1;
-      samples += (int64_t)n * m;
-    }
-    done += n;
-    double sse = -1.0;
-    if (pt_ctx_get_noise(c, &sse, nullptr, nullptr)) return -1;
-    if (sse < 0.0) continue;  // one group says nothing about the spread
-    psnr = pt_psnr_from_sse(sse, g.N);
-    if (psnr > target_db) break;
-  }
-  if (iters_done) *iters_done = done;
-  if (samples_done) *samples_done = samples;
-  if (psnr_db) *psnr_db = psnr;
-  return 0;
-}
-
-int pt_ctx_readback_adaptive(PtContext* c, int32_t* counts) {
-  if (need(c, "pt_readback_adaptive")) return -1;
-  if (!counts) return fail("pt_readback_adaptive: null buffer");
-  Ctx& g = *c;
-  if (!g.adaptive) {  // the uniform state: the fold's T and M for every pixel
-    if (pt_ctx_sync(c)) return -1;
-    for (size_t p = 0; p < (size_t)g.N; ++p) counts[2 * p] = (int32_t)std::min<int64_t>(g.noise_iters, INT32_MAX), counts[2 * p + 1] = g.noise_groups;
-    return 0;
-  }
-  HIP_OK(hipSetDevice(g.device));
-  HIP_OK(hipMemcpyAsync(counts, g.d_acnt, (size_t)g.N * sizeof(ptad::Cnt), hipMemcpyDeviceToHost, g.stream));
-  return pt_ctx_sync(c);
-}
-
-int pt_ctx_resolve_device(PtContext* c, const float** rgb_dev) {
-  if (need(c, "pt_resolve")) return -1;
-  Ctx& g = *c;
-  if (g.failed) return fail("pt_resolve: an earlier batch of this context failed (%s); free it and create a new one", g_err.c_str());
-  if (g.noise_groups < 1) return fail("pt_resolve: nothing has been folded (pt_noise_fold): the sample counts are the folds'");
-  if (g.rendered != g.noise_iters)
-    return fail("pt_resolve: %lld iteration(s) rendered since the last fold; fold first (pt_noise_fold)", (long long)(g.rendered - g.noise_iters));
-  if (g.noise_iters > INT32_MAX) return fail("pt_resolve: %lld iterations folded", (long long)g.noise_iters);
-  HIP_OK(hipSetDevice(g.device));
-  if (!g.d_resolved && dalloc(g, &g.d_resolved, 3 * (size_t)g.N)) return -1;
-  if (pt_adaptive_resolve_launch(g.stream, g.N, g.d_image, g.adaptive ? g.d_acnt : nullptr, (int)g.noise_iters, g.d_resolved)) return -1;
-  if (rgb_dev) *rgb_dev = g.d_resolved;
-  return 0;
-}
-int pt_ctx_resolve(PtContext* c, float* rgb_avg_host) {
-  if (!rgb_avg_host) return fail("pt_resolve: null buffer");
-  const float* d = nullptr;
-  if (pt_ctx_resolve_device(c, &d)) return -1;
-  HIP_OK(hipMemcpyAsync(rgb_avg_host, d, 3 * (size_t)c->N * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  return pt_ctx_sync(c);
-}
-
 int pt_ctx_sync(PtContext* c) {
   if (need(c, "pt_sync")) return -1;
   HIP_OK(hipSetDevice(c->device));
@@ -1225,18 +704,12 @@ int pt_ctx_sync(PtContext* c) {
 
 int pt_ctx_readback(PtContext* c, float* out) {
   if (need(c, "pt_readback")) return -1;
-  if (!out) return fail("pt_readback: null buffer");
-  HIP_OK(hipSetDevice(c->device));
-  HIP_OK(hipMemcpyAsync(out, c->d_image, 3 * (size_t)c->N * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  return pt_ctx_sync(c);
+  return copy_out(c, "pt_readback", out, 3, [&](const float** d) { return *d = c->d_image, 0; });
 }
 
 int pt_ctx_readback_device(PtContext* c, void* out) {
   if (need(c, "pt_readback_device")) return -1;
-  if (!out) return fail("pt_readback_device: null buffer");
-  HIP_OK(hipSetDevice(c->device));
-  HIP_OK(hipMemcpyAsync(out, c->d_image, 3 * (size_t)c->N * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-  return pt_ctx_sync(c);
+  return copy_out(c, "pt_readback_device", static_cast<float*>(out), 3, [&](const float** d) { return *d = c->d_image, 0; }, hipMemcpyDeviceToDevice);
 }
 
 const float* pt_ctx_device_image(PtContext* c) { return c ? c->d_image : nullptr; }
@@ -1249,30 +722,25 @@ int pt_ctx_save_u8_device(PtContext* c, float samples, const uint8_t** rgb8_dev)
   if (need(c, "pt_save_u8")) return -1;
   Ctx& g = *c;
   const int W = g.cam.resolution[0];
-  if (!(samples > 0.0f)) return fail("pt_save_u8: samples must be positive");
-  if (refuse_adaptive(g, "pt_save_u8")) return -1;
-  if (g.pixel_begin % W || g.N % W || (g.stripe && g.stripe != W))
-    return fail("pt_save_u8: the tile must consist of whole image rows (begin %d, count %d, stripe %d, width %d)", g.pixel_begin, g.N, g.stripe, W);
+  if (!(samples > 0.0f)) return pt_fail("pt_save_u8: samples must be positive");
+  if (admit(g, "pt_save_u8", kUniform)) return -1;
+  if (g.pixel_begin % W || g.N % W || (g.stripe && g.stripe != W))  // (its own rule: the rows of a striped frame need not be contiguous)
+    return pt_fail("pt_save_u8: the tile must consist of whole image rows (begin %d, count %d, stripe %d, width %d)", g.pixel_begin, g.N, g.stripe, W);
   HIP_OK(hipSetDevice(g.device));
-  if (!g.d_rgb8 && dalloc(g, &g.d_rgb8, 3 * (size_t)g.N)) return -1;
+  if (ensure(g, g.d_rgb8, 3 * (size_t)g.N)) return -1;
   g.k->save_u8(g.stream, g.N, W, samples, g.d_image, g.d_rgb8);
   HIP_OK(hipGetLastError());
   if (rgb8_dev) *rgb8_dev = g.d_rgb8;
   return 0;
 }
 int pt_ctx_save_u8(PtContext* c, float samples, uint8_t* rgb8_host) {
-  if (!rgb8_host) return fail("pt_save_u8: null buffer");
-  const uint8_t* d = nullptr;
-  if (pt_ctx_save_u8_device(c, samples, &d)) return -1;
-  HIP_OK(hipMemcpyAsync(rgb8_host, d, 3 * (size_t)c->N, hipMemcpyDeviceToHost, c->stream));
-  return pt_ctx_sync(c);
+  return copy_out(c, "pt_save_u8", rgb8_host, 3, [&](const uint8_t** d) { return pt_ctx_save_u8_device(c, samples, d); });
 }
 
 int pt_ctx_preview_rgba8_device(PtContext* c, int iterations, void* rgba_dev) {
   if (need(c, "pt_preview_rgba8_device")) return -1;
-  if (!rgba_dev || iterations <= 0) return fail("pt_preview_rgba8_device: bad argument");
-  if (refuse_adaptive(*c, "pt_preview_rgba8_device")) return -1;
-  HIP_OK(hipSetDevice(c->device));
+  if (!rgba_dev || iterations <= 0) return pt_fail("pt_preview_rgba8_device: bad argument");
+  if (admit(*c, "pt_preview_rgba8_device", kUniform | kOnDevice)) return -1;
   c->k->preview(c->stream, c->N, iterations, c->d_image, reinterpret_cast<uchar4*>(rgba_dev));
   HIP_OK(hipStreamSynchronize(c->stream));
   return 0;
@@ -1280,22 +748,21 @@ int pt_ctx_preview_rgba8_device(PtContext* c, int iterations, void* rgba_dev) {
 
 int pt_ctx_preview_rgba8(PtContext* c, int iterations, uint8_t* rgba_host) {
   if (need(c, "pt_preview_rgba8")) return -1;
-  if (!rgba_host || iterations <= 0) return fail("pt_preview_rgba8: bad argument");
-  if (refuse_adaptive(*c, "pt_preview_rgba8")) return -1;
-  HIP_OK(hipSetDevice(c->device));
+  if (!rgba_host || iterations <= 0) return pt_fail("pt_preview_rgba8: bad argument");
+  if (admit(*c, "pt_preview_rgba8", kUniform | kOnDevice)) return -1;
   uchar4* d = nullptr;
   HIP_OK(hipMalloc((void**)&d, (size_t)c->N * 4));
   c->k->preview(c->stream, c->N, iterations, c->d_image, d);
   hipError_t e = hipMemcpyAsync(rgba_host, d, (size_t)c->N * 4, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   (void)hipFree(d);
-  if (e != hipSuccess) return fail("pt_preview_rgba8: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return pt_fail("pt_preview_rgba8: %s", hipGetErrorString(e));
   return 0;
 }
 
 int pt_ctx_get_stats(PtContext* c, PtStats* out) {
   if (need(c, "pt_get_stats")) return -1;
-  if (!out) return fail("pt_get_stats: null");
+  if (!out) return pt_fail("pt_get_stats: null");
   if (pt_ctx_sync(c)) return -1;
   Ctx& g = *c;
   std::memset(out, 0, sizeof(*out));
@@ -1369,8 +836,8 @@ int pt_ctx_clear(PtContext* c) {
 // ---- convergence metric ---------------------------------------------------------------------
 int pt_ctx_set_reference(PtContext* c, const float* rgb_avg_host) {
   if (need(c, "pt_set_reference")) return -1;
-  if (!rgb_avg_host) return fail("pt_set_reference: null image");
-  if (c->conv != -1) return fail("pt_set_reference: the renderer was created with PtOptions.convergence = %d, not -1", c->conv);
+  if (!rgb_avg_host) return pt_fail("pt_set_reference: null image");
+  if (c->conv != -1) return pt_fail("pt_set_reference: the renderer was created with PtOptions.convergence = %d, not -1", c->conv);
   if (pt_ctx_sync(c)) return -1;
   HIP_OK(hipMemcpyAsync(c->d_ref, rgb_avg_host, 3 * (size_t)c->N * sizeof(float), hipMemcpyHostToDevice, c->stream));
   HIP_OK(hipStreamSynchronize(c->stream));
@@ -1380,8 +847,8 @@ int pt_ctx_set_reference(PtContext* c, const float* rgb_avg_host) {
 
 int pt_ctx_get_convergence(PtContext* c, int iter_first, int iter_count, double* sse) {
   if (need(c, "pt_get_convergence")) return -1;
-  if (!c->conv) return fail("pt_get_convergence: the renderer was created with PtOptions.convergence = 0 (metric off)");
-  if (iter_count < 0 || (iter_count > 0 && !sse)) return fail("pt_get_convergence: bad argument");
+  if (!c->conv) return pt_fail("pt_get_convergence: the renderer was created with PtOptions.convergence = 0 (metric off)");
+  if (iter_count < 0 || (iter_count > 0 && !sse)) return pt_fail("pt_get_convergence: bad argument");
   if (pt_ctx_sync(c)) return -1;
   for (int j = 0; j < iter_count; ++j) sse[j] = -1.0;
   const int64_t lo = std::max<int64_t>(iter_first, 1), hi = std::min<int64_t>((int64_t)iter_first + iter_count, (int64_t)PT_CONVERGENCE_CAPACITY + 1);
@@ -1395,7 +862,7 @@ int pt_ctx_get_convergence(PtContext* c, int iter_first, int iter_count, double*
 
 int pt_ctx_iterations_to_clean(PtContext* c, float threshold_db, int* iteration) {
   if (need(c, "pt_iterations_to_clean")) return -1;
-  if (!iteration) return fail("pt_iterations_to_clean: null output");
+  if (!iteration) return pt_fail("pt_iterations_to_clean: null output");
   std::vector<double> sse((size_t)std::max(c->conv_last, 0));
   if (pt_ctx_get_convergence(c, 1, (int)sse.size(), sse.data())) return -1;
   *iteration = -1;
@@ -1448,271 +915,5 @@ int pt_resolve(float* rgb_avg_host) { return pt_ctx_resolve(g_default, rgb_avg_h
 int pt_set_reference(const float* rgb_avg_host) { return pt_ctx_set_reference(g_default, rgb_avg_host); }
 int pt_get_convergence(int iter_first, int iter_count, double* sse) { return pt_ctx_get_convergence(g_default, iter_first, iter_count, sse); }
 int pt_iterations_to_clean(float threshold_db, int* iteration) { return pt_ctx_iterations_to_clean(g_default, threshold_db, iteration); }
-
-// ---- stage entry points (tests; default context) ------------------------------------------------
-// The C ABI of the stages takes plain SoA float arrays ([3][n]); the kernels stream three planes of 16-byte path records
-// (ptd::PathBuf), so the stage wrappers pack / unpack on the host.
-namespace {
-struct StagePaths {
-  ptd::PathBuf pb{};
-  std::vector<ptd::Word4> host;
-  size_t cap = 0;
-  bool alloc(Scratch& sc, size_t cap_) {
-    cap = cap_;
-    pb.stride = (int64_t)cap;
-    pb.r = sc.get<ptd::Word4>(3 * cap);
-    host.assign(3 * cap, ptd::Word4{0.f, 0.f, 0.f, 0.f});
-    return pb.r != nullptr;
-  }
-  void pack(int n, const float* o, const float* d, const float* c) {  // arrays are [3][n]; null = zeros
-    for (int i = 0; i < n; ++i) {
-      auto at = [&](const float* a, int k) { return a ? a[(size_t)k * n + i] : 0.0f; };
-      host[i] = ptd::Word4{at(o, 0), at(o, 1), at(o, 2), at(d, 0)};
-      host[cap + i] = ptd::Word4{at(d, 1), at(d, 2), at(c, 0), at(c, 1)};
-      reinterpret_cast<float*>(&host[2 * cap])[(size_t)i * (ptd::kPathPlane2Bytes / 4)] = at(c, 2);
-    }
-  }
-  int upload() { return hipMemcpy(pb.r, host.data(), host.size() * sizeof(ptd::Word4), hipMemcpyHostToDevice) == hipSuccess ? 0 : -1; }
-  int download() { return hipMemcpy(host.data(), pb.r, host.size() * sizeof(ptd::Word4), hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1; }
-  void unpack(int n, float* o, float* d, float* c) const {
-    for (int i = 0; i < n; ++i) {
-      const ptd::Word4 &w0 = host[i], &w1 = host[cap + i];
-      const float cz = reinterpret_cast<const float*>(&host[2 * cap])[(size_t)i * (ptd::kPathPlane2Bytes / 4)];
-      if (o) o[i] = w0.x, o[(size_t)n + i] = w0.y, o[2 * (size_t)n + i] = w0.z;
-      if (d) d[i] = w0.w, d[(size_t)n + i] = w1.x, d[2 * (size_t)n + i] = w1.y;
-      if (c) c[i] = w1.z, c[(size_t)n + i] = w1.w, c[2 * (size_t)n + i] = cz;
-    }
-  }
-};
-}  // namespace
-
-int pt_stage_generate(int pix_begin, int n, float* origin, float* dir) {
-  if (need(g_default, "pt_stage_generate")) return -1;
-  Ctx& g = *g_default;
-  if (n <= 0) return 0;
-  HIP_OK(hipSetDevice(g.device));
-  Scratch sc;
-  ptd::Queues qs = single_queue(g, n);
-  StagePaths sp;
-  int32_t* cnt = sc.get<int32_t>(16);
-  if (!sp.alloc(sc, (size_t)qs.cap) || !cnt) return fail("pt_stage_generate: out of device memory");
-  const ptd::PathBuf pb = sp.pb;
-  ptk::BatchInfo b{};
-  b.iter_first = 1, b.K = 1, b.N = n, b.pixel_begin = pix_begin, b.trace_depth = g.depth;
-  b.slot_shift = 30;
-  b.aa_jitter = g.aa_jitter ? 1 : 0;
-  g.k->generate(g.stream, g.grid, g.dcam, b, qs, pb, cnt);
-  HIP_OK(hipStreamSynchronize(g.stream));
-  if (sp.download()) return fail("pt_stage_generate: download failed");
-  sp.unpack(n, origin, dir, nullptr);
-  return 0;
-}
-
-int pt_stage_intersect(int n, const float* origin, const float* dir, float* t, float* normal, int32_t* material,
-                       float* point) {
-  if (need(g_default, "pt_stage_intersect")) return -1;
-  Ctx& g = *g_default;
-  if (n <= 0) return 0;
-  if (g.tight_leaves > 0) {
-    // the tightened sphere boxes of a large scene are sized for ray origins inside the scene bounds or at the camera
-    // (sphere_tight_box): rays from elsewhere could lose grazing hits, so they are refused rather than traced differently
-    double olo[3], ohi[3];
-    pt::origin_region(g.scene.root_min, g.scene.root_max, g.cam.position, olo, ohi);
-    for (int i = 0; i < n; ++i)
-      for (int a = 0; a < 3; ++a) {
-        const float v = origin[(size_t)a * n + i];
-        if (!(v >= olo[a] && v <= ohi[a]))
-          return fail("pt_stage_intersect: ray %d starts outside the scene bounds (this scene's sphere leaves are tightened for origins inside them; "
-                      "PtOptions.debug_flags 2048 keeps the reference's boxes)", i);
-      }
-  }
-  HIP_OK(hipSetDevice(g.device));
-  Scratch sc;
-  ptd::Queues qs = single_queue(g, n);
-  const size_t cap = qs.cap;
-  StagePaths sp;
-  const bool have_paths = sp.alloc(sc, cap);
-  const ptd::PathBuf pb = sp.pb;
-  ptd::HitBuf hb{};
-  hb.stride = cap;
-  hb.t = sc.get<float>(cap);
-  hb.n = sc.get<float>(3 * cap);
-  hb.mat = sc.get<int32_t>(cap);
-  hb.p = sc.get<float>(3 * cap);
-  int32_t* cnt = sc.get<int32_t>(16);
-  if (!have_paths || !hb.t || !hb.n || !hb.mat || !hb.p || !cnt) return fail("pt_stage_intersect: out of device memory");
-  sp.pack(n, origin, dir, nullptr);
-  if (sp.upload()) return fail("pt_stage_intersect: upload failed");
-  HIP_OK(hipMemcpy(cnt, &n, 4, hipMemcpyHostToDevice));
-  g.k->intersect(g.stream, g.grid, tables(g), qs, cnt, pb, hb, g.legacy, false);
-  HIP_OK(hipStreamSynchronize(g.stream));
-  HIP_OK(hipMemcpy(t, hb.t, (size_t)n * 4, hipMemcpyDeviceToHost));
-  HIP_OK(hipMemcpy(material, hb.mat, (size_t)n * 4, hipMemcpyDeviceToHost));
-  for (int c = 0; c < 3; ++c) {
-    HIP_OK(hipMemcpy(normal + (size_t)c * n, hb.n + c * cap, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(point + (size_t)c * n, hb.p + c * cap, (size_t)n * 4, hipMemcpyDeviceToHost));
-  }
-  return 0;
-}
-
-int pt_stage_shade(int n, int depth, const int32_t* iter, const int32_t* pixel, const float* t, const float* normal,
-                   const int32_t* material, const float* point, float* origin, float* dir, float* color,
-                   int32_t* alive) {
-  if (need(g_default, "pt_stage_shade")) return -1;
-  Ctx& g = *g_default;
-  if (n <= 0) return 0;
-  if (depth < 0 || depth >= g.depth) return fail("pt_stage_shade: depth %d outside [0,%d)", depth, g.depth);
-  for (int i = 0; i < n; ++i)
-    if (t[i] >= 0.0f && (material[i] < 0 || material[i] >= g.scene.num_mats))
-      return fail("pt_stage_shade: material id %d out of range at %d", material[i], i);
-  HIP_OK(hipSetDevice(g.device));
-  Scratch sc;
-  const size_t cap = n;
-  StagePaths sp;
-  const bool have_paths = sp.alloc(sc, cap);
-  const ptd::PathBuf pb = sp.pb;
-  ptd::HitBuf hb{};
-  hb.stride = cap;
-  hb.t = sc.get<float>(cap);
-  hb.n = sc.get<float>(3 * cap);
-  hb.mat = sc.get<int32_t>(cap);
-  hb.p = sc.get<float>(3 * cap);
-  int32_t* d_iter = sc.get<int32_t>(cap);
-  int32_t* d_pix = sc.get<int32_t>(cap);
-  int32_t* d_alive = sc.get<int32_t>(cap);
-  if (!have_paths || !hb.t || !hb.n || !hb.mat || !hb.p || !d_iter || !d_pix || !d_alive)
-    return fail("pt_stage_shade: out of device memory");
-  const size_t b1 = (size_t)n * 4, b3 = 3 * b1;
-  sp.pack(n, origin, dir, color);
-  if (sp.upload()) return fail("pt_stage_shade: upload failed");
-  HIP_OK(hipMemcpy(hb.t, t, b1, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(hb.n, normal, b3, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(hb.mat, material, b1, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(hb.p, point, b3, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(d_iter, iter, b1, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(d_pix, pixel, b1, hipMemcpyHostToDevice));
-  g.k->shade_stage(g.stream, tables(g), g.depth, depth, n, d_iter, d_pix, hb, pb, d_alive);
-  HIP_OK(hipStreamSynchronize(g.stream));
-  if (sp.download()) return fail("pt_stage_shade: download failed");
-  sp.unpack(n, origin, dir, color);
-  HIP_OK(hipMemcpy(alive, d_alive, b1, hipMemcpyDeviceToHost));
-  return 0;
-}
-
-// k_save_u8 on a caller-supplied SUM image of whole rows (tests: pins the device conversion to the reference writer's bytes)
-int pt_stage_save_u8(int w, int h, float samples, const float* rgb_sum, uint8_t* rgb8) {
-  if (need(g_default, "pt_stage_save_u8")) return -1;
-  Ctx& g = *g_default;
-  if (w <= 0 || h <= 0 || h >= 32768 || !rgb_sum || !rgb8 || !(samples > 0.0f)) return fail("pt_stage_save_u8: bad argument");
-  HIP_OK(hipSetDevice(g.device));
-  Scratch sc;
-  const size_t n = (size_t)w * h;
-  float* d_img = sc.get<float>(3 * n);
-  uint8_t* d_u8 = sc.get<uint8_t>(3 * n);
-  if (!d_img || !d_u8) return fail("pt_stage_save_u8: out of device memory");
-  HIP_OK(hipMemcpy(d_img, rgb_sum, 3 * n * sizeof(float), hipMemcpyHostToDevice));
-  g.k->save_u8(g.stream, (int)n, w, samples, d_img, d_u8);
-  HIP_OK(hipStreamSynchronize(g.stream));
-  HIP_OK(hipMemcpy(rgb8, d_u8, 3 * n, hipMemcpyDeviceToHost));
-  return 0;
-}
-
-// The filter kernels on caller-supplied host arrays (tests: frames a renderer would never produce)
-int pt_stage_denoise(int w, int rows, const float* rgb_sum, const float* planes, float samples, const PtDenoiseOptions* opt, float* rgb_avg) {
-  if (need(g_default, "pt_stage_denoise")) return -1;
-  Ctx& g = *g_default;
-  if (w <= 0 || rows <= 0 || rows >= 32768 || (int64_t)w * rows > (1ll << 30) || !rgb_sum || !planes || !rgb_avg) return fail("pt_stage_denoise: bad argument");
-  ptdn::Params P{};
-  if (pt_denoise_resolve("pt_stage_denoise", samples, opt, &P)) return -1;
-  HIP_OK(hipSetDevice(g.device));
-  Scratch sc;
-  const size_t n = (size_t)w * rows;
-  float* d_img = sc.get<float>(3 * n);
-  float* d_planes = sc.get<float>(4 * PT_FEATURE_PLANES * n);
-  char* d_ws = sc.get<char>(pt_denoise_workspace_bytes(n));
-  if (!d_img || !d_planes || !d_ws) return fail("pt_stage_denoise: out of device memory");
-  HIP_OK(hipMemcpy(d_img, rgb_sum, 3 * n * sizeof(float), hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(d_planes, planes, 4 * PT_FEATURE_PLANES * n * sizeof(float), hipMemcpyHostToDevice));
-  const float* d_out = nullptr;
-  if (pt_denoise_launch(g.stream, w, rows, d_img, d_planes, samples, P, d_ws, &d_out)) return -1;
-  HIP_OK(hipStreamSynchronize(g.stream));
-  HIP_OK(hipMemcpy(rgb_avg, d_out, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
-  return 0;
-}
-
-// The guided filter's kernels on caller-supplied host arrays
-int pt_stage_denoise_guided(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, int groups, int64_t iters,
-                            const PtDenoiseOptions* opt, float* rgb_avg) {
-  if (need(g_default, "pt_stage_denoise_guided")) return -1;
-  Ctx& g = *g_default;
-  if (w <= 0 || rows <= 0 || rows >= 32768 || (int64_t)w * rows > (1ll << 30) || !rgb_sum || !planes || !noise_planes || !rgb_avg)
-    return fail("pt_stage_denoise_guided: bad argument");
-  ptdn::Params P{};
-  float Tf = 0.0f, Df = 0.0f;
-  if (pt_denoise_guided_resolve("pt_stage_denoise_guided", groups, iters, opt, &P, &Tf, &Df)) return -1;
-  HIP_OK(hipSetDevice(g.device));
-  Scratch sc;
-  const size_t n = (size_t)w * rows;
-  float* d_img = sc.get<float>(3 * n);
-  float* d_planes = sc.get<float>(4 * PT_FEATURE_PLANES * n);
-  float* d_noise = sc.get<float>(4 * PT_NOISE_PLANES * n);
-  char* d_ws = sc.get<char>(pt_denoise_workspace_bytes(n));
-  if (!d_img || !d_planes || !d_noise || !d_ws) return fail("pt_stage_denoise_guided: out of device memory");
-  HIP_OK(hipMemcpy(d_img, rgb_sum, 3 * n * sizeof(float), hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(d_planes, planes, 4 * PT_FEATURE_PLANES * n * sizeof(float), hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(d_noise, noise_planes, 4 * PT_NOISE_PLANES * n * sizeof(float), hipMemcpyHostToDevice));
-  const float* d_out = nullptr;
-  if (pt_denoise_guided_launch(g.stream, w, rows, d_img, d_planes, d_noise, Tf, Df, P, d_ws, &d_out)) return -1;
-  HIP_OK(hipStreamSynchronize(g.stream));
-  HIP_OK(hipMemcpy(rgb_avg, d_out, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
-  return 0;
-}
-
-// The selection's kernels on caller-supplied host arrays (pt_adaptive_select_host's arguments)
-int pt_stage_adaptive_select(int w, int rows, const float* noise_planes, const int32_t* counts, int m, int32_t* list) {
-  if (need(g_default, "pt_stage_adaptive_select")) return -1;
-  Ctx& g = *g_default;
-  if (pt_adaptive_check_select("pt_stage_adaptive_select", w, rows, noise_planes, counts, m, list)) return -1;
-  HIP_OK(hipSetDevice(g.device));
-  Scratch sc;
-  const size_t n = (size_t)w * rows;
-  float* d_plane0 = sc.get<float>(4 * n);  // the selection reads plane 0 only
-  int32_t* d_counts = sc.get<int32_t>(2 * n);
-  char* d_ws = sc.get<char>(pt_adaptive_select_bytes(n));
-  int32_t* d_list = sc.get<int32_t>((size_t)m);
-  if (!d_plane0 || !d_counts || !d_ws || !d_list) return fail("pt_stage_adaptive_select: out of device memory");
-  HIP_OK(hipMemcpy(d_plane0, noise_planes, 4 * n * sizeof(float), hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(d_counts, counts, 2 * n * sizeof(int32_t), hipMemcpyHostToDevice));
-  HIP_OK(hipMemset(d_list, 0xff, (size_t)m * sizeof(int32_t)));  // an entry nobody wrote shows as -1
-  if (pt_adaptive_select_launch(g.stream, w, rows, d_plane0, d_counts, m, d_ws, d_list)) return -1;
-  HIP_OK(hipStreamSynchronize(g.stream));
-  HIP_OK(hipMemcpy(list, d_list, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost));
-  return 0;
-}
-
-// The worker context alone: iterations iter_first .. iter_first + iter_count - 1 of the m listed tile pixels (distinct, any order);
-// rgb_sum_host receives the group sum, m * 3 floats in list order.  Leaves image, folds and state of the renderer alone.
-int pt_stage_render_list(const int32_t* list, int m, int iter_first, int iter_count, float* rgb_sum_host) {
-  if (need(g_default, "pt_stage_render_list")) return -1;
-  Ctx& g = *g_default;
-  if (!list || !rgb_sum_host || m < 1 || m > g.N || iter_first < 1 || iter_count < 0 || (int64_t)iter_first + iter_count - 1 > INT32_MAX)
-    return fail("pt_stage_render_list: bad argument (a list of %d out of %d pixels, iterations %d, +%d)", m, g.N, iter_first, iter_count);
-  if (g.failed) return fail("pt_stage_render_list: an earlier batch of this context failed (%s); free it and create a new one", g_err.c_str());
-  if (g.stripe) return fail("pt_stage_render_list: a striped tile has no list form");
-  {
-    std::vector<uint8_t> seen((size_t)g.N, 0);
-    for (int i = 0; i < m; ++i) {
-      if (list[i] < 0 || list[i] >= g.N || seen[(size_t)list[i]]) return fail("pt_stage_render_list: list[%d] = %d is outside the tile or repeated", i, list[i]);
-      seen[(size_t)list[i]] = 1;
-    }
-  }
-  HIP_OK(hipSetDevice(g.device));
-  if (ensure_worker(g, m)) return -1;
-  HIP_OK(hipStreamSynchronize(g.stream));  // (the list may still be read by an earlier round)
-  HIP_OK(hipMemcpy(g.d_list, list, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice));
-  if (render_list(g, iter_first, iter_count)) return -1;
-  HIP_OK(hipMemcpyAsync(rgb_sum_host, g.worker->d_image, 3 * (size_t)m * sizeof(float), hipMemcpyDeviceToHost, g.stream));
-  return pt_ctx_sync(&g);
-}
 
 }  // extern "C"

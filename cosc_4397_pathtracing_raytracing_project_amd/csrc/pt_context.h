@@ -1,0 +1,213 @@
+// pt_context.h — the renderer context and the helpers shared by the translation units that work on it: pt_api.cpp (lifecycle,
+// run_batch, readback), pt_post.cpp (what reads or extends a rendered image) and pt_stage.cpp (the stage entry points of the tests).
+// Not part of the ABI; nothing outside csrc/ includes it.  The helpers live in namespace ptc, so the library exports them under
+// mangled names only.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <vector>
+
+#include "../../include/pt_amd.h"
+#include "pt_device.h"
+#include "pt_internal.h"
+#include "pt_kernels.h"
+#include "pt_tables.h"
+
+#define HIP_OK(expr)                                                                                      \
+  do {                                                                                                    \
+    hipError_t e_ = (expr);                                                                               \
+    if (e_ != hipSuccess) return pt_fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+  } while (0)
+
+struct EventPair {
+  hipEvent_t a, b;
+};
+
+// What a worker context (pt_post.cpp ensure_worker) takes from its parent in one assignment: the device and its stream, the kernels,
+// the scene as uploaded, every option that decides how a batch is traced.  A member a batch depends on and that does not follow from
+// the tile belongs here, so that a worker cannot miss it.  Ownership stays: PtContext::borrowed keeps a worker from freeing the stream,
+// and the device memory behind `scene` and `grids` is in the parent's `allocs`.
+struct PtShared {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  const ptk::KernelApi* k = nullptr;  // kernels of the selected arithmetic mode
+  int arith = 0;
+  int num_cus = 0;
+  // scene
+  PtCamera cam{};
+  ptd::Camera dcam{};
+  int depth = 0;
+  ptk::SceneTables scene{};  // what upload_tables() put on the device; tables() adds the fields that options and launches decide
+  int lds_table_bytes = -1;        // SceneTables::lds_table_bytes
+  int lds_table_forced = -1;       // PtOptions.lds_table_kb in bytes; -1: KernelApi::lds_table_limit decides
+  int primary_pieces = 0;          // BatchInfo::primary_pieces forced by PtOptions.primary_pieces; 0: run_batch decides
+  int primary_share = 0;           // BatchInfo::primary_share forced through PT_PRIMARY_PIECES; 0: automatic (primary_share_of)
+  int paths_pieces = 0;            // BatchInfo::paths_pieces (PtOptions.paths_pieces, paths_min_piece)
+  // Uniform grids over the leaf boxes (pt::build_grid; SceneTables::grid_*), large scenes where one beats the BVH scan: setup()
+  // uploads the candidates of pt::build_scene_tables, choose_traversal() times them, keeps the fastest and frees the rest.
+  struct DeviceGrid {
+    pt::GridShape shape;
+    size_t guard;  // empty cells in front of (and behind) the cell table proper
+    const uint32_t* d_start;
+    const ptd::Node* d_items;
+    const ptd::Node* d_items_b;  // == d_items unless the build wants centre / half extent
+    size_t bytes;
+  };
+  std::vector<DeviceGrid> grids;
+  size_t grid_pick = 0;  // grids[grid_pick] is the one the kernels walk (when grids is not empty)
+  int tight_leaves = 0;  // sphere leaves with a tightened traversal box (pt::tighten_sphere_leaves)
+  bool grid_enabled = true;      // the outcome of choose_traversal()
+  int cap_bpc = 8;
+  bool legacy = false;
+  int debug_flags = 0;
+  bool fuse_primary = true, fuse_bounces = true;
+  bool aa_jitter = false;
+};
+
+// One renderer instance = one device, one stream, one tile of the framebuffer.  The reference keeps this state in
+// file-scope statics (pathtrace.cu:446-456); here it is an object so that one process can drive several GPUs
+// (pt_group_*, pt_group.cpp) — the old single-instance entry points act on a default context.
+struct PtContext : PtShared {
+  // tile / batch geometry
+  int N = 0, pixel_begin = 0, K = 1;
+  int slot_shift = 0;  // BatchInfo::slot_shift
+  int stripe = 0, stripe_stride = 0;
+  int grid = 0;  // widest persistent grid (stats / test stages)
+  int grid_gen = 0, grid_isect = 0, grid_shade = 0;
+  ptd::Queues qs{};
+  int64_t stride = 0;  // plane stride = Q*cap
+  // device memory
+  std::vector<void*> allocs;
+  int64_t device_bytes = 0;
+  float probe_ms[2] = {0.f, 0.f};  // a few iterations with the BVH scan / with the (fastest) grid, as timed by choose_traversal()
+  int grid_primary = 0, grid_paths = 0;
+  ptd::PathBuf buf[2]{};
+  ptd::HitBuf hits{};
+  ptd::RetireBuf ret{};  // retirement records + fill levels (pt_device.h)
+  float* d_image = nullptr;
+  // First-hit feature buffers (pt_ctx_render_features): PT_FEATURE_PLANES planes of N float4 sums; absent until the first feature pass
+  float4* d_feat = nullptr;
+  int grid_features = 0;
+  void* d_denoise = nullptr;  // workspace of pt_ctx_denoise (pt_denoise_workspace_bytes(N)); absent until the first denoise call
+  // Noise estimate (pt_ctx_noise_fold, csrc/pt_noise.hip): planes, partial sums and their sum (pt_noise_state_bytes(N)); absent until the first fold
+  void* d_noise = nullptr;
+  int noise_groups = 0;      // M: folds since pt_init / pt_clear that had something to fold
+  int64_t noise_iters = 0;   // T: iterations those folds took
+  int64_t rendered = 0;      // iterations handed to pt_ctx_render since pt_init / pt_clear (samples is zeroed by pt_reset_stats; setup()'s timing batches never count)
+  // Convergence metric (PtOptions.convergence, pt_kernels.h ConvInfo): all of it absent when the option is 0
+  int conv = 0;                // the option: N > 0 capture the frame at iteration N, -1 supplied
+  bool conv_live = false;      // off while setup() renders its timing batches: they leave no trace in the curve or the frame
+  bool conv_have_ref = false;  // d_ref holds the frame (supplied, or the batch that captures it has been submitted)
+  int conv_last = 0;           // highest iteration submitted with the metric on
+  float* d_ref = nullptr;      // [N][3]
+  double* d_partial = nullptr;  // [K][Q][kConvWaves]
+  double* d_sse = nullptr;      // [PT_CONVERGENCE_CAPACITY], iteration i at i - 1; all bits set (a NaN) = no value
+  uint8_t* d_rgb8 = nullptr;  // lazily allocated output of pt_ctx_save_u8
+  int32_t* d_cnt = nullptr;
+  unsigned long long* d_stats = nullptr;
+  // timing
+  bool time_kernels = false;
+  std::vector<EventPair> free_events, pending_isect, pending_render;
+  double isect_ms = 0, render_ms = 0;
+  int64_t isect_launches = 0;
+  int64_t samples = 0;
+  // A batch that failed half-way (a launch or an event call returned an error) leaves counters and record regions in an
+  // undefined state: the context refuses further renders instead of appending past them.
+  bool failed = false;
+  // Adaptive sampling (pt_ctx_adaptive_round, csrc/pt_adaptive.hip): all of it absent until the first round (d_list and the worker: or
+  // until pt_stage_render_list)
+  int opt_iters_per_batch = 0, opt_num_queues = 0;  // PtOptions, as given: a worker plans its own batches from them
+  bool borrowed = false;           // a worker context: what PtShared holds belongs to its parent
+  const int32_t* list = nullptr;   // BatchInfo::list of this context's batches (a worker's: the parent's d_list)
+  PtContext* worker = nullptr;     // the context that renders the pixel list; its tile is the list's m pixels, its d_image the group sum Sw
+  int32_t* d_list = nullptr;       // N entries, the first worker->N in use
+  void* d_acnt = nullptr;          // the plane cnt: N * ptad::Cnt
+  void* d_select = nullptr;        // pt_adaptive_select_bytes(N)
+  float* d_resolved = nullptr;     // [N][3], output of pt_ctx_resolve_device; absent until the first resolve
+  bool adaptive = false;           // the adaptive state: from the first round to pt_clear
+  int adaptive_rounds = 0;
+  int64_t adaptive_last = 0;       // highest iteration number folded or merged
+};
+
+namespace ptc {
+using Ctx = PtContext;
+
+PtContext* default_context();  // the instance behind pt_init / pt_render / pt_free, or nullptr
+
+template <typename T>
+int dalloc(Ctx& g, T** out, size_t count) {  // owned by the context: destroy() frees it
+  void* p = nullptr;
+  size_t bytes = std::max<size_t>(count * sizeof(T), 16);
+  hipError_t e = hipMalloc(&p, bytes);
+  if (e != hipSuccess) return pt_fail("hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
+  g.allocs.push_back(p);
+  g.device_bytes += (int64_t)bytes;
+  *out = reinterpret_cast<T*>(p);
+  return 0;
+}
+// A buffer that exists from its first use on: `bytes` through dalloc if `p` is still null, then zeroed as `zero` says or left as it comes.
+enum class Zero { none, blocking, on_stream };
+template <typename T>
+int ensure(Ctx& g, T*& p, size_t bytes, Zero zero = Zero::none) {
+  if (p) return 0;
+  char* q = nullptr;
+  if (dalloc(g, &q, bytes)) return -1;
+  p = reinterpret_cast<T*>(q);
+  if (zero == Zero::blocking) HIP_OK(hipMemset(q, 0, bytes));
+  if (zero == Zero::on_stream) HIP_OK(hipMemsetAsync(q, 0, bytes, g.stream));
+  return 0;
+}
+struct Scratch {  // frees on scope exit
+  std::vector<void*> p;
+  ~Scratch() { for (void* q : p) (void)hipFree(q); }
+  template <typename T>
+  T* get(size_t n) {
+    void* q = nullptr;
+    if (hipMalloc(&q, std::max<size_t>(n * sizeof(T), 16)) != hipSuccess) return nullptr;
+    p.push_back(q);
+    return reinterpret_cast<T*>(q);
+  }
+};
+
+int need(const PtContext* c, const char* who);  // the context exists, or the refusal under the public name `who`
+// The rest of an entry point's prologue: the requirements in `req`, checked in the order of the enumerators; the first one not met is
+// the refusal, 0 when all hold.  An entry point whose own checks lie between two of them, or that orders them differently, calls
+// admit() once per run of requirements: the order of an entry point's refusals is its behaviour.
+enum Require : unsigned {
+  kNotFailed = 1,   // no batch of the context failed half-way
+  kUniform = 2,     // not in the adaptive state
+  kWholeRows = 4,   // the tile is rows of the image, whole and one after the other
+  kFoldedAll = 8,   // nothing rendered since the last fold
+  kOnDevice = 16,   // not a refusal: makes the context's device current
+};
+int admit(const PtContext& g, const char* who, unsigned req);
+
+// The host form of an entry point: refuses a null buffer, has `source` name the device buffer (the `_device` form of the entry point,
+// or a readback's own check; nonzero: refused), copies per_pixel * N elements of it to `host` on the context's stream and synchronises.
+template <typename T, typename Source>
+int copy_out(PtContext* c, const char* who, T* host, size_t per_pixel, Source source, hipMemcpyKind kind = hipMemcpyDeviceToHost) {
+  if (!host) return pt_fail("%s: null buffer", who);
+  const T* d = nullptr;
+  if (source(&d)) return -1;
+  HIP_OK(hipSetDevice(c->device));
+  HIP_OK(hipMemcpyAsync(host, d, per_pixel * (size_t)c->N * sizeof(T), kind, c->stream));
+  return pt_ctx_sync(c);
+}
+
+// pt_api.cpp
+ptk::SceneTables tables(const Ctx& g);
+ptk::BatchInfo tile_batch(const Ctx& g, int iter_first, int K);  // BatchInfo's iterations and the fields that describe the tile
+int run_batch(Ctx& g, int iter_first, int kb);
+int batch_iters_for(int iters_per_batch, int N, int* slot_shift);
+int plan_batches(Ctx& g, const PtOptions& opt);
+void plan_launch(Ctx& g);
+int alloc_batch_buffers(Ctx& g);
+int get_events(Ctx& g, EventPair* ev);
+ptd::Queues single_queue(const Ctx& g, int n);
+void destroy(Ctx* c);
+// pt_post.cpp: the worker context of adaptive sampling
+int ensure_worker(Ctx& g, int m);                         // g.worker: a context whose tile is the first m entries of g.d_list
+int render_list(Ctx& g, int iter_first, int iter_count);  // those iterations of the listed pixels into the worker's cleared sum
+}  // namespace ptc

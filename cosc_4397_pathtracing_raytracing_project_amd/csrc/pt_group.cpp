@@ -27,15 +27,8 @@
 #include <string>
 #include <vector>
 
-#include "../../include/pt_amd.h"
+#include "pt_context.h"  // HIP_OK; a group reaches its contexts through the C ABI only
 #include "pt_denoise.h"
-#include "pt_internal.h"
-
-#define HIP_OK(expr)                                                                                      \
-  do {                                                                                                    \
-    hipError_t e_ = (expr);                                                                               \
-    if (e_ != hipSuccess) return pt_fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
 #define NCCL_OK(expr)                                                                                      \
   do {                                                                                                     \
     ncclResult_t r_ = (expr);                                                                              \

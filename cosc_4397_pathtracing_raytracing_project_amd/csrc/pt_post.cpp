@@ -1,0 +1,303 @@
+// pt_post.cpp — what reads or extends a rendered image, on a context (pt_context.h): the first-hit feature buffers, the two
+// edge-avoiding filters, the noise estimate and render-until, adaptive sampling with its worker context, and resolve.  The kernels
+// are pt_features.inc (through KernelApi), pt_denoise.hip, pt_noise.hip and pt_adaptive.hip; this file holds their host side: what
+// an entry point refuses, the buffers that exist from the first use on, and the launches.
+#include <cmath>
+
+#include "pt_adaptive.h"
+#include "pt_context.h"
+#include "pt_denoise.h"
+#include "pt_noise.h"
+
+using namespace ptc;
+
+// pt_internal.h (pt_group_denoise_guided: the group refuses what its contexts would refuse, before anything is exchanged)
+int64_t pt_ctx_unfolded_iterations(const PtContext* c) { return c ? c->rendered - c->noise_iters : 0; }
+
+extern "C" {
+
+// ---- first-hit feature buffers (csrc/pt_features.inc) --------------------------------------------
+int pt_ctx_render_features(PtContext* c, int iter_first, int iter_count) {
+  if (need(c, "pt_render_features")) return -1;
+  Ctx& g = *c;
+  if (iter_first < 1 || iter_count < 0 || (int64_t)iter_first + iter_count - 1 > INT32_MAX)
+    return pt_fail("pt_render_features: iterations %d, +%d: the first is >= 1, the count >= 0", iter_first, iter_count);
+  if (admit(g, "pt_render_features", kNotFailed | kOnDevice)) return -1;
+  const ptk::SceneTables sc = tables(g);
+  static_assert(sizeof(float4) == 16, "a feature plane holds 16 bytes per pixel");
+  if (ensure(g, g.d_feat, (size_t)PT_FEATURE_PLANES * g.N * sizeof(float4), Zero::on_stream)) return -1;  // the first feature pass of the context
+  if (iter_count == 0) return 0;
+  // one wave per group of 64 pixels, no more workgroups than are resident (the table placement can differ between calls: debug grids)
+  const int groups = (g.N + 63) / 64;
+  g.grid_features = std::min((groups + ptk::kWavesPerBlock - 1) / ptk::kWavesPerBlock,
+                             g.num_cus * std::min(g.cap_bpc, g.k->resident_blocks_per_cu(ptk::kFeatures, sc)));
+  g.k->features(g.stream, g.grid_features, sc, g.dcam, tile_batch(g, iter_first, iter_count), g.d_feat);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int pt_ctx_readback_features(PtContext* c, float* planes_host) {
+  if (need(c, "pt_readback_features")) return -1;
+  return copy_out(c, "pt_readback_features", planes_host, 4 * PT_FEATURE_PLANES, [&](const float** d) {
+    return (*d = pt_ctx_device_features(c)) ? 0 : pt_fail("pt_readback_features: no feature pass has been rendered (pt_render_features)");
+  });
+}
+
+const float* pt_ctx_device_features(PtContext* c) { return c ? reinterpret_cast<const float*>(c->d_feat) : nullptr; }
+
+// ---- edge-avoiding filter over the image and the feature buffers (csrc/pt_denoise.hip) ------------------------
+int pt_ctx_denoise_device(PtContext* c, float samples, const PtDenoiseOptions* opt, const float** rgb_dev) {
+  if (need(c, "pt_denoise")) return -1;
+  Ctx& g = *c;
+  if (admit(g, "pt_denoise", kNotFailed | kUniform | kWholeRows)) return -1;
+  const int W = g.cam.resolution[0];
+  if (!g.d_feat) return pt_fail("pt_denoise: no feature pass has been rendered (pt_render_features)");
+  ptdn::Params P{};
+  if (pt_denoise_resolve("pt_denoise", samples, opt, &P)) return -1;
+  HIP_OK(hipSetDevice(g.device));
+  if (ensure(g, g.d_denoise, pt_denoise_workspace_bytes((size_t)g.N))) return -1;  // the first denoise call of the context, of either kind
+  return pt_denoise_launch(g.stream, W, g.N / W, g.d_image, reinterpret_cast<const float*>(g.d_feat), samples, P, g.d_denoise, rgb_dev);
+}
+int pt_ctx_denoise(PtContext* c, float samples, const PtDenoiseOptions* opt, float* rgb_avg_host) {
+  return copy_out(c, "pt_denoise", rgb_avg_host, 3, [&](const float** d) { return pt_ctx_denoise_device(c, samples, opt, d); });
+}
+
+// The variance-guided form: the same tile, the same workspace, plus the planes of the noise estimate — which must describe the image
+// as it is, so iterations rendered since the last fold are refused rather than filtered with a stale variance.
+int pt_ctx_denoise_guided_device(PtContext* c, const PtDenoiseOptions* opt, const float** rgb_dev) {
+  if (need(c, "pt_denoise_guided")) return -1;
+  Ctx& g = *c;
+  if (admit(g, "pt_denoise_guided", kNotFailed | kUniform | kWholeRows)) return -1;
+  const int W = g.cam.resolution[0];
+  if (!g.d_feat) return pt_fail("pt_denoise_guided: no feature pass has been rendered (pt_render_features)");
+  if (!g.d_noise || g.noise_groups < 1) return pt_fail("pt_denoise_guided: nothing has been folded (pt_noise_fold)");
+  if (admit(g, "pt_denoise_guided", kFoldedAll)) return -1;
+  ptdn::Params P{};
+  float Tf = 0.0f, Df = 0.0f;
+  if (pt_denoise_guided_resolve("pt_denoise_guided", g.noise_groups, g.noise_iters, opt, &P, &Tf, &Df)) return -1;
+  HIP_OK(hipSetDevice(g.device));
+  if (ensure(g, g.d_denoise, pt_denoise_workspace_bytes((size_t)g.N))) return -1;
+  return pt_denoise_guided_launch(g.stream, W, g.N / W, g.d_image, reinterpret_cast<const float*>(g.d_feat), static_cast<const float*>(g.d_noise), Tf, Df, P,
+                                  g.d_denoise, rgb_dev);
+}
+int pt_ctx_denoise_guided(PtContext* c, const PtDenoiseOptions* opt, float* rgb_avg_host) {
+  return copy_out(c, "pt_denoise_guided", rgb_avg_host, 3, [&](const float** d) { return pt_ctx_denoise_guided_device(c, opt, d); });
+}
+
+// ---- noise estimate from batch sums, render until a target PSNR (csrc/pt_noise.hip) ----------------------------
+int pt_ctx_noise_fold(PtContext* c) {
+  if (need(c, "pt_noise_fold")) return -1;
+  Ctx& g = *c;
+  if (admit(g, "pt_noise_fold", kNotFailed | kUniform)) return -1;
+  const int64_t n = g.rendered - g.noise_iters;
+  if (n <= 0) return 0;  // nothing rendered since the last fold
+  HIP_OK(hipSetDevice(g.device));
+  if (ensure(g, g.d_noise, pt_noise_state_bytes((size_t)g.N), Zero::on_stream)) return -1;  // the first fold of the context: zeroed like the image it starts from
+  if (pt_noise_launch(g.stream, g.N, g.d_image, g.d_noise, ptnz::fold_scalars(n, g.noise_groups + 1, g.noise_iters + n))) return -1;
+  g.noise_groups += 1;
+  g.noise_iters += n;
+  return 0;
+}
+
+int pt_ctx_get_noise(PtContext* c, double* sse, int* groups, int* iterations) {
+  if (need(c, "pt_get_noise")) return -1;
+  if (pt_ctx_sync(c)) return -1;
+  Ctx& g = *c;
+  if (sse) {
+    *sse = -1.0;
+    if (g.d_noise && g.noise_groups >= 2) {
+      const char* result = static_cast<const char*>(g.d_noise) + pt_noise_state_bytes((size_t)g.N) - sizeof(double);
+      HIP_OK(hipMemcpy(sse, result, sizeof(double), hipMemcpyDeviceToHost));
+    }
+  }
+  // (the adaptive state: the last merge's SSE_est lies where a fold's does; every round counts as a group)
+  if (groups) *groups = g.noise_groups + g.adaptive_rounds;
+  if (iterations) *iterations = (int)std::min<int64_t>(g.adaptive ? g.adaptive_last : g.noise_iters, INT32_MAX);
+  return 0;
+}
+
+int pt_ctx_readback_noise(PtContext* c, float* planes_host) {
+  if (need(c, "pt_readback_noise")) return -1;
+  return copy_out(c, "pt_readback_noise", planes_host, 4 * PT_NOISE_PLANES, [&](const float** d) {
+    return (*d = pt_ctx_device_noise(c)) ? 0 : pt_fail("pt_readback_noise: nothing has been folded (pt_noise_fold)");
+  });
+}
+
+const float* pt_ctx_device_noise(PtContext* c) { return c ? static_cast<const float*>(c->d_noise) : nullptr; }
+
+int pt_ctx_render_until(PtContext* c, int iter_first, int max_iters, int group_iters, float target_db, int* iters_done, float* psnr_db) {
+  if (need(c, "pt_render_until")) return -1;
+  Ctx& g = *c;
+  if (iter_first < 1 || max_iters < 1 || (int64_t)iter_first + max_iters - 1 > INT32_MAX || group_iters < 0 || !std::isfinite(target_db))
+    return pt_fail("pt_render_until: iterations %d, +%d in groups of %d until %g dB: the first is >= 1, the count >= 1, the group >= 0 (0 = a batch), the target finite",
+                iter_first, max_iters, group_iters, (double)target_db);
+  if (admit(g, "pt_render_until", kNotFailed | kUniform)) return -1;
+  const int group = group_iters ? group_iters : g.K;
+  int done = 0;
+  float psnr = -1.0f;
+  while (done < max_iters) {
+    const int n = std::min(group, max_iters - done);
+    if (pt_ctx_render(c, iter_first + done, n)) return -1;
+    done += n;
+    double sse = -1.0;
+    if (pt_ctx_noise_fold(c) || pt_ctx_get_noise(c, &sse, nullptr, nullptr)) return -1;
+    if (sse < 0.0) continue;  // one group says nothing about the spread
+    psnr = pt_psnr_from_sse(sse, g.N);
+    if (psnr > target_db) break;
+  }
+  if (iters_done) *iters_done = done;
+  if (psnr_db) *psnr_db = psnr;
+  return 0;
+}
+
+}  // extern "C"
+
+// ---- adaptive sampling: further groups over the noisiest pixels only (csrc/pt_adaptive.hip) -------------------------------
+namespace ptc {
+// The worker context for a list of m pixels: batches, queues, buffers and launch widths planned for N = m like any context's; the
+// scene tables, the grid or BVH choice and the LDS-table decision are the parent's (neither uploaded nor measured again, not owned).
+int ensure_worker(Ctx& g, int m) {
+  if (g.worker && g.worker->N == m) return 0;
+  if (g.worker) g.device_bytes -= g.worker->device_bytes, destroy(g.worker), g.worker = nullptr;
+  if (ensure(g, g.d_list, (size_t)g.N * sizeof(int32_t), Zero::blocking)) return -1;  // the list: every entry a tile pixel from the start
+  Ctx* w = new Ctx();
+  w->borrowed = true;
+  static_cast<PtShared&>(*w) = g;
+  PtOptions o{};
+  o.pixel_begin = g.pixel_begin, o.pixel_count = m;
+  o.iters_per_batch = g.opt_iters_per_batch, o.num_queues = g.opt_num_queues;  // 0: automatic for m pixels
+  if (plan_batches(*w, o)) return destroy(w), -1;
+  plan_launch(*w);
+  if (alloc_batch_buffers(*w)) return destroy(w), -1;
+  w->list = g.d_list;
+  g.worker = w;
+  g.device_bytes += w->device_bytes;
+  return 0;
+}
+
+// Iterations iter_first .. iter_first + iter_count - 1 of the listed pixels into the worker's cleared group sum.
+int render_list(Ctx& g, int iter_first, int iter_count) {
+  Ctx& w = *g.worker;
+  HIP_OK(hipMemsetAsync(w.d_image, 0, 3 * (size_t)w.N * sizeof(float), g.stream));
+  const int end = iter_first + iter_count;
+  for (int it = iter_first; it < end; it += w.K)
+    if (run_batch(w, it, std::min(w.K, end - it))) {
+      g.failed = true;
+      return -1;
+    }
+  return 0;
+}
+
+// Everything a round refuses, before anything is allocated or launched.  pt_render_adaptive asks with folds == false: without the
+// state of the folds, which its uniform groups establish, and with its own words about the first iteration (its group may be 0).
+static int adaptive_refusal(const Ctx& g, const char* who, int iter_first, int group_iters, float fraction, bool folds = true) {
+  if (admit(g, who, kNotFailed)) return -1;
+  if (folds && (iter_first < 1 || group_iters < 1 || (int64_t)iter_first + group_iters - 1 > INT32_MAX))
+    return pt_fail("%s: iterations %d, +%d: the first is >= 1, the group holds at least one", who, iter_first, group_iters);
+  if (!folds && iter_first < 1) return pt_fail("%s: the first iteration %d is not >= 1", who, iter_first);
+  if (!(fraction > 0.0f && fraction <= 1.0f)) return pt_fail("%s: fraction %g is not in (0, 1]", who, (double)fraction);
+  if (g.conv) return pt_fail("%s: the renderer was created with PtOptions.convergence = %d; the convergence metric follows whole iterations", who, g.conv);
+  if (admit(g, who, kWholeRows)) return -1;
+  if (g.adaptive || !folds) return 0;
+  if (g.noise_groups < 2) return pt_fail("%s: %d group(s) folded; the selection needs the noise estimate of at least 2 (pt_noise_fold)", who, g.noise_groups);
+  if (admit(g, who, kFoldedAll)) return -1;
+  if (g.noise_iters > INT32_MAX / 2) return pt_fail("%s: %lld iterations folded: the per-pixel counts are int32", who, (long long)g.noise_iters);
+  return 0;
+}
+}  // namespace ptc
+
+extern "C" {
+
+int pt_ctx_adaptive_round(PtContext* c, int iter_first, int group_iters, float fraction) {
+  if (need(c, "pt_adaptive_round")) return -1;
+  Ctx& g = *c;
+  if (adaptive_refusal(g, "pt_adaptive_round", iter_first, group_iters, fraction)) return -1;
+  HIP_OK(hipSetDevice(g.device));
+  const int W = g.cam.resolution[0];
+  if (!g.adaptive) {  // the first round since pt_init / pt_clear: every pixel has the fold's T and M
+    if (ensure(g, g.d_acnt, (size_t)g.N * sizeof(ptad::Cnt)) || ensure(g, g.d_select, pt_adaptive_select_bytes((size_t)g.N))) return -1;
+    if (pt_adaptive_init_counts_launch(g.stream, g.N, g.d_acnt, (int)g.noise_iters, g.noise_groups)) return -1;
+    g.adaptive = true;
+    g.adaptive_rounds = 0;
+    g.adaptive_last = g.noise_iters;
+  }
+  const int m = ptad::list_length((double)fraction, g.N);
+  if (ensure_worker(g, m)) return -1;
+  if (pt_adaptive_select_launch(g.stream, W, g.N / W, static_cast<const float*>(g.d_noise), g.d_acnt, m, g.d_select, g.d_list)) return -1;
+  if (render_list(g, iter_first, group_iters)) return -1;
+  if (pt_adaptive_merge_launch(g.stream, g.N, g.d_image, g.d_noise, g.d_acnt, g.d_list, m, g.worker->d_image, group_iters)) return -1;
+  g.adaptive_rounds += 1;
+  g.adaptive_last = std::max<int64_t>(g.adaptive_last, (int64_t)iter_first + group_iters - 1);
+  g.samples += (int64_t)group_iters * m;  // (live_rays and the kernel timings stay the parent's own launches')
+  return 0;
+}
+
+int pt_ctx_render_adaptive(PtContext* c, int iter_first, int max_iters, int group_iters, float fraction, float target_db, int* iters_done,
+                           int64_t* samples_done, float* psnr_db) {
+  if (need(c, "pt_render_adaptive")) return -1;
+  Ctx& g = *c;
+  if (max_iters < 1 || (int64_t)iter_first + max_iters - 1 > INT32_MAX || group_iters < 0 || !std::isfinite(target_db))
+    return pt_fail("pt_render_adaptive: iterations %d, +%d in groups of %d until %g dB: the count is >= 1, the group >= 0 (0 = a batch of the worker), the target finite",
+                iter_first, max_iters, group_iters, (double)target_db);
+  // what a round would refuse, apart from the state of the folds, which the uniform groups below establish
+  if (adaptive_refusal(g, "pt_render_adaptive", iter_first, group_iters, fraction, false)) return -1;
+  const int m = ptad::list_length((double)fraction, g.N);
+  // group_iters == 0: the iterations per batch a worker for m pixels plans (plan_batches' own function)
+  const int group = group_iters ? group_iters : g.worker && g.worker->N == m ? g.worker->K : batch_iters_for(g.opt_iters_per_batch, m, nullptr);
+  int done = 0;
+  int64_t samples = 0;
+  float psnr = -1.0f;
+  while (done < max_iters) {
+    const int n = std::min(group, max_iters - done);
+    if (!g.adaptive && g.noise_groups < 2) {  // a uniform group and its fold, as pt_render_until
+      if (pt_ctx_render(c, iter_first + done, n) || pt_ctx_noise_fold(c)) return -1;
+      samples += (int64_t)n * g.N;
+    } else {
+      if (!g.adaptive && g.rendered != g.noise_iters && pt_ctx_noise_fold(c)) return -1;  // iterations of the caller's, not yet folded
+      if (pt_ctx_adaptive_round(c, iter_first + done, n, fraction)) return -1;
+      samples += (int64_t)n * m;
+    }
+    done += n;
+    double sse = -1.0;
+    if (pt_ctx_get_noise(c, &sse, nullptr, nullptr)) return -1;
+    if (sse < 0.0) continue;  // one group says nothing about the spread
+    psnr = pt_psnr_from_sse(sse, g.N);
+    if (psnr > target_db) break;
+  }
+  if (iters_done) *iters_done = done;
+  if (samples_done) *samples_done = samples;
+  if (psnr_db) *psnr_db = psnr;
+  return 0;
+}
+
+int pt_ctx_readback_adaptive(PtContext* c, int32_t* counts) {
+  if (need(c, "pt_readback_adaptive")) return -1;
+  if (!counts) return pt_fail("pt_readback_adaptive: null buffer");
+  Ctx& g = *c;
+  if (!g.adaptive) {  // the uniform state: the fold's T and M for every pixel
+    if (pt_ctx_sync(c)) return -1;
+    for (size_t p = 0; p < (size_t)g.N; ++p) counts[2 * p] = (int32_t)std::min<int64_t>(g.noise_iters, INT32_MAX), counts[2 * p + 1] = g.noise_groups;
+    return 0;
+  }
+  static_assert(sizeof(ptad::Cnt) == 2 * sizeof(int32_t), "pt_amd.h: T_p and M_p per pixel");
+  return copy_out(c, "pt_readback_adaptive", counts, 2, [&](const int32_t** d) { return *d = static_cast<const int32_t*>(g.d_acnt), 0; });
+}
+
+int pt_ctx_resolve_device(PtContext* c, const float** rgb_dev) {
+  if (need(c, "pt_resolve")) return -1;
+  Ctx& g = *c;
+  if (admit(g, "pt_resolve", kNotFailed)) return -1;
+  if (g.noise_groups < 1) return pt_fail("pt_resolve: nothing has been folded (pt_noise_fold): the sample counts are the folds'");
+  if (admit(g, "pt_resolve", kFoldedAll)) return -1;
+  if (g.noise_iters > INT32_MAX) return pt_fail("pt_resolve: %lld iterations folded", (long long)g.noise_iters);
+  HIP_OK(hipSetDevice(g.device));
+  if (ensure(g, g.d_resolved, 3 * (size_t)g.N * sizeof(float))) return -1;
+  if (pt_adaptive_resolve_launch(g.stream, g.N, g.d_image, g.adaptive ? g.d_acnt : nullptr, (int)g.noise_iters, g.d_resolved)) return -1;
+  if (rgb_dev) *rgb_dev = g.d_resolved;
+  return 0;
+}
+int pt_ctx_resolve(PtContext* c, float* rgb_avg_host) {
+  return copy_out(c, "pt_resolve", rgb_avg_host, 3, [&](const float** d) { return pt_ctx_resolve_device(c, d); });
+}
+
+}  // extern "C"

@@ -1,0 +1,268 @@
+// pt_stage.cpp — the stage entry points (pt_stage_*) of the tests: single kernels of the pipeline on caller-supplied host arrays.
+// They act on the default context (pt_context.h) and keep nothing: every device buffer is scratch, freed on return.  The C ABI of
+// the stages takes plain SoA float arrays ([3][n]); the kernels stream three planes of 16-byte path records (ptd::PathBuf), so the
+// stage wrappers pack / unpack on the host.
+#include "pt_context.h"
+#include "pt_denoise.h"
+#include "pt_scene.h"
+
+using namespace ptc;
+
+namespace {
+// A scratch device copy of host[0 .. n): *out, or the refusal under the stage's name.
+template <typename T>
+int device_copy(Scratch& sc, const char* who, const T* host, size_t n, T** out) {
+  if (!(*out = sc.get<T>(n))) return pt_fail("%s: out of device memory", who);
+  HIP_OK(hipMemcpy(*out, host, n * sizeof(T), hipMemcpyHostToDevice));
+  return 0;
+}
+// Scratch hit records for `cap` paths; false when the device has no room.
+bool scratch_hits(Scratch& sc, size_t cap, ptd::HitBuf* hb) {
+  hb->stride = cap;
+  hb->t = sc.get<float>(cap);
+  hb->n = sc.get<float>(3 * cap);
+  hb->mat = sc.get<int32_t>(cap);
+  hb->p = sc.get<float>(3 * cap);
+  return hb->t && hb->n && hb->mat && hb->p;
+}
+
+struct StagePaths {
+  ptd::PathBuf pb{};
+  std::vector<ptd::Word4> host;
+  size_t cap = 0;
+  bool alloc(Scratch& sc, size_t cap_) {
+    cap = cap_;
+    pb.stride = (int64_t)cap;
+    pb.r = sc.get<ptd::Word4>(3 * cap);
+    host.assign(3 * cap, ptd::Word4{0.f, 0.f, 0.f, 0.f});
+    return pb.r != nullptr;
+  }
+  void pack(int n, const float* o, const float* d, const float* c) {  // arrays are [3][n]; null = zeros
+    for (int i = 0; i < n; ++i) {
+      auto at = [&](const float* a, int k) { return a ? a[(size_t)k * n + i] : 0.0f; };
+      host[i] = ptd::Word4{at(o, 0), at(o, 1), at(o, 2), at(d, 0)};
+      host[cap + i] = ptd::Word4{at(d, 1), at(d, 2), at(c, 0), at(c, 1)};
+      reinterpret_cast<float*>(&host[2 * cap])[(size_t)i * (ptd::kPathPlane2Bytes / 4)] = at(c, 2);
+    }
+  }
+  int upload() { return hipMemcpy(pb.r, host.data(), host.size() * sizeof(ptd::Word4), hipMemcpyHostToDevice) == hipSuccess ? 0 : -1; }
+  int download() { return hipMemcpy(host.data(), pb.r, host.size() * sizeof(ptd::Word4), hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1; }
+  void unpack(int n, float* o, float* d, float* c) const {
+    for (int i = 0; i < n; ++i) {
+      const ptd::Word4 &w0 = host[i], &w1 = host[cap + i];
+      const float cz = reinterpret_cast<const float*>(&host[2 * cap])[(size_t)i * (ptd::kPathPlane2Bytes / 4)];
+      if (o) o[i] = w0.x, o[(size_t)n + i] = w0.y, o[2 * (size_t)n + i] = w0.z;
+      if (d) d[i] = w0.w, d[(size_t)n + i] = w1.x, d[2 * (size_t)n + i] = w1.y;
+      if (c) c[i] = w1.z, c[(size_t)n + i] = w1.w, c[2 * (size_t)n + i] = cz;
+    }
+  }
+};
+
+// What the two filter stages share: the frame and its feature planes (and the noise planes of the guided form) up, `launch` with
+// the device arrays and a workspace, the filtered frame down.
+template <typename Launch>
+int filter_stage(Ctx& g, const char* who, size_t n, const float* rgb_sum, const float* planes, const float* noise_planes, float* rgb_avg, Launch launch) {
+  HIP_OK(hipSetDevice(g.device));
+  Scratch sc;
+  float *d_img = nullptr, *d_planes = nullptr, *d_noise = nullptr;
+  char* d_ws = sc.get<char>(pt_denoise_workspace_bytes(n));
+  if (!d_ws) return pt_fail("%s: out of device memory", who);
+  if (device_copy(sc, who, rgb_sum, 3 * n, &d_img) || device_copy(sc, who, planes, 4 * PT_FEATURE_PLANES * n, &d_planes)) return -1;
+  if (noise_planes && device_copy(sc, who, noise_planes, 4 * PT_NOISE_PLANES * n, &d_noise)) return -1;
+  const float* d_out = nullptr;
+  if (launch(d_img, d_planes, d_noise, d_ws, &d_out)) return -1;
+  HIP_OK(hipStreamSynchronize(g.stream));
+  HIP_OK(hipMemcpy(rgb_avg, d_out, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int pt_stage_generate(int pix_begin, int n, float* origin, float* dir) {
+  if (need(default_context(), "pt_stage_generate")) return -1;
+  Ctx& g = *default_context();
+  if (n <= 0) return 0;
+  HIP_OK(hipSetDevice(g.device));
+  Scratch sc;
+  ptd::Queues qs = single_queue(g, n);
+  StagePaths sp;
+  int32_t* cnt = sc.get<int32_t>(16);
+  if (!sp.alloc(sc, (size_t)qs.cap) || !cnt) return pt_fail("pt_stage_generate: out of device memory");
+  ptk::BatchInfo b{};
+  b.iter_first = 1, b.K = 1, b.N = n, b.pixel_begin = pix_begin, b.trace_depth = g.depth;
+  b.slot_shift = 30;
+  b.aa_jitter = g.aa_jitter ? 1 : 0;
+  g.k->generate(g.stream, g.grid, g.dcam, b, qs, sp.pb, cnt);
+  HIP_OK(hipStreamSynchronize(g.stream));
+  if (sp.download()) return pt_fail("pt_stage_generate: download failed");
+  sp.unpack(n, origin, dir, nullptr);
+  return 0;
+}
+
+int pt_stage_intersect(int n, const float* origin, const float* dir, float* t, float* normal, int32_t* material,
+                       float* point) {
+  if (need(default_context(), "pt_stage_intersect")) return -1;
+  Ctx& g = *default_context();
+  if (n <= 0) return 0;
+  if (g.tight_leaves > 0) {
+    // the tightened sphere boxes of a large scene are sized for ray origins inside the scene bounds or at the camera
+    // (sphere_tight_box): rays from elsewhere could lose grazing hits, so they are refused rather than traced differently
+    double olo[3], ohi[3];
+    pt::origin_region(g.scene.root_min, g.scene.root_max, g.cam.position, olo, ohi);
+    for (int i = 0; i < n; ++i)
+      for (int a = 0; a < 3; ++a) {
+        const float v = origin[(size_t)a * n + i];
+        if (!(v >= olo[a] && v <= ohi[a]))
+          return pt_fail("pt_stage_intersect: ray %d starts outside the scene bounds (this scene's sphere leaves are tightened for origins inside them; "
+                      "PtOptions.debug_flags 2048 keeps the reference's boxes)", i);
+      }
+  }
+  HIP_OK(hipSetDevice(g.device));
+  Scratch sc;
+  ptd::Queues qs = single_queue(g, n);
+  const size_t cap = qs.cap;
+  StagePaths sp;
+  const bool have_paths = sp.alloc(sc, cap);
+  ptd::HitBuf hb{};
+  int32_t* cnt = sc.get<int32_t>(16);
+  if (!have_paths || !scratch_hits(sc, cap, &hb) || !cnt) return pt_fail("pt_stage_intersect: out of device memory");
+  sp.pack(n, origin, dir, nullptr);
+  if (sp.upload()) return pt_fail("pt_stage_intersect: upload failed");
+  HIP_OK(hipMemcpy(cnt, &n, 4, hipMemcpyHostToDevice));
+  g.k->intersect(g.stream, g.grid, tables(g), qs, cnt, sp.pb, hb, g.legacy, false);
+  HIP_OK(hipStreamSynchronize(g.stream));
+  HIP_OK(hipMemcpy(t, hb.t, (size_t)n * 4, hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(material, hb.mat, (size_t)n * 4, hipMemcpyDeviceToHost));
+  for (int c = 0; c < 3; ++c) {
+    HIP_OK(hipMemcpy(normal + (size_t)c * n, hb.n + c * cap, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(point + (size_t)c * n, hb.p + c * cap, (size_t)n * 4, hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+
+int pt_stage_shade(int n, int depth, const int32_t* iter, const int32_t* pixel, const float* t, const float* normal,
+                   const int32_t* material, const float* point, float* origin, float* dir, float* color,
+                   int32_t* alive) {
+  if (need(default_context(), "pt_stage_shade")) return -1;
+  Ctx& g = *default_context();
+  if (n <= 0) return 0;
+  if (depth < 0 || depth >= g.depth) return pt_fail("pt_stage_shade: depth %d outside [0,%d)", depth, g.depth);
+  for (int i = 0; i < n; ++i)
+    if (t[i] >= 0.0f && (material[i] < 0 || material[i] >= g.scene.num_mats))
+      return pt_fail("pt_stage_shade: material id %d out of range at %d", material[i], i);
+  HIP_OK(hipSetDevice(g.device));
+  Scratch sc;
+  const size_t cap = n;
+  StagePaths sp;
+  const bool have_paths = sp.alloc(sc, cap);
+  ptd::HitBuf hb{};
+  int32_t *d_iter = nullptr, *d_pix = nullptr, *d_alive = sc.get<int32_t>(cap);
+  if (!have_paths || !scratch_hits(sc, cap, &hb) || !d_alive) return pt_fail("pt_stage_shade: out of device memory");
+  const size_t b1 = (size_t)n * 4, b3 = 3 * b1;
+  sp.pack(n, origin, dir, color);
+  if (sp.upload()) return pt_fail("pt_stage_shade: upload failed");
+  HIP_OK(hipMemcpy(hb.t, t, b1, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(hb.n, normal, b3, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(hb.mat, material, b1, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(hb.p, point, b3, hipMemcpyHostToDevice));
+  if (device_copy(sc, "pt_stage_shade", iter, cap, &d_iter) || device_copy(sc, "pt_stage_shade", pixel, cap, &d_pix)) return -1;
+  g.k->shade_stage(g.stream, tables(g), g.depth, depth, n, d_iter, d_pix, hb, sp.pb, d_alive);
+  HIP_OK(hipStreamSynchronize(g.stream));
+  if (sp.download()) return pt_fail("pt_stage_shade: download failed");
+  sp.unpack(n, origin, dir, color);
+  HIP_OK(hipMemcpy(alive, d_alive, b1, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// k_save_u8 on a caller-supplied SUM image of whole rows (tests: pins the device conversion to the reference writer's bytes)
+int pt_stage_save_u8(int w, int h, float samples, const float* rgb_sum, uint8_t* rgb8) {
+  if (need(default_context(), "pt_stage_save_u8")) return -1;
+  Ctx& g = *default_context();
+  if (w <= 0 || h <= 0 || h >= 32768 || !rgb_sum || !rgb8 || !(samples > 0.0f)) return pt_fail("pt_stage_save_u8: bad argument");
+  HIP_OK(hipSetDevice(g.device));
+  Scratch sc;
+  const size_t n = (size_t)w * h;
+  float* d_img = nullptr;
+  uint8_t* d_u8 = sc.get<uint8_t>(3 * n);
+  if (!d_u8) return pt_fail("pt_stage_save_u8: out of device memory");
+  if (device_copy(sc, "pt_stage_save_u8", rgb_sum, 3 * n, &d_img)) return -1;
+  g.k->save_u8(g.stream, (int)n, w, samples, d_img, d_u8);
+  HIP_OK(hipStreamSynchronize(g.stream));
+  HIP_OK(hipMemcpy(rgb8, d_u8, 3 * n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// The filter kernels on caller-supplied host arrays (tests: frames a renderer would never produce)
+int pt_stage_denoise(int w, int rows, const float* rgb_sum, const float* planes, float samples, const PtDenoiseOptions* opt, float* rgb_avg) {
+  if (need(default_context(), "pt_stage_denoise")) return -1;
+  Ctx& g = *default_context();
+  if (w <= 0 || rows <= 0 || rows >= 32768 || (int64_t)w * rows > (1ll << 30) || !rgb_sum || !planes || !rgb_avg) return pt_fail("pt_stage_denoise: bad argument");
+  ptdn::Params P{};
+  if (pt_denoise_resolve("pt_stage_denoise", samples, opt, &P)) return -1;
+  return filter_stage(g, "pt_stage_denoise", (size_t)w * rows, rgb_sum, planes, nullptr, rgb_avg,
+                      [&](const float* img, const float* pl, const float*, void* ws, const float** out) { return pt_denoise_launch(g.stream, w, rows, img, pl, samples, P, ws, out); });
+}
+
+// The guided filter's kernels on caller-supplied host arrays
+int pt_stage_denoise_guided(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, int groups, int64_t iters,
+                            const PtDenoiseOptions* opt, float* rgb_avg) {
+  if (need(default_context(), "pt_stage_denoise_guided")) return -1;
+  Ctx& g = *default_context();
+  if (w <= 0 || rows <= 0 || rows >= 32768 || (int64_t)w * rows > (1ll << 30) || !rgb_sum || !planes || !noise_planes || !rgb_avg)
+    return pt_fail("pt_stage_denoise_guided: bad argument");
+  ptdn::Params P{};
+  float Tf = 0.0f, Df = 0.0f;
+  if (pt_denoise_guided_resolve("pt_stage_denoise_guided", groups, iters, opt, &P, &Tf, &Df)) return -1;
+  return filter_stage(g, "pt_stage_denoise_guided", (size_t)w * rows, rgb_sum, planes, noise_planes, rgb_avg,
+                      [&](const float* img, const float* pl, const float* nz, void* ws, const float** out) { return pt_denoise_guided_launch(g.stream, w, rows, img, pl, nz, Tf, Df, P, ws, out); });
+}
+
+// The selection's kernels on caller-supplied host arrays (pt_adaptive_select_host's arguments)
+int pt_stage_adaptive_select(int w, int rows, const float* noise_planes, const int32_t* counts, int m, int32_t* list) {
+  if (need(default_context(), "pt_stage_adaptive_select")) return -1;
+  Ctx& g = *default_context();
+  if (pt_adaptive_check_select("pt_stage_adaptive_select", w, rows, noise_planes, counts, m, list)) return -1;
+  HIP_OK(hipSetDevice(g.device));
+  Scratch sc;
+  const size_t n = (size_t)w * rows;
+  float* d_plane0 = nullptr;
+  int32_t* d_counts = nullptr;
+  char* d_ws = sc.get<char>(pt_adaptive_select_bytes(n));
+  int32_t* d_list = sc.get<int32_t>((size_t)m);
+  if (!d_ws || !d_list) return pt_fail("pt_stage_adaptive_select: out of device memory");
+  if (device_copy(sc, "pt_stage_adaptive_select", noise_planes, 4 * n, &d_plane0)) return -1;  // the selection reads plane 0 only
+  if (device_copy(sc, "pt_stage_adaptive_select", counts, 2 * n, &d_counts)) return -1;
+  HIP_OK(hipMemset(d_list, 0xff, (size_t)m * sizeof(int32_t)));  // an entry nobody wrote shows as -1
+  if (pt_adaptive_select_launch(g.stream, w, rows, d_plane0, d_counts, m, d_ws, d_list)) return -1;
+  HIP_OK(hipStreamSynchronize(g.stream));
+  HIP_OK(hipMemcpy(list, d_list, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// The worker context alone: iterations iter_first .. iter_first + iter_count - 1 of the m listed tile pixels (distinct, any order);
+// rgb_sum_host receives the group sum, m * 3 floats in list order.  Leaves image, folds and state of the renderer alone.
+int pt_stage_render_list(const int32_t* list, int m, int iter_first, int iter_count, float* rgb_sum_host) {
+  if (need(default_context(), "pt_stage_render_list")) return -1;
+  Ctx& g = *default_context();
+  if (!list || !rgb_sum_host || m < 1 || m > g.N || iter_first < 1 || iter_count < 0 || (int64_t)iter_first + iter_count - 1 > INT32_MAX)
+    return pt_fail("pt_stage_render_list: bad argument (a list of %d out of %d pixels, iterations %d, +%d)", m, g.N, iter_first, iter_count);
+  if (admit(g, "pt_stage_render_list", kNotFailed)) return -1;
+  if (g.stripe) return pt_fail("pt_stage_render_list: a striped tile has no list form");
+  {
+    std::vector<uint8_t> seen((size_t)g.N, 0);
+    for (int i = 0; i < m; ++i) {
+      if (list[i] < 0 || list[i] >= g.N || seen[(size_t)list[i]]) return pt_fail("pt_stage_render_list: list[%d] = %d is outside the tile or repeated", i, list[i]);
+      seen[(size_t)list[i]] = 1;
+    }
+  }
+  HIP_OK(hipSetDevice(g.device));
+  if (ensure_worker(g, m)) return -1;
+  HIP_OK(hipStreamSynchronize(g.stream));  // (the list may still be read by an earlier round)
+  HIP_OK(hipMemcpy(g.d_list, list, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice));
+  if (render_list(g, iter_first, iter_count)) return -1;
+  HIP_OK(hipMemcpyAsync(rgb_sum_host, g.worker->d_image, 3 * (size_t)m * sizeof(float), hipMemcpyDeviceToHost, g.stream));
+  return pt_ctx_sync(&g);
+}
+
+}  // extern "C"

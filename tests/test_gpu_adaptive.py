@@ -1,5 +1,5 @@
 """Adaptive sampling on the device (pt_adaptive_round, pt_render_adaptive, pt_resolve; csrc/pt_adaptive.hip and the worker context
-of csrc/pt_api.cpp) against the numpy restatement tests/adaptive_ref.py, bit for bit; what it buys against uniform sampling; and
+of csrc/pt_post.cpp) against the numpy restatement tests/adaptive_ref.py, bit for bit; what it buys against uniform sampling; and
 the edges of the adaptive state."""
 import numpy as np
 import pytest

@@ -25,7 +25,8 @@ $K -ffp-contract=off -DPT_ARITH=0 -c $KSRC/pt_kernels.hip -o $OUT/obj_$NAME/k0.o
 $K -ffp-contract=fast-honor-pragmas -DPT_ARITH=1 -c $KSRC/pt_kernels.hip -o $OUT/obj_$NAME/k1.o &
 $K -ffp-contract=fast-honor-pragmas -DPT_ARITH=2 -c $KSRC/pt_kernels.hip -o $OUT/obj_$NAME/k2.o &
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $OUT/$NAME.so $OUT/obj_$NAME/k0.o $OUT/obj_$NAME/k1.o $OUT/obj_$NAME/k2.o $SRC/build/pt_api.o \
-  $SRC/build/pt_group.o $SRC/build/pt_scene.o $SRC/build/pt_tables.o $SRC/build/pt_image.o $SRC/build/pathtrace_shim.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+HOSTOBJS=$(make -s -C $SRC print-hostobjs)  # the Makefile's list of everything in the library but the kernels
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $OUT/$NAME.so $OUT/obj_$NAME/k0.o $OUT/obj_$NAME/k1.o $OUT/obj_$NAME/k2.o $HOSTOBJS \
+  -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 rm -rf $OUT/obj_$NAME
 echo "$OUT/$NAME.so"
