@@ -63,20 +63,16 @@ __global__ __launch_bounds__(kBlock) void k_features(SceneTables sc, ptd::Camera
         const f3 d = Ar<kD0>::camera_dir(cam, inv_w, p, b.aa_jitter != 0, jx, jy);
         if (PACKET) trace_group_packet<kD0>(w, nodes, sc.num_nodes, geoms, o, d, valid, lane, tri);
         else trace_group<kD0>(w, top, sc.num_top, nodes, geoms, o, d, valid, lane, sc.cull_margin, sc.top_xor, tri);
-        const unsigned long long best = w.best[lane];
-        const bool hit = valid && (uint32_t)(best >> 32) != 0x7f7fffffu;
-        vn = vp = vc = mk(0.f, 0.f, 0.f);
+        const Hit h = resolve_hit(w.best[lane], w.rec + lane, valid, LeafGeom<>{nodes, geoms});
+        vn = h.n, vp = h.p, vc = mk(0.f, 0.f, 0.f);
         vt = vh = 0.f;
         id = 0;
-        if (hit) {
-          const int gi = nodes[(uint32_t)best].geom;
-          const float* col = sc.mats[geoms[gi].material].color;
-          vt = __uint_as_float((uint32_t)(best >> 32));
+        if (h.hit) {
+          const float* col = sc.mats[h.mat].color;
+          vt = h.t;
           vh = 1.0f;
-          vn = mk(w.rec[0 * 64 + lane], w.rec[1 * 64 + lane], w.rec[2 * 64 + lane]);
-          vp = mk(w.rec[3 * 64 + lane], w.rec[4 * 64 + lane], w.rec[5 * 64 + lane]);
           vc = mk(col[0], col[1], col[2]);
-          id = gi + 1;
+          id = h.geom + 1;
         }
       }
       s0.x = s0.x + vn.x, s0.y = s0.y + vn.y, s0.z = s0.z + vn.z, s0.w = s0.w + vt;

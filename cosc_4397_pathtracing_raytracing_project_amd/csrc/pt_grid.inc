@@ -175,7 +175,7 @@ PT_DEV void grid_search(Carry<false, NPAR>& c, CellRing& cr, const SceneTables& 
     if (splits < 2 && __popcll(M) <= kGridSplit) {
       ++splits;
       const int n_on = __popcll(M);
-      const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(M >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)M, 0));
+      const int rank = rank_in(M);
       if (w.on) c.slot[rank] = lane;
       const int k = 64 / n_on;
       const int r = lane / k, seg = lane - r * k;

@@ -21,6 +21,8 @@
 //                depth-1 ray; three search forms (LDS tables / top list + subtree scans / uniform grid walk)
 // (k_generate / k_intersect / k_shade remain as the unfused form for stage-parity tests and A/B runs,
 // k_intersect_legacy as the per-lane tree walk the wave-cooperative search replaced.)
+// Shared: keep_closest / resolve_hit pack and unpack a closest-hit key and record; k_primary's two loop forms go through one front
+// end (group_of + trace) and differ in the shading lambda; scan_subtrees is trace_group's and carry_search<true>'s subtree walk.
 //
 // Arithmetic contract.  This file is compiled once per arithmetic mode (PT_ARITH, see pt_kernels.h KernelApi):
 //   0 exact: -ffp-contract=off; every float operation is written in the order GLM 0.9.6 / the reference
@@ -441,8 +443,8 @@ PT_DEV void steal_step(Walker& w, uint32_t& pend, uint32_t xm, bool idle, unsign
   const unsigned long long Dn = ballot(pend != 0);
   if (!Dn) return;
   const int nd = __popcll(Dn), ni = __popcll(I);
-  const int drank = __builtin_amdgcn_mbcnt_hi((uint32_t)(Dn >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)Dn, 0));
-  const int irank = __builtin_amdgcn_mbcnt_hi((uint32_t)(I >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)I, 0));
+  const int drank = rank_in(Dn);
+  const int irank = rank_in(I);
   if (pend != 0) slot[drank] = lane;  // the k-th donor's lane id
   const bool take = idle && irank < nd;
   const int donor = slot[take ? irank : 0];
@@ -461,6 +463,46 @@ PT_DEV void steal_step(Walker& w, uint32_t& pend, uint32_t xm, bool idle, unsign
     w.ri.ix = si.x, w.ri.iy = si.y, w.ri.iz = si.z;
     w.ri.sx = si.x < 0.0f, w.ri.sy = si.y < 0.0f, w.ri.sz = si.z < 0.0f;
     w.ri.nx = -so.x * si.x, w.ri.ny = -so.y * si.y, w.ri.nz = -so.z * si.z;
+  }
+}
+// The subtree scans of one group: every lane walks the subtrees its ray entered (`pend`: their top entries) back to back,
+// independently of the others, nearest first; lanes without work steal pending (ray, subtree) pairs (steal_step, donor table
+// `slot`).  scan(walker, act, bt, cand, leaf, geom) is one scan_step on the caller's node table; file(cand, leaf, owner, geom)
+// files a candidate under the lane that owns its ray — wave-uniform control flow, so the primitive tests downstream fetch the
+// ray from the owner as for a top-list leaf.  best: the group's closest-hit keys (the closer-hit cull reads the owner's).
+// (PT_WALK_STATS builds: counters 1-3 also count trace_group's scans; tools/walk_stats.py runs the fused kernels, i.e. carry_search's.)
+template <typename Scan, typename File>
+PT_DEV void scan_subtrees(uint32_t pend, const float4* top, f3 o, const RayInv& ri, int lane, unsigned long long top_xor, float cull,
+                          const unsigned long long* best, int* slot, Scan scan, File file) {
+  if (!ballot(pend != 0)) return;
+  Walker wk{0, 0, lane, o, ri};
+  const uint32_t xm = octant_mask(ri, top_xor);
+  pend = permute_xor(pend, xm);
+  while (true) {
+    if (wk.cur >= wk.end && pend) {  // own subtrees first, nearest first
+      const int e = __builtin_ctz(pend) ^ (int)xm;
+      pend &= pend - 1;
+      const float4 TB = top[2 * e + 1];
+      wk.cur = __float_as_int(TB.z) + 1;  // the subtree root's box is the top entry's box: already passed
+      wk.end = __float_as_int(TB.w);
+    }
+    const bool idle = wk.cur >= wk.end;
+    const unsigned long long I = ballot(idle);
+    if (I == ~0ull) break;
+    if (__popcll(I) >= kStealMin) {
+      PT_STAT(3, 1);
+      steal_step(wk, pend, xm, idle, I, slot, top, lane);
+    }
+    const bool act = wk.cur < wk.end;
+    PT_STAT(1, 1);
+    PT_STAT(2, __popcll(ballot(act)));
+    // closer-hit cull: a box entered beyond the ray's best hit so far (+ margin, see SceneTables::cull_margin)
+    // cannot hold the closest hit
+    const float bt = __uint_as_float(reinterpret_cast<const uint32_t*>(best)[2 * wk.own + 1]) + cull;
+    bool cand;
+    int at_n, aux;
+    scan(wk, act, bt, cand, at_n, aux);
+    file(cand, at_n, wk.own, aux);
   }
 }
 // Legacy traversal (kept for A/B measurements, PtOptions flag): one lane walks the threaded
@@ -570,7 +612,56 @@ PT_DEV WaveLds wave_lds_init(char* base) {  // on a WaveMap::bytes block
   return w;
 }
 constexpr unsigned long long kNoHit = ((unsigned long long)0x7f7fffffu << 32) | 0xffffffffull;  // t_min = FLT_MAX
-
+// Keep the closest hit of a ray: `best_slot` its key, rec + col its column of a [6][64] record block (normal xyz, point xyz).
+// A candidate counts iff t > 0 && t < FLT_MAX (pathtrace.cu:314 with t_min starting at FLT_MAX).
+// (run_chunk passes block + owner lane, carry_chunk the column and col = 0, each the address arithmetic it had: with the column
+// run_chunk's callers k_features<true, false> and k_primary<kTopScan> lose a wave of occupancy, with block + lane k_paths<kGrid> spills.)
+PT_DEV void keep_closest(unsigned long long* best_slot, float* rec, int col, float t, uint32_t leaf, f3 nrm, f3 pt, bool valid) {
+  const uint32_t tb = __float_as_uint(t);
+  if (valid && t > 0.f && tb < 0x7f7fffffu) {
+    const unsigned long long key = ((unsigned long long)tb << 32) | leaf;
+    atomicMin(best_slot, key);
+    if (*best_slot == key) {  // this candidate is the ray's best so far: publish its record
+      rec[0 * 64 + col] = nrm.x, rec[1 * 64 + col] = nrm.y, rec[2 * 64 + col] = nrm.z;
+      rec[3 * 64 + col] = pt.x, rec[4 * 64 + col] = pt.y, rec[5 * 64 + col] = pt.z;
+    }
+  }
+}
+// A ray's closest hit as the shading takes it: t = -1, material 0 and zeros on a miss (the reference's hit record after its
+// per-depth memset, pathtrace.cu:562).
+struct Hit {
+  bool hit;
+  float t;
+  int geom, mat;
+  f3 n, p;
+};
+// The usual way from a hit's leaf to its geom and material: through the threaded node.  FINISH: the chunks left the world-space
+// normal to the winner (carry_chunk, LEAN: the grid walk), in the arithmetic EX.
+template <bool FINISH = false, bool EX = false>
+struct LeafGeom {
+  const ptd::Node* nodes;
+  const ptd::Geom* geoms;
+  PT_DEV void operator()(uint32_t leaf, Hit& h) const {
+    h.geom = nodes[leaf].geom;
+    const ptd::Geom* G = geoms + h.geom;
+    h.mat = G->material;
+    if constexpr (FINISH) h.n = Ar<EX>::finish_normal(G, h.n);
+  }
+};
+// Unpacks a closest-hit key (keep_closest) and its record for the lanes that `want` it; look(leaf, hit) fills in geom and
+// material (LeafGeom, or a table of the caller's).
+template <typename Look>
+PT_DEV Hit resolve_hit(unsigned long long best, const float* rec, bool want, Look look) {
+  Hit h{false, -1.0f, -1, 0, mk(0.f, 0.f, 0.f), mk(0.f, 0.f, 0.f)};
+  if (want && (uint32_t)(best >> 32) != 0x7f7fffffu) {
+    h.hit = true;
+    h.t = __uint_as_float((uint32_t)(best >> 32));
+    h.n = mk(rec[0 * 64], rec[1 * 64], rec[2 * 64]);
+    h.p = mk(rec[3 * 64], rec[4 * 64], rec[5 * 64]);
+    look((uint32_t)best, h);
+  }
+  return h;
+}
 
 // Runs the pending candidates; called at wave-uniform control flow with all 64 lanes active.
 // One chunk of <= 64 candidates: `nc` cubes starting at list[cfirst] followed by `nsph` spheres starting at
@@ -591,15 +682,7 @@ PT_DEV void run_chunk(const WaveLds& w, int cfirst, int nc, int sfirst, int nsph
   const ptd::Geom* G = geoms + gi;
   f3 pt, nrm;
   const float t = Ar<EX>::template geom_test<TYPE, false>(G, ro, rd, pt, nrm, mk(0.f, 0.f, 0.f));
-  const uint32_t tb = __float_as_uint(t);
-  if (valid && t > 0.f && tb < 0x7f7fffffu) {
-    const unsigned long long key = ((unsigned long long)tb << 32) | leaf;
-    atomicMin(&w.best[src], key);
-    if (w.best[src] == key) {  // this candidate is the ray's best so far: publish its record
-      w.rec[0 * 64 + src] = nrm.x, w.rec[1 * 64 + src] = nrm.y, w.rec[2 * 64 + src] = nrm.z;
-      w.rec[3 * 64 + src] = pt.x, w.rec[4 * 64 + src] = pt.y, w.rec[5 * 64 + src] = pt.z;
-    }
-  }
+  keep_closest(&w.best[src], w.rec, src, t, leaf, nrm, pt, valid);
 }
 // Runs the pending candidates; called at wave-uniform control flow with all 64 lanes active.
 // Chunk plan (a typical group at depth >= 1 holds ~55 cubes and ~12 spheres): full chunks of cubes,
@@ -650,7 +733,7 @@ PT_DEV void trace_group(const WaveLds& w, const float4* top, int ntop, const ptd
           flush_candidates<false, EX>(w, nb, ns, lane, o, d, nodes, geoms, tri);
           nb = ns = 0;
         }
-        const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+        const int rank = rank_in(m);
         const int cnt = __popcll(m);
         const uint32_t entry = ((uint32_t)t_idx << 6) | (uint32_t)lane;
         if (t_link == -2) {  // cube
@@ -665,53 +748,33 @@ PT_DEV void trace_group(const WaveLds& w, const float4* top, int ntop, const ptd
       pend |= 1u << e;
     }
   }
-  // subtrees below the cut: every lane walks its entered subtrees back to back, independently of the others, nearest
-  // first; lanes without work steal pending (ray, subtree) pairs (steal_step; the donor table lives in the spare row
-  // of w.rec).  Candidates are filed under the owner's lane and the primitive tests fetch the ray from the owner's
-  // registers o, d as before.
-  if (ballot(pend != 0)) {
-    Walker wk{0, 0, lane, o, ri};
-    int* slot = reinterpret_cast<int*>(w.rec + 6 * 64);
-    const uint32_t xm = octant_mask(ri, top_xor);
-    pend = permute_xor(pend, xm);
-    while (true) {
-      if (wk.cur >= wk.end && pend) {  // own subtrees first, nearest first
-        const int e = __builtin_ctz(pend) ^ (int)xm;
-        pend &= pend - 1;
-        const float4 TB = top[2 * e + 1];
-        wk.cur = __float_as_int(TB.z) + 1;  // the subtree root's box is the top entry's box: already passed
-        wk.end = __float_as_int(TB.w);
-      }
-      const bool idle = wk.cur >= wk.end;
-      const unsigned long long I = ballot(idle);
-      if (I == ~0ull) break;
-      if (__popcll(I) >= kStealMin) steal_step(wk, pend, xm, idle, I, slot, top, lane);
-      const bool act = wk.cur < wk.end;
-      // closer-hit cull: a box entered beyond the ray's best hit so far (+ margin, see SceneTables::cull_margin)
-      // cannot hold the closest hit
-      const float bt = __uint_as_float(reinterpret_cast<const uint32_t*>(w.best)[2 * wk.own + 1]) + cull;
-      bool cand;
-      int at_n, aux;
-      scan_step<EX>(reinterpret_cast<const v4f*>(nodes), wk.o, wk.ri, act, wk.cur, bt, cand, at_n, aux);
-      const bool cbox = cand && geoms[aux].type == 1;
-      const bool csph = cand && !cbox;
-      const unsigned long long mb = ballot(cbox), msp = ballot(csph);
-      if (mb | msp) {
-        if (nb + ns + 128 > kCandCap) {
-          flush_candidates<false, EX>(w, nb, ns, lane, o, d, nodes, geoms, tri);
-          nb = ns = 0;
+  // (The top-list loop above is restated in carry_search<SUB = true>, which files into the ring: written once, with the leaf filing
+  // as a callable, k_intersect and k_features take 12 B / lane of scratch in every build and two instances lose a wave.)
+  // subtrees below the cut (the donor table lives in the spare row of w.rec); the chunks fetch the ray from the owner's registers
+  scan_subtrees(
+      pend, top, o, ri, lane, top_xor, cull, w.best, reinterpret_cast<int*>(w.rec + 6 * 64),
+      [&](Walker& wk, bool act, float bt, bool& cand, int& at_n, int& aux) {
+        scan_step<EX>(reinterpret_cast<const v4f*>(nodes), wk.o, wk.ri, act, wk.cur, bt, cand, at_n, aux);
+      },
+      [&](bool cand, int at_n, int own, int aux) {
+        const bool cbox = cand && geoms[aux].type == 1;
+        const bool csph = cand && !cbox;
+        const unsigned long long mb = ballot(cbox), msp = ballot(csph);
+        if (mb | msp) {
+          if (nb + ns + 128 > kCandCap) {
+            flush_candidates<false, EX>(w, nb, ns, lane, o, d, nodes, geoms, tri);
+            nb = ns = 0;
+          }
+          const uint32_t entry = ((uint32_t)at_n << 6) | (uint32_t)own;
+          const int rb = rank_in(mb);
+          const int rs = rank_in(msp);
+          const int cb = __popcll(mb), cs = __popcll(msp);
+          if (cbox) w.list[nb + rb] = entry;
+          if (csph) w.list[kCandCap - ns - cs + rs] = entry;
+          nb += cb;
+          ns += cs;
         }
-        const uint32_t entry = ((uint32_t)at_n << 6) | (uint32_t)wk.own;
-        const int rb = __builtin_amdgcn_mbcnt_hi((uint32_t)(mb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mb, 0));
-        const int rs = __builtin_amdgcn_mbcnt_hi((uint32_t)(msp >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)msp, 0));
-        const int cb = __popcll(mb), cs = __popcll(msp);
-        if (cbox) w.list[nb + rb] = entry;
-        if (csph) w.list[kCandCap - ns - cs + rs] = entry;
-        nb += cb;
-        ns += cs;
-      }
-    }
-  }
+      });
   if (nb + ns) flush_candidates<false, EX>(w, nb, ns, lane, o, d, nodes, geoms, tri);
 }
 
@@ -805,10 +868,11 @@ __global__ __launch_bounds__(kBlock) void k_intersect(SceneTables sc, ptd::Queue
     path_load_ray(paths, qbase + min((j + wq) * 64 + lane, last), no, nd);
     trace_group<EX>(w, top, ntop, nodes, geoms, o, d, valid, lane, sc.cull_margin, sc.top_xor, sc.has_triangles != 0);
 
+    // record layout of the reference after its per-depth memset (pathtrace.cu:562): miss → t = -1 and zeros elsewhere.
+    // (resolve_hit's unpacking, written out with selects: every lane loads and stores, see above — and through resolve_hit's branch
+    // the fast build's LDS-table instance takes 82 VGPRs instead of 80 and loses its sixth wave.)
     const unsigned long long best = w.best[lane];
     const bool hit = (uint32_t)(best >> 32) != 0x7f7fffffu;
-    // record layout of the reference after its per-depth memset (pathtrace.cu:562):
-    // miss → t = -1 and zeros elsewhere.
     const int leaf = hit ? (int)(uint32_t)best : 0;
     hits.t[at] = hit ? __uint_as_float((uint32_t)(best >> 32)) : -1.0f;
     hits.n[at] = hit ? w.rec[0 * 64 + lane] : 0.f;
@@ -901,17 +965,7 @@ PT_DEV void carry_chunk(Carry<SMALL, NPAR>& c, int n, int lane, const ptd::Node*
   if (LEAN) t = Ar<EX>::template geom_test<-1, false, true>(G, ro, rd, pt, nrm, mk(0.f, 0.f, 0.f), valid ? (int)(gw >> 30) : 0);
   else if (QO) t = Ar<EX>::template geom_test<-1, true>(G, ro, rd, pt, nrm, mk(c.qo_tab[3 * gi], c.qo_tab[3 * gi + 1], c.qo_tab[3 * gi + 2]));
   else t = Ar<EX>::template geom_test<-1, false>(G, ro, rd, pt, nrm, mk(0.f, 0.f, 0.f));
-  const uint32_t tb = __float_as_uint(t);
-  if (valid && t > 0.f && tb < 0x7f7fffffu) {
-    const unsigned long long key = ((unsigned long long)tb << 32) | leaf;
-    unsigned long long* slot = &c.best[par * 64 + src];
-    atomicMin(slot, key);
-    if (*slot == key) {  // this candidate is the ray's best so far: publish its record
-      float* r = c.rec + par * 6 * 64 + src;
-      r[0 * 64] = nrm.x, r[1 * 64] = nrm.y, r[2 * 64] = nrm.z;
-      r[3 * 64] = pt.x, r[4 * 64] = pt.y, r[5 * 64] = pt.z;
-    }
-  }
+  keep_closest(&c.best[par * 64 + src], c.rec + par * 6 * 64 + src, 0, t, leaf, nrm, pt, valid);
   c.head = (c.head + n) & (kRing - 1);
   c.count -= n;
   c.processed += n;
@@ -923,7 +977,7 @@ PT_DEV void carry_append(Carry<SMALL, NPAR>& c, bool pass, uint32_t leaf, int pa
                          const ptd::Node* __restrict__ nodes, const ptd::Geom* __restrict__ geoms, uint32_t gword = 0u) {
   const unsigned long long m = ballot(pass);
   if (!m) return;
-  const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+  const int rank = rank_in(m);
   if (pass) {
     const int idx = (c.head + c.count + rank) & (kRing - 1);
     c.ent[idx] = (typename Carry<SMALL, NPAR>::Ent)((leaf << 7) | ((uint32_t)par << 6) | (uint32_t)owner);
@@ -958,7 +1012,7 @@ PT_DEV void carry_search(Carry<!SUB, NPAR>& c, const float4* top, int ntop, cons
     // (max candidates of a lane, ~3) instead of once per entry (7 for cornell.txt).  The order of the ring entries changes,
     // the set does not, and the closest-hit key is order-independent.
     // box tests, eight at a time fully unrolled (no loop-carried box registers to rotate); the pass bit is shifted into the mask
-    // by ONE v_addc (push_bit): bit (ntop - 1 - e) of the mask = entry e
+    // by ONE v_addc (push_bit): bit (ntop - 1 - e) of the mask = entry e.  (paths_search restates this two-phase search.)
     uint32_t mask = 0;
     for (int e0 = 0; e0 < ntop; e0 += 8) {
 #pragma unroll
@@ -975,7 +1029,7 @@ PT_DEV void carry_search(Carry<!SUB, NPAR>& c, const float4* top, int ntop, cons
     while (true) {
       const unsigned long long m = ballot(mask != 0u);
       if (!m) break;
-      const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+      const int rank = rank_in(m);
       if (mask != 0u) {
         const int te = ntop - 1 - __builtin_ctz(mask);
         mask &= mask - 1u;
@@ -989,6 +1043,7 @@ PT_DEV void carry_search(Carry<!SUB, NPAR>& c, const float4* top, int ntop, cons
     }
     return;
   }
+  // (The top-list loop below restates trace_group's, which files into the two-ended list.)
   uint32_t pend = 0;  // per lane: top entries that are subtrees and whose box this ray passes
   PT_STAT(0, 1);
   PT_STAT(13, __popcll(ballot(valid)));
@@ -1007,36 +1062,14 @@ PT_DEV void carry_search(Carry<!SUB, NPAR>& c, const float4* top, int ntop, cons
   }
   // Subtrees below the cut (large scenes only): per-lane stackless scans, nearest subtree first, with work stealing
   // (scan_step / steal_step); candidates are filed under the lane that owns the ray, so nothing downstream changes.
-  if (SUB && ballot(pend != 0)) {
-    Walker wk{0, 0, lane, o, ri};
-    const uint32_t xm = octant_mask(ri, top_xor);
-    pend = permute_xor(pend, xm);
-    while (true) {
-      if (wk.cur >= wk.end && pend) {  // own subtrees first, nearest first
-        const int e = __builtin_ctz(pend) ^ (int)xm;
-        pend &= pend - 1;
-        const float4 TB = top[2 * e + 1];
-        wk.cur = __float_as_int(TB.z) + 1;  // the subtree root's box is the top entry's box: already passed
-        wk.end = __float_as_int(TB.w);
-      }
-      const bool idle = wk.cur >= wk.end;
-      const unsigned long long I = ballot(idle);
-      if (I == ~0ull) break;
-      if (__popcll(I) >= kStealMin) {
-        PT_STAT(3, 1);
-        steal_step(wk, pend, xm, idle, I, c.slot, top, lane);
-      }
-      const bool act = wk.cur < wk.end;
-      PT_STAT(1, 1);
-      PT_STAT(2, __popcll(ballot(act)));
-      const float bt = __uint_as_float(reinterpret_cast<const uint32_t*>(c.best)[2 * (par * 64 + wk.own) + 1]) + cull;
-      bool cand;
-      int at_n, aux;
-      if (c.lds_nodes) scan_step(c.lnodes, wk.o, wk.ri, act, wk.cur, bt, cand, at_n, aux);
-      else scan_step(reinterpret_cast<const v4f*>(nodes), wk.o, wk.ri, act, wk.cur, bt, cand, at_n, aux);
-      carry_append(c, cand, (uint32_t)at_n, par, wk.own, lane, nodes, geoms);
-    }
-  }
+  if constexpr (SUB)
+    scan_subtrees(
+        pend, top, o, ri, lane, top_xor, cull, c.best + par * 64, c.slot,
+        [&](Walker& wk, bool act, float bt, bool& cand, int& at_n, int& aux) {
+          if (c.lds_nodes) scan_step(c.lnodes, wk.o, wk.ri, act, wk.cur, bt, cand, at_n, aux);
+          else scan_step(reinterpret_cast<const v4f*>(nodes), wk.o, wk.ri, act, wk.cur, bt, cand, at_n, aux);
+        },
+        [&](bool cand, int at_n, int own, int) { carry_append(c, cand, (uint32_t)at_n, par, own, lane, nodes, geoms); });
 }
 // Make sure everything appended up to `mark` has been tested (only runs a partial chunk when the ring
 // did not fill up since).
@@ -1159,34 +1192,84 @@ __global__ __launch_bounds__(kBlock, (primary_waves<F, SPLIT>())) void k_primary
       ++ck;
       crho = crho + 1 == wq ? 0 : crho + 1;
     };
+    // A group of 64 primary rays (one per lane): what its shading needs besides the hit.  (valid is an int: as a bool the exact
+    // build's two shared ring instances lose their seventh wave — 74 VGPRs, or 20 B / lane of scratch under the bound.)
+    struct Group {
+      f3 d;
+      int k, pl, slot;  // pl: tile pixel; k, slot (per-iteration form only): the iteration inside the batch and the sample id
+      uint32_t phash;
+      int valid;  // 0: a lane past the tile's last pixel
+    };
+    // generate: chunk jj of the queue (in iteration k: the shared form's rays do not depend on it and pass 0)
+    auto group_of = [&](int jj, int k) {
+      Group g;
+      const int pl_raw = chunk_pixel(q, jj, qs.Q) + lane;
+      g.valid = pl_raw < b.N;
+      g.pl = g.valid ? pl_raw : b.N - 1;
+      g.k = k, g.slot = SHARE ? 0 : make_slot(b, k, g.pl);
+      const int p = global_pixel(b, g.pl);  // global pixel index
+      g.phash = utilhash((uint32_t)p);
+      float jx = 0.f, jy = 0.f;
+      const bool aa = !SHARE && b.aa_jitter != 0;  // (the shared form is chosen for unjittered rays only)
+      if (aa) aa_jitter(b.iter_first + k, p, jx, jy);
+      g.d = Ar<kD0>::camera_dir(cam, inv_w, p, aa, jx, jy);
+      return g;
+    };
+    // the group that waits between its search and its shading (RING: shaded one group later)
+    struct {
+      Group g;
+      int par, mark;
+      bool any;
+    } pp;
+    pp.any = false;
+    // Search of group `g`, the `it`-th of the wave's loop, then shade(key, record column, group) of the group whose hit is resolved
+    // by then: g itself, or in the ring form the group before it — the last one is left to the loop's end (the tails below).
+    auto trace = [&](int it, const Group& g, auto&& shade) {
+      // Primary rays come in bundles of 64 neighbouring pixels and half of the 16:9 frame looks past the scene:
+      // one test against the bounds of the whole tree per lane, and if no lane passes (a parent box rejects
+      // whatever its children would, the slab arithmetic being monotone) the 7 leaf-box tests are skipped.
+      const bool near_scene = ballot(g.valid && Ar<kD0>::slab(o, Ar<kD0>::ray_inv(g.d, o), sc.root_min[0], sc.root_min[1], sc.root_min[2],
+                                                       sc.root_max[0], sc.root_max[1], sc.root_max[2])) != 0;
+      if constexpr (RING) {
+        const int par = it & 1;
+        ws.best[par * 64 + lane] = kNoHit;
+        if (near_scene) carry_search<false, 2, true, kD0>(ws, cam_top, ntop, nodes, geoms, o, g.d, g.valid, lane, par, sc.cull_margin, sc.top_xor);
+        if (pp.any) {  // the waiting group's candidates are now all resolved; its key and record stay in its parity's half while it is shaded
+          carry_drain_to<true, 2, kD0, true>(ws, pp.mark, lane, nodes, geoms);
+          shade(ws.best[pp.par * 64 + lane], ws.rec + pp.par * 6 * 64 + lane, pp.g);
+        }
+        pp.g = g, pp.par = par, pp.mark = ws.appended, pp.any = true;
+      } else if constexpr (GRID) {
+        ws.cy.best[lane] = kNoHit;
+        if (near_scene) {
+          grid_search<1, kD0>(ws.cy, ws.cr, sc, nodes, geoms, o, g.d, g.valid, lane, 0);
+          while (ws.cy.count > 0) carry_chunk<false, 1, kD0, true>(ws.cy, min(64, ws.cy.count), lane, nodes, geoms);
+        }
+        shade(ws.cy.best[lane], ws.cy.rec + lane, g);
+      } else {
+        if (near_scene) trace_group_packet<kD0>(ws, nodes, sc.num_nodes, geoms, o, g.d, g.valid, lane, sc.has_triangles != 0);
+        else ws.best[lane] = kNoHit;
+        shade(ws.best[lane], ws.rec + lane, g);
+      }
+    };
+    const LeafGeom<GRID, kD0> leaf_geom{nodes, geoms};  // the grid's chunks leave the normal to the winner
     // shading + retirement + compaction of one group of primary rays from its resolved hit key / record
-    auto shade_group = [&](unsigned long long best, const float* rec, bool valid, int k, int pl, int slot, uint32_t phash, f3 d) {
-      const bool hit = (uint32_t)(best >> 32) != 0x7f7fffffu;
+    auto shade_group = [&](unsigned long long best, const float* rec, const Group& g) {
+      const bool valid = g.valid;
+      const int k = g.k, pl = g.pl;
       ShadeIO s;
       s.o = o;
-      s.d = d;
+      s.d = g.d;
       s.c = mk(1.0f, 1.0f, 1.0f);
       s.alive = false;
       Bounce bo;
       bo.kind = 0;
-      f3 hn = mk(0.f, 0.f, 0.f), hp = mk(0.f, 0.f, 0.f);
-      if (valid) {
-        float ht = -1.0f;
-        int hmat = 0;
-        if (hit) {
-          ht = __uint_as_float((uint32_t)(best >> 32));
-          const ptd::Geom* G = geoms + nodes[(uint32_t)best].geom;
-          hmat = G->material;
-          hn = mk(rec[0 * 64], rec[1 * 64], rec[2 * 64]);
-          hp = mk(rec[3 * 64], rec[4 * 64], rec[5 * 64]);
-          if (GRID) hn = Ar<kD0>::finish_normal(G, hn);  // the grid's chunks leave the normal to the winner (carry_chunk, LEAN)
-        }
-        bo = shade_decide(mats, b.trace_depth, 0, iter_hash_of(ihash, sc, b, 0, k) ^ phash, ht, hmat, s);
-      }
+      const Hit h = resolve_hit(best, rec, valid, leaf_geom);
+      if (valid) bo = shade_decide(mats, b.trace_depth, 0, iter_hash_of(ihash, sc, b, 0, k) ^ g.phash, h.t, h.mat, s);
       const bool alive = valid && s.alive, dead = valid && !s.alive;
-      if (alive) shade_bounce(bo, hn, hp, s);
+      if (alive) shade_bounce(bo, h.n, h.p, s);
       const unsigned long long live = ballot(alive);
-      const PathTag tag{slot, phash, k};
+      const PathTag tag{g.slot, g.phash, k};
       if (b.flat) {  // unfused consumers: one dense list per queue behind an atomic, records appended one by one (test / A-B form)
         int base = 0;
         if (live && lane == 0) base = atomicAdd(counter, (int)__popcll(live));
@@ -1202,20 +1285,8 @@ __global__ __launch_bounds__(kBlock, (primary_waves<F, SPLIT>())) void k_primary
       if (dead) rt.rec[sub0 + nd + rank_in(deadm)] = ptd::Word4{s.c.x, s.c.y, s.c.z, __int_as_float(pl)};
       nl += (int)__popcll(live), nd += (int)__popcll(deadm);
     };
-    // a group between its search and its shading (RING)
-    struct {
-      f3 d;
-      int k, pl, slot;
-      uint32_t phash;
-      bool valid;
-      int par, mark;
-      bool any;
-    } pp;
-    pp.any = false;
     if constexpr (RING) ws = carry_init<true, 2>(wbase), ws.qo_tab = cam_qo, ws.cam_o = o;  // every strand starts with an empty ring
     if constexpr (SHARE) {
-      // (The per-group search dispatch below and shade_run restate the per-iteration loop and shade_group of the else branch, kept
-      // apart so that the per-iteration instance compiles to the code it had: a fix to one copy has to be made in the other.)
       // Shared form (pt_sched.h): the wave keeps residue r through the piece, so chunk jj is traced ONCE per run of iterations
       // [s0, s1) and shaded s1 - s0 times from the same hit; lane l of vnl / vnd counts the survivors / retirees of iteration s0 + l.
       const int cap = shared_run_cap(b.primary_share), sub_off = sub_offset(quo, rem, shared_rho(r, k0, wq)) * 64;
@@ -1225,19 +1296,15 @@ __global__ __launch_bounds__(kBlock, (primary_waves<F, SPLIT>())) void k_primary
         const int s0 = sr.k0, s1 = sr.k1;
         int vnl = 0, vnd = 0;
         // shading + retirement + compaction of one group of primary rays in every iteration of the run
-        auto shade_run = [&](unsigned long long best, const float* rec, bool valid, int pl, uint32_t phash, f3 d) {
-          const bool hit = (uint32_t)(best >> 32) != 0x7f7fffffu;
-          f3 hn = mk(0.f, 0.f, 0.f), hp = mk(0.f, 0.f, 0.f);
-          float ht = -1.0f;
-          int hmat = 0;
-          if (valid && hit) {
-            ht = __uint_as_float((uint32_t)(best >> 32));
-            const ptd::Geom* G = geoms + nodes[(uint32_t)best].geom;
-            hmat = G->material;
-            hn = mk(rec[0 * 64], rec[1 * 64], rec[2 * 64]);
-            hp = mk(rec[3 * 64], rec[4 * 64], rec[5 * 64]);
-            if (GRID) hn = Ar<kD0>::finish_normal(G, hn);
-          }
+        auto shade_run = [&](unsigned long long best, const float* rec, const Group& g) {
+          const bool valid = g.valid;
+          const int pl = g.pl;
+          const uint32_t phash = g.phash;
+          const f3 d = g.d;
+          const Hit h = resolve_hit(best, rec, valid, leaf_geom);
+          const float ht = h.t;
+          const int hmat = h.mat;
+          const f3 hn = h.n, hp = h.p;
           if constexpr (SPLIT) {
             // BatchInfo::split_records (pt_sched.h): the lanes that survive — every hit but an emitter's, in every iteration — get their
             // invariant word (shade_bounce's origin, the material) from the run that holds iteration 0 of the batch, at the slot their
@@ -1297,41 +1364,14 @@ __global__ __launch_bounds__(kBlock, (primary_waves<F, SPLIT>())) void k_primary
         if constexpr (RING) ws = carry_init<true, 2>(wbase), ws.qo_tab = cam_qo, ws.cam_o = o;  // every run starts with an empty ring
         pp.any = false;
         int it = 0;
-        for (int jj = shared_rho(r, s0, wq); jj < sh.my_nq; jj += wq, ++it) {
-          const int pl_raw = chunk_pixel(q, jj, qs.Q) + lane;
-          const bool valid = pl_raw < b.N;
-          const int pl = valid ? pl_raw : b.N - 1;  // tile pixel
-          const int p = global_pixel(b, pl);        // global pixel index
-          const uint32_t phash = utilhash((uint32_t)p);
-          const f3 d = Ar<kD0>::camera_dir(cam, inv_w, p, false, 0.f, 0.f);
-          const bool near_scene = ballot(valid && Ar<kD0>::slab(o, Ar<kD0>::ray_inv(d, o), sc.root_min[0], sc.root_min[1], sc.root_min[2],
-                                                         sc.root_max[0], sc.root_max[1], sc.root_max[2])) != 0;
-          if constexpr (RING) {
-            const int par = it & 1;
-            ws.best[par * 64 + lane] = kNoHit;
-            if (near_scene) carry_search<false, 2, true, kD0>(ws, cam_top, ntop, nodes, geoms, o, d, valid, lane, par, sc.cull_margin, sc.top_xor);
-            if (pp.any) {  // the previous group's candidates are now all resolved; its key and record stay in its parity's half while it is shaded
-              carry_drain_to<true, 2, kD0, true>(ws, pp.mark, lane, nodes, geoms);
-              shade_run(ws.best[pp.par * 64 + lane], ws.rec + pp.par * 6 * 64 + lane, pp.valid, pp.pl, pp.phash, pp.d);
-            }
-            pp.d = d, pp.pl = pl, pp.phash = phash, pp.valid = valid, pp.par = par, pp.mark = ws.appended, pp.any = true;
-          } else if constexpr (GRID) {
-            ws.cy.best[lane] = kNoHit;
-            if (near_scene) {
-              grid_search<1, kD0>(ws.cy, ws.cr, sc, nodes, geoms, o, d, valid, lane, 0);
-              while (ws.cy.count > 0) carry_chunk<false, 1, kD0, true>(ws.cy, min(64, ws.cy.count), lane, nodes, geoms);
-            }
-            shade_run(ws.cy.best[lane], ws.cy.rec + lane, valid, pl, phash, d);
-          } else {
-            if (near_scene) trace_group_packet<kD0>(ws, nodes, sc.num_nodes, geoms, o, d, valid, lane, sc.has_triangles != 0);
-            else ws.best[lane] = kNoHit;
-            shade_run(ws.best[lane], ws.rec + lane, valid, pl, phash, d);
-          }
-        }
+        for (int jj = shared_rho(r, s0, wq); jj < sh.my_nq; jj += wq, ++it) trace(it, group_of(jj, 0), shade_run);
+        // the ring's last group.  (These three lines and their twin below the per-iteration loops stay written out: as a lambda or a
+        // function template, alone or shared with trace(), they cost the exact build's two shared ring instances their seventh wave —
+        // 74 VGPRs instead of 72, or 12 B / lane of scratch under the bound.)
         if constexpr (RING) {
           if (pp.any) {
             carry_drain_to<true, 2, kD0, true>(ws, pp.mark, lane, nodes, geoms);
-            shade_run(ws.best[pp.par * 64 + lane], ws.rec + pp.par * 6 * 64 + lane, pp.valid, pp.pl, pp.phash, pp.d);
+            shade_run(ws.best[pp.par * 64 + lane], ws.rec + pp.par * 6 * 64 + lane, pp.g);
           }
         }
         // the run's counts, one lane per iteration (zeros where the wave had no chunk)
@@ -1340,46 +1380,12 @@ __global__ __launch_bounds__(kBlock, (primary_waves<F, SPLIT>())) void k_primary
     } else {
       int it = 0;
       for (int k = k0, rho = strand_rho(r, k0, wq); k < k1; ++k, rho = rho + 1 == wq ? 0 : rho + 1) {
-        for (int jj = rho; jj < sh.my_nq; jj += wq, ++it) {
-          const int pl_raw = chunk_pixel(q, jj, qs.Q) + lane;
-          const bool valid = pl_raw < b.N;
-          const int pl = valid ? pl_raw : b.N - 1;  // tile pixel
-          const int slot = make_slot(b, k, pl);
-          const int p = global_pixel(b, pl);  // global pixel index
-          const uint32_t phash = utilhash((uint32_t)p);
-          float jx = 0.f, jy = 0.f;
-          if (b.aa_jitter) aa_jitter(b.iter_first + k, p, jx, jy);
-          const f3 d = Ar<kD0>::camera_dir(cam, inv_w, p, b.aa_jitter != 0, jx, jy);
-          // Primary rays come in bundles of 64 neighbouring pixels and half of the 16:9 frame looks past the scene:
-          // one test against the bounds of the whole tree per lane, and if no lane passes (a parent box rejects
-          // whatever its children would, the slab arithmetic being monotone) the 7 leaf-box tests are skipped.
-          const bool near_scene = ballot(valid && Ar<kD0>::slab(o, Ar<kD0>::ray_inv(d, o), sc.root_min[0], sc.root_min[1], sc.root_min[2],
-                                                         sc.root_max[0], sc.root_max[1], sc.root_max[2])) != 0;
-          if constexpr (RING) {
-            const int par = it & 1;
-            ws.best[par * 64 + lane] = kNoHit;
-            if (near_scene) carry_search<false, 2, true, kD0>(ws, cam_top, ntop, nodes, geoms, o, d, valid, lane, par, sc.cull_margin, sc.top_xor);
-            if (pp.any) carry_drain_to<true, 2, kD0, true>(ws, pp.mark, lane, nodes, geoms);  // the previous group's candidates are now all resolved
-            if (pp.any) shade_group(ws.best[pp.par * 64 + lane], ws.rec + pp.par * 6 * 64 + lane, pp.valid, pp.k, pp.pl, pp.slot, pp.phash, pp.d);
-            pp.d = d, pp.k = k, pp.pl = pl, pp.slot = slot, pp.phash = phash, pp.valid = valid, pp.par = par, pp.mark = ws.appended, pp.any = true;
-          } else if constexpr (GRID) {
-            ws.cy.best[lane] = kNoHit;
-            if (near_scene) {
-              grid_search<1, kD0>(ws.cy, ws.cr, sc, nodes, geoms, o, d, valid, lane, 0);
-              while (ws.cy.count > 0) carry_chunk<false, 1, kD0, true>(ws.cy, min(64, ws.cy.count), lane, nodes, geoms);
-            }
-            shade_group(ws.cy.best[lane], ws.cy.rec + lane, valid, k, pl, slot, phash, d);
-          } else {
-            if (near_scene) trace_group_packet<kD0>(ws, nodes, sc.num_nodes, geoms, o, d, valid, lane, sc.has_triangles != 0);
-            else ws.best[lane] = kNoHit;
-            shade_group(ws.best[lane], ws.rec + lane, valid, k, pl, slot, phash, d);
-          }
-        }
+        for (int jj = rho; jj < sh.my_nq; jj += wq, ++it) trace(it, group_of(jj, k), shade_group);
       }
-      if constexpr (RING) {
+      if constexpr (RING) {  // the ring's last group (see the shared form's tail)
         if (pp.any) {
           carry_drain_to<true, 2, kD0, true>(ws, pp.mark, lane, nodes, geoms);
-          shade_group(ws.best[pp.par * 64 + lane], ws.rec + pp.par * 6 * 64 + lane, pp.valid, pp.k, pp.pl, pp.slot, pp.phash, pp.d);
+          shade_group(ws.best[pp.par * 64 + lane], ws.rec + pp.par * 6 * 64 + lane, pp.g);
         }
       }
       if (!b.flat)
@@ -1498,6 +1504,7 @@ PT_DEV void paths_chunk(Lanes& c, int n, int lane, f3 o, f3 d, const uint32_t* t
   const ptd::Geom* G = geoms + (valid ? (int)(tw >> 8) : 0);
   f3 pt = mk(0.f, 0.f, 0.f), nrm = mk(0.f, 0.f, 0.f);
   const float t = geom_test<-1, false>(G, ro, rd, pt, nrm, mk(0.f, 0.f, 0.f));
+  // keep_closest and (k_paths' shading) resolve_hit written out: through them k_paths on cornell took 1149.9 us against 1144.5 (fast)
   const uint32_t tb = __float_as_uint(t);
   if (valid && t > 0.f && tb < 0x7f7fffffu) {
     const unsigned long long key = ((unsigned long long)tb << 32) | leaf;
@@ -1526,18 +1533,16 @@ PT_DEV void paths_search(Lanes& c, TOP* top, const uint32_t* tword, int ntop, co
     mark = c.processed;  // no candidate: resolved at once
   }
   // box tests, eight at a time fully unrolled (no loop-carried box registers to rotate); bit (ntop - 1 - e) of the mask = entry e
+  // (carry_search<SUB = false> restates this two-phase search; fetching four boxes together before testing them — one wait for four
+  // scalar loads instead of one per box — was measured in the fast build: k_paths 1292 -> 1315 us, 32 more SGPRs in flight and 19 spilled)
   uint32_t mask = 0;
-  {
-    // (fetching four boxes together before testing them — one wait for four scalar loads instead of one per box — was measured in
-    // the fast build: k_paths 1292 -> 1315 us, 32 more SGPRs in flight and 19 spilled)
-    for (int e0 = 0; e0 < ntop; e0 += 8) {
+  for (int e0 = 0; e0 < ntop; e0 += 8) {
 #pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int e = e0 + u;
-        if (e < ntop) {
-          const auto A = top[2 * e], B = top[2 * e + 1];
-          mask = push_bit(mask, slab(o, ri, A.x, A.y, A.z, A.w, B.x, B.y));
-        }
+    for (int u = 0; u < 8; ++u) {
+      const int e = e0 + u;
+      if (e < ntop) {
+        const auto A = top[2 * e], B = top[2 * e + 1];
+        mask = push_bit(mask, slab(o, ri, A.x, A.y, A.z, A.w, B.x, B.y));
       }
     }
   }
@@ -1914,8 +1919,6 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
     fresh = false;
     // ── shade the resolved lanes ──
     {
-      const unsigned long long best = cy.best[lane];
-      const bool hit = (uint32_t)(best >> 32) != 0x7f7fffffu;
       ShadeIO s;
       s.o = mk(0.f, 0.f, 0.f);
       s.d = d;
@@ -1923,31 +1926,30 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
       s.alive = false;
       Bounce bo;
       bo.kind = 0;
-      f3 hn = mk(0.f, 0.f, 0.f), hp = mk(0.f, 0.f, 0.f);
       const int k = (int)((uint32_t)slot >> b.slot_shift);
+      const unsigned long long best = cy.best[lane];
+      Hit h{false, -1.0f, -1, 0, mk(0.f, 0.f, 0.f), mk(0.f, 0.f, 0.f)};  // resolve_hit's unpacking written out (see paths_chunk)
       if (ready) {
-        float ht = -1.0f;
-        int hmat = 0;
-        if (hit) {
-          ht = __uint_as_float((uint32_t)(best >> 32));
+        if ((uint32_t)(best >> 32) != 0x7f7fffffu) {
+          h.t = __uint_as_float((uint32_t)(best >> 32));
           const float* rr = cy.rec + lane;
-          hn = mk(rr[0 * 64], rr[1 * 64], rr[2 * 64]);
-          hp = mk(rr[3 * 64], rr[4 * 64], rr[5 * 64]);
+          h.n = mk(rr[0 * 64], rr[1 * 64], rr[2 * 64]);
+          h.p = mk(rr[3 * 64], rr[4 * 64], rr[5 * 64]);
           if constexpr (MODE == 0) {
-            hmat = lmat[(uint32_t)best & 63u];
+            h.mat = lmat[(uint32_t)best & 63u];
           } else {
             const ptd::Geom* G = geoms + nodes[(uint32_t)best].geom;
-            hmat = G->material;
-            if (MODE == 2) hn = finish_normal(G, hn);  // the grid's chunks leave the normal to the winner (carry_chunk, LEAN)
+            h.mat = G->material;
+            if (MODE == 2) h.n = finish_normal(G, h.n);  // the grid's chunks leave the normal to the winner (carry_chunk, LEAN)
           }
         }
         const uint32_t ih = he > 0 ? ihash[(depth - 1) * he + k] : iter_hash(b.iter_first + k, depth);
-        bo = shade_decide(mats, b.trace_depth, depth, ih ^ phash, ht, hmat, s);
+        bo = shade_decide(mats, b.trace_depth, depth, ih ^ phash, h.t, h.mat, s);
       }
       const bool alive = ready && s.alive, dead = ready && !s.alive;
       if (dead) atomicAdd(&died[depth & 63], 1);  // statistics: rays traced at depth d = paths retired at depth >= d
       if (dead) rslot = atomicAdd(&fillc[rslot & (kVisitRing - 1)], 1);  // lanes of one visit get consecutive record slots
-      if (alive) shade_bounce(bo, hn, hp, s);
+      if (alive) shade_bounce(bo, h.n, h.p, s);
       if (ready) {
         c = s.c;
         if (alive) o = s.o, d = s.d, depth += 1, fresh = true;
