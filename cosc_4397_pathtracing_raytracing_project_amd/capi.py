@@ -131,6 +131,9 @@ def lib() -> C.CDLL:
     L.pt_get_stats.argtypes = [C.POINTER(PtStats)]
     L.pt_stage_generate.argtypes = [C.c_int, C.c_int, _fp, _fp]
     L.pt_stage_intersect.argtypes = [C.c_int, _fp, _fp, _fp, _fp, _ip, _fp]
+    if hasattr(L, "pt_stage_intersect_grid"):  # absent only in older A/B builds loaded through PT_AMD_LIB (tools/build_rev.sh)
+        L.pt_stage_intersect_grid.argtypes = [C.c_int, _fp, _fp, C.c_int, _fp, _fp, _ip, _fp]
+        L.pt_stage_grid_info.argtypes = [C.POINTER(PtGridInfo), C.POINTER(C.c_int32)]
     L.pt_stage_shade.argtypes = [C.c_int, C.c_int, _ip, _ip, _fp, _fp, _ip, _fp, _fp, _fp, _fp, _ip]
     _u8p = C.POINTER(C.c_uint8)
     L.pt_save_u8.argtypes = [C.c_float, _u8p]
@@ -696,6 +699,27 @@ class Renderer:
         pt = np.zeros((3, n), np.float32)
         _check(lib().pt_stage_intersect(n, _f(o), _f(d), _f(t), _f(nrm), _i(mat), _f(pt)))
         return dict(t=t, nrm=nrm, mat=mat, pt=pt)
+
+    @staticmethod
+    def stage_intersect_grid(o: np.ndarray, d: np.ndarray, primary_form: bool = False):
+        """stage_intersect's records through the uniform-grid walk of the fused kernels (pt_stage_intersect_grid): as depth 0
+        walks (primary_form) or as the bounce kernel does.  The renderer must walk a grid (stats().grid_cells > 0)."""
+        n = o.shape[1]
+        o = np.ascontiguousarray(o, np.float32)
+        d = np.ascontiguousarray(d, np.float32)
+        t = np.zeros(n, np.float32)
+        nrm = np.zeros((3, n), np.float32)
+        mat = np.zeros(n, np.int32)
+        pt = np.zeros((3, n), np.float32)
+        _check(lib().pt_stage_intersect_grid(n, _f(o), _f(d), 1 if primary_form else 0, _f(t), _f(nrm), _i(mat), _f(pt)))
+        return dict(t=t, nrm=nrm, mat=mat, pt=pt)
+
+    @staticmethod
+    def grid_info():
+        """(PtGridInfo, longest cell list) of the grid the renderer walks (pt_stage_grid_info)."""
+        info, longest = PtGridInfo(), C.c_int32(0)
+        _check(lib().pt_stage_grid_info(C.byref(info), C.byref(longest)))
+        return info, int(longest.value)
 
     @staticmethod
     def stage_save_u8(rgb_sum: np.ndarray, w: int, h: int, samples: float) -> np.ndarray:

@@ -442,7 +442,7 @@ static int upload_tables(Ctx& g, const pt::HostTables& t) {
   s.nodes_b = s.nodes, s.top_b = s.top;  // the bounce kernels' box tables: the same, except for the fast build's centre / half extent copies
   if (!t.nodes_b.empty() && (!(s.nodes_b = upload(g, t.nodes_b)) || !(s.top_b = upload(g, t.top_b)))) return -1;
   for (const pt::Grid& gr : t.grids) {
-    Ctx::DeviceGrid d{gr.shape, gr.guard, nullptr, nullptr, nullptr, 0};
+    Ctx::DeviceGrid d{gr.shape, gr.guard, nullptr, nullptr, nullptr, 0, gr.start};
     const int64_t before = g.device_bytes;
     if (!(d.d_start = upload(g, gr.start)) || !(d.d_items = upload(g, gr.items))) return -1;
     if (!(d.d_items_b = gr.items_b.empty() ? d.d_items : upload(g, gr.items_b))) return -1;

@@ -106,8 +106,11 @@ PT_DEV float tri_test(const ptd::Geom* __restrict__ G, f3 ro, f3 rd, f3& point, 
 }
 
 // DEFER: the world-space normal is left to finish_normal() (only a ray's winning candidate needs one): `normal` returns
-// what that needs — the cube's object-space normal code, the sphere's object-space normal with the inside flip applied
-// (negation commutes exactly with the products, sums and the normalisation that follow), a triangle's final normal.
+// what that needs — the cube's object-space normal code, the sphere's object-space normal, times 4 where the hit is seen from
+// inside (|normal| = 0.5, so its length tells; exact both ways, and a zero keeps its sign), a triangle's final normal.  (The
+// flip itself waits for the finished normal, as in the reference: negating the INPUT negates every product but not a component
+// whose terms cancel — +0 + -0 and -0 + +0 are both +0 — where the reference reports -0; tests/test_gpu_grid_rays.py, rays in
+// a symmetry plane of a sphere.)
 // rt_type >= 0: the primitive type when the caller already has it (TYPE < 0), which spares the read of G->type.
 template <int TYPE, bool QO = false, bool DEFER = false>
 PT_DEV float geom_test(const ptd::Geom* __restrict__ G_in, f3 ro_w, f3 rd_w, f3& point, f3& normal, f3 qo_pre = f3{0.f, 0.f, 0.f},
@@ -213,7 +216,7 @@ PT_DEV float geom_test(const ptd::Geom* __restrict__ G_in, f3 ro_w, f3 rd_w, f3&
   // of the random-scene pixels then move by > 1e-5, over tests/test_gpu_arith.py's bound of 0.2 %; LABNOTES.md §9.3)
   point = mulMV<1>(xf, objp);
   if (DEFER) {
-    normal = is_box ? mk(__int_as_float(ncode), 0.f, 0.f) : (flip ? neg(nobj) : nobj);
+    normal = is_box ? mk(__int_as_float(ncode), 0.f, 0.f) : (flip ? scl(nobj, 4.0f) : nobj);
   } else if (is_box) {
     normal = mk(G->box_normal[ncode][0], G->box_normal[ncode][1], G->box_normal[ncode][2]);  // precomputed, exact
   } else {
@@ -230,7 +233,9 @@ PT_DEV f3 finish_normal(const ptd::Geom* __restrict__ G, f3 stored) {
     return mk(G->box_normal[c][0], G->box_normal[c][1], G->box_normal[c][2]);
   }
   if (gtype == 2) return stored;
-  return normalize(mulMV<0>(G->invT, stored));
+  const bool flip = dot(stored, stored) > 1.0f;  // 0.25 outside, 4 inside
+  const f3 n = normalize(mulMV<0>(G->invT, flip ? scl(stored, 0.25f) : stored));
+  return flip ? neg(n) : n;
 }
 
 

@@ -54,6 +54,7 @@ struct PtShared {
     const ptd::Node* d_items;
     const ptd::Node* d_items_b;  // == d_items unless the build wants centre / half extent
     size_t bytes;
+    std::vector<uint32_t> start;  // the host copy of what d_start holds, guard cells included (pt_stage_grid_info)
   };
   std::vector<DeviceGrid> grids;
   size_t grid_pick = 0;  // grids[grid_pick] is the one the kernels walk (when grids is not empty)

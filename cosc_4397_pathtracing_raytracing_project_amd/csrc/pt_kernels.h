@@ -172,6 +172,10 @@ struct KernelApi {
   // of b.N float4 behind `feat` (normal + t | material colour + hit count | point + object id of the last iteration).
   void (*features)(hipStream_t s, int grid, const SceneTables& sc, const ptd::Camera& cam, const BatchInfo& b, float4* feat);
   int boxes_center_half;  // 1: the bounce kernels of this build expect SceneTables::*_b as centre / half extent (the fast build)
+  // `intersect` with the uniform-grid walk of the fused kernels as the candidate search (sc.use_grid; tests).  primary: the walk as
+  // k_primary runs it (the reference's arithmetic on grid_items), otherwise as k_paths runs it (the build's arithmetic on grid_items_b).
+  void (*intersect_grid)(hipStream_t s, int grid, const SceneTables& sc, const ptd::Queues& qs, const int32_t* cnt_in,
+                         ptd::PathBuf paths, ptd::HitBuf hits, bool primary);
 };
 const KernelApi* api_exact();
 const KernelApi* api_fma();

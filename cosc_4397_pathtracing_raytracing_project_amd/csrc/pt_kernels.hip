@@ -1080,6 +1080,49 @@ PT_DEV void carry_drain_to(Carry<SMALL, NPAR>& c, int mark, int lane, const ptd:
 }
 
 #include "pt_grid.inc"
+// k_intersect's stage form of the grid walk (tests: pt_stage_intersect_grid hands it rays no camera produces): k_intersect's
+// queue, group and prefetch frame around the per-group body of the fused kernels on a grid — grid_search, the drain of the
+// candidate ring, the winner's normal — with nothing of its own in between.  EX = kD0: the depth-0 form (k_primary: the
+// reference's arithmetic on grid_items, without the near_scene pre-test, which is no part of the walk); EX = false: the
+// bounce form (k_paths<kGrid>: the build's arithmetic on grid_items_b).  Stands here, not beside k_intersect: after the walk.
+template <bool EX>
+__global__ __launch_bounds__(kBlock) void k_intersect_grid(SceneTables sc, ptd::Queues qs, const int32_t* __restrict__ cnt_in,
+                                                           ptd::PathBuf paths, ptd::HitBuf hits) {
+  extern __shared__ float4 lds_raw[];
+  char* lds = reinterpret_cast<char*>(lds_raw);
+  const IntersectGridLds L = intersect_grid_lds<kFast, EX>(sc);  // one grid block per wave; the tables stay in memory
+  const ptd::Node* nodes = EX ? sc.nodes : sc.nodes_b;
+  const ptd::Geom* geoms = sc.geoms;
+  const int wib = threadIdx.x >> 6;
+  GridRings ws = grid_rings_init<EX>(lds + L.waves + wib * L.wave_bytes);
+  const LeafGeom<true, EX> leaf_geom{nodes, geoms};  // the grid's chunks leave the normal to the winner
+
+  const int wave = blockIdx.x * kWavesPerBlock + wib;
+  const int lane = lane_id();
+  const auto [q, r, wq] = wave_slot(wave, qs.Q, qs.W);
+  const int n_q = cnt_in[cnt_index(qs, 0, q)];
+  const int64_t HS = hits.stride;
+  const int64_t qbase = (int64_t)q * qs.cap;
+  // (k_intersect's frame: lanes past the fill level trace nothing and store a miss into the unused tail of the queue's region)
+  const int last = qs.cap - 64 + lane;
+  f3 no, nd;
+  path_load_ray(paths, qbase + min(r * 64 + lane, last), no, nd);
+  for (int j = r; j * 64 < n_q; j += wq) {
+    const int i = j * 64 + lane;
+    const bool valid = i < n_q;
+    const int64_t at = qbase + i;
+    const f3 o = no, d = nd;
+    path_load_ray(paths, qbase + min((j + wq) * 64 + lane, last), no, nd);
+    ws.cy.best[lane] = kNoHit;
+    grid_search<1, EX>(ws.cy, ws.cr, sc, nodes, geoms, o, d, valid, lane, 0);
+    while (ws.cy.count > 0) carry_chunk<false, 1, EX, true>(ws.cy, min(64, ws.cy.count), lane, nodes, geoms);
+    const Hit h = resolve_hit(ws.cy.best[lane], ws.cy.rec + lane, valid, leaf_geom);  // a miss: t = -1, zeros elsewhere
+    hits.t[at] = h.t;
+    hits.n[at] = h.n.x, hits.n[HS + at] = h.n.y, hits.n[2 * HS + at] = h.n.z;
+    hits.mat[at] = h.mat;
+    hits.p[at] = h.p.x, hits.p[HS + at] = h.p.y, hits.p[2 * HS + at] = h.p.z;
+  }
+}
 // Waves per SIMD a k_primary instance is compiled for.  Two shared instances end at 72 VGPRs — seven waves, which the persistent
 // grid of a scene with little LDS per block uses — by the allocator's choice, not by the bound; their SPLIT forms came out at 74
 // under the same bound and are asked for the seven outright (72 VGPRs, no scratch; exact / kTopScan would spill, and has six either way).
@@ -2016,7 +2059,7 @@ const KernelApi kApi = {
 #endif
     launch_generate, launch_primary, launch_intersect, launch_shade, launch_collect, launch_count_stats,
     launch_preview, launch_save_u8, launch_shade_stage, lds_table_limit, resident_blocks_per_cu, launch_ieee_check, launch_paths,
-    launch_collect_conv, launch_features, kFast ? 1 : 0};
+    launch_collect_conv, launch_features, kFast ? 1 : 0, launch_intersect_grid};
 
 }  // namespace
 }  // namespace PT_NS

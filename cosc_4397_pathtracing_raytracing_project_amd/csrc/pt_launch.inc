@@ -15,6 +15,11 @@ template <typename F>
 void with_intersect(const SceneTables& sc, bool legacy, bool exact, F&& f) {
   exact ? with_intersect_of<kD0>(sc, legacy, f) : with_intersect_of<false>(sc, legacy, f);
 }
+// The stage form of the grid walk; primary: the depth-0 form (k_primary's walk), else the bounce form (k_paths<kGrid>'s)
+template <typename F>
+void with_intersect_grid(const SceneTables& sc, bool primary, F&& f) {
+  primary ? f(k_intersect_grid<kD0>, intersect_grid_lds<kFast, kD0>(sc).total) : f(k_intersect_grid<false>, intersect_grid_lds<kFast, false>(sc).total);
+}
 // The LDS-table kernel variants assume that every leaf is a top-list entry (no subtrees).
 bool leaves_fit_top(const SceneTables& sc) { return (sc.num_nodes + 1) / 2 <= kMaxTop; }
 // k_features: k_intersect's LDS map; scenes whose tables stay in memory and whose leaves do not all fit the top list take the
@@ -135,6 +140,11 @@ void launch_generate(hipStream_t s, int grid, const ptd::Camera& cam, const Batc
 void launch_intersect(hipStream_t s, int grid, const SceneTables& sc, const ptd::Queues& qs, const int32_t* cnt_in,
                       ptd::PathBuf paths, ptd::HitBuf hits, bool legacy, bool exact_arith) {
   with_intersect(sc, legacy, exact_arith, [&](auto kernel, int lds) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, sc, qs, cnt_in, paths, hits); });
+}
+
+void launch_intersect_grid(hipStream_t s, int grid, const SceneTables& sc, const ptd::Queues& qs, const int32_t* cnt_in,
+                           ptd::PathBuf paths, ptd::HitBuf hits, bool primary) {
+  with_intersect_grid(sc, primary, [&](auto kernel, int lds) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, sc, qs, cnt_in, paths, hits); });
 }
 
 void launch_primary(hipStream_t s, int grid, const SceneTables& sc, const ptd::Camera& cam, const BatchInfo& b,

@@ -105,6 +105,18 @@ __host__ __device__ inline IntersectLds intersect_lds(const SceneTables& sc) {
   return L;
 }
 
+struct IntersectGridLds {  // k_intersect_grid: the waves' grid blocks alone (the walk reads every table from memory)
+  int waves, wave_bytes, total;
+};
+template <bool FAST, bool EX>
+__host__ __device__ inline IntersectGridLds intersect_grid_lds(const SceneTables&) {
+  IntersectGridLds L;
+  L.waves = 0;
+  L.wave_bytes = GridMap<FAST, EX>::bytes;
+  L.total = L.waves + kWavesPerBlock * L.wave_bytes;
+  return L;
+}
+
 struct PrimaryLds {  // k_primary; cam_top / cam_qo: camera-relative copies of the top list / the camera in every geom's object space
   int top, mats, nodes, geoms, waves, wave_bytes, ihash, cam_top, cam_qo, total;
 };

@@ -2,6 +2,8 @@
 // They act on the default context (pt_context.h) and keep nothing: every device buffer is scratch, freed on return.  The C ABI of
 // the stages takes plain SoA float arrays ([3][n]); the kernels stream three planes of 16-byte path records (ptd::PathBuf), so the
 // stage wrappers pack / unpack on the host.
+#include <cstring>
+
 #include "pt_context.h"
 #include "pt_denoise.h"
 #include "pt_scene.h"
@@ -75,6 +77,48 @@ int filter_stage(Ctx& g, const char* who, size_t n, const float* rgb_sum, const 
   HIP_OK(hipMemcpy(rgb_avg, d_out, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
   return 0;
 }
+
+// What the two intersect stages share.  tight_rule: with tightened leaves, refuse origins outside the region the boxes were sized for.
+template <typename Launch>
+int intersect_stage(Ctx& g, const char* who, bool tight_rule, int n, const float* origin, const float* dir, float* t, float* normal,
+                    int32_t* material, float* point, Launch launch) {
+  if (tight_rule && g.tight_leaves > 0) {
+    // the tightened sphere boxes of a large scene are sized for ray origins inside the scene bounds or at the camera
+    // (sphere_tight_box): rays from elsewhere could lose grazing hits, so they are refused rather than traced differently
+    double olo[3], ohi[3];
+    pt::origin_region(g.scene.root_min, g.scene.root_max, g.cam.position, olo, ohi);
+    for (int i = 0; i < n; ++i)
+      for (int a = 0; a < 3; ++a) {
+        const float v = origin[(size_t)a * n + i];
+        if (!(v >= olo[a] && v <= ohi[a]))
+          return pt_fail("%s: ray %d starts outside the scene bounds (this scene's sphere leaves are tightened for origins inside them; "
+                      "PtOptions.debug_flags 2048 keeps the reference's boxes)", who, i);
+      }
+  }
+  HIP_OK(hipSetDevice(g.device));
+  Scratch sc;
+  ptd::Queues qs = single_queue(g, n);
+  const size_t cap = qs.cap;
+  StagePaths sp;
+  const bool have_paths = sp.alloc(sc, cap);
+  ptd::HitBuf hb{};
+  int32_t* cnt = sc.get<int32_t>(16);
+  if (!have_paths || !scratch_hits(sc, cap, &hb) || !cnt) return pt_fail("%s: out of device memory", who);
+  sp.pack(n, origin, dir, nullptr);
+  if (sp.upload()) return pt_fail("%s: upload failed", who);
+  HIP_OK(hipMemcpy(cnt, &n, 4, hipMemcpyHostToDevice));
+  launch(qs, cnt, sp.pb, hb);
+  HIP_OK(hipStreamSynchronize(g.stream));
+  HIP_OK(hipMemcpy(t, hb.t, (size_t)n * 4, hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(material, hb.mat, (size_t)n * 4, hipMemcpyDeviceToHost));
+  for (int c = 0; c < 3; ++c) {
+    HIP_OK(hipMemcpy(normal + (size_t)c * n, hb.n + c * cap, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(point + (size_t)c * n, hb.p + c * cap, (size_t)n * 4, hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+// The grid the fused kernels of `g` walk, or nullptr (PtStats.grid_cells == 0)
+const Ctx::DeviceGrid* walked_grid(const Ctx& g) { return tables(g).use_grid && g.fuse_bounces ? &g.grids[g.grid_pick] : nullptr; }
 }  // namespace
 
 extern "C" {
@@ -105,39 +149,44 @@ int pt_stage_intersect(int n, const float* origin, const float* dir, float* t, f
   if (need(default_context(), "pt_stage_intersect")) return -1;
   Ctx& g = *default_context();
   if (n <= 0) return 0;
-  if (g.tight_leaves > 0) {
-    // the tightened sphere boxes of a large scene are sized for ray origins inside the scene bounds or at the camera
-    // (sphere_tight_box): rays from elsewhere could lose grazing hits, so they are refused rather than traced differently
-    double olo[3], ohi[3];
-    pt::origin_region(g.scene.root_min, g.scene.root_max, g.cam.position, olo, ohi);
-    for (int i = 0; i < n; ++i)
-      for (int a = 0; a < 3; ++a) {
-        const float v = origin[(size_t)a * n + i];
-        if (!(v >= olo[a] && v <= ohi[a]))
-          return pt_fail("pt_stage_intersect: ray %d starts outside the scene bounds (this scene's sphere leaves are tightened for origins inside them; "
-                      "PtOptions.debug_flags 2048 keeps the reference's boxes)", i);
-      }
-  }
-  HIP_OK(hipSetDevice(g.device));
-  Scratch sc;
-  ptd::Queues qs = single_queue(g, n);
-  const size_t cap = qs.cap;
-  StagePaths sp;
-  const bool have_paths = sp.alloc(sc, cap);
-  ptd::HitBuf hb{};
-  int32_t* cnt = sc.get<int32_t>(16);
-  if (!have_paths || !scratch_hits(sc, cap, &hb) || !cnt) return pt_fail("pt_stage_intersect: out of device memory");
-  sp.pack(n, origin, dir, nullptr);
-  if (sp.upload()) return pt_fail("pt_stage_intersect: upload failed");
-  HIP_OK(hipMemcpy(cnt, &n, 4, hipMemcpyHostToDevice));
-  g.k->intersect(g.stream, g.grid, tables(g), qs, cnt, sp.pb, hb, g.legacy, false);
-  HIP_OK(hipStreamSynchronize(g.stream));
-  HIP_OK(hipMemcpy(t, hb.t, (size_t)n * 4, hipMemcpyDeviceToHost));
-  HIP_OK(hipMemcpy(material, hb.mat, (size_t)n * 4, hipMemcpyDeviceToHost));
-  for (int c = 0; c < 3; ++c) {
-    HIP_OK(hipMemcpy(normal + (size_t)c * n, hb.n + c * cap, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(point + (size_t)c * n, hb.p + c * cap, (size_t)n * 4, hipMemcpyDeviceToHost));
-  }
+  return intersect_stage(g, "pt_stage_intersect", true, n, origin, dir, t, normal, material, point, [&](const ptd::Queues& qs, const int32_t* cnt, ptd::PathBuf pb, ptd::HitBuf hb) {
+    g.k->intersect(g.stream, g.grid, tables(g), qs, cnt, pb, hb, g.legacy, false);
+  });
+}
+
+// The grid walk of the fused kernels (k_intersect_grid) on caller-supplied rays: pt_stage_intersect's arrays and miss convention.
+// primary_form 1: as k_primary walks (the reference's arithmetic and boxes, any origin), 0: as k_paths walks (the mode's arithmetic,
+// the bounce tables; with tightened leaves the origins pt_stage_intersect accepts).
+int pt_stage_intersect_grid(int n, const float* origin, const float* dir, int primary_form, float* t, float* normal, int32_t* material,
+                            float* point) {
+  if (need(default_context(), "pt_stage_intersect_grid")) return -1;
+  Ctx& g = *default_context();
+  if (n <= 0) return 0;
+  if (!walked_grid(g)) return pt_fail("pt_stage_intersect_grid: this context walks no grid (PtStats.grid_cells is 0; PtOptions.debug_flags 256 forces one)");
+  if (!origin || !dir || !t || !normal || !material || !point) return pt_fail("pt_stage_intersect_grid: null argument");
+  return intersect_stage(g, "pt_stage_intersect_grid", primary_form == 0, n, origin, dir, t, normal, material, point,
+                         [&](const ptd::Queues& qs, const int32_t* cnt, ptd::PathBuf pb, ptd::HitBuf hb) {
+                           g.k->intersect_grid(g.stream, g.grid, tables(g), qs, cnt, pb, hb, primary_form != 0);
+                         });
+}
+
+// The grid that pt_stage_intersect_grid walks, from the host copy of the uploaded cell table
+int pt_stage_grid_info(PtGridInfo* info, int32_t* max_cell_records) {
+  if (need(default_context(), "pt_stage_grid_info")) return -1;
+  const Ctx& g = *default_context();
+  if (!info || !max_cell_records) return pt_fail("pt_stage_grid_info: null argument");
+  const Ctx::DeviceGrid* gr = walked_grid(g);
+  if (!gr) return pt_fail("pt_stage_grid_info: this context walks no grid (PtStats.grid_cells is 0; PtOptions.debug_flags 256 forces one)");
+  std::memset(info, 0, sizeof(*info));
+  for (int a = 0; a < 3; ++a) info->res[a] = gr->shape.res[a], info->origin[a] = gr->shape.gmin[a], info->cell_size[a] = gr->shape.cs[a];
+  info->pad = gr->shape.pad;
+  const size_t cells = gr->start.size() - 1 - 2 * gr->guard;
+  info->num_cells = (int32_t)cells;
+  info->num_records = (int32_t)gr->start[gr->guard + cells];
+  info->num_leaves = (g.scene.num_nodes + 1) / 2;
+  uint32_t longest = 0;
+  for (size_t c = 0; c < cells; ++c) longest = std::max(longest, gr->start[gr->guard + c + 1] - gr->start[gr->guard + c]);
+  *max_cell_records = (int32_t)longest;
   return 0;
 }
 

@@ -644,6 +644,19 @@ int pt_stage_generate(int pix_begin, int n, float* origin, float* dir);
 /* computeIntersections (pathtrace.cu:288-333): closest hit per ray. */
 int pt_stage_intersect(int n, const float* origin, const float* dir, float* t, float* normal, int32_t* material,
                        float* point);
+/* The same closest hits, found with the uniform-grid walk of the fused kernels instead of the BVH scan (arrays and miss
+ * convention of pt_stage_intersect): the walk hands the leaf tests a superset of the leaves whose box the ray passes, so
+ * every ray's record equals pt_stage_intersect's bit for bit, in every arithmetic mode (tests/test_gpu_grid_rays.py).
+ * primary_form 1: the walk as depth 0 runs it — the reference's arithmetic on the reference's (or tightened) boxes, as
+ * pt_stage_intersect of an exact-mode renderer computes; 0: as the bounce kernel runs it, in the mode's arithmetic.  Refused
+ * when the renderer walks no grid (PtStats.grid_cells == 0; PtOptions.debug_flags 256 forces one), on a null pointer and,
+ * with primary_form 0 on tightened leaves (PtStats.tight_leaves > 0), for the origins pt_stage_intersect refuses. */
+int pt_stage_intersect_grid(int n, const float* origin, const float* dir, int primary_form, float* t, float* normal,
+                            int32_t* material, float* point);
+/* The grid that walk runs on, read from the host copy of the uploaded cell table: shape, pad, cells, records
+ * (num_leaves: the scene's primitives) and the length of the longest cell list.  pt_build_grid builds the cost model's
+ * grid without the camera; this is the one pt_init kept.  Refused when the renderer walks no grid. */
+int pt_stage_grid_info(PtGridInfo* info, int32_t* max_cell_records);
 /* shadeAndExtendRays (pathtrace.cu:336-437) for live paths at `depth`:
  * in/out origin, dir, color; out alive[n] (1 = path continues).  Dead paths get the
  * retirement colour (sky factor applied (trace_depth - depth) times on a miss). */

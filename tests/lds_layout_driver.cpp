@@ -11,6 +11,7 @@ static void put(const char* name, const LegacyLds& L) { printf("%s nodes=%d geom
 static void put(const char* name, const IntersectLds& L) {
   printf("%s top=%d nodes=%d geoms=%d waves=%d wave_bytes=%d total=%d\n", name, L.top, L.nodes, L.geoms, L.waves, L.wave_bytes, L.total);
 }
+static void put(const char* name, const IntersectGridLds& L) { printf("%s waves=%d wave_bytes=%d total=%d\n", name, L.waves, L.wave_bytes, L.total); }
 static void put(const char* name, const PrimaryLds& L) {
   printf("%s top=%d mats=%d nodes=%d geoms=%d waves=%d wave_bytes=%d ihash=%d cam_top=%d cam_qo=%d total=%d\n", name, L.top, L.mats, L.nodes,
          L.geoms, L.waves, L.wave_bytes, L.ihash, L.cam_top, L.cam_qo, L.total);
@@ -44,6 +45,8 @@ static void put_case(const SceneTables& sc) {
   put("legacy.1", legacy_lds<true>(sc));
   put("intersect.0", intersect_lds<false>(sc));
   put("intersect.1", intersect_lds<true>(sc));
+  put("intersect_grid.primary", intersect_grid_lds<FAST, EX>(sc));  // the stage kernel's two forms: depth 0 (EX) and bounce
+  put("intersect_grid.bounce", intersect_grid_lds<FAST, false>(sc));
   put("primary.lds", primary_lds<kLdsTables, FAST, EX>(sc));
   put("primary.scan", primary_lds<kTopScan, FAST, EX>(sc));
   put("primary.grid", primary_lds<kGrid, FAST, EX>(sc));

@@ -176,6 +176,11 @@ def test_block_maps(maps):
                        ("waves", L["waves"], 4 * L["wave_bytes"], 16)], L["total"], what("intersect"))
             assert L["wave_bytes"] == WAVE_LDS
             assert L["total"] == (r16(table_bytes(s)) if t else 0) + 4 * WAVE_LDS + top
+        for form, e in (("primary", ex), ("bounce", 0)):  # k_intersect_grid: the waves' grid blocks and nothing else
+            L = m["intersect_grid." + form]
+            assert L["wave_bytes"] == grid_wave_bytes(fast, e) and L["wave_bytes"] % 16 == 0
+            _in_order([("waves", L["waves"], 4 * L["wave_bytes"], 16)], L["total"], what("intersect_grid." + form))
+            assert L["total"] == 4 * grid_wave_bytes(fast, e) <= 64 * 1024  # (what a kernel gets without asking)
         for form, in_lds, grid in (("lds", 1, 0), ("scan", 0, 0), ("grid", 0, 1)):
             L = m["primary." + form]
             wave = grid_wave_bytes(fast, ex) if grid else carry_bytes(True, 2) if in_lds else WAVE_LDS
