@@ -239,6 +239,15 @@ def lib() -> C.CDLL:
         L.pt_stage_adaptive_select.argtypes = [C.c_int, C.c_int, _fp, _ip, C.c_int, _ip]
         L.pt_adaptive_merge_host.argtypes = [C.c_int, _fp, _fp, _ip, _ip, C.c_int, _fp, C.c_int, _dp]
         L.pt_stage_render_list.argtypes = [_ip, C.c_int, C.c_int, C.c_int, _fp]
+    if hasattr(L, "pt_denoise_adaptive"):  # absent from older A/B builds of the library (tools/build_rev.sh)
+        _dno = C.POINTER(PtDenoiseOptions)
+        _dn_adaptive = [C.c_int, C.c_int, _fp, _fp, _fp, _ip, _dno]
+        L.pt_denoise_adaptive.argtypes = [_dno, _fp]
+        L.pt_ctx_denoise_adaptive.argtypes = [C.c_void_p, _dno, _fp]
+        L.pt_ctx_denoise_adaptive_device.argtypes = [C.c_void_p, _dno, C.POINTER(C.c_void_p)]
+        L.pt_stage_denoise_adaptive.argtypes = _dn_adaptive + [_fp]
+        L.pt_denoise_adaptive_host.argtypes = _dn_adaptive + [_fp]
+        L.pt_denoise_adaptive_variance_host.argtypes = _dn_adaptive + [_fp, _fp]
     _lib = L
     return L
 
@@ -465,6 +474,34 @@ def denoise_guided_variance_host(rgb_sum: np.ndarray, planes: np.ndarray, noise_
     return raw, pre
 
 
+def _denoise_adaptive_arrays(rgb_sum, planes, noise_planes, counts, w: int, rows: int):
+    s, p, z, out = _denoise_guided_arrays(rgb_sum, planes, noise_planes, w, rows)
+    c = np.ascontiguousarray(counts, np.int32).reshape(-1)
+    if c.size != 2 * w * rows:
+        raise PtError(f"denoise_adaptive: {c.size} counts for a frame of {w}x{rows}")
+    return s, p, z, c, out
+
+
+def denoise_adaptive_host(rgb_sum: np.ndarray, planes: np.ndarray, noise_planes: np.ndarray, counts: np.ndarray, w: int, rows: int,
+                          **opts) -> np.ndarray:
+    """The variance-guided filter with per-pixel counts on the host (pt_denoise_adaptive_host; no GPU): denoise_guided_host's arrays
+    and counts int32 [w*rows, 2] (T_p, M_p; Renderer.readback_adaptive).  The device result equals it bit for bit."""
+    s, p, z, c, out = _denoise_adaptive_arrays(rgb_sum, planes, noise_planes, counts, w, rows)
+    opt = denoise_options(**opts)
+    _check(lib().pt_denoise_adaptive_host(int(w), int(rows), _f(s), _f(p), _f(z), _i(c), C.byref(opt), _f(out)))
+    return out
+
+
+def denoise_adaptive_variance_host(rgb_sum: np.ndarray, planes: np.ndarray, noise_planes: np.ndarray, counts: np.ndarray, w: int, rows: int,
+                                   **opts):
+    """The two variances the adaptive filter's levels start from (pt_denoise_adaptive_variance_host): (var_raw, var_0), [w*rows] each."""
+    s, p, z, c, _ = _denoise_adaptive_arrays(rgb_sum, planes, noise_planes, counts, w, rows)
+    raw, pre = np.empty(w * rows, np.float32), np.empty(w * rows, np.float32)
+    opt = denoise_options(**opts)
+    _check(lib().pt_denoise_adaptive_variance_host(int(w), int(rows), _f(s), _f(p), _f(z), _i(c), C.byref(opt), _f(raw), _f(pre)))
+    return raw, pre
+
+
 def _select_arrays(noise_planes: np.ndarray, counts: np.ndarray, w: int, rows: int, m: int):
     z = np.ascontiguousarray(noise_planes, np.float32).reshape(-1)
     c = np.ascontiguousarray(counts, np.int32).reshape(-1)
@@ -610,6 +647,14 @@ class Renderer:
         _check(lib().pt_denoise_guided(C.byref(opt), _f(out)))
         return out
 
+    def denoise_adaptive(self, **opts) -> np.ndarray:
+        """The image filtered by the variance-guided filter with per-pixel sample counts (pt_denoise_adaptive): denoise_guided for
+        the adaptive state, valid in the uniform state too.  Same preconditions as denoise_guided."""
+        out = np.empty((self.n, 3), np.float32)
+        opt = denoise_options(**opts)
+        _check(lib().pt_denoise_adaptive(C.byref(opt), _f(out)))
+        return out
+
     # ---- noise estimate from batch sums (include/pt_amd.h: pt_noise_fold) ----
     def noise_fold(self) -> None:
         """Folds the iterations rendered since the last fold into the noise estimate as one group (asynchronous)."""
@@ -743,6 +788,15 @@ class Renderer:
         s, p, z, out = _denoise_guided_arrays(rgb_sum, planes, noise_planes, w, rows)
         opt = denoise_options(**opts)
         _check(lib().pt_stage_denoise_guided(int(w), int(rows), _f(s), _f(p), _f(z), int(groups), int(iters), C.byref(opt), _f(out)))
+        return out
+
+    @staticmethod
+    def stage_denoise_adaptive(rgb_sum: np.ndarray, planes: np.ndarray, noise_planes: np.ndarray, counts: np.ndarray, w: int, rows: int,
+                               **opts) -> np.ndarray:
+        """denoise_adaptive_host's arguments through the adaptive filter's kernels (pt_stage_denoise_adaptive)."""
+        s, p, z, c, out = _denoise_adaptive_arrays(rgb_sum, planes, noise_planes, counts, w, rows)
+        opt = denoise_options(**opts)
+        _check(lib().pt_stage_denoise_adaptive(int(w), int(rows), _f(s), _f(p), _f(z), _i(c), C.byref(opt), _f(out)))
         return out
 
     @staticmethod

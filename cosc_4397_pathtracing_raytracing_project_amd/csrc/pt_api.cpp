@@ -899,6 +899,7 @@ int pt_render_features(int iter_first, int iter_count) { return pt_ctx_render_fe
 int pt_readback_features(float* planes_host) { return pt_ctx_readback_features(g_default, planes_host); }
 int pt_denoise(float samples, const PtDenoiseOptions* opt, float* rgb_avg_host) { return pt_ctx_denoise(g_default, samples, opt, rgb_avg_host); }
 int pt_denoise_guided(const PtDenoiseOptions* opt, float* rgb_avg_host) { return pt_ctx_denoise_guided(g_default, opt, rgb_avg_host); }
+int pt_denoise_adaptive(const PtDenoiseOptions* opt, float* rgb_avg_host) { return pt_ctx_denoise_adaptive(g_default, opt, rgb_avg_host); }
 int pt_noise_fold(void) { return pt_ctx_noise_fold(g_default); }
 int pt_get_noise(double* sse, int* groups, int* iterations) { return pt_ctx_get_noise(g_default, sse, groups, iterations); }
 int pt_readback_noise(float* planes_host) { return pt_ctx_readback_noise(g_default, planes_host); }

@@ -4,6 +4,8 @@
 // (denoise_host, exported as pt_denoise_host) both run, so the two cannot disagree; tests/denoise_ref.py restates them in numpy.
 // The variance-guided form (pt_denoise_guided; tests/denoise_guided_ref.py) is the same code with kGuided = true: the colour term is
 // scaled by the centre's variance, which is prepared from the noise planes, prefiltered once and filtered along with the colour.
+// The adaptive form (pt_denoise_adaptive; tests/denoise_adaptive_ref.py) is the guided one with the sample counts of every pixel
+// instead of two scalars: a prepare and a prefilter of its own, then the guided levels and the finish as they are.
 // Every float operation is a separate IEEE operation in the order pt_amd.h states (`#pragma clang fp contract(off)` in every body, correctly
 // rounded division, denormals kept), so the result does not depend on the arithmetic mode of the build or on the side it runs on.
 // Plain C++ apart from PT_HD: the system compiler accepts it (a host sanitizer run needs nothing else).
@@ -20,6 +22,7 @@
 #include <vector>
 
 #include "../../include/pt_amd.h"
+#include "pt_adaptive.h"
 #include "pt_portable_math.h"
 
 namespace ptdn {
@@ -145,6 +148,64 @@ PT_HD void var_prefilter_pixel(int W, int R, int x, int y, const V4* n, const V4
     }
   }
   c0[i0].w = acc / gsum;
+}
+
+// adaptive (pt_denoise_adaptive; tests/denoise_adaptive_ref.py): prepare_pixel_guided with the counts of the pixel itself — cnt, the
+// plane of pt_adaptive.h, or nullptr: the uniform state, (T, M) for every pixel, as ptad::resolve_pixel — and Tf_p into the position
+// buffer's spare word, which no tap reads (dist2: xyz) and the two bodies above leave 0.
+PT_HD void prepare_pixel_adaptive(size_t i, size_t npix, const float* S, const V4* planes, const V4* noise, const ptad::Cnt* cnt, int32_t T, int32_t M,
+                                  int keep_albedo, V4* n, V4* p, V4* a, V4* c) {
+#pragma clang fp contract(off)
+  const int32_t Tp = cnt ? cnt[i].T : T, Mp = cnt ? cnt[i].M : M;
+  const float Tf = (float)Tp;
+  const float Df = (float)(Mp - 1) * Tf;
+  const V4 s0 = planes[i], s1 = planes[npix + i], s2 = planes[2 * npix + i];
+  const bool hit = s1.w > 0.0f;
+  V4 vn{0.0f, 0.0f, 0.0f, hit ? 1.0f : 0.0f}, va{0.0f, 0.0f, 0.0f, 0.0f}, vp{0.0f, 0.0f, 0.0f, Tf};
+  if (hit) {
+    vn.x = s0.x / s1.w, vn.y = s0.y / s1.w, vn.z = s0.z / s1.w;
+    va.x = s1.x / s1.w, va.y = s1.y / s1.w, va.z = s1.z / s1.w;
+    vp.x = s2.x / s1.w, vp.y = s2.y / s1.w, vp.z = s2.z / s1.w;
+  }
+  V4 vc{S[3 * i] / Tf, S[3 * i + 1] / Tf, S[3 * i + 2] / Tf, 0.0f};
+  if (!keep_albedo) {
+    vc.x = va.x > 0.0f ? vc.x / va.x : vc.x;
+    vc.y = va.y > 0.0f ? vc.y / va.y : vc.y;
+    vc.z = va.z > 0.0f ? vc.z / va.z : vc.z;
+  }
+  const V4 prev = noise[i], q = noise[npix + i];
+  const float vx = guided_variance(prev.x, q.x, va.x, Tf, Df, keep_albedo);
+  const float vy = guided_variance(prev.y, q.y, va.y, Tf, Df, keep_albedo);
+  const float vz = guided_variance(prev.z, q.z, va.z, Tf, Df, keep_albedo);
+  va.w = (vx + vy) + vz;
+  n[i] = vn, p[i] = vp, a[i] = va, c[i] = vc;
+}
+
+// adaptive variance prefilter: var_prefilter_pixel over the per-sample variance var_raw(q) * Tf_q (neighbours differ in their counts:
+// the selection key's argument and arithmetic, ptad::key_pixel), back in the centre's unit.  Reads n.w, a.w, p.w, writes c0.w.
+PT_HD void var_prefilter_pixel_adaptive(int W, int R, int x, int y, const V4* n, const V4* a, const V4* p, V4* c0) {
+#pragma clang fp contract(off)
+  constexpr float G[3] = {1.0f / 4.0f, 1.0f / 2.0f, 1.0f / 4.0f};
+  const size_t i0 = (size_t)y * W + x;
+  const float hit = n[i0].w;
+  float num = 0.0f, den = 0.0f;
+#pragma unroll
+  for (int j = -1; j <= 1; ++j) {
+    const int yt = y + j;
+    if (yt < 0 || yt >= R) continue;
+#pragma unroll
+    for (int i = -1; i <= 1; ++i) {
+      const int xt = x + i;
+      if (xt < 0 || xt >= W) continue;
+      const size_t q = (size_t)yt * W + xt;
+      if (n[q].w != hit) continue;
+      const float g = G[j + 1] * G[i + 1];
+      const float s = a[q].w * p[q].w;
+      num = num + g * s;
+      den = den + g;
+    }
+  }
+  c0[i0].w = (num / den) / p[i0].w;
 }
 
 // ── level: one tap against one centre ────────────────────────────────────────────────────────────────────────────────────
@@ -302,6 +363,30 @@ inline void denoise_guided_host(int W, int R, const float* S, const float* plane
   for (size_t i = 0; i < npix; ++i) prepare_pixel_guided(i, npix, S, pl.data(), nz, Tf, Df, P.keep_albedo, n, p, a, col[0]);
   for (int y = 0; y < R; ++y)
     for (int x = 0; x < W; ++x) var_prefilter_pixel(W, R, x, y, n, a, col[0]);
+  for (size_t i = 0; i < npix && var_raw; ++i) var_raw[i] = a[i].w;
+  for (size_t i = 0; i < npix && var_0; ++i) var_0[i] = col[0][i].w;
+  if (!out) return;
+  for (int l = 0; l < P.levels; ++l)
+    for (int ty = 0; ty < level_slots(R, l); ++ty)
+      for (int x = 0; x < W; ++x) level_column_guided(W, R, x, ty, l, P, col[color_buffer(l)], n, p, col[color_buffer(l + 1)]);
+  for (size_t i = 0; i < npix; ++i) finish_pixel(i, P.keep_albedo, col[color_buffer(P.levels)], a, out);
+}
+
+// The adaptive filter on the host: counts holds {T_p, M_p} per pixel (pt_readback_adaptive's layout), every M_p >= 2 and T_p >= M_p.
+inline void denoise_adaptive_host(int W, int R, const float* S, const float* planes, const float* noise, const int32_t* counts, const Params& P, float* out,
+                                  float* var_raw = nullptr, float* var_0 = nullptr) {
+  const size_t npix = (size_t)W * R;
+  std::vector<V4> ws(kWorkspaceV4 * npix);
+  V4 *n = ws.data(), *p = n + npix, *a = p + npix, *col[2] = {a + npix, a + 2 * npix};
+  std::vector<V4> pl((PT_FEATURE_PLANES + PT_NOISE_PLANES) * npix);
+  for (size_t i = 0; i < PT_FEATURE_PLANES * npix; ++i) pl[i] = V4{planes[4 * i], planes[4 * i + 1], planes[4 * i + 2], planes[4 * i + 3]};
+  V4* nz = pl.data() + PT_FEATURE_PLANES * npix;
+  for (size_t i = 0; i < PT_NOISE_PLANES * npix; ++i) nz[i] = V4{noise[4 * i], noise[4 * i + 1], noise[4 * i + 2], noise[4 * i + 3]};
+  std::vector<ptad::Cnt> cnt(npix);
+  for (size_t i = 0; i < npix; ++i) cnt[i] = ptad::Cnt{counts[2 * i], counts[2 * i + 1]};
+  for (size_t i = 0; i < npix; ++i) prepare_pixel_adaptive(i, npix, S, pl.data(), nz, cnt.data(), 0, 0, P.keep_albedo, n, p, a, col[0]);
+  for (int y = 0; y < R; ++y)
+    for (int x = 0; x < W; ++x) var_prefilter_pixel_adaptive(W, R, x, y, n, a, p, col[0]);
   for (size_t i = 0; i < npix && var_raw; ++i) var_raw[i] = a[i].w;
   for (size_t i = 0; i < npix && var_0; ++i) var_0[i] = col[0][i].w;
   if (!out) return;

@@ -24,6 +24,15 @@ int pt_denoise_launch(hipStream_t stream, int w, int rows, const float* rgb_sum_
 int pt_denoise_guided_resolve(const char* who, int groups, int64_t iters, const PtDenoiseOptions* opt, ptdn::Params* P, float* Tf, float* Df);
 int pt_denoise_guided_launch(hipStream_t stream, int w, int rows, const float* rgb_sum_dev, const float* planes_dev, const float* noise_dev, float Tf,
                              float Df, const ptdn::Params& P, void* workspace_dev, const float** rgb_avg_dev);
+// The adaptive form (pt_denoise_adaptive): the guided form with per-pixel counts.  pt_denoise_adaptive_resolve: the options -> parameters, or
+// the refusal.  pt_denoise_adaptive_check: what the host and stage entries refuse in their arrays (counts: w*rows * {T_p, M_p}, the first pixel
+// with M_p < 2 or T_p < M_p is named), then the options.  pt_denoise_adaptive_launch: as pt_denoise_guided_launch with counts_dev, the plane
+// `cnt` of adaptive sampling, or nullptr: every pixel has (iters, groups), groups >= 2; same workspace.
+int pt_denoise_adaptive_resolve(const char* who, const PtDenoiseOptions* opt, ptdn::Params* P);
+int pt_denoise_adaptive_check(const char* who, int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, const int32_t* counts,
+                              const PtDenoiseOptions* opt, ptdn::Params* P);
+int pt_denoise_adaptive_launch(hipStream_t stream, int w, int rows, const float* rgb_sum_dev, const float* planes_dev, const float* noise_dev,
+                               const void* counts_dev, int iters, int groups, const ptdn::Params& P, void* workspace_dev, const float** rgb_avg_dev);
 
 // The noise estimate (pt_noise.hip), on raw device pointers and a stream.  state_dev holds pt_noise_state_bytes(pixels) bytes:
 // PT_NOISE_PLANES planes of `pixels` float4, then one double per PT_NOISE_PIXELS_PER_PARTIAL pixels (k_noise_fold's partial sums),

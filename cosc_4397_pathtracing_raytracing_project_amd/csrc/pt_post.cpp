@@ -84,6 +84,30 @@ int pt_ctx_denoise_guided(PtContext* c, const PtDenoiseOptions* opt, float* rgb_
   return copy_out(c, "pt_denoise_guided", rgb_avg_host, 3, [&](const float** d) { return pt_ctx_denoise_guided_device(c, opt, d); });
 }
 
+// The adaptive form: the guided filter with the sample counts of every pixel, so the one filter that runs in the adaptive state (the
+// count plane) as well as in the uniform state (the fold's counters for every pixel, as pt_readback_adaptive reports them).
+int pt_ctx_denoise_adaptive_device(PtContext* c, const PtDenoiseOptions* opt, const float** rgb_dev) {
+  if (need(c, "pt_denoise_adaptive")) return -1;
+  Ctx& g = *c;
+  if (admit(g, "pt_denoise_adaptive", kNotFailed | kWholeRows)) return -1;
+  const int W = g.cam.resolution[0];
+  if (!g.d_feat) return pt_fail("pt_denoise_adaptive: no feature pass has been rendered (pt_render_features)");
+  if (!g.d_noise || g.noise_groups < 1) return pt_fail("pt_denoise_adaptive: nothing has been folded (pt_noise_fold)");
+  if (admit(g, "pt_denoise_adaptive", kFoldedAll)) return -1;
+  if (g.noise_groups < 2)
+    return pt_fail("pt_denoise_adaptive: %d group(s) folded; a variance needs at least 2 (pt_noise_fold after each group of iterations)", g.noise_groups);
+  if (g.noise_iters > INT32_MAX) return pt_fail("pt_denoise_adaptive: %lld iterations folded: the per-pixel counts are int32", (long long)g.noise_iters);
+  ptdn::Params P{};
+  if (pt_denoise_adaptive_resolve("pt_denoise_adaptive", opt, &P)) return -1;
+  HIP_OK(hipSetDevice(g.device));
+  if (ensure(g, g.d_denoise, pt_denoise_workspace_bytes((size_t)g.N))) return -1;
+  return pt_denoise_adaptive_launch(g.stream, W, g.N / W, g.d_image, reinterpret_cast<const float*>(g.d_feat), static_cast<const float*>(g.d_noise),
+                                    g.adaptive ? g.d_acnt : nullptr, (int)g.noise_iters, g.noise_groups, P, g.d_denoise, rgb_dev);
+}
+int pt_ctx_denoise_adaptive(PtContext* c, const PtDenoiseOptions* opt, float* rgb_avg_host) {
+  return copy_out(c, "pt_denoise_adaptive", rgb_avg_host, 3, [&](const float** d) { return pt_ctx_denoise_adaptive_device(c, opt, d); });
+}
+
 // ---- noise estimate from batch sums, render until a target PSNR (csrc/pt_noise.hip) ----------------------------
 int pt_ctx_noise_fold(PtContext* c) {
   if (need(c, "pt_noise_fold")) return -1;

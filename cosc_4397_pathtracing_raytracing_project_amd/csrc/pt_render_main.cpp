@@ -7,7 +7,7 @@
 //                       [--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa]
 //                       [--preview N] [--convergence N | --reference FILE.pfm] [--clean-db X] [--features]
 //                       [--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]]
-//                       [--denoise-guided] [--until-db X [--until-group G] [--adaptive F]]
+//                       [--denoise-guided] [--until-db X [--until-group G] [--adaptive F [--denoise-adaptive]]]
 //
 // Without --gpus the run goes through the pathtrace.h-compatible shim (pathtraceInit / pathtrace per
 // iteration / pathtraceFree), i.e. the code path a reference main.cpp would take.  With --gpus K (K >= 1;
@@ -36,12 +36,15 @@
 // iterations (--until-group, default 0 = one batch), a fold after each, until the estimated PSNR is above X dB; --spp becomes the cap.
 // Prints `noise: <iterations> iterations, <groups> groups, estimated PSNR <x> dB`; the file names, --features, --denoise and the
 // curves carry the iterations actually rendered.
-// --adaptive F (needs --until-db X, takes --until-group; excludes --gpus / --devices, --denoise*, --convergence, --reference and
-// --preview): adaptive sampling (pt_render_adaptive) — two uniform groups of G iterations, then rounds of G iterations over the
+// --adaptive F (needs --until-db X, takes --until-group; excludes --gpus / --devices, --denoise, --denoise-guided, --convergence,
+// --reference and --preview): adaptive sampling (pt_render_adaptive) — two uniform groups of G iterations, then rounds of G iterations over the
 // noisiest fraction F (0 < F <= 1) of the pixels, until the estimated PSNR is above X dB or --spp iteration numbers are used up.
 // Prints `adaptive: <iterations> iterations, <rounds> rounds, <samples> samples (<x> of uniform), estimated PSNR <y> dB`, x being
 // the samples over iterations * pixels; the PNG / PFM / HDR hold the resolved image (pt_resolve: every pixel's sum over its own
 // sample count) and the file name carries ceil(samples / pixels).
+// --denoise-adaptive (needs --adaptive F; implies --features; excludes --denoise and --denoise-guided, takes the --denoise-* options,
+// sigma C's default being 8): the variance-guided filter with per-pixel sample counts (pt_denoise_adaptive) over the adaptive image,
+// after the resolved image is written.  Same output files as --denoise.
 // Output name: PREFIX.<spp>samp.png, or with --stamp the reference's own
 // <FILE>.<UTC start time>.<spp>samp.png (main.cpp:99-102).
 #include <hip/hip_runtime.h>
@@ -65,12 +68,12 @@ int main(int argc, char** argv) {
     std::printf("Usage: %s SCENEFILE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] "
                 "[--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa] [--preview N] "
                 "[--convergence N | --reference FILE.pfm] [--clean-db X] [--features] "
-                "[--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]] [--denoise-guided] [--until-db X [--until-group G] [--adaptive F]]\n", argv[0]);
+                "[--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]] [--denoise-guided] [--until-db X [--until-group G] [--adaptive F [--denoise-adaptive]]]\n", argv[0]);
     return 1;
   }
   int rw = 0, rh = 0, spp = 0, depth = 0, gpus = -1, arith = PT_ARITH_EXACT, preview = 0, transport = PT_GROUP_TRANSPORT_AUTO;
   std::vector<int> device_list;
-  bool pfm = false, hdr = false, stamp = false, aa = false, features = false, denoise = false, guided = false;
+  bool pfm = false, hdr = false, stamp = false, aa = false, features = false, denoise = false, guided = false, dn_adaptive = false;
   PtDenoiseOptions dn_opt{};
   int convergence = 0, until_group = 0;
   bool until = false, until_group_given = false;
@@ -117,6 +120,7 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[i], "--features")) features = true;  // first-hit feature buffers next to the image
     else if (!std::strcmp(argv[i], "--denoise")) denoise = true;    // the filtered image next to the image
     else if (!std::strcmp(argv[i], "--denoise-guided")) guided = true;  // ... by the variance-guided form of the filter
+    else if (!std::strcmp(argv[i], "--denoise-adaptive")) dn_adaptive = true;  // ... by the form that reads per-pixel sample counts
     else if (!std::strcmp(argv[i], "--denoise-keep-albedo")) dn_opt.keep_albedo = 1;
     else if (!std::strcmp(argv[i], "--denoise-levels") && i + 1 < argc) {
       char* end = nullptr;
@@ -183,11 +187,19 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--denoise and --denoise-guided exclude each other (one filtered image)\n");
     return 1;
   }
-  if (!denoise && !guided && (dn_opt.levels || dn_opt.keep_albedo || dn_opt.sigma_color != 0.0f || dn_opt.sigma_normal != 0.0f || dn_opt.sigma_position != 0.0f)) {
-    std::fprintf(stderr, "--denoise-levels, --denoise-sigma and --denoise-keep-albedo want --denoise or --denoise-guided\n");
+  if (dn_adaptive && (denoise || guided)) {
+    std::fprintf(stderr, "--denoise-adaptive excludes --denoise and --denoise-guided (one filtered image)\n");
     return 1;
   }
-  if (denoise || guided) features = true;
+  if (dn_adaptive && !(adaptive > 0.0f)) {
+    std::fprintf(stderr, "--denoise-adaptive wants --adaptive (the filter of an adaptively sampled image)\n");
+    return 1;
+  }
+  if (!denoise && !guided && !dn_adaptive && (dn_opt.levels || dn_opt.keep_albedo || dn_opt.sigma_color != 0.0f || dn_opt.sigma_normal != 0.0f || dn_opt.sigma_position != 0.0f)) {
+    std::fprintf(stderr, "--denoise-levels, --denoise-sigma and --denoise-keep-albedo want --denoise, --denoise-guided or --denoise-adaptive\n");
+    return 1;
+  }
+  if (denoise || guided || dn_adaptive) features = true;
   if (until_group_given && !until && !guided) {
     std::fprintf(stderr, "--until-group wants --until-db or --denoise-guided\n");
     return 1;
@@ -373,6 +385,14 @@ int main(int argc, char** argv) {
       std::vector<float> rgb((size_t)W * H * 3);
       if (pt_denoise_guided(&dn_opt, rgb.data())) {
         std::fprintf(stderr, "HIP error (pt_denoise_guided): %s\n", pt_last_error());
+        return EXIT_FAILURE;
+      }
+      save_denoised(rgb);
+    }
+    if (dn_adaptive) {
+      std::vector<float> rgb((size_t)W * H * 3);
+      if (pt_denoise_adaptive(&dn_opt, rgb.data())) {
+        std::fprintf(stderr, "HIP error (pt_denoise_adaptive): %s\n", pt_last_error());
         return EXIT_FAILURE;
       }
       save_denoised(rgb);

@@ -267,6 +267,25 @@ int pt_stage_denoise_guided(int w, int rows, const float* rgb_sum, const float* 
                       [&](const float* img, const float* pl, const float* nz, void* ws, const float** out) { return pt_denoise_guided_launch(g.stream, w, rows, img, pl, nz, Tf, Df, P, ws, out); });
 }
 
+// The adaptive filter's kernels on caller-supplied host arrays (pt_denoise_adaptive_host's arguments); the counts travel beside the frame
+int pt_stage_denoise_adaptive(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, const int32_t* counts,
+                              const PtDenoiseOptions* opt, float* rgb_avg) {
+  if (need(default_context(), "pt_stage_denoise_adaptive")) return -1;
+  Ctx& g = *default_context();
+  if (rows >= 32768) return pt_fail("pt_stage_denoise_adaptive: a frame of %d x %d pixels is not supported", w, rows);
+  if (!rgb_avg) return pt_fail("pt_stage_denoise_adaptive: null argument");
+  ptdn::Params P{};
+  if (pt_denoise_adaptive_check("pt_stage_denoise_adaptive", w, rows, rgb_sum, planes, noise_planes, counts, opt, &P)) return -1;
+  Scratch counts_sc;  // (filter_stage synchronises before it returns)
+  int32_t* d_counts = nullptr;
+  HIP_OK(hipSetDevice(g.device));
+  if (device_copy(counts_sc, "pt_stage_denoise_adaptive", counts, 2 * (size_t)w * rows, &d_counts)) return -1;
+  return filter_stage(g, "pt_stage_denoise_adaptive", (size_t)w * rows, rgb_sum, planes, noise_planes, rgb_avg,
+                      [&](const float* img, const float* pl, const float* nz, void* ws, const float** out) {
+                        return pt_denoise_adaptive_launch(g.stream, w, rows, img, pl, nz, d_counts, 0, 0, P, ws, out);
+                      });
+}
+
 // The selection's kernels on caller-supplied host arrays (pt_adaptive_select_host's arguments)
 int pt_stage_adaptive_select(int w, int rows, const float* noise_planes, const int32_t* counts, int m, int32_t* list) {
   if (need(default_context(), "pt_stage_adaptive_select")) return -1;

@@ -500,9 +500,9 @@ int pt_denoise_guided_variance_host(int w, int rows, const float* rgb_sum, const
  *     MI355X in that configuration (tests/test_gpu_adaptive.py): 0.843, the estimate reading 33.84 dB where the image has 33.10 dB.
  *   - A pixel whose first two groups agree exactly has w = 0 and is sampled again only through its neighbours' variance (the
  *     prefilter).  For background and emitter pixels that is the point; a pixel that is noisy but unlucky twice is reached the same way.
- * Out of scope: pt_group_* (a rank's top m is not the frame's), filtering an adaptive image on the device (pt_ctx_resolve_device is
- * the hook: pt_denoise and pt_denoise_guided refuse the adaptive state), a list length that varies from round to round, and any
- * tuning of the path-tracing kernels for incoherent lists.
+ * Out of scope: pt_group_* (a rank's top m is not the frame's), a list length that varies from round to round, and any tuning of
+ * the path-tracing kernels for incoherent lists.  pt_denoise and pt_denoise_guided refuse the adaptive state; pt_denoise_adaptive
+ * (below) is the filter that reads the per-pixel counts.
  * In the adaptive state pt_readback (S), pt_get_noise (sse = the last merge's, groups = M + rounds, iterations = the highest
  * iteration number folded or merged), pt_readback_noise, pt_render_features and pt_get_stats still work; pt_render, pt_noise_fold,
  * pt_render_until, pt_denoise, pt_denoise_guided, pt_save_u8 and pt_preview_rgba8* fail with a message that names pt_resolve and
@@ -528,6 +528,51 @@ int pt_adaptive_select_host(int w, int rows, const float* noise_planes, const in
  * pixels added in pixel order.  The device's image, planes and counts equal it bit for bit. */
 int pt_adaptive_merge_host(int pixels, float* rgb_sum, float* planes, int32_t* counts, const int32_t* list, int m, const float* group_sum,
                            int group_iters, double* sse);
+
+/* ---- variance-guided filter with per-pixel sample counts: pt_denoise_guided for an adaptively sampled image.  Valid in both states;
+ * in the uniform state every pixel has the fold's (T, M), exactly as pt_readback_adaptive reports them.  Everything not stated here
+ * is pt_denoise_guided's specification word for word: float32 throughout, every operation a separate IEEE operation in the order
+ * written, no contraction, correctly rounded division, denormals kept; skipped taps, dn, dp, H, exp32, rows outer and columns inner;
+ * the level formula with cf = inv_c / (var_l + PT_DENOISE_VARIANCE_FLOOR); var_l+1 = vsum / (wsum * wsum); finish; PtDenoiseOptions
+ * with sigma_color == 0 meaning 8.0 and < 0 switching the colour term off.
+ * Inputs: S, s0 s1 s2, the noise planes prev.xyz | w and q.xyz | 0 (the merge keeps prev == S), and the plane cnt = {T_p, M_p}.
+ *   prepare  per pixel p:  Tf_p = (float)T_p;  Df_p = (float)(M_p - 1) * Tf_p;  c = S_p / Tf_p per component (pt_resolve's value bit
+ *            for bit, before demodulation); n, a, p, hit and demodulation as pt_denoise; per component k:
+ *            d = q_k - (prev_k * prev_k) / Tf_p;  v_k = (d > 0 ? d : 0) / Df_p   (the merge's own v_k bit for bit, or the fold's for
+ *            a pixel no round has touched);  unless keep_albedo: v_k = a_k > 0 ? v_k / (a_k * a_k) : v_k;   var_raw = (v_x + v_y) + v_z
+ *   variance prefilter, once, over the PER-SAMPLE variance (var_raw is the variance of a mean: where neighbours differ in their
+ *            counts it is not one quantity; the argument and the arithmetic of pt_adaptive_round's selection key):
+ *            num = 0, den = 0;  for j = -1 .. 1 (rows, outer), i = -1 .. 1, q = (x + i, y + j), skipped when q is outside the W x R
+ *            rectangle or hit(q) != hit(x, y):   g = G[j + 1] * G[i + 1], G = 1/4 1/2 1/4;   s = var_raw(q) * Tf_q;
+ *            num = num + g * s;   den = den + g   (multiply, then add);      var_0(x, y) = (num / den) / Tf_(x, y)
+ *   levels and finish: the guided form's, unchanged (the same kernels).
+ * In the uniform state with T a power of two the multiplication and the division by Tf are exact, and the result equals
+ * pt_denoise_guided's bit for bit (barring subnormal products); with any other T the two agree to a few roundings of var_0
+ * (tests/test_denoise_adaptive_host.py, 97 x 61: no pixel differs at T = 8; at T = 7, 1,920 of 5,917 differ, by at most 2.3e-7 relative).
+ * Errors with a message, before anything is allocated or launched, in this order: a failed context; a striped or ragged tile; no
+ * feature pass yet; nothing folded; iterations rendered since the last fold ("fold first"); fewer than 2 groups folded; levels, a
+ * sigma or keep_albedo as pt_denoise_guided refuses them.  The adaptive state is not refused.
+ * Nothing new is allocated: the workspace is the 80 bytes per pixel of pt_denoise and pt_denoise_guided, allocated by whichever of
+ * the three runs first.  Tf_p travels in the position buffer's spare word (no tap reads it; the other two filters leave it 0),
+ * var_raw in the albedo buffer's, var_l in the colour buffers'.  Neither the image, the feature buffers, the noise planes, the count
+ * plane, the fold and round counters nor PtStats.samples change: a round after a filter call selects and renders what it would have
+ * without the call.  Synchronises.
+ * What it buys (cornell 96x54, depth 8, PT_ARITH_EXACT, MSE against 2048 spp; two uniform groups of 4 then rounds of 4 over a quarter
+ * of the pixels, 32 iterations' worth of samples; default options): the raw adaptive image (a) has 4.903e-4, the filtered one (b) 8.080e-5, 32 uniform
+ * iterations folded in four groups of 8 and filtered by pt_denoise_guided (c) 1.294e-4: b / a = 0.1648, b / c = 0.6242 — at equal
+ * samples, filtered adaptive beats filtered uniform here.  These figures were simulated on the CPU (the oracle's samples with the
+ * host fold, select, merge and filters) and measured on an MI355X (tests/test_gpu_denoise_adaptive.py); the two agree in every
+ * printed digit, as they should: the exact build reproduces the oracle's samples bit for bit and the filter is specified to the bit.
+ * One scene, one sample budget: no claim beyond it. */
+int pt_denoise_adaptive(const PtDenoiseOptions* opt, float* rgb_avg_host);
+/* The same on the host (no GPU): pt_denoise_guided_host's arrays, counts w*rows * 2 int32 (T_p, M_p; pt_readback_adaptive's layout)
+ * with every M_p >= 2 and T_p >= M_p (the first pixel that breaks this is named in the refusal).  The device result equals it bit
+ * for bit. */
+int pt_denoise_adaptive_host(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, const int32_t* counts,
+                             const PtDenoiseOptions* opt, float* rgb_avg);
+/* Host-only, for tests and tuning: the two variances the levels start from, w*rows floats each (either may be NULL). */
+int pt_denoise_adaptive_variance_host(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, const int32_t* counts,
+                                      const PtDenoiseOptions* opt, float* var_raw, float* var_0);
 
 /* saveImage()'s per-pixel conversion (main.cpp:91-97 x mirror, image.cpp:26-30 clamp * 255 truncated) on the
  * device: pixel_count*3 bytes, row-major, x mirrored inside each row; the tile must consist of whole rows.
@@ -559,6 +604,8 @@ int pt_ctx_denoise(PtContext* c, float samples, const PtDenoiseOptions* opt, flo
 int pt_ctx_denoise_device(PtContext* c, float samples, const PtDenoiseOptions* opt, const float** rgb_dev);
 int pt_ctx_denoise_guided(PtContext* c, const PtDenoiseOptions* opt, float* rgb_avg_host);
 int pt_ctx_denoise_guided_device(PtContext* c, const PtDenoiseOptions* opt, const float** rgb_dev); /* as pt_ctx_denoise_device */
+int pt_ctx_denoise_adaptive(PtContext* c, const PtDenoiseOptions* opt, float* rgb_avg_host);
+int pt_ctx_denoise_adaptive_device(PtContext* c, const PtDenoiseOptions* opt, const float** rgb_dev); /* as pt_ctx_denoise_device */
 int pt_ctx_noise_fold(PtContext* c);
 int pt_ctx_get_noise(PtContext* c, double* sse, int* groups, int* iterations);
 int pt_ctx_readback_noise(PtContext* c, float* planes_host);
@@ -673,6 +720,9 @@ int pt_stage_denoise(int w, int rows, const float* rgb_sum, const float* planes,
 int pt_stage_denoise_guided(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, int groups, int64_t iters,
                             const PtDenoiseOptions* opt, float* rgb_avg);
 
+/* The kernels of pt_denoise_adaptive on caller-supplied host arrays (pt_denoise_adaptive_host's arguments; rows < 32768). */
+int pt_stage_denoise_adaptive(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, const int32_t* counts,
+                              const PtDenoiseOptions* opt, float* rgb_avg);
 /* The selection's kernels on caller-supplied host arrays (pt_adaptive_select_host's arguments; rows < 32768). */
 int pt_stage_adaptive_select(int w, int rows, const float* noise_planes, const int32_t* counts, int m, int32_t* list);
 /* The worker context of pt_adaptive_round alone: iterations iter_first .. iter_first + iter_count - 1 of the m listed tile pixels
