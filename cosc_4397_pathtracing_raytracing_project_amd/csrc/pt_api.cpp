@@ -17,13 +17,14 @@
 
 #include "pt_adaptive.h"
 #include "pt_context.h"
+#include "pt_lds.h"
 #include "pt_scene.h"
 #include "pt_sched.h"
 
 namespace {
 
 std::string g_err;
-constexpr int kDebugFlags = 16 | 32 | 64 | 128 | 256 | 512 | ptk::kRetireEveryIteration | 2048 | ptk::kWholeRecords;  // the PtOptions.debug_flags bits pt_init accepts
+constexpr int kDebugFlags = 16 | 32 | 64 | 128 | 256 | 512 | ptk::kRetireEveryIteration | 2048 | ptk::kWholeRecords | ptk::kNoFirstBounce;  // the PtOptions.debug_flags bits pt_init accepts
 static_assert(sizeof(PtOptions) == 80, "capi.PtOptions mirrors this layout");
 static_assert(PT_CONVERGENCE_WAVES == ptk::kConvWaves, "pt_amd.h documents the size of the convergence metric's partial sums");
 }  // namespace
@@ -135,11 +136,13 @@ int run_batch(Ctx& g, int iter_first, int kb) {
   b.primary_pieces = g.primary_pieces ? g.primary_pieces
                      : ptk::primary_shares(b) ? ptk::auto_shared_pieces(kb, g.qs.nq, g.ret.wq0) : ptk::auto_primary_pieces(kb, g.qs.nq, g.ret.wq0);
   b.paths_pieces = g.paths_pieces;
+  const ptk::SceneTables sc = tables(g);
   b.retire_once = ptk::retires_once(b, g.debug_flags) ? 1 : 0;  // (every batch of the context, the timing batches of choose_traversal among them)
-  b.split_records = ptk::splits_records(b, g.debug_flags) ? 1 : 0;  // (likewise; the unfused kernels' batches are flat: whole records)
+  b.split_records = ptk::record_form(b, g.debug_flags, ptk::search_form(sc), sc.num_mats);  // (likewise; the unfused kernels' batches are flat: whole records)
+  if (b.split_records == ptk::kFirstBounce) b.primary_pieces = 1;  // one trace per chunk and batch: primary_pieces / primary_share cut nothing
+  g.record_form = b.split_records;
   b.list = g.list;
   if (b.list) b.stripe = 1, b.gap = 0, b.inv_stripe = 1.0f;  // (BatchInfo::list: the list form sits behind the stripe test)
-  const ptk::SceneTables sc = tables(g);
   const ptk::KernelApi& k = *g.k;
   auto cnt_row = [&](int d) { return g.d_cnt + ptk::cnt_index(g.qs, d, 0); };  // the counter row of depth d
   int d0 = 0;
@@ -786,6 +789,7 @@ int pt_ctx_get_stats(PtContext* c, PtStats* out) {
     out->grid_cells = res[0] * res[1] * res[2];
   }
   out->tight_leaves = g.tight_leaves;
+  out->record_form = g.record_form;
   out->paths_waves = 0;
   if (g.qs.deal && g.grid_paths > 0) {  // the table the NEXT batch's k_paths launch will read (ptd::Queues::deal)
     const ptk::DealMap dm = ptk::deal_map(g.qs);

@@ -63,6 +63,7 @@ struct PtShared {
   int cap_bpc = 8;
   bool legacy = false;
   int debug_flags = 0;
+  int record_form = 0;  // BatchInfo::split_records of the last batch (PtStats.record_form)
   bool fuse_primary = true, fuse_bounces = true;
   bool aa_jitter = false;
 };

@@ -91,6 +91,9 @@ struct BatchInfo {
   const int32_t* list;
   int32_t split_records;   // 1 (the host sets it from pt_sched.h splits_records): a depth-1 record's origin and material index are stored once per
                            // batch, in plane 1 at the slot of iteration 0; plane 0 holds direction, sample id and the specular / diffuse bit
+                           // 2 (pt_sched.h first_bounces, LDS-table search form only): one whole record per surviving pixel and batch at the slot
+                           // of iteration 0 — bounce origin, hit normal, camera direction, tile pixel | material — and k_paths decides depth 0
+                           // and samples the first bounce of every iteration's path itself; k_primary runs no iteration loop
 };
 
 // Convergence metric of the gather (PtOptions.convergence; k_collect_conv in pt_output.inc).  Iteration iter_first + k of a batch gets

@@ -1126,9 +1126,9 @@ __global__ __launch_bounds__(kBlock) void k_intersect_grid(SceneTables sc, ptd::
 // Waves per SIMD a k_primary instance is compiled for.  Two shared instances end at 72 VGPRs — seven waves, which the persistent
 // grid of a scene with little LDS per block uses — by the allocator's choice, not by the bound; their SPLIT forms came out at 74
 // under the same bound and are asked for the seven outright (72 VGPRs, no scratch; exact / kTopScan would spill, and has six either way).
-template <Search F, bool SPLIT>
+template <Search F, int SPLIT>
 constexpr int primary_waves() {
-  return SPLIT && ((PT_ARITH == 2 && F == kTopScan) || (PT_ARITH == 0 && F == kLdsTables)) ? 7 : kPrimaryWaves;
+  return SPLIT == kSplitRecords && ((PT_ARITH == 2 && F == kTopScan) || (PT_ARITH == 0 && F == kLdsTables)) ? 7 : kPrimaryWaves;
 }
 // ── depth 0 fused: generateRayFromCamera + computeIntersections + shadeAndExtendRays ────────
 // Primary rays are a pure function of the sample id, so depth 0 needs no path state in memory at
@@ -1156,7 +1156,10 @@ constexpr int primary_waves() {
 // SPLIT (BatchInfo::split_records, shared form only; pt_sched.h): a survivor's record is the 16-byte per-iteration word (direction,
 // sample id | specular bit) in plane 0 and, from the run that holds iteration 0 of the batch only, the 16-byte invariant word
 // (origin, material index) in plane 1 at the slot of iteration 0; its throughput is not stored at all.
-template <Search F, bool SHARE = false, bool SPLIT = false>
+// SPLIT == kFirstBounce (BatchInfo::split_records 2, kLdsTables only; pt_sched.h first_bounces): the kernel has no per-iteration work
+// left — a chunk is traced once per BATCH, a survivor's one record (bounce origin, hit normal, camera direction, pixel | material)
+// goes to the slot of iteration 0, and k_paths decides depth 0 and samples the first bounce of every iteration from it.
+template <Search F, bool SHARE = false, int SPLIT = 0>
 __global__ __launch_bounds__(kBlock, (primary_waves<F, SPLIT>())) void k_primary(SceneTables sc, ptd::Camera cam, BatchInfo b, ptd::Queues qs,
                                                     int32_t* __restrict__ cnt0, int32_t* __restrict__ cnt_out,
                                                     ptd::PathBuf out, ptd::RetireBuf ret) {
@@ -1329,7 +1332,42 @@ __global__ __launch_bounds__(kBlock, (primary_waves<F, SPLIT>())) void k_primary
       nl += (int)__popcll(live), nd += (int)__popcll(deadm);
     };
     if constexpr (RING) ws = carry_init<true, 2>(wbase), ws.qo_tab = cam_qo, ws.cam_o = o;  // every strand starts with an empty ring
-    if constexpr (SHARE) {
+    if constexpr (SHARE && SPLIT == kFirstBounce) {
+      // First bounce in k_paths (pt_sched.h first_bounces; the host gives such a batch ONE piece, and the run is the whole batch):
+      // chunk jj is traced once, a surviving pixel gets its one record — what every iteration's depth-0 shading starts from — at the
+      // slot of iteration 0, a retiring one its record as in every BatchInfo::retire_once batch, and the pair of counts, the same in
+      // every iteration, goes to sub[] of all of them.  No iteration loop, no shade_decide of a survivor, no direction sampling.
+      const int sub_off = sub_offset(quo, rem, shared_rho(r, 0, wq)) * 64;
+      int fnl = 0, fnd = 0;  // survivors / retirees of the wave's chunks so far (wave-uniform)
+      auto record_group = [&](unsigned long long best, const float* rec, const Group& g) {
+        const bool valid = g.valid;
+        const Hit h = resolve_hit(best, rec, valid, leaf_geom);
+        const bool cdead = valid && (h.t < 0.0f || mats[h.mat].emittance > 0.0f), lives = valid && !cdead;  // shade_decide's own tests (see retire_once below)
+        const unsigned long long livem = ballot(lives), cdeadm = ballot(cdead);
+        if (lives) path_store(out, qbase + sub_off + fnl + rank_in(livem), bounce_origin(h.n, h.p), h.n, g.d, PathTag{pack_first(g.pl, h.mat, b.slot_shift), g.phash, 0});
+        if (cdead) {
+          ShadeIO s;
+          s.o = o;
+          s.d = g.d;
+          s.c = mk(1.0f, 1.0f, 1.0f);
+          s.alive = false;
+          shade_decide(mats, b.trace_depth, 0, iter_hash_of(ihash, sc, b, 0, 0) ^ g.phash, h.t, h.mat, s);
+          rt.rec[sub_off + fnd + rank_in(cdeadm)] = ptd::Word4{s.c.x, s.c.y, s.c.z, __int_as_float(g.pl)};
+        }
+        fnl += (int)__popcll(livem), fnd += (int)__popcll(cdeadm);
+      };
+      pp.any = false;
+      int it = 0;
+      for (int jj = shared_rho(r, 0, wq); jj < sh.my_nq; jj += wq, ++it) trace(it, group_of(jj, 0), record_group);
+      if constexpr (RING) {  // the ring's last group (see the shared form's tail)
+        if (pp.any) {
+          carry_drain_to<true, 2, kD0, true>(ws, pp.mark, lane, nodes, geoms);
+          record_group(ws.best[pp.par * 64 + lane], ws.rec + pp.par * 6 * 64 + lane, pp.g);
+        }
+      }
+      // K identical counts (zeros where the wave had no chunk); K may exceed the 64 lanes
+      for (int k = lane; k < b.K; k += 64) rt.sub[k * rt.wq0 + shared_rho(r, k, wq)] = ((unsigned long long)(uint32_t)fnd << 32) | (uint32_t)fnl;
+    } else if constexpr (SHARE) {
       // Shared form (pt_sched.h): the wave keeps residue r through the piece, so chunk jj is traced ONCE per run of iterations
       // [s0, s1) and shaded s1 - s0 times from the same hit; lane l of vnl / vnd counts the survivors / retirees of iteration s0 + l.
       const int cap = shared_run_cap(b.primary_share), sub_off = sub_offset(quo, rem, shared_rho(r, k0, wq)) * 64;
@@ -1348,7 +1386,7 @@ __global__ __launch_bounds__(kBlock, (primary_waves<F, SPLIT>())) void k_primary
           const float ht = h.t;
           const int hmat = h.mat;
           const f3 hn = h.n, hp = h.p;
-          if constexpr (SPLIT) {
+          if constexpr (SPLIT == kSplitRecords) {
             // BatchInfo::split_records (pt_sched.h): the lanes that survive — every hit but an emitter's, in every iteration — get their
             // invariant word (shade_bounce's origin, the material) from the run that holds iteration 0 of the batch, at the slot their
             // records have in that iteration (invariant_slot of every other iteration's).
@@ -1397,7 +1435,7 @@ __global__ __launch_bounds__(kBlock, (primary_waves<F, SPLIT>())) void k_primary
             const int nl = __builtin_amdgcn_readlane(vnl, k - s0), nd = __builtin_amdgcn_readlane(vnd, k - s0);
             const int sub0 = k * rt.seg_cap + sub_off;  // first slot of sub-list / sub-region (q, k, r)
             const PathTag tag{make_slot(b, k, pl), phash, k};
-            if constexpr (SPLIT) {
+            if constexpr (SPLIT == kSplitRecords) {
               if (alive) out.r[qbase + sub0 + nl + rank_in(live)] = ptd::Word4{s.d.x, s.d.y, s.d.z, __uint_as_float(pack_kind(tag.slot, bo.kind == 1))};
             } else if (alive) path_store(out, qbase + sub0 + nl + rank_in(live), s.o, s.d, s.c, tag);
             if (dead && !once) rt.rec[sub0 + nd + rank_in(deadm)] = ptd::Word4{s.c.x, s.c.y, s.c.z, __int_as_float(pl)};
@@ -1516,6 +1554,21 @@ PT_DEV void fetch_split_to_lds(const void* b0, const void* b1, int i, int i0, ui
       : [base] "s"(lds_base), [b0] "s"(b0), [b1] "s"(b1), [o] "v"(off), [o0] "v"(off0)
       : "memory", "scc");
 }
+// The whole record waiting in a lane's refill slot (fetch_record_to_lds) and its visit word, once every vector-memory operation has
+// landed: everything outstanding here (last refill's transfers, last refill's retirement stores) is a whole iteration old.
+PT_DEV void read_record_slot(uint32_t s16, uint32_t s4, v4f& w0, v4f& w1, float& cz, int& nslot, int& nrs) {
+  asm volatile(
+      "s_waitcnt vmcnt(0)\n\t"
+      "ds_read_b128 %0, %5\n\t"
+      "ds_read_b128 %1, %5 offset:1024\n\t"
+      "ds_read_b32 %2, %6\n\t"
+      "ds_read_b32 %3, %6 offset:256\n\t"
+      "ds_read_b32 %4, %6 offset:512\n\t"
+      "s_waitcnt lgkmcnt(0)"
+      : "=&v"(w0), "=&v"(w1), "=&v"(cz), "=&v"(nslot), "=&v"(nrs)
+      : "v"(s16), "v"(s4)
+      : "memory");
+}
 // Per-wave LDS of k_paths: closest-hit keys, winner records, the candidate ring (16-bit entries: top entry << 6 | owner lane;
 // the chunk looks leaf and geom index up in tword[top entry] = leaf | geom << 8, so it does not go through nodes[leaf]) and the
 // running totals.  The rays are NOT kept in LDS: the lanes are persistent, a chunk fetches a candidate's ray from its owner's
@@ -1627,7 +1680,10 @@ static_assert((kVisitRing & (kVisitRing - 1)) == 0, "visit numbers wrap with a m
 // SPLIT (BatchInfo::split_records, pt_sched.h): a path's record is the per-iteration word (direction, sample id | specular bit) at its
 // own slot of plane 0 and the invariant word (origin, material index) at the same slot of ITERATION 0 in plane 1 — the cursor
 // keeps both bases — and its throughput is (1, 1, 1) times the material's spec or color, formed when the lane takes the path.
-template <Search MODE, bool SPLIT = false>
+// SPLIT == kFirstBounce (BatchInfo::split_records 2, MODE 0 only; pt_sched.h first_bounces): the record is the pixel's one whole record at
+// the slot of iteration 0; the iteration comes from the cursor and waits beside the visit number (pack_visit), and the lane that
+// takes the record decides depth 0 and samples the first bounce itself, in the rotated loop behind the other forms'.
+template <Search MODE, int SPLIT = 0>
 __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPathsScanWaves : kPathsGridWaves) void k_paths(SceneTables sc, BatchInfo b, ptd::Queues qs, int32_t* __restrict__ cnt /* [depth][Q] rows */,
                                                                ptd::PathBuf in, ptd::RetireBuf ret) {
   extern __shared__ float4 lds_raw[];
@@ -1729,6 +1785,10 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
   [[maybe_unused]] int clist0 = 0;  // SPLIT: clist without its iteration's k * seg_cap — where the sub-list of iteration 0 starts
   int ce = ne, cstart = total, ccnt = 0, clist = 0;  // cursor (wave-uniform): sub-list e = k * wq0 + rho; nothing to stream leaves it at the end
   int cord = 0;  // sub-list visits of the cursor so far
+  // kFirstBounce: the cursor's iteration and its depth-0 hash iter_hash(iter_first + k, 0), formed where the cursor moves; next_h (per lane):
+  // that hash of the record waiting in the lane's slot.  (Hashed per lane at the take instead: k_paths 12-20 us slower, profiles/first_bounce.log.)
+  [[maybe_unused]] int cur_k = 0;
+  [[maybe_unused]] uint32_t cur_h = 0u, next_h = 0u;
   // A window of 64 consecutive sub[] words in registers (lane l holds sub[win0 + l]): the cursor reads counts and retiree numbers
   // with v_readlane instead of a dependent global load per sub-list.  With a whole 1080p frame a wave's piece touches a handful of
   // sub-lists of ~1000 paths; with an eighth of it (eight GPUs, ~190 iterations per batch) dozens of sub-lists of ~25, a fifth of
@@ -1754,7 +1814,8 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
   auto cursor_bases = [&](int first_rank) {
     const int ec = min(ce, ne - 1), ck = ec / wq0, crho = ec - ck * wq0;  // (wave-uniform: scalar instructions)
     clist = ck * rt.seg_cap + sub_offset(quo, rem, crho) * 64;
-    if constexpr (SPLIT) clist0 = invariant_slot(clist, ck, rt.seg_cap);
+    if constexpr (SPLIT != 0) clist0 = invariant_slot(clist, ck, rt.seg_cap);
+    if constexpr (SPLIT == kFirstBounce) cur_k = ck, cur_h = iter_hash(b.iter_first + ck, 0);  // (wave-uniform: the hash runs on the scalar unit)
     window_to(ec);
     const int crec = clist + (int)(uint32_t)(sub_word(ec) >> 32);
     if (lane == 0) fillc[cord & (kVisitRing - 1)] = crec + (first_rank - cstart);  // where this wave's first record of the visit goes
@@ -1796,8 +1857,10 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
     while (true) {
       const bool in = pending && rank < cstart + ccnt;
       if (in) at = clist + (rank - cstart), rs = cord;
-      if constexpr (SPLIT)
+      if constexpr (SPLIT != 0)
         if (in) at0 = clist0 + (rank - cstart);
+      if constexpr (SPLIT == kFirstBounce)
+        if (in) rs = (int)pack_visit(cur_k, cord), next_h = cur_h;  // the iteration waits with the record, its depth-0 hash in a register of the lane
       pending = pending && !in;
       if (!ballot(pending) || ce >= ne || cord - cord0 >= kVisitsPerRefill) break;
       cstart += ccnt;  // on to the next sub-list that holds anything: the first non-empty one behind ce in the window, else the window moves on
@@ -1829,9 +1892,9 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
   int nx_rs = 0;  // !SLOTS: ... and its visit
   int* slot_rs = reinterpret_cast<int*>(slots + kSlotVisit) + lane;  // SLOTS: the visit of the record waiting in the lane's slot
   auto fetch = [&](int at, [[maybe_unused]] int at0, int rs) {
-    if constexpr (SLOTS && SPLIT) fetch_split_to_lds(in0, in1, at, at0, s_base), *slot_rs = rs;
-    else if constexpr (SLOTS) fetch_record_to_lds(in0, in1, in2, at, s_base), *slot_rs = rs;
-    else if constexpr (SPLIT) {  // the two words as they lie in memory: unpacked when the lane takes them
+    if constexpr (SLOTS && SPLIT == kSplitRecords) fetch_split_to_lds(in0, in1, at, at0, s_base), *slot_rs = rs;
+    else if constexpr (SLOTS) fetch_record_to_lds(in0, in1, in2, SPLIT == kFirstBounce ? at0 : at, s_base), *slot_rs = rs;  // (first bounce: the pixel's one record)
+    else if constexpr (SPLIT == kSplitRecords) {  // the two words as they lie in memory: unpacked when the lane takes them
       const ptd::Word4 w0 = in.r[qbase + at], w1 = in.r[in.stride + qbase + at0];
       nx.o = mk(w0.x, w0.y, w0.z), nx.d = mk(w0.w, w1.x, w1.y), nx.c = mk(w1.z, w1.w, 0.f), nx_rs = rs;
     } else nx = path_load(in, qbase + at), nx_rs = rs;
@@ -1843,7 +1906,7 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
   bool valid = false, fresh = false, owes = false;  // owes: the lane's path died and its retirement record is not stored yet
   bool has_next = false;                            // a record is waiting in the lane's slot (on its way there)
   int streamed = 0, p_hi = 0;  // the current piece: records [.., streamed) handed out, the piece ends at p_hi; -1: no piece left for this wave
-  while (true) {
+  while (SPLIT != kFirstBounce) {  // (that form's loop, the same round rotated, follows this one)
     // ── on to the wave's next piece, once the current one is handed out: its own, then whatever the queue's counter gives ──
     if (streamed >= p_hi && p_hi >= 0) {
       int nextp = -1;
@@ -1867,7 +1930,7 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
       v4f w0, w1;
       float cz;
       int nslot, nrs;
-      if constexpr (SLOTS && SPLIT) {
+      if constexpr (SLOTS && SPLIT == kSplitRecords) {
         asm volatile(
             "s_waitcnt vmcnt(0)\n\t"
             "ds_read_b128 %0, %3\n\t"
@@ -1879,18 +1942,7 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
             : "memory");
         cz = 0.f, nslot = 0;
       } else if constexpr (SLOTS) {
-        // everything outstanding here (last refill's transfers, last refill's retirement stores) is a whole iteration old
-        asm volatile(
-            "s_waitcnt vmcnt(0)\n\t"
-            "ds_read_b128 %0, %5\n\t"
-            "ds_read_b128 %1, %5 offset:1024\n\t"
-            "ds_read_b32 %2, %6\n\t"
-            "ds_read_b32 %3, %6 offset:256\n\t"
-            "ds_read_b32 %4, %6 offset:512\n\t"
-            "s_waitcnt lgkmcnt(0)"
-            : "=&v"(w0), "=&v"(w1), "=&v"(cz), "=&v"(nslot), "=&v"(nrs)
-            : "v"(s16), "v"(s4)
-            : "memory");
+        read_record_slot(s16, s4, w0, w1, cz, nslot, nrs);
       } else {
         w0 = v4f{nx.o.x, nx.o.y, nx.o.z, nx.d.x}, w1 = v4f{nx.d.y, nx.d.z, nx.c.x, nx.c.y}, cz = nx.c.z, nslot = nx.tag.slot, nrs = nx_rs;
       }
@@ -1898,7 +1950,7 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
         rt.rec[rslot] = ptd::Word4{c.x, c.y, c.z, __int_as_float(slot & ((1 << b.slot_shift) - 1))};
         owes = false;
       }
-      if constexpr (SPLIT) {  // (per-iteration word, invariant word)
+      if constexpr (SPLIT == kSplitRecords) {  // (per-iteration word, invariant word)
         if (take) {
           const uint32_t word = __float_as_uint(w0.w);
           const ptd::Mat* m = mats + __float_as_int(w1.w);
@@ -1998,6 +2050,130 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
         if (alive) o = s.o, d = s.d, depth += 1, fresh = true;
         else valid = false, owes = true;
       }
+    }
+  }
+  // ── BatchInfo::split_records 2 (pt_sched.h first_bounces): the same round, rotated ────────────────────────────────────────────
+  // search, shade_decide of the resolved lanes, pieces + refill, direction sampling.  The refill above follows the shading at once
+  // anyway; here it sits between shade_bounce's two halves, so a lane whose path has just died — or that never had one — takes its
+  // next record, decides depth 0 for it (shade_decide's own depth-0 path: the seed of the record's iteration, at most one draw, the
+  // throughput (1, 1, 1) times spec or color) and samples the path's first bounce in the instruction stream that samples the
+  // survivors' next one, in lanes that would sit it out.  Across the refill a lane holds the new origin, the axis and the Bounce instead
+  // of hit point, normal and old direction.  A taken path leaves the round at depth 1, fresh: it never sees a search at depth 0.
+  // Memory ordering as above: a slot is read a round or more after its transfer was issued, the retirement store of a path that died
+  // in this round's decide is issued after the slot reads, and what is outstanding at the wait is a whole round old.  Start
+  // (nothing to search or decide, the refill fetches) and end (nothing valid, waiting or left after a refill) are ordinary rounds.
+  if constexpr (SPLIT == kFirstBounce) {
+    static_assert(MODE == kLdsTables, "the first-bounce form takes its records from the refill slots of the LDS-table form");
+    while (true) {
+      // ── search: box tests + appends for the lanes with a new ray; too few resolved lanes with candidates pending: a partial chunk ──
+      if (ballot(fresh)) {
+        if constexpr (kFast) paths_search(cy, (cfloat4*)(uintptr_t)sc.top_b, tword, ntop, geoms, o, d, fresh, lane, mark);
+        else paths_search(cy, top, tword, ntop, geoms, o, d, fresh, lane, mark);
+      }
+      bool ready = valid && (cy.processed - mark) >= 0;
+      if (cy.count > 0 && __popcll(ballot(ready)) < kPathsMinReady) {
+        paths_chunk(cy, cy.count, lane, o, d, tword, geoms);  // count < 64 here
+        ready = valid;
+      }
+      fresh = false;
+      // ── decide for the resolved lanes; a survivor's new origin and axis ──
+      Bounce bo;
+      bo.kind = 0, bo.rng_x = 1u, bo.roughness = 0.f;
+      f3 axis = mk(0.f, 0.f, 0.f);
+      bool go = false;  // the lane samples a direction in this round
+      {
+        ShadeIO s;
+        s.o = mk(0.f, 0.f, 0.f);
+        s.d = d;
+        s.c = c;
+        s.alive = false;
+        const int k = (int)((uint32_t)slot >> b.slot_shift);
+        const unsigned long long best = cy.best[lane];
+        Hit h{false, -1.0f, -1, 0, mk(0.f, 0.f, 0.f), mk(0.f, 0.f, 0.f)};
+        if (ready) {
+          if ((uint32_t)(best >> 32) != 0x7f7fffffu) {
+            h.t = __uint_as_float((uint32_t)(best >> 32));
+            const float* rr = cy.rec + lane;
+            h.n = mk(rr[0 * 64], rr[1 * 64], rr[2 * 64]);
+            h.p = mk(rr[3 * 64], rr[4 * 64], rr[5 * 64]);
+            h.mat = lmat[(uint32_t)best & 63u];
+          }
+          const uint32_t ih = he > 0 ? ihash[(depth - 1) * he + k] : iter_hash(b.iter_first + k, depth);
+          bo = shade_decide(mats, b.trace_depth, depth, ih ^ phash, h.t, h.mat, s);
+        }
+        const bool alive = ready && s.alive, dead = ready && !s.alive;
+        if (dead) atomicAdd(&died[depth & 63], 1);
+        if (dead) rslot = atomicAdd(&fillc[rslot & (kVisitRing - 1)], 1);
+        if (ready) {
+          c = s.c;
+          if (alive) {
+            const BounceAxis a = bounce_axis(bo, h.n, h.p, d);
+            o = a.o, axis = a.f, go = true;
+          } else valid = false, owes = true;
+        }
+      }
+      // ── on to the wave's next piece, once the current one is handed out ──
+      if (streamed >= p_hi && p_hi >= 0) {
+        int nextp = -1;
+        if (cord == 0) nextp = r;
+        else if (pieces.needs_counter()) {
+          int v = 0;
+          if (lane == 0) v = atomicAdd(&qs.deal[dm.piece_counter(q)], 1);
+          nextp = wq + __builtin_amdgcn_readfirstlane(v);
+        }
+        const PieceRange pr = pieces.piece_range(nextp);
+        if (pr.some) {
+          streamed = pr.start, p_hi = pr.end;
+          seek(streamed);
+        } else {
+          p_hi = -1;
+        }
+      }
+      // ── refill: lanes without a path take the record waiting in their slot and decide its depth 0; the slot gets the next record ──
+      const bool take = !valid && has_next;
+      if (ballot(take || owes || (!valid && !has_next && streamed < p_hi))) {
+        v4f w0, w1;
+        float cz;
+        int word, vword;
+        read_record_slot(s16, s4, w0, w1, cz, word, vword);
+        if (owes) {
+          rt.rec[rslot] = ptd::Word4{c.x, c.y, c.z, __int_as_float(slot & ((1 << b.slot_shift) - 1))};
+          owes = false;
+        }
+        if (take) {  // (bounce origin, hit normal, camera direction, pixel | material) and iteration | visit
+          const int pl = first_pixel(word, b.slot_shift), k = visit_k((uint32_t)vword);
+          const f3 hn = mk(w0.w, w1.x, w1.y), cam_d = mk(w1.z, w1.w, cz);
+          slot = make_slot(b, k, pl), rslot = visit_number((uint32_t)vword);
+          phash = utilhash((uint32_t)global_pixel(b, pl));
+          ShadeIO s;
+          s.o = mk(0.f, 0.f, 0.f);
+          s.d = cam_d;
+          s.c = mk(1.0f, 1.0f, 1.0f);
+          s.alive = false;
+          bo = shade_decide(mats, b.trace_depth, 0, next_h ^ phash, 0.0f, first_material(word, b.slot_shift), s);  // a hit, and no emitter's: it survives
+          o = mk(w0.x, w0.y, w0.z), c = s.c;
+          axis = bo.kind == 1 ? bounce_reflect(cam_d, hn) : hn;
+          depth = 0;
+          valid = go = true;
+          has_next = false;
+        }
+        // (rslot of a path in flight: its visit modulo the packed width, as it waited in the slot)
+        const bool lapping = ballot(valid && visit_gap(cord, rslot) >= kVisitLap) != 0ull;
+        const bool empty = !has_next && !lapping;
+        const unsigned long long em = ballot(empty);
+        const int rank = rank_in(em);
+        const bool more = empty && streamed + rank < p_hi;
+        int at = 0, at0 = 0, rs = 0;
+        const bool served = assign(more, streamed + rank, at, at0, rs);
+        if (served) {
+          has_next = true;
+          fetch(at, at0, rs);
+        }
+        streamed += (int)__popcll(ballot(served));
+      }
+      if (!ballot(valid || has_next) && p_hi < 0) break;  // every path of the wave's pieces has retired
+      // ── direction sampling: this round's survivors and the lanes that took a path ──
+      if (go) d = bounce_sample(bo, axis), depth += 1, fresh = true;
     }
   }
   // statistics: rays traced at depth d >= 2 = this wave's paths retired at depth >= d (row 1 holds the queue's input count already)

@@ -31,14 +31,16 @@ void with_features(const SceneTables& sc, F&& f) {
   return f(k_features<false, true>, intersect_lds<false>(sc).total);
 }
 // share: the shared loop form (one trace per chunk and run of iterations, pt_sched.h) — both forms use the same LDS map;
-// split (shared form only): BatchInfo::split_records
+// split (shared form only): BatchInfo::split_records — 0, kSplitRecords or (the LDS-table form only) kFirstBounce
 template <Search S, typename F>
-void with_primary_of(const SceneTables& sc, bool share, bool split, F&& f) {
+void with_primary_of(const SceneTables& sc, bool share, int split, F&& f) {
   const int lds = primary_lds<S, kFast, kD0>(sc).total;
-  return !share ? f(k_primary<S>, lds) : split ? f(k_primary<S, true, true>, lds) : f(k_primary<S, true>, lds);
+  if constexpr (S == kLdsTables)
+    if (share && split == kFirstBounce) return f(k_primary<S, true, kFirstBounce>, lds);
+  return !share ? f(k_primary<S>, lds) : split ? f(k_primary<S, true, kSplitRecords>, lds) : f(k_primary<S, true>, lds);
 }
 template <typename F>
-void with_primary(const SceneTables& sc, bool share, bool split, F&& f) {
+void with_primary(const SceneTables& sc, bool share, int split, F&& f) {
   switch (search_form(sc)) {
     case kLdsTables: return with_primary_of<kLdsTables>(sc, share, split, f);
     case kTopScan: return with_primary_of<kTopScan>(sc, share, split, f);
@@ -46,18 +48,20 @@ void with_primary(const SceneTables& sc, bool share, bool split, F&& f) {
   }
 }
 
-// split: BatchInfo::split_records — the same LDS map
+// split: BatchInfo::split_records (0, kSplitRecords; kLdsTables also kFirstBounce) — the same LDS map
 template <typename F>
-void with_paths(const SceneTables& sc, Search form, bool split, F&& f) {  // (SceneTables::scan_nodes_lds resolved by the caller)
+void with_paths(const SceneTables& sc, Search form, int split, F&& f) {  // (SceneTables::scan_nodes_lds resolved by the caller)
   switch (form) {
-    case kLdsTables: return split ? f(k_paths<kLdsTables, true>, paths_lds<kLdsTables, kFast>(sc).total) : f(k_paths<kLdsTables>, paths_lds<kLdsTables, kFast>(sc).total);
-    case kTopScan: return split ? f(k_paths<kTopScan, true>, paths_lds<kTopScan, kFast>(sc).total) : f(k_paths<kTopScan>, paths_lds<kTopScan, kFast>(sc).total);
-    case kGrid: return split ? f(k_paths<kGrid, true>, paths_lds<kGrid, kFast>(sc).total) : f(k_paths<kGrid>, paths_lds<kGrid, kFast>(sc).total);
+    case kLdsTables:
+      if (split == kFirstBounce) return f(k_paths<kLdsTables, kFirstBounce>, paths_lds<kLdsTables, kFast>(sc).total);
+      return split ? f(k_paths<kLdsTables, kSplitRecords>, paths_lds<kLdsTables, kFast>(sc).total) : f(k_paths<kLdsTables>, paths_lds<kLdsTables, kFast>(sc).total);
+    case kTopScan: return split ? f(k_paths<kTopScan, kSplitRecords>, paths_lds<kTopScan, kFast>(sc).total) : f(k_paths<kTopScan>, paths_lds<kTopScan, kFast>(sc).total);
+    case kGrid: return split ? f(k_paths<kGrid, kSplitRecords>, paths_lds<kGrid, kFast>(sc).total) : f(k_paths<kGrid>, paths_lds<kGrid, kFast>(sc).total);
   }
 }
 int paths_lds_bytes(const SceneTables& sc, Search form) {
   int bytes = 0;
-  with_paths(sc, form, false, [&](auto, int lds) { bytes = lds; });
+  with_paths(sc, form, 0, [&](auto, int lds) { bytes = lds; });
   return bytes;
 }
 int lds_share_limit(int bytes);
@@ -100,9 +104,9 @@ int lds_table_limit(const SceneTables& sc, int forced_bytes) {
   if (tbl <= kLdsTableBytes && leaves_fit_top(sc)) {
     SceneTables in = sc;
     in.lds_table_bytes = tbl;
-    with_paths(in, kLdsTables, false, occupancy_into(with, 0));
+    with_paths(in, kLdsTables, 0, occupancy_into(with, 0));
   }
-  with_paths(sc, kTopScan, false, occupancy_into(without, 1));
+  with_paths(sc, kTopScan, 0, occupancy_into(without, 1));
   (void)hipGetLastError();
   return (with >= without && with > 0) ? tbl : -1;
 }
@@ -120,10 +124,17 @@ int resident_blocks_per_cu(KernelId id, const SceneTables& sc) {
     case kGenerate: query(k_generate, 0); break;
     case kIntersect: with_intersect(sc, false, false, query); break;
     case kIntersectLegacy: with_intersect(sc, true, false, query); break;
-    case kPrimary: with_primary(sc, false, false, query_share); break;
-    // (a context's batches run either record form of these two, BatchInfo::split_records: same launch bounds and LDS; the smaller count serves both)
-    case kPrimaryShared: with_primary(sc, true, false, query_share), m = n, with_primary(sc, true, true, query_share), n = min(n, m); break;
-    case kPaths: with_paths(resolve_scan_nodes(sc), search_form(sc), false, query_share), m = n, with_paths(resolve_scan_nodes(sc), search_form(sc), true, query_share), n = min(n, m); break;
+    case kPrimary: with_primary(sc, false, 0, query_share); break;
+    // (a context's batches run any record form of these two, BatchInfo::split_records: same LDS; the smallest count serves all — where a
+    // form does not exist for the tables' search form, kFirstBounce, the selectors give the split form again)
+    case kPrimaryShared:
+      for (int form : {0, kSplitRecords, kFirstBounce}) with_primary(sc, true, form, query_share), m = form ? min(m, n) : n;
+      n = m;
+      break;
+    case kPaths:
+      for (int form : {0, kSplitRecords, kFirstBounce}) with_paths(resolve_scan_nodes(sc), search_form(sc), form, query_share), m = form ? min(m, n) : n;
+      n = m;
+      break;
     case kShade: query(k_shade, shade_lds<true>(sc).total); break;
     case kFeatures: with_features(sc, query); break;
   }
@@ -149,7 +160,7 @@ void launch_intersect_grid(hipStream_t s, int grid, const SceneTables& sc, const
 
 void launch_primary(hipStream_t s, int grid, const SceneTables& sc, const ptd::Camera& cam, const BatchInfo& b,
                     const ptd::Queues& qs, int32_t* cnt0, int32_t* cnt_out, ptd::PathBuf out, ptd::RetireBuf ret) {
-  with_primary(sc, primary_shares(b), primary_shares(b) && b.split_records != 0, [&](auto kernel, int lds) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, sc, cam, b, qs, cnt0, cnt_out, out, ret); });
+  with_primary(sc, primary_shares(b), primary_shares(b) ? b.split_records : 0, [&](auto kernel, int lds) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, sc, cam, b, qs, cnt0, cnt_out, out, ret); });
 }
 
 void launch_features(hipStream_t s, int grid, const SceneTables& sc, const ptd::Camera& cam, const BatchInfo& b, float4* feat) {
@@ -162,7 +173,7 @@ void launch_features(hipStream_t s, int grid, const SceneTables& sc, const ptd::
 
 void launch_paths(hipStream_t s, int grid, const SceneTables& sc_in, const BatchInfo& b, const ptd::Queues& qs, int32_t* cnt, ptd::PathBuf in, ptd::RetireBuf ret) {
   const SceneTables sc = resolve_scan_nodes(sc_in);
-  with_paths(sc, search_form(sc), b.split_records != 0, [&](auto kernel, int lds) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, sc, b, qs, cnt, in, ret); });
+  with_paths(sc, search_form(sc), b.split_records, [&](auto kernel, int lds) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, sc, b, qs, cnt, in, ret); });
 }
 void launch_shade(hipStream_t s, int grid, const SceneTables& sc, const BatchInfo& b, int depth, const ptd::Queues& qs,
                   const int32_t* cnt_in, int32_t* cnt_out, ptd::PathBuf in, ptd::HitBuf hits, ptd::PathBuf out,

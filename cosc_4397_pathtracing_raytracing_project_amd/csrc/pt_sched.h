@@ -237,6 +237,51 @@ PT_SCHED uint32_t pack_kind(int sample_id, bool specular) { return (uint32_t)sam
 PT_SCHED int kind_sample_id(uint32_t word) { return (int)(word & 0x7fffffffu); }
 PT_SCHED bool kind_specular(uint32_t word) { return (word >> 31) != 0u; }
 
+// ── depth-1 records: the first bounce sampled in k_paths ──────────────────────────────────────────────────────────────────
+// In a batch that splits its records everything the depth-0 shading of a surviving pixel does per iteration — the seed, the one
+// specular / diffuse draw, the direction sampling — is a pure function of the pixel's first hit and the iteration.  Such a batch
+// (BatchInfo::split_records == kFirstBounce) stores ONE whole 40-byte record per surviving pixel and batch, at the slot its record has
+// in iteration 0 (invariant_slot), and nothing per iteration:
+//   origin      bounce_origin(hit normal, hit point)                      where PathBuf keeps a path's origin
+//   hit normal                                                            where it keeps the direction
+//   camera direction                                                      where it keeps the throughput
+//   tile pixel | material index << slot_shift  (pack_first)               where it keeps the sample id
+// k_primary traces a chunk once per batch and publishes the same pair of counts for every iteration; a lane of k_paths that takes
+// the record of sub-list (k, rho) decides depth 0 for iteration k itself and samples the first bounce with the lanes that
+// survived that round.  The conditions are those of splits_records and retires_once together, plus: the LDS-table search form
+// (the other forms keep the next record in registers; they stay with split records), a material index that fits beside the
+// tile pixel, and a K that fits beside the visit number (pack_visit).  PtOptions.debug_flags kNoFirstBounce: off as an A/B switch.
+constexpr int kNoFirstBounce = 8192;
+constexpr int kSplitRecords = 1, kFirstBounce = 2;  // BatchInfo::split_records
+// The word that waits with a record in a lane's refill slot: the iteration k of its sub-list above the visit number modulo
+// 2^kVisitBits.  A path in flight was taken fewer than kVisitRing (pt_lds.h) <= 2^(kVisitBits - 1) visits ago, so the distance
+// of two visit numbers is compared modulo the packed width (visit_gap).
+constexpr int kVisitBits = 8;
+PT_SCHED uint32_t pack_visit(int k, int visit) { return ((uint32_t)k << kVisitBits) | ((uint32_t)visit & ((1u << kVisitBits) - 1u)); }
+PT_SCHED int visit_k(uint32_t word) { return (int)(word >> kVisitBits); }
+PT_SCHED int visit_number(uint32_t word) { return (int)(word & ((1u << kVisitBits) - 1u)); }  // modulo 2^kVisitBits
+PT_SCHED int visit_gap(int visits_now, int visit) { return (visits_now - visit) & ((1 << kVisitBits) - 1); }
+PT_SCHED bool visit_k_fits(int K) { return K <= (1 << (31 - kVisitBits)); }
+// The record's last word: tile pixel pl < 2^slot_shift below the material index, 31 bits in all.
+PT_SCHED int pack_first(int pl, int mat, int slot_shift) { return (mat << slot_shift) | pl; }
+PT_SCHED int first_pixel(int word, int slot_shift) { return word & ((1 << slot_shift) - 1); }
+PT_SCHED int first_material(int word, int slot_shift) { return (int)((uint32_t)word >> slot_shift); }
+PT_SCHED bool first_material_fits(int num_mats, int slot_shift) { return num_mats <= (1 << (31 - slot_shift)); }
+// search_form: pt_lds.h Search of the context's tables (0: the LDS-table form)
+PT_SCHED bool first_bounces(int primary_share, bool aa_jitter, bool flat, int trace_depth, int debug_flags, int search_form, int num_mats,
+                            int slot_shift, int K) {
+  return splits_records(primary_share, aa_jitter, flat, trace_depth, debug_flags) &&
+         retires_once(primary_share, aa_jitter, flat, trace_depth, debug_flags) && !(debug_flags & kNoFirstBounce) && search_form == 0 &&
+         first_material_fits(num_mats, slot_shift) && visit_k_fits(K);
+}
+PT_SCHED bool first_bounces(const BatchInfo& b, int debug_flags, int search_form, int num_mats) {
+  return first_bounces(b.primary_share, b.aa_jitter != 0, b.flat != 0, b.trace_depth, debug_flags, search_form, num_mats, b.slot_shift, b.K);
+}
+// BatchInfo::split_records of a batch: whole records, split records or the first bounce in k_paths.
+PT_SCHED int record_form(const BatchInfo& b, int debug_flags, int search_form, int num_mats) {
+  return first_bounces(b, debug_flags, search_form, num_mats) ? kFirstBounce : splits_records(b, debug_flags) ? kSplitRecords : 0;
+}
+
 // ── k_paths: falling pieces ───────────────────────────────────────────────────────────────────────────────────────────────
 // BatchInfo::paths_pieces: pieces per wave | fewest paths in a piece << 16.
 PT_SCHED int pack_paths_pieces(int count, int min_piece) { return count | min_piece << 16; }

@@ -86,14 +86,27 @@ PT_DEV f3 bounce_origin(f3 hn, f3 hp) {
   if (kFast || kFloatTrig) return madd(hn, 0.001f, hp);
   return add(hp, scl(hn, 0.001f));
 }
+// shade_bounce in two halves, so that a kernel can put other work between them (k_paths takes new paths there, whose first bounce
+// then runs through the same sampling): bounce_axis — the new origin and the axis the direction is sampled around,
+// f = specular ? reflect(d, n) : n, after which the hit record and the old direction are dead — and bounce_sample, the remaining
+// draws and the trigonometry.  A perfect mirror keeps the reflected direction, which IS its axis.
+struct BounceAxis {
+  f3 o, f;
+};
+PT_DEV f3 bounce_reflect(f3 d, f3 hn) {  // reflect(): incident - 2*dot(incident, n)*n, in the build's arithmetic
+  if (kFast || kFloatTrig) return madd(hn, -2.0f * dot(d, hn), d);
+  return sub(d, scl(hn, 2.0f * dot(d, hn)));
+}
+PT_DEV BounceAxis bounce_axis(const Bounce& bo, f3 hn, f3 hp, f3 d) {
+  const f3 refl = bounce_reflect(d, hn);
+  return BounceAxis{bounce_origin(hn, hp), bo.kind == 1 ? refl : hn};
+}
 template <bool HW>
-PT_DEV void shade_bounce_float(const Bounce& bo, f3 hn, f3 hp, ShadeIO& s) {
+PT_DEV f3 bounce_sample_float(const Bounce& bo, f3 f) {
   MinStd rng(1u);
   rng.x = bo.rng_x;
   const bool spec = bo.kind == 1;
   const float r1 = rng.u01(), r2 = rng.u01(), r3 = rng.u01();
-  const f3 refl = madd(hn, -2.0f * dot(s.d, hn), s.d);
-  const f3 f = spec ? refl : hn;
   const float rev = bo.roughness * r1 * 0.25f;
   const float ct = HW ? __builtin_amdgcn_sqrtf(1.0f - r1) : __builtin_sqrtf(1.0f - r1);
   const float st2 = __builtin_fmaxf(fma_(-ct, ct, 1.0f), 0.0f);
@@ -119,12 +132,11 @@ PT_DEV void shade_bounce_float(const Bounce& bo, f3 hn, f3 hp, ShadeIO& s) {
   local_frame(f, tangent, bitangent);
   const f3 pert = normalize(madd(tangent, x, madd(f, y, scl(bitangent, z))));
   const bool perturb = !spec || bo.roughness > 0.0f;
-  s.o = bounce_origin(hn, hp);
-  s.d = perturb ? pert : refl;
+  return perturb ? pert : f;
 }
-PT_DEV void shade_bounce(const Bounce& bo, f3 hn, f3 hp, ShadeIO& s) {
-  if (kFast) return shade_bounce_float<true>(bo, hn, hp, s);
-  if (kFloatTrig) return shade_bounce_float<false>(bo, hn, hp, s);
+PT_DEV f3 bounce_sample(const Bounce& bo, f3 f) {
+  if (kFast) return bounce_sample_float<true>(bo, f);
+  if (kFloatTrig) return bounce_sample_float<false>(bo, f);
   // The specular branch (pathtrace.cu:402-422) and the diffuse branch (:424-435, :225-238) have the
   // same shape — a frame around an axis f, three trigonometric evaluations, normalize(t*x + f*y + b*z)
   // — so both are evaluated by ONE instruction stream with per-lane operands instead of two divergent
@@ -140,8 +152,6 @@ PT_DEV void shade_bounce(const Bounce& bo, f3 hn, f3 hp, ShadeIO& s) {
   rng.x = bo.rng_x;
   const bool spec = bo.kind == 1;
   const float r1 = rng.u01(), r2 = rng.u01(), r3 = rng.u01();  // diffuse consumes only two; the engine dies here
-  const f3 refl = sub(s.d, scl(hn, 2.0f * dot(s.d, hn)));     // reflect(): incident - 2*dot(incident, n)*n
-  const f3 f = spec ? refl : hn;
   const float angle = (float)((double)(bo.roughness * r1) * kPi * (double)0.5f);
   const float theta = ptmath::acosf32(__builtin_sqrtf(1.0f - r1));
   const float phi = (float)((double)2.0f * kPi * (double)r2);
@@ -160,9 +170,13 @@ PT_DEV void shade_bounce(const Bounce& bo, f3 hn, f3 hp, ShadeIO& s) {
   f3 tangent, bitangent;
   local_frame(f, tangent, bitangent);
   const f3 pert = normalize(add(add(scl(tangent, x), scl(f, y)), scl(bitangent, z)));
-  const bool perturb = !spec || bo.roughness > 0.0f;  // a perfect mirror keeps the reflected direction
-  s.o = bounce_origin(hn, hp);
-  s.d = perturb ? pert : refl;
+  const bool perturb = !spec || bo.roughness > 0.0f;  // a perfect mirror keeps the reflected direction: its axis
+  return perturb ? pert : f;
+}
+PT_DEV void shade_bounce(const Bounce& bo, f3 hn, f3 hp, ShadeIO& s) {  // the two halves back to back
+  const BounceAxis a = bounce_axis(bo, hn, hp, s.d);
+  s.o = a.o;
+  s.d = bounce_sample(bo, a.f);
 }
 
 

@@ -108,7 +108,13 @@ typedef struct PtOptions {
                                and is stored and gathered in iteration 0 of a batch only), 4096
                                whole 40-byte depth-1 records in every iteration (default under the same conditions: origin and
                                material of a surviving pixel are stored once per batch, direction, sample id and the
-                               specular / diffuse choice per iteration, and the throughput is formed where the path is taken), 2048
+                               specular / diffuse choice per iteration, and the throughput is formed where the path is taken), 8192
+                               split records where the default is less still (scenes whose tables the fused kernels keep in LDS,
+                               under the conditions of 1024 and 4096 together, while iterations per batch and materials fit their
+                               words: ONE record per surviving pixel and batch — bounce origin, hit normal, camera direction,
+                               pixel and material — the primary kernel traces every chunk once per batch, and the bounce kernel
+                               decides depth 0 and samples the first bounce of every iteration's path when a lane takes it;
+                               primary_pieces and primary_share are ignored by that form; PtStats.record_form tells), 2048
                                keep the reference's leaf boxes for spheres (default for large scenes: tightened to the
                                ellipsoid's box, PtStats.tight_leaves; pt_stage_intersect on such a scene then expects ray
                                origins inside the scene bounds or at the camera).  pt_init fails on any other bit. */
@@ -142,7 +148,8 @@ typedef struct PtOptions {
                                (PT_PRIMARY_PIECES below; the struct keeps its 20 words): the kernel traces a group of camera
                                rays once for at most that many iterations of a batch and shades it in each of them (0 =
                                automatic: a whole piece, at most 64; 1: a trace per iteration, as debug_flags 128; always a
-                               trace per iteration with aa_jitter, whose rays differ from iteration to iteration) */
+                               trace per iteration with aa_jitter, whose rays differ from iteration to iteration).  Both are
+                               ignored where the kernel traces once per batch (PtStats.record_form 2, see debug_flags 8192). */
   int32_t paths_pieces;     /* the fused bounce kernel's depth-1 rays cut into this many pieces per wave (automatic: 2) */
   int32_t paths_min_piece;  /* fewest paths in one of those pieces (automatic: 64; small values send small images through
                                the piece switches).  The three piece counts are clamped to 1..0x7fff (of primary_pieces: its low 16
@@ -187,6 +194,9 @@ typedef struct PtStats {
   int32_t paths_waves;                /* 0: every queue has the same number of waves in the fused bounce kernel; otherwise
                                          fewest << 16 | most waves a queue gets in the next batch — dealt by the time the
                                          queues' waves took in the last one (small tiles; same image, debug_flags 64 turns it off) */
+  int32_t record_form;                /* how the last batch handed depth 0 to the fused bounce kernel: 0 whole 40-byte records per
+                                         sample, 1 split records (debug_flags 4096 turns them off), 2 one record per surviving pixel
+                                         and batch, the first bounce sampled in the bounce kernel (debug_flags 8192 turns it off) */
 } PtStats;
 
 /* ---- scene loading (host).  Replaces `new Scene(file)` (src/main.cpp:45,
