@@ -201,7 +201,25 @@ def _mesh_object(idx: int, material: int, trans, rotat, scale, tris) -> str:
             f"SCALE       {f(scale)}\n{body}\n")
 
 
-def mesh_scene_text(res: Tuple[int, int] = (200, 120), iterations: int = 16, depth: int = 8, name: str = "mesh",
+def triangle_table_scene_text(tris, fillers: int = 0, filler_at=(0.0, 0.0, 0.0), res: Tuple[int, int] = (64, 48),
+                              iterations: int = 4, depth: int = 8, name: str = "triangles") -> str:
+    """EXTENSION test input: one `mesh` object per row of a [n, 9] table of world-space vertices (v0 v1 v2), one TRI line
+    each, written with repr(float) under TRANS 0 / ROTAT 0 / SCALE 1 so that the loader returns the float32 values of the
+    table unchanged; cornell's materials, material 1 + k % 4.  `fillers` adds that many small octahedra (scale 0.01, eight
+    triangles each, a 4 x 4 x n lattice of pitch 0.05 from `filler_at`): more leaves, for the global-table kernels."""
+    out: List[str] = [_material(i, **m) for i, m in enumerate(_CORNELL_MATERIALS)]
+    out.append(_camera(res, 45, iterations, depth, name, ("0.0", 5, "10.5"), (0, 5, 0), (0, 1, 0)))
+    idx = 0
+    for k, t in enumerate(tris):
+        out.append(_mesh_object(idx, 1 + k % 4, (0, 0, 0), (0, 0, 0), (1, 1, 1), [tuple(float(x) for x in t)])); idx += 1
+    octa = _octahedron_tris()
+    for k in range(fillers):
+        t = tuple(round(filler_at[a] + 0.05 * c, 4) for a, c in enumerate((k % 4, (k // 4) % 4, k // 16)))
+        out.append(_mesh_object(idx, 1 + k % 4, t, ((k * 13) % 90, (k * 7) % 90, 0), (".01", ".01", ".01"), octa)); idx += 1
+    return "".join(out)
+
+
+def mesh_scene_text(res: Tuple[int, int] = (200, 120),iterations: int = 16, depth: int = 8, name: str = "mesh",
                     grid: int = 0) -> str:
     """EXTENSION test input (not a reference scene): cornell.txt's box and sphere plus `mesh` objects — a red
     octahedron, a mirror-material octahedron, an axis-aligned two-triangle quad facing the camera — and a cube AFTER the

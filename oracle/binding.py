@@ -158,6 +158,20 @@ def generate(pix_begin: int, count: int, iteration: int = 1):
     return o, d
 
 
+def geom_test(g: int, o, d):
+    """The primitive test of geom g alone (box / sphere / triangle by its type) on one ray: (t float32, point [3], normal [3],
+    outside); t = -1 for a miss, where point and normal are not meaningful."""
+    fp = C.POINTER(C.c_float)
+    o = np.ascontiguousarray(o, np.float32)
+    d = np.ascontiguousarray(d, np.float32)
+    p = np.zeros(3, np.float32)
+    n = np.zeros(3, np.float32)
+    out = C.c_int(0)
+    t = lib().orc_geom_test(int(g), o.ctypes.data_as(fp), d.ctypes.data_as(fp), p.ctypes.data_as(fp), n.ctypes.data_as(fp),
+                            C.byref(out))
+    return np.float32(t), p, n, int(out.value)
+
+
 def intersect(o: np.ndarray, d: np.ndarray, stats: bool = False):
     n = o.shape[1]
     t = np.zeros(n, np.float32)

@@ -70,6 +70,10 @@ CASES = [
     ("tiny sub-lists", "cornell", (96, 64), 40, 8, dict(iters_per_batch=40, **_stripes(96, 64, 0, 8)), FIRST),
     # pieces of a path or more: piece switches while taken lanes are in flight, last rounds with nothing left to take
     ("many pieces", "cornell", (96, 64), 5, 8, dict(iters_per_batch=3, paths_pieces=4, paths_min_piece=1), FIRST),
+    # triangles: the one record per pixel stores a triangle's FINISHED normal where the other types store theirs.  scenes.mesh_scene_text
+    # has 26 leaves, which fit the top list, so its tables are in LDS (search form 0, pt_lds.h), and pt_sched.h first_bounces holds:
+    # shared depth 0, no jitter, depth 8, five materials, K = 3 (the sweep of tests/sched_first_bounce_driver.cpp: record_form=2)
+    ("mesh", "mesh", (96, 64), 5, 8, dict(iters_per_batch=3), FIRST),
 ]
 
 _refs = {}
@@ -90,9 +94,12 @@ def _reference(oracle, name, path, res, spp, depth, kw):
 def test_same_image_four_ways(scene_dir, oracle, tmp_path_factory, name, scene, res, spp, depth, kw, form, arith):
     from cosc_4397_pathtracing_raytracing_project_amd import scenes
     tmp = tmp_path_factory.mktemp("first_bounce")
-    path = scenes.write_scene(_half_mirror_text(), str(tmp / "half_mirror.txt")) if scene == "half mirror" else _scene(scene, depth, res, scene_dir, tmp)
+    if scene == "mesh":
+        path = scenes.write_scene(scenes.mesh_scene_text(res=res, depth=depth), str(tmp / "mesh.txt"))
+    else:
+        path = scenes.write_scene(_half_mirror_text(), str(tmp / "half_mirror.txt")) if scene == "half mirror" else _scene(scene, depth, res, scene_dir, tmp)
     img, st = four_ways(path, res, spp, arith, form, **kw)
-    if scene in ("cornell", "half mirror") and depth >= 2:
+    if scene in ("cornell", "half mirror", "mesh") and depth >= 2:
         assert 0 < st.live_rays[1] < st.samples  # some samples survive depth 0 and some do not: depth-1 records exist
     if name == "packet scan":
         assert st.grid_cells == 0

@@ -1,6 +1,7 @@
 """Triangle `mesh` objects — an EXTENSION: the scene format names the type (INSTRUCTION.md:246) and the reference includes
-<glm/gtx/intersect.hpp> (intersections.h:4), but neither its loader nor its kernels implement it.  PARITY UNPINNED: nothing in
-the reference to compare with.  Tested instead:
+<glm/gtx/intersect.hpp> (intersections.h:4), but neither its loader nor its kernels implement it.  The intersection decision and
+distance are pinned to that header's compiled glm::intersectRayTriangle elsewhere (test_ref_tri_golden.py, test_gpu_mesh_pin.py); the
+loader, the padded boxes and the rendering have nothing in the reference to compare with.  Tested here:
   * scenes without meshes are untouched (the rest of the suite);
   * loader: product == oracle byte for byte (triangle primitives, BVH with padded triangle boxes), OBJECT ids keep counting
     objects (a cube after two meshes is still accepted), the reference's scenes parse as before;
@@ -135,3 +136,25 @@ def test_gpu_mesh_modes_within_tolerance(oracle, tmp_path, arith):
     mse = np.mean((a.astype(np.float64) - b) ** 2)
     print(f"{arith} mesh scene: {100 * off:.3f} % off (floor {100 * floor:.3f} %), PSNR {10 * np.log10(1 / mse):.1f} dB")
     assert np.isfinite(a).all() and off <= 0.002 + 3 * floor and 10 * np.log10(1 / mse) >= 45
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("grid", [0, 4])  # LDS tables; global tables with subtree scans
+@pytest.mark.parametrize("arith", ["fma", "fast"])
+def test_gpu_mesh_fused_bounces_equal_the_unfused_stages(tmp_path, arith, grid):
+    """What pt_stage_intersect sees is what k_paths renders: within fma and fast the mesh scene rendered by the fused bounce kernel
+    equals the unfused intersect / shade stages bit for bit (test_gpu_arith.py asserts this for cornell, which has no triangle)."""
+    res, spp = (200, 120) if grid == 0 else (160, 96), 6
+    path = scenes.write_scene(scenes.mesh_scene_text(res=res, grid=grid), str(tmp_path / "m.txt"))
+    imgs = []
+    for kw in ({}, dict(unfused_bounces=True), dict(unfused_bounces=True, iters_per_batch=3)):
+        r = capi.Renderer(capi.Scene(path, res=res), arith=arith, **kw)
+        try:
+            r.render(1, spp)
+            imgs.append(r.readback())
+        finally:
+            r.free()
+    assert np.isfinite(imgs[0]).all() and (imgs[0] > 0).any()
+    for img, what in zip(imgs[1:], ("unfused_bounces", "unfused_bounces, batches of 3")):
+        diff = (bits(imgs[0]) != bits(img)).any(axis=1)
+        assert not diff.any(), f"{arith}, {what}: {diff.sum()} pixels differ, first {np.flatnonzero(diff)[:8]}"
