@@ -24,7 +24,7 @@
 namespace {
 
 std::string g_err;
-constexpr int kDebugFlags = 16 | 32 | 64 | 128 | 256 | 512 | ptk::kRetireEveryIteration | 2048 | ptk::kWholeRecords | ptk::kNoFirstBounce;  // the PtOptions.debug_flags bits pt_init accepts
+constexpr int kDebugFlags = 16 | 32 | 64 | 128 | 256 | 512 | ptk::kRetireEveryIteration | 2048 | ptk::kWholeRecords | ptk::kNoFirstBounce | ptk::kRecordsByVisit | ptk::kTileGather;  // the PtOptions.debug_flags bits pt_init accepts
 static_assert(sizeof(PtOptions) == 80, "capi.PtOptions mirrors this layout");
 static_assert(PT_CONVERGENCE_WAVES == ptk::kConvWaves, "pt_amd.h documents the size of the convergence metric's partial sums");
 }  // namespace
@@ -141,6 +141,7 @@ int run_batch(Ctx& g, int iter_first, int kb) {
   b.split_records = ptk::record_form(b, g.debug_flags, ptk::search_form(sc), sc.num_mats);  // (likewise; the unfused kernels' batches are flat: whole records)
   if (b.split_records == ptk::kFirstBounce) b.primary_pieces = 1;  // one trace per chunk and batch: primary_pieces / primary_share cut nothing
   g.record_form = b.split_records;
+  b.fixed_slots = ptk::fixed_slots(b, g.debug_flags, ptk::search_form(sc), sc.num_mats, g.ret.seg_cap) ? 1 : 0;
   b.list = g.list;
   if (b.list) b.stripe = 1, b.gap = 0, b.inv_stripe = 1.0f;  // (BatchInfo::list: the list form sits behind the stripe test)
   const ptk::KernelApi& k = *g.k;
@@ -185,15 +186,22 @@ int run_batch(Ctx& g, int iter_first, int kb) {
     k.shade(g.stream, g.grid_shade, sc, b, d, queues_for(g, g.grid_shade), cin, cout, g.buf[src], g.hits, g.buf[src ^ 1], g.ret);
     src ^= 1;
   }
-  k.count_stats(g.stream, g.qs, g.d_cnt, g.depth, g.d_stats);
   ptk::ConvInfo cv{g.d_ref, g.d_partial, -1, kb};
   if (g.conv_live) {
     if (g.conv_have_ref) cv.first_k = 0;
     else if (g.conv >= iter_first && g.conv < iter_first + kb) cv.capture_k = g.conv - iter_first, cv.first_k = cv.capture_k + 1, g.conv_have_ref = true;
     g.conv_last = std::max(g.conv_last, iter_first + kb - 1);
   }
-  if (cv.capture_k >= 0 || cv.first_k < kb) k.collect_conv(g.stream, b, g.qs, g.ret, g.d_image, cv, g.d_sse);
-  else k.collect(g.stream, b, g.qs, g.ret, g.d_image);
+  // The gather: a batch with fixed record slots streams them, the counter rows' blocks in the same launch; the metric's batches (its
+  // partial sums have a fixed partition) and every other batch keep the tile gather behind k_count_stats.
+  const bool conv_batch = cv.capture_k >= 0 || cv.first_k < kb;
+  g.gather_form = ptk::gather_form(b.fixed_slots != 0, g.debug_flags, conv_batch);
+  if (g.gather_form == ptk::kGatherStream) k.collect_stream(g.stream, b, g.qs, g.ret, g.d_image, g.d_cnt, g.depth, g.d_stats);
+  else {
+    k.count_stats(g.stream, g.qs, g.d_cnt, g.depth, g.d_stats);
+    if (conv_batch) k.collect_conv(g.stream, b, g.qs, g.ret, g.d_image, cv, g.d_sse);
+    else k.collect(g.stream, b, g.qs, g.ret, g.d_image);
+  }
   HIP_OK(hipGetLastError());
   g.samples += (int64_t)kb * g.N;
   if (g.pending_isect.size() > 16384) {
@@ -790,6 +798,7 @@ int pt_ctx_get_stats(PtContext* c, PtStats* out) {
   }
   out->tight_leaves = g.tight_leaves;
   out->record_form = g.record_form;
+  out->gather_form = g.gather_form;
   out->paths_waves = 0;
   if (g.qs.deal && g.grid_paths > 0) {  // the table the NEXT batch's k_paths launch will read (ptd::Queues::deal)
     const ptk::DealMap dm = ptk::deal_map(g.qs);

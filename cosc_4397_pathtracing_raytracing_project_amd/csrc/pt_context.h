@@ -64,6 +64,7 @@ struct PtShared {
   bool legacy = false;
   int debug_flags = 0;
   int record_form = 0;  // BatchInfo::split_records of the last batch (PtStats.record_form)
+  int gather_form = 0;  // pt_sched.h gather_form of the last batch (PtStats.gather_form)
   bool fuse_primary = true, fuse_bounces = true;
   bool aa_jitter = false;
 };

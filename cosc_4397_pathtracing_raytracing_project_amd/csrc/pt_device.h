@@ -121,10 +121,16 @@ struct HitBuf {
 //     of the sub-region from counters in its registers, stores at once, and leaves the two counts in sub[q][k][rho];
 //   * depths >= 1 (k_paths) run after depth 0 of the whole batch.  A wave takes a contiguous slice of the queue's concatenated
 //     sub-lists; the record of the path at index i of sub-list (k, rho) goes to slot retirees(k, rho) + i of sub-region
-//     (k, rho): decided when the path is taken, no counters at all.  Every sample of the sub-region's chunks retires exactly
-//     once, so the region ends up exactly full (but for the <= 63 slots of a tile's partial last chunk, which k_collect skips);
-//   * k_collect, one workgroup per queue, reads region (q, k) for k = 0, 1, ... front to back, drops the colours into an LDS
-//     tile indexed by pixel, and adds the tile to the queue's pixels — the reference's summation order.
+//     (k, rho) in a batch with fixed slots (BatchInfo::fixed_slots, pt_sched.h fixed_slot: a first-bounce batch) — decided when the
+//     path is taken, no counters at all; in every other batch the paths a wave takes out of one visit of the sub-list, indices
+//     [i0, i1), fill slots retirees + [i0, i1) in order of retirement through a counter per visit in LDS.  Every sample of the
+//     sub-region's chunks retires exactly once, so the region ends up exactly full (but for the <= 63 slots of a tile's partial
+//     last chunk, which the gathers skip);
+//   * fixed slots: record i of sub-list (q, k, rho) is the same pixel for every k there, so slot s of region (q, k) holds ONE pixel
+//     in all K iterations, and k_collect_stream, one thread per slot, adds the K records at s, s + seg_cap, ... to that pixel in
+//     iteration order — the reference's summation order, no tile;
+//   * otherwise (and with the convergence metric) k_collect, one workgroup per queue, reads region (q, k) for k = 0, 1, ... front
+//     to back, drops the colours into an LDS tile indexed by the record's pixel word, and adds the tile to the queue's pixels.
 // The unfused stage kernels (tests, A/B: BatchInfo::flat) append every record at the front of its region through cnt[q][k],
 // one atomic per record, and keep ONE dense depth-1 list per queue.
 struct RetireBuf {

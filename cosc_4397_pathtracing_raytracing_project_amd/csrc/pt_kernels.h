@@ -94,6 +94,8 @@ struct BatchInfo {
                            // 2 (pt_sched.h first_bounces, LDS-table search form only): one whole record per surviving pixel and batch at the slot
                            // of iteration 0 — bounce origin, hit normal, camera direction, tile pixel | material — and k_paths decides depth 0
                            // and samples the first bounce of every iteration's path itself; k_primary runs no iteration loop
+  int32_t fixed_slots;     // 1 (the host sets it from pt_sched.h fixed_slots; split_records 2 only): k_paths stores a path's retirement record at the
+                           // slot its list position gives (pt_sched.h fixed_slot), so a slot holds the same pixel in every iteration's region
 };
 
 // Convergence metric of the gather (PtOptions.convergence; k_collect_conv in pt_output.inc).  Iteration iter_first + k of a batch gets
@@ -179,6 +181,10 @@ struct KernelApi {
   // k_primary runs it (the reference's arithmetic on grid_items), otherwise as k_paths runs it (the build's arithmetic on grid_items_b).
   void (*intersect_grid)(hipStream_t s, int grid, const SceneTables& sc, const ptd::Queues& qs, const int32_t* cnt_in,
                          ptd::PathBuf paths, ptd::HitBuf hits, bool primary);
+  // `collect` for a batch with fixed record slots (BatchInfo::fixed_slots) and `count_stats` in ONE launch: a thread per record slot adds
+  // the slot's K records in iteration order, no tile (k_collect_stream in pt_output.inc); the counter rows' blocks ride behind the gather's.
+  void (*collect_stream)(hipStream_t s, const BatchInfo& b, const ptd::Queues& qs, ptd::RetireBuf ret, float* image_rgb, int32_t* cnt, int depth_count,
+                         unsigned long long* stats);
 };
 const KernelApi* api_exact();
 const KernelApi* api_fma();

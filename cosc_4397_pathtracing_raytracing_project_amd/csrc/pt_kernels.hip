@@ -1683,6 +1683,9 @@ static_assert((kVisitRing & (kVisitRing - 1)) == 0, "visit numbers wrap with a m
 // SPLIT == kFirstBounce (BatchInfo::split_records 2, MODE 0 only; pt_sched.h first_bounces): the record is the pixel's one whole record at
 // the slot of iteration 0; the iteration comes from the cursor and waits beside the visit number (pack_visit), and the lane that
 // takes the record decides depth 0 and samples the first bounce itself, in the rotated loop behind the other forms'.
+// SPLIT == kFixedSlots (such a batch with BatchInfo::fixed_slots; pt_sched.h fixed_slots): the first-bounce form without the visit ring — the
+// cursor keeps where the record of its sub-list's first path goes, the word that waits beside a record is the path's own record slot
+// (pack_fixed), and a dying lane has nothing to ask anybody: no counter, no lap guard, no limit on the visits of a refill.
 template <Search MODE, int SPLIT = 0>
 __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPathsScanWaves : kPathsGridWaves) void k_paths(SceneTables sc, BatchInfo b, ptd::Queues qs, int32_t* __restrict__ cnt /* [depth][Q] rows */,
                                                                ptd::PathBuf in, ptd::RetireBuf ret) {
@@ -1705,6 +1708,7 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
     lnodes = lds + L.nodes;
   }
   using WM = PathsWaveMap<MODE, kFast>;
+  constexpr bool FIXED = SPLIT == kFixedSlots, FIRST = SPLIT == kFirstBounce || FIXED;  // FIRST: the first bounce is sampled here
   const int he = iter_hash_entries(sc);
   uint32_t* tword = reinterpret_cast<uint32_t*>(lds + L.tword);  // MODE 0: [kMaxTop] leaf | geom << 8 per top entry
   int* lmat = reinterpret_cast<int*>(lds + L.lmat);              // MODE 0: [64] material of the leaf at threaded node index i
@@ -1726,7 +1730,7 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
   constexpr bool SLOTS = MODE == 0;
   char* slots = wbase + WM::slots;  // SLOTS: [64] x 16 B, [64] x 16 B, [64] x 4 B, [64] x 4 B, [64] x 4 B
   int* died = reinterpret_cast<int*>(wbase + WM::died);    // [64]: paths of this wave retired AT depth d (statistics; PT_MAX_DEPTH = 64)
-  int* fillc = reinterpret_cast<int*>(wbase + WM::fillc);  // [kVisitRing]: next record slot per sub-list visit
+  [[maybe_unused]] int* fillc = reinterpret_cast<int*>(wbase + WM::fillc);  // [kVisitRing]: next record slot per sub-list visit (FIXED: unused)
   const int ntop = sc.num_top;
   const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + wib);  // (the compiler cannot see that threadIdx.x >> 6 is wave-uniform)
   const int lane = lane_id();
@@ -1789,6 +1793,9 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
   // that hash of the record waiting in the lane's slot.  (Hashed per lane at the take instead: k_paths 12-20 us slower, profiles/first_bounce.log.)
   [[maybe_unused]] int cur_k = 0;
   [[maybe_unused]] uint32_t cur_h = 0u, next_h = 0u;
+  // FIXED: the record slot of the cursor's sub-list's first path, without its iteration's k * seg_cap, and the bits it is packed in
+  [[maybe_unused]] int crec0 = 0;
+  [[maybe_unused]] const int fbits = fixed_bits(rt.seg_cap);
   // A window of 64 consecutive sub[] words in registers (lane l holds sub[win0 + l]): the cursor reads counts and retiree numbers
   // with v_readlane instead of a dependent global load per sub-list.  With a whole 1080p frame a wave's piece touches a handful of
   // sub-lists of ~1000 paths; with an eighth of it (eight GPUs, ~190 iterations per batch) dozens of sub-lists of ~25, a fifth of
@@ -1815,10 +1822,11 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
     const int ec = min(ce, ne - 1), ck = ec / wq0, crho = ec - ck * wq0;  // (wave-uniform: scalar instructions)
     clist = ck * rt.seg_cap + sub_offset(quo, rem, crho) * 64;
     if constexpr (SPLIT != 0) clist0 = invariant_slot(clist, ck, rt.seg_cap);
-    if constexpr (SPLIT == kFirstBounce) cur_k = ck, cur_h = iter_hash(b.iter_first + ck, 0);  // (wave-uniform: the hash runs on the scalar unit)
+    if constexpr (FIRST) cur_k = ck, cur_h = iter_hash(b.iter_first + ck, 0);  // (wave-uniform: the hash runs on the scalar unit)
     window_to(ec);
     const int crec = clist + (int)(uint32_t)(sub_word(ec) >> 32);
-    if (lane == 0) fillc[cord & (kVisitRing - 1)] = crec + (first_rank - cstart);  // where this wave's first record of the visit goes
+    if constexpr (FIXED) crec0 = invariant_slot(crec, ck, rt.seg_cap);  // (pt_sched.h fixed_slot: + the path's list position)
+    else if (lane == 0) fillc[cord & (kVisitRing - 1)] = crec + (first_rank - cstart);  // where this wave's first record of the visit goes
   };
   // put the cursor on the sub-list that rank `at_rank` (< total) lies in: a new visit
   auto seek = [&](int at_rank) {
@@ -1859,10 +1867,10 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
       if (in) at = clist + (rank - cstart), rs = cord;
       if constexpr (SPLIT != 0)
         if (in) at0 = clist0 + (rank - cstart);
-      if constexpr (SPLIT == kFirstBounce)
-        if (in) rs = (int)pack_visit(cur_k, cord), next_h = cur_h;  // the iteration waits with the record, its depth-0 hash in a register of the lane
+      if constexpr (FIRST)
+        if (in) rs = (int)(FIXED ? pack_fixed(cur_k, crec0 + (rank - cstart), fbits) : pack_visit(cur_k, cord)), next_h = cur_h;  // the iteration waits with the record, its depth-0 hash in a register of the lane
       pending = pending && !in;
-      if (!ballot(pending) || ce >= ne || cord - cord0 >= kVisitsPerRefill) break;
+      if (!ballot(pending) || ce >= ne || (!FIXED && cord - cord0 >= kVisitsPerRefill)) break;
       cstart += ccnt;  // on to the next sub-list that holds anything: the first non-empty one behind ce in the window, else the window moves on
       ccnt = 0;
       int nxt = ce + 1;
@@ -1893,7 +1901,7 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
   int* slot_rs = reinterpret_cast<int*>(slots + kSlotVisit) + lane;  // SLOTS: the visit of the record waiting in the lane's slot
   auto fetch = [&](int at, [[maybe_unused]] int at0, int rs) {
     if constexpr (SLOTS && SPLIT == kSplitRecords) fetch_split_to_lds(in0, in1, at, at0, s_base), *slot_rs = rs;
-    else if constexpr (SLOTS) fetch_record_to_lds(in0, in1, in2, SPLIT == kFirstBounce ? at0 : at, s_base), *slot_rs = rs;  // (first bounce: the pixel's one record)
+    else if constexpr (SLOTS) fetch_record_to_lds(in0, in1, in2, FIRST ? at0 : at, s_base), *slot_rs = rs;  // (first bounce: the pixel's one record)
     else if constexpr (SPLIT == kSplitRecords) {  // the two words as they lie in memory: unpacked when the lane takes them
       const ptd::Word4 w0 = in.r[qbase + at], w1 = in.r[in.stride + qbase + at0];
       nx.o = mk(w0.x, w0.y, w0.z), nx.d = mk(w0.w, w1.x, w1.y), nx.c = mk(w1.z, w1.w, 0.f), nx_rs = rs;
@@ -1906,7 +1914,7 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
   bool valid = false, fresh = false, owes = false;  // owes: the lane's path died and its retirement record is not stored yet
   bool has_next = false;                            // a record is waiting in the lane's slot (on its way there)
   int streamed = 0, p_hi = 0;  // the current piece: records [.., streamed) handed out, the piece ends at p_hi; -1: no piece left for this wave
-  while (SPLIT != kFirstBounce) {  // (that form's loop, the same round rotated, follows this one)
+  while (!FIRST) {  // (that form's loop, the same round rotated, follows this one)
     // ── on to the wave's next piece, once the current one is handed out: its own, then whatever the queue's counter gives ──
     if (streamed >= p_hi && p_hi >= 0) {
       int nextp = -1;
@@ -2062,7 +2070,7 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
   // Memory ordering as above: a slot is read a round or more after its transfer was issued, the retirement store of a path that died
   // in this round's decide is issued after the slot reads, and what is outstanding at the wait is a whole round old.  Start
   // (nothing to search or decide, the refill fetches) and end (nothing valid, waiting or left after a refill) are ordinary rounds.
-  if constexpr (SPLIT == kFirstBounce) {
+  if constexpr (FIRST) {
     static_assert(MODE == kLdsTables, "the first-bounce form takes its records from the refill slots of the LDS-table form");
     while (true) {
       // ── search: box tests + appends for the lanes with a new ray; too few resolved lanes with candidates pending: a partial chunk ──
@@ -2103,7 +2111,8 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
         }
         const bool alive = ready && s.alive, dead = ready && !s.alive;
         if (dead) atomicAdd(&died[depth & 63], 1);
-        if (dead) rslot = atomicAdd(&fillc[rslot & (kVisitRing - 1)], 1);
+        if constexpr (!FIXED)
+          if (dead) rslot = atomicAdd(&fillc[rslot & (kVisitRing - 1)], 1);
         if (ready) {
           c = s.c;
           if (alive) {
@@ -2141,9 +2150,9 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
           owes = false;
         }
         if (take) {  // (bounce origin, hit normal, camera direction, pixel | material) and iteration | visit
-          const int pl = first_pixel(word, b.slot_shift), k = visit_k((uint32_t)vword);
+          const int pl = first_pixel(word, b.slot_shift), k = FIXED ? fixed_k((uint32_t)vword, fbits) : visit_k((uint32_t)vword);
           const f3 hn = mk(w0.w, w1.x, w1.y), cam_d = mk(w1.z, w1.w, cz);
-          slot = make_slot(b, k, pl), rslot = visit_number((uint32_t)vword);
+          slot = make_slot(b, k, pl), rslot = FIXED ? fixed_slot_of((uint32_t)vword, fbits, rt.seg_cap) : visit_number((uint32_t)vword);  // (FIXED: the record slot at once)
           phash = utilhash((uint32_t)global_pixel(b, pl));
           ShadeIO s;
           s.o = mk(0.f, 0.f, 0.f);
@@ -2158,7 +2167,8 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
           has_next = false;
         }
         // (rslot of a path in flight: its visit modulo the packed width, as it waited in the slot)
-        const bool lapping = ballot(valid && visit_gap(cord, rslot) >= kVisitLap) != 0ull;
+        bool lapping = false;  // (FIXED: no ring to lap)
+        if constexpr (!FIXED) lapping = ballot(valid && visit_gap(cord, rslot) >= kVisitLap) != 0ull;
         const bool empty = !has_next && !lapping;
         const unsigned long long em = ballot(empty);
         const int rank = rank_in(em);
@@ -2235,7 +2245,7 @@ const KernelApi kApi = {
 #endif
     launch_generate, launch_primary, launch_intersect, launch_shade, launch_collect, launch_count_stats,
     launch_preview, launch_save_u8, launch_shade_stage, lds_table_limit, resident_blocks_per_cu, launch_ieee_check, launch_paths,
-    launch_collect_conv, launch_features, kFast ? 1 : 0, launch_intersect_grid};
+    launch_collect_conv, launch_features, kFast ? 1 : 0, launch_intersect_grid, launch_collect_stream};
 
 }  // namespace
 }  // namespace PT_NS

@@ -48,12 +48,13 @@ void with_primary(const SceneTables& sc, bool share, int split, F&& f) {
   }
 }
 
-// split: BatchInfo::split_records (0, kSplitRecords; kLdsTables also kFirstBounce) — the same LDS map
+// split: BatchInfo::split_records (0, kSplitRecords; kLdsTables also kFirstBounce and, with BatchInfo::fixed_slots, kFixedSlots) — the same LDS map
 template <typename F>
 void with_paths(const SceneTables& sc, Search form, int split, F&& f) {  // (SceneTables::scan_nodes_lds resolved by the caller)
   switch (form) {
     case kLdsTables:
       if (split == kFirstBounce) return f(k_paths<kLdsTables, kFirstBounce>, paths_lds<kLdsTables, kFast>(sc).total);
+      if (split == kFixedSlots) return f(k_paths<kLdsTables, kFixedSlots>, paths_lds<kLdsTables, kFast>(sc).total);
       return split ? f(k_paths<kLdsTables, kSplitRecords>, paths_lds<kLdsTables, kFast>(sc).total) : f(k_paths<kLdsTables>, paths_lds<kLdsTables, kFast>(sc).total);
     case kTopScan: return split ? f(k_paths<kTopScan, kSplitRecords>, paths_lds<kTopScan, kFast>(sc).total) : f(k_paths<kTopScan>, paths_lds<kTopScan, kFast>(sc).total);
     case kGrid: return split ? f(k_paths<kGrid, kSplitRecords>, paths_lds<kGrid, kFast>(sc).total) : f(k_paths<kGrid>, paths_lds<kGrid, kFast>(sc).total);
@@ -126,13 +127,13 @@ int resident_blocks_per_cu(KernelId id, const SceneTables& sc) {
     case kIntersectLegacy: with_intersect(sc, true, false, query); break;
     case kPrimary: with_primary(sc, false, 0, query_share); break;
     // (a context's batches run any record form of these two, BatchInfo::split_records: same LDS; the smallest count serves all — where a
-    // form does not exist for the tables' search form, kFirstBounce, the selectors give the split form again)
+    // form does not exist for the tables' search form, kFirstBounce and kFixedSlots, the selectors give the split form again)
     case kPrimaryShared:
       for (int form : {0, kSplitRecords, kFirstBounce}) with_primary(sc, true, form, query_share), m = form ? min(m, n) : n;
       n = m;
       break;
     case kPaths:
-      for (int form : {0, kSplitRecords, kFirstBounce}) with_paths(resolve_scan_nodes(sc), search_form(sc), form, query_share), m = form ? min(m, n) : n;
+      for (int form : {0, kSplitRecords, kFirstBounce, kFixedSlots}) with_paths(resolve_scan_nodes(sc), search_form(sc), form, query_share), m = form ? min(m, n) : n;
       n = m;
       break;
     case kShade: query(k_shade, shade_lds<true>(sc).total); break;
@@ -173,7 +174,7 @@ void launch_features(hipStream_t s, int grid, const SceneTables& sc, const ptd::
 
 void launch_paths(hipStream_t s, int grid, const SceneTables& sc_in, const BatchInfo& b, const ptd::Queues& qs, int32_t* cnt, ptd::PathBuf in, ptd::RetireBuf ret) {
   const SceneTables sc = resolve_scan_nodes(sc_in);
-  with_paths(sc, search_form(sc), b.split_records, [&](auto kernel, int lds) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, sc, b, qs, cnt, in, ret); });
+  with_paths(sc, search_form(sc), b.split_records == kFirstBounce && b.fixed_slots ? kFixedSlots : b.split_records, [&](auto kernel, int lds) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, sc, b, qs, cnt, in, ret); });
 }
 void launch_shade(hipStream_t s, int grid, const SceneTables& sc, const BatchInfo& b, int depth, const ptd::Queues& qs,
                   const int32_t* cnt_in, int32_t* cnt_out, ptd::PathBuf in, ptd::HitBuf hits, ptd::PathBuf out,
@@ -190,6 +191,12 @@ void launch_collect(hipStream_t s, const BatchInfo& b, const ptd::Queues& qs, pt
   // 96 KB of dynamic LDS (and the residues' retiree counts): above the 64 KB a kernel gets without asking (per device: set on every launch, it is cheap)
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_collect), hipFuncAttributeMaxDynamicSharedMemorySize, collect_lds_bytes(ret.wq0));
   hipLaunchKernelGGL(k_collect, dim3(qs.Q), dim3(kCollectThreads), collect_lds_bytes(ret.wq0), s, b, qs, ret, image_rgb);
+}
+// The stream gather and the counter rows in one launch: ceil(seg_cap / kBlock) blocks per queue, then k_count_stats' depth_count + 2
+void launch_collect_stream(hipStream_t s, const BatchInfo& b, const ptd::Queues& qs, ptd::RetireBuf ret, float* image_rgb, int32_t* cnt, int depth_count,
+                           unsigned long long* stats) {
+  const int per_queue = (ret.seg_cap + kBlock - 1) / kBlock;
+  hipLaunchKernelGGL(k_collect_stream, dim3(qs.Q * per_queue + depth_count + 2), dim3(kBlock), 0, s, b, qs, ret, image_rgb, per_queue, cnt, depth_count, stats);
 }
 void launch_collect_conv(hipStream_t s, const BatchInfo& b, const ptd::Queues& qs, ptd::RetireBuf ret, float* image_rgb, const ConvInfo& cv, double* sse) {
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_collect_conv), hipFuncAttributeMaxDynamicSharedMemorySize, collect_lds_bytes(ret.wq0));

@@ -308,11 +308,9 @@ PT_DEV void deal_waves(const ptd::Queues& qs) {
   }
 }
 
-__global__ void k_count_stats(ptd::Queues qs, int32_t* __restrict__ cnt, int depth_count,
-                              unsigned long long* __restrict__ stats) {
-  // one block per counter row (depth 0 .. depth_count): add the row's fill levels to the statistics and leave the
-  // row zeroed for the next batch (saves a memset launch per batch)
-  const int d = blockIdx.x;
+// one block per counter row (d = 0 .. depth_count): add the row's fill levels to the statistics and leave the
+// row zeroed for the next batch (saves a memset launch per batch); block depth_count + 1 deals k_paths' waves
+PT_DEV void count_stats_row(const ptd::Queues& qs, int32_t* __restrict__ cnt, int depth_count, unsigned long long* __restrict__ stats, int d) {
   if (d == depth_count + 1) {
     deal_waves(qs);
     return;
@@ -334,6 +332,61 @@ __global__ void k_count_stats(ptd::Queues qs, int32_t* __restrict__ cnt, int dep
     for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += part[w];
     stats[d] += t;
   }
+}
+__global__ void k_count_stats(ptd::Queues qs, int32_t* __restrict__ cnt, int depth_count,
+                              unsigned long long* __restrict__ stats) {
+  count_stats_row(qs, cnt, depth_count, stats, blockIdx.x);
+}
+
+// finalGather of a batch with fixed record slots (BatchInfo::fixed_slots, pt_sched.h): slot s of region (q, k) holds the same pixel for
+// every k, so the gather is a plain stream — one thread per slot of the queue's region 0, `per_queue` blocks of kBlock per queue, no
+// tile, no barrier.  Once per thread: the slot's sub-region and position there (sub_slot), the sub-region's depth-0 retiree count
+// (row 0 of sub[]: the rows of such a batch are equal), the unused slots of the tile's partial last chunk (region_gap), and the pixel
+// from the last word of the slot's record of iteration 0.  A survivor slot adds its K records to the pixel's accumulator strictly in
+// iteration order — image[p] = (((image[p] + c_0) + c_1) + ...), k_collect's order — with kStreamGroup coalesced 16-byte loads in flight;
+// a depth-0 retiree slot holds ONE record per batch (retire_once) and adds it K times, as the tile gather does from the value its tile
+// keeps.  The blocks behind the gather's are k_count_stats' (count_stats_row): they touch the counter rows, the deal table and the
+// statistics, the gather the records, sub[], ret.cnt and the image — nothing in common, so the batch saves a launch.
+constexpr int kStreamGroup = 8;
+__global__ __launch_bounds__(kBlock) void k_collect_stream(BatchInfo b, ptd::Queues qs, ptd::RetireBuf ret, float* __restrict__ image, int per_queue,
+                                                           int32_t* __restrict__ cnt, int depth_count, unsigned long long* __restrict__ stats) {
+  const int gather_blocks = qs.Q * per_queue;
+  if ((int)blockIdx.x >= gather_blocks) {
+    count_stats_row(qs, cnt, depth_count, stats, (int)blockIdx.x - gather_blocks);
+    return;
+  }
+  const int q = (int)blockIdx.x / per_queue, blk = (int)blockIdx.x - q * per_queue;
+  const int s = blk * kBlock + (int)threadIdx.x;
+  // the records are consumed: zero counters for the next batch
+  if (blk == 0)
+    for (int i = threadIdx.x; i < ret.kmax; i += kBlock) ret.cnt[(int64_t)q * ret.kmax + i] = 0ull;
+  const QueueShare sh = queue_share(b, qs, q);
+  const Gap gap = region_gap(sh, ret.wq0);
+  if (s >= sh.my_nq * 64 || (s >= gap.g0 && s < gap.g1)) return;
+  const SubSlot ss = sub_slot(sh.my_nq / ret.wq0, sh.my_nq % ret.wq0, s);
+  const int retirees = (int)(ret.sub[(int64_t)q * ret.kmax * ret.wq0 + ss.rho] >> 32);
+  const ptd::Word4* rec = ret.rec + (int64_t)q * ret.kmax * ret.seg_cap + s;  // the slot in region (q, 0); region (q, k): + k * seg_cap
+  const ptd::Word4 r0 = rec[0];
+  const int pl = __float_as_int(r0.w);
+  if (pl < 0 || pl >= b.N) return;  // (no record names a pixel outside the tile; a slot nobody wrote must not send a store there)
+  float* px = image + 3 * (int64_t)pl;
+  float a0 = px[0], a1 = px[1], a2 = px[2];
+  if (retiree_slot(ss, retirees)) {
+    for (int k = 0; k < b.K; ++k) a0 += r0.x, a1 += r0.y, a2 += r0.z;
+  } else {
+    a0 += r0.x, a1 += r0.y, a2 += r0.z;
+    for (int k0 = 1; k0 < b.K; k0 += kStreamGroup) {  // (K is uniform: the loads of a group are issued back to back, the last group's clamped)
+      ptd::Word4 v[kStreamGroup];
+#pragma unroll
+      for (int u = 0; u < kStreamGroup; ++u) v[u] = rec[(int64_t)min(k0 + u, b.K - 1) * ret.seg_cap];
+#pragma unroll
+      for (int u = 0; u < kStreamGroup; ++u) {
+        const bool have = k0 + u < b.K;
+        a0 = have ? a0 + v[u].x : a0, a1 = have ? a1 + v[u].y : a1, a2 = have ? a2 + v[u].z : a2;
+      }
+    }
+  }
+  px[0] = a0, px[1] = a1, px[2] = a2;
 }
 
 __global__ __launch_bounds__(kBlock) void k_preview(int n, int iterations, const float* __restrict__ image,

@@ -282,6 +282,38 @@ PT_SCHED int record_form(const BatchInfo& b, int debug_flags, int search_form, i
   return first_bounces(b, debug_flags, search_form, num_mats) ? kFirstBounce : splits_records(b, debug_flags) ? kSplitRecords : 0;
 }
 
+// ── retirement records of a first-bounce batch: fixed slots, gathered as a stream ─────────────────────────────────────────
+// In a first-bounce batch record i of sub-list (q, k, rho) is the same pixel for every k (above), and the lane of k_paths that takes
+// it knows i.  Such a batch (BatchInfo::fixed_slots) stores the path's retirement record at slot retirees(rho) + i of sub-region
+// (q, k, rho) — the range the wave's visit of the sub-list fills anyway, in list order instead of in order of retirement — so slot s of
+// region (q, k) holds the same pixel for every k, and the gather (k_collect_stream, pt_output.inc) needs no tile: one thread per slot
+// adds its K records in iteration order.  PtOptions.debug_flags kRecordsByVisit: records in order of retirement and the tile gather;
+// kTileGather: fixed slots under the tile gather, which places a record by its pixel word wherever it lies.
+constexpr int kRecordsByVisit = 16384, kTileGather = 32768;
+constexpr int kFixedSlots = 3;  // k_paths' SPLIT argument for such a batch (BatchInfo::split_records stays kFirstBounce: k_primary does not care)
+// The record slot, inside its queue's regions, of the path at list position i of sub-list (k, rho).  (quo, rem: sub_offset)
+PT_SCHED int fixed_slot(int k, int seg_cap, int quo, int rem, int rho, int retirees, int i) { return k * seg_cap + sub_offset(quo, rem, rho) * 64 + retirees + i; }
+// The word that waits with a record in a lane's refill slot, in place of pack_visit: the iteration k above the slot's offset in its
+// region, slot - k * seg_cap < seg_cap, in fixed_bits(seg_cap) bits.  The take shifts k out and forms the slot with one multiply-add
+// (the whole slot alone would cost the lane a division by seg_cap for k).  (seg_cap >= 64: a multiple of 64)
+PT_SCHED int fixed_bits(int seg_cap) { return 32 - __builtin_clz((unsigned)(seg_cap - 1)); }
+PT_SCHED uint32_t pack_fixed(int k, int in_region, int bits) { return ((uint32_t)k << bits) | (uint32_t)in_region; }
+PT_SCHED int fixed_k(uint32_t word, int bits) { return (int)(word >> bits); }
+PT_SCHED int fixed_slot_of(uint32_t word, int bits, int seg_cap) { return (int)(word >> bits) * seg_cap + (int)(word & ((1u << bits) - 1u)); }
+PT_SCHED bool fixed_word_fits(int K, int seg_cap) { return K <= (1 << (31 - fixed_bits(seg_cap))); }
+PT_SCHED bool fixed_slots(int primary_share, bool aa_jitter, bool flat, int trace_depth, int debug_flags, int search_form, int num_mats, int slot_shift,
+                          int K, int seg_cap) {
+  return first_bounces(primary_share, aa_jitter, flat, trace_depth, debug_flags, search_form, num_mats, slot_shift, K) && fixed_word_fits(K, seg_cap) &&
+         !(debug_flags & kRecordsByVisit);
+}
+PT_SCHED bool fixed_slots(const BatchInfo& b, int debug_flags, int search_form, int num_mats, int seg_cap) {
+  return fixed_slots(b.primary_share, b.aa_jitter != 0, b.flat != 0, b.trace_depth, debug_flags, search_form, num_mats, b.slot_shift, b.K, seg_cap);
+}
+// PtStats.gather_form of a batch: 0 the tile gather over records in order of retirement, 1 the tile gather over fixed slots (kTileGather,
+// and every batch with the convergence metric, whose partial sums keep their partition), 2 the stream.
+constexpr int kGatherTile = 0, kGatherTileFixed = 1, kGatherStream = 2;
+PT_SCHED int gather_form(bool fixed, int debug_flags, bool convergence) { return !fixed ? kGatherTile : (debug_flags & kTileGather) || convergence ? kGatherTileFixed : kGatherStream; }
+
 // ── k_paths: falling pieces ───────────────────────────────────────────────────────────────────────────────────────────────
 // BatchInfo::paths_pieces: pieces per wave | fewest paths in a piece << 16.
 PT_SCHED int pack_paths_pieces(int count, int min_piece) { return count | min_piece << 16; }

@@ -114,7 +114,11 @@ typedef struct PtOptions {
                                words: ONE record per surviving pixel and batch — bounce origin, hit normal, camera direction,
                                pixel and material — the primary kernel traces every chunk once per batch, and the bounce kernel
                                decides depth 0 and samples the first bounce of every iteration's path when a lane takes it;
-                               primary_pieces and primary_share are ignored by that form; PtStats.record_form tells), 2048
+                               primary_pieces and primary_share are ignored by that form; PtStats.record_form tells), 16384
+                               retirement records in order of retirement, gathered through a tile (default in a batch of the
+                               8192 form whose words fit: a path's record goes to the slot its position in its list gives, so a
+                               slot holds the same pixel in every iteration of the batch and the gather streams the records,
+                               one thread per slot; PtStats.gather_form tells), 32768 the tile gather over such fixed slots, 2048
                                keep the reference's leaf boxes for spheres (default for large scenes: tightened to the
                                ellipsoid's box, PtStats.tight_leaves; pt_stage_intersect on such a scene then expects ray
                                origins inside the scene bounds or at the camera).  pt_init fails on any other bit. */
@@ -197,6 +201,9 @@ typedef struct PtStats {
   int32_t record_form;                /* how the last batch handed depth 0 to the fused bounce kernel: 0 whole 40-byte records per
                                          sample, 1 split records (debug_flags 4096 turns them off), 2 one record per surviving pixel
                                          and batch, the first bounce sampled in the bounce kernel (debug_flags 8192 turns it off) */
+  int32_t gather_form;                /* how the last batch was gathered: 0 through a tile, from records in order of retirement
+                                         (debug_flags 16384 asks for it), 1 through a tile, from fixed record slots (debug_flags
+                                         32768, and every batch that computes the convergence metric), 2 as a stream over fixed slots */
 } PtStats;
 
 /* ---- scene loading (host).  Replaces `new Scene(file)` (src/main.cpp:45,

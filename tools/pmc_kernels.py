@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel counter table from `rocprofv3 --pmc` runs of bench.py, one output directory per run (counters only, no tracing):
 for every directory DIR/NAME* with a *counter_collection.csv, the mean / min / max over the last three dispatches of k_primary,
-k_paths, k_count_stats and k_collect (a dispatch's value = the sum over the counter's instances), and the sum over the four
+k_paths, k_count_stats, k_collect and k_collect_stream (a dispatch's value = the sum over the counter's instances), and the sum over these
 kernels per batch.  FETCH_SIZE / WRITE_SIZE are printed on the profiler's scale (KiB; the project's byte convention is
 2 x FETCH_SIZE + WRITE_SIZE, tools/pmc_traffic.py).  The tables of profiles/retire_once.log.
 usage: tools/pmc_kernels.py DIR [NAME-PREFIX]"""
@@ -11,7 +11,7 @@ import glob
 import os
 import sys
 
-KERNELS = ("k_primary", "k_paths", "k_count_stats", "k_collect")
+KERNELS = ("k_primary", "k_paths", "k_count_stats", "k_collect", "k_collect_stream")
 
 
 def table(path):
@@ -27,7 +27,7 @@ def table(path):
         print(f"  {k:14s} {c:14s} dispatches {len(v):3d}  mean of the last {len(vals)} {mean:16.1f} min {min(vals):16.1f} max {max(vals):16.1f}")
         total[c] += mean
     for c, t in total.items():
-        print(f"  all four       {c:14s} per batch {t:16.1f}")
+        print(f"  all kernels    {c:14s} per batch {t:16.1f}")
 
 
 def main():
