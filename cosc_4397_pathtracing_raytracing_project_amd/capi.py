@@ -240,6 +240,17 @@ def lib() -> C.CDLL:
         L.pt_stage_adaptive_select.argtypes = [C.c_int, C.c_int, _fp, _ip, C.c_int, _ip]
         L.pt_adaptive_merge_host.argtypes = [C.c_int, _fp, _fp, _ip, _ip, C.c_int, _fp, C.c_int, _dp]
         L.pt_stage_render_list.argtypes = [_ip, C.c_int, C.c_int, C.c_int, _fp]
+    if hasattr(L, "pt_adaptive_round_threshold"):  # absent from older A/B builds of the library (tools/build_rev.sh)
+        _i64p = C.POINTER(C.c_int64)
+        _threshold = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _ip, _i64p, _ip]
+        _select_thr = [C.c_int, C.c_int, _fp, _ip, C.c_float, C.c_int, _ip, _ip, _ip]
+        L.pt_adaptive_round_threshold.argtypes = [C.c_int, C.c_int, C.c_float, C.c_float, _ip, _ip]
+        L.pt_render_threshold.argtypes = _threshold
+        L.pt_ctx_adaptive_round_threshold.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, _ip, _ip]
+        L.pt_ctx_render_threshold.argtypes = [C.c_void_p] + _threshold
+        L.pt_adaptive_select_threshold_host.argtypes = _select_thr
+        L.pt_stage_adaptive_select_threshold.argtypes = _select_thr
+        L.pt_stage_render_list_capacity.argtypes = [_ip, C.c_int, C.c_int, C.c_int, C.c_int, _fp]
     if hasattr(L, "pt_denoise_adaptive"):  # absent from older A/B builds of the library (tools/build_rev.sh)
         _dno = C.POINTER(PtDenoiseOptions)
         _dn_adaptive = [C.c_int, C.c_int, _fp, _fp, _fp, _ip, _dno]
@@ -557,6 +568,35 @@ def stage_render_list(pixel_list: np.ndarray, iter_first: int, iter_count: int) 
     return out
 
 
+def stage_render_list_capacity(pixel_list: np.ndarray, capacity: int, iter_first: int, iter_count: int) -> np.ndarray:
+    """stage_render_list on a worker planned for `capacity` >= len(pixel_list) pixels (pt_stage_render_list_capacity): the worker is
+    kept across calls while the capacity is equal."""
+    lst = np.ascontiguousarray(pixel_list, np.int32).reshape(-1)
+    out = np.empty((lst.size, 3), np.float32)
+    _check(lib().pt_stage_render_list_capacity(_i(lst), lst.size, int(capacity), int(iter_first), int(iter_count), _f(out)))
+    return out
+
+
+def _select_threshold(call, noise_planes, counts, w: int, rows: int, threshold: float, cap: int):
+    z, c, out = _select_arrays(noise_planes, counts, w, rows, cap)
+    above, m = C.c_int32(-1), C.c_int32(-1)
+    _check(call(int(w), int(rows), _f(z), _i(c), C.c_float(threshold), int(cap), _i(out), C.byref(above), C.byref(m)))
+    if not 0 <= m.value <= int(cap) or (out[m.value:] != -1).any():
+        raise PtError(f"adaptive_select_threshold: a list of {m.value} (cap {cap}) with entries written behind it")
+    return out[:m.value].copy(), int(above.value), int(m.value)
+
+
+def adaptive_select_threshold_host(noise_planes: np.ndarray, counts: np.ndarray, w: int, rows: int, threshold: float, cap: int):
+    """The selection by threshold on the host (pt_adaptive_select_threshold_host; no GPU): adaptive_select_host's arrays -> (the list
+    int32 [m] in ascending tile index, above = pixels whose key exceeds threshold^2, m = min(above, cap))."""
+    return _select_threshold(lib().pt_adaptive_select_threshold_host, noise_planes, counts, w, rows, threshold, cap)
+
+
+def stage_adaptive_select_threshold(noise_planes: np.ndarray, counts: np.ndarray, w: int, rows: int, threshold: float, cap: int):
+    """adaptive_select_threshold_host's arguments through the selection's kernels (pt_stage_adaptive_select_threshold; needs a Renderer)."""
+    return _select_threshold(lib().pt_stage_adaptive_select_threshold, noise_planes, counts, w, rows, threshold, cap)
+
+
 def _noise(call, *handle) -> dict:
     sse, groups, iters = C.c_double(-1.0), C.c_int32(0), C.c_int32(0)
     _check(call(*handle, C.byref(sse), C.byref(groups), C.byref(iters)))
@@ -688,6 +728,23 @@ class Renderer:
         _check(lib().pt_render_adaptive(int(iter_first), int(max_iters), int(group_iters), C.c_float(fraction), C.c_float(target_db), C.byref(done),
                                         C.byref(samples), C.byref(psnr)))
         return int(done.value), int(samples.value), float(psnr.value)
+
+    def adaptive_round_threshold(self, iter_first: int, group_iters: int, threshold: float, max_fraction: float = 1.0):
+        """One round over the pixels whose estimated standard error exceeds `threshold`, the noisiest max_fraction of the tile at the
+        most (pt_adaptive_round_threshold; synchronises once): (pixels above, pixels rendered)."""
+        above, selected = C.c_int32(-1), C.c_int32(-1)
+        _check(lib().pt_adaptive_round_threshold(int(iter_first), int(group_iters), C.c_float(threshold), C.c_float(max_fraction), C.byref(above),
+                                                 C.byref(selected)))
+        return int(above.value), int(selected.value)
+
+    def render_threshold(self, iter_first: int, max_iters: int, threshold: float, max_fraction: float = 0.25, group_iters: int = 0,
+                         min_pixels: int = 0):
+        """Uniform groups until two are folded, then threshold rounds until at most min_pixels pixels are above or max_iters iteration
+        numbers are used (pt_render_threshold): (iteration numbers used, pixel-samples rendered, pixels above at the last count or -1)."""
+        done, samples, above = C.c_int32(0), C.c_int64(0), C.c_int32(-1)
+        _check(lib().pt_render_threshold(int(iter_first), int(max_iters), int(group_iters), C.c_float(threshold), C.c_float(max_fraction), int(min_pixels),
+                                         C.byref(done), C.byref(samples), C.byref(above)))
+        return int(done.value), int(samples.value), int(above.value)
 
     def readback_adaptive(self) -> np.ndarray:
         """The per-pixel counts int32 [n, 2]: iterations T_p, groups M_p."""

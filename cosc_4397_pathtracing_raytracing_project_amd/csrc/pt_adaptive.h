@@ -96,24 +96,68 @@ inline int list_length(double fraction, int64_t npix) {
   return (int)std::min<double>((double)npix, std::max(1.0, want));
 }
 
-// The whole selection on the host: the m pixels with the largest key, equal keys by the smaller tile index, in ascending tile index.
-inline void select_host(int W, int R, const float* noise_planes, const int32_t* counts, int m, int32_t* list) {
-  const size_t n = (size_t)W * R;
+// Selection by threshold (pt_amd.h pt_adaptive_round_threshold): the key bits a pixel must EXCEED, thr = threshold * threshold in
+// one float32 multiply (threshold finite and >= 0, so thr is never a NaN and its bits order like the float).
+PT_HD uint32_t threshold_bits(float threshold) {
+#pragma clang fp contract(off)
+  const float thr = threshold * threshold;
+  return __builtin_bit_cast(uint32_t, thr);
+}
+PT_HD bool above_threshold(uint32_t key, uint32_t thr) { return key > thr; }  // equal is not above; a NaN key (all bits set) is
+// The cut (tau, r) of the top-`cap` selection — tau the cap-th largest key, r the pixels equal to it to take — under the threshold:
+// while tau lies above thr the top `cap` are all above and the cut stands; otherwise every pixel above thr is taken and no tie.
+struct Cut {
+  uint32_t tau, r;
+};
+PT_HD Cut threshold_cut(uint32_t tau, uint32_t r, uint32_t thr) { return above_threshold(tau, thr) ? Cut{tau, r} : Cut{thr, 0u}; }
+PT_HD uint32_t threshold_length(uint32_t above, uint32_t cap) { return above < cap ? above : cap; }  // m
+
+inline std::vector<uint32_t> keys_host(int W, int R, const float* noise_planes, const int32_t* counts) {
   const ptnz::F4* plane0 = reinterpret_cast<const ptnz::F4*>(noise_planes);
   const Cnt* cnt = reinterpret_cast<const Cnt*>(counts);
-  std::vector<uint32_t> key(n);
+  std::vector<uint32_t> key((size_t)W * R);
   for (int y = 0; y < R; ++y)
     for (int x = 0; x < W; ++x) key[(size_t)y * W + x] = key_pixel(x, y, W, R, plane0, cnt);
+  return key;
+}
+// The cut of the top-m selection: the m-th largest key and the pixels equal to it that belong to the m.
+inline Cut cut_host(const std::vector<uint32_t>& key, int m) {
   std::vector<uint32_t> sorted(key);
   std::nth_element(sorted.begin(), sorted.begin() + (m - 1), sorted.end(), [](uint32_t a, uint32_t b) { return a > b; });
-  const uint32_t tau = sorted[(size_t)m - 1];  // the m-th largest key
+  const uint32_t tau = sorted[(size_t)m - 1];
   size_t above = 0;
-  for (size_t p = 0; p < n; ++p) above += key[p] > tau ? 1 : 0;
-  size_t ties = (size_t)m - above, out = 0;  // pixels equal to tau to take, the first in tile order
-  for (size_t p = 0; p < n; ++p) {
-    if (key[p] > tau) list[out++] = (int32_t)p;
-    else if (key[p] == tau && ties > 0) list[out++] = (int32_t)p, --ties;
+  for (uint32_t k : key) above += k > tau ? 1 : 0;
+  return Cut{tau, (uint32_t)((size_t)m - above)};
+}
+// The pixels above the cut and the first r equal to it, in tile order; returns how many.
+inline size_t scatter_host(const std::vector<uint32_t>& key, Cut c, int32_t* list) {
+  size_t ties = c.r, out = 0;
+  for (size_t p = 0; p < key.size(); ++p) {
+    if (key[p] > c.tau) list[out++] = (int32_t)p;
+    else if (key[p] == c.tau && ties > 0) list[out++] = (int32_t)p, --ties;
   }
+  return out;
+}
+
+// The whole selection on the host: the m pixels with the largest key, equal keys by the smaller tile index, in ascending tile index.
+inline void select_host(int W, int R, const float* noise_planes, const int32_t* counts, int m, int32_t* list) {
+  const std::vector<uint32_t> key = keys_host(W, R, noise_planes, counts);
+  scatter_host(key, cut_host(key, m), list);
+}
+
+// Selection by threshold on the host: *above = pixels whose key exceeds thr, *m = min(above, cap); list receives the m of them with
+// the largest keys (ties by the smaller tile index) in ascending tile index.  The steps are the device's: cut for rank cap, clamp, scatter.
+inline void select_threshold_host(int W, int R, const float* noise_planes, const int32_t* counts, float threshold, int cap, int32_t* list,
+                                  int* above, int* m) {
+  const std::vector<uint32_t> key = keys_host(W, R, noise_planes, counts);
+  const uint32_t thr = threshold_bits(threshold);
+  const Cut top = cut_host(key, cap);
+  uint32_t n_above = 0;
+  for (uint32_t k : key) n_above += above_threshold(k, thr) ? 1u : 0u;
+  const size_t wrote = scatter_host(key, threshold_cut(top.tau, top.r, thr), list);
+  *above = (int)n_above;
+  *m = (int)threshold_length(n_above, (uint32_t)cap);
+  (void)wrote;  // == *m
 }
 
 // A merge on the host; the estimates of ALL tile pixels are added in pixel order.

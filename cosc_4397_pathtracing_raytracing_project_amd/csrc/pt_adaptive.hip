@@ -2,7 +2,8 @@
 //
 // A translation unit of its own, compiled ONCE with -ffp-contract=off like pt_noise.hip: key, merge and resolve are specified as
 // separate IEEE float32 operations (pt_adaptive.h), the selection works on the keys' bit patterns.  All of it is streaming and
-// memory-bound; nothing synchronises with the host, and the only atomics are integer adds on histogram bins.
+// memory-bound; nothing synchronises with the host, and the only atomics are integer adds on histogram bins
+// and on the threshold selection's count.
 //
 //   k_adaptive_key      one thread per tile pixel: 9 taps of plane 0's w and of the counts, 4 B out.
 //   k_adaptive_hist     radix select, pass P = 0, 1, 2 over bits 31..21, 20..10, 9..0 of the key: a workgroup of 256 threads owns 1024
@@ -12,6 +13,8 @@
 //                       the m-th largest key; leaves the longer prefix and the rank inside the bin in device memory.  After pass 2
 //                       the prefix is the threshold key tau and the rank is r, the number of pixels equal to tau to take.
 //   k_adaptive_count    per 1024-pixel block: pixels with key > tau, pixels with key == tau.
+//   k_adaptive_above    selection by threshold: per 1024-pixel block, pixels with key > thr, added to one word with an integer atomic;
+//   k_adaptive_threshold  one thread: (tau, r) := the cut under the threshold (pt_adaptive.h threshold_cut), m = min(above, cap).
 //   k_adaptive_scan     one workgroup: the exclusive scan of both counts over the blocks.
 //   k_adaptive_scatter  a pixel with a > pixels above tau and e pixels equal to tau in front of it (tile order) is taken when its key
 //                       is above tau, or equal with e < r, and lands at list[a + min(e, r)]: ascending tile index, ties to the smaller
@@ -38,10 +41,18 @@ static_assert(kBins == kBlock * 8, "k_adaptive_pick: 8 bins per thread");
 
 // The select's words in device memory
 struct Sel {
-  uint32_t prefix;  // the bits of tau found so far (the passes' bins, in place)
-  uint32_t rank;    // the key looked for is the rank-th largest (1-based) among the keys that share the prefix
+  // While the passes run: the bits of tau found so far (the passes' bins, in place), and the rank (1-based) of the key looked for among
+  // the keys that share the prefix.  Pass 2 leaves both words zero, and the selection by threshold keeps its two counts there (so the
+  // workspace is as large as it was): pixels whose key exceeds thr, and min(above, cap), the list's length.
+  union {
+    uint32_t prefix, above;
+  };
+  union {
+    uint32_t rank, m;
+  };
   uint32_t tau, r;  // after pass 2: prefix and rank under their final names
 };
+static_assert(sizeof(Sel) == 16, "pt_adaptive_select_bytes, pt_adaptive_select_result");
 
 __device__ __forceinline__ int pass_shift(int pass) { return pass == 0 ? 21 : pass == 1 ? 10 : 0; }
 __device__ __forceinline__ uint32_t pass_bin(uint32_t key, int pass) { return pass == 0 ? key >> 21 : pass == 1 ? (key >> 10) & 0x7ffu : key & 0x3ffu; }
@@ -123,7 +134,7 @@ __global__ __launch_bounds__(kBlock) void k_adaptive_pick(const uint32_t* __rest
     for (int i = 0; i < 8; ++i) {
       if (rank > above && rank <= above + c[i]) {
         const uint32_t p = prefix | (uint32_t)(top - i) << pass_shift(pass);
-        sel->prefix = p, sel->rank = rank - above;
+        sel->prefix = pass == 2 ? 0u : p, sel->rank = pass == 2 ? 0u : rank - above;  // (after pass 2: Sel::above and Sel::m, from zero)
         sel->tau = p, sel->r = rank - above;
       }
       above += c[i];
@@ -157,6 +168,33 @@ __global__ __launch_bounds__(kBlock) void k_adaptive_count(size_t npix, const ui
     for (int w = 0; w < kWaves; ++w) s.gt += wave_gt[w], s.eq += wave_eq[w];
     per_block[blockIdx.x] = s;
   }
+}
+
+// Selection by threshold, after the picks for rank `cap`: sel->above += the block's pixels whose key exceeds thr (an integer atomic: the
+// sum is the same in any order).
+__global__ __launch_bounds__(kBlock) void k_adaptive_above(size_t npix, const uint32_t* __restrict__ key, uint32_t thr, Sel* __restrict__ sel) {
+  __shared__ uint32_t wave_n[kWaves];
+  const size_t base = (size_t)blockIdx.x * kPerBlock + threadIdx.x;
+  uint32_t n = 0u;
+#pragma unroll
+  for (int j = 0; j < kPerThread; ++j) {
+    const size_t p = base + (size_t)j * kBlock;
+    if (p < npix) n += ptad::above_threshold(key[p], thr) ? 1u : 0u;
+  }
+  for (int off = 32; off > 0; off >>= 1) n += __shfl_down(n, off, 64);
+  if ((threadIdx.x & 63) == 0) wave_n[threadIdx.x >> 6] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t s = 0u;
+    for (int w = 0; w < kWaves; ++w) s += wave_n[w];
+    if (s) atomicAdd(&sel->above, s);
+  }
+}
+// ... and one thread: the cut under the threshold (pt_adaptive.h threshold_cut) for count, scan and scatter, and the list's length.
+__global__ void k_adaptive_threshold(Sel* __restrict__ sel, uint32_t thr, uint32_t cap) {
+  const ptad::Cut c = ptad::threshold_cut(sel->tau, sel->r, thr);
+  sel->tau = c.tau, sel->r = c.r;
+  sel->m = ptad::threshold_length(sel->above, cap);
 }
 
 // per_block[b] := the counts of the blocks in front of b.  One workgroup, kBlock blocks per pass, the running sums carried along.
@@ -275,25 +313,44 @@ int pt_adaptive_init_counts_launch(hipStream_t stream, int pixels, void* counts_
   return launched("pt_adaptive_round");
 }
 
-int pt_adaptive_select_launch(hipStream_t stream, int w, int rows, const float* noise_dev, const void* counts_dev, int m, void* workspace_dev,
-                              int32_t* list_dev) {
+// The selection's launches; thr == nullptr: the top m, else the pixels above *thr, the `m` with the largest keys at the most.
+static int select_launches(const char* who, hipStream_t stream, int w, int rows, const float* noise_dev, const void* counts_dev, int m, const uint32_t* thr,
+                           void* workspace_dev, int32_t* list_dev) {
   const size_t npix = (size_t)w * rows;
   if (w <= 0 || rows <= 0 || npix > ((size_t)1 << 30) || m < 1 || (size_t)m > npix || !noise_dev || !counts_dev || !workspace_dev || !list_dev)
-    return pt_fail("pt_adaptive_select: bad argument");
+    return pt_fail("%s: bad argument", who);
   const Workspace ws = carve(workspace_dev, npix);
   const unsigned blocks = blocks_of(npix, kPerBlock);
-  if (hipMemsetAsync(ws.hist, 0, 4 * 3 * kBins + sizeof(Sel), stream) != hipSuccess) return pt_fail("pt_adaptive_select: hipMemsetAsync failed");
+  if (hipMemsetAsync(ws.hist, 0, 4 * 3 * kBins + sizeof(Sel), stream) != hipSuccess) return pt_fail("%s: hipMemsetAsync failed", who);
   hipLaunchKernelGGL(k_adaptive_key, dim3(blocks_of(npix, kBlock)), dim3(kBlock), 0, stream, w, rows, reinterpret_cast<const V4*>(noise_dev),
                      static_cast<const Cnt*>(counts_dev), ws.key);
   for (int pass = 0; pass < 3; ++pass) {
     hipLaunchKernelGGL(k_adaptive_hist, dim3(blocks), dim3(kBlock), 0, stream, npix, ws.key, ws.sel, pass, ws.hist + pass * kBins);
     hipLaunchKernelGGL(k_adaptive_pick, dim3(1), dim3(kBlock), 0, stream, ws.hist + pass * kBins, ws.sel, pass, (uint32_t)m);
   }
+  if (thr) {
+    hipLaunchKernelGGL(k_adaptive_above, dim3(blocks), dim3(kBlock), 0, stream, npix, ws.key, *thr, ws.sel);
+    hipLaunchKernelGGL(k_adaptive_threshold, dim3(1), dim3(1), 0, stream, ws.sel, *thr, (uint32_t)m);
+  }
   hipLaunchKernelGGL(k_adaptive_count, dim3(blocks), dim3(kBlock), 0, stream, npix, ws.key, ws.sel, ws.per_block);
   hipLaunchKernelGGL(k_adaptive_scan, dim3(1), dim3(kBlock), 0, stream, (int)blocks, ws.per_block);
   hipLaunchKernelGGL(k_adaptive_scatter, dim3(blocks), dim3(kBlock), 0, stream, npix, ws.key, ws.sel, ws.per_block, (uint32_t)m, list_dev);
-  return launched("pt_adaptive_select");
+  return launched(who);
 }
+
+int pt_adaptive_select_launch(hipStream_t stream, int w, int rows, const float* noise_dev, const void* counts_dev, int m, void* workspace_dev,
+                              int32_t* list_dev) {
+  return select_launches("pt_adaptive_select", stream, w, rows, noise_dev, counts_dev, m, nullptr, workspace_dev, list_dev);
+}
+
+int pt_adaptive_select_threshold_launch(hipStream_t stream, int w, int rows, const float* noise_dev, const void* counts_dev, float threshold, int cap,
+                                        void* workspace_dev, int32_t* list_dev) {
+  if (!std::isfinite(threshold) || threshold < 0.0f) return pt_fail("pt_adaptive_select_threshold: bad argument");
+  const uint32_t thr = ptad::threshold_bits(threshold);
+  return select_launches("pt_adaptive_select_threshold", stream, w, rows, noise_dev, counts_dev, cap, &thr, workspace_dev, list_dev);
+}
+
+const uint32_t* pt_adaptive_select_result(const void* workspace_dev, size_t pixels) { return &carve(const_cast<void*>(workspace_dev), pixels).sel->above; }
 
 int pt_adaptive_merge_launch(hipStream_t stream, int pixels, float* rgb_sum_dev, void* noise_state_dev, void* counts_dev, const int32_t* list_dev, int m,
                              const float* group_sum_dev, int group_iters) {
@@ -330,6 +387,19 @@ int pt_adaptive_check_select(const char* who, int w, int rows, const float* nois
 extern "C" int pt_adaptive_select_host(int w, int rows, const float* noise_planes, const int32_t* counts, int m, int32_t* list) {
   if (pt_adaptive_check_select("pt_adaptive_select_host", w, rows, noise_planes, counts, m, list)) return -1;
   ptad::select_host(w, rows, noise_planes, counts, m, list);
+  return 0;
+}
+
+int pt_adaptive_check_threshold(const char* who, float threshold) {
+  return std::isfinite(threshold) && threshold >= 0.0f ? 0 : pt_fail("%s: threshold %g is not finite and >= 0", who, (double)threshold);
+}
+
+extern "C" int pt_adaptive_select_threshold_host(int w, int rows, const float* noise_planes, const int32_t* counts, float threshold, int cap, int32_t* list,
+                                                 int* above, int* m) {
+  if (pt_adaptive_check_select("pt_adaptive_select_threshold_host", w, rows, noise_planes, counts, cap, list)) return -1;
+  if (pt_adaptive_check_threshold("pt_adaptive_select_threshold_host", threshold)) return -1;
+  if (!above || !m) return pt_fail("pt_adaptive_select_threshold_host: bad argument");
+  ptad::select_threshold_host(w, rows, noise_planes, counts, threshold, cap, list, above, m);
   return 0;
 }
 

@@ -925,6 +925,13 @@ int pt_render_adaptive(int iter_first, int max_iters, int group_iters, float fra
   return pt_ctx_render_adaptive(g_default, iter_first, max_iters, group_iters, fraction, target_db, iters_done, samples_done, psnr_db);
 }
 int pt_readback_adaptive(int32_t* counts) { return pt_ctx_readback_adaptive(g_default, counts); }
+int pt_adaptive_round_threshold(int iter_first, int group_iters, float threshold, float max_fraction, int* above, int* selected) {
+  return pt_ctx_adaptive_round_threshold(g_default, iter_first, group_iters, threshold, max_fraction, above, selected);
+}
+int pt_render_threshold(int iter_first, int max_iters, int group_iters, float threshold, float max_fraction, int min_pixels, int* iters_done,
+                        int64_t* samples_done, int* above_left) {
+  return pt_ctx_render_threshold(g_default, iter_first, max_iters, group_iters, threshold, max_fraction, min_pixels, iters_done, samples_done, above_left);
+}
 int pt_resolve(float* rgb_avg_host) { return pt_ctx_resolve(g_default, rgb_avg_host); }
 int pt_set_reference(const float* rgb_avg_host) { return pt_ctx_set_reference(g_default, rgb_avg_host); }
 int pt_get_convergence(int iter_first, int iter_count, double* sse) { return pt_ctx_get_convergence(g_default, iter_first, iter_count, sse); }

@@ -125,6 +125,7 @@ struct PtContext : PtShared {
   bool borrowed = false;           // a worker context: what PtShared holds belongs to its parent
   const int32_t* list = nullptr;   // BatchInfo::list of this context's batches (a worker's: the parent's d_list)
   PtContext* worker = nullptr;     // the context that renders the pixel list; its tile is the list's m pixels, its d_image the group sum Sw
+  int capacity = 0;                // a worker: the pixels it was planned and allocated for; its N is the LIVE list length, <= capacity
   int32_t* d_list = nullptr;       // N entries, the first worker->N in use
   void* d_acnt = nullptr;          // the plane cnt: N * ptad::Cnt
   void* d_select = nullptr;        // pt_adaptive_select_bytes(N)
@@ -211,6 +212,7 @@ int get_events(Ctx& g, EventPair* ev);
 ptd::Queues single_queue(const Ctx& g, int n);
 void destroy(Ctx* c);
 // pt_post.cpp: the worker context of adaptive sampling
-int ensure_worker(Ctx& g, int m);                         // g.worker: a context whose tile is the first m entries of g.d_list
+int ensure_worker(Ctx& g, int capacity);                  // g.worker: a context planned for `capacity` pixels, its live tile the first `capacity` entries of g.d_list
+void set_worker_live(Ctx& w, int m);                      // the worker's tile := the first m <= capacity entries; nothing allocated, freed or cleared
 int render_list(Ctx& g, int iter_first, int iter_count);  // those iterations of the listed pixels into the worker's cleared sum
 }  // namespace ptc

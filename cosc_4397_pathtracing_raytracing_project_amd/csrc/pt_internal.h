@@ -60,6 +60,13 @@ int pt_adaptive_check_select(const char* who, int w, int rows, const float* nois
 int pt_adaptive_init_counts_launch(hipStream_t stream, int pixels, void* counts_dev, int iters, int groups);
 int pt_adaptive_select_launch(hipStream_t stream, int w, int rows, const float* noise_dev, const void* counts_dev, int m, void* workspace_dev,
                               int32_t* list_dev);
+// Selection by threshold: the pixels whose key exceeds threshold * threshold, the `cap` with the largest keys at the most, at the
+// front of list_dev (cap entries; those behind the list's length keep what they held).  pt_adaptive_select_result: two uint32 in the
+// workspace, {above, m = min(above, cap)}, valid once the launches have run.
+int pt_adaptive_check_threshold(const char* who, float threshold);  // finite and >= 0, or the refusal
+int pt_adaptive_select_threshold_launch(hipStream_t stream, int w, int rows, const float* noise_dev, const void* counts_dev, float threshold, int cap,
+                                        void* workspace_dev, int32_t* list_dev);
+const uint32_t* pt_adaptive_select_result(const void* workspace_dev, size_t pixels);
 int pt_adaptive_merge_launch(hipStream_t stream, int pixels, float* rgb_sum_dev, void* noise_state_dev, void* counts_dev, const int32_t* list_dev, int m,
                              const float* group_sum_dev, int group_iters);
 int pt_adaptive_resolve_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, const void* counts_dev, int iters, float* rgb_avg_dev);

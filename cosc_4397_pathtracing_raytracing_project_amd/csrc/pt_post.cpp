@@ -8,6 +8,7 @@
 #include "pt_context.h"
 #include "pt_denoise.h"
 #include "pt_noise.h"
+#include "pt_sched.h"
 
 using namespace ptc;
 
@@ -178,10 +179,26 @@ int pt_ctx_render_until(PtContext* c, int iter_first, int max_iters, int group_i
 
 // ---- adaptive sampling: further groups over the noisiest pixels only (csrc/pt_adaptive.hip) -------------------------------
 namespace ptc {
-// The worker context for a list of m pixels: batches, queues, buffers and launch widths planned for N = m like any context's; the
+// A round over m <= capacity pixels on a worker planned for `capacity`: only what follows from N is planned again — the chunks per
+// queue, the paths per queue and batch, the record slots per region (pt_sched.h queue_plan).  K, Q, slot_shift, the launch widths and
+// every buffer stay those of the capacity: queue_plan is monotone in N for fixed Q and K (tests/test_sched_capacity.py), so the
+// smaller plan's regions lie inside the larger one's, and the path buffers keep their plane distance (PathBuf::stride, an allocation's
+// property).  Nothing is freed, allocated or cleared; the retirement fill levels and the counter rows are zero between batches anyway.
+void set_worker_live(Ctx& w, int m) {
+  const ptk::QueuePlan plan = ptk::queue_plan(m, w.qs.Q, w.K);
+  w.N = m;
+  w.qs.nq = plan.nq;
+  w.qs.inv_nq = 1.0f / (float)plan.nq;
+  w.qs.cap = plan.cap;
+  w.stride = (int64_t)w.qs.Q * plan.cap;
+  w.ret.seg_cap = plan.seg_cap;
+}
+
+// The worker context for a list of up to m pixels: batches, queues, buffers and launch widths planned for N = m like any context's; the
 // scene tables, the grid or BVH choice and the LDS-table decision are the parent's (neither uploaded nor measured again, not owned).
+// A worker of that capacity is kept, with its live size back at the capacity; one of another capacity is replaced.
 int ensure_worker(Ctx& g, int m) {
-  if (g.worker && g.worker->N == m) return 0;
+  if (g.worker && g.worker->capacity == m) return set_worker_live(*g.worker, m), 0;
   if (g.worker) g.device_bytes -= g.worker->device_bytes, destroy(g.worker), g.worker = nullptr;
   if (ensure(g, g.d_list, (size_t)g.N * sizeof(int32_t), Zero::blocking)) return -1;  // the list: every entry a tile pixel from the start
   Ctx* w = new Ctx();
@@ -194,6 +211,7 @@ int ensure_worker(Ctx& g, int m) {
   plan_launch(*w);
   if (alloc_batch_buffers(*w)) return destroy(w), -1;
   w->list = g.d_list;
+  w->capacity = m;
   g.worker = w;
   g.device_bytes += w->device_bytes;
   return 0;
@@ -228,6 +246,50 @@ static int adaptive_refusal(const Ctx& g, const char* who, int iter_first, int g
   if (g.noise_iters > INT32_MAX / 2) return pt_fail("%s: %lld iterations folded: the per-pixel counts are int32", who, (long long)g.noise_iters);
   return 0;
 }
+
+// The first round since pt_init / pt_clear, of either kind: every pixel has the fold's T and M.
+static int enter_adaptive(Ctx& g) {
+  if (g.adaptive) return 0;
+  if (ensure(g, g.d_acnt, (size_t)g.N * sizeof(ptad::Cnt)) || ensure(g, g.d_select, pt_adaptive_select_bytes((size_t)g.N))) return -1;
+  if (pt_adaptive_init_counts_launch(g.stream, g.N, g.d_acnt, (int)g.noise_iters, g.noise_groups)) return -1;
+  g.adaptive = true;
+  g.adaptive_rounds = 0;
+  g.adaptive_last = g.noise_iters;
+  return 0;
+}
+
+// The second half of a round: the worker's live tile renders the group, the merge joins it.
+static int render_and_merge(Ctx& g, int iter_first, int group_iters, int m) {
+  if (render_list(g, iter_first, group_iters)) return -1;
+  if (pt_adaptive_merge_launch(g.stream, g.N, g.d_image, g.d_noise, g.d_acnt, g.d_list, m, g.worker->d_image, group_iters)) return -1;
+  g.adaptive_rounds += 1;
+  g.adaptive_last = std::max<int64_t>(g.adaptive_last, (int64_t)iter_first + group_iters - 1);
+  g.samples += (int64_t)group_iters * m;  // (live_rays and the kernel timings stay the parent's own launches')
+  return 0;
+}
+
+// A threshold round after its refusals: key and select, the two counts read back (8 bytes and ONE synchronise, which a fixed-fraction
+// round does not have: the list's length decides the launches that follow), then the group over the first m entries unless
+// above <= min_pixels.  *selected: the pixels rendered, 0 when nothing was.
+static int threshold_round(Ctx& g, int iter_first, int group_iters, float threshold, float max_fraction, int min_pixels, int* above, int* selected) {
+  HIP_OK(hipSetDevice(g.device));
+  const int W = g.cam.resolution[0];
+  if (enter_adaptive(g)) return -1;
+  const int cap = ptad::list_length((double)max_fraction, g.N);
+  if (ensure_worker(g, cap)) return -1;
+  if (pt_adaptive_select_threshold_launch(g.stream, W, g.N / W, static_cast<const float*>(g.d_noise), g.d_acnt, threshold, cap, g.d_select, g.d_list)) return -1;
+  uint32_t result[2] = {0u, 0u};  // above, m
+  HIP_OK(hipMemcpyAsync(result, pt_adaptive_select_result(g.d_select, (size_t)g.N), sizeof(result), hipMemcpyDeviceToHost, g.stream));
+  HIP_OK(hipStreamSynchronize(g.stream));
+  const int m = (int)result[1];
+  if (m < 0 || m > cap || (int)result[0] < m) return pt_fail("pt_adaptive_round_threshold: the selection left %u above, a list of %u (cap %d)", result[0], result[1], cap);
+  const bool render = m > 0 && (int)result[0] > min_pixels;
+  if (above) *above = (int)result[0];
+  if (selected) *selected = render ? m : 0;
+  if (!render) return 0;  // nothing rendered or merged, no round counted, SSE_est where it was
+  set_worker_live(*g.worker, m);
+  return render_and_merge(g, iter_first, group_iters, m);
+}
 }  // namespace ptc
 
 extern "C" {
@@ -238,21 +300,53 @@ int pt_ctx_adaptive_round(PtContext* c, int iter_first, int group_iters, float f
   if (adaptive_refusal(g, "pt_adaptive_round", iter_first, group_iters, fraction)) return -1;
   HIP_OK(hipSetDevice(g.device));
   const int W = g.cam.resolution[0];
-  if (!g.adaptive) {  // the first round since pt_init / pt_clear: every pixel has the fold's T and M
-    if (ensure(g, g.d_acnt, (size_t)g.N * sizeof(ptad::Cnt)) || ensure(g, g.d_select, pt_adaptive_select_bytes((size_t)g.N))) return -1;
-    if (pt_adaptive_init_counts_launch(g.stream, g.N, g.d_acnt, (int)g.noise_iters, g.noise_groups)) return -1;
-    g.adaptive = true;
-    g.adaptive_rounds = 0;
-    g.adaptive_last = g.noise_iters;
-  }
+  if (enter_adaptive(g)) return -1;
   const int m = ptad::list_length((double)fraction, g.N);
-  if (ensure_worker(g, m)) return -1;
+  if (ensure_worker(g, m)) return -1;  // (a worker of that capacity: its live size is the capacity again, whatever a threshold round left)
   if (pt_adaptive_select_launch(g.stream, W, g.N / W, static_cast<const float*>(g.d_noise), g.d_acnt, m, g.d_select, g.d_list)) return -1;
-  if (render_list(g, iter_first, group_iters)) return -1;
-  if (pt_adaptive_merge_launch(g.stream, g.N, g.d_image, g.d_noise, g.d_acnt, g.d_list, m, g.worker->d_image, group_iters)) return -1;
-  g.adaptive_rounds += 1;
-  g.adaptive_last = std::max<int64_t>(g.adaptive_last, (int64_t)iter_first + group_iters - 1);
-  g.samples += (int64_t)group_iters * m;  // (live_rays and the kernel timings stay the parent's own launches')
+  return render_and_merge(g, iter_first, group_iters, m);
+}
+
+int pt_ctx_adaptive_round_threshold(PtContext* c, int iter_first, int group_iters, float threshold, float max_fraction, int* above, int* selected) {
+  if (need(c, "pt_adaptive_round_threshold")) return -1;
+  Ctx& g = *c;
+  if (adaptive_refusal(g, "pt_adaptive_round_threshold", iter_first, group_iters, max_fraction)) return -1;
+  if (pt_adaptive_check_threshold("pt_adaptive_round_threshold", threshold)) return -1;
+  return threshold_round(g, iter_first, group_iters, threshold, max_fraction, 0, above, selected);
+}
+
+int pt_ctx_render_threshold(PtContext* c, int iter_first, int max_iters, int group_iters, float threshold, float max_fraction, int min_pixels,
+                            int* iters_done, int64_t* samples_done, int* above_left) {
+  if (need(c, "pt_render_threshold")) return -1;
+  Ctx& g = *c;
+  if (max_iters < 1 || (int64_t)iter_first + max_iters - 1 > INT32_MAX || group_iters < 0 || min_pixels < 0)
+    return pt_fail("pt_render_threshold: iterations %d, +%d in groups of %d until at most %d pixels are above: the count is >= 1, the group >= 0 (0 = a batch of the worker), the pixels >= 0",
+                iter_first, max_iters, group_iters, min_pixels);
+  // what a round would refuse, apart from the state of the folds, which the uniform groups below establish
+  if (adaptive_refusal(g, "pt_render_threshold", iter_first, group_iters, max_fraction, false)) return -1;
+  if (pt_adaptive_check_threshold("pt_render_threshold", threshold)) return -1;
+  const int cap = ptad::list_length((double)max_fraction, g.N);
+  const int group = group_iters ? group_iters : g.worker && g.worker->capacity == cap ? g.worker->K : batch_iters_for(g.opt_iters_per_batch, cap, nullptr);
+  int done = 0, above = -1;
+  int64_t samples = 0;
+  while (done < max_iters) {
+    const int n = std::min(group, max_iters - done);
+    if (!g.adaptive && g.noise_groups < 2) {  // a uniform group and its fold, as pt_render_adaptive
+      if (pt_ctx_render(c, iter_first + done, n) || pt_ctx_noise_fold(c)) return -1;
+      samples += (int64_t)n * g.N;
+    } else {
+      if (!g.adaptive && g.rendered != g.noise_iters && pt_ctx_noise_fold(c)) return -1;  // iterations of the caller's, not yet folded
+      if (adaptive_refusal(g, "pt_render_threshold", iter_first + done, n, max_fraction)) return -1;
+      int m = 0;
+      if (threshold_round(g, iter_first + done, n, threshold, max_fraction, min_pixels, &above, &m)) return -1;
+      if (above <= min_pixels) break;  // nothing was rendered
+      samples += (int64_t)n * m;
+    }
+    done += n;
+  }
+  if (iters_done) *iters_done = done;
+  if (samples_done) *samples_done = samples;
+  if (above_left) *above_left = above;
   return 0;
 }
 
@@ -267,7 +361,7 @@ int pt_ctx_render_adaptive(PtContext* c, int iter_first, int max_iters, int grou
   if (adaptive_refusal(g, "pt_render_adaptive", iter_first, group_iters, fraction, false)) return -1;
   const int m = ptad::list_length((double)fraction, g.N);
   // group_iters == 0: the iterations per batch a worker for m pixels plans (plan_batches' own function)
-  const int group = group_iters ? group_iters : g.worker && g.worker->N == m ? g.worker->K : batch_iters_for(g.opt_iters_per_batch, m, nullptr);
+  const int group = group_iters ? group_iters : g.worker && g.worker->capacity == m ? g.worker->K : batch_iters_for(g.opt_iters_per_batch, m, nullptr);
   int done = 0;
   int64_t samples = 0;
   float psnr = -1.0f;

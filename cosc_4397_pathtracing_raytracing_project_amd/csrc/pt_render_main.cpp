@@ -8,6 +8,7 @@
 //                       [--preview N] [--convergence N | --reference FILE.pfm] [--clean-db X] [--features]
 //                       [--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]]
 //                       [--denoise-guided] [--until-db X [--until-group G] [--adaptive F [--denoise-adaptive]]]
+//                       [--adaptive-threshold E [--adaptive-cap F] [--adaptive-min-pixels P] [--until-group G] [--denoise-adaptive]]
 //
 // Without --gpus the run goes through the pathtrace.h-compatible shim (pathtraceInit / pathtrace per
 // iteration / pathtraceFree), i.e. the code path a reference main.cpp would take.  With --gpus K (K >= 1;
@@ -42,7 +43,14 @@
 // Prints `adaptive: <iterations> iterations, <rounds> rounds, <samples> samples (<x> of uniform), estimated PSNR <y> dB`, x being
 // the samples over iterations * pixels; the PNG / PFM / HDR hold the resolved image (pt_resolve: every pixel's sum over its own
 // sample count) and the file name carries ceil(samples / pixels).
-// --denoise-adaptive (needs --adaptive F; implies --features; excludes --denoise and --denoise-guided, takes the --denoise-* options,
+// --adaptive-threshold E (takes --until-group, --adaptive-cap F, default 0.25, and --adaptive-min-pixels P, default 0; excludes
+// --adaptive, --until-db, --gpus / --devices, --denoise, --denoise-guided, --convergence, --reference and --preview): adaptive sampling
+// until every pixel is below a noise threshold (pt_render_threshold) — two uniform groups of G iterations, then rounds of G iterations
+// over the pixels whose estimated standard error exceeds E, the noisiest fraction F of the frame at the most, until at most P pixels
+// are above or --spp iteration numbers are used up.  The worker's memory follows F and the iterations per batch.  Prints
+// `adaptive: threshold <E>: <iterations> iterations, <rounds> rounds, <samples> samples (<x> of uniform), <n> pixels above, estimated
+// PSNR <y> dB`; the files are those of --adaptive, named the same way.
+// --denoise-adaptive (needs --adaptive F or --adaptive-threshold E; implies --features; excludes --denoise and --denoise-guided, takes the --denoise-* options,
 // sigma C's default being 8): the variance-guided filter with per-pixel sample counts (pt_denoise_adaptive) over the adaptive image,
 // after the resolved image is written.  Same output files as --denoise.
 // Output name: PREFIX.<spp>samp.png, or with --stamp the reference's own
@@ -68,7 +76,8 @@ int main(int argc, char** argv) {
     std::printf("Usage: %s SCENEFILE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] "
                 "[--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa] [--preview N] "
                 "[--convergence N | --reference FILE.pfm] [--clean-db X] [--features] "
-                "[--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]] [--denoise-guided] [--until-db X [--until-group G] [--adaptive F [--denoise-adaptive]]]\n", argv[0]);
+                "[--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]] [--denoise-guided] [--until-db X [--until-group G] [--adaptive F [--denoise-adaptive]]] "
+                "[--adaptive-threshold E [--adaptive-cap F] [--adaptive-min-pixels P] [--until-group G] [--denoise-adaptive]]\n", argv[0]);
     return 1;
   }
   int rw = 0, rh = 0, spp = 0, depth = 0, gpus = -1, arith = PT_ARITH_EXACT, preview = 0, transport = PT_GROUP_TRANSPORT_AUTO;
@@ -78,6 +87,9 @@ int main(int argc, char** argv) {
   int convergence = 0, until_group = 0;
   bool until = false, until_group_given = false;
   float clean_db = 35.0f, until_db = 0.0f, adaptive = 0.0f;  // adaptive > 0: --adaptive F
+  float threshold = 0.0f, threshold_cap = 0.25f;           // --adaptive-threshold E, --adaptive-cap F
+  int threshold_min_pixels = 0;                            // --adaptive-min-pixels P
+  bool by_threshold = false, threshold_cap_given = false, threshold_min_given = false;
   std::string out, reference;
   for (int i = 2; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--res") && i + 1 < argc) std::sscanf(argv[++i], "%dx%d", &rw, &rh);
@@ -163,6 +175,31 @@ int main(int argc, char** argv) {
         return 1;
       }
     }
+    else if (!std::strcmp(argv[i], "--adaptive-threshold") && i + 1 < argc) {
+      char* end = nullptr;
+      threshold = std::strtof(argv[++i], &end);
+      if (end == argv[i] || *end || !std::isfinite(threshold) || threshold < 0.0f) {
+        std::fprintf(stderr, "--adaptive-threshold wants the standard error below which a pixel is left alone, a finite number >= 0\n");
+        return 1;
+      }
+      by_threshold = true;
+    } else if (!std::strcmp(argv[i], "--adaptive-cap") && i + 1 < argc) {
+      char* end = nullptr;
+      threshold_cap = std::strtof(argv[++i], &end);
+      if (end == argv[i] || *end || !(threshold_cap > 0.0f && threshold_cap <= 1.0f)) {
+        std::fprintf(stderr, "--adaptive-cap wants the largest fraction of the pixels a round samples, 0 < F <= 1\n");
+        return 1;
+      }
+      threshold_cap_given = true;
+    } else if (!std::strcmp(argv[i], "--adaptive-min-pixels") && i + 1 < argc) {
+      char* end = nullptr;
+      const long v = std::strtol(argv[++i], &end, 10);
+      if (end == argv[i] || *end || v < 0 || v > INT32_MAX) {
+        std::fprintf(stderr, "--adaptive-min-pixels wants the number of pixels above the threshold at which to stop, >= 0\n");
+        return 1;
+      }
+      threshold_min_pixels = (int)v, threshold_min_given = true;
+    }
     else if (!std::strcmp(argv[i], "--aa")) aa = true;  // extension: stochastic anti-aliasing (PtOptions.aa_jitter)
     else if (!std::strcmp(argv[i], "--arith") && i + 1 < argc) {
       const char* a = argv[++i];
@@ -191,8 +228,8 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--denoise-adaptive excludes --denoise and --denoise-guided (one filtered image)\n");
     return 1;
   }
-  if (dn_adaptive && !(adaptive > 0.0f)) {
-    std::fprintf(stderr, "--denoise-adaptive wants --adaptive (the filter of an adaptively sampled image)\n");
+  if (dn_adaptive && !(adaptive > 0.0f) && !by_threshold) {
+    std::fprintf(stderr, "--denoise-adaptive wants --adaptive or --adaptive-threshold (the filter of an adaptively sampled image)\n");
     return 1;
   }
   if (!denoise && !guided && !dn_adaptive && (dn_opt.levels || dn_opt.keep_albedo || dn_opt.sigma_color != 0.0f || dn_opt.sigma_normal != 0.0f || dn_opt.sigma_position != 0.0f)) {
@@ -200,8 +237,8 @@ int main(int argc, char** argv) {
     return 1;
   }
   if (denoise || guided || dn_adaptive) features = true;
-  if (until_group_given && !until && !guided) {
-    std::fprintf(stderr, "--until-group wants --until-db or --denoise-guided\n");
+  if (until_group_given && !until && !guided && !by_threshold) {
+    std::fprintf(stderr, "--until-group wants --until-db, --denoise-guided or --adaptive-threshold\n");
     return 1;
   }
   if (guided && preview > 0) {
@@ -218,6 +255,15 @@ int main(int argc, char** argv) {
       return 1;
     }
   }
+  if ((threshold_cap_given || threshold_min_given) && !by_threshold) {
+    std::fprintf(stderr, "--adaptive-cap and --adaptive-min-pixels want --adaptive-threshold\n");
+    return 1;
+  }
+  if (by_threshold && (adaptive > 0.0f || until || gpus >= 0 || denoise || guided || convergence != 0 || preview > 0)) {
+    std::fprintf(stderr, "--adaptive-threshold excludes --adaptive, --until-db, --gpus / --devices, --denoise, --denoise-guided, --convergence, --reference and --preview\n");
+    return 1;
+  }
+  const bool adaptive_mode = adaptive > 0.0f || by_threshold;  // the image is the resolved one, the samples are counted
   if (until && preview > 0) {
     std::fprintf(stderr, "--until-db and --preview exclude each other (one loop over the iterations)\n");
     return 1;
@@ -318,7 +364,24 @@ int main(int argc, char** argv) {
     }
     const auto t0 = std::chrono::high_resolution_clock::now();
     int64_t adaptive_samples = 0;
-    if (adaptive > 0.0f) {
+    if (by_threshold) {
+      int done = 0, groups = 0, above = -1;
+      double sse = -1.0;
+      scene->state.image.resize((size_t)W * H * 3);
+      if (pt_render_threshold(1, iters, until_group, threshold, threshold_cap, threshold_min_pixels, &done, &adaptive_samples, &above) ||
+          pt_get_noise(&sse, &groups, nullptr) || pt_resolve(scene->state.image.data())) {
+        std::fprintf(stderr, "HIP error (pt_render_threshold): %s\n", pt_last_error());
+        return EXIT_FAILURE;
+      }
+      const int64_t pixels = (int64_t)W * H;
+      std::printf("adaptive: threshold %.9g: %d iterations, %d rounds, %lld samples (%.4f of uniform), %d pixels above, estimated PSNR %.9g dB\n", (double)threshold,
+                  done, std::max(0, groups - 2), (long long)adaptive_samples, (double)adaptive_samples / ((double)done * (double)pixels), above,
+                  sse < 0.0 ? -1.0 : (double)pt_psnr_from_sse(sse, pixels));
+      scene->state.iterations = done;
+      iters = (int)((adaptive_samples + pixels - 1) / pixels);  // what the file names carry
+      name_outputs();
+      iters = done;  // (the feature pass covers the iteration numbers used)
+    } else if (adaptive > 0.0f) {
       int done = 0, groups = 0;
       float psnr = -1.0f;
       scene->state.image.resize((size_t)W * H * 3);
@@ -351,14 +414,14 @@ int main(int argc, char** argv) {
     } else {
       for (int it = 1; it <= iters; ++it) pathtrace(nullptr, 0, it);  // main.cpp:138-149
     }
-    if (adaptive > 0.0f) pt_sync();  // (the resolved image is already in scene->state.image; the SUM image alone means nothing)
+    if (adaptive_mode) pt_sync();  // (the resolved image is already in scene->state.image; the SUM image alone means nothing)
     else pathtraceSyncImage();
     secs = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
-    const double samples_done = adaptive > 0.0f ? (double)adaptive_samples : (double)W * H * iters;
+    const double samples_done = adaptive_mode ? (double)adaptive_samples : (double)W * H * iters;
     // (adaptive: the spp of the file names, ceil(samples / pixels), beside the rate of the samples actually rendered)
-    const int spp_done = adaptive > 0.0f ? (int)((adaptive_samples + (int64_t)W * H - 1) / ((int64_t)W * H)) : iters;
+    const int spp_done = adaptive_mode ? (int)((adaptive_samples + (int64_t)W * H - 1) / ((int64_t)W * H)) : iters;
     std::printf("%dx%d, %d spp, depth %d: %.3f s, %.2f Msamples/s\n", W, H, spp_done, scene->state.traceDepth, secs, samples_done / secs / 1e6);
-    const float image_samples = adaptive > 0.0f ? 1.0f : (float)iters;  // the resolved image is averaged radiance already
+    const float image_samples = adaptive_mode ? 1.0f : (float)iters;  // the resolved image is averaged radiance already
     if (pt_save_png((base + ".png").c_str(), scene->state.image.data(), W, H, image_samples) == 0)
       std::printf("Saved %s.png.\n", base.c_str());
     if (pfm && pt_save_pfm((base + ".pfm").c_str(), scene->state.image.data(), W, H, image_samples) == 0)

@@ -308,29 +308,65 @@ int pt_stage_adaptive_select(int w, int rows, const float* noise_planes, const i
   return 0;
 }
 
+// The threshold selection's kernels on caller-supplied host arrays (pt_adaptive_select_threshold_host's arguments)
+int pt_stage_adaptive_select_threshold(int w, int rows, const float* noise_planes, const int32_t* counts, float threshold, int cap, int32_t* list,
+                                       int* above, int* m) {
+  if (need(default_context(), "pt_stage_adaptive_select_threshold")) return -1;
+  Ctx& g = *default_context();
+  if (pt_adaptive_check_select("pt_stage_adaptive_select_threshold", w, rows, noise_planes, counts, cap, list)) return -1;
+  if (pt_adaptive_check_threshold("pt_stage_adaptive_select_threshold", threshold)) return -1;
+  if (!above || !m) return pt_fail("pt_stage_adaptive_select_threshold: bad argument");
+  HIP_OK(hipSetDevice(g.device));
+  Scratch sc;
+  const size_t n = (size_t)w * rows;
+  float* d_plane0 = nullptr;
+  int32_t* d_counts = nullptr;
+  char* d_ws = sc.get<char>(pt_adaptive_select_bytes(n));
+  int32_t* d_list = sc.get<int32_t>((size_t)cap);
+  if (!d_ws || !d_list) return pt_fail("pt_stage_adaptive_select_threshold: out of device memory");
+  if (device_copy(sc, "pt_stage_adaptive_select_threshold", noise_planes, 4 * n, &d_plane0)) return -1;  // the selection reads plane 0 only
+  if (device_copy(sc, "pt_stage_adaptive_select_threshold", counts, 2 * n, &d_counts)) return -1;
+  HIP_OK(hipMemset(d_list, 0xff, (size_t)cap * sizeof(int32_t)));  // an entry nobody wrote shows as -1
+  if (pt_adaptive_select_threshold_launch(g.stream, w, rows, d_plane0, d_counts, threshold, cap, d_ws, d_list)) return -1;
+  HIP_OK(hipStreamSynchronize(g.stream));
+  uint32_t result[2] = {0u, 0u};
+  HIP_OK(hipMemcpy(result, pt_adaptive_select_result(d_ws, n), sizeof(result), hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(list, d_list, (size_t)cap * sizeof(int32_t), hipMemcpyDeviceToHost));  // all cap entries: those behind m must still be -1
+  *above = (int)result[0], *m = (int)result[1];
+  return 0;
+}
+
 // The worker context alone: iterations iter_first .. iter_first + iter_count - 1 of the m listed tile pixels (distinct, any order);
 // rgb_sum_host receives the group sum, m * 3 floats in list order.  Leaves image, folds and state of the renderer alone.
-int pt_stage_render_list(const int32_t* list, int m, int iter_first, int iter_count, float* rgb_sum_host) {
-  if (need(default_context(), "pt_stage_render_list")) return -1;
+static int stage_render_list(const char* who, const int32_t* list, int m, int capacity, int iter_first, int iter_count, float* rgb_sum_host) {
+  if (need(default_context(), who)) return -1;
   Ctx& g = *default_context();
-  if (!list || !rgb_sum_host || m < 1 || m > g.N || iter_first < 1 || iter_count < 0 || (int64_t)iter_first + iter_count - 1 > INT32_MAX)
-    return pt_fail("pt_stage_render_list: bad argument (a list of %d out of %d pixels, iterations %d, +%d)", m, g.N, iter_first, iter_count);
-  if (admit(g, "pt_stage_render_list", kNotFailed)) return -1;
-  if (g.stripe) return pt_fail("pt_stage_render_list: a striped tile has no list form");
+  if (!list || !rgb_sum_host || m < 1 || m > capacity || capacity > g.N || iter_first < 1 || iter_count < 0 || (int64_t)iter_first + iter_count - 1 > INT32_MAX)
+    return pt_fail("%s: bad argument (a list of %d, a worker for %d out of %d pixels, iterations %d, +%d)", who, m, capacity, g.N, iter_first, iter_count);
+  if (admit(g, who, kNotFailed)) return -1;
+  if (g.stripe) return pt_fail("%s: a striped tile has no list form", who);
   {
     std::vector<uint8_t> seen((size_t)g.N, 0);
     for (int i = 0; i < m; ++i) {
-      if (list[i] < 0 || list[i] >= g.N || seen[(size_t)list[i]]) return pt_fail("pt_stage_render_list: list[%d] = %d is outside the tile or repeated", i, list[i]);
+      if (list[i] < 0 || list[i] >= g.N || seen[(size_t)list[i]]) return pt_fail("%s: list[%d] = %d is outside the tile or repeated", who, i, list[i]);
       seen[(size_t)list[i]] = 1;
     }
   }
   HIP_OK(hipSetDevice(g.device));
-  if (ensure_worker(g, m)) return -1;
+  if (ensure_worker(g, capacity)) return -1;
+  set_worker_live(*g.worker, m);
   HIP_OK(hipStreamSynchronize(g.stream));  // (the list may still be read by an earlier round)
   HIP_OK(hipMemcpy(g.d_list, list, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice));
   if (render_list(g, iter_first, iter_count)) return -1;
   HIP_OK(hipMemcpyAsync(rgb_sum_host, g.worker->d_image, 3 * (size_t)m * sizeof(float), hipMemcpyDeviceToHost, g.stream));
   return pt_ctx_sync(&g);
+}
+int pt_stage_render_list(const int32_t* list, int m, int iter_first, int iter_count, float* rgb_sum_host) {
+  return stage_render_list("pt_stage_render_list", list, m, m, iter_first, iter_count, rgb_sum_host);
+}
+// ... on a worker planned for `capacity` pixels, kept across calls while the capacity is equal
+int pt_stage_render_list_capacity(const int32_t* list, int m, int capacity, int iter_first, int iter_count, float* rgb_sum_host) {
+  return stage_render_list("pt_stage_render_list_capacity", list, m, capacity, iter_first, iter_count, rgb_sum_host);
 }
 
 }  // extern "C"

@@ -494,7 +494,7 @@ int pt_denoise_guided_variance_host(int w, int rows, const float* rgb_sum, const
  * the smaller tile index, stored in ascending tile index.  On the device a radix select (11 / 11 / 10 bits, integer atomics on
  * histogram bins only) finds the threshold key and the number of pixels equal to it to take, and a counting pass, a scan and a
  * scatter write the list; no host synchronisation, equal inputs give an equal list.
- * Render: a worker context owned by the renderer, whose tile is the list (created by the first round, recreated when m changes,
+ * Render: a worker context owned by the renderer, whose tile is the list (created by the first round, replaced when m differs from the capacity it was planned for,
  * its memory part of PtStats.device_bytes), renders iterations iter_first .. iter_first + G - 1 (global iteration numbers, the RNG
  * keyed by the global pixel as everywhere) for the listed pixels into a cleared group sum Sw[m][3], with the renderer's arithmetic
  * mode, scene tables, traversal choice and options; iters_per_batch and num_queues of 0 are automatic for m pixels.  Pixels outside
@@ -517,8 +517,8 @@ int pt_denoise_guided_variance_host(int w, int rows, const float* rgb_sum, const
  *     MI355X in that configuration (tests/test_gpu_adaptive.py): 0.843, the estimate reading 33.84 dB where the image has 33.10 dB.
  *   - A pixel whose first two groups agree exactly has w = 0 and is sampled again only through its neighbours' variance (the
  *     prefilter).  For background and emitter pixels that is the point; a pixel that is noisy but unlucky twice is reached the same way.
- * Out of scope: pt_group_* (a rank's top m is not the frame's), a list length that varies from round to round, and any tuning of
- * the path-tracing kernels for incoherent lists.  pt_denoise and pt_denoise_guided refuse the adaptive state; pt_denoise_adaptive
+ * Out of scope: pt_group_* (a rank's top m is not the frame's) and any tuning of the path-tracing kernels for incoherent lists; a list
+ * length that varies from round to round is pt_adaptive_round_threshold, below.  pt_denoise and pt_denoise_guided refuse the adaptive state; pt_denoise_adaptive
  * (below) is the filter that reads the per-pixel counts.
  * In the adaptive state pt_readback (S), pt_get_noise (sse = the last merge's, groups = M + rounds, iterations = the highest
  * iteration number folded or merged), pt_readback_noise, pt_render_features and pt_get_stats still work; pt_render, pt_noise_fold,
@@ -545,6 +545,50 @@ int pt_adaptive_select_host(int w, int rows, const float* noise_planes, const in
  * pixels added in pixel order.  The device's image, planes and counts equal it bit for bit. */
 int pt_adaptive_merge_host(int pixels, float* rgb_sum, float* planes, int32_t* counts, const int32_t* list, int m, const float* group_sum,
                            int group_iters, double* sse);
+
+/* ---- adaptive sampling until every pixel is below a noise threshold: rounds whose list is the pixels ABOVE an absolute threshold,
+ * so that it shrinks as the frame cleans up and a round over an almost clean frame costs what its few pixels cost.  Key, render,
+ * merge, resolve and the adaptive state are those of pt_adaptive_round, bit for bit; only the selection differs, and the two kinds of
+ * round may alternate on one renderer.
+ * Threshold: thr = threshold * threshold, ONE float32 multiply (threshold is a standard error of the pixel's mean, summed over the
+ * three channels like w; it must be finite and >= 0).  Pixel p is ABOVE iff bits(key_p) > bits(thr) as uint32, key_p exactly the key
+ * above (NaN -> 0xffffffff): a key equal to thr is not above, a NaN key is above, a zero-variance pixel never is.
+ * Counts: above = #{p above};  cap = clamp(ceil((double)max_fraction * N), 1, N)  (the fixed-fraction round's m);  m = min(above, cap).
+ * List: the m above-pixels with the largest keys, equal keys resolved by the smaller tile index, in ascending tile index: every
+ * above-pixel when above <= cap, and bit for bit the list of the top-cap selection when above > cap.
+ * On the device the radix select runs for rank cap and leaves (tau, r); one more counting pass counts `above` (integer atomics only,
+ * no float atomics: equal inputs give an equal list); count, scan and scatter then run with tau' = max(tau, bits(thr)) and
+ * r' = tau > bits(thr) ? r : 0.  above and m stay in the selection's workspace, which is as large as it was.
+ * Render: the worker context is planned and allocated ONCE, for cap pixels, as a fixed-fraction round's for m = cap; a round over
+ * m <= cap pixels plans again only what follows from N (chunks per queue, paths per queue and batch, record slots per region) and
+ * frees, allocates and clears nothing but the 3 * m floats of the group sum.  iters_per_batch and num_queues of 0 are automatic for
+ * cap pixels.  A fixed-fraction round whose m equals the worker's capacity uses the same worker; another m replaces it.
+ * What to know, besides the three caveats above, which all hold:
+ *   - The threshold is ONE SIGMA of an ESTIMATE, not a bound, and the estimate reads low under selection (the pixels that
+ *     underestimate their variance are the ones that stop).  Simulated (cornell 96x54, depth 8, groups of 4, threshold 0.05, cap 1):
+ *     15 % of the pixels of the finished image have an actual error above the threshold, 1.6 % above twice the threshold.
+ *   - Every round SYNCHRONISES: above and m are read back (8 bytes) before the group is launched, because the list's length decides
+ *     the launches.  A fixed-fraction round does not.
+ * Out of scope: pt_group_*, longer groups for short lists, and a threshold relative to the pixel's brightness (simulated: worse than
+ * uniform sampling at loose thresholds, the brightness of 8 samples being too noisy to normalise by). */
+/* One round: key, select, read back, render, merge.  Refuses what pt_adaptive_round refuses, in the same order (max_fraction for
+ * fraction), then a threshold that is negative or not finite; a refusal allocates and launches nothing.  The first call enters the
+ * adaptive state even if it selects nothing.  m == 0: nothing is rendered or merged, no round is counted, SSE_est stays.  Otherwise
+ * the first m entries of the list are rendered and merged and PtStats.samples grows by group_iters * m.  *above, *selected (either
+ * may be NULL): the two counts. */
+int pt_adaptive_round_threshold(int iter_first, int group_iters, float threshold, float max_fraction, int* above, int* selected);
+/* The driver: while fewer than 2 groups are folded, uniform groups with a fold each exactly as pt_render_adaptive; then threshold
+ * rounds.  Stops BEFORE rendering when above <= min_pixels (>= 0; the tail of short lists is mostly fixed cost), or when max_iters
+ * iteration numbers are used up (the last group is cut).  group_iters == 0: the iterations per batch of a worker for cap pixels.
+ * *iters_done: iteration numbers used; *samples_done: pixel-samples rendered by this call; *above_left: the last count, -1 when no
+ * selection ran (any may be NULL).  pt_get_noise, pt_resolve, pt_readback_adaptive and pt_denoise_adaptive work afterwards as in any
+ * adaptive state. */
+int pt_render_threshold(int iter_first, int max_iters, int group_iters, float threshold, float max_fraction, int min_pixels, int* iters_done,
+                        int64_t* samples_done, int* above_left);
+/* The selection by threshold on the host (no GPU): pt_adaptive_select_host's arrays, 1 <= cap <= w*rows; list (cap entries) receives
+ * *m tile indices, *above the count.  The device's list and counts equal it. */
+int pt_adaptive_select_threshold_host(int w, int rows, const float* noise_planes, const int32_t* counts, float threshold, int cap, int32_t* list,
+                                      int* above, int* m);
 
 /* ---- variance-guided filter with per-pixel sample counts: pt_denoise_guided for an adaptively sampled image.  Valid in both states;
  * in the uniform state every pixel has the fold's (T, M), exactly as pt_readback_adaptive reports them.  Everything not stated here
@@ -631,6 +675,9 @@ int pt_ctx_adaptive_round(PtContext* c, int iter_first, int group_iters, float f
 int pt_ctx_render_adaptive(PtContext* c, int iter_first, int max_iters, int group_iters, float fraction, float target_db, int* iters_done,
                            int64_t* samples_done, float* psnr_db);
 int pt_ctx_readback_adaptive(PtContext* c, int32_t* counts);
+int pt_ctx_adaptive_round_threshold(PtContext* c, int iter_first, int group_iters, float threshold, float max_fraction, int* above, int* selected);
+int pt_ctx_render_threshold(PtContext* c, int iter_first, int max_iters, int group_iters, float threshold, float max_fraction, int min_pixels,
+                            int* iters_done, int64_t* samples_done, int* above_left);
 int pt_ctx_resolve(PtContext* c, float* rgb_avg_host);
 /* Asynchronous on the context's stream; *rgb_dev (pixel_count * 3 floats, owned by the context, allocated by the first resolve) stays
  * valid until the next resolve: where a later filter of the resolved image can start from. */
@@ -746,6 +793,12 @@ int pt_stage_adaptive_select(int w, int rows, const float* noise_planes, const i
  * (distinct, in any order) — rgb_sum_host receives their group sum, m * 3 floats in list order: bit for bit the listed rows of what
  * pt_render adds to the image for the same iterations.  Changes neither the image nor the folds nor the state of the renderer. */
 int pt_stage_render_list(const int32_t* list, int m, int iter_first, int iter_count, float* rgb_sum_host);
+/* pt_stage_render_list on a worker planned for `capacity` >= m pixels (pt_adaptive_round_threshold's): the worker is kept across
+ * calls while the capacity is equal, so calls with different m run one set of buffers under different live plans. */
+int pt_stage_render_list_capacity(const int32_t* list, int m, int capacity, int iter_first, int iter_count, float* rgb_sum_host);
+/* The threshold selection's kernels on caller-supplied host arrays (pt_adaptive_select_threshold_host's arguments; rows < 32768). */
+int pt_stage_adaptive_select_threshold(int w, int rows, const float* noise_planes, const int32_t* counts, float threshold, int cap, int32_t* list,
+                                       int* above, int* m);
 
 /* ---- image output (src/image.cpp:22-45, src/main.cpp:86-107) ------------- */
 /* rgb_sum: W*H*3 floats (raw orientation); writes <path> as 8-bit PNG of
