@@ -260,6 +260,22 @@ def lib() -> C.CDLL:
         L.pt_stage_denoise_adaptive.argtypes = _dn_adaptive + [_fp]
         L.pt_denoise_adaptive_host.argtypes = _dn_adaptive + [_fp]
         L.pt_denoise_adaptive_variance_host.argtypes = _dn_adaptive + [_fp, _fp]
+    if hasattr(L, "pt_group_adaptive_round_threshold"):  # absent from older A/B builds of the library (tools/build_rev.sh)
+        _i64p = C.POINTER(C.c_int64)
+        _dno = C.POINTER(PtDenoiseOptions)
+        _partition = [C.c_int, C.c_int, C.c_int, _ip, C.c_int, _ip, _ip]
+        L.pt_adaptive_round_list.argtypes = [C.c_int, C.c_int, _ip, C.c_int, C.c_int]
+        L.pt_ctx_adaptive_round_list.argtypes = [C.c_void_p, C.c_int, C.c_int, _ip, C.c_int, C.c_int]
+        L.pt_ctx_adaptive_round_list_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]
+        L.pt_ctx_device_counts.argtypes = [C.c_void_p]
+        L.pt_ctx_device_counts.restype = C.c_void_p
+        L.pt_group_adaptive_round_threshold.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, _ip, _ip]
+        L.pt_group_render_threshold.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _ip, _i64p, _ip]
+        L.pt_group_gather_adaptive.argtypes = [C.c_void_p, _ip]
+        L.pt_group_resolve.argtypes = [C.c_void_p, _fp]
+        L.pt_group_denoise_adaptive.argtypes = [C.c_void_p, _dno, _fp]
+        L.pt_group_partition_host.argtypes = _partition
+        L.pt_stage_group_partition.argtypes = _partition
     _lib = L
     return L
 
@@ -597,6 +613,26 @@ def stage_adaptive_select_threshold(noise_planes: np.ndarray, counts: np.ndarray
     return _select_threshold(lib().pt_stage_adaptive_select_threshold, noise_planes, counts, w, rows, threshold, cap)
 
 
+def _group_partition(call, pixel_list, w: int, h: int, n: int):
+    lst = np.ascontiguousarray(pixel_list, np.int32).reshape(-1)
+    parts = np.full(max(lst.size, 1), -1, np.int32)
+    counts = np.full(max(int(n), 1), -1, np.int32)
+    _check(call(int(w), int(h), int(n), _i(lst), lst.size, _i(parts), _i(counts)))
+    ends = np.cumsum(counts)
+    return [parts[e - c:e].copy() for c, e in zip(counts, ends)], counts
+
+
+def group_partition_host(pixel_list: np.ndarray, w: int, h: int, n: int):
+    """A frame's pixel list (ascending frame indices of a frame w x h) cut for the n contexts of a group (pt_group_partition_host; no
+    GPU): ([part 0, ..., part n-1] as int32 tile indices, their lengths int32 [n])."""
+    return _group_partition(lib().pt_group_partition_host, pixel_list, w, h, n)
+
+
+def stage_group_partition(pixel_list: np.ndarray, w: int, h: int, n: int):
+    """group_partition_host's arguments through the partition's kernels (pt_stage_group_partition; needs a Renderer)."""
+    return _group_partition(lib().pt_stage_group_partition, pixel_list, w, h, n)
+
+
 def _noise(call, *handle) -> dict:
     sse, groups, iters = C.c_double(-1.0), C.c_int32(0), C.c_int32(0)
     _check(call(*handle, C.byref(sse), C.byref(groups), C.byref(iters)))
@@ -745,6 +781,13 @@ class Renderer:
         _check(lib().pt_render_threshold(int(iter_first), int(max_iters), int(group_iters), C.c_float(threshold), C.c_float(max_fraction), int(min_pixels),
                                          C.byref(done), C.byref(samples), C.byref(above)))
         return int(done.value), int(samples.value), int(above.value)
+
+    def adaptive_round_list(self, iter_first: int, group_iters: int, pixel_list: np.ndarray, capacity: int) -> None:
+        """One round over the caller's list (pt_adaptive_round_list): distinct tile indices in ascending order, at most `capacity`, on
+        the worker kept for `capacity` pixels; any tile, striped ones included.  Asynchronous."""
+        lst = np.ascontiguousarray(pixel_list, np.int32).reshape(-1)
+        self._round_list = lst  # (the upload is queued on the renderer's stream)
+        _check(lib().pt_adaptive_round_list(int(iter_first), int(group_iters), _i(lst), lst.size, int(capacity)))
 
     def readback_adaptive(self) -> np.ndarray:
         """The per-pixel counts int32 [n, 2]: iterations T_p, groups M_p."""
@@ -938,6 +981,48 @@ class Group:
     def render_until(self, iter_first: int, max_iters: int, target_db: float, group_iters: int = 0):
         """Renderer.render_until of the whole frame (pt_group_render_until); the PSNR is taken over W*H pixels."""
         return _render_until(lib().pt_group_render_until, (self._h,), iter_first, max_iters, group_iters, target_db)
+
+    # ---- adaptive sampling by threshold across the group (include/pt_amd.h: pt_group_adaptive_round_threshold) ----
+    def adaptive_round_threshold(self, iter_first: int, group_iters: int, threshold: float, max_fraction: float = 1.0):
+        """Renderer.adaptive_round_threshold of the whole frame (pt_group_adaptive_round_threshold): (pixels above, pixels rendered)."""
+        above, selected = C.c_int32(-1), C.c_int32(-1)
+        _check(lib().pt_group_adaptive_round_threshold(self._h, int(iter_first), int(group_iters), C.c_float(threshold), C.c_float(max_fraction),
+                                                       C.byref(above), C.byref(selected)))
+        return int(above.value), int(selected.value)
+
+    def render_threshold(self, iter_first: int, max_iters: int, threshold: float, max_fraction: float = 0.25, group_iters: int = 0,
+                         min_pixels: int = 0):
+        """Renderer.render_threshold of the whole frame (pt_group_render_threshold); group_iters 0 = the first context's batch."""
+        done, samples, above = C.c_int32(0), C.c_int64(0), C.c_int32(-1)
+        _check(lib().pt_group_render_threshold(self._h, int(iter_first), int(max_iters), int(group_iters), C.c_float(threshold), C.c_float(max_fraction),
+                                               int(min_pixels), C.byref(done), C.byref(samples), C.byref(above)))
+        return int(done.value), int(samples.value), int(above.value)
+
+    def gather_adaptive(self) -> np.ndarray:
+        """The per-pixel counts of the whole frame int32 [W*H, 2] (pt_group_gather_adaptive), raw orientation."""
+        w, h = self.scene.resolution
+        out = np.empty((w * h, 2), np.int32)
+        _check(lib().pt_group_gather_adaptive(self._h, _i(out)))
+        return out
+
+    def resolve(self) -> np.ndarray:
+        """Renderer.resolve of the whole frame (pt_group_resolve): float32 [W*H, 3], raw orientation."""
+        w, h = self.scene.resolution
+        out = np.empty((w * h, 3), np.float32)
+        _check(lib().pt_group_resolve(self._h, _f(out)))
+        return out
+
+    def denoise_adaptive(self, **opts) -> np.ndarray:
+        """Renderer.denoise_adaptive of the whole frame (pt_group_denoise_adaptive): float32 [W*H, 3], raw orientation."""
+        w, h = self.scene.resolution
+        out = np.empty((w * h, 3), np.float32)
+        opt = denoise_options(**opts)
+        _check(lib().pt_group_denoise_adaptive(self._h, C.byref(opt), _f(out)))
+        return out
+
+    def context(self, i: int) -> int:
+        """The handle of context i for the pt_ctx_* functions (pt_group_context)."""
+        return lib().pt_group_context(self._h, int(i))
 
     def gather_u8(self, samples: float) -> np.ndarray:
         w, h = self.scene.resolution

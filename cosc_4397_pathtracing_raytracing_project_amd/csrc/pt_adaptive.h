@@ -28,9 +28,10 @@ PT_HD uint32_t key_bits(float key) {
 }
 
 // The selection key of pixel (x, y) of a tile of W x R pixels: the 3x3 binomial prefilter of the per-sample variance s = w * T,
-// back in the unit of w.  plane0 = the first noise plane.
-template <typename P4>
-PT_HD uint32_t key_pixel(int x, int y, int W, int R, const P4* plane0, const Cnt* cnt) {
+// back in the unit of w.  plane0 = the first noise plane (any type with a float member w), cnt = the count plane (any type with an
+// int32 member T: pt_group_select.h reads both from one packed plane).
+template <typename P4, typename C>
+PT_HD uint32_t key_pixel(int x, int y, int W, int R, const P4* plane0, const C* cnt) {
 #pragma clang fp contract(off)
   float num = 0.0f, den = 0.0f;
   for (int j = -1; j <= 1; ++j) {

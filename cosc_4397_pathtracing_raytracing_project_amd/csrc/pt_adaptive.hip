@@ -314,16 +314,18 @@ int pt_adaptive_init_counts_launch(hipStream_t stream, int pixels, void* counts_
 }
 
 // The selection's launches; thr == nullptr: the top m, else the pixels above *thr, the `m` with the largest keys at the most.
+// noise_dev == nullptr: the keys are in the workspace already (pt_adaptive_select_keys), and nothing else of the pixels is read.
 static int select_launches(const char* who, hipStream_t stream, int w, int rows, const float* noise_dev, const void* counts_dev, int m, const uint32_t* thr,
                            void* workspace_dev, int32_t* list_dev) {
   const size_t npix = (size_t)w * rows;
-  if (w <= 0 || rows <= 0 || npix > ((size_t)1 << 30) || m < 1 || (size_t)m > npix || !noise_dev || !counts_dev || !workspace_dev || !list_dev)
+  if (w <= 0 || rows <= 0 || npix > ((size_t)1 << 30) || m < 1 || (size_t)m > npix || !noise_dev != !counts_dev || !workspace_dev || !list_dev)
     return pt_fail("%s: bad argument", who);
   const Workspace ws = carve(workspace_dev, npix);
   const unsigned blocks = blocks_of(npix, kPerBlock);
   if (hipMemsetAsync(ws.hist, 0, 4 * 3 * kBins + sizeof(Sel), stream) != hipSuccess) return pt_fail("%s: hipMemsetAsync failed", who);
-  hipLaunchKernelGGL(k_adaptive_key, dim3(blocks_of(npix, kBlock)), dim3(kBlock), 0, stream, w, rows, reinterpret_cast<const V4*>(noise_dev),
-                     static_cast<const Cnt*>(counts_dev), ws.key);
+  if (noise_dev)
+    hipLaunchKernelGGL(k_adaptive_key, dim3(blocks_of(npix, kBlock)), dim3(kBlock), 0, stream, w, rows, reinterpret_cast<const V4*>(noise_dev),
+                       static_cast<const Cnt*>(counts_dev), ws.key);
   for (int pass = 0; pass < 3; ++pass) {
     hipLaunchKernelGGL(k_adaptive_hist, dim3(blocks), dim3(kBlock), 0, stream, npix, ws.key, ws.sel, pass, ws.hist + pass * kBins);
     hipLaunchKernelGGL(k_adaptive_pick, dim3(1), dim3(kBlock), 0, stream, ws.hist + pass * kBins, ws.sel, pass, (uint32_t)m);
@@ -349,6 +351,14 @@ int pt_adaptive_select_threshold_launch(hipStream_t stream, int w, int rows, con
   const uint32_t thr = ptad::threshold_bits(threshold);
   return select_launches("pt_adaptive_select_threshold", stream, w, rows, noise_dev, counts_dev, cap, &thr, workspace_dev, list_dev);
 }
+
+int pt_adaptive_select_threshold_keys_launch(hipStream_t stream, int w, int rows, float threshold, int cap, void* workspace_dev, int32_t* list_dev) {
+  if (!std::isfinite(threshold) || threshold < 0.0f) return pt_fail("pt_adaptive_select_threshold: bad argument");
+  const uint32_t thr = ptad::threshold_bits(threshold);
+  return select_launches("pt_adaptive_select_threshold", stream, w, rows, nullptr, nullptr, cap, &thr, workspace_dev, list_dev);
+}
+
+uint32_t* pt_adaptive_select_keys(void* workspace_dev, size_t pixels) { return carve(workspace_dev, pixels).key; }
 
 const uint32_t* pt_adaptive_select_result(const void* workspace_dev, size_t pixels) { return &carve(const_cast<void*>(workspace_dev), pixels).sel->above; }
 

@@ -932,6 +932,9 @@ int pt_render_threshold(int iter_first, int max_iters, int group_iters, float th
                         int64_t* samples_done, int* above_left) {
   return pt_ctx_render_threshold(g_default, iter_first, max_iters, group_iters, threshold, max_fraction, min_pixels, iters_done, samples_done, above_left);
 }
+int pt_adaptive_round_list(int iter_first, int group_iters, const int32_t* list_host, int m, int capacity) {
+  return pt_ctx_adaptive_round_list(g_default, iter_first, group_iters, list_host, m, capacity);
+}
 int pt_resolve(float* rgb_avg_host) { return pt_ctx_resolve(g_default, rgb_avg_host); }
 int pt_set_reference(const float* rgb_avg_host) { return pt_ctx_set_reference(g_default, rgb_avg_host); }
 int pt_get_convergence(int iter_first, int iter_count, double* sse) { return pt_ctx_get_convergence(g_default, iter_first, iter_count, sse); }

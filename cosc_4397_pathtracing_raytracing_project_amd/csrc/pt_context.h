@@ -123,10 +123,11 @@ struct PtContext : PtShared {
   // until pt_stage_render_list)
   int opt_iters_per_batch = 0, opt_num_queues = 0;  // PtOptions, as given: a worker plans its own batches from them
   bool borrowed = false;           // a worker context: what PtShared holds belongs to its parent
-  const int32_t* list = nullptr;   // BatchInfo::list of this context's batches (a worker's: the parent's d_list)
+  const int32_t* list = nullptr;   // BatchInfo::list of this context's batches (a worker's: the parent's d_list, or its d_list_frame)
   PtContext* worker = nullptr;     // the context that renders the pixel list; its tile is the list's m pixels, its d_image the group sum Sw
   int capacity = 0;                // a worker: the pixels it was planned and allocated for; its N is the LIVE list length, <= capacity
   int32_t* d_list = nullptr;       // N entries, the first worker->N in use
+  int32_t* d_list_frame = nullptr; // a striped tile: the same entries as offsets in the frame, what the worker's batches read (pt_adaptive_round_list)
   void* d_acnt = nullptr;          // the plane cnt: N * ptad::Cnt
   void* d_select = nullptr;        // pt_adaptive_select_bytes(N)
   float* d_resolved = nullptr;     // [N][3], output of pt_ctx_resolve_device; absent until the first resolve
@@ -134,6 +135,21 @@ struct PtContext : PtShared {
   int adaptive_rounds = 0;
   int64_t adaptive_last = 0;       // highest iteration number folded or merged
 };
+
+// What a group (pt_group.cpp) asks of its contexts beyond the C ABI; C++ linkage, so none of it is exported under a plain name.
+struct PtCtxState {
+  bool adaptive;     // in the adaptive state
+  int groups;        // M: groups folded
+  int64_t iters;     // T: iterations those folds took
+  int64_t unfolded;  // iterations rendered since the last fold
+};
+PtCtxState pt_ctx_state(const PtContext* c);
+// the refusal, under the name `who`, of a context whose batch failed half-way, and (uniform) of one in the adaptive state
+int pt_ctx_admit_state(const PtContext* c, const char* who, bool uniform);
+// What pt_adaptive_round_threshold refuses before its threshold, in its order and under the name `who`, apart from a tile that is not
+// whole contiguous rows; folds == false: apart from the state of the folds too (pt_render_threshold's first look).
+int pt_ctx_adaptive_refusal(const PtContext* c, const char* who, int iter_first, int group_iters, float max_fraction, bool folds);
+int pt_ctx_enter_adaptive(PtContext* c);  // the count plane with the fold's (T, M) in every pixel, unless the context is in the adaptive state already
 
 namespace ptc {
 using Ctx = PtContext;

@@ -27,8 +27,10 @@
 #include <string>
 #include <vector>
 
-#include "pt_context.h"  // HIP_OK; a group reaches its contexts through the C ABI only
+#include "pt_adaptive.h"
+#include "pt_context.h"  // HIP_OK; a group reaches its contexts through the C ABI and the helpers declared there
 #include "pt_denoise.h"
+#include "pt_group_select.h"
 #define NCCL_OK(expr)                                                                                      \
   do {                                                                                                     \
     ncclResult_t r_ = (expr);                                                                              \
@@ -56,6 +58,18 @@ struct PtGroup {
   float* d_full_feat = nullptr;
   float* d_full_noise = nullptr;  // root: the assembled noise planes (pt_group_denoise_guided; the receive buffer is d_recv_feat)
   void* d_denoise = nullptr;  // root: workspace of pt_group_denoise over the whole frame
+  // Adaptive sampling by threshold (pt_group_adaptive_round_threshold); all of it absent until the first round (the pair buffers: or
+  // until the first write-out of the count planes)
+  std::vector<void*> d_pack;       // per context, on its device: {w_p, T_p} of its tile, 8 B per pixel
+  std::vector<int32_t*> d_part;    // per context i >= 1, on its device: its part of the frame's list
+  int32_t* d_recv_pair = nullptr;  // root: 8 B per pixel of the tiles of devices 1..n-1 (the packed pairs; the count planes at write-out)
+  int32_t* d_full_pair = nullptr;  // root: the same of the assembled frame
+  void* d_select = nullptr;        // root: the selection's workspace for W*H pixels (pt_adaptive_select_bytes)
+  void* d_partition = nullptr;     // root: the partition's workspace (pt_group_partition_bytes)
+  int32_t* d_list = nullptr;       // root: the frame's list, W*H entries, the first m in use
+  int32_t* d_parts = nullptr;      // root: the contexts' lists back to back
+  uint32_t* d_result = nullptr;    // root: above, m, m_0 .. m_(n-1)
+  hipEvent_t parts_ready = nullptr;  // root: the parts are complete (recorded on the root's stream)
 };
 
 namespace {
@@ -74,8 +88,15 @@ void release(PtGroup* g) {
     }
   if (!g->devices.empty()) (void)hipSetDevice(g->devices[0]);
   for (void* p : {(void*)g->d_recv, (void*)g->d_full, (void*)g->d_recv8, (void*)g->d_full8, (void*)g->d_recv_prev,
-                  (void*)g->d_full_prev, (void*)g->d_recv_feat, (void*)g->d_full_feat, (void*)g->d_full_noise, g->d_denoise})
+                  (void*)g->d_full_prev, (void*)g->d_recv_feat, (void*)g->d_full_feat, (void*)g->d_full_noise, g->d_denoise, (void*)g->d_recv_pair,
+                  (void*)g->d_full_pair, g->d_select, g->d_partition, (void*)g->d_list, (void*)g->d_parts, (void*)g->d_result})
     if (p) (void)hipFree(p);
+  if (g->parts_ready) (void)hipEventDestroy(g->parts_ready);
+  for (size_t i = 0; i < g->d_pack.size() || i < g->d_part.size(); ++i) {
+    (void)hipSetDevice(g->devices[i]);
+    if (i < g->d_pack.size() && g->d_pack[i]) (void)hipFree(g->d_pack[i]);
+    if (i < g->d_part.size() && g->d_part[i]) (void)hipFree(g->d_part[i]);
+  }
   for (size_t i = 0; i < g->d_prev.size(); ++i)
     if (g->d_prev[i]) {
       (void)hipSetDevice(g->devices[i]);
@@ -186,6 +207,150 @@ int assemble_features(PtGroup* g) {  // -> g->d_full_feat: PT_FEATURE_PLANES pla
 }
 int assemble_noise(PtGroup* g) {  // -> g->d_full_noise: PT_NOISE_PLANES planes of W*H float4
   return assemble_planes(g, PT_NOISE_PLANES, &g->d_full_noise, [](PtContext* c) { return pt_ctx_device_noise(c); });
+}
+
+// 8 bytes per pixel of every context (the packed pairs of a round, the count planes at write-out) -> g->d_full_pair: the frame's
+int assemble_pairs(PtGroup* g, const std::vector<const int32_t*>& tiles) {
+  const size_t frame = (size_t)g->W * g->H;
+  HIP_OK(hipSetDevice(g->devices[0]));
+  if (!g->d_full_pair) HIP_OK(hipMalloc((void**)&g->d_full_pair, frame * 8));
+  if (!g->d_recv_pair) HIP_OK(hipMalloc((void**)&g->d_recv_pair, g->recv_pixels * 8));
+  if (exchange(g, ncclInt32, 2, g->d_recv_pair, [&](int i) { return tiles[i]; })) return fail_after_drain(g);
+  HIP_OK(hipSetDevice(g->devices[0]));
+  for (int i = 0; i < g->n; ++i)
+    if (place_rows(g, i, i == 0 ? tiles[0] : g->d_recv_pair + 2 * g->recv_off[i], g->d_full_pair, 8)) return fail_after_drain(g);
+  return 0;
+}
+
+// The contexts of a group share the fold counters M and T and the state they are in (pt_group_noise_fold and the group's rounds keep
+// them so; pt_group_context lets a caller break it): the first context that differs from context 0 is the refusal.
+int shared_state(PtGroup* g, const char* who, PtCtxState* out) {
+  const PtCtxState s0 = pt_ctx_state(g->ctx[0]);
+  for (int i = 1; i < g->n; ++i) {
+    const PtCtxState s = pt_ctx_state(g->ctx[i]);
+    if (s.groups != s0.groups || s.iters != s0.iters)
+      return pt_fail("%s: context %d folded %d groups of %lld iterations, context 0 %d of %lld; the contexts of a group share them", who, i, s.groups,
+                     (long long)s.iters, s0.groups, (long long)s0.iters);
+    if (s.adaptive != s0.adaptive)
+      return pt_fail("%s: context %d is %s the adaptive state, context 0 %s it; the contexts of a group share it", who, i, s.adaptive ? "in" : "out of",
+                     s0.adaptive ? "in" : "out of");
+  }
+  *out = s0;
+  return 0;
+}
+
+// One round of pt_group_adaptive_round_threshold for n > 1, after the arguments' refusals; the driver's min_pixels as in the context's round.
+//
+// Buffer order.  The root writes d_list and d_parts on its own stream; context i reads its part on ITS stream.
+//   COPY: context i's copy out of d_parts waits for parts_ready, recorded on the root's stream behind the partition.  The next
+//         round's pack exchange has the root's stream wait for ready[i], recorded on context i's stream behind that copy (and behind the
+//         render and merge that follow it), before the root selects and partitions again: the parts are never overwritten early.
+//   RCCL: the sends of the parts are on the root's stream like the partition before them and the next round's selection after them.
+//         Context i receives into its own d_part[i] on its stream, which also copies it into the context's list; the next receive
+//         into d_part[i] is behind that copy in stream order.
+// Either way the root's host thread has synchronised the root's stream in between (the read-back), and d_pack[i] is written by
+// context i's stream only after the exchange that read it: COPY through that synchronise, RCCL because the send is on that stream.
+int group_round(PtGroup* g, const char* who, int iter_first, int group_iters, float threshold, float max_fraction, int min_pixels, int* above, int* selected) {
+  const int n = g->n, W = g->W, H = g->H;
+  const size_t frame = (size_t)W * H;
+  for (int i = 0; i < n; ++i)
+    if (pt_ctx_adaptive_refusal(g->ctx[i], who, iter_first, group_iters, max_fraction, true)) return -1;
+  if (pt_adaptive_check_threshold(who, threshold)) return -1;
+  if (n > ptgs::kMaxParts || H >= 32768 || frame > ((size_t)1 << 30))
+    return pt_fail("%s: %d contexts on a frame of %d x %d: at most %d contexts, fewer than 32768 rows, at most 2^30 pixels", who, n, W, H, ptgs::kMaxParts);
+  PtCtxState shared{};
+  if (shared_state(g, who, &shared)) return -1;
+  const int cap = ptad::list_length((double)max_fraction, (int64_t)frame);
+  hipStream_t root = (hipStream_t)pt_ctx_stream(g->ctx[0]);
+
+  // the group's buffers: the first round
+  HIP_OK(hipSetDevice(g->devices[0]));
+  if (!g->d_select) HIP_OK(hipMalloc(&g->d_select, pt_adaptive_select_bytes(frame)));
+  if (!g->d_partition) HIP_OK(hipMalloc(&g->d_partition, pt_group_partition_bytes(frame, n)));
+  if (!g->d_list) HIP_OK(hipMalloc((void**)&g->d_list, frame * sizeof(int32_t)));
+  if (!g->d_parts) HIP_OK(hipMalloc((void**)&g->d_parts, frame * sizeof(int32_t)));
+  if (!g->d_result) HIP_OK(hipMalloc((void**)&g->d_result, (2 + (size_t)n) * sizeof(uint32_t)));
+  if (!g->parts_ready) HIP_OK(hipEventCreateWithFlags(&g->parts_ready, hipEventDisableTiming));
+  if (g->d_pack.empty()) g->d_pack.assign(n, nullptr), g->d_part.assign(n, nullptr);
+  for (int i = 0; i < n; ++i) {
+    const size_t pixels = (size_t)pt_ctx_pixel_count(g->ctx[i]);
+    HIP_OK(hipSetDevice(g->devices[i]));
+    if (!g->d_pack[i]) HIP_OK(hipMalloc(&g->d_pack[i], pixels * 8));
+    if (i >= 1 && !g->d_part[i]) HIP_OK(hipMalloc((void**)&g->d_part[i], pixels * sizeof(int32_t)));
+  }
+
+  // collect on the root: every context packs on its own stream, one exchange, the rows into the frame, key, select, partition
+  std::vector<const int32_t*> tiles(n, nullptr);
+  for (int i = 0; i < n; ++i) {
+    if (pt_ctx_enter_adaptive(g->ctx[i])) return -1;
+    HIP_OK(hipSetDevice(g->devices[i]));
+    if (pt_group_pack_launch((hipStream_t)pt_ctx_stream(g->ctx[i]), pt_ctx_pixel_count(g->ctx[i]), pt_ctx_device_noise(g->ctx[i]),
+                             pt_ctx_device_counts(g->ctx[i]), g->d_pack[i]))
+      return -1;
+    tiles[i] = static_cast<const int32_t*>(g->d_pack[i]);
+  }
+  if (assemble_pairs(g, tiles)) return -1;
+  if (pt_group_keys_launch(root, W, H, g->d_full_pair, pt_adaptive_select_keys(g->d_select, frame)) ||
+      pt_adaptive_select_threshold_keys_launch(root, W, H, threshold, cap, g->d_select, g->d_list) ||
+      pt_group_partition_launch(root, W, n, g->d_list, pt_adaptive_select_result(g->d_select, frame), cap, g->d_partition, g->d_parts, g->d_result))
+    return fail_after_drain(g);
+
+  // read back: above, m and the parts' lengths, 8 + 4n bytes and ONE synchronise
+  std::vector<uint32_t> result(2 + (size_t)n, 0u);
+  HIP_OK(hipMemcpyAsync(result.data(), g->d_result, result.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, root));
+  HIP_OK(hipStreamSynchronize(root));
+  const int m = (int)result[1];
+  int64_t sum = 0;
+  for (int i = 0; i < n; ++i) sum += result[2 + (size_t)i];
+  bool fits = m >= 0 && m <= cap && (int)result[0] >= m && sum == m;
+  for (int i = 0; i < n && fits; ++i) fits = (int64_t)result[2 + (size_t)i] <= pt_ctx_pixel_count(g->ctx[i]);
+  if (!fits) return pt_fail("%s: the selection left %u above, a list of %u (cap %d) in parts that add up to %lld", who, result[0], result[1], cap, (long long)sum);
+  const bool render = m > 0 && (int)result[0] > min_pixels;
+  if (above) *above = (int)result[0];
+  if (selected) *selected = render ? m : 0;
+  if (!render) return 0;  // nothing rendered or merged, no context counts a round
+
+  // distribute and render: part i to context i, on context i's stream
+  HIP_OK(hipEventRecord(g->parts_ready, root));
+  std::vector<const int32_t*> lists(n, nullptr);
+  std::vector<size_t> off(n, 0);
+  for (int i = 1; i < n; ++i) off[i] = off[i - 1] + result[2 + (size_t)i - 1];
+  lists[0] = g->d_parts;
+  if (g->transport == PT_GROUP_TRANSPORT_COPY) {
+    for (int i = 1; i < n; ++i) {
+      hipStream_t si = (hipStream_t)pt_ctx_stream(g->ctx[i]);
+      const size_t bytes = (size_t)result[2 + (size_t)i] * sizeof(int32_t);
+      HIP_OK(hipSetDevice(g->devices[i]));
+      HIP_OK(hipStreamWaitEvent(si, g->parts_ready, 0));
+      if (bytes && g->devices[i] == g->devices[0]) HIP_OK(hipMemcpyAsync(g->d_part[i], g->d_parts + off[i], bytes, hipMemcpyDeviceToDevice, si));
+      else if (bytes) HIP_OK(hipMemcpyPeerAsync(g->d_part[i], g->devices[i], g->d_parts + off[i], g->devices[0], bytes, si));
+      lists[i] = g->d_part[i];
+    }
+  } else {
+    NCCL_OK(ncclGroupStart());
+    int rc = 0;
+    for (int i = 1; i < n && !rc; ++i) {  // an error inside the group must still close it
+      const size_t count = result[2 + (size_t)i];
+      lists[i] = g->d_part[i];
+      if (!count) continue;
+      ncclResult_t r = ncclSuccess;
+      if (hipSetDevice(g->devices[0]) != hipSuccess) rc = pt_fail("hipSetDevice(%d) failed", g->devices[0]);
+      else if ((r = ncclSend(g->d_parts + off[i], count, ncclInt32, i, g->comms[0], root)) != ncclSuccess)
+        rc = pt_fail("ncclSend to device %d failed: %s", g->devices[i], ncclGetErrorString(r));
+      else if (hipSetDevice(g->devices[i]) != hipSuccess) rc = pt_fail("hipSetDevice(%d) failed", g->devices[i]);
+      else if ((r = ncclRecv(g->d_part[i], count, ncclInt32, 0, g->comms[i], (hipStream_t)pt_ctx_stream(g->ctx[i]))) != ncclSuccess)
+        rc = pt_fail("ncclRecv on device %d failed: %s", g->devices[i], ncclGetErrorString(r));
+    }
+    const ncclResult_t e = ncclGroupEnd();
+    if (!rc && e != ncclSuccess) rc = pt_fail("ncclGroupEnd failed: %s", ncclGetErrorString(e));
+    if (rc) return fail_after_drain(g);
+  }
+  for (int i = 0; i < n; ++i) {  // asynchronous: the contexts render concurrently; a context without pixels counts the round
+    const int pixels = pt_ctx_pixel_count(g->ctx[i]);
+    if (pt_ctx_adaptive_round_list_device(g->ctx[i], iter_first, group_iters, lists[i], (int)result[2 + (size_t)i], cap < pixels ? cap : pixels))
+      return fail_after_drain(g);
+  }
+  return 0;
 }
 
 }  // namespace
@@ -315,6 +480,8 @@ int pt_group_denoise(PtGroup* g, float samples, const PtDenoiseOptions* opt, flo
   if (!g || !rgb_avg_host) return pt_fail("pt_group_denoise: bad argument");
   if (g->n == 1) return pt_ctx_denoise(g->ctx[0], samples, opt, rgb_avg_host);
   const size_t frame = (size_t)g->W * g->H;
+  for (PtContext* c : g->ctx)  // (a group's rounds bring its contexts into the adaptive state: one sample count no longer describes the image)
+    if (pt_ctx_admit_state(c, "pt_group_denoise", true)) return -1;
   if (need_features(g, "pt_group_denoise")) return -1;
   ptdn::Params P{};
   if (pt_denoise_resolve("pt_group_denoise", samples, opt, &P)) return -1;
@@ -334,6 +501,8 @@ int pt_group_denoise_guided(PtGroup* g, const PtDenoiseOptions* opt, float* rgb_
   if (!g || !rgb_avg_host) return pt_fail("pt_group_denoise_guided: bad argument");
   if (g->n == 1) return pt_ctx_denoise_guided(g->ctx[0], opt, rgb_avg_host);
   const size_t frame = (size_t)g->W * g->H;
+  for (PtContext* c : g->ctx)
+    if (pt_ctx_admit_state(c, "pt_group_denoise_guided", true)) return -1;
   if (need_features(g, "pt_group_denoise_guided")) return -1;
   int groups = 0, iters = 0;
   for (int i = 0; i < g->n; ++i) {
@@ -405,6 +574,136 @@ int pt_group_render_until(PtGroup* g, int iter_first, int max_iters, int group_i
   if (iters_done) *iters_done = done;
   if (psnr_db) *psnr_db = psnr;
   return 0;
+}
+
+// ---- adaptive sampling by threshold across the group: the frame's selection once, on the root; every context renders and merges its
+// own part (group_round above).  Everything a single context would hold after the same calls, the contexts hold between them, bit for bit.
+int pt_group_adaptive_round_threshold(PtGroup* g, int iter_first, int group_iters, float threshold, float max_fraction, int* above, int* selected) {
+  if (!g) return pt_fail("pt_group_adaptive_round_threshold: null group");
+  if (g->n == 1) return pt_ctx_adaptive_round_threshold(g->ctx[0], iter_first, group_iters, threshold, max_fraction, above, selected);
+  return group_round(g, "pt_group_adaptive_round_threshold", iter_first, group_iters, threshold, max_fraction, 0, above, selected);
+}
+
+// pt_ctx_render_threshold's loop over pt_group_render, pt_group_noise_fold and the round above.
+int pt_group_render_threshold(PtGroup* g, int iter_first, int max_iters, int group_iters, float threshold, float max_fraction, int min_pixels,
+                              int* iters_done, int64_t* samples_done, int* above_left) {
+  const char* who = "pt_group_render_threshold";
+  if (!g) return pt_fail("%s: null group", who);
+  if (g->n == 1)
+    return pt_ctx_render_threshold(g->ctx[0], iter_first, max_iters, group_iters, threshold, max_fraction, min_pixels, iters_done, samples_done, above_left);
+  if (max_iters < 1 || (int64_t)iter_first + max_iters - 1 > INT32_MAX || group_iters < 0 || min_pixels < 0)
+    return pt_fail("%s: iterations %d, +%d in groups of %d until at most %d pixels are above: the count is >= 1, the group >= 0 (0 = a batch), the pixels >= 0", who,
+                   iter_first, max_iters, group_iters, min_pixels);
+  // what a round would refuse, apart from the state of the folds, which the uniform groups below establish
+  for (PtContext* c : g->ctx)
+    if (pt_ctx_adaptive_refusal(c, who, iter_first, group_iters, max_fraction, false)) return -1;
+  if (pt_adaptive_check_threshold(who, threshold)) return -1;
+  int group = group_iters;
+  if (!group) {
+    PtStats st;
+    if (pt_ctx_get_stats(g->ctx[0], &st)) return -1;
+    group = st.iters_per_batch;
+  }
+  int done = 0, above = -1;
+  int64_t samples = 0;
+  while (done < max_iters) {
+    const int n = group < max_iters - done ? group : max_iters - done;
+    PtCtxState s{};
+    if (shared_state(g, who, &s)) return -1;
+    if (!s.adaptive && s.groups < 2) {  // a uniform group and its fold
+      if (pt_group_render(g, iter_first + done, n) || pt_group_noise_fold(g)) return -1;
+      samples += (int64_t)n * g->W * g->H;
+    } else {
+      if (!s.adaptive && pt_group_noise_fold(g)) return -1;  // iterations of the caller's, not yet folded (a context without any folds nothing)
+      int m = 0;
+      if (group_round(g, who, iter_first + done, n, threshold, max_fraction, min_pixels, &above, &m)) return -1;
+      if (above <= min_pixels) break;  // nothing was rendered
+      samples += (int64_t)n * m;
+    }
+    done += n;
+  }
+  if (iters_done) *iters_done = done;
+  if (samples_done) *samples_done = samples;
+  if (above_left) *above_left = above;
+  return 0;
+}
+
+// The per-pixel counts of the whole frame: in the adaptive state the count planes meet like a plane of 8 bytes per pixel; in the
+// uniform state every pixel has the shared (T, M), as pt_readback_adaptive reports them.
+int pt_group_gather_adaptive(PtGroup* g, int32_t* counts) {
+  if (!g || !counts) return pt_fail("pt_group_gather_adaptive: bad argument");
+  if (g->n == 1) return pt_ctx_readback_adaptive(g->ctx[0], counts);
+  const size_t frame = (size_t)g->W * g->H;
+  PtCtxState s{};
+  if (shared_state(g, "pt_group_gather_adaptive", &s)) return -1;
+  if (!s.adaptive) {
+    if (pt_group_sync(g)) return -1;
+    for (size_t p = 0; p < frame; ++p) counts[2 * p] = (int32_t)std::min<int64_t>(s.iters, INT32_MAX), counts[2 * p + 1] = s.groups;
+    return 0;
+  }
+  std::vector<const int32_t*> tiles(g->n, nullptr);
+  for (int i = 0; i < g->n; ++i) tiles[i] = pt_ctx_device_counts(g->ctx[i]);
+  if (assemble_pairs(g, tiles)) return -1;
+  HIP_OK(hipMemcpyAsync(counts, g->d_full_pair, frame * 8, hipMemcpyDeviceToHost, (hipStream_t)pt_ctx_stream(g->ctx[0])));
+  return pt_group_sync(g);
+}
+
+// pt_resolve of the whole frame: every context resolves its own rows; the rows meet like the image (and in its buffers).
+int pt_group_resolve(PtGroup* g, float* rgb_avg_host) {
+  if (!g || !rgb_avg_host) return pt_fail("pt_group_resolve: bad argument");
+  if (g->n == 1) return pt_ctx_resolve(g->ctx[0], rgb_avg_host);
+  const size_t frame = (size_t)g->W * g->H;
+  std::vector<const float*> tiles(g->n, nullptr);
+  for (int i = 0; i < g->n; ++i)
+    if (pt_ctx_resolve_device(g->ctx[i], &tiles[i])) return -1;
+  HIP_OK(hipSetDevice(g->devices[0]));
+  if (!g->d_full) HIP_OK(hipMalloc((void**)&g->d_full, frame * 12));
+  if (!g->d_recv) HIP_OK(hipMalloc((void**)&g->d_recv, g->recv_pixels * 12));
+  if (exchange(g, ncclFloat, 3, g->d_recv, [&](int i) { return tiles[i]; })) return fail_after_drain(g);
+  HIP_OK(hipSetDevice(g->devices[0]));
+  for (int i = 0; i < g->n; ++i)
+    if (place_rows(g, i, i == 0 ? tiles[0] : g->d_recv + 3 * g->recv_off[i], g->d_full, 12)) return fail_after_drain(g);
+  HIP_OK(hipMemcpyAsync(rgb_avg_host, g->d_full, frame * 12, hipMemcpyDeviceToHost, (hipStream_t)pt_ctx_stream(g->ctx[0])));
+  return pt_group_sync(g);
+}
+
+// pt_denoise_adaptive of the whole frame: as pt_group_denoise_guided, and in the adaptive state the count planes meet on the root too
+// (the uniform state: the launcher gives every pixel the shared (T, M), as it does for a context).  Refuses what the context's
+// function refuses, in its order, each condition over the contexts in turn.
+int pt_group_denoise_adaptive(PtGroup* g, const PtDenoiseOptions* opt, float* rgb_avg_host) {
+  const char* who = "pt_group_denoise_adaptive";
+  if (!g || !rgb_avg_host) return pt_fail("%s: bad argument", who);
+  if (g->n == 1) return pt_ctx_denoise_adaptive(g->ctx[0], opt, rgb_avg_host);
+  const size_t frame = (size_t)g->W * g->H;
+  for (PtContext* c : g->ctx)
+    if (pt_ctx_admit_state(c, who, false)) return -1;
+  if (need_features(g, who)) return -1;
+  for (PtContext* c : g->ctx)
+    if (!pt_ctx_device_noise(c) || pt_ctx_state(c).groups < 1) return pt_fail("%s: nothing has been folded (pt_group_noise_fold)", who);
+  for (int i = 0; i < g->n; ++i)
+    if (pt_ctx_state(g->ctx[i]).unfolded != 0)
+      return pt_fail("%s: context %d has iterations rendered since its last fold; fold first (pt_group_noise_fold)", who, i);
+  PtCtxState s{};
+  if (shared_state(g, who, &s)) return -1;
+  if (s.groups < 2) return pt_fail("%s: %d group(s) folded; a variance needs at least 2 (pt_group_noise_fold after each group of iterations)", who, s.groups);
+  if (s.iters > INT32_MAX) return pt_fail("%s: %lld iterations folded: the per-pixel counts are int32", who, (long long)s.iters);
+  ptdn::Params P{};
+  if (pt_denoise_adaptive_resolve(who, opt, &P)) return -1;
+  HIP_OK(hipSetDevice(g->devices[0]));
+  if (!g->d_denoise) HIP_OK(hipMalloc(&g->d_denoise, pt_denoise_workspace_bytes(frame)));
+  if (assemble_image(g) || assemble_features(g) || assemble_noise(g)) return -1;
+  if (s.adaptive) {
+    std::vector<const int32_t*> tiles(g->n, nullptr);
+    for (int i = 0; i < g->n; ++i) tiles[i] = pt_ctx_device_counts(g->ctx[i]);
+    if (assemble_pairs(g, tiles)) return -1;
+  }
+  hipStream_t root = (hipStream_t)pt_ctx_stream(g->ctx[0]);
+  const float* d_out = nullptr;
+  if (pt_denoise_adaptive_launch(root, g->W, g->H, g->d_full, g->d_full_feat, g->d_full_noise, s.adaptive ? g->d_full_pair : nullptr, (int)s.iters, s.groups, P,
+                                 g->d_denoise, &d_out))
+    return fail_after_drain(g);
+  HIP_OK(hipMemcpyAsync(rgb_avg_host, d_out, frame * 12, hipMemcpyDeviceToHost, root));
+  return pt_group_sync(g);
 }
 
 int pt_group_gather_u8(PtGroup* g, float samples, uint8_t* rgb8_host) {

@@ -67,6 +67,26 @@ int pt_adaptive_check_threshold(const char* who, float threshold);  // finite an
 int pt_adaptive_select_threshold_launch(hipStream_t stream, int w, int rows, const float* noise_dev, const void* counts_dev, float threshold, int cap,
                                         void* workspace_dev, int32_t* list_dev);
 const uint32_t* pt_adaptive_select_result(const void* workspace_dev, size_t pixels);
+// The same selection from keys that are in the workspace already: pt_adaptive_select_keys names the w*rows words a caller fills on
+// `stream` before the launches (pt_group_select.hip: the keys of a frame whose noise planes lie on several devices).
+uint32_t* pt_adaptive_select_keys(void* workspace_dev, size_t pixels);
+int pt_adaptive_select_threshold_keys_launch(hipStream_t stream, int w, int rows, float threshold, int cap, void* workspace_dev, int32_t* list_dev);
 int pt_adaptive_merge_launch(hipStream_t stream, int pixels, float* rgb_sum_dev, void* noise_state_dev, void* counts_dev, const int32_t* list_dev, int m,
                              const float* group_sum_dev, int group_iters);
 int pt_adaptive_resolve_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, const void* counts_dev, int iters, float* rgb_avg_dev);
+
+// Adaptive sampling across a group of contexts (pt_group_select.hip), on raw device pointers and a stream; asynchronous, nothing allocated.
+// pt_group_pack_launch: packed_dev[p] = {w_p, T_p} of a tile (8 bytes per pixel) from plane 0 of noise_dev and counts_dev.
+// pt_group_keys_launch: the selection keys of a frame of w x rows pixels from its packed pairs -> key_dev (pt_adaptive_select_keys).
+// pt_group_partition_launch: the first m = select_result_dev[1] entries of list_dev (ascending frame pixels of a frame w wide, at most
+// max_entries of them; select_result_dev = pt_adaptive_select_result's {above, m}) cut for n contexts -> parts_dev, the parts back to back;
+// result_dev receives 2 + n words {above, m, m_0 .. m_(n-1)}; workspace_dev holds pt_group_partition_bytes(max_entries, n) bytes.
+// pt_group_offsets_launch: offsets_dev[i] = the frame offset of tile pixel list_dev[i] on a striped tile (ptgs::stripe_offset), i < m.
+int pt_group_pack_launch(hipStream_t stream, int pixels, const float* noise_dev, const void* counts_dev, void* packed_dev);
+int pt_group_keys_launch(hipStream_t stream, int w, int rows, const void* packed_dev, uint32_t* key_dev);
+size_t pt_group_partition_bytes(size_t max_entries, int n);
+int pt_group_partition_launch(hipStream_t stream, int w, int n, const int32_t* list_dev, const uint32_t* select_result_dev, int max_entries,
+                              void* workspace_dev, int32_t* parts_dev, uint32_t* result_dev);
+int pt_group_offsets_launch(hipStream_t stream, const int32_t* list_dev, int m, int stripe, int gap, int32_t* offsets_dev);
+// what the host and stage forms of the partition refuse
+int pt_group_partition_check(const char* who, int w, int h, int n, const int32_t* list, int m, const int32_t* parts, const int32_t* counts);

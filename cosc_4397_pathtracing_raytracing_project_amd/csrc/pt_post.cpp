@@ -1,6 +1,6 @@
 // pt_post.cpp — what reads or extends a rendered image, on a context (pt_context.h): the first-hit feature buffers, the two
 // edge-avoiding filters, the noise estimate and render-until, adaptive sampling with its worker context, and resolve.  The kernels
-// are pt_features.inc (through KernelApi), pt_denoise.hip, pt_noise.hip and pt_adaptive.hip; this file holds their host side: what
+// are pt_features.inc (through KernelApi), pt_denoise.hip, pt_noise.hip, pt_adaptive.hip and (a striped tile's list) pt_group_select.hip; this file holds their host side: what
 // an entry point refuses, the buffers that exist from the first use on, and the launches.
 #include <cmath>
 
@@ -201,6 +201,9 @@ int ensure_worker(Ctx& g, int m) {
   if (g.worker && g.worker->capacity == m) return set_worker_live(*g.worker, m), 0;
   if (g.worker) g.device_bytes -= g.worker->device_bytes, destroy(g.worker), g.worker = nullptr;
   if (ensure(g, g.d_list, (size_t)g.N * sizeof(int32_t), Zero::blocking)) return -1;  // the list: every entry a tile pixel from the start
+  // A striped tile: the kernels read a list entry as an offset from pixel_begin in the FRAME (pt_kernels.hip global_pixel), the merge as
+  // a TILE index; the worker gets a second list, derived from the first on the device (round_list).  A contiguous tile: one buffer.
+  if (g.stripe && ensure(g, g.d_list_frame, (size_t)g.N * sizeof(int32_t), Zero::blocking)) return -1;
   Ctx* w = new Ctx();
   w->borrowed = true;
   static_cast<PtShared&>(*w) = g;
@@ -210,7 +213,7 @@ int ensure_worker(Ctx& g, int m) {
   if (plan_batches(*w, o)) return destroy(w), -1;
   plan_launch(*w);
   if (alloc_batch_buffers(*w)) return destroy(w), -1;
-  w->list = g.d_list;
+  w->list = g.stripe ? g.d_list_frame : g.d_list;
   w->capacity = m;
   g.worker = w;
   g.device_bytes += w->device_bytes;
@@ -232,14 +235,18 @@ int render_list(Ctx& g, int iter_first, int iter_count) {
 
 // Everything a round refuses, before anything is allocated or launched.  pt_render_adaptive asks with folds == false: without the
 // state of the folds, which its uniform groups establish, and with its own words about the first iteration (its group may be 0).
-static int adaptive_refusal(const Ctx& g, const char* who, int iter_first, int group_iters, float fraction, bool folds = true) {
+// A round over a caller's list has no fraction (nullptr) and needs no rows (rows == false); a group's round has the fraction, and its
+// contexts' tiles are rows dealt in turn.
+static int adaptive_refusal(const Ctx& g, const char* who, int iter_first, int group_iters, const float* fraction_or_null, bool folds = true,
+                            bool rows = true) {
+  const float fraction = fraction_or_null ? *fraction_or_null : 1.0f;
   if (admit(g, who, kNotFailed)) return -1;
   if (folds && (iter_first < 1 || group_iters < 1 || (int64_t)iter_first + group_iters - 1 > INT32_MAX))
     return pt_fail("%s: iterations %d, +%d: the first is >= 1, the group holds at least one", who, iter_first, group_iters);
   if (!folds && iter_first < 1) return pt_fail("%s: the first iteration %d is not >= 1", who, iter_first);
   if (!(fraction > 0.0f && fraction <= 1.0f)) return pt_fail("%s: fraction %g is not in (0, 1]", who, (double)fraction);
   if (g.conv) return pt_fail("%s: the renderer was created with PtOptions.convergence = %d; the convergence metric follows whole iterations", who, g.conv);
-  if (admit(g, who, kWholeRows)) return -1;
+  if (rows && admit(g, who, kWholeRows)) return -1;
   if (g.adaptive || !folds) return 0;
   if (g.noise_groups < 2) return pt_fail("%s: %d group(s) folded; the selection needs the noise estimate of at least 2 (pt_noise_fold)", who, g.noise_groups);
   if (admit(g, who, kFoldedAll)) return -1;
@@ -247,10 +254,11 @@ static int adaptive_refusal(const Ctx& g, const char* who, int iter_first, int g
   return 0;
 }
 
-// The first round since pt_init / pt_clear, of either kind: every pixel has the fold's T and M.
+// The first round since pt_init / pt_clear, of any kind: every pixel has the fold's T and M.  (The selection's workspace belongs to
+// the rounds that select: a round over a caller's list has none.)
 static int enter_adaptive(Ctx& g) {
   if (g.adaptive) return 0;
-  if (ensure(g, g.d_acnt, (size_t)g.N * sizeof(ptad::Cnt)) || ensure(g, g.d_select, pt_adaptive_select_bytes((size_t)g.N))) return -1;
+  if (ensure(g, g.d_acnt, (size_t)g.N * sizeof(ptad::Cnt))) return -1;
   if (pt_adaptive_init_counts_launch(g.stream, g.N, g.d_acnt, (int)g.noise_iters, g.noise_groups)) return -1;
   g.adaptive = true;
   g.adaptive_rounds = 0;
@@ -274,7 +282,7 @@ static int render_and_merge(Ctx& g, int iter_first, int group_iters, int m) {
 static int threshold_round(Ctx& g, int iter_first, int group_iters, float threshold, float max_fraction, int min_pixels, int* above, int* selected) {
   HIP_OK(hipSetDevice(g.device));
   const int W = g.cam.resolution[0];
-  if (enter_adaptive(g)) return -1;
+  if (enter_adaptive(g) || ensure(g, g.d_select, pt_adaptive_select_bytes((size_t)g.N))) return -1;
   const int cap = ptad::list_length((double)max_fraction, g.N);
   if (ensure_worker(g, cap)) return -1;
   if (pt_adaptive_select_threshold_launch(g.stream, W, g.N / W, static_cast<const float*>(g.d_noise), g.d_acnt, threshold, cap, g.d_select, g.d_list)) return -1;
@@ -290,17 +298,72 @@ static int threshold_round(Ctx& g, int iter_first, int group_iters, float thresh
   set_worker_live(*g.worker, m);
   return render_and_merge(g, iter_first, group_iters, m);
 }
+
+// A round over a caller's list after its refusals: a pt_adaptive_round without the selection.  `list` lies on the host (host == true:
+// uploaded on the context's stream, from pageable memory, so the call returns once the entries have left the caller's array) or on
+// the context's device; either way it is copied into the context's own list behind whatever still reads that, and nothing synchronises.
+static int round_list(Ctx& g, int iter_first, int group_iters, const int32_t* list, bool host, int m, int capacity) {
+  HIP_OK(hipSetDevice(g.device));
+  if (enter_adaptive(g) || ensure_worker(g, capacity)) return -1;
+  if (m == 0) {  // nothing rendered or merged, SSE_est where it was; the round and its iterations count, so that a group's contexts stay in step
+    g.adaptive_rounds += 1;
+    g.adaptive_last = std::max<int64_t>(g.adaptive_last, (int64_t)iter_first + group_iters - 1);
+    return 0;
+  }
+  set_worker_live(*g.worker, m);
+  HIP_OK(hipMemcpyAsync(g.d_list, list, (size_t)m * sizeof(int32_t), host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, g.stream));
+  if (g.stripe && pt_group_offsets_launch(g.stream, g.d_list, m, g.stripe, g.stripe_stride - g.stripe, g.d_list_frame)) return -1;
+  return render_and_merge(g, iter_first, group_iters, m);
+}
+
+static int round_list_entry(PtContext* c, const char* who, int iter_first, int group_iters, const int32_t* list, bool host, int m, int capacity) {
+  if (need(c, who)) return -1;
+  Ctx& g = *c;
+  if (adaptive_refusal(g, who, iter_first, group_iters, nullptr, true, false)) return -1;
+  if (capacity < 1 || capacity > g.N || m < 0 || m > capacity)
+    return pt_fail("%s: a list of %d on a worker for %d out of %d pixels: the capacity is 1 .. the tile, the list 0 .. the capacity", who, m, capacity, g.N);
+  if (m > 0 && !list) return pt_fail("%s: null list", who);
+  for (int i = 0; host && i < m; ++i)
+    if (list[i] < 0 || list[i] >= g.N || (i > 0 && list[i] <= list[i - 1]))
+      return pt_fail("%s: list[%d] = %d is outside the tile or not above its predecessor", who, i, list[i]);
+  return round_list(g, iter_first, group_iters, list, host, m, capacity);
+}
 }  // namespace ptc
 
+// pt_context.h: what a group asks of its contexts
+PtCtxState pt_ctx_state(const PtContext* c) {
+  PtCtxState s{};
+  if (c) s.adaptive = c->adaptive, s.groups = c->noise_groups, s.iters = c->noise_iters, s.unfolded = c->rendered - c->noise_iters;
+  return s;
+}
+int pt_ctx_adaptive_refusal(const PtContext* c, const char* who, int iter_first, int group_iters, float max_fraction, bool folds) {
+  if (need(c, who)) return -1;
+  return adaptive_refusal(*c, who, iter_first, group_iters, &max_fraction, folds, false);
+}
+int pt_ctx_enter_adaptive(PtContext* c) {
+  if (need(c, "pt_adaptive_round")) return -1;
+  HIP_OK(hipSetDevice(c->device));
+  return enter_adaptive(*c);
+}
+int pt_ctx_admit_state(const PtContext* c, const char* who, bool uniform) { return need(c, who) ? -1 : admit(*c, who, kNotFailed | (uniform ? kUniform : 0u)); }
+
 extern "C" {
+
+int pt_ctx_adaptive_round_list(PtContext* c, int iter_first, int group_iters, const int32_t* list_host, int m, int capacity) {
+  return round_list_entry(c, "pt_adaptive_round_list", iter_first, group_iters, list_host, true, m, capacity);
+}
+int pt_ctx_adaptive_round_list_device(PtContext* c, int iter_first, int group_iters, const int32_t* list_dev, int m, int capacity) {
+  return round_list_entry(c, "pt_adaptive_round_list", iter_first, group_iters, list_dev, false, m, capacity);
+}
+const int32_t* pt_ctx_device_counts(PtContext* c) { return c && c->adaptive ? static_cast<const int32_t*>(c->d_acnt) : nullptr; }
 
 int pt_ctx_adaptive_round(PtContext* c, int iter_first, int group_iters, float fraction) {
   if (need(c, "pt_adaptive_round")) return -1;
   Ctx& g = *c;
-  if (adaptive_refusal(g, "pt_adaptive_round", iter_first, group_iters, fraction)) return -1;
+  if (adaptive_refusal(g, "pt_adaptive_round", iter_first, group_iters, &fraction)) return -1;
   HIP_OK(hipSetDevice(g.device));
   const int W = g.cam.resolution[0];
-  if (enter_adaptive(g)) return -1;
+  if (enter_adaptive(g) || ensure(g, g.d_select, pt_adaptive_select_bytes((size_t)g.N))) return -1;
   const int m = ptad::list_length((double)fraction, g.N);
   if (ensure_worker(g, m)) return -1;  // (a worker of that capacity: its live size is the capacity again, whatever a threshold round left)
   if (pt_adaptive_select_launch(g.stream, W, g.N / W, static_cast<const float*>(g.d_noise), g.d_acnt, m, g.d_select, g.d_list)) return -1;
@@ -310,7 +373,7 @@ int pt_ctx_adaptive_round(PtContext* c, int iter_first, int group_iters, float f
 int pt_ctx_adaptive_round_threshold(PtContext* c, int iter_first, int group_iters, float threshold, float max_fraction, int* above, int* selected) {
   if (need(c, "pt_adaptive_round_threshold")) return -1;
   Ctx& g = *c;
-  if (adaptive_refusal(g, "pt_adaptive_round_threshold", iter_first, group_iters, max_fraction)) return -1;
+  if (adaptive_refusal(g, "pt_adaptive_round_threshold", iter_first, group_iters, &max_fraction)) return -1;
   if (pt_adaptive_check_threshold("pt_adaptive_round_threshold", threshold)) return -1;
   return threshold_round(g, iter_first, group_iters, threshold, max_fraction, 0, above, selected);
 }
@@ -323,7 +386,7 @@ int pt_ctx_render_threshold(PtContext* c, int iter_first, int max_iters, int gro
     return pt_fail("pt_render_threshold: iterations %d, +%d in groups of %d until at most %d pixels are above: the count is >= 1, the group >= 0 (0 = a batch of the worker), the pixels >= 0",
                 iter_first, max_iters, group_iters, min_pixels);
   // what a round would refuse, apart from the state of the folds, which the uniform groups below establish
-  if (adaptive_refusal(g, "pt_render_threshold", iter_first, group_iters, max_fraction, false)) return -1;
+  if (adaptive_refusal(g, "pt_render_threshold", iter_first, group_iters, &max_fraction, false)) return -1;
   if (pt_adaptive_check_threshold("pt_render_threshold", threshold)) return -1;
   const int cap = ptad::list_length((double)max_fraction, g.N);
   const int group = group_iters ? group_iters : g.worker && g.worker->capacity == cap ? g.worker->K : batch_iters_for(g.opt_iters_per_batch, cap, nullptr);
@@ -336,7 +399,7 @@ int pt_ctx_render_threshold(PtContext* c, int iter_first, int max_iters, int gro
       samples += (int64_t)n * g.N;
     } else {
       if (!g.adaptive && g.rendered != g.noise_iters && pt_ctx_noise_fold(c)) return -1;  // iterations of the caller's, not yet folded
-      if (adaptive_refusal(g, "pt_render_threshold", iter_first + done, n, max_fraction)) return -1;
+      if (adaptive_refusal(g, "pt_render_threshold", iter_first + done, n, &max_fraction)) return -1;
       int m = 0;
       if (threshold_round(g, iter_first + done, n, threshold, max_fraction, min_pixels, &above, &m)) return -1;
       if (above <= min_pixels) break;  // nothing was rendered
@@ -358,7 +421,7 @@ int pt_ctx_render_adaptive(PtContext* c, int iter_first, int max_iters, int grou
     return pt_fail("pt_render_adaptive: iterations %d, +%d in groups of %d until %g dB: the count is >= 1, the group >= 0 (0 = a batch of the worker), the target finite",
                 iter_first, max_iters, group_iters, (double)target_db);
   // what a round would refuse, apart from the state of the folds, which the uniform groups below establish
-  if (adaptive_refusal(g, "pt_render_adaptive", iter_first, group_iters, fraction, false)) return -1;
+  if (adaptive_refusal(g, "pt_render_adaptive", iter_first, group_iters, &fraction, false)) return -1;
   const int m = ptad::list_length((double)fraction, g.N);
   // group_iters == 0: the iterations per batch a worker for m pixels plans (plan_batches' own function)
   const int group = group_iters ? group_iters : g.worker && g.worker->capacity == m ? g.worker->K : batch_iters_for(g.opt_iters_per_batch, m, nullptr);

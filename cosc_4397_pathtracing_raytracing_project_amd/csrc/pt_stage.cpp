@@ -336,6 +336,34 @@ int pt_stage_adaptive_select_threshold(int w, int rows, const float* noise_plane
   return 0;
 }
 
+// The partition's kernels on caller-supplied host arrays (pt_group_partition_host's arguments).  The list's length reaches the kernels
+// as it does in a group's round: in the second of two words on the device.
+int pt_stage_group_partition(int w, int h, int n, const int32_t* list, int m, int32_t* parts, int32_t* counts) {
+  if (need(default_context(), "pt_stage_group_partition")) return -1;
+  Ctx& g = *default_context();
+  if (pt_group_partition_check("pt_stage_group_partition", w, h, n, list, m, parts, counts)) return -1;
+  HIP_OK(hipSetDevice(g.device));
+  Scratch sc;
+  const int entries = std::max(m, 1);
+  int32_t* d_list = sc.get<int32_t>((size_t)entries);
+  int32_t* d_parts = sc.get<int32_t>((size_t)entries);
+  uint32_t* d_words = sc.get<uint32_t>(2 + 2 + (size_t)n);  // {above, m} as the selection leaves them | the partition's result
+  char* d_ws = sc.get<char>(pt_group_partition_bytes((size_t)entries, n));
+  if (!d_list || !d_parts || !d_words || !d_ws) return pt_fail("pt_stage_group_partition: out of device memory");
+  const uint32_t sel[2] = {(uint32_t)m, (uint32_t)m};
+  HIP_OK(hipMemcpy(d_words, sel, sizeof(sel), hipMemcpyHostToDevice));
+  if (m) HIP_OK(hipMemcpy(d_list, list, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_OK(hipMemset(d_parts, 0xff, (size_t)entries * sizeof(int32_t)));  // an entry nobody wrote shows as -1
+  if (pt_group_partition_launch(g.stream, w, n, d_list, d_words, entries, d_ws, d_parts, d_words + 2)) return -1;
+  HIP_OK(hipStreamSynchronize(g.stream));
+  std::vector<uint32_t> result(2 + (size_t)n);
+  HIP_OK(hipMemcpy(result.data(), d_words + 2, result.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (m) HIP_OK(hipMemcpy(parts, d_parts, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (result[0] != (uint32_t)m || result[1] != (uint32_t)m) return pt_fail("pt_stage_group_partition: the kernels read a list of %u, not %d", result[1], m);
+  for (int i = 0; i < n; ++i) counts[i] = (int32_t)result[2 + (size_t)i];
+  return 0;
+}
+
 // The worker context alone: iterations iter_first .. iter_first + iter_count - 1 of the m listed tile pixels (distinct, any order);
 // rgb_sum_host receives the group sum, m * 3 floats in list order.  Leaves image, folds and state of the renderer alone.
 static int stage_render_list(const char* who, const int32_t* list, int m, int capacity, int iter_first, int iter_count, float* rgb_sum_host) {

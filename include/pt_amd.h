@@ -517,7 +517,8 @@ int pt_denoise_guided_variance_host(int w, int rows, const float* rgb_sum, const
  *     MI355X in that configuration (tests/test_gpu_adaptive.py): 0.843, the estimate reading 33.84 dB where the image has 33.10 dB.
  *   - A pixel whose first two groups agree exactly has w = 0 and is sampled again only through its neighbours' variance (the
  *     prefilter).  For background and emitter pixels that is the point; a pixel that is noisy but unlucky twice is reached the same way.
- * Out of scope: pt_group_* (a rank's top m is not the frame's) and any tuning of the path-tracing kernels for incoherent lists; a list
+ * A group (pt_group_*) has the threshold round and its driver, below: the frame's selection runs once, on the root device.  Out of
+ * scope: a group form of THIS round and of pt_render_adaptive, and any tuning of the path-tracing kernels for incoherent lists; a list
  * length that varies from round to round is pt_adaptive_round_threshold, below.  pt_denoise and pt_denoise_guided refuse the adaptive state; pt_denoise_adaptive
  * (below) is the filter that reads the per-pixel counts.
  * In the adaptive state pt_readback (S), pt_get_noise (sse = the last merge's, groups = M + rounds, iterations = the highest
@@ -569,7 +570,8 @@ int pt_adaptive_merge_host(int pixels, float* rgb_sum, float* planes, int32_t* c
  *     15 % of the pixels of the finished image have an actual error above the threshold, 1.6 % above twice the threshold.
  *   - Every round SYNCHRONISES: above and m are read back (8 bytes) before the group is launched, because the list's length decides
  *     the launches.  A fixed-fraction round does not.
- * Out of scope: pt_group_*, longer groups for short lists, and a threshold relative to the pixel's brightness (simulated: worse than
+ * A group runs these rounds as pt_group_adaptive_round_threshold / pt_group_render_threshold (below, after pt_group_render_until).  Out
+ * of scope: longer groups for short lists, load balance between the contexts of a group whose parts differ in length, and a threshold relative to the pixel's brightness (simulated: worse than
  * uniform sampling at loose thresholds, the brightness of 8 samples being too noisy to normalise by). */
 /* One round: key, select, read back, render, merge.  Refuses what pt_adaptive_round refuses, in the same order (max_fraction for
  * fraction), then a threshold that is negative or not finite; a refusal allocates and launches nothing.  The first call enters the
@@ -589,6 +591,19 @@ int pt_render_threshold(int iter_first, int max_iters, int group_iters, float th
  * *m tile indices, *above the count.  The device's list and counts equal it. */
 int pt_adaptive_select_threshold_host(int w, int rows, const float* noise_planes, const int32_t* counts, float threshold, int cap, int32_t* list,
                                       int* above, int* m);
+/* A round over a CALLER'S list: pt_adaptive_round without the selection, on any tile (a list needs no rows, so a striped or ragged
+ * tile is not refused).  list_host: m distinct tile indices in ascending order, 0 <= m <= capacity; the worker is the one kept for
+ * `capacity` pixels (1 <= capacity <= pixel_count; pt_adaptive_round_threshold's for cap), made live for m.  Render, merge, the
+ * counters and PtStats.samples are pt_adaptive_round's, bit for bit.  m == 0 enters the adaptive state if need be, renders and merges
+ * nothing and leaves SSE_est where it was, but DOES count the round and the highest iteration number (the contexts of a group stay
+ * in step that way).  Asynchronous: the list is uploaded on the renderer's stream and nothing synchronises.
+ * Refuses what pt_adaptive_round refuses, in its order, apart from the fraction and the tile's rows; then capacity or m out of range, a
+ * null list with m > 0, and the first entry that is outside the tile or not above its predecessor, named by index.  A refusal
+ * allocates and launches nothing.
+ * On a striped tile the kernels want a list entry as an offset in the frame, p + (p / stripe) * (stride - stripe), where the merge
+ * wants the tile index p: the renderer keeps the tile list and derives a second list for the worker on the device (4 more bytes per
+ * tile pixel from the first such round on).  A contiguous tile has one list, as before. */
+int pt_adaptive_round_list(int iter_first, int group_iters, const int32_t* list_host, int m, int capacity);
 
 /* ---- variance-guided filter with per-pixel sample counts: pt_denoise_guided for an adaptively sampled image.  Valid in both states;
  * in the uniform state every pixel has the fold's (T, M), exactly as pt_readback_adaptive reports them.  Everything not stated here
@@ -676,6 +691,10 @@ int pt_ctx_render_adaptive(PtContext* c, int iter_first, int max_iters, int grou
                            int64_t* samples_done, float* psnr_db);
 int pt_ctx_readback_adaptive(PtContext* c, int32_t* counts);
 int pt_ctx_adaptive_round_threshold(PtContext* c, int iter_first, int group_iters, float threshold, float max_fraction, int* above, int* selected);
+int pt_ctx_adaptive_round_list(PtContext* c, int iter_first, int group_iters, const int32_t* list_host, int m, int capacity);
+/* The same with the list on the context's device: copied into the context's own list on the context's stream, entries not checked. */
+int pt_ctx_adaptive_round_list_device(PtContext* c, int iter_first, int group_iters, const int32_t* list_dev, int m, int capacity);
+const int32_t* pt_ctx_device_counts(PtContext* c); /* device pointer of the plane cnt (T_p, M_p); NULL outside the adaptive state */
 int pt_ctx_render_threshold(PtContext* c, int iter_first, int max_iters, int group_iters, float threshold, float max_fraction, int min_pixels,
                             int* iters_done, int64_t* samples_done, int* above_left);
 int pt_ctx_resolve(PtContext* c, float* rgb_avg_host);
@@ -736,6 +755,44 @@ int pt_group_denoise_guided(PtGroup* g, const PtDenoiseOptions* opt, float* rgb_
 int pt_group_noise_fold(PtGroup* g);
 int pt_group_get_noise(PtGroup* g, double* sse, int* groups, int* iterations);
 int pt_group_render_until(PtGroup* g, int iter_first, int max_iters, int group_iters, float target_db, int* iters_done, float* psnr_db);
+/* ---- adaptive sampling by threshold across a group (pt_adaptive_round_threshold, pt_render_threshold).  A context owns the rows
+ * i, i + n, ...: the 3x3 prefilter of the key reads rows of other contexts, and "the cap largest keys" are the frame's, not a tile's.
+ * So the frame is selected ONCE, on the root device, and the frame's list is cut into one list per context:
+ *   pack       every context, on its own stream: {float w_p, int32 T_p} of its tile pixels, 8 bytes per pixel: all the key reads.
+ *   exchange   one exchange of those 8 bytes per pixel to the root (either transport), the rows placed into the frame.
+ *   select     the key of pt_adaptive_round on the packed frame (the same arithmetic on the same values over W x H), then the
+ *              selection by threshold for cap = clamp(ceil((double)max_fraction * W*H), 1, W*H): the single context's kernels.
+ *   partition  frame pixel f of the list belongs to context i = (f / W) % n as tile pixel ((f / W) / n) * W + f % W; part i holds
+ *              them in input order, which is ascending tile index; the parts lie back to back.  Positions come from counts and a
+ *              scan; integer atomics on counters only, so equal inputs give equal parts.  At most 64 contexts.
+ *   read back  above, m and the n lengths m_i: 8 + 4n bytes and ONE synchronise of the root's stream, as a context's round has.
+ *   render     part i goes to context i (a copy on context i's stream behind an event of the root's, or a grouped RCCL send /
+ *              receive), and every context runs pt_ctx_adaptive_round_list_device over it on a worker for min(cap, its pixels),
+ *              contexts with m_i == 0 included; they render concurrently and the call returns without a further synchronise.
+ * After the same calls the SUM image, the noise planes, the counts, (above, m) of every round, the iteration numbers, the samples,
+ * the resolved and the filtered image are a single context's, bit for bit.  SSE_est is added per context and then in context order
+ * (pt_group_get_noise), so it may differ from the single context's in the last bits.
+ * Refuses, allocating and launching nothing: what pt_adaptive_round_threshold refuses of any context, in its order, apart from the
+ * tile's rows; then contexts that differ in the groups or iterations folded or in being in the adaptive state, naming the context.
+ * m == 0 (or, in the driver, above <= min_pixels): nothing is rendered and no context counts a round.
+ * The group's buffers (the packed frame and its receive buffer, the selection's workspace for W*H pixels, the frame's list and the
+ * parts, all on the root; 8 + 4 bytes per tile pixel on every device) are allocated by the first round and freed by pt_group_destroy.
+ * pt_group_render_threshold is pt_render_threshold's loop over pt_group_render, pt_group_noise_fold and the round; group_iters 0 =
+ * the first context's iters_per_batch, as in pt_group_render_until.
+ * Out of scope: a group form of pt_adaptive_round / pt_render_adaptive, load balance between contexts whose parts differ in length
+ * (interleaved rows are what a group has for that), and the command-line driver, which keeps --adaptive-threshold to one device. */
+int pt_group_adaptive_round_threshold(PtGroup* g, int iter_first, int group_iters, float threshold, float max_fraction, int* above, int* selected);
+int pt_group_render_threshold(PtGroup* g, int iter_first, int max_iters, int group_iters, float threshold, float max_fraction, int min_pixels,
+                              int* iters_done, int64_t* samples_done, int* above_left);
+int pt_group_gather_adaptive(PtGroup* g, int32_t* counts); /* W*H*2 int32 (T_p, M_p), raw orientation; the uniform state: the shared T, M */
+int pt_group_resolve(PtGroup* g, float* rgb_avg_host);     /* W*H*3 floats: every context resolves its rows, the rows meet like the image */
+/* pt_denoise_adaptive of the whole frame, bit-identical to a single context's: as pt_group_denoise_guided, and in the adaptive state
+ * the count planes meet on the root as well.  Refuses what pt_denoise_adaptive refuses, in its order, apart from the tile's rows, and
+ * contexts that differ as above. */
+int pt_group_denoise_adaptive(PtGroup* g, const PtDenoiseOptions* opt, float* rgb_avg_host);
+/* The partition on the host (no GPU): list holds m frame pixels of a frame w x h in ascending order (0 <= m <= w*h), 1 <= n <= min(h, 64);
+ * parts receives m tile indices, part after part, counts the n lengths.  The device's parts equal it. */
+int pt_group_partition_host(int w, int h, int n, const int32_t* list, int m, int32_t* parts, int32_t* counts);
 /* Progressive preview of the running average (sendImageToPBO, pathtrace.cu:250-268, which the reference runs after every
  * iteration): W*H RGBA8 bytes, raw orientation, converted on each device, one exchange of 4 B per pixel. */
 int pt_group_preview_rgba8(PtGroup* g, int iterations, uint8_t* rgba_host);
@@ -797,6 +854,8 @@ int pt_stage_render_list(const int32_t* list, int m, int iter_first, int iter_co
  * calls while the capacity is equal, so calls with different m run one set of buffers under different live plans. */
 int pt_stage_render_list_capacity(const int32_t* list, int m, int capacity, int iter_first, int iter_count, float* rgb_sum_host);
 /* The threshold selection's kernels on caller-supplied host arrays (pt_adaptive_select_threshold_host's arguments; rows < 32768). */
+/* The partition's kernels on caller-supplied host arrays (pt_group_partition_host's arguments). */
+int pt_stage_group_partition(int w, int h, int n, const int32_t* list, int m, int32_t* parts, int32_t* counts);
 int pt_stage_adaptive_select_threshold(int w, int rows, const float* noise_planes, const int32_t* counts, float threshold, int cap, int32_t* list,
                                        int* above, int* m);
 
