@@ -6,12 +6,18 @@
 // smoothly down the cornell frame, interleaving gives every device the same mix) and runs ALL iterations on them
 // on its own stream; samples are keyed by the global pixel index (makeSeededRandomEngine(iter, idx, depth),
 // src/pathtrace.cu:203-207,368), so nothing is ever summed across devices and the assembled image is bit-identical
-// to the single-GPU image.  The only communication is, once per write-out, one grouped ncclSend/ncclRecv of the
-// tiles into devices[0] on a ncclCommInitAll communicator — xGMI is point-to-point, the tiles go straight to the
+// to the single-GPU image.  The only communication towards the root is, once per write-out, one grouped ncclSend/ncclRecv
+// of the tiles into devices[0] on a ncclCommInitAll communicator — xGMI is point-to-point, the tiles go straight to the
 // root over their own links, there is no ring and no reduction.  Placement of the interleaved rows (a strided 2-D
 // copy on the root device) and one D2H copy follow.
 //
-// Two transports for that one exchange (PtGroup::transport, pt_group_create_ex):
+// Every write-out is that one path, gather(), with a payload of B bytes per pixel (Payload below): the SUM image and the resolved
+// image (12 B), a feature or noise plane (16 B, one exchange per plane), the packed {w, T} pairs of a round and the count planes (8 B),
+// the converted bytes (3 B) and the preview (4 B).  The tiles meet in ONE receive buffer of 16 B per received pixel (PtGroup::d_recv);
+// each payload has a frame buffer of its own, since a filter reads several of them in one launch.  The one exchange in the other
+// direction, the parts of the frame's list back to the contexts, is scatter_parts().
+//
+// Two transports for those exchanges (PtGroup::transport, pt_group_create_ex):
 //   RCCL  the grouped ncclSend / ncclRecv above — the default for distinct devices;
 //   COPY  hipMemcpyPeerAsync (hipMemcpyAsync when source and root are the same device) of every tile into the same
 //         receive buffer at the same offsets, ordered after the tile's producer by an event the root's stream waits
@@ -25,6 +31,7 @@
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "pt_adaptive.h"
@@ -47,23 +54,24 @@ struct PtGroup {
   std::vector<int> rows;         // image rows owned by device i
   std::vector<size_t> recv_off;  // pixel offset of device i's tile in the root's receive buffer (i >= 1)
   size_t recv_pixels = 0;
-  float* d_recv = nullptr;    // root: tiles of devices 1..n-1, float RGB
-  float* d_full = nullptr;    // root: assembled frame
-  uint8_t* d_recv8 = nullptr; // same for the converted bytes (3 B/pixel)
-  uint8_t* d_full8 = nullptr;
-  std::vector<uint8_t*> d_prev;  // per device: RGBA8 preview of its tile (sendImageToPBO)
-  uint8_t* d_recv_prev = nullptr;  // root: preview tiles of devices 1..n-1 / assembled preview (kept: previews recur)
-  uint8_t* d_full_prev = nullptr;
-  float* d_recv_feat = nullptr;  // root: one feature plane of the tiles of devices 1..n-1 (16 B per pixel) / the assembled planes
-  float* d_full_feat = nullptr;
-  float* d_full_noise = nullptr;  // root: the assembled noise planes (pt_group_denoise_guided; the receive buffer is d_recv_feat)
-  void* d_denoise = nullptr;  // root: workspace of pt_group_denoise over the whole frame
-  // Adaptive sampling by threshold (pt_group_adaptive_round_threshold); all of it absent until the first round (the pair buffers: or
-  // until the first write-out of the count planes)
+  std::vector<std::pair<int, void*>> owned;  // (device, buffer): every device buffer below; ensure() allocates it at its first use, release() frees it
+  // root: THE receive buffer of every write-out, the tiles of devices 1..n-1 back to back, kRecvBytes (the widest payload) per pixel.
+  // Payloads of different widths follow each other in it with nothing but stream order between them.  That is sound because all three
+  // parties are queued on the ROOT context's stream: the COPY transport's copies into it, RCCL's ncclRecv into it, and the placement
+  // of the rows that reads it.  A plane that follows a plane (gather_planes) is a case of it.
+  char* d_recv = nullptr;
+  // root: the assembled frames, one per payload — a filter reads the image, the planes and the pairs in one launch
+  float* d_full = nullptr;          // the SUM image; the resolved image
+  uint8_t* d_full8 = nullptr;       // the converted bytes (3 B/pixel)
+  uint8_t* d_full_prev = nullptr;   // the RGBA8 preview (kept: previews recur)
+  float* d_full_feat = nullptr;     // the feature planes
+  float* d_full_noise = nullptr;    // the noise planes (pt_group_denoise_guided)
+  int32_t* d_full_pair = nullptr;   // 8 B per pixel: the packed pairs of a round; the count planes at write-out
+  void* d_denoise = nullptr;        // root: workspace of pt_group_denoise over the whole frame
+  std::vector<uint8_t*> d_prev;     // per device: RGBA8 preview of its tile (sendImageToPBO)
+  // Adaptive sampling by threshold (pt_group_adaptive_round_threshold); all of it absent until the first round
   std::vector<void*> d_pack;       // per context, on its device: {w_p, T_p} of its tile, 8 B per pixel
   std::vector<int32_t*> d_part;    // per context i >= 1, on its device: its part of the frame's list
-  int32_t* d_recv_pair = nullptr;  // root: 8 B per pixel of the tiles of devices 1..n-1 (the packed pairs; the count planes at write-out)
-  int32_t* d_full_pair = nullptr;  // root: the same of the assembled frame
   void* d_select = nullptr;        // root: the selection's workspace for W*H pixels (pt_adaptive_select_bytes)
   void* d_partition = nullptr;     // root: the partition's workspace (pt_group_partition_bytes)
   int32_t* d_list = nullptr;       // root: the frame's list, W*H entries, the first m in use
@@ -73,6 +81,29 @@ struct PtGroup {
 };
 
 namespace {
+
+// What one pixel of a write-out is: `bytes` to the copies and the placement, `elems` elements of `type` to RCCL.
+struct Payload {
+  size_t bytes;
+  ncclDataType_t type;
+  int elems;
+};
+constexpr size_t kRecvBytes = 16;  // per pixel of PtGroup::d_recv
+constexpr Payload kRgb{12, ncclFloat, 3}, kPlane{16, ncclFloat, 4}, kPair{8, ncclInt32, 2}, kRgb8{3, ncclUint8, 3}, kRgba8{4, ncclUint8, 4};
+constexpr bool payload_ok(Payload p, size_t elem_bytes) { return p.bytes == p.elems * elem_bytes && p.bytes <= kRecvBytes; }
+static_assert(payload_ok(kRgb, 4) && payload_ok(kPlane, 4) && payload_ok(kPair, 4) && payload_ok(kRgb8, 1) && payload_ok(kRgba8, 1), "a payload wider than the receive buffer's pixel");
+
+size_t frame_pixels(const PtGroup* g) { return (size_t)g->W * g->H; }
+hipStream_t stream(const PtGroup* g, int i) { return (hipStream_t)pt_ctx_stream(g->ctx[i]); }
+
+// A buffer of the group's that exists from its first use on (a context's is ptc::ensure): `bytes` on devices[i], which is current.
+template <typename T>
+int ensure(PtGroup* g, int i, T*& p, size_t bytes) {
+  if (p) return 0;
+  HIP_OK(hipMalloc((void**)&p, bytes));
+  g->owned.emplace_back(g->devices[i], p);
+  return 0;
+}
 
 void release(PtGroup* g) {
   if (!g) return;
@@ -87,68 +118,63 @@ void release(PtGroup* g) {
       (void)hipEventDestroy(g->ready[i]);
     }
   if (!g->devices.empty()) (void)hipSetDevice(g->devices[0]);
-  for (void* p : {(void*)g->d_recv, (void*)g->d_full, (void*)g->d_recv8, (void*)g->d_full8, (void*)g->d_recv_prev,
-                  (void*)g->d_full_prev, (void*)g->d_recv_feat, (void*)g->d_full_feat, (void*)g->d_full_noise, g->d_denoise, (void*)g->d_recv_pair,
-                  (void*)g->d_full_pair, g->d_select, g->d_partition, (void*)g->d_list, (void*)g->d_parts, (void*)g->d_result})
-    if (p) (void)hipFree(p);
   if (g->parts_ready) (void)hipEventDestroy(g->parts_ready);
-  for (size_t i = 0; i < g->d_pack.size() || i < g->d_part.size(); ++i) {
-    (void)hipSetDevice(g->devices[i]);
-    if (i < g->d_pack.size() && g->d_pack[i]) (void)hipFree(g->d_pack[i]);
-    if (i < g->d_part.size() && g->d_part[i]) (void)hipFree(g->d_part[i]);
+  for (const auto& [device, p] : g->owned) {
+    (void)hipSetDevice(device);
+    (void)hipFree(p);
   }
-  for (size_t i = 0; i < g->d_prev.size(); ++i)
-    if (g->d_prev[i]) {
-      (void)hipSetDevice(g->devices[i]);
-      (void)hipFree(g->d_prev[i]);
-    }
   for (PtContext* c : g->ctx) (void)pt_ctx_destroy(c);
   delete g;
 }
 
-// COPY transport: the root's stream waits for tile i's producer, then pulls the tile into the receive buffer.
-int exchange_copy(PtGroup* g, size_t bytes_per_pixel, char* root_recv, const void* const* src) {
-  hipStream_t root = (hipStream_t)pt_ctx_stream(g->ctx[0]);
-  for (int i = 1; i < g->n; ++i) {
-    const size_t bytes = bytes_per_pixel * (size_t)pt_ctx_pixel_count(g->ctx[i]);
-    HIP_OK(hipSetDevice(g->devices[i]));
-    HIP_OK(hipEventRecord(g->ready[i], (hipStream_t)pt_ctx_stream(g->ctx[i])));
-    HIP_OK(hipSetDevice(g->devices[0]));
-    HIP_OK(hipStreamWaitEvent(root, g->ready[i], 0));
-    char* dst = root_recv + bytes_per_pixel * g->recv_off[i];
-    if (g->devices[i] == g->devices[0]) HIP_OK(hipMemcpyAsync(dst, src[i], bytes, hipMemcpyDeviceToDevice, root));
-    else HIP_OK(hipMemcpyPeerAsync(dst, g->devices[0], src[i], g->devices[i], bytes, root));
-  }
-  return 0;
-}
-
-// The one exchange of a write-out: device i >= 1 hands `elems_per_pixel * pixels_i` elements of `src(i)` to the root,
-// which receives them back to back (recv_off) on its stream.  RCCL: one grouped send/recv, each send on its own
-// device's stream.
-template <typename T, typename SrcFn>
-int exchange(PtGroup* g, ncclDataType_t type, int elems_per_pixel, T* root_recv, SrcFn src) {
-  if (g->n == 1) return 0;
-  if (g->transport == PT_GROUP_TRANSPORT_COPY) {
-    std::vector<const void*> srcs(g->n, nullptr);
-    for (int i = 1; i < g->n; ++i) srcs[i] = src(i);
-    return exchange_copy(g, sizeof(T) * (size_t)elems_per_pixel, reinterpret_cast<char*>(root_recv), srcs.data());
-  }
+// ---- the transport layer, both directions
+// One RCCL group around `body`: an error inside the group must still close it, and the first error wins.
+template <typename Body>
+int rccl_group(Body body) {
   NCCL_OK(ncclGroupStart());
-  int rc = 0;
-  for (int i = 1; i < g->n && !rc; ++i) {  // an error inside the group must still close it
-    const size_t count = (size_t)elems_per_pixel * pt_ctx_pixel_count(g->ctx[i]);
-    ncclResult_t r = ncclSuccess;
-    if (hipSetDevice(g->devices[i]) != hipSuccess) rc = pt_fail("hipSetDevice(%d) failed", g->devices[i]);
-    else if ((r = ncclSend(src(i), count, type, 0, g->comms[i], (hipStream_t)pt_ctx_stream(g->ctx[i]))) != ncclSuccess)
-      rc = pt_fail("ncclSend from device %d failed: %s", g->devices[i], ncclGetErrorString(r));
-    else if (hipSetDevice(g->devices[0]) != hipSuccess) rc = pt_fail("hipSetDevice(%d) failed", g->devices[0]);
-    else if ((r = ncclRecv(root_recv + (size_t)elems_per_pixel * g->recv_off[i], count, type, i, g->comms[0],
-                           (hipStream_t)pt_ctx_stream(g->ctx[0]))) != ncclSuccess)
-      rc = pt_fail("ncclRecv from device %d failed: %s", g->devices[i], ncclGetErrorString(r));
-  }
+  int rc = body();
   const ncclResult_t e = ncclGroupEnd();
   if (!rc && e != ncclSuccess) rc = pt_fail("ncclGroupEnd failed: %s", ncclGetErrorString(e));
   return rc;
+}
+
+// COPY transport: `bytes` from context `from`'s device to context `to`'s, on `s`.
+int copy_between(PtGroup* g, void* dst, int to, const void* src, int from, size_t bytes, hipStream_t s) {
+  if (g->devices[to] == g->devices[from]) HIP_OK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s));
+  else HIP_OK(hipMemcpyPeerAsync(dst, g->devices[to], src, g->devices[from], bytes, s));
+  return 0;
+}
+
+// The one exchange of a write-out: device i >= 1 hands the payload of its pixels at tile(i) to the root, which receives them back to
+// back (recv_off) in d_recv on its stream.  RCCL: one grouped send/recv, each send on its own device's stream.  COPY: the root's
+// stream waits for tile i's producer, then pulls the tile.
+template <typename TileFn>
+int exchange(PtGroup* g, Payload pl, TileFn tile) {
+  hipStream_t root = stream(g, 0);
+  if (g->transport == PT_GROUP_TRANSPORT_COPY) {
+    for (int i = 1; i < g->n; ++i) {
+      HIP_OK(hipSetDevice(g->devices[i]));
+      HIP_OK(hipEventRecord(g->ready[i], stream(g, i)));
+      HIP_OK(hipSetDevice(g->devices[0]));
+      HIP_OK(hipStreamWaitEvent(root, g->ready[i], 0));
+      if (copy_between(g, g->d_recv + pl.bytes * g->recv_off[i], 0, tile(i), i, pl.bytes * (size_t)pt_ctx_pixel_count(g->ctx[i]), root)) return -1;
+    }
+    return 0;
+  }
+  return rccl_group([&] {
+    int rc = 0;
+    for (int i = 1; i < g->n && !rc; ++i) {
+      const size_t count = (size_t)pl.elems * pt_ctx_pixel_count(g->ctx[i]);
+      ncclResult_t r = ncclSuccess;
+      if (hipSetDevice(g->devices[i]) != hipSuccess) rc = pt_fail("hipSetDevice(%d) failed", g->devices[i]);
+      else if ((r = ncclSend(tile(i), count, pl.type, 0, g->comms[i], stream(g, i))) != ncclSuccess)
+        rc = pt_fail("ncclSend from device %d failed: %s", g->devices[i], ncclGetErrorString(r));
+      else if (hipSetDevice(g->devices[0]) != hipSuccess) rc = pt_fail("hipSetDevice(%d) failed", g->devices[0]);
+      else if ((r = ncclRecv(g->d_recv + pl.bytes * g->recv_off[i], count, pl.type, i, g->comms[0], root)) != ncclSuccess)
+        rc = pt_fail("ncclRecv from device %d failed: %s", g->devices[i], ncclGetErrorString(r));
+    }
+    return rc;
+  });
 }
 
 // After a failed exchange / placement some sends, receives or copies may already be queued on the devices' streams:
@@ -159,66 +185,98 @@ int fail_after_drain(PtGroup* g) {
   return pt_fail("%s", first.c_str());
 }
 
-// Rows of device i (tile order) -> rows i, i+n, ... of the frame, on the root's stream.
-template <typename T>
-int place_rows(PtGroup* g, int i, const T* tile, T* full, size_t bytes_per_pixel) {
-  const size_t row = (size_t)g->W * bytes_per_pixel;
-  HIP_OK(hipMemcpy2DAsync(reinterpret_cast<char*>(full) + (size_t)i * row, (size_t)g->n * row, tile, row, row, (size_t)g->rows[i],
-                          hipMemcpyDeviceToDevice, (hipStream_t)pt_ctx_stream(g->ctx[0])));
-  return 0;
+// The way back, beside the root's own part at the head of d_parts: part i >= 1, counts[i] entries behind those of the contexts before
+// it, to context i's d_part[i] on context i's stream; a part without entries is not sent.
+//
+// Buffer order.  The root writes d_list and d_parts on its own stream; context i reads its part on ITS stream.
+//   COPY: context i's copy out of d_parts waits for parts_ready, recorded on the root's stream behind the partition.  The next
+//         round's pack exchange has the root's stream wait for ready[i], recorded on context i's stream behind that copy (and behind the
+//         render and merge that follow it), before the root selects and partitions again: the parts are never overwritten early.
+//   RCCL: the sends of the parts are on the root's stream like the partition before them and the next round's selection after them.
+//         Context i receives into its own d_part[i] on its stream, which also copies it into the context's list; the next receive
+//         into d_part[i] is behind that copy in stream order.
+// Either way the root's host thread has synchronised the root's stream in between (the read-back), and d_pack[i] is written by
+// context i's stream only after the exchange that read it: COPY through that synchronise, RCCL because the send is on that stream.
+int scatter_parts(PtGroup* g, const uint32_t* counts) {
+  hipStream_t root = stream(g, 0);
+  HIP_OK(hipEventRecord(g->parts_ready, root));
+  std::vector<size_t> off(g->n, 0);
+  for (int i = 1; i < g->n; ++i) off[i] = off[i - 1] + counts[i - 1];
+  if (g->transport == PT_GROUP_TRANSPORT_COPY) {
+    for (int i = 1; i < g->n; ++i) {
+      HIP_OK(hipSetDevice(g->devices[i]));
+      HIP_OK(hipStreamWaitEvent(stream(g, i), g->parts_ready, 0));
+      if (counts[i] && copy_between(g, g->d_part[i], i, g->d_parts + off[i], 0, counts[i] * sizeof(int32_t), stream(g, i))) return -1;
+    }
+    return 0;
+  }
+  const int rc = rccl_group([&] {
+    int rc = 0;
+    for (int i = 1; i < g->n && !rc; ++i) {
+      const size_t count = counts[i];
+      if (!count) continue;
+      ncclResult_t r = ncclSuccess;
+      if (hipSetDevice(g->devices[0]) != hipSuccess) rc = pt_fail("hipSetDevice(%d) failed", g->devices[0]);
+      else if ((r = ncclSend(g->d_parts + off[i], count, ncclInt32, i, g->comms[0], root)) != ncclSuccess)
+        rc = pt_fail("ncclSend to device %d failed: %s", g->devices[i], ncclGetErrorString(r));
+      else if (hipSetDevice(g->devices[i]) != hipSuccess) rc = pt_fail("hipSetDevice(%d) failed", g->devices[i]);
+      else if ((r = ncclRecv(g->d_part[i], count, ncclInt32, 0, g->comms[i], stream(g, i))) != ncclSuccess)
+        rc = pt_fail("ncclRecv on device %d failed: %s", g->devices[i], ncclGetErrorString(r));
+    }
+    return rc;
+  });
+  return rc ? fail_after_drain(g) : 0;
 }
 
-// The device side of the two write-out gathers (n > 1; the root device is current), on the root's stream: the tiles' exchange into
-// the receive buffer and the placement of everybody's rows in the frame buffer.  What follows — a copy to the host, the filter —
-// is queued behind them on the same stream.
-int assemble_image(PtGroup* g) {  // -> g->d_full: W*H*3 floats
-  const size_t frame = (size_t)g->W * g->H;
-  if (!g->d_full) HIP_OK(hipMalloc((void**)&g->d_full, frame * 12));
-  if (!g->d_recv) HIP_OK(hipMalloc((void**)&g->d_recv, g->recv_pixels * 12));
-  if (exchange(g, ncclFloat, 3, g->d_recv, [&](int i) { return pt_ctx_device_image(g->ctx[i]); })) return fail_after_drain(g);
-  HIP_OK(hipSetDevice(g->devices[0]));
-  for (int i = 0; i < g->n; ++i)
-    if (place_rows(g, i, i == 0 ? pt_ctx_device_image(g->ctx[0]) : g->d_recv + 3 * g->recv_off[i], g->d_full, 12))
-      return fail_after_drain(g);
+// ---- the write-outs
+// The device side of every write-out (n > 1; the root device is current), on the root's stream: the payload of every context's tile
+// (tile(i), on device i) through the receive buffer into plane `plane` of the `planes` frames of that payload in `full` — the exchange,
+// then the rows of context i (tile order) to the rows i, i + n, ... of the frame.  What follows — a copy to the host, the selection, a
+// filter — is queued behind them on the same stream.
+template <typename T, typename TileFn>
+int gather(PtGroup* g, Payload pl, TileFn tile, T*& full, int planes = 1, int plane = 0) {
+  const size_t row = (size_t)g->W * pl.bytes;
+  if (ensure(g, 0, full, planes * g->H * row) || ensure(g, 0, g->d_recv, g->recv_pixels * kRecvBytes)) return -1;
+  if (exchange(g, pl, tile)) return fail_after_drain(g);
+  char* frame = reinterpret_cast<char*>(full) + plane * g->H * row;
+  hipError_t e = hipSetDevice(g->devices[0]);
+  for (int i = 0; i < g->n && e == hipSuccess; ++i)
+    e = hipMemcpy2DAsync(frame + i * row, g->n * row, i == 0 ? (const void*)tile(0) : g->d_recv + pl.bytes * g->recv_off[i], row, row, (size_t)g->rows[i],
+                         hipMemcpyDeviceToDevice, stream(g, 0));
+  if (e == hipSuccess) return 0;
+  pt_fail("placing the rows of a %zu-byte payload failed: %s", pl.bytes, hipGetErrorString(e));
+  return fail_after_drain(g);
+}
+// The tail of a write-out: `bytes` of a root buffer to the host on the root's stream, and every context synchronised.
+int to_host(PtGroup* g, void* host, const void* d_root, size_t bytes) {
+  HIP_OK(hipMemcpyAsync(host, d_root, bytes, hipMemcpyDeviceToHost, stream(g, 0)));
+  return pt_group_sync(g);
+}
+
+int gather_image(PtGroup* g) {  // -> g->d_full: W*H*3 floats
+  return gather(g, kRgb, [&](int i) { return pt_ctx_device_image(g->ctx[i]); }, g->d_full);
+}
+// `count` float4 planes of every context (planes(c): plane 0 of context c, the planes contiguous) -> full: the planes of the frame.
+// One exchange and placement per plane: a tile's planes are its pixel_count apart, not recv_pixels.
+template <typename PlanesFn>
+int gather_planes(PtGroup* g, int count, float*& full, PlanesFn planes) {
+  for (int pl = 0; pl < count; ++pl)
+    if (gather(g, kPlane, [&](int i) { return planes(g->ctx[i]) + 4 * (size_t)pl * pt_ctx_pixel_count(g->ctx[i]); }, full, count, pl)) return -1;
   return 0;
 }
+int gather_features(PtGroup* g) {  // -> g->d_full_feat: PT_FEATURE_PLANES planes of W*H float4
+  return gather_planes(g, PT_FEATURE_PLANES, g->d_full_feat, [](PtContext* c) { return pt_ctx_device_features(c); });
+}
+int gather_noise(PtGroup* g) {  // -> g->d_full_noise: PT_NOISE_PLANES planes of W*H float4
+  return gather_planes(g, PT_NOISE_PLANES, g->d_full_noise, [](PtContext* c) { return pt_ctx_device_noise(c); });
+}
+int gather_counts(PtGroup* g) {  // -> g->d_full_pair: the count planes, 8 bytes per pixel (where a round has the packed pairs)
+  return gather(g, kPair, [&](int i) { return pt_ctx_device_counts(g->ctx[i]); }, g->d_full_pair);
+}
+
 int need_features(PtGroup* g, const char* who) {
   for (PtContext* c : g->ctx)
     if (!pt_ctx_device_features(c)) return pt_fail("%s: no feature pass has been rendered (pt_group_render_features)", who);
-  return 0;
-}
-// `count` float4 planes of every context (planes(c): plane 0 of context c, the planes contiguous) -> *full: the planes of the frame
-template <typename PlanesFn>
-int assemble_planes(PtGroup* g, int count, float** full, PlanesFn planes) {
-  const size_t frame = (size_t)g->W * g->H;
-  if (!*full) HIP_OK(hipMalloc((void**)full, count * frame * 16));
-  if (!g->d_recv_feat) HIP_OK(hipMalloc((void**)&g->d_recv_feat, g->recv_pixels * 16));
-  for (int pl = 0; pl < count; ++pl) {  // the root's stream orders plane pl + 1's receives behind plane pl's placement
-    auto tile = [&](int i) { return planes(g->ctx[i]) + 4 * (size_t)pl * pt_ctx_pixel_count(g->ctx[i]); };
-    if (exchange(g, ncclFloat, 4, g->d_recv_feat, tile)) return fail_after_drain(g);
-    HIP_OK(hipSetDevice(g->devices[0]));
-    for (int i = 0; i < g->n; ++i)
-      if (place_rows(g, i, i == 0 ? tile(0) : g->d_recv_feat + 4 * g->recv_off[i], *full + 4 * pl * frame, 16)) return fail_after_drain(g);
-  }
-  return 0;
-}
-int assemble_features(PtGroup* g) {  // -> g->d_full_feat: PT_FEATURE_PLANES planes of W*H float4
-  return assemble_planes(g, PT_FEATURE_PLANES, &g->d_full_feat, [](PtContext* c) { return pt_ctx_device_features(c); });
-}
-int assemble_noise(PtGroup* g) {  // -> g->d_full_noise: PT_NOISE_PLANES planes of W*H float4
-  return assemble_planes(g, PT_NOISE_PLANES, &g->d_full_noise, [](PtContext* c) { return pt_ctx_device_noise(c); });
-}
-
-// 8 bytes per pixel of every context (the packed pairs of a round, the count planes at write-out) -> g->d_full_pair: the frame's
-int assemble_pairs(PtGroup* g, const std::vector<const int32_t*>& tiles) {
-  const size_t frame = (size_t)g->W * g->H;
-  HIP_OK(hipSetDevice(g->devices[0]));
-  if (!g->d_full_pair) HIP_OK(hipMalloc((void**)&g->d_full_pair, frame * 8));
-  if (!g->d_recv_pair) HIP_OK(hipMalloc((void**)&g->d_recv_pair, g->recv_pixels * 8));
-  if (exchange(g, ncclInt32, 2, g->d_recv_pair, [&](int i) { return tiles[i]; })) return fail_after_drain(g);
-  HIP_OK(hipSetDevice(g->devices[0]));
-  for (int i = 0; i < g->n; ++i)
-    if (place_rows(g, i, i == 0 ? tiles[0] : g->d_recv_pair + 2 * g->recv_off[i], g->d_full_pair, 8)) return fail_after_drain(g);
   return 0;
 }
 
@@ -239,20 +297,31 @@ int shared_state(PtGroup* g, const char* who, PtCtxState* out) {
   return 0;
 }
 
+// ---- the three filters of a group (n > 1), around what differs between them: the refusals in between and the launcher.
+// The head, after the arguments: no context failed half-way (uniform: or is in the adaptive state), every context has its features.
+int filter_admit(PtGroup* g, const char* who, bool uniform) {
+  for (PtContext* c : g->ctx)  // (a group's rounds bring its contexts into the adaptive state: one sample count no longer describes the image)
+    if (pt_ctx_admit_state(c, who, uniform)) return -1;
+  return need_features(g, who);
+}
+// The tail, after the last refusal: a context owns interleaved rows and cannot filter its own tile, so the SUM image, the feature
+// planes and, where the filter reads them, the noise planes and the count planes meet on the root device as for the gathers, and the
+// launcher every context uses (launch(stream, &d_out)) runs there on the root's stream over the whole frame.
+template <typename Launch>
+int filter_run(PtGroup* g, bool noise, bool counts, float* rgb_avg_host, Launch launch) {
+  const size_t frame = frame_pixels(g);
+  HIP_OK(hipSetDevice(g->devices[0]));
+  if (ensure(g, 0, g->d_denoise, pt_denoise_workspace_bytes(frame))) return -1;
+  if (gather_image(g) || gather_features(g) || (noise && gather_noise(g)) || (counts && gather_counts(g))) return -1;
+  const float* d_out = nullptr;
+  if (launch(stream(g, 0), &d_out)) return fail_after_drain(g);
+  return to_host(g, rgb_avg_host, d_out, frame * 12);
+}
+
 // One round of pt_group_adaptive_round_threshold for n > 1, after the arguments' refusals; the driver's min_pixels as in the context's round.
-//
-// Buffer order.  The root writes d_list and d_parts on its own stream; context i reads its part on ITS stream.
-//   COPY: context i's copy out of d_parts waits for parts_ready, recorded on the root's stream behind the partition.  The next
-//         round's pack exchange has the root's stream wait for ready[i], recorded on context i's stream behind that copy (and behind the
-//         render and merge that follow it), before the root selects and partitions again: the parts are never overwritten early.
-//   RCCL: the sends of the parts are on the root's stream like the partition before them and the next round's selection after them.
-//         Context i receives into its own d_part[i] on its stream, which also copies it into the context's list; the next receive
-//         into d_part[i] is behind that copy in stream order.
-// Either way the root's host thread has synchronised the root's stream in between (the read-back), and d_pack[i] is written by
-// context i's stream only after the exchange that read it: COPY through that synchronise, RCCL because the send is on that stream.
 int group_round(PtGroup* g, const char* who, int iter_first, int group_iters, float threshold, float max_fraction, int min_pixels, int* above, int* selected) {
   const int n = g->n, W = g->W, H = g->H;
-  const size_t frame = (size_t)W * H;
+  const size_t frame = frame_pixels(g);
   for (int i = 0; i < n; ++i)
     if (pt_ctx_adaptive_refusal(g->ctx[i], who, iter_first, group_iters, max_fraction, true)) return -1;
   if (pt_adaptive_check_threshold(who, threshold)) return -1;
@@ -261,35 +330,30 @@ int group_round(PtGroup* g, const char* who, int iter_first, int group_iters, fl
   PtCtxState shared{};
   if (shared_state(g, who, &shared)) return -1;
   const int cap = ptad::list_length((double)max_fraction, (int64_t)frame);
-  hipStream_t root = (hipStream_t)pt_ctx_stream(g->ctx[0]);
+  hipStream_t root = stream(g, 0);
 
   // the group's buffers: the first round
   HIP_OK(hipSetDevice(g->devices[0]));
-  if (!g->d_select) HIP_OK(hipMalloc(&g->d_select, pt_adaptive_select_bytes(frame)));
-  if (!g->d_partition) HIP_OK(hipMalloc(&g->d_partition, pt_group_partition_bytes(frame, n)));
-  if (!g->d_list) HIP_OK(hipMalloc((void**)&g->d_list, frame * sizeof(int32_t)));
-  if (!g->d_parts) HIP_OK(hipMalloc((void**)&g->d_parts, frame * sizeof(int32_t)));
-  if (!g->d_result) HIP_OK(hipMalloc((void**)&g->d_result, (2 + (size_t)n) * sizeof(uint32_t)));
+  if (ensure(g, 0, g->d_select, pt_adaptive_select_bytes(frame)) || ensure(g, 0, g->d_partition, pt_group_partition_bytes(frame, n)) ||
+      ensure(g, 0, g->d_list, frame * sizeof(int32_t)) || ensure(g, 0, g->d_parts, frame * sizeof(int32_t)) ||
+      ensure(g, 0, g->d_result, (2 + (size_t)n) * sizeof(uint32_t)))
+    return -1;
   if (!g->parts_ready) HIP_OK(hipEventCreateWithFlags(&g->parts_ready, hipEventDisableTiming));
   if (g->d_pack.empty()) g->d_pack.assign(n, nullptr), g->d_part.assign(n, nullptr);
   for (int i = 0; i < n; ++i) {
     const size_t pixels = (size_t)pt_ctx_pixel_count(g->ctx[i]);
     HIP_OK(hipSetDevice(g->devices[i]));
-    if (!g->d_pack[i]) HIP_OK(hipMalloc(&g->d_pack[i], pixels * 8));
-    if (i >= 1 && !g->d_part[i]) HIP_OK(hipMalloc((void**)&g->d_part[i], pixels * sizeof(int32_t)));
+    if (ensure(g, i, g->d_pack[i], pixels * 8) || (i >= 1 && ensure(g, i, g->d_part[i], pixels * sizeof(int32_t)))) return -1;
   }
 
   // collect on the root: every context packs on its own stream, one exchange, the rows into the frame, key, select, partition
-  std::vector<const int32_t*> tiles(n, nullptr);
   for (int i = 0; i < n; ++i) {
     if (pt_ctx_enter_adaptive(g->ctx[i])) return -1;
     HIP_OK(hipSetDevice(g->devices[i]));
-    if (pt_group_pack_launch((hipStream_t)pt_ctx_stream(g->ctx[i]), pt_ctx_pixel_count(g->ctx[i]), pt_ctx_device_noise(g->ctx[i]),
-                             pt_ctx_device_counts(g->ctx[i]), g->d_pack[i]))
-      return -1;
-    tiles[i] = static_cast<const int32_t*>(g->d_pack[i]);
+    if (pt_group_pack_launch(stream(g, i), pt_ctx_pixel_count(g->ctx[i]), pt_ctx_device_noise(g->ctx[i]), pt_ctx_device_counts(g->ctx[i]), g->d_pack[i])) return -1;
   }
-  if (assemble_pairs(g, tiles)) return -1;
+  HIP_OK(hipSetDevice(g->devices[0]));
+  if (gather(g, kPair, [&](int i) { return g->d_pack[i]; }, g->d_full_pair)) return -1;
   if (pt_group_keys_launch(root, W, H, g->d_full_pair, pt_adaptive_select_keys(g->d_select, frame)) ||
       pt_adaptive_select_threshold_keys_launch(root, W, H, threshold, cap, g->d_select, g->d_list) ||
       pt_group_partition_launch(root, W, n, g->d_list, pt_adaptive_select_result(g->d_select, frame), cap, g->d_partition, g->d_parts, g->d_result))
@@ -311,45 +375,20 @@ int group_round(PtGroup* g, const char* who, int iter_first, int group_iters, fl
   if (!render) return 0;  // nothing rendered or merged, no context counts a round
 
   // distribute and render: part i to context i, on context i's stream
-  HIP_OK(hipEventRecord(g->parts_ready, root));
-  std::vector<const int32_t*> lists(n, nullptr);
-  std::vector<size_t> off(n, 0);
-  for (int i = 1; i < n; ++i) off[i] = off[i - 1] + result[2 + (size_t)i - 1];
-  lists[0] = g->d_parts;
-  if (g->transport == PT_GROUP_TRANSPORT_COPY) {
-    for (int i = 1; i < n; ++i) {
-      hipStream_t si = (hipStream_t)pt_ctx_stream(g->ctx[i]);
-      const size_t bytes = (size_t)result[2 + (size_t)i] * sizeof(int32_t);
-      HIP_OK(hipSetDevice(g->devices[i]));
-      HIP_OK(hipStreamWaitEvent(si, g->parts_ready, 0));
-      if (bytes && g->devices[i] == g->devices[0]) HIP_OK(hipMemcpyAsync(g->d_part[i], g->d_parts + off[i], bytes, hipMemcpyDeviceToDevice, si));
-      else if (bytes) HIP_OK(hipMemcpyPeerAsync(g->d_part[i], g->devices[i], g->d_parts + off[i], g->devices[0], bytes, si));
-      lists[i] = g->d_part[i];
-    }
-  } else {
-    NCCL_OK(ncclGroupStart());
-    int rc = 0;
-    for (int i = 1; i < n && !rc; ++i) {  // an error inside the group must still close it
-      const size_t count = result[2 + (size_t)i];
-      lists[i] = g->d_part[i];
-      if (!count) continue;
-      ncclResult_t r = ncclSuccess;
-      if (hipSetDevice(g->devices[0]) != hipSuccess) rc = pt_fail("hipSetDevice(%d) failed", g->devices[0]);
-      else if ((r = ncclSend(g->d_parts + off[i], count, ncclInt32, i, g->comms[0], root)) != ncclSuccess)
-        rc = pt_fail("ncclSend to device %d failed: %s", g->devices[i], ncclGetErrorString(r));
-      else if (hipSetDevice(g->devices[i]) != hipSuccess) rc = pt_fail("hipSetDevice(%d) failed", g->devices[i]);
-      else if ((r = ncclRecv(g->d_part[i], count, ncclInt32, 0, g->comms[i], (hipStream_t)pt_ctx_stream(g->ctx[i]))) != ncclSuccess)
-        rc = pt_fail("ncclRecv on device %d failed: %s", g->devices[i], ncclGetErrorString(r));
-    }
-    const ncclResult_t e = ncclGroupEnd();
-    if (!rc && e != ncclSuccess) rc = pt_fail("ncclGroupEnd failed: %s", ncclGetErrorString(e));
-    if (rc) return fail_after_drain(g);
-  }
+  if (scatter_parts(g, result.data() + 2)) return -1;
   for (int i = 0; i < n; ++i) {  // asynchronous: the contexts render concurrently; a context without pixels counts the round
     const int pixels = pt_ctx_pixel_count(g->ctx[i]);
-    if (pt_ctx_adaptive_round_list_device(g->ctx[i], iter_first, group_iters, lists[i], (int)result[2 + (size_t)i], cap < pixels ? cap : pixels))
+    if (pt_ctx_adaptive_round_list_device(g->ctx[i], iter_first, group_iters, i == 0 ? g->d_parts : g->d_part[i], (int)result[2 + (size_t)i], cap < pixels ? cap : pixels))
       return fail_after_drain(g);
   }
+  return 0;
+}
+
+// group_iters == 0 means the iterations per batch of context 0 (pt_group_render_until, pt_group_render_threshold)
+int group_or_batch(PtGroup* g, int group_iters, int* group) {
+  PtStats st{};
+  if (!group_iters && pt_ctx_get_stats(g->ctx[0], &st)) return -1;
+  *group = group_iters ? group_iters : st.iters_per_batch;
   return 0;
 }
 
@@ -446,12 +485,10 @@ int pt_group_sync(PtGroup* g) {
 
 int pt_group_gather(PtGroup* g, float* rgb_sum_host) {
   if (!g || !rgb_sum_host) return pt_fail("pt_group_gather: bad argument");
-  const size_t frame = (size_t)g->W * g->H;
   HIP_OK(hipSetDevice(g->devices[0]));
   if (g->n == 1) return pt_ctx_readback(g->ctx[0], rgb_sum_host);
-  if (assemble_image(g)) return -1;
-  HIP_OK(hipMemcpyAsync(rgb_sum_host, g->d_full, frame * 12, hipMemcpyDeviceToHost, (hipStream_t)pt_ctx_stream(g->ctx[0])));
-  return pt_group_sync(g);
+  if (gather_image(g)) return -1;
+  return to_host(g, rgb_sum_host, g->d_full, frame_pixels(g) * 12);
 }
 
 // First-hit feature buffers (pt_ctx_render_features) of the whole frame: every context sums its own rows; the planes meet like
@@ -465,45 +502,35 @@ int pt_group_render_features(PtGroup* g, int iter_first, int iter_count) {
 
 int pt_group_gather_features(PtGroup* g, float* planes_host) {
   if (!g || !planes_host) return pt_fail("pt_group_gather_features: bad argument");
-  const size_t frame = (size_t)g->W * g->H;
   if (need_features(g, "pt_group_gather_features")) return -1;
   HIP_OK(hipSetDevice(g->devices[0]));
   if (g->n == 1) return pt_ctx_readback_features(g->ctx[0], planes_host);
-  if (assemble_features(g)) return -1;
-  HIP_OK(hipMemcpyAsync(planes_host, g->d_full_feat, PT_FEATURE_PLANES * frame * 16, hipMemcpyDeviceToHost, (hipStream_t)pt_ctx_stream(g->ctx[0])));
-  return pt_group_sync(g);
+  if (gather_features(g)) return -1;
+  return to_host(g, planes_host, g->d_full_feat, PT_FEATURE_PLANES * frame_pixels(g) * 16);
 }
 
-// pt_denoise of the whole frame: a context owns interleaved rows and cannot filter its own tile, so the SUM image and the planes
-// meet on the root device as for the two gathers, and the launcher every context uses runs there on the root's stream.
+// pt_denoise of the whole frame (filter_admit, filter_run): the SUM image and the feature planes meet on the root.
 int pt_group_denoise(PtGroup* g, float samples, const PtDenoiseOptions* opt, float* rgb_avg_host) {
-  if (!g || !rgb_avg_host) return pt_fail("pt_group_denoise: bad argument");
+  const char* who = "pt_group_denoise";
+  if (!g || !rgb_avg_host) return pt_fail("%s: bad argument", who);
   if (g->n == 1) return pt_ctx_denoise(g->ctx[0], samples, opt, rgb_avg_host);
-  const size_t frame = (size_t)g->W * g->H;
-  for (PtContext* c : g->ctx)  // (a group's rounds bring its contexts into the adaptive state: one sample count no longer describes the image)
-    if (pt_ctx_admit_state(c, "pt_group_denoise", true)) return -1;
-  if (need_features(g, "pt_group_denoise")) return -1;
+  if (filter_admit(g, who, true)) return -1;
   ptdn::Params P{};
-  if (pt_denoise_resolve("pt_group_denoise", samples, opt, &P)) return -1;
-  HIP_OK(hipSetDevice(g->devices[0]));
-  if (!g->d_denoise) HIP_OK(hipMalloc(&g->d_denoise, pt_denoise_workspace_bytes(frame)));
-  if (assemble_image(g) || assemble_features(g)) return -1;
-  hipStream_t root = (hipStream_t)pt_ctx_stream(g->ctx[0]);
-  const float* d_out = nullptr;
-  if (pt_denoise_launch(root, g->W, g->H, g->d_full, g->d_full_feat, samples, P, g->d_denoise, &d_out)) return fail_after_drain(g);
-  HIP_OK(hipMemcpyAsync(rgb_avg_host, d_out, frame * 12, hipMemcpyDeviceToHost, root));
-  return pt_group_sync(g);
+  if (pt_denoise_resolve(who, samples, opt, &P)) return -1;
+  return filter_run(g, false, false, rgb_avg_host, [&](hipStream_t root, const float** d_out) {
+    return pt_denoise_launch(root, g->W, g->H, g->d_full, g->d_full_feat, samples, P, g->d_denoise, d_out);
+  });
 }
 
 // pt_denoise_guided of the whole frame: as above, and the noise planes meet on the root like the feature planes.  The filter has ONE
-// M and T, so the contexts must agree on them (and none may hold unfolded iterations: its own call would be refused).
+// M and T, so the contexts must agree on them (and none may hold unfolded iterations: its own call would be refused).  The conditions
+// are checked context by context, so this is not shared_state() behind two loops: a caller who broke the agreement (pt_group_context)
+// would meet another first refusal.
 int pt_group_denoise_guided(PtGroup* g, const PtDenoiseOptions* opt, float* rgb_avg_host) {
-  if (!g || !rgb_avg_host) return pt_fail("pt_group_denoise_guided: bad argument");
+  const char* who = "pt_group_denoise_guided";
+  if (!g || !rgb_avg_host) return pt_fail("%s: bad argument", who);
   if (g->n == 1) return pt_ctx_denoise_guided(g->ctx[0], opt, rgb_avg_host);
-  const size_t frame = (size_t)g->W * g->H;
-  for (PtContext* c : g->ctx)
-    if (pt_ctx_admit_state(c, "pt_group_denoise_guided", true)) return -1;
-  if (need_features(g, "pt_group_denoise_guided")) return -1;
+  if (filter_admit(g, who, true)) return -1;
   int groups = 0, iters = 0;
   for (int i = 0; i < g->n; ++i) {
     int m = 0, t = 0;
@@ -516,15 +543,10 @@ int pt_group_denoise_guided(PtGroup* g, const PtDenoiseOptions* opt, float* rgb_
   }
   ptdn::Params P{};
   float Tf = 0.0f, Df = 0.0f;
-  if (pt_denoise_guided_resolve("pt_group_denoise_guided", groups, iters, opt, &P, &Tf, &Df)) return -1;
-  HIP_OK(hipSetDevice(g->devices[0]));
-  if (!g->d_denoise) HIP_OK(hipMalloc(&g->d_denoise, pt_denoise_workspace_bytes(frame)));
-  if (assemble_image(g) || assemble_features(g) || assemble_noise(g)) return -1;
-  hipStream_t root = (hipStream_t)pt_ctx_stream(g->ctx[0]);
-  const float* d_out = nullptr;
-  if (pt_denoise_guided_launch(root, g->W, g->H, g->d_full, g->d_full_feat, g->d_full_noise, Tf, Df, P, g->d_denoise, &d_out)) return fail_after_drain(g);
-  HIP_OK(hipMemcpyAsync(rgb_avg_host, d_out, frame * 12, hipMemcpyDeviceToHost, root));
-  return pt_group_sync(g);
+  if (pt_denoise_guided_resolve(who, groups, iters, opt, &P, &Tf, &Df)) return -1;
+  return filter_run(g, true, false, rgb_avg_host, [&](hipStream_t root, const float** d_out) {
+    return pt_denoise_guided_launch(root, g->W, g->H, g->d_full, g->d_full_feat, g->d_full_noise, Tf, Df, P, g->d_denoise, d_out);
+  });
 }
 
 // The noise estimate of the whole frame (pt_ctx_noise_fold): every context folds its own rows on its own stream, nothing is exchanged;
@@ -553,12 +575,8 @@ int pt_group_render_until(PtGroup* g, int iter_first, int max_iters, int group_i
   if (iter_first < 1 || max_iters < 1 || (int64_t)iter_first + max_iters - 1 > INT32_MAX || group_iters < 0 || !std::isfinite(target_db))
     return pt_fail("pt_group_render_until: iterations %d, +%d in groups of %d until %g dB: the first is >= 1, the count >= 1, the group >= 0 (0 = a batch), the target finite",
                    iter_first, max_iters, group_iters, (double)target_db);
-  int group = group_iters;
-  if (!group) {
-    PtStats st;
-    if (pt_ctx_get_stats(g->ctx[0], &st)) return -1;
-    group = st.iters_per_batch;
-  }
+  int group = 0;
+  if (group_or_batch(g, group_iters, &group)) return -1;
   int done = 0;
   float psnr = -1.0f;
   while (done < max_iters) {
@@ -598,12 +616,8 @@ int pt_group_render_threshold(PtGroup* g, int iter_first, int max_iters, int gro
   for (PtContext* c : g->ctx)
     if (pt_ctx_adaptive_refusal(c, who, iter_first, group_iters, max_fraction, false)) return -1;
   if (pt_adaptive_check_threshold(who, threshold)) return -1;
-  int group = group_iters;
-  if (!group) {
-    PtStats st;
-    if (pt_ctx_get_stats(g->ctx[0], &st)) return -1;
-    group = st.iters_per_batch;
-  }
+  int group = 0;
+  if (group_or_batch(g, group_iters, &group)) return -1;
   int done = 0, above = -1;
   int64_t samples = 0;
   while (done < max_iters) {
@@ -633,7 +647,7 @@ int pt_group_render_threshold(PtGroup* g, int iter_first, int max_iters, int gro
 int pt_group_gather_adaptive(PtGroup* g, int32_t* counts) {
   if (!g || !counts) return pt_fail("pt_group_gather_adaptive: bad argument");
   if (g->n == 1) return pt_ctx_readback_adaptive(g->ctx[0], counts);
-  const size_t frame = (size_t)g->W * g->H;
+  const size_t frame = frame_pixels(g);
   PtCtxState s{};
   if (shared_state(g, "pt_group_gather_adaptive", &s)) return -1;
   if (!s.adaptive) {
@@ -641,30 +655,22 @@ int pt_group_gather_adaptive(PtGroup* g, int32_t* counts) {
     for (size_t p = 0; p < frame; ++p) counts[2 * p] = (int32_t)std::min<int64_t>(s.iters, INT32_MAX), counts[2 * p + 1] = s.groups;
     return 0;
   }
-  std::vector<const int32_t*> tiles(g->n, nullptr);
-  for (int i = 0; i < g->n; ++i) tiles[i] = pt_ctx_device_counts(g->ctx[i]);
-  if (assemble_pairs(g, tiles)) return -1;
-  HIP_OK(hipMemcpyAsync(counts, g->d_full_pair, frame * 8, hipMemcpyDeviceToHost, (hipStream_t)pt_ctx_stream(g->ctx[0])));
-  return pt_group_sync(g);
+  HIP_OK(hipSetDevice(g->devices[0]));
+  if (gather_counts(g)) return -1;
+  return to_host(g, counts, g->d_full_pair, frame * 8);
 }
 
 // pt_resolve of the whole frame: every context resolves its own rows; the rows meet like the image (and in its buffers).
 int pt_group_resolve(PtGroup* g, float* rgb_avg_host) {
   if (!g || !rgb_avg_host) return pt_fail("pt_group_resolve: bad argument");
   if (g->n == 1) return pt_ctx_resolve(g->ctx[0], rgb_avg_host);
-  const size_t frame = (size_t)g->W * g->H;
+  const size_t frame = frame_pixels(g);
   std::vector<const float*> tiles(g->n, nullptr);
   for (int i = 0; i < g->n; ++i)
     if (pt_ctx_resolve_device(g->ctx[i], &tiles[i])) return -1;
   HIP_OK(hipSetDevice(g->devices[0]));
-  if (!g->d_full) HIP_OK(hipMalloc((void**)&g->d_full, frame * 12));
-  if (!g->d_recv) HIP_OK(hipMalloc((void**)&g->d_recv, g->recv_pixels * 12));
-  if (exchange(g, ncclFloat, 3, g->d_recv, [&](int i) { return tiles[i]; })) return fail_after_drain(g);
-  HIP_OK(hipSetDevice(g->devices[0]));
-  for (int i = 0; i < g->n; ++i)
-    if (place_rows(g, i, i == 0 ? tiles[0] : g->d_recv + 3 * g->recv_off[i], g->d_full, 12)) return fail_after_drain(g);
-  HIP_OK(hipMemcpyAsync(rgb_avg_host, g->d_full, frame * 12, hipMemcpyDeviceToHost, (hipStream_t)pt_ctx_stream(g->ctx[0])));
-  return pt_group_sync(g);
+  if (gather(g, kRgb, [&](int i) { return tiles[i]; }, g->d_full)) return -1;
+  return to_host(g, rgb_avg_host, g->d_full, frame * 12);
 }
 
 // pt_denoise_adaptive of the whole frame: as pt_group_denoise_guided, and in the adaptive state the count planes meet on the root too
@@ -674,10 +680,7 @@ int pt_group_denoise_adaptive(PtGroup* g, const PtDenoiseOptions* opt, float* rg
   const char* who = "pt_group_denoise_adaptive";
   if (!g || !rgb_avg_host) return pt_fail("%s: bad argument", who);
   if (g->n == 1) return pt_ctx_denoise_adaptive(g->ctx[0], opt, rgb_avg_host);
-  const size_t frame = (size_t)g->W * g->H;
-  for (PtContext* c : g->ctx)
-    if (pt_ctx_admit_state(c, who, false)) return -1;
-  if (need_features(g, who)) return -1;
+  if (filter_admit(g, who, false)) return -1;
   for (PtContext* c : g->ctx)
     if (!pt_ctx_device_noise(c) || pt_ctx_state(c).groups < 1) return pt_fail("%s: nothing has been folded (pt_group_noise_fold)", who);
   for (int i = 0; i < g->n; ++i)
@@ -689,42 +692,22 @@ int pt_group_denoise_adaptive(PtGroup* g, const PtDenoiseOptions* opt, float* rg
   if (s.iters > INT32_MAX) return pt_fail("%s: %lld iterations folded: the per-pixel counts are int32", who, (long long)s.iters);
   ptdn::Params P{};
   if (pt_denoise_adaptive_resolve(who, opt, &P)) return -1;
-  HIP_OK(hipSetDevice(g->devices[0]));
-  if (!g->d_denoise) HIP_OK(hipMalloc(&g->d_denoise, pt_denoise_workspace_bytes(frame)));
-  if (assemble_image(g) || assemble_features(g) || assemble_noise(g)) return -1;
-  if (s.adaptive) {
-    std::vector<const int32_t*> tiles(g->n, nullptr);
-    for (int i = 0; i < g->n; ++i) tiles[i] = pt_ctx_device_counts(g->ctx[i]);
-    if (assemble_pairs(g, tiles)) return -1;
-  }
-  hipStream_t root = (hipStream_t)pt_ctx_stream(g->ctx[0]);
-  const float* d_out = nullptr;
-  if (pt_denoise_adaptive_launch(root, g->W, g->H, g->d_full, g->d_full_feat, g->d_full_noise, s.adaptive ? g->d_full_pair : nullptr, (int)s.iters, s.groups, P,
-                                 g->d_denoise, &d_out))
-    return fail_after_drain(g);
-  HIP_OK(hipMemcpyAsync(rgb_avg_host, d_out, frame * 12, hipMemcpyDeviceToHost, root));
-  return pt_group_sync(g);
+  return filter_run(g, true, s.adaptive, rgb_avg_host, [&](hipStream_t root, const float** d_out) {
+    return pt_denoise_adaptive_launch(root, g->W, g->H, g->d_full, g->d_full_feat, g->d_full_noise, s.adaptive ? g->d_full_pair : nullptr, (int)s.iters, s.groups, P,
+                                      g->d_denoise, d_out);
+  });
 }
 
 int pt_group_gather_u8(PtGroup* g, float samples, uint8_t* rgb8_host) {
   if (!g || !rgb8_host) return pt_fail("pt_group_gather_u8: bad argument");
-  const size_t frame = (size_t)g->W * g->H;
+  const size_t frame = frame_pixels(g);
   std::vector<const uint8_t*> tiles(g->n, nullptr);
   for (int i = 0; i < g->n; ++i)  // every device converts its own rows (x mirror is inside a row)
     if (pt_ctx_save_u8_device(g->ctx[i], samples, &tiles[i])) return -1;
   HIP_OK(hipSetDevice(g->devices[0]));
-  if (g->n == 1) {
-    HIP_OK(hipMemcpyAsync(rgb8_host, tiles[0], frame * 3, hipMemcpyDeviceToHost, (hipStream_t)pt_ctx_stream(g->ctx[0])));
-    return pt_group_sync(g);
-  }
-  if (!g->d_full8) HIP_OK(hipMalloc((void**)&g->d_full8, frame * 3));
-  if (!g->d_recv8) HIP_OK(hipMalloc((void**)&g->d_recv8, g->recv_pixels * 3));
-  if (exchange(g, ncclUint8, 3, g->d_recv8, [&](int i) { return tiles[i]; })) return fail_after_drain(g);
-  HIP_OK(hipSetDevice(g->devices[0]));
-  for (int i = 0; i < g->n; ++i)
-    if (place_rows(g, i, i == 0 ? tiles[0] : g->d_recv8 + 3 * g->recv_off[i], g->d_full8, 3)) return fail_after_drain(g);
-  HIP_OK(hipMemcpyAsync(rgb8_host, g->d_full8, frame * 3, hipMemcpyDeviceToHost, (hipStream_t)pt_ctx_stream(g->ctx[0])));
-  return pt_group_sync(g);
+  if (g->n == 1) return to_host(g, rgb8_host, tiles[0], frame * 3);
+  if (gather(g, kRgb8, [&](int i) { return tiles[i]; }, g->d_full8)) return -1;
+  return to_host(g, rgb8_host, g->d_full8, frame * 3);
 }
 
 // Convergence metric of the whole frame (PtOptions.convergence in `base`): every context keeps the sums of its own rows; they
@@ -778,27 +761,17 @@ int pt_group_iterations_to_clean(PtGroup* g, float threshold_db, int* iteration)
 // batches while rendering continues; it synchronises the devices (the image is read at a batch boundary).
 int pt_group_preview_rgba8(PtGroup* g, int iterations, uint8_t* rgba_host) {
   if (!g || !rgba_host || iterations <= 0) return pt_fail("pt_group_preview_rgba8: bad argument");
-  const size_t frame = (size_t)g->W * g->H;
+  const size_t frame = frame_pixels(g);
   if (g->d_prev.empty()) g->d_prev.assign(g->n, nullptr);
   for (int i = 0; i < g->n; ++i) {
     HIP_OK(hipSetDevice(g->devices[i]));
-    if (!g->d_prev[i]) HIP_OK(hipMalloc((void**)&g->d_prev[i], (size_t)pt_ctx_pixel_count(g->ctx[i]) * 4));
+    if (ensure(g, i, g->d_prev[i], (size_t)pt_ctx_pixel_count(g->ctx[i]) * 4)) return -1;
     if (pt_ctx_preview_rgba8_device(g->ctx[i], iterations, g->d_prev[i])) return -1;
   }
   HIP_OK(hipSetDevice(g->devices[0]));
-  if (g->n == 1) {
-    HIP_OK(hipMemcpyAsync(rgba_host, g->d_prev[0], frame * 4, hipMemcpyDeviceToHost, (hipStream_t)pt_ctx_stream(g->ctx[0])));
-    return pt_group_sync(g);
-  }
-  if (!g->d_full_prev) HIP_OK(hipMalloc((void**)&g->d_full_prev, frame * 4));  // kept in the group: previews recur every
-  if (!g->d_recv_prev) HIP_OK(hipMalloc((void**)&g->d_recv_prev, g->recv_pixels * 4));  // few batches; freed by release()
-  if (exchange(g, ncclUint8, 4, g->d_recv_prev, [&](int i) { return (const uint8_t*)g->d_prev[i]; })) return fail_after_drain(g);
-  HIP_OK(hipSetDevice(g->devices[0]));
-  for (int i = 0; i < g->n; ++i)
-    if (place_rows(g, i, i == 0 ? (const uint8_t*)g->d_prev[0] : g->d_recv_prev + 4 * g->recv_off[i], g->d_full_prev, 4))
-      return fail_after_drain(g);
-  HIP_OK(hipMemcpyAsync(rgba_host, g->d_full_prev, frame * 4, hipMemcpyDeviceToHost, (hipStream_t)pt_ctx_stream(g->ctx[0])));
-  return pt_group_sync(g);
+  if (g->n == 1) return to_host(g, rgba_host, g->d_prev[0], frame * 4);
+  if (gather(g, kRgba8, [&](int i) { return g->d_prev[i]; }, g->d_full_prev)) return -1;
+  return to_host(g, rgba_host, g->d_full_prev, frame * 4);
 }
 
 }  // extern "C"

@@ -775,8 +775,9 @@ int pt_group_render_until(PtGroup* g, int iter_first, int max_iters, int group_i
  * Refuses, allocating and launching nothing: what pt_adaptive_round_threshold refuses of any context, in its order, apart from the
  * tile's rows; then contexts that differ in the groups or iterations folded or in being in the adaptive state, naming the context.
  * m == 0 (or, in the driver, above <= min_pixels): nothing is rendered and no context counts a round.
- * The group's buffers (the packed frame and its receive buffer, the selection's workspace for W*H pixels, the frame's list and the
- * parts, all on the root; 8 + 4 bytes per tile pixel on every device) are allocated by the first round and freed by pt_group_destroy.
+ * The group's buffers (the packed frame, the selection's workspace for W*H pixels, the frame's list and the parts, all on the root;
+ * 8 + 4 bytes per tile pixel on every device) are allocated by the first round and freed by pt_group_destroy; the exchange goes through
+ * the one receive buffer of all the group's write-outs (16 bytes per pixel of the other contexts' tiles, allocated by the first of them).
  * pt_group_render_threshold is pt_render_threshold's loop over pt_group_render, pt_group_noise_fold and the round; group_iters 0 =
  * the first context's iters_per_batch, as in pt_group_render_until.
  * Out of scope: a group form of pt_adaptive_round / pt_render_adaptive, load balance between contexts whose parts differ in length
