@@ -87,6 +87,12 @@ class PtDenoiseOptions(C.Structure):
                 ("keep_albedo", C.c_int32)]
 
 
+class PtSetupTimes(C.Structure):
+    """Host wall-clock times of a renderer's setup and of its last camera move, ms (include/pt_amd.h: pt_get_setup_times)."""
+    _fields_ = [("tables_ms", C.c_double), ("upload_ms", C.c_double), ("buffers_ms", C.c_double), ("probe_ms", C.c_double),
+                ("set_camera_ms", C.c_double), ("set_camera_calls", C.c_int32)]
+
+
 class PtError(RuntimeError):
     pass
 
@@ -276,6 +282,17 @@ def lib() -> C.CDLL:
         L.pt_group_denoise_adaptive.argtypes = [C.c_void_p, _dno, _fp]
         L.pt_group_partition_host.argtypes = _partition
         L.pt_stage_group_partition.argtypes = _partition
+    if hasattr(L, "pt_set_camera"):
+        _cam = C.POINTER(PtCamera)
+        L.pt_set_camera.argtypes = [_cam]
+        L.pt_ctx_set_camera.argtypes = [C.c_void_p, _cam]
+        L.pt_group_set_camera.argtypes = [C.c_void_p, _cam]
+        L.pt_get_setup_times.argtypes = [C.POINTER(PtSetupTimes)]
+        L.pt_ctx_get_setup_times.argtypes = [C.c_void_p, C.POINTER(PtSetupTimes)]
+        L.pt_camera_tables_host.argtypes = [C.POINTER(PtSceneDesc), _cam, C.c_int, C.c_int, _ip, _ip, _ip]
+        L.pt_scene_orbit.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_float]
+        L.pt_scene_camera.argtypes = [C.c_void_p, _cam]
+        L.pt_scene_orbit_state.argtypes = [C.c_void_p, _fp, _fp, _fp]
     _lib = L
     return L
 
@@ -331,6 +348,27 @@ class Scene:
     def image_name(self) -> str:
         return lib().pt_scene_image_name(self._h).decode()
 
+    @property
+    def camera(self) -> PtCamera:
+        """A copy of the scene's camera as it stands (pt_scene_camera): what Renderer.set_camera takes."""
+        cam = PtCamera()
+        _check(lib().pt_scene_camera(self._h, C.byref(cam)))
+        return cam
+
+    def orbit(self, dphi: float, dtheta: float, dzoom: float) -> PtCamera:
+        """A mouse drag of the reference's viewer (pt_scene_orbit); `desc.camera` follows.  Returns the new camera."""
+        _check(lib().pt_scene_orbit(self._h, C.c_float(dphi), C.c_float(dtheta), C.c_float(dzoom)))
+        cam = self.camera
+        self.desc.camera = cam
+        return cam
+
+    @property
+    def orbit_state(self) -> Tuple[float, float, float]:
+        """(phi, theta, zoom) of main.cpp:63-71 as float32 values."""
+        v = [C.c_float(0) for _ in range(3)]
+        _check(lib().pt_scene_orbit_state(self._h, *(C.byref(x) for x in v)))
+        return tuple(float(x.value) for x in v)
+
     def geoms(self):
         return [self.desc.geoms[i] for i in range(self.desc.num_geoms)]
 
@@ -375,6 +413,16 @@ def selfcheck_ieee(kind: int, first: int, count: int, seed: int = 0, arith: str 
     n = C.c_uint64(0)
     _check(lib().pt_selfcheck_ieee(ARITH[arith], kind, first, count, seed, C.byref(n)))
     return int(n.value)
+
+
+def camera_tables_host(scene: "Scene", cam: PtCamera, debug_flags: int = 0, center_half: bool = False):
+    """The host rebuild of the camera-dependent scene tables against a fresh build (pt_camera_tables_host, no GPU):
+    (grid resolution at `cam` or (0, 0, 0), tightened leaves at `cam`, bit mask of the tables that differ; it must be 0)."""
+    res = (C.c_int32 * 3)()
+    tight, differing = C.c_int32(-1), C.c_int32(-1)
+    _check(lib().pt_camera_tables_host(C.byref(scene.desc), C.byref(cam), int(debug_flags), int(bool(center_half)), res,
+                                       C.byref(tight), C.byref(differing)))
+    return tuple(res), int(tight.value), int(differing.value)
 
 
 def build_transform(trs: Sequence[float]):
@@ -697,6 +745,16 @@ class Renderer:
         """Restart the accumulation (SUM image and statistics zeroed) on the same, already touched buffers."""
         _check(lib().pt_clear())
 
+    def set_camera(self, cam: PtCamera) -> None:
+        """Move the camera of the live renderer (pt_set_camera): from here on it gives what a renderer freshly created with
+        `cam` gives, without the teardown, the allocations and the traversal probe of a new one."""
+        _check(lib().pt_set_camera(C.byref(cam)))
+
+    def setup_times(self) -> PtSetupTimes:
+        t = PtSetupTimes()
+        _check(lib().pt_get_setup_times(C.byref(t)))
+        return t
+
     # ---- first-hit feature buffers (include/pt_amd.h: pt_render_features) ----
     def render_features(self, iter_first: int, iter_count: int) -> None:
         """Adds what the camera rays of iterations iter_first .. iter_first + iter_count - 1 see to the feature SUM buffers."""
@@ -937,6 +995,10 @@ class Group:
 
     def render(self, iter_first: int, iter_count: int) -> None:
         _check(lib().pt_group_render(self._h, int(iter_first), int(iter_count)))
+
+    def set_camera(self, cam: PtCamera) -> None:
+        """Renderer.set_camera on every context (pt_group_set_camera); a refusal leaves every context as it was."""
+        _check(lib().pt_group_set_camera(self._h, C.byref(cam)))
 
     def gather(self) -> np.ndarray:
         w, h = self.scene.resolution

@@ -3,6 +3,8 @@
 #include <cfloat>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <vector>
 
 #include "../../include/pathtrace_amd.hpp"
 #include "pt_scene.h"
@@ -17,6 +19,20 @@ int last_iter = 0;
 int arith_mode = PT_ARITH_EXACT;
 int aa_mode = 0;
 int conv_mode = 0;
+// pathtraceSetKeepRenderer: a renderer that pathtraceFree() parked instead of freeing, and what it was created from; the next
+// pathtraceInit() moves its camera (pt_set_camera) when nothing but the camera differs
+int keep_mode = 0;
+bool parked = false;
+struct Created {
+  std::vector<PtGeom> geoms;
+  std::vector<PtMaterial> materials;
+  int res[2] = {0, 0}, depth = 0, arith = 0, aa = 0, conv = 0;
+  bool same_but_camera(const Created& o) const {
+    auto equal = [](const auto& a, const auto& b) { return a.size() == b.size() && (a.empty() || !std::memcmp(a.data(), b.data(), a.size() * sizeof(a[0]))); };
+    return equal(geoms, o.geoms) && equal(materials, o.materials) && res[0] == o.res[0] && res[1] == o.res[1] && depth == o.depth && arith == o.arith &&
+           aa == o.aa && conv == o.conv;
+  }
+} created;
 
 void check(int rc, const char* what) {  // pathtrace.cu:141-150
   if (rc == 0) return;
@@ -33,6 +49,7 @@ void InitDataContainer(GuiDataContainer* imGuiData) { guiData = imGuiData; }
 void pathtraceSetArith(int pt_arith) { arith_mode = pt_arith; }
 void pathtraceSetAntialias(int on) { aa_mode = on ? 1 : 0; }
 void pathtraceSetConvergence(int n) { conv_mode = n; }
+void pathtraceSetKeepRenderer(int on) { keep_mode = on ? 1 : 0; }
 
 void pathtraceInit(pt::Scene* scene) {
   hst_scene = scene;
@@ -41,9 +58,22 @@ void pathtraceInit(pt::Scene* scene) {
   opt.arith = arith_mode;
   opt.aa_jitter = aa_mode;
   opt.convergence = conv_mode;
-  check(pt_init(&d, &opt), "pathtraceInit");
   q_count = 0;
   last_iter = 0;
+  const bool was_parked = parked;
+  parked = false;
+  if (keep_mode || was_parked) {
+    Created now;
+    now.geoms = scene->geoms, now.materials = scene->materials;
+    now.res[0] = d.camera.resolution[0], now.res[1] = d.camera.resolution[1];
+    now.depth = d.trace_depth, now.arith = arith_mode, now.aa = aa_mode, now.conv = conv_mode;
+    if (was_parked && keep_mode && now.same_but_camera(created)) {  // the camchanged case: the renderer stays, its camera moves
+      check(pt_set_camera(&d.camera), "pathtraceInit (pt_set_camera)");
+      return;
+    }
+    created = std::move(now);
+  }
+  check(pt_init(&d, &opt), "pathtraceInit");  // (frees a parked renderer first)
 }
 
 void pathtraceSyncImage() {
@@ -56,10 +86,21 @@ void pathtraceSyncImage() {
 
 void pathtraceFree() {
   if (hst_scene && last_iter > 0) pathtraceSyncImage();
-  check(pt_free(), "pathtraceFree");
+  if (keep_mode && hst_scene) parked = true;  // the image is read back as always; the renderer waits for the next pathtraceInit()
+  else if (!(keep_mode && parked)) {  // (a second pathtraceFree() leaves a parked renderer parked)
+    check(pt_free(), "pathtraceFree");
+    parked = false;
+  }
   hst_scene = nullptr;
   q_count = 0;
   last_iter = 0;
+}
+
+void pathtraceShutdown() {
+  pathtraceFree();
+  parked = false;
+  check(pt_free(), "pathtraceShutdown");
+  created = Created{};
 }
 
 void pathtrace(pt_uchar4* pbo, int /*frame*/, int iter) {

@@ -9,6 +9,7 @@
 //     no per-iteration malloc/free, no per-iteration D2H frame copies or printf;
 //   * K iterations are traced as one wavefront batch so each launch has enough rays;
 //   * kernel sizes are fixed (persistent grid), live counts stay on the device.
+#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -224,6 +225,15 @@ void plan_launch(Ctx& g) {
   g.qs.paths_W = g.grid_paths * ptk::kWavesPerBlock;  // what k_count_stats deals to the queues (a table made for another width is ignored)
 }
 
+// A grid's device memory back to the device (choose_traversal's losers, a camera move that changes a grid's size).
+static void free_grid(Ctx& g, const Ctx::DeviceGrid& d) {
+  for (void* p : {(void*)d.d_start, (void*)d.d_items, d.d_items_b != d.d_items ? (void*)d.d_items_b : nullptr}) {
+    if (!p) continue;
+    (void)hipFree(p);
+    g.allocs.erase(std::remove(g.allocs.begin(), g.allocs.end(), p), g.allocs.end());
+  }
+  g.device_bytes -= (int64_t)d.bytes;
+}
 // Grid or BVH scan, and which grid?  All give the same image (LABNOTES.md section 9.1); which is faster depends on how the
 // primitives are spread and how far rays fly, and no count of references predicted it across lattice, random and clustered
 // scenes — so it is measured: up to 8 iterations of the context's own tile with each (the second of two runs counts), before
@@ -231,16 +241,8 @@ void plan_launch(Ctx& g) {
 // the measurement.
 static int choose_traversal(Ctx& g) {
   auto drop_unused_grids = [&](size_t keep) {
-    for (size_t i = 0; i < g.grids.size(); ++i) {
-      const Ctx::DeviceGrid& d = g.grids[i];
-      if (i == keep) continue;
-      for (void* p : {(void*)d.d_start, (void*)d.d_items, d.d_items_b != d.d_items ? (void*)d.d_items_b : nullptr}) {
-        if (!p) continue;
-        (void)hipFree(p);
-        g.allocs.erase(std::remove(g.allocs.begin(), g.allocs.end(), p), g.allocs.end());
-      }
-      g.device_bytes -= (int64_t)d.bytes;
-    }
+    for (size_t i = 0; i < g.grids.size(); ++i)
+      if (i != keep) free_grid(g, g.grids[i]);
     g.grids = {g.grids[keep]};
     g.grid_pick = 0;
   };
@@ -341,15 +343,18 @@ static int open_device(Ctx& g, const PtOptions& opt) {
 }
 
 // The camera, the scene's sizes and the options that choose kernels and schedules.
-static void take_scene_and_options(Ctx& g, const PtSceneDesc* sc, const PtOptions& opt) {
-  g.cam = sc->camera;
-  g.depth = sc->trace_depth;
+static void take_camera(PtShared& g, const PtCamera& cam) {
+  g.cam = cam;
   g.dcam.res_x = g.cam.resolution[0], g.dcam.res_y = g.cam.resolution[1];
   std::memcpy(g.dcam.pos, g.cam.position, 12);
   std::memcpy(g.dcam.view, g.cam.view, 12);
   std::memcpy(g.dcam.up, g.cam.up, 12);
   std::memcpy(g.dcam.right, g.cam.right, 12);
   g.dcam.pl_x = g.cam.pixelLength[0], g.dcam.pl_y = g.cam.pixelLength[1];
+}
+static void take_scene_and_options(Ctx& g, const PtSceneDesc* sc, const PtOptions& opt) {
+  take_camera(g, sc->camera);
+  g.depth = sc->trace_depth;
   g.legacy = opt.legacy_traversal != 0;
   g.aa_jitter = opt.aa_jitter != 0;
   g.debug_flags = opt.debug_flags;
@@ -439,6 +444,16 @@ static const T* upload(Ctx& g, const std::vector<T>& v) {
   const hipError_t e = hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
   return e == hipSuccess ? p : (pt_fail("hipMemcpy(%zu bytes) failed: %s", v.size() * sizeof(T), hipGetErrorString(e)), nullptr);
 }
+static int upload_grid(Ctx& g, const pt::Grid& gr) {  // one more entry of g.grids
+  Ctx::DeviceGrid d{gr.shape, gr.guard, nullptr, nullptr, nullptr, 0, gr.start};
+  const int64_t before = g.device_bytes;
+  if (!(d.d_start = upload(g, gr.start)) || !(d.d_items = upload(g, gr.items))) return -1;
+  if (!(d.d_items_b = gr.items_b.empty() ? d.d_items : upload(g, gr.items_b))) return -1;
+  d.bytes = (size_t)(g.device_bytes - before);
+  d.items = gr.items.size();
+  g.grids.push_back(d);
+  return 0;
+}
 // What pt::build_scene_tables built, on the device (g.scene), the grids as candidates for choose_traversal().
 static int upload_tables(Ctx& g, const pt::HostTables& t) {
   ptk::SceneTables& s = g.scene;
@@ -452,14 +467,8 @@ static int upload_tables(Ctx& g, const pt::HostTables& t) {
   if (!(s.nodes = upload(g, t.nodes)) || !(s.geoms = upload(g, t.geoms)) || !(s.mats = upload(g, t.mats)) || !(s.top = upload(g, t.top))) return -1;
   s.nodes_b = s.nodes, s.top_b = s.top;  // the bounce kernels' box tables: the same, except for the fast build's centre / half extent copies
   if (!t.nodes_b.empty() && (!(s.nodes_b = upload(g, t.nodes_b)) || !(s.top_b = upload(g, t.top_b)))) return -1;
-  for (const pt::Grid& gr : t.grids) {
-    Ctx::DeviceGrid d{gr.shape, gr.guard, nullptr, nullptr, nullptr, 0, gr.start};
-    const int64_t before = g.device_bytes;
-    if (!(d.d_start = upload(g, gr.start)) || !(d.d_items = upload(g, gr.items))) return -1;
-    if (!(d.d_items_b = gr.items_b.empty() ? d.d_items : upload(g, gr.items_b))) return -1;
-    d.bytes = (size_t)(g.device_bytes - before);
-    g.grids.push_back(d);
-  }
+  for (const pt::Grid& gr : t.grids)
+    if (upload_grid(g, gr)) return -1;
   return 0;
 }
 
@@ -468,6 +477,27 @@ static __global__ void k_poison_records(ptd::Word4* rec, unsigned long long per_
   const float nan = __builtin_nanf("");
   for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (unsigned long long)gridDim.x * blockDim.x)
     rec[i] = ptd::Word4{nan, nan, nan, __int_as_float(ptk::chunk_pixel((int)(i / per_queue), 0, Q))};
+}
+
+static int poison_records(Ctx& g) {  // on the context's stream; the plan in g.ret must be the one the records were allocated for
+  const size_t regions = (size_t)g.qs.Q * g.ret.kmax, per_queue = (size_t)g.ret.kmax * g.ret.seg_cap;
+  hipLaunchKernelGGL(k_poison_records, dim3((unsigned)std::min<size_t>((regions * g.ret.seg_cap + 255) / 256, 65536)), dim3(256), 0, g.stream, g.ret.rec,
+                     (unsigned long long)per_queue, (unsigned long long)(regions * g.ret.seg_cap), g.qs.Q);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+static size_t sub_words_max(const Ctx& g) { return ptk::sub_stride(g.num_cus * 8 * ptk::kWavesPerBlock, g.qs.Q); }  // (8 resident workgroups per CU at the most)
+
+// The "first batch of a context" state of alloc_batch_buffers again, on the stream, for a context that starts over with another view
+// (pt_ctx_set_camera): path buffers all ones, records poisoned, fill levels and the deal of the waves zero.  A slot wrongly gathered
+// from the previous view then shows as NaN, not as a plausible pixel.
+static int rearm_batch_buffers(Ctx& g) {
+  for (const ptd::PathBuf& pb : g.buf) HIP_OK(hipMemsetAsync(pb.r, 0xff, pathbuf_words(pb.stride) * sizeof(ptd::Word4), g.stream));
+  const size_t regions = (size_t)g.qs.Q * g.ret.kmax;
+  HIP_OK(hipMemsetAsync(g.ret.cnt, 0, regions * sizeof(*g.ret.cnt), g.stream));
+  HIP_OK(hipMemsetAsync(g.ret.sub, 0, regions * sub_words_max(g) * sizeof(*g.ret.sub), g.stream));
+  if (g.qs.deal) HIP_OK(hipMemsetAsync(g.qs.deal, 0, (size_t)ptk::deal_map(g.qs).words() * sizeof(int32_t), g.stream));
+  return poison_records(g);
 }
 
 // Path state, hit records, retirement records, image, counters.
@@ -481,19 +511,14 @@ int alloc_batch_buffers(Ctx& g) {
   if (!g.fuse_bounces && alloc_hitbuf(g, &g.hits, g.stride)) return -1;  // hit records reach HBM only in the unfused form
   {
     const size_t regions = (size_t)Q * g.ret.kmax;
-    const size_t wq_max = ptk::sub_stride(g.num_cus * 8 * ptk::kWavesPerBlock, Q);  // (8 resident workgroups per CU at the most)
+    const size_t wq_max = sub_words_max(g);
     if (dalloc(g, &g.ret.rec, regions * g.ret.seg_cap)) return -1;
     // the fill levels start at zero; k_collect re-zeroes them after every batch
     if (ensure(g, g.ret.cnt, regions * sizeof(*g.ret.cnt), Zero::blocking) || ensure(g, g.ret.sub, regions * wq_max * sizeof(*g.ret.sub), Zero::blocking)) return -1;
     // In a BatchInfo::retire_once batch nobody writes the retiree slots at the front of the regions k >= 1, and later they hold an older
     // batch's identical records: a gather that wrongly read them would still produce the right image.  So every slot starts as
     // (NaN, NaN, NaN, first pixel of the slot's queue) — a wrongly gathered slot then shows in the first batch of a context.
-    {
-      const size_t per_queue = (size_t)g.ret.kmax * g.ret.seg_cap;
-      hipLaunchKernelGGL(k_poison_records, dim3((unsigned)std::min<size_t>((regions * g.ret.seg_cap + 255) / 256, 65536)), dim3(256), 0, g.stream, g.ret.rec,
-                         (unsigned long long)per_queue, (unsigned long long)(regions * g.ret.seg_cap), Q);
-      HIP_OK(hipGetLastError());
-    }
+    if (poison_records(g)) return -1;
   }
   const size_t image_bytes = 3 * (size_t)g.N * sizeof(float);
   const size_t cnt_words = ptk::cnt_index(g.qs, g.depth + 1, 0);  // rows 0 .. depth; k_count_stats re-zeroes them after every batch
@@ -518,10 +543,24 @@ static int setup(Ctx& g, const PtSceneDesc* sc, const PtOptions& opt) {
   take_scene_and_options(g, sc, opt);
   if (plan_batches(g, opt)) return -1;
   if ((size_t)sc->num_materials * sizeof(ptd::Mat) > 60 * 1024) return pt_fail("pt_init: %zu materials exceed the LDS table", (size_t)sc->num_materials);
-  const pt::HostTables host = pt::build_scene_tables(*sc, g.debug_flags, g.k->boxes_center_half != 0);
+  using clock = std::chrono::steady_clock;
+  auto ms_since = [](clock::time_point t0) { return std::chrono::duration<double, std::milli>(clock::now() - t0).count(); };
+  clock::time_point t0 = clock::now();
+  const pt::HostTables host = pt::build_scene_tables(*sc, g.debug_flags, g.k->boxes_center_half != 0, pt::GridRequest{}, &g.camera_base);
+  g.setup_times.tables_ms = ms_since(t0), t0 = clock::now();
   if (upload_tables(g, host)) return -1;
+  g.setup_times.upload_ms = ms_since(t0), t0 = clock::now();
   plan_launch(g);
-  if (alloc_batch_buffers(g) || choose_traversal(g)) return -1;
+  if (alloc_batch_buffers(g)) return -1;
+  g.setup_times.buffers_ms = ms_since(t0), t0 = clock::now();
+  if (choose_traversal(g)) return -1;
+  g.setup_times.probe_ms = ms_since(t0);
+  // what a camera move rebuilds (pt_ctx_set_camera): the grid the kernels walk, at its resolution, or none
+  g.grid_request.kind = pt::GridRequest::kNone;
+  if (tables(g).use_grid) {
+    g.grid_request.kind = pt::GridRequest::kFixed;
+    std::memcpy(g.grid_request.res, g.grids[g.grid_pick].shape.res, sizeof(g.grid_request.res));
+  }
   g.time_kernels = opt.time_kernels != 0;
   g.conv_live = g.conv != 0;
   return 0;
@@ -591,6 +630,23 @@ void pt_scene_free(PtScene* s) { delete s; }
 int pt_scene_desc(const PtScene* s, PtSceneDesc* out) {
   if (!s || !out) return pt_fail("pt_scene_desc: null argument");
   *out = s->scene.desc();
+  return 0;
+}
+int pt_scene_orbit(PtScene* s, float dphi, float dtheta, float dzoom) {
+  if (!s) return pt_fail("pt_scene_orbit: null scene");
+  s->scene.orbit(dphi, dtheta, dzoom);
+  return 0;
+}
+int pt_scene_camera(const PtScene* s, PtCamera* out) {
+  if (!s || !out) return pt_fail("pt_scene_camera: null argument");
+  *out = s->scene.state.camera;
+  return 0;
+}
+int pt_scene_orbit_state(const PtScene* s, float* phi, float* theta, float* zoom) {
+  if (!s) return pt_fail("pt_scene_orbit_state: null scene");
+  if (phi) *phi = s->scene.phi;
+  if (theta) *theta = s->scene.theta;
+  if (zoom) *zoom = s->scene.zoom;
   return 0;
 }
 int pt_scene_iterations(const PtScene* s) { return s ? (int)s->scene.state.iterations : 0; }
@@ -846,6 +902,99 @@ int pt_ctx_clear(PtContext* c) {
   return pt_ctx_reset_stats(c);
 }
 
+// ---- moving the camera -----------------------------------------------------------------------
+}  // extern "C"
+// What pt_set_camera refuses, under the name `who`; a group asks every context before it changes one.
+int pt_ctx_camera_refusal(const PtContext* c, const PtCamera* cam, const char* who) {
+  if (need(c, who) || admit(*c, who, kNotFailed)) return -1;
+  if (!cam) return pt_fail("%s: null camera", who);
+  if (cam->resolution[0] != c->cam.resolution[0] || cam->resolution[1] != c->cam.resolution[1])
+    return pt_fail("%s: resolution %dx%d differs from the renderer's %dx%d; a new resolution needs pt_init", who, cam->resolution[0], cam->resolution[1],
+                   c->cam.resolution[0], c->cam.resolution[1]);
+  const struct {
+    const char* name;
+    const float* v;
+    int n;
+  } fields[] = {{"position", cam->position, 3}, {"view", cam->view, 3}, {"up", cam->up, 3}, {"right", cam->right, 3}, {"fov", cam->fov, 2}, {"pixelLength", cam->pixelLength, 2}};
+  for (const auto& f : fields)
+    for (int i = 0; i < f.n; ++i)
+      if (!std::isfinite(f.v[i])) return pt_fail("%s: camera %s[%d] is not finite", who, f.name, i);
+  return 0;
+}
+namespace {
+template <typename T>
+int reupload(const T* dev, const std::vector<T>& v) {  // into a table of unchanged size
+  HIP_OK(hipMemcpy(const_cast<T*>(dev), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  return 0;
+}
+// The camera-dependent tables for g.cam, on the device (setup()'s build_scene_tables + upload_tables for that part).  The stream is idle.
+int move_tables(Ctx& g) {
+  pt::HostTables t;
+  std::memcpy(t.root_min, g.scene.root_min, 12);
+  std::memcpy(t.root_max, g.scene.root_max, 12);
+  const bool center_half = g.k->boxes_center_half != 0;
+  pt::camera_tables(t, g.camera_base, g.cam.position, g.debug_flags, center_half, g.grid_request);
+  ptk::SceneTables& s = g.scene;
+  if (reupload(s.nodes, t.nodes) || reupload(s.top, t.top)) return -1;
+  if (center_half && (reupload(s.nodes_b, t.nodes_b) || reupload(s.top_b, t.top_b))) return -1;
+  s.cull_margin = t.cull_margin;
+  g.tight_leaves = t.tight_leaves;
+  // The grid: the one choose_traversal() kept is rebuilt at its resolution, or dropped (the probe preferred the BVH scan, or
+  // build_grid refuses for this camera).  Cell table and records are reused where their sizes are unchanged.
+  const pt::Grid* gr = t.grids.empty() ? nullptr : &t.grids[0];
+  if (!g.grids.empty()) {
+    Ctx::DeviceGrid& d = g.grids[g.grid_pick];
+    if (gr && gr->start.size() == d.start.size() && gr->items.size() == d.items && gr->items_b.empty() == (d.d_items_b == d.d_items)) {
+      if (reupload(d.d_start, gr->start) || reupload(d.d_items, gr->items)) return -1;
+      if (!gr->items_b.empty() && reupload(d.d_items_b, gr->items_b)) return -1;
+      d.shape = gr->shape, d.guard = gr->guard, d.start = gr->start;
+      return 0;
+    }
+    free_grid(g, d);
+    g.grids.clear();
+    g.grid_pick = 0;
+  }
+  return gr ? upload_grid(g, *gr) : 0;
+}
+}  // namespace
+extern "C" {
+
+int pt_ctx_set_camera(PtContext* c, const PtCamera* cam) {
+  if (pt_ctx_camera_refusal(c, cam, "pt_set_camera")) return -1;
+  const auto t0 = std::chrono::steady_clock::now();
+  Ctx& g = *c;
+  if (pt_ctx_sync(c)) return -1;
+  take_camera(g, *cam);
+  if (move_tables(g)) return g.failed = true, -1;  // (tables half replaced: nothing may render from them)
+  plan_launch(g);
+  g.record_form = g.gather_form = 0;
+  if (Ctx* w = g.worker) {  // the worker's view of the scene is a copy: camera, table pointers, grid and launch widths again
+    static_cast<PtShared&>(*w) = g;
+    set_worker_live(*w, w->capacity);
+    plan_launch(*w);
+    if (rearm_batch_buffers(*w)) return g.failed = true, -1;
+  }
+  if (rearm_batch_buffers(g)) return g.failed = true, -1;
+  if (pt_ctx_clear(c)) return -1;
+  g.setup_times.set_camera_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  g.setup_times.set_camera_calls += 1;
+  return 0;
+}
+
+int pt_ctx_get_setup_times(PtContext* c, PtSetupTimes* out) {
+  if (need(c, "pt_get_setup_times")) return -1;
+  if (!out) return pt_fail("pt_get_setup_times: null");
+  *out = c->setup_times;
+  return 0;
+}
+
+int pt_camera_tables_host(const PtSceneDesc* scene, const PtCamera* cam, int debug_flags, int center_half, int32_t grid_res_out[3],
+                          int32_t* tight_leaves, int32_t* differing) {
+  if (!scene || !cam || !grid_res_out || !tight_leaves || !differing || !scene->geoms || scene->num_geoms <= 0 || !scene->materials || scene->num_materials <= 0)
+    return pt_fail("pt_camera_tables_host: null argument");
+  return pt::camera_tables_check(*scene, *cam, debug_flags, center_half != 0, grid_res_out, tight_leaves, differing);
+}
+
 // ---- convergence metric ---------------------------------------------------------------------
 int pt_ctx_set_reference(PtContext* c, const float* rgb_avg_host) {
   if (need(c, "pt_set_reference")) return -1;
@@ -908,6 +1057,8 @@ int pt_preview_rgba8_device(int iterations, void* rgba_dev) { return pt_ctx_prev
 int pt_get_stats(PtStats* out) { return pt_ctx_get_stats(g_default, out); }
 int pt_reset_stats(void) { return pt_ctx_reset_stats(g_default); }
 int pt_clear(void) { return pt_ctx_clear(g_default); }
+int pt_set_camera(const PtCamera* cam) { return pt_ctx_set_camera(g_default, cam); }
+int pt_get_setup_times(PtSetupTimes* out) { return pt_ctx_get_setup_times(g_default, out); }
 int pt_render_features(int iter_first, int iter_count) { return pt_ctx_render_features(g_default, iter_first, iter_count); }
 int pt_readback_features(float* planes_host) { return pt_ctx_readback_features(g_default, planes_host); }
 int pt_denoise(float samples, const PtDenoiseOptions* opt, float* rgb_avg_host) { return pt_ctx_denoise(g_default, samples, opt, rgb_avg_host); }

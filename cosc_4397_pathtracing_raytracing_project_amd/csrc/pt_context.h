@@ -55,6 +55,7 @@ struct PtShared {
     const ptd::Node* d_items_b;  // == d_items unless the build wants centre / half extent
     size_t bytes;
     std::vector<uint32_t> start;  // the host copy of what d_start holds, guard cells included (pt_stage_grid_info)
+    size_t items = 0;             // records in d_items (a camera move reuses the buffers while the sizes stay)
   };
   std::vector<DeviceGrid> grids;
   size_t grid_pick = 0;  // grids[grid_pick] is the one the kernels walk (when grids is not empty)
@@ -131,6 +132,10 @@ struct PtContext : PtShared {
   void* d_acnt = nullptr;          // the plane cnt: N * ptad::Cnt
   void* d_select = nullptr;        // pt_adaptive_select_bytes(N)
   float* d_resolved = nullptr;     // [N][3], output of pt_ctx_resolve_device; absent until the first resolve
+  // Moving the camera (pt_ctx_set_camera): the camera-independent tables on the host, and the grid to rebuild (the one init kept)
+  pt::CameraBase camera_base;
+  pt::GridRequest grid_request;
+  PtSetupTimes setup_times{};
   bool adaptive = false;           // the adaptive state: from the first round to pt_clear
   int adaptive_rounds = 0;
   int64_t adaptive_last = 0;       // highest iteration number folded or merged
@@ -149,6 +154,7 @@ int pt_ctx_admit_state(const PtContext* c, const char* who, bool uniform);
 // What pt_adaptive_round_threshold refuses before its threshold, in its order and under the name `who`, apart from a tile that is not
 // whole contiguous rows; folds == false: apart from the state of the folds too (pt_render_threshold's first look).
 int pt_ctx_adaptive_refusal(const PtContext* c, const char* who, int iter_first, int group_iters, float max_fraction, bool folds);
+int pt_ctx_camera_refusal(const PtContext* c, const PtCamera* cam, const char* who);  // what pt_set_camera refuses, in its order; nothing changes
 int pt_ctx_enter_adaptive(PtContext* c);  // the count plane with the fold's (T, M) in every pixel, unless the context is in the adaptive state already
 
 namespace ptc {

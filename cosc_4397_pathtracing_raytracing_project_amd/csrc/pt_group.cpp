@@ -483,6 +483,16 @@ int pt_group_sync(PtGroup* g) {
   return 0;
 }
 
+// pt_ctx_set_camera on every context; all of them are asked before the first one changes.  The group's own buffers stay.
+int pt_group_set_camera(PtGroup* g, const PtCamera* cam) {
+  if (!g) return pt_fail("pt_group_set_camera: null group");
+  for (PtContext* c : g->ctx)
+    if (pt_ctx_camera_refusal(c, cam, "pt_group_set_camera")) return -1;
+  for (PtContext* c : g->ctx)
+    if (pt_ctx_set_camera(c, cam)) return -1;
+  return 0;
+}
+
 int pt_group_gather(PtGroup* g, float* rgb_sum_host) {
   if (!g || !rgb_sum_host) return pt_fail("pt_group_gather: bad argument");
   HIP_OK(hipSetDevice(g->devices[0]));

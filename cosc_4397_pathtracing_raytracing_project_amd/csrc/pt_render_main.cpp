@@ -3,7 +3,7 @@
 // state.iterations iterations, write the PNG saveImage() would write.  Flags exist only because
 // the reference takes resolution, iteration count and depth from the scene file (scene.cpp:103-114).
 //
-//   pt_render SCENE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr]
+//   pt_render SCENE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] [--orbit N]
 //                       [--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa]
 //                       [--preview N] [--convergence N | --reference FILE.pfm] [--clean-db X] [--features]
 //                       [--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]]
@@ -53,6 +53,11 @@
 // --denoise-adaptive (needs --adaptive F or --adaptive-threshold E; implies --features; excludes --denoise and --denoise-guided, takes the --denoise-* options,
 // sigma C's default being 8): the variance-guided filter with per-pixel sample counts (pt_denoise_adaptive) over the adaptive image,
 // after the resolved image is written.  Same output files as --denoise.
+// --orbit N (1 .. 999; excludes every option from --preview to --denoise-adaptive above): N views of the scene on ONE renderer, a full
+// turn around LOOKAT in steps of 2 pi / N — frame 0 is the scene's camera through pt_init (pt_group_create with --gpus / --devices),
+// frame f > 0 the viewer's mouse drag (pt_scene_orbit) followed by pt_set_camera (pt_group_set_camera) where the reference frees and
+// initialises; every frame renders iterations 1 .. --spp and is written as <base>.orbit<fff>.png (.pfm, .hdr).  Prints the setup
+// times once and per frame `orbit: frame f: camera x y z, set_camera a ms, render b ms`.
 // Output name: PREFIX.<spp>samp.png, or with --stamp the reference's own
 // <FILE>.<UTC start time>.<spp>samp.png (main.cpp:99-102).
 #include <hip/hip_runtime.h>
@@ -74,7 +79,7 @@
 int main(int argc, char** argv) {
   if (argc < 2) {
     std::printf("Usage: %s SCENEFILE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] "
-                "[--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa] [--preview N] "
+                "[--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa] [--orbit N] [--preview N] "
                 "[--convergence N | --reference FILE.pfm] [--clean-db X] [--features] "
                 "[--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]] [--denoise-guided] [--until-db X [--until-group G] [--adaptive F [--denoise-adaptive]]] "
                 "[--adaptive-threshold E [--adaptive-cap F] [--adaptive-min-pixels P] [--until-group G] [--denoise-adaptive]]\n", argv[0]);
@@ -84,7 +89,7 @@ int main(int argc, char** argv) {
   std::vector<int> device_list;
   bool pfm = false, hdr = false, stamp = false, aa = false, features = false, denoise = false, guided = false, dn_adaptive = false;
   PtDenoiseOptions dn_opt{};
-  int convergence = 0, until_group = 0;
+  int convergence = 0, until_group = 0, orbit = 0;  // orbit > 0: --orbit N
   bool until = false, until_group_given = false;
   float clean_db = 35.0f, until_db = 0.0f, adaptive = 0.0f;  // adaptive > 0: --adaptive F
   float threshold = 0.0f, threshold_cap = 0.25f;           // --adaptive-threshold E, --adaptive-cap F
@@ -98,6 +103,15 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) out = argv[++i];
     else if (!std::strcmp(argv[i], "--gpus") && i + 1 < argc) gpus = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--preview") && i + 1 < argc) preview = std::atoi(argv[++i]);
+    else if (!std::strcmp(argv[i], "--orbit") && i + 1 < argc) {
+      char* end = nullptr;
+      const long v = std::strtol(argv[++i], &end, 10);
+      if (end == argv[i] || *end || v < 1 || v > 999) {
+        std::fprintf(stderr, "--orbit wants the number of frames of a full turn around the scene, 1 to 999\n");
+        return 1;
+      }
+      orbit = (int)v;
+    }
     else if (!std::strcmp(argv[i], "--convergence") && i + 1 < argc) {
       convergence = std::atoi(argv[++i]);
       if (convergence <= 0) {
@@ -268,6 +282,21 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--until-db and --preview exclude each other (one loop over the iterations)\n");
     return 1;
   }
+  if (orbit > 0) {  // a plain render per frame: what works on the image of one view is not carried from view to view
+    const struct {
+      bool given;
+      const char* name;
+    } excluded[] = {{preview > 0, "--preview"}, {convergence > 0, "--convergence"}, {!reference.empty(), "--reference"}, {denoise, "--denoise"},
+                    {guided, "--denoise-guided"}, {dn_adaptive, "--denoise-adaptive"}, {features, "--features"}, {until, "--until-db"},
+                    {until_group_given, "--until-group"}, {adaptive > 0.0f, "--adaptive"}, {by_threshold, "--adaptive-threshold"},
+                    {threshold_cap_given, "--adaptive-cap"}, {threshold_min_given, "--adaptive-min-pixels"}};
+    for (const auto& e : excluded)
+      if (e.given) {
+        std::fprintf(stderr, "--orbit excludes %s (it renders --spp iterations per frame and writes the image; allowed: --res --spp --depth --arith --aa --pfm --hdr --out "
+                             "--stamp --gpus / --devices --transport)\n", e.name);
+        return 1;
+      }
+  }
   pt::Scene* scene = nullptr;
   try {
     scene = new pt::Scene(argv[1]);
@@ -349,7 +378,74 @@ int main(int argc, char** argv) {
   };
 
   double secs = 0;
-  if (gpus < 0) {
+  if (orbit > 0) {
+    // --orbit N: one renderer (or group), N views.  Frame 0 is the scene's camera through init; frame f > 0 follows a drag of 2 pi / N
+    // (pt::Scene::orbit, the viewer's mouse rule) and pt_set_camera / pt_group_set_camera where the viewer would free and init.
+    PtOptions opt{};
+    opt.arith = arith;
+    opt.aa_jitter = aa ? 1 : 0;
+    PtGroup* grp = nullptr;
+    std::vector<int> devices;
+    if (gpus >= 0) {
+      int ndev = 0;
+      if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        std::fprintf(stderr, "no HIP device\n");
+        return 1;
+      }
+      if (gpus == 0) gpus = ndev;
+      if (device_list.empty() && gpus > ndev) {
+        std::fprintf(stderr, "--gpus %d but only %d device(s) visible\n", gpus, ndev);
+        return 1;
+      }
+      for (int i = 0; i < gpus; ++i) devices.push_back(device_list.empty() ? i : device_list[i]);
+      for (int d : devices)
+        if (d < 0 || d >= ndev) {
+          std::fprintf(stderr, "device %d named but only %d device(s) visible\n", d, ndev);
+          return 1;
+        }
+    }
+    const PtSceneDesc desc = scene->desc();
+    if (gpus >= 0 ? pt_group_create_ex(&desc, &opt, devices.data(), gpus, transport, &grp) : pt_init(&desc, &opt)) {
+      std::fprintf(stderr, "HIP error (pt_init): %s\n", pt_last_error());
+      return EXIT_FAILURE;
+    }
+    PtSetupTimes st{};
+    if (grp ? pt_ctx_get_setup_times(pt_group_context(grp, 0), &st) : pt_get_setup_times(&st)) {
+      std::fprintf(stderr, "HIP error (pt_get_setup_times): %s\n", pt_last_error());
+      return EXIT_FAILURE;
+    }
+    std::printf("setup: tables %.3f ms, upload %.3f ms, buffers %.3f ms, probe %.3f ms\n", st.tables_ms, st.upload_ms, st.buffers_ms, st.probe_ms);
+    scene->state.image.resize((size_t)W * H * 3);
+    const float step = (float)(2.0 * 3.14159265358979323846 / orbit);
+    for (int f = 0; f < orbit; ++f) {
+      double move_ms = 0.0;
+      if (f > 0) {
+        scene->orbit(step, 0.0f, 0.0f);
+        const auto m0 = std::chrono::high_resolution_clock::now();
+        if (grp ? pt_group_set_camera(grp, &scene->state.camera) : pt_set_camera(&scene->state.camera)) {
+          std::fprintf(stderr, "HIP error (pt_set_camera): %s\n", pt_last_error());
+          return EXIT_FAILURE;
+        }
+        move_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - m0).count();
+      }
+      const auto t0 = std::chrono::high_resolution_clock::now();
+      if (grp ? (pt_group_render(grp, 1, iters) || pt_group_gather(grp, scene->state.image.data())) : (pt_render(1, iters) || pt_readback(scene->state.image.data()))) {
+        std::fprintf(stderr, "HIP error (pt_render): %s\n", pt_last_error());
+        return EXIT_FAILURE;
+      }
+      const double render_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
+      const float* p = scene->state.camera.position;
+      std::printf("orbit: frame %d: camera %.9g %.9g %.9g, set_camera %.3f ms, render %.3f ms\n", f, (double)p[0], (double)p[1], (double)p[2], move_ms, render_ms);
+      char tag[32];
+      std::snprintf(tag, sizeof tag, ".orbit%03d", f);
+      const std::string frame = base + tag;
+      if (pt_save_png((frame + ".png").c_str(), scene->state.image.data(), W, H, (float)iters) == 0) std::printf("Saved %s.png.\n", frame.c_str());
+      if (pfm && pt_save_pfm((frame + ".pfm").c_str(), scene->state.image.data(), W, H, (float)iters) == 0) std::printf("Saved %s.pfm.\n", frame.c_str());
+      if (hdr && pt_save_hdr((frame + ".hdr").c_str(), scene->state.image.data(), W, H, (float)iters) == 0) std::printf("Saved %s.hdr.\n", frame.c_str());
+    }
+    if (grp) pt_group_destroy(grp);
+    else pt_free();
+  } else if (gpus < 0) {
     // the reference's call sequence (main.cpp:133-152) through the pathtrace.h shim
     GuiDataContainer gui;
     InitDataContainer(&gui);

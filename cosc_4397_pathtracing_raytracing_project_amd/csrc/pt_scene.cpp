@@ -365,10 +365,23 @@ void Scene::applyInitialCameraState() {
   // main.cpp:63-70 — orbit angles and zoom from the loaded camera
   const V3 viewXZ = normalize3({view.x, 0.0f, view.z});
   const V3 viewZY = normalize3({0.0f, view.y, view.z});
-  const float phi = std::acos(dot3(viewXZ, {0, 0, -1}));
-  const float theta = std::acos(dot3(viewZY, {0, 1, 0}));
-  const float zoom = length3({pos.x - look.x, pos.y - look.y, pos.z - look.z});
-  // main.cpp:110-128 — first runCuda() with camchanged == true
+  phi = std::acos(dot3(viewXZ, {0, 0, -1}));
+  theta = std::acos(dot3(viewZY, {0, 1, 0}));
+  zoom = length3({pos.x - look.x, pos.y - look.y, pos.z - look.z});
+  applyOrbitState();  // main.cpp:110-128 — first runCuda() with camchanged == true
+}
+
+void Scene::orbit(float dphi, float dtheta, float dzoom) {
+  const float pi = 3.1415926535897932384626422832795028841971f;  // utilities.h:9
+  phi += dphi;
+  theta = fmaxf(0.001f, fminf(theta + dtheta, pi));
+  zoom = fmaxf(0.1f, zoom + dzoom);
+  applyOrbitState();
+}
+
+void Scene::applyOrbitState() {
+  PtCamera& cam = state.camera;
+  const V3 look{cam.lookAt[0], cam.lookAt[1], cam.lookAt[2]};
   V3 cp;
   cp.x = zoom * std::sin(phi) * std::sin(theta);
   cp.y = zoom * std::cos(theta);

@@ -33,7 +33,13 @@ class Scene {  // src/scene.h:11-26
   void overrideResolution(int w, int h);
   // main.cpp:57-71 + 110-128: what the first runCuda() does to the camera.
   void applyInitialCameraState();
+  // main.cpp:192-199: a mouse drag in float (phi += dphi, theta and zoom clamped as there), then the camchanged block.
+  void orbit(float dphi, float dtheta, float dzoom);
+  float phi = 0.0f, theta = 0.0f, zoom = 0.0f;  // main.cpp:63-71, set by applyInitialCameraState()
   PtSceneDesc desc() const;
+
+ private:
+  void applyOrbitState();  // main.cpp:112-126: the camera from phi, theta, zoom and lookAt
 };
 
 // utilities.cpp:64-72 / scene.cpp:83-86 restated (exposed for tests).

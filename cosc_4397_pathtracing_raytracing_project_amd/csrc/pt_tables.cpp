@@ -226,7 +226,7 @@ void origin_region(const float root_min[3], const float root_max[3], const float
 // for a small scene far from the origin (|coordinate| / extent >~ 1e3) 1e-4 * extent alone would sink below the
 // walk's rounding; the pad therefore never goes below 64 ulps of that magnitude.
 bool build_grid(const std::vector<ptd::Node>& nodes, const PtGeom* geoms, int num_geoms, const float root_min[3], const float root_max[3],
-                double coord_mag, double density, bool forced, Grid& grid) {
+                double coord_mag, double density, bool forced, Grid& grid, const int* fixed_res) {
   std::vector<int> leaves;
   for (size_t i = 0; i < nodes.size(); ++i)
     if (nodes[i].geom >= 0) leaves.push_back((int)i);
@@ -269,7 +269,9 @@ bool build_grid(const std::vector<ptd::Node>& nodes, const PtGeom* geoms, int nu
   };
   GridShape& s = grid.shape;
   const double base = std::cbrt((double)leaves.size() / vol);
-  if (density > 0.0) {
+  if (fixed_res) {
+    for (int a = 0; a < 3; ++a) s.res[a] = std::min(512, std::max(1, fixed_res[a]));
+  } else if (density > 0.0) {
     resolution(std::cbrt(density) * base, s.res);
   } else {
     double best_cost = INFINITY;
@@ -363,34 +365,83 @@ double scene_magnitude(const float root_min[3], const float root_max[3], const f
   return m;
 }
 
-HostTables build_scene_tables(const PtSceneDesc& desc, int debug_flags, bool center_half) {
-  HostTables t;
-  ThreadedBvh bvh = threaded_bvh(desc.geoms, desc.num_geoms);
-  build_top(bvh.ref, bvh.nodes, bvh.where, desc.geoms, t.top, &t.top_xor);
-  t.nodes = std::move(bvh.nodes);
-  std::memcpy(t.root_min, bvh.ref[0].bmin, 12);
-  std::memcpy(t.root_max, bvh.ref[0].bmax, 12);
+// What follows the camera position (pt_tables.h).  The order matters: the copies and the grids are made from the tightened boxes.
+void camera_tables(HostTables& t, const CameraBase& base, const float cam[3], int debug_flags, bool center_half, const GridRequest& request) {
+  t.nodes = base.nodes;
+  t.top = base.top;
+  t.tight_leaves = 0;
   if ((int)t.nodes.size() >= kTightNodes && !(debug_flags & 2048)) {
     double olo[3], ohi[3];
-    origin_region(t.root_min, t.root_max, desc.camera.position, olo, ohi);
-    t.tight_leaves = tighten_sphere_leaves(t.nodes, desc.geoms, olo, ohi);
+    origin_region(t.root_min, t.root_max, cam, olo, ohi);
+    t.tight_leaves = tighten_sphere_leaves(t.nodes, base.geoms.data(), olo, ohi);
     for (ptd::TopEntry& e : t.top)
       if (e.link < 0) std::memcpy(e.bmin, t.nodes[e.idx].bmin, 12), std::memcpy(e.bmax, t.nodes[e.idx].bmax, 12);
   }
   {
     // SceneTables::cull_margin: >= 10x the worst undershoot of a reported hit distance (1e-4 object units mapped
     // to world space + rounding of the transforms at the scene's coordinate magnitudes)
-    float max_xf = 1.0f;
-    for (int i = 0; i < desc.num_geoms; ++i) {
-      const PtGeom& gm = desc.geoms[i];
-      if (gm.type == PT_GEOM_TRIANGLE) continue;  // world-space test: the pull-back is 1e-4 world units (max_xf >= 1 covers it)
-      float f = 0.f;
-      for (int c = 0; c < 3; ++c)
-        for (int r = 0; r < 3; ++r) f += gm.transform[c * 4 + r] * gm.transform[c * 4 + r];
-      max_xf = std::max(max_xf, sqrtf(f));
+    const float extent = std::max(1.0f, (float)scene_magnitude(t.root_min, t.root_max, cam));
+    t.cull_margin = 1e-3f * base.max_xf + 1e-4f * extent;
+  }
+  t.nodes_b.clear(), t.top_b.clear();
+  if (center_half) {  // the fast build: converted copies for the bounce kernels
+    const double mag = scene_magnitude(t.root_min, t.root_max, cam);
+    t.nodes_b = t.nodes;
+    for (ptd::Node& n : t.nodes_b) center_half_box(n.bmin, n.bmax, n.geom < 0, mag);
+    t.top_b = t.top;
+    for (ptd::TopEntry& e : t.top_b) center_half_box(e.bmin, e.bmax, e.link >= 0, mag);
+  }
+  t.grids.clear();
+  const bool forced = (debug_flags & 256) != 0;
+  const bool candidates = request.kind == GridRequest::kCandidates && ((int)t.nodes.size() >= kGridNodes || forced);
+  if ((candidates || request.kind == GridRequest::kFixed) && !(debug_flags & 512)) {
+    double cam_mag = 0.0;
+    for (int a = 0; a < 3; ++a) cam_mag = std::max(cam_mag, std::fabs((double)cam[a]));
+    // Candidates: the resolution the host's cost model finds (about one cell per primitive; build_grid) and two finer ones.
+    // The model prices a uniform spread of primitives and rays; where the primitives cluster, a finer grid pays (clustered 1500
+    // objects: 2319 Msamples/s at the model's resolution, 2931 at 8 cells per primitive; a lattice wants exactly its pitch),
+    // so choose_traversal() measures.  A forced grid (debug_flags 256) is the only candidate, as is one of a given resolution.
+    std::vector<double> densities{0.0};
+    if (!forced && candidates) densities.insert(densities.end(), {4.0, 8.0});
+    for (double density : densities) {
+      Grid grid;
+      if (!build_grid(t.nodes, base.geoms.data(), (int)base.geoms.size(), t.root_min, t.root_max, cam_mag, density, forced, grid,
+                      candidates ? nullptr : request.res))
+        continue;
+      bool repeat = false;
+      for (const Grid& o : t.grids) repeat = repeat || std::equal(o.shape.res, o.shape.res + 3, grid.shape.res);
+      if (repeat) continue;
+      // the cell table with empty cells before and after it: a walk may run up to one cell per axis past the grid's far side
+      // before its distance test ends it (pt_grid.inc CellWalk)
+      grid.guard = (size_t)grid.shape.res[0] * grid.shape.res[1] + grid.shape.res[0] + 2;
+      const uint32_t total = grid.start.back();
+      grid.start.insert(grid.start.begin(), grid.guard, 0u);
+      grid.start.resize(grid.start.size() + grid.guard, total);
+      if (center_half) {  // the grid's records are leaf boxes
+        grid.items_b = grid.items;
+        for (ptd::Node& n : grid.items_b) center_half_box(n.bmin, n.bmax, false, 0.0);
+      }
+      t.grids.push_back(std::move(grid));
     }
-    const float extent = std::max(1.0f, (float)scene_magnitude(t.root_min, t.root_max, desc.camera.position));
-    t.cull_margin = 1e-3f * max_xf + 1e-4f * extent;
+  }
+}
+
+HostTables build_scene_tables(const PtSceneDesc& desc, int debug_flags, bool center_half, const GridRequest& request, CameraBase* keep) {
+  HostTables t;
+  CameraBase base;
+  ThreadedBvh bvh = threaded_bvh(desc.geoms, desc.num_geoms);
+  build_top(bvh.ref, bvh.nodes, bvh.where, desc.geoms, base.top, &t.top_xor);
+  base.nodes = std::move(bvh.nodes);
+  base.geoms.assign(desc.geoms, desc.geoms + desc.num_geoms);
+  std::memcpy(t.root_min, bvh.ref[0].bmin, 12);
+  std::memcpy(t.root_max, bvh.ref[0].bmax, 12);
+  for (int i = 0; i < desc.num_geoms; ++i) {
+    const PtGeom& gm = desc.geoms[i];
+    if (gm.type == PT_GEOM_TRIANGLE) continue;  // world-space test: the pull-back is 1e-4 world units (max_xf >= 1 covers it)
+    float f = 0.f;
+    for (int c = 0; c < 3; ++c)
+      for (int r = 0; r < 3; ++r) f += gm.transform[c * 4 + r] * gm.transform[c * 4 + r];
+    base.max_xf = std::max(base.max_xf, sqrtf(f));
   }
   t.geoms.assign(desc.num_geoms, ptd::Geom{});
   for (int i = 0; i < desc.num_geoms; ++i) {
@@ -415,43 +466,62 @@ HostTables build_scene_tables(const PtSceneDesc& desc, int debug_flags, bool cen
     std::memcpy(t.mats[i].spec, m.specular_color, 12);
     t.mats[i].reflective = m.hasReflective, t.mats[i].refractive = m.hasRefractive, t.mats[i].emittance = m.emittance;
   }
-  if (center_half) {  // the fast build: converted copies for the bounce kernels
-    const double mag = scene_magnitude(t.root_min, t.root_max, desc.camera.position);
-    t.nodes_b = t.nodes;
-    for (ptd::Node& n : t.nodes_b) center_half_box(n.bmin, n.bmax, n.geom < 0, mag);
-    t.top_b = t.top;
-    for (ptd::TopEntry& e : t.top_b) center_half_box(e.bmin, e.bmax, e.link >= 0, mag);
-  }
-  if (((int)t.nodes.size() >= kGridNodes || (debug_flags & 256)) && !(debug_flags & 512)) {
-    double cam_mag = 0.0;
-    for (int a = 0; a < 3; ++a) cam_mag = std::max(cam_mag, std::fabs((double)desc.camera.position[a]));
-    // Candidates: the resolution the host's cost model finds (about one cell per primitive; build_grid) and two finer ones.
-    // The model prices a uniform spread of primitives and rays; where the primitives cluster, a finer grid pays (clustered 1500
-    // objects: 2319 Msamples/s at the model's resolution, 2931 at 8 cells per primitive; a lattice wants exactly its pitch),
-    // so choose_traversal() measures.  A forced grid (debug_flags 256) is the only candidate.
-    const bool forced = (debug_flags & 256) != 0;
-    std::vector<double> densities{0.0};
-    if (!forced) densities.insert(densities.end(), {4.0, 8.0});
-    for (double density : densities) {
-      Grid grid;
-      if (!build_grid(t.nodes, desc.geoms, desc.num_geoms, t.root_min, t.root_max, cam_mag, density, forced, grid)) continue;
-      bool repeat = false;
-      for (const Grid& o : t.grids) repeat = repeat || std::equal(o.shape.res, o.shape.res + 3, grid.shape.res);
-      if (repeat) continue;
-      // the cell table with empty cells before and after it: a walk may run up to one cell per axis past the grid's far side
-      // before its distance test ends it (pt_grid.inc CellWalk)
-      grid.guard = (size_t)grid.shape.res[0] * grid.shape.res[1] + grid.shape.res[0] + 2;
-      const uint32_t total = grid.start.back();
-      grid.start.insert(grid.start.begin(), grid.guard, 0u);
-      grid.start.resize(grid.start.size() + grid.guard, total);
-      if (center_half) {  // the grid's records are leaf boxes
-        grid.items_b = grid.items;
-        for (ptd::Node& n : grid.items_b) center_half_box(n.bmin, n.bmax, false, 0.0);
-      }
-      t.grids.push_back(std::move(grid));
-    }
-  }
+  camera_tables(t, base, desc.camera.position, debug_flags, center_half, request);
+  if (keep) *keep = std::move(base);
   return t;
+}
+
+GridRequest first_grid_request(const HostTables& t) {
+  GridRequest r;
+  r.kind = t.grids.empty() ? GridRequest::kNone : GridRequest::kFixed;
+  if (!t.grids.empty()) std::memcpy(r.res, t.grids[0].shape.res, sizeof(r.res));
+  return r;
+}
+
+// Bit i of the result: table i of the list in pt_amd.h (pt_camera_tables_host) differs between a and b.
+template <typename T>
+static bool same_bytes(const std::vector<T>& a, const std::vector<T>& b) {
+  return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
+}
+static int tables_differ(const HostTables& a, const HostTables& b) {
+  int d = 0;
+  d |= same_bytes(a.nodes, b.nodes) ? 0 : 1;
+  d |= same_bytes(a.nodes_b, b.nodes_b) ? 0 : 2;
+  d |= same_bytes(a.top, b.top) ? 0 : 4;
+  d |= same_bytes(a.top_b, b.top_b) ? 0 : 8;
+  d |= same_bytes(a.geoms, b.geoms) ? 0 : 16;
+  d |= same_bytes(a.mats, b.mats) ? 0 : 32;
+  d |= std::memcmp(&a.cull_margin, &b.cull_margin, sizeof(float)) == 0 ? 0 : 64;
+  d |= a.tight_leaves == b.tight_leaves && a.top_xor == b.top_xor ? 0 : 2048;
+  if (a.grids.empty() != b.grids.empty()) return d | 128;
+  if (a.grids.empty()) return d;
+  const Grid &ga = a.grids[0], &gb = b.grids[0];
+  d |= std::memcmp(&ga.shape, &gb.shape, sizeof(GridShape)) == 0 && ga.guard == gb.guard ? 0 : 128;
+  d |= same_bytes(ga.start, gb.start) ? 0 : 256;
+  d |= same_bytes(ga.items, gb.items) ? 0 : 512;
+  d |= same_bytes(ga.items_b, gb.items_b) ? 0 : 1024;
+  return d;
+}
+
+int camera_tables_check(const PtSceneDesc& desc, const PtCamera& cam, int debug_flags, bool center_half, int32_t grid_res_out[3], int32_t* tight_leaves,
+                        int32_t* differing) {
+  CameraBase base;
+  const HostTables init = build_scene_tables(desc, debug_flags, center_half, GridRequest{}, &base);
+  const GridRequest request = first_grid_request(init);
+  HostTables moved = init;
+  if (moved.grids.size() > 1) moved.grids.resize(1);
+  const HostTables home = moved;
+  camera_tables(moved, base, cam.position, debug_flags, center_half, request);
+  PtSceneDesc there = desc;
+  there.camera = cam;
+  const HostTables fresh = build_scene_tables(there, debug_flags, center_half, request);
+  int d = tables_differ(moved, fresh);
+  camera_tables(moved, base, desc.camera.position, debug_flags, center_half, request);  // and back: what init built, at init's resolution
+  d |= tables_differ(moved, home) << 16;
+  for (int a = 0; a < 3; ++a) grid_res_out[a] = fresh.grids.empty() ? 0 : fresh.grids[0].shape.res[a];
+  *tight_leaves = fresh.tight_leaves;
+  *differing = d;
+  return 0;
 }
 
 }  // namespace pt

@@ -32,8 +32,10 @@ struct Grid {
   std::vector<uint32_t> start;   // cell c's records: items[start[guard + c] .. start[guard + c + 1])
   std::vector<ptd::Node> items, items_b;  // items_b: centre / half extent copies, empty unless asked for
 };
+// fixed_res: a resolution taken as given (a renderer that moves its camera keeps the one chosen at init); the cost-model search and
+// `density` are skipped, everything else (pad, refusals, records) is computed as for any grid
 bool build_grid(const std::vector<ptd::Node>& nodes, const PtGeom* geoms, int num_geoms, const float root_min[3], const float root_max[3],
-                double coord_mag, double density, bool forced, Grid& grid);
+                double coord_mag, double density, bool forced, Grid& grid, const int* fixed_res = nullptr);
 void origin_region(const float root_min[3], const float root_max[3], const float cam[3], double olo[3], double ohi[3]);
 int tighten_sphere_leaves(std::vector<ptd::Node>& nodes, const PtGeom* geoms, const double origin_lo[3], const double origin_hi[3]);
 double scene_magnitude(const float root_min[3], const float root_max[3], const float cam[3]);
@@ -50,7 +52,30 @@ struct HostTables {              // what ptk::SceneTables points to, on the host
   int tight_leaves = 0;
   bool has_triangles = false;
 };
-// debug_flags: PtOptions.debug_flags; center_half: ptk::KernelApi::boxes_center_half
-HostTables build_scene_tables(const PtSceneDesc& desc, int debug_flags, bool center_half);
+// The part of the tables that does not follow the camera and that the part that does is rebuilt from: a renderer keeps it from init
+// (pt_ctx_set_camera), a few MB for 10 000 primitives.
+struct CameraBase {
+  std::vector<ptd::Node> nodes;    // the threaded BVH before tighten_sphere_leaves
+  std::vector<ptd::TopEntry> top;  // the top list before it copies the tightened leaves
+  std::vector<PtGeom> geoms;       // what sphere_tight_box and build_grid read
+  float max_xf = 1.0f;             // cull_margin's share of the transforms
+};
+// Which grids camera_tables() builds: the candidates for choose_traversal(), one grid of a given resolution, or none.
+struct GridRequest {
+  enum Kind { kCandidates, kFixed, kNone } kind = kCandidates;
+  int res[3] = {0, 0, 0};
+};
+// Everything in `t` that follows the camera position, from `base` and t.root_min / root_max: the tightened leaves in nodes and top,
+// tight_leaves, cull_margin, the centre / half extent copies, the grids.  build_scene_tables() ends with it, and a renderer that
+// moves its camera runs it again.  A kFixed grid that build_grid refuses for this camera leaves t.grids empty.
+void camera_tables(HostTables& t, const CameraBase& base, const float cam[3], int debug_flags, bool center_half, const GridRequest& request);
+// debug_flags: PtOptions.debug_flags; center_half: ptk::KernelApi::boxes_center_half; keep: receives the CameraBase
+HostTables build_scene_tables(const PtSceneDesc& desc, int debug_flags, bool center_half, const GridRequest& request = GridRequest{},
+                              CameraBase* keep = nullptr);
+// The grid a renderer without a timing probe has in use after build_scene_tables(): the cost model's candidate, as a request.
+GridRequest first_grid_request(const HostTables& t);
+// pt_camera_tables_host (include/pt_amd.h).
+int camera_tables_check(const PtSceneDesc& desc, const PtCamera& cam, int debug_flags, bool center_half, int32_t grid_res_out[3], int32_t* tight_leaves,
+                        int32_t* differing);
 
 }  // namespace pt

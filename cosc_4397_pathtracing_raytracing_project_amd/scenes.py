@@ -84,13 +84,18 @@ _CORNELL_OBJECTS = [
 ]
 
 
+# EYE / LOOKAT of the reference's scenes; the generators take others (`eye`, `lookat`: three numbers or strings each)
+_EYE = ("0.0", 5, "10.5")
+_LOOKAT = (0, 5, 0)
+
+
 def cornell_scene_text(res: Tuple[int, int] = (800, 800), iterations: int = 1000, depth: int = 8,
-                       name: str = "cornell") -> str:
+                       name: str = "cornell", eye=None, lookat=None) -> str:
     """Text equivalent to the reference's scenes/cornell.txt (RES/ITERATIONS/DEPTH adjustable)."""
     out: List[str] = []
     for i, m in enumerate(_CORNELL_MATERIALS):
         out.append(_material(i, **m))
-    out.append(_camera(res, 45, iterations, depth, name, ("0.0", 5, "10.5"), (0, 5, 0), (0, 1, 0)))
+    out.append(_camera(res, 45, iterations, depth, name, eye or _EYE, lookat or _LOOKAT, (0, 1, 0)))
     for i, (kind, mat, t, r, s) in enumerate(_CORNELL_OBJECTS):
         out.append(_object(i, kind, mat, t, r, s))
     return "".join(out)
@@ -107,13 +112,13 @@ def sphere_scene_text(res: Tuple[int, int] = (800, 800), iterations: int = 5000,
 
 
 def stress_scene_text(grid: Tuple[int, int, int] = (22, 22, 21), res: Tuple[int, int] = (1920, 1080),
-                      iterations: int = 2000, depth: int = 8, name: str = "stress") -> str:
+                      iterations: int = 2000, depth: int = 8, name: str = "stress", eye=None, lookat=None) -> str:
     """Config C5: cornell walls + light, sphere replaced by a grid of small
     alternating cubes/spheres (scale .25, materials cycling 1..4, rotated about y)."""
     out: List[str] = []
     for i, m in enumerate(_CORNELL_MATERIALS):
         out.append(_material(i, **m))
-    out.append(_camera(res, 45, iterations, depth, name, ("0.0", 5, "10.5"), (0, 5, 0), (0, 1, 0)))
+    out.append(_camera(res, 45, iterations, depth, name, eye or _EYE, lookat or _LOOKAT, (0, 1, 0)))
     idx = 0
     for kind, mat, t, r, s in _CORNELL_OBJECTS[:6]:
         out.append(_object(idx, kind, mat, t, r, s))
@@ -136,7 +141,7 @@ def stress_scene_text(grid: Tuple[int, int, int] = (22, 22, 21), res: Tuple[int,
 
 
 def random_scene_text(seed: int, n_objects: int, res: Tuple[int, int] = (96, 64), iterations: int = 16, depth: int = 8,
-                      clustered: bool = False, name: str = "random") -> str:
+                      clustered: bool = False, name: str = "random", eye=None, lookat=None) -> str:
     """Fuzz input for the parity tests: `n_objects` cubes / spheres with random translation, rotation about all three
     axes and NON-uniform scale inside (and poking through) the cornell box, random materials out of six (diffuse,
     mirror, partly reflective with / without the refractive flag, two emitters).  `clustered` puts 80 % of the
@@ -154,7 +159,7 @@ def random_scene_text(seed: int, n_objects: int, res: Tuple[int, int] = (96, 64)
         dict(rgb=(1, ".6", ".2"), emittance=".7"),
     ]
     out: List[str] = [_material(i, **m) for i, m in enumerate(mats)]
-    out.append(_camera(res, 45, iterations, depth, name, ("0.0", 5, "10.5"), (0, 5, 0), (0, 1, 0)))
+    out.append(_camera(res, 45, iterations, depth, name, eye or _EYE, lookat or _LOOKAT, (0, 1, 0)))
     idx = 0
     for kind, mat, t, r, sc in _CORNELL_OBJECTS[:6]:
         out.append(_object(idx, kind, min(mat, 2), t, r, sc))

@@ -5,7 +5,7 @@
 //   void InitDataContainer(GuiDataContainer*)   same
 //   void pathtraceInit(Scene*)                  same, Scene = pt::Scene (pt_scene.h; same public
 //                                               members geoms / materials / state as src/scene.h:20-25)
-//   void pathtraceFree()                        same (legal before Init and twice, main.cpp:134)
+//   void pathtraceFree()                        same (legal before Init and twice, main.cpp:134); see pathtraceSetKeepRenderer
 //   void pathtrace(uchar4* pbo,int frame,int i) same; pbo may be nullptr (headless) or a DEVICE
 //                                               pointer to W*H uchar4 (as the GL-mapped PBO is)
 // Errors keep the reference's convention: message on stderr + exit(EXIT_FAILURE)
@@ -49,3 +49,12 @@ void pathtraceSetConvergence(int n);
 // extension: flushes queued iterations and returns what the reference prints as "PSNR" after iteration `iter`
 // (pathtrace.cu:627-638): FLT_MAX where it prints "Inf" (no reference frame yet, or mse <= 1e-12)
 float pathtracePSNR(int iter);
+// extension: the reference answers every camera move with pathtraceFree(); pathtraceInit(scene) (main.cpp:110-136).  With this on
+// (default off: exactly the behaviour above) pathtraceFree() reads the image back as always but parks the renderer, and the next
+// pathtraceInit(scene) moves its camera (pt_set_camera: no teardown, no allocation, no traversal probe) when geoms and materials
+// compare equal to the parked renderer's and resolution, trace depth, arithmetic, anti-aliasing and convergence settings are the
+// same; in any other case it frees and initialises for real.  The images are the same either way.
+void pathtraceSetKeepRenderer(int on);
+// extension: frees a parked renderer (and a live one, like pathtraceFree); safe to call twice.  What a program that turned
+// pathtraceSetKeepRenderer on calls before it exits.
+void pathtraceShutdown();

@@ -215,6 +215,13 @@ int pt_scene_load(const char* path, int res_w, int res_h, PtScene** out);
 void pt_scene_free(PtScene* s);
 int pt_scene_desc(const PtScene* s, PtSceneDesc* out); /* pointers valid until pt_scene_free */
 int pt_scene_iterations(const PtScene* s);             /* CAMERA ITERATIONS */
+/* A mouse drag of the reference's viewer (main.cpp:192-199) in float on the orbit state pt_scene_load derived (main.cpp:63-71):
+ * phi += dphi; theta = fmaxf(0.001f, fminf(theta + dtheta, PI)); zoom = fmaxf(0.1f, zoom + dzoom); then the camchanged block
+ * (main.cpp:112-126) through the code pt_scene_load ran.  (0, 0, 0) leaves the camera as it is, bit for bit, for a scene whose
+ * theta and zoom lie inside the clamps.  pt_scene_desc must be called again to see the new camera. */
+int pt_scene_orbit(PtScene* s, float dphi, float dtheta, float dzoom);
+int pt_scene_camera(const PtScene* s, PtCamera* out);
+int pt_scene_orbit_state(const PtScene* s, float* phi, float* theta, float* zoom); /* any pointer may be NULL */
 const char* pt_scene_image_name(const PtScene* s);     /* CAMERA FILE */
 
 /* BVH exactly as pathtraceInit builds it (pathtrace.cu:34-111, 483-489).
@@ -293,9 +300,49 @@ int pt_preview_rgba8_device(int iterations, void* rgba_dev); /* same, into a dev
 int pt_get_stats(PtStats* out);
 int pt_reset_stats(void);
 /* Restart the accumulation without giving up the renderer: the SUM image and the statistics are zeroed, every buffer
- * stays allocated (and warm).  What the reference does by pathtraceFree() + pathtraceInit() when the camera moves
- * (main.cpp:134-135), minus the teardown. */
+ * stays allocated (and warm).  The camera stays where it is: what the reference does by pathtraceFree() + pathtraceInit()
+ * when the camera moves (main.cpp:134-135) is pt_set_camera, below. */
 int pt_clear(void);
+/* ---- moving the camera of a live renderer: what the reference answers with pathtraceFree() + pathtraceInit() after every
+ * mouse drag (main.cpp:110-136), without the teardown, the allocations, the host build of the camera-independent tables and the
+ * timing probe of the traversal structures.
+ * Contract: after a successful call every later call on the renderer gives what a renderer freshly created from the same scene,
+ * options and `cam` gives, bit for bit in all three PT_ARITH_* modes: the image, the feature buffers, the noise planes, the
+ * adaptive lists and counts, the resolved and the filtered images.  What may differ from a fresh renderer: the timing fields of
+ * PtStats, which traversal structure is walked (the choice of pt_init is kept, the probe does not run again; any valid structure
+ * gives the same image) and PtStats.device_bytes.
+ * A camera move is more than a new kernel argument: the tightened sphere leaves (pt_traversal_boxes) and their copies in the
+ * top list, the cull margin, the centre / half extent copies and the grid's pad all follow the camera position, so they are
+ * rebuilt on the host from a copy of the camera-independent tables the renderer keeps from pt_init (the threaded BVH, the top
+ * list, the PtGeoms), and uploaded: into the buffers they have when the size is unchanged, else into new ones.  A renderer that
+ * walks a grid rebuilds it at the resolution pt_init chose; where no grid can be built for the new camera (a camera so far away
+ * that the pad would swallow the cells) it walks the BVH scan (PtStats.grid_cells == 0) until a later camera allows the grid again.
+ * Then everything pt_clear does happens (the adaptive state is left, a supplied reference frame survives), the launch widths
+ * are planned again, an existing worker of the adaptive rounds receives the new camera and tables, and the path buffers and
+ * retirement records return to the state a new renderer has (every word a NaN).  Workspaces (features, filter, noise, selection,
+ * resolve, the byte image) stay allocated.  Synchronises.
+ * Refused, in this order, with nothing changed, allocated or launched: no renderer; a failed renderer; a null `cam`; a resolution
+ * other than the renderer's (a new resolution needs pt_init); a component of position, view, up, right, fov or pixelLength that
+ * is not finite.  lookAt is not read by the renderer. */
+int pt_set_camera(const PtCamera* cam);
+/* Host wall-clock times of a renderer's setup, in milliseconds: the host build of the scene tables, their upload, the
+ * allocation of the batch buffers, the timing probe of the traversal structures (0 where none ran), and the last pt_set_camera
+ * (its synchronise included) with the number of such calls since the renderer was created. */
+typedef struct PtSetupTimes {
+  double tables_ms, upload_ms, buffers_ms, probe_ms, set_camera_ms;
+  int32_t set_camera_calls;
+} PtSetupTimes;
+int pt_get_setup_times(PtSetupTimes* out);
+/* Host-only check of the rebuild (no GPU): builds the tables for `scene`, moves them to `cam` with the code pt_set_camera runs,
+ * builds fresh tables for `scene` with `cam` at the same grid resolution (the cost model's for scene->camera, where the scene
+ * has a grid) and compares byte for byte.  *differing receives a bit per table that differs: 1 nodes, 2 their centre / half
+ * extent copies, 4 the top list, 8 its copies, 16 geoms, 32 materials, 64 the cull margin, 128 the grid's shape (or that only one
+ * side has a grid), 256 its cell table with the guard cells, 512 its records, 1024 their copies, 2048 the count of tightened
+ * leaves; bits 16 and up: the same after moving back to scene->camera, against the tables built first.  It must be 0.
+ * grid_res_out: the grid at `cam` (0 0 0: none); *tight_leaves: the tightened leaves at `cam`.  center_half != 0: with the copies
+ * the FAST build uploads. */
+int pt_camera_tables_host(const PtSceneDesc* scene, const PtCamera* cam, int debug_flags, int center_half, int32_t grid_res_out[3],
+                          int32_t* tight_leaves, int32_t* differing);
 const char* pt_last_error(void);
 /* Device self-check.  The exact and fma kernels (and depth 0 of every mode) take correctly rounded square roots,
  * reciprocals and quotients from instruction sequences shorter than the compiler's general expansions whenever every
@@ -670,6 +717,8 @@ int pt_ctx_preview_rgba8_device(PtContext* c, int iterations, void* rgba_dev);
 int pt_ctx_get_stats(PtContext* c, PtStats* out);
 int pt_ctx_reset_stats(PtContext* c);
 int pt_ctx_clear(PtContext* c);
+int pt_ctx_set_camera(PtContext* c, const PtCamera* cam);
+int pt_ctx_get_setup_times(PtContext* c, PtSetupTimes* out);
 int pt_ctx_set_reference(PtContext* c, const float* rgb_avg_host);
 int pt_ctx_get_convergence(PtContext* c, int iter_first, int iter_count, double* sse);
 int pt_ctx_iterations_to_clean(PtContext* c, float threshold_db, int* iteration);
@@ -733,6 +782,9 @@ int pt_group_size(const PtGroup* g);
 PtContext* pt_group_context(PtGroup* g, int i);
 int pt_group_render(PtGroup* g, int iter_first, int iter_count); /* asynchronous on every device */
 int pt_group_sync(PtGroup* g);
+/* pt_set_camera on every context: the camera is checked against all of them before any of them changes, so a refusal leaves
+ * the whole group as it was; the group's own buffers on the root device stay. */
+int pt_group_set_camera(PtGroup* g, const PtCamera* cam);
 int pt_group_gather(PtGroup* g, float* rgb_sum_host);             /* W*H*3 floats, raw orientation */
 int pt_group_gather_u8(PtGroup* g, float samples, uint8_t* rgb8_host); /* W*H*3 bytes as pt_save_u8, converted on each device */
 /* The feature buffers of the whole frame: every context sums its own rows, the planes meet at the root like the image (one
