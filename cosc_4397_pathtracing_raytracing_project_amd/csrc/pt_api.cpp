@@ -25,7 +25,7 @@
 namespace {
 
 std::string g_err;
-constexpr int kDebugFlags = 16 | 32 | 64 | 128 | 256 | 512 | ptk::kRetireEveryIteration | 2048 | ptk::kWholeRecords | ptk::kNoFirstBounce | ptk::kRecordsByVisit | ptk::kTileGather;  // the PtOptions.debug_flags bits pt_init accepts
+constexpr int kDebugFlags = 16 | 32 | 64 | 128 | 256 | 512 | ptk::kRetireEveryIteration | 2048 | ptk::kWholeRecords | ptk::kNoFirstBounce | ptk::kRecordsByVisit | ptk::kTileGather | ptk::kPrimaryEveryBatch;  // the PtOptions.debug_flags bits pt_init accepts
 static_assert(sizeof(PtOptions) == 80, "capi.PtOptions mirrors this layout");
 static_assert(PT_CONVERGENCE_WAVES == ptk::kConvWaves, "pt_amd.h documents the size of the convergence metric's partial sums");
 }  // namespace
@@ -148,10 +148,23 @@ int run_batch(Ctx& g, int iter_first, int kb) {
   const ptk::KernelApi& k = *g.k;
   auto cnt_row = [&](int d) { return g.d_cnt + ptk::cnt_index(g.qs, d, 0); };  // the counter row of depth d
   int d0 = 0;
+  // Depth 0 once per camera (pt_sched.h primary_once): whether the first-hit records of an earlier batch serve this one.  Until this
+  // batch is submitted whole they serve nobody (a batch of another form overwrites them, a failed one leaves them undefined).
+  const bool once = g.fuse_primary && ptk::primary_once(b, g.debug_flags, ptk::search_form(sc), sc.num_mats, g.ret.seg_cap);
+  const bool had_first_hits = g.primary_valid;
+  g.primary_valid = false;
   if (g.fuse_primary) {
     // depth 0 in one launch; its survivors are the depth-1 input (buf[1], cnt[1])
-    k.primary(g.stream, g.grid_primary, sc, g.dcam, b, queues_for(g, g.grid_primary), cnt_row(0), cnt_row(1), g.buf[1],
-              g.ret);
+    const ptd::Queues pq = queues_for(g, g.grid_primary);
+    Ctx::PrimaryKey key;
+    std::memset(&key, 0, sizeof(key));
+    key.sc = sc, key.cam = g.dcam, key.b = b, key.b.iter_first = key.b.K = 0, key.qs = pq, key.out = g.buf[1], key.ret = g.ret;
+    key.kernels = &k, key.grid = g.grid_primary, key.debug_flags = g.debug_flags;
+    if (!(once && had_first_hits && std::memcmp(&key, &g.primary_key, sizeof(key)) == 0)) {
+      k.primary(g.stream, g.grid_primary, sc, g.dcam, b, pq, cnt_row(0), cnt_row(1), g.buf[1], g.ret);
+      g.primary_launches += 1;
+      std::memcpy(&g.primary_key, &key, sizeof(key));
+    }
     d0 = 1;
   } else {
     k.generate(g.stream, g.grid_gen, g.dcam, b, queues_for(g, g.grid_gen), g.buf[0], cnt_row(0));
@@ -204,6 +217,7 @@ int run_batch(Ctx& g, int iter_first, int kb) {
     else k.collect(g.stream, b, g.qs, g.ret, g.d_image);
   }
   HIP_OK(hipGetLastError());
+  g.primary_valid = once;
   g.samples += (int64_t)kb * g.N;
   if (g.pending_isect.size() > 16384) {
     HIP_OK(hipStreamSynchronize(g.stream));
@@ -223,6 +237,7 @@ void plan_launch(Ctx& g) {
   g.ret.wq0 = ptk::wave_slot(0, g.qs.Q, g.grid_primary * ptk::kWavesPerBlock).wq;  // the sub-lists' residue count (pt_device.h RetireBuf)
   g.grid_paths = (g.fuse_bounces && g.depth > 1) ? g.num_cus * std::min(g.cap_bpc, g.k->resident_blocks_per_cu(ptk::kPaths, t)) : 0;
   g.qs.paths_W = g.grid_paths * ptk::kWavesPerBlock;  // what k_count_stats deals to the queues (a table made for another width is ignored)
+  g.primary_valid = false;  // (the first-hit records of another plan: pt_sched.h primary_once)
 }
 
 // A grid's device memory back to the device (choose_traversal's losers, a camera move that changes a grid's size).
@@ -285,6 +300,7 @@ static int choose_traversal(Ctx& g) {
   HIP_OK(hipMemsetAsync(g.d_stats, 0, PT_MAX_DEPTH * sizeof(unsigned long long), g.stream));
   HIP_OK(hipStreamSynchronize(g.stream));
   g.samples = 0;
+  g.primary_launches = 0;
   return 0;
 }
 
@@ -492,6 +508,7 @@ static size_t sub_words_max(const Ctx& g) { return ptk::sub_stride(g.num_cus * 8
 // (pt_ctx_set_camera): path buffers all ones, records poisoned, fill levels and the deal of the waves zero.  A slot wrongly gathered
 // from the previous view then shows as NaN, not as a plausible pixel.
 static int rearm_batch_buffers(Ctx& g) {
+  g.primary_valid = false;  // the first-hit records go with the buffers (pt_sched.h primary_once)
   for (const ptd::PathBuf& pb : g.buf) HIP_OK(hipMemsetAsync(pb.r, 0xff, pathbuf_words(pb.stride) * sizeof(ptd::Word4), g.stream));
   const size_t regions = (size_t)g.qs.Q * g.ret.kmax;
   HIP_OK(hipMemsetAsync(g.ret.cnt, 0, regions * sizeof(*g.ret.cnt), g.stream));
@@ -855,6 +872,7 @@ int pt_ctx_get_stats(PtContext* c, PtStats* out) {
   out->tight_leaves = g.tight_leaves;
   out->record_form = g.record_form;
   out->gather_form = g.gather_form;
+  out->primary_launches = g.primary_launches;
   out->paths_waves = 0;
   if (g.qs.deal && g.grid_paths > 0) {  // the table the NEXT batch's k_paths launch will read (ptd::Queues::deal)
     const ptk::DealMap dm = ptk::deal_map(g.qs);

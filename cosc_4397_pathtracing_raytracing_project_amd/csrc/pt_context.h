@@ -117,6 +117,23 @@ struct PtContext : PtShared {
   double isect_ms = 0, render_ms = 0;
   int64_t isect_launches = 0;
   int64_t samples = 0;
+  // Depth 0 once per camera (pt_sched.h primary_once): what the first-hit records now in buf[1], ret.rec and ret.sub were traced for —
+  // every argument of the k_primary launch that wrote them but the batch's first iteration and its length, which that output does not
+  // depend on.  run_batch launches k_primary again unless the next batch's arguments are these, bit for bit; what changes behind
+  // the pointers they hold (the tables of a moved camera, a worker's pixel list, buffers armed again) clears primary_valid itself.
+  struct PrimaryKey {
+    ptk::SceneTables sc;
+    ptd::Camera cam;
+    ptk::BatchInfo b;  // iter_first = K = 0
+    ptd::Queues qs;
+    ptd::PathBuf out;
+    ptd::RetireBuf ret;
+    const void* kernels;
+    int32_t grid, debug_flags;
+  };
+  PrimaryKey primary_key{};
+  bool primary_valid = false;
+  int64_t primary_launches = 0;  // k_primary launches of pt_render and the adaptive rounds (PtStats.primary_launches)
   // A batch that failed half-way (a launch or an event call returned an error) leaves counters and record regions in an
   // undefined state: the context refuses further renders instead of appending past them.
   bool failed = false;

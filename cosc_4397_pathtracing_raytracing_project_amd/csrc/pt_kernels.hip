@@ -1365,8 +1365,9 @@ __global__ __launch_bounds__(kBlock, (primary_waves<F, SPLIT>())) void k_primary
           record_group(ws.best[pp.par * 64 + lane], ws.rec + pp.par * 6 * 64 + lane, pp.g);
         }
       }
-      // K identical counts (zeros where the wave had no chunk); K may exceed the 64 lanes
-      for (int k = lane; k < b.K; k += 64) rt.sub[k * rt.wq0 + shared_rho(r, k, wq)] = ((unsigned long long)(uint32_t)fnd << 32) | (uint32_t)fnl;
+      // identical counts (zeros where the wave had no chunk) for every iteration the regions are provisioned for, not this batch's K
+      // alone: a longer batch of the same camera finds them without another trace (pt_sched.h primary_once); kmax may exceed the 64 lanes
+      for (int k = lane; k < ret.kmax; k += 64) rt.sub[k * rt.wq0 + shared_rho(r, k, wq)] = ((unsigned long long)(uint32_t)fnd << 32) | (uint32_t)fnl;
     } else if constexpr (SHARE) {
       // Shared form (pt_sched.h): the wave keeps residue r through the piece, so chunk jj is traced ONCE per run of iterations
       // [s0, s1) and shaded s1 - s0 times from the same hit; lane l of vnl / vnd counts the survivors / retirees of iteration s0 + l.
@@ -1756,7 +1757,8 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
   // path region, and where the records of its paths go — the slots from retirees(e) + i on in sub-region e for the paths from
   // index i on (RetireBuf).
   const int wq0 = rt.wq0, ne = b.K * wq0;
-  const int my_nq = queue_share(b, qs, q).my_nq, quo = my_nq / wq0, rem = my_nq % wq0;
+  const QueueShare qshare = queue_share(b, qs, q);
+  const int my_nq = qshare.my_nq, quo = my_nq / wq0, rem = my_nq % wq0;
   auto count_of = [&](int e) { return e < ne ? (int)(uint32_t)rt.sub[e] : 0; };
   // Every wave of the queue scans sub[] for the total and for where its slice begins.  With a small tile that is thousands of
   // words (an eighth of 1080p: 195 iterations x 20 residues): the words are fetched four 64-entry chunks ahead of their
@@ -1776,6 +1778,9 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
     }
   }
   if (r == 0 && lane == 0) cnt[cnt_index(qs, 1, q)] = total;  // statistics: rays traced at depth 1
+  // ... and at depth 0, k_primary's own figure: a first-bounce batch may run without that kernel (pt_sched.h primary_once), and the row is zeroed after every batch
+  if constexpr (SPLIT == kFirstBounce || SPLIT == kFixedSlots)
+    if (r == 0 && lane == 0) cnt[cnt_index(qs, 0, q)] = b.K * qshare.my_pixels;
   // The queue's ranks [0, total) are cut into pieces of `ps` paths.  Piece r is the wave's own; the pieces from wq on go, in
   // order, to whichever wave of the queue has finished what it had (a counter per queue behind ptd::Queues::deal, zeroed by
   // k_count_stats): equal numbers of depth-1 rays are not equal work — a piece's paths come from a few dozen pixel chunks, and

@@ -282,6 +282,19 @@ PT_SCHED int record_form(const BatchInfo& b, int debug_flags, int search_form, i
   return first_bounces(b, debug_flags, search_form, num_mats) ? kFirstBounce : splits_records(b, debug_flags) ? kSplitRecords : 0;
 }
 
+// ── depth 0 of a first-bounce batch: traced once per camera ───────────────────────────────────────────────────────────────
+// What k_primary leaves behind in a first-bounce batch — the surviving pixels' records at their slots of iteration 0, the depth-0
+// retirees' records at the front of the sub-regions of iteration 0, the pair of counts in sub[] — depends on the camera, the scene
+// tables, the tile or list and the queue geometry, and on neither the batch's first iteration nor (the counts are published for every
+// iteration the regions are provisioned for, RetireBuf::kmax) on how many it holds; k_paths and the gathers only read it.  So the next
+// such batch of the same context finds it as it needs it, and the host launches k_primary only when one of those inputs has changed
+// (pt_api.cpp run_batch keeps the launch's arguments as the key).  The counter row of depth 0, which the statistics read and re-zero
+// after every batch, is written by k_paths in this form.  Every other form's depth 0 has per-iteration output and is traced in every
+// batch.  The rule holds for the batches with fixed record slots (primary_once, behind fixed_slots below): there k_paths' own stores
+// into the record regions go to slots the path's list position gives, behind the retirees', in every batch alike.
+// PtOptions.debug_flags kPrimaryEveryBatch: in every batch, as an A/B switch.
+constexpr int kPrimaryEveryBatch = 65536;
+
 // ── retirement records of a first-bounce batch: fixed slots, gathered as a stream ─────────────────────────────────────────
 // In a first-bounce batch record i of sub-list (q, k, rho) is the same pixel for every k (above), and the lane of k_paths that takes
 // it knows i.  Such a batch (BatchInfo::fixed_slots) stores the path's retirement record at slot retirees(rho) + i of sub-region
@@ -308,6 +321,14 @@ PT_SCHED bool fixed_slots(int primary_share, bool aa_jitter, bool flat, int trac
 }
 PT_SCHED bool fixed_slots(const BatchInfo& b, int debug_flags, int search_form, int num_mats, int seg_cap) {
   return fixed_slots(b.primary_share, b.aa_jitter != 0, b.flat != 0, b.trace_depth, debug_flags, search_form, num_mats, b.slot_shift, b.K, seg_cap);
+}
+// Depth 0 once per camera (above): such a batch reads the first-hit records an earlier batch of the same camera, tile and plan left.
+PT_SCHED bool primary_once(int primary_share, bool aa_jitter, bool flat, int trace_depth, int debug_flags, int search_form, int num_mats, int slot_shift,
+                           int K, int seg_cap) {
+  return fixed_slots(primary_share, aa_jitter, flat, trace_depth, debug_flags, search_form, num_mats, slot_shift, K, seg_cap) && !(debug_flags & kPrimaryEveryBatch);
+}
+PT_SCHED bool primary_once(const BatchInfo& b, int debug_flags, int search_form, int num_mats, int seg_cap) {
+  return primary_once(b.primary_share, b.aa_jitter != 0, b.flat != 0, b.trace_depth, debug_flags, search_form, num_mats, b.slot_shift, b.K, seg_cap);
 }
 // PtStats.gather_form of a batch: 0 the tile gather over records in order of retirement, 1 the tile gather over fixed slots (kTileGather,
 // and every batch with the convergence metric, whose partial sums keep their partition), 2 the stream.

@@ -118,7 +118,11 @@ typedef struct PtOptions {
                                retirement records in order of retirement, gathered through a tile (default in a batch of the
                                8192 form whose words fit: a path's record goes to the slot its position in its list gives, so a
                                slot holds the same pixel in every iteration of the batch and the gather streams the records,
-                               one thread per slot; PtStats.gather_form tells), 32768 the tile gather over such fixed slots, 2048
+                               one thread per slot; PtStats.gather_form tells), 32768 the tile gather over such fixed slots, 65536
+                               the primary kernel runs in every batch (default in a batch of the 8192 form with the fixed slots
+                               of 16384: its output there depends on neither the iteration nor the batch's length, so it runs
+                               in the first batch after pt_init or pt_set_camera and later batches read what it left;
+                               PtStats.primary_launches tells), 2048
                                keep the reference's leaf boxes for spheres (default for large scenes: tightened to the
                                ellipsoid's box, PtStats.tight_leaves; pt_stage_intersect on such a scene then expects ray
                                origins inside the scene bounds or at the camera).  pt_init fails on any other bit. */
@@ -204,6 +208,9 @@ typedef struct PtStats {
   int32_t gather_form;                /* how the last batch was gathered: 0 through a tile, from records in order of retirement
                                          (debug_flags 16384 asks for it), 1 through a tile, from fixed record slots (debug_flags
                                          32768, and every batch that computes the convergence metric), 2 as a stream over fixed slots */
+  int64_t primary_launches;           /* launches of the fused primary kernel by pt_render since pt_init (pt_reset_stats and pt_clear
+                                         leave it): with record_form 2 one per camera — the first batch after pt_init or
+                                         pt_set_camera — instead of one per batch (debug_flags 65536 asks for every batch) */
 } PtStats;
 
 /* ---- scene loading (host).  Replaces `new Scene(file)` (src/main.cpp:45,
