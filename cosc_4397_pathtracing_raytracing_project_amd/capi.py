@@ -93,6 +93,17 @@ class PtSetupTimes(C.Structure):
                 ("set_camera_ms", C.c_double), ("set_camera_calls", C.c_int32)]
 
 
+class PtSetCameraTimes(C.Structure):
+    """Host wall-clock times of a renderer's last camera move, ms, and which build made its tables (include/pt_amd.h:
+    pt_get_set_camera_times): path 0 host / 1 device, fallback 0 or PT_DEVICE_TABLES_LIST / PT_DEVICE_TABLES_CELLS."""
+    _fields_ = [("tables_ms", C.c_double), ("rearm_ms", C.c_double), ("total_ms", C.c_double), ("path", C.c_int32), ("fallback", C.c_int32)]
+
+
+PT_SET_CAMERA_DEVICE_TABLES = 1
+PT_DEVICE_TABLES_LIST, PT_DEVICE_TABLES_CELLS = 1, 2
+TABLE_NAMES = ("nodes", "nodes_b", "top", "top_b", "grid_start", "grid_items", "grid_items_b", "cull_margin")  # pt_stage_read_tables' `which`
+
+
 class PtError(RuntimeError):
     pass
 
@@ -291,6 +302,15 @@ def lib() -> C.CDLL:
         L.pt_ctx_get_setup_times.argtypes = [C.c_void_p, C.POINTER(PtSetupTimes)]
         L.pt_camera_tables_host.argtypes = [C.POINTER(PtSceneDesc), _cam, C.c_int, C.c_int, _ip, _ip, _ip]
         L.pt_scene_orbit.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_float]
+    if hasattr(L, "pt_set_camera_ex"):
+        _cam = C.POINTER(PtCamera)
+        L.pt_set_camera_ex.argtypes = [_cam, C.c_uint32]
+        L.pt_ctx_set_camera_ex.argtypes = [C.c_void_p, _cam, C.c_uint32]
+        L.pt_group_set_camera_ex.argtypes = [C.c_void_p, _cam, C.c_uint32]
+        L.pt_get_set_camera_times.argtypes = [C.POINTER(PtSetCameraTimes)]
+        L.pt_ctx_get_set_camera_times.argtypes = [C.c_void_p, C.POINTER(PtSetCameraTimes)]
+        L.pt_stage_read_tables.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.pt_selfcheck_camera_math.argtypes = [C.c_int, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
         L.pt_scene_camera.argtypes = [C.c_void_p, _cam]
         L.pt_scene_orbit_state.argtypes = [C.c_void_p, _fp, _fp, _fp]
     _lib = L
@@ -412,6 +432,14 @@ def selfcheck_ieee(kind: int, first: int, count: int, seed: int = 0, arith: str 
     (pt_selfcheck_ieee)."""
     n = C.c_uint64(0)
     _check(lib().pt_selfcheck_ieee(ARITH[arith], kind, first, count, seed, C.byref(n)))
+    return int(n.value)
+
+
+def selfcheck_camera_math(kind: int, count: int, seed: int = 0) -> int:
+    """Operand sets on which a function of csrc/pt_camera_tables.h gives other bits on the GPU than on the host
+    (pt_selfcheck_camera_math: kind 0 sqrt, 1 a / b, 2 nextafterf of (float)double, 3 center_half_box, 4 sphere_tight_box, 5 cell_range)."""
+    n = C.c_uint64(0)
+    _check(lib().pt_selfcheck_camera_math(int(kind), int(count), int(seed), C.byref(n)))
     return int(n.value)
 
 
@@ -745,10 +773,32 @@ class Renderer:
         """Restart the accumulation (SUM image and statistics zeroed) on the same, already touched buffers."""
         _check(lib().pt_clear())
 
-    def set_camera(self, cam: PtCamera) -> None:
+    def set_camera(self, cam: PtCamera, device_tables: bool = False) -> None:
         """Move the camera of the live renderer (pt_set_camera): from here on it gives what a renderer freshly created with
-        `cam` gives, without the teardown, the allocations and the traversal probe of a new one."""
-        _check(lib().pt_set_camera(C.byref(cam)))
+        `cam` gives, without the teardown, the allocations and the traversal probe of a new one.  device_tables: the
+        camera-dependent tables are rebuilt on the device (pt_set_camera_ex, PT_SET_CAMERA_DEVICE_TABLES), the same bytes."""
+        if device_tables:
+            _check(lib().pt_set_camera_ex(C.byref(cam), PT_SET_CAMERA_DEVICE_TABLES))
+        else:
+            _check(lib().pt_set_camera(C.byref(cam)))
+
+    def set_camera_times(self) -> PtSetCameraTimes:
+        """Tables / re-arm / total milliseconds of the last move, and which build made its tables (pt_get_set_camera_times)."""
+        t = PtSetCameraTimes()
+        _check(lib().pt_get_set_camera_times(C.byref(t)))
+        return t
+
+    @staticmethod
+    def read_tables() -> dict:
+        """The camera-dependent tables as they lie on the device, bytes by name (TABLE_NAMES; pt_stage_read_tables); b"" = absent."""
+        out = {}
+        for which, name in enumerate(TABLE_NAMES):
+            n = C.c_uint64(0)
+            _check(lib().pt_stage_read_tables(which, None, 0, C.byref(n)))
+            buf = (C.c_uint8 * max(int(n.value), 1))()
+            _check(lib().pt_stage_read_tables(which, buf, int(n.value), C.byref(n)))
+            out[name] = bytes(buf)[:int(n.value)]
+        return out
 
     def setup_times(self) -> PtSetupTimes:
         t = PtSetupTimes()
@@ -996,9 +1046,12 @@ class Group:
     def render(self, iter_first: int, iter_count: int) -> None:
         _check(lib().pt_group_render(self._h, int(iter_first), int(iter_count)))
 
-    def set_camera(self, cam: PtCamera) -> None:
-        """Renderer.set_camera on every context (pt_group_set_camera); a refusal leaves every context as it was."""
-        _check(lib().pt_group_set_camera(self._h, C.byref(cam)))
+    def set_camera(self, cam: PtCamera, device_tables: bool = False) -> None:
+        """Renderer.set_camera on every context (pt_group_set_camera, pt_group_set_camera_ex); a refusal leaves every context as it was."""
+        if device_tables:
+            _check(lib().pt_group_set_camera_ex(self._h, C.byref(cam), PT_SET_CAMERA_DEVICE_TABLES))
+        else:
+            _check(lib().pt_group_set_camera(self._h, C.byref(cam)))
 
     def gather(self) -> np.ndarray:
         w, h = self.scene.resolution

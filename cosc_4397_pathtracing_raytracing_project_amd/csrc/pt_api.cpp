@@ -17,6 +17,7 @@
 #include <string>
 
 #include "pt_adaptive.h"
+#include "pt_camera_tables_device.h"
 #include "pt_context.h"
 #include "pt_lds.h"
 #include "pt_scene.h"
@@ -939,6 +940,13 @@ int pt_ctx_camera_refusal(const PtContext* c, const PtCamera* cam, const char* w
       if (!std::isfinite(f.v[i])) return pt_fail("%s: camera %s[%d] is not finite", who, f.name, i);
   return 0;
 }
+// ... and what pt_set_camera_ex adds: a flag bit that is not defined, looked at after the null camera
+int pt_ctx_camera_refusal_ex(const PtContext* c, const PtCamera* cam, uint32_t flags, const char* who) {
+  if (need(c, who) || admit(*c, who, kNotFailed)) return -1;
+  if (!cam) return pt_fail("%s: null camera", who);
+  if (flags & ~(uint32_t)PT_SET_CAMERA_DEVICE_TABLES) return pt_fail("%s: undefined flag bit(s) 0x%x (defined: PT_SET_CAMERA_DEVICE_TABLES = 0x%x)", who, flags & ~(uint32_t)PT_SET_CAMERA_DEVICE_TABLES, PT_SET_CAMERA_DEVICE_TABLES);
+  return pt_ctx_camera_refusal(c, cam, who);
+}
 namespace {
 template <typename T>
 int reupload(const T* dev, const std::vector<T>& v) {  // into a table of unchanged size
@@ -965,7 +973,7 @@ int move_tables(Ctx& g) {
     if (gr && gr->start.size() == d.start.size() && gr->items.size() == d.items && gr->items_b.empty() == (d.d_items_b == d.d_items)) {
       if (reupload(d.d_start, gr->start) || reupload(d.d_items, gr->items)) return -1;
       if (!gr->items_b.empty() && reupload(d.d_items_b, gr->items_b)) return -1;
-      d.shape = gr->shape, d.guard = gr->guard, d.start = gr->start;
+      d.shape = gr->shape, d.guard = gr->guard, d.start = gr->start, d.start_stale = false;
       return 0;
     }
     free_grid(g, d);
@@ -974,16 +982,137 @@ int move_tables(Ctx& g) {
   }
   return gr ? upload_grid(g, *gr) : 0;
 }
-}  // namespace
-extern "C" {
 
-int pt_ctx_set_camera(PtContext* c, const PtCamera* cam) {
-  if (pt_ctx_camera_refusal(c, cam, "pt_set_camera")) return -1;
-  const auto t0 = std::chrono::steady_clock::now();
+// The first device-path move of a renderer: camera_base on the device (base nodes, base top list, the fields of PtGeom the build reads)
+// and the build's workspace, sized for the grid the renderer rebuilds (grid_request never changes after setup()).
+int ensure_device_base(Ctx& g) {
+  Ctx::DeviceBase& b = g.device_base;
+  if (b.ready) return 0;
+  const pt::CameraBase& cb = g.camera_base;
+  std::vector<ptct::DeviceGeom> geoms(cb.geoms.size());
+  for (size_t i = 0; i < geoms.size(); ++i) {
+    geoms[i] = ptct::DeviceGeom{};
+    std::memcpy(geoms[i].inv, cb.geoms[i].inverseTransform, sizeof(geoms[i].inv));
+    geoms[i].type = cb.geoms[i].type;
+  }
+  if (!(b.nodes = upload(g, cb.nodes)) || !(b.top = upload(g, cb.top)) || !(b.geoms = upload(g, geoms))) return -1;
+  if (dalloc(g, &b.rec, 1)) return -1;
+  if (g.grid_request.kind == pt::GridRequest::kFixed) {
+    int64_t ncell = 1, leaves = 0;
+    for (int a = 0; a < 3; ++a) ncell *= std::min(512, std::max(1, g.grid_request.res[a]));
+    for (const ptd::Node& n : cb.nodes) leaves += n.geom >= 0 ? 1 : 0;
+    if (ncell <= ptct::kDeviceMaxCells) {  // (else every device-path move falls back to the host: no workspace)
+      // a grid that is not forced is refused beyond 64 references per leaf (build_grid), any grid beyond kMaxRefs
+      b.scratch_cap = (size_t)((g.debug_flags & 256) ? ptct::kMaxRefs : std::min<int64_t>(ptct::kMaxRefs, 64 * leaves));
+      if (dalloc(g, &b.count, (size_t)ncell) || dalloc(g, &b.sums, pt_camera_tables_scan_blocks((size_t)ncell)) || dalloc(g, &b.scratch, b.scratch_cap)) return -1;
+    }
+  }
+  b.ready = true;
+  return 0;
+}
+
+// move_tables() with the build on the device (csrc/pt_camera_tables.hip): the host computes the scalars as camera_tables() and build_grid()
+// do, the kernels everything per node, per top entry and per (leaf, cell) reference.  *fallback != 0: a limit of the device build
+// (PT_DEVICE_TABLES_*) was met and nothing the renderer reads was left half built that move_tables() does not write again.
+int move_tables_device(Ctx& g, int32_t* fallback) {
+  *fallback = 0;
+  const pt::CameraBase& cb = g.camera_base;
+  const bool center_half = g.k->boxes_center_half != 0;
+  const bool forced = (g.debug_flags & 256) != 0;
+  ptk::SceneTables& s = g.scene;
+  ptct::BuildArgs a{};
+  a.num_nodes = (int32_t)cb.nodes.size(), a.num_top = (int32_t)cb.top.size();
+  a.tighten = ((int)cb.nodes.size() >= pt::kTightNodes && !(g.debug_flags & 2048)) ? 1 : 0;
+  a.center_half = center_half ? 1 : 0;
+  pt::origin_region(s.root_min, s.root_max, g.cam.position, a.origin_lo, a.origin_hi);
+  a.magnitude = pt::scene_magnitude(s.root_min, s.root_max, g.cam.position);
+  // the grid's scalars, as camera_tables() and build_grid() compute them for a kFixed request
+  pt::GridShape shape{};
+  bool want_grid = g.grid_request.kind == pt::GridRequest::kFixed && !(g.debug_flags & 512);
+  if (want_grid) {
+    double cam_mag = 0.0;
+    for (int k = 0; k < 3; ++k) cam_mag = std::max(cam_mag, std::fabs((double)g.cam.position[k]));
+    want_grid = pt::grid_frame(s.root_min, s.root_max, cam_mag, a.frame);
+    if (want_grid) {
+      for (int k = 0; k < 3; ++k) a.frame.res[k] = std::min(512, std::max(1, g.grid_request.res[k]));
+      const int64_t ncell = pt::grid_shape(a.frame, shape);
+      if (ncell > (int64_t)64 * 1024 * 1024 || (int64_t)cb.geoms.size() > (1 << 24)) want_grid = false;  // build_grid's refusals
+      else if (ncell > ptct::kDeviceMaxCells) return *fallback = PT_DEVICE_TABLES_CELLS, 0;
+      a.ncell = (uint32_t)ncell, a.guard = (uint32_t)pt::grid_guard(shape);
+    }
+  }
+  if (ensure_device_base(g)) return -1;
+  const Ctx::DeviceBase& b = g.device_base;
+  ptd::Node* nodes_b = center_half ? const_cast<ptd::Node*>(s.nodes_b) : nullptr;
+  ptd::TopEntry* top_b = center_half ? const_cast<ptd::TopEntry*>(s.top_b) : nullptr;
+  if (pt_camera_tables_nodes_launch(g.stream, a, b.nodes, b.top, b.geoms, const_cast<ptd::Node*>(s.nodes), nodes_b, const_cast<ptd::TopEntry*>(s.top), top_b, b.rec))
+    return -1;
+  if (want_grid && pt_camera_tables_count_launch(g.stream, a, s.nodes, b.count, b.rec)) return -1;
+  ptct::BuildRecord rec{};  // the one readback: references, longest list, tightened leaves
+  HIP_OK(hipMemcpyAsync(&rec, b.rec, sizeof(rec), hipMemcpyDeviceToHost, g.stream));
+  HIP_OK(hipStreamSynchronize(g.stream));
+  {
+    const float extent = std::max(1.0f, (float)pt::scene_magnitude(s.root_min, s.root_max, g.cam.position));
+    s.cull_margin = 1e-3f * cb.max_xf + 1e-4f * extent;
+  }
+  g.tight_leaves = (int)rec.tight;
+  if (want_grid) {  // build_grid's refusals on what the kernels counted
+    const int64_t leaves = ((int64_t)cb.nodes.size() + 1) / 2;
+    if ((int64_t)rec.refs > ptct::kMaxRefs || (!forced && (int64_t)rec.refs > 64 * leaves) || (!forced && rec.longest > 4096)) want_grid = false;
+    else if (rec.longest > ptct::kDeviceMaxList || rec.refs > b.scratch_cap) return *fallback = PT_DEVICE_TABLES_LIST, 0;
+  }
+  // the grid's buffers: reused where the sizes are unchanged, else replaced (move_tables' rule)
+  if (!g.grids.empty()) {
+    Ctx::DeviceGrid& d = g.grids[g.grid_pick];
+    const bool keep = want_grid && (size_t)a.ncell + 1 + 2 * (size_t)a.guard == d.start.size() && (size_t)rec.refs == d.items && center_half == (d.d_items_b != d.d_items);
+    if (!keep) {
+      free_grid(g, d);
+      g.grids.clear();
+      g.grid_pick = 0;
+    }
+  }
+  if (want_grid) {
+    if (g.grids.empty()) {
+      Ctx::DeviceGrid d{shape, a.guard, nullptr, nullptr, nullptr, 0, {}};
+      const int64_t before = g.device_bytes;
+      uint32_t* start = nullptr;
+      ptd::Node *items = nullptr, *items_b = nullptr;
+      if (dalloc(g, &start, (size_t)a.ncell + 1 + 2 * (size_t)a.guard) || dalloc(g, &items, (size_t)rec.refs)) return -1;
+      if (center_half && dalloc(g, &items_b, (size_t)rec.refs)) return -1;
+      d.d_start = start, d.d_items = items, d.d_items_b = center_half ? items_b : items;
+      d.bytes = (size_t)(g.device_bytes - before);
+      d.items = (size_t)rec.refs;
+      d.start.assign((size_t)a.ncell + 1 + 2 * (size_t)a.guard, 0u);
+      g.grids.push_back(d);
+    }
+    Ctx::DeviceGrid& d = g.grids[g.grid_pick];
+    d.shape = shape, d.guard = a.guard, d.start_stale = true;
+    if (pt_camera_tables_grid_launch(g.stream, a, s.nodes, b.geoms, b.count, b.sums, b.scratch, (uint32_t)rec.refs, const_cast<uint32_t*>(d.d_start),
+                                     const_cast<ptd::Node*>(d.d_items), center_half ? const_cast<ptd::Node*>(d.d_items_b) : nullptr))
+      return -1;
+  }
+  HIP_OK(hipStreamSynchronize(g.stream));  // (so that PtSetCameraTimes.tables_ms holds the build, not its launches)
+  return 0;
+}
+
+int set_camera(PtContext* c, const PtCamera* cam, uint32_t flags) {  // after the refusals
+  using clock = std::chrono::steady_clock;
+  auto ms_since = [](clock::time_point t0) { return std::chrono::duration<double, std::milli>(clock::now() - t0).count(); };
+  const auto t0 = clock::now();
   Ctx& g = *c;
   if (pt_ctx_sync(c)) return -1;
   take_camera(g, *cam);
-  if (move_tables(g)) return g.failed = true, -1;  // (tables half replaced: nothing may render from them)
+  PtSetCameraTimes times{};
+  if (flags & PT_SET_CAMERA_DEVICE_TABLES) {
+    times.path = 1;
+    if (move_tables_device(g, &times.fallback)) return g.failed = true, -1;
+  }
+  if (!(flags & PT_SET_CAMERA_DEVICE_TABLES) || times.fallback) {
+    times.path = 0;
+    if (move_tables(g)) return g.failed = true, -1;  // (tables half replaced: nothing may render from them)
+  }
+  times.tables_ms = ms_since(t0);
+  const auto t1 = clock::now();
   plan_launch(g);
   g.record_form = g.gather_form = 0;
   if (Ctx* w = g.worker) {  // the worker's view of the scene is a copy: camera, table pointers, grid and launch widths again
@@ -994,8 +1123,39 @@ int pt_ctx_set_camera(PtContext* c, const PtCamera* cam) {
   }
   if (rearm_batch_buffers(g)) return g.failed = true, -1;
   if (pt_ctx_clear(c)) return -1;
-  g.setup_times.set_camera_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  times.rearm_ms = ms_since(t1);
+  times.total_ms = ms_since(t0);
+  g.camera_times = times;
+  g.setup_times.set_camera_ms = times.total_ms;
   g.setup_times.set_camera_calls += 1;
+  return 0;
+}
+}  // namespace
+
+namespace ptc {
+int grid_start_host(Ctx& g, Ctx::DeviceGrid& d) {
+  if (!d.start_stale) return 0;
+  HIP_OK(hipSetDevice(g.device));
+  HIP_OK(hipStreamSynchronize(g.stream));
+  HIP_OK(hipMemcpy(d.start.data(), d.d_start, d.start.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  d.start_stale = false;
+  return 0;
+}
+}  // namespace ptc
+extern "C" {
+
+int pt_ctx_set_camera(PtContext* c, const PtCamera* cam) {
+  if (pt_ctx_camera_refusal(c, cam, "pt_set_camera")) return -1;
+  return set_camera(c, cam, 0u);
+}
+int pt_ctx_set_camera_ex(PtContext* c, const PtCamera* cam, uint32_t flags) {
+  if (pt_ctx_camera_refusal_ex(c, cam, flags, "pt_set_camera_ex")) return -1;
+  return set_camera(c, cam, flags);
+}
+int pt_ctx_get_set_camera_times(PtContext* c, PtSetCameraTimes* out) {
+  if (need(c, "pt_get_set_camera_times")) return -1;
+  if (!out) return pt_fail("pt_get_set_camera_times: null");
+  *out = c->camera_times;
   return 0;
 }
 
@@ -1076,6 +1236,8 @@ int pt_get_stats(PtStats* out) { return pt_ctx_get_stats(g_default, out); }
 int pt_reset_stats(void) { return pt_ctx_reset_stats(g_default); }
 int pt_clear(void) { return pt_ctx_clear(g_default); }
 int pt_set_camera(const PtCamera* cam) { return pt_ctx_set_camera(g_default, cam); }
+int pt_set_camera_ex(const PtCamera* cam, uint32_t flags) { return pt_ctx_set_camera_ex(g_default, cam, flags); }
+int pt_get_set_camera_times(PtSetCameraTimes* out) { return pt_ctx_get_set_camera_times(g_default, out); }
 int pt_get_setup_times(PtSetupTimes* out) { return pt_ctx_get_setup_times(g_default, out); }
 int pt_render_features(int iter_first, int iter_count) { return pt_ctx_render_features(g_default, iter_first, iter_count); }
 int pt_readback_features(float* planes_host) { return pt_ctx_readback_features(g_default, planes_host); }

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/pt_amd.h"
+#include "pt_camera_tables.h"
 #include "pt_device.h"
 #include "pt_internal.h"
 #include "pt_kernels.h"
@@ -56,6 +57,7 @@ struct PtShared {
     size_t bytes;
     std::vector<uint32_t> start;  // the host copy of what d_start holds, guard cells included (pt_stage_grid_info)
     size_t items = 0;             // records in d_items (a camera move reuses the buffers while the sizes stay)
+    bool start_stale = false;     // a device build wrote d_start: `start` has its size but not yet its contents (grid_start_host fetches them)
   };
   std::vector<DeviceGrid> grids;
   size_t grid_pick = 0;  // grids[grid_pick] is the one the kernels walk (when grids is not empty)
@@ -153,6 +155,21 @@ struct PtContext : PtShared {
   pt::CameraBase camera_base;
   pt::GridRequest grid_request;
   PtSetupTimes setup_times{};
+  // The device build of those tables (pt_ctx_set_camera_ex, csrc/pt_camera_tables.hip): camera_base on the device and the build's workspace,
+  // all of it absent until the first move that asks for the device path
+  struct DeviceBase {
+    bool ready = false;
+    const ptd::Node* nodes = nullptr;
+    const ptd::TopEntry* top = nullptr;
+    const ptct::DeviceGeom* geoms = nullptr;
+    ptct::BuildRecord* rec = nullptr;
+    uint32_t* count = nullptr;    // one word per cell of grid_request's resolution: the counters, then the scatter's fill levels
+    uint32_t* sums = nullptr;     // the scan's sums per workgroup
+    uint32_t* scratch = nullptr;  // the scatter's list: scratch_cap leaf indices
+    size_t scratch_cap = 0;
+  };
+  DeviceBase device_base;
+  PtSetCameraTimes camera_times{};  // the last move (pt_get_set_camera_times)
   bool adaptive = false;           // the adaptive state: from the first round to pt_clear
   int adaptive_rounds = 0;
   int64_t adaptive_last = 0;       // highest iteration number folded or merged
@@ -172,6 +189,7 @@ int pt_ctx_admit_state(const PtContext* c, const char* who, bool uniform);
 // whole contiguous rows; folds == false: apart from the state of the folds too (pt_render_threshold's first look).
 int pt_ctx_adaptive_refusal(const PtContext* c, const char* who, int iter_first, int group_iters, float max_fraction, bool folds);
 int pt_ctx_camera_refusal(const PtContext* c, const PtCamera* cam, const char* who);  // what pt_set_camera refuses, in its order; nothing changes
+int pt_ctx_camera_refusal_ex(const PtContext* c, const PtCamera* cam, uint32_t flags, const char* who);  // ... with the undefined flag bit after the null camera
 int pt_ctx_enter_adaptive(PtContext* c);  // the count plane with the fold's (T, M) in every pixel, unless the context is in the adaptive state already
 
 namespace ptc {
@@ -246,6 +264,7 @@ int run_batch(Ctx& g, int iter_first, int kb);
 int batch_iters_for(int iters_per_batch, int N, int* slot_shift);
 int plan_batches(Ctx& g, const PtOptions& opt);
 void plan_launch(Ctx& g);
+int grid_start_host(Ctx& g, Ctx::DeviceGrid& d);  // d.start as d_start holds it (fetched after a device build of the tables)
 int alloc_batch_buffers(Ctx& g);
 int get_events(Ctx& g, EventPair* ev);
 ptd::Queues single_queue(const Ctx& g, int n);

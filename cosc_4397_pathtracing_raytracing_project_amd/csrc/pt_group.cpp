@@ -493,6 +493,15 @@ int pt_group_set_camera(PtGroup* g, const PtCamera* cam) {
   return 0;
 }
 
+int pt_group_set_camera_ex(PtGroup* g, const PtCamera* cam, uint32_t flags) {
+  if (!g) return pt_fail("pt_group_set_camera_ex: null group");
+  for (PtContext* c : g->ctx)
+    if (pt_ctx_camera_refusal_ex(c, cam, flags, "pt_group_set_camera_ex")) return -1;
+  for (PtContext* c : g->ctx)
+    if (pt_ctx_set_camera_ex(c, cam, flags)) return -1;
+  return 0;
+}
+
 int pt_group_gather(PtGroup* g, float* rgb_sum_host) {
   if (!g || !rgb_sum_host) return pt_fail("pt_group_gather: bad argument");
   HIP_OK(hipSetDevice(g->devices[0]));

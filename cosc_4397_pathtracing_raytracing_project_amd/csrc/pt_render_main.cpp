@@ -3,7 +3,7 @@
 // state.iterations iterations, write the PNG saveImage() would write.  Flags exist only because
 // the reference takes resolution, iteration count and depth from the scene file (scene.cpp:103-114).
 //
-//   pt_render SCENE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] [--orbit N]
+//   pt_render SCENE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] [--orbit N [--device-tables]]
 //                       [--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa]
 //                       [--preview N] [--convergence N | --reference FILE.pfm] [--clean-db X] [--features]
 //                       [--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]]
@@ -57,7 +57,9 @@
 // turn around LOOKAT in steps of 2 pi / N — frame 0 is the scene's camera through pt_init (pt_group_create with --gpus / --devices),
 // frame f > 0 the viewer's mouse drag (pt_scene_orbit) followed by pt_set_camera (pt_group_set_camera) where the reference frees and
 // initialises; every frame renders iterations 1 .. --spp and is written as <base>.orbit<fff>.png (.pfm, .hdr).  Prints the setup
-// times once and per frame `orbit: frame f: camera x y z, set_camera a ms, render b ms`.
+// times once and per frame `orbit: frame f: camera x y z, set_camera a ms, render b ms`.  --device-tables (with --orbit): every move
+// passes PT_SET_CAMERA_DEVICE_TABLES (pt_set_camera_ex: the camera-dependent tables are rebuilt on the device, the same images), and the
+// frame's line ends `, tables a ms, rearm b ms (device|host tables)` from pt_get_set_camera_times.
 // Output name: PREFIX.<spp>samp.png, or with --stamp the reference's own
 // <FILE>.<UTC start time>.<spp>samp.png (main.cpp:99-102).
 #include <hip/hip_runtime.h>
@@ -79,7 +81,7 @@
 int main(int argc, char** argv) {
   if (argc < 2) {
     std::printf("Usage: %s SCENEFILE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] "
-                "[--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa] [--orbit N] [--preview N] "
+                "[--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa] [--orbit N [--device-tables]] [--preview N] "
                 "[--convergence N | --reference FILE.pfm] [--clean-db X] [--features] "
                 "[--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]] [--denoise-guided] [--until-db X [--until-group G] [--adaptive F [--denoise-adaptive]]] "
                 "[--adaptive-threshold E [--adaptive-cap F] [--adaptive-min-pixels P] [--until-group G] [--denoise-adaptive]]\n", argv[0]);
@@ -90,6 +92,7 @@ int main(int argc, char** argv) {
   bool pfm = false, hdr = false, stamp = false, aa = false, features = false, denoise = false, guided = false, dn_adaptive = false;
   PtDenoiseOptions dn_opt{};
   int convergence = 0, until_group = 0, orbit = 0;  // orbit > 0: --orbit N
+  bool device_tables = false;                       // --device-tables
   bool until = false, until_group_given = false;
   float clean_db = 35.0f, until_db = 0.0f, adaptive = 0.0f;  // adaptive > 0: --adaptive F
   float threshold = 0.0f, threshold_cap = 0.25f;           // --adaptive-threshold E, --adaptive-cap F
@@ -112,6 +115,7 @@ int main(int argc, char** argv) {
       }
       orbit = (int)v;
     }
+    else if (!std::strcmp(argv[i], "--device-tables")) device_tables = true;
     else if (!std::strcmp(argv[i], "--convergence") && i + 1 < argc) {
       convergence = std::atoi(argv[++i]);
       if (convergence <= 0) {
@@ -282,6 +286,10 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--until-db and --preview exclude each other (one loop over the iterations)\n");
     return 1;
   }
+  if (device_tables && orbit <= 0) {
+    std::fprintf(stderr, "--device-tables goes with --orbit N (it says how the camera moves rebuild the scene tables)\n");
+    return 1;
+  }
   if (orbit > 0) {  // a plain render per frame: what works on the image of one view is not carried from view to view
     const struct {
       bool given;
@@ -419,14 +427,21 @@ int main(int argc, char** argv) {
     const float step = (float)(2.0 * 3.14159265358979323846 / orbit);
     for (int f = 0; f < orbit; ++f) {
       double move_ms = 0.0;
+      PtSetCameraTimes ct{};
       if (f > 0) {
         scene->orbit(step, 0.0f, 0.0f);
+        const uint32_t flags = device_tables ? PT_SET_CAMERA_DEVICE_TABLES : 0u;
         const auto m0 = std::chrono::high_resolution_clock::now();
-        if (grp ? pt_group_set_camera(grp, &scene->state.camera) : pt_set_camera(&scene->state.camera)) {
+        if (device_tables ? (grp ? pt_group_set_camera_ex(grp, &scene->state.camera, flags) : pt_set_camera_ex(&scene->state.camera, flags))
+                          : (grp ? pt_group_set_camera(grp, &scene->state.camera) : pt_set_camera(&scene->state.camera))) {
           std::fprintf(stderr, "HIP error (pt_set_camera): %s\n", pt_last_error());
           return EXIT_FAILURE;
         }
         move_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - m0).count();
+        if (device_tables && (grp ? pt_ctx_get_set_camera_times(pt_group_context(grp, 0), &ct) : pt_get_set_camera_times(&ct))) {
+          std::fprintf(stderr, "HIP error (pt_get_set_camera_times): %s\n", pt_last_error());
+          return EXIT_FAILURE;
+        }
       }
       const auto t0 = std::chrono::high_resolution_clock::now();
       if (grp ? (pt_group_render(grp, 1, iters) || pt_group_gather(grp, scene->state.image.data())) : (pt_render(1, iters) || pt_readback(scene->state.image.data()))) {
@@ -435,7 +450,9 @@ int main(int argc, char** argv) {
       }
       const double render_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
       const float* p = scene->state.camera.position;
-      std::printf("orbit: frame %d: camera %.9g %.9g %.9g, set_camera %.3f ms, render %.3f ms\n", f, (double)p[0], (double)p[1], (double)p[2], move_ms, render_ms);
+      std::printf("orbit: frame %d: camera %.9g %.9g %.9g, set_camera %.3f ms, render %.3f ms", f, (double)p[0], (double)p[1], (double)p[2], move_ms, render_ms);
+      if (device_tables && f > 0) std::printf(", tables %.3f ms, rearm %.3f ms (%s tables)", ct.tables_ms, ct.rearm_ms, ct.path ? "device" : "host");
+      std::printf("\n");
       char tag[32];
       std::snprintf(tag, sizeof tag, ".orbit%03d", f);
       const std::string frame = base + tag;

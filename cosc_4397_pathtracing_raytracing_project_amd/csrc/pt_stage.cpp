@@ -4,6 +4,7 @@
 // stage wrappers pack / unpack on the host.
 #include <cstring>
 
+#include "pt_camera_tables_device.h"
 #include "pt_context.h"
 #include "pt_denoise.h"
 #include "pt_scene.h"
@@ -173,10 +174,11 @@ int pt_stage_intersect_grid(int n, const float* origin, const float* dir, int pr
 // The grid that pt_stage_intersect_grid walks, from the host copy of the uploaded cell table
 int pt_stage_grid_info(PtGridInfo* info, int32_t* max_cell_records) {
   if (need(default_context(), "pt_stage_grid_info")) return -1;
-  const Ctx& g = *default_context();
+  Ctx& g = *default_context();
   if (!info || !max_cell_records) return pt_fail("pt_stage_grid_info: null argument");
   const Ctx::DeviceGrid* gr = walked_grid(g);
   if (!gr) return pt_fail("pt_stage_grid_info: this context walks no grid (PtStats.grid_cells is 0; PtOptions.debug_flags 256 forces one)");
+  if (grid_start_host(g, g.grids[g.grid_pick])) return -1;  // (a device build of the tables leaves the host copy to whoever asks)
   std::memset(info, 0, sizeof(*info));
   for (int a = 0; a < 3; ++a) info->res[a] = gr->shape.res[a], info->origin[a] = gr->shape.gmin[a], info->cell_size[a] = gr->shape.cs[a];
   info->pad = gr->shape.pad;
@@ -188,6 +190,42 @@ int pt_stage_grid_info(PtGridInfo* info, int32_t* max_cell_records) {
   for (size_t c = 0; c < cells; ++c) longest = std::max(longest, gr->start[gr->guard + c + 1] - gr->start[gr->guard + c]);
   *max_cell_records = (int32_t)longest;
   return 0;
+}
+
+int pt_stage_read_tables(int which, void* out, uint64_t cap, uint64_t* bytes) {
+  if (need(default_context(), "pt_stage_read_tables")) return -1;
+  Ctx& g = *default_context();
+  if (which < 0 || which > 7 || !bytes || (cap && !out)) return pt_fail("pt_stage_read_tables: bad argument");
+  if (pt_ctx_sync(&g)) return -1;
+  const ptk::SceneTables& s = g.scene;
+  const Ctx::DeviceGrid* gr = g.grids.empty() ? nullptr : &g.grids[g.grid_pick];
+  const bool copies = g.k->boxes_center_half != 0;
+  const void* src = nullptr;
+  size_t n = 0;
+  switch (which) {
+    case 0: src = s.nodes, n = (size_t)s.num_nodes * sizeof(ptd::Node); break;
+    case 1: if (copies) src = s.nodes_b, n = (size_t)s.num_nodes * sizeof(ptd::Node); break;
+    case 2: src = s.top, n = (size_t)s.num_top * sizeof(ptd::TopEntry); break;
+    case 3: if (copies) src = s.top_b, n = (size_t)s.num_top * sizeof(ptd::TopEntry); break;
+    case 4: if (gr) src = gr->d_start, n = gr->start.size() * sizeof(uint32_t); break;
+    case 5: if (gr) src = gr->d_items, n = gr->items * sizeof(ptd::Node); break;
+    case 6: if (gr && gr->d_items_b != gr->d_items) src = gr->d_items_b, n = gr->items * sizeof(ptd::Node); break;
+    default: break;
+  }
+  if (which == 7) {
+    *bytes = sizeof(float);
+    if (cap) std::memcpy(out, &s.cull_margin, std::min<size_t>((size_t)cap, sizeof(float)));
+    return 0;
+  }
+  *bytes = n;
+  const size_t take = std::min<size_t>(n, (size_t)cap);
+  if (take) HIP_OK(hipMemcpy(out, src, take, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int pt_selfcheck_camera_math(int kind, uint64_t count, uint32_t seed, uint64_t* mismatches) {
+  if (kind < 0 || kind >= ptct::kMathKinds || count > ((uint64_t)1 << 24) || !mismatches) return pt_fail("pt_selfcheck_camera_math: bad argument");
+  return pt_camera_math_check(kind, count, seed, mismatches);
 }
 
 int pt_stage_shade(int n, int depth, const int32_t* iter, const int32_t* pixel, const float* t, const float* normal,

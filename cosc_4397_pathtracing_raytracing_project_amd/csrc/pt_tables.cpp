@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "pt_camera_tables.h"
 #include "pt_scene.h"
 
 namespace pt {
@@ -146,59 +147,13 @@ static void pack_rows(const float m16[16], float out12[12]) {
 // reference's, and the ones we drop return "no hit" there.  Exact mode stays bit-identical (tests: stress scenes and the
 // random-scene fuzz against the oracle, which keeps the reference's boxes); debug_flags 2048 keeps the reference's boxes.
 // pt_stage_intersect on such a scene inherits the assumption about ray origins.
-// One sphere: ref_lo / ref_hi = the reference's leaf box; returns false when nothing could be tightened.
-static bool sphere_tight_box(const PtGeom& gm, const double origin_lo[3], const double origin_hi[3], const float ref_lo[3], const float ref_hi[3],
-                             float lo[3], float hi[3]) {
-  const double u = 1.0 / 16777216.0;
-  double M = 0.0;
-  for (int a = 0; a < 3; ++a) M = std::max({M, std::fabs(origin_lo[a]), std::fabs(origin_hi[a])});
-  M *= std::sqrt(3.0);
-  const float* inv = gm.inverseTransform;  // column-major 4x4, m[c*4+r]
-  double A[3][3], t[3], B[3][3];
-  for (int r = 0; r < 3; ++r) {
-    for (int c = 0; c < 3; ++c) A[r][c] = inv[c * 4 + r];
-    t[r] = inv[3 * 4 + r];
-  }
-  const double det = A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0]) +
-                     A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]);
-  if (!(std::fabs(det) > 0.0) || !std::isfinite(det)) return false;
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) {
-      const int r1 = (c + 1) % 3, r2 = (c + 2) % 3, c1 = (r + 1) % 3, c2 = (r + 2) % 3;  // B = A^-1: cofactor of A[c][r] over det
-      B[r][c] = (A[r1][c1] * A[r2][c2] - A[r1][c2] * A[r2][c1]) / det;
-    }
-  double nA = 0.0, nB = 0.0, nt = 0.0, ctr[3], D = 0.0;
-  for (int r = 0; r < 3; ++r) {
-    for (int c = 0; c < 3; ++c) nA += A[r][c] * A[r][c], nB += B[r][c] * B[r][c];
-    nt += t[r] * t[r];
-    ctr[r] = -(B[r][0] * t[0] + B[r][1] * t[1] + B[r][2] * t[2]);
-  }
-  nA = std::sqrt(nA), nB = std::sqrt(nB), nt = std::sqrt(nt);
-  for (int a = 0; a < 3; ++a) {
-    const double far = std::max(std::fabs(ctr[a] - origin_lo[a]), std::fabs(ctr[a] - origin_hi[a]));
-    D += far * far;
-  }
-  const double D_obj = nA * std::sqrt(D), M_obj = nA * M + nt;
-  const double rho = std::sqrt(0.25 + 4.0 * u * (18.0 * D_obj * D_obj + 14.0 * M_obj + 5.0 * nA * nB * D_obj));
-  if (!std::isfinite(rho)) return false;
-  const double slab = 32.0 * (double)FLT_EPSILON * M;
-  bool changed = false;
-  for (int a = 0; a < 3; ++a) {
-    const double half = rho * std::sqrt(B[a][0] * B[a][0] + B[a][1] * B[a][1] + B[a][2] * B[a][2]) + slab;
-    lo[a] = std::nextafterf((float)(ctr[a] - half), -INFINITY);
-    hi[a] = std::nextafterf((float)(ctr[a] + half), INFINITY);
-    if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) lo[a] = ref_lo[a], hi[a] = ref_hi[a];
-    lo[a] = std::max(lo[a], ref_lo[a]), hi[a] = std::min(hi[a], ref_hi[a]);
-    changed = changed || lo[a] != ref_lo[a] || hi[a] != ref_hi[a];
-  }
-  return changed && lo[0] < hi[0] && lo[1] < hi[1] && lo[2] < hi[2];
-}
+// One sphere: ptct::sphere_tight_box (pt_camera_tables.h), the arithmetic the device build of the tables runs as well.
 int tighten_sphere_leaves(std::vector<ptd::Node>& nodes, const PtGeom* geoms, const double origin_lo[3], const double origin_hi[3]) {
   int tightened = 0;
   for (ptd::Node& n : nodes) {
     if (n.geom < 0 || geoms[n.geom].type != PT_GEOM_SPHERE) continue;
     float lo[3], hi[3];
-    if (!sphere_tight_box(geoms[n.geom], origin_lo, origin_hi, n.bmin, n.bmax, lo, hi)) continue;
+    if (!ptct::sphere_tight_box(geoms[n.geom].inverseTransform, origin_lo, origin_hi, n.bmin, n.bmax, lo, hi)) continue;
     std::memcpy(n.bmin, lo, 12);
     std::memcpy(n.bmax, hi, 12);
     ++tightened;
@@ -225,30 +180,52 @@ void origin_region(const float root_min[3], const float root_max[3], const float
 // camera position).  The float cell walk's error grows with eps * |coordinate| and eps * t_in, not with the extent, so
 // for a small scene far from the origin (|coordinate| / extent >~ 1e3) 1e-4 * extent alone would sink below the
 // walk's rounding; the pad therefore never goes below 64 ulps of that magnitude.
+// The grid's frame for a scene's bounds: pad, lower corner and extent, or false where no grid is built (an empty or non-finite extent, a
+// scene that is a speck at its distance from the origin).  Host arithmetic for both builds of the tables.
+bool grid_frame(const float root_min[3], const float root_max[3], double coord_mag, ptct::GridFrame& f) {
+  double maxext = 0.0;
+  for (int a = 0; a < 3; ++a) maxext = std::max(maxext, (double)root_max[a] - (double)root_min[a]);
+  if (!(maxext > 0.0) || !std::isfinite(maxext)) return false;
+  for (int a = 0; a < 3; ++a) coord_mag = std::max({coord_mag, std::fabs((double)root_min[a]), std::fabs((double)root_max[a])});
+  f.pad = std::max(1e-4 * maxext, 64.0 * (double)FLT_EPSILON * coord_mag);
+  if (!(f.pad < 0.05 * maxext)) return false;  // the scene is a speck at its distance from the origin: cells would be all padding
+  for (int a = 0; a < 3; ++a) {
+    f.lo[a] = (double)root_min[a] - 2.0 * f.pad;
+    f.ext[a] = ((double)root_max[a] + 2.0 * f.pad) - f.lo[a];
+  }
+  return true;
+}
+// The shape the kernels read, for the resolution in f.res; returns the number of cells.
+int64_t grid_shape(const ptct::GridFrame& f, GridShape& s) {
+  int64_t ncell = 1;
+  for (int a = 0; a < 3; ++a) {
+    s.res[a] = f.res[a];
+    s.gmin[a] = (float)f.lo[a];
+    s.cs[a] = (float)(f.ext[a] / s.res[a]);
+    s.inv_cs[a] = (float)(s.res[a] / f.ext[a]);
+    ncell *= s.res[a];
+  }
+  s.pad = (float)f.pad;
+  return ncell;
+}
+size_t grid_guard(const GridShape& s) { return (size_t)s.res[0] * s.res[1] + s.res[0] + 2; }
+
 bool build_grid(const std::vector<ptd::Node>& nodes, const PtGeom* geoms, int num_geoms, const float root_min[3], const float root_max[3],
                 double coord_mag, double density, bool forced, Grid& grid, const int* fixed_res) {
   std::vector<int> leaves;
   for (size_t i = 0; i < nodes.size(); ++i)
     if (nodes[i].geom >= 0) leaves.push_back((int)i);
   if (leaves.empty()) return false;
-  double ext[3], maxext = 0.0;
-  for (int a = 0; a < 3; ++a) maxext = std::max(maxext, (double)root_max[a] - (double)root_min[a]);
-  if (!(maxext > 0.0) || !std::isfinite(maxext)) return false;
-  for (int a = 0; a < 3; ++a) coord_mag = std::max({coord_mag, std::fabs((double)root_min[a]), std::fabs((double)root_max[a])});
-  const double pad = std::max(1e-4 * maxext, 64.0 * (double)FLT_EPSILON * coord_mag);
-  if (!(pad < 0.05 * maxext)) return false;  // the scene is a speck at its distance from the origin: cells would be all padding
-  double lo[3], vol = 1.0;
-  for (int a = 0; a < 3; ++a) {
-    lo[a] = (double)root_min[a] - 2.0 * pad;
-    ext[a] = ((double)root_max[a] + 2.0 * pad) - lo[a];
-    vol *= ext[a];
-  }
-  // the cells [c0, c1] per axis that a leaf's box grown by `pad` touches, at resolution `res`
+  ptct::GridFrame frame;
+  if (!grid_frame(root_min, root_max, coord_mag, frame)) return false;
+  const double* ext = frame.ext;
+  double vol = 1.0;
+  for (int a = 0; a < 3; ++a) vol *= ext[a];
+  // the cells [c0, c1] per axis that a leaf's box grown by `pad` touches, at resolution `res` (pt_camera_tables.h)
   auto cell_range = [&](const ptd::Node& n, const int res[3], int c0[3], int c1[3]) {
-    for (int a = 0; a < 3; ++a) {
-      c0[a] = std::min(std::max((int)std::floor(((double)n.bmin[a] - pad - lo[a]) / ext[a] * res[a]), 0), res[a] - 1);
-      c1[a] = std::min(std::max((int)std::floor(((double)n.bmax[a] + pad - lo[a]) / ext[a] * res[a]), 0), res[a] - 1);
-    }
+    ptct::GridFrame f = frame;
+    std::memcpy(f.res, res, sizeof(f.res));
+    ptct::cell_range(n.bmin, n.bmax, f, c0, c1);
   };
   auto references = [&](const int res[3]) {
     int64_t refs = 0;
@@ -286,17 +263,11 @@ bool build_grid(const std::vector<ptd::Node>& nodes, const PtGeom* geoms, int nu
       if (cost < best_cost) best_cost = cost, std::memcpy(s.res, res, sizeof(res));
     }
   }
-  int64_t ncell = 1;
-  for (int a = 0; a < 3; ++a) {
-    s.gmin[a] = (float)lo[a];
-    s.cs[a] = (float)(ext[a] / s.res[a]);
-    s.inv_cs[a] = (float)(s.res[a] / ext[a]);
-    ncell *= s.res[a];
-  }
-  s.pad = (float)pad;
+  std::memcpy(frame.res, s.res, sizeof(frame.res));
+  const int64_t ncell = grid_shape(frame, s);
   if (ncell > (int64_t)64 * 1024 * 1024) return false;
   const int64_t refs = references(s.res);
-  if (refs > (int64_t)1 << 22) return false;  // ring entries hold 22-bit record indices
+  if (refs > ptct::kMaxRefs) return false;  // ring entries hold 22-bit record indices
   if (num_geoms > (1 << 24)) return false;    // records hold 24-bit geom indices
   // a candidate only while the lists stay moderate (whether it beats the BVH scan is measured, choose_traversal())
   if (!forced && refs > 64 * (int64_t)leaves.size()) return false;
@@ -326,8 +297,7 @@ bool build_grid(const std::vector<ptd::Node>& nodes, const PtGeom* geoms, int nu
         for (int x = c0[0]; x <= c1[0]; ++x) {
           ptd::Node it = nodes[li];
           it.skip = li;
-          it.geom = (x > c0[0] ? 1 : 0) | (x < c1[0] ? 2 : 0) | (y > c0[1] ? 4 : 0) | (y < c1[1] ? 8 : 0) | (z > c0[2] ? 16 : 0) |
-                    (z < c1[2] ? 32 : 0) | ((geoms[nodes[li].geom].type & 3) << 6) | (nodes[li].geom << 8);
+          it.geom = ptct::record_geom_word(x, y, z, c0, c1, geoms[nodes[li].geom].type, nodes[li].geom);
           grid.items[fill[cell(x, y, z)]++] = it;
         }
   }
@@ -347,17 +317,7 @@ bool build_grid(const std::vector<ptd::Node>& nodes, const PtGeom* geoms, int nu
 // ORIGIN, not the box: a small node next to the world origin of a wide scene needs the margin of the whole scene.  So the slack is
 // 1e-5 of the half extent plus 1e-5 * `magnitude`, M = scene_magnitude() (where ray origins lie: the scene bounds, the camera):
 // 1e-5 / (10 u) = 16.7 times the bound.
-void center_half_box(float bmin[3], float bmax[3], bool inner, double magnitude) {
-  for (int a = 0; a < 3; ++a) {
-    const double lo = bmin[a], hi = bmax[a];
-    const float c = (float)(0.5 * (lo + hi));
-    double h = std::max(hi - (double)c, (double)c - lo);
-    if (inner) h = h * (1.0 + 1e-5) + 1e-5 * magnitude + 1e-30;
-    float hf = (float)h;
-    if ((double)hf < h) hf = std::nextafter(hf, INFINITY);
-    bmin[a] = c, bmax[a] = hf;
-  }
-}
+void center_half_box(float bmin[3], float bmax[3], bool inner, double magnitude) { ptct::center_half_box(bmin, bmax, inner, magnitude); }
 // The largest coordinate magnitude a ray origin of the scene has: hit points lie in the scene bounds, depth 0 starts at the camera.
 double scene_magnitude(const float root_min[3], const float root_max[3], const float cam[3]) {
   double m = 0.0;
@@ -413,7 +373,7 @@ void camera_tables(HostTables& t, const CameraBase& base, const float cam[3], in
       if (repeat) continue;
       // the cell table with empty cells before and after it: a walk may run up to one cell per axis past the grid's far side
       // before its distance test ends it (pt_grid.inc CellWalk)
-      grid.guard = (size_t)grid.shape.res[0] * grid.shape.res[1] + grid.shape.res[0] + 2;
+      grid.guard = grid_guard(grid.shape);
       const uint32_t total = grid.start.back();
       grid.start.insert(grid.start.begin(), grid.guard, 0u);
       grid.start.resize(grid.start.size() + grid.guard, total);

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/pt_amd.h"
+#include "pt_camera_tables.h"
 #include "pt_device.h"
 
 namespace pt {
@@ -36,6 +37,11 @@ struct Grid {
 // `density` are skipped, everything else (pad, refusals, records) is computed as for any grid
 bool build_grid(const std::vector<ptd::Node>& nodes, const PtGeom* geoms, int num_geoms, const float root_min[3], const float root_max[3],
                 double coord_mag, double density, bool forced, Grid& grid, const int* fixed_res = nullptr);
+// The host scalars of a grid, for both builds of the camera-dependent tables (pt_camera_tables.h): the frame (false: no grid for these
+// bounds and this coordinate magnitude), the shape for frame.res with the number of cells, the guard cells of a renderer's cell table.
+bool grid_frame(const float root_min[3], const float root_max[3], double coord_mag, ptct::GridFrame& frame);
+int64_t grid_shape(const ptct::GridFrame& frame, GridShape& shape);
+size_t grid_guard(const GridShape& shape);
 void origin_region(const float root_min[3], const float root_max[3], const float cam[3], double olo[3], double ohi[3]);
 int tighten_sphere_leaves(std::vector<ptd::Node>& nodes, const PtGeom* geoms, const double origin_lo[3], const double origin_hi[3]);
 double scene_magnitude(const float root_min[3], const float root_max[3], const float cam[3]);

@@ -332,6 +332,35 @@ int pt_clear(void);
  * other than the renderer's (a new resolution needs pt_init); a component of position, view, up, right, fov or pixelLength that
  * is not finite.  lookAt is not read by the renderer. */
 int pt_set_camera(const PtCamera* cam);
+/* pt_set_camera with options.  The contract is pt_set_camera's, word for word, refusals and their order included (under the name
+ * pt_set_camera_ex), with one more refusal, placed after the null camera: a bit of `flags` that is not defined below.  flags == 0 is
+ * pt_set_camera.
+ * PT_SET_CAMERA_DEVICE_TABLES: the camera-dependent tables are rebuilt ON THE DEVICE (csrc/pt_camera_tables.hip) from a device copy of
+ * the camera-independent tables: per node, per top entry and per (leaf, cell) reference the kernels run the very functions the host
+ * build runs (csrc/pt_camera_tables.h), the grid is a counting sort whose records are placed by rank, and the host contributes the
+ * scalars it computes as ever (origin region, scene magnitude, cull margin, the grid's pad, corner, extent and refusals).  The tables
+ * are the host build's byte for byte, so everything pt_set_camera promises holds.  One 16-byte record is read back between the
+ * grid's count and its scan (references, longest list, tightened leaves); nothing else crosses the bus.  The first such move of a
+ * renderer uploads that copy (base nodes, base top list, 80 bytes per geom) and allocates the build's workspace (a word per grid
+ * cell, the scan's sums, a word per possible reference: at most 64 per leaf, 2^22 for a forced grid); both stay and count in
+ * PtStats.device_bytes from then on.  A renderer that never asks for the device path allocates nothing of this.
+ * What the device build does not take runs on the host, with the same result, and PtSetCameraTimes.fallback says why:
+ * PT_DEVICE_TABLES_LIST: a cell of a forced grid (debug_flags 256) lists more than 4096 records (the host refuses such a grid unless
+ * it is forced); PT_DEVICE_TABLES_CELLS: the grid has more than 2^22 cells. */
+#define PT_SET_CAMERA_DEVICE_TABLES 1u
+#define PT_DEVICE_TABLES_LIST 1
+#define PT_DEVICE_TABLES_CELLS 2
+int pt_set_camera_ex(const PtCamera* cam, uint32_t flags);
+/* The last move of the renderer (pt_set_camera or pt_set_camera_ex), host wall clock, milliseconds; all zero before the first. */
+typedef struct PtSetCameraTimes {
+  double tables_ms;  /* the camera-dependent tables: host build + upload, or the device build with its one readback (the first
+                        device-path move: with the upload of the camera-independent tables and the workspace's allocation)   */
+  double rearm_ms;   /* launch plan, path buffers and records back to their first state, the worker, pt_clear              */
+  double total_ms;   /* = PtSetupTimes.set_camera_ms                                                                        */
+  int32_t path;      /* 0 host tables, 1 device tables                                                                     */
+  int32_t fallback;  /* 0, or why a requested device build ran on the host (PT_DEVICE_TABLES_*); path is then 0            */
+} PtSetCameraTimes;
+int pt_get_set_camera_times(PtSetCameraTimes* out);
 /* Host wall-clock times of a renderer's setup, in milliseconds: the host build of the scene tables, their upload, the
  * allocation of the batch buffers, the timing probe of the traversal structures (0 where none ran), and the last pt_set_camera
  * (its synchronise included) with the number of such calls since the renderer was created. */
@@ -726,6 +755,8 @@ int pt_ctx_reset_stats(PtContext* c);
 int pt_ctx_clear(PtContext* c);
 int pt_ctx_set_camera(PtContext* c, const PtCamera* cam);
 int pt_ctx_get_setup_times(PtContext* c, PtSetupTimes* out);
+int pt_ctx_set_camera_ex(PtContext* c, const PtCamera* cam, uint32_t flags);
+int pt_ctx_get_set_camera_times(PtContext* c, PtSetCameraTimes* out);
 int pt_ctx_set_reference(PtContext* c, const float* rgb_avg_host);
 int pt_ctx_get_convergence(PtContext* c, int iter_first, int iter_count, double* sse);
 int pt_ctx_iterations_to_clean(PtContext* c, float threshold_db, int* iteration);
@@ -792,6 +823,7 @@ int pt_group_sync(PtGroup* g);
 /* pt_set_camera on every context: the camera is checked against all of them before any of them changes, so a refusal leaves
  * the whole group as it was; the group's own buffers on the root device stay. */
 int pt_group_set_camera(PtGroup* g, const PtCamera* cam);
+int pt_group_set_camera_ex(PtGroup* g, const PtCamera* cam, uint32_t flags); /* pt_set_camera_ex on every context, asked first in the same way */
 int pt_group_gather(PtGroup* g, float* rgb_sum_host);             /* W*H*3 floats, raw orientation */
 int pt_group_gather_u8(PtGroup* g, float samples, uint8_t* rgb8_host); /* W*H*3 bytes as pt_save_u8, converted on each device */
 /* The feature buffers of the whole frame: every context sums its own rows, the planes meet at the root like the image (one
@@ -885,6 +917,18 @@ int pt_stage_intersect_grid(int n, const float* origin, const float* dir, int pr
  * (num_leaves: the scene's primitives) and the length of the longest cell list.  pt_build_grid builds the cost model's
  * grid without the camera; this is the one pt_init kept.  Refused when the renderer walks no grid. */
 int pt_stage_grid_info(PtGridInfo* info, int32_t* max_cell_records);
+/* The camera-dependent tables of the default renderer as they lie on the device, byte for byte: `which` 0 nodes, 1 their centre / half
+ * extent copies, 2 the top list, 3 its copies, 4 the cell table of the grid with its guard cells, 5 the grid's records, 6 their copies,
+ * 7 the cull margin (4 bytes).  *bytes receives the table's size; up to `cap` bytes of it go to `out` (may be NULL with cap 0).  A
+ * table the renderer does not have (copies outside the fast build, a grid where none is built) gives *bytes = 0.  Synchronises. */
+int pt_stage_read_tables(int which, void* out, uint64_t cap, uint64_t* bytes);
+/* Device self-check of csrc/pt_camera_tables.h, in the manner of pt_selfcheck_ieee: one of its functions runs on the GPU and on the
+ * host over the same operands, and *mismatches counts the operand sets whose results differ in any bit.  kind 0 double sqrt, 1 double
+ * a / b (a result that is a NaN on both sides counts as equal), 2 (float) of a double and nextafterf of it in both directions (also
+ * against libm's nextafterf on the host), 3 center_half_box (leaf and inner form), 4 sphere_tight_box, 5 the grid's cell_range.
+ * The operands are a fixed list of edge values per kind (+-0, denormals, the largest finite values, values that convert to infinity,
+ * singular matrices) followed by `count` pseudo-random sets derived from `seed`.  Needs no renderer; runs on the current device. */
+int pt_selfcheck_camera_math(int kind, uint64_t count, uint32_t seed, uint64_t* mismatches);
 /* shadeAndExtendRays (pathtrace.cu:336-437) for live paths at `depth`:
  * in/out origin, dir, color; out alive[n] (1 = path continues).  Dead paths get the
  * retirement colour (sky factor applied (trace_depth - depth) times on a miss). */
