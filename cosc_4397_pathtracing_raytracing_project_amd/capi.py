@@ -78,7 +78,7 @@ class PtStats(C.Structure):
                 ("grid_blocks", C.c_int32), ("num_queues", C.c_int32), ("iters_per_batch", C.c_int32),
                 ("device_bytes", C.c_int64), ("primary_fused", C.c_int32), ("bounces_fused", C.c_int32),
                 ("arith", C.c_int32), ("grid_cells", C.c_int32), ("tight_leaves", C.c_int32), ("paths_waves", C.c_int32), ("record_form", C.c_int32),
-                ("gather_form", C.c_int32), ("primary_launches", C.c_int64)]
+                ("gather_form", C.c_int32), ("primary_launches", C.c_int64), ("inline_gathers", C.c_int64)]
 
 
 class PtDenoiseOptions(C.Structure):

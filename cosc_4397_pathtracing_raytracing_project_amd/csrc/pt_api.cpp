@@ -26,7 +26,7 @@
 namespace {
 
 std::string g_err;
-constexpr int kDebugFlags = 16 | 32 | 64 | 128 | 256 | 512 | ptk::kRetireEveryIteration | 2048 | ptk::kWholeRecords | ptk::kNoFirstBounce | ptk::kRecordsByVisit | ptk::kTileGather | ptk::kPrimaryEveryBatch;  // the PtOptions.debug_flags bits pt_init accepts
+constexpr int kDebugFlags = 16 | 32 | 64 | 128 | 256 | 512 | ptk::kRetireEveryIteration | 2048 | ptk::kWholeRecords | ptk::kNoFirstBounce | ptk::kRecordsByVisit | ptk::kTileGather | ptk::kPrimaryEveryBatch | ptk::kGatherEveryBatch;  // the PtOptions.debug_flags bits pt_init accepts
 static_assert(sizeof(PtOptions) == 80, "capi.PtOptions mirrors this layout");
 static_assert(PT_CONVERGENCE_WAVES == ptk::kConvWaves, "pt_amd.h documents the size of the convergence metric's partial sums");
 }  // namespace
@@ -130,7 +130,16 @@ ptk::BatchInfo tile_batch(const Ctx& g, int iter_first, int K) {
   return b;
 }
 
-int run_batch(Ctx& g, int iter_first, int kb) {
+// The stream gather of the batch that waits (pt_sched.h inline_gather) as a launch of its own: its successor could not take it.
+static void gather_waiting(Ctx& g) {
+  if (!g.waiting.live) return;
+  ptd::RetireBuf ret = g.ret;
+  if (g.waiting.plane) ret.rec = g.rec_plane1;
+  g.k->collect_stream_planes(g.stream, g.waiting.b, g.qs, ret, g.ret.rec, g.d_image);
+  g.waiting.live = false;
+}
+
+int run_batch(Ctx& g, int iter_first, int kb, int after) {
   ptk::BatchInfo b = tile_batch(g, iter_first, kb);
   b.slot_shift = g.slot_shift;
   b.flat = g.fuse_bounces ? 0 : 1;
@@ -154,6 +163,17 @@ int run_batch(Ctx& g, int iter_first, int kb) {
   const bool once = g.fuse_primary && ptk::primary_once(b, g.debug_flags, ptk::search_form(sc), sc.num_mats, g.ret.seg_cap);
   const bool had_first_hits = g.primary_valid;
   g.primary_valid = false;
+  // The gather: a batch with fixed record slots streams them; the metric's batches (its partial sums have a fixed partition) and every
+  // other batch keep the tile gather behind k_count_stats.
+  ptk::ConvInfo cv{g.d_ref, g.d_partial, -1, kb};
+  if (g.conv_live) {
+    if (g.conv_have_ref) cv.first_k = 0;
+    else if (g.conv >= iter_first && g.conv < iter_first + kb) cv.capture_k = g.conv - iter_first, cv.first_k = cv.capture_k + 1, g.conv_have_ref = true;
+    g.conv_last = std::max(g.conv_last, iter_first + kb - 1);
+  }
+  const bool conv_batch = cv.capture_k >= 0 || cv.first_k < kb;
+  const int form = ptk::gather_form(b.fixed_slots != 0, g.debug_flags, conv_batch);
+  bool gathers_waiting = false;  // this batch's k_paths gathers the batch before it
   if (g.fuse_primary) {
     // depth 0 in one launch; its survivors are the depth-1 input (buf[1], cnt[1])
     const ptd::Queues pq = queues_for(g, g.grid_primary);
@@ -161,15 +181,26 @@ int run_batch(Ctx& g, int iter_first, int kb) {
     std::memset(&key, 0, sizeof(key));
     key.sc = sc, key.cam = g.dcam, key.b = b, key.b.iter_first = key.b.K = 0, key.qs = pq, key.out = g.buf[1], key.ret = g.ret;
     key.kernels = &k, key.grid = g.grid_primary, key.debug_flags = g.debug_flags;
-    if (!(once && had_first_hits && std::memcmp(&key, &g.primary_key, sizeof(key)) == 0)) {
+    const bool same_key = once && had_first_hits && std::memcmp(&key, &g.primary_key, sizeof(key)) == 0;
+    gathers_waiting = ptk::inline_gather(g.waiting.live, form, once, same_key, g.rec_plane1 != nullptr && !g.conv, g.debug_flags) && g.grid_paths > 0;
+    if (!gathers_waiting) gather_waiting(g);  // before k_primary rewrites what that gather reads
+    if (!same_key) {
       k.primary(g.stream, g.grid_primary, sc, g.dcam, b, pq, cnt_row(0), cnt_row(1), g.buf[1], g.ret);
       g.primary_launches += 1;
       std::memcpy(&g.primary_key, &key, sizeof(key));
     }
     d0 = 1;
   } else {
+    gather_waiting(g);
     k.generate(g.stream, g.grid_gen, g.dcam, b, queues_for(g, g.grid_gen), g.buf[0], cnt_row(0));
   }
+  // A batch whose gather waits for its successor stores its records in plane `after` mod 2, so that the planes alternate along the call
+  // and its last batch — gathered by k_collect_stream, like the only batch of a call — lies in plane 0; k_paths of a batch that gathers
+  // its predecessor takes the plane that one did not use (the same thing, unless the chain began in mid-call).
+  const bool defers = ptk::defers_gather(after > 0, form, once, g.rec_plane1 != nullptr && !g.conv, g.debug_flags) && g.grid_paths > 0;
+  const int plane = gathers_waiting ? 1 - g.waiting.plane : defers ? after & 1 : 0;
+  ptd::RetireBuf ret = g.ret;
+  if (plane) ret.rec = g.rec_plane1;
   int src = d0 & 1;
   // Depths >= 1, fused: ONE launch of k_paths — persistent lanes with their own depth, no path state through HBM after depth 0
   const bool all_depths = g.grid_paths > 0;
@@ -188,7 +219,12 @@ int run_batch(Ctx& g, int iter_first, int kb) {
   };
   if (all_depths) {
     if (timed_from()) return -1;
-    k.paths(g.stream, g.grid_paths, sc, b, queues_for(g, g.grid_paths), g.d_cnt, g.buf[1], g.ret);
+    if (gathers_waiting) {
+      const ptk::PrevGather prev{g.waiting.plane ? g.rec_plane1 : g.ret.rec, g.ret.rec, g.d_image, g.waiting.b.K, 0};
+      k.paths_gather(g.stream, g.grid_paths, sc, b, queues_for(g, g.grid_paths), g.d_cnt, g.buf[1], ret, prev);
+      g.waiting.live = false;
+      g.inline_gathers += 1;
+    } else k.paths(g.stream, g.grid_paths, sc, b, queues_for(g, g.grid_paths), g.d_cnt, g.buf[1], ret);
     if (timed_to()) return -1;
   }
   // ... unfused (tests, A/B): computeIntersections and shadeAndExtendRays as separate launches per depth
@@ -201,18 +237,19 @@ int run_batch(Ctx& g, int iter_first, int kb) {
     k.shade(g.stream, g.grid_shade, sc, b, d, queues_for(g, g.grid_shade), cin, cout, g.buf[src], g.hits, g.buf[src ^ 1], g.ret);
     src ^= 1;
   }
-  ptk::ConvInfo cv{g.d_ref, g.d_partial, -1, kb};
-  if (g.conv_live) {
-    if (g.conv_have_ref) cv.first_k = 0;
-    else if (g.conv >= iter_first && g.conv < iter_first + kb) cv.capture_k = g.conv - iter_first, cv.first_k = cv.capture_k + 1, g.conv_have_ref = true;
-    g.conv_last = std::max(g.conv_last, iter_first + kb - 1);
-  }
-  // The gather: a batch with fixed record slots streams them, the counter rows' blocks in the same launch; the metric's batches (its
-  // partial sums have a fixed partition) and every other batch keep the tile gather behind k_count_stats.
-  const bool conv_batch = cv.capture_k >= 0 || cv.first_k < kb;
-  g.gather_form = ptk::gather_form(b.fixed_slots != 0, g.debug_flags, conv_batch);
-  if (g.gather_form == ptk::kGatherStream) k.collect_stream(g.stream, b, g.qs, g.ret, g.d_image, g.d_cnt, g.depth, g.d_stats);
-  else {
+  // A stream-gathered batch with a successor in its render call leaves its gather to that batch's k_paths (pt_sched.h defers_gather):
+  // only the counter rows are folded now.  Otherwise the stream gather runs here, the counter rows' blocks in the same launch when the
+  // records lie in plane 0.
+  g.gather_form = form;
+  if (defers) {
+    k.count_stats(g.stream, g.qs, g.d_cnt, g.depth, g.d_stats);
+    g.waiting.live = true, g.waiting.b = b, g.waiting.plane = plane;
+    g.gather_form = ptk::kGatherInline;
+  } else if (form == ptk::kGatherStream && plane == 0) k.collect_stream(g.stream, b, g.qs, g.ret, g.d_image, g.d_cnt, g.depth, g.d_stats);
+  else if (form == ptk::kGatherStream) {
+    k.count_stats(g.stream, g.qs, g.d_cnt, g.depth, g.d_stats);
+    k.collect_stream_planes(g.stream, b, g.qs, ret, g.ret.rec, g.d_image);
+  } else {
     k.count_stats(g.stream, g.qs, g.d_cnt, g.depth, g.d_stats);
     if (conv_batch) k.collect_conv(g.stream, b, g.qs, g.ret, g.d_image, cv, g.d_sse);
     else k.collect(g.stream, b, g.qs, g.ret, g.d_image);
@@ -498,8 +535,10 @@ static __global__ void k_poison_records(ptd::Word4* rec, unsigned long long per_
 
 static int poison_records(Ctx& g) {  // on the context's stream; the plan in g.ret must be the one the records were allocated for
   const size_t regions = (size_t)g.qs.Q * g.ret.kmax, per_queue = (size_t)g.ret.kmax * g.ret.seg_cap;
-  hipLaunchKernelGGL(k_poison_records, dim3((unsigned)std::min<size_t>((regions * g.ret.seg_cap + 255) / 256, 65536)), dim3(256), 0, g.stream, g.ret.rec,
-                     (unsigned long long)per_queue, (unsigned long long)(regions * g.ret.seg_cap), g.qs.Q);
+  for (ptd::Word4* plane : {g.ret.rec, g.rec_plane1})
+    if (plane)
+      hipLaunchKernelGGL(k_poison_records, dim3((unsigned)std::min<size_t>((regions * g.ret.seg_cap + 255) / 256, 65536)), dim3(256), 0, g.stream, plane,
+                         (unsigned long long)per_queue, (unsigned long long)(regions * g.ret.seg_cap), g.qs.Q);
   HIP_OK(hipGetLastError());
   return 0;
 }
@@ -531,6 +570,22 @@ int alloc_batch_buffers(Ctx& g) {
     const size_t regions = (size_t)Q * g.ret.kmax;
     const size_t wq_max = sub_words_max(g);
     if (dalloc(g, &g.ret.rec, regions * g.ret.seg_cap)) return -1;
+    // The second record plane (pt_sched.h inline_gather), where a context's batches can be of that form at all: several batches per render
+    // call need K > 1 iterations per batch to be worth a plane, the form needs the fused kernels and no switch against it.  Whether a
+    // batch has fixed slots is decided per batch (run_batch).  A failed allocation leaves the context on the standalone gather.
+    g.rec_plane1 = nullptr;
+    // (A context with the convergence metric gets the plane too — PtStats.device_bytes differs by the metric's own buffers, as
+    // documented — and never uses it; a worker's batches are single launches of run_batch: none.)
+    if (g.fuse_primary && g.fuse_bounces && g.depth > 1 && !g.aa_jitter && !g.borrowed &&
+        !(g.debug_flags & (ptk::kGatherEveryBatch | ptk::kTileGather | ptk::kRecordsByVisit | ptk::kNoFirstBounce | ptk::kPrimaryEveryBatch))) {
+      void* p = nullptr;
+      const size_t bytes = regions * g.ret.seg_cap * sizeof(ptd::Word4);
+      if (hipMalloc(&p, bytes) == hipSuccess) {
+        g.allocs.push_back(p);
+        g.device_bytes += (int64_t)bytes;
+        g.rec_plane1 = static_cast<ptd::Word4*>(p);
+      } else (void)hipGetLastError();
+    }
     // the fill levels start at zero; k_collect re-zeroes them after every batch
     if (ensure(g, g.ret.cnt, regions * sizeof(*g.ret.cnt), Zero::blocking) || ensure(g, g.ret.sub, regions * wq_max * sizeof(*g.ret.sub), Zero::blocking)) return -1;
     // In a BatchInfo::retire_once batch nobody writes the retiree slots at the front of the regions k >= 1, and later they hold an older
@@ -769,7 +824,7 @@ int pt_ctx_render(PtContext* c, int iter_first, int iter_count) {
   HIP_OK(hipEventRecord(ev.a, g.stream));
   const int end = iter_first + iter_count;
   for (int it = iter_first; it < end; it += g.K)
-    if (run_batch(g, it, std::min(g.K, end - it))) {
+    if (run_batch(g, it, std::min(g.K, end - it), it + g.K < end ? (end - it - 1) / g.K : 0)) {
       g.failed = true;
       g.free_events.push_back(ev);  // back to the pool (destroy() releases it)
       return -1;
@@ -873,6 +928,7 @@ int pt_ctx_get_stats(PtContext* c, PtStats* out) {
   out->tight_leaves = g.tight_leaves;
   out->record_form = g.record_form;
   out->gather_form = g.gather_form;
+  out->inline_gathers = g.inline_gathers;
   out->primary_launches = g.primary_launches;
   out->paths_waves = 0;
   if (g.qs.deal && g.grid_paths > 0) {  // the table the NEXT batch's k_paths launch will read (ptd::Queues::deal)

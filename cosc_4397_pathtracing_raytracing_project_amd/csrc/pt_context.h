@@ -92,6 +92,15 @@ struct PtContext : PtShared {
   ptd::PathBuf buf[2]{};
   ptd::HitBuf hits{};
   ptd::RetireBuf ret{};  // retirement records + fill levels (pt_device.h)
+  // The second record plane and the batch whose stream gather waits for the next batch's k_paths (pt_sched.h inline_gather).  Set and
+  // consumed inside one pt_ctx_render call: nothing waits when a call returns.
+  ptd::Word4* rec_plane1 = nullptr;  // as large as ret.rec (plane 0); absent where the form cannot apply or the allocation failed
+  struct WaitingGather {
+    bool live = false;
+    ptk::BatchInfo b{};
+    int plane = 0;  // where that batch's k_paths stored its records
+  } waiting;
+  int64_t inline_gathers = 0;  // batches gathered inside the next batch's k_paths (PtStats.inline_gathers)
   float* d_image = nullptr;
   // First-hit feature buffers (pt_ctx_render_features): PT_FEATURE_PLANES planes of N float4 sums; absent until the first feature pass
   float4* d_feat = nullptr;
@@ -260,7 +269,7 @@ int copy_out(PtContext* c, const char* who, T* host, size_t per_pixel, Source so
 // pt_api.cpp
 ptk::SceneTables tables(const Ctx& g);
 ptk::BatchInfo tile_batch(const Ctx& g, int iter_first, int K);  // BatchInfo's iterations and the fields that describe the tile
-int run_batch(Ctx& g, int iter_first, int kb);
+int run_batch(Ctx& g, int iter_first, int kb, int after = 0);  // after: batches of the same render call that follow this one
 int batch_iters_for(int iters_per_batch, int N, int* slot_shift);
 int plan_batches(Ctx& g, const PtOptions& opt);
 void plan_launch(Ctx& g);

@@ -110,6 +110,16 @@ struct ConvInfo {
   int32_t first_k;    // first k with a value; K: none
 };
 
+// The gather of the batch BEFORE the one a k_paths launch traces, done by that launch's waves (pt_sched.h inline_gather): the records
+// that batch's k_paths wrote, in the record plane this launch does not write.
+struct PrevGather {
+  const ptd::Word4* rec;     // the plane the previous batch's k_paths wrote: [Q][kmax][seg_cap] like RetireBuf::rec
+  const ptd::Word4* plane0;  // the first plane: k_primary's depth-0 retirees lie there whichever plane a batch writes
+  float* image;              // [N][3]
+  int32_t K;                 // iterations of the previous batch
+  int32_t pad;
+};
+
 // Resident workgroups per CU for each persistent kernel (hipOccupancyMaxActiveBlocksPerMultiprocessor),
 // so that grid = CUs * blocks never exceeds what is co-resident: work is dealt statically to waves,
 // a workgroup that has to wait for a free slot would run its whole share after everybody else.
@@ -185,6 +195,11 @@ struct KernelApi {
   // the slot's K records in iteration order, no tile (k_collect_stream in pt_output.inc); the counter rows' blocks ride behind the gather's.
   void (*collect_stream)(hipStream_t s, const BatchInfo& b, const ptd::Queues& qs, ptd::RetireBuf ret, float* image_rgb, int32_t* cnt, int depth_count,
                          unsigned long long* stats);
+  // `paths` for a batch with fixed record slots whose waves also gather the batch before it (PrevGather; k_paths' own stores go to ret.rec,
+  // the other record plane), and the standalone stream gather of a batch in whichever plane (ret.rec), without the counter rows' blocks.
+  void (*paths_gather)(hipStream_t s, int grid, const SceneTables& sc, const BatchInfo& b, const ptd::Queues& qs, int32_t* cnt, ptd::PathBuf in,
+                       ptd::RetireBuf ret, const PrevGather& prev);
+  void (*collect_stream_planes)(hipStream_t s, const BatchInfo& b, const ptd::Queues& qs, ptd::RetireBuf ret, const ptd::Word4* plane0, float* image_rgb);
 };
 const KernelApi* api_exact();
 const KernelApi* api_fma();

@@ -1687,9 +1687,21 @@ static_assert((kVisitRing & (kVisitRing - 1)) == 0, "visit numbers wrap with a m
 // SPLIT == kFixedSlots (such a batch with BatchInfo::fixed_slots; pt_sched.h fixed_slots): the first-bounce form without the visit ring — the
 // cursor keeps where the record of its sub-list's first path goes, the word that waits beside a record is the path's own record slot
 // (pack_fixed), and a dying lane has nothing to ask anybody: no counter, no lap guard, no limit on the visits of a refill.
-template <Search MODE, int SPLIT = 0>
+// PREV (empty, or PrevGather alone; kFixedSlots only — pt_sched.h inline_gather): the launch also gathers the batch before its own, whose
+// records lie in the other record plane.  The waves of queue q add that batch's records of queue q to the image, stream_gather_slot's
+// work for 64 consecutive slots at a time: group j of the queue's my_nq goes to wave j mod wq, which takes one group each time it moves
+// on to a piece (not the first: nothing is in flight beside it then) and the rest of its share after its last path has retired.  A step
+// is synchronous — loads, wait, adds, stores — and stands where no transfer into the refill slots is younger than a round, so the
+// refill's accounting of what is outstanding is what it was; its time is taken off the ticks the wave reports for the deal.
+constexpr int kInlineGroup = 8;  // loads in flight per lane in a step
+template <int GROUP>
+PT_DEV void stream_gather_slot(int N, int K, const QueueShare& sh, const ptd::RetireBuf& ret, const ptd::Word4* plane, const ptd::Word4* front,
+                               float* __restrict__ image, int q, int s);  // pt_output.inc
+template <typename T, typename... R>
+PT_DEV const T& first_of(const T& t, const R&...) { return t; }
+template <Search MODE, int SPLIT = 0, typename... PREV>
 __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPathsScanWaves : kPathsGridWaves) void k_paths(SceneTables sc, BatchInfo b, ptd::Queues qs, int32_t* __restrict__ cnt /* [depth][Q] rows */,
-                                                               ptd::PathBuf in, ptd::RetireBuf ret) {
+                                                               ptd::PathBuf in, ptd::RetireBuf ret, PREV... prev) {
   extern __shared__ float4 lds_raw[];
   char* lds = reinterpret_cast<char*>(lds_raw);
   const PathsLds L = paths_lds<MODE, kFast>(sc);
@@ -1710,6 +1722,8 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
   }
   using WM = PathsWaveMap<MODE, kFast>;
   constexpr bool FIXED = SPLIT == kFixedSlots, FIRST = SPLIT == kFirstBounce || FIXED;  // FIRST: the first bounce is sampled here
+  constexpr bool GATHER = sizeof...(PREV) > 0;
+  static_assert(!GATHER || FIXED, "only a batch with fixed record slots gathers its predecessor");
   const int he = iter_hash_entries(sc);
   uint32_t* tword = reinterpret_cast<uint32_t*>(lds + L.tword);  // MODE 0: [kMaxTop] leaf | geom << 8 per top entry
   int* lmat = reinterpret_cast<int*>(lds + L.lmat);              // MODE 0: [64] material of the leaf at threaded node index i
@@ -1919,6 +1933,18 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
   bool valid = false, fresh = false, owes = false;  // owes: the lane's path died and its retirement record is not stored yet
   bool has_next = false;                            // a record is waiting in the lane's slot (on its way there)
   int streamed = 0, p_hi = 0;  // the current piece: records [.., streamed) handed out, the piece ends at p_hi; -1: no piece left for this wave
+  // GATHER: the wave's next group of the previous batch's slots, and the time its steps took (100 MHz ticks)
+  [[maybe_unused]] int gj = r;
+  [[maybe_unused]] uint32_t gather_time = 0u;
+  [[maybe_unused]] auto gather_step = [&]() {
+    if constexpr (GATHER) {
+      const PrevGather& pg = first_of(prev...);
+      const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+      stream_gather_slot<kInlineGroup>(b.N, pg.K, qshare, ret, pg.rec, pg.plane0, pg.image, q, gj * 64 + lane);
+      gj += wq;
+      gather_time += (uint32_t)(__builtin_amdgcn_s_memrealtime() - t0);
+    }
+  };
   while (!FIRST) {  // (that form's loop, the same round rotated, follows this one)
     // ── on to the wave's next piece, once the current one is handed out: its own, then whatever the queue's counter gives ──
     if (streamed >= p_hi && p_hi >= 0) {
@@ -2128,6 +2154,8 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
       }
       // ── on to the wave's next piece, once the current one is handed out ──
       if (streamed >= p_hi && p_hi >= 0) {
+        if constexpr (GATHER)
+          if (cord != 0 && gj < my_nq) gather_step();
         int nextp = -1;
         if (cord == 0) nextp = r;
         else if (pieces.needs_counter()) {
@@ -2191,6 +2219,11 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
       if (go) d = bounce_sample(bo, axis), depth += 1, fresh = true;
     }
   }
+  if constexpr (GATHER) {
+    while (gj < my_nq) gather_step();  // the rest of the wave's share
+    if (r == 0)  // the records are consumed: zero counters for the next batch (k_collect_stream's block 0 of the queue)
+      for (int i = lane; i < ret.kmax; i += 64) ret.cnt[(int64_t)q * ret.kmax + i] = 0ull;
+  }
   // statistics: rays traced at depth d >= 2 = this wave's paths retired at depth >= d (row 1 holds the queue's input count already)
   if (lane == 0) {
     int reached = 0, rays = 0;
@@ -2204,7 +2237,9 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
     // finishing times together whatever a ray costs where).  Rays traced were the first measure: an eighth of 1080p kept waves
     // resident for 73 % of the launch with it.
     rays += reached + died[1];  // (the wave's rays: every path it took has retired somewhere)
-    const int ticks = (int)min((uint64_t)(__builtin_amdgcn_s_memrealtime() - t_begin) >> 6, (uint64_t)0x3ffff);  // units of 0.64 us; a queue's sum stays below 2^31
+    uint64_t spent = __builtin_amdgcn_s_memrealtime() - t_begin;
+    if constexpr (GATHER) spent -= min(spent, (uint64_t)gather_time);  // (the previous batch's gather is not this queue's paths)
+    const int ticks = (int)min(spent >> 6, (uint64_t)0x3ffff);  // units of 0.64 us; a queue's sum stays below 2^31
     if (qs.deal != nullptr && rays) atomicAdd(&qs.deal[dm.time(q)], ticks), atomicAdd(&qs.deal[dm.rays(q)], rays);
   }
 }
@@ -2250,7 +2285,8 @@ const KernelApi kApi = {
 #endif
     launch_generate, launch_primary, launch_intersect, launch_shade, launch_collect, launch_count_stats,
     launch_preview, launch_save_u8, launch_shade_stage, lds_table_limit, resident_blocks_per_cu, launch_ieee_check, launch_paths,
-    launch_collect_conv, launch_features, kFast ? 1 : 0, launch_intersect_grid, launch_collect_stream};
+    launch_collect_conv, launch_features, kFast ? 1 : 0, launch_intersect_grid, launch_collect_stream, launch_paths_gather,
+    launch_collect_stream_planes};
 
 }  // namespace
 }  // namespace PT_NS

@@ -135,6 +135,7 @@ int resident_blocks_per_cu(KernelId id, const SceneTables& sc) {
     case kPaths:
       for (int form : {0, kSplitRecords, kFirstBounce, kFixedSlots}) with_paths(resolve_scan_nodes(sc), search_form(sc), form, query_share), m = form ? min(m, n) : n;
       n = m;
+      if (search_form(sc) == kLdsTables) query_share(k_paths<kLdsTables, kFixedSlots, PrevGather>, paths_lds<kLdsTables, kFast>(resolve_scan_nodes(sc)).total), n = min(m, n);
       break;
     case kShade: query(k_shade, shade_lds<true>(sc).total); break;
     case kFeatures: with_features(sc, query); break;
@@ -176,6 +177,14 @@ void launch_paths(hipStream_t s, int grid, const SceneTables& sc_in, const Batch
   const SceneTables sc = resolve_scan_nodes(sc_in);
   with_paths(sc, search_form(sc), b.split_records == kFirstBounce && b.fixed_slots ? kFixedSlots : b.split_records, [&](auto kernel, int lds) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, sc, b, qs, cnt, in, ret); });
 }
+// The fixed-slot instance that also gathers the previous batch (k_paths, PREV): the LDS-table form only, the same LDS map
+void launch_paths_gather(hipStream_t s, int grid, const SceneTables& sc_in, const BatchInfo& b, const ptd::Queues& qs, int32_t* cnt, ptd::PathBuf in,
+                         ptd::RetireBuf ret, const PrevGather& prev) {
+  const SceneTables sc = resolve_scan_nodes(sc_in);
+  const auto kernel = k_paths<kLdsTables, kFixedSlots, PrevGather>;
+  const int lds = paths_lds<kLdsTables, kFast>(sc).total;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, sc, b, qs, cnt, in, ret, prev);
+}
 void launch_shade(hipStream_t s, int grid, const SceneTables& sc, const BatchInfo& b, int depth, const ptd::Queues& qs,
                   const int32_t* cnt_in, int32_t* cnt_out, ptd::PathBuf in, ptd::HitBuf hits, ptd::PathBuf out,
                   ptd::RetireBuf ret) {
@@ -197,6 +206,10 @@ void launch_collect_stream(hipStream_t s, const BatchInfo& b, const ptd::Queues&
                            unsigned long long* stats) {
   const int per_queue = (ret.seg_cap + kBlock - 1) / kBlock;
   hipLaunchKernelGGL(k_collect_stream, dim3(qs.Q * per_queue + depth_count + 2), dim3(kBlock), 0, s, b, qs, ret, image_rgb, per_queue, cnt, depth_count, stats);
+}
+void launch_collect_stream_planes(hipStream_t s, const BatchInfo& b, const ptd::Queues& qs, ptd::RetireBuf ret, const ptd::Word4* plane0, float* image_rgb) {
+  const int per_queue = (ret.seg_cap + kBlock - 1) / kBlock;
+  hipLaunchKernelGGL(k_collect_stream_planes, dim3(qs.Q * per_queue), dim3(kBlock), 0, s, b, qs, ret, plane0, image_rgb, per_queue);
 }
 void launch_collect_conv(hipStream_t s, const BatchInfo& b, const ptd::Queues& qs, ptd::RetireBuf ret, float* image_rgb, const ConvInfo& cv, double* sse) {
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_collect_conv), hipFuncAttributeMaxDynamicSharedMemorySize, collect_lds_bytes(ret.wq0));

@@ -348,6 +348,41 @@ __global__ void k_count_stats(ptd::Queues qs, int32_t* __restrict__ cnt, int dep
 // keeps.  The blocks behind the gather's are k_count_stats' (count_stats_row): they touch the counter rows, the deal table and the
 // statistics, the gather the records, sub[], ret.cnt and the image — nothing in common, so the batch saves a launch.
 constexpr int kStreamGroup = 8;
+// What one thread of the stream gather does for slot s of its queue — k_collect_stream's body, and a lane's share of a step of the gather
+// k_paths runs for the batch before its own (pt_kernels.hip, PrevGather).  sh: the queue's share of the tile; K: the iterations of the batch
+// that wrote the records; plane: the record plane that batch's k_paths wrote; front: plane 0, where k_primary leaves the depth-0
+// retirees' records once per camera (the standalone gather of a batch in plane 0 passes the same plane twice).  GROUP: loads in flight.
+template <int GROUP>
+PT_DEV void stream_gather_slot(int N, int K, const QueueShare& sh, const ptd::RetireBuf& ret, const ptd::Word4* plane, const ptd::Word4* front,
+                               float* __restrict__ image, int q, int s) {
+  const Gap gap = region_gap(sh, ret.wq0);
+  if (s >= sh.my_nq * 64 || (s >= gap.g0 && s < gap.g1)) return;
+  const SubSlot ss = sub_slot(sh.my_nq / ret.wq0, sh.my_nq % ret.wq0, s);
+  const int retirees = (int)(ret.sub[(int64_t)q * ret.kmax * ret.wq0 + ss.rho] >> 32);
+  const bool once = retiree_slot(ss, retirees);
+  const ptd::Word4* rec = (once ? front : plane) + (int64_t)q * ret.kmax * ret.seg_cap + s;  // the slot in region (q, 0); region (q, k): + k * seg_cap
+  const ptd::Word4 r0 = rec[0];
+  const int pl = __float_as_int(r0.w);
+  if (pl < 0 || pl >= N) return;  // (no record names a pixel outside the tile; a slot nobody wrote must not send a store there)
+  float* px = image + 3 * (int64_t)pl;
+  float a0 = px[0], a1 = px[1], a2 = px[2];
+  if (once) {
+    for (int k = 0; k < K; ++k) a0 += r0.x, a1 += r0.y, a2 += r0.z;
+  } else {
+    a0 += r0.x, a1 += r0.y, a2 += r0.z;
+    for (int k0 = 1; k0 < K; k0 += GROUP) {  // (K is uniform: the loads of a group are issued back to back, the last group's clamped)
+      ptd::Word4 v[GROUP];
+#pragma unroll
+      for (int u = 0; u < GROUP; ++u) v[u] = rec[(int64_t)min(k0 + u, K - 1) * ret.seg_cap];
+#pragma unroll
+      for (int u = 0; u < GROUP; ++u) {
+        const bool have = k0 + u < K;
+        a0 = have ? a0 + v[u].x : a0, a1 = have ? a1 + v[u].y : a1, a2 = have ? a2 + v[u].z : a2;
+      }
+    }
+  }
+  px[0] = a0, px[1] = a1, px[2] = a2;
+}
 __global__ __launch_bounds__(kBlock) void k_collect_stream(BatchInfo b, ptd::Queues qs, ptd::RetireBuf ret, float* __restrict__ image, int per_queue,
                                                            int32_t* __restrict__ cnt, int depth_count, unsigned long long* __restrict__ stats) {
   const int gather_blocks = qs.Q * per_queue;
@@ -360,33 +395,17 @@ __global__ __launch_bounds__(kBlock) void k_collect_stream(BatchInfo b, ptd::Que
   // the records are consumed: zero counters for the next batch
   if (blk == 0)
     for (int i = threadIdx.x; i < ret.kmax; i += kBlock) ret.cnt[(int64_t)q * ret.kmax + i] = 0ull;
-  const QueueShare sh = queue_share(b, qs, q);
-  const Gap gap = region_gap(sh, ret.wq0);
-  if (s >= sh.my_nq * 64 || (s >= gap.g0 && s < gap.g1)) return;
-  const SubSlot ss = sub_slot(sh.my_nq / ret.wq0, sh.my_nq % ret.wq0, s);
-  const int retirees = (int)(ret.sub[(int64_t)q * ret.kmax * ret.wq0 + ss.rho] >> 32);
-  const ptd::Word4* rec = ret.rec + (int64_t)q * ret.kmax * ret.seg_cap + s;  // the slot in region (q, 0); region (q, k): + k * seg_cap
-  const ptd::Word4 r0 = rec[0];
-  const int pl = __float_as_int(r0.w);
-  if (pl < 0 || pl >= b.N) return;  // (no record names a pixel outside the tile; a slot nobody wrote must not send a store there)
-  float* px = image + 3 * (int64_t)pl;
-  float a0 = px[0], a1 = px[1], a2 = px[2];
-  if (retiree_slot(ss, retirees)) {
-    for (int k = 0; k < b.K; ++k) a0 += r0.x, a1 += r0.y, a2 += r0.z;
-  } else {
-    a0 += r0.x, a1 += r0.y, a2 += r0.z;
-    for (int k0 = 1; k0 < b.K; k0 += kStreamGroup) {  // (K is uniform: the loads of a group are issued back to back, the last group's clamped)
-      ptd::Word4 v[kStreamGroup];
-#pragma unroll
-      for (int u = 0; u < kStreamGroup; ++u) v[u] = rec[(int64_t)min(k0 + u, b.K - 1) * ret.seg_cap];
-#pragma unroll
-      for (int u = 0; u < kStreamGroup; ++u) {
-        const bool have = k0 + u < b.K;
-        a0 = have ? a0 + v[u].x : a0, a1 = have ? a1 + v[u].y : a1, a2 = have ? a2 + v[u].z : a2;
-      }
-    }
-  }
-  px[0] = a0, px[1] = a1, px[2] = a2;
+  stream_gather_slot<kStreamGroup>(b.N, b.K, queue_share(b, qs, q), ret, ret.rec, ret.rec, image, q, s);
+}
+// The same gather for a batch whose k_paths wrote the second record plane (ret.rec; plane0: where the depth-0 retirees' records lie), without
+// the counter rows' blocks: the last batch of a render call when it ends up in that plane, and a batch whose successor could not take it.
+__global__ __launch_bounds__(kBlock) void k_collect_stream_planes(BatchInfo b, ptd::Queues qs, ptd::RetireBuf ret, const ptd::Word4* __restrict__ plane0,
+                                                                  float* __restrict__ image, int per_queue) {
+  const int q = (int)blockIdx.x / per_queue, blk = (int)blockIdx.x - q * per_queue;
+  const int s = blk * kBlock + (int)threadIdx.x;
+  if (blk == 0)
+    for (int i = threadIdx.x; i < ret.kmax; i += kBlock) ret.cnt[(int64_t)q * ret.kmax + i] = 0ull;
+  stream_gather_slot<kStreamGroup>(b.N, b.K, queue_share(b, qs, q), ret, ret.rec, plane0, image, q, s);
 }
 
 __global__ __launch_bounds__(kBlock) void k_preview(int n, int iterations, const float* __restrict__ image,

@@ -334,6 +334,27 @@ PT_SCHED bool primary_once(const BatchInfo& b, int debug_flags, int search_form,
 // and every batch with the convergence metric, whose partial sums keep their partition), 2 the stream.
 constexpr int kGatherTile = 0, kGatherTileFixed = 1, kGatherStream = 2;
 PT_SCHED int gather_form(bool fixed, int debug_flags, bool convergence) { return !fixed ? kGatherTile : (debug_flags & kTileGather) || convergence ? kGatherTileFixed : kGatherStream; }
+// The stream gather of a batch inside the NEXT batch's k_paths (PtStats.gather_form 3 while such a batch waits; the last batch of a render
+// call is always gathered by k_collect_stream, so a finished call reports 2 and PtStats.inline_gathers counts the others).  k_paths is bound
+// by instruction issue and leaves most of the memory system idle, the gather is memory traffic alone, and as separate launches they run
+// one after the other: the waves of batch n + 1 therefore add batch n's records to the image in small steps beside their own work
+// (pt_kernels.hip k_paths, PREV).  Batch n + 1 stores its records in the other of two record planes; what k_primary writes once per
+// camera — the depth-0 retirees' records, sub[] — stays in plane 0 and is only read.  It applies when both batches belong to one render
+// call, both are stream-gathered batches of a context with depth 0 once per camera, the second launches no k_primary (same camera, tile or
+// list, queues and plan: run_batch's PrimaryKey) and the second plane exists and may be used (second_plane: not in a context with the
+// convergence metric, whose batches change form in mid-call).  Noise folds, read-backs and camera moves happen between render calls,
+// where nothing waits.  PtOptions.debug_flags kGatherEveryBatch:
+// every batch by k_collect_stream, as an A/B switch.
+constexpr int kGatherInline = 3;
+constexpr int kGatherEveryBatch = 131072;
+// May the gather of a batch wait for the next batch's k_paths?  (more: another batch of the same render call follows)
+PT_SCHED bool defers_gather(bool more, int form, bool primary_once, bool second_plane, int debug_flags) {
+  return more && form == kGatherStream && primary_once && second_plane && !(debug_flags & kGatherEveryBatch);
+}
+// Does this batch's k_paths gather the waiting one?  (same_key: this batch launches no k_primary — everything that launch depends on is unchanged)
+PT_SCHED bool inline_gather(bool waiting, int form, bool primary_once, bool same_key, bool second_plane, int debug_flags) {
+  return waiting && form == kGatherStream && primary_once && same_key && second_plane && !(debug_flags & kGatherEveryBatch);
+}
 
 // ── k_paths: falling pieces ───────────────────────────────────────────────────────────────────────────────────────────────
 // BatchInfo::paths_pieces: pieces per wave | fewest paths in a piece << 16.

@@ -122,7 +122,10 @@ typedef struct PtOptions {
                                the primary kernel runs in every batch (default in a batch of the 8192 form with the fixed slots
                                of 16384: its output there depends on neither the iteration nor the batch's length, so it runs
                                in the first batch after pt_init or pt_set_camera and later batches read what it left;
-                               PtStats.primary_launches tells), 2048
+                               PtStats.primary_launches tells), 131072 every batch is gathered by a launch of its own (default for
+                               the batches of the 16384 form's stream gather that another batch of the same pt_render call follows
+                               with the same camera, tile and plan: the next batch's bounce kernel adds their records to the image
+                               beside its own work, from the other of two record planes; PtStats.inline_gathers counts), 2048
                                keep the reference's leaf boxes for spheres (default for large scenes: tightened to the
                                ellipsoid's box, PtStats.tight_leaves; pt_stage_intersect on such a scene then expects ray
                                origins inside the scene bounds or at the camera).  pt_init fails on any other bit. */
@@ -207,10 +210,14 @@ typedef struct PtStats {
                                          and batch, the first bounce sampled in the bounce kernel (debug_flags 8192 turns it off) */
   int32_t gather_form;                /* how the last batch was gathered: 0 through a tile, from records in order of retirement
                                          (debug_flags 16384 asks for it), 1 through a tile, from fixed record slots (debug_flags
-                                         32768, and every batch that computes the convergence metric), 2 as a stream over fixed slots */
+                                         32768, and every batch that computes the convergence metric), 2 as a stream over fixed slots,
+                                         3 as that stream inside the next batch's bounce kernel (only while a pt_render call is
+                                         being submitted: the last batch of every call is gathered by a launch of its own) */
   int64_t primary_launches;           /* launches of the fused primary kernel by pt_render since pt_init (pt_reset_stats and pt_clear
                                          leave it): with record_form 2 one per camera — the first batch after pt_init or
                                          pt_set_camera — instead of one per batch (debug_flags 65536 asks for every batch) */
+  int64_t inline_gathers;             /* batches gathered inside the next batch's bounce kernel since pt_init (debug_flags 131072: none);
+                                         the second record plane this needs counts in device_bytes */
 } PtStats;
 
 /* ---- scene loading (host).  Replaces `new Scene(file)` (src/main.cpp:45,
