@@ -14,9 +14,9 @@
 // never needed.
 //
 // What of src/pathtrace.cu is pinned where: its plain-C++ functions (buildBVH / computeBounds, intersectAABB, the sampling
-// helpers) are compiled from the file's own text by ref_pt_harness.cpp; its __global__ bodies (computeIntersections' stack
-// walk, shadeAndExtendRays, finalGather) and main.cpp's camera fix-up compile with neither g++ nor clang's CUDA mode without
-// stand-ins for the CUDA toolchain and stay pinned by restatement + SURVEY §4 KATs.  The one formula of pathtrace.cu this
+// helpers) are compiled from the file's own text by ref_pt_harness.cpp; its __global__ bodies (generateRayFromCamera,
+// computeIntersections, shadeAndExtendRays, finalGather) and main.cpp's camera fix-up by ref_kernels_harness.cpp, which holds
+// the stand-ins for the CUDA toolchain they need (the seed expression included, there as the file's text).  The one formula of pathtrace.cu this
 // harness restates is the seed expression of makeSeededRandomEngine (pathtrace.cu:205) — around the reference's own
 // utilhash — to produce the seed list that ref_rng_harness.cpp feeds to rocThrust's minstd_rand.
 //

@@ -12,9 +12,10 @@
 // does for intersections.h in ref_hot_harness.cpp.  Nothing of the reference is copied into the repository; the fixtures
 // hold numbers only.
 //
-// What still rests on SURVEY §4's KATs after this: the __global__ bodies (computeIntersections' stack walk and dispatch,
-// shadeAndExtendRays' branch structure and draw order, finalGather) and main.cpp's camera fix-up — neither compiles
-// without stand-ins for the CUDA toolchain.
+// The __global__ bodies (generateRayFromCamera, computeIntersections, shadeAndExtendRays, finalGather) and main.cpp's camera
+// fix-up need stand-ins for the CUDA toolchain to compile; ref_kernels_harness.cpp holds those and pins them the same way.
+// What still rests on SURVEY §4's KATs after both: the launch order of pathtrace()'s host loop, restated in that harness, and
+// the mouse callbacks' double-precision increments, which pt_scene_orbit replaces by a float rule of its own.
 //
 // Modes:
 //   ref_pt bvh     OUT.bin SCENE.txt...          per scene: the node table buildBVH returns (bounds, left, right, geomIndex)
