@@ -26,7 +26,7 @@
 namespace {
 
 std::string g_err;
-constexpr int kDebugFlags = 16 | 32 | 64 | 128 | 256 | 512 | ptk::kRetireEveryIteration | 2048 | ptk::kWholeRecords | ptk::kNoFirstBounce | ptk::kRecordsByVisit | ptk::kTileGather | ptk::kPrimaryEveryBatch | ptk::kGatherEveryBatch;  // the PtOptions.debug_flags bits pt_init accepts
+constexpr int kDebugFlags = 16 | 32 | 64 | 256 | 512 | 2048 | ptk::kFormSwitches;  // the PtOptions.debug_flags bits pt_init accepts
 static_assert(sizeof(PtOptions) == 80, "capi.PtOptions mirrors this layout");
 static_assert(PT_CONVERGENCE_WAVES == ptk::kConvWaves, "pt_amd.h documents the size of the convergence metric's partial sums");
 }  // namespace
@@ -110,11 +110,10 @@ static ptd::Queues queues_for(const Ctx& g, int grid) {
   return q;
 }
 
-// BatchInfo::primary_share of the context's batches: debug_flags 128 and a primary_share of 1 both mean a trace per iteration;
-// automatic: the longest run, a whole piece per trace (on the whole frame caps of 8 to 64 iterations measure alike, 4 is 0.5 %
-// slower: profiles/first_hit_sharing.log section 2b).
-static int primary_share_of(const Ctx& g) { return (g.debug_flags & 128) ? 1 : g.primary_share ? g.primary_share : ptk::kShareMax; }
-static bool shares_first_hit(const Ctx& g) { return ptk::primary_shares(primary_share_of(g), g.aa_jitter, !g.fuse_bounces); }
+// BatchInfo::primary_share of the context's batches: debug_flags kTraceEveryIteration and a primary_share of 1 both mean a trace per
+// iteration; automatic: the longest run, a whole piece per trace (on the whole frame caps of 8 to 64 iterations measure alike, 4 is
+// 0.5 % slower: profiles/first_hit_sharing.log section 2b).
+static int primary_share_of(const Ctx& g) { return (g.debug_flags & ptk::kTraceEveryIteration) ? 1 : g.primary_share ? g.primary_share : ptk::kShareMax; }
 
 ptk::BatchInfo tile_batch(const Ctx& g, int iter_first, int K) {
   ptk::BatchInfo b{};
@@ -129,8 +128,14 @@ ptk::BatchInfo tile_batch(const Ctx& g, int iter_first, int K) {
   b.inv_stripe = g.stripe ? 1.0f / (float)g.stripe : 0.0f;
   return b;
 }
+// ... and the fields pt_sched.h batch_form reads besides, in every batch of the context (the unfused kernels' batches are flat: whole records)
+static ptk::BatchInfo form_batch(const Ctx& g, int iter_first, int K) {
+  ptk::BatchInfo b = tile_batch(g, iter_first, K);
+  b.slot_shift = g.slot_shift, b.flat = g.fuse_bounces ? 0 : 1, b.primary_share = primary_share_of(g);
+  return b;
+}
 
-// The stream gather of the batch that waits (pt_sched.h inline_gather) as a launch of its own: its successor could not take it.
+// The stream gather of the batch that waits (pt_sched.h gather_plan) as a launch of its own: its successor could not take it.
 static void gather_waiting(Ctx& g) {
   if (!g.waiting.live) return;
   ptd::RetireBuf ret = g.ret;
@@ -140,70 +145,52 @@ static void gather_waiting(Ctx& g) {
 }
 
 int run_batch(Ctx& g, int iter_first, int kb, int after) {
-  ptk::BatchInfo b = tile_batch(g, iter_first, kb);
-  b.slot_shift = g.slot_shift;
-  b.flat = g.fuse_bounces ? 0 : 1;
-  b.primary_share = primary_share_of(g);
-  b.primary_pieces = g.primary_pieces ? g.primary_pieces
-                     : ptk::primary_shares(b) ? ptk::auto_shared_pieces(kb, g.qs.nq, g.ret.wq0) : ptk::auto_primary_pieces(kb, g.qs.nq, g.ret.wq0);
-  b.paths_pieces = g.paths_pieces;
-  const ptk::SceneTables sc = tables(g);
-  b.retire_once = ptk::retires_once(b, g.debug_flags) ? 1 : 0;  // (every batch of the context, the timing batches of choose_traversal among them)
-  b.split_records = ptk::record_form(b, g.debug_flags, ptk::search_form(sc), sc.num_mats);  // (likewise; the unfused kernels' batches are flat: whole records)
-  if (b.split_records == ptk::kFirstBounce) b.primary_pieces = 1;  // one trace per chunk and batch: primary_pieces / primary_share cut nothing
-  g.record_form = b.split_records;
-  b.fixed_slots = ptk::fixed_slots(b, g.debug_flags, ptk::search_form(sc), sc.num_mats, g.ret.seg_cap) ? 1 : 0;
-  b.list = g.list;
+  // 1. the batch
+  ptk::BatchInfo b = form_batch(g, iter_first, kb);
+  b.paths_pieces = g.paths_pieces, b.list = g.list;
   if (b.list) b.stripe = 1, b.gap = 0, b.inv_stripe = 1.0f;  // (BatchInfo::list: the list form sits behind the stripe test)
+  const ptk::SceneTables sc = tables(g);
+  // 2. its form (pt_sched.h batch_form), decided once, handed to the kernels here
+  const ptk::BatchForm form = ptk::batch_form(ptk::form_inputs(b, g.debug_flags, ptk::search_form(sc), sc.num_mats, g.ret.seg_cap));
+  b.retire_once = form.retire_once, b.split_records = g.record_form = form.records, b.fixed_slots = form.fixed_slots;
+  b.primary_pieces = form.shares ? ptk::auto_shared_pieces(kb, g.qs.nq, g.ret.wq0) : ptk::auto_primary_pieces(kb, g.qs.nq, g.ret.wq0);
+  if (g.primary_pieces) b.primary_pieces = g.primary_pieces;
+  if (form.records == ptk::kFirstBounce) b.primary_pieces = 1;  // one trace per chunk and batch: primary_pieces / primary_share cut nothing
   const ptk::KernelApi& k = *g.k;
   auto cnt_row = [&](int d) { return g.d_cnt + ptk::cnt_index(g.qs, d, 0); };  // the counter row of depth d
-  int d0 = 0;
-  // Depth 0 once per camera (pt_sched.h primary_once): whether the first-hit records of an earlier batch serve this one.  Until this
-  // batch is submitted whole they serve nobody (a batch of another form overwrites them, a failed one leaves them undefined).
-  const bool once = g.fuse_primary && ptk::primary_once(b, g.debug_flags, ptk::search_form(sc), sc.num_mats, g.ret.seg_cap);
-  const bool had_first_hits = g.primary_valid;
+  // 3. depth 0 once per camera (BatchForm::primary_once; never without k_primary: flat): do an earlier batch's first-hit records serve this
+  // one?  Until this batch is submitted whole they serve nobody (a batch of another form overwrites them, a failed one leaves them undefined).
+  const ptd::Queues pq = queues_for(g, g.grid_primary);
+  Ctx::PrimaryKey key;
+  std::memset(&key, 0, sizeof(key));
+  key.sc = sc, key.cam = g.dcam, key.b = b, key.b.iter_first = key.b.K = 0, key.qs = pq, key.out = g.buf[1], key.ret = g.ret;
+  key.kernels = &k, key.grid = g.grid_primary, key.debug_flags = g.debug_flags;
+  const bool same_key = form.primary_once && g.primary_valid && std::memcmp(&key, &g.primary_key, sizeof(key)) == 0;
   g.primary_valid = false;
-  // The gather: a batch with fixed record slots streams them; the metric's batches (its partial sums have a fixed partition) and every
-  // other batch keep the tile gather behind k_count_stats.
+  // 4. the gather (pt_sched.h gather_plan)
   ptk::ConvInfo cv{g.d_ref, g.d_partial, -1, kb};
   if (g.conv_live) {
     if (g.conv_have_ref) cv.first_k = 0;
     else if (g.conv >= iter_first && g.conv < iter_first + kb) cv.capture_k = g.conv - iter_first, cv.first_k = cv.capture_k + 1, g.conv_have_ref = true;
     g.conv_last = std::max(g.conv_last, iter_first + kb - 1);
   }
-  const bool conv_batch = cv.capture_k >= 0 || cv.first_k < kb;
-  const int form = ptk::gather_form(b.fixed_slots != 0, g.debug_flags, conv_batch);
-  bool gathers_waiting = false;  // this batch's k_paths gathers the batch before it
-  if (g.fuse_primary) {
-    // depth 0 in one launch; its survivors are the depth-1 input (buf[1], cnt[1])
-    const ptd::Queues pq = queues_for(g, g.grid_primary);
-    Ctx::PrimaryKey key;
-    std::memset(&key, 0, sizeof(key));
-    key.sc = sc, key.cam = g.dcam, key.b = b, key.b.iter_first = key.b.K = 0, key.qs = pq, key.out = g.buf[1], key.ret = g.ret;
-    key.kernels = &k, key.grid = g.grid_primary, key.debug_flags = g.debug_flags;
-    const bool same_key = once && had_first_hits && std::memcmp(&key, &g.primary_key, sizeof(key)) == 0;
-    gathers_waiting = ptk::inline_gather(g.waiting.live, form, once, same_key, g.rec_plane1 != nullptr && !g.conv, g.debug_flags) && g.grid_paths > 0;
-    if (!gathers_waiting) gather_waiting(g);  // before k_primary rewrites what that gather reads
-    if (!same_key) {
-      k.primary(g.stream, g.grid_primary, sc, g.dcam, b, pq, cnt_row(0), cnt_row(1), g.buf[1], g.ret);
-      g.primary_launches += 1;
-      std::memcpy(&g.primary_key, &key, sizeof(key));
-    }
-    d0 = 1;
-  } else {
-    gather_waiting(g);
-    k.generate(g.stream, g.grid_gen, g.dcam, b, queues_for(g, g.grid_gen), g.buf[0], cnt_row(0));
-  }
-  // A batch whose gather waits for its successor stores its records in plane `after` mod 2, so that the planes alternate along the call
-  // and its last batch — gathered by k_collect_stream, like the only batch of a call — lies in plane 0; k_paths of a batch that gathers
-  // its predecessor takes the plane that one did not use (the same thing, unless the chain began in mid-call).
-  const bool defers = ptk::defers_gather(after > 0, form, once, g.rec_plane1 != nullptr && !g.conv, g.debug_flags) && g.grid_paths > 0;
-  const int plane = gathers_waiting ? 1 - g.waiting.plane : defers ? after & 1 : 0;
+  const bool all_depths = g.grid_paths > 0;  // depths >= 1 fused
+  const ptk::GatherPlan plan = ptk::gather_plan({form, cv.capture_k >= 0 || cv.first_k < kb, g.waiting.live, g.waiting.plane, same_key,
+                                                 g.rec_plane1 != nullptr && !g.conv, after, g.debug_flags, all_depths});
   ptd::RetireBuf ret = g.ret;
-  if (plane) ret.rec = g.rec_plane1;
-  int src = d0 & 1;
+  if (plan.plane) ret.rec = g.rec_plane1;
+  // 5. the launches
+  if (!plan.gathers_waiting) gather_waiting(g);  // before k_primary rewrites what that gather reads
+  if (!g.fuse_primary) k.generate(g.stream, g.grid_gen, g.dcam, b, queues_for(g, g.grid_gen), g.buf[0], cnt_row(0));
+  else if (!same_key) {
+    // depth 0 in one launch; its survivors are the depth-1 input (buf[1], cnt[1])
+    k.primary(g.stream, g.grid_primary, sc, g.dcam, b, pq, cnt_row(0), cnt_row(1), g.buf[1], g.ret);
+    g.primary_launches += 1;
+    std::memcpy(&g.primary_key, &key, sizeof(key));
+  }
+  const int d0 = g.fuse_primary ? 1 : 0;
+  int src = d0;
   // Depths >= 1, fused: ONE launch of k_paths — persistent lanes with their own depth, no path state through HBM after depth 0
-  const bool all_depths = g.grid_paths > 0;
   EventPair ev{};  // brackets the dominant kernel of a depth (fused: of all depths) when the context times its kernels
   auto timed_from = [&]() -> int {
     if (!g.time_kernels) return 0;
@@ -219,7 +206,7 @@ int run_batch(Ctx& g, int iter_first, int kb, int after) {
   };
   if (all_depths) {
     if (timed_from()) return -1;
-    if (gathers_waiting) {
+    if (plan.gathers_waiting) {
       const ptk::PrevGather prev{g.waiting.plane ? g.rec_plane1 : g.ret.rec, g.ret.rec, g.d_image, g.waiting.b.K, 0};
       k.paths_gather(g.stream, g.grid_paths, sc, b, queues_for(g, g.grid_paths), g.d_cnt, g.buf[1], ret, prev);
       g.waiting.live = false;
@@ -237,25 +224,16 @@ int run_batch(Ctx& g, int iter_first, int kb, int after) {
     k.shade(g.stream, g.grid_shade, sc, b, d, queues_for(g, g.grid_shade), cin, cout, g.buf[src], g.hits, g.buf[src ^ 1], g.ret);
     src ^= 1;
   }
-  // A stream-gathered batch with a successor in its render call leaves its gather to that batch's k_paths (pt_sched.h defers_gather):
-  // only the counter rows are folded now.  Otherwise the stream gather runs here, the counter rows' blocks in the same launch when the
-  // records lie in plane 0.
-  g.gather_form = form;
-  if (defers) {
-    k.count_stats(g.stream, g.qs, g.d_cnt, g.depth, g.d_stats);
-    g.waiting.live = true, g.waiting.b = b, g.waiting.plane = plane;
-    g.gather_form = ptk::kGatherInline;
-  } else if (form == ptk::kGatherStream && plane == 0) k.collect_stream(g.stream, b, g.qs, g.ret, g.d_image, g.d_cnt, g.depth, g.d_stats);
-  else if (form == ptk::kGatherStream) {
-    k.count_stats(g.stream, g.qs, g.d_cnt, g.depth, g.d_stats);
-    k.collect_stream_planes(g.stream, b, g.qs, ret, g.ret.rec, g.d_image);
-  } else {
-    k.count_stats(g.stream, g.qs, g.d_cnt, g.depth, g.d_stats);
-    if (conv_batch) k.collect_conv(g.stream, b, g.qs, g.ret, g.d_image, cv, g.d_sse);
-    else k.collect(g.stream, b, g.qs, g.ret, g.d_image);
-  }
+  // The closing launch (pt_sched.h Closing).  A batch whose gather waits for its successor's k_paths folds only the counter rows now.
+  g.gather_form = plan.reported;
+  if (plan.closing == ptk::kCloseStream) k.collect_stream(g.stream, b, g.qs, g.ret, g.d_image, g.d_cnt, g.depth, g.d_stats);
+  else k.count_stats(g.stream, g.qs, g.d_cnt, g.depth, g.d_stats);
+  if (plan.closing == ptk::kCloseStatsStreamPlanes) k.collect_stream_planes(g.stream, b, g.qs, ret, g.ret.rec, g.d_image);
+  if (plan.closing == ptk::kCloseStatsConv) k.collect_conv(g.stream, b, g.qs, g.ret, g.d_image, cv, g.d_sse);
+  if (plan.closing == ptk::kCloseStatsTile) k.collect(g.stream, b, g.qs, g.ret, g.d_image);
+  if (plan.defers) g.waiting.live = true, g.waiting.b = b, g.waiting.plane = plan.plane;
   HIP_OK(hipGetLastError());
-  g.primary_valid = once;
+  g.primary_valid = form.primary_once;
   g.samples += (int64_t)kb * g.N;
   if (g.pending_isect.size() > 16384) {
     HIP_OK(hipStreamSynchronize(g.stream));
@@ -271,11 +249,11 @@ void plan_launch(Ctx& g) {
   g.grid_gen = g.num_cus * std::min(g.cap_bpc, g.k->resident_blocks_per_cu(ptk::kGenerate, t));
   g.grid_isect = g.num_cus * std::min(g.cap_bpc, g.k->resident_blocks_per_cu(g.legacy ? ptk::kIntersectLegacy : ptk::kIntersect, t));
   g.grid_shade = g.num_cus * std::min(g.cap_bpc, g.k->resident_blocks_per_cu(ptk::kShade, t));
-  g.grid_primary = g.num_cus * std::min(g.cap_bpc, g.k->resident_blocks_per_cu(shares_first_hit(g) ? ptk::kPrimaryShared : ptk::kPrimary, t));
+  g.grid_primary = g.num_cus * std::min(g.cap_bpc, g.k->resident_blocks_per_cu(ptk::primary_shares(form_batch(g, 0, g.K)) ? ptk::kPrimaryShared : ptk::kPrimary, t));
   g.ret.wq0 = ptk::wave_slot(0, g.qs.Q, g.grid_primary * ptk::kWavesPerBlock).wq;  // the sub-lists' residue count (pt_device.h RetireBuf)
   g.grid_paths = (g.fuse_bounces && g.depth > 1) ? g.num_cus * std::min(g.cap_bpc, g.k->resident_blocks_per_cu(ptk::kPaths, t)) : 0;
   g.qs.paths_W = g.grid_paths * ptk::kWavesPerBlock;  // what k_count_stats deals to the queues (a table made for another width is ignored)
-  g.primary_valid = false;  // (the first-hit records of another plan: pt_sched.h primary_once)
+  g.primary_valid = false;  // (the first-hit records of another plan: pt_sched.h BatchForm::primary_once)
 }
 
 // A grid's device memory back to the device (choose_traversal's losers, a camera move that changes a grid's size).
@@ -548,7 +526,7 @@ static size_t sub_words_max(const Ctx& g) { return ptk::sub_stride(g.num_cus * 8
 // (pt_ctx_set_camera): path buffers all ones, records poisoned, fill levels and the deal of the waves zero.  A slot wrongly gathered
 // from the previous view then shows as NaN, not as a plausible pixel.
 static int rearm_batch_buffers(Ctx& g) {
-  g.primary_valid = false;  // the first-hit records go with the buffers (pt_sched.h primary_once)
+  g.primary_valid = false;  // the first-hit records go with the buffers (pt_sched.h batch_form)
   for (const ptd::PathBuf& pb : g.buf) HIP_OK(hipMemsetAsync(pb.r, 0xff, pathbuf_words(pb.stride) * sizeof(ptd::Word4), g.stream));
   const size_t regions = (size_t)g.qs.Q * g.ret.kmax;
   HIP_OK(hipMemsetAsync(g.ret.cnt, 0, regions * sizeof(*g.ret.cnt), g.stream));
@@ -570,14 +548,12 @@ int alloc_batch_buffers(Ctx& g) {
     const size_t regions = (size_t)Q * g.ret.kmax;
     const size_t wq_max = sub_words_max(g);
     if (dalloc(g, &g.ret.rec, regions * g.ret.seg_cap)) return -1;
-    // The second record plane (pt_sched.h inline_gather), where a context's batches can be of that form at all: several batches per render
-    // call need K > 1 iterations per batch to be worth a plane, the form needs the fused kernels and no switch against it.  Whether a
-    // batch has fixed slots is decided per batch (run_batch).  A failed allocation leaves the context on the standalone gather.
+    // The second record plane (pt_sched.h gather_plan), where a context's batches can be of that form at all: the fused kernels and no
+    // switch against it (kNoSecondPlane); whether a batch has fixed slots is decided per batch.  A failed allocation leaves the context on
+    // the standalone gather.  (A context with the convergence metric gets the plane too — PtStats.device_bytes differs by the metric's own
+    // buffers, as documented — and never uses it; a worker's batches are single launches of run_batch: none.)
     g.rec_plane1 = nullptr;
-    // (A context with the convergence metric gets the plane too — PtStats.device_bytes differs by the metric's own buffers, as
-    // documented — and never uses it; a worker's batches are single launches of run_batch: none.)
-    if (g.fuse_primary && g.fuse_bounces && g.depth > 1 && !g.aa_jitter && !g.borrowed &&
-        !(g.debug_flags & (ptk::kGatherEveryBatch | ptk::kTileGather | ptk::kRecordsByVisit | ptk::kNoFirstBounce | ptk::kPrimaryEveryBatch))) {
+    if (g.fuse_primary && g.fuse_bounces && g.depth > 1 && !g.aa_jitter && !g.borrowed && !(g.debug_flags & ptk::kNoSecondPlane)) {
       void* p = nullptr;
       const size_t bytes = regions * g.ret.seg_cap * sizeof(ptd::Word4);
       if (hipMalloc(&p, bytes) == hipSuccess) {

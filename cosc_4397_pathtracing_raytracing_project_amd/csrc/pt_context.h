@@ -67,7 +67,7 @@ struct PtShared {
   bool legacy = false;
   int debug_flags = 0;
   int record_form = 0;  // BatchInfo::split_records of the last batch (PtStats.record_form)
-  int gather_form = 0;  // pt_sched.h gather_form of the last batch (PtStats.gather_form)
+  int gather_form = 0;  // pt_sched.h GatherPlan::reported of the last batch (PtStats.gather_form)
   bool fuse_primary = true, fuse_bounces = true;
   bool aa_jitter = false;
 };
@@ -92,7 +92,7 @@ struct PtContext : PtShared {
   ptd::PathBuf buf[2]{};
   ptd::HitBuf hits{};
   ptd::RetireBuf ret{};  // retirement records + fill levels (pt_device.h)
-  // The second record plane and the batch whose stream gather waits for the next batch's k_paths (pt_sched.h inline_gather).  Set and
+  // The second record plane and the batch whose stream gather waits for the next batch's k_paths (pt_sched.h gather_plan).  Set and
   // consumed inside one pt_ctx_render call: nothing waits when a call returns.
   ptd::Word4* rec_plane1 = nullptr;  // as large as ret.rec (plane 0); absent where the form cannot apply or the allocation failed
   struct WaitingGather {
@@ -128,7 +128,7 @@ struct PtContext : PtShared {
   double isect_ms = 0, render_ms = 0;
   int64_t isect_launches = 0;
   int64_t samples = 0;
-  // Depth 0 once per camera (pt_sched.h primary_once): what the first-hit records now in buf[1], ret.rec and ret.sub were traced for —
+  // Depth 0 once per camera (pt_sched.h batch_form): what the first-hit records now in buf[1], ret.rec and ret.sub were traced for —
   // every argument of the k_primary launch that wrote them but the batch's first iteration and its length, which that output does not
   // depend on.  run_batch launches k_primary again unless the next batch's arguments are these, bit for bit; what changes behind
   // the pointers they hold (the tables of a moved camera, a worker's pixel list, buffers armed again) clears primary_valid itself.

@@ -83,7 +83,7 @@ struct Camera {
 // 40 B per path, the algorithmic minimum of SURVEY §8(d) (+ 0: the id replaces the reference's pixelIndex).
 // A batch that splits its records (BatchInfo::split_records, pt_sched.h) keeps (direction.xyz, sample id | specular bit << 31) in plane 0 and,
 // at the path's slot of ITERATION 0, (origin.xyz, material index) in plane 1, written once per batch; plane 2 is not touched.
-// A batch that leaves the first bounce to k_paths (split_records 2, pt_sched.h first_bounces) keeps ONE whole record per surviving pixel, at
+// A batch that leaves the first bounce to k_paths (split_records 2, pt_sched.h batch_form) keeps ONE whole record per surviving pixel, at
 // that slot of iteration 0, in the three planes as they are: bounce origin for the origin, the hit normal for the direction, the camera
 // direction for the colour, tile pixel | material index << slot_shift for the sample id.
 struct alignas(16) Word4 {

@@ -83,18 +83,18 @@ struct BatchInfo {
                            // at most this many iterations (and 64) and shaded in each of them; <= 1: traced in every iteration
   int32_t paths_pieces;    // k_paths: low 16 bits: a queue's depth-1 rays cut into this many pieces per wave, one its own, the others first
                            // come, first served (counters behind ptd::Queues::deal); <= 1: one piece per wave; high 16 bits: fewest paths in a piece
-  int32_t retire_once;     // 1 (the host sets it from pt_sched.h retires_once): a sample that retires at depth 0 does so in every iteration, with the
+  int32_t retire_once;     // 1 (the host sets it from pt_sched.h batch_form): a sample that retires at depth 0 does so in every iteration, with the
                            // same colour — k_primary stores its record in iteration 0 of the batch only, k_collect gathers it there only
   // Pixel list (adaptive sampling, pt_adaptive.hip): not nullptr, with stripe != 0 (any value: the list is looked at behind the
   // stripe test, so that contiguous tiles run the code they always ran): tile pixel p is global pixel pixel_begin + list[p] —
   // N entries, distinct, in any order.  Queues, slots, records and the gather work on tile pixels and never look at it.
   const int32_t* list;
-  int32_t split_records;   // 1 (the host sets it from pt_sched.h splits_records): a depth-1 record's origin and material index are stored once per
+  int32_t split_records;   // 1 (the host sets it from pt_sched.h batch_form): a depth-1 record's origin and material index are stored once per
                            // batch, in plane 1 at the slot of iteration 0; plane 0 holds direction, sample id and the specular / diffuse bit
-                           // 2 (pt_sched.h first_bounces, LDS-table search form only): one whole record per surviving pixel and batch at the slot
+                           // 2 (pt_sched.h batch_form, LDS-table search form only): one whole record per surviving pixel and batch at the slot
                            // of iteration 0 — bounce origin, hit normal, camera direction, tile pixel | material — and k_paths decides depth 0
                            // and samples the first bounce of every iteration's path itself; k_primary runs no iteration loop
-  int32_t fixed_slots;     // 1 (the host sets it from pt_sched.h fixed_slots; split_records 2 only): k_paths stores a path's retirement record at the
+  int32_t fixed_slots;     // 1 (the host sets it from pt_sched.h batch_form; split_records 2 only): k_paths stores a path's retirement record at the
                            // slot its list position gives (pt_sched.h fixed_slot), so a slot holds the same pixel in every iteration's region
 };
 
@@ -110,7 +110,7 @@ struct ConvInfo {
   int32_t first_k;    // first k with a value; K: none
 };
 
-// The gather of the batch BEFORE the one a k_paths launch traces, done by that launch's waves (pt_sched.h inline_gather): the records
+// The gather of the batch BEFORE the one a k_paths launch traces, done by that launch's waves (pt_sched.h gather_plan): the records
 // that batch's k_paths wrote, in the record plane this launch does not write.
 struct PrevGather {
   const ptd::Word4* rec;     // the plane the previous batch's k_paths wrote: [Q][kmax][seg_cap] like RetireBuf::rec

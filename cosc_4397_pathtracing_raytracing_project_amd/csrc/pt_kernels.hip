@@ -1156,7 +1156,7 @@ constexpr int primary_waves() {
 // SPLIT (BatchInfo::split_records, shared form only; pt_sched.h): a survivor's record is the 16-byte per-iteration word (direction,
 // sample id | specular bit) in plane 0 and, from the run that holds iteration 0 of the batch only, the 16-byte invariant word
 // (origin, material index) in plane 1 at the slot of iteration 0; its throughput is not stored at all.
-// SPLIT == kFirstBounce (BatchInfo::split_records 2, kLdsTables only; pt_sched.h first_bounces): the kernel has no per-iteration work
+// SPLIT == kFirstBounce (BatchInfo::split_records 2, kLdsTables only; pt_sched.h batch_form): the kernel has no per-iteration work
 // left — a chunk is traced once per BATCH, a survivor's one record (bounce origin, hit normal, camera direction, pixel | material)
 // goes to the slot of iteration 0, and k_paths decides depth 0 and samples the first bounce of every iteration from it.
 template <Search F, bool SHARE = false, int SPLIT = 0>
@@ -1333,7 +1333,7 @@ __global__ __launch_bounds__(kBlock, (primary_waves<F, SPLIT>())) void k_primary
     };
     if constexpr (RING) ws = carry_init<true, 2>(wbase), ws.qo_tab = cam_qo, ws.cam_o = o;  // every strand starts with an empty ring
     if constexpr (SHARE && SPLIT == kFirstBounce) {
-      // First bounce in k_paths (pt_sched.h first_bounces; the host gives such a batch ONE piece, and the run is the whole batch):
+      // First bounce in k_paths (pt_sched.h batch_form; the host gives such a batch ONE piece, and the run is the whole batch):
       // chunk jj is traced once, a surviving pixel gets its one record — what every iteration's depth-0 shading starts from — at the
       // slot of iteration 0, a retiring one its record as in every BatchInfo::retire_once batch, and the pair of counts, the same in
       // every iteration, goes to sub[] of all of them.  No iteration loop, no shade_decide of a survivor, no direction sampling.
@@ -1366,7 +1366,7 @@ __global__ __launch_bounds__(kBlock, (primary_waves<F, SPLIT>())) void k_primary
         }
       }
       // identical counts (zeros where the wave had no chunk) for every iteration the regions are provisioned for, not this batch's K
-      // alone: a longer batch of the same camera finds them without another trace (pt_sched.h primary_once); kmax may exceed the 64 lanes
+      // alone: a longer batch of the same camera finds them without another trace (pt_sched.h batch_form); kmax may exceed the 64 lanes
       for (int k = lane; k < ret.kmax; k += 64) rt.sub[k * rt.wq0 + shared_rho(r, k, wq)] = ((unsigned long long)(uint32_t)fnd << 32) | (uint32_t)fnl;
     } else if constexpr (SHARE) {
       // Shared form (pt_sched.h): the wave keeps residue r through the piece, so chunk jj is traced ONCE per run of iterations
@@ -1681,13 +1681,13 @@ static_assert((kVisitRing & (kVisitRing - 1)) == 0, "visit numbers wrap with a m
 // SPLIT (BatchInfo::split_records, pt_sched.h): a path's record is the per-iteration word (direction, sample id | specular bit) at its
 // own slot of plane 0 and the invariant word (origin, material index) at the same slot of ITERATION 0 in plane 1 — the cursor
 // keeps both bases — and its throughput is (1, 1, 1) times the material's spec or color, formed when the lane takes the path.
-// SPLIT == kFirstBounce (BatchInfo::split_records 2, MODE 0 only; pt_sched.h first_bounces): the record is the pixel's one whole record at
+// SPLIT == kFirstBounce (BatchInfo::split_records 2, MODE 0 only; pt_sched.h batch_form): the record is the pixel's one whole record at
 // the slot of iteration 0; the iteration comes from the cursor and waits beside the visit number (pack_visit), and the lane that
 // takes the record decides depth 0 and samples the first bounce itself, in the rotated loop behind the other forms'.
-// SPLIT == kFixedSlots (such a batch with BatchInfo::fixed_slots; pt_sched.h fixed_slots): the first-bounce form without the visit ring — the
+// SPLIT == kFixedSlots (such a batch with BatchInfo::fixed_slots; pt_sched.h batch_form): the first-bounce form without the visit ring — the
 // cursor keeps where the record of its sub-list's first path goes, the word that waits beside a record is the path's own record slot
 // (pack_fixed), and a dying lane has nothing to ask anybody: no counter, no lap guard, no limit on the visits of a refill.
-// PREV (empty, or PrevGather alone; kFixedSlots only — pt_sched.h inline_gather): the launch also gathers the batch before its own, whose
+// PREV (empty, or PrevGather alone; kFixedSlots only — pt_sched.h gather_plan): the launch also gathers the batch before its own, whose
 // records lie in the other record plane.  The waves of queue q add that batch's records of queue q to the image, stream_gather_slot's
 // work for 64 consecutive slots at a time: group j of the queue's my_nq goes to wave j mod wq, which takes one group each time it moves
 // on to a piece (not the first: nothing is in flight beside it then) and the rest of its share after its last path has retired.  A step
@@ -1792,7 +1792,7 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
     }
   }
   if (r == 0 && lane == 0) cnt[cnt_index(qs, 1, q)] = total;  // statistics: rays traced at depth 1
-  // ... and at depth 0, k_primary's own figure: a first-bounce batch may run without that kernel (pt_sched.h primary_once), and the row is zeroed after every batch
+  // ... and at depth 0, k_primary's own figure: a first-bounce batch may run without that kernel (pt_sched.h batch_form), and the row is zeroed after every batch
   if constexpr (SPLIT == kFirstBounce || SPLIT == kFixedSlots)
     if (r == 0 && lane == 0) cnt[cnt_index(qs, 0, q)] = b.K * qshare.my_pixels;
   // The queue's ranks [0, total) are cut into pieces of `ps` paths.  Piece r is the wave's own; the pieces from wq on go, in
@@ -2091,7 +2091,7 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
       }
     }
   }
-  // ── BatchInfo::split_records 2 (pt_sched.h first_bounces): the same round, rotated ────────────────────────────────────────────
+  // ── BatchInfo::split_records 2 (pt_sched.h batch_form): the same round, rotated ────────────────────────────────────────────
   // search, shade_decide of the resolved lanes, pieces + refill, direction sampling.  The refill above follows the shading at once
   // anyway; here it sits between shade_bounce's two halves, so a lane whose path has just died — or that never had one — takes its
   // next record, decides depth 0 for it (shade_decide's own depth-0 path: the seed of the record's iteration, at most one draw, the

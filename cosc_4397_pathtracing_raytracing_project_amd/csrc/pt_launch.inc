@@ -20,6 +20,7 @@ template <typename F>
 void with_intersect_grid(const SceneTables& sc, bool primary, F&& f) {
   primary ? f(k_intersect_grid<kD0>, intersect_grid_lds<kFast, kD0>(sc).total) : f(k_intersect_grid<false>, intersect_grid_lds<kFast, false>(sc).total);
 }
+static_assert((int)kLdsTables == kSearchLdsTables, "pt_sched.h batch_form names the LDS-table search form");
 // The LDS-table kernel variants assume that every leaf is a top-list entry (no subtrees).
 bool leaves_fit_top(const SceneTables& sc) { return (sc.num_nodes + 1) / 2 <= kMaxTop; }
 // k_features: k_intersect's LDS map; scenes whose tables stay in memory and whose leaves do not all fit the top list take the
@@ -48,7 +49,7 @@ void with_primary(const SceneTables& sc, bool share, int split, F&& f) {
   }
 }
 
-// split: BatchInfo::split_records (0, kSplitRecords; kLdsTables also kFirstBounce and, with BatchInfo::fixed_slots, kFixedSlots) — the same LDS map
+// split: pt_sched.h paths_split (0, kSplitRecords; kLdsTables also kFirstBounce and kFixedSlots) — the same LDS map
 template <typename F>
 void with_paths(const SceneTables& sc, Search form, int split, F&& f) {  // (SceneTables::scan_nodes_lds resolved by the caller)
   switch (form) {
@@ -129,11 +130,11 @@ int resident_blocks_per_cu(KernelId id, const SceneTables& sc) {
     // (a context's batches run any record form of these two, BatchInfo::split_records: same LDS; the smallest count serves all — where a
     // form does not exist for the tables' search form, kFirstBounce and kFixedSlots, the selectors give the split form again)
     case kPrimaryShared:
-      for (int form : {0, kSplitRecords, kFirstBounce}) with_primary(sc, true, form, query_share), m = form ? min(m, n) : n;
+      for (int form : kRecordForms) with_primary(sc, true, form, query_share), m = form ? min(m, n) : n;
       n = m;
       break;
     case kPaths:
-      for (int form : {0, kSplitRecords, kFirstBounce, kFixedSlots}) with_paths(resolve_scan_nodes(sc), search_form(sc), form, query_share), m = form ? min(m, n) : n;
+      for (int form : kPathsSplits) with_paths(resolve_scan_nodes(sc), search_form(sc), form, query_share), m = form ? min(m, n) : n;
       n = m;
       if (search_form(sc) == kLdsTables) query_share(k_paths<kLdsTables, kFixedSlots, PrevGather>, paths_lds<kLdsTables, kFast>(resolve_scan_nodes(sc)).total), n = min(m, n);
       break;
@@ -162,7 +163,7 @@ void launch_intersect_grid(hipStream_t s, int grid, const SceneTables& sc, const
 
 void launch_primary(hipStream_t s, int grid, const SceneTables& sc, const ptd::Camera& cam, const BatchInfo& b,
                     const ptd::Queues& qs, int32_t* cnt0, int32_t* cnt_out, ptd::PathBuf out, ptd::RetireBuf ret) {
-  with_primary(sc, primary_shares(b), primary_shares(b) ? b.split_records : 0, [&](auto kernel, int lds) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, sc, cam, b, qs, cnt0, cnt_out, out, ret); });
+  with_primary(sc, primary_shares(b), b.split_records, [&](auto kernel, int lds) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, sc, cam, b, qs, cnt0, cnt_out, out, ret); });
 }
 
 void launch_features(hipStream_t s, int grid, const SceneTables& sc, const ptd::Camera& cam, const BatchInfo& b, float4* feat) {
@@ -175,7 +176,7 @@ void launch_features(hipStream_t s, int grid, const SceneTables& sc, const ptd::
 
 void launch_paths(hipStream_t s, int grid, const SceneTables& sc_in, const BatchInfo& b, const ptd::Queues& qs, int32_t* cnt, ptd::PathBuf in, ptd::RetireBuf ret) {
   const SceneTables sc = resolve_scan_nodes(sc_in);
-  with_paths(sc, search_form(sc), b.split_records == kFirstBounce && b.fixed_slots ? kFixedSlots : b.split_records, [&](auto kernel, int lds) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, sc, b, qs, cnt, in, ret); });
+  with_paths(sc, search_form(sc), paths_split(b.split_records, b.fixed_slots != 0), [&](auto kernel, int lds) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, sc, b, qs, cnt, in, ret); });
 }
 // The fixed-slot instance that also gathers the previous batch (k_paths, PREV): the LDS-table form only, the same LDS map
 void launch_paths_gather(hipStream_t s, int grid, const SceneTables& sc_in, const BatchInfo& b, const ptd::Queues& qs, int32_t* cnt, ptd::PathBuf in,

@@ -223,7 +223,7 @@ int ensure_worker(Ctx& g, int m) {
 // Iterations iter_first .. iter_first + iter_count - 1 of the listed pixels into the worker's cleared group sum.
 int render_list(Ctx& g, int iter_first, int iter_count) {
   Ctx& w = *g.worker;
-  w.primary_valid = false;  // a round's list is new behind the same pointer: depth 0 is traced once per round (pt_sched.h primary_once)
+  w.primary_valid = false;  // a round's list is new behind the same pointer: depth 0 is traced once per round (pt_sched.h BatchForm::primary_once)
   HIP_OK(hipMemsetAsync(w.d_image, 0, 3 * (size_t)w.N * sizeof(float), g.stream));
   const int end = iter_first + iter_count;
   for (int it = iter_first; it < end; it += w.K)

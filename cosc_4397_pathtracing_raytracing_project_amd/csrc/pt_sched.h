@@ -155,7 +155,9 @@ PT_SCHED int auto_primary_pieces(int K, int nq, int wq0) {
 // longer piece is walked as sub-runs, each tracing the chunks again.
 constexpr int kShareMax = 64;
 // Which form a batch runs: the shared one needs the camera rays to be the same in every iteration (no jitter) and the
-// per-(queue, iteration) sub-lists (not flat); BatchInfo::primary_share <= 1 asks for a trace per iteration.
+// per-(queue, iteration) sub-lists (not flat); BatchInfo::primary_share <= 1 asks for a trace per iteration, and so does
+// PtOptions.debug_flags kTraceEveryIteration (the host passes a primary_share of 1 then).  The first rung of batch_form, below.
+constexpr int kTraceEveryIteration = 128;
 PT_SCHED bool primary_shares(int primary_share, bool aa_jitter, bool flat) { return primary_share > 1 && !aa_jitter && !flat; }
 PT_SCHED bool primary_shares(const BatchInfo& b) { return primary_shares(b.primary_share, b.aa_jitter != 0, b.flat != 0); }
 PT_SCHED int shared_rho(int r, int /*k*/, int /*wq*/) { return r; }  // the strand's residue in iteration k: the same in all of them (beside strand_rho)
@@ -189,12 +191,6 @@ PT_SCHED int auto_shared_pieces(int K, int /*nq*/, int /*wq0*/) {
 // simply neither written nor read.  With trace_depth == 1 EVERY sample retires at depth 0, with a colour that depends on the
 // iteration's specular / diffuse draw: the rule is off.  PtOptions.debug_flags kRetireEveryIteration: off as an A/B switch.
 constexpr int kRetireEveryIteration = 1024;
-PT_SCHED bool retires_once(int primary_share, bool aa_jitter, bool flat, int trace_depth, int debug_flags) {
-  return primary_shares(primary_share, aa_jitter, flat) && trace_depth >= 2 && !(debug_flags & kRetireEveryIteration);
-}
-PT_SCHED bool retires_once(const BatchInfo& b, int debug_flags) {
-  return retires_once(b.primary_share, b.aa_jitter != 0, b.flat != 0, b.trace_depth, debug_flags);
-}
 // Slot i of a region (q, k) -> the sub-region (q, k, rho) that holds it and its position there: the inverse of sub_offset /
 // sub_chunks.  Residues below rem own quo + 1 chunks each, the others quo; slots behind the last sub-region
 // (i >= my_nq * 64) do not exist.  (quo = my_nq / wq0, rem = my_nq % wq0)
@@ -218,16 +214,9 @@ PT_SCHED bool retiree_slot(const SubSlot& s, int retirees) { return s.pos < reti
 // same strides,
 //   plane 0, slot at                   (direction.xyz, sample id | kind << 31)   per iteration, as before
 //   plane 1, slot at - k * seg_cap     (origin.xyz, material index)              once, by the run that holds iteration 0
-// and leaves plane 2 alone; k_paths forms the throughput from its material table.  The conditions are those of retires_once
-// (trace_depth 1: nobody survives; jitter, flat lists, a trace per iteration: whole records).  PtOptions.debug_flags
-// kWholeRecords: off as an A/B switch.
+// and leaves plane 2 alone; k_paths forms the throughput from its material table.  (trace_depth 1: nobody survives; jitter,
+// flat lists, a trace per iteration: whole records.)  PtOptions.debug_flags kWholeRecords: off as an A/B switch.
 constexpr int kWholeRecords = 4096;
-PT_SCHED bool splits_records(int primary_share, bool aa_jitter, bool flat, int trace_depth, int debug_flags) {
-  return primary_shares(primary_share, aa_jitter, flat) && trace_depth >= 2 && !(debug_flags & kWholeRecords);
-}
-PT_SCHED bool splits_records(const BatchInfo& b, int debug_flags) {
-  return splits_records(b.primary_share, b.aa_jitter != 0, b.flat != 0, b.trace_depth, debug_flags);
-}
 // Where the invariant half of the record at path slot `at` = k * seg_cap + sub_offset(quo, rem, rho) * 64 + i of a queue lives:
 // the same slot of iteration 0.
 PT_SCHED int invariant_slot(int at, int k, int seg_cap) { return at - k * seg_cap; }
@@ -248,11 +237,12 @@ PT_SCHED bool kind_specular(uint32_t word) { return (word >> 31) != 0u; }
 //   tile pixel | material index << slot_shift  (pack_first)               where it keeps the sample id
 // k_primary traces a chunk once per batch and publishes the same pair of counts for every iteration; a lane of k_paths that takes
 // the record of sub-list (k, rho) decides depth 0 for iteration k itself and samples the first bounce with the lanes that
-// survived that round.  The conditions are those of splits_records and retires_once together, plus: the LDS-table search form
-// (the other forms keep the next record in registers; they stay with split records), a material index that fits beside the
-// tile pixel, and a K that fits beside the visit number (pack_visit).  PtOptions.debug_flags kNoFirstBounce: off as an A/B switch.
+// survived that round.  It needs the LDS-table search form (the other forms keep the next record in registers; they stay with split
+// records), a material index that fits beside the tile pixel, and a K that fits beside the visit number (pack_visit).
+// PtOptions.debug_flags kNoFirstBounce: off as an A/B switch.
 constexpr int kNoFirstBounce = 8192;
 constexpr int kSplitRecords = 1, kFirstBounce = 2;  // BatchInfo::split_records
+constexpr int kSearchLdsTables = 0;                  // FormInputs::search_form: pt_lds.h kLdsTables
 // The word that waits with a record in a lane's refill slot: the iteration k of its sub-list above the visit number modulo
 // 2^kVisitBits.  A path in flight was taken fewer than kVisitRing (pt_lds.h) <= 2^(kVisitBits - 1) visits ago, so the distance
 // of two visit numbers is compared modulo the packed width (visit_gap).
@@ -267,20 +257,6 @@ PT_SCHED int pack_first(int pl, int mat, int slot_shift) { return (mat << slot_s
 PT_SCHED int first_pixel(int word, int slot_shift) { return word & ((1 << slot_shift) - 1); }
 PT_SCHED int first_material(int word, int slot_shift) { return (int)((uint32_t)word >> slot_shift); }
 PT_SCHED bool first_material_fits(int num_mats, int slot_shift) { return num_mats <= (1 << (31 - slot_shift)); }
-// search_form: pt_lds.h Search of the context's tables (0: the LDS-table form)
-PT_SCHED bool first_bounces(int primary_share, bool aa_jitter, bool flat, int trace_depth, int debug_flags, int search_form, int num_mats,
-                            int slot_shift, int K) {
-  return splits_records(primary_share, aa_jitter, flat, trace_depth, debug_flags) &&
-         retires_once(primary_share, aa_jitter, flat, trace_depth, debug_flags) && !(debug_flags & kNoFirstBounce) && search_form == 0 &&
-         first_material_fits(num_mats, slot_shift) && visit_k_fits(K);
-}
-PT_SCHED bool first_bounces(const BatchInfo& b, int debug_flags, int search_form, int num_mats) {
-  return first_bounces(b.primary_share, b.aa_jitter != 0, b.flat != 0, b.trace_depth, debug_flags, search_form, num_mats, b.slot_shift, b.K);
-}
-// BatchInfo::split_records of a batch: whole records, split records or the first bounce in k_paths.
-PT_SCHED int record_form(const BatchInfo& b, int debug_flags, int search_form, int num_mats) {
-  return first_bounces(b, debug_flags, search_form, num_mats) ? kFirstBounce : splits_records(b, debug_flags) ? kSplitRecords : 0;
-}
 
 // ── depth 0 of a first-bounce batch: traced once per camera ───────────────────────────────────────────────────────────────
 // What k_primary leaves behind in a first-bounce batch — the surviving pixels' records at their slots of iteration 0, the depth-0
@@ -290,7 +266,7 @@ PT_SCHED int record_form(const BatchInfo& b, int debug_flags, int search_form, i
 // such batch of the same context finds it as it needs it, and the host launches k_primary only when one of those inputs has changed
 // (pt_api.cpp run_batch keeps the launch's arguments as the key).  The counter row of depth 0, which the statistics read and re-zero
 // after every batch, is written by k_paths in this form.  Every other form's depth 0 has per-iteration output and is traced in every
-// batch.  The rule holds for the batches with fixed record slots (primary_once, behind fixed_slots below): there k_paths' own stores
+// batch.  The rule holds for the batches with fixed record slots (the rung behind them in batch_form below): there k_paths' own stores
 // into the record regions go to slots the path's list position gives, behind the retirees', in every batch alike.
 // PtOptions.debug_flags kPrimaryEveryBatch: in every batch, as an A/B switch.
 constexpr int kPrimaryEveryBatch = 65536;
@@ -314,46 +290,93 @@ PT_SCHED uint32_t pack_fixed(int k, int in_region, int bits) { return ((uint32_t
 PT_SCHED int fixed_k(uint32_t word, int bits) { return (int)(word >> bits); }
 PT_SCHED int fixed_slot_of(uint32_t word, int bits, int seg_cap) { return (int)(word >> bits) * seg_cap + (int)(word & ((1u << bits) - 1u)); }
 PT_SCHED bool fixed_word_fits(int K, int seg_cap) { return K <= (1 << (31 - fixed_bits(seg_cap))); }
-PT_SCHED bool fixed_slots(int primary_share, bool aa_jitter, bool flat, int trace_depth, int debug_flags, int search_form, int num_mats, int slot_shift,
-                          int K, int seg_cap) {
-  return first_bounces(primary_share, aa_jitter, flat, trace_depth, debug_flags, search_form, num_mats, slot_shift, K) && fixed_word_fits(K, seg_cap) &&
-         !(debug_flags & kRecordsByVisit);
+// k_paths' SPLIT argument from BatchInfo::split_records and BatchInfo::fixed_slots (BatchForm::split; pt_launch.inc launch_paths).
+PT_SCHED int paths_split(int records, bool fixed_slots) { return records == kFirstBounce && fixed_slots ? kFixedSlots : records; }
+
+// ── the form of a batch: the rungs above, each a step from the one before it ──────────────────────────────────────────────
+// Host code only: run_batch (pt_api.cpp) decides the form once per batch and copies it into BatchInfo::retire_once, split_records and
+// fixed_slots; the kernels and their launch wrappers read those.  (tests/test_sched_form.py)
+struct FormInputs {  // (search_form: pt_lds.h Search of the context's tables; seg_cap: RetireBuf::seg_cap)
+  int primary_share;
+  bool aa_jitter, flat;
+  int trace_depth, debug_flags, search_form, num_mats, slot_shift, K, seg_cap;
+};
+PT_SCHED FormInputs form_inputs(const BatchInfo& b, int debug_flags, int search_form, int num_mats, int seg_cap) {
+  return FormInputs{b.primary_share, b.aa_jitter != 0, b.flat != 0, b.trace_depth, debug_flags, search_form, num_mats, b.slot_shift, b.K, seg_cap};
 }
-PT_SCHED bool fixed_slots(const BatchInfo& b, int debug_flags, int search_form, int num_mats, int seg_cap) {
-  return fixed_slots(b.primary_share, b.aa_jitter != 0, b.flat != 0, b.trace_depth, debug_flags, search_form, num_mats, b.slot_shift, b.K, seg_cap);
+struct BatchForm {
+  bool shares, retire_once;  // k_primary's shared form; BatchInfo::retire_once
+  int records;               // BatchInfo::split_records: 0, kSplitRecords or kFirstBounce
+  bool fixed_slots;          // BatchInfo::fixed_slots
+  bool primary_once;         // the batch reads the first-hit records an earlier batch of the same camera, tile and plan left
+  int split;                 // k_paths' SPLIT argument (paths_split)
+};
+PT_SCHED BatchForm batch_form(const FormInputs& in) {
+  BatchForm f{};
+  f.shares = primary_shares(in.primary_share, in.aa_jitter, in.flat);
+  const bool invariant = f.shares && in.trace_depth >= 2;  // what leaves depth 0, and how, is a function of the pixel alone
+  f.retire_once = invariant && !(in.debug_flags & kRetireEveryIteration);
+  const bool splits = invariant && !(in.debug_flags & kWholeRecords);
+  const bool first = splits && f.retire_once && !(in.debug_flags & kNoFirstBounce) && in.search_form == kSearchLdsTables &&
+                     first_material_fits(in.num_mats, in.slot_shift) && visit_k_fits(in.K);
+  f.records = first ? kFirstBounce : splits ? kSplitRecords : 0;
+  f.fixed_slots = first && fixed_word_fits(in.K, in.seg_cap) && !(in.debug_flags & kRecordsByVisit);
+  f.primary_once = f.fixed_slots && !(in.debug_flags & kPrimaryEveryBatch);
+  f.split = paths_split(f.records, f.fixed_slots);
+  return f;
 }
-// Depth 0 once per camera (above): such a batch reads the first-hit records an earlier batch of the same camera, tile and plan left.
-PT_SCHED bool primary_once(int primary_share, bool aa_jitter, bool flat, int trace_depth, int debug_flags, int search_form, int num_mats, int slot_shift,
-                           int K, int seg_cap) {
-  return fixed_slots(primary_share, aa_jitter, flat, trace_depth, debug_flags, search_form, num_mats, slot_shift, K, seg_cap) && !(debug_flags & kPrimaryEveryBatch);
-}
-PT_SCHED bool primary_once(const BatchInfo& b, int debug_flags, int search_form, int num_mats, int seg_cap) {
-  return primary_once(b.primary_share, b.aa_jitter != 0, b.flat != 0, b.trace_depth, debug_flags, search_form, num_mats, b.slot_shift, b.K, seg_cap);
-}
+// Every value of BatchForm::records and of BatchForm::split: what a context's batches can ask of k_primary and k_paths (residency).
+constexpr int kRecordForms[] = {0, kSplitRecords, kFirstBounce}, kPathsSplits[] = {0, kSplitRecords, kFirstBounce, kFixedSlots};
+
+// ── the gather of a batch: one plan ───────────────────────────────────────────────────────────────────────────────────────
 // PtStats.gather_form of a batch: 0 the tile gather over records in order of retirement, 1 the tile gather over fixed slots (kTileGather,
 // and every batch with the convergence metric, whose partial sums keep their partition), 2 the stream.
 constexpr int kGatherTile = 0, kGatherTileFixed = 1, kGatherStream = 2;
-PT_SCHED int gather_form(bool fixed, int debug_flags, bool convergence) { return !fixed ? kGatherTile : (debug_flags & kTileGather) || convergence ? kGatherTileFixed : kGatherStream; }
 // The stream gather of a batch inside the NEXT batch's k_paths (PtStats.gather_form 3 while such a batch waits; the last batch of a render
 // call is always gathered by k_collect_stream, so a finished call reports 2 and PtStats.inline_gathers counts the others).  k_paths is bound
 // by instruction issue and leaves most of the memory system idle, the gather is memory traffic alone, and as separate launches they run
 // one after the other: the waves of batch n + 1 therefore add batch n's records to the image in small steps beside their own work
 // (pt_kernels.hip k_paths, PREV).  Batch n + 1 stores its records in the other of two record planes; what k_primary writes once per
-// camera — the depth-0 retirees' records, sub[] — stays in plane 0 and is only read.  It applies when both batches belong to one render
-// call, both are stream-gathered batches of a context with depth 0 once per camera, the second launches no k_primary (same camera, tile or
-// list, queues and plan: run_batch's PrimaryKey) and the second plane exists and may be used (second_plane: not in a context with the
-// convergence metric, whose batches change form in mid-call).  Noise folds, read-backs and camera moves happen between render calls,
-// where nothing waits.  PtOptions.debug_flags kGatherEveryBatch:
-// every batch by k_collect_stream, as an A/B switch.
-constexpr int kGatherInline = 3;
-constexpr int kGatherEveryBatch = 131072;
-// May the gather of a batch wait for the next batch's k_paths?  (more: another batch of the same render call follows)
-PT_SCHED bool defers_gather(bool more, int form, bool primary_once, bool second_plane, int debug_flags) {
-  return more && form == kGatherStream && primary_once && second_plane && !(debug_flags & kGatherEveryBatch);
-}
-// Does this batch's k_paths gather the waiting one?  (same_key: this batch launches no k_primary — everything that launch depends on is unchanged)
-PT_SCHED bool inline_gather(bool waiting, int form, bool primary_once, bool same_key, bool second_plane, int debug_flags) {
-  return waiting && form == kGatherStream && primary_once && same_key && second_plane && !(debug_flags & kGatherEveryBatch);
+// camera — the depth-0 retirees' records, sub[] — stays in plane 0 and is only read.  The second plane may not be used in a context with
+// the convergence metric, whose batches change form in mid-call.  Noise folds, read-backs and camera moves happen between render calls,
+// where nothing waits.  PtOptions.debug_flags kGatherEveryBatch: every batch by k_collect_stream, as an A/B switch.
+constexpr int kGatherInline = 3, kGatherEveryBatch = 131072;
+// The switches under which no batch of a context takes that form (such a context gets no second plane), and every switch read here.
+constexpr int kNoSecondPlane = kGatherEveryBatch | kTileGather | kRecordsByVisit | kNoFirstBounce | kPrimaryEveryBatch;
+constexpr int kFormSwitches = kTraceEveryIteration | kRetireEveryIteration | kWholeRecords | kNoSecondPlane;
+struct GatherInputs {
+  BatchForm form;
+  bool metric, waiting;  // the batch carries the convergence metric; the batch before it waits for its gather ...
+  int waiting_plane;     // ... with its records in this plane
+  bool same_key;         // this batch launches no k_primary (run_batch's PrimaryKey is unchanged)
+  bool second_plane;     // the second plane exists and may be used
+  int after, debug_flags;  // after: batches of the same render call that follow this one
+  bool fused;            // the bounces run in k_paths
+};
+// The launch that closes a batch: the stream gather with the counter rows' blocks (records in plane 0), or k_count_stats and then
+// the stream gather over both planes, the tile gather with or without the metric, or nothing (the gather waits).
+enum Closing { kCloseStream, kCloseStatsStreamPlanes, kCloseStatsConv, kCloseStatsTile, kCloseStats };
+struct GatherPlan {
+  int form;                      // kGatherTile, kGatherTileFixed or kGatherStream
+  bool gathers_waiting, defers;  // this batch's k_paths gathers the batch before it; its own gather waits for the next batch's k_paths
+  int plane, reported;           // the record plane this batch's k_paths writes; PtStats.gather_form
+  Closing closing;
+};
+// A batch whose gather waits stores its records in plane `after` mod 2, so that the planes alternate along the call and its last batch —
+// which never waits, like the only batch of a call — lies in plane 0; a batch that gathers its predecessor takes the plane that one did
+// not use (the same thing, unless the chain began in mid-call).
+PT_SCHED GatherPlan gather_plan(const GatherInputs& in) {
+  GatherPlan p{};
+  p.form = !in.form.fixed_slots ? kGatherTile : (in.debug_flags & kTileGather) || in.metric ? kGatherTileFixed : kGatherStream;
+  const bool chains = p.form == kGatherStream && in.form.primary_once && in.second_plane && in.fused && !(in.debug_flags & kGatherEveryBatch);
+  p.gathers_waiting = chains && in.waiting && in.same_key;
+  p.defers = chains && in.after > 0;
+  p.plane = p.gathers_waiting ? 1 - in.waiting_plane : p.defers ? in.after & 1 : 0;
+  p.reported = p.defers ? kGatherInline : p.form;
+  if (p.defers) p.closing = kCloseStats;
+  else if (p.form == kGatherStream) p.closing = p.plane == 0 ? kCloseStream : kCloseStatsStreamPlanes;
+  else p.closing = in.metric ? kCloseStatsConv : kCloseStatsTile;
+  return p;
 }
 
 // ── k_paths: falling pieces ───────────────────────────────────────────────────────────────────────────────────────────────

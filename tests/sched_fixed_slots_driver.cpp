@@ -1,6 +1,6 @@
-// Prints the fixed-slot rule of csrc/pt_sched.h — the record slot of the path at list position i of sub-list (k, rho), the word that
-// waits beside a record in a refill slot, which batches store their records that way and how they are gathered — over a sweep
-// (tests/test_sched_fixed_slots.py compiles this with the system compiler, runs it and checks the output by enumeration).
+// Prints the layout behind the fixed-slot rule of csrc/pt_sched.h — the record slot of the path at list position i of sub-list (k, rho)
+// and the word that waits beside a record in a refill slot — over a sweep (tests/test_sched_fixed_slots.py compiles this with the system
+// compiler, runs it and checks the output by enumeration; which batches store their records that way: tests/sched_form_driver.cpp).
 // Output: one header line per case (`name key=value ...`), for `slots` followed by lines of plain numbers.
 #include <cstdint>
 #include <cstdio>
@@ -58,8 +58,6 @@ static void put_slots() {
 }
 
 int main() {
-  printf("consts by_visit=%d tile=%d template=%d first=%d forms=%d,%d,%d\n", kRecordsByVisit, kTileGather, kFixedSlots, kFirstBounce, kGatherTile, kGatherTileFixed,
-         kGatherStream);
   put_slots();
   // word: the largest k and offset of every region size
   for (int seg_cap : {64, 128, 192, 8128, 8192, 8256, 1 << 20, (1 << 20) + 64, 1 << 30}) {
@@ -72,25 +70,5 @@ int main() {
       }
     for (int K : {1, kmax - 1, kmax, kmax + 1}) printf("kfits seg_cap=%d bits=%d K=%d ok=%d\n", seg_cap, bits, K, (int)fixed_word_fits(K, seg_cap));
   }
-  // rule: the predicate over its conditions, as a function and on a BatchInfo, and the gather it leads to
-  for (int share : {1, 64})
-    for (int aa = 0; aa < 2; ++aa)
-      for (int flat = 0; flat < 2; ++flat)
-        for (int depth : {1, 8})
-          for (int flags : {0, 16, 8192, 4096, 1024, 16384, 32768, 16384 | 32768, 16384 | 16, 32768 | 8192})
-            for (int form : {0, 1})
-              for (int mats : {8, 9})  // slot_shift 28 below: 2^(31 - 28) = 8 material indices fit
-                for (int K : {25, 1 << 18, (1 << 18) + 1})  // seg_cap 8128 below: 13 bits, 2^18 iterations fit
-                  for (int conv = 0; conv < 2; ++conv) {
-                    BatchInfo b{};
-                    b.primary_share = share, b.aa_jitter = aa, b.flat = flat, b.trace_depth = depth, b.slot_shift = 28, b.K = K;
-                    const int seg_cap = 8128;
-                    const bool fixed = fixed_slots(share, aa != 0, flat != 0, depth, flags, form, mats, b.slot_shift, K, seg_cap);
-                    printf("rule share=%d aa=%d flat=%d depth=%d flags=%d form=%d mats=%d K=%d conv=%d seg_cap=%d first=%d fixed=%d fixed_b=%d gather=%d\n", share, aa, flat, depth,
-                           flags, form, mats, K, conv, seg_cap, (int)first_bounces(b, flags, form, mats), (int)fixed, (int)fixed_slots(b, flags, form, mats, seg_cap),
-                           gather_form(fixed, flags, conv != 0));
-                  }
-  BatchInfo zero{};
-  printf("fresh fixed_slots=%d size=%d\n", (int)zero.fixed_slots, (int)sizeof(BatchInfo));
   return 0;
 }

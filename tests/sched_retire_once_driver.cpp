@@ -1,6 +1,6 @@
-// Prints the retire-once rule of csrc/pt_sched.h — which batches store their depth-0 retirees once, and the map from a region's
-// slot to its sub-region and position there — over a sweep (tests/test_sched_retire_once.py compiles this with the system
-// compiler, runs it and checks the output by enumeration).  Output: one header line per case (`name key=value ...`) followed
+// Prints the slot map behind the retire-once rule of csrc/pt_sched.h — from a region's slot to its sub-region and position there —
+// over a sweep (tests/test_sched_retire_once.py compiles this with the system compiler, runs it and checks the output by
+// enumeration; which batches retire once: tests/sched_form_driver.cpp).  Output: one header line per case (`name key=value ...`) followed
 // by lines of plain numbers.
 #include <cstdint>
 #include <cstdio>
@@ -59,17 +59,5 @@ static void put_slots() {
 
 int main() {
   put_slots();
-  for (int share : {-1, 0, 1, 2, 25, 64})
-    for (int aa = 0; aa < 2; ++aa)
-      for (int flat = 0; flat < 2; ++flat)
-        for (int depth : {1, 2, 3, 8})
-          for (int flags : {0, 128, 1024, 1024 | 16, 2048 | 512}) {
-            BatchInfo b{};
-            b.primary_share = share, b.aa_jitter = aa, b.flat = flat, b.trace_depth = depth;
-            printf("rule share=%d aa=%d flat=%d depth=%d flags=%d once=%d once_b=%d bit=%d\n", share, aa, flat, depth, flags,
-                   (int)retires_once(share, aa != 0, flat != 0, depth, flags), (int)retires_once(b, flags), kRetireEveryIteration);
-          }
-  BatchInfo zero{};
-  printf("fresh retire_once=%d size=%d\n", (int)zero.retire_once, (int)sizeof(BatchInfo));
   return 0;
 }

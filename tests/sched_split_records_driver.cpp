@@ -1,6 +1,6 @@
-// Prints the split-record rule of csrc/pt_sched.h — which batches store the invariant half of a depth-1 record once, where that
-// half lives, and the specular bit beside the sample id — over a sweep (tests/test_sched_split_records.py compiles this with the
-// system compiler, runs it and checks the output by enumeration).  Output: one header line per case (`name key=value ...`)
+// Prints the layout behind the split-record rule of csrc/pt_sched.h — where the invariant half of a depth-1 record lives, and the
+// specular bit beside the sample id — over a sweep (tests/test_sched_split_records.py compiles this with the system compiler, runs
+// it and checks the output by enumeration; which batches split their records: tests/sched_form_driver.cpp).  Output: one header line per case (`name key=value ...`)
 // followed by lines of plain numbers.
 #include <cstdint>
 #include <cstdio>
@@ -57,17 +57,5 @@ int main() {
           printf("kind shift=%d k=%d pl=%d spec=%d id=%d word=%u out_id=%d out_spec=%d\n", shift, k, pl, spec, id, (unsigned)w, kind_sample_id(w), (int)kind_specular(w));
         }
   }
-  for (int share : {-1, 0, 1, 2, 25, 64})
-    for (int aa = 0; aa < 2; ++aa)
-      for (int flat = 0; flat < 2; ++flat)
-        for (int depth : {1, 2, 3, 8})
-          for (int flags : {0, 128, 1024, 4096, 4096 | 16, 2048 | 512}) {
-            BatchInfo b{};
-            b.primary_share = share, b.aa_jitter = aa, b.flat = flat, b.trace_depth = depth;
-            printf("rule share=%d aa=%d flat=%d depth=%d flags=%d split=%d split_b=%d once=%d bit=%d\n", share, aa, flat, depth, flags,
-                   (int)splits_records(share, aa != 0, flat != 0, depth, flags), (int)splits_records(b, flags), (int)retires_once(b, flags), kWholeRecords);
-          }
-  BatchInfo zero{};
-  printf("fresh split_records=%d\n", (int)zero.split_records);
   return 0;
 }

@@ -1,5 +1,6 @@
-"""The first-bounce rule of csrc/pt_sched.h without a GPU: which batches store one record per surviving pixel and batch and leave
-the first bounce to k_paths, when the host falls back to split records, and how the words of that form are packed.
+"""The first-bounce rule of csrc/pt_sched.h without a GPU: the fits that make the host fall back to split records, and how the
+words of that form are packed.  (Which batches store one record per surviving pixel and batch and leave the first bounce to k_paths
+is a rung of batch_form: tests/test_sched_form.py.)
 
 The record's last word holds the tile pixel below the material index (pack_first); the word that waits beside a record in a lane's
 refill slot holds the iteration of its sub-list above the visit number modulo 2^kVisitBits (pack_visit), and k_paths compares visit
@@ -13,7 +14,6 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), "cosc_4397_pathtracing_raytracing_project_amd", "csrc")
-NO_FIRST_BOUNCE, WHOLE_RECORDS, EVERY_ITERATION = 8192, 4096, 1024  # PtOptions.debug_flags
 
 
 @pytest.fixture(scope="module")
@@ -30,27 +30,6 @@ def out(tmp_path_factory):
         name, *tokens = line.split()
         cases.setdefault(name, []).append({k: int(v) for k, v in (t.split("=") for t in tokens)})
     return cases
-
-
-def test_which_batches_leave_the_first_bounce_to_k_paths(out):
-    (c,), = [out["consts"]]
-    assert c["bit"] == NO_FIRST_BOUNCE and (c["split"], c["first"]) == (1, 2)
-    vmax = 1 << (31 - c["visit_bits"])
-    assert len(out["rule"]) == 4 * 2 * 2 * 3 * 8 * 3 * 3 * 4
-    on = 0
-    for f in out["rule"]:
-        shared = f["share"] > 1 and not f["aa"] and not f["flat"] and f["depth"] >= 2
-        assert f["split"] == int(shared and not f["flags"] & WHOLE_RECORDS) and f["once"] == int(shared and not f["flags"] & EVERY_ITERATION)
-        want = int(f["split"] and f["once"] and not f["flags"] & NO_FIRST_BOUNCE and f["form"] == 0
-                   and f["mats"] <= 1 << (31 - f["shift"]) and f["K"] <= vmax)
-        assert f["first"] == f["first_b"] == want, f
-        assert f["record_form"] == (2 if want else f["split"]), f  # the fallback is the split form wherever that one holds
-        on += want
-    # share 2, 64 x depth 2, 8 x flags 0, 16, 128 (bit 128 acts through the share the host passes) x the LDS-table form x 1 or 8
-    # materials x the three K that fit
-    assert on == 2 * 2 * 3 * 2 * 3
-    (fresh,), = [out["fresh"]]
-    assert fresh["split_records"] == 0  # `BatchInfo b{}` (the drivers, the stage helpers): whole records unless the host sets it
 
 
 def test_fallbacks_for_words_that_do_not_fit(out):

@@ -1,6 +1,6 @@
 """The fixed-slot rule of csrc/pt_sched.h without a GPU: where k_paths stores the retirement record of the path at list position i of
-sub-list (k, rho) in a first-bounce batch, the word that waits beside the path's record in a lane's refill slot, which batches store
-their records that way and how they are then gathered.
+sub-list (k, rho) in a first-bounce batch, and the word that waits beside the path's record in a lane's refill slot.  (Which batches
+store their records that way is a rung of batch_form, tests/test_sched_form.py; how they are gathered, tests/test_sched_gather.py.)
 
 A slot must lie among the survivors' slots of its sub-region, behind the depth-0 retirees k_primary put at the front; no two paths
 of a queue may share one; and the slot without its iteration's k * seg_cap must be the same in every iteration, because the stream
@@ -14,7 +14,6 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), "cosc_4397_pathtracing_raytracing_project_amd", "csrc")
-BY_VISIT, TILE_GATHER, NO_FIRST_BOUNCE, WHOLE_RECORDS, EVERY_ITERATION = 16384, 32768, 8192, 4096, 1024  # PtOptions.debug_flags
 
 
 @pytest.fixture(scope="module")
@@ -81,25 +80,3 @@ def test_waiting_word_round_trips_at_the_limits(out):
     for f in out["kfits"]:
         assert f["ok"] == int(f["K"] <= 1 << (31 - f["bits"])), f
     assert {f["ok"] for f in out["kfits"]} == {0, 1}
-
-
-def test_which_batches_use_fixed_slots_and_which_gather(out):
-    (c,), = [out["consts"]]
-    assert (c["by_visit"], c["tile"]) == (BY_VISIT, TILE_GATHER) and c["forms"] == "0,1,2" and c["template"] != c["first"]
-    assert len(out["rule"]) == 2 * 2 * 2 * 2 * 10 * 2 * 2 * 3 * 2
-    on = {0: 0, 1: 0, 2: 0}
-    for f in out["rule"]:
-        shared = f["share"] > 1 and not f["aa"] and not f["flat"] and f["depth"] >= 2
-        first = int(shared and not f["flags"] & (WHOLE_RECORDS | EVERY_ITERATION | NO_FIRST_BOUNCE) and f["form"] == 0 and f["mats"] <= 8 and f["K"] <= 1 << 23)
-        assert f["first"] == first, f
-        fits = f["K"] <= 1 << (31 - (f["seg_cap"] - 1).bit_length())
-        want = int(first and fits and not f["flags"] & BY_VISIT)  # false exactly when first_bounces is, the bit is set or the word does not fit
-        assert f["fixed"] == f["fixed_b"] == want, f
-        gather = 0 if not want else 1 if f["flags"] & TILE_GATHER or f["conv"] else 2
-        assert f["gather"] == gather, f
-        on[gather] += 1
-    assert min(on.values()) > 0
-    # (K = 2^18 + 1 fits beside the visit number and not beside the slot: the word alone turns the rule off there)
-    assert any(f["first"] and not f["fixed"] and not f["flags"] & BY_VISIT for f in out["rule"])
-    (fresh,), = [out["fresh"]]
-    assert fresh["fixed_slots"] == 0 and fresh["size"] == 80  # `BatchInfo b{}`: records by visit; the new word fills the struct's tail padding

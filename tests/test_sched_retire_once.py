@@ -1,5 +1,6 @@
-"""The retire-once rule of csrc/pt_sched.h without a GPU: which batches store and gather their depth-0 retirees once, and the
-map from a slot of a region to (residue, position inside the sub-region) that k_collect tells a retiree slot by.
+"""The retire-once rule of csrc/pt_sched.h without a GPU: the map from a slot of a region to (residue, position inside the
+sub-region) that k_collect tells a retiree slot by.  (Which batches store and gather their depth-0 retirees once is a rung of
+batch_form: tests/test_sched_form.py.)
 
 k_primary puts the depth-0 retirees of sub-region (q, k, rho) at its front; in a retire_once batch those slots are written and
 read in iteration 0 only.  k_collect therefore has to know, for slot i of a region, which sub-region holds it and how far in:
@@ -101,20 +102,3 @@ def test_every_slot_is_classified_once_and_the_gap_never_is_a_retiree(out):
                 if fill == 1:
                     assert g0 > 0 and is_retiree[g0 - 1]
     assert gaps > 100
-
-
-def test_which_batches_retire_once(out):
-    assert len(out["rule"]) == 6 * 2 * 2 * 4 * 5
-    on = 0
-    for f, _ in out["rule"]:
-        want = int(f["share"] > 1 and not f["aa"] and not f["flat"] and f["depth"] >= 2 and not f["flags"] & 1024)
-        assert f["once"] == f["once_b"] == want, f
-        assert f["bit"] == 1024
-        on += want
-    assert on == 3 * 3 * 3  # share 2, 25, 64 x depth 2, 3, 8 x the three flag words without bit 1024
-    # off for trace_depth 1, for jitter, for the flat lists, for primary_share <= 1 and with bit 1024, whatever else holds
-    for f, _ in out["rule"]:
-        if f["depth"] == 1 or f["aa"] or f["flat"] or f["share"] <= 1 or f["flags"] & 1024:
-            assert f["once"] == 0
-    (fresh, _), = out["fresh"]
-    assert fresh["retire_once"] == 0  # `BatchInfo b{}` (the drivers, the stage helpers): the rule is off unless the host sets it

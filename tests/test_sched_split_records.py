@@ -1,5 +1,6 @@
-"""The split-record rule of csrc/pt_sched.h without a GPU: which batches store the iteration-invariant half of a depth-1 record
-once, where that half lives, and how the specular / diffuse bit shares a word with the sample id.
+"""The split-record rule of csrc/pt_sched.h without a GPU: where the iteration-invariant half of a depth-1 record lives, and how
+the specular / diffuse bit shares a word with the sample id.  (Which batches split their records is a rung of batch_form:
+tests/test_sched_form.py.)
 
 In such a batch k_primary writes (origin, material) of a surviving pixel once, at the slot its record has in iteration 0 of the
 batch, and k_paths reads it from there for the record of every iteration: invariant_slot must send slot i of sub-list (q, k, r)
@@ -15,7 +16,6 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), "cosc_4397_pathtracing_raytracing_project_amd", "csrc")
-WHOLE_RECORDS = 4096  # PtOptions.debug_flags: whole 40-byte records in every iteration
 
 
 def _fields(tokens):
@@ -88,21 +88,3 @@ def test_kind_bit_and_sample_id_share_a_word(out):
     assert shifts == set(range(1, 31))
     largest = {f["shift"]: f["k"] for f, _ in out["kind"]}  # (the last line of a shift holds its largest k)
     assert all(k == min(256, 1 << (31 - s)) - 1 for s, k in largest.items())  # what pt_init allows: K <= 256 and K <= 2^(31 - slot_shift)
-
-
-def test_which_batches_split_their_records(out):
-    assert len(out["rule"]) == 6 * 2 * 2 * 4 * 6
-    on = 0
-    for f, _ in out["rule"]:
-        want = int(f["share"] > 1 and not f["aa"] and not f["flat"] and f["depth"] >= 2 and not f["flags"] & WHOLE_RECORDS)
-        assert f["split"] == f["split_b"] == want, f
-        assert f["bit"] == WHOLE_RECORDS
-        if not f["flags"] & (WHOLE_RECORDS | 1024):
-            assert f["split"] == f["once"]  # the conditions of retires_once, with a switch of its own
-        on += want
-    assert on == 3 * 3 * 4  # share 2, 25, 64 x depth 2, 3, 8 x the four flag words without bit 4096
-    for f, _ in out["rule"]:
-        if f["depth"] == 1 or f["aa"] or f["flat"] or f["share"] <= 1 or f["flags"] & WHOLE_RECORDS:
-            assert f["split"] == 0
-    (fresh, _), = out["fresh"]
-    assert fresh["split_records"] == 0  # `BatchInfo b{}` (the drivers, the stage helpers): whole records unless the host sets it
