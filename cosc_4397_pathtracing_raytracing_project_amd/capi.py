@@ -87,6 +87,12 @@ class PtDenoiseOptions(C.Structure):
                 ("keep_albedo", C.c_int32)]
 
 
+class PtHistoryOptions(C.Structure):
+    """Options of the reprojected sample history (include/pt_amd.h); 0 in a field = its default (cap 32, normal dot 0.9, plane
+    tolerance 0.02, reflective geoms carry nothing); a negative min_normal_dot / plane_tol switches that test off."""
+    _fields_ = [("cap", C.c_float), ("min_normal_dot", C.c_float), ("plane_tol", C.c_float), ("keep_view_dependent", C.c_int32)]
+
+
 class PtSetupTimes(C.Structure):
     """Host wall-clock times of a renderer's setup and of its last camera move, ms (include/pt_amd.h: pt_get_setup_times)."""
     _fields_ = [("tables_ms", C.c_double), ("upload_ms", C.c_double), ("buffers_ms", C.c_double), ("probe_ms", C.c_double),
@@ -313,6 +319,24 @@ def lib() -> C.CDLL:
         L.pt_selfcheck_camera_math.argtypes = [C.c_int, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
         L.pt_scene_camera.argtypes = [C.c_void_p, _cam]
         L.pt_scene_orbit_state.argtypes = [C.c_void_p, _fp, _fp, _fp]
+    if hasattr(L, "pt_history_capture"):  # absent from older A/B builds of the library (tools/build_rev.sh)
+        _hio, _cam, _u8 = C.POINTER(PtHistoryOptions), C.POINTER(PtCamera), C.POINTER(C.c_uint8)
+        _reproject = [C.c_int, C.c_int, C.c_int, _cam, _fp, _fp, _u8, C.c_int, _hio, _fp]
+        L.pt_history_capture.argtypes = [C.c_float]
+        L.pt_history_reproject.argtypes = [_hio]
+        L.pt_history_resolve.argtypes = [C.c_float, _fp]
+        L.pt_readback_history.argtypes = [_fp, _fp]
+        L.pt_history_drop.argtypes = []
+        L.pt_ctx_history_capture.argtypes = [C.c_void_p, C.c_float]
+        L.pt_ctx_history_reproject.argtypes = [C.c_void_p, _hio]
+        L.pt_ctx_history_resolve.argtypes = [C.c_void_p, C.c_float, _fp]
+        L.pt_ctx_history_resolve_device.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_void_p)]
+        L.pt_ctx_readback_history.argtypes = [C.c_void_p, _fp, _fp]
+        L.pt_ctx_history_drop.argtypes = [C.c_void_p]
+        L.pt_history_capture_host.argtypes = [C.c_int, _fp, _fp, _fp, C.c_float, _fp]
+        L.pt_history_reproject_host.argtypes = _reproject
+        L.pt_stage_history_reproject.argtypes = _reproject
+        L.pt_history_blend_host.argtypes = [C.c_int, _fp, C.c_float, _fp, _fp]
     _lib = L
     return L
 
@@ -521,6 +545,71 @@ def denoise_host(rgb_sum: np.ndarray, planes: np.ndarray, w: int, rows: int, sam
     s, p, out = _denoise_arrays(rgb_sum, planes, w, rows)
     opt = denoise_options(**opts)
     _check(lib().pt_denoise_host(int(w), int(rows), _f(s), _f(p), C.c_float(samples), C.byref(opt), _f(out)))
+    return out
+
+
+HISTORY_KEPT_PLANES = 3  # PT_HISTORY_KEPT_PLANES
+
+
+def history_options(cap: float = 0.0, min_normal_dot: float = 0.0, plane_tol: float = 0.0, keep_view_dependent: bool = False) -> PtHistoryOptions:
+    """PtHistoryOptions; 0 = the default of a field, a negative min_normal_dot / plane_tol switches its test off."""
+    return PtHistoryOptions(float(cap), float(min_normal_dot), float(plane_tol), 1 if keep_view_dependent else 0)
+
+
+def reject_geoms(scene: "Scene") -> np.ndarray:
+    """reject_geom of pt_history_reproject for a scene: uint8 [num_geoms], 1 where the geom's material reflects."""
+    geoms, mats = scene.geoms(), scene.materials()
+    return np.array([1 if mats[g.materialid].hasReflective > 0 else 0 for g in geoms], np.uint8)
+
+
+def history_capture_host(rgb_sum: np.ndarray, planes: np.ndarray, samples: float, current: Optional[np.ndarray] = None) -> np.ndarray:
+    """pt_history_capture on the host (no GPU): SUM image [n, 3], feature SUM planes [PT_FEATURE_PLANES, n, 4] and the current plane
+    [n, 4] (None: absent) in, the kept planes [PT_HISTORY_KEPT_PLANES, n, 4] out."""
+    s = np.ascontiguousarray(rgb_sum, np.float32).reshape(-1)
+    p = np.ascontiguousarray(planes, np.float32).reshape(-1)
+    n = s.size // 3
+    c = None if current is None else np.ascontiguousarray(current, np.float32).reshape(-1)
+    if s.size != 3 * n or p.size != 4 * FEATURE_PLANES * n or (c is not None and c.size != 4 * n):
+        raise PtError(f"history_capture_host: {s.size} image, {p.size} plane floats")
+    out = np.empty((HISTORY_KEPT_PLANES, n, 4), np.float32)
+    _check(lib().pt_history_capture_host(n, _f(s), _f(p), None if c is None else _f(c), C.c_float(samples), _f(out)))
+    return out
+
+
+def _history_reproject(call, kept_cam: PtCamera, kept: np.ndarray, planes: np.ndarray, reject: np.ndarray, w: int, rows: int, row0: int, **opts):
+    k = np.ascontiguousarray(kept, np.float32).reshape(-1)
+    p = np.ascontiguousarray(planes, np.float32).reshape(-1)
+    r = np.ascontiguousarray(reject, np.uint8).reshape(-1)
+    if k.size != 4 * HISTORY_KEPT_PLANES * w * rows or p.size != 4 * FEATURE_PLANES * w * rows:
+        raise PtError(f"history_reproject: {k.size} kept and {p.size} plane floats for a tile of {w}x{rows}")
+    out = np.empty((w * rows, 4), np.float32)
+    opt = history_options(**opts)
+    _check(call(int(w), int(rows), int(row0), C.byref(kept_cam), _f(k), _f(p), r.ctypes.data_as(C.POINTER(C.c_uint8)) if r.size else None, int(r.size),
+                C.byref(opt), _f(out)))
+    return out
+
+
+def history_reproject_host(kept_cam: PtCamera, kept: np.ndarray, planes: np.ndarray, reject: np.ndarray, w: int, rows: int, row0: int = 0, **opts) -> np.ndarray:
+    """pt_history_reproject on the host (no GPU): the kept camera and planes [PT_HISTORY_KEPT_PLANES, w*rows, 4], the CURRENT view's
+    feature SUM planes and reject_geom (uint8 [num_geoms]) in, the current plane [w*rows, 4] out; options: history_options."""
+    return _history_reproject(lib().pt_history_reproject_host, kept_cam, kept, planes, reject, w, rows, row0, **opts)
+
+
+def stage_history_reproject(kept_cam: PtCamera, kept: np.ndarray, planes: np.ndarray, reject: np.ndarray, w: int, rows: int, row0: int = 0, **opts) -> np.ndarray:
+    """history_reproject_host's arrays through the production kernel (pt_stage_history_reproject; a renderer must be live)."""
+    return _history_reproject(lib().pt_stage_history_reproject, kept_cam, kept, planes, reject, w, rows, row0, **opts)
+
+
+def history_blend_host(rgb_sum: np.ndarray, samples: float, current: Optional[np.ndarray] = None) -> np.ndarray:
+    """pt_history_resolve's blend on the host (no GPU): SUM image [n, 3] and the current plane [n, 4] (None: absent) in, averaged
+    radiance [n, 3] out."""
+    s = np.ascontiguousarray(rgb_sum, np.float32).reshape(-1)
+    n = s.size // 3
+    c = None if current is None else np.ascontiguousarray(current, np.float32).reshape(-1)
+    if s.size != 3 * n or (c is not None and c.size != 4 * n):
+        raise PtError(f"history_blend_host: {s.size} image floats")
+    out = np.empty((n, 3), np.float32)
+    _check(lib().pt_history_blend_host(n, _f(s), C.c_float(samples), None if c is None else _f(c), _f(out)))
     return out
 
 
@@ -815,6 +904,38 @@ class Renderer:
         out = np.empty((FEATURE_PLANES, self.n, 4), np.float32)
         _check(lib().pt_readback_features(_f(out)))
         return split_features(out)
+
+    def readback_feature_planes(self) -> np.ndarray:
+        """The feature SUM buffers of the tile as they lie, float32 [PT_FEATURE_PLANES, n, 4] (what the *_host functions take)."""
+        out = np.empty((FEATURE_PLANES, self.n, 4), np.float32)
+        _check(lib().pt_readback_features(_f(out)))
+        return out
+
+    # ---- reprojected sample history (include/pt_amd.h: pt_history_capture) ----
+    def history_capture(self, samples: float) -> None:
+        """Keeps the blend of the image (`samples` iterations) with the current history, and the first-hit surface, for the next view."""
+        _check(lib().pt_history_capture(C.c_float(samples)))
+
+    def history_reproject(self, **opts) -> None:
+        """Resamples the kept history to the current camera from the current feature sums (options: history_options)."""
+        opt = history_options(**opts)
+        _check(lib().pt_history_reproject(C.byref(opt)))
+
+    def history_resolve(self, samples: float) -> np.ndarray:
+        """The image blended with the reprojected history: averaged radiance of the tile, float32 [n, 3]."""
+        out = np.empty((self.n, 3), np.float32)
+        _check(lib().pt_history_resolve(C.c_float(samples), _f(out)))
+        return out
+
+    def readback_history(self):
+        """(kept planes [PT_HISTORY_KEPT_PLANES, n, 4], current plane [n, 4]; zeros while it is absent)."""
+        kept = np.empty((HISTORY_KEPT_PLANES, self.n, 4), np.float32)
+        cur = np.empty((self.n, 4), np.float32)
+        _check(lib().pt_readback_history(_f(kept), _f(cur)))
+        return kept, cur
+
+    def history_drop(self) -> None:
+        _check(lib().pt_history_drop())
 
     def denoise(self, samples: float, **opts) -> np.ndarray:
         """The image filtered by the edge-avoiding filter over the feature buffers (pt_denoise; options: denoise_options):

@@ -945,6 +945,7 @@ int pt_ctx_clear(PtContext* c) {
   c->adaptive = false;
   c->adaptive_rounds = 0;
   c->adaptive_last = 0;
+  c->hist_current = c->feat_fresh = false;  // the history's current plane is absent; its kept planes stay (pt_history.h)
   if (c->conv) {  // forget the curve, re-arm the capture (a supplied frame stays)
     HIP_OK(hipMemsetAsync(c->d_sse, 0xff, (size_t)PT_CONVERGENCE_CAPACITY * sizeof(double), c->stream));
     c->conv_last = 0;
@@ -1299,6 +1300,11 @@ int pt_adaptive_round_list(int iter_first, int group_iters, const int32_t* list_
   return pt_ctx_adaptive_round_list(g_default, iter_first, group_iters, list_host, m, capacity);
 }
 int pt_resolve(float* rgb_avg_host) { return pt_ctx_resolve(g_default, rgb_avg_host); }
+int pt_history_capture(float samples) { return pt_ctx_history_capture(g_default, samples); }
+int pt_history_reproject(const PtHistoryOptions* opt) { return pt_ctx_history_reproject(g_default, opt); }
+int pt_history_resolve(float samples, float* rgb_avg_host) { return pt_ctx_history_resolve(g_default, samples, rgb_avg_host); }
+int pt_readback_history(float* kept_planes, float* current_plane) { return pt_ctx_readback_history(g_default, kept_planes, current_plane); }
+int pt_history_drop(void) { return pt_ctx_history_drop(g_default); }
 int pt_set_reference(const float* rgb_avg_host) { return pt_ctx_set_reference(g_default, rgb_avg_host); }
 int pt_get_convergence(int iter_first, int iter_count, double* sse) { return pt_ctx_get_convergence(g_default, iter_first, iter_count, sse); }
 int pt_iterations_to_clean(float threshold_db, int* iteration) { return pt_ctx_iterations_to_clean(g_default, threshold_db, iteration); }

@@ -160,6 +160,13 @@ struct PtContext : PtShared {
   void* d_acnt = nullptr;          // the plane cnt: N * ptad::Cnt
   void* d_select = nullptr;        // pt_adaptive_select_bytes(N)
   float* d_resolved = nullptr;     // [N][3], output of pt_ctx_resolve_device; absent until the first resolve
+  // Reprojected sample history (pt_ctx_history_capture, csrc/pt_history.hip): all of it absent until the first capture
+  void* d_hist = nullptr;          // pt_history_state_bytes(N): the kept planes K0 K1 K2, then the current plane C
+  uint8_t* d_hist_reject = nullptr;  // one byte per geom: its material reflects (the first pt_ctx_history_reproject builds it)
+  PtCamera hist_cam{};             // the camera K is aligned to
+  bool hist_kept = false;          // K holds a capture (pt_ctx_history_drop forgets it)
+  bool hist_current = false;       // C holds a reprojection for the current camera; pt_clear and a camera move make it absent
+  bool feat_fresh = false;         // a feature pass has run since pt_init / pt_clear / the last camera move
   // Moving the camera (pt_ctx_set_camera): the camera-independent tables on the host, and the grid to rebuild (the one init kept)
   pt::CameraBase camera_base;
   pt::GridRequest grid_request;

@@ -1,0 +1,200 @@
+// pt_history.h — the reprojected sample history of include/pt_amd.h (pt_history_capture / _reproject / _resolve), ONE implementation
+// of its arithmetic.
+//
+// capture_pixel, reproject_pixel and blend_pixel below are what the HIP kernels (pt_history.hip) and the host loops (exported as
+// pt_history_*_host) both run, so the two cannot disagree; tests/history_ref.py restates them in numpy.  Every float operation is a
+// separate IEEE operation in the order pt_amd.h states (`#pragma clang fp contract(off)` in every body, correctly rounded division,
+// denormals kept), so the planes do not depend on the arithmetic mode of the build or on the side they are computed on.  Plain C++
+// apart from PT_HD.
+//
+// Out of scope (pt_amd.h says the same): pt_group_* (a context's interleaved rows cannot look up their neighbours), feeding the
+// history into the noise estimate, the filters or adaptive sampling, motion of anything but the camera, and correcting the smoothing
+// the bilinear lookup adds — the carried image is a biased estimator.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/pt_amd.h"
+#include "pt_portable_math.h"
+
+namespace pthi {
+
+struct alignas(16) V4 {  // the device's planes: one 16-byte load or store per pixel and plane
+  float x, y, z, w;
+};
+struct F4 {  // a caller's host array of floats promises no more than float alignment
+  float x, y, z, w;
+};
+constexpr int kKeptPlanes = PT_HISTORY_KEPT_PLANES;  // K0 colour | weight, K1 position | id, K2 normal | 0
+constexpr int kPlanes = kKeptPlanes + 1;             // ... and the current plane C
+static_assert(kPlanes * sizeof(V4) == 64, "pt_amd.h documents 64 bytes of state per pixel");
+constexpr float kMinWeight = 0.015625f;  // a lookup with less bilinear weight than 1/64 left carries nothing
+
+// PtHistoryOptions with the defaults filled in.  A test that is switched off keeps its flag, not a sentinel value, so that the
+// comparison it would make is not made at all.
+struct Params {
+  float cap, min_dot, plane_tol;
+  int use_dot, use_plane, keep_view_dependent;
+};
+// 0 = the default in every field, NULL = all defaults; the message of a refusal, or nullptr.
+inline const char* resolve(const PtHistoryOptions* opt, Params* out) {
+  PtHistoryOptions o{};
+  if (opt) o = *opt;
+  if (!(o.cap - o.cap == 0.0f) || !(o.min_normal_dot - o.min_normal_dot == 0.0f) || !(o.plane_tol - o.plane_tol == 0.0f)) return "an option is not finite";
+  if (o.cap == 0.0f) o.cap = 32.0f;
+  if (!(o.cap > 0.0f)) return "cap must be positive";
+  if (o.min_normal_dot == 0.0f) o.min_normal_dot = 0.9f;
+  if (o.plane_tol == 0.0f) o.plane_tol = 0.02f;
+  if (o.keep_view_dependent != 0 && o.keep_view_dependent != 1) return "keep_view_dependent is 0 or 1";
+  *out = Params{o.cap, o.min_normal_dot, o.plane_tol, o.min_normal_dot < 0.0f ? 0 : 1, o.plane_tol < 0.0f ? 0 : 1, o.keep_view_dependent};
+  return nullptr;
+}
+
+// The kept camera as the lookup reads it, and the tile it looks into: W x R pixels starting at frame row row0.
+struct View {
+  float pos[3], view[3], up[3], right[3];
+  float plx, ply, hw, hh, wmax, hmax;  // wmax = (float)(W - 1), hmax = (float)(H - 1)
+  int W, R, row0;
+};
+inline View make_view(const PtCamera& cam, int rows, int row0) {
+#pragma clang fp contract(off)
+  View v{};
+  for (int k = 0; k < 3; ++k) v.pos[k] = cam.position[k], v.view[k] = cam.view[k], v.up[k] = cam.up[k], v.right[k] = cam.right[k];
+  v.plx = cam.pixelLength[0], v.ply = cam.pixelLength[1];
+  v.hw = (float)cam.resolution[0] * 0.5f, v.hh = (float)cam.resolution[1] * 0.5f;
+  v.wmax = (float)(cam.resolution[0] - 1), v.hmax = (float)(cam.resolution[1] - 1);
+  v.W = cam.resolution[0], v.R = rows, v.row0 = row0;
+  return v;
+}
+
+PT_HD float dot3(float ax, float ay, float az, float bx, float by, float bz) {
+#pragma clang fp contract(off)
+  return (ax * bx + ay * by) + az * bz;
+}
+PT_HD int32_t float_bits(float f) {
+  int32_t i;
+  __builtin_memcpy(&i, &f, sizeof i);
+  return i;
+}
+PT_HD float bits_float(int32_t i) {
+  float f;
+  __builtin_memcpy(&f, &i, sizeof f);
+  return f;
+}
+
+// What pt_denoise's prepare makes of a pixel's feature sums: hit, normal, position; and the object id (0 on a miss).
+struct Surface {
+  bool hit;
+  float nx, ny, nz, px, py, pz;
+  int32_t id;
+};
+template <typename P4>
+PT_HD Surface surface(size_t i, size_t npix, const P4* feat) {
+#pragma clang fp contract(off)
+  const P4 s0 = feat[i], s1 = feat[npix + i], s2 = feat[2 * npix + i];
+  Surface s{s1.w > 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0};
+  if (s.hit) {
+    s.nx = s0.x / s1.w, s.ny = s0.y / s1.w, s.nz = s0.z / s1.w;
+    s.px = s2.x / s1.w, s.py = s2.y / s1.w, s.pz = s2.z / s1.w;
+    s.id = float_bits(s2.w);
+  }
+  return s;
+}
+
+// The blend of one component: the SUM over `samples` new samples with the history's h over Th samples.  C absent: h = Th = +0.
+PT_HD float blend_component(float S, float samples, float h, float Th) {
+#pragma clang fp contract(off)
+  const float m = h * Th;
+  const float a = S + m;
+  const float d = samples + Th;
+  return a / d;
+}
+
+// Pixel i of a tile of npix pixels: rgb_avg[3 i ..] = the blend.  C: the current plane, or nullptr (absent).
+template <typename P4>
+PT_HD void blend_pixel(size_t i, const float* S, float samples, const P4* C, float* rgb_avg) {
+  const P4 c = C ? C[i] : P4{0.0f, 0.0f, 0.0f, 0.0f};
+  rgb_avg[3 * i] = blend_component(S[3 * i], samples, c.x, c.w);
+  rgb_avg[3 * i + 1] = blend_component(S[3 * i + 1], samples, c.y, c.w);
+  rgb_avg[3 * i + 2] = blend_component(S[3 * i + 2], samples, c.z, c.w);
+}
+
+// Pixel i: the kept planes K (kKeptPlanes planes of npix) from the SUM image, the feature sums and the current plane (or nullptr).
+template <typename P4>
+PT_HD void capture_pixel(size_t i, size_t npix, const float* S, const P4* feat, const P4* C, float samples, P4* K) {
+#pragma clang fp contract(off)
+  const Surface s = surface(i, npix, feat);
+  const P4 c = C ? C[i] : P4{0.0f, 0.0f, 0.0f, 0.0f};
+  K[i] = P4{blend_component(S[3 * i], samples, c.x, c.w), blend_component(S[3 * i + 1], samples, c.y, c.w),
+            blend_component(S[3 * i + 2], samples, c.z, c.w), samples + c.w};
+  K[npix + i] = P4{s.px, s.py, s.pz, bits_float(s.id)};
+  K[2 * npix + i] = P4{s.nx, s.ny, s.nz, 0.0f};
+}
+
+// Tile pixel i = (x, r): the history K as seen through the kept camera, resampled at this pixel's first hit.  reject: one byte per
+// geom (num_geoms of them), read unless keep_view_dependent; an id outside 1 .. num_geoms is rejected like a listed geom.  A gather:
+// of each tap K1 is read first, then K2, and K0 only when the tap passed.
+template <typename P4>
+PT_HD P4 reproject_pixel(size_t i, const View& v, const P4* K, const P4* feat, const uint8_t* reject, int32_t num_geoms, const Params& P) {
+#pragma clang fp contract(off)
+  const size_t npix = (size_t)v.W * v.R;
+  const P4 zero{0.0f, 0.0f, 0.0f, 0.0f};
+  const Surface s = surface(i, npix, feat);
+  if (!s.hit) return zero;
+  if (!P.keep_view_dependent && (s.id < 1 || s.id > num_geoms || reject[s.id - 1])) return zero;
+  const float vx = s.px - v.pos[0], vy = s.py - v.pos[1], vz = s.pz - v.pos[2];
+  const float dz = dot3(vx, vy, vz, v.view[0], v.view[1], v.view[2]);
+  if (!(dz > 0.0f)) return zero;
+  const float sx = v.hw - dot3(vx, vy, vz, v.right[0], v.right[1], v.right[2]) / (dz * v.plx);
+  const float sy = v.hh - dot3(vx, vy, vz, v.up[0], v.up[1], v.up[2]) / (dz * v.ply);
+  const float fx = __builtin_floorf(sx), fy = __builtin_floorf(sy);
+  if (!(fx >= -1.0f && fx <= v.wmax && fy >= -1.0f && fy <= v.hmax)) return zero;
+  const float ax = sx - fx, ay = sy - fy;
+  const int ix = (int)fx, iy = (int)fy - v.row0;  // in range: the comparisons above were made in float
+  const float tol = P.plane_tol * dz;
+  float accx = 0.0f, accy = 0.0f, accz = 0.0f, tacc = 0.0f, wsum = 0.0f;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int qr = iy + j;
+    if (qr < 0 || qr >= v.R) continue;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const int qx = ix + t;
+      if (qx < 0 || qx >= v.W) continue;
+      const size_t q = (size_t)qr * v.W + qx;
+      const P4 k1 = K[npix + q];
+      if (float_bits(k1.w) != s.id) continue;
+      const P4 k2 = K[2 * npix + q];
+      if (P.use_dot && dot3(s.nx, s.ny, s.nz, k2.x, k2.y, k2.z) < P.min_dot) continue;
+      if (P.use_plane) {
+        const float e = dot3(s.nx, s.ny, s.nz, k1.x - s.px, k1.y - s.py, k1.z - s.pz);
+        if ((e < 0.0f ? -e : e) > tol) continue;
+      }
+      const P4 k0 = K[q];
+      if (!(k0.w > 0.0f)) continue;
+      const float b = (t ? ax : 1.0f - ax) * (j ? ay : 1.0f - ay);
+      accx = accx + b * k0.x, accy = accy + b * k0.y, accz = accz + b * k0.z;
+      tacc = tacc + b * k0.w;
+      wsum = wsum + b;
+    }
+  }
+  if (!(wsum >= kMinWeight)) return zero;
+  const float tw = tacc / wsum;
+  return P4{accx / wsum, accy / wsum, accz / wsum, tw < P.cap ? tw : P.cap};
+}
+
+// The whole tile on the host.
+inline void capture_host(size_t npix, const float* S, const float* feat, const float* C, float samples, float* K) {
+  for (size_t i = 0; i < npix; ++i)
+    capture_pixel(i, npix, S, reinterpret_cast<const F4*>(feat), reinterpret_cast<const F4*>(C), samples, reinterpret_cast<F4*>(K));
+}
+inline void reproject_host(const View& v, const float* K, const float* feat, const uint8_t* reject, int32_t num_geoms, const Params& P, float* C) {
+  const size_t npix = (size_t)v.W * v.R;
+  F4* out = reinterpret_cast<F4*>(C);
+  for (size_t i = 0; i < npix; ++i) out[i] = reproject_pixel(i, v, reinterpret_cast<const F4*>(K), reinterpret_cast<const F4*>(feat), reject, num_geoms, P);
+}
+inline void blend_host(size_t npix, const float* S, float samples, const float* C, float* rgb_avg) {
+  for (size_t i = 0; i < npix; ++i) blend_pixel(i, S, samples, reinterpret_cast<const F4*>(C), rgb_avg);
+}
+
+}  // namespace pthi

@@ -90,3 +90,24 @@ int pt_group_partition_launch(hipStream_t stream, int w, int n, const int32_t* l
 int pt_group_offsets_launch(hipStream_t stream, const int32_t* list_dev, int m, int stripe, int gap, int32_t* offsets_dev);
 // what the host and stage forms of the partition refuse
 int pt_group_partition_check(const char* who, int w, int h, int n, const int32_t* list, int m, const int32_t* parts, const int32_t* counts);
+
+// The reprojected sample history (pt_history.hip), on raw device pointers and a stream; everything asynchronous, nothing allocated.
+// state: pt_history_state_bytes(pixels) bytes, the kept planes K0 K1 K2 and the current plane C, `pixels` float4 each.  current_dev may
+// be nullptr in the capture and the blend: C absent, all zero.  pt_history_reproject_launch: v = pthi::make_view(kept camera, rows, row0);
+// reject_dev one byte per geom.  pt_history_check_samples / _resolve_options / _reproject_check: the refusals under the name `who`.
+struct PtCamera;
+struct PtHistoryOptions;
+namespace pthi {
+struct Params;
+struct View;
+}
+inline size_t pt_history_state_bytes(size_t pixels) { return 64 * pixels; }
+int pt_history_check_samples(const char* who, float samples);
+int pt_history_resolve_options(const char* who, const PtHistoryOptions* opt, pthi::Params* P);
+int pt_history_reproject_check(const char* who, int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
+                               const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, const float* current_plane, pthi::Params* P);
+int pt_history_capture_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, const float* planes_dev, const void* current_dev, float samples,
+                              void* kept_dev);
+int pt_history_reproject_launch(hipStream_t stream, const pthi::View& v, const void* kept_dev, const float* planes_dev, const uint8_t* reject_dev,
+                                int num_geoms, const pthi::Params& P, void* current_dev);
+int pt_history_blend_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, float samples, const void* current_dev, float* rgb_avg_dev);

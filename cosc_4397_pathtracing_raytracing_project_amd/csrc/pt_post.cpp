@@ -1,12 +1,13 @@
 // pt_post.cpp — what reads or extends a rendered image, on a context (pt_context.h): the first-hit feature buffers, the two
 // edge-avoiding filters, the noise estimate and render-until, adaptive sampling with its worker context, and resolve.  The kernels
-// are pt_features.inc (through KernelApi), pt_denoise.hip, pt_noise.hip, pt_adaptive.hip and (a striped tile's list) pt_group_select.hip; this file holds their host side: what
+// are pt_features.inc (through KernelApi), pt_denoise.hip, pt_noise.hip, pt_adaptive.hip, pt_history.hip and (a striped tile's list) pt_group_select.hip; this file holds their host side: what
 // an entry point refuses, the buffers that exist from the first use on, and the launches.
 #include <cmath>
 
 #include "pt_adaptive.h"
 #include "pt_context.h"
 #include "pt_denoise.h"
+#include "pt_history.h"
 #include "pt_noise.h"
 #include "pt_sched.h"
 
@@ -34,6 +35,7 @@ int pt_ctx_render_features(PtContext* c, int iter_first, int iter_count) {
                              g.num_cus * std::min(g.cap_bpc, g.k->resident_blocks_per_cu(ptk::kFeatures, sc)));
   g.k->features(g.stream, g.grid_features, sc, g.dcam, tile_batch(g, iter_first, iter_count), g.d_feat);
   HIP_OK(hipGetLastError());
+  g.feat_fresh = true;
   return 0;
 }
 
@@ -480,6 +482,106 @@ int pt_ctx_resolve_device(PtContext* c, const float** rgb_dev) {
 }
 int pt_ctx_resolve(PtContext* c, float* rgb_avg_host) {
   return copy_out(c, "pt_resolve", rgb_avg_host, 3, [&](const float** d) { return pt_ctx_resolve_device(c, d); });
+}
+
+// ---- reprojected sample history (csrc/pt_history.hip) ---------------------------------------------------------------------
+// What the three entry points refuse first, in their order: a failed context, a tile that is not whole rows, the adaptive state.
+static int history_admit(const Ctx& g, const char* who) { return admit(g, who, kNotFailed) || admit(g, who, kWholeRows) || admit(g, who, kUniform) ? -1 : 0; }
+static pthi::V4* history_plane(const Ctx& g, int plane) { return static_cast<pthi::V4*>(g.d_hist) + (size_t)plane * g.N; }
+static const char kNoFeatures[] = "%s: no feature pass has been rendered since the last pt_clear or camera move (pt_render_features)";
+
+int pt_ctx_history_capture(PtContext* c, float samples) {
+  if (need(c, "pt_history_capture")) return -1;
+  Ctx& g = *c;
+  if (history_admit(g, "pt_history_capture")) return -1;
+  if (!g.d_feat || !g.feat_fresh) return pt_fail(kNoFeatures, "pt_history_capture");
+  if (pt_history_check_samples("pt_history_capture", samples)) return -1;
+  HIP_OK(hipSetDevice(g.device));
+  if (ensure(g, g.d_hist, pt_history_state_bytes((size_t)g.N), Zero::on_stream)) return -1;  // the first capture of the context
+  if (pt_history_capture_launch(g.stream, g.N, g.d_image, reinterpret_cast<const float*>(g.d_feat), g.hist_current ? history_plane(g, pthi::kKeptPlanes) : nullptr,
+                                samples, g.d_hist))
+    return -1;
+  g.hist_cam = g.cam;
+  g.hist_kept = true;
+  return 0;
+}
+
+// reject_geom of pt_amd.h from the tables the renderer holds: the geoms' material ids (host) and the materials (device).  Blocking;
+// once per context.
+static int history_reject_table(Ctx& g) {
+  if (g.d_hist_reject) return 0;
+  std::vector<ptd::Mat> mats((size_t)std::max(g.scene.num_mats, 0));
+  if (!mats.empty()) HIP_OK(hipMemcpy(mats.data(), g.scene.mats, mats.size() * sizeof(ptd::Mat), hipMemcpyDeviceToHost));
+  const std::vector<PtGeom>& geoms = g.camera_base.geoms;
+  std::vector<uint8_t> reject(std::max<size_t>(geoms.size(), 1), 0);
+  for (size_t i = 0; i < geoms.size(); ++i) {
+    const int32_t m = geoms[i].materialid;
+    reject[i] = m >= 0 && (size_t)m < mats.size() && mats[(size_t)m].reflective > 0.0f ? 1 : 0;
+  }
+  if (ensure(g, g.d_hist_reject, reject.size())) return -1;
+  HIP_OK(hipMemcpy(g.d_hist_reject, reject.data(), reject.size(), hipMemcpyHostToDevice));
+  return 0;
+}
+
+int pt_ctx_history_reproject(PtContext* c, const PtHistoryOptions* opt) {
+  if (need(c, "pt_history_reproject")) return -1;
+  Ctx& g = *c;
+  if (history_admit(g, "pt_history_reproject")) return -1;
+  if (!g.d_hist || !g.hist_kept) return pt_fail("pt_history_reproject: nothing has been captured (pt_history_capture)");
+  if (!g.d_feat || !g.feat_fresh) return pt_fail(kNoFeatures, "pt_history_reproject");
+  pthi::Params P{};
+  if (pt_history_resolve_options("pt_history_reproject", opt, &P)) return -1;
+  HIP_OK(hipSetDevice(g.device));
+  if (history_reject_table(g)) return -1;
+  const int W = g.cam.resolution[0];
+  const pthi::View v = pthi::make_view(g.hist_cam, g.N / W, g.pixel_begin / W);
+  if (pt_history_reproject_launch(g.stream, v, g.d_hist, reinterpret_cast<const float*>(g.d_feat), g.d_hist_reject, (int)g.camera_base.geoms.size(), P,
+                                  history_plane(g, pthi::kKeptPlanes)))
+    return -1;
+  g.hist_current = true;
+  return 0;
+}
+
+int pt_ctx_history_resolve_device(PtContext* c, float samples, const float** rgb_dev) {
+  if (need(c, "pt_history_resolve")) return -1;
+  Ctx& g = *c;
+  if (history_admit(g, "pt_history_resolve")) return -1;
+  if (pt_history_check_samples("pt_history_resolve", samples)) return -1;
+  if (!rgb_dev) return pt_fail("pt_history_resolve: null buffer");
+  HIP_OK(hipSetDevice(g.device));
+  if (ensure(g, g.d_resolved, 3 * (size_t)g.N * sizeof(float))) return -1;
+  if (pt_history_blend_launch(g.stream, g.N, g.d_image, samples, g.hist_current ? history_plane(g, pthi::kKeptPlanes) : nullptr, g.d_resolved)) return -1;
+  *rgb_dev = g.d_resolved;
+  return 0;
+}
+int pt_ctx_history_resolve(PtContext* c, float samples, float* rgb_avg_host) {
+  if (need(c, "pt_history_resolve")) return -1;
+  if (history_admit(*c, "pt_history_resolve") || pt_history_check_samples("pt_history_resolve", samples)) return -1;  // (before the null buffer)
+  return copy_out(c, "pt_history_resolve", rgb_avg_host, 3, [&](const float** d) { return pt_ctx_history_resolve_device(c, samples, d); });
+}
+
+int pt_ctx_readback_history(PtContext* c, float* kept_planes, float* current_plane) {
+  if (need(c, "pt_readback_history")) return -1;
+  Ctx& g = *c;
+  if (!g.d_hist) return pt_fail("pt_readback_history: nothing has been captured (pt_history_capture)");
+  HIP_OK(hipSetDevice(g.device));
+  const size_t plane = (size_t)g.N * sizeof(pthi::V4);
+  if (kept_planes) HIP_OK(hipMemcpyAsync(kept_planes, g.d_hist, pthi::kKeptPlanes * plane, hipMemcpyDeviceToHost, g.stream));
+  if (current_plane && g.hist_current) HIP_OK(hipMemcpyAsync(current_plane, history_plane(g, pthi::kKeptPlanes), plane, hipMemcpyDeviceToHost, g.stream));
+  if (pt_ctx_sync(c)) return -1;
+  if (current_plane && !g.hist_current) std::fill(current_plane, current_plane + 4 * (size_t)g.N, 0.0f);
+  return 0;
+}
+
+int pt_ctx_history_drop(PtContext* c) {
+  if (need(c, "pt_history_drop")) return -1;
+  Ctx& g = *c;
+  if (g.d_hist) {  // forgotten, not freed: a readback sees zeros, a reprojection has nothing to read
+    HIP_OK(hipSetDevice(g.device));
+    HIP_OK(hipMemsetAsync(g.d_hist, 0, pt_history_state_bytes((size_t)g.N), g.stream));
+  }
+  g.hist_kept = g.hist_current = false;
+  return 0;
 }
 
 }  // extern "C"

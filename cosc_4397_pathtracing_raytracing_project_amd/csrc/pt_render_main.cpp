@@ -3,7 +3,7 @@
 // state.iterations iterations, write the PNG saveImage() would write.  Flags exist only because
 // the reference takes resolution, iteration count and depth from the scene file (scene.cpp:103-114).
 //
-//   pt_render SCENE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] [--orbit N [--device-tables]]
+//   pt_render SCENE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] [--orbit N [--device-tables] [--reproject [--history-cap C]]]
 //                       [--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa]
 //                       [--preview N] [--convergence N | --reference FILE.pfm] [--clean-db X] [--features]
 //                       [--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]]
@@ -60,6 +60,11 @@
 // times once and per frame `orbit: frame f: camera x y z, set_camera a ms, render b ms`.  --device-tables (with --orbit): every move
 // passes PT_SET_CAMERA_DEVICE_TABLES (pt_set_camera_ex: the camera-dependent tables are rebuilt on the device, the same images), and the
 // frame's line ends `, tables a ms, rearm b ms (device|host tables)` from pt_get_set_camera_times.
+// --reproject (with --orbit, excludes --gpus / --devices): the image is carried from view to view (pt_history_*).  After a frame's render
+// comes pt_render_features(1, 1); from frame 1 on pt_history_reproject; pt_history_resolve, written next to the raw frame as
+// <base>.orbit<fff>.reprojected.png (.pfm with --pfm); pt_history_capture; then the move.  Frame f renders iterations f * spp + 1 ..
+// (f + 1) * spp instead of 1 .. spp (printed once).  --history-cap C: PtHistoryOptions.cap (default 32).  Prints per frame
+// `history: frame f: <valid> of <pixels> pixels carried, mean weight <x>`.
 // Output name: PREFIX.<spp>samp.png, or with --stamp the reference's own
 // <FILE>.<UTC start time>.<spp>samp.png (main.cpp:99-102).
 #include <hip/hip_runtime.h>
@@ -81,7 +86,7 @@
 int main(int argc, char** argv) {
   if (argc < 2) {
     std::printf("Usage: %s SCENEFILE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] "
-                "[--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa] [--orbit N [--device-tables]] [--preview N] "
+                "[--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa] [--orbit N [--device-tables] [--reproject [--history-cap C]]] [--preview N] "
                 "[--convergence N | --reference FILE.pfm] [--clean-db X] [--features] "
                 "[--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]] [--denoise-guided] [--until-db X [--until-group G] [--adaptive F [--denoise-adaptive]]] "
                 "[--adaptive-threshold E [--adaptive-cap F] [--adaptive-min-pixels P] [--until-group G] [--denoise-adaptive]]\n", argv[0]);
@@ -93,6 +98,9 @@ int main(int argc, char** argv) {
   PtDenoiseOptions dn_opt{};
   int convergence = 0, until_group = 0, orbit = 0;  // orbit > 0: --orbit N
   bool device_tables = false;                       // --device-tables
+  bool reproject = false;                           // --reproject
+  float history_cap = 0.0f;                         // --history-cap C (0: the default)
+  bool history_cap_given = false;
   bool until = false, until_group_given = false;
   float clean_db = 35.0f, until_db = 0.0f, adaptive = 0.0f;  // adaptive > 0: --adaptive F
   float threshold = 0.0f, threshold_cap = 0.25f;           // --adaptive-threshold E, --adaptive-cap F
@@ -116,6 +124,15 @@ int main(int argc, char** argv) {
       orbit = (int)v;
     }
     else if (!std::strcmp(argv[i], "--device-tables")) device_tables = true;
+    else if (!std::strcmp(argv[i], "--reproject")) reproject = true;
+    else if (!std::strcmp(argv[i], "--history-cap") && i + 1 < argc) {
+      history_cap = (float)std::atof(argv[++i]);
+      history_cap_given = true;
+      if (!std::isfinite(history_cap) || !(history_cap > 0.0f)) {
+        std::fprintf(stderr, "--history-cap wants the most samples a carried colour counts for, a positive number\n");
+        return 1;
+      }
+    }
     else if (!std::strcmp(argv[i], "--convergence") && i + 1 < argc) {
       convergence = std::atoi(argv[++i]);
       if (convergence <= 0) {
@@ -290,7 +307,15 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--device-tables goes with --orbit N (it says how the camera moves rebuild the scene tables)\n");
     return 1;
   }
-  if (orbit > 0) {  // a plain render per frame: what works on the image of one view is not carried from view to view
+  if ((reproject && orbit <= 0) || (history_cap_given && !reproject)) {
+    std::fprintf(stderr, "--reproject goes with --orbit N (it carries the image from view to view), --history-cap C with --reproject\n");
+    return 1;
+  }
+  if (reproject && (gpus >= 0 || !device_list.empty())) {
+    std::fprintf(stderr, "--reproject excludes --gpus / --devices: a context's interleaved rows cannot look up their neighbours in the previous view\n");
+    return 1;
+  }
+  if (orbit > 0) {  // a plain render per frame: what works on the image of one view is not carried from view to view (but --reproject)
     const struct {
       bool given;
       const char* name;
@@ -424,6 +449,20 @@ int main(int argc, char** argv) {
     }
     std::printf("setup: tables %.3f ms, upload %.3f ms, buffers %.3f ms, probe %.3f ms\n", st.tables_ms, st.upload_ms, st.buffers_ms, st.probe_ms);
     scene->state.image.resize((size_t)W * H * 3);
+    // --reproject: the history of the views before (pt_history_*).  The RNG is keyed by (iteration, pixel): the same iteration numbers
+    // after a small move would repeat almost the same paths, and the history would add nothing — every frame gets numbers of its own.
+    std::vector<float> carried, current;
+    PtHistoryOptions hopt{};
+    hopt.cap = history_cap;
+    if (reproject) {
+      if ((int64_t)orbit * iters > INT32_MAX) {
+        std::fprintf(stderr, "--reproject: %d frames of %d iterations run out of iteration numbers\n", orbit, iters);
+        return 1;
+      }
+      carried.resize((size_t)W * H * 3);
+      current.resize((size_t)W * H * 4);
+      std::printf("history: frame f renders iterations f * %d + 1 .. (f + 1) * %d, not 1 .. %d: repeated iteration numbers would repeat the paths\n", iters, iters, iters);
+    }
     const float step = (float)(2.0 * 3.14159265358979323846 / orbit);
     for (int f = 0; f < orbit; ++f) {
       double move_ms = 0.0;
@@ -444,7 +483,9 @@ int main(int argc, char** argv) {
         }
       }
       const auto t0 = std::chrono::high_resolution_clock::now();
-      if (grp ? (pt_group_render(grp, 1, iters) || pt_group_gather(grp, scene->state.image.data())) : (pt_render(1, iters) || pt_readback(scene->state.image.data()))) {
+      const int iter_first = reproject ? f * iters + 1 : 1;
+      if (grp ? (pt_group_render(grp, 1, iters) || pt_group_gather(grp, scene->state.image.data()))
+              : (pt_render(iter_first, iters) || pt_readback(scene->state.image.data()))) {
         std::fprintf(stderr, "HIP error (pt_render): %s\n", pt_last_error());
         return EXIT_FAILURE;
       }
@@ -459,6 +500,20 @@ int main(int argc, char** argv) {
       if (pt_save_png((frame + ".png").c_str(), scene->state.image.data(), W, H, (float)iters) == 0) std::printf("Saved %s.png.\n", frame.c_str());
       if (pfm && pt_save_pfm((frame + ".pfm").c_str(), scene->state.image.data(), W, H, (float)iters) == 0) std::printf("Saved %s.pfm.\n", frame.c_str());
       if (hdr && pt_save_hdr((frame + ".hdr").c_str(), scene->state.image.data(), W, H, (float)iters) == 0) std::printf("Saved %s.hdr.\n", frame.c_str());
+      if (reproject) {  // the view's first hits, the history looked up from them, the blend written, the blend kept for the next view
+        if (pt_render_features(1, 1) || (f > 0 && pt_history_reproject(&hopt)) || pt_history_resolve((float)iters, carried.data()) ||
+            pt_history_capture((float)iters) || pt_readback_history(nullptr, current.data())) {
+          std::fprintf(stderr, "HIP error (pt_history): %s\n", pt_last_error());
+          return EXIT_FAILURE;
+        }
+        size_t valid = 0;
+        double weight = 0.0;
+        for (size_t p = 0; p < (size_t)W * H; ++p)
+          if (current[4 * p + 3] > 0.0f) valid += 1, weight += (double)current[4 * p + 3];
+        std::printf("history: frame %d: %zu of %zu pixels carried, mean weight %.3f\n", f, valid, (size_t)W * H, valid ? weight / (double)valid : 0.0);
+        if (pt_save_png((frame + ".reprojected.png").c_str(), carried.data(), W, H, 1.0f) == 0) std::printf("Saved %s.reprojected.png.\n", frame.c_str());
+        if (pfm && pt_save_pfm((frame + ".reprojected.pfm").c_str(), carried.data(), W, H, 1.0f) == 0) std::printf("Saved %s.reprojected.pfm.\n", frame.c_str());
+      }
     }
     if (grp) pt_group_destroy(grp);
     else pt_free();

@@ -7,6 +7,7 @@
 #include "pt_camera_tables_device.h"
 #include "pt_context.h"
 #include "pt_denoise.h"
+#include "pt_history.h"
 #include "pt_scene.h"
 
 using namespace ptc;
@@ -322,6 +323,32 @@ int pt_stage_denoise_adaptive(int w, int rows, const float* rgb_sum, const float
                       [&](const float* img, const float* pl, const float* nz, void* ws, const float** out) {
                         return pt_denoise_adaptive_launch(g.stream, w, rows, img, pl, nz, d_counts, 0, 0, P, ws, out);
                       });
+}
+
+// The reprojection's kernel on caller-supplied host arrays (pt_history_reproject_host's arguments)
+int pt_stage_history_reproject(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
+                               const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, float* current_plane) {
+  if (need(default_context(), "pt_stage_history_reproject")) return -1;
+  Ctx& g = *default_context();
+  pthi::Params P{};
+  if (pt_history_reproject_check("pt_stage_history_reproject", w, rows, row0, kept_cam, kept_planes, feature_planes, reject_geom, num_geoms, opt, current_plane, &P))
+    return -1;
+  if (rows >= 32768) return pt_fail("pt_stage_history_reproject: a tile of %d x %d pixels is not supported", w, rows);
+  HIP_OK(hipSetDevice(g.device));
+  Scratch sc;
+  const size_t n = (size_t)w * rows;
+  float *d_kept = nullptr, *d_feat = nullptr;
+  uint8_t* d_reject = nullptr;
+  float* d_cur = sc.get<float>(4 * n);
+  if (!d_cur) return pt_fail("pt_stage_history_reproject: out of device memory");
+  if (device_copy(sc, "pt_stage_history_reproject", kept_planes, 4 * PT_HISTORY_KEPT_PLANES * n, &d_kept)) return -1;
+  if (device_copy(sc, "pt_stage_history_reproject", feature_planes, 4 * PT_FEATURE_PLANES * n, &d_feat)) return -1;
+  if (!P.keep_view_dependent && num_geoms > 0 && device_copy(sc, "pt_stage_history_reproject", reject_geom, (size_t)num_geoms, &d_reject)) return -1;
+  HIP_OK(hipMemset(d_cur, 0xff, 4 * n * sizeof(float)));  // a pixel nobody wrote shows as NaNs
+  if (pt_history_reproject_launch(g.stream, pthi::make_view(*kept_cam, rows, row0), d_kept, d_feat, d_reject, num_geoms, P, d_cur)) return -1;
+  HIP_OK(hipStreamSynchronize(g.stream));
+  HIP_OK(hipMemcpy(current_plane, d_cur, 4 * n * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
 }
 
 // The selection's kernels on caller-supplied host arrays (pt_adaptive_select_host's arguments)

@@ -740,6 +740,72 @@ int pt_denoise_adaptive_host(int w, int rows, const float* rgb_sum, const float*
 int pt_denoise_adaptive_variance_host(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, const int32_t* counts,
                                       const PtDenoiseOptions* opt, float* var_raw, float* var_0);
 
+/* ---- reprojected sample history: carry the image across a camera move.  pt_set_camera restores the state of a new renderer, so
+ * every view of a moving camera starts at 0 spp; this unit keeps the previous view's blended image with its first-hit surface, looks
+ * it up again from the new view's first hits, and blends it with the new samples.  Streaming kernels of their own
+ * (csrc/pt_history.hip); pt_render, pt_clear, pt_set_camera and their kernels know nothing of it.  Specified to the bit like the
+ * filters above: float32 throughout, every operation a separate IEEE operation in the order written (no FMA contraction, correctly
+ * rounded division, denormals kept), dot products (a.x*b.x + a.y*b.y) + a.z*b.z, so the planes are the same in all three PT_ARITH_*
+ * builds, on the host (pt_history_*_host) and on the device.
+ * State, 64 bytes per tile pixel, allocated and zeroed by the first pt_history_capture and part of PtStats.device_bytes from then on
+ * (a renderer that never calls these functions allocates and launches nothing for them):
+ *   kept planes, PT_HISTORY_KEPT_PLANES planes of pixel_count float4, aligned to the camera of the last capture (kept on the host):
+ *     K0 = blended colour xyz | weight Tk (a float sample count)      K1 = first-hit position xyz | object id (int32 bit pattern)
+ *     K2 = first-hit normal xyz | +0
+ *   current plane C = {h.xyz, Th}: the history resampled to the renderer's CURRENT camera; "absent" counts as all zero.
+ * pt_history_reproject also keeps one byte per geom, reject_geom[g] = materials[geoms[g].materialid].hasReflective > 0 (a mirror's
+ * radiance follows the view and must not be carried), allocated by the first call and counted like any buffer.
+ * The tile must be whole contiguous rows (W x R), starting at frame row row0 = pixel_begin / W; taps outside the tile's rows are outside.
+ * Lifetime: K and the kept camera survive pt_clear and pt_set_camera[_ex]; C becomes absent on both; pt_history_drop forgets K and C
+ * and keeps the memory.
+ *   blend, per component k:  m = h_k * Th;  a = S_k + m;  d = samples + Th;  c_k = a / d      (C absent: S_k / samples)
+ *   capture  hit = s1.w > 0;  hit: n = s0.xyz / s1.w, p = s2.xyz / s1.w, id = bits(s2.w);  miss: n = p = 0, id = 0   (pt_denoise's prepare)
+ *            K0.xyz = blend, K0.w = samples + Th;  K1 = p | id;  K2 = n | +0;  kept camera = the renderer's
+ *   reproject  tile pixel (x, r), n p id from the CURRENT feature sums as above, cam = the kept camera, hw = (float)W * 0.5f,
+ *            hh = (float)H * 0.5f — the inverse of generateRayFromCamera (pathtrace.cu:270-286) for the orthonormal view / up / right of
+ *            pt_scene_load.  "Rejected" = C := 0.
+ *     1  rejected on a miss; and, unless keep_view_dependent, when id is outside 1 .. num_geoms or reject_geom[id - 1] != 0
+ *     2  v = p - cam.position;  dz = v . view;  rejected unless dz > 0
+ *     3  sx = hw - (v . right) / (dz * pixelLength.x);  sy = hh - (v . up) / (dz * pixelLength.y)
+ *     4  fx = floorf(sx), fy = floorf(sy);  rejected unless fx >= -1 && fx <= W - 1 && fy >= -1 && fy <= H - 1 (compared as floats
+ *        before any conversion: NaN and infinity are rejected)
+ *     5  ax = sx - fx;  ay = sy - fy
+ *     6  acc = 0, tacc = 0, wsum = 0;  for j = 0, 1 (rows, outer), i = 0, 1:  q = (fx + i, fy + j - row0);  the tap is skipped when q is
+ *        outside the W x R tile, K0(q).w is not > 0, id_K(q) != id, n . n_K(q) < min_normal_dot, or |n . (p_K(q) - p)| > plane_tol * dz;
+ *        else b = (i ? ax : 1 - ax) * (j ? ay : 1 - ay);  acc_k = acc_k + b * K0(q).k;  tacc = tacc + b * K0(q).w;  wsum = wsum + b
+ *     7  wsum >= 0.015625f:  h = acc / wsum;  t = tacc / wsum;  Th = t < cap ? t : cap;   else C = 0
+ * The defaults are those of a CPU simulation on the cornell box (tests/test_history_sim.py; README "Reprojected history" has its
+ * figures).  The bilinear lookup also smooths: the carried image is a BIASED estimator, and nothing here corrects that.
+ * Out of scope: pt_group_* (a context's interleaved rows cannot look up their neighbours); feeding the history into the noise
+ * estimate, the filters or adaptive sampling; motion of anything but the camera. */
+#define PT_HISTORY_KEPT_PLANES 3
+typedef struct PtHistoryOptions { /* every field: 0 = the default */
+  float cap;                   /* default 32: the most samples a carried colour counts for; finite and > 0                 */
+  float min_normal_dot;        /* default 0.9; < 0 switches the normal test off                                            */
+  float plane_tol;             /* default 0.02 (of the view depth dz); < 0 switches the plane-distance test off            */
+  int32_t keep_view_dependent; /* 0 = pixels of reflective geoms carry nothing (default); 1 = they are carried like others */
+} PtHistoryOptions;
+/* Each refuses with a message that names it, nothing allocated or launched, in this order — capture: no renderer / a failed context; a
+ * striped or ragged tile; the adaptive state (read the image with pt_resolve, or return with pt_clear); no feature pass
+ * (pt_render_features) since the last clear or move; samples not finite or <= 0.  reproject: the same first three; nothing captured;
+ * no feature pass since the last clear or move; an option out of range.  resolve: the same first three; samples; a null pointer.
+ * capture and reproject are asynchronous on the renderer's stream; resolve (the blend for every pixel, pixel_count * 3 floats) and
+ * the readback synchronise.  `samples` is the number of iterations the SUM image holds. */
+int pt_history_capture(float samples);
+int pt_history_reproject(const PtHistoryOptions* opt); /* NULL: all defaults.  Fills C from K and the current feature sums */
+int pt_history_resolve(float samples, float* rgb_avg_host);
+/* kept_planes: PT_HISTORY_KEPT_PLANES * pixel_count * 4 floats; current_plane: pixel_count * 4 floats, zeros while C is absent.  Either
+ * may be NULL.  An error before the first capture. */
+int pt_readback_history(float* kept_planes, float* current_plane);
+int pt_history_drop(void);
+/* The same arithmetic on the host (no GPU); the device results equal these bit for bit.  current_plane of the capture and the blend
+ * may be NULL (absent).  reject_geom: num_geoms bytes, read unless opt->keep_view_dependent.  kept_cam->resolution is the FRAME's
+ * W x H; the tile is rows row0 .. row0 + rows - 1 of it. */
+int pt_history_capture_host(int pixels, const float* rgb_sum, const float* feature_planes, const float* current_plane, float samples, float* kept_planes);
+int pt_history_reproject_host(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
+                              const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, float* current_plane);
+int pt_history_blend_host(int pixels, const float* rgb_sum, float samples, const float* current_plane, float* rgb_avg);
+
 /* saveImage()'s per-pixel conversion (main.cpp:91-97 x mirror, image.cpp:26-30 clamp * 255 truncated) on the
  * device: pixel_count*3 bytes, row-major, x mirrored inside each row; the tile must consist of whole rows.
  * Reads back 3 B per pixel instead of 12. */
@@ -795,6 +861,13 @@ int pt_ctx_resolve(PtContext* c, float* rgb_avg_host);
 /* Asynchronous on the context's stream; *rgb_dev (pixel_count * 3 floats, owned by the context, allocated by the first resolve) stays
  * valid until the next resolve: where a later filter of the resolved image can start from. */
 int pt_ctx_resolve_device(PtContext* c, const float** rgb_dev);
+int pt_ctx_history_capture(PtContext* c, float samples);
+int pt_ctx_history_reproject(PtContext* c, const PtHistoryOptions* opt);
+int pt_ctx_history_resolve(PtContext* c, float samples, float* rgb_avg_host);
+/* Asynchronous on the context's stream; *rgb_dev is pt_ctx_resolve_device's buffer (valid until the next resolve of either kind). */
+int pt_ctx_history_resolve_device(PtContext* c, float samples, const float** rgb_dev);
+int pt_ctx_readback_history(PtContext* c, float* kept_planes, float* current_plane);
+int pt_ctx_history_drop(PtContext* c);
 const float* pt_ctx_device_noise(PtContext* c); /* device pointer of plane 0; the planes are contiguous; NULL before the first fold */
 const float* pt_ctx_device_features(PtContext* c); /* device pointer of plane 0; the planes are contiguous; NULL before the first pt_ctx_render_features */
 const float* pt_ctx_device_image(PtContext* c); /* device pointer of the tile SUM image */
@@ -969,6 +1042,10 @@ int pt_stage_render_list_capacity(const int32_t* list, int m, int capacity, int 
 int pt_stage_group_partition(int w, int h, int n, const int32_t* list, int m, int32_t* parts, int32_t* counts);
 int pt_stage_adaptive_select_threshold(int w, int rows, const float* noise_planes, const int32_t* counts, float threshold, int cap, int32_t* list,
                                        int* above, int* m);
+
+/* The reprojection's kernel on caller-supplied host arrays (pt_history_reproject_host's arguments; rows < 32768). */
+int pt_stage_history_reproject(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
+                               const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, float* current_plane);
 
 /* ---- image output (src/image.cpp:22-45, src/main.cpp:86-107) ------------- */
 /* rgb_sum: W*H*3 floats (raw orientation); writes <path> as 8-bit PNG of

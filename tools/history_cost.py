@@ -1,0 +1,140 @@
+#!/usr/bin/env python3
+"""What the reprojected sample history costs (pt_history_capture / _reproject / _resolve);
+profiles/history_cost.log is this tool's output.
+
+  tools/history_cost.py [--reps 21] [--log FILE]
+
+Cornell and the 10,170-primitive stress scene at 1920 x 1080, fast arithmetic, one context.  A view is rendered (4 iterations), its
+first hits are taken (pt_render_features(1, 1)) and captured; the camera moves one orbit step of 2 pi / 120; then, per repetition,
+reproject, resolve (the device form: no readback) and capture run back to back on the context's stream between HIP events, and the
+median, minimum and maximum of each are printed with the bytes a call moves by its specification (the gather's taps: 4 x 32 B read
+at the most, 4 x 16 B more for taps that pass, before any cache) and the rate that makes.  The yardstick is one iteration of pt_render
+at the same camera, in the same process, timed the same way.  The first repetition (allocations, code objects) is dropped.  No timing
+is asserted anywhere."""
+import argparse
+import ctypes as C
+import os
+import statistics
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+
+from cosc_4397_pathtracing_raytracing_project_amd import capi, scenes  # noqa: E402
+
+W, H, SPP = 1920, 1080, 4
+ap = argparse.ArgumentParser()
+ap.add_argument("--reps", type=int, default=21)
+ap.add_argument("--log", default=os.devnull)
+args = ap.parse_args()
+out = open(args.log, "w")
+
+
+def say(*a):
+    line = " ".join(str(x) for x in a)
+    print(line, flush=True)
+    out.write(line + "\n")
+    out.flush()
+
+
+hip = C.CDLL("libamdhip64.so")
+hip.hipEventCreate.argtypes = [C.POINTER(C.c_void_p)]
+hip.hipEventRecord.argtypes = [C.c_void_p, C.c_void_p]
+hip.hipEventSynchronize.argtypes = [C.c_void_p]
+hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
+hip.hipEventDestroy.argtypes = [C.c_void_p]
+
+
+def hip_ok(rc):
+    if rc != 0:
+        raise RuntimeError(f"HIP error {rc}")
+
+
+def events(n):
+    ev = [C.c_void_p() for _ in range(n)]
+    for e in ev:
+        hip_ok(hip.hipEventCreate(C.byref(e)))
+    return ev
+
+
+def elapsed(a, b):
+    ms = C.c_float(0)
+    hip_ok(hip.hipEventElapsedTime(C.byref(ms), a, b))
+    return float(ms.value)
+
+
+def line(what, v, bytes_per_pixel=None):
+    v = sorted(v)
+    med = statistics.median(v)
+    rate = f"  {bytes_per_pixel} B/pixel by specification = {bytes_per_pixel * W * H / med / 1e6:7.1f} GB/s at the median" if bytes_per_pixel else ""
+    say(f"{what:28s} median {med:8.4f} ms  min {v[0]:8.4f}  max {v[-1]:8.4f}  (n={len(v)}){rate}")
+
+
+L = capi.lib()
+L.pt_ctx_stream.argtypes = [C.c_void_p]
+L.pt_ctx_stream.restype = C.c_void_p
+say(f"# pt_history_* on one context, MI355X, {W} x {H}, fast arithmetic; HIP events on the context's stream; {args.reps} repetitions, the first dropped")
+say("# per repetition: reproject, resolve, capture, then ONE iteration of pt_render (the yardstick), so every history call follows a render")
+say("# the rates are bytes by specification over time, not memory traffic: where one exceeds what HBM delivers (about 6.3 TB/s measured on")
+say("# this chip), the caches served part of it - the history's planes, the feature planes, S and the output are about 280 MB at this size,")
+say("# the Infinity Cache holds 256 MiB, and the gather's four taps share lines between neighbouring pixels")
+tmp = tempfile.mkdtemp()
+for name, text in (("cornell (7 primitives)", scenes.cornell_scene_text(res=(W, H))), ("stress 22x22x21 (10170 primitives)", scenes.stress_scene_text())):
+    path = scenes.write_scene(text, os.path.join(tmp, "s.txt"))
+    scene = capi.Scene(path, res=(W, H))
+    opt = capi.make_options(arith="fast")
+    ctx = C.c_void_p()
+    capi._check(L.pt_ctx_create(C.byref(scene.desc), C.byref(opt), C.byref(ctx)))
+    try:
+        stream = L.pt_ctx_stream(ctx)
+        st = capi.PtStats()
+        capi._check(L.pt_ctx_get_stats(ctx, C.byref(st)))
+        before = st.device_bytes
+        capi._check(L.pt_ctx_render(ctx, 1, SPP))
+        capi._check(L.pt_ctx_render_features(ctx, 1, 1))
+        capi._check(L.pt_ctx_history_capture(ctx, C.c_float(SPP)))
+        cam = scene.orbit(np.float32(2 * np.pi / 120), 0.0, 0.0)
+        capi._check(L.pt_ctx_set_camera(ctx, C.byref(cam)))
+        capi._check(L.pt_ctx_render(ctx, SPP + 1, SPP))
+        capi._check(L.pt_ctx_render_features(ctx, 1, 1))
+        times = dict(reproject=[], resolve=[], capture=[], render=[])
+        ev = events(6)
+        dev = C.c_void_p()
+        hopt = capi.history_options()
+        for rep in range(args.reps):
+            hip_ok(hip.hipEventRecord(ev[0], stream))
+            capi._check(L.pt_ctx_history_reproject(ctx, C.byref(hopt)))
+            hip_ok(hip.hipEventRecord(ev[1], stream))
+            capi._check(L.pt_ctx_history_resolve_device(ctx, C.c_float(SPP), C.byref(dev)))
+            hip_ok(hip.hipEventRecord(ev[2], stream))
+            capi._check(L.pt_ctx_history_capture(ctx, C.c_float(SPP)))
+            hip_ok(hip.hipEventRecord(ev[3], stream))
+            hip_ok(hip.hipEventRecord(ev[4], stream))
+            capi._check(L.pt_ctx_render(ctx, 2 * SPP + 1 + rep, 1))
+            hip_ok(hip.hipEventRecord(ev[5], stream))
+            hip_ok(hip.hipEventSynchronize(ev[5]))
+            if rep:
+                times["reproject"].append(elapsed(ev[0], ev[1]))
+                times["resolve"].append(elapsed(ev[1], ev[2]))
+                times["capture"].append(elapsed(ev[2], ev[3]))
+                times["render"].append(elapsed(ev[4], ev[5]))
+        for e in ev:
+            hip.hipEventDestroy(e)
+        kept = np.empty((capi.HISTORY_KEPT_PLANES, W * H, 4), np.float32)
+        cur = np.empty((W * H, 4), np.float32)
+        capi._check(L.pt_ctx_readback_history(ctx, capi._f(kept), capi._f(cur)))
+        capi._check(L.pt_ctx_get_stats(ctx, C.byref(st)))
+        carried = cur[:, 3] > 0
+        say(f"\n## {name}: {int(carried.sum())} of {W * H} pixels carried after the step, mean weight {float(cur[carried, 3].mean()) if carried.any() else 0.0:.2f}; "
+            f"state {(st.device_bytes - before) / 2**20:.1f} MB (history planes, reject table, the resolve's buffer, the feature planes)")
+        line("pt_history_reproject", times["reproject"], 48 + 16 + 4 * 48)
+        line("pt_history_resolve (device)", times["resolve"], 12 + 16 + 12)
+        line("pt_history_capture", times["capture"], 12 + 48 + 16 + 48)
+        line("pt_render, 1 iteration", times["render"])
+        three = statistics.median(times["reproject"]) + statistics.median(times["resolve"]) + statistics.median(times["capture"])
+        say(f"the three together {three:.4f} ms = {three / statistics.median(times['render']):.3f} of one iteration")
+    finally:
+        L.pt_ctx_destroy(ctx)
+out.close()
