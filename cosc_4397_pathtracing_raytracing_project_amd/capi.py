@@ -531,21 +531,36 @@ def denoise_options(levels: int = 0, sigma_color: float = 0.0, sigma_normal: flo
     return PtDenoiseOptions(int(levels), float(sigma_color), float(sigma_normal), float(sigma_position), 1 if keep_albedo else 0)
 
 
-def _denoise_arrays(rgb_sum: np.ndarray, planes: np.ndarray, w: int, rows: int):
+def _denoise_arrays(rgb_sum, planes, w: int, rows: int, noise_planes=None, counts=None):
+    """The flat, checked arrays of a filter call, those of the guided forms only where given, and the output: (s, p[, z][, c], out)."""
     s = np.ascontiguousarray(rgb_sum, np.float32).reshape(-1)
     p = np.ascontiguousarray(planes, np.float32).reshape(-1)
     if s.size != 3 * w * rows or p.size != 4 * FEATURE_PLANES * w * rows:
         raise PtError(f"denoise: {s.size} image and {p.size} plane floats for a frame of {w}x{rows}")
-    return s, p, np.empty((w * rows, 3), np.float32)
+    arrays = [s, p]
+    if noise_planes is not None:
+        arrays.append(np.ascontiguousarray(noise_planes, np.float32).reshape(-1))
+        if arrays[-1].size != 4 * NOISE_PLANES * w * rows:
+            raise PtError(f"denoise_guided: {arrays[-1].size} noise plane floats for a frame of {w}x{rows}")
+    if counts is not None:
+        arrays.append(np.ascontiguousarray(counts, np.int32).reshape(-1))
+        if arrays[-1].size != 2 * w * rows:
+            raise PtError(f"denoise_adaptive: {arrays[-1].size} counts for a frame of {w}x{rows}")
+    return (*arrays, np.empty((w * rows, 3), np.float32))
+
+
+def _filter(fn, out: np.ndarray, *args, **opts) -> np.ndarray:
+    """fn(*args, the options, out) -> out: what a denoise* wrapper does once it has its arrays."""
+    opt = denoise_options(**opts)
+    _check(fn(*args, C.byref(opt), _f(out)))
+    return out
 
 
 def denoise_host(rgb_sum: np.ndarray, planes: np.ndarray, w: int, rows: int, samples: float, **opts) -> np.ndarray:
     """The edge-avoiding filter on the host (pt_denoise_host; no GPU): SUM image [w*rows, 3] and feature SUM planes
     [PT_FEATURE_PLANES, w*rows, 4] in, averaged radiance [w*rows, 3] out.  The device result equals it bit for bit."""
     s, p, out = _denoise_arrays(rgb_sum, planes, w, rows)
-    opt = denoise_options(**opts)
-    _check(lib().pt_denoise_host(int(w), int(rows), _f(s), _f(p), C.c_float(samples), C.byref(opt), _f(out)))
-    return out
+    return _filter(lib().pt_denoise_host, out, int(w), int(rows), _f(s), _f(p), C.c_float(samples), **opts)
 
 
 HISTORY_KEPT_PLANES = 3  # PT_HISTORY_KEPT_PLANES
@@ -639,56 +654,36 @@ def join_noise(noise: dict) -> np.ndarray:
     return planes
 
 
-def _denoise_guided_arrays(rgb_sum, planes, noise_planes, w: int, rows: int):
-    s, p, out = _denoise_arrays(rgb_sum, planes, w, rows)
-    z = np.ascontiguousarray(noise_planes, np.float32).reshape(-1)
-    if z.size != 4 * NOISE_PLANES * w * rows:
-        raise PtError(f"denoise_guided: {z.size} noise plane floats for a frame of {w}x{rows}")
-    return s, p, z, out
-
-
 def denoise_guided_host(rgb_sum: np.ndarray, planes: np.ndarray, noise_planes: np.ndarray, w: int, rows: int, groups: int, iters: int,
                         **opts) -> np.ndarray:
     """The variance-guided filter on the host (pt_denoise_guided_host; no GPU): denoise_host's arrays, the noise planes
     [PT_NOISE_PLANES, w*rows, 4] and the counters M, T of the folds that made them.  The device result equals it bit for bit."""
-    s, p, z, out = _denoise_guided_arrays(rgb_sum, planes, noise_planes, w, rows)
-    opt = denoise_options(**opts)
-    _check(lib().pt_denoise_guided_host(int(w), int(rows), _f(s), _f(p), _f(z), int(groups), int(iters), C.byref(opt), _f(out)))
-    return out
+    s, p, z, out = _denoise_arrays(rgb_sum, planes, w, rows, noise_planes)
+    return _filter(lib().pt_denoise_guided_host, out, int(w), int(rows), _f(s), _f(p), _f(z), int(groups), int(iters), **opts)
 
 
 def denoise_guided_variance_host(rgb_sum: np.ndarray, planes: np.ndarray, noise_planes: np.ndarray, w: int, rows: int, groups: int, iters: int,
                                  **opts):
     """The two variances the guided filter's levels start from (pt_denoise_guided_variance_host): (var_raw, var_0), [w*rows] each."""
-    s, p, z, _ = _denoise_guided_arrays(rgb_sum, planes, noise_planes, w, rows)
+    s, p, z, _ = _denoise_arrays(rgb_sum, planes, w, rows, noise_planes)
     raw, pre = np.empty(w * rows, np.float32), np.empty(w * rows, np.float32)
     opt = denoise_options(**opts)
     _check(lib().pt_denoise_guided_variance_host(int(w), int(rows), _f(s), _f(p), _f(z), int(groups), int(iters), C.byref(opt), _f(raw), _f(pre)))
     return raw, pre
 
 
-def _denoise_adaptive_arrays(rgb_sum, planes, noise_planes, counts, w: int, rows: int):
-    s, p, z, out = _denoise_guided_arrays(rgb_sum, planes, noise_planes, w, rows)
-    c = np.ascontiguousarray(counts, np.int32).reshape(-1)
-    if c.size != 2 * w * rows:
-        raise PtError(f"denoise_adaptive: {c.size} counts for a frame of {w}x{rows}")
-    return s, p, z, c, out
-
-
 def denoise_adaptive_host(rgb_sum: np.ndarray, planes: np.ndarray, noise_planes: np.ndarray, counts: np.ndarray, w: int, rows: int,
                           **opts) -> np.ndarray:
     """The variance-guided filter with per-pixel counts on the host (pt_denoise_adaptive_host; no GPU): denoise_guided_host's arrays
     and counts int32 [w*rows, 2] (T_p, M_p; Renderer.readback_adaptive).  The device result equals it bit for bit."""
-    s, p, z, c, out = _denoise_adaptive_arrays(rgb_sum, planes, noise_planes, counts, w, rows)
-    opt = denoise_options(**opts)
-    _check(lib().pt_denoise_adaptive_host(int(w), int(rows), _f(s), _f(p), _f(z), _i(c), C.byref(opt), _f(out)))
-    return out
+    s, p, z, c, out = _denoise_arrays(rgb_sum, planes, w, rows, noise_planes, counts)
+    return _filter(lib().pt_denoise_adaptive_host, out, int(w), int(rows), _f(s), _f(p), _f(z), _i(c), **opts)
 
 
 def denoise_adaptive_variance_host(rgb_sum: np.ndarray, planes: np.ndarray, noise_planes: np.ndarray, counts: np.ndarray, w: int, rows: int,
                                    **opts):
     """The two variances the adaptive filter's levels start from (pt_denoise_adaptive_variance_host): (var_raw, var_0), [w*rows] each."""
-    s, p, z, c, _ = _denoise_adaptive_arrays(rgb_sum, planes, noise_planes, counts, w, rows)
+    s, p, z, c, _ = _denoise_arrays(rgb_sum, planes, w, rows, noise_planes, counts)
     raw, pre = np.empty(w * rows, np.float32), np.empty(w * rows, np.float32)
     opt = denoise_options(**opts)
     _check(lib().pt_denoise_adaptive_variance_host(int(w), int(rows), _f(s), _f(p), _f(z), _i(c), C.byref(opt), _f(raw), _f(pre)))
@@ -940,26 +935,17 @@ class Renderer:
     def denoise(self, samples: float, **opts) -> np.ndarray:
         """The image filtered by the edge-avoiding filter over the feature buffers (pt_denoise; options: denoise_options):
         averaged radiance of the tile, float32 [n, 3].  The tile is whole contiguous rows; a feature pass must have run."""
-        out = np.empty((self.n, 3), np.float32)
-        opt = denoise_options(**opts)
-        _check(lib().pt_denoise(C.c_float(samples), C.byref(opt), _f(out)))
-        return out
+        return _filter(lib().pt_denoise, np.empty((self.n, 3), np.float32), C.c_float(samples), **opts)
 
     def denoise_guided(self, **opts) -> np.ndarray:
         """The image filtered by the variance-guided form of the filter (pt_denoise_guided): as denoise, the colour term following
         the noise estimate.  At least two groups must have been folded and nothing rendered since the last fold."""
-        out = np.empty((self.n, 3), np.float32)
-        opt = denoise_options(**opts)
-        _check(lib().pt_denoise_guided(C.byref(opt), _f(out)))
-        return out
+        return _filter(lib().pt_denoise_guided, np.empty((self.n, 3), np.float32), **opts)
 
     def denoise_adaptive(self, **opts) -> np.ndarray:
         """The image filtered by the variance-guided filter with per-pixel sample counts (pt_denoise_adaptive): denoise_guided for
         the adaptive state, valid in the uniform state too.  Same preconditions as denoise_guided."""
-        out = np.empty((self.n, 3), np.float32)
-        opt = denoise_options(**opts)
-        _check(lib().pt_denoise_adaptive(C.byref(opt), _f(out)))
-        return out
+        return _filter(lib().pt_denoise_adaptive, np.empty((self.n, 3), np.float32), **opts)
 
     # ---- noise estimate from batch sums (include/pt_amd.h: pt_noise_fold) ----
     def noise_fold(self) -> None:
@@ -1107,27 +1093,21 @@ class Renderer:
     def stage_denoise(rgb_sum: np.ndarray, planes: np.ndarray, w: int, rows: int, samples: float, **opts) -> np.ndarray:
         """denoise_host's arguments through the filter kernels (pt_stage_denoise)."""
         s, p, out = _denoise_arrays(rgb_sum, planes, w, rows)
-        opt = denoise_options(**opts)
-        _check(lib().pt_stage_denoise(int(w), int(rows), _f(s), _f(p), C.c_float(samples), C.byref(opt), _f(out)))
-        return out
+        return _filter(lib().pt_stage_denoise, out, int(w), int(rows), _f(s), _f(p), C.c_float(samples), **opts)
 
     @staticmethod
     def stage_denoise_guided(rgb_sum: np.ndarray, planes: np.ndarray, noise_planes: np.ndarray, w: int, rows: int, groups: int, iters: int,
                              **opts) -> np.ndarray:
         """denoise_guided_host's arguments through the guided filter's kernels (pt_stage_denoise_guided)."""
-        s, p, z, out = _denoise_guided_arrays(rgb_sum, planes, noise_planes, w, rows)
-        opt = denoise_options(**opts)
-        _check(lib().pt_stage_denoise_guided(int(w), int(rows), _f(s), _f(p), _f(z), int(groups), int(iters), C.byref(opt), _f(out)))
-        return out
+        s, p, z, out = _denoise_arrays(rgb_sum, planes, w, rows, noise_planes)
+        return _filter(lib().pt_stage_denoise_guided, out, int(w), int(rows), _f(s), _f(p), _f(z), int(groups), int(iters), **opts)
 
     @staticmethod
     def stage_denoise_adaptive(rgb_sum: np.ndarray, planes: np.ndarray, noise_planes: np.ndarray, counts: np.ndarray, w: int, rows: int,
                                **opts) -> np.ndarray:
         """denoise_adaptive_host's arguments through the adaptive filter's kernels (pt_stage_denoise_adaptive)."""
-        s, p, z, c, out = _denoise_adaptive_arrays(rgb_sum, planes, noise_planes, counts, w, rows)
-        opt = denoise_options(**opts)
-        _check(lib().pt_stage_denoise_adaptive(int(w), int(rows), _f(s), _f(p), _f(z), _i(c), C.byref(opt), _f(out)))
-        return out
+        s, p, z, c, out = _denoise_arrays(rgb_sum, planes, w, rows, noise_planes, counts)
+        return _filter(lib().pt_stage_denoise_adaptive, out, int(w), int(rows), _f(s), _f(p), _f(z), _i(c), **opts)
 
     @staticmethod
     def stage_shade(depth: int, it, pixel, hit: dict, o, d, color):
@@ -1193,18 +1173,12 @@ class Group:
     def denoise(self, samples: float, **opts) -> np.ndarray:
         """Renderer.denoise of the whole frame (pt_group_denoise): float32 [W*H, 3], raw orientation."""
         w, h = self.scene.resolution
-        out = np.empty((w * h, 3), np.float32)
-        opt = denoise_options(**opts)
-        _check(lib().pt_group_denoise(self._h, C.c_float(samples), C.byref(opt), _f(out)))
-        return out
+        return _filter(lib().pt_group_denoise, np.empty((w * h, 3), np.float32), self._h, C.c_float(samples), **opts)
 
     def denoise_guided(self, **opts) -> np.ndarray:
         """Renderer.denoise_guided of the whole frame (pt_group_denoise_guided): float32 [W*H, 3], raw orientation."""
         w, h = self.scene.resolution
-        out = np.empty((w * h, 3), np.float32)
-        opt = denoise_options(**opts)
-        _check(lib().pt_group_denoise_guided(self._h, C.byref(opt), _f(out)))
-        return out
+        return _filter(lib().pt_group_denoise_guided, np.empty((w * h, 3), np.float32), self._h, **opts)
 
     def noise_fold(self) -> None:
         """Renderer.noise_fold on every context (pt_group_noise_fold)."""
@@ -1251,10 +1225,7 @@ class Group:
     def denoise_adaptive(self, **opts) -> np.ndarray:
         """Renderer.denoise_adaptive of the whole frame (pt_group_denoise_adaptive): float32 [W*H, 3], raw orientation."""
         w, h = self.scene.resolution
-        out = np.empty((w * h, 3), np.float32)
-        opt = denoise_options(**opts)
-        _check(lib().pt_group_denoise_adaptive(self._h, C.byref(opt), _f(out)))
-        return out
+        return _filter(lib().pt_group_denoise_adaptive, np.empty((w * h, 3), np.float32), self._h, **opts)
 
     def context(self, i: int) -> int:
         """The handle of context i for the pt_ctx_* functions (pt_group_context)."""

@@ -2,10 +2,11 @@
 //
 // The per-pixel prepare / level / finish bodies below are what the HIP kernels (pt_denoise.hip) and the host loop
 // (denoise_host, exported as pt_denoise_host) both run, so the two cannot disagree; tests/denoise_ref.py restates them in numpy.
-// The variance-guided form (pt_denoise_guided; tests/denoise_guided_ref.py) is the same code with kGuided = true: the colour term is
-// scaled by the centre's variance, which is prepared from the noise planes, prefiltered once and filtered along with the colour.
-// The adaptive form (pt_denoise_adaptive; tests/denoise_adaptive_ref.py) is the guided one with the sample counts of every pixel
-// instead of two scalars: a prepare and a prefilter of its own, then the guided levels and the finish as they are.
+// There is one body per step, and what a form (ptdn::Form) adds to it stands under `if constexpr`.  The variance-guided form
+// (pt_denoise_guided; tests/denoise_guided_ref.py): the colour term is scaled by the centre's variance, which is prepared from the noise
+// planes, prefiltered once and filtered along with the colour.  The adaptive form (pt_denoise_adaptive; tests/denoise_adaptive_ref.py)
+// is the guided one with the sample counts of every pixel instead of two scalars in the prepare and the prefilter; its levels and its
+// finish are the guided form's.
 // Every float operation is a separate IEEE operation in the order pt_amd.h states (`#pragma clang fp contract(off)` in every body, correctly
 // rounded division, denormals kept), so the result does not depend on the arithmetic mode of the build or on the side it runs on.
 // Plain C++ apart from PT_HD: the system compiler accepts it (a host sanitizer run needs nothing else).
@@ -69,26 +70,17 @@ PT_HD float color_factor(const Params& P, int l) {
   return P.inv_c * (float)(1 << (2 * l));
 }
 
-// ── prepare: pixel i of the frame ────────────────────────────────────────────────────────────────────────────────────────
-PT_HD void prepare_pixel(size_t i, size_t npix, const float* S, const V4* planes, float samples, int keep_albedo, V4* n, V4* p, V4* a, V4* c) {
-#pragma clang fp contract(off)
-  const V4 s0 = planes[i], s1 = planes[npix + i], s2 = planes[2 * npix + i];
-  const bool hit = s1.w > 0.0f;
-  V4 vn{0.0f, 0.0f, 0.0f, hit ? 1.0f : 0.0f}, va{0.0f, 0.0f, 0.0f, 0.0f}, vp{0.0f, 0.0f, 0.0f, 0.0f};
-  if (hit) {
-    vn.x = s0.x / s1.w, vn.y = s0.y / s1.w, vn.z = s0.z / s1.w;
-    va.x = s1.x / s1.w, va.y = s1.y / s1.w, va.z = s1.z / s1.w;
-    vp.x = s2.x / s1.w, vp.y = s2.y / s1.w, vp.z = s2.z / s1.w;
-  }
-  V4 vc{S[3 * i] / samples, S[3 * i + 1] / samples, S[3 * i + 2] / samples, 0.0f};
-  if (!keep_albedo) {
-    vc.x = va.x > 0.0f ? vc.x / va.x : vc.x;
-    vc.y = va.y > 0.0f ? vc.y / va.y : vc.y;
-    vc.z = va.z > 0.0f ? vc.z / va.z : vc.z;
-  }
-  n[i] = vn, p[i] = vp, a[i] = va, c[i] = vc;
-}
+// The three forms of the filter, and what a form divides by.  Plain: Tf, the samples.  Guided: ptnz::fold_scalars' Tf and Df of the folds so
+// far.  Adaptive: the counts of the pixel itself — cnt, the plane of pt_adaptive.h, or nullptr: the uniform state, (T, M) for every
+// pixel, as ptad::resolve_pixel.
+enum class Form { Plain, Guided, Adaptive };
+struct Divisors {
+  float Tf, Df;
+  const ptad::Cnt* cnt;
+  int32_t T, M;
+};
 
+// ── prepare: pixel i of the frame ────────────────────────────────────────────────────────────────────────────────────────
 // guided: the fold's own estimate of one component (pt_noise.h fold_component's last two lines, on the planes it left), demodulated
 // like the colour it belongs to
 PT_HD float guided_variance(float prev, float q, float albedo, float Tf, float Df, int keep_albedo) {
@@ -97,14 +89,25 @@ PT_HD float guided_variance(float prev, float q, float albedo, float Tf, float D
   const float v = (d > 0.0f ? d : 0.0f) / Df;
   return !keep_albedo && albedo > 0.0f ? v / (albedo * albedo) : v;
 }
-// guided prepare: prepare_pixel with samples = Tf (its twin, so that the kernel above stays the code it was), and var_raw into the
-// albedo buffer's spare word.  noise: the fold's two planes.
-PT_HD void prepare_pixel_guided(size_t i, size_t npix, const float* S, const V4* planes, const V4* noise, float Tf, float Df, int keep_albedo, V4* n,
-                                V4* p, V4* a, V4* c) {
+// The guided forms (noise: the fold's two planes) leave var_raw in the albedo buffer's spare word.  The adaptive form leaves Tf_p in
+// the position buffer's spare word, which no tap reads (dist2: xyz) and the other two leave 0.
+// D: Divisors, or the members of it that the form reads (a kernel takes no more than those).
+template <Form kForm, typename D>
+PT_HD void prepare_pixel_of(size_t i, size_t npix, const float* S, const V4* planes, const V4* noise, const D& d, int keep_albedo, V4* n, V4* p, V4* a,
+                            V4* c) {
 #pragma clang fp contract(off)
+  float Tf, Df = 0.0f;
+  if constexpr (kForm == Form::Adaptive) {
+    const int32_t Tp = d.cnt ? d.cnt[i].T : d.T, Mp = d.cnt ? d.cnt[i].M : d.M;
+    Tf = (float)Tp;
+    Df = (float)(Mp - 1) * Tf;
+  } else {
+    Tf = d.Tf;
+    if constexpr (kForm == Form::Guided) Df = d.Df;
+  }
   const V4 s0 = planes[i], s1 = planes[npix + i], s2 = planes[2 * npix + i];
   const bool hit = s1.w > 0.0f;
-  V4 vn{0.0f, 0.0f, 0.0f, hit ? 1.0f : 0.0f}, va{0.0f, 0.0f, 0.0f, 0.0f}, vp{0.0f, 0.0f, 0.0f, 0.0f};
+  V4 vn{0.0f, 0.0f, 0.0f, hit ? 1.0f : 0.0f}, va{0.0f, 0.0f, 0.0f, 0.0f}, vp{0.0f, 0.0f, 0.0f, kForm == Form::Adaptive ? Tf : 0.0f};
   if (hit) {
     vn.x = s0.x / s1.w, vn.y = s0.y / s1.w, vn.z = s0.z / s1.w;
     va.x = s1.x / s1.w, va.y = s1.y / s1.w, va.z = s1.z / s1.w;
@@ -116,17 +119,22 @@ PT_HD void prepare_pixel_guided(size_t i, size_t npix, const float* S, const V4*
     vc.y = va.y > 0.0f ? vc.y / va.y : vc.y;
     vc.z = va.z > 0.0f ? vc.z / va.z : vc.z;
   }
-  const V4 prev = noise[i], q = noise[npix + i];
-  const float vx = guided_variance(prev.x, q.x, va.x, Tf, Df, keep_albedo);
-  const float vy = guided_variance(prev.y, q.y, va.y, Tf, Df, keep_albedo);
-  const float vz = guided_variance(prev.z, q.z, va.z, Tf, Df, keep_albedo);
-  va.w = (vx + vy) + vz;
+  if constexpr (kForm != Form::Plain) {
+    const V4 prev = noise[i], q = noise[npix + i];
+    const float vx = guided_variance(prev.x, q.x, va.x, Tf, Df, keep_albedo);
+    const float vy = guided_variance(prev.y, q.y, va.y, Tf, Df, keep_albedo);
+    const float vz = guided_variance(prev.z, q.z, va.z, Tf, Df, keep_albedo);
+    va.w = (vx + vy) + vz;
+  }
   n[i] = vn, p[i] = vp, a[i] = va, c[i] = vc;
 }
 
 // guided variance prefilter: pixel (x, y); 3 x 3, binomial, over the pixels on the centre's side of hit / miss.  Reads the hit flags
 // and var_raw (a.w), writes var_0 into the spare word of colour buffer 0 (4 bytes each: 24 B per pixel with the eight neighbours in cache).
-PT_HD void var_prefilter_pixel(int W, int R, int x, int y, const V4* n, const V4* a, V4* c0) {
+// kAdaptive: over the per-sample variance var_raw(q) * Tf_q (p.w; neighbours differ in their counts: the selection key's argument and
+// arithmetic, ptad::key_pixel), back in the centre's unit.
+template <bool kAdaptive>
+PT_HD void var_prefilter_of(int W, int R, int x, int y, const V4* n, const V4* a, const V4* p, V4* c0) {
 #pragma clang fp contract(off)
   constexpr float G[3] = {1.0f / 4.0f, 1.0f / 2.0f, 1.0f / 4.0f};
   const size_t i0 = (size_t)y * W + x;
@@ -143,69 +151,15 @@ PT_HD void var_prefilter_pixel(int W, int R, int x, int y, const V4* n, const V4
       const size_t q = (size_t)yt * W + xt;
       if (n[q].w != hit) continue;
       const float g = G[j + 1] * G[i + 1];
-      acc = acc + g * a[q].w;
+      float s = a[q].w;
+      if constexpr (kAdaptive) s = s * p[q].w;
+      acc = acc + g * s;
       gsum = gsum + g;
     }
   }
-  c0[i0].w = acc / gsum;
-}
-
-// adaptive (pt_denoise_adaptive; tests/denoise_adaptive_ref.py): prepare_pixel_guided with the counts of the pixel itself — cnt, the
-// plane of pt_adaptive.h, or nullptr: the uniform state, (T, M) for every pixel, as ptad::resolve_pixel — and Tf_p into the position
-// buffer's spare word, which no tap reads (dist2: xyz) and the two bodies above leave 0.
-PT_HD void prepare_pixel_adaptive(size_t i, size_t npix, const float* S, const V4* planes, const V4* noise, const ptad::Cnt* cnt, int32_t T, int32_t M,
-                                  int keep_albedo, V4* n, V4* p, V4* a, V4* c) {
-#pragma clang fp contract(off)
-  const int32_t Tp = cnt ? cnt[i].T : T, Mp = cnt ? cnt[i].M : M;
-  const float Tf = (float)Tp;
-  const float Df = (float)(Mp - 1) * Tf;
-  const V4 s0 = planes[i], s1 = planes[npix + i], s2 = planes[2 * npix + i];
-  const bool hit = s1.w > 0.0f;
-  V4 vn{0.0f, 0.0f, 0.0f, hit ? 1.0f : 0.0f}, va{0.0f, 0.0f, 0.0f, 0.0f}, vp{0.0f, 0.0f, 0.0f, Tf};
-  if (hit) {
-    vn.x = s0.x / s1.w, vn.y = s0.y / s1.w, vn.z = s0.z / s1.w;
-    va.x = s1.x / s1.w, va.y = s1.y / s1.w, va.z = s1.z / s1.w;
-    vp.x = s2.x / s1.w, vp.y = s2.y / s1.w, vp.z = s2.z / s1.w;
-  }
-  V4 vc{S[3 * i] / Tf, S[3 * i + 1] / Tf, S[3 * i + 2] / Tf, 0.0f};
-  if (!keep_albedo) {
-    vc.x = va.x > 0.0f ? vc.x / va.x : vc.x;
-    vc.y = va.y > 0.0f ? vc.y / va.y : vc.y;
-    vc.z = va.z > 0.0f ? vc.z / va.z : vc.z;
-  }
-  const V4 prev = noise[i], q = noise[npix + i];
-  const float vx = guided_variance(prev.x, q.x, va.x, Tf, Df, keep_albedo);
-  const float vy = guided_variance(prev.y, q.y, va.y, Tf, Df, keep_albedo);
-  const float vz = guided_variance(prev.z, q.z, va.z, Tf, Df, keep_albedo);
-  va.w = (vx + vy) + vz;
-  n[i] = vn, p[i] = vp, a[i] = va, c[i] = vc;
-}
-
-// adaptive variance prefilter: var_prefilter_pixel over the per-sample variance var_raw(q) * Tf_q (neighbours differ in their counts:
-// the selection key's argument and arithmetic, ptad::key_pixel), back in the centre's unit.  Reads n.w, a.w, p.w, writes c0.w.
-PT_HD void var_prefilter_pixel_adaptive(int W, int R, int x, int y, const V4* n, const V4* a, const V4* p, V4* c0) {
-#pragma clang fp contract(off)
-  constexpr float G[3] = {1.0f / 4.0f, 1.0f / 2.0f, 1.0f / 4.0f};
-  const size_t i0 = (size_t)y * W + x;
-  const float hit = n[i0].w;
-  float num = 0.0f, den = 0.0f;
-#pragma unroll
-  for (int j = -1; j <= 1; ++j) {
-    const int yt = y + j;
-    if (yt < 0 || yt >= R) continue;
-#pragma unroll
-    for (int i = -1; i <= 1; ++i) {
-      const int xt = x + i;
-      if (xt < 0 || xt >= W) continue;
-      const size_t q = (size_t)yt * W + xt;
-      if (n[q].w != hit) continue;
-      const float g = G[j + 1] * G[i + 1];
-      const float s = a[q].w * p[q].w;
-      num = num + g * s;
-      den = den + g;
-    }
-  }
-  c0[i0].w = (num / den) / p[i0].w;
+  float v = acc / gsum;
+  if constexpr (kAdaptive) v = v / p[i0].w;
+  c0[i0].w = v;
 }
 
 // ── level: one tap against one centre ────────────────────────────────────────────────────────────────────────────────────
@@ -218,18 +172,6 @@ PT_HD float dist2(const V4& q, const V4& o) {
   const float dx = q.x - o.x, dy = q.y - o.y, dz = q.z - o.z;
   return (dx * dx + dy * dy) + dz * dz;
 }
-PT_HD void tap(Centre& ce, float h, float cf, const Params& P, const V4& qc, const V4& qn, const V4& qp) {
-#pragma clang fp contract(off)
-  if (qn.w != ce.n.w) return;
-  const float dc = dist2(qc, ce.c), dn = dist2(qn, ce.n), dp = dist2(qp, ce.p);
-  const float e = (dc * cf + dn * P.inv_n) + dp * P.inv_p;
-  const float w = h * ptmath::exp32(-e);
-  ce.ax = ce.ax + w * qc.x;
-  ce.ay = ce.ay + w * qc.y;
-  ce.az = ce.az + w * qc.z;
-  ce.wsum = ce.wsum + w;
-}
-
 // guided: the centre carries its own colour factor (set once from its variance) and the sum of w^2 var(q); qc.w is var_l(q)
 struct CentreGuided : Centre {
   float cf, vsum;
@@ -240,17 +182,20 @@ PT_HD float guided_color_factor(const Params& P, float var) {
 #pragma clang fp contract(off)
   return P.inv_c / (var + PT_DENOISE_VARIANCE_FLOOR);
 }
-PT_HD void tap_guided(CentreGuided& ce, float h, const Params& P, const V4& qc, const V4& qn, const V4& qp) {
+// cf: the level's colour factor, which the guided form replaces with the centre's own
+template <bool kGuided>
+PT_HD void tap_of(CentreOf<kGuided>& ce, float h, float cf, const Params& P, const V4& qc, const V4& qn, const V4& qp) {
 #pragma clang fp contract(off)
   if (qn.w != ce.n.w) return;
+  if constexpr (kGuided) cf = ce.cf;
   const float dc = dist2(qc, ce.c), dn = dist2(qn, ce.n), dp = dist2(qp, ce.p);
-  const float e = (dc * ce.cf + dn * P.inv_n) + dp * P.inv_p;
+  const float e = (dc * cf + dn * P.inv_n) + dp * P.inv_p;
   const float w = h * ptmath::exp32(-e);
   ce.ax = ce.ax + w * qc.x;
   ce.ay = ce.ay + w * qc.y;
   ce.az = ce.az + w * qc.z;
   ce.wsum = ce.wsum + w;
-  ce.vsum = ce.vsum + (w * w) * qc.w;
+  if constexpr (kGuided) ce.vsum = ce.vsum + (w * w) * qc.w;
 }
 
 // Threads of a level over a frame of R rows: column x, row slot ty < level_slots(R, l); slot ty filters the rows
@@ -298,10 +243,7 @@ PT_HD void level_column_of(int W, int R, int x, int ty, int l, const Params& P, 
 #pragma unroll
       for (int k = 0; k < kRows; ++k) {
         const int j = m - 2 - k;
-        if (j >= -2 && j <= 2) {
-          if constexpr (kGuided) tap_guided(ce[k], H[j + 2] * H[i + 2], P, qc, qn, qp);
-          else tap(ce[k], H[j + 2] * H[i + 2], cf, P, qc, qn, qp);
-        }
+        if (j >= -2 && j <= 2) tap_of<kGuided>(ce[k], H[j + 2] * H[i + 2], cf, P, qc, qn, qp);
       }
     }
   }
@@ -313,12 +255,6 @@ PT_HD void level_column_of(int W, int R, int x, int ty, int l, const Params& P, 
     if constexpr (kGuided) var = ce[k].vsum / (ce[k].wsum * ce[k].wsum);
     out[(size_t)y * W + x] = V4{ce[k].ax / ce[k].wsum, ce[k].ay / ce[k].wsum, ce[k].az / ce[k].wsum, var};
   }
-}
-PT_HD void level_column(int W, int R, int x, int ty, int l, const Params& P, const V4* c, const V4* n, const V4* p, V4* out) {
-  level_column_of<false>(W, R, x, ty, l, P, c, n, p, out);
-}
-PT_HD void level_column_guided(int W, int R, int x, int ty, int l, const Params& P, const V4* c, const V4* n, const V4* p, V4* out) {
-  level_column_of<true>(W, R, x, ty, l, P, c, n, p, out);
 }
 
 // ── finish: pixel i ──────────────────────────────────────────────────────────────────────────────────────────────────────
@@ -335,64 +271,56 @@ PT_HD void finish_pixel(size_t i, int keep_albedo, const V4* c, const V4* a, flo
 // writes its 12 bytes per pixel over the buffer that does not hold c_levels.
 PT_HD int color_buffer(int l) { return l & 1; }
 
-// The whole filter on the host, with the bodies above in the kernels' own thread order.
-inline void denoise_host(int W, int R, const float* S, const float* planes, float samples, const Params& P, float* out) {
-  const size_t npix = (size_t)W * R;
-  std::vector<V4> ws(kWorkspaceV4 * npix);
-  V4 *n = ws.data(), *p = n + npix, *a = p + npix, *col[2] = {a + npix, a + 2 * npix};
-  std::vector<V4> pl(PT_FEATURE_PLANES * npix);  // (the caller's planes need not be 16-byte aligned)
-  for (size_t i = 0; i < pl.size(); ++i) pl[i] = V4{planes[4 * i], planes[4 * i + 1], planes[4 * i + 2], planes[4 * i + 3]};
-  for (size_t i = 0; i < npix; ++i) prepare_pixel(i, npix, S, pl.data(), samples, P.keep_albedo, n, p, a, col[0]);
-  for (int l = 0; l < P.levels; ++l)
-    for (int ty = 0; ty < level_slots(R, l); ++ty)
-      for (int x = 0; x < W; ++x) level_column(W, R, x, ty, l, P, col[color_buffer(l)], n, p, col[color_buffer(l + 1)]);
-  for (size_t i = 0; i < npix; ++i) finish_pixel(i, P.keep_albedo, col[color_buffer(P.levels)], a, out);
-}
+// What a launch or the host loop filters: the frame and its arrays (noise: the fold's PT_NOISE_PLANES planes, null for the plain form),
+// and the resolved divisors and parameters.  pt_denoise_launch reads device pointers, denoise_host the caller's arrays.
+struct Frame {
+  int w, rows;
+  const float *rgb_sum, *planes, *noise;
+};
+struct Job {
+  Form form;
+  Frame f;
+  Divisors div;
+  Params P;
+};
 
-// The guided filter on the host: noise holds the fold's PT_NOISE_PLANES planes, Tf and Df are ptnz::fold_scalars' of the folds so far.
-// var_raw / var_0 (npix floats each, or null) receive the prepared and the prefiltered variance.
-inline void denoise_guided_host(int W, int R, const float* S, const float* planes, const float* noise, float Tf, float Df, const Params& P, float* out,
-                                float* var_raw = nullptr, float* var_0 = nullptr) {
+// The whole filter on the host, with the bodies above in the kernels' own thread order.  counts (the adaptive form): {T_p, M_p} per pixel
+// (pt_readback_adaptive's layout), every M_p >= 2 and T_p >= M_p.  var_raw / var_0 (npix floats each, or null; the two guided forms)
+// receive the prepared and the prefiltered variance; out may then be null.
+inline void denoise_host(const Job& j, const int32_t* counts, float* out, float* var_raw = nullptr, float* var_0 = nullptr) {
+  const int W = j.f.w, R = j.f.rows;
+  const Params& P = j.P;
+  const bool guided = j.form != Form::Plain;
   const size_t npix = (size_t)W * R;
   std::vector<V4> ws(kWorkspaceV4 * npix);
   V4 *n = ws.data(), *p = n + npix, *a = p + npix, *col[2] = {a + npix, a + 2 * npix};
-  std::vector<V4> pl((PT_FEATURE_PLANES + PT_NOISE_PLANES) * npix);
-  for (size_t i = 0; i < PT_FEATURE_PLANES * npix; ++i) pl[i] = V4{planes[4 * i], planes[4 * i + 1], planes[4 * i + 2], planes[4 * i + 3]};
+  std::vector<V4> pl((PT_FEATURE_PLANES + (guided ? PT_NOISE_PLANES : 0)) * npix);  // (the caller's planes need not be 16-byte aligned)
   V4* nz = pl.data() + PT_FEATURE_PLANES * npix;
-  for (size_t i = 0; i < PT_NOISE_PLANES * npix; ++i) nz[i] = V4{noise[4 * i], noise[4 * i + 1], noise[4 * i + 2], noise[4 * i + 3]};
-  for (size_t i = 0; i < npix; ++i) prepare_pixel_guided(i, npix, S, pl.data(), nz, Tf, Df, P.keep_albedo, n, p, a, col[0]);
-  for (int y = 0; y < R; ++y)
-    for (int x = 0; x < W; ++x) var_prefilter_pixel(W, R, x, y, n, a, col[0]);
+  for (size_t i = 0; i < PT_FEATURE_PLANES * npix; ++i) pl[i] = V4{j.f.planes[4 * i], j.f.planes[4 * i + 1], j.f.planes[4 * i + 2], j.f.planes[4 * i + 3]};
+  for (size_t i = 0; i < PT_NOISE_PLANES * npix && guided; ++i) nz[i] = V4{j.f.noise[4 * i], j.f.noise[4 * i + 1], j.f.noise[4 * i + 2], j.f.noise[4 * i + 3]};
+  std::vector<ptad::Cnt> cnt(counts ? npix : 0);
+  for (size_t i = 0; i < cnt.size(); ++i) cnt[i] = ptad::Cnt{counts[2 * i], counts[2 * i + 1]};
+  Divisors d = j.div;
+  if (counts) d.cnt = cnt.data();
+  for (size_t i = 0; i < npix; ++i) {
+    if (j.form == Form::Plain) prepare_pixel_of<Form::Plain>(i, npix, j.f.rgb_sum, pl.data(), nz, d, P.keep_albedo, n, p, a, col[0]);
+    else if (j.form == Form::Guided) prepare_pixel_of<Form::Guided>(i, npix, j.f.rgb_sum, pl.data(), nz, d, P.keep_albedo, n, p, a, col[0]);
+    else prepare_pixel_of<Form::Adaptive>(i, npix, j.f.rgb_sum, pl.data(), nz, d, P.keep_albedo, n, p, a, col[0]);
+  }
+  for (int y = 0; y < R && guided; ++y)
+    for (int x = 0; x < W; ++x) {
+      if (j.form == Form::Adaptive) var_prefilter_of<true>(W, R, x, y, n, a, p, col[0]);
+      else var_prefilter_of<false>(W, R, x, y, n, a, p, col[0]);
+    }
   for (size_t i = 0; i < npix && var_raw; ++i) var_raw[i] = a[i].w;
   for (size_t i = 0; i < npix && var_0; ++i) var_0[i] = col[0][i].w;
   if (!out) return;
   for (int l = 0; l < P.levels; ++l)
     for (int ty = 0; ty < level_slots(R, l); ++ty)
-      for (int x = 0; x < W; ++x) level_column_guided(W, R, x, ty, l, P, col[color_buffer(l)], n, p, col[color_buffer(l + 1)]);
-  for (size_t i = 0; i < npix; ++i) finish_pixel(i, P.keep_albedo, col[color_buffer(P.levels)], a, out);
-}
-
-// The adaptive filter on the host: counts holds {T_p, M_p} per pixel (pt_readback_adaptive's layout), every M_p >= 2 and T_p >= M_p.
-inline void denoise_adaptive_host(int W, int R, const float* S, const float* planes, const float* noise, const int32_t* counts, const Params& P, float* out,
-                                  float* var_raw = nullptr, float* var_0 = nullptr) {
-  const size_t npix = (size_t)W * R;
-  std::vector<V4> ws(kWorkspaceV4 * npix);
-  V4 *n = ws.data(), *p = n + npix, *a = p + npix, *col[2] = {a + npix, a + 2 * npix};
-  std::vector<V4> pl((PT_FEATURE_PLANES + PT_NOISE_PLANES) * npix);
-  for (size_t i = 0; i < PT_FEATURE_PLANES * npix; ++i) pl[i] = V4{planes[4 * i], planes[4 * i + 1], planes[4 * i + 2], planes[4 * i + 3]};
-  V4* nz = pl.data() + PT_FEATURE_PLANES * npix;
-  for (size_t i = 0; i < PT_NOISE_PLANES * npix; ++i) nz[i] = V4{noise[4 * i], noise[4 * i + 1], noise[4 * i + 2], noise[4 * i + 3]};
-  std::vector<ptad::Cnt> cnt(npix);
-  for (size_t i = 0; i < npix; ++i) cnt[i] = ptad::Cnt{counts[2 * i], counts[2 * i + 1]};
-  for (size_t i = 0; i < npix; ++i) prepare_pixel_adaptive(i, npix, S, pl.data(), nz, cnt.data(), 0, 0, P.keep_albedo, n, p, a, col[0]);
-  for (int y = 0; y < R; ++y)
-    for (int x = 0; x < W; ++x) var_prefilter_pixel_adaptive(W, R, x, y, n, a, p, col[0]);
-  for (size_t i = 0; i < npix && var_raw; ++i) var_raw[i] = a[i].w;
-  for (size_t i = 0; i < npix && var_0; ++i) var_0[i] = col[0][i].w;
-  if (!out) return;
-  for (int l = 0; l < P.levels; ++l)
-    for (int ty = 0; ty < level_slots(R, l); ++ty)
-      for (int x = 0; x < W; ++x) level_column_guided(W, R, x, ty, l, P, col[color_buffer(l)], n, p, col[color_buffer(l + 1)]);
+      for (int x = 0; x < W; ++x) {
+        if (guided) level_column_of<true>(W, R, x, ty, l, P, col[color_buffer(l)], n, p, col[color_buffer(l + 1)]);
+        else level_column_of<false>(W, R, x, ty, l, P, col[color_buffer(l)], n, p, col[color_buffer(l + 1)]);
+      }
   for (size_t i = 0; i < npix; ++i) finish_pixel(i, P.keep_albedo, col[color_buffer(P.levels)], a, out);
 }
 

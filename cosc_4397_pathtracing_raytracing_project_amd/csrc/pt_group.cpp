@@ -534,10 +534,10 @@ int pt_group_denoise(PtGroup* g, float samples, const PtDenoiseOptions* opt, flo
   if (!g || !rgb_avg_host) return pt_fail("%s: bad argument", who);
   if (g->n == 1) return pt_ctx_denoise(g->ctx[0], samples, opt, rgb_avg_host);
   if (filter_admit(g, who, true)) return -1;
-  ptdn::Params P{};
-  if (pt_denoise_resolve(who, samples, opt, &P)) return -1;
+  ptdn::Job j{};
+  if (pt_denoise_resolve(who, ptdn::Form::Plain, samples, 0, 0, opt, &j)) return -1;
   return filter_run(g, false, false, rgb_avg_host, [&](hipStream_t root, const float** d_out) {
-    return pt_denoise_launch(root, g->W, g->H, g->d_full, g->d_full_feat, samples, P, g->d_denoise, d_out);
+    return j.f = {g->W, g->H, g->d_full, g->d_full_feat, nullptr}, pt_denoise_launch(root, j, g->d_denoise, d_out);
   });
 }
 
@@ -560,11 +560,10 @@ int pt_group_denoise_guided(PtGroup* g, const PtDenoiseOptions* opt, float* rgb_
     else if (m != groups || t != iters)
       return pt_fail("pt_group_denoise_guided: context %d folded %d groups of %d iterations, context 0 %d of %d; the contexts of a group share them", i, m, t, groups, iters);
   }
-  ptdn::Params P{};
-  float Tf = 0.0f, Df = 0.0f;
-  if (pt_denoise_guided_resolve(who, groups, iters, opt, &P, &Tf, &Df)) return -1;
+  ptdn::Job j{};
+  if (pt_denoise_resolve(who, ptdn::Form::Guided, 0.0f, groups, iters, opt, &j)) return -1;
   return filter_run(g, true, false, rgb_avg_host, [&](hipStream_t root, const float** d_out) {
-    return pt_denoise_guided_launch(root, g->W, g->H, g->d_full, g->d_full_feat, g->d_full_noise, Tf, Df, P, g->d_denoise, d_out);
+    return j.f = {g->W, g->H, g->d_full, g->d_full_feat, g->d_full_noise}, pt_denoise_launch(root, j, g->d_denoise, d_out);
   });
 }
 
@@ -709,11 +708,12 @@ int pt_group_denoise_adaptive(PtGroup* g, const PtDenoiseOptions* opt, float* rg
   if (shared_state(g, who, &s)) return -1;
   if (s.groups < 2) return pt_fail("%s: %d group(s) folded; a variance needs at least 2 (pt_group_noise_fold after each group of iterations)", who, s.groups);
   if (s.iters > INT32_MAX) return pt_fail("%s: %lld iterations folded: the per-pixel counts are int32", who, (long long)s.iters);
-  ptdn::Params P{};
-  if (pt_denoise_adaptive_resolve(who, opt, &P)) return -1;
+  ptdn::Job j{};
+  if (pt_denoise_resolve(who, ptdn::Form::Adaptive, 0.0f, s.groups, s.iters, opt, &j)) return -1;
   return filter_run(g, true, s.adaptive, rgb_avg_host, [&](hipStream_t root, const float** d_out) {
-    return pt_denoise_adaptive_launch(root, g->W, g->H, g->d_full, g->d_full_feat, g->d_full_noise, s.adaptive ? g->d_full_pair : nullptr, (int)s.iters, s.groups, P,
-                                      g->d_denoise, d_out);
+    j.f = {g->W, g->H, g->d_full, g->d_full_feat, g->d_full_noise};
+    j.div.cnt = s.adaptive ? reinterpret_cast<const ptad::Cnt*>(g->d_full_pair) : nullptr;
+    return pt_denoise_launch(root, j, g->d_denoise, d_out);
   });
 }
 

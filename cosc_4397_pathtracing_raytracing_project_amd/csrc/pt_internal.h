@@ -2,37 +2,30 @@
 #pragma once
 int pt_fail(const char* fmt, ...) __attribute__((format(printf, 1, 2)));  // sets pt_last_error(), returns -1
 
-// The edge-avoiding filter (pt_denoise.hip), on raw device pointers and a stream so that a context (its tile) and a group (the frame
-// assembled on the root device) run the same launches.  pt_denoise_resolve: samples and options -> parameters, or the refusal.
-// pt_denoise_launch: w x rows pixels; rgb_sum_dev w*rows*3 floats, planes_dev PT_FEATURE_PLANES * w*rows float4, workspace_dev
-// pt_denoise_workspace_bytes(w * rows) bytes; asynchronous on `stream`; *rgb_avg_dev (w*rows*3 floats) points into the workspace.
+// The edge-avoiding filter in its three forms (pt_denoise.hip; ptdn::Form and ptdn::Job: pt_denoise.h), on raw device pointers and a stream
+// so that a context (its tile) and a group (the frame assembled on the root device) run the same launches.
+// pt_denoise_resolve: the options and the form's counters (plain: samples; guided: the fold counters M = groups, T = iters; adaptive: the
+// same two for every pixel of the uniform state) -> j->form, j->P and j->div, the rest of *j zero, or the refusal.
+// pt_denoise_adaptive_check: what the host and stage entries of the adaptive form refuse in their arrays (counts: w*rows * {T_p, M_p},
+// the first pixel with M_p < 2 or T_p < M_p is named), then the options.
+// pt_denoise_launch: j.w x j.rows pixels; j.rgb_sum w*rows*3 floats, j.planes PT_FEATURE_PLANES * w*rows float4, j.noise (the guided
+// forms) the fold's PT_NOISE_PLANES planes, j.div.cnt (the adaptive form) the plane `cnt` of adaptive sampling or nullptr: every pixel
+// has (div.T, div.M); workspace_dev pt_denoise_workspace_bytes(w * rows) bytes; asynchronous on `stream`; *rgb_avg_dev (w*rows*3 floats)
+// points into the workspace.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <cstdint>
 struct PtDenoiseOptions;
 namespace ptdn {
-struct Params;
+enum class Form;
+struct Job;
 }
 inline size_t pt_denoise_workspace_bytes(size_t pixels) { return 80 * pixels; }
-int pt_denoise_resolve(const char* who, float samples, const PtDenoiseOptions* opt, ptdn::Params* P);
-int pt_denoise_launch(hipStream_t stream, int w, int rows, const float* rgb_sum_dev, const float* planes_dev, float samples, const ptdn::Params& P,
-                      void* workspace_dev, const float** rgb_avg_dev);
-// The variance-guided form (pt_denoise_guided).  pt_denoise_guided_resolve: the fold counters M, T and the options -> parameters and
-// ptnz::fold_scalars' Tf, Df, or the refusal.  pt_denoise_guided_launch: as pt_denoise_launch, plus noise_dev, the fold's
-// PT_NOISE_PLANES planes of w*rows float4; same workspace.
-int pt_denoise_guided_resolve(const char* who, int groups, int64_t iters, const PtDenoiseOptions* opt, ptdn::Params* P, float* Tf, float* Df);
-int pt_denoise_guided_launch(hipStream_t stream, int w, int rows, const float* rgb_sum_dev, const float* planes_dev, const float* noise_dev, float Tf,
-                             float Df, const ptdn::Params& P, void* workspace_dev, const float** rgb_avg_dev);
-// The adaptive form (pt_denoise_adaptive): the guided form with per-pixel counts.  pt_denoise_adaptive_resolve: the options -> parameters, or
-// the refusal.  pt_denoise_adaptive_check: what the host and stage entries refuse in their arrays (counts: w*rows * {T_p, M_p}, the first pixel
-// with M_p < 2 or T_p < M_p is named), then the options.  pt_denoise_adaptive_launch: as pt_denoise_guided_launch with counts_dev, the plane
-// `cnt` of adaptive sampling, or nullptr: every pixel has (iters, groups), groups >= 2; same workspace.
-int pt_denoise_adaptive_resolve(const char* who, const PtDenoiseOptions* opt, ptdn::Params* P);
+int pt_denoise_resolve(const char* who, ptdn::Form form, float samples, int groups, int64_t iters, const PtDenoiseOptions* opt, ptdn::Job* j);
 int pt_denoise_adaptive_check(const char* who, int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, const int32_t* counts,
-                              const PtDenoiseOptions* opt, ptdn::Params* P);
-int pt_denoise_adaptive_launch(hipStream_t stream, int w, int rows, const float* rgb_sum_dev, const float* planes_dev, const float* noise_dev,
-                               const void* counts_dev, int iters, int groups, const ptdn::Params& P, void* workspace_dev, const float** rgb_avg_dev);
+                              const PtDenoiseOptions* opt, ptdn::Job* j);
+int pt_denoise_launch(hipStream_t stream, const ptdn::Job& j, void* workspace_dev, const float** rgb_avg_dev);
 
 // The noise estimate (pt_noise.hip), on raw device pointers and a stream.  state_dev holds pt_noise_state_bytes(pixels) bytes:
 // PT_NOISE_PLANES planes of `pixels` float4, then one double per PT_NOISE_PIXELS_PER_PARTIAL pixels (k_noise_fold's partial sums),

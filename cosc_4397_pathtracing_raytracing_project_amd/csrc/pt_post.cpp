@@ -49,63 +49,47 @@ int pt_ctx_readback_features(PtContext* c, float* planes_host) {
 const float* pt_ctx_device_features(PtContext* c) { return c ? reinterpret_cast<const float*>(c->d_feat) : nullptr; }
 
 // ---- edge-avoiding filter over the image and the feature buffers (csrc/pt_denoise.hip) ------------------------
-int pt_ctx_denoise_device(PtContext* c, float samples, const PtDenoiseOptions* opt, const float** rgb_dev) {
-  if (need(c, "pt_denoise")) return -1;
+// One body for the three forms.  The guided forms run on the same tile and in the same workspace, plus the planes of the noise estimate
+// — which must describe the image as it is, so iterations rendered since the last fold are refused rather than filtered with a stale
+// variance.  The adaptive form is the guided filter with the sample counts of every pixel, so the one filter that runs in the adaptive
+// state (the count plane) as well as in the uniform state (the fold's counters for every pixel, as pt_readback_adaptive reports them).
+static int denoise_device(PtContext* c, const char* who, ptdn::Form form, float samples, const PtDenoiseOptions* opt, const float** rgb_dev) {
+  const bool plain = form == ptdn::Form::Plain, adaptive = form == ptdn::Form::Adaptive;
+  if (need(c, who)) return -1;
   Ctx& g = *c;
-  if (admit(g, "pt_denoise", kNotFailed | kUniform | kWholeRows)) return -1;
+  if (admit(g, who, kNotFailed | (adaptive ? 0u : kUniform) | kWholeRows)) return -1;
   const int W = g.cam.resolution[0];
-  if (!g.d_feat) return pt_fail("pt_denoise: no feature pass has been rendered (pt_render_features)");
-  ptdn::Params P{};
-  if (pt_denoise_resolve("pt_denoise", samples, opt, &P)) return -1;
+  if (!g.d_feat) return pt_fail("%s: no feature pass has been rendered (pt_render_features)", who);
+  if (!plain) {
+    if (!g.d_noise || g.noise_groups < 1) return pt_fail("%s: nothing has been folded (pt_noise_fold)", who);
+    if (admit(g, who, kFoldedAll)) return -1;
+  }
+  if (adaptive) {
+    if (g.noise_groups < 2) return pt_fail("%s: %d group(s) folded; a variance needs at least 2 (pt_noise_fold after each group of iterations)", who, g.noise_groups);
+    if (g.noise_iters > INT32_MAX) return pt_fail("%s: %lld iterations folded: the per-pixel counts are int32", who, (long long)g.noise_iters);
+  }
+  ptdn::Job j{};
+  if (pt_denoise_resolve(who, form, samples, g.noise_groups, g.noise_iters, opt, &j)) return -1;
   HIP_OK(hipSetDevice(g.device));
-  if (ensure(g, g.d_denoise, pt_denoise_workspace_bytes((size_t)g.N))) return -1;  // the first denoise call of the context, of either kind
-  return pt_denoise_launch(g.stream, W, g.N / W, g.d_image, reinterpret_cast<const float*>(g.d_feat), samples, P, g.d_denoise, rgb_dev);
+  if (ensure(g, g.d_denoise, pt_denoise_workspace_bytes((size_t)g.N))) return -1;  // the first denoise call of the context, of any kind
+  j.f = {W, g.N / W, g.d_image, reinterpret_cast<const float*>(g.d_feat), plain ? nullptr : static_cast<const float*>(g.d_noise)};
+  j.div.cnt = adaptive && g.adaptive ? static_cast<const ptad::Cnt*>(g.d_acnt) : nullptr;
+  return pt_denoise_launch(g.stream, j, g.d_denoise, rgb_dev);
+}
+int pt_ctx_denoise_device(PtContext* c, float samples, const PtDenoiseOptions* opt, const float** rgb_dev) {
+  return denoise_device(c, "pt_denoise", ptdn::Form::Plain, samples, opt, rgb_dev);
 }
 int pt_ctx_denoise(PtContext* c, float samples, const PtDenoiseOptions* opt, float* rgb_avg_host) {
   return copy_out(c, "pt_denoise", rgb_avg_host, 3, [&](const float** d) { return pt_ctx_denoise_device(c, samples, opt, d); });
 }
-
-// The variance-guided form: the same tile, the same workspace, plus the planes of the noise estimate — which must describe the image
-// as it is, so iterations rendered since the last fold are refused rather than filtered with a stale variance.
 int pt_ctx_denoise_guided_device(PtContext* c, const PtDenoiseOptions* opt, const float** rgb_dev) {
-  if (need(c, "pt_denoise_guided")) return -1;
-  Ctx& g = *c;
-  if (admit(g, "pt_denoise_guided", kNotFailed | kUniform | kWholeRows)) return -1;
-  const int W = g.cam.resolution[0];
-  if (!g.d_feat) return pt_fail("pt_denoise_guided: no feature pass has been rendered (pt_render_features)");
-  if (!g.d_noise || g.noise_groups < 1) return pt_fail("pt_denoise_guided: nothing has been folded (pt_noise_fold)");
-  if (admit(g, "pt_denoise_guided", kFoldedAll)) return -1;
-  ptdn::Params P{};
-  float Tf = 0.0f, Df = 0.0f;
-  if (pt_denoise_guided_resolve("pt_denoise_guided", g.noise_groups, g.noise_iters, opt, &P, &Tf, &Df)) return -1;
-  HIP_OK(hipSetDevice(g.device));
-  if (ensure(g, g.d_denoise, pt_denoise_workspace_bytes((size_t)g.N))) return -1;
-  return pt_denoise_guided_launch(g.stream, W, g.N / W, g.d_image, reinterpret_cast<const float*>(g.d_feat), static_cast<const float*>(g.d_noise), Tf, Df, P,
-                                  g.d_denoise, rgb_dev);
+  return denoise_device(c, "pt_denoise_guided", ptdn::Form::Guided, 0.0f, opt, rgb_dev);
 }
 int pt_ctx_denoise_guided(PtContext* c, const PtDenoiseOptions* opt, float* rgb_avg_host) {
   return copy_out(c, "pt_denoise_guided", rgb_avg_host, 3, [&](const float** d) { return pt_ctx_denoise_guided_device(c, opt, d); });
 }
-
-// The adaptive form: the guided filter with the sample counts of every pixel, so the one filter that runs in the adaptive state (the
-// count plane) as well as in the uniform state (the fold's counters for every pixel, as pt_readback_adaptive reports them).
 int pt_ctx_denoise_adaptive_device(PtContext* c, const PtDenoiseOptions* opt, const float** rgb_dev) {
-  if (need(c, "pt_denoise_adaptive")) return -1;
-  Ctx& g = *c;
-  if (admit(g, "pt_denoise_adaptive", kNotFailed | kWholeRows)) return -1;
-  const int W = g.cam.resolution[0];
-  if (!g.d_feat) return pt_fail("pt_denoise_adaptive: no feature pass has been rendered (pt_render_features)");
-  if (!g.d_noise || g.noise_groups < 1) return pt_fail("pt_denoise_adaptive: nothing has been folded (pt_noise_fold)");
-  if (admit(g, "pt_denoise_adaptive", kFoldedAll)) return -1;
-  if (g.noise_groups < 2)
-    return pt_fail("pt_denoise_adaptive: %d group(s) folded; a variance needs at least 2 (pt_noise_fold after each group of iterations)", g.noise_groups);
-  if (g.noise_iters > INT32_MAX) return pt_fail("pt_denoise_adaptive: %lld iterations folded: the per-pixel counts are int32", (long long)g.noise_iters);
-  ptdn::Params P{};
-  if (pt_denoise_adaptive_resolve("pt_denoise_adaptive", opt, &P)) return -1;
-  HIP_OK(hipSetDevice(g.device));
-  if (ensure(g, g.d_denoise, pt_denoise_workspace_bytes((size_t)g.N))) return -1;
-  return pt_denoise_adaptive_launch(g.stream, W, g.N / W, g.d_image, reinterpret_cast<const float*>(g.d_feat), static_cast<const float*>(g.d_noise),
-                                    g.adaptive ? g.d_acnt : nullptr, (int)g.noise_iters, g.noise_groups, P, g.d_denoise, rgb_dev);
+  return denoise_device(c, "pt_denoise_adaptive", ptdn::Form::Adaptive, 0.0f, opt, rgb_dev);
 }
 int pt_ctx_denoise_adaptive(PtContext* c, const PtDenoiseOptions* opt, float* rgb_avg_host) {
   return copy_out(c, "pt_denoise_adaptive", rgb_avg_host, 3, [&](const float** d) { return pt_ctx_denoise_adaptive_device(c, opt, d); });

@@ -281,29 +281,31 @@ int pt_stage_save_u8(int w, int h, float samples, const float* rgb_sum, uint8_t*
   return 0;
 }
 
-// The filter kernels on caller-supplied host arrays (tests: frames a renderer would never produce)
+// The filter kernels on caller-supplied host arrays (tests: frames a renderer would never produce): the resolved job `j` with the arrays
+// filter_stage left on the device
+static int filter_stage_job(Ctx& g, const char* who, int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, float* rgb_avg,
+                            ptdn::Job& j) {
+  return filter_stage(g, who, (size_t)w * rows, rgb_sum, planes, noise_planes, rgb_avg, [&](const float* img, const float* pl, const float* nz, void* ws, const float** out) {
+    return j.f = {w, rows, img, pl, nz}, pt_denoise_launch(g.stream, j, ws, out);
+  });
+}
 int pt_stage_denoise(int w, int rows, const float* rgb_sum, const float* planes, float samples, const PtDenoiseOptions* opt, float* rgb_avg) {
   if (need(default_context(), "pt_stage_denoise")) return -1;
-  Ctx& g = *default_context();
   if (w <= 0 || rows <= 0 || rows >= 32768 || (int64_t)w * rows > (1ll << 30) || !rgb_sum || !planes || !rgb_avg) return pt_fail("pt_stage_denoise: bad argument");
-  ptdn::Params P{};
-  if (pt_denoise_resolve("pt_stage_denoise", samples, opt, &P)) return -1;
-  return filter_stage(g, "pt_stage_denoise", (size_t)w * rows, rgb_sum, planes, nullptr, rgb_avg,
-                      [&](const float* img, const float* pl, const float*, void* ws, const float** out) { return pt_denoise_launch(g.stream, w, rows, img, pl, samples, P, ws, out); });
+  ptdn::Job j{};
+  if (pt_denoise_resolve("pt_stage_denoise", ptdn::Form::Plain, samples, 0, 0, opt, &j)) return -1;
+  return filter_stage_job(*default_context(), "pt_stage_denoise", w, rows, rgb_sum, planes, nullptr, rgb_avg, j);
 }
 
 // The guided filter's kernels on caller-supplied host arrays
 int pt_stage_denoise_guided(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, int groups, int64_t iters,
                             const PtDenoiseOptions* opt, float* rgb_avg) {
   if (need(default_context(), "pt_stage_denoise_guided")) return -1;
-  Ctx& g = *default_context();
   if (w <= 0 || rows <= 0 || rows >= 32768 || (int64_t)w * rows > (1ll << 30) || !rgb_sum || !planes || !noise_planes || !rgb_avg)
     return pt_fail("pt_stage_denoise_guided: bad argument");
-  ptdn::Params P{};
-  float Tf = 0.0f, Df = 0.0f;
-  if (pt_denoise_guided_resolve("pt_stage_denoise_guided", groups, iters, opt, &P, &Tf, &Df)) return -1;
-  return filter_stage(g, "pt_stage_denoise_guided", (size_t)w * rows, rgb_sum, planes, noise_planes, rgb_avg,
-                      [&](const float* img, const float* pl, const float* nz, void* ws, const float** out) { return pt_denoise_guided_launch(g.stream, w, rows, img, pl, nz, Tf, Df, P, ws, out); });
+  ptdn::Job j{};
+  if (pt_denoise_resolve("pt_stage_denoise_guided", ptdn::Form::Guided, 0.0f, groups, iters, opt, &j)) return -1;
+  return filter_stage_job(*default_context(), "pt_stage_denoise_guided", w, rows, rgb_sum, planes, noise_planes, rgb_avg, j);
 }
 
 // The adaptive filter's kernels on caller-supplied host arrays (pt_denoise_adaptive_host's arguments); the counts travel beside the frame
@@ -313,16 +315,14 @@ int pt_stage_denoise_adaptive(int w, int rows, const float* rgb_sum, const float
   Ctx& g = *default_context();
   if (rows >= 32768) return pt_fail("pt_stage_denoise_adaptive: a frame of %d x %d pixels is not supported", w, rows);
   if (!rgb_avg) return pt_fail("pt_stage_denoise_adaptive: null argument");
-  ptdn::Params P{};
-  if (pt_denoise_adaptive_check("pt_stage_denoise_adaptive", w, rows, rgb_sum, planes, noise_planes, counts, opt, &P)) return -1;
+  ptdn::Job j{};
+  if (pt_denoise_adaptive_check("pt_stage_denoise_adaptive", w, rows, rgb_sum, planes, noise_planes, counts, opt, &j)) return -1;
   Scratch counts_sc;  // (filter_stage synchronises before it returns)
   int32_t* d_counts = nullptr;
   HIP_OK(hipSetDevice(g.device));
   if (device_copy(counts_sc, "pt_stage_denoise_adaptive", counts, 2 * (size_t)w * rows, &d_counts)) return -1;
-  return filter_stage(g, "pt_stage_denoise_adaptive", (size_t)w * rows, rgb_sum, planes, noise_planes, rgb_avg,
-                      [&](const float* img, const float* pl, const float* nz, void* ws, const float** out) {
-                        return pt_denoise_adaptive_launch(g.stream, w, rows, img, pl, nz, d_counts, 0, 0, P, ws, out);
-                      });
+  j.div.cnt = reinterpret_cast<const ptad::Cnt*>(d_counts);
+  return filter_stage_job(g, "pt_stage_denoise_adaptive", w, rows, rgb_sum, planes, noise_planes, rgb_avg, j);
 }
 
 // The reprojection's kernel on caller-supplied host arrays (pt_history_reproject_host's arguments)

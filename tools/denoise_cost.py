@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
-"""What the two forms of the à-trous filter cost (pt_denoise / pt_denoise_guided) for the bench.py
-configuration (cornell 1080p, depth 8, fast): four groups of one batch with a fold after each, a feature pass, then the two filters
-alternating at their defaults.
+"""What the three forms of the à-trous filter cost (pt_denoise / pt_denoise_guided / pt_denoise_adaptive) for the
+bench.py configuration (cornell 1080p, depth 8, fast): four groups of one batch with a fold after each, a feature pass, then the three
+filters alternating at their defaults (the adaptive form in the uniform state: the folds' counters for every pixel).
 usage: tools/denoise_cost.py [--reps 10] [--once]
---once: three calls of each and nothing timed on the host — the run to put under `rocprofv3 --kernel-trace --stats`
-(k_denoise_level_guided beside k_denoise_level, k_denoise_var_prefilter, the two prepares).  Without it: host time per call,
-readback of the 25 MB result included."""
+--once: three calls of each and nothing timed on the host — the run to put under `rocprofv3 --kernel-trace --stats`: all eight kernels
+(k_denoise_level<true> beside k_denoise_level<false>, the two k_denoise_var_prefilter<..>, the three k_denoise_prepare<..>,
+k_denoise_finish).  Without it: host time per call, readback of the 25 MB result included."""
 import argparse
 import os
 import statistics
@@ -32,7 +32,7 @@ def main() -> int:
             r.render(1 + g * k, k)
             r.noise_fold()
         r.render_features(1, 4 * k)
-        calls = {"denoise": lambda: r.denoise(4 * k), "denoise_guided": lambda: r.denoise_guided()}
+        calls = {"denoise": lambda: r.denoise(4 * k), "denoise_guided": lambda: r.denoise_guided(), "denoise_adaptive": lambda: r.denoise_adaptive()}
         times = {what: [] for what in calls}
         for _ in range(3 if a.once else a.reps + 1):
             for what, call in calls.items():
@@ -43,7 +43,7 @@ def main() -> int:
         if not a.once:
             for what, v in times.items():
                 v = sorted(v[1:])  # the first call allocates
-                print(f"1080p 5 levels {what:15s}: median {statistics.median(v):7.3f} ms  min {v[0]:7.3f} max {v[-1]:7.3f}  (n={len(v)}, with the readback)", flush=True)
+                print(f"1080p 5 levels {what:16s}: median {statistics.median(v):7.3f} ms  min {v[0]:7.3f} max {v[-1]:7.3f}  (n={len(v)}, with the readback)", flush=True)
     finally:
         r.free()
     return 0
