@@ -255,13 +255,20 @@ PT_DEV void stage16(void* lds, const void* g, int bytes) {
 }
 
 // Tile pixel → global pixel index (what keys the RNG and the camera ray), see BatchInfo::stripe and BatchInfo::list (p < b.N).
-PT_DEV int global_pixel(const BatchInfo& b, int p) {
+struct PixelMap {  // the fields of BatchInfo that global_pixel reads
+  int pixel_begin, stripe, gap;
+  float inv_stripe;
+  const int32_t* list;
+};
+PT_DEV PixelMap pixel_map(const BatchInfo& b) { return PixelMap{b.pixel_begin, b.stripe, b.gap, b.inv_stripe, b.list}; }
+PT_DEV int global_pixel(const PixelMap& b, int p) {
   if (b.stripe == 0) return b.pixel_begin + p;
   if (b.list) return b.pixel_begin + b.list[p];  // (the host gives a list batch stripe != 0, so the contiguous form pays nothing for this test)
   int i, r;
   divmod(p, b.stripe, b.inv_stripe, i, r);
   return b.pixel_begin + p + i * b.gap;
 }
+PT_DEV int global_pixel(const BatchInfo& b, int p) { return global_pixel(pixel_map(b), p); }
 
 // ───────────────────────────── path records (ptd::PathBuf) ─────────────────
 // What rides along with a path besides its ray and colour: the sample id.  (phash / k: the per-pixel half of the RNG seed and the
@@ -1697,8 +1704,39 @@ constexpr int kInlineGroup = 8;  // loads in flight per lane in a step
 template <int GROUP>
 PT_DEV void stream_gather_slot(int N, int K, const QueueShare& sh, const ptd::RetireBuf& ret, const ptd::Word4* plane, const ptd::Word4* front,
                                float* __restrict__ image, int q, int s);  // pt_output.inc
-template <typename T, typename... R>
-PT_DEV const T& first_of(const T& t, const R&...) { return t; }
+// Wave-uniform state that only the cold sites of k_paths<kLdsTables, ..> read — the piece switch, seek, a gather step, the epilogue — is
+// not kept in scalar registers across the round: the kernel has more of it than the scalar file holds, and what does not fit is
+// parked in the lanes of a VGPR and comes back through v_readlane_b32, a vector instruction, in whichever block the register allocator
+// picks (tools/isa_spills.py).  Kernel arguments are read again where they are used, from the kernarg segment through the
+// scalar cache (PathsArgs mirrors the segment: the arguments by value, in order, each at its natural alignment); a value computed in
+// the prologue passes through cold(), behind which whatever is derived from it stays at the site instead of being hoisted to the
+// loop's entry and parked.  Neither may stand where a round passes every time: a scalar load there is a wait per round.
+template <typename... PREV>
+struct PathsPrev {};
+template <typename P>
+struct PathsPrev<P> {
+  P p;
+};
+template <typename... PREV>
+struct PathsArgs {
+  SceneTables sc;
+  BatchInfo b;
+  ptd::Queues qs;
+  int32_t* cnt;
+  ptd::PathBuf in;
+  ptd::RetireBuf ret;
+  PathsPrev<PREV...> prev;
+};
+template <typename A>
+PT_DEV const A& cold_args() {
+  auto p = __builtin_amdgcn_kernarg_segment_ptr();  // (constant address space: scalar loads)
+  asm volatile("" : "+s"(p));  // (the loads behind it cannot be merged with the prologue's or moved above this point)
+  return *(const A*)p;
+}
+PT_DEV int cold(int v) {
+  asm volatile("" : "+s"(v));
+  return v;
+}
 template <Search MODE, int SPLIT = 0, typename... PREV>
 __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPathsScanWaves : kPathsGridWaves) void k_paths(SceneTables sc, BatchInfo b, ptd::Queues qs, int32_t* __restrict__ cnt /* [depth][Q] rows */,
                                                                ptd::PathBuf in, ptd::RetireBuf ret, PREV... prev) {
@@ -1724,6 +1762,17 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
   constexpr bool FIXED = SPLIT == kFixedSlots, FIRST = SPLIT == kFirstBounce || FIXED;  // FIRST: the first bounce is sampled here
   constexpr bool GATHER = sizeof...(PREV) > 0;
   static_assert(!GATHER || FIXED, "only a batch with fixed record slots gathers its predecessor");
+  // COLD: the cold sites read the arguments from the kernarg segment (cold_args); the other search forms keep them as they were
+  constexpr bool COLD = MODE == kLdsTables;
+  using Args = PathsArgs<PREV...>;
+  auto c_b = [&]() -> const BatchInfo& {
+    if constexpr (COLD) return cold_args<Args>().b;
+    else return b;
+  };
+  auto c_qs = [&]() -> const ptd::Queues& {
+    if constexpr (COLD) return cold_args<Args>().qs;
+    else return qs;
+  };
   const int he = iter_hash_entries(sc);
   uint32_t* tword = reinterpret_cast<uint32_t*>(lds + L.tword);  // MODE 0: [kMaxTop] leaf | geom << 8 per top entry
   int* lmat = reinterpret_cast<int*>(lds + L.lmat);              // MODE 0: [64] material of the leaf at threaded node index i
@@ -1804,7 +1853,11 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
   // Piece sizes fall: the pieces of level l = p / wq hold ps0 (1 - 1 / P)^l paths (not fewer than a refill's worth; tests: fewer),
   // ps0 = total / (wq P), P = paths_pieces, so that the levels add up to the queue — large pieces while everybody is busy, small
   // ones at the end, where a launch waits for the last piece (pieces of one size left half a piece of idle time per wave).
-  const PiecePlan pieces = piece_plan(total, wq, b.paths_pieces, qs.deal != nullptr, chunk_sums);
+  const PiecePlan pieces0 = piece_plan(total, wq, b.paths_pieces, qs.deal != nullptr, chunk_sums);
+  auto piece_plan_here = [&]() {  // (COLD: formed again at the switch from the total and the arguments — five registers less across the round)
+    if constexpr (COLD) return piece_plan(cold(total), wq, c_b().paths_pieces, c_qs().deal != nullptr, cold(ne) <= 64 * 64);
+    else return pieces0;
+  };
   [[maybe_unused]] int clist0 = 0;  // SPLIT: clist without its iteration's k * seg_cap — where the sub-list of iteration 0 starts
   int ce = ne, cstart = total, ccnt = 0, clist = 0;  // cursor (wave-uniform): sub-list e = k * wq0 + rho; nothing to stream leaves it at the end
   int cord = 0;  // sub-list visits of the cursor so far
@@ -1850,7 +1903,7 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
   // put the cursor on the sub-list that rank `at_rank` (< total) lies in: a new visit
   auto seek = [&](int at_rank) {
     int cum = 0, e_begin = 0;
-    if (chunk_sums) {
+    if (COLD ? cold(ne) <= 64 * 64 : chunk_sums) {
       int all;
       const int cbefore = wave_prefix6(csum, all);
       const unsigned long long here = ballot(csum > 0 && cbefore <= at_rank && at_rank < cbefore + csum);
@@ -1926,6 +1979,26 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
       nx.o = mk(w0.x, w0.y, w0.z), nx.d = mk(w0.w, w1.x, w1.y), nx.c = mk(w1.z, w1.w, 0.f), nx_rs = rs;
     } else nx = path_load(in, qbase + at), nx_rs = rs;
   };
+  // Tile pixel -> global pixel at the take.  The form is fixed for the launch: a contiguous tile costs one add from one register.  The
+  // striped and the list form fetch their five fields at the head of the refill (refill_pixel_map: independent scalar loads from one
+  // pointer, issued in front of the slot's LDS reads, so they land under the wait the refill has anyway) and keep nothing across the round.
+  const int pix0 = b.stripe == 0 && b.pixel_begin >= 0 ? b.pixel_begin : -1;
+  auto refill_pixel_map = [&]() {
+    PixelMap pm{0, 0, 0, 0.f, nullptr};
+    if constexpr (COLD)
+      if (pix0 < 0) pm = pixel_map(c_b());
+    return pm;
+  };
+  auto pixel_of = [&](const PixelMap& pm, int pl) {
+    if constexpr (COLD) {
+      if (pix0 >= 0) return pix0 + pl;
+      return global_pixel(pm, pl);
+    } else return global_pixel(b, pl);
+  };
+  // fast build: the top list's base for the search's scalar loads, a value of its own — left an argument, the compiler may read it from the
+  // kernarg segment again in every round (a scalar load and its wait at the top of the search) instead of keeping it
+  [[maybe_unused]] uintptr_t top_b_scalar = (uintptr_t)sc.top_b;
+  if constexpr (COLD && kFast) asm volatile("" : "+s"(top_b_scalar));
   // lane state
   f3 o = mk(0.f, 0.f, 0.f), d = o, c = o;
   int slot = 0, depth = 1, mark = 0, rslot = 0;  // rslot: the visit the path was taken in; from its death on: its record slot
@@ -1938,9 +2011,11 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
   [[maybe_unused]] uint32_t gather_time = 0u;
   [[maybe_unused]] auto gather_step = [&]() {
     if constexpr (GATHER) {
-      const PrevGather& pg = first_of(prev...);
+      const Args& ka = cold_args<Args>();  // (everything a step needs but the wave's place in it: nothing of it is kept across the round)
+      const PrevGather& pg = ka.prev.p;
+      const int gq = cold(q);
       const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-      stream_gather_slot<kInlineGroup>(b.N, pg.K, qshare, ret, pg.rec, pg.plane0, pg.image, q, gj * 64 + lane);
+      stream_gather_slot<kInlineGroup>(ka.b.N, pg.K, queue_share(ka.b, ka.qs, gq), ka.ret, pg.rec, pg.plane0, pg.image, gq, gj * 64 + lane);
       gj += wq;
       gather_time += (uint32_t)(__builtin_amdgcn_s_memrealtime() - t0);
     }
@@ -1948,11 +2023,12 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
   while (!FIRST) {  // (that form's loop, the same round rotated, follows this one)
     // ── on to the wave's next piece, once the current one is handed out: its own, then whatever the queue's counter gives ──
     if (streamed >= p_hi && p_hi >= 0) {
+      const PiecePlan pieces = piece_plan_here();
       int nextp = -1;
       if (cord == 0) nextp = r;  // (every piece starts with a visit)
       else if (pieces.needs_counter()) {
         int v = 0;
-        if (lane == 0) v = atomicAdd(&qs.deal[dm.piece_counter(q)], 1);
+        if (lane == 0) v = atomicAdd(&c_qs().deal[deal_map(c_qs()).piece_counter(q)], 1);
         nextp = wq + __builtin_amdgcn_readfirstlane(v);
       }
       const PieceRange pr = pieces.piece_range(nextp);
@@ -1966,6 +2042,7 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
     // ── refill: dead lanes take the record waiting in their slot; the slot gets the next record of the piece ──
     const bool take = !valid && has_next;
     if (ballot(take || owes || (!valid && !has_next && streamed < p_hi))) {
+      const PixelMap pm = refill_pixel_map();
       v4f w0, w1;
       float cz;
       int nslot, nrs;
@@ -2000,7 +2077,7 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
       } else if (take) o = mk(w0.x, w0.y, w0.z), d = mk(w0.w, w1.x, w1.y), c = mk(w1.z, w1.w, cz);
       if (take) {
         slot = nslot, rslot = nrs;
-        phash = utilhash((uint32_t)global_pixel(b, nslot & ((1 << b.slot_shift) - 1)));
+        phash = utilhash((uint32_t)pixel_of(pm, nslot & ((1 << b.slot_shift) - 1)));
         depth = 1;
         valid = fresh = true;
         has_next = false;
@@ -2029,7 +2106,7 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
       if (ballot(fresh)) {
         // fast build: the top list's boxes come through scalar loads (constant address space: s_load into SGPRs, the scalar cache)
         // instead of broadcast LDS reads into VGPRs: 73 -> 67 VGPRs; in-box fast +0.8 %, exact -1.4 % (its longer tests cover the LDS latency)
-        if constexpr (kFast) paths_search(cy, (cfloat4*)(uintptr_t)sc.top_b, tword, ntop, geoms, o, d, fresh, lane, mark);
+        if constexpr (kFast) paths_search(cy, (cfloat4*)top_b_scalar, tword, ntop, geoms, o, d, fresh, lane, mark);
         else paths_search(cy, top, tword, ntop, geoms, o, d, fresh, lane, mark);
       }
       // ── which lanes are resolved?  Too few, with candidates pending: run them as a partial chunk ──
@@ -2106,7 +2183,7 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
     while (true) {
       // ── search: box tests + appends for the lanes with a new ray; too few resolved lanes with candidates pending: a partial chunk ──
       if (ballot(fresh)) {
-        if constexpr (kFast) paths_search(cy, (cfloat4*)(uintptr_t)sc.top_b, tword, ntop, geoms, o, d, fresh, lane, mark);
+        if constexpr (kFast) paths_search(cy, (cfloat4*)top_b_scalar, tword, ntop, geoms, o, d, fresh, lane, mark);
         else paths_search(cy, top, tword, ntop, geoms, o, d, fresh, lane, mark);
       }
       bool ready = valid && (cy.processed - mark) >= 0;
@@ -2153,14 +2230,15 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
         }
       }
       // ── on to the wave's next piece, once the current one is handed out ──
-      if (streamed >= p_hi && p_hi >= 0) {
+      if (__builtin_expect(streamed >= p_hi && p_hi >= 0, 0)) {  // (rare: the register allocator parks what only this block reads, not the round's state)
         if constexpr (GATHER)
           if (cord != 0 && gj < my_nq) gather_step();
+        const PiecePlan pieces = piece_plan_here();
         int nextp = -1;
         if (cord == 0) nextp = r;
         else if (pieces.needs_counter()) {
           int v = 0;
-          if (lane == 0) v = atomicAdd(&qs.deal[dm.piece_counter(q)], 1);
+          if (lane == 0) v = atomicAdd(&c_qs().deal[deal_map(c_qs()).piece_counter(q)], 1);
           nextp = wq + __builtin_amdgcn_readfirstlane(v);
         }
         const PieceRange pr = pieces.piece_range(nextp);
@@ -2174,6 +2252,7 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
       // ── refill: lanes without a path take the record waiting in their slot and decide its depth 0; the slot gets the next record ──
       const bool take = !valid && has_next;
       if (ballot(take || owes || (!valid && !has_next && streamed < p_hi))) {
+        const PixelMap pm = refill_pixel_map();
         v4f w0, w1;
         float cz;
         int word, vword;
@@ -2186,7 +2265,7 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
           const int pl = first_pixel(word, b.slot_shift), k = FIXED ? fixed_k((uint32_t)vword, fbits) : visit_k((uint32_t)vword);
           const f3 hn = mk(w0.w, w1.x, w1.y), cam_d = mk(w1.z, w1.w, cz);
           slot = make_slot(b, k, pl), rslot = FIXED ? fixed_slot_of((uint32_t)vword, fbits, rt.seg_cap) : visit_number((uint32_t)vword);  // (FIXED: the record slot at once)
-          phash = utilhash((uint32_t)global_pixel(b, pl));
+          phash = utilhash((uint32_t)pixel_of(pm, pl));
           ShadeIO s;
           s.o = mk(0.f, 0.f, 0.f);
           s.d = cam_d;
@@ -2222,15 +2301,16 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
   if constexpr (GATHER) {
     while (gj < my_nq) gather_step();  // the rest of the wave's share
     if (r == 0)  // the records are consumed: zero counters for the next batch (k_collect_stream's block 0 of the queue)
-      for (int i = lane; i < ret.kmax; i += 64) ret.cnt[(int64_t)q * ret.kmax + i] = 0ull;
+      for (int i = lane, kmax = cold_args<Args>().ret.kmax; i < kmax; i += 64) cold_args<Args>().ret.cnt[(int64_t)q * kmax + i] = 0ull;
   }
   // statistics: rays traced at depth d >= 2 = this wave's paths retired at depth >= d (row 1 holds the queue's input count already)
   if (lane == 0) {
     int reached = 0, rays = 0;
-    for (int dd = min(b.trace_depth - 1, 63); dd >= 2; --dd) {
+    int32_t* const ecnt = COLD ? cold_args<Args>().cnt : cnt;
+    for (int dd = min(c_b().trace_depth - 1, 63); dd >= 2; --dd) {
       reached += died[dd];
       rays += reached;
-      if (reached) atomicAdd(&cnt[cnt_index(qs, dd, q)], reached);
+      if (reached) atomicAdd(&ecnt[cnt_index(c_qs(), dd, q)], reached);
     }
     // What this queue's paths cost, for the next batch's deal: the TIME its waves spent on them (the waves of a queue finish together
     // — they share its pieces — so the sum is waves x the queue's finishing time, and dealing in proportion to it moves the
@@ -2240,9 +2320,20 @@ __global__ __launch_bounds__(kBlock, MODE == 0 ? kPathsWaves : MODE == 1 ? kPath
     uint64_t spent = __builtin_amdgcn_s_memrealtime() - t_begin;
     if constexpr (GATHER) spent -= min(spent, (uint64_t)gather_time);  // (the previous batch's gather is not this queue's paths)
     const int ticks = (int)min(spent >> 6, (uint64_t)0x3ffff);  // units of 0.64 us; a queue's sum stays below 2^31
-    if (qs.deal != nullptr && rays) atomicAdd(&qs.deal[dm.time(q)], ticks), atomicAdd(&qs.deal[dm.rays(q)], rays);
+    const ptd::Queues& eq = c_qs();
+    if (eq.deal != nullptr && rays) atomicAdd(&eq.deal[deal_map(eq).time(q)], ticks), atomicAdd(&eq.deal[deal_map(eq).rays(q)], rays);
   }
 }
+
+// PathsArgs against the kernel: the members' types in order ARE the parameter list, so an argument added, dropped or moved stops the build
+// here instead of shifting what the cold sites read.  (A struct's members and a kernel's by-value arguments are both laid out in order, each
+// at its natural alignment: equal lists give equal offsets.)
+template <typename... PREV>
+using PathsSignature = void (*)(decltype(PathsArgs<PREV...>::sc), decltype(PathsArgs<PREV...>::b), decltype(PathsArgs<PREV...>::qs), decltype(PathsArgs<PREV...>::cnt),
+                                decltype(PathsArgs<PREV...>::in), decltype(PathsArgs<PREV...>::ret), PREV...);
+static_assert(std::is_same<decltype(&k_paths<kLdsTables, kFixedSlots>), PathsSignature<>>::value, "PathsArgs does not mirror k_paths' arguments");
+static_assert(std::is_same<decltype(&k_paths<kLdsTables, kFixedSlots, PrevGather>), PathsSignature<PrevGather>>::value, "PathsArgs does not mirror k_paths' arguments");
+static_assert(std::is_same<decltype(PathsArgs<PrevGather>::prev.p), PrevGather>::value && std::is_standard_layout<PathsArgs<PrevGather>>::value, "PathsArgs: the gathered batch comes last");
 
 // test-only stage: explicit (iter, pixel) per path, in-place, no compaction
 __global__ __launch_bounds__(kBlock) void k_shade_stage(SceneTables sc, int trace_depth, int depth, int n,
