@@ -337,6 +337,25 @@ def lib() -> C.CDLL:
         L.pt_history_reproject_host.argtypes = _reproject
         L.pt_stage_history_reproject.argtypes = _reproject
         L.pt_history_blend_host.argtypes = [C.c_int, _fp, C.c_float, _fp, _fp]
+    if hasattr(L, "pt_history_denoise"):  # absent from older A/B builds of the library (tools/build_rev.sh)
+        _hio = C.POINTER(PtHistoryOptions)
+        _dno = C.POINTER(PtDenoiseOptions)
+        _reproject_var = [C.c_int, C.c_int, C.c_int, C.POINTER(PtCamera), _fp, _fp, _u8p, C.c_int, _hio, _fp, _fp, _fp]
+        _hdn = [C.c_int, C.c_int, _fp, _fp, _fp, C.c_int, C.c_int64, C.c_float, _fp, _fp, _dno, _fp]
+        L.pt_history_capture_ex.argtypes = [C.c_float, C.c_uint32]
+        L.pt_history_reproject_ex.argtypes = [_hio, C.c_uint32]
+        L.pt_history_denoise.argtypes = [C.c_float, _dno, _fp]
+        L.pt_readback_history_variance.argtypes = [_fp, _fp]
+        L.pt_ctx_history_capture_ex.argtypes = [C.c_void_p, C.c_float, C.c_uint32]
+        L.pt_ctx_history_reproject_ex.argtypes = [C.c_void_p, _hio, C.c_uint32]
+        L.pt_ctx_history_denoise.argtypes = [C.c_void_p, C.c_float, _dno, _fp]
+        L.pt_ctx_history_denoise_device.argtypes = [C.c_void_p, C.c_float, _dno, C.POINTER(C.c_void_p)]
+        L.pt_ctx_readback_history_variance.argtypes = [C.c_void_p, _fp, _fp]
+        L.pt_history_capture_variance_host.argtypes = [C.c_int, _fp, C.c_int, C.c_int64, C.c_float, _fp, _fp, _fp]
+        L.pt_history_reproject_variance_host.argtypes = _reproject_var
+        L.pt_stage_history_reproject_variance.argtypes = _reproject_var
+        L.pt_history_denoise_host.argtypes = _hdn
+        L.pt_stage_history_denoise.argtypes = _hdn
     _lib = L
     return L
 
@@ -626,6 +645,72 @@ def history_blend_host(rgb_sum: np.ndarray, samples: float, current: Optional[np
     out = np.empty((n, 3), np.float32)
     _check(lib().pt_history_blend_host(n, _f(s), C.c_float(samples), None if c is None else _f(c), _f(out)))
     return out
+
+
+HISTORY_VARIANCE = 1  # PT_HISTORY_VARIANCE
+
+
+def history_capture_variance_host(noise_planes: np.ndarray, groups: int, iters: int, samples: float, current: Optional[np.ndarray] = None,
+                                  current_var: Optional[np.ndarray] = None) -> np.ndarray:
+    """The variance side of pt_history_capture_ex on the host (no GPU): the fold's planes [PT_NOISE_PLANES, n, 4] with their counters
+    M, T, and the planes C, VC [n, 4] (None: absent) in, VK [n, 4] out.  K is history_capture_host's."""
+    z = np.ascontiguousarray(noise_planes, np.float32).reshape(-1)
+    n = z.size // (4 * NOISE_PLANES)
+    c = None if current is None else np.ascontiguousarray(current, np.float32).reshape(-1)
+    v = None if current_var is None else np.ascontiguousarray(current_var, np.float32).reshape(-1)
+    if z.size != 4 * NOISE_PLANES * n or any(a is not None and a.size != 4 * n for a in (c, v)):
+        raise PtError(f"history_capture_variance_host: {z.size} noise plane floats")
+    out = np.empty((n, 4), np.float32)
+    _check(lib().pt_history_capture_variance_host(n, _f(z), int(groups), int(iters), C.c_float(samples), None if c is None else _f(c),
+                                                  None if v is None else _f(v), _f(out)))
+    return out
+
+
+def _history_reproject_variance(call, kept_cam: PtCamera, kept, planes, reject, kept_var, w: int, rows: int, row0: int, **opts):
+    k = np.ascontiguousarray(kept, np.float32).reshape(-1)
+    p = np.ascontiguousarray(planes, np.float32).reshape(-1)
+    r = np.ascontiguousarray(reject, np.uint8).reshape(-1)
+    vk = np.ascontiguousarray(kept_var, np.float32).reshape(-1)
+    if k.size != 4 * HISTORY_KEPT_PLANES * w * rows or p.size != 4 * FEATURE_PLANES * w * rows or vk.size != 4 * w * rows:
+        raise PtError(f"history_reproject_variance: {k.size} kept, {p.size} plane and {vk.size} variance floats for a tile of {w}x{rows}")
+    out, vout = np.empty((w * rows, 4), np.float32), np.empty((w * rows, 4), np.float32)
+    opt = history_options(**opts)
+    _check(call(int(w), int(rows), int(row0), C.byref(kept_cam), _f(k), _f(p), r.ctypes.data_as(C.POINTER(C.c_uint8)) if r.size else None, int(r.size),
+                C.byref(opt), _f(vk), _f(out), _f(vout)))
+    return out, vout
+
+
+def history_reproject_variance_host(kept_cam: PtCamera, kept, planes, reject, kept_var, w: int, rows: int, row0: int = 0, **opts):
+    """pt_history_reproject_ex with PT_HISTORY_VARIANCE on the host (no GPU): history_reproject_host's arrays and VK [w*rows, 4] in,
+    (C, VC), [w*rows, 4] each, out."""
+    return _history_reproject_variance(lib().pt_history_reproject_variance_host, kept_cam, kept, planes, reject, kept_var, w, rows, row0, **opts)
+
+
+def stage_history_reproject_variance(kept_cam: PtCamera, kept, planes, reject, kept_var, w: int, rows: int, row0: int = 0, **opts):
+    """history_reproject_variance_host's arrays through the production kernel (pt_stage_history_reproject_variance; a renderer must be live)."""
+    return _history_reproject_variance(lib().pt_stage_history_reproject_variance, kept_cam, kept, planes, reject, kept_var, w, rows, row0, **opts)
+
+
+def _history_denoise(call, rgb_sum, planes, noise_planes, w: int, rows: int, groups: int, iters: int, samples: float, current, current_var, **opts):
+    s, p, z, out = _denoise_arrays(rgb_sum, planes, w, rows, noise_planes)
+    c = None if current is None else np.ascontiguousarray(current, np.float32).reshape(-1)
+    v = None if current_var is None else np.ascontiguousarray(current_var, np.float32).reshape(-1)
+    if any(a is not None and a.size != 4 * w * rows for a in (c, v)):
+        raise PtError(f"history_denoise: the current plane or its variance is not [{w * rows}, 4]")
+    return _filter(call, out, int(w), int(rows), _f(s), _f(p), _f(z), int(groups), int(iters), C.c_float(samples), None if c is None else _f(c),
+                   None if v is None else _f(v), **opts)
+
+
+def history_denoise_host(rgb_sum, planes, noise_planes, w: int, rows: int, groups: int, iters: int, samples: float, current=None, current_var=None,
+                         **opts) -> np.ndarray:
+    """pt_history_denoise on the host (no GPU): denoise_guided_host's arrays, samples, and the planes C, VC [w*rows, 4] (None: absent)."""
+    return _history_denoise(lib().pt_history_denoise_host, rgb_sum, planes, noise_planes, w, rows, groups, iters, samples, current, current_var, **opts)
+
+
+def stage_history_denoise(rgb_sum, planes, noise_planes, w: int, rows: int, groups: int, iters: int, samples: float, current=None, current_var=None,
+                          **opts) -> np.ndarray:
+    """history_denoise_host's arguments through the filter's kernels (pt_stage_history_denoise; a renderer must be live)."""
+    return _history_denoise(lib().pt_stage_history_denoise, rgb_sum, planes, noise_planes, w, rows, groups, iters, samples, current, current_var, **opts)
 
 
 def split_noise(planes: np.ndarray) -> dict:
@@ -931,6 +1016,26 @@ class Renderer:
 
     def history_drop(self) -> None:
         _check(lib().pt_history_drop())
+
+    def history_capture_ex(self, samples: float, flags: int = HISTORY_VARIANCE) -> None:
+        """history_capture, with PT_HISTORY_VARIANCE also keeping the variance of the blend (pt_history_capture_ex)."""
+        _check(lib().pt_history_capture_ex(C.c_float(samples), int(flags)))
+
+    def history_reproject_ex(self, flags: int = HISTORY_VARIANCE, **opts) -> None:
+        """history_reproject, with PT_HISTORY_VARIANCE also resampling the kept variance (pt_history_reproject_ex)."""
+        opt = history_options(**opts)
+        _check(lib().pt_history_reproject_ex(C.byref(opt), int(flags)))
+
+    def history_denoise(self, samples: float, **opts) -> np.ndarray:
+        """The blend of history_resolve filtered by the variance-guided filter with the blend's variance (pt_history_denoise;
+        options: denoise_options): float32 [n, 3]."""
+        return _filter(lib().pt_history_denoise, np.empty((self.n, 3), np.float32), C.c_float(samples), **opts)
+
+    def readback_history_variance(self):
+        """(VK, VC), float32 [n, 4] each; zeros while absent."""
+        vk, vc = np.empty((self.n, 4), np.float32), np.empty((self.n, 4), np.float32)
+        _check(lib().pt_readback_history_variance(_f(vk), _f(vc)))
+        return vk, vc
 
     def denoise(self, samples: float, **opts) -> np.ndarray:
         """The image filtered by the edge-avoiding filter over the feature buffers (pt_denoise; options: denoise_options):

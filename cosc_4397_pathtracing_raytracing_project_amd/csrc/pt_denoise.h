@@ -6,7 +6,9 @@
 // (pt_denoise_guided; tests/denoise_guided_ref.py): the colour term is scaled by the centre's variance, which is prepared from the noise
 // planes, prefiltered once and filtered along with the colour.  The adaptive form (pt_denoise_adaptive; tests/denoise_adaptive_ref.py)
 // is the guided one with the sample counts of every pixel instead of two scalars in the prepare and the prefilter; its levels and its
-// finish are the guided form's.
+// finish are the guided form's.  The history form (pt_history_denoise; tests/history_variance_ref.py) is the guided one over the blend
+// of the image with the reprojected history (pt_history.h): its prepare takes the blend for the colour and the blend's variance for
+// the variance; prefilter, levels and finish are the guided form's.
 // Every float operation is a separate IEEE operation in the order pt_amd.h states (`#pragma clang fp contract(off)` in every body, correctly
 // rounded division, denormals kept), so the result does not depend on the arithmetic mode of the build or on the side it runs on.
 // Plain C++ apart from PT_HD: the system compiler accepts it (a host sanitizer run needs nothing else).
@@ -24,6 +26,7 @@
 
 #include "../../include/pt_amd.h"
 #include "pt_adaptive.h"
+#include "pt_history.h"
 #include "pt_portable_math.h"
 
 namespace ptdn {
@@ -46,6 +49,7 @@ struct Params {
 // PtDenoiseOptions -> Params (0 = the default in every field, NULL = all defaults); the message of a refusal, or nullptr.
 // default_color: sigma_color's default, 4 for pt_denoise, kGuidedSigmaColor for the guided form.
 constexpr float kGuidedSigmaColor = 8.0f;
+constexpr float kHistorySigmaColor = 8.0f;  // the history form's
 inline const char* resolve(const PtDenoiseOptions* opt, Params* out, float default_color = 4.0f) {
 #pragma clang fp contract(off)
   PtDenoiseOptions o{};
@@ -72,12 +76,15 @@ PT_HD float color_factor(const Params& P, int l) {
 
 // The three forms of the filter, and what a form divides by.  Plain: Tf, the samples.  Guided: ptnz::fold_scalars' Tf and Df of the folds so
 // far.  Adaptive: the counts of the pixel itself — cnt, the plane of pt_adaptive.h, or nullptr: the uniform state, (T, M) for every
-// pixel, as ptad::resolve_pixel.
-enum class Form { Plain, Guided, Adaptive };
+// pixel, as ptad::resolve_pixel.  History: the guided form's two for the new samples' variance, and what the blend reads — samples, the
+// history's current plane C and its variance VC (both nullptr: absent).
+enum class Form { Plain, Guided, Adaptive, History };
 struct Divisors {
   float Tf, Df;
   const ptad::Cnt* cnt;
   int32_t T, M;
+  float samples;
+  const V4 *C, *VC;
 };
 
 // ── prepare: pixel i of the frame ────────────────────────────────────────────────────────────────────────────────────────
@@ -85,8 +92,13 @@ struct Divisors {
 // like the colour it belongs to
 PT_HD float guided_variance(float prev, float q, float albedo, float Tf, float Df, int keep_albedo) {
 #pragma clang fp contract(off)
-  const float d = q - (prev * prev) / Tf;
-  const float v = (d > 0.0f ? d : 0.0f) / Df;
+  const float v = pthi::sample_variance(prev, q, Tf, Df);
+  return !keep_albedo && albedo > 0.0f ? v / (albedo * albedo) : v;
+}
+// history: the variance of the blend of one component (pt_history.h blend_variance over the same estimate), demodulated likewise
+PT_HD float history_variance(float prev, float q, float albedo, float Tf, float Df, float samples, float vh, float Th, int keep_albedo) {
+#pragma clang fp contract(off)
+  const float v = pthi::blend_variance(pthi::sample_variance(prev, q, Tf, Df), samples, vh, Th);
   return !keep_albedo && albedo > 0.0f ? v / (albedo * albedo) : v;
 }
 // The guided forms (noise: the fold's two planes) leave var_raw in the albedo buffer's spare word.  The adaptive form leaves Tf_p in
@@ -103,7 +115,7 @@ PT_HD void prepare_pixel_of(size_t i, size_t npix, const float* S, const V4* pla
     Df = (float)(Mp - 1) * Tf;
   } else {
     Tf = d.Tf;
-    if constexpr (kForm == Form::Guided) Df = d.Df;
+    if constexpr (kForm == Form::Guided || kForm == Form::History) Df = d.Df;
   }
   const V4 s0 = planes[i], s1 = planes[npix + i], s2 = planes[2 * npix + i];
   const bool hit = s1.w > 0.0f;
@@ -113,13 +125,29 @@ PT_HD void prepare_pixel_of(size_t i, size_t npix, const float* S, const V4* pla
     va.x = s1.x / s1.w, va.y = s1.y / s1.w, va.z = s1.z / s1.w;
     vp.x = s2.x / s1.w, vp.y = s2.y / s1.w, vp.z = s2.z / s1.w;
   }
-  V4 vc{S[3 * i] / Tf, S[3 * i + 1] / Tf, S[3 * i + 2] / Tf, 0.0f};
+  V4 vc{0.0f, 0.0f, 0.0f, 0.0f};
+  [[maybe_unused]] V4 hc{0.0f, 0.0f, 0.0f, 0.0f}, hv{0.0f, 0.0f, 0.0f, 0.0f};  // history: C and VC of the pixel (absent: +0)
+  if constexpr (kForm == Form::History) {
+    if (d.C) hc = d.C[i];
+    if (d.VC) hv = d.VC[i];
+    vc.x = pthi::blend_component(S[3 * i], d.samples, hc.x, hc.w);
+    vc.y = pthi::blend_component(S[3 * i + 1], d.samples, hc.y, hc.w);
+    vc.z = pthi::blend_component(S[3 * i + 2], d.samples, hc.z, hc.w);
+  } else {
+    vc.x = S[3 * i] / Tf, vc.y = S[3 * i + 1] / Tf, vc.z = S[3 * i + 2] / Tf;
+  }
   if (!keep_albedo) {
     vc.x = va.x > 0.0f ? vc.x / va.x : vc.x;
     vc.y = va.y > 0.0f ? vc.y / va.y : vc.y;
     vc.z = va.z > 0.0f ? vc.z / va.z : vc.z;
   }
-  if constexpr (kForm != Form::Plain) {
+  if constexpr (kForm == Form::History) {
+    const V4 prev = noise[i], q = noise[npix + i];
+    const float vx = history_variance(prev.x, q.x, va.x, Tf, Df, d.samples, hv.x, hc.w, keep_albedo);
+    const float vy = history_variance(prev.y, q.y, va.y, Tf, Df, d.samples, hv.y, hc.w, keep_albedo);
+    const float vz = history_variance(prev.z, q.z, va.z, Tf, Df, d.samples, hv.z, hc.w, keep_albedo);
+    va.w = (vx + vy) + vz;
+  } else if constexpr (kForm != Form::Plain) {
     const V4 prev = noise[i], q = noise[npix + i];
     const float vx = guided_variance(prev.x, q.x, va.x, Tf, Df, keep_albedo);
     const float vy = guided_variance(prev.y, q.y, va.y, Tf, Df, keep_albedo);
@@ -273,9 +301,11 @@ PT_HD int color_buffer(int l) { return l & 1; }
 
 // What a launch or the host loop filters: the frame and its arrays (noise: the fold's PT_NOISE_PLANES planes, null for the plain form),
 // and the resolved divisors and parameters.  pt_denoise_launch reads device pointers, denoise_host the caller's arrays.
+// current, current_var (the history form; both null: absent): the planes C and VC, which the host loop reads here and a launch in div.
 struct Frame {
   int w, rows;
   const float *rgb_sum, *planes, *noise;
+  const float *current = nullptr, *current_var = nullptr;
 };
 struct Job {
   Form form;
@@ -302,9 +332,16 @@ inline void denoise_host(const Job& j, const int32_t* counts, float* out, float*
   for (size_t i = 0; i < cnt.size(); ++i) cnt[i] = ptad::Cnt{counts[2 * i], counts[2 * i + 1]};
   Divisors d = j.div;
   if (counts) d.cnt = cnt.data();
+  std::vector<V4> hist(j.form == Form::History && j.f.current ? 2 * npix : 0);
+  for (size_t i = 0; i < hist.size() / 2; ++i) {
+    const float *c = j.f.current + 4 * i, *v = j.f.current_var + 4 * i;
+    hist[i] = V4{c[0], c[1], c[2], c[3]}, hist[npix + i] = V4{v[0], v[1], v[2], v[3]};
+  }
+  if (j.form == Form::History) d.C = hist.empty() ? nullptr : hist.data(), d.VC = hist.empty() ? nullptr : hist.data() + npix;
   for (size_t i = 0; i < npix; ++i) {
     if (j.form == Form::Plain) prepare_pixel_of<Form::Plain>(i, npix, j.f.rgb_sum, pl.data(), nz, d, P.keep_albedo, n, p, a, col[0]);
     else if (j.form == Form::Guided) prepare_pixel_of<Form::Guided>(i, npix, j.f.rgb_sum, pl.data(), nz, d, P.keep_albedo, n, p, a, col[0]);
+    else if (j.form == Form::History) prepare_pixel_of<Form::History>(i, npix, j.f.rgb_sum, pl.data(), nz, d, P.keep_albedo, n, p, a, col[0]);
     else prepare_pixel_of<Form::Adaptive>(i, npix, j.f.rgb_sum, pl.data(), nz, d, P.keep_albedo, n, p, a, col[0]);
   }
   for (int y = 0; y < R && guided; ++y)

@@ -3,13 +3,15 @@
 // A translation unit of its own, compiled ONCE with -ffp-contract=off: the filter is specified as separate IEEE float32 operations
 // (pt_denoise.h), so there is nothing an arithmetic mode could change, and the path tracer's kernels (pt_kernels.hip) are not
 // rebuilt differently because of it.  The kernels are thin: thread indices in, the PT_HD bodies of pt_denoise.h, which the host
-// loop (ptdn::denoise_host, behind the pt_denoise*_host entry points) runs too.  Four templates, eight kernels (ptdn::Form: Plain =
-// pt_denoise, Guided = pt_denoise_guided, Adaptive = pt_denoise_adaptive):
+// loop (ptdn::denoise_host, behind the pt_denoise*_host entry points) runs too.  Four templates, nine kernels (ptdn::Form: Plain =
+// pt_denoise, Guided = pt_denoise_guided, Adaptive = pt_denoise_adaptive, History = pt_history_denoise):
 //
 //   k_denoise_prepare<Form>        one thread per pixel: SUM image + feature SUM planes -> normal | hit, position, albedo, colour (4 x 16 B)
 //                                  <Guided>: + the two noise planes in, var_raw out in the albedo's spare word
 //                                  <Adaptive>: <Guided> with the pixel's own counts (8 B more in; the count plane, or the fold's two
 //                                  scalars in the uniform state), Tf_p out in the position's spare word
+//                                  <History>: <Guided> over the blend with the reprojected history: + 16 B of C and 16 B of VC in (when
+//                                  present); per pixel 12 B of S, 48 B of features, 32 B of noise, 16 + 16 B of history in, 64 B out
 //   k_denoise_var_prefilter<bool>  the guided forms; one thread per pixel, 64 x 4 tiles: 3 x 3 over var_raw and the hit flags, var_0 into
 //                                  colour buffer 0's .w.  <true>, the adaptive form: over var_raw * Tf of the nine neighbours (n.w, a.w,
 //                                  p.w), back in the centre's unit
@@ -51,6 +53,13 @@ struct PrepareIn<Form::Adaptive> {
   const ptad::Cnt* __restrict__ cnt;
   int T, M;
 };
+template <>
+struct PrepareIn<Form::History> {
+  const V4* __restrict__ noise;
+  const V4* __restrict__ C;
+  const V4* __restrict__ VC;
+  float Tf, Df, samples;
+};
 template <Form kForm, typename... In>
 __global__ __launch_bounds__(kBlock) void k_denoise_prepare(int npix, const float* __restrict__ S, const V4* __restrict__ planes, In... in, int keep_albedo,
                                                             V4* __restrict__ n, V4* __restrict__ p, V4* __restrict__ a, V4* __restrict__ c) {
@@ -87,26 +96,30 @@ __global__ __launch_bounds__(kBlock) void k_denoise_finish(int npix, int keep_al
 
 // pt_internal.h.  Everything is checked before the first launch; no allocation, no synchronisation.
 int pt_denoise_launch(hipStream_t stream, const ptdn::Job& j, void* workspace_dev, const float** rgb_avg_dev) {
-  static const char* const kWho[] = {"pt_denoise", "pt_denoise_guided", "pt_denoise_adaptive"};
+  static const char* const kWho[] = {"pt_denoise", "pt_denoise_guided", "pt_denoise_adaptive", "pt_history_denoise"};
   const char* who = kWho[(int)j.form];
   const int w = j.f.w, rows = j.f.rows;
   const Params& P = j.P;
   const Divisors& d = j.div;
   if (w <= 0 || rows <= 0 || rows >= 32768 || (int64_t)w * rows > (1ll << 30)) return pt_fail("%s: a frame of %d x %d pixels is not supported", who, w, rows);
-  const bool ok = j.form == Form::Plain    ? d.Tf > 0.0f
-                  : j.form == Form::Guided ? j.f.noise && d.Tf >= 2.0f && d.Df >= d.Tf
-                                           : j.f.noise && (d.cnt || (d.M >= 2 && d.T >= d.M));
+  const bool ok = j.form == Form::Plain      ? d.Tf > 0.0f
+                  : j.form == Form::Guided   ? j.f.noise && d.Tf >= 2.0f && d.Df >= d.Tf
+                  : j.form == Form::Adaptive ? j.f.noise && (d.cnt || (d.M >= 2 && d.T >= d.M))
+                                             : j.f.noise && d.Tf >= 2.0f && d.Df >= d.Tf && d.samples > 0.0f && !d.C == !d.VC;
   if (!j.f.rgb_sum || !j.f.planes || !workspace_dev || !ok || P.levels < 1 || P.levels > ptdn::kMaxLevels) return pt_fail("%s: bad argument", who);
   const int npix = w * rows;
   V4* n = static_cast<V4*>(workspace_dev);
   V4 *p = n + npix, *a = p + npix, *col[2] = {a + npix, a + 2 * (size_t)npix};
   const int flat = (npix + kBlock - 1) / kBlock;
   const dim3 tiles((w + kLevelX - 1) / kLevelX, (rows + kLevelY - 1) / kLevelY);
-  const bool guided = j.form != Form::Plain, adaptive = j.form == Form::Adaptive;
+  const bool guided = j.form != Form::Plain, adaptive = j.form == Form::Adaptive, history = j.form == Form::History;
   const V4 *planes = reinterpret_cast<const V4*>(j.f.planes), *noise = reinterpret_cast<const V4*>(j.f.noise);
   if (adaptive)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_denoise_prepare<Form::Adaptive, const V4* __restrict__, const ptad::Cnt* __restrict__, int, int>), dim3(flat), dim3(kBlock),
                        0, stream, npix, j.f.rgb_sum, planes, noise, d.cnt, d.T, d.M, P.keep_albedo, n, p, a, col[0]);
+  else if (history)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_denoise_prepare<Form::History, const V4* __restrict__, const V4* __restrict__, const V4* __restrict__, float, float, float>),
+                       dim3(flat), dim3(kBlock), 0, stream, npix, j.f.rgb_sum, planes, noise, d.C, d.VC, d.Tf, d.Df, d.samples, P.keep_albedo, n, p, a, col[0]);
   else if (guided)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_denoise_prepare<Form::Guided, const V4* __restrict__, float, float>), dim3(flat), dim3(kBlock), 0, stream, npix, j.f.rgb_sum,
                        planes, noise, d.Tf, d.Df, P.keep_albedo, n, p, a, col[0]);
@@ -129,18 +142,20 @@ int pt_denoise_launch(hipStream_t stream, const ptdn::Job& j, void* workspace_de
 }
 
 // pt_internal.h.  Plain: samples.  Guided: the fold counters M = groups, T = iters -> ptnz::fold_scalars' Tf, Df.  Adaptive: (T, M) for
-// every pixel of the uniform state; whoever has a count plane sets div.cnt afterwards.
+// every pixel of the uniform state; whoever has a count plane sets div.cnt afterwards.  History: the guided form's two and samples;
+// whoever has the planes C and VC sets div.C and div.VC (a launch) or f.current and f.current_var (the host loop) afterwards.
 int pt_denoise_resolve(const char* who, ptdn::Form form, float samples, int groups, int64_t iters, const PtDenoiseOptions* opt, ptdn::Job* j) {
   if (form == Form::Plain && !(samples > 0.0f)) return pt_fail("%s: samples must be positive", who);
-  if (form == Form::Guided) {
+  if (form == Form::Guided || form == Form::History) {
     if (groups < 2) return pt_fail("%s: %d group(s) folded; a variance needs at least 2 (pt_noise_fold after each group of iterations)", who, groups);
     if (iters < groups) return pt_fail("%s: %d groups cannot hold %lld iterations (every group holds at least one)", who, groups, (long long)iters);
   }
   *j = ptdn::Job{};
   j->form = form;
-  if (const char* msg = ptdn::resolve(opt, &j->P, form == Form::Plain ? 4.0f : ptdn::kGuidedSigmaColor)) return pt_fail("%s: %s", who, msg);
+  if (const char* msg = ptdn::resolve(opt, &j->P, form == Form::Plain ? 4.0f : form == Form::History ? ptdn::kHistorySigmaColor : ptdn::kGuidedSigmaColor)) return pt_fail("%s: %s", who, msg);
   if (form == Form::Plain) j->div.Tf = samples;
-  if (form == Form::Guided) {
+  if (form == Form::History) j->div.samples = samples;
+  if (form == Form::Guided || form == Form::History) {
     const ptnz::Fold f = ptnz::fold_scalars(1, groups, iters);
     j->div.Tf = f.Tf, j->div.Df = f.Df;
   }
@@ -159,6 +174,24 @@ int pt_denoise_adaptive_check(const char* who, int w, int rows, const float* rgb
   return pt_denoise_resolve(who, Form::Adaptive, 0.0f, 0, 0, opt, j);
 }
 
+// What the host and stage forms of the history filter refuse, in the order of pt_history_denoise: the arrays' shape, samples, the options,
+// the folds' counters, samples != (float)iters, C without VC, a null output.
+int pt_history_denoise_check(const char* who, int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, int groups, int64_t iters,
+                             float samples, const float* current_plane, const float* current_var, const PtDenoiseOptions* opt, const float* rgb_avg, ptdn::Job* j) {
+  if (w <= 0 || rows <= 0 || (int64_t)w * rows > (1ll << 30)) return pt_fail("%s: a frame of %d x %d pixels is not supported", who, w, rows);
+  if (!rgb_sum || !planes || !noise_planes) return pt_fail("%s: null argument", who);
+  if (pt_history_check_samples(who, samples)) return -1;
+  ptdn::Params P{};  // (the options before the folds' counters: pt_denoise_resolve alone would look at the counters first)
+  if (const char* msg = ptdn::resolve(opt, &P, ptdn::kHistorySigmaColor)) return pt_fail("%s: %s", who, msg);
+  if (pt_denoise_resolve(who, Form::History, samples, groups, iters, opt, j)) return -1;
+  if (pt_history_check_fold_samples(who, samples, iters)) return -1;
+  if (!current_plane != !current_var)
+    return pt_fail("%s: the current plane %s its variance: both or neither (a lookup made with PT_HISTORY_VARIANCE gives both)", who,
+                   current_plane ? "comes without" : "is absent, but not");
+  if (!rgb_avg) return pt_fail("%s: null buffer", who);
+  return 0;
+}
+
 namespace {
 // The host entry points: what they refuse (the adaptive form: pt_denoise_adaptive_check), then the one host loop.  want_avg: rgb_avg
 // is the output (the variance variants have none and ask for no level).
@@ -169,7 +202,7 @@ int host_filter(const char* who, Form form, int w, int rows, const float* rgb_su
     if (want_avg && !rgb_avg) return pt_fail("%s: null argument", who);
     if (pt_denoise_adaptive_check(who, w, rows, rgb_sum, planes, noise_planes, counts, opt, &j)) return -1;
   } else {
-    if (w <= 0 || rows <= 0 || (int64_t)w * rows > (1ll << 30) || !rgb_sum || !planes || (form == Form::Guided && !noise_planes) || (want_avg && !rgb_avg))
+    if (w <= 0 || rows <= 0 || (int64_t)w * rows > (1ll << 30) || !rgb_sum || !planes || (form != Form::Plain && !noise_planes) || (want_avg && !rgb_avg))
       return pt_fail("%s: bad argument", who);
     if (pt_denoise_resolve(who, form, samples, groups, iters, opt, &j)) return -1;
   }
@@ -191,6 +224,15 @@ int pt_denoise_guided_variance_host(int w, int rows, const float* rgb_sum, const
                                     const PtDenoiseOptions* opt, float* var_raw, float* var_0) {
   return host_filter("pt_denoise_guided_variance_host", Form::Guided, w, rows, rgb_sum, planes, noise_planes, nullptr, 0.0f, groups, iters, opt, false, nullptr,
                      var_raw, var_0);
+}
+int pt_history_denoise_host(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, int groups, int64_t iters, float samples,
+                            const float* current_plane, const float* current_var, const PtDenoiseOptions* opt, float* rgb_avg) {
+  ptdn::Job j{};
+  if (pt_history_denoise_check("pt_history_denoise_host", w, rows, rgb_sum, planes, noise_planes, groups, iters, samples, current_plane, current_var, opt, rgb_avg, &j))
+    return -1;
+  j.f = {w, rows, rgb_sum, planes, noise_planes, current_plane, current_var};
+  ptdn::denoise_host(j, nullptr, rgb_avg);
+  return 0;
 }
 int pt_denoise_adaptive_host(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, const int32_t* counts,
                              const PtDenoiseOptions* opt, float* rgb_avg) {

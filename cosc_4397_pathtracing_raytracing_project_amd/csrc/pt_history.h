@@ -7,9 +7,17 @@
 // denormals kept), so the planes do not depend on the arithmetic mode of the build or on the side they are computed on.  Plain C++
 // apart from PT_HD.
 //
+//
+// The variance side (PT_HISTORY_VARIANCE; capture_pixel_of<true>, reproject_pixel_of<true>): two more planes, VK = the per-channel
+// variance of K0.xyz and VC = VK resampled beside C, so that the blend has a variance the guided filter can follow
+// (pt_history_denoise: ptdn::Form::History in pt_denoise.h, whose prepare runs blend_component and blend_variance below).  The
+// <false> instantiations are the bodies as they stood before the variance side existed.
+//
 // Out of scope (pt_amd.h says the same): pt_group_* (a context's interleaved rows cannot look up their neighbours), feeding the
-// history into the noise estimate, the filters or adaptive sampling, motion of anything but the camera, and correcting the smoothing
-// the bilinear lookup adds — the carried image is a biased estimator.
+// history into the noise estimate or adaptive sampling, feeding the FILTERED image back into the history (K keeps the unfiltered
+// blend), a view with fewer than 2 folds (1 spp per frame), a spatial variance fallback for disoccluded pixels, motion of anything
+// but the camera, and correcting the smoothing the bilinear lookup adds — the carried image is a biased estimator, and the carried
+// variance is interpolated linearly (as SVGF interpolates its moments), which overstates it: the lookup's smoothing lowers the true one.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -28,6 +36,8 @@ struct F4 {  // a caller's host array of floats promises no more than float alig
 constexpr int kKeptPlanes = PT_HISTORY_KEPT_PLANES;  // K0 colour | weight, K1 position | id, K2 normal | 0
 constexpr int kPlanes = kKeptPlanes + 1;             // ... and the current plane C
 static_assert(kPlanes * sizeof(V4) == 64, "pt_amd.h documents 64 bytes of state per pixel");
+constexpr int kVarPlanes = 2;  // the variance state, a buffer of its own: VK beside K0, VC beside C
+static_assert(kVarPlanes * sizeof(V4) == 32, "pt_amd.h documents 32 bytes of variance state per pixel");
 constexpr float kMinWeight = 0.015625f;  // a lookup with less bilinear weight than 1/64 left carries nothing
 
 // PtHistoryOptions with the defaults filled in.  A test that is switched off keeps its flag, not a sentinel value, so that the
@@ -110,6 +120,36 @@ PT_HD float blend_component(float S, float samples, float h, float Th) {
   return a / d;
 }
 
+// The variance the fold's planes give one component of the mean of the new samples (pt_noise.h fold_component's last two lines, on
+// the planes it left): Tf = (float)T, Df = (float)(M - 1) * Tf.  ptdn::guided_variance is this and the albedo step.
+PT_HD float sample_variance(float prev, float q, float Tf, float Df) {
+#pragma clang fp contract(off)
+  const float d = q - (prev * prev) / Tf;
+  return (d > 0.0f ? d : 0.0f) / Df;
+}
+// The variance of the blend of one component: vn of the new samples' mean, vh of the history's colour.  C absent: Th = vh = +0.
+PT_HD float blend_variance(float vn, float samples, float vh, float Th) {
+#pragma clang fp contract(off)
+  const float dn = samples + Th;
+  const float wn = samples / dn;
+  const float wh = Th / dn;
+  return (wn * wn) * vn + (wh * wh) * vh;
+}
+// What the variance side of a capture reads and writes: the fold's two planes with their divisors, VC (or nullptr: absent) and VK.
+template <typename P4>
+struct VarCapture {
+  const P4* noise;
+  float Tf, Df;
+  const P4* VC;
+  P4* VK;
+};
+// ... and of a reprojection: VK beside K0, VC beside C.
+template <typename P4>
+struct VarReproject {
+  const P4* VK;
+  P4* VC;
+};
+
 // Pixel i of a tile of npix pixels: rgb_avg[3 i ..] = the blend.  C: the current plane, or nullptr (absent).
 template <typename P4>
 PT_HD void blend_pixel(size_t i, const float* S, float samples, const P4* C, float* rgb_avg) {
@@ -119,9 +159,20 @@ PT_HD void blend_pixel(size_t i, const float* S, float samples, const P4* C, flo
   rgb_avg[3 * i + 2] = blend_component(S[3 * i + 2], samples, c.z, c.w);
 }
 
-// Pixel i: the kept planes K (kKeptPlanes planes of npix) from the SUM image, the feature sums and the current plane (or nullptr).
+// The variance side of a capture: VK[i] = the variance of the blend K0.xyz; Th = C.w of the pixel (C absent: +0).
 template <typename P4>
-PT_HD void capture_pixel(size_t i, size_t npix, const float* S, const P4* feat, const P4* C, float samples, P4* K) {
+PT_HD void capture_variance_pixel(size_t i, size_t npix, float samples, float Th, const VarCapture<P4>& var) {
+#pragma clang fp contract(off)
+  const P4 prev = var.noise[i], q = var.noise[npix + i];
+  const P4 vh = var.VC ? var.VC[i] : P4{0.0f, 0.0f, 0.0f, 0.0f};
+  var.VK[i] = P4{blend_variance(sample_variance(prev.x, q.x, var.Tf, var.Df), samples, vh.x, Th),
+                 blend_variance(sample_variance(prev.y, q.y, var.Tf, var.Df), samples, vh.y, Th),
+                 blend_variance(sample_variance(prev.z, q.z, var.Tf, var.Df), samples, vh.z, Th), 0.0f};
+}
+// Pixel i: the kept planes K (kKeptPlanes planes of npix) from the SUM image, the feature sums and the current plane (or nullptr).
+// kVar: also VK[i], from `var` (read only then).
+template <bool kVar, typename P4>
+PT_HD void capture_pixel_of(size_t i, size_t npix, const float* S, const P4* feat, const P4* C, float samples, P4* K, const VarCapture<P4>& var) {
 #pragma clang fp contract(off)
   const Surface s = surface(i, npix, feat);
   const P4 c = C ? C[i] : P4{0.0f, 0.0f, 0.0f, 0.0f};
@@ -129,16 +180,24 @@ PT_HD void capture_pixel(size_t i, size_t npix, const float* S, const P4* feat, 
             blend_component(S[3 * i + 2], samples, c.z, c.w), samples + c.w};
   K[npix + i] = P4{s.px, s.py, s.pz, bits_float(s.id)};
   K[2 * npix + i] = P4{s.nx, s.ny, s.nz, 0.0f};
+  if constexpr (kVar) capture_variance_pixel(i, npix, samples, c.w, var);
+}
+template <typename P4>
+PT_HD void capture_pixel(size_t i, size_t npix, const float* S, const P4* feat, const P4* C, float samples, P4* K) {
+  capture_pixel_of<false>(i, npix, S, feat, C, samples, K, VarCapture<P4>{});
 }
 
 // Tile pixel i = (x, r): the history K as seen through the kept camera, resampled at this pixel's first hit.  reject: one byte per
 // geom (num_geoms of them), read unless keep_view_dependent; an id outside 1 .. num_geoms is rejected like a listed geom.  A gather:
-// of each tap K1 is read first, then K2, and K0 only when the tap passed.
-template <typename P4>
-PT_HD P4 reproject_pixel(size_t i, const View& v, const P4* K, const P4* feat, const uint8_t* reject, int32_t num_geoms, const Params& P) {
+// of each tap K1 is read first, then K2, and K0 only when the tap passed.  kVar: VK(q) is read after K0, for a tap that passed only;
+// vh receives VC's value for the pixel, all zero wherever the pixel is rejected (it is not touched otherwise).
+template <bool kVar, typename P4>
+PT_HD P4 reproject_pixel_of(size_t i, const View& v, const P4* K, const P4* feat, const uint8_t* reject, int32_t num_geoms, const Params& P, const P4* VK,
+                            P4& vh) {
 #pragma clang fp contract(off)
   const size_t npix = (size_t)v.W * v.R;
   const P4 zero{0.0f, 0.0f, 0.0f, 0.0f};
+  if constexpr (kVar) vh = zero;
   const Surface s = surface(i, npix, feat);
   if (!s.hit) return zero;
   if (!P.keep_view_dependent && (s.id < 1 || s.id > num_geoms || reject[s.id - 1])) return zero;
@@ -153,6 +212,7 @@ PT_HD P4 reproject_pixel(size_t i, const View& v, const P4* K, const P4* feat, c
   const int ix = (int)fx, iy = (int)fy - v.row0;  // in range: the comparisons above were made in float
   const float tol = P.plane_tol * dz;
   float accx = 0.0f, accy = 0.0f, accz = 0.0f, tacc = 0.0f, wsum = 0.0f;
+  [[maybe_unused]] float vaccx = 0.0f, vaccy = 0.0f, vaccz = 0.0f;
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int qr = iy + j;
@@ -175,12 +235,22 @@ PT_HD P4 reproject_pixel(size_t i, const View& v, const P4* K, const P4* feat, c
       const float b = (t ? ax : 1.0f - ax) * (j ? ay : 1.0f - ay);
       accx = accx + b * k0.x, accy = accy + b * k0.y, accz = accz + b * k0.z;
       tacc = tacc + b * k0.w;
+      if constexpr (kVar) {
+        const P4 vk = VK[q];
+        vaccx = vaccx + b * vk.x, vaccy = vaccy + b * vk.y, vaccz = vaccz + b * vk.z;
+      }
       wsum = wsum + b;
     }
   }
   if (!(wsum >= kMinWeight)) return zero;
   const float tw = tacc / wsum;
+  if constexpr (kVar) vh = P4{vaccx / wsum, vaccy / wsum, vaccz / wsum, 0.0f};
   return P4{accx / wsum, accy / wsum, accz / wsum, tw < P.cap ? tw : P.cap};
+}
+template <typename P4>
+PT_HD P4 reproject_pixel(size_t i, const View& v, const P4* K, const P4* feat, const uint8_t* reject, int32_t num_geoms, const Params& P) {
+  P4 unused;
+  return reproject_pixel_of<false>(i, v, K, feat, reject, num_geoms, P, static_cast<const P4*>(nullptr), unused);
 }
 
 // The whole tile on the host.
@@ -192,6 +262,20 @@ inline void reproject_host(const View& v, const float* K, const float* feat, con
   const size_t npix = (size_t)v.W * v.R;
   F4* out = reinterpret_cast<F4*>(C);
   for (size_t i = 0; i < npix; ++i) out[i] = reproject_pixel(i, v, reinterpret_cast<const F4*>(K), reinterpret_cast<const F4*>(feat), reject, num_geoms, P);
+}
+// ... and with the variance side: VK beside K's capture (which capture_host makes), C and VC in one pass of the lookup.
+inline void capture_variance_host(size_t npix, const float* noise, float Tf, float Df, float samples, const float* C, const float* VC, float* VK) {
+  const F4* c4 = reinterpret_cast<const F4*>(C);
+  const VarCapture<F4> var{reinterpret_cast<const F4*>(noise), Tf, Df, reinterpret_cast<const F4*>(VC), reinterpret_cast<F4*>(VK)};
+  for (size_t i = 0; i < npix; ++i) capture_variance_pixel(i, npix, samples, c4 ? c4[i].w : 0.0f, var);  // (K: capture_host, from the image and the features)
+}
+inline void reproject_variance_host(const View& v, const float* K, const float* feat, const uint8_t* reject, int32_t num_geoms, const Params& P, const float* VK,
+                                    float* C, float* VC) {
+  const size_t npix = (size_t)v.W * v.R;
+  F4 *out = reinterpret_cast<F4*>(C), *vout = reinterpret_cast<F4*>(VC);
+  for (size_t i = 0; i < npix; ++i)
+    out[i] = reproject_pixel_of<true>(i, v, reinterpret_cast<const F4*>(K), reinterpret_cast<const F4*>(feat), reject, num_geoms, P, reinterpret_cast<const F4*>(VK),
+                                      vout[i]);
 }
 inline void blend_host(size_t npix, const float* S, float samples, const float* C, float* rgb_avg) {
   for (size_t i = 0; i < npix; ++i) blend_pixel(i, S, samples, reinterpret_cast<const F4*>(C), rgb_avg);

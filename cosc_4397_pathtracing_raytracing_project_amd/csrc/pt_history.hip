@@ -12,10 +12,15 @@
 //                        view land on neighbouring pixels of the kept one, so the taps of a wave are a few runs of rows of K and
 //                        the four taps of a pixel share lines with its neighbours': the reuse is L1's and L2's, no LDS
 //   k_history_blend      streaming: 12 B of S and (when present) 16 B of C in, 12 B out per pixel
+// The variance side (PT_HISTORY_VARIANCE) is a template parameter of the first two; <false> is the kernel as it stood before, with
+// the arguments it took, and what flags == 0 launches.
+//   k_history_capture<true>    + 32 B of the fold's planes and (when present) 16 B of VC in, 16 B of VK out per pixel
+//   k_history_reproject<true>  + 16 B of VC out per pixel; per tap that passed 16 B of VK, read after K0 at the same index
 #include <hip/hip_runtime.h>
 
 #include "pt_history.h"
 #include "pt_internal.h"
+#include "pt_noise.h"
 
 namespace {
 using pthi::Params;
@@ -23,16 +28,28 @@ using pthi::V4;
 using pthi::View;
 constexpr int kBlock = 256;
 
+// In...: nothing, or the members of pthi::VarCapture one by one (scalars at fixed offsets; the <false> kernel takes what it took)
+template <bool kVar, typename... In>
 __global__ __launch_bounds__(kBlock) void k_history_capture(int npix, const float* __restrict__ S, const V4* __restrict__ feat, const V4* C, float samples,
-                                                            V4* __restrict__ K) {
+                                                            V4* __restrict__ K, In... in) {
   const int i = blockIdx.x * kBlock + threadIdx.x;
-  if (i < npix) pthi::capture_pixel((size_t)i, (size_t)npix, S, feat, C, samples, K);
+  if (i < npix) pthi::capture_pixel_of<kVar>((size_t)i, (size_t)npix, S, feat, C, samples, K, pthi::VarCapture<V4>{in...});
 }
 
+// In...: nothing, or VK and VC
+template <bool kVar, typename... In>
 __global__ __launch_bounds__(kBlock) void k_history_reproject(int npix, View v, const V4* __restrict__ K, const V4* __restrict__ feat,
-                                                              const uint8_t* __restrict__ reject, int num_geoms, Params P, V4* __restrict__ C) {
+                                                              const uint8_t* __restrict__ reject, int num_geoms, Params P, V4* __restrict__ C, In... in) {
   const int i = blockIdx.x * kBlock + threadIdx.x;
-  if (i < npix) C[i] = pthi::reproject_pixel((size_t)i, v, K, feat, reject, num_geoms, P);
+  if (i >= npix) return;
+  if constexpr (kVar) {
+    const auto [VK, VC] = pthi::VarReproject<V4>{in...};
+    V4 vh;
+    C[i] = pthi::reproject_pixel_of<true>((size_t)i, v, K, feat, reject, num_geoms, P, VK, vh);
+    VC[i] = vh;
+  } else {
+    C[i] = pthi::reproject_pixel((size_t)i, v, K, feat, reject, num_geoms, P);
+  }
 }
 
 __global__ __launch_bounds__(kBlock) void k_history_blend(int npix, const float* __restrict__ S, float samples, const V4* __restrict__ C,
@@ -53,9 +70,21 @@ bool bad_frame(int w, int rows) { return w <= 0 || rows <= 0 || rows >= 32768 ||
 int pt_history_capture_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, const float* planes_dev, const void* current_dev, float samples,
                               void* kept_dev) {
   if (pixels <= 0 || pixels > (1 << 30) || !rgb_sum_dev || !planes_dev || !kept_dev || !(samples > 0.0f)) return pt_fail("pt_history_capture: bad argument");
-  hipLaunchKernelGGL(k_history_capture, dim3((pixels + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, pixels, rgb_sum_dev,
+  hipLaunchKernelGGL(k_history_capture<false>, dim3((pixels + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, pixels, rgb_sum_dev,
                      reinterpret_cast<const V4*>(planes_dev), static_cast<const V4*>(current_dev), samples, static_cast<V4*>(kept_dev));
   return launched("pt_history_capture");
+}
+// ... with the variance side: noise_dev the fold's planes, Tf and Df ptnz::fold_scalars' of the folds so far, current_var_dev VC beside
+// current_dev (both or neither), kept_var_dev VK.
+int pt_history_capture_variance_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, const float* planes_dev, const void* current_dev, float samples,
+                                       void* kept_dev, const float* noise_dev, float Tf, float Df, const void* current_var_dev, void* kept_var_dev) {
+  if (pixels <= 0 || pixels > (1 << 30) || !rgb_sum_dev || !planes_dev || !kept_dev || !(samples > 0.0f) || !noise_dev || !(Tf >= 2.0f) || !(Df >= Tf) ||
+      !kept_var_dev || !current_dev != !current_var_dev)
+    return pt_fail("pt_history_capture_ex: bad argument");
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_history_capture<true, const V4*, float, float, const V4*, V4*>), dim3((pixels + kBlock - 1) / kBlock), dim3(kBlock), 0, stream,
+                     pixels, rgb_sum_dev, reinterpret_cast<const V4*>(planes_dev), static_cast<const V4*>(current_dev), samples, static_cast<V4*>(kept_dev),
+                     reinterpret_cast<const V4*>(noise_dev), Tf, Df, static_cast<const V4*>(current_var_dev), static_cast<V4*>(kept_var_dev));
+  return launched("pt_history_capture_ex");
 }
 
 int pt_history_reproject_launch(hipStream_t stream, const pthi::View& v, const void* kept_dev, const float* planes_dev, const uint8_t* reject_dev,
@@ -64,9 +93,22 @@ int pt_history_reproject_launch(hipStream_t stream, const pthi::View& v, const v
   if (!kept_dev || !planes_dev || !current_dev || (!P.keep_view_dependent && (num_geoms < 0 || (num_geoms > 0 && !reject_dev))))
     return pt_fail("pt_history_reproject: bad argument");
   const int npix = v.W * v.R;
-  hipLaunchKernelGGL(k_history_reproject, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, npix, v, static_cast<const V4*>(kept_dev),
+  hipLaunchKernelGGL(k_history_reproject<false>, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, npix, v, static_cast<const V4*>(kept_dev),
                      reinterpret_cast<const V4*>(planes_dev), reject_dev, num_geoms, P, static_cast<V4*>(current_dev));
   return launched("pt_history_reproject");
+}
+// ... with the variance side: kept_var_dev VK, current_var_dev VC.
+int pt_history_reproject_variance_launch(hipStream_t stream, const pthi::View& v, const void* kept_dev, const float* planes_dev, const uint8_t* reject_dev,
+                                         int num_geoms, const pthi::Params& P, void* current_dev, const void* kept_var_dev, void* current_var_dev) {
+  if (bad_frame(v.W, v.R)) return pt_fail("pt_history_reproject_ex: a tile of %d x %d pixels is not supported", v.W, v.R);
+  if (!kept_dev || !planes_dev || !current_dev || !kept_var_dev || !current_var_dev ||
+      (!P.keep_view_dependent && (num_geoms < 0 || (num_geoms > 0 && !reject_dev))))
+    return pt_fail("pt_history_reproject_ex: bad argument");
+  const int npix = v.W * v.R;
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_history_reproject<true, const V4*, V4*>), dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, npix, v,
+                     static_cast<const V4*>(kept_dev), reinterpret_cast<const V4*>(planes_dev), reject_dev, num_geoms, P, static_cast<V4*>(current_dev),
+                     static_cast<const V4*>(kept_var_dev), static_cast<V4*>(current_var_dev));
+  return launched("pt_history_reproject_ex");
 }
 
 int pt_history_blend_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, float samples, const void* current_dev, float* rgb_avg_dev) {
@@ -78,6 +120,11 @@ int pt_history_blend_launch(hipStream_t stream, int pixels, const float* rgb_sum
 
 int pt_history_check_samples(const char* who, float samples) {
   if (!(samples - samples == 0.0f) || !(samples > 0.0f)) return pt_fail("%s: samples must be finite and positive", who);
+  return 0;
+}
+// The variance describes the folded image: the blend's weights must count the samples the folds counted.
+int pt_history_check_fold_samples(const char* who, float samples, int64_t iters) {
+  if (samples != (float)iters) return pt_fail("%s: samples %g, but the folds hold %lld iterations: the variance is that of the folded image", who, (double)samples, (long long)iters);
   return 0;
 }
 int pt_history_resolve_options(const char* who, const PtHistoryOptions* opt, pthi::Params* P) {
@@ -111,6 +158,31 @@ extern "C" int pt_history_reproject_host(int w, int rows, int row0, const PtCame
   if (pt_history_reproject_check("pt_history_reproject_host", w, rows, row0, kept_cam, kept_planes, feature_planes, reject_geom, num_geoms, opt, current_plane, &P))
     return -1;
   pthi::reproject_host(pthi::make_view(*kept_cam, rows, row0), kept_planes, feature_planes, reject_geom, num_geoms, P, current_plane);
+  return 0;
+}
+
+extern "C" int pt_history_capture_variance_host(int pixels, const float* noise_planes, int groups, int64_t iters, float samples, const float* current_plane,
+                                                const float* current_var, float* kept_var) {
+  const char* who = "pt_history_capture_variance_host";
+  if (pixels <= 0 || pixels > (1 << 30) || !noise_planes || !kept_var) return pt_fail("%s: bad argument", who);
+  if (pt_history_check_samples(who, samples)) return -1;
+  if (groups < 2) return pt_fail("%s: %d group(s) folded; a variance needs at least 2 (pt_noise_fold after each group of iterations)", who, groups);
+  if (iters < groups) return pt_fail("%s: %d groups cannot hold %lld iterations (every group holds at least one)", who, groups, (long long)iters);
+  if (pt_history_check_fold_samples(who, samples, iters)) return -1;
+  if (!current_plane != !current_var) return pt_fail("%s: the current plane and its variance come together or not at all", who);
+  const ptnz::Fold f = ptnz::fold_scalars(1, groups, iters);
+  pthi::capture_variance_host((size_t)pixels, noise_planes, f.Tf, f.Df, samples, current_plane, current_var, kept_var);
+  return 0;
+}
+
+extern "C" int pt_history_reproject_variance_host(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
+                                                  const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, const float* kept_var,
+                                                  float* current_plane, float* current_var) {
+  pthi::Params P{};
+  const char* who = "pt_history_reproject_variance_host";
+  if (pt_history_reproject_check(who, w, rows, row0, kept_cam, kept_planes, feature_planes, reject_geom, num_geoms, opt, current_plane, &P)) return -1;
+  if (!kept_var || !current_var) return pt_fail("%s: null argument", who);
+  pthi::reproject_variance_host(pthi::make_view(*kept_cam, rows, row0), kept_planes, feature_planes, reject_geom, num_geoms, P, kept_var, current_plane, current_var);
   return 0;
 }
 

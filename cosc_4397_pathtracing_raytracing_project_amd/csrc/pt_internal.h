@@ -26,6 +26,10 @@ int pt_denoise_resolve(const char* who, ptdn::Form form, float samples, int grou
 int pt_denoise_adaptive_check(const char* who, int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, const int32_t* counts,
                               const PtDenoiseOptions* opt, ptdn::Job* j);
 int pt_denoise_launch(hipStream_t stream, const ptdn::Job& j, void* workspace_dev, const float** rgb_avg_dev);
+// The history form (ptdn::Form::History, pt_history_denoise): what its host and stage entries refuse, in pt_history_denoise's order, and
+// the job resolved; a launch reads the planes C and VC from j->div.C and j->div.VC (both or neither), the host loop from j->f.
+int pt_history_denoise_check(const char* who, int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, int groups, int64_t iters,
+                             float samples, const float* current_plane, const float* current_var, const PtDenoiseOptions* opt, const float* rgb_avg, ptdn::Job* j);
 
 // The noise estimate (pt_noise.hip), on raw device pointers and a stream.  state_dev holds pt_noise_state_bytes(pixels) bytes:
 // PT_NOISE_PLANES planes of `pixels` float4, then one double per PT_NOISE_PIXELS_PER_PARTIAL pixels (k_noise_fold's partial sums),
@@ -95,7 +99,9 @@ struct Params;
 struct View;
 }
 inline size_t pt_history_state_bytes(size_t pixels) { return 64 * pixels; }
+inline size_t pt_history_variance_bytes(size_t pixels) { return 32 * pixels; }  // the variance state: VK, then VC, `pixels` float4 each
 int pt_history_check_samples(const char* who, float samples);
+int pt_history_check_fold_samples(const char* who, float samples, int64_t iters);  // samples == (float)iters, or the refusal
 int pt_history_resolve_options(const char* who, const PtHistoryOptions* opt, pthi::Params* P);
 int pt_history_reproject_check(const char* who, int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
                                const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, const float* current_plane, pthi::Params* P);
@@ -103,4 +109,10 @@ int pt_history_capture_launch(hipStream_t stream, int pixels, const float* rgb_s
                               void* kept_dev);
 int pt_history_reproject_launch(hipStream_t stream, const pthi::View& v, const void* kept_dev, const float* planes_dev, const uint8_t* reject_dev,
                                 int num_geoms, const pthi::Params& P, void* current_dev);
+// The same two with the variance side (PT_HISTORY_VARIANCE): the fold's planes and ptnz::fold_scalars' Tf, Df; VC beside C (both or
+// neither) and VK in the capture, VK and VC in the reprojection.  C and K are what the plain launches write, bit for bit.
+int pt_history_capture_variance_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, const float* planes_dev, const void* current_dev, float samples,
+                                       void* kept_dev, const float* noise_dev, float Tf, float Df, const void* current_var_dev, void* kept_var_dev);
+int pt_history_reproject_variance_launch(hipStream_t stream, const pthi::View& v, const void* kept_dev, const float* planes_dev, const uint8_t* reject_dev,
+                                         int num_geoms, const pthi::Params& P, void* current_dev, const void* kept_var_dev, void* current_var_dev);
 int pt_history_blend_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, float samples, const void* current_dev, float* rgb_avg_dev);

@@ -474,21 +474,54 @@ static int history_admit(const Ctx& g, const char* who) { return admit(g, who, k
 static pthi::V4* history_plane(const Ctx& g, int plane) { return static_cast<pthi::V4*>(g.d_hist) + (size_t)plane * g.N; }
 static const char kNoFeatures[] = "%s: no feature pass has been rendered since the last pt_clear or camera move (pt_render_features)";
 
-int pt_ctx_history_capture(PtContext* c, float samples) {
-  if (need(c, "pt_history_capture")) return -1;
-  Ctx& g = *c;
-  if (history_admit(g, "pt_history_capture")) return -1;
-  if (!g.d_feat || !g.feat_fresh) return pt_fail(kNoFeatures, "pt_history_capture");
-  if (pt_history_check_samples("pt_history_capture", samples)) return -1;
-  HIP_OK(hipSetDevice(g.device));
-  if (ensure(g, g.d_hist, pt_history_state_bytes((size_t)g.N), Zero::on_stream)) return -1;  // the first capture of the context
-  if (pt_history_capture_launch(g.stream, g.N, g.d_image, reinterpret_cast<const float*>(g.d_feat), g.hist_current ? history_plane(g, pthi::kKeptPlanes) : nullptr,
-                                samples, g.d_hist))
-    return -1;
-  g.hist_cam = g.cam;
-  g.hist_kept = true;
+static pthi::V4* history_var_plane(const Ctx& g, int plane) { return static_cast<pthi::V4*>(g.d_hist_var) + (size_t)plane * g.N; }  // 0: VK, 1: VC
+// An undefined flag bit: what the _ex forms refuse right after a failed context.
+static int history_flags(const char* who, uint32_t flags) {
+  if (flags & ~PT_HISTORY_VARIANCE) return pt_fail("%s: undefined flag bit(s) 0x%x (defined: PT_HISTORY_VARIANCE)", who, flags & ~PT_HISTORY_VARIANCE);
   return 0;
 }
+// What the variance needs of the folds: at least two, nothing rendered since, and `samples` the iterations they hold.
+static int history_folds(const Ctx& g, const char* who, float samples) {
+  if (!g.d_noise || g.noise_groups < 1) return pt_fail("%s: nothing has been folded (pt_noise_fold)", who);
+  if (g.noise_groups < 2) return pt_fail("%s: %d group(s) folded; a variance needs at least 2 (pt_noise_fold after each group of iterations)", who, g.noise_groups);
+  if (admit(g, who, kFoldedAll)) return -1;
+  return pt_history_check_fold_samples(who, samples, g.noise_iters);
+}
+static int history_current_variance(const Ctx& g, const char* who) {
+  if (g.hist_current && !g.hist_var_current)
+    return pt_fail("%s: the current plane has no variance: the lookup was made without PT_HISTORY_VARIANCE (pt_history_reproject_ex)", who);
+  return 0;
+}
+
+// ex: the _ex form, which refuses an undefined flag bit and carries its own name; flags == 0 is the old call either way.
+static int history_capture(PtContext* c, const char* who, float samples, uint32_t flags, bool ex) {
+  if (need(c, who)) return -1;
+  Ctx& g = *c;
+  if (ex && (admit(g, who, kNotFailed) || history_flags(who, flags))) return -1;
+  if (history_admit(g, who)) return -1;
+  if (!g.d_feat || !g.feat_fresh) return pt_fail(kNoFeatures, who);
+  if (pt_history_check_samples(who, samples)) return -1;
+  const bool var = (flags & PT_HISTORY_VARIANCE) != 0;
+  if (var && (history_folds(g, who, samples) || history_current_variance(g, who))) return -1;
+  HIP_OK(hipSetDevice(g.device));
+  if (ensure(g, g.d_hist, pt_history_state_bytes((size_t)g.N), Zero::on_stream)) return -1;  // the first capture of the context
+  if (var && ensure(g, g.d_hist_var, pt_history_variance_bytes((size_t)g.N), Zero::on_stream)) return -1;  // ... with variance
+  const pthi::V4* current = g.hist_current ? history_plane(g, pthi::kKeptPlanes) : nullptr;
+  if (var) {
+    const ptnz::Fold f = ptnz::fold_scalars(1, g.noise_groups, g.noise_iters);
+    if (pt_history_capture_variance_launch(g.stream, g.N, g.d_image, reinterpret_cast<const float*>(g.d_feat), current, samples, g.d_hist,
+                                           static_cast<const float*>(g.d_noise), f.Tf, f.Df, current ? history_var_plane(g, 1) : nullptr, history_var_plane(g, 0)))
+      return -1;
+  } else if (pt_history_capture_launch(g.stream, g.N, g.d_image, reinterpret_cast<const float*>(g.d_feat), current, samples, g.d_hist)) {
+    return -1;
+  }
+  g.hist_cam = g.cam;
+  g.hist_kept = true;
+  g.hist_var_kept = var;  // a plain capture: kept without variance
+  return 0;
+}
+int pt_ctx_history_capture(PtContext* c, float samples) { return history_capture(c, "pt_history_capture", samples, 0u, false); }
+int pt_ctx_history_capture_ex(PtContext* c, float samples, uint32_t flags) { return history_capture(c, "pt_history_capture_ex", samples, flags, true); }
 
 // reject_geom of pt_amd.h from the tables the renderer holds: the geoms' material ids (host) and the materials (device).  Blocking;
 // once per context.
@@ -507,23 +540,70 @@ static int history_reject_table(Ctx& g) {
   return 0;
 }
 
-int pt_ctx_history_reproject(PtContext* c, const PtHistoryOptions* opt) {
-  if (need(c, "pt_history_reproject")) return -1;
+static int history_reproject(PtContext* c, const char* who, const PtHistoryOptions* opt, uint32_t flags, bool ex) {
+  if (need(c, who)) return -1;
   Ctx& g = *c;
-  if (history_admit(g, "pt_history_reproject")) return -1;
-  if (!g.d_hist || !g.hist_kept) return pt_fail("pt_history_reproject: nothing has been captured (pt_history_capture)");
-  if (!g.d_feat || !g.feat_fresh) return pt_fail(kNoFeatures, "pt_history_reproject");
+  if (ex && (admit(g, who, kNotFailed) || history_flags(who, flags))) return -1;
+  if (history_admit(g, who)) return -1;
+  if (!g.d_hist || !g.hist_kept) return pt_fail("%s: nothing has been captured (pt_history_capture)", who);
+  if (!g.d_feat || !g.feat_fresh) return pt_fail(kNoFeatures, who);
   pthi::Params P{};
-  if (pt_history_resolve_options("pt_history_reproject", opt, &P)) return -1;
+  if (pt_history_resolve_options(who, opt, &P)) return -1;
+  const bool var = (flags & PT_HISTORY_VARIANCE) != 0;
+  if (var && (!g.d_hist_var || !g.hist_var_kept))
+    return pt_fail("%s: nothing has been captured with variance (pt_history_capture_ex with PT_HISTORY_VARIANCE)", who);
   HIP_OK(hipSetDevice(g.device));
   if (history_reject_table(g)) return -1;
   const int W = g.cam.resolution[0];
   const pthi::View v = pthi::make_view(g.hist_cam, g.N / W, g.pixel_begin / W);
-  if (pt_history_reproject_launch(g.stream, v, g.d_hist, reinterpret_cast<const float*>(g.d_feat), g.d_hist_reject, (int)g.camera_base.geoms.size(), P,
-                                  history_plane(g, pthi::kKeptPlanes)))
+  const float* feat = reinterpret_cast<const float*>(g.d_feat);
+  const int num_geoms = (int)g.camera_base.geoms.size();
+  if (var ? pt_history_reproject_variance_launch(g.stream, v, g.d_hist, feat, g.d_hist_reject, num_geoms, P, history_plane(g, pthi::kKeptPlanes),
+                                                 history_var_plane(g, 0), history_var_plane(g, 1))
+          : pt_history_reproject_launch(g.stream, v, g.d_hist, feat, g.d_hist_reject, num_geoms, P, history_plane(g, pthi::kKeptPlanes)))
     return -1;
   g.hist_current = true;
+  g.hist_var_current = var;
   return 0;
+}
+int pt_ctx_history_reproject(PtContext* c, const PtHistoryOptions* opt) { return history_reproject(c, "pt_history_reproject", opt, 0u, false); }
+int pt_ctx_history_reproject_ex(PtContext* c, const PtHistoryOptions* opt, uint32_t flags) {
+  return history_reproject(c, "pt_history_reproject_ex", opt, flags, true);
+}
+
+// ---- the guided filter over the blend (ptdn::Form::History) --------------------------------------------------------------
+// Everything pt_history_denoise refuses but the null buffer, in its order; the job resolved.
+static int history_denoise_refusal(const Ctx& g, const char* who, float samples, const PtDenoiseOptions* opt, ptdn::Job* j) {
+  if (history_admit(g, who)) return -1;
+  if (!g.d_feat || !g.feat_fresh) return pt_fail(kNoFeatures, who);
+  if (pt_history_check_samples(who, samples)) return -1;
+  ptdn::Params P{};
+  if (const char* msg = ptdn::resolve(opt, &P, ptdn::kHistorySigmaColor)) return pt_fail("%s: %s", who, msg);
+  if (history_folds(g, who, samples) || history_current_variance(g, who)) return -1;
+  return pt_denoise_resolve(who, ptdn::Form::History, samples, g.noise_groups, g.noise_iters, opt, j);
+}
+int pt_ctx_history_denoise_device(PtContext* c, float samples, const PtDenoiseOptions* opt, const float** rgb_dev) {
+  const char* who = "pt_history_denoise";
+  if (need(c, who)) return -1;
+  Ctx& g = *c;
+  ptdn::Job j{};
+  if (history_denoise_refusal(g, who, samples, opt, &j)) return -1;
+  if (!rgb_dev) return pt_fail("%s: null buffer", who);
+  HIP_OK(hipSetDevice(g.device));
+  if (ensure(g, g.d_denoise, pt_denoise_workspace_bytes((size_t)g.N))) return -1;  // the first denoise call of the context, of any kind
+  const int W = g.cam.resolution[0];
+  j.f = {W, g.N / W, g.d_image, reinterpret_cast<const float*>(g.d_feat), static_cast<const float*>(g.d_noise)};
+  if (g.hist_current) {
+    j.div.C = reinterpret_cast<const ptdn::V4*>(history_plane(g, pthi::kKeptPlanes));
+    j.div.VC = reinterpret_cast<const ptdn::V4*>(history_var_plane(g, 1));
+  }
+  return pt_denoise_launch(g.stream, j, g.d_denoise, rgb_dev);
+}
+int pt_ctx_history_denoise(PtContext* c, float samples, const PtDenoiseOptions* opt, float* rgb_avg_host) {
+  if (need(c, "pt_history_denoise")) return -1;
+  ptdn::Job j{};
+  if (history_denoise_refusal(*c, "pt_history_denoise", samples, opt, &j)) return -1;  // (before the null buffer)
+  return copy_out(c, "pt_history_denoise", rgb_avg_host, 3, [&](const float** d) { return pt_ctx_history_denoise_device(c, samples, opt, d); });
 }
 
 int pt_ctx_history_resolve_device(PtContext* c, float samples, const float** rgb_dev) {
@@ -557,14 +637,29 @@ int pt_ctx_readback_history(PtContext* c, float* kept_planes, float* current_pla
   return 0;
 }
 
+int pt_ctx_readback_history_variance(PtContext* c, float* kept_var, float* current_var) {
+  if (need(c, "pt_readback_history_variance")) return -1;
+  Ctx& g = *c;
+  HIP_OK(hipSetDevice(g.device));
+  const size_t plane = (size_t)g.N * sizeof(pthi::V4);
+  const bool kept = g.d_hist_var && g.hist_var_kept, current = g.d_hist_var && g.hist_var_current;
+  if (kept_var && kept) HIP_OK(hipMemcpyAsync(kept_var, history_var_plane(g, 0), plane, hipMemcpyDeviceToHost, g.stream));
+  if (current_var && current) HIP_OK(hipMemcpyAsync(current_var, history_var_plane(g, 1), plane, hipMemcpyDeviceToHost, g.stream));
+  if (pt_ctx_sync(c)) return -1;
+  if (kept_var && !kept) std::fill(kept_var, kept_var + 4 * (size_t)g.N, 0.0f);
+  if (current_var && !current) std::fill(current_var, current_var + 4 * (size_t)g.N, 0.0f);
+  return 0;
+}
+
 int pt_ctx_history_drop(PtContext* c) {
   if (need(c, "pt_history_drop")) return -1;
   Ctx& g = *c;
   if (g.d_hist) {  // forgotten, not freed: a readback sees zeros, a reprojection has nothing to read
     HIP_OK(hipSetDevice(g.device));
     HIP_OK(hipMemsetAsync(g.d_hist, 0, pt_history_state_bytes((size_t)g.N), g.stream));
+    if (g.d_hist_var) HIP_OK(hipMemsetAsync(g.d_hist_var, 0, pt_history_variance_bytes((size_t)g.N), g.stream));
   }
-  g.hist_kept = g.hist_current = false;
+  g.hist_kept = g.hist_current = g.hist_var_kept = g.hist_var_current = false;
   return 0;
 }
 

@@ -3,7 +3,7 @@
 // state.iterations iterations, write the PNG saveImage() would write.  Flags exist only because
 // the reference takes resolution, iteration count and depth from the scene file (scene.cpp:103-114).
 //
-//   pt_render SCENE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] [--orbit N [--device-tables] [--reproject [--history-cap C]]]
+//   pt_render SCENE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] [--orbit N [--device-tables] [--reproject [--history-cap C] [--denoise-history]]]
 //                       [--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa]
 //                       [--preview N] [--convergence N | --reference FILE.pfm] [--clean-db X] [--features]
 //                       [--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]]
@@ -62,7 +62,10 @@
 // frame's line ends `, tables a ms, rearm b ms (device|host tables)` from pt_get_set_camera_times.
 // --reproject (with --orbit, excludes --gpus / --devices): the image is carried from view to view (pt_history_*).  After a frame's render
 // comes pt_render_features(1, 1); from frame 1 on pt_history_reproject; pt_history_resolve, written next to the raw frame as
-// <base>.orbit<fff>.reprojected.png (.pfm with --pfm); pt_history_capture; then the move.  Frame f renders iterations f * spp + 1 ..
+// <base>.orbit<fff>.reprojected.png (.pfm with --pfm); pt_history_capture; then the move.  --denoise-history (with --reproject, --spp >= 2;
+// takes the --denoise-* options, sigma C's default being 8): a frame's iterations are rendered in groups of ceil(spp / 4) with
+// pt_noise_fold after each, the lookup and the capture carry the variance (pt_history_*_ex with PT_HISTORY_VARIANCE), and after the
+// resolve pt_history_denoise writes <base>.orbit<fff>.reprojected.denoised.png (.pfm); the history keeps the unfiltered blend.  Frame f renders iterations f * spp + 1 ..
 // (f + 1) * spp instead of 1 .. spp (printed once).  --history-cap C: PtHistoryOptions.cap (default 32).  Prints per frame
 // `history: frame f: <valid> of <pixels> pixels carried, mean weight <x>`.
 // Output name: PREFIX.<spp>samp.png, or with --stamp the reference's own
@@ -86,7 +89,7 @@
 int main(int argc, char** argv) {
   if (argc < 2) {
     std::printf("Usage: %s SCENEFILE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] "
-                "[--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa] [--orbit N [--device-tables] [--reproject [--history-cap C]]] [--preview N] "
+                "[--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa] [--orbit N [--device-tables] [--reproject [--history-cap C] [--denoise-history]]] [--preview N] "
                 "[--convergence N | --reference FILE.pfm] [--clean-db X] [--features] "
                 "[--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]] [--denoise-guided] [--until-db X [--until-group G] [--adaptive F [--denoise-adaptive]]] "
                 "[--adaptive-threshold E [--adaptive-cap F] [--adaptive-min-pixels P] [--until-group G] [--denoise-adaptive]]\n", argv[0]);
@@ -99,6 +102,7 @@ int main(int argc, char** argv) {
   int convergence = 0, until_group = 0, orbit = 0;  // orbit > 0: --orbit N
   bool device_tables = false;                       // --device-tables
   bool reproject = false;                           // --reproject
+  bool dn_history = false;                          // --denoise-history
   float history_cap = 0.0f;                         // --history-cap C (0: the default)
   bool history_cap_given = false;
   bool until = false, until_group_given = false;
@@ -125,6 +129,7 @@ int main(int argc, char** argv) {
     }
     else if (!std::strcmp(argv[i], "--device-tables")) device_tables = true;
     else if (!std::strcmp(argv[i], "--reproject")) reproject = true;
+    else if (!std::strcmp(argv[i], "--denoise-history")) dn_history = true;  // the blend filtered with the variance the history carries
     else if (!std::strcmp(argv[i], "--history-cap") && i + 1 < argc) {
       history_cap = (float)std::atof(argv[++i]);
       history_cap_given = true;
@@ -267,8 +272,12 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--denoise-adaptive wants --adaptive or --adaptive-threshold (the filter of an adaptively sampled image)\n");
     return 1;
   }
-  if (!denoise && !guided && !dn_adaptive && (dn_opt.levels || dn_opt.keep_albedo || dn_opt.sigma_color != 0.0f || dn_opt.sigma_normal != 0.0f || dn_opt.sigma_position != 0.0f)) {
-    std::fprintf(stderr, "--denoise-levels, --denoise-sigma and --denoise-keep-albedo want --denoise, --denoise-guided or --denoise-adaptive\n");
+  if (dn_history && (orbit <= 0 || !reproject)) {
+    std::fprintf(stderr, "--denoise-history wants --orbit N --reproject (it filters the blend of the view with the reprojected history)\n");
+    return 1;
+  }
+  if (!denoise && !guided && !dn_adaptive && !dn_history && (dn_opt.levels || dn_opt.keep_albedo || dn_opt.sigma_color != 0.0f || dn_opt.sigma_normal != 0.0f || dn_opt.sigma_position != 0.0f)) {
+    std::fprintf(stderr, "--denoise-levels, --denoise-sigma and --denoise-keep-albedo want --denoise, --denoise-guided, --denoise-adaptive or --denoise-history\n");
     return 1;
   }
   if (denoise || guided || dn_adaptive) features = true;
@@ -345,6 +354,10 @@ int main(int argc, char** argv) {
   int iters = (int)scene->state.iterations;  // with --until-db the cap, until the render has said how many it took
   if (guided && iters < 2) {
     std::fprintf(stderr, "--denoise-guided wants at least 2 iterations (--spp): a variance needs two groups\n");
+    return 1;
+  }
+  if (dn_history && iters < 2) {
+    std::fprintf(stderr, "--denoise-history wants at least 2 iterations (--spp): a variance needs two groups per view\n");
     return 1;
   }
   // --denoise-guided without --until-db: the iterations in groups of G (default ceil(spp / 4)), a fold after each
@@ -451,7 +464,7 @@ int main(int argc, char** argv) {
     scene->state.image.resize((size_t)W * H * 3);
     // --reproject: the history of the views before (pt_history_*).  The RNG is keyed by (iteration, pixel): the same iteration numbers
     // after a small move would repeat almost the same paths, and the history would add nothing — every frame gets numbers of its own.
-    std::vector<float> carried, current;
+    std::vector<float> carried, current, filtered;
     PtHistoryOptions hopt{};
     hopt.cap = history_cap;
     if (reproject) {
@@ -461,6 +474,7 @@ int main(int argc, char** argv) {
       }
       carried.resize((size_t)W * H * 3);
       current.resize((size_t)W * H * 4);
+      if (dn_history) filtered.resize((size_t)W * H * 3);
       std::printf("history: frame f renders iterations f * %d + 1 .. (f + 1) * %d, not 1 .. %d: repeated iteration numbers would repeat the paths\n", iters, iters, iters);
     }
     const float step = (float)(2.0 * 3.14159265358979323846 / orbit);
@@ -484,8 +498,16 @@ int main(int argc, char** argv) {
       }
       const auto t0 = std::chrono::high_resolution_clock::now();
       const int iter_first = reproject ? f * iters + 1 : 1;
-      if (grp ? (pt_group_render(grp, 1, iters) || pt_group_gather(grp, scene->state.image.data()))
-              : (pt_render(iter_first, iters) || pt_readback(scene->state.image.data()))) {
+      bool render_failed = false;
+      if (dn_history) {  // the view's iterations in groups of ceil(spp / 4), a fold after each: the variance of the view's own samples
+        for (int done = 0; done < iters && !render_failed; done += fold_group)
+          render_failed = pt_render(iter_first + done, std::min(fold_group, iters - done)) || pt_noise_fold();
+        render_failed = render_failed || pt_readback(scene->state.image.data());
+      } else {
+        render_failed = grp ? (pt_group_render(grp, 1, iters) || pt_group_gather(grp, scene->state.image.data()))
+                            : (pt_render(iter_first, iters) || pt_readback(scene->state.image.data()));
+      }
+      if (render_failed) {
         std::fprintf(stderr, "HIP error (pt_render): %s\n", pt_last_error());
         return EXIT_FAILURE;
       }
@@ -501,8 +523,10 @@ int main(int argc, char** argv) {
       if (pfm && pt_save_pfm((frame + ".pfm").c_str(), scene->state.image.data(), W, H, (float)iters) == 0) std::printf("Saved %s.pfm.\n", frame.c_str());
       if (hdr && pt_save_hdr((frame + ".hdr").c_str(), scene->state.image.data(), W, H, (float)iters) == 0) std::printf("Saved %s.hdr.\n", frame.c_str());
       if (reproject) {  // the view's first hits, the history looked up from them, the blend written, the blend kept for the next view
-        if (pt_render_features(1, 1) || (f > 0 && pt_history_reproject(&hopt)) || pt_history_resolve((float)iters, carried.data()) ||
-            pt_history_capture((float)iters) || pt_readback_history(nullptr, current.data())) {
+        const uint32_t hflags = dn_history ? PT_HISTORY_VARIANCE : 0u;  // 0: the plain calls
+        if (pt_render_features(1, 1) || (f > 0 && pt_history_reproject_ex(&hopt, hflags)) || pt_history_resolve((float)iters, carried.data()) ||
+            (dn_history && pt_history_denoise((float)iters, &dn_opt, filtered.data())) || pt_history_capture_ex((float)iters, hflags) ||
+            pt_readback_history(nullptr, current.data())) {
           std::fprintf(stderr, "HIP error (pt_history): %s\n", pt_last_error());
           return EXIT_FAILURE;
         }
@@ -513,6 +537,11 @@ int main(int argc, char** argv) {
         std::printf("history: frame %d: %zu of %zu pixels carried, mean weight %.3f\n", f, valid, (size_t)W * H, valid ? weight / (double)valid : 0.0);
         if (pt_save_png((frame + ".reprojected.png").c_str(), carried.data(), W, H, 1.0f) == 0) std::printf("Saved %s.reprojected.png.\n", frame.c_str());
         if (pfm && pt_save_pfm((frame + ".reprojected.pfm").c_str(), carried.data(), W, H, 1.0f) == 0) std::printf("Saved %s.reprojected.pfm.\n", frame.c_str());
+        if (dn_history) {  // the history keeps the unfiltered blend: the filtered one is written, not fed back
+          if (pt_save_png((frame + ".reprojected.denoised.png").c_str(), filtered.data(), W, H, 1.0f) == 0) std::printf("Saved %s.reprojected.denoised.png.\n", frame.c_str());
+          if (pfm && pt_save_pfm((frame + ".reprojected.denoised.pfm").c_str(), filtered.data(), W, H, 1.0f) == 0)
+            std::printf("Saved %s.reprojected.denoised.pfm.\n", frame.c_str());
+        }
       }
     }
     if (grp) pt_group_destroy(grp);

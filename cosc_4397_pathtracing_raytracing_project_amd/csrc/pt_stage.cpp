@@ -351,6 +351,55 @@ int pt_stage_history_reproject(int w, int rows, int row0, const PtCamera* kept_c
   return 0;
 }
 
+// ... with the variance side (pt_history_reproject_variance_host's arguments): C and VC of one launch
+int pt_stage_history_reproject_variance(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
+                                        const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, const float* kept_var, float* current_plane,
+                                        float* current_var) {
+  const char* who = "pt_stage_history_reproject_variance";
+  if (need(default_context(), who)) return -1;
+  Ctx& g = *default_context();
+  pthi::Params P{};
+  if (pt_history_reproject_check(who, w, rows, row0, kept_cam, kept_planes, feature_planes, reject_geom, num_geoms, opt, current_plane, &P)) return -1;
+  if (!kept_var || !current_var) return pt_fail("%s: null argument", who);
+  if (rows >= 32768) return pt_fail("%s: a tile of %d x %d pixels is not supported", who, w, rows);
+  HIP_OK(hipSetDevice(g.device));
+  Scratch sc;
+  const size_t n = (size_t)w * rows;
+  float *d_kept = nullptr, *d_feat = nullptr, *d_kvar = nullptr;
+  uint8_t* d_reject = nullptr;
+  float* d_cur = sc.get<float>(8 * n);  // C, then VC
+  if (!d_cur) return pt_fail("%s: out of device memory", who);
+  if (device_copy(sc, who, kept_planes, 4 * PT_HISTORY_KEPT_PLANES * n, &d_kept) || device_copy(sc, who, feature_planes, 4 * PT_FEATURE_PLANES * n, &d_feat) ||
+      device_copy(sc, who, kept_var, 4 * n, &d_kvar))
+    return -1;
+  if (!P.keep_view_dependent && num_geoms > 0 && device_copy(sc, who, reject_geom, (size_t)num_geoms, &d_reject)) return -1;
+  HIP_OK(hipMemset(d_cur, 0xff, 8 * n * sizeof(float)));  // a pixel nobody wrote shows as NaNs
+  if (pt_history_reproject_variance_launch(g.stream, pthi::make_view(*kept_cam, rows, row0), d_kept, d_feat, d_reject, num_geoms, P, d_cur, d_kvar, d_cur + 4 * n))
+    return -1;
+  HIP_OK(hipStreamSynchronize(g.stream));
+  HIP_OK(hipMemcpy(current_plane, d_cur, 4 * n * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(current_var, d_cur + 4 * n, 4 * n * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// The history filter's kernels on caller-supplied host arrays (pt_history_denoise_host's arguments); C and VC travel beside the frame
+int pt_stage_history_denoise(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, int groups, int64_t iters, float samples,
+                             const float* current_plane, const float* current_var, const PtDenoiseOptions* opt, float* rgb_avg) {
+  const char* who = "pt_stage_history_denoise";
+  if (need(default_context(), who)) return -1;
+  Ctx& g = *default_context();
+  if (rows >= 32768) return pt_fail("%s: a frame of %d x %d pixels is not supported", who, w, rows);
+  ptdn::Job j{};
+  if (pt_history_denoise_check(who, w, rows, rgb_sum, planes, noise_planes, groups, iters, samples, current_plane, current_var, opt, rgb_avg, &j)) return -1;
+  Scratch hist_sc;  // (filter_stage synchronises before it returns)
+  float *d_cur = nullptr, *d_var = nullptr;
+  HIP_OK(hipSetDevice(g.device));
+  const size_t n = (size_t)w * rows;
+  if (current_plane && (device_copy(hist_sc, who, current_plane, 4 * n, &d_cur) || device_copy(hist_sc, who, current_var, 4 * n, &d_var))) return -1;
+  j.div.C = reinterpret_cast<const ptdn::V4*>(d_cur), j.div.VC = reinterpret_cast<const ptdn::V4*>(d_var);
+  return filter_stage_job(g, who, w, rows, rgb_sum, planes, noise_planes, rgb_avg, j);
+}
+
 // The selection's kernels on caller-supplied host arrays (pt_adaptive_select_host's arguments)
 int pt_stage_adaptive_select(int w, int rows, const float* noise_planes, const int32_t* counts, int m, int32_t* list) {
   if (need(default_context(), "pt_stage_adaptive_select")) return -1;

@@ -777,7 +777,7 @@ int pt_denoise_adaptive_variance_host(int w, int rows, const float* rgb_sum, con
  * The defaults are those of a CPU simulation on the cornell box (tests/test_history_sim.py; README "Reprojected history" has its
  * figures).  The bilinear lookup also smooths: the carried image is a BIASED estimator, and nothing here corrects that.
  * Out of scope: pt_group_* (a context's interleaved rows cannot look up their neighbours); feeding the history into the noise
- * estimate, the filters or adaptive sampling; motion of anything but the camera. */
+ * estimate or adaptive sampling; motion of anything but the camera.  (The filter over the blend: "variance of the history" below.) */
 #define PT_HISTORY_KEPT_PLANES 3
 typedef struct PtHistoryOptions { /* every field: 0 = the default */
   float cap;                   /* default 32: the most samples a carried colour counts for; finite and > 0                 */
@@ -805,6 +805,67 @@ int pt_history_capture_host(int pixels, const float* rgb_sum, const float* featu
 int pt_history_reproject_host(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
                               const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, float* current_plane);
 int pt_history_blend_host(int pixels, const float* rgb_sum, float samples, const float* current_plane, float* rgb_avg);
+
+/* ---- variance of the history, and the variance-guided filter over the blend (temporal SVGF).  pt_denoise_guided sees the variance of
+ * the current view's few samples only; the blend of pt_history_resolve has many effective samples but no variance.  With
+ * PT_HISTORY_VARIANCE a variance travels with the history, and pt_history_denoise runs the guided filter on the blend with it.  Opt-in:
+ * flags == 0 is the old call (the same kernels, arithmetic, memory and launches), and a renderer that never sets the flag allocates and
+ * launches nothing for it.  Specified like the history above: float32 throughout, every operation a separate IEEE operation in the
+ * order written, no FMA contraction, correctly rounded division, denormals kept; one implementation for kernels and host loops.
+ * Variance state, a buffer of its own, 32 bytes per tile pixel, allocated and zeroed by the first capture with the flag and part of
+ * PtStats.device_bytes from then on (the 64 bytes of the state above and K2.w = +0 stay as they are):
+ *   VK = {vk.xyz, +0}: per-channel variance of the kept blended colour K0.xyz, aligned with K
+ *   VC = {vh.xyz, +0}: VK resampled to the current camera, aligned with C
+ * Lifetime: VK survives pt_clear and pt_set_camera[_ex] like K; VC becomes absent on both like C; pt_history_drop forgets both; a plain
+ * pt_history_capture after a capture with the flag leaves VK invalid ("kept without variance"), a plain pt_history_reproject leaves
+ * VC absent while C is present.
+ *   new-sample variance, per component k, from the fold's planes prev, q with Tf = (float)T, Df = (float)(M - 1) * Tf:
+ *            d = q_k - (prev_k * prev_k) / Tf;  vn_k = (d > 0 ? d : 0) / Df          (pt_denoise_guided's v_k before the albedo step)
+ *   variance of the blend:  dn = samples + Th;  wn = samples / dn;  wh = Th / dn;  vb_k = (wn * wn) * vn_k + (wh * wh) * vh_k
+ *            (C absent: Th = vh = +0)
+ *   capture with the flag:  K exactly as without;  VK = {vb.xyz, +0}
+ *   reproject with the flag:  C exactly as without, the same bits.  Step 6 also starts vacc = 0 and, for a tap that passed every
+ *            test, adds vacc_k = vacc_k + b * VK(q).k after tacc (VK(q) is read after K0(q), for such a tap only);  step 7:
+ *            vh_k = vacc_k / wsum.  A rejected pixel gets VC = 0.  Capping Th does not touch vh.  The variance is interpolated
+ *            linearly, as SVGF interpolates its moments: conservative, since the lookup's smoothing lowers the true variance.
+ *   pt_history_denoise: pt_denoise_guided with another prepare.  n, a, p and the hit flag as pt_denoise;
+ *            c_k = blend(S_k, samples, C.k, C.w) (the blend above), demodulated like any colour;  v_k = vb_k, and unless keep_albedo
+ *            v_k = a_k > 0 ? v_k / (a_k * a_k) : v_k;  var_raw = (v_x + v_y) + v_z in the albedo buffer's spare word.  Then the
+ *            guided form's variance prefilter (the one without counts), levels and finish, unchanged: the same kernels.
+ *            sigma_color == 0 means 8.0.  The workspace is the shared 80 bytes per pixel of the other filters.
+ * With C and VC absent, samples == (float)T and S >= 0, wn = 1 and wh = 0, so vb = vn and the result equals pt_denoise_guided's bit
+ * for bit (tests/test_history_variance_host.py).
+ * Refusals, each with a message that names the function, nothing allocated or launched, in this order.  capture_ex and reproject_ex:
+ * no renderer / a failed context; an undefined flag bit; then what pt_history_capture / _reproject refuse, in their order.  With the
+ * flag capture_ex then refuses: nothing folded, or fewer than 2 groups folded; iterations rendered since the last fold ("fold
+ * first"); samples != (float)T of the folds; C present but VC absent (the lookup was made without the flag).  With the flag
+ * reproject_ex then refuses: nothing captured with variance.  pt_history_denoise: a failed context, a striped or ragged tile, the
+ * adaptive state; no feature pass since the last clear or move; samples; levels, a sigma or keep_albedo as pt_denoise refuses them;
+ * the fold conditions above; C without VC; a null buffer.
+ * What it buys (cornell 96x54, depth 8, 8 views 3 degrees apart, 4 spp per view in 4 groups of 1, MSE against 1024 spp at the last
+ * camera; tests/test_history_variance_sim.py on the CPU, tests/test_gpu_history_variance.py on an MI355X, the same digits): the blend
+ * 4.525e-4, the filtered blend 1.396e-4 (0.3086 of it), pt_denoise_guided on the last view's own 4 spp 4.539e-4 (the filtered blend is
+ * 0.3076 of it): history plus filter beats either alone.  The carried variance reads high (sum of VK 15.39 against the blend's squared
+ * error 7.037 over the last view): recorded, not bounded.  One scene, one orbit: no claim beyond it.
+ * Out of scope: feeding the FILTERED image back into the history (K keeps the unfiltered blend); pt_group_*; a view with fewer than 2
+ * folds (1 spp per frame); a spatial variance fallback for disoccluded pixels (they start again from the view's own estimate). */
+#define PT_HISTORY_VARIANCE 1u
+int pt_history_capture_ex(float samples, uint32_t flags);
+int pt_history_reproject_ex(const PtHistoryOptions* opt, uint32_t flags);
+int pt_history_denoise(float samples, const PtDenoiseOptions* opt, float* rgb_avg_host); /* synchronises; pixel_count * 3 floats */
+/* pixel_count * 4 floats each; either may be NULL; zeros while the plane is absent (or kept without variance). */
+int pt_readback_history_variance(float* kept_var, float* current_var);
+/* The same arithmetic on the host (no GPU); the device results equal these bit for bit.  The capture's K is pt_history_capture_host's;
+ * this gives VK beside it from the fold's planes (groups = M >= 2 folds over iters = T iterations, samples == (float)T) and C, VC
+ * (both NULL: absent).  The lookup gives C — pt_history_reproject_host's, bit for bit — and VC in one pass. */
+int pt_history_capture_variance_host(int pixels, const float* noise_planes, int groups, int64_t iters, float samples, const float* current_plane,
+                                     const float* current_var, float* kept_var);
+int pt_history_reproject_variance_host(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
+                                       const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, const float* kept_var, float* current_plane,
+                                       float* current_var);
+/* pt_denoise_guided_host's arrays, samples, and C, VC (both NULL: absent). */
+int pt_history_denoise_host(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, int groups, int64_t iters, float samples,
+                            const float* current_plane, const float* current_var, const PtDenoiseOptions* opt, float* rgb_avg);
 
 /* saveImage()'s per-pixel conversion (main.cpp:91-97 x mirror, image.cpp:26-30 clamp * 255 truncated) on the
  * device: pixel_count*3 bytes, row-major, x mirrored inside each row; the tile must consist of whole rows.
@@ -868,6 +929,11 @@ int pt_ctx_history_resolve(PtContext* c, float samples, float* rgb_avg_host);
 int pt_ctx_history_resolve_device(PtContext* c, float samples, const float** rgb_dev);
 int pt_ctx_readback_history(PtContext* c, float* kept_planes, float* current_plane);
 int pt_ctx_history_drop(PtContext* c);
+int pt_ctx_history_capture_ex(PtContext* c, float samples, uint32_t flags);
+int pt_ctx_history_reproject_ex(PtContext* c, const PtHistoryOptions* opt, uint32_t flags);
+int pt_ctx_history_denoise(PtContext* c, float samples, const PtDenoiseOptions* opt, float* rgb_avg_host);
+int pt_ctx_history_denoise_device(PtContext* c, float samples, const PtDenoiseOptions* opt, const float** rgb_dev); /* as pt_ctx_denoise_device */
+int pt_ctx_readback_history_variance(PtContext* c, float* kept_var, float* current_var);
 const float* pt_ctx_device_noise(PtContext* c); /* device pointer of plane 0; the planes are contiguous; NULL before the first fold */
 const float* pt_ctx_device_features(PtContext* c); /* device pointer of plane 0; the planes are contiguous; NULL before the first pt_ctx_render_features */
 const float* pt_ctx_device_image(PtContext* c); /* device pointer of the tile SUM image */
@@ -1046,6 +1112,13 @@ int pt_stage_adaptive_select_threshold(int w, int rows, const float* noise_plane
 /* The reprojection's kernel on caller-supplied host arrays (pt_history_reproject_host's arguments; rows < 32768). */
 int pt_stage_history_reproject(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
                                const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, float* current_plane);
+/* The same with the variance side (pt_history_reproject_variance_host's arguments), and the history filter's kernels on
+ * caller-supplied host arrays (pt_history_denoise_host's arguments; rows < 32768). */
+int pt_stage_history_reproject_variance(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
+                                        const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, const float* kept_var, float* current_plane,
+                                        float* current_var);
+int pt_stage_history_denoise(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, int groups, int64_t iters, float samples,
+                             const float* current_plane, const float* current_var, const PtDenoiseOptions* opt, float* rgb_avg);
 
 /* ---- image output (src/image.cpp:22-45, src/main.cpp:86-107) ------------- */
 /* rgb_sum: W*H*3 floats (raw orientation); writes <path> as 8-bit PNG of

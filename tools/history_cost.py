@@ -10,7 +10,13 @@ reproject, resolve (the device form: no readback) and capture run back to back o
 median, minimum and maximum of each are printed with the bytes a call moves by its specification (the gather's taps: 4 x 32 B read
 at the most, 4 x 16 B more for taps that pass, before any cache) and the rate that makes.  The yardstick is one iteration of pt_render
 at the same camera, in the same process, timed the same way.  The first repetition (allocations, code objects) is dropped.  No timing
-is asserted anywhere."""
+is asserted anywhere.
+
+Then the variance side (PT_HISTORY_VARIANCE; profiles/history_variance_cost.log holds a run with both parts): the context is
+cleared, a view is rendered in 4 groups of 1 with a fold each and captured with variance, the camera moves another step, the next view
+is rendered and folded the same way; per repetition pt_history_reproject_ex and pt_history_capture_ex with the flag and
+pt_history_denoise (device form) run between HIP events, and pt_denoise_guided (device form) on the same frame for scale.  The
+first part is untouched by this: its calls are the flags == 0 ones, to be compared with earlier logs."""
 import argparse
 import ctypes as C
 import os
@@ -135,6 +141,58 @@ for name, text in (("cornell (7 primitives)", scenes.cornell_scene_text(res=(W, 
         line("pt_render, 1 iteration", times["render"])
         three = statistics.median(times["reproject"]) + statistics.median(times["resolve"]) + statistics.median(times["capture"])
         say(f"the three together {three:.4f} ms = {three / statistics.median(times['render']):.3f} of one iteration")
+        have = hasattr(L, "pt_ctx_history_denoise_device")  # False: an older build of the library (PT_AMD_LIB), which gives pt_denoise_guided's time
+        # ---- the variance side: the same context, cleared; views folded in 4 groups of 1
+        capi._check(L.pt_ctx_get_stats(ctx, C.byref(st)))
+        before = st.device_bytes
+        capi._check(L.pt_ctx_clear(ctx))
+        VAR = capi.HISTORY_VARIANCE
+
+        def folded_view(first):
+            for g in range(SPP):
+                capi._check(L.pt_ctx_render(ctx, first + g, 1))
+                capi._check(L.pt_ctx_noise_fold(ctx))
+            capi._check(L.pt_ctx_render_features(ctx, 1, 1))
+
+        folded_view(1)
+        if have:
+            capi._check(L.pt_ctx_history_capture_ex(ctx, C.c_float(SPP), VAR))
+        cam = scene.orbit(np.float32(2 * np.pi / 120), 0.0, 0.0)
+        capi._check(L.pt_ctx_set_camera(ctx, C.byref(cam)))
+        folded_view(SPP + 1)
+        times = dict(reproject=[], denoise=[], capture=[], guided=[])
+        ev = events(5)
+        for rep in range(args.reps):
+            hip_ok(hip.hipEventRecord(ev[0], stream))
+            if have:
+                capi._check(L.pt_ctx_history_reproject_ex(ctx, C.byref(hopt), VAR))
+            hip_ok(hip.hipEventRecord(ev[1], stream))
+            if have:
+                capi._check(L.pt_ctx_history_denoise_device(ctx, C.c_float(SPP), None, C.byref(dev)))
+            hip_ok(hip.hipEventRecord(ev[2], stream))
+            capi._check(L.pt_ctx_denoise_guided_device(ctx, None, C.byref(dev)))
+            hip_ok(hip.hipEventRecord(ev[3], stream))
+            if have:
+                capi._check(L.pt_ctx_history_capture_ex(ctx, C.c_float(SPP), VAR))
+            hip_ok(hip.hipEventRecord(ev[4], stream))
+            hip_ok(hip.hipEventSynchronize(ev[4]))
+            if rep:
+                for k, name_ in enumerate(("reproject", "denoise", "guided", "capture")):
+                    times[name_].append(elapsed(ev[k], ev[k + 1]))
+        for e in ev:
+            hip.hipEventDestroy(e)
+        capi._check(L.pt_ctx_get_stats(ctx, C.byref(st)))
+        if not have:
+            say("### this build of the library has no PT_HISTORY_VARIANCE: the guided filter on the same frame, for scale")
+            line("pt_denoise_guided (device)", times["guided"])
+            continue
+        say(f"### with PT_HISTORY_VARIANCE: {(st.device_bytes - before) / 2**20:.1f} MB more state (VK and VC, the fold's planes, the filters' workspace)")
+        line("pt_history_reproject_ex", times["reproject"], 48 + 16 + 16 + 4 * 64)
+        line("pt_history_capture_ex", times["capture"], 12 + 48 + 16 + 48 + 32 + 16 + 16)
+        line("pt_history_denoise (device)", times["denoise"])
+        line("pt_denoise_guided (device)", times["guided"])
+        extra = statistics.median(times["denoise"]) - statistics.median(times["guided"])
+        say(f"the history form's prepare reads 12 + 48 + 32 + 16 + 16 B and writes 64 B per pixel (the guided form's: 12 + 48 + 32 in); the two filters differ by {extra:+.4f} ms")
     finally:
         L.pt_ctx_destroy(ctx)
 out.close()
