@@ -356,6 +356,16 @@ def lib() -> C.CDLL:
         L.pt_stage_history_reproject_variance.argtypes = _reproject_var
         L.pt_history_denoise_host.argtypes = _hdn
         L.pt_stage_history_denoise.argtypes = _hdn
+    if hasattr(L, "pt_history_denoise_ex"):  # absent from older A/B builds of the library (tools/build_rev.sh)
+        _mdn = [C.c_int, C.c_int, _fp, _fp, C.c_float, _fp, _fp, _dno]
+        L.pt_history_denoise_ex.argtypes = [C.c_float, _dno, C.c_uint32, _fp]
+        L.pt_ctx_history_denoise_ex.argtypes = [C.c_void_p, C.c_float, _dno, C.c_uint32, _fp]
+        L.pt_ctx_history_denoise_ex_device.argtypes = [C.c_void_p, C.c_float, _dno, C.c_uint32, C.POINTER(C.c_void_p)]
+        L.pt_history_capture_moments_host.argtypes = [C.c_int, _fp, C.c_float, _fp, _fp, _fp]
+        L.pt_history_reproject_moments_host.argtypes = _reproject_var
+        L.pt_stage_history_reproject_moments.argtypes = _reproject_var
+        L.pt_history_denoise_moments_host.argtypes = _mdn + [_fp, _fp, _u8p]
+        L.pt_stage_history_denoise_moments.argtypes = _mdn + [_fp]
     _lib = L
     return L
 
@@ -713,6 +723,69 @@ def stage_history_denoise(rgb_sum, planes, noise_planes, w: int, rows: int, grou
     return _history_denoise(lib().pt_stage_history_denoise, rgb_sum, planes, noise_planes, w, rows, groups, iters, samples, current, current_var, **opts)
 
 
+HISTORY_MOMENTS = 2  # PT_HISTORY_MOMENTS
+HISTORY_MOMENTS_R_MAX = np.float32(0.3)  # PT_HISTORY_MOMENTS_R_MAX
+
+
+def history_capture_moments_host(rgb_sum: np.ndarray, samples: float, current: Optional[np.ndarray] = None,
+                                 current_var: Optional[np.ndarray] = None) -> np.ndarray:
+    """The moments side of pt_history_capture_ex on the host (no GPU): the SUM image [n, 3] and the planes C, VC [n, 4] (None: absent)
+    in, VK = {m2b.xyz, rb} [n, 4] out.  K is history_capture_host's."""
+    s = np.ascontiguousarray(rgb_sum, np.float32).reshape(-1)
+    n = s.size // 3
+    c = None if current is None else np.ascontiguousarray(current, np.float32).reshape(-1)
+    v = None if current_var is None else np.ascontiguousarray(current_var, np.float32).reshape(-1)
+    if s.size != 3 * n or any(a is not None and a.size != 4 * n for a in (c, v)):
+        raise PtError(f"history_capture_moments_host: {s.size} image floats")
+    out = np.empty((n, 4), np.float32)
+    _check(lib().pt_history_capture_moments_host(n, _f(s), C.c_float(samples), None if c is None else _f(c), None if v is None else _f(v), _f(out)))
+    return out
+
+
+def history_reproject_moments_host(kept_cam: PtCamera, kept, planes, reject, kept_var, w: int, rows: int, row0: int = 0, **opts):
+    """pt_history_reproject_ex with PT_HISTORY_MOMENTS on the host (no GPU): history_reproject_host's arrays and VK [w*rows, 4] in,
+    (C, VC), [w*rows, 4] each, out."""
+    return _history_reproject_variance(lib().pt_history_reproject_moments_host, kept_cam, kept, planes, reject, kept_var, w, rows, row0, **opts)
+
+
+def stage_history_reproject_moments(kept_cam: PtCamera, kept, planes, reject, kept_var, w: int, rows: int, row0: int = 0, **opts):
+    """history_reproject_moments_host's arrays through the production kernel (pt_stage_history_reproject_moments; a renderer must be live)."""
+    return _history_reproject_variance(lib().pt_stage_history_reproject_moments, kept_cam, kept, planes, reject, kept_var, w, rows, row0, **opts)
+
+
+def _history_planes(current, current_var, w: int, rows: int):
+    c = None if current is None else np.ascontiguousarray(current, np.float32).reshape(-1)
+    v = None if current_var is None else np.ascontiguousarray(current_var, np.float32).reshape(-1)
+    if any(a is not None and a.size != 4 * w * rows for a in (c, v)):
+        raise PtError(f"history_denoise_moments: the current plane or its moments are not [{w * rows}, 4]")
+    return c, v
+
+
+def history_denoise_moments_host(rgb_sum, planes, w: int, rows: int, samples: float, current=None, current_var=None, stats: Optional[dict] = None,
+                                 **opts) -> np.ndarray:
+    """pt_history_denoise_ex with PT_HISTORY_MOMENTS on the host (no GPU): denoise_host's arrays, samples, and the planes C, VC
+    [w*rows, 4] (None: absent).  stats (a dict) receives var_raw (after the spatial step) and mark (bool)."""
+    s, p, out = _denoise_arrays(rgb_sum, planes, w, rows)
+    c, v = _history_planes(current, current_var, w, rows)
+    var_raw = np.empty(w * rows, np.float32) if stats is not None else None
+    mark = np.empty(w * rows, np.uint8) if stats is not None else None
+    opt = denoise_options(**opts)
+    _check(lib().pt_history_denoise_moments_host(int(w), int(rows), _f(s), _f(p), C.c_float(samples), None if c is None else _f(c), None if v is None else _f(v),
+                                                 C.byref(opt), _f(out), None if var_raw is None else _f(var_raw),
+                                                 None if mark is None else mark.ctypes.data_as(C.POINTER(C.c_uint8))))
+    if stats is not None:
+        stats.update(var_raw=var_raw, mark=mark.astype(bool))
+    return out
+
+
+def stage_history_denoise_moments(rgb_sum, planes, w: int, rows: int, samples: float, current=None, current_var=None, **opts) -> np.ndarray:
+    """history_denoise_moments_host's arguments through the filter's kernels (pt_stage_history_denoise_moments; a renderer must be live)."""
+    s, p, out = _denoise_arrays(rgb_sum, planes, w, rows)
+    c, v = _history_planes(current, current_var, w, rows)
+    return _filter(lib().pt_stage_history_denoise_moments, out, int(w), int(rows), _f(s), _f(p), C.c_float(samples), None if c is None else _f(c),
+                   None if v is None else _f(v), **opts)
+
+
 def split_noise(planes: np.ndarray) -> dict:
     """The noise planes [PT_NOISE_PLANES, n, 4] (pt_readback_noise) by name: prev [n, 3] (the SUM image at the last fold),
     q [n, 3] (sum over the groups of B^2 / n), variance [n] (w: estimated variance of the averaged radiance, channels added)."""
@@ -1030,6 +1103,14 @@ class Renderer:
         """The blend of history_resolve filtered by the variance-guided filter with the blend's variance (pt_history_denoise;
         options: denoise_options): float32 [n, 3]."""
         return _filter(lib().pt_history_denoise, np.empty((self.n, 3), np.float32), C.c_float(samples), **opts)
+
+    def history_denoise_ex(self, samples: float, flags: int = HISTORY_MOMENTS, **opts) -> np.ndarray:
+        """The blend filtered with the variance the history's moments give (pt_history_denoise_ex with PT_HISTORY_MOMENTS: no folds,
+        1 spp per view is enough); flags == 0 is history_denoise."""
+        opt = denoise_options(**opts)
+        out = np.empty((self.n, 3), np.float32)
+        _check(lib().pt_history_denoise_ex(C.c_float(samples), C.byref(opt), int(flags), _f(out)))
+        return out
 
     def readback_history_variance(self):
         """(VK, VC), float32 [n, 4] each; zeros while absent."""

@@ -945,7 +945,8 @@ int pt_ctx_clear(PtContext* c) {
   c->adaptive = false;
   c->adaptive_rounds = 0;
   c->adaptive_last = 0;
-  c->hist_current = c->hist_var_current = c->feat_fresh = false;  // the history's current planes are absent; its kept planes stay (pt_history.h)
+  c->hist_current = c->feat_fresh = false;
+  c->hist_var_current = 0;  // the history's current planes are absent; its kept planes stay (pt_history.h)
   if (c->conv) {  // forget the curve, re-arm the capture (a supplied frame stays)
     HIP_OK(hipMemsetAsync(c->d_sse, 0xff, (size_t)PT_CONVERGENCE_CAPACITY * sizeof(double), c->stream));
     c->conv_last = 0;
@@ -1308,6 +1309,9 @@ int pt_history_drop(void) { return pt_ctx_history_drop(g_default); }
 int pt_history_capture_ex(float samples, uint32_t flags) { return pt_ctx_history_capture_ex(g_default, samples, flags); }
 int pt_history_reproject_ex(const PtHistoryOptions* opt, uint32_t flags) { return pt_ctx_history_reproject_ex(g_default, opt, flags); }
 int pt_history_denoise(float samples, const PtDenoiseOptions* opt, float* rgb_avg_host) { return pt_ctx_history_denoise(g_default, samples, opt, rgb_avg_host); }
+int pt_history_denoise_ex(float samples, const PtDenoiseOptions* opt, uint32_t flags, float* rgb_avg_host) {
+  return pt_ctx_history_denoise_ex(g_default, samples, opt, flags, rgb_avg_host);
+}
 int pt_readback_history_variance(float* kept_var, float* current_var) { return pt_ctx_readback_history_variance(g_default, kept_var, current_var); }
 int pt_set_reference(const float* rgb_avg_host) { return pt_ctx_set_reference(g_default, rgb_avg_host); }
 int pt_get_convergence(int iter_first, int iter_count, double* sse) { return pt_ctx_get_convergence(g_default, iter_first, iter_count, sse); }

@@ -166,9 +166,9 @@ struct PtContext : PtShared {
   PtCamera hist_cam{};             // the camera K is aligned to
   bool hist_kept = false;          // K holds a capture (pt_ctx_history_drop forgets it)
   bool hist_current = false;       // C holds a reprojection for the current camera; pt_clear and a camera move make it absent
-  void* d_hist_var = nullptr;      // pt_history_variance_bytes(N): VK, then VC; absent until the first capture with PT_HISTORY_VARIANCE
-  bool hist_var_kept = false;      // VK is the variance of K0 (a plain capture leaves K "kept without variance")
-  bool hist_var_current = false;   // VC belongs to C (the lookup was made with PT_HISTORY_VARIANCE); absent whenever C is
+  void* d_hist_var = nullptr;      // pt_history_variance_bytes(N): VK, then VC; absent until the first capture with PT_HISTORY_VARIANCE or _MOMENTS
+  uint32_t hist_var_kept = 0;      // the flag of the capture VK belongs to K0 by: the variance of K0 or its moments (0: a plain capture, K "kept without")
+  uint32_t hist_var_current = 0;   // the flag of the lookup VC belongs to C by; 0 (absent) whenever C is
   bool feat_fresh = false;         // a feature pass has run since pt_init / pt_clear / the last camera move
   // Moving the camera (pt_ctx_set_camera): the camera-independent tables on the host, and the grid to rebuild (the one init kept)
   pt::CameraBase camera_base;

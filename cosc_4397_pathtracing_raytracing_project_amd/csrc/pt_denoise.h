@@ -8,7 +8,10 @@
 // is the guided one with the sample counts of every pixel instead of two scalars in the prepare and the prefilter; its levels and its
 // finish are the guided form's.  The history form (pt_history_denoise; tests/history_variance_ref.py) is the guided one over the blend
 // of the image with the reprojected history (pt_history.h): its prepare takes the blend for the colour and the blend's variance for
-// the variance; prefilter, levels and finish are the guided form's.
+// the variance; prefilter, levels and finish are the guided form's.  The moments form (pt_history_denoise_ex with PT_HISTORY_MOMENTS;
+// tests/history_moments_ref.py) is the history form without a fold: its prepare takes the blend's variance from the moments the history
+// carries (the differences between views), and marks the pixels whose history is too short; var_spatial_pixel — a step of its own
+// between prepare and the prefilter — gives those the variance of their 7 x 7 neighbourhood instead.
 // Every float operation is a separate IEEE operation in the order pt_amd.h states (`#pragma clang fp contract(off)` in every body, correctly
 // rounded division, denormals kept), so the result does not depend on the arithmetic mode of the build or on the side it runs on.
 // Plain C++ apart from PT_HD: the system compiler accepts it (a host sanitizer run needs nothing else).
@@ -78,7 +81,8 @@ PT_HD float color_factor(const Params& P, int l) {
 // far.  Adaptive: the counts of the pixel itself — cnt, the plane of pt_adaptive.h, or nullptr: the uniform state, (T, M) for every
 // pixel, as ptad::resolve_pixel.  History: the guided form's two for the new samples' variance, and what the blend reads — samples, the
 // history's current plane C and its variance VC (both nullptr: absent).
-enum class Form { Plain, Guided, Adaptive, History };
+// Moments: what the blend reads only — samples, C and VC = {m2h.xyz, rh} (both nullptr: absent); no fold, no noise planes.
+enum class Form { Plain, Guided, Adaptive, History, Moments };
 struct Divisors {
   float Tf, Df;
   const ptad::Cnt* cnt;
@@ -101,6 +105,18 @@ PT_HD float history_variance(float prev, float q, float albedo, float Tf, float 
   const float v = pthi::blend_variance(pthi::sample_variance(prev, q, Tf, Df), samples, vh, Th);
   return !keep_albedo && albedo > 0.0f ? v / (albedo * albedo) : v;
 }
+// moments: the unbiased variance of the weighted mean of the views from their second moment m2b and mean cb, f = rb / (1 - rb)
+// (m2 - c^2 underestimates the per-view variance by (1 - r), and the blend's variance is r times that), demodulated likewise
+PT_HD float moments_variance(float m2b, float cb, float f, float albedo, int keep_albedo) {
+#pragma clang fp contract(off)
+  const float d = m2b - cb * cb;
+  const float v = (d > 0.0f ? d : 0.0f) * f;
+  return !keep_albedo && albedo > 0.0f ? v / (albedo * albedo) : v;
+}
+// ... and what its prepare leaves in var_raw's place for a pixel whose history is too short to have one (every other var_raw is
+// >= 0 or NaN: sums of clamped terms times f >= 0)
+constexpr float kSpatialMark = -1.0f;
+PT_HD bool spatial_marked(float var_raw) { return var_raw == kSpatialMark; }
 // The guided forms (noise: the fold's two planes) leave var_raw in the albedo buffer's spare word.  The adaptive form leaves Tf_p in
 // the position buffer's spare word, which no tap reads (dist2: xyz) and the other two leave 0.
 // D: Divisors, or the members of it that the form reads (a kernel takes no more than those).
@@ -108,12 +124,12 @@ template <Form kForm, typename D>
 PT_HD void prepare_pixel_of(size_t i, size_t npix, const float* S, const V4* planes, const V4* noise, const D& d, int keep_albedo, V4* n, V4* p, V4* a,
                             V4* c) {
 #pragma clang fp contract(off)
-  float Tf, Df = 0.0f;
+  [[maybe_unused]] float Tf = 0.0f, Df = 0.0f;
   if constexpr (kForm == Form::Adaptive) {
     const int32_t Tp = d.cnt ? d.cnt[i].T : d.T, Mp = d.cnt ? d.cnt[i].M : d.M;
     Tf = (float)Tp;
     Df = (float)(Mp - 1) * Tf;
-  } else {
+  } else if constexpr (kForm != Form::Moments) {
     Tf = d.Tf;
     if constexpr (kForm == Form::Guided || kForm == Form::History) Df = d.Df;
   }
@@ -127,7 +143,7 @@ PT_HD void prepare_pixel_of(size_t i, size_t npix, const float* S, const V4* pla
   }
   V4 vc{0.0f, 0.0f, 0.0f, 0.0f};
   [[maybe_unused]] V4 hc{0.0f, 0.0f, 0.0f, 0.0f}, hv{0.0f, 0.0f, 0.0f, 0.0f};  // history: C and VC of the pixel (absent: +0)
-  if constexpr (kForm == Form::History) {
+  if constexpr (kForm == Form::History || kForm == Form::Moments) {
     if (d.C) hc = d.C[i];
     if (d.VC) hv = d.VC[i];
     vc.x = pthi::blend_component(S[3 * i], d.samples, hc.x, hc.w);
@@ -136,6 +152,7 @@ PT_HD void prepare_pixel_of(size_t i, size_t npix, const float* S, const V4* pla
   } else {
     vc.x = S[3 * i] / Tf, vc.y = S[3 * i + 1] / Tf, vc.z = S[3 * i + 2] / Tf;
   }
+  [[maybe_unused]] const V4 cb = vc;  // (moments: the blend before demodulation)
   if (!keep_albedo) {
     vc.x = va.x > 0.0f ? vc.x / va.x : vc.x;
     vc.y = va.y > 0.0f ? vc.y / va.y : vc.y;
@@ -147,6 +164,17 @@ PT_HD void prepare_pixel_of(size_t i, size_t npix, const float* S, const V4* pla
     const float vy = history_variance(prev.y, q.y, va.y, Tf, Df, d.samples, hv.y, hc.w, keep_albedo);
     const float vz = history_variance(prev.z, q.z, va.z, Tf, Df, d.samples, hv.z, hc.w, keep_albedo);
     va.w = (vx + vy) + vz;
+  } else if constexpr (kForm == Form::Moments) {
+    const V4 mb = pthi::blend_moments(i, S, d.samples, hc.w, hv);
+    if (mb.w <= PT_HISTORY_MOMENTS_R_MAX) {
+      const float f = mb.w / (1.0f - mb.w);
+      const float vx = moments_variance(mb.x, cb.x, f, va.x, keep_albedo);
+      const float vy = moments_variance(mb.y, cb.y, f, va.y, keep_albedo);
+      const float vz = moments_variance(mb.z, cb.z, f, va.z, keep_albedo);
+      va.w = (vx + vy) + vz;
+    } else {
+      va.w = kSpatialMark;  // too few views behind the blend (C absent included): var_spatial_pixel
+    }
   } else if constexpr (kForm != Form::Plain) {
     const V4 prev = noise[i], q = noise[npix + i];
     const float vx = guided_variance(prev.x, q.x, va.x, Tf, Df, keep_albedo);
@@ -155,6 +183,47 @@ PT_HD void prepare_pixel_of(size_t i, size_t npix, const float* S, const V4* pla
     va.w = (vx + vy) + vz;
   }
   n[i] = vn, p[i] = vp, a[i] = va, c[i] = vc;
+}
+
+// The squared distance of two colours, normals or positions (xyz)
+PT_HD float dist2(const V4& q, const V4& o) {
+#pragma clang fp contract(off)
+  const float dx = q.x - o.x, dy = q.y - o.y, dz = q.z - o.z;
+  return (dx * dx + dy * dy) + dz * dz;
+}
+
+// moments, the spatial estimate: a marked pixel (x, y) takes var_raw from the DEMODULATED colours c of its 7 x 7 neighbourhood on its
+// own side of hit / miss, weighted by the level's normal and position terms (no colour term, no H): the weighted variance of the
+// neighbours, per channel, summed.  Reads c, n, p of the taps (3 x 16 B each), writes the centre's own spare word a.w only and reads
+// no neighbour's, so the update in place has no hazard.  The centre tap passes with w = 1: wsum >= 1.
+constexpr int kSpatialRadius = 3;
+PT_HD void var_spatial_pixel(int W, int R, int x, int y, const Params& P, const V4* n, const V4* p, const V4* c, V4* a) {
+#pragma clang fp contract(off)
+  const size_t i0 = (size_t)y * W + x;
+  const V4 cn = n[i0], cp = p[i0];
+  float wsum = 0.0f, s1x = 0.0f, s1y = 0.0f, s1z = 0.0f, s2x = 0.0f, s2y = 0.0f, s2z = 0.0f;
+  for (int j = -kSpatialRadius; j <= kSpatialRadius; ++j) {
+    const int yt = y + j;
+    if (yt < 0 || yt >= R) continue;
+    for (int i = -kSpatialRadius; i <= kSpatialRadius; ++i) {
+      const int xt = x + i;
+      if (xt < 0 || xt >= W) continue;
+      const size_t q = (size_t)yt * W + xt;
+      const V4 qn = n[q];
+      if (qn.w != cn.w) continue;
+      const V4 qp = p[q], qc = c[q];
+      const float dn = dist2(qn, cn), dp = dist2(qp, cp);
+      const float e = dn * P.inv_n + dp * P.inv_p;
+      const float w = ptmath::exp32(-e);
+      wsum = wsum + w;
+      s1x = s1x + w * qc.x, s1y = s1y + w * qc.y, s1z = s1z + w * qc.z;
+      s2x = s2x + w * (qc.x * qc.x), s2y = s2y + w * (qc.y * qc.y), s2z = s2z + w * (qc.z * qc.z);
+    }
+  }
+  const float mx = s1x / wsum, my = s1y / wsum, mz = s1z / wsum;
+  float dx = s2x / wsum - mx * mx, dy = s2y / wsum - my * my, dz = s2z / wsum - mz * mz;
+  dx = dx > 0.0f ? dx : 0.0f, dy = dy > 0.0f ? dy : 0.0f, dz = dz > 0.0f ? dz : 0.0f;
+  a[i0].w = (dx + dy) + dz;
 }
 
 // guided variance prefilter: pixel (x, y); 3 x 3, binomial, over the pixels on the centre's side of hit / miss.  Reads the hit flags
@@ -195,11 +264,6 @@ struct Centre {
   V4 c, n, p;  // n.w: the hit flag (1 / 0), or -1: no such pixel (no tap matches it)
   float ax, ay, az, wsum;
 };
-PT_HD float dist2(const V4& q, const V4& o) {
-#pragma clang fp contract(off)
-  const float dx = q.x - o.x, dy = q.y - o.y, dz = q.z - o.z;
-  return (dx * dx + dy * dy) + dz * dz;
-}
 // guided: the centre carries its own colour factor (set once from its variance) and the sum of w^2 var(q); qc.w is var_l(q)
 struct CentreGuided : Centre {
   float cf, vsum;
@@ -316,34 +380,40 @@ struct Job {
 
 // The whole filter on the host, with the bodies above in the kernels' own thread order.  counts (the adaptive form): {T_p, M_p} per pixel
 // (pt_readback_adaptive's layout), every M_p >= 2 and T_p >= M_p.  var_raw / var_0 (npix floats each, or null; the two guided forms)
-// receive the prepared and the prefiltered variance; out may then be null.
-inline void denoise_host(const Job& j, const int32_t* counts, float* out, float* var_raw = nullptr, float* var_0 = nullptr) {
+// receive the prepared and the prefiltered variance; out may then be null.  The moments form: var_raw is what the spatial step left,
+// and mark (npix bytes, or null) receives 1 for the pixels prepare marked for it, 0 for the others.
+inline void denoise_host(const Job& j, const int32_t* counts, float* out, float* var_raw = nullptr, float* var_0 = nullptr, uint8_t* mark = nullptr) {
   const int W = j.f.w, R = j.f.rows;
   const Params& P = j.P;
-  const bool guided = j.form != Form::Plain;
+  const bool guided = j.form != Form::Plain, folded = guided && j.form != Form::Moments, blended = j.form == Form::History || j.form == Form::Moments;
   const size_t npix = (size_t)W * R;
   std::vector<V4> ws(kWorkspaceV4 * npix);
   V4 *n = ws.data(), *p = n + npix, *a = p + npix, *col[2] = {a + npix, a + 2 * npix};
-  std::vector<V4> pl((PT_FEATURE_PLANES + (guided ? PT_NOISE_PLANES : 0)) * npix);  // (the caller's planes need not be 16-byte aligned)
+  std::vector<V4> pl((PT_FEATURE_PLANES + (folded ? PT_NOISE_PLANES : 0)) * npix);  // (the caller's planes need not be 16-byte aligned)
   V4* nz = pl.data() + PT_FEATURE_PLANES * npix;
   for (size_t i = 0; i < PT_FEATURE_PLANES * npix; ++i) pl[i] = V4{j.f.planes[4 * i], j.f.planes[4 * i + 1], j.f.planes[4 * i + 2], j.f.planes[4 * i + 3]};
-  for (size_t i = 0; i < PT_NOISE_PLANES * npix && guided; ++i) nz[i] = V4{j.f.noise[4 * i], j.f.noise[4 * i + 1], j.f.noise[4 * i + 2], j.f.noise[4 * i + 3]};
+  for (size_t i = 0; i < PT_NOISE_PLANES * npix && folded; ++i) nz[i] = V4{j.f.noise[4 * i], j.f.noise[4 * i + 1], j.f.noise[4 * i + 2], j.f.noise[4 * i + 3]};
   std::vector<ptad::Cnt> cnt(counts ? npix : 0);
   for (size_t i = 0; i < cnt.size(); ++i) cnt[i] = ptad::Cnt{counts[2 * i], counts[2 * i + 1]};
   Divisors d = j.div;
   if (counts) d.cnt = cnt.data();
-  std::vector<V4> hist(j.form == Form::History && j.f.current ? 2 * npix : 0);
+  std::vector<V4> hist(blended && j.f.current ? 2 * npix : 0);
   for (size_t i = 0; i < hist.size() / 2; ++i) {
     const float *c = j.f.current + 4 * i, *v = j.f.current_var + 4 * i;
     hist[i] = V4{c[0], c[1], c[2], c[3]}, hist[npix + i] = V4{v[0], v[1], v[2], v[3]};
   }
-  if (j.form == Form::History) d.C = hist.empty() ? nullptr : hist.data(), d.VC = hist.empty() ? nullptr : hist.data() + npix;
+  if (blended) d.C = hist.empty() ? nullptr : hist.data(), d.VC = hist.empty() ? nullptr : hist.data() + npix;
   for (size_t i = 0; i < npix; ++i) {
     if (j.form == Form::Plain) prepare_pixel_of<Form::Plain>(i, npix, j.f.rgb_sum, pl.data(), nz, d, P.keep_albedo, n, p, a, col[0]);
     else if (j.form == Form::Guided) prepare_pixel_of<Form::Guided>(i, npix, j.f.rgb_sum, pl.data(), nz, d, P.keep_albedo, n, p, a, col[0]);
     else if (j.form == Form::History) prepare_pixel_of<Form::History>(i, npix, j.f.rgb_sum, pl.data(), nz, d, P.keep_albedo, n, p, a, col[0]);
+    else if (j.form == Form::Moments) prepare_pixel_of<Form::Moments>(i, npix, j.f.rgb_sum, pl.data(), nullptr, d, P.keep_albedo, n, p, a, col[0]);
     else prepare_pixel_of<Form::Adaptive>(i, npix, j.f.rgb_sum, pl.data(), nz, d, P.keep_albedo, n, p, a, col[0]);
   }
+  for (size_t i = 0; i < npix && mark; ++i) mark[i] = j.form == Form::Moments && spatial_marked(a[i].w) ? 1 : 0;
+  for (int y = 0; y < R && j.form == Form::Moments; ++y)
+    for (int x = 0; x < W; ++x)
+      if (spatial_marked(a[(size_t)y * W + x].w)) var_spatial_pixel(W, R, x, y, P, n, p, col[0], a);
   for (int y = 0; y < R && guided; ++y)
     for (int x = 0; x < W; ++x) {
       if (j.form == Form::Adaptive) var_prefilter_of<true>(W, R, x, y, n, a, p, col[0]);

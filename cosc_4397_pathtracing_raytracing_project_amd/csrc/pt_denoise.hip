@@ -3,8 +3,9 @@
 // A translation unit of its own, compiled ONCE with -ffp-contract=off: the filter is specified as separate IEEE float32 operations
 // (pt_denoise.h), so there is nothing an arithmetic mode could change, and the path tracer's kernels (pt_kernels.hip) are not
 // rebuilt differently because of it.  The kernels are thin: thread indices in, the PT_HD bodies of pt_denoise.h, which the host
-// loop (ptdn::denoise_host, behind the pt_denoise*_host entry points) runs too.  Four templates, nine kernels (ptdn::Form: Plain =
-// pt_denoise, Guided = pt_denoise_guided, Adaptive = pt_denoise_adaptive, History = pt_history_denoise):
+// loop (ptdn::denoise_host, behind the pt_denoise*_host entry points) runs too.  Five templates, eleven kernels (ptdn::Form: Plain =
+// pt_denoise, Guided = pt_denoise_guided, Adaptive = pt_denoise_adaptive, History = pt_history_denoise, Moments = pt_history_denoise_ex
+// with PT_HISTORY_MOMENTS):
 //
 //   k_denoise_prepare<Form>        one thread per pixel: SUM image + feature SUM planes -> normal | hit, position, albedo, colour (4 x 16 B)
 //                                  <Guided>: + the two noise planes in, var_raw out in the albedo's spare word
@@ -12,6 +13,14 @@
 //                                  scalars in the uniform state), Tf_p out in the position's spare word
 //                                  <History>: <Guided> over the blend with the reprojected history: + 16 B of C and 16 B of VC in (when
 //                                  present); per pixel 12 B of S, 48 B of features, 32 B of noise, 16 + 16 B of history in, 64 B out
+//                                  <Moments>: the blend and its variance from the history's moments, no noise planes: per pixel 12 B of
+//                                  S, 48 B of features, 16 + 16 B of history in, 64 B out; var_raw = -1 marks a pixel for the next kernel
+//   k_denoise_var_spatial          the moments form, between prepare and the prefilter; the level kernel's shape (64 x 4 tiles, a wave is
+//                                  64 pixels of a row).  A wave with no marked lane leaves on a ballot of the mark (4 B per lane read):
+//                                  how many do is the frame's affair (misses are always marked).  A marked lane walks its 7 x 7 neighbourhood, 3 x 16 B per tap
+//                                  (n, p, c), rows outer; neighbouring lanes read neighbouring pixels (1 KiB per wave and load when all
+//                                  are marked, as on the first view), the 7-fold reuse between rows and columns is L1's and L2's; no
+//                                  LDS.  Writes the lane's own a.w only
 //   k_denoise_var_prefilter<bool>  the guided forms; one thread per pixel, 64 x 4 tiles: 3 x 3 over var_raw and the hit flags, var_0 into
 //                                  colour buffer 0's .w.  <true>, the adaptive form: over var_raw * Tf of the nine neighbours (n.w, a.w,
 //                                  p.w), back in the centre's unit
@@ -60,14 +69,30 @@ struct PrepareIn<Form::History> {
   const V4* __restrict__ VC;
   float Tf, Df, samples;
 };
+template <>
+struct PrepareIn<Form::Moments> {
+  const V4* __restrict__ C;
+  const V4* __restrict__ VC;
+  float samples;
+};
 template <Form kForm, typename... In>
 __global__ __launch_bounds__(kBlock) void k_denoise_prepare(int npix, const float* __restrict__ S, const V4* __restrict__ planes, In... in, int keep_albedo,
                                                             V4* __restrict__ n, V4* __restrict__ p, V4* __restrict__ a, V4* __restrict__ c) {
   const int i = blockIdx.x * kBlock + threadIdx.x;
   const PrepareIn<kForm> d{in...};
   const V4* noise = nullptr;
-  if constexpr (kForm != Form::Plain) noise = d.noise;
+  if constexpr (kForm != Form::Plain && kForm != Form::Moments) noise = d.noise;
   if (i < npix) ptdn::prepare_pixel_of<kForm>((size_t)i, (size_t)npix, S, planes, noise, d, keep_albedo, n, p, a, c);
+}
+
+// `a` is read (the lane's own mark) and written (the lane's own var_raw): no __restrict__ promise is needed or made for it.
+__global__ __launch_bounds__(kBlock) void k_denoise_var_spatial(int W, int R, Params P, const V4* __restrict__ n, const V4* __restrict__ p,
+                                                                const V4* __restrict__ c, V4* a) {
+  const int x = blockIdx.x * kLevelX + (threadIdx.x & (kLevelX - 1));
+  const int y = blockIdx.y * kLevelY + threadIdx.x / kLevelX;
+  const bool marked = x < W && y < R && ptdn::spatial_marked(a[(size_t)y * W + x].w);
+  if (__ballot(marked) == 0) return;  // wave-uniform: no lane of this wave has anything to do
+  if (marked) ptdn::var_spatial_pixel(W, R, x, y, P, n, p, c, a);
 }
 
 template <bool kAdaptive>
@@ -96,7 +121,7 @@ __global__ __launch_bounds__(kBlock) void k_denoise_finish(int npix, int keep_al
 
 // pt_internal.h.  Everything is checked before the first launch; no allocation, no synchronisation.
 int pt_denoise_launch(hipStream_t stream, const ptdn::Job& j, void* workspace_dev, const float** rgb_avg_dev) {
-  static const char* const kWho[] = {"pt_denoise", "pt_denoise_guided", "pt_denoise_adaptive", "pt_history_denoise"};
+  static const char* const kWho[] = {"pt_denoise", "pt_denoise_guided", "pt_denoise_adaptive", "pt_history_denoise", "pt_history_denoise_ex"};
   const char* who = kWho[(int)j.form];
   const int w = j.f.w, rows = j.f.rows;
   const Params& P = j.P;
@@ -105,6 +130,7 @@ int pt_denoise_launch(hipStream_t stream, const ptdn::Job& j, void* workspace_de
   const bool ok = j.form == Form::Plain      ? d.Tf > 0.0f
                   : j.form == Form::Guided   ? j.f.noise && d.Tf >= 2.0f && d.Df >= d.Tf
                   : j.form == Form::Adaptive ? j.f.noise && (d.cnt || (d.M >= 2 && d.T >= d.M))
+                  : j.form == Form::Moments  ? d.samples > 0.0f && !d.C == !d.VC
                                              : j.f.noise && d.Tf >= 2.0f && d.Df >= d.Tf && d.samples > 0.0f && !d.C == !d.VC;
   if (!j.f.rgb_sum || !j.f.planes || !workspace_dev || !ok || P.levels < 1 || P.levels > ptdn::kMaxLevels) return pt_fail("%s: bad argument", who);
   const int npix = w * rows;
@@ -112,7 +138,7 @@ int pt_denoise_launch(hipStream_t stream, const ptdn::Job& j, void* workspace_de
   V4 *p = n + npix, *a = p + npix, *col[2] = {a + npix, a + 2 * (size_t)npix};
   const int flat = (npix + kBlock - 1) / kBlock;
   const dim3 tiles((w + kLevelX - 1) / kLevelX, (rows + kLevelY - 1) / kLevelY);
-  const bool guided = j.form != Form::Plain, adaptive = j.form == Form::Adaptive, history = j.form == Form::History;
+  const bool guided = j.form != Form::Plain, adaptive = j.form == Form::Adaptive, history = j.form == Form::History, moments = j.form == Form::Moments;
   const V4 *planes = reinterpret_cast<const V4*>(j.f.planes), *noise = reinterpret_cast<const V4*>(j.f.noise);
   if (adaptive)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_denoise_prepare<Form::Adaptive, const V4* __restrict__, const ptad::Cnt* __restrict__, int, int>), dim3(flat), dim3(kBlock),
@@ -120,12 +146,16 @@ int pt_denoise_launch(hipStream_t stream, const ptdn::Job& j, void* workspace_de
   else if (history)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_denoise_prepare<Form::History, const V4* __restrict__, const V4* __restrict__, const V4* __restrict__, float, float, float>),
                        dim3(flat), dim3(kBlock), 0, stream, npix, j.f.rgb_sum, planes, noise, d.C, d.VC, d.Tf, d.Df, d.samples, P.keep_albedo, n, p, a, col[0]);
+  else if (moments)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_denoise_prepare<Form::Moments, const V4* __restrict__, const V4* __restrict__, float>), dim3(flat), dim3(kBlock), 0, stream,
+                       npix, j.f.rgb_sum, planes, d.C, d.VC, d.samples, P.keep_albedo, n, p, a, col[0]);
   else if (guided)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_denoise_prepare<Form::Guided, const V4* __restrict__, float, float>), dim3(flat), dim3(kBlock), 0, stream, npix, j.f.rgb_sum,
                        planes, noise, d.Tf, d.Df, P.keep_albedo, n, p, a, col[0]);
   else
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_denoise_prepare<Form::Plain, float>), dim3(flat), dim3(kBlock), 0, stream, npix, j.f.rgb_sum, planes, d.Tf, P.keep_albedo, n, p,
                        a, col[0]);
+  if (moments) hipLaunchKernelGGL(k_denoise_var_spatial, tiles, dim3(kBlock), 0, stream, w, rows, P, n, p, col[0], a);
   if (guided)
     hipLaunchKernelGGL(adaptive ? k_denoise_var_prefilter<true> : k_denoise_var_prefilter<false>, tiles, dim3(kBlock), 0, stream, w, rows, n, a, p, col[0]);
   for (int l = 0; l < P.levels; ++l) {
@@ -144,6 +174,7 @@ int pt_denoise_launch(hipStream_t stream, const ptdn::Job& j, void* workspace_de
 // pt_internal.h.  Plain: samples.  Guided: the fold counters M = groups, T = iters -> ptnz::fold_scalars' Tf, Df.  Adaptive: (T, M) for
 // every pixel of the uniform state; whoever has a count plane sets div.cnt afterwards.  History: the guided form's two and samples;
 // whoever has the planes C and VC sets div.C and div.VC (a launch) or f.current and f.current_var (the host loop) afterwards.
+// Moments: samples alone, and the planes likewise.
 int pt_denoise_resolve(const char* who, ptdn::Form form, float samples, int groups, int64_t iters, const PtDenoiseOptions* opt, ptdn::Job* j) {
   if (form == Form::Plain && !(samples > 0.0f)) return pt_fail("%s: samples must be positive", who);
   if (form == Form::Guided || form == Form::History) {
@@ -152,9 +183,9 @@ int pt_denoise_resolve(const char* who, ptdn::Form form, float samples, int grou
   }
   *j = ptdn::Job{};
   j->form = form;
-  if (const char* msg = ptdn::resolve(opt, &j->P, form == Form::Plain ? 4.0f : form == Form::History ? ptdn::kHistorySigmaColor : ptdn::kGuidedSigmaColor)) return pt_fail("%s: %s", who, msg);
+  if (const char* msg = ptdn::resolve(opt, &j->P, form == Form::Plain ? 4.0f : form == Form::History || form == Form::Moments ? ptdn::kHistorySigmaColor : ptdn::kGuidedSigmaColor)) return pt_fail("%s: %s", who, msg);
   if (form == Form::Plain) j->div.Tf = samples;
-  if (form == Form::History) j->div.samples = samples;
+  if (form == Form::History || form == Form::Moments) j->div.samples = samples;
   if (form == Form::Guided || form == Form::History) {
     const ptnz::Fold f = ptnz::fold_scalars(1, groups, iters);
     j->div.Tf = f.Tf, j->div.Df = f.Df;
@@ -189,6 +220,20 @@ int pt_history_denoise_check(const char* who, int w, int rows, const float* rgb_
     return pt_fail("%s: the current plane %s its variance: both or neither (a lookup made with PT_HISTORY_VARIANCE gives both)", who,
                    current_plane ? "comes without" : "is absent, but not");
   if (!rgb_avg) return pt_fail("%s: null buffer", who);
+  return 0;
+}
+
+// ... and of the moments form, in pt_history_denoise_ex's order: the arrays' shape, samples, the options, C without VC, no output.
+int pt_history_denoise_moments_check(const char* who, int w, int rows, const float* rgb_sum, const float* planes, float samples, const float* current_plane,
+                                     const float* current_var, const PtDenoiseOptions* opt, bool has_output, ptdn::Job* j) {
+  if (w <= 0 || rows <= 0 || (int64_t)w * rows > (1ll << 30)) return pt_fail("%s: a frame of %d x %d pixels is not supported", who, w, rows);
+  if (!rgb_sum || !planes) return pt_fail("%s: null argument", who);
+  if (pt_history_check_samples(who, samples)) return -1;
+  if (pt_denoise_resolve(who, Form::Moments, samples, 0, 0, opt, j)) return -1;
+  if (!current_plane != !current_var)
+    return pt_fail("%s: the current plane %s its moments: both or neither (a lookup made with PT_HISTORY_MOMENTS gives both)", who,
+                   current_plane ? "comes without" : "is absent, but not");
+  if (!has_output) return pt_fail("%s: null buffer", who);
   return 0;
 }
 
@@ -232,6 +277,16 @@ int pt_history_denoise_host(int w, int rows, const float* rgb_sum, const float* 
     return -1;
   j.f = {w, rows, rgb_sum, planes, noise_planes, current_plane, current_var};
   ptdn::denoise_host(j, nullptr, rgb_avg);
+  return 0;
+}
+int pt_history_denoise_moments_host(int w, int rows, const float* rgb_sum, const float* planes, float samples, const float* current_plane,
+                                    const float* current_var, const PtDenoiseOptions* opt, float* rgb_avg, float* var_raw, uint8_t* mark) {
+  ptdn::Job j{};
+  if (pt_history_denoise_moments_check("pt_history_denoise_moments_host", w, rows, rgb_sum, planes, samples, current_plane, current_var, opt,
+                                       rgb_avg || var_raw || mark, &j))
+    return -1;
+  j.f = {w, rows, rgb_sum, planes, nullptr, current_plane, current_var};
+  ptdn::denoise_host(j, nullptr, rgb_avg, var_raw, nullptr, mark);
   return 0;
 }
 int pt_denoise_adaptive_host(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, const int32_t* counts,

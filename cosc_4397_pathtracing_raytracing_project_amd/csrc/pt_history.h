@@ -13,10 +13,16 @@
 // (pt_history_denoise: ptdn::Form::History in pt_denoise.h, whose prepare runs blend_component and blend_variance below).  The
 // <false> instantiations are the bodies as they stood before the variance side existed.
 //
+// The moments side (PT_HISTORY_MOMENTS; capture_pixel_of<kMoments>, and the same reproject_pixel_of<true>): the two planes hold
+// VK = {m2.xyz, r} instead — the second moment of the views' mean colours that formed K0.xyz, weighted as the colour was, and the sum
+// of the squared weights of those views — so that the variance of the blend comes from the differences BETWEEN views and a view
+// needs no fold (1 spp per view).  Its lookup interpolates all four components of VK where the variance kind's interpolates three and
+// writes +0: reproject_pixel_of<kMoments>, an instantiation of its own, so that the variance kind's kernel is the code it was.
+// pt_history_denoise_ex: ptdn::Form::Moments in pt_denoise.h, whose prepare runs blend_moments below.
+//
 // Out of scope (pt_amd.h says the same): pt_group_* (a context's interleaved rows cannot look up their neighbours), feeding the
 // history into the noise estimate or adaptive sampling, feeding the FILTERED image back into the history (K keeps the unfiltered
-// blend), a view with fewer than 2 folds (1 spp per frame), a spatial variance fallback for disoccluded pixels, motion of anything
-// but the camera, and correcting the smoothing the bilinear lookup adds — the carried image is a biased estimator, and the carried
+// blend), motion of anything but the camera, and correcting the smoothing the bilinear lookup adds — the carried image is a biased estimator, and the carried
 // variance is interpolated linearly (as SVGF interpolates its moments), which overstates it: the lookup's smoothing lowers the true one.
 #pragma once
 #include <cstddef>
@@ -135,11 +141,45 @@ PT_HD float blend_variance(float vn, float samples, float vh, float Th) {
   const float wh = Th / dn;
   return (wn * wn) * vn + (wh * wh) * vh;
 }
+// The moments of the blend: x the mean of the new samples of one component, m2h the history's second moment of it; and the blend's
+// sum of squared weights from the history's rh (one value per pixel).  C absent: Th = m2h = rh = +0, which gives {x * x, 1}.
+struct MomentWeights {
+  float wn, wh;
+};
+PT_HD MomentWeights moment_weights(float samples, float Th) {
+#pragma clang fp contract(off)
+  const float dn = samples + Th;
+  return MomentWeights{samples / dn, Th / dn};
+}
+PT_HD float blend_moment(float x, float m2h, const MomentWeights& w) {
+#pragma clang fp contract(off)
+  return w.wn * (x * x) + w.wh * m2h;
+}
+PT_HD float blend_weight_sum(float rh, const MomentWeights& w) {
+#pragma clang fp contract(off)
+  return w.wn * w.wn + (w.wh * w.wh) * rh;
+}
+// {m2b.xyz, rb} of pixel i from the SUM image and the history's {m2h.xyz, rh} (vh; absent: all +0)
+template <typename P4>
+PT_HD P4 blend_moments(size_t i, const float* S, float samples, float Th, const P4& vh) {
+#pragma clang fp contract(off)
+  const MomentWeights w = moment_weights(samples, Th);
+  const float x = S[3 * i] / samples, y = S[3 * i + 1] / samples, z = S[3 * i + 2] / samples;
+  return P4{blend_moment(x, vh.x, w), blend_moment(y, vh.y, w), blend_moment(z, vh.z, w), blend_weight_sum(vh.w, w)};
+}
+// What travels beside the history: nothing, a variance (PT_HISTORY_VARIANCE) or moments (PT_HISTORY_MOMENTS)
+constexpr int kPlain = 0, kVariance = 1, kMoments = 2;
 // What the variance side of a capture reads and writes: the fold's two planes with their divisors, VC (or nullptr: absent) and VK.
 template <typename P4>
 struct VarCapture {
   const P4* noise;
   float Tf, Df;
+  const P4* VC;
+  P4* VK;
+};
+// ... and the moments side: VC (or nullptr: absent) and VK; the new samples' part comes from the SUM image itself.
+template <typename P4>
+struct MomCapture {
   const P4* VC;
   P4* VK;
 };
@@ -169,10 +209,16 @@ PT_HD void capture_variance_pixel(size_t i, size_t npix, float samples, float Th
                  blend_variance(sample_variance(prev.y, q.y, var.Tf, var.Df), samples, vh.y, Th),
                  blend_variance(sample_variance(prev.z, q.z, var.Tf, var.Df), samples, vh.z, Th), 0.0f};
 }
+// The moments side of a capture: VK[i] = {m2b.xyz, rb} of the blend K0.xyz; Th = C.w of the pixel (C absent: +0).
+template <typename P4>
+PT_HD void capture_moments_pixel(size_t i, const float* S, float samples, float Th, const MomCapture<P4>& mom) {
+  const P4 vh = mom.VC ? mom.VC[i] : P4{0.0f, 0.0f, 0.0f, 0.0f};
+  mom.VK[i] = blend_moments(i, S, samples, Th, vh);
+}
 // Pixel i: the kept planes K (kKeptPlanes planes of npix) from the SUM image, the feature sums and the current plane (or nullptr).
-// kVar: also VK[i], from `var` (read only then).
-template <bool kVar, typename P4>
-PT_HD void capture_pixel_of(size_t i, size_t npix, const float* S, const P4* feat, const P4* C, float samples, P4* K, const VarCapture<P4>& var) {
+// kKind: kVariance / kMoments also write VK[i], from `var` (a VarCapture / MomCapture; read only then).
+template <int kKind, typename P4, typename Side>
+PT_HD void capture_pixel_of(size_t i, size_t npix, const float* S, const P4* feat, const P4* C, float samples, P4* K, const Side& var) {
 #pragma clang fp contract(off)
   const Surface s = surface(i, npix, feat);
   const P4 c = C ? C[i] : P4{0.0f, 0.0f, 0.0f, 0.0f};
@@ -180,23 +226,26 @@ PT_HD void capture_pixel_of(size_t i, size_t npix, const float* S, const P4* fea
             blend_component(S[3 * i + 2], samples, c.z, c.w), samples + c.w};
   K[npix + i] = P4{s.px, s.py, s.pz, bits_float(s.id)};
   K[2 * npix + i] = P4{s.nx, s.ny, s.nz, 0.0f};
-  if constexpr (kVar) capture_variance_pixel(i, npix, samples, c.w, var);
+  if constexpr (kKind == kVariance) capture_variance_pixel(i, npix, samples, c.w, var);
+  if constexpr (kKind == kMoments) capture_moments_pixel(i, S, samples, c.w, var);
 }
 template <typename P4>
 PT_HD void capture_pixel(size_t i, size_t npix, const float* S, const P4* feat, const P4* C, float samples, P4* K) {
-  capture_pixel_of<false>(i, npix, S, feat, C, samples, K, VarCapture<P4>{});
+  capture_pixel_of<kPlain>(i, npix, S, feat, C, samples, K, VarCapture<P4>{});
 }
 
 // Tile pixel i = (x, r): the history K as seen through the kept camera, resampled at this pixel's first hit.  reject: one byte per
 // geom (num_geoms of them), read unless keep_view_dependent; an id outside 1 .. num_geoms is rejected like a listed geom.  A gather:
 // of each tap K1 is read first, then K2, and K0 only when the tap passed.  kVar: VK(q) is read after K0, for a tap that passed only;
-// vh receives VC's value for the pixel, all zero wherever the pixel is rejected (it is not touched otherwise).
-template <bool kVar, typename P4>
+// vh receives VC's value for the pixel, all zero wherever the pixel is rejected (it is not touched otherwise).  kKind: kPlain reads no
+// VK; kVariance interpolates VK.xyz and writes w = +0; kMoments interpolates all four components (w: the sum of squared weights).
+template <int kKind, typename P4>
 PT_HD P4 reproject_pixel_of(size_t i, const View& v, const P4* K, const P4* feat, const uint8_t* reject, int32_t num_geoms, const Params& P, const P4* VK,
                             P4& vh) {
 #pragma clang fp contract(off)
   const size_t npix = (size_t)v.W * v.R;
   const P4 zero{0.0f, 0.0f, 0.0f, 0.0f};
+  constexpr bool kVar = kKind != kPlain;
   if constexpr (kVar) vh = zero;
   const Surface s = surface(i, npix, feat);
   if (!s.hit) return zero;
@@ -212,7 +261,7 @@ PT_HD P4 reproject_pixel_of(size_t i, const View& v, const P4* K, const P4* feat
   const int ix = (int)fx, iy = (int)fy - v.row0;  // in range: the comparisons above were made in float
   const float tol = P.plane_tol * dz;
   float accx = 0.0f, accy = 0.0f, accz = 0.0f, tacc = 0.0f, wsum = 0.0f;
-  [[maybe_unused]] float vaccx = 0.0f, vaccy = 0.0f, vaccz = 0.0f;
+  [[maybe_unused]] float vaccx = 0.0f, vaccy = 0.0f, vaccz = 0.0f, vaccw = 0.0f;
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int qr = iy + j;
@@ -238,19 +287,21 @@ PT_HD P4 reproject_pixel_of(size_t i, const View& v, const P4* K, const P4* feat
       if constexpr (kVar) {
         const P4 vk = VK[q];
         vaccx = vaccx + b * vk.x, vaccy = vaccy + b * vk.y, vaccz = vaccz + b * vk.z;
+        if constexpr (kKind == kMoments) vaccw = vaccw + b * vk.w;
       }
       wsum = wsum + b;
     }
   }
   if (!(wsum >= kMinWeight)) return zero;
   const float tw = tacc / wsum;
-  if constexpr (kVar) vh = P4{vaccx / wsum, vaccy / wsum, vaccz / wsum, 0.0f};
+  if constexpr (kKind == kVariance) vh = P4{vaccx / wsum, vaccy / wsum, vaccz / wsum, 0.0f};
+  if constexpr (kKind == kMoments) vh = P4{vaccx / wsum, vaccy / wsum, vaccz / wsum, vaccw / wsum};
   return P4{accx / wsum, accy / wsum, accz / wsum, tw < P.cap ? tw : P.cap};
 }
 template <typename P4>
 PT_HD P4 reproject_pixel(size_t i, const View& v, const P4* K, const P4* feat, const uint8_t* reject, int32_t num_geoms, const Params& P) {
   P4 unused;
-  return reproject_pixel_of<false>(i, v, K, feat, reject, num_geoms, P, static_cast<const P4*>(nullptr), unused);
+  return reproject_pixel_of<kPlain>(i, v, K, feat, reject, num_geoms, P, static_cast<const P4*>(nullptr), unused);
 }
 
 // The whole tile on the host.
@@ -269,13 +320,28 @@ inline void capture_variance_host(size_t npix, const float* noise, float Tf, flo
   const VarCapture<F4> var{reinterpret_cast<const F4*>(noise), Tf, Df, reinterpret_cast<const F4*>(VC), reinterpret_cast<F4*>(VK)};
   for (size_t i = 0; i < npix; ++i) capture_variance_pixel(i, npix, samples, c4 ? c4[i].w : 0.0f, var);  // (K: capture_host, from the image and the features)
 }
-inline void reproject_variance_host(const View& v, const float* K, const float* feat, const uint8_t* reject, int32_t num_geoms, const Params& P, const float* VK,
-                                    float* C, float* VC) {
+// ... and the moments side: VK beside K's capture, C and VC = {m2h.xyz, rh} in one pass of the lookup
+inline void capture_moments_host(size_t npix, const float* S, float samples, const float* C, const float* VC, float* VK) {
+  const F4* c4 = reinterpret_cast<const F4*>(C);
+  const MomCapture<F4> mom{reinterpret_cast<const F4*>(VC), reinterpret_cast<F4*>(VK)};
+  for (size_t i = 0; i < npix; ++i) capture_moments_pixel(i, S, samples, c4 ? c4[i].w : 0.0f, mom);
+}
+template <int kKind>
+inline void reproject_with_host(const View& v, const float* K, const float* feat, const uint8_t* reject, int32_t num_geoms, const Params& P, const float* VK,
+                                float* C, float* VC) {
   const size_t npix = (size_t)v.W * v.R;
   F4 *out = reinterpret_cast<F4*>(C), *vout = reinterpret_cast<F4*>(VC);
   for (size_t i = 0; i < npix; ++i)
-    out[i] = reproject_pixel_of<true>(i, v, reinterpret_cast<const F4*>(K), reinterpret_cast<const F4*>(feat), reject, num_geoms, P, reinterpret_cast<const F4*>(VK),
+    out[i] = reproject_pixel_of<kKind>(i, v, reinterpret_cast<const F4*>(K), reinterpret_cast<const F4*>(feat), reject, num_geoms, P, reinterpret_cast<const F4*>(VK),
                                       vout[i]);
+}
+inline void reproject_variance_host(const View& v, const float* K, const float* feat, const uint8_t* reject, int32_t num_geoms, const Params& P, const float* VK,
+                                    float* C, float* VC) {
+  reproject_with_host<kVariance>(v, K, feat, reject, num_geoms, P, VK, C, VC);
+}
+inline void reproject_moments_host(const View& v, const float* K, const float* feat, const uint8_t* reject, int32_t num_geoms, const Params& P, const float* VK,
+                                   float* C, float* VC) {
+  reproject_with_host<kMoments>(v, K, feat, reject, num_geoms, P, VK, C, VC);
 }
 inline void blend_host(size_t npix, const float* S, float samples, const float* C, float* rgb_avg) {
   for (size_t i = 0; i < npix; ++i) blend_pixel(i, S, samples, reinterpret_cast<const F4*>(C), rgb_avg);

@@ -12,11 +12,15 @@
 //                        view land on neighbouring pixels of the kept one, so the taps of a wave are a few runs of rows of K and
 //                        the four taps of a pixel share lines with its neighbours': the reuse is L1's and L2's, no LDS
 //   k_history_blend      streaming: 12 B of S and (when present) 16 B of C in, 12 B out per pixel
-// The variance side (PT_HISTORY_VARIANCE) is a template parameter of the first two; <false> is the kernel as it stood before, with
-// the arguments it took, and what flags == 0 launches.
-//   k_history_capture<true>    + 32 B of the fold's planes and (when present) 16 B of VC in, 16 B of VK out per pixel
-//   k_history_reproject<true>  + 16 B of VC out per pixel; per tap that passed 16 B of VK, read after K0 at the same index
+// What travels beside the history (PT_HISTORY_VARIANCE, PT_HISTORY_MOMENTS) is a template parameter of the first two; <kPlain> and
+// <kVariance> are the kernels as they stood before, with the arguments they took, and what flags == 0 launches.
+//   k_history_capture<kVariance>  + 32 B of the fold's planes and (when present) 16 B of VC in, 16 B of VK out per pixel
+//   k_history_capture<kMoments>   + (when present) 16 B of VC in, 16 B of VK out per pixel; no fold is read
+//   k_history_reproject<kVariance>  + 16 B of VC out per pixel; per tap that passed 16 B of VK, read after K0 at the same index
+//   k_history_reproject<kMoments>   the same loads and stores; the fourth component of VK is interpolated too
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "pt_history.h"
 #include "pt_internal.h"
@@ -28,24 +32,26 @@ using pthi::V4;
 using pthi::View;
 constexpr int kBlock = 256;
 
-// In...: nothing, or the members of pthi::VarCapture one by one (scalars at fixed offsets; the <false> kernel takes what it took)
-template <bool kVar, typename... In>
+// In...: nothing, or the members of pthi::VarCapture (kMoments: pthi::MomCapture) one by one (scalars at fixed offsets; the kPlain
+// kernel takes what it took)
+template <int kKind, typename... In>
 __global__ __launch_bounds__(kBlock) void k_history_capture(int npix, const float* __restrict__ S, const V4* __restrict__ feat, const V4* C, float samples,
                                                             V4* __restrict__ K, In... in) {
+  using Side = std::conditional_t<kKind == pthi::kMoments, pthi::MomCapture<V4>, pthi::VarCapture<V4>>;
   const int i = blockIdx.x * kBlock + threadIdx.x;
-  if (i < npix) pthi::capture_pixel_of<kVar>((size_t)i, (size_t)npix, S, feat, C, samples, K, pthi::VarCapture<V4>{in...});
+  if (i < npix) pthi::capture_pixel_of<kKind>((size_t)i, (size_t)npix, S, feat, C, samples, K, Side{in...});
 }
 
 // In...: nothing, or VK and VC
-template <bool kVar, typename... In>
+template <int kKind, typename... In>
 __global__ __launch_bounds__(kBlock) void k_history_reproject(int npix, View v, const V4* __restrict__ K, const V4* __restrict__ feat,
                                                               const uint8_t* __restrict__ reject, int num_geoms, Params P, V4* __restrict__ C, In... in) {
   const int i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= npix) return;
-  if constexpr (kVar) {
+  if constexpr (kKind != pthi::kPlain) {
     const auto [VK, VC] = pthi::VarReproject<V4>{in...};
     V4 vh;
-    C[i] = pthi::reproject_pixel_of<true>((size_t)i, v, K, feat, reject, num_geoms, P, VK, vh);
+    C[i] = pthi::reproject_pixel_of<kKind>((size_t)i, v, K, feat, reject, num_geoms, P, VK, vh);
     VC[i] = vh;
   } else {
     C[i] = pthi::reproject_pixel((size_t)i, v, K, feat, reject, num_geoms, P);
@@ -70,7 +76,7 @@ bool bad_frame(int w, int rows) { return w <= 0 || rows <= 0 || rows >= 32768 ||
 int pt_history_capture_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, const float* planes_dev, const void* current_dev, float samples,
                               void* kept_dev) {
   if (pixels <= 0 || pixels > (1 << 30) || !rgb_sum_dev || !planes_dev || !kept_dev || !(samples > 0.0f)) return pt_fail("pt_history_capture: bad argument");
-  hipLaunchKernelGGL(k_history_capture<false>, dim3((pixels + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, pixels, rgb_sum_dev,
+  hipLaunchKernelGGL(k_history_capture<pthi::kPlain>, dim3((pixels + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, pixels, rgb_sum_dev,
                      reinterpret_cast<const V4*>(planes_dev), static_cast<const V4*>(current_dev), samples, static_cast<V4*>(kept_dev));
   return launched("pt_history_capture");
 }
@@ -81,9 +87,19 @@ int pt_history_capture_variance_launch(hipStream_t stream, int pixels, const flo
   if (pixels <= 0 || pixels > (1 << 30) || !rgb_sum_dev || !planes_dev || !kept_dev || !(samples > 0.0f) || !noise_dev || !(Tf >= 2.0f) || !(Df >= Tf) ||
       !kept_var_dev || !current_dev != !current_var_dev)
     return pt_fail("pt_history_capture_ex: bad argument");
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_history_capture<true, const V4*, float, float, const V4*, V4*>), dim3((pixels + kBlock - 1) / kBlock), dim3(kBlock), 0, stream,
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_history_capture<pthi::kVariance, const V4*, float, float, const V4*, V4*>), dim3((pixels + kBlock - 1) / kBlock), dim3(kBlock), 0, stream,
                      pixels, rgb_sum_dev, reinterpret_cast<const V4*>(planes_dev), static_cast<const V4*>(current_dev), samples, static_cast<V4*>(kept_dev),
                      reinterpret_cast<const V4*>(noise_dev), Tf, Df, static_cast<const V4*>(current_var_dev), static_cast<V4*>(kept_var_dev));
+  return launched("pt_history_capture_ex");
+}
+// ... with the moments side: current_var_dev VC beside current_dev (both or neither), kept_var_dev VK; no fold.
+int pt_history_capture_moments_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, const float* planes_dev, const void* current_dev, float samples,
+                                      void* kept_dev, const void* current_var_dev, void* kept_var_dev) {
+  if (pixels <= 0 || pixels > (1 << 30) || !rgb_sum_dev || !planes_dev || !kept_dev || !(samples > 0.0f) || !kept_var_dev || !current_dev != !current_var_dev)
+    return pt_fail("pt_history_capture_ex: bad argument");
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_history_capture<pthi::kMoments, const V4*, V4*>), dim3((pixels + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, pixels,
+                     rgb_sum_dev, reinterpret_cast<const V4*>(planes_dev), static_cast<const V4*>(current_dev), samples, static_cast<V4*>(kept_dev),
+                     static_cast<const V4*>(current_var_dev), static_cast<V4*>(kept_var_dev));
   return launched("pt_history_capture_ex");
 }
 
@@ -93,22 +109,32 @@ int pt_history_reproject_launch(hipStream_t stream, const pthi::View& v, const v
   if (!kept_dev || !planes_dev || !current_dev || (!P.keep_view_dependent && (num_geoms < 0 || (num_geoms > 0 && !reject_dev))))
     return pt_fail("pt_history_reproject: bad argument");
   const int npix = v.W * v.R;
-  hipLaunchKernelGGL(k_history_reproject<false>, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, npix, v, static_cast<const V4*>(kept_dev),
+  hipLaunchKernelGGL(k_history_reproject<pthi::kPlain>, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, npix, v, static_cast<const V4*>(kept_dev),
                      reinterpret_cast<const V4*>(planes_dev), reject_dev, num_geoms, P, static_cast<V4*>(current_dev));
   return launched("pt_history_reproject");
 }
-// ... with the variance side: kept_var_dev VK, current_var_dev VC.
-int pt_history_reproject_variance_launch(hipStream_t stream, const pthi::View& v, const void* kept_dev, const float* planes_dev, const uint8_t* reject_dev,
-                                         int num_geoms, const pthi::Params& P, void* current_dev, const void* kept_var_dev, void* current_var_dev) {
+// ... with the variance or the moments side: kept_var_dev VK, current_var_dev VC.
+template <int kKind>
+static int reproject_with_launch(hipStream_t stream, const pthi::View& v, const void* kept_dev, const float* planes_dev, const uint8_t* reject_dev,
+                                 int num_geoms, const pthi::Params& P, void* current_dev, const void* kept_var_dev, void* current_var_dev) {
   if (bad_frame(v.W, v.R)) return pt_fail("pt_history_reproject_ex: a tile of %d x %d pixels is not supported", v.W, v.R);
   if (!kept_dev || !planes_dev || !current_dev || !kept_var_dev || !current_var_dev ||
       (!P.keep_view_dependent && (num_geoms < 0 || (num_geoms > 0 && !reject_dev))))
     return pt_fail("pt_history_reproject_ex: bad argument");
   const int npix = v.W * v.R;
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_history_reproject<true, const V4*, V4*>), dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, npix, v,
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_history_reproject<kKind, const V4*, V4*>), dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, npix, v,
                      static_cast<const V4*>(kept_dev), reinterpret_cast<const V4*>(planes_dev), reject_dev, num_geoms, P, static_cast<V4*>(current_dev),
                      static_cast<const V4*>(kept_var_dev), static_cast<V4*>(current_var_dev));
   return launched("pt_history_reproject_ex");
+}
+
+int pt_history_reproject_variance_launch(hipStream_t stream, const pthi::View& v, const void* kept_dev, const float* planes_dev, const uint8_t* reject_dev,
+                                         int num_geoms, const pthi::Params& P, void* current_dev, const void* kept_var_dev, void* current_var_dev) {
+  return reproject_with_launch<pthi::kVariance>(stream, v, kept_dev, planes_dev, reject_dev, num_geoms, P, current_dev, kept_var_dev, current_var_dev);
+}
+int pt_history_reproject_moments_launch(hipStream_t stream, const pthi::View& v, const void* kept_dev, const float* planes_dev, const uint8_t* reject_dev,
+                                        int num_geoms, const pthi::Params& P, void* current_dev, const void* kept_var_dev, void* current_var_dev) {
+  return reproject_with_launch<pthi::kMoments>(stream, v, kept_dev, planes_dev, reject_dev, num_geoms, P, current_dev, kept_var_dev, current_var_dev);
 }
 
 int pt_history_blend_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, float samples, const void* current_dev, float* rgb_avg_dev) {
@@ -183,6 +209,27 @@ extern "C" int pt_history_reproject_variance_host(int w, int rows, int row0, con
   if (pt_history_reproject_check(who, w, rows, row0, kept_cam, kept_planes, feature_planes, reject_geom, num_geoms, opt, current_plane, &P)) return -1;
   if (!kept_var || !current_var) return pt_fail("%s: null argument", who);
   pthi::reproject_variance_host(pthi::make_view(*kept_cam, rows, row0), kept_planes, feature_planes, reject_geom, num_geoms, P, kept_var, current_plane, current_var);
+  return 0;
+}
+
+extern "C" int pt_history_capture_moments_host(int pixels, const float* rgb_sum, float samples, const float* current_plane, const float* current_var,
+                                               float* kept_var) {
+  const char* who = "pt_history_capture_moments_host";
+  if (pixels <= 0 || pixels > (1 << 30) || !rgb_sum || !kept_var) return pt_fail("%s: bad argument", who);
+  if (pt_history_check_samples(who, samples)) return -1;
+  if (!current_plane != !current_var) return pt_fail("%s: the current plane and its moments come together or not at all", who);
+  pthi::capture_moments_host((size_t)pixels, rgb_sum, samples, current_plane, current_var, kept_var);
+  return 0;
+}
+
+extern "C" int pt_history_reproject_moments_host(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
+                                                 const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, const float* kept_var,
+                                                 float* current_plane, float* current_var) {
+  pthi::Params P{};
+  const char* who = "pt_history_reproject_moments_host";
+  if (pt_history_reproject_check(who, w, rows, row0, kept_cam, kept_planes, feature_planes, reject_geom, num_geoms, opt, current_plane, &P)) return -1;
+  if (!kept_var || !current_var) return pt_fail("%s: null argument", who);
+  pthi::reproject_moments_host(pthi::make_view(*kept_cam, rows, row0), kept_planes, feature_planes, reject_geom, num_geoms, P, kept_var, current_plane, current_var);
   return 0;
 }
 

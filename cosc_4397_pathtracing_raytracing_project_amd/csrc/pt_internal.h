@@ -30,6 +30,10 @@ int pt_denoise_launch(hipStream_t stream, const ptdn::Job& j, void* workspace_de
 // the job resolved; a launch reads the planes C and VC from j->div.C and j->div.VC (both or neither), the host loop from j->f.
 int pt_history_denoise_check(const char* who, int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, int groups, int64_t iters,
                              float samples, const float* current_plane, const float* current_var, const PtDenoiseOptions* opt, const float* rgb_avg, ptdn::Job* j);
+// The moments form (ptdn::Form::Moments, pt_history_denoise_ex with PT_HISTORY_MOMENTS): the same for it; no fold, no noise planes.
+// has_output: the caller gave a buffer to write to.
+int pt_history_denoise_moments_check(const char* who, int w, int rows, const float* rgb_sum, const float* planes, float samples, const float* current_plane,
+                                     const float* current_var, const PtDenoiseOptions* opt, bool has_output, ptdn::Job* j);
 
 // The noise estimate (pt_noise.hip), on raw device pointers and a stream.  state_dev holds pt_noise_state_bytes(pixels) bytes:
 // PT_NOISE_PLANES planes of `pixels` float4, then one double per PT_NOISE_PIXELS_PER_PARTIAL pixels (k_noise_fold's partial sums),
@@ -115,4 +119,10 @@ int pt_history_capture_variance_launch(hipStream_t stream, int pixels, const flo
                                        void* kept_dev, const float* noise_dev, float Tf, float Df, const void* current_var_dev, void* kept_var_dev);
 int pt_history_reproject_variance_launch(hipStream_t stream, const pthi::View& v, const void* kept_dev, const float* planes_dev, const uint8_t* reject_dev,
                                          int num_geoms, const pthi::Params& P, void* current_dev, const void* kept_var_dev, void* current_var_dev);
+// The capture with the moments side (PT_HISTORY_MOMENTS): VC beside C (both or neither) and VK = {m2b.xyz, rb}; no fold is read.  The
+// lookup with moments interpolates all four components of VK (a kernel instantiation of its own; the variance kind's is untouched).
+int pt_history_capture_moments_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, const float* planes_dev, const void* current_dev, float samples,
+                                      void* kept_dev, const void* current_var_dev, void* kept_var_dev);
+int pt_history_reproject_moments_launch(hipStream_t stream, const pthi::View& v, const void* kept_dev, const float* planes_dev, const uint8_t* reject_dev,
+                                        int num_geoms, const pthi::Params& P, void* current_dev, const void* kept_var_dev, void* current_var_dev);
 int pt_history_blend_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, float samples, const void* current_dev, float* rgb_avg_dev);

@@ -477,7 +477,9 @@ static const char kNoFeatures[] = "%s: no feature pass has been rendered since t
 static pthi::V4* history_var_plane(const Ctx& g, int plane) { return static_cast<pthi::V4*>(g.d_hist_var) + (size_t)plane * g.N; }  // 0: VK, 1: VC
 // An undefined flag bit: what the _ex forms refuse right after a failed context.
 static int history_flags(const char* who, uint32_t flags) {
-  if (flags & ~PT_HISTORY_VARIANCE) return pt_fail("%s: undefined flag bit(s) 0x%x (defined: PT_HISTORY_VARIANCE)", who, flags & ~PT_HISTORY_VARIANCE);
+  constexpr uint32_t defined = PT_HISTORY_VARIANCE | PT_HISTORY_MOMENTS;
+  if (flags & ~defined) return pt_fail("%s: undefined flag bit(s) 0x%x (defined: PT_HISTORY_VARIANCE, PT_HISTORY_MOMENTS)", who, flags & ~defined);
+  if (flags == defined) return pt_fail("%s: the flags PT_HISTORY_VARIANCE and PT_HISTORY_MOMENTS exclude each other", who);
   return 0;
 }
 // What the variance needs of the folds: at least two, nothing rendered since, and `samples` the iterations they hold.
@@ -488,8 +490,13 @@ static int history_folds(const Ctx& g, const char* who, float samples) {
   return pt_history_check_fold_samples(who, samples, g.noise_iters);
 }
 static int history_current_variance(const Ctx& g, const char* who) {
-  if (g.hist_current && !g.hist_var_current)
+  if (g.hist_current && g.hist_var_current != PT_HISTORY_VARIANCE)
     return pt_fail("%s: the current plane has no variance: the lookup was made without PT_HISTORY_VARIANCE (pt_history_reproject_ex)", who);
+  return 0;
+}
+static int history_current_moments(const Ctx& g, const char* who) {
+  if (g.hist_current && g.hist_var_current != PT_HISTORY_MOMENTS)
+    return pt_fail("%s: the current plane has no moments: the lookup was made without PT_HISTORY_MOMENTS (pt_history_reproject_ex)", who);
   return 0;
 }
 
@@ -501,23 +508,28 @@ static int history_capture(PtContext* c, const char* who, float samples, uint32_
   if (history_admit(g, who)) return -1;
   if (!g.d_feat || !g.feat_fresh) return pt_fail(kNoFeatures, who);
   if (pt_history_check_samples(who, samples)) return -1;
-  const bool var = (flags & PT_HISTORY_VARIANCE) != 0;
+  const bool var = (flags & PT_HISTORY_VARIANCE) != 0, mom = (flags & PT_HISTORY_MOMENTS) != 0;
   if (var && (history_folds(g, who, samples) || history_current_variance(g, who))) return -1;
+  if (mom && history_current_moments(g, who)) return -1;
   HIP_OK(hipSetDevice(g.device));
   if (ensure(g, g.d_hist, pt_history_state_bytes((size_t)g.N), Zero::on_stream)) return -1;  // the first capture of the context
-  if (var && ensure(g, g.d_hist_var, pt_history_variance_bytes((size_t)g.N), Zero::on_stream)) return -1;  // ... with variance
+  if ((var || mom) && ensure(g, g.d_hist_var, pt_history_variance_bytes((size_t)g.N), Zero::on_stream)) return -1;  // ... with variance or moments
   const pthi::V4* current = g.hist_current ? history_plane(g, pthi::kKeptPlanes) : nullptr;
   if (var) {
     const ptnz::Fold f = ptnz::fold_scalars(1, g.noise_groups, g.noise_iters);
     if (pt_history_capture_variance_launch(g.stream, g.N, g.d_image, reinterpret_cast<const float*>(g.d_feat), current, samples, g.d_hist,
                                            static_cast<const float*>(g.d_noise), f.Tf, f.Df, current ? history_var_plane(g, 1) : nullptr, history_var_plane(g, 0)))
       return -1;
+  } else if (mom) {
+    if (pt_history_capture_moments_launch(g.stream, g.N, g.d_image, reinterpret_cast<const float*>(g.d_feat), current, samples, g.d_hist,
+                                          current ? history_var_plane(g, 1) : nullptr, history_var_plane(g, 0)))
+      return -1;
   } else if (pt_history_capture_launch(g.stream, g.N, g.d_image, reinterpret_cast<const float*>(g.d_feat), current, samples, g.d_hist)) {
     return -1;
   }
   g.hist_cam = g.cam;
   g.hist_kept = true;
-  g.hist_var_kept = var;  // a plain capture: kept without variance
+  g.hist_var_kept = flags;  // a plain capture: kept without variance or moments
   return 0;
 }
 int pt_ctx_history_capture(PtContext* c, float samples) { return history_capture(c, "pt_history_capture", samples, 0u, false); }
@@ -549,21 +561,26 @@ static int history_reproject(PtContext* c, const char* who, const PtHistoryOptio
   if (!g.d_feat || !g.feat_fresh) return pt_fail(kNoFeatures, who);
   pthi::Params P{};
   if (pt_history_resolve_options(who, opt, &P)) return -1;
-  const bool var = (flags & PT_HISTORY_VARIANCE) != 0;
-  if (var && (!g.d_hist_var || !g.hist_var_kept))
+  if (flags == PT_HISTORY_VARIANCE && (!g.d_hist_var || g.hist_var_kept != PT_HISTORY_VARIANCE))
     return pt_fail("%s: nothing has been captured with variance (pt_history_capture_ex with PT_HISTORY_VARIANCE)", who);
+  if (flags == PT_HISTORY_MOMENTS && (!g.d_hist_var || g.hist_var_kept != PT_HISTORY_MOMENTS))
+    return pt_fail("%s: nothing has been captured with moments (pt_history_capture_ex with PT_HISTORY_MOMENTS)", who);
   HIP_OK(hipSetDevice(g.device));
   if (history_reject_table(g)) return -1;
   const int W = g.cam.resolution[0];
   const pthi::View v = pthi::make_view(g.hist_cam, g.N / W, g.pixel_begin / W);
   const float* feat = reinterpret_cast<const float*>(g.d_feat);
   const int num_geoms = (int)g.camera_base.geoms.size();
-  if (var ? pt_history_reproject_variance_launch(g.stream, v, g.d_hist, feat, g.d_hist_reject, num_geoms, P, history_plane(g, pthi::kKeptPlanes),
+  if (flags == PT_HISTORY_VARIANCE
+          ? pt_history_reproject_variance_launch(g.stream, v, g.d_hist, feat, g.d_hist_reject, num_geoms, P, history_plane(g, pthi::kKeptPlanes),
                                                  history_var_plane(g, 0), history_var_plane(g, 1))
+      : flags == PT_HISTORY_MOMENTS
+          ? pt_history_reproject_moments_launch(g.stream, v, g.d_hist, feat, g.d_hist_reject, num_geoms, P, history_plane(g, pthi::kKeptPlanes),
+                                                history_var_plane(g, 0), history_var_plane(g, 1))
           : pt_history_reproject_launch(g.stream, v, g.d_hist, feat, g.d_hist_reject, num_geoms, P, history_plane(g, pthi::kKeptPlanes)))
     return -1;
   g.hist_current = true;
-  g.hist_var_current = var;
+  g.hist_var_current = flags;
   return 0;
 }
 int pt_ctx_history_reproject(PtContext* c, const PtHistoryOptions* opt) { return history_reproject(c, "pt_history_reproject", opt, 0u, false); }
@@ -582,8 +599,7 @@ static int history_denoise_refusal(const Ctx& g, const char* who, float samples,
   if (history_folds(g, who, samples) || history_current_variance(g, who)) return -1;
   return pt_denoise_resolve(who, ptdn::Form::History, samples, g.noise_groups, g.noise_iters, opt, j);
 }
-int pt_ctx_history_denoise_device(PtContext* c, float samples, const PtDenoiseOptions* opt, const float** rgb_dev) {
-  const char* who = "pt_history_denoise";
+static int history_denoise_device(PtContext* c, const char* who, float samples, const PtDenoiseOptions* opt, const float** rgb_dev) {
   if (need(c, who)) return -1;
   Ctx& g = *c;
   ptdn::Job j{};
@@ -599,11 +615,57 @@ int pt_ctx_history_denoise_device(PtContext* c, float samples, const PtDenoiseOp
   }
   return pt_denoise_launch(g.stream, j, g.d_denoise, rgb_dev);
 }
+int pt_ctx_history_denoise_device(PtContext* c, float samples, const PtDenoiseOptions* opt, const float** rgb_dev) {
+  return history_denoise_device(c, "pt_history_denoise", samples, opt, rgb_dev);
+}
 int pt_ctx_history_denoise(PtContext* c, float samples, const PtDenoiseOptions* opt, float* rgb_avg_host) {
   if (need(c, "pt_history_denoise")) return -1;
   ptdn::Job j{};
   if (history_denoise_refusal(*c, "pt_history_denoise", samples, opt, &j)) return -1;  // (before the null buffer)
   return copy_out(c, "pt_history_denoise", rgb_avg_host, 3, [&](const float** d) { return pt_ctx_history_denoise_device(c, samples, opt, d); });
+}
+
+// ---- ... and with the history's moments (ptdn::Form::Moments) -----------------------------------------------------------------
+// Everything pt_history_denoise_ex refuses with PT_HISTORY_MOMENTS but the null buffer, in its order (the flag word: the callers); the
+// job resolved.  No fold conditions: the form reads no noise planes.
+static int history_denoise_moments_refusal(const Ctx& g, const char* who, float samples, const PtDenoiseOptions* opt, ptdn::Job* j) {
+  if (history_admit(g, who)) return -1;
+  if (!g.d_feat || !g.feat_fresh) return pt_fail(kNoFeatures, who);
+  if (pt_history_check_samples(who, samples)) return -1;
+  if (pt_denoise_resolve(who, ptdn::Form::Moments, samples, 0, 0, opt, j)) return -1;
+  return history_current_moments(g, who);
+}
+// The flag word of pt_history_denoise_ex: PT_HISTORY_MOMENTS or nothing.
+static int history_denoise_flags(const char* who, uint32_t flags) {
+  if (flags & ~PT_HISTORY_MOMENTS) return pt_fail("%s: undefined flag bit(s) 0x%x (defined: PT_HISTORY_MOMENTS)", who, flags & ~PT_HISTORY_MOMENTS);
+  return 0;
+}
+int pt_ctx_history_denoise_ex_device(PtContext* c, float samples, const PtDenoiseOptions* opt, uint32_t flags, const float** rgb_dev) {
+  const char* who = "pt_history_denoise_ex";
+  if (need(c, who)) return -1;
+  Ctx& g = *c;
+  if (admit(g, who, kNotFailed) || history_denoise_flags(who, flags)) return -1;
+  if (!flags) return history_denoise_device(c, who, samples, opt, rgb_dev);
+  ptdn::Job j{};
+  if (history_denoise_moments_refusal(g, who, samples, opt, &j)) return -1;
+  if (!rgb_dev) return pt_fail("%s: null buffer", who);
+  HIP_OK(hipSetDevice(g.device));
+  if (ensure(g, g.d_denoise, pt_denoise_workspace_bytes((size_t)g.N))) return -1;  // the first denoise call of the context, of any kind
+  const int W = g.cam.resolution[0];
+  j.f = {W, g.N / W, g.d_image, reinterpret_cast<const float*>(g.d_feat), nullptr};
+  if (g.hist_current) {
+    j.div.C = reinterpret_cast<const ptdn::V4*>(history_plane(g, pthi::kKeptPlanes));
+    j.div.VC = reinterpret_cast<const ptdn::V4*>(history_var_plane(g, 1));
+  }
+  return pt_denoise_launch(g.stream, j, g.d_denoise, rgb_dev);
+}
+int pt_ctx_history_denoise_ex(PtContext* c, float samples, const PtDenoiseOptions* opt, uint32_t flags, float* rgb_avg_host) {
+  const char* who = "pt_history_denoise_ex";
+  if (need(c, who)) return -1;
+  if (admit(*c, who, kNotFailed) || history_denoise_flags(who, flags)) return -1;
+  ptdn::Job j{};
+  if (flags ? history_denoise_moments_refusal(*c, who, samples, opt, &j) : history_denoise_refusal(*c, who, samples, opt, &j)) return -1;  // (before the null buffer)
+  return copy_out(c, who, rgb_avg_host, 3, [&](const float** d) { return pt_ctx_history_denoise_ex_device(c, samples, opt, flags, d); });
 }
 
 int pt_ctx_history_resolve_device(PtContext* c, float samples, const float** rgb_dev) {
@@ -642,7 +704,7 @@ int pt_ctx_readback_history_variance(PtContext* c, float* kept_var, float* curre
   Ctx& g = *c;
   HIP_OK(hipSetDevice(g.device));
   const size_t plane = (size_t)g.N * sizeof(pthi::V4);
-  const bool kept = g.d_hist_var && g.hist_var_kept, current = g.d_hist_var && g.hist_var_current;
+  const bool kept = g.d_hist_var && g.hist_var_kept, current = g.d_hist_var && g.hist_var_current;  // (whichever kind they hold)
   if (kept_var && kept) HIP_OK(hipMemcpyAsync(kept_var, history_var_plane(g, 0), plane, hipMemcpyDeviceToHost, g.stream));
   if (current_var && current) HIP_OK(hipMemcpyAsync(current_var, history_var_plane(g, 1), plane, hipMemcpyDeviceToHost, g.stream));
   if (pt_ctx_sync(c)) return -1;
@@ -659,7 +721,8 @@ int pt_ctx_history_drop(PtContext* c) {
     HIP_OK(hipMemsetAsync(g.d_hist, 0, pt_history_state_bytes((size_t)g.N), g.stream));
     if (g.d_hist_var) HIP_OK(hipMemsetAsync(g.d_hist_var, 0, pt_history_variance_bytes((size_t)g.N), g.stream));
   }
-  g.hist_kept = g.hist_current = g.hist_var_kept = g.hist_var_current = false;
+  g.hist_kept = g.hist_current = false;
+  g.hist_var_kept = g.hist_var_current = 0;
   return 0;
 }
 

@@ -3,7 +3,7 @@
 // state.iterations iterations, write the PNG saveImage() would write.  Flags exist only because
 // the reference takes resolution, iteration count and depth from the scene file (scene.cpp:103-114).
 //
-//   pt_render SCENE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] [--orbit N [--device-tables] [--reproject [--history-cap C] [--denoise-history]]]
+//   pt_render SCENE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] [--orbit N [--device-tables] [--reproject [--history-cap C] [--denoise-history [--history-moments]]]]
 //                       [--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa]
 //                       [--preview N] [--convergence N | --reference FILE.pfm] [--clean-db X] [--features]
 //                       [--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]]
@@ -66,7 +66,9 @@
 // takes the --denoise-* options, sigma C's default being 8): a frame's iterations are rendered in groups of ceil(spp / 4) with
 // pt_noise_fold after each, the lookup and the capture carry the variance (pt_history_*_ex with PT_HISTORY_VARIANCE), and after the
 // resolve pt_history_denoise writes <base>.orbit<fff>.reprojected.denoised.png (.pfm); the history keeps the unfiltered blend.  Frame f renders iterations f * spp + 1 ..
-// (f + 1) * spp instead of 1 .. spp (printed once).  --history-cap C: PtHistoryOptions.cap (default 32).  Prints per frame
+// (f + 1) * spp instead of 1 .. spp (printed once).  --history-moments (with --denoise-history; --spp 1 is enough): the lookup and the
+// capture carry the history's moments instead (PT_HISTORY_MOMENTS), the filter is pt_history_denoise_ex with them, and a frame is one
+// pt_render call without folds; the same output names.  --history-cap C: PtHistoryOptions.cap (default 32).  Prints per frame
 // `history: frame f: <valid> of <pixels> pixels carried, mean weight <x>`.
 // Output name: PREFIX.<spp>samp.png, or with --stamp the reference's own
 // <FILE>.<UTC start time>.<spp>samp.png (main.cpp:99-102).
@@ -89,7 +91,7 @@
 int main(int argc, char** argv) {
   if (argc < 2) {
     std::printf("Usage: %s SCENEFILE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] "
-                "[--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa] [--orbit N [--device-tables] [--reproject [--history-cap C] [--denoise-history]]] [--preview N] "
+                "[--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa] [--orbit N [--device-tables] [--reproject [--history-cap C] [--denoise-history [--history-moments]]]] [--preview N] "
                 "[--convergence N | --reference FILE.pfm] [--clean-db X] [--features] "
                 "[--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]] [--denoise-guided] [--until-db X [--until-group G] [--adaptive F [--denoise-adaptive]]] "
                 "[--adaptive-threshold E [--adaptive-cap F] [--adaptive-min-pixels P] [--until-group G] [--denoise-adaptive]]\n", argv[0]);
@@ -103,6 +105,7 @@ int main(int argc, char** argv) {
   bool device_tables = false;                       // --device-tables
   bool reproject = false;                           // --reproject
   bool dn_history = false;                          // --denoise-history
+  bool hist_moments = false;                        // --history-moments
   float history_cap = 0.0f;                         // --history-cap C (0: the default)
   bool history_cap_given = false;
   bool until = false, until_group_given = false;
@@ -130,6 +133,7 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[i], "--device-tables")) device_tables = true;
     else if (!std::strcmp(argv[i], "--reproject")) reproject = true;
     else if (!std::strcmp(argv[i], "--denoise-history")) dn_history = true;  // the blend filtered with the variance the history carries
+    else if (!std::strcmp(argv[i], "--history-moments")) hist_moments = true;  // ... with the variance its moments give: no folds
     else if (!std::strcmp(argv[i], "--history-cap") && i + 1 < argc) {
       history_cap = (float)std::atof(argv[++i]);
       history_cap_given = true;
@@ -276,6 +280,10 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--denoise-history wants --orbit N --reproject (it filters the blend of the view with the reprojected history)\n");
     return 1;
   }
+  if (hist_moments && !dn_history) {
+    std::fprintf(stderr, "--history-moments wants --denoise-history (it chooses what the filter over the blend takes its variance from)\n");
+    return 1;
+  }
   if (!denoise && !guided && !dn_adaptive && !dn_history && (dn_opt.levels || dn_opt.keep_albedo || dn_opt.sigma_color != 0.0f || dn_opt.sigma_normal != 0.0f || dn_opt.sigma_position != 0.0f)) {
     std::fprintf(stderr, "--denoise-levels, --denoise-sigma and --denoise-keep-albedo want --denoise, --denoise-guided, --denoise-adaptive or --denoise-history\n");
     return 1;
@@ -356,7 +364,7 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--denoise-guided wants at least 2 iterations (--spp): a variance needs two groups\n");
     return 1;
   }
-  if (dn_history && iters < 2) {
+  if (dn_history && !hist_moments && iters < 2) {
     std::fprintf(stderr, "--denoise-history wants at least 2 iterations (--spp): a variance needs two groups per view\n");
     return 1;
   }
@@ -499,7 +507,7 @@ int main(int argc, char** argv) {
       const auto t0 = std::chrono::high_resolution_clock::now();
       const int iter_first = reproject ? f * iters + 1 : 1;
       bool render_failed = false;
-      if (dn_history) {  // the view's iterations in groups of ceil(spp / 4), a fold after each: the variance of the view's own samples
+      if (dn_history && !hist_moments) {  // the view's iterations in groups of ceil(spp / 4), a fold after each: the variance of the view's own samples
         for (int done = 0; done < iters && !render_failed; done += fold_group)
           render_failed = pt_render(iter_first + done, std::min(fold_group, iters - done)) || pt_noise_fold();
         render_failed = render_failed || pt_readback(scene->state.image.data());
@@ -523,9 +531,10 @@ int main(int argc, char** argv) {
       if (pfm && pt_save_pfm((frame + ".pfm").c_str(), scene->state.image.data(), W, H, (float)iters) == 0) std::printf("Saved %s.pfm.\n", frame.c_str());
       if (hdr && pt_save_hdr((frame + ".hdr").c_str(), scene->state.image.data(), W, H, (float)iters) == 0) std::printf("Saved %s.hdr.\n", frame.c_str());
       if (reproject) {  // the view's first hits, the history looked up from them, the blend written, the blend kept for the next view
-        const uint32_t hflags = dn_history ? PT_HISTORY_VARIANCE : 0u;  // 0: the plain calls
+        const uint32_t hflags = !dn_history ? 0u : hist_moments ? PT_HISTORY_MOMENTS : PT_HISTORY_VARIANCE;  // 0: the plain calls
         if (pt_render_features(1, 1) || (f > 0 && pt_history_reproject_ex(&hopt, hflags)) || pt_history_resolve((float)iters, carried.data()) ||
-            (dn_history && pt_history_denoise((float)iters, &dn_opt, filtered.data())) || pt_history_capture_ex((float)iters, hflags) ||
+            (dn_history && (hist_moments ? pt_history_denoise_ex((float)iters, &dn_opt, PT_HISTORY_MOMENTS, filtered.data())
+                                         : pt_history_denoise((float)iters, &dn_opt, filtered.data()))) || pt_history_capture_ex((float)iters, hflags) ||
             pt_readback_history(nullptr, current.data())) {
           std::fprintf(stderr, "HIP error (pt_history): %s\n", pt_last_error());
           return EXIT_FAILURE;

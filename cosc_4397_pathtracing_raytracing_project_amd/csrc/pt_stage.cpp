@@ -351,11 +351,10 @@ int pt_stage_history_reproject(int w, int rows, int row0, const PtCamera* kept_c
   return 0;
 }
 
-// ... with the variance side (pt_history_reproject_variance_host's arguments): C and VC of one launch
-int pt_stage_history_reproject_variance(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
+// ... with the variance or the moments side (pt_history_reproject_variance_host's arguments): C and VC of one launch
+static int stage_history_reproject_with(const char* who, bool moments, int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
                                         const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, const float* kept_var, float* current_plane,
                                         float* current_var) {
-  const char* who = "pt_stage_history_reproject_variance";
   if (need(default_context(), who)) return -1;
   Ctx& g = *default_context();
   pthi::Params P{};
@@ -374,12 +373,26 @@ int pt_stage_history_reproject_variance(int w, int rows, int row0, const PtCamer
     return -1;
   if (!P.keep_view_dependent && num_geoms > 0 && device_copy(sc, who, reject_geom, (size_t)num_geoms, &d_reject)) return -1;
   HIP_OK(hipMemset(d_cur, 0xff, 8 * n * sizeof(float)));  // a pixel nobody wrote shows as NaNs
-  if (pt_history_reproject_variance_launch(g.stream, pthi::make_view(*kept_cam, rows, row0), d_kept, d_feat, d_reject, num_geoms, P, d_cur, d_kvar, d_cur + 4 * n))
+  if ((moments ? pt_history_reproject_moments_launch : pt_history_reproject_variance_launch)(g.stream, pthi::make_view(*kept_cam, rows, row0), d_kept, d_feat,
+                                                                                            d_reject, num_geoms, P, d_cur, d_kvar, d_cur + 4 * n))
     return -1;
   HIP_OK(hipStreamSynchronize(g.stream));
   HIP_OK(hipMemcpy(current_plane, d_cur, 4 * n * sizeof(float), hipMemcpyDeviceToHost));
   HIP_OK(hipMemcpy(current_var, d_cur + 4 * n, 4 * n * sizeof(float), hipMemcpyDeviceToHost));
   return 0;
+}
+
+int pt_stage_history_reproject_variance(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
+                                        const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, const float* kept_var, float* current_plane,
+                                        float* current_var) {
+  return stage_history_reproject_with("pt_stage_history_reproject_variance", false, w, rows, row0, kept_cam, kept_planes, feature_planes, reject_geom, num_geoms, opt, kept_var,
+                                      current_plane, current_var);
+}
+int pt_stage_history_reproject_moments(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
+                                       const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, const float* kept_var, float* current_plane,
+                                       float* current_var) {
+  return stage_history_reproject_with("pt_stage_history_reproject_moments", true, w, rows, row0, kept_cam, kept_planes, feature_planes, reject_geom, num_geoms, opt, kept_var,
+                                      current_plane, current_var);
 }
 
 // The history filter's kernels on caller-supplied host arrays (pt_history_denoise_host's arguments); C and VC travel beside the frame
@@ -398,6 +411,24 @@ int pt_stage_history_denoise(int w, int rows, const float* rgb_sum, const float*
   if (current_plane && (device_copy(hist_sc, who, current_plane, 4 * n, &d_cur) || device_copy(hist_sc, who, current_var, 4 * n, &d_var))) return -1;
   j.div.C = reinterpret_cast<const ptdn::V4*>(d_cur), j.div.VC = reinterpret_cast<const ptdn::V4*>(d_var);
   return filter_stage_job(g, who, w, rows, rgb_sum, planes, noise_planes, rgb_avg, j);
+}
+
+// ... and the moments form's (pt_history_denoise_moments_host's arguments but its optional outputs)
+int pt_stage_history_denoise_moments(int w, int rows, const float* rgb_sum, const float* planes, float samples, const float* current_plane,
+                                     const float* current_var, const PtDenoiseOptions* opt, float* rgb_avg) {
+  const char* who = "pt_stage_history_denoise_moments";
+  if (need(default_context(), who)) return -1;
+  Ctx& g = *default_context();
+  if (rows >= 32768) return pt_fail("%s: a frame of %d x %d pixels is not supported", who, w, rows);
+  ptdn::Job j{};
+  if (pt_history_denoise_moments_check(who, w, rows, rgb_sum, planes, samples, current_plane, current_var, opt, rgb_avg != nullptr, &j)) return -1;
+  Scratch hist_sc;  // (filter_stage synchronises before it returns)
+  float *d_cur = nullptr, *d_var = nullptr;
+  HIP_OK(hipSetDevice(g.device));
+  const size_t n = (size_t)w * rows;
+  if (current_plane && (device_copy(hist_sc, who, current_plane, 4 * n, &d_cur) || device_copy(hist_sc, who, current_var, 4 * n, &d_var))) return -1;
+  j.div.C = reinterpret_cast<const ptdn::V4*>(d_cur), j.div.VC = reinterpret_cast<const ptdn::V4*>(d_var);
+  return filter_stage_job(g, who, w, rows, rgb_sum, planes, nullptr, rgb_avg, j);
 }
 
 // The selection's kernels on caller-supplied host arrays (pt_adaptive_select_host's arguments)

@@ -847,8 +847,8 @@ int pt_history_blend_host(int pixels, const float* rgb_sum, float samples, const
  * 4.525e-4, the filtered blend 1.396e-4 (0.3086 of it), pt_denoise_guided on the last view's own 4 spp 4.539e-4 (the filtered blend is
  * 0.3076 of it): history plus filter beats either alone.  The carried variance reads high (sum of VK 15.39 against the blend's squared
  * error 7.037 over the last view): recorded, not bounded.  One scene, one orbit: no claim beyond it.
- * Out of scope: feeding the FILTERED image back into the history (K keeps the unfiltered blend); pt_group_*; a view with fewer than 2
- * folds (1 spp per frame); a spatial variance fallback for disoccluded pixels (they start again from the view's own estimate). */
+ * Out of scope: feeding the FILTERED image back into the history (K keeps the unfiltered blend); pt_group_*.  A view with fewer than 2
+ * folds (1 spp per frame) and a spatial estimate for disoccluded pixels: PT_HISTORY_MOMENTS, "moments with the history" below. */
 #define PT_HISTORY_VARIANCE 1u
 int pt_history_capture_ex(float samples, uint32_t flags);
 int pt_history_reproject_ex(const PtHistoryOptions* opt, uint32_t flags);
@@ -866,6 +866,74 @@ int pt_history_reproject_variance_host(int w, int rows, int row0, const PtCamera
 /* pt_denoise_guided_host's arrays, samples, and C, VC (both NULL: absent). */
 int pt_history_denoise_host(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, int groups, int64_t iters, float samples,
                             const float* current_plane, const float* current_var, const PtDenoiseOptions* opt, float* rgb_avg);
+
+/* ---- moments with the history: a variance from the differences BETWEEN views, and a spatial estimate for fresh pixels (SVGF's two
+ * devices).  PT_HISTORY_VARIANCE takes the new samples' variance from pt_noise_fold, which needs two folded groups per view; a
+ * moving camera at 1 spp per view has none.  With PT_HISTORY_MOMENTS the history carries a second moment beside the colour instead,
+ * and pixels whose history is too short take their variance from their neighbourhood.  A third kind of history state beside "none"
+ * and the variance; opt-in like it: with flags == 0 and with PT_HISTORY_VARIANCE every call keeps its results, memory, launches and
+ * refusals, and a renderer that never sets the flag allocates and launches nothing for it.  Specified like the rest: float32
+ * throughout, every operation a separate IEEE operation in the order written, no FMA contraction, correctly rounded division,
+ * denormals kept; one implementation for kernels and host loops; the same result in all three PT_ARITH_* builds, host and device.
+ * State: the moments reuse the 32-byte buffer of the variance kind (allocated by the first capture with either flag), and the
+ * renderer remembers which kind each plane holds:
+ *   VK = {m2.xyz, r}: m2 the per-channel second moment of the views' mean colours that formed K0.xyz, weighted as the colour was;
+ *        r the sum of the squared weights of those views (1 for one view, 1/L for L equal views); aligned with K
+ *   VC = {m2h.xyz, rh}: VK resampled to the current camera, aligned with C
+ * Lifetime: that of VK / VC above.  pt_readback_history_variance returns the planes whichever kind they hold.
+ *   capture with the flag:  K exactly as without; no fold is needed and none is read.  Per component k, with Th = C.w and
+ *            m2h = rh = Th = +0 when C is absent:
+ *            x_k = S_k / samples;  dn = samples + Th;  wn = samples / dn;  wh = Th / dn
+ *            m2b_k = wn * (x_k * x_k) + wh * m2h_k;  rb = wn * wn + (wh * wh) * rh;  VK = {m2b.xyz, rb}
+ *   reproject with the flag:  C exactly as without, the same bits.  Step 6 accumulates vacc over FOUR components x, y, z, w:
+ *            vacc_k = vacc_k + b * VK(q).k after tacc, for a tap that passed every test;  step 7: VC.k = vacc_k / wsum for the four.
+ *            A rejected pixel gets VC = 0.  Capping Th touches neither m2h nor rh.  (The lookup with PT_HISTORY_VARIANCE is untouched:
+ *            three components, w = +0.)
+ *   pt_history_denoise_ex(samples, opt, flags, rgb_avg_host): flags == 0 is pt_history_denoise, with its refusals under the new name;
+ *            PT_HISTORY_VARIANCE is an undefined bit here; PT_HISTORY_MOMENTS selects the moments form, which reads no noise planes and
+ *            has no fold conditions:
+ *     prepare:  n, a, p and the hit flag as pt_denoise;  cb_k = blend(S_k, samples, C.k, C.w);  m2b, rb as in the capture above;
+ *            d_k = m2b_k - cb_k * cb_k;  d_k = d_k > 0 ? d_k : 0
+ *            rb <= PT_HISTORY_MOMENTS_R_MAX:  f = rb / (1.0f - rb);  v_k = d_k * f;  unless keep_albedo
+ *                 v_k = a_k > 0 ? v_k / (a_k * a_k) : v_k;  var_raw = (v_x + v_y) + v_z
+ *            otherwise (C absent included):  var_raw = -1.0f, the mark for the spatial estimate
+ *            The colour c is cb demodulated as in every form.  d r / (1 - r) is the unbiased variance of the weighted mean: m2 - c^2
+ *            underestimates the per-view variance by the factor (1 - r), and the blend's variance is r times that.
+ *     spatial estimate, a launch of its own between prepare and the variance prefilter, for the marked pixels (var_raw == -1.0f)
+ *            only, on the DEMODULATED colour c that prepare wrote:  wsum = s1 = s2 = 0;  for j = -3 .. 3 (rows, outer), i = -3 .. 3,
+ *            q = (x + i, y + j), skipped when outside the W x R rectangle or hit(q) != hit(x, y):
+ *            dn, dp as pt_denoise;  e = dn * inv_n + dp * inv_p;  w = exp32(-e)      (no colour term, no H)
+ *            wsum = wsum + w;  s1_k = s1_k + w * c_k(q);  s2_k = s2_k + w * (c_k(q) * c_k(q))
+ *            then  mean_k = s1_k / wsum;  u_k = s2_k / wsum;  d_k = u_k - mean_k * mean_k;  d_k = d_k > 0 ? d_k : 0;
+ *            var_raw = (d_x + d_y) + d_z, written to the centre's own spare word only (the centre tap passes with w = 1, so
+ *            wsum >= 1; no neighbour's var_raw is read, so the update in place has no hazard).
+ *     then the guided form's variance prefilter (the one without counts), levels and finish, unchanged: the same kernels.
+ *            sigma_color == 0 means 8.0.  The workspace is the shared 80 bytes per pixel.
+ * Refusals, each with a message that names the function, nothing allocated or launched.  capture_ex / reproject_ex: the check of
+ * the flag word keeps its place and now also refuses both bits together (the flags exclude each other).  After what
+ * pt_history_capture / _reproject refuse, with the moments flag: capture — C present but filled by a lookup of another kind;
+ * reproject — nothing captured with moments.  (Likewise the variance flag refuses a C or a K of the moments kind.)
+ * pt_history_denoise_ex with the moments flag, in this order: a failed context; an undefined flag bit; a striped or ragged tile; the
+ * adaptive state; no feature pass since the last clear or move; samples; levels, a sigma or keep_albedo as pt_denoise refuses them;
+ * C present with VC absent or of the variance kind; a null buffer.
+ * What it buys: README "Moments with the history" (tests/test_history_moments_sim.py on the CPU, tests/test_gpu_history_moments.py on
+ * an MI355X, the same digits).  One scene, one orbit: no claim beyond it.
+ * Out of scope: feeding the FILTERED image back into the history; pt_group_*; feeding the history into the noise estimate or
+ * adaptive sampling; a luminance-only variant; motion of anything but the camera. */
+#define PT_HISTORY_MOMENTS 2u
+#define PT_HISTORY_MOMENTS_R_MAX 0.3f /* four equal views or more (r = 1/4): the literature's history length 4 */
+int pt_history_denoise_ex(float samples, const PtDenoiseOptions* opt, uint32_t flags, float* rgb_avg_host); /* synchronises */
+/* The same arithmetic on the host (no GPU); the device results equal these bit for bit.  The capture's K is pt_history_capture_host's;
+ * this gives VK beside it from the SUM image and C, VC (both NULL: absent).  The lookup gives C — pt_history_reproject_host's, bit
+ * for bit — and VC in one pass. */
+int pt_history_capture_moments_host(int pixels, const float* rgb_sum, float samples, const float* current_plane, const float* current_var, float* kept_var);
+int pt_history_reproject_moments_host(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
+                                      const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, const float* kept_var, float* current_plane,
+                                      float* current_var);
+/* pt_denoise_host's arrays, samples, and C, VC (both NULL: absent).  var_raw (w*rows floats; after the spatial step) and mark (w*rows
+ * bytes: 1 where prepare marked the pixel) are optional outputs; with one of them rgb_avg may be NULL, and no level runs. */
+int pt_history_denoise_moments_host(int w, int rows, const float* rgb_sum, const float* planes, float samples, const float* current_plane,
+                                    const float* current_var, const PtDenoiseOptions* opt, float* rgb_avg, float* var_raw, uint8_t* mark);
 
 /* saveImage()'s per-pixel conversion (main.cpp:91-97 x mirror, image.cpp:26-30 clamp * 255 truncated) on the
  * device: pixel_count*3 bytes, row-major, x mirrored inside each row; the tile must consist of whole rows.
@@ -934,6 +1002,8 @@ int pt_ctx_history_reproject_ex(PtContext* c, const PtHistoryOptions* opt, uint3
 int pt_ctx_history_denoise(PtContext* c, float samples, const PtDenoiseOptions* opt, float* rgb_avg_host);
 int pt_ctx_history_denoise_device(PtContext* c, float samples, const PtDenoiseOptions* opt, const float** rgb_dev); /* as pt_ctx_denoise_device */
 int pt_ctx_readback_history_variance(PtContext* c, float* kept_var, float* current_var);
+int pt_ctx_history_denoise_ex(PtContext* c, float samples, const PtDenoiseOptions* opt, uint32_t flags, float* rgb_avg_host);
+int pt_ctx_history_denoise_ex_device(PtContext* c, float samples, const PtDenoiseOptions* opt, uint32_t flags, const float** rgb_dev); /* as pt_ctx_denoise_device */
 const float* pt_ctx_device_noise(PtContext* c); /* device pointer of plane 0; the planes are contiguous; NULL before the first fold */
 const float* pt_ctx_device_features(PtContext* c); /* device pointer of plane 0; the planes are contiguous; NULL before the first pt_ctx_render_features */
 const float* pt_ctx_device_image(PtContext* c); /* device pointer of the tile SUM image */
@@ -1119,6 +1189,13 @@ int pt_stage_history_reproject_variance(int w, int rows, int row0, const PtCamer
                                         float* current_var);
 int pt_stage_history_denoise(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, int groups, int64_t iters, float samples,
                              const float* current_plane, const float* current_var, const PtDenoiseOptions* opt, float* rgb_avg);
+/* The lookup with moments (pt_history_reproject_moments_host's arguments) and the moments form of the filter — prepare, the spatial
+ * estimate, prefilter, levels, finish — (pt_history_denoise_moments_host's arguments but its optional outputs; rows < 32768). */
+int pt_stage_history_reproject_moments(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
+                                       const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, const float* kept_var, float* current_plane,
+                                       float* current_var);
+int pt_stage_history_denoise_moments(int w, int rows, const float* rgb_sum, const float* planes, float samples, const float* current_plane,
+                                     const float* current_var, const PtDenoiseOptions* opt, float* rgb_avg);
 
 /* ---- image output (src/image.cpp:22-45, src/main.cpp:86-107) ------------- */
 /* rgb_sum: W*H*3 floats (raw orientation); writes <path> as 8-bit PNG of

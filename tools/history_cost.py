@@ -16,7 +16,16 @@ Then the variance side (PT_HISTORY_VARIANCE; profiles/history_variance_cost.log 
 cleared, a view is rendered in 4 groups of 1 with a fold each and captured with variance, the camera moves another step, the next view
 is rendered and folded the same way; per repetition pt_history_reproject_ex and pt_history_capture_ex with the flag and
 pt_history_denoise (device form) run between HIP events, and pt_denoise_guided (device form) on the same frame for scale.  The
-first part is untouched by this: its calls are the flags == 0 ones, to be compared with earlier logs."""
+first part is untouched by this: its calls are the flags == 0 ones, to be compared with earlier logs.
+
+Then the moments side (PT_HISTORY_MOMENTS; profiles/history_moments_cost.log holds a run with all three parts, of this library and of
+the parent revision's through PT_AMD_LIB), on cornell as above — at 16 : 9 over half of its camera rays miss, and a miss is marked
+at every view — and on cornell with the eye inside the box, where every ray hits: the context is cleared and a view of 1 iteration is rendered; per repetition
+pt_history_denoise_ex (device form) runs with C absent — the first view: every pixel is marked and k_denoise_var_spatial walks 49 taps
+for each — and pt_history_capture_ex with the flag.  Then an orbit of 8 views 2 pi / 120 apart is run through lookup, filter and
+capture, and at its last view — a steady view — pt_history_reproject_ex and pt_history_denoise_ex are timed per repetition, beside
+pt_denoise (device form) on the same frame for scale; nothing is captured between the repetitions, so each looks the same history
+up and marks the same pixels, whose share is printed with the times.  pt_history_capture_ex is timed afterwards, on its own."""
 import argparse
 import ctypes as C
 import os
@@ -87,7 +96,9 @@ say("# the rates are bytes by specification over time, not memory traffic: where
 say("# this chip), the caches served part of it - the history's planes, the feature planes, S and the output are about 280 MB at this size,")
 say("# the Infinity Cache holds 256 MiB, and the gather's four taps share lines between neighbouring pixels")
 tmp = tempfile.mkdtemp()
-for name, text in (("cornell (7 primitives)", scenes.cornell_scene_text(res=(W, H))), ("stress 22x22x21 (10170 primitives)", scenes.stress_scene_text())):
+# (the third: the eye inside the box, so that every camera ray hits — a miss carries no history and is marked at every view)
+for name, text in (("cornell (7 primitives)", scenes.cornell_scene_text(res=(W, H))), ("stress 22x22x21 (10170 primitives)", scenes.stress_scene_text()),
+                   ("cornell from inside the box", scenes.cornell_scene_text(res=(W, H), eye=(0.0, 5.0, 4.5)))):
     path = scenes.write_scene(text, os.path.join(tmp, "s.txt"))
     scene = capi.Scene(path, res=(W, H))
     opt = capi.make_options(arith="fast")
@@ -193,6 +204,73 @@ for name, text in (("cornell (7 primitives)", scenes.cornell_scene_text(res=(W, 
         line("pt_denoise_guided (device)", times["guided"])
         extra = statistics.median(times["denoise"]) - statistics.median(times["guided"])
         say(f"the history form's prepare reads 12 + 48 + 32 + 16 + 16 B and writes 64 B per pixel (the guided form's: 12 + 48 + 32 in); the two filters differ by {extra:+.4f} ms")
+        history_denoise_median = statistics.median(times["denoise"])
+        # ---- the moments side: the same context, cleared; views of 1 iteration, no fold
+        if not hasattr(L, "pt_ctx_history_denoise_ex_device"):
+            say("### this build of the library has no PT_HISTORY_MOMENTS")
+            continue
+        if not name.startswith("cornell"):
+            continue
+        MOM = capi.HISTORY_MOMENTS
+        capi._check(L.pt_ctx_history_drop(ctx))
+        capi._check(L.pt_ctx_clear(ctx))
+        capi._check(L.pt_ctx_render(ctx, 1, 1))
+        capi._check(L.pt_ctx_render_features(ctx, 1, 1))
+
+        def timed(calls):
+            """calls: (name, function) run back to back per repetition between HIP events; the first repetition is dropped."""
+            ev = events(len(calls) + 1)
+            t = {k: [] for k, _ in calls}
+            for rep in range(args.reps):
+                for k, (_, fn) in enumerate(calls):
+                    hip_ok(hip.hipEventRecord(ev[k], stream))
+                    capi._check(fn())
+                hip_ok(hip.hipEventRecord(ev[len(calls)], stream))
+                hip_ok(hip.hipEventSynchronize(ev[len(calls)]))
+                if rep:
+                    for k, (key, _) in enumerate(calls):
+                        t[key].append(elapsed(ev[k], ev[k + 1]))
+            for e in ev:
+                hip.hipEventDestroy(e)
+            return t
+
+        def marked_share():
+            """The share of pixels pt_history_denoise_ex's prepare marks at this view: rb > PT_HISTORY_MOMENTS_R_MAX, from the readbacks."""
+            vc, c4 = np.empty((W * H, 4), np.float32), np.empty((W * H, 4), np.float32)
+            capi._check(L.pt_ctx_readback_history_variance(ctx, None, capi._f(vc)))
+            capi._check(L.pt_ctx_readback_history(ctx, None, capi._f(c4)))
+            dn = np.float32(1) + c4[:, 3]
+            wn, wh = np.float32(1) / dn, c4[:, 3] / dn
+            rb = wn * wn + (wh * wh) * vc[:, 3]
+            return float((~(rb <= capi.HISTORY_MOMENTS_R_MAX)).mean())
+
+        one = C.c_float(1.0)
+        t = timed([("denoise", lambda: L.pt_ctx_history_denoise_ex_device(ctx, one, None, MOM, C.byref(dev))),
+                   ("capture", lambda: L.pt_ctx_history_capture_ex(ctx, one, MOM))])
+        say("### with PT_HISTORY_MOMENTS, the first view (C absent): every pixel is marked for the spatial estimate")
+        line("pt_history_denoise_ex (dev.)", t["denoise"])
+        line("pt_history_capture_ex", t["capture"], 12 + 48 + 48 + 16)
+        for f in range(1, 8):
+            cam = scene.orbit(np.float32(2 * np.pi / 120), 0.0, 0.0)
+            capi._check(L.pt_ctx_set_camera(ctx, C.byref(cam)))
+            capi._check(L.pt_ctx_render(ctx, f + 1, 1))
+            capi._check(L.pt_ctx_render_features(ctx, 1, 1))
+            capi._check(L.pt_ctx_history_reproject_ex(ctx, C.byref(hopt), MOM))
+            if f < 7:
+                capi._check(L.pt_ctx_history_capture_ex(ctx, one, MOM))
+        share = marked_share()
+        t = timed([("reproject", lambda: L.pt_ctx_history_reproject_ex(ctx, C.byref(hopt), MOM)),
+                   ("denoise", lambda: L.pt_ctx_history_denoise_ex_device(ctx, one, None, MOM, C.byref(dev))),
+                   ("plain", lambda: L.pt_ctx_denoise_device(ctx, one, None, C.byref(dev)))])
+        assert marked_share() == share  # no capture between the repetitions: every one looks the same history up and marks the same pixels
+        t.update(timed([("capture", lambda: L.pt_ctx_history_capture_ex(ctx, one, MOM))]))  # (the same K and VK every time: C stays)
+        say(f"### with PT_HISTORY_MOMENTS, a steady view (the 8th of an orbit, 1 iteration each): {100 * share:.3f} % of the pixels marked")
+        line("pt_history_reproject_ex", t["reproject"], 48 + 16 + 16 + 4 * 64)
+        line("pt_history_capture_ex", t["capture"], 12 + 48 + 16 + 48 + 16 + 16)
+        line("pt_history_denoise_ex (dev.)", t["denoise"])
+        line("pt_denoise (device)", t["plain"])
+        say(f"the steady-view filter against pt_history_denoise above: {statistics.median(t['denoise']) - history_denoise_median:+.4f} ms "
+            f"(one launch more, k_denoise_var_spatial, which leaves on a ballot in every wave without a marked pixel; no noise planes read)")
     finally:
         L.pt_ctx_destroy(ctx)
 out.close()
