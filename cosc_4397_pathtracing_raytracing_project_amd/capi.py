@@ -140,6 +140,8 @@ def lib() -> C.CDLL:
     L.pt_build_grid.argtypes = [C.POINTER(PtGeom), C.c_int, C.c_int, C.POINTER(PtGridInfo), C.POINTER(C.c_uint32), C.POINTER(PtGridRecord)]
     if hasattr(L, "pt_selfcheck_ieee"):
         L.pt_selfcheck_ieee.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
+    if hasattr(L, "pt_selfcheck_fast_math"):
+        L.pt_selfcheck_fast_math.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_double)]
     if hasattr(L, "pt_traversal_boxes"):  # absent from older A/B builds of the library (tools/build_rev.sh)
         L.pt_traversal_boxes.argtypes = [C.POINTER(PtGeom), C.c_int, _fp, _fp]
     if hasattr(L, "pt_center_half_box"):
@@ -486,6 +488,18 @@ def selfcheck_ieee(kind: int, first: int, count: int, seed: int = 0, arith: str 
     n = C.c_uint64(0)
     _check(lib().pt_selfcheck_ieee(ARITH[arith], kind, first, count, seed, C.byref(n)))
     return int(n.value)
+
+
+FAST_MATH_KINDS = ("rcp", "sqrt", "rsq", "sin_rev", "cos_rev", "sin_lobe", "cos_lobe", "sin_rev_ulp", "cos_rev_ulp")
+
+
+def selfcheck_fast_math(kind, first: int, count: int, arith: str = "fast") -> float:
+    """The largest error of one of a mode's scalar primitives against double precision on the GPU over `count` operands from `first`
+    (pt_selfcheck_fast_math; kind: a name of FAST_MATH_KINDS or its number): ulp for rcp / sqrt / rsq / *_ulp, absolute otherwise."""
+    k = FAST_MATH_KINDS.index(kind) if isinstance(kind, str) else int(kind)
+    e = C.c_double(0.0)
+    _check(lib().pt_selfcheck_fast_math(ARITH[arith], k, int(first), int(count), C.byref(e)))
+    return float(e.value)
 
 
 def selfcheck_camera_math(kind: int, count: int, seed: int = 0) -> int:

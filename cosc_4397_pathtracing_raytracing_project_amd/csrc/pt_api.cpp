@@ -657,6 +657,24 @@ int pt_selfcheck_ieee(int arith, int kind, uint64_t first, uint64_t count, uint3
   return 0;
 }
 
+int pt_selfcheck_fast_math(int arith, int kind, uint64_t first, uint64_t count, double* max_err) {
+  const ptk::KernelApi* k = ptk::api_for(arith);
+  if (!k || kind < 0 || kind > 8 || !max_err) return pt_fail("pt_selfcheck_fast_math: bad argument");
+  unsigned long long* d = nullptr;
+  HIP_OK(hipMalloc(&d, sizeof(*d)));
+  hipError_t e = hipMemset(d, 0, sizeof(*d));
+  if (e == hipSuccess) {
+    k->fast_math_check(nullptr, kind, first, count, d);
+    e = hipGetLastError();
+  }
+  unsigned long long h = 0;
+  if (e == hipSuccess) e = hipMemcpy(&h, d, sizeof(h), hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  if (e != hipSuccess) return pt_fail("pt_selfcheck_fast_math: %s", hipGetErrorString(e));
+  std::memcpy(max_err, &h, sizeof(h));  // the bits of a non-negative double
+  return 0;
+}
+
 // ---- scene -----------------------------------------------------------------
 struct PtScene {
   pt::Scene scene;

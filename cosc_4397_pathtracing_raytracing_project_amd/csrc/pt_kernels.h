@@ -200,6 +200,9 @@ struct KernelApi {
   void (*paths_gather)(hipStream_t s, int grid, const SceneTables& sc, const BatchInfo& b, const ptd::Queues& qs, int32_t* cnt, ptd::PathBuf in,
                        ptd::RetireBuf ret, const PrevGather& prev);
   void (*collect_stream_planes)(hipStream_t s, const BatchInfo& b, const ptd::Queues& qs, ptd::RetireBuf ret, const ptd::Word4* plane0, float* image_rgb);
+  // Measurement of the mode's own scalar primitives (rcp_, sqrt_, normalize's 1 / sqrt, the sampling's sin / cos) against double precision
+  // on `count` operands starting at `first` (pt_fast_math_check.inc): *worst = max(*worst, the largest error), as the bits of a double.
+  void (*fast_math_check)(hipStream_t s, int kind, unsigned long long first, unsigned long long count, unsigned long long* worst);
 };
 const KernelApi* api_exact();
 const KernelApi* api_fma();

@@ -2377,7 +2377,7 @@ const KernelApi kApi = {
     launch_generate, launch_primary, launch_intersect, launch_shade, launch_collect, launch_count_stats,
     launch_preview, launch_save_u8, launch_shade_stage, lds_table_limit, resident_blocks_per_cu, launch_ieee_check, launch_paths,
     launch_collect_conv, launch_features, kFast ? 1 : 0, launch_intersect_grid, launch_collect_stream, launch_paths_gather,
-    launch_collect_stream_planes};
+    launch_collect_stream_planes, launch_fast_math_check};
 
 }  // namespace
 }  // namespace PT_NS

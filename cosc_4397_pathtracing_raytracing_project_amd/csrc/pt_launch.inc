@@ -219,6 +219,7 @@ void launch_collect_conv(hipStream_t s, const BatchInfo& b, const ptd::Queues& q
 }
 
 #include "pt_ieee_check.inc"
+#include "pt_fast_math_check.inc"
 
 void launch_count_stats(hipStream_t s, const ptd::Queues& qs, int32_t* cnt, int depth_count,
                         unsigned long long* stats) {

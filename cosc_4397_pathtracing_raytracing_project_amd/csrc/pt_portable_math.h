@@ -131,9 +131,18 @@ PT_HD float acosf32(float x) {
 // f = u - k/4 (one FMA, exact), |f| <= 1/8; r = 2 pi f is formed as a head + tail product (float(2 pi) and its remainder,
 // the head product's rounding recovered with an FMA), rounded once, and the tail of that sum corrects the results to first
 // order.  Same polynomials as sincos_r.  Measured against double-precision sin / cos over all 2^24 + 1 arguments i / 2^24
-// and 10^7 random ones (tests/test_portable_math.py): <= 1.5 ulp, i.e. inside what CUDA documents for the sinf / cosf
+// and 10^7 random ones (tests/test_portable_math.py): <= 1.5 ulp; over every value a draw can return (minstd states 1 .. 2^31 - 2,
+// host and device): 1.56 (sin), 1.57 (cos), i.e. inside what CUDA documents for the sinf / cosf
 // the reference itself runs on (2 ulp) and tighter than evaluating sinf on a 2 pi u that was rounded to float first.
+// The head + tail arithmetic below is only right as SEPARATE operations: the fma build compiles its kernels with contraction on,
+// and the compiler then formed r as fma(f, TWO_PI_HI, rl) — the EXACT head product plus a tail that already holds what the rounded
+// head product lost — so that the argument carried that rounding error twice: 1.97 ulp over the values a draw can return instead
+// of the 1.56 of the sequence as written (found by pt_selfcheck_fast_math, tests/test_gpu_fast_math_blocks.py).  The pragma pins
+// the sequence in every build.
 PT_HD void sincos_rev(float u, float* s_out, float* c_out) {
+#if defined(__HIPCC__)  // (the host builds of this header compile without contraction: -ffp-contract=off)
+#pragma clang fp contract(off)
+#endif
   const float TWO_PI_HI = 6.2831854820251465f;   // float(2 pi)
   const float TWO_PI_LO = -1.7484555e-07f;       // 2 pi - float(2 pi)
   const float k = __builtin_rintf(4.0f * u);

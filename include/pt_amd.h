@@ -394,6 +394,16 @@ const char* pt_last_error(void);
  * `count` bit patterns starting at `first` (2^32 patterns = every float); kind 3 a/b, 4 the shared-reciprocal forms over
  * `count` pseudo-random operand sets derived from `seed` and the set's index first + i.  `arith` selects the kernel build. */
 int pt_selfcheck_ieee(int arith, int kind, uint64_t first, uint64_t count, uint32_t seed, uint64_t* mismatches);
+/* Device measurement of the scalar primitives a mode's kernels are built from, against double precision on the GPU
+ * (csrc/pt_fast_math_check.inc): *max_err = the largest error over `count` operands starting at `first`.
+ * kind 0 the reciprocal, 1 the square root, 2 normalize()'s 1 / sqrt(x): x = the float with the bit pattern first + i, error in ulp
+ * of the double result (zeros, subnormals, infinities, NaNs and results outside the normal range are passed over; 1, 2: x > 0);
+ * kind 3 sin(2 pi u), 4 cos(2 pi u) of the direction sampling: u = the draw of the minstd state first + i (1 .. 2^31 - 2 covers every
+ * value a draw can return), absolute error; 5, 6 sin and cos of the specular lobe's angle roughness u pi / 2 for roughness 1, 0.7,
+ * 0.5 and 0.05, absolute; 7, 8 as 3, 4 but in ulp over the values above 1e-3 in magnitude.
+ * fast: v_rcp_f32, v_sqrt_f32, v_rsq_f32, v_sin_f32 / v_cos_f32; fma: the IEEE sequences and ptmath::sincos_rev; exact: the IEEE
+ * sequences and ptmath::sin_r / cos_r.  A NaN result reads as an infinite error. */
+int pt_selfcheck_fast_math(int arith, int kind, uint64_t first, uint64_t count, double* max_err);
 /* ---- convergence metric (PtOptions.convergence != 0).  For a tile pixel p after iteration i, with S the running SUM image and R
  * the reference frame (averaged radiance), computePSNR's terms (pathtrace.cu:184-201) in float32: cur = S[p] / float(i) per
  * component (correctly rounded), d = cur - R[p], term = d.x*d.x + d.y*d.y + d.z*d.z left to right without FMA contraction in

@@ -14,6 +14,12 @@ and the portable sinf / cosf — two equally valid evaluations of the reference'
 pixels (stress_big 160x90 at 8 spp: 0.39 %).  For those scenes the bound is therefore 0.2 % + 3 x that noise floor,
 the floor being measured in the test itself (oracle PORTABLE vs oracle LIBM, CPU only); (1) and (3) stay absolute.
 
+What this tolerance does NOT have to carry alone: radiance here is a product of per-material constants, so an image moves only
+where an error changes which object the next ray hits.  Per sample and per ray, fma and fast are held against float64 by
+tests/test_gpu_shade_modes.py (decisions exact, new direction / origin / colour bounded in units of the oracle's own rounding) and
+tests/test_gpu_primitive_modes.py (hit / miss, material and cube normal exact on clear rays, t / point / sphere normal bounded per
+geom), and their scalar building blocks by tests/test_gpu_fast_math_blocks.py.
+
 Primary rays are traced with the reference's exact arithmetic in every mode (pt_kernels.hip, namespace ex): they are the
 same in every iteration of a pixel, so a tie broken differently there (the diagonals of a square cornell frame look
 exactly along the box's corner edges) would not average out.
