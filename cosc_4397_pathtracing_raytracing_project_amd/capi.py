@@ -8,6 +8,7 @@ called, an exception is raised.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Optional, Sequence, Tuple
 
@@ -91,6 +92,12 @@ class PtHistoryOptions(C.Structure):
     """Options of the reprojected sample history (include/pt_amd.h); 0 in a field = its default (cap 32, normal dot 0.9, plane
     tolerance 0.02, reflective geoms carry nothing); a negative min_normal_dot / plane_tol switches that test off."""
     _fields_ = [("cap", C.c_float), ("min_normal_dot", C.c_float), ("plane_tol", C.c_float), ("keep_view_dependent", C.c_int32)]
+
+
+class PtHistoryRoundOptions(C.Structure):
+    """Options of the history round (include/pt_amd.h: pt_history_round); 0 in a field = its default (min_history 4 samples,
+    max_fraction 1)."""
+    _fields_ = [("min_history", C.c_float), ("max_fraction", C.c_float)]
 
 
 class PtSetupTimes(C.Structure):
@@ -368,6 +375,22 @@ def lib() -> C.CDLL:
         L.pt_stage_history_reproject_moments.argtypes = _reproject_var
         L.pt_history_denoise_moments_host.argtypes = _mdn + [_fp, _fp, _u8p]
         L.pt_stage_history_denoise_moments.argtypes = _mdn + [_fp]
+    if hasattr(L, "pt_history_round"):  # absent from older A/B builds of the library (tools/build_rev.sh)
+        _hro, _dno = C.POINTER(PtHistoryRoundOptions), C.POINTER(PtDenoiseOptions)
+        _select = [C.c_int, C.c_int, _fp, _fp, _u8p, C.c_int, _hro, _ip, _ip, _ip]
+        _merge = [C.c_int, _fp, _fp, _ip, C.c_int, _fp, C.c_int]
+        L.pt_history_round.argtypes = [C.c_int, C.c_int, _hro, _ip, _ip]
+        L.pt_ctx_history_round.argtypes = [C.c_void_p, C.c_int, C.c_int, _hro, _ip, _ip]
+        L.pt_readback_history_extra.argtypes = [_fp]
+        L.pt_ctx_readback_history_extra.argtypes = [C.c_void_p, _fp]
+        L.pt_history_select_host.argtypes = _select
+        L.pt_stage_history_select.argtypes = _select
+        L.pt_history_merge_host.argtypes = _merge
+        L.pt_stage_history_merge.argtypes = _merge
+        L.pt_history_blend_counted_host.argtypes = [C.c_int, _fp, C.c_float, _fp, _fp, _fp]
+        L.pt_history_capture_counted_host.argtypes = [C.c_int, _fp, _fp, _fp, C.c_float, _fp, _fp]
+        L.pt_history_capture_moments_counted_host.argtypes = [C.c_int, _fp, C.c_float, _fp, _fp, _fp, _fp]
+        L.pt_history_denoise_moments_counted_host.argtypes = [C.c_int, C.c_int, _fp, _fp, C.c_float, _fp, _fp, _fp, _dno, _fp, _fp, _u8p]
     _lib = L
     return L
 
@@ -800,6 +823,141 @@ def stage_history_denoise_moments(rgb_sum, planes, w: int, rows: int, samples: f
                    None if v is None else _f(v), **opts)
 
 
+# ---- the history round: extra samples for the pixels whose history is short (include/pt_amd.h: pt_history_round) ----
+HISTORY_ROUND_MIN_HISTORY = np.float32(4.0)  # PT_HISTORY_ROUND_MIN_HISTORY
+
+
+def history_round_options(min_history: float = 0.0, max_fraction: float = 0.0) -> PtHistoryRoundOptions:
+    """PtHistoryRoundOptions; 0 = the default of a field."""
+    return PtHistoryRoundOptions(float(min_history), float(max_fraction))
+
+
+def emitter_geoms(scene: "Scene") -> np.ndarray:
+    """emitter_geom of pt_history_round for a scene: uint8 [num_geoms], 1 where the geom's material emits."""
+    geoms, mats = scene.geoms(), scene.materials()
+    return np.array([1 if mats[g.materialid].emittance > 0 else 0 for g in geoms], np.uint8)
+
+
+def history_list_capacity(max_fraction: float, n: int) -> int:
+    """cap of pt_history_round: clamp(ceil((double)(float)max_fraction * n), 1, n); 0 = the default 1."""
+    f = float(np.float32(max_fraction)) or 1.0
+    return int(min(n, max(1, math.ceil(f * n))))
+
+
+def _history_select(call, planes, w: int, rows: int, current, emitter, min_history: float, max_fraction: float):
+    n = w * rows
+    p = np.ascontiguousarray(planes, np.float32).reshape(-1)
+    c = None if current is None else np.ascontiguousarray(current, np.float32).reshape(-1)
+    e = np.ascontiguousarray(emitter, np.uint8).reshape(-1)
+    if p.size != 4 * FEATURE_PLANES * n or (c is not None and c.size != 4 * n):
+        raise PtError(f"history_select: {p.size} plane floats for a tile of {w}x{rows}")
+    opt = history_round_options(min_history, max_fraction)
+    cap = history_list_capacity(max_fraction, n) if 0 <= max_fraction <= 1 and math.isfinite(max_fraction) else 1  # (a refused option: the call says so)
+    lst = np.full(cap, -1, np.int32)
+    fresh, m = C.c_int32(-1), C.c_int32(-1)
+    _check(call(int(w), int(rows), _f(p), None if c is None else _f(c), e.ctypes.data_as(C.POINTER(C.c_uint8)) if e.size else None, int(e.size), C.byref(opt),
+                _i(lst), C.byref(fresh), C.byref(m)))
+    return lst, int(fresh.value), int(m.value)
+
+
+def history_select_host(planes, w: int, rows: int, current=None, emitter=(), min_history: float = 0.0, max_fraction: float = 0.0):
+    """The history round's key and selection on the host (pt_history_select_host; no GPU): the feature SUM planes
+    [PT_FEATURE_PLANES, w*rows, 4], the current plane [w*rows, 4] (None: absent) and emitter_geom in; (list [cap] int32 with the first
+    m entries written, fresh, m) out."""
+    return _history_select(lib().pt_history_select_host, planes, w, rows, current, emitter, min_history, max_fraction)
+
+
+def stage_history_select(planes, w: int, rows: int, current=None, emitter=(), min_history: float = 0.0, max_fraction: float = 0.0):
+    """history_select_host's arguments through the device kernels (pt_stage_history_select; a renderer must be live); the entries
+    behind m are -1."""
+    return _history_select(lib().pt_stage_history_select, planes, w, rows, current, emitter, min_history, max_fraction)
+
+
+def _history_merge(call, rgb_sum, extra, lst, group_sum, group_iters: int):
+    s = np.array(rgb_sum, np.float32).reshape(-1)
+    e = np.array(extra, np.float32).reshape(-1)
+    l = np.ascontiguousarray(lst, np.int32).reshape(-1)
+    b = np.ascontiguousarray(group_sum, np.float32).reshape(-1)
+    if s.size != 3 * e.size or b.size != 3 * l.size:
+        raise PtError(f"history_merge: {s.size} image, {e.size} extra, {b.size} group floats for a list of {l.size}")
+    _check(call(int(e.size), _f(s), _f(e), _i(l), int(l.size), _f(b), int(group_iters)))
+    return s.reshape(-1, 3), e
+
+
+def history_merge_host(rgb_sum, extra, lst, group_sum, group_iters: int):
+    """The history round's merge on the host (pt_history_merge_host; no GPU): copies of the SUM image [n, 3] and the extra plane [n]
+    with the group sum [m, 3] of group_iters iterations joined at the listed pixels: (rgb_sum, extra)."""
+    return _history_merge(lib().pt_history_merge_host, rgb_sum, extra, lst, group_sum, group_iters)
+
+
+def stage_history_merge(rgb_sum, extra, lst, group_sum, group_iters: int):
+    """history_merge_host's arguments through the device kernel (pt_stage_history_merge; a renderer must be live)."""
+    return _history_merge(lib().pt_stage_history_merge, rgb_sum, extra, lst, group_sum, group_iters)
+
+
+def _extra(extra, n: int) -> np.ndarray:
+    e = np.ascontiguousarray(extra, np.float32).reshape(-1)
+    if e.size != n:
+        raise PtError(f"history: {e.size} extra floats for {n} pixels")
+    return e
+
+
+def history_blend_counted_host(rgb_sum, samples: float, extra, current=None) -> np.ndarray:
+    """history_blend_host with the extra plane [n]: every pixel's samples are samples + extra[p] (pt_history_blend_counted_host)."""
+    s = np.ascontiguousarray(rgb_sum, np.float32).reshape(-1)
+    n = s.size // 3
+    c = None if current is None else np.ascontiguousarray(current, np.float32).reshape(-1)
+    if s.size != 3 * n or (c is not None and c.size != 4 * n):
+        raise PtError(f"history_blend_counted_host: {s.size} image floats")
+    out = np.empty((n, 3), np.float32)
+    _check(lib().pt_history_blend_counted_host(n, _f(s), C.c_float(samples), _f(_extra(extra, n)), None if c is None else _f(c), _f(out)))
+    return out
+
+
+def history_capture_counted_host(rgb_sum, planes, samples: float, extra, current=None) -> np.ndarray:
+    """history_capture_host with the extra plane [n] (pt_history_capture_counted_host)."""
+    s = np.ascontiguousarray(rgb_sum, np.float32).reshape(-1)
+    p = np.ascontiguousarray(planes, np.float32).reshape(-1)
+    n = s.size // 3
+    c = None if current is None else np.ascontiguousarray(current, np.float32).reshape(-1)
+    if s.size != 3 * n or p.size != 4 * FEATURE_PLANES * n or (c is not None and c.size != 4 * n):
+        raise PtError(f"history_capture_counted_host: {s.size} image, {p.size} plane floats")
+    out = np.empty((HISTORY_KEPT_PLANES, n, 4), np.float32)
+    _check(lib().pt_history_capture_counted_host(n, _f(s), _f(p), None if c is None else _f(c), C.c_float(samples), _f(_extra(extra, n)), _f(out)))
+    return out
+
+
+def history_capture_moments_counted_host(rgb_sum, samples: float, extra, current=None, current_var=None) -> np.ndarray:
+    """history_capture_moments_host with the extra plane [n] (pt_history_capture_moments_counted_host)."""
+    s = np.ascontiguousarray(rgb_sum, np.float32).reshape(-1)
+    n = s.size // 3
+    c = None if current is None else np.ascontiguousarray(current, np.float32).reshape(-1)
+    v = None if current_var is None else np.ascontiguousarray(current_var, np.float32).reshape(-1)
+    if s.size != 3 * n or any(a is not None and a.size != 4 * n for a in (c, v)):
+        raise PtError(f"history_capture_moments_counted_host: {s.size} image floats")
+    out = np.empty((n, 4), np.float32)
+    _check(lib().pt_history_capture_moments_counted_host(n, _f(s), C.c_float(samples), _f(_extra(extra, n)), None if c is None else _f(c),
+                                                         None if v is None else _f(v), _f(out)))
+    return out
+
+
+def history_denoise_moments_counted_host(rgb_sum, planes, w: int, rows: int, samples: float, extra, current=None, current_var=None,
+                                         stats: Optional[dict] = None, **opts) -> np.ndarray:
+    """history_denoise_moments_host with the extra plane [w*rows] (pt_history_denoise_moments_counted_host)."""
+    s, p, out = _denoise_arrays(rgb_sum, planes, w, rows)
+    c, v = _history_planes(current, current_var, w, rows)
+    var_raw = np.empty(w * rows, np.float32) if stats is not None else None
+    mark = np.empty(w * rows, np.uint8) if stats is not None else None
+    opt = denoise_options(**opts)
+    _check(lib().pt_history_denoise_moments_counted_host(int(w), int(rows), _f(s), _f(p), C.c_float(samples), _f(_extra(extra, w * rows)),
+                                                         None if c is None else _f(c), None if v is None else _f(v), C.byref(opt), _f(out),
+                                                         None if var_raw is None else _f(var_raw),
+                                                         None if mark is None else mark.ctypes.data_as(C.POINTER(C.c_uint8))))
+    if stats is not None:
+        stats.update(var_raw=var_raw, mark=mark.astype(bool))
+    return out
+
+
 def split_noise(planes: np.ndarray) -> dict:
     """The noise planes [PT_NOISE_PLANES, n, 4] (pt_readback_noise) by name: prev [n, 3] (the SUM image at the last fold),
     q [n, 3] (sum over the groups of B^2 / n), variance [n] (w: estimated variance of the averaged radiance, channels added)."""
@@ -1124,6 +1282,20 @@ class Renderer:
         opt = denoise_options(**opts)
         out = np.empty((self.n, 3), np.float32)
         _check(lib().pt_history_denoise_ex(C.c_float(samples), C.byref(opt), int(flags), _f(out)))
+        return out
+
+    def history_round(self, iter_first: int, group_iters: int, min_history: float = 0, max_fraction: float = 0):
+        """A group of further iterations for the pixels whose carried history weighs less than min_history samples, the shortest
+        max_fraction of the tile at the most (pt_history_round; synchronises once): (fresh pixels, pixels rendered)."""
+        opt = history_round_options(min_history, max_fraction)
+        fresh, selected = C.c_int32(-1), C.c_int32(-1)
+        _check(lib().pt_history_round(int(iter_first), int(group_iters), C.byref(opt), C.byref(fresh), C.byref(selected)))
+        return int(fresh.value), int(selected.value)
+
+    def readback_history_extra(self) -> np.ndarray:
+        """The extra plane E, float32 [n]: the samples a pixel holds beyond the uniform ones; zeros while absent."""
+        out = np.empty(self.n, np.float32)
+        _check(lib().pt_readback_history_extra(_f(out)))
         return out
 
     def readback_history_variance(self):

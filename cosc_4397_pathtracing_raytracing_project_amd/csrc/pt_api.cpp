@@ -623,6 +623,9 @@ int admit(const PtContext& g, const char* who, unsigned req) {
   if ((req & kUniform) && g.adaptive)
     return pt_fail("%s: the renderer is in the adaptive state (pt_adaptive_round): one sample count no longer describes the image; read it with pt_resolve, or "
                    "return to the uniform state with pt_clear", who);
+  if ((req & kNoExtras) && g.hist_extra)
+    return pt_fail("%s: the history round left extra samples in some pixels (pt_history_round): one sample count no longer describes the image; read it with "
+                   "pt_history_resolve, or return to the uniform state with pt_clear", who);
   const int W = g.cam.resolution[0];
   if ((req & kWholeRows) && (g.stripe || g.pixel_begin % W || g.N % W))
     return pt_fail("%s: the tile must consist of whole contiguous image rows (begin %d, count %d, stripe %d, width %d)", who, g.pixel_begin, g.N, g.stripe, W);
@@ -857,7 +860,7 @@ int pt_ctx_save_u8_device(PtContext* c, float samples, const uint8_t** rgb8_dev)
   Ctx& g = *c;
   const int W = g.cam.resolution[0];
   if (!(samples > 0.0f)) return pt_fail("pt_save_u8: samples must be positive");
-  if (admit(g, "pt_save_u8", kUniform)) return -1;
+  if (admit(g, "pt_save_u8", kUniform | kNoExtras)) return -1;
   if (g.pixel_begin % W || g.N % W || (g.stripe && g.stripe != W))  // (its own rule: the rows of a striped frame need not be contiguous)
     return pt_fail("pt_save_u8: the tile must consist of whole image rows (begin %d, count %d, stripe %d, width %d)", g.pixel_begin, g.N, g.stripe, W);
   HIP_OK(hipSetDevice(g.device));
@@ -874,7 +877,7 @@ int pt_ctx_save_u8(PtContext* c, float samples, uint8_t* rgb8_host) {
 int pt_ctx_preview_rgba8_device(PtContext* c, int iterations, void* rgba_dev) {
   if (need(c, "pt_preview_rgba8_device")) return -1;
   if (!rgba_dev || iterations <= 0) return pt_fail("pt_preview_rgba8_device: bad argument");
-  if (admit(*c, "pt_preview_rgba8_device", kUniform | kOnDevice)) return -1;
+  if (admit(*c, "pt_preview_rgba8_device", kUniform | kNoExtras | kOnDevice)) return -1;
   c->k->preview(c->stream, c->N, iterations, c->d_image, reinterpret_cast<uchar4*>(rgba_dev));
   HIP_OK(hipStreamSynchronize(c->stream));
   return 0;
@@ -883,7 +886,7 @@ int pt_ctx_preview_rgba8_device(PtContext* c, int iterations, void* rgba_dev) {
 int pt_ctx_preview_rgba8(PtContext* c, int iterations, uint8_t* rgba_host) {
   if (need(c, "pt_preview_rgba8")) return -1;
   if (!rgba_host || iterations <= 0) return pt_fail("pt_preview_rgba8: bad argument");
-  if (admit(*c, "pt_preview_rgba8", kUniform | kOnDevice)) return -1;
+  if (admit(*c, "pt_preview_rgba8", kUniform | kNoExtras | kOnDevice)) return -1;
   uchar4* d = nullptr;
   HIP_OK(hipMalloc((void**)&d, (size_t)c->N * 4));
   c->k->preview(c->stream, c->N, iterations, c->d_image, d);
@@ -965,6 +968,8 @@ int pt_ctx_clear(PtContext* c) {
   c->adaptive_last = 0;
   c->hist_current = c->feat_fresh = false;
   c->hist_var_current = 0;  // the history's current planes are absent; its kept planes stay (pt_history.h)
+  if (c->d_hist_extra) HIP_OK(hipMemsetAsync(c->d_hist_extra, 0, (size_t)c->N * sizeof(float), c->stream));  // the extras belong to the image
+  c->hist_extra = false;
   if (c->conv) {  // forget the curve, re-arm the capture (a supplied frame stays)
     HIP_OK(hipMemsetAsync(c->d_sse, 0xff, (size_t)PT_CONVERGENCE_CAPACITY * sizeof(double), c->stream));
     c->conv_last = 0;
@@ -1331,6 +1336,10 @@ int pt_history_denoise_ex(float samples, const PtDenoiseOptions* opt, uint32_t f
   return pt_ctx_history_denoise_ex(g_default, samples, opt, flags, rgb_avg_host);
 }
 int pt_readback_history_variance(float* kept_var, float* current_var) { return pt_ctx_readback_history_variance(g_default, kept_var, current_var); }
+int pt_history_round(int iter_first, int group_iters, const PtHistoryRoundOptions* opt, int* fresh, int* selected) {
+  return pt_ctx_history_round(g_default, iter_first, group_iters, opt, fresh, selected);
+}
+int pt_readback_history_extra(float* extra_host) { return pt_ctx_readback_history_extra(g_default, extra_host); }
 int pt_set_reference(const float* rgb_avg_host) { return pt_ctx_set_reference(g_default, rgb_avg_host); }
 int pt_get_convergence(int iter_first, int iter_count, double* sse) { return pt_ctx_get_convergence(g_default, iter_first, iter_count, sse); }
 int pt_iterations_to_clean(float threshold_db, int* iteration) { return pt_ctx_iterations_to_clean(g_default, threshold_db, iteration); }

@@ -169,6 +169,10 @@ struct PtContext : PtShared {
   void* d_hist_var = nullptr;      // pt_history_variance_bytes(N): VK, then VC; absent until the first capture with PT_HISTORY_VARIANCE or _MOMENTS
   uint32_t hist_var_kept = 0;      // the flag of the capture VK belongs to K0 by: the variance of K0 or its moments (0: a plain capture, K "kept without")
   uint32_t hist_var_current = 0;   // the flag of the lookup VC belongs to C by; 0 (absent) whenever C is
+  // The history round (pt_ctx_history_round): all of it absent until the first round that renders something
+  float* d_hist_extra = nullptr;   // the extra plane E: N floats, the samples the image holds per pixel beyond the uniform ones
+  bool hist_extra = false;         // E is present: from a round that rendered to pt_clear or a camera move, which zero it
+  uint8_t* d_hist_emitter = nullptr;  // one byte per geom: its material emits (the first round builds it)
   bool feat_fresh = false;         // a feature pass has run since pt_init / pt_clear / the last camera move
   // Moving the camera (pt_ctx_set_camera): the camera-independent tables on the host, and the grid to rebuild (the one init kept)
   pt::CameraBase camera_base;
@@ -261,6 +265,7 @@ enum Require : unsigned {
   kWholeRows = 4,   // the tile is rows of the image, whole and one after the other
   kFoldedAll = 8,   // nothing rendered since the last fold
   kOnDevice = 16,   // not a refusal: makes the context's device current
+  kNoExtras = 32,   // the history round's extra plane is absent (checked right after kUniform: both say "one sample count describes the image")
 };
 int admit(const PtContext& g, const char* who, unsigned req);
 

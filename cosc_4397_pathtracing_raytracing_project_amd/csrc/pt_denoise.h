@@ -25,6 +25,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/pt_amd.h"
@@ -82,6 +83,7 @@ PT_HD float color_factor(const Params& P, int l) {
 // pixel, as ptad::resolve_pixel.  History: the guided form's two for the new samples' variance, and what the blend reads — samples, the
 // history's current plane C and its variance VC (both nullptr: absent).
 // Moments: what the blend reads only — samples, C and VC = {m2h.xyz, rh} (both nullptr: absent); no fold, no noise planes.
+// E (the moments form; nullptr: absent): the extra plane of the history round — the pixel's samples are samples + E_p (pthi::Counted).
 enum class Form { Plain, Guided, Adaptive, History, Moments };
 struct Divisors {
   float Tf, Df;
@@ -89,7 +91,22 @@ struct Divisors {
   int32_t T, M;
   float samples;
   const V4 *C, *VC;
+  const float* E;
 };
+// A prepare's D has a member E: Divisors (the host loop, and a launch's checks) and the counted kernel's arguments; the kernels that
+// existed before the history round take structs without one and are compiled as they were.
+template <typename D, typename = void>
+struct HasExtra : std::false_type {};
+template <typename D>
+struct HasExtra<D, std::void_t<decltype(std::declval<const D&>().E)>> : std::true_type {};
+// The samples of pixel i as the history forms' prepare reads them
+template <typename D>
+PT_HD float history_samples(const D& d, size_t i) {
+  if constexpr (HasExtra<D>::value) {
+    if (d.E) return pthi::samples_of(pthi::Counted{d.samples, d.E}, i);
+  }
+  return d.samples;
+}
 
 // ── prepare: pixel i of the frame ────────────────────────────────────────────────────────────────────────────────────────
 // guided: the fold's own estimate of one component (pt_noise.h fold_component's last two lines, on the planes it left), demodulated
@@ -143,12 +160,14 @@ PT_HD void prepare_pixel_of(size_t i, size_t npix, const float* S, const V4* pla
   }
   V4 vc{0.0f, 0.0f, 0.0f, 0.0f};
   [[maybe_unused]] V4 hc{0.0f, 0.0f, 0.0f, 0.0f}, hv{0.0f, 0.0f, 0.0f, 0.0f};  // history: C and VC of the pixel (absent: +0)
+  [[maybe_unused]] float ns = 0.0f;  // history: the pixel's samples (with its extras, where the history round left some)
   if constexpr (kForm == Form::History || kForm == Form::Moments) {
+    ns = history_samples(d, i);
     if (d.C) hc = d.C[i];
     if (d.VC) hv = d.VC[i];
-    vc.x = pthi::blend_component(S[3 * i], d.samples, hc.x, hc.w);
-    vc.y = pthi::blend_component(S[3 * i + 1], d.samples, hc.y, hc.w);
-    vc.z = pthi::blend_component(S[3 * i + 2], d.samples, hc.z, hc.w);
+    vc.x = pthi::blend_component(S[3 * i], ns, hc.x, hc.w);
+    vc.y = pthi::blend_component(S[3 * i + 1], ns, hc.y, hc.w);
+    vc.z = pthi::blend_component(S[3 * i + 2], ns, hc.z, hc.w);
   } else {
     vc.x = S[3 * i] / Tf, vc.y = S[3 * i + 1] / Tf, vc.z = S[3 * i + 2] / Tf;
   }
@@ -160,12 +179,12 @@ PT_HD void prepare_pixel_of(size_t i, size_t npix, const float* S, const V4* pla
   }
   if constexpr (kForm == Form::History) {
     const V4 prev = noise[i], q = noise[npix + i];
-    const float vx = history_variance(prev.x, q.x, va.x, Tf, Df, d.samples, hv.x, hc.w, keep_albedo);
-    const float vy = history_variance(prev.y, q.y, va.y, Tf, Df, d.samples, hv.y, hc.w, keep_albedo);
-    const float vz = history_variance(prev.z, q.z, va.z, Tf, Df, d.samples, hv.z, hc.w, keep_albedo);
+    const float vx = history_variance(prev.x, q.x, va.x, Tf, Df, ns, hv.x, hc.w, keep_albedo);
+    const float vy = history_variance(prev.y, q.y, va.y, Tf, Df, ns, hv.y, hc.w, keep_albedo);
+    const float vz = history_variance(prev.z, q.z, va.z, Tf, Df, ns, hv.z, hc.w, keep_albedo);
     va.w = (vx + vy) + vz;
   } else if constexpr (kForm == Form::Moments) {
-    const V4 mb = pthi::blend_moments(i, S, d.samples, hc.w, hv);
+    const V4 mb = pthi::blend_moments(i, S, ns, hc.w, hv);
     if (mb.w <= PT_HISTORY_MOMENTS_R_MAX) {
       const float f = mb.w / (1.0f - mb.w);
       const float vx = moments_variance(mb.x, cb.x, f, va.x, keep_albedo);
@@ -370,6 +389,7 @@ struct Frame {
   int w, rows;
   const float *rgb_sum, *planes, *noise;
   const float *current = nullptr, *current_var = nullptr;
+  const float* extra = nullptr;  // the moments form: the extra plane E, w * rows floats (null: absent)
 };
 struct Job {
   Form form;
@@ -403,6 +423,7 @@ inline void denoise_host(const Job& j, const int32_t* counts, float* out, float*
     hist[i] = V4{c[0], c[1], c[2], c[3]}, hist[npix + i] = V4{v[0], v[1], v[2], v[3]};
   }
   if (blended) d.C = hist.empty() ? nullptr : hist.data(), d.VC = hist.empty() ? nullptr : hist.data() + npix;
+  d.E = j.form == Form::Moments ? j.f.extra : nullptr;
   for (size_t i = 0; i < npix; ++i) {
     if (j.form == Form::Plain) prepare_pixel_of<Form::Plain>(i, npix, j.f.rgb_sum, pl.data(), nz, d, P.keep_albedo, n, p, a, col[0]);
     else if (j.form == Form::Guided) prepare_pixel_of<Form::Guided>(i, npix, j.f.rgb_sum, pl.data(), nz, d, P.keep_albedo, n, p, a, col[0]);

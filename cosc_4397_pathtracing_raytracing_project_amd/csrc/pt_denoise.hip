@@ -15,6 +15,8 @@
 //                                  present); per pixel 12 B of S, 48 B of features, 32 B of noise, 16 + 16 B of history in, 64 B out
 //                                  <Moments>: the blend and its variance from the history's moments, no noise planes: per pixel 12 B of
 //                                  S, 48 B of features, 16 + 16 B of history in, 64 B out; var_raw = -1 marks a pixel for the next kernel
+//   k_denoise_prepare_counted      <Moments> while the history round's extra plane is present (pt_history_round): + 4 B of E in per pixel,
+//                                  the pixel's samples are samples + E_p; a twelfth kernel, launched only then
 //   k_denoise_var_spatial          the moments form, between prepare and the prefilter; the level kernel's shape (64 x 4 tiles, a wave is
 //                                  64 pixels of a row).  A wave with no marked lane leaves on a ballot of the mark (4 B per lane read):
 //                                  how many do is the frame's affair (misses are always marked).  A marked lane walks its 7 x 7 neighbourhood, 3 x 16 B per tap
@@ -85,6 +87,22 @@ __global__ __launch_bounds__(kBlock) void k_denoise_prepare(int npix, const floa
   if (i < npix) ptdn::prepare_pixel_of<kForm>((size_t)i, (size_t)npix, S, planes, noise, d, keep_albedo, n, p, a, c);
 }
 
+// The moments form's prepare while the history round's extra plane E is present: 4 B of E more per pixel in, ns = samples + E_p for
+// `samples`.  A kernel of its own, so that k_denoise_prepare<Moments> keeps its arguments and its code.
+struct PrepareInCounted {
+  const V4* __restrict__ C;
+  const V4* __restrict__ VC;
+  float samples;
+  const float* __restrict__ E;
+};
+__global__ __launch_bounds__(kBlock) void k_denoise_prepare_counted(int npix, const float* __restrict__ S, const V4* __restrict__ planes, const V4* __restrict__ C,
+                                                                    const V4* __restrict__ VC, float samples, const float* __restrict__ E, int keep_albedo,
+                                                                    V4* __restrict__ n, V4* __restrict__ p, V4* __restrict__ a, V4* __restrict__ c) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  const PrepareInCounted d{C, VC, samples, E};
+  if (i < npix) ptdn::prepare_pixel_of<Form::Moments>((size_t)i, (size_t)npix, S, planes, nullptr, d, keep_albedo, n, p, a, c);
+}
+
 // `a` is read (the lane's own mark) and written (the lane's own var_raw): no __restrict__ promise is needed or made for it.
 __global__ __launch_bounds__(kBlock) void k_denoise_var_spatial(int W, int R, Params P, const V4* __restrict__ n, const V4* __restrict__ p,
                                                                 const V4* __restrict__ c, V4* a) {
@@ -132,7 +150,7 @@ int pt_denoise_launch(hipStream_t stream, const ptdn::Job& j, void* workspace_de
                   : j.form == Form::Adaptive ? j.f.noise && (d.cnt || (d.M >= 2 && d.T >= d.M))
                   : j.form == Form::Moments  ? d.samples > 0.0f && !d.C == !d.VC
                                              : j.f.noise && d.Tf >= 2.0f && d.Df >= d.Tf && d.samples > 0.0f && !d.C == !d.VC;
-  if (!j.f.rgb_sum || !j.f.planes || !workspace_dev || !ok || P.levels < 1 || P.levels > ptdn::kMaxLevels) return pt_fail("%s: bad argument", who);
+  if (!j.f.rgb_sum || !j.f.planes || !workspace_dev || !ok || (d.E && j.form != Form::Moments) || P.levels < 1 || P.levels > ptdn::kMaxLevels) return pt_fail("%s: bad argument", who);
   const int npix = w * rows;
   V4* n = static_cast<V4*>(workspace_dev);
   V4 *p = n + npix, *a = p + npix, *col[2] = {a + npix, a + 2 * (size_t)npix};
@@ -146,6 +164,9 @@ int pt_denoise_launch(hipStream_t stream, const ptdn::Job& j, void* workspace_de
   else if (history)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_denoise_prepare<Form::History, const V4* __restrict__, const V4* __restrict__, const V4* __restrict__, float, float, float>),
                        dim3(flat), dim3(kBlock), 0, stream, npix, j.f.rgb_sum, planes, noise, d.C, d.VC, d.Tf, d.Df, d.samples, P.keep_albedo, n, p, a, col[0]);
+  else if (moments && d.E)
+    hipLaunchKernelGGL(k_denoise_prepare_counted, dim3(flat), dim3(kBlock), 0, stream, npix, j.f.rgb_sum, planes, d.C, d.VC, d.samples, d.E, P.keep_albedo, n, p, a,
+                       col[0]);
   else if (moments)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_denoise_prepare<Form::Moments, const V4* __restrict__, const V4* __restrict__, float>), dim3(flat), dim3(kBlock), 0, stream,
                        npix, j.f.rgb_sum, planes, d.C, d.VC, d.samples, P.keep_albedo, n, p, a, col[0]);
@@ -286,6 +307,17 @@ int pt_history_denoise_moments_host(int w, int rows, const float* rgb_sum, const
                                        rgb_avg || var_raw || mark, &j))
     return -1;
   j.f = {w, rows, rgb_sum, planes, nullptr, current_plane, current_var};
+  ptdn::denoise_host(j, nullptr, rgb_avg, var_raw, nullptr, mark);
+  return 0;
+}
+int pt_history_denoise_moments_counted_host(int w, int rows, const float* rgb_sum, const float* planes, float samples, const float* extra,
+                                            const float* current_plane, const float* current_var, const PtDenoiseOptions* opt, float* rgb_avg,
+                                            float* var_raw, uint8_t* mark) {
+  const char* who = "pt_history_denoise_moments_counted_host";
+  ptdn::Job j{};
+  if (pt_history_denoise_moments_check(who, w, rows, rgb_sum, planes, samples, current_plane, current_var, opt, rgb_avg || var_raw || mark, &j)) return -1;
+  if (pt_history_check_extra(who, w * rows, extra)) return -1;
+  j.f = {w, rows, rgb_sum, planes, nullptr, current_plane, current_var, extra};
   ptdn::denoise_host(j, nullptr, rgb_avg, var_raw, nullptr, mark);
   return 0;
 }

@@ -20,8 +20,14 @@
 // writes +0: reproject_pixel_of<kMoments>, an instantiation of its own, so that the variance kind's kernel is the code it was.
 // pt_history_denoise_ex: ptdn::Form::Moments in pt_denoise.h, whose prepare runs blend_moments below.
 //
+// The history round (pt_history_round; round_key, merge_entry and Counted below): pixels whose carried weight Th is below min_history
+// get a group of further iterations, for those pixels alone — the key orders them, pt_adaptive.h's selection lists them, the adaptive
+// rounds' worker renders them, and the merge counts them in the extra plane E.  While E is present the blend, the capture and the
+// moments read ns = samples + E_p where they read `samples`: the Counted instantiations, beside the ones that take a float and are
+// the bodies as they stood.
+//
 // Out of scope (pt_amd.h says the same): pt_group_* (a context's interleaved rows cannot look up their neighbours), feeding the
-// history into the noise estimate or adaptive sampling, feeding the FILTERED image back into the history (K keeps the unfiltered
+// history into the noise estimate, the history round in groups of contexts, a key that uses the carried variance, feeding the FILTERED image back into the history (K keeps the unfiltered
 // blend), motion of anything but the camera, and correcting the smoothing the bilinear lookup adds — the carried image is a biased estimator, and the carried
 // variance is interpolated linearly (as SVGF interpolates its moments), which overstates it: the lookup's smoothing lowers the true one.
 #pragma once
@@ -29,6 +35,7 @@
 #include <cstdint>
 
 #include "../../include/pt_amd.h"
+#include "pt_adaptive.h"
 #include "pt_portable_math.h"
 
 namespace pthi {
@@ -98,6 +105,18 @@ PT_HD float bits_float(int32_t i) {
   return f;
 }
 
+// The samples the SUM image holds for pixel i: one number for the tile (a float: the forms as they stood), or that number and the
+// pixel's extras (Counted: while the extra plane E of the history round is present) — one float add, made before anything else.
+struct Counted {
+  float samples;
+  const float* E;
+};
+PT_HD float samples_of(float samples, size_t) { return samples; }
+PT_HD float samples_of(const Counted& c, size_t i) {
+#pragma clang fp contract(off)
+  return c.samples + c.E[i];
+}
+
 // What pt_denoise's prepare makes of a pixel's feature sums: hit, normal, position; and the object id (0 on a miss).
 struct Surface {
   bool hit;
@@ -160,6 +179,7 @@ PT_HD float blend_weight_sum(float rh, const MomentWeights& w) {
   return w.wn * w.wn + (w.wh * w.wh) * rh;
 }
 // {m2b.xyz, rb} of pixel i from the SUM image and the history's {m2h.xyz, rh} (vh; absent: all +0)
+// (samples: the pixel's own, samples_of)
 template <typename P4>
 PT_HD P4 blend_moments(size_t i, const float* S, float samples, float Th, const P4& vh) {
 #pragma clang fp contract(off)
@@ -191,12 +211,14 @@ struct VarReproject {
 };
 
 // Pixel i of a tile of npix pixels: rgb_avg[3 i ..] = the blend.  C: the current plane, or nullptr (absent).
-template <typename P4>
-PT_HD void blend_pixel(size_t i, const float* S, float samples, const P4* C, float* rgb_avg) {
+// Ns: float, or Counted.
+template <typename P4, typename Ns>
+PT_HD void blend_pixel(size_t i, const float* S, const Ns& samples, const P4* C, float* rgb_avg) {
+  const float ns = samples_of(samples, i);
   const P4 c = C ? C[i] : P4{0.0f, 0.0f, 0.0f, 0.0f};
-  rgb_avg[3 * i] = blend_component(S[3 * i], samples, c.x, c.w);
-  rgb_avg[3 * i + 1] = blend_component(S[3 * i + 1], samples, c.y, c.w);
-  rgb_avg[3 * i + 2] = blend_component(S[3 * i + 2], samples, c.z, c.w);
+  rgb_avg[3 * i] = blend_component(S[3 * i], ns, c.x, c.w);
+  rgb_avg[3 * i + 1] = blend_component(S[3 * i + 1], ns, c.y, c.w);
+  rgb_avg[3 * i + 2] = blend_component(S[3 * i + 2], ns, c.z, c.w);
 }
 
 // The variance side of a capture: VK[i] = the variance of the blend K0.xyz; Th = C.w of the pixel (C absent: +0).
@@ -217,9 +239,11 @@ PT_HD void capture_moments_pixel(size_t i, const float* S, float samples, float 
 }
 // Pixel i: the kept planes K (kKeptPlanes planes of npix) from the SUM image, the feature sums and the current plane (or nullptr).
 // kKind: kVariance / kMoments also write VK[i], from `var` (a VarCapture / MomCapture; read only then).
-template <int kKind, typename P4, typename Side>
-PT_HD void capture_pixel_of(size_t i, size_t npix, const float* S, const P4* feat, const P4* C, float samples, P4* K, const Side& var) {
+// Ns: float, or Counted (kPlain and kMoments; the fold's variance knows nothing of the extras).
+template <int kKind, typename P4, typename Side, typename Ns>
+PT_HD void capture_pixel_of(size_t i, size_t npix, const float* S, const P4* feat, const P4* C, const Ns& tile_samples, P4* K, const Side& var) {
 #pragma clang fp contract(off)
+  const float samples = samples_of(tile_samples, i);
   const Surface s = surface(i, npix, feat);
   const P4 c = C ? C[i] : P4{0.0f, 0.0f, 0.0f, 0.0f};
   K[i] = P4{blend_component(S[3 * i], samples, c.x, c.w), blend_component(S[3 * i + 1], samples, c.y, c.w),
@@ -345,6 +369,82 @@ inline void reproject_moments_host(const View& v, const float* K, const float* f
 }
 inline void blend_host(size_t npix, const float* S, float samples, const float* C, float* rgb_avg) {
   for (size_t i = 0; i < npix; ++i) blend_pixel(i, S, samples, reinterpret_cast<const F4*>(C), rgb_avg);
+}
+
+// ── the history round (pt_history_round) ─────────────────────────────────────────────────────────────────────────────────
+// PtHistoryRoundOptions with the defaults filled in; the message of a refusal, or nullptr.
+struct RoundParams {
+  float min_history, max_fraction;
+};
+inline const char* resolve_round(const PtHistoryRoundOptions* opt, RoundParams* out) {
+  PtHistoryRoundOptions o{};
+  if (opt) o = *opt;
+  if (!(o.min_history - o.min_history == 0.0f) || !(o.max_fraction - o.max_fraction == 0.0f)) return "an option is not finite";
+  if (o.min_history == 0.0f) o.min_history = PT_HISTORY_ROUND_MIN_HISTORY;
+  if (!(o.min_history > 0.0f)) return "min_history must be positive";
+  if (o.max_fraction == 0.0f) o.max_fraction = 1.0f;
+  if (!(o.max_fraction > 0.0f && o.max_fraction <= 1.0f)) return "max_fraction is not in (0, 1]";
+  *out = RoundParams{o.min_history, o.max_fraction};
+  return nullptr;
+}
+// The key of tile pixel i as its uint32 bit pattern: how far the carried weight Th = C.w lies below min_history, +0 for a miss, an id
+// outside 1 .. num_geoms or an emitter (emitter: one byte per geom), and for a history that is long enough.  C == nullptr: absent,
+// Th = +0.  Of the feature sums only s1.w and s2.w are read, of C only its w.  A pixel is FRESH when the bits are > 0; a NaN Th gives
+// d > 0 false and so +0.
+template <typename P4>
+PT_HD uint32_t round_key(size_t i, size_t npix, const P4* feat, const P4* C, const uint8_t* emitter, int32_t num_geoms, float min_history) {
+#pragma clang fp contract(off)
+  const float hitw = feat[npix + i].w;
+  const int32_t id = float_bits(feat[2 * npix + i].w);
+  if (!(hitw > 0.0f) || id < 1 || id > num_geoms || emitter[id - 1]) return 0u;
+  const float Th = C ? C[i].w : 0.0f;
+  const float d = min_history - Th;
+  return d > 0.0f ? (uint32_t)float_bits(d) : 0u;
+}
+// List entry i of the merge: the worker's group sum Sw[i] of G iterations joins tile pixel p = list[i], and E_p counts them (gf = (float)G).
+PT_HD void merge_entry(size_t i, const int32_t* list, const float* Sw, float gf, float* S, float* E) {
+#pragma clang fp contract(off)
+  const size_t p = (size_t)list[i];
+  S[3 * p] = S[3 * p] + Sw[3 * i];
+  S[3 * p + 1] = S[3 * p + 1] + Sw[3 * i + 1];
+  S[3 * p + 2] = S[3 * p + 2] + Sw[3 * i + 2];
+  E[p] = E[p] + gf;
+}
+
+inline std::vector<uint32_t> round_keys_host(size_t npix, const float* feat, const float* C, const uint8_t* emitter, int32_t num_geoms, float min_history) {
+  std::vector<uint32_t> key(npix);
+  for (size_t i = 0; i < npix; ++i)
+    key[i] = round_key(i, npix, reinterpret_cast<const F4*>(feat), reinterpret_cast<const F4*>(C), emitter, num_geoms, min_history);
+  return key;
+}
+// The selection on the host: pt_adaptive.h's selection by threshold on these keys with threshold bits 0 — the cut for rank cap, the
+// clamp under the threshold, the scatter.  list holds cap entries; those behind *m keep what they held.
+inline void select_host(size_t npix, const float* feat, const float* C, const uint8_t* emitter, int32_t num_geoms, float min_history, int cap, int32_t* list,
+                        int* fresh, int* m) {
+  const std::vector<uint32_t> key = round_keys_host(npix, feat, C, emitter, num_geoms, min_history);
+  const ptad::Cut top = ptad::cut_host(key, cap);
+  uint32_t n_fresh = 0;
+  for (uint32_t k : key) n_fresh += ptad::above_threshold(k, 0u) ? 1u : 0u;
+  ptad::scatter_host(key, ptad::threshold_cut(top.tau, top.r, 0u), list);
+  *fresh = (int)n_fresh;
+  *m = (int)ptad::threshold_length(n_fresh, (uint32_t)cap);
+}
+inline void merge_host(float* S, float* E, const int32_t* list, int m, const float* Sw, int group_iters) {
+  for (int i = 0; i < m; ++i) merge_entry((size_t)i, list, Sw, (float)group_iters, S, E);
+}
+// The counted forms of the whole-tile loops above: E_p extras beside the tile's `samples`.
+inline void blend_counted_host(size_t npix, const float* S, float samples, const float* E, const float* C, float* rgb_avg) {
+  for (size_t i = 0; i < npix; ++i) blend_pixel(i, S, Counted{samples, E}, reinterpret_cast<const F4*>(C), rgb_avg);
+}
+inline void capture_counted_host(size_t npix, const float* S, const float* feat, const float* C, float samples, const float* E, float* K) {
+  for (size_t i = 0; i < npix; ++i)
+    capture_pixel_of<kPlain>(i, npix, S, reinterpret_cast<const F4*>(feat), reinterpret_cast<const F4*>(C), Counted{samples, E}, reinterpret_cast<F4*>(K),
+                             VarCapture<F4>{});
+}
+inline void capture_moments_counted_host(size_t npix, const float* S, float samples, const float* E, const float* C, const float* VC, float* VK) {
+  const F4* c4 = reinterpret_cast<const F4*>(C);
+  const MomCapture<F4> mom{reinterpret_cast<const F4*>(VC), reinterpret_cast<F4*>(VK)};
+  for (size_t i = 0; i < npix; ++i) capture_moments_pixel(i, S, samples_of(Counted{samples, E}, i), c4 ? c4[i].w : 0.0f, mom);
 }
 
 }  // namespace pthi

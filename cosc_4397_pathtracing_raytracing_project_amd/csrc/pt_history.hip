@@ -18,9 +18,20 @@
 //   k_history_capture<kMoments>   + (when present) 16 B of VC in, 16 B of VK out per pixel; no fold is read
 //   k_history_reproject<kVariance>  + 16 B of VC out per pixel; per tap that passed 16 B of VK, read after K0 at the same index
 //   k_history_reproject<kMoments>   the same loads and stores; the fourth component of VK is interpolated too
+// The history round (pt_history_round):
+//   k_history_key        a pure stream, one thread per tile pixel: the .w words of the feature sums s1 and s2 and (when present) of C
+//                        in, as 4-byte loads 16 bytes apart — 12 B per pixel asked for, whole lines moved: consecutive lanes sit in
+//                        the same 128-byte lines, so the planes' 48 B per pixel cross the memory bus as with 16-byte loads, but a lane
+//                        holds 3 registers of them, not 12 — one byte of the emitter table for a hit (a gather into a few lines), 4 B
+//                        of key out.  No LDS, no scratch
+//   k_history_merge      a short scatter, one thread per list entry: 4 B of the list and 12 B of Sw in (streaming), 12 B of S and
+//                        4 B of E read and written at the listed pixel
+//   k_history_capture_counted<kPlain | kMoments>, k_history_blend_counted   the kernels above with 4 B of E more per pixel in and
+//                        ns = samples + E_p for `samples` (pthi::Counted); launched only while E is present
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
+#include <vector>
 
 #include "pt_history.h"
 #include "pt_internal.h"
@@ -62,6 +73,32 @@ __global__ __launch_bounds__(kBlock) void k_history_blend(int npix, const float*
                                                           float* __restrict__ out) {
   const int i = blockIdx.x * kBlock + threadIdx.x;
   if (i < npix) pthi::blend_pixel((size_t)i, S, samples, C, out);
+}
+
+// ... with the pixel's extras: ns = samples + E[i]
+template <int kKind, typename... In>
+__global__ __launch_bounds__(kBlock) void k_history_capture_counted(int npix, const float* __restrict__ S, const V4* __restrict__ feat, const V4* C, float samples,
+                                                                    const float* __restrict__ E, V4* __restrict__ K, In... in) {
+  using Side = std::conditional_t<kKind == pthi::kMoments, pthi::MomCapture<V4>, pthi::VarCapture<V4>>;
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < npix) pthi::capture_pixel_of<kKind>((size_t)i, (size_t)npix, S, feat, C, pthi::Counted{samples, E}, K, Side{in...});
+}
+__global__ __launch_bounds__(kBlock) void k_history_blend_counted(int npix, const float* __restrict__ S, float samples, const float* __restrict__ E,
+                                                                  const V4* __restrict__ C, float* __restrict__ out) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < npix) pthi::blend_pixel((size_t)i, S, pthi::Counted{samples, E}, C, out);
+}
+
+__global__ __launch_bounds__(kBlock) void k_history_key(int npix, const V4* __restrict__ feat, const V4* __restrict__ C, const uint8_t* __restrict__ emitter,
+                                                        int num_geoms, float min_history, uint32_t* __restrict__ key) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < npix) key[i] = pthi::round_key((size_t)i, (size_t)npix, feat, C, emitter, num_geoms, min_history);
+}
+// S and E are read and written at list[i]: distinct entries, so no two threads meet.  (An entry outside the tile writes nothing.)
+__global__ __launch_bounds__(kBlock) void k_history_merge(int npix, int m, const int32_t* __restrict__ list, const float* __restrict__ Sw, float gf, float* S,
+                                                          float* E) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < m && (uint32_t)list[i] < (uint32_t)npix) pthi::merge_entry((size_t)i, list, Sw, gf, S, E);
 }
 
 int launched(const char* who) {
@@ -142,6 +179,85 @@ int pt_history_blend_launch(hipStream_t stream, int pixels, const float* rgb_sum
   hipLaunchKernelGGL(k_history_blend, dim3((pixels + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, pixels, rgb_sum_dev, samples,
                      static_cast<const V4*>(current_dev), rgb_avg_dev);
   return launched("pt_history_resolve");
+}
+
+// The counted forms: extra_dev the plane E, `pixels` floats.
+int pt_history_capture_counted_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, const float* planes_dev, const void* current_dev, float samples,
+                                      const float* extra_dev, void* kept_dev) {
+  if (pixels <= 0 || pixels > (1 << 30) || !rgb_sum_dev || !planes_dev || !kept_dev || !(samples > 0.0f) || !extra_dev) return pt_fail("pt_history_capture: bad argument");
+  hipLaunchKernelGGL(k_history_capture_counted<pthi::kPlain>, dim3((pixels + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, pixels, rgb_sum_dev,
+                     reinterpret_cast<const V4*>(planes_dev), static_cast<const V4*>(current_dev), samples, extra_dev, static_cast<V4*>(kept_dev));
+  return launched("pt_history_capture");
+}
+int pt_history_capture_moments_counted_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, const float* planes_dev, const void* current_dev,
+                                              float samples, const float* extra_dev, void* kept_dev, const void* current_var_dev, void* kept_var_dev) {
+  if (pixels <= 0 || pixels > (1 << 30) || !rgb_sum_dev || !planes_dev || !kept_dev || !(samples > 0.0f) || !extra_dev || !kept_var_dev ||
+      !current_dev != !current_var_dev)
+    return pt_fail("pt_history_capture_ex: bad argument");
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_history_capture_counted<pthi::kMoments, const V4*, V4*>), dim3((pixels + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, pixels,
+                     rgb_sum_dev, reinterpret_cast<const V4*>(planes_dev), static_cast<const V4*>(current_dev), samples, extra_dev, static_cast<V4*>(kept_dev),
+                     static_cast<const V4*>(current_var_dev), static_cast<V4*>(kept_var_dev));
+  return launched("pt_history_capture_ex");
+}
+int pt_history_blend_counted_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, float samples, const float* extra_dev, const void* current_dev,
+                                    float* rgb_avg_dev) {
+  if (pixels <= 0 || pixels > (1 << 30) || !rgb_sum_dev || !rgb_avg_dev || !(samples > 0.0f) || !extra_dev) return pt_fail("pt_history_resolve: bad argument");
+  hipLaunchKernelGGL(k_history_blend_counted, dim3((pixels + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, pixels, rgb_sum_dev, samples, extra_dev,
+                     static_cast<const V4*>(current_dev), rgb_avg_dev);
+  return launched("pt_history_resolve");
+}
+
+// The history round's key into key_dev (pixels words: pt_adaptive_select_keys) and its merge.  emitter_dev: one byte per geom, read for
+// ids 1 .. num_geoms only.
+int pt_history_key_launch(hipStream_t stream, int pixels, const float* planes_dev, const void* current_dev, const uint8_t* emitter_dev, int num_geoms,
+                          float min_history, uint32_t* key_dev) {
+  if (pixels <= 0 || pixels > (1 << 30) || !planes_dev || !key_dev || num_geoms < 0 || (num_geoms > 0 && !emitter_dev) || !(min_history > 0.0f))
+    return pt_fail("pt_history_round: bad argument");
+  hipLaunchKernelGGL(k_history_key, dim3((pixels + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, pixels, reinterpret_cast<const V4*>(planes_dev),
+                     static_cast<const V4*>(current_dev), emitter_dev, num_geoms, min_history, key_dev);
+  return launched("pt_history_round");
+}
+int pt_history_merge_launch(hipStream_t stream, int pixels, float* rgb_sum_dev, float* extra_dev, const int32_t* list_dev, int m, const float* group_sum_dev,
+                            int group_iters) {
+  if (pixels <= 0 || pixels > (1 << 30) || m < 1 || m > pixels || group_iters < 1 || !rgb_sum_dev || !extra_dev || !list_dev || !group_sum_dev)
+    return pt_fail("pt_history_round: bad argument");
+  hipLaunchKernelGGL(k_history_merge, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, pixels, m, list_dev, group_sum_dev, (float)group_iters, rgb_sum_dev,
+                     extra_dev);
+  return launched("pt_history_round");
+}
+
+int pt_history_round_options(const char* who, const PtHistoryRoundOptions* opt, pthi::RoundParams* P) {
+  if (const char* msg = pthi::resolve_round(opt, P)) return pt_fail("%s: %s", who, msg);
+  return 0;
+}
+// What the host and stage forms of the selection refuse: the frame, the arrays, the options; *cap the list's capacity.
+int pt_history_select_check(const char* who, int w, int rows, const float* feature_planes, const uint8_t* emitter_geom, int num_geoms,
+                            const PtHistoryRoundOptions* opt, const int32_t* list, const int* fresh, const int* m, pthi::RoundParams* P, int* cap) {
+  if (w <= 0 || rows <= 0 || (int64_t)w * rows > (1ll << 30)) return pt_fail("%s: a tile of %d x %d pixels is not supported", who, w, rows);
+  if (!feature_planes || !list || !fresh || !m) return pt_fail("%s: null argument", who);
+  if (num_geoms < 0 || (num_geoms > 0 && !emitter_geom)) return pt_fail("%s: null emitter_geom for %d geoms", who, num_geoms);
+  if (pt_history_round_options(who, opt, P)) return -1;
+  *cap = ptad::list_length((double)P->max_fraction, (int64_t)w * rows);
+  return 0;
+}
+// ... and of the merge: the arrays, the list's entries (inside the tile, distinct), the group.
+int pt_history_merge_check(const char* who, int pixels, const float* rgb_sum, const float* extra, const int32_t* list, int m, const float* group_sum,
+                           int group_iters) {
+  if (pixels <= 0 || pixels > (1 << 30) || !rgb_sum || !extra || !list || !group_sum) return pt_fail("%s: bad argument", who);
+  if (m < 1 || m > pixels || group_iters < 1) return pt_fail("%s: a list of %d out of %d pixels, a group of %d iterations", who, m, pixels, group_iters);
+  std::vector<uint8_t> seen((size_t)pixels, 0);
+  for (int i = 0; i < m; ++i) {
+    if (list[i] < 0 || list[i] >= pixels || seen[(size_t)list[i]]) return pt_fail("%s: list[%d] = %d is outside the tile or repeated", who, i, list[i]);
+    seen[(size_t)list[i]] = 1;
+  }
+  return 0;
+}
+// extra: every E_p finite and >= 0 (a count of samples)
+int pt_history_check_extra(const char* who, int pixels, const float* extra) {
+  if (!extra) return pt_fail("%s: null extra", who);
+  for (int i = 0; i < pixels; ++i)
+    if (!(extra[i] - extra[i] == 0.0f) || extra[i] < 0.0f) return pt_fail("%s: extra[%d] = %g is not finite and >= 0", who, i, (double)extra[i]);
+  return 0;
 }
 
 int pt_history_check_samples(const char* who, float samples) {
@@ -237,5 +353,44 @@ extern "C" int pt_history_blend_host(int pixels, const float* rgb_sum, float sam
   if (pixels <= 0 || pixels > (1 << 30) || !rgb_sum || !rgb_avg) return pt_fail("pt_history_blend_host: bad argument");
   if (pt_history_check_samples("pt_history_blend_host", samples)) return -1;
   pthi::blend_host((size_t)pixels, rgb_sum, samples, current_plane, rgb_avg);
+  return 0;
+}
+
+// ---- the history round on the host ---------------------------------------------------------------------------------------
+extern "C" int pt_history_select_host(int w, int rows, const float* feature_planes, const float* current_plane, const uint8_t* emitter_geom, int num_geoms,
+                                      const PtHistoryRoundOptions* opt, int32_t* list, int* fresh, int* m) {
+  pthi::RoundParams P{};
+  int cap = 0;
+  if (pt_history_select_check("pt_history_select_host", w, rows, feature_planes, emitter_geom, num_geoms, opt, list, fresh, m, &P, &cap)) return -1;
+  pthi::select_host((size_t)w * rows, feature_planes, current_plane, emitter_geom, num_geoms, P.min_history, cap, list, fresh, m);
+  return 0;
+}
+extern "C" int pt_history_merge_host(int pixels, float* rgb_sum, float* extra, const int32_t* list, int m, const float* group_sum, int group_iters) {
+  if (pt_history_merge_check("pt_history_merge_host", pixels, rgb_sum, extra, list, m, group_sum, group_iters)) return -1;
+  pthi::merge_host(rgb_sum, extra, list, m, group_sum, group_iters);
+  return 0;
+}
+extern "C" int pt_history_blend_counted_host(int pixels, const float* rgb_sum, float samples, const float* extra, const float* current_plane, float* rgb_avg) {
+  const char* who = "pt_history_blend_counted_host";
+  if (pixels <= 0 || pixels > (1 << 30) || !rgb_sum || !rgb_avg) return pt_fail("%s: bad argument", who);
+  if (pt_history_check_samples(who, samples) || pt_history_check_extra(who, pixels, extra)) return -1;
+  pthi::blend_counted_host((size_t)pixels, rgb_sum, samples, extra, current_plane, rgb_avg);
+  return 0;
+}
+extern "C" int pt_history_capture_counted_host(int pixels, const float* rgb_sum, const float* feature_planes, const float* current_plane, float samples,
+                                               const float* extra, float* kept_planes) {
+  const char* who = "pt_history_capture_counted_host";
+  if (pixels <= 0 || pixels > (1 << 30) || !rgb_sum || !feature_planes || !kept_planes) return pt_fail("%s: bad argument", who);
+  if (pt_history_check_samples(who, samples) || pt_history_check_extra(who, pixels, extra)) return -1;
+  pthi::capture_counted_host((size_t)pixels, rgb_sum, feature_planes, current_plane, samples, extra, kept_planes);
+  return 0;
+}
+extern "C" int pt_history_capture_moments_counted_host(int pixels, const float* rgb_sum, float samples, const float* extra, const float* current_plane,
+                                                       const float* current_var, float* kept_var) {
+  const char* who = "pt_history_capture_moments_counted_host";
+  if (pixels <= 0 || pixels > (1 << 30) || !rgb_sum || !kept_var) return pt_fail("%s: bad argument", who);
+  if (pt_history_check_samples(who, samples) || pt_history_check_extra(who, pixels, extra)) return -1;
+  if (!current_plane != !current_var) return pt_fail("%s: the current plane and its moments come together or not at all", who);
+  pthi::capture_moments_counted_host((size_t)pixels, rgb_sum, samples, extra, current_plane, current_var, kept_var);
   return 0;
 }

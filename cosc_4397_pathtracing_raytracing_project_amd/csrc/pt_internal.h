@@ -126,3 +126,27 @@ int pt_history_capture_moments_launch(hipStream_t stream, int pixels, const floa
 int pt_history_reproject_moments_launch(hipStream_t stream, const pthi::View& v, const void* kept_dev, const float* planes_dev, const uint8_t* reject_dev,
                                         int num_geoms, const pthi::Params& P, void* current_dev, const void* kept_var_dev, void* current_var_dev);
 int pt_history_blend_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, float samples, const void* current_dev, float* rgb_avg_dev);
+// The history round (pt_history_round): the key of every tile pixel into key_dev (pt_adaptive_select_keys of the selection's workspace;
+// emitter_dev one byte per geom), the merge of the worker's group sum (m >= 1 list entries) into the image and the extra plane E
+// (`pixels` floats), and the counted forms of capture and blend, which read ns = samples + E_p for `samples`.  The checks: what the
+// host and stage forms refuse, under the name `who`.
+struct PtHistoryRoundOptions;
+namespace pthi {
+struct RoundParams;
+}
+int pt_history_round_options(const char* who, const PtHistoryRoundOptions* opt, pthi::RoundParams* P);
+int pt_history_select_check(const char* who, int w, int rows, const float* feature_planes, const uint8_t* emitter_geom, int num_geoms,
+                            const PtHistoryRoundOptions* opt, const int32_t* list, const int* fresh, const int* m, pthi::RoundParams* P, int* cap);
+int pt_history_merge_check(const char* who, int pixels, const float* rgb_sum, const float* extra, const int32_t* list, int m, const float* group_sum,
+                           int group_iters);
+int pt_history_check_extra(const char* who, int pixels, const float* extra);
+int pt_history_key_launch(hipStream_t stream, int pixels, const float* planes_dev, const void* current_dev, const uint8_t* emitter_dev, int num_geoms,
+                          float min_history, uint32_t* key_dev);
+int pt_history_merge_launch(hipStream_t stream, int pixels, float* rgb_sum_dev, float* extra_dev, const int32_t* list_dev, int m, const float* group_sum_dev,
+                            int group_iters);
+int pt_history_capture_counted_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, const float* planes_dev, const void* current_dev, float samples,
+                                      const float* extra_dev, void* kept_dev);
+int pt_history_capture_moments_counted_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, const float* planes_dev, const void* current_dev,
+                                              float samples, const float* extra_dev, void* kept_dev, const void* current_var_dev, void* kept_var_dev);
+int pt_history_blend_counted_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, float samples, const float* extra_dev, const void* current_dev,
+                                    float* rgb_avg_dev);

@@ -57,7 +57,7 @@ static int denoise_device(PtContext* c, const char* who, ptdn::Form form, float 
   const bool plain = form == ptdn::Form::Plain, adaptive = form == ptdn::Form::Adaptive;
   if (need(c, who)) return -1;
   Ctx& g = *c;
-  if (admit(g, who, kNotFailed | (adaptive ? 0u : kUniform) | kWholeRows)) return -1;
+  if (admit(g, who, kNotFailed | (adaptive ? 0u : kUniform) | kNoExtras | kWholeRows)) return -1;
   const int W = g.cam.resolution[0];
   if (!g.d_feat) return pt_fail("%s: no feature pass has been rendered (pt_render_features)", who);
   if (!plain) {
@@ -99,7 +99,7 @@ int pt_ctx_denoise_adaptive(PtContext* c, const PtDenoiseOptions* opt, float* rg
 int pt_ctx_noise_fold(PtContext* c) {
   if (need(c, "pt_noise_fold")) return -1;
   Ctx& g = *c;
-  if (admit(g, "pt_noise_fold", kNotFailed | kUniform)) return -1;
+  if (admit(g, "pt_noise_fold", kNotFailed | kUniform | kNoExtras)) return -1;
   const int64_t n = g.rendered - g.noise_iters;
   if (n <= 0) return 0;  // nothing rendered since the last fold
   HIP_OK(hipSetDevice(g.device));
@@ -142,7 +142,7 @@ int pt_ctx_render_until(PtContext* c, int iter_first, int max_iters, int group_i
   if (iter_first < 1 || max_iters < 1 || (int64_t)iter_first + max_iters - 1 > INT32_MAX || group_iters < 0 || !std::isfinite(target_db))
     return pt_fail("pt_render_until: iterations %d, +%d in groups of %d until %g dB: the first is >= 1, the count >= 1, the group >= 0 (0 = a batch), the target finite",
                 iter_first, max_iters, group_iters, (double)target_db);
-  if (admit(g, "pt_render_until", kNotFailed | kUniform)) return -1;
+  if (admit(g, "pt_render_until", kNotFailed | kUniform | kNoExtras)) return -1;
   const int group = group_iters ? group_iters : g.K;
   int done = 0;
   float psnr = -1.0f;
@@ -227,7 +227,7 @@ int render_list(Ctx& g, int iter_first, int iter_count) {
 static int adaptive_refusal(const Ctx& g, const char* who, int iter_first, int group_iters, const float* fraction_or_null, bool folds = true,
                             bool rows = true) {
   const float fraction = fraction_or_null ? *fraction_or_null : 1.0f;
-  if (admit(g, who, kNotFailed)) return -1;
+  if (admit(g, who, kNotFailed | kNoExtras)) return -1;  // (the history round's extras: the counts of a round are the folds')
   if (folds && (iter_first < 1 || group_iters < 1 || (int64_t)iter_first + group_iters - 1 > INT32_MAX))
     return pt_fail("%s: iterations %d, +%d: the first is >= 1, the group holds at least one", who, iter_first, group_iters);
   if (!folds && iter_first < 1) return pt_fail("%s: the first iteration %d is not >= 1", who, iter_first);
@@ -454,7 +454,7 @@ int pt_ctx_readback_adaptive(PtContext* c, int32_t* counts) {
 int pt_ctx_resolve_device(PtContext* c, const float** rgb_dev) {
   if (need(c, "pt_resolve")) return -1;
   Ctx& g = *c;
-  if (admit(g, "pt_resolve", kNotFailed)) return -1;
+  if (admit(g, "pt_resolve", kNotFailed | kNoExtras)) return -1;
   if (g.noise_groups < 1) return pt_fail("pt_resolve: nothing has been folded (pt_noise_fold): the sample counts are the folds'");
   if (admit(g, "pt_resolve", kFoldedAll)) return -1;
   if (g.noise_iters > INT32_MAX) return pt_fail("pt_resolve: %lld iterations folded", (long long)g.noise_iters);
@@ -509,7 +509,7 @@ static int history_capture(PtContext* c, const char* who, float samples, uint32_
   if (!g.d_feat || !g.feat_fresh) return pt_fail(kNoFeatures, who);
   if (pt_history_check_samples(who, samples)) return -1;
   const bool var = (flags & PT_HISTORY_VARIANCE) != 0, mom = (flags & PT_HISTORY_MOMENTS) != 0;
-  if (var && (history_folds(g, who, samples) || history_current_variance(g, who))) return -1;
+  if (var && (admit(g, who, kNoExtras) || history_folds(g, who, samples) || history_current_variance(g, who))) return -1;
   if (mom && history_current_moments(g, who)) return -1;
   HIP_OK(hipSetDevice(g.device));
   if (ensure(g, g.d_hist, pt_history_state_bytes((size_t)g.N), Zero::on_stream)) return -1;  // the first capture of the context
@@ -521,9 +521,13 @@ static int history_capture(PtContext* c, const char* who, float samples, uint32_
                                            static_cast<const float*>(g.d_noise), f.Tf, f.Df, current ? history_var_plane(g, 1) : nullptr, history_var_plane(g, 0)))
       return -1;
   } else if (mom) {
-    if (pt_history_capture_moments_launch(g.stream, g.N, g.d_image, reinterpret_cast<const float*>(g.d_feat), current, samples, g.d_hist,
-                                          current ? history_var_plane(g, 1) : nullptr, history_var_plane(g, 0)))
+    if (g.hist_extra ? pt_history_capture_moments_counted_launch(g.stream, g.N, g.d_image, reinterpret_cast<const float*>(g.d_feat), current, samples,
+                                                                 g.d_hist_extra, g.d_hist, current ? history_var_plane(g, 1) : nullptr, history_var_plane(g, 0))
+                     : pt_history_capture_moments_launch(g.stream, g.N, g.d_image, reinterpret_cast<const float*>(g.d_feat), current, samples, g.d_hist,
+                                                         current ? history_var_plane(g, 1) : nullptr, history_var_plane(g, 0)))
       return -1;
+  } else if (g.hist_extra) {  // counted: ns = samples + E_p
+    if (pt_history_capture_counted_launch(g.stream, g.N, g.d_image, reinterpret_cast<const float*>(g.d_feat), current, samples, g.d_hist_extra, g.d_hist)) return -1;
   } else if (pt_history_capture_launch(g.stream, g.N, g.d_image, reinterpret_cast<const float*>(g.d_feat), current, samples, g.d_hist)) {
     return -1;
   }
@@ -591,7 +595,7 @@ int pt_ctx_history_reproject_ex(PtContext* c, const PtHistoryOptions* opt, uint3
 // ---- the guided filter over the blend (ptdn::Form::History) --------------------------------------------------------------
 // Everything pt_history_denoise refuses but the null buffer, in its order; the job resolved.
 static int history_denoise_refusal(const Ctx& g, const char* who, float samples, const PtDenoiseOptions* opt, ptdn::Job* j) {
-  if (history_admit(g, who)) return -1;
+  if (history_admit(g, who) || admit(g, who, kNoExtras)) return -1;  // (the fold's variance knows nothing of the extras)
   if (!g.d_feat || !g.feat_fresh) return pt_fail(kNoFeatures, who);
   if (pt_history_check_samples(who, samples)) return -1;
   ptdn::Params P{};
@@ -657,6 +661,7 @@ int pt_ctx_history_denoise_ex_device(PtContext* c, float samples, const PtDenois
     j.div.C = reinterpret_cast<const ptdn::V4*>(history_plane(g, pthi::kKeptPlanes));
     j.div.VC = reinterpret_cast<const ptdn::V4*>(history_var_plane(g, 1));
   }
+  j.div.E = g.hist_extra ? g.d_hist_extra : nullptr;  // counted: the prepare reads ns = samples + E_p
   return pt_denoise_launch(g.stream, j, g.d_denoise, rgb_dev);
 }
 int pt_ctx_history_denoise_ex(PtContext* c, float samples, const PtDenoiseOptions* opt, uint32_t flags, float* rgb_avg_host) {
@@ -676,7 +681,10 @@ int pt_ctx_history_resolve_device(PtContext* c, float samples, const float** rgb
   if (!rgb_dev) return pt_fail("pt_history_resolve: null buffer");
   HIP_OK(hipSetDevice(g.device));
   if (ensure(g, g.d_resolved, 3 * (size_t)g.N * sizeof(float))) return -1;
-  if (pt_history_blend_launch(g.stream, g.N, g.d_image, samples, g.hist_current ? history_plane(g, pthi::kKeptPlanes) : nullptr, g.d_resolved)) return -1;
+  const pthi::V4* current = g.hist_current ? history_plane(g, pthi::kKeptPlanes) : nullptr;
+  if (g.hist_extra ? pt_history_blend_counted_launch(g.stream, g.N, g.d_image, samples, g.d_hist_extra, current, g.d_resolved)
+                   : pt_history_blend_launch(g.stream, g.N, g.d_image, samples, current, g.d_resolved))
+    return -1;
   *rgb_dev = g.d_resolved;
   return 0;
 }
@@ -711,6 +719,73 @@ int pt_ctx_readback_history_variance(PtContext* c, float* kept_var, float* curre
   if (kept_var && !kept) std::fill(kept_var, kept_var + 4 * (size_t)g.N, 0.0f);
   if (current_var && !current) std::fill(current_var, current_var + 4 * (size_t)g.N, 0.0f);
   return 0;
+}
+
+// ---- the history round: a group of further iterations for the pixels whose history is short --------------------------------
+// emitter_geom of pt_amd.h from the tables the renderer holds, as history_reject_table.  Blocking; once per context.
+static int history_emitter_table(Ctx& g) {
+  if (g.d_hist_emitter) return 0;
+  std::vector<ptd::Mat> mats((size_t)std::max(g.scene.num_mats, 0));
+  if (!mats.empty()) HIP_OK(hipMemcpy(mats.data(), g.scene.mats, mats.size() * sizeof(ptd::Mat), hipMemcpyDeviceToHost));
+  const std::vector<PtGeom>& geoms = g.camera_base.geoms;
+  std::vector<uint8_t> emitter(std::max<size_t>(geoms.size(), 1), 0);
+  for (size_t i = 0; i < geoms.size(); ++i) {
+    const int32_t m = geoms[i].materialid;
+    emitter[i] = m >= 0 && (size_t)m < mats.size() && mats[(size_t)m].emittance > 0.0f ? 1 : 0;
+  }
+  if (ensure(g, g.d_hist_emitter, emitter.size())) return -1;
+  HIP_OK(hipMemcpy(g.d_hist_emitter, emitter.data(), emitter.size(), hipMemcpyHostToDevice));
+  return 0;
+}
+
+int pt_ctx_history_round(PtContext* c, int iter_first, int group_iters, const PtHistoryRoundOptions* opt, int* fresh, int* selected) {
+  const char* who = "pt_history_round";
+  if (need(c, who)) return -1;
+  Ctx& g = *c;
+  if (admit(g, who, kNotFailed)) return -1;
+  if (iter_first < 1 || group_iters < 1 || (int64_t)iter_first + group_iters - 1 > INT32_MAX)
+    return pt_fail("%s: iterations %d, +%d: the first is >= 1, the group holds at least one", who, iter_first, group_iters);
+  if (g.conv) return pt_fail("%s: the renderer was created with PtOptions.convergence = %d; the convergence metric follows whole iterations", who, g.conv);
+  if (admit(g, who, kWholeRows) || admit(g, who, kUniform)) return -1;
+  if (!g.d_feat || !g.feat_fresh) return pt_fail(kNoFeatures, who);
+  pthi::RoundParams P{};
+  if (pt_history_round_options(who, opt, &P)) return -1;
+  HIP_OK(hipSetDevice(g.device));
+  const int W = g.cam.resolution[0];
+  const int cap = ptad::list_length((double)P.max_fraction, g.N);
+  if (history_emitter_table(g) || ensure(g, g.d_select, pt_adaptive_select_bytes((size_t)g.N)) || ensure_worker(g, cap)) return -1;
+  // key and select; the two counts read back (8 bytes and ONE synchronise: the list's length decides the launches that follow)
+  if (pt_history_key_launch(g.stream, g.N, reinterpret_cast<const float*>(g.d_feat), g.hist_current ? history_plane(g, pthi::kKeptPlanes) : nullptr,
+                            g.d_hist_emitter, (int)g.camera_base.geoms.size(), P.min_history, pt_adaptive_select_keys(g.d_select, (size_t)g.N)))
+    return -1;
+  if (pt_adaptive_select_threshold_keys_launch(g.stream, W, g.N / W, 0.0f, cap, g.d_select, g.d_list)) return -1;
+  uint32_t result[2] = {0u, 0u};  // fresh, m
+  HIP_OK(hipMemcpyAsync(result, pt_adaptive_select_result(g.d_select, (size_t)g.N), sizeof(result), hipMemcpyDeviceToHost, g.stream));
+  HIP_OK(hipStreamSynchronize(g.stream));
+  const int m = (int)result[1];
+  if (m < 0 || m > cap || (int)result[0] < m) return pt_fail("%s: the selection left %u fresh, a list of %u (cap %d)", who, result[0], result[1], cap);
+  if (fresh) *fresh = (int)result[0];
+  if (selected) *selected = m;
+  if (m == 0) return 0;  // nothing rendered, merged or allocated; E keeps its state
+  if (ensure(g, g.d_hist_extra, (size_t)g.N * sizeof(float), Zero::on_stream)) return -1;  // the first round that renders (pt_clear zeroes it from then on)
+  set_worker_live(*g.worker, m);
+  if (render_list(g, iter_first, group_iters)) return -1;
+  if (pt_history_merge_launch(g.stream, g.N, g.d_image, g.d_hist_extra, g.d_list, m, g.worker->d_image, group_iters)) return -1;
+  g.hist_extra = true;
+  g.samples += (int64_t)group_iters * m;
+  return 0;
+}
+
+int pt_ctx_readback_history_extra(PtContext* c, float* extra_host) {
+  if (need(c, "pt_readback_history_extra")) return -1;
+  Ctx& g = *c;
+  if (!extra_host) return pt_fail("pt_readback_history_extra: null buffer");
+  if (!g.hist_extra) {
+    if (pt_ctx_sync(c)) return -1;
+    std::fill(extra_host, extra_host + (size_t)g.N, 0.0f);
+    return 0;
+  }
+  return copy_out(c, "pt_readback_history_extra", extra_host, 1, [&](const float** d) { return *d = g.d_hist_extra, 0; });
 }
 
 int pt_ctx_history_drop(PtContext* c) {

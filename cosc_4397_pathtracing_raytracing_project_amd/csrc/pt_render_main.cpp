@@ -3,7 +3,7 @@
 // state.iterations iterations, write the PNG saveImage() would write.  Flags exist only because
 // the reference takes resolution, iteration count and depth from the scene file (scene.cpp:103-114).
 //
-//   pt_render SCENE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] [--orbit N [--device-tables] [--reproject [--history-cap C] [--denoise-history [--history-moments]]]]
+//   pt_render SCENE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] [--orbit N [--device-tables] [--reproject [--history-cap C] [--denoise-history [--history-moments]] [--history-extra G [--history-min M] [--history-extra-cap F]]]]
 //                       [--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa]
 //                       [--preview N] [--convergence N | --reference FILE.pfm] [--clean-db X] [--features]
 //                       [--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]]
@@ -70,6 +70,11 @@
 // capture carry the history's moments instead (PT_HISTORY_MOMENTS), the filter is pt_history_denoise_ex with them, and a frame is one
 // pt_render call without folds; the same output names.  --history-cap C: PtHistoryOptions.cap (default 32).  Prints per frame
 // `history: frame f: <valid> of <pixels> pixels carried, mean weight <x>`.
+// --history-extra G (with --reproject, alone or with --denoise-history --history-moments; refused with --denoise-history alone, whose
+// variance comes from the folds and knows nothing of extra samples): between the lookup and the resolve pt_history_round gives the
+// pixels whose carried weight is below --history-min M (default 4) G further iterations, --history-extra-cap F of the frame at the
+// most (default 1); resolve, filter and capture then count them per pixel.  Frame f takes spp + G iteration numbers: the uniform ones
+// f (spp + G) + 1 .., then G for the round.  Prints per frame `history: frame f: <G> extra over <m> of <fresh> fresh pixels`.
 // Output name: PREFIX.<spp>samp.png, or with --stamp the reference's own
 // <FILE>.<UTC start time>.<spp>samp.png (main.cpp:99-102).
 #include <hip/hip_runtime.h>
@@ -91,7 +96,7 @@
 int main(int argc, char** argv) {
   if (argc < 2) {
     std::printf("Usage: %s SCENEFILE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] "
-                "[--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa] [--orbit N [--device-tables] [--reproject [--history-cap C] [--denoise-history [--history-moments]]]] [--preview N] "
+                "[--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa] [--orbit N [--device-tables] [--reproject [--history-cap C] [--denoise-history [--history-moments]] [--history-extra G [--history-min M] [--history-extra-cap F]]]] [--preview N] "
                 "[--convergence N | --reference FILE.pfm] [--clean-db X] [--features] "
                 "[--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]] [--denoise-guided] [--until-db X [--until-group G] [--adaptive F [--denoise-adaptive]]] "
                 "[--adaptive-threshold E [--adaptive-cap F] [--adaptive-min-pixels P] [--until-group G] [--denoise-adaptive]]\n", argv[0]);
@@ -108,6 +113,9 @@ int main(int argc, char** argv) {
   bool hist_moments = false;                        // --history-moments
   float history_cap = 0.0f;                         // --history-cap C (0: the default)
   bool history_cap_given = false;
+  int history_extra = 0;                            // --history-extra G (0: no rounds)
+  PtHistoryRoundOptions round_opt{};                // --history-min M, --history-extra-cap F (0: the defaults)
+  bool history_min_given = false, history_extra_cap_given = false;
   bool until = false, until_group_given = false;
   float clean_db = 35.0f, until_db = 0.0f, adaptive = 0.0f;  // adaptive > 0: --adaptive F
   float threshold = 0.0f, threshold_cap = 0.25f;           // --adaptive-threshold E, --adaptive-cap F
@@ -139,6 +147,31 @@ int main(int argc, char** argv) {
       history_cap_given = true;
       if (!std::isfinite(history_cap) || !(history_cap > 0.0f)) {
         std::fprintf(stderr, "--history-cap wants the most samples a carried colour counts for, a positive number\n");
+        return 1;
+      }
+    }
+    else if (!std::strcmp(argv[i], "--history-extra") && i + 1 < argc) {
+      char* end = nullptr;
+      const long v = std::strtol(argv[++i], &end, 10);
+      if (end == argv[i] || *end || v < 1 || v > 4096) {
+        std::fprintf(stderr, "--history-extra wants the iterations a pixel with a short history gets on top, 1 to 4096\n");
+        return 1;
+      }
+      history_extra = (int)v;
+    }
+    else if (!std::strcmp(argv[i], "--history-min") && i + 1 < argc) {
+      round_opt.min_history = (float)std::atof(argv[++i]);
+      history_min_given = true;
+      if (!std::isfinite(round_opt.min_history) || !(round_opt.min_history > 0.0f)) {
+        std::fprintf(stderr, "--history-min wants the carried samples below which a pixel gets extra ones, a positive number\n");
+        return 1;
+      }
+    }
+    else if (!std::strcmp(argv[i], "--history-extra-cap") && i + 1 < argc) {
+      round_opt.max_fraction = (float)std::atof(argv[++i]);
+      history_extra_cap_given = true;
+      if (!(round_opt.max_fraction > 0.0f && round_opt.max_fraction <= 1.0f)) {
+        std::fprintf(stderr, "--history-extra-cap wants the largest share of the frame a round may render, in (0, 1]\n");
         return 1;
       }
     }
@@ -328,6 +361,18 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--reproject goes with --orbit N (it carries the image from view to view), --history-cap C with --reproject\n");
     return 1;
   }
+  if ((history_min_given || history_extra_cap_given) && !history_extra) {
+    std::fprintf(stderr, "--history-min and --history-extra-cap go with --history-extra G\n");
+    return 1;
+  }
+  if (history_extra && (orbit <= 0 || !reproject)) {
+    std::fprintf(stderr, "--history-extra wants --orbit N --reproject (it gives extra samples to the pixels whose reprojected history is short)\n");
+    return 1;
+  }
+  if (history_extra && dn_history && !hist_moments) {
+    std::fprintf(stderr, "--history-extra excludes --denoise-history without --history-moments: the folds' variance knows nothing of the extra samples\n");
+    return 1;
+  }
   if (reproject && (gpus >= 0 || !device_list.empty())) {
     std::fprintf(stderr, "--reproject excludes --gpus / --devices: a context's interleaved rows cannot look up their neighbours in the previous view\n");
     return 1;
@@ -476,14 +521,18 @@ int main(int argc, char** argv) {
     PtHistoryOptions hopt{};
     hopt.cap = history_cap;
     if (reproject) {
-      if ((int64_t)orbit * iters > INT32_MAX) {
+      if ((int64_t)orbit * (iters + history_extra) > INT32_MAX) {
         std::fprintf(stderr, "--reproject: %d frames of %d iterations run out of iteration numbers\n", orbit, iters);
         return 1;
       }
       carried.resize((size_t)W * H * 3);
       current.resize((size_t)W * H * 4);
       if (dn_history) filtered.resize((size_t)W * H * 3);
-      std::printf("history: frame f renders iterations f * %d + 1 .. (f + 1) * %d, not 1 .. %d: repeated iteration numbers would repeat the paths\n", iters, iters, iters);
+      if (history_extra)
+        std::printf("history: frame f renders iterations f * %d + 1 .. f * %d + %d, then %d more for the pixels whose history is short\n", iters + history_extra,
+                    iters + history_extra, iters, history_extra);
+      else
+        std::printf("history: frame f renders iterations f * %d + 1 .. (f + 1) * %d, not 1 .. %d: repeated iteration numbers would repeat the paths\n", iters, iters, iters);
     }
     const float step = (float)(2.0 * 3.14159265358979323846 / orbit);
     for (int f = 0; f < orbit; ++f) {
@@ -505,7 +554,7 @@ int main(int argc, char** argv) {
         }
       }
       const auto t0 = std::chrono::high_resolution_clock::now();
-      const int iter_first = reproject ? f * iters + 1 : 1;
+      const int iter_first = reproject ? f * (iters + history_extra) + 1 : 1;
       bool render_failed = false;
       if (dn_history && !hist_moments) {  // the view's iterations in groups of ceil(spp / 4), a fold after each: the variance of the view's own samples
         for (int done = 0; done < iters && !render_failed; done += fold_group)
@@ -532,7 +581,9 @@ int main(int argc, char** argv) {
       if (hdr && pt_save_hdr((frame + ".hdr").c_str(), scene->state.image.data(), W, H, (float)iters) == 0) std::printf("Saved %s.hdr.\n", frame.c_str());
       if (reproject) {  // the view's first hits, the history looked up from them, the blend written, the blend kept for the next view
         const uint32_t hflags = !dn_history ? 0u : hist_moments ? PT_HISTORY_MOMENTS : PT_HISTORY_VARIANCE;  // 0: the plain calls
-        if (pt_render_features(1, 1) || (f > 0 && pt_history_reproject_ex(&hopt, hflags)) || pt_history_resolve((float)iters, carried.data()) ||
+        int fresh = 0, selected = 0;  // --history-extra: the round, between the lookup and the resolve
+        if (pt_render_features(1, 1) || (f > 0 && pt_history_reproject_ex(&hopt, hflags)) ||
+            (history_extra && pt_history_round(iter_first + iters, history_extra, &round_opt, &fresh, &selected)) || pt_history_resolve((float)iters, carried.data()) ||
             (dn_history && (hist_moments ? pt_history_denoise_ex((float)iters, &dn_opt, PT_HISTORY_MOMENTS, filtered.data())
                                          : pt_history_denoise((float)iters, &dn_opt, filtered.data()))) || pt_history_capture_ex((float)iters, hflags) ||
             pt_readback_history(nullptr, current.data())) {
@@ -544,6 +595,7 @@ int main(int argc, char** argv) {
         for (size_t p = 0; p < (size_t)W * H; ++p)
           if (current[4 * p + 3] > 0.0f) valid += 1, weight += (double)current[4 * p + 3];
         std::printf("history: frame %d: %zu of %zu pixels carried, mean weight %.3f\n", f, valid, (size_t)W * H, valid ? weight / (double)valid : 0.0);
+        if (history_extra) std::printf("history: frame %d: %d extra over %d of %d fresh pixels\n", f, history_extra, selected, fresh);
         if (pt_save_png((frame + ".reprojected.png").c_str(), carried.data(), W, H, 1.0f) == 0) std::printf("Saved %s.reprojected.png.\n", frame.c_str());
         if (pfm && pt_save_pfm((frame + ".reprojected.pfm").c_str(), carried.data(), W, H, 1.0f) == 0) std::printf("Saved %s.reprojected.pfm.\n", frame.c_str());
         if (dn_history) {  // the history keeps the unfiltered blend: the filtered one is written, not fed back

@@ -481,6 +481,59 @@ int pt_stage_adaptive_select_threshold(int w, int rows, const float* noise_plane
   return 0;
 }
 
+// The history round's key and selection on caller-supplied host arrays (pt_history_select_host's arguments): the key kernel writes into
+// the selection's workspace, the selection is the round's own launch.
+int pt_stage_history_select(int w, int rows, const float* feature_planes, const float* current_plane, const uint8_t* emitter_geom, int num_geoms,
+                            const PtHistoryRoundOptions* opt, int32_t* list, int* fresh, int* m) {
+  const char* who = "pt_stage_history_select";
+  if (need(default_context(), who)) return -1;
+  Ctx& g = *default_context();
+  pthi::RoundParams P{};
+  int cap = 0;
+  if (pt_history_select_check(who, w, rows, feature_planes, emitter_geom, num_geoms, opt, list, fresh, m, &P, &cap)) return -1;
+  if (rows >= 32768) return pt_fail("%s: a tile of %d x %d pixels is not supported", who, w, rows);
+  HIP_OK(hipSetDevice(g.device));
+  Scratch sc;
+  const size_t n = (size_t)w * rows;
+  float *d_feat = nullptr, *d_cur = nullptr;
+  uint8_t* d_emitter = nullptr;
+  char* d_ws = sc.get<char>(pt_adaptive_select_bytes(n));
+  int32_t* d_list = sc.get<int32_t>((size_t)cap);
+  if (!d_ws || !d_list) return pt_fail("%s: out of device memory", who);
+  if (device_copy(sc, who, feature_planes, 4 * PT_FEATURE_PLANES * n, &d_feat)) return -1;
+  if (current_plane && device_copy(sc, who, current_plane, 4 * n, &d_cur)) return -1;
+  if (num_geoms > 0 && device_copy(sc, who, emitter_geom, (size_t)num_geoms, &d_emitter)) return -1;
+  HIP_OK(hipMemset(d_list, 0xff, (size_t)cap * sizeof(int32_t)));  // an entry nobody wrote shows as -1
+  if (pt_history_key_launch(g.stream, (int)n, d_feat, d_cur, d_emitter, num_geoms, P.min_history, pt_adaptive_select_keys(d_ws, n))) return -1;
+  if (pt_adaptive_select_threshold_keys_launch(g.stream, w, rows, 0.0f, cap, d_ws, d_list)) return -1;
+  HIP_OK(hipStreamSynchronize(g.stream));
+  uint32_t result[2] = {0u, 0u};
+  HIP_OK(hipMemcpy(result, pt_adaptive_select_result(d_ws, n), sizeof(result), hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(list, d_list, (size_t)cap * sizeof(int32_t), hipMemcpyDeviceToHost));  // all cap entries: those behind m must still be -1
+  *fresh = (int)result[0], *m = (int)result[1];
+  return 0;
+}
+
+// ... and its merge (pt_history_merge_host's arguments): rgb_sum and extra go up, through the kernel and come back.
+int pt_stage_history_merge(int pixels, float* rgb_sum, float* extra, const int32_t* list, int m, const float* group_sum, int group_iters) {
+  const char* who = "pt_stage_history_merge";
+  if (need(default_context(), who)) return -1;
+  Ctx& g = *default_context();
+  if (pt_history_merge_check(who, pixels, rgb_sum, extra, list, m, group_sum, group_iters)) return -1;
+  HIP_OK(hipSetDevice(g.device));
+  Scratch sc;
+  float *d_img = nullptr, *d_extra = nullptr, *d_sw = nullptr;
+  int32_t* d_list = nullptr;
+  if (device_copy(sc, who, rgb_sum, 3 * (size_t)pixels, &d_img) || device_copy(sc, who, extra, (size_t)pixels, &d_extra) ||
+      device_copy(sc, who, group_sum, 3 * (size_t)m, &d_sw) || device_copy(sc, who, list, (size_t)m, &d_list))
+    return -1;
+  if (pt_history_merge_launch(g.stream, pixels, d_img, d_extra, d_list, m, d_sw, group_iters)) return -1;
+  HIP_OK(hipStreamSynchronize(g.stream));
+  HIP_OK(hipMemcpy(rgb_sum, d_img, 3 * (size_t)pixels * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(extra, d_extra, (size_t)pixels * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
 // The partition's kernels on caller-supplied host arrays (pt_group_partition_host's arguments).  The list's length reaches the kernels
 // as it does in a group's round: in the second of two words on the device.
 int pt_stage_group_partition(int w, int h, int n, const int32_t* list, int m, int32_t* parts, int32_t* counts) {

@@ -787,7 +787,8 @@ int pt_denoise_adaptive_variance_host(int w, int rows, const float* rgb_sum, con
  * The defaults are those of a CPU simulation on the cornell box (tests/test_history_sim.py; README "Reprojected history" has its
  * figures).  The bilinear lookup also smooths: the carried image is a BIASED estimator, and nothing here corrects that.
  * Out of scope: pt_group_* (a context's interleaved rows cannot look up their neighbours); feeding the history into the noise
- * estimate or adaptive sampling; motion of anything but the camera.  (The filter over the blend: "variance of the history" below.) */
+ * estimate; a selection key that uses the carried variance; motion of anything but the camera.  (The filter over the blend: "variance of
+ * the history" below; extra samples for short histories: "the history round" below.) */
 #define PT_HISTORY_KEPT_PLANES 3
 typedef struct PtHistoryOptions { /* every field: 0 = the default */
   float cap;                   /* default 32: the most samples a carried colour counts for; finite and > 0                 */
@@ -928,8 +929,8 @@ int pt_history_denoise_host(int w, int rows, const float* rgb_sum, const float* 
  * C present with VC absent or of the variance kind; a null buffer.
  * What it buys: README "Moments with the history" (tests/test_history_moments_sim.py on the CPU, tests/test_gpu_history_moments.py on
  * an MI355X, the same digits).  One scene, one orbit: no claim beyond it.
- * Out of scope: feeding the FILTERED image back into the history; pt_group_*; feeding the history into the noise estimate or
- * adaptive sampling; a luminance-only variant; motion of anything but the camera. */
+ * Out of scope: feeding the FILTERED image back into the history; pt_group_*; feeding the history into the noise estimate; a
+ * luminance-only variant; motion of anything but the camera.  (Extra samples for the marked pixels: "the history round" below.) */
 #define PT_HISTORY_MOMENTS 2u
 #define PT_HISTORY_MOMENTS_R_MAX 0.3f /* four equal views or more (r = 1/4): the literature's history length 4 */
 int pt_history_denoise_ex(float samples, const PtDenoiseOptions* opt, uint32_t flags, float* rgb_avg_host); /* synchronises */
@@ -944,6 +945,74 @@ int pt_history_reproject_moments_host(int w, int rows, int row0, const PtCamera*
  * bytes: 1 where prepare marked the pixel) are optional outputs; with one of them rgb_avg may be NULL, and no level runs. */
 int pt_history_denoise_moments_host(int w, int rows, const float* rgb_sum, const float* planes, float samples, const float* current_plane,
                                     const float* current_var, const PtDenoiseOptions* opt, float* rgb_avg, float* var_raw, uint8_t* mark);
+
+/* ---- the history round: extra samples for the pixels whose history is short.  After the lookup, the pixels whose carried weight
+ * Th = C.w is below min_history get a group of further iterations, for those pixels alone; blend, capture and the moments filter then
+ * count these samples per pixel.  A capture writes K0.w = samples_p + Th, so a pixel that received extras is no longer short at the
+ * next view: the round limits itself (but for the pixels of reflective geoms, which carry nothing and are selected at every view).
+ * Opt-in: a renderer that never calls these functions allocates and launches nothing new, and every other call keeps its kernels,
+ * memory, launches, results and refusals.  Specified like the rest of the history: float32, separate IEEE operations in the order
+ * written, one implementation for kernels and host loops, the same bits in all three PT_ARITH_* builds, host and device.
+ * State:
+ *   E, the extra plane: pixel_count floats; E_p = the extra samples the SUM image holds for pixel p beyond the uniform `samples`.
+ *        The first round that renders something allocates and zeroes it (PtStats.device_bytes counts it from then on); it is
+ *        "present" from that round until pt_clear or pt_set_camera[_ex], which zero it and make it absent (S is zero then too).
+ *        pt_history_drop leaves it: E belongs to S, not to K.
+ *   emitter_geom: one byte per geom, materials[geoms[g].materialid].emittance > 0; the first round builds it.  An emitter seen
+ *        directly has the same colour in every sample, so extra samples there buy nothing.
+ *   the selection workspace and the worker of the adaptive rounds (pt_adaptive_round_threshold).
+ * key (one thread per tile pixel; s1, s2 the feature sums, C the current plane — absent reads as Th = +0):
+ *        hit = s1.w > 0;  id = bits(s2.w)
+ *        key = +0 if !hit, or id outside 1 .. num_geoms, or emitter_geom[id - 1] != 0
+ *        else Th = C.w;  d = min_history - Th;  key = d > 0 ? d : +0
+ *        stored as its uint32 bit pattern.  A pixel is FRESH when bits(key) > 0.
+ * select: pt_adaptive_round_threshold's selection on these keys with threshold bits 0 and cap = clamp(ceil((double)max_fraction * N), 1, N):
+ *        fresh = #{key > 0}, m = min(fresh, cap); the list holds the m fresh pixels with the largest keys (the shortest histories),
+ *        equal keys by the smaller tile index, in ascending tile index.  The two counts are read back: 8 bytes and ONE synchronise.
+ * render: the worker, kept for cap pixels and live for m, renders iterations iter_first .. iter_first + G - 1 of the listed pixels
+ *        into its cleared group sum Sw[m][3].  m == 0: nothing is rendered, merged or allocated beyond the selection; E keeps its state.
+ * merge (one thread per list entry), p = list[i]:  S_p.k = S_p.k + Sw[i].k per component;  E_p = E_p + (float)G.  Pixels outside the
+ *        list keep every word.  PtStats.samples grows by G * m.
+ * Counted forms: while E is present, pt_history_resolve, pt_history_capture, pt_history_capture_ex with PT_HISTORY_MOMENTS and
+ *        pt_history_denoise_ex with PT_HISTORY_MOMENTS use ns = samples + E_p — one float add per pixel, made before anything else —
+ *        wherever their specification says `samples`: d = ns + Th, K0.w = ns + Th, x_k = S_k / ns, wn = ns / (ns + Th),
+ *        wh = Th / (ns + Th), and the filter's prepare.  Kernel instantiations of their own; with E absent the ones that run are those
+ *        that ran before.  With E all zero the counted forms give the uncounted results bit for bit.
+ * While E is present, what reads S as a uniform SUM refuses with a message that names the function, pt_history_resolve and
+ *        pt_clear, nothing allocated or launched: pt_noise_fold, pt_render_until, pt_denoise, pt_denoise_guided, pt_denoise_adaptive,
+ *        pt_history_denoise, pt_history_denoise_ex with flags 0, pt_history_capture_ex with PT_HISTORY_VARIANCE (the fold's variance
+ *        knows nothing of the extras), every adaptive round and driver, pt_resolve, pt_save_u8*, pt_preview_rgba8*.  These keep
+ *        working: pt_render, pt_readback, pt_render_features, the lookups, pt_get_stats.
+ * pt_history_round refuses, in this order, nothing allocated or launched: no renderer or a failed context; iter_first < 1,
+ *        group_iters < 1 or iterations past 2^31 - 1; PtOptions.convergence != 0; a striped or ragged tile; the adaptive state; no
+ *        feature pass since the last clear or move; an option that is not finite or out of range.  It needs no capture and no
+ *        lookup: with C absent every non-emitter hit pixel is fresh (the first view).  fresh / selected may be NULL.
+ * What it buys: README "History-guided sampling" (tests/test_history_round_sim.py).
+ * Out of scope: pt_group_*; feeding the history into the noise estimate; scaling the spatial variance estimate by a pixel's extras;
+ * a key that uses rh or the carried variance; motion of anything but the camera. */
+#define PT_HISTORY_ROUND_MIN_HISTORY 4.0f /* the default of PtHistoryRoundOptions.min_history, in samples */
+typedef struct PtHistoryRoundOptions { /* every field: 0 = the default */
+  float min_history;  /* default 4.0 (samples): finite and > 0 */
+  float max_fraction; /* default 1.0; in (0, 1] */
+} PtHistoryRoundOptions;
+int pt_history_round(int iter_first, int group_iters, const PtHistoryRoundOptions* opt, int* fresh, int* selected);
+int pt_readback_history_extra(float* extra_host); /* pixel_count floats, zeros while E is absent; synchronises */
+/* The same arithmetic on the host (no GPU); the device results equal these bit for bit.  list: cap = clamp(ceil(max_fraction * w * rows),
+ * 1, w * rows) entries, of which the first *m are written.  current_plane may be NULL (absent); emitter_geom may be NULL when num_geoms == 0. */
+int pt_history_select_host(int w, int rows, const float* feature_planes, const float* current_plane, const uint8_t* emitter_geom, int num_geoms,
+                           const PtHistoryRoundOptions* opt, int32_t* list, int* fresh, int* m);
+/* list: m >= 1 distinct tile pixels; group_sum: m * 3 floats in list order; rgb_sum and extra are updated in place. */
+int pt_history_merge_host(int pixels, float* rgb_sum, float* extra, const int32_t* list, int m, const float* group_sum, int group_iters);
+/* The counted twins of pt_history_blend_host, pt_history_capture_host, pt_history_capture_moments_host and
+ * pt_history_denoise_moments_host: the same arguments and `extra`, pixels (w * rows) floats, finite and >= 0. */
+int pt_history_blend_counted_host(int pixels, const float* rgb_sum, float samples, const float* extra, const float* current_plane, float* rgb_avg);
+int pt_history_capture_counted_host(int pixels, const float* rgb_sum, const float* feature_planes, const float* current_plane, float samples,
+                                    const float* extra, float* kept_planes);
+int pt_history_capture_moments_counted_host(int pixels, const float* rgb_sum, float samples, const float* extra, const float* current_plane,
+                                            const float* current_var, float* kept_var);
+int pt_history_denoise_moments_counted_host(int w, int rows, const float* rgb_sum, const float* planes, float samples, const float* extra,
+                                            const float* current_plane, const float* current_var, const PtDenoiseOptions* opt, float* rgb_avg,
+                                            float* var_raw, uint8_t* mark);
 
 /* saveImage()'s per-pixel conversion (main.cpp:91-97 x mirror, image.cpp:26-30 clamp * 255 truncated) on the
  * device: pixel_count*3 bytes, row-major, x mirrored inside each row; the tile must consist of whole rows.
@@ -1014,6 +1083,8 @@ int pt_ctx_history_denoise_device(PtContext* c, float samples, const PtDenoiseOp
 int pt_ctx_readback_history_variance(PtContext* c, float* kept_var, float* current_var);
 int pt_ctx_history_denoise_ex(PtContext* c, float samples, const PtDenoiseOptions* opt, uint32_t flags, float* rgb_avg_host);
 int pt_ctx_history_denoise_ex_device(PtContext* c, float samples, const PtDenoiseOptions* opt, uint32_t flags, const float** rgb_dev); /* as pt_ctx_denoise_device */
+int pt_ctx_history_round(PtContext* c, int iter_first, int group_iters, const PtHistoryRoundOptions* opt, int* fresh, int* selected);
+int pt_ctx_readback_history_extra(PtContext* c, float* extra_host);
 const float* pt_ctx_device_noise(PtContext* c); /* device pointer of plane 0; the planes are contiguous; NULL before the first fold */
 const float* pt_ctx_device_features(PtContext* c); /* device pointer of plane 0; the planes are contiguous; NULL before the first pt_ctx_render_features */
 const float* pt_ctx_device_image(PtContext* c); /* device pointer of the tile SUM image */
@@ -1206,6 +1277,12 @@ int pt_stage_history_reproject_moments(int w, int rows, int row0, const PtCamera
                                        float* current_var);
 int pt_stage_history_denoise_moments(int w, int rows, const float* rgb_sum, const float* planes, float samples, const float* current_plane,
                                      const float* current_var, const PtDenoiseOptions* opt, float* rgb_avg);
+/* The history round's key and selection, and its merge, through the device kernels on caller-supplied host arrays
+ * (pt_history_select_host's and pt_history_merge_host's arguments; rows < 32768).  list: all cap entries are returned, those behind
+ * *m are -1. */
+int pt_stage_history_select(int w, int rows, const float* feature_planes, const float* current_plane, const uint8_t* emitter_geom, int num_geoms,
+                            const PtHistoryRoundOptions* opt, int32_t* list, int* fresh, int* m);
+int pt_stage_history_merge(int pixels, float* rgb_sum, float* extra, const int32_t* list, int m, const float* group_sum, int group_iters);
 
 /* ---- image output (src/image.cpp:22-45, src/main.cpp:86-107) ------------- */
 /* rgb_sum: W*H*3 floats (raw orientation); writes <path> as 8-bit PNG of
