@@ -112,9 +112,14 @@ class PtSetCameraTimes(C.Structure):
     _fields_ = [("tables_ms", C.c_double), ("rearm_ms", C.c_double), ("total_ms", C.c_double), ("path", C.c_int32), ("fallback", C.c_int32)]
 
 
+class PtSetGeomsTimes(C.Structure):
+    """Host wall-clock times of a renderer's last pt_set_geoms, ms (include/pt_amd.h: pt_get_set_geoms_times)."""
+    _fields_ = [("build_ms", C.c_double), ("upload_ms", C.c_double), ("rearm_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 PT_SET_CAMERA_DEVICE_TABLES = 1
 PT_DEVICE_TABLES_LIST, PT_DEVICE_TABLES_CELLS = 1, 2
-TABLE_NAMES = ("nodes", "nodes_b", "top", "top_b", "grid_start", "grid_items", "grid_items_b", "cull_margin")  # pt_stage_read_tables' `which`
+TABLE_NAMES = ("nodes", "nodes_b", "top", "top_b", "grid_start", "grid_items", "grid_items_b", "cull_margin", "geoms")  # pt_stage_read_tables' `which`
 
 
 class PtError(RuntimeError):
@@ -391,6 +396,19 @@ def lib() -> C.CDLL:
         L.pt_history_capture_counted_host.argtypes = [C.c_int, _fp, _fp, _fp, C.c_float, _fp, _fp]
         L.pt_history_capture_moments_counted_host.argtypes = [C.c_int, _fp, C.c_float, _fp, _fp, _fp, _fp]
         L.pt_history_denoise_moments_counted_host.argtypes = [C.c_int, C.c_int, _fp, _fp, C.c_float, _fp, _fp, _fp, _dno, _fp, _fp, _u8p]
+    if hasattr(L, "pt_set_geoms"):  # absent from older A/B builds of the library (tools/build_rev.sh)
+        _gp, _cam, _hio = C.POINTER(PtGeom), C.POINTER(PtCamera), C.POINTER(PtHistoryOptions)
+        _reproject_motion = [C.c_int, C.c_int, C.c_int, _cam, _fp, _fp, _u8p, C.c_int, _hio, _fp, _fp, _u8p, C.c_uint32, _fp, _fp]
+        L.pt_set_geoms.argtypes = [_gp, C.c_int]
+        L.pt_ctx_set_geoms.argtypes = [C.c_void_p, _gp, C.c_int]
+        L.pt_group_set_geoms.argtypes = [C.c_void_p, _gp, C.c_int]
+        L.pt_get_set_geoms_times.argtypes = [C.POINTER(PtSetGeomsTimes)]
+        L.pt_ctx_get_set_geoms_times.argtypes = [C.c_void_p, C.POINTER(PtSetGeomsTimes)]
+        L.pt_scene_geom_trs.argtypes = [C.c_void_p, C.c_int, _fp]
+        L.pt_scene_set_geom_trs.argtypes = [C.c_void_p, C.c_int, _fp]
+        L.pt_history_motion_host.argtypes = [_gp, _gp, C.c_int, _fp, _u8p]
+        L.pt_history_reproject_motion_host.argtypes = _reproject_motion
+        L.pt_stage_history_reproject_motion.argtypes = _reproject_motion
     _lib = L
     return L
 
@@ -469,6 +487,21 @@ class Scene:
 
     def geoms(self):
         return [self.desc.geoms[i] for i in range(self.desc.num_geoms)]
+
+    def geom_trs(self, geom: int) -> np.ndarray:
+        """The TRANS / ROTAT / SCALE of the OBJECT geom `geom` came from, float32 [9] (pt_scene_geom_trs)."""
+        trs = np.empty(9, np.float32)
+        _check(lib().pt_scene_geom_trs(self._h, int(geom), _f(trs)))
+        return trs
+
+    def set_geom_trs(self, geom: int, trs: Sequence[float]) -> None:
+        """Moves an object as the loader would have placed it (pt_scene_set_geom_trs); `desc` follows.  Renderer.set_geoms(scene)
+        hands the moved geoms to a live renderer."""
+        t = np.ascontiguousarray(trs, np.float32).reshape(-1)
+        if t.size != 9:
+            raise PtError(f"set_geom_trs: {t.size} values, 9 expected")
+        _check(lib().pt_scene_set_geom_trs(self._h, int(geom), _f(t)))
+        _check(lib().pt_scene_desc(self._h, C.byref(self.desc)))
 
     def materials(self):
         return [self.desc.materials[i] for i in range(self.desc.num_materials)]
@@ -788,6 +821,63 @@ def history_reproject_moments_host(kept_cam: PtCamera, kept, planes, reject, kep
 def stage_history_reproject_moments(kept_cam: PtCamera, kept, planes, reject, kept_var, w: int, rows: int, row0: int = 0, **opts):
     """history_reproject_moments_host's arrays through the production kernel (pt_stage_history_reproject_moments; a renderer must be live)."""
     return _history_reproject_variance(lib().pt_stage_history_reproject_moments, kept_cam, kept, planes, reject, kept_var, w, rows, row0, **opts)
+
+
+HISTORY_MOTION = 4  # PT_HISTORY_MOTION
+HISTORY_MOTION_ROW = 24  # floats per geom of the motion table: D (3 x 4), Nm (3 x 3), 3 zeros
+
+
+def _geom_array(geoms):
+    """A ctypes array of PtGeom from a Scene, a ctypes array or a sequence of PtGeom; (array, count)."""
+    if isinstance(geoms, Scene):
+        return geoms.desc.geoms, geoms.desc.num_geoms
+    seq = list(geoms)
+    return (PtGeom * max(len(seq), 1))(*seq), len(seq)
+
+
+def history_motion_host(kept, cur):
+    """The motion table of PT_HISTORY_MOTION (pt_history_motion_host, no GPU): the kept and the current geoms (Scene, or sequences of
+    PtGeom) in, (table float32 [n, 24], kind uint8 [n]) out: 0 still, 1 moved, 2 carries nothing."""
+    ka, kn = _geom_array(kept)
+    ca, cn = _geom_array(cur)
+    if kn != cn or kn < 1:
+        raise PtError(f"history_motion_host: {kn} kept and {cn} current geoms")
+    table, kind = np.empty((kn, HISTORY_MOTION_ROW), np.float32), np.empty(kn, np.uint8)
+    _check(lib().pt_history_motion_host(ka, ca, kn, _f(table), kind.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return table, kind
+
+
+def _history_reproject_motion(call, kept_cam: PtCamera, kept, planes, reject, table, kind, w: int, rows: int, row0: int, flags: int, kept_var, **opts):
+    k = np.ascontiguousarray(kept, np.float32).reshape(-1)
+    p = np.ascontiguousarray(planes, np.float32).reshape(-1)
+    r = np.ascontiguousarray(reject, np.uint8).reshape(-1)
+    t = np.ascontiguousarray(table, np.float32).reshape(-1)
+    kd = np.ascontiguousarray(kind, np.uint8).reshape(-1)
+    vk = None if kept_var is None else np.ascontiguousarray(kept_var, np.float32).reshape(-1)
+    if k.size != 4 * HISTORY_KEPT_PLANES * w * rows or p.size != 4 * FEATURE_PLANES * w * rows or (vk is not None and vk.size != 4 * w * rows):
+        raise PtError(f"history_reproject_motion: {k.size} kept and {p.size} plane floats for a tile of {w}x{rows}")
+    if t.size != HISTORY_MOTION_ROW * kd.size or kd.size != r.size:
+        raise PtError(f"history_reproject_motion: {t.size} table floats and {kd.size} kinds for {r.size} geoms")
+    out = np.empty((w * rows, 4), np.float32)
+    vout = None if vk is None else np.empty((w * rows, 4), np.float32)
+    opt = history_options(**opts)
+    u8 = C.POINTER(C.c_uint8)
+    _check(call(int(w), int(rows), int(row0), C.byref(kept_cam), _f(k), _f(p), r.ctypes.data_as(u8), int(r.size), C.byref(opt), None if vk is None else _f(vk),
+                _f(t), kd.ctypes.data_as(u8), int(flags), _f(out), None if vout is None else _f(vout)))
+    return out if vk is None else (out, vout)
+
+
+def history_reproject_motion_host(kept_cam: PtCamera, kept, planes, reject, table, kind, w: int, rows: int, row0: int = 0, flags: int = HISTORY_MOTION,
+                                  kept_var=None, **opts):
+    """pt_history_reproject_ex with PT_HISTORY_MOTION on the host (no GPU): history_reproject_host's arrays, the motion table and the
+    kinds (history_motion_host) in; C [w*rows, 4] out, or (C, VC) with HISTORY_VARIANCE or HISTORY_MOMENTS in `flags` and VK in kept_var."""
+    return _history_reproject_motion(lib().pt_history_reproject_motion_host, kept_cam, kept, planes, reject, table, kind, w, rows, row0, flags, kept_var, **opts)
+
+
+def stage_history_reproject_motion(kept_cam: PtCamera, kept, planes, reject, table, kind, w: int, rows: int, row0: int = 0, flags: int = HISTORY_MOTION,
+                                   kept_var=None, **opts):
+    """history_reproject_motion_host's arrays through the production kernel (pt_stage_history_reproject_motion; a renderer must be live)."""
+    return _history_reproject_motion(lib().pt_stage_history_reproject_motion, kept_cam, kept, planes, reject, table, kind, w, rows, row0, flags, kept_var, **opts)
 
 
 def _history_planes(current, current_var, w: int, rows: int):
@@ -1202,6 +1292,18 @@ class Renderer:
         _check(lib().pt_get_set_camera_times(C.byref(t)))
         return t
 
+    def set_geoms(self, geoms) -> None:
+        """New transforms for the objects of the live renderer (pt_set_geoms): a Scene (after Scene.set_geom_trs) or a sequence of
+        PtGeom.  From here on the renderer gives what one freshly created with these geoms gives; the camera stays."""
+        arr, n = _geom_array(geoms)
+        _check(lib().pt_set_geoms(arr, n))
+
+    def set_geoms_times(self) -> PtSetGeomsTimes:
+        """Build / upload / re-arm / total milliseconds of the last set_geoms (pt_get_set_geoms_times)."""
+        t = PtSetGeomsTimes()
+        _check(lib().pt_get_set_geoms_times(C.byref(t)))
+        return t
+
     @staticmethod
     def read_tables() -> dict:
         """The camera-dependent tables as they lie on the device, bytes by name (TABLE_NAMES; pt_stage_read_tables); b"" = absent."""
@@ -1267,7 +1369,8 @@ class Renderer:
         _check(lib().pt_history_capture_ex(C.c_float(samples), int(flags)))
 
     def history_reproject_ex(self, flags: int = HISTORY_VARIANCE, **opts) -> None:
-        """history_reproject, with PT_HISTORY_VARIANCE also resampling the kept variance (pt_history_reproject_ex)."""
+        """history_reproject, with PT_HISTORY_VARIANCE also resampling the kept variance (pt_history_reproject_ex); HISTORY_MOTION, alone
+        or beside one of the two kinds, follows the objects that set_geoms moved since the capture."""
         opt = history_options(**opts)
         _check(lib().pt_history_reproject_ex(C.byref(opt), int(flags)))
 
@@ -1525,6 +1628,11 @@ class Group:
             _check(lib().pt_group_set_camera_ex(self._h, C.byref(cam), PT_SET_CAMERA_DEVICE_TABLES))
         else:
             _check(lib().pt_group_set_camera(self._h, C.byref(cam)))
+
+    def set_geoms(self, geoms) -> None:
+        """Renderer.set_geoms on every context (pt_group_set_geoms); a refusal leaves every context as it was."""
+        arr, n = _geom_array(geoms)
+        _check(lib().pt_group_set_geoms(self._h, arr, n))
 
     def gather(self) -> np.ndarray:
         w, h = self.scene.resolution

@@ -719,6 +719,25 @@ int pt_scene_orbit_state(const PtScene* s, float* phi, float* theta, float* zoom
   if (zoom) *zoom = s->scene.zoom;
   return 0;
 }
+// The geom's OBJECT placement, or the refusal under the name `who`.
+static int scene_geom(const PtScene* s, int geom, const void* trs, const char* who) {
+  if (!s || !trs) return pt_fail("%s: null argument", who);
+  if (geom < 0 || (size_t)geom >= s->scene.geoms.size()) return pt_fail("%s: geom %d is outside the scene's %zu geoms", who, geom, s->scene.geoms.size());
+  if (s->scene.geom_trs[(size_t)geom].mesh) return pt_fail("%s: geom %d is a triangle of a mesh object: its vertices are world-space, it has no TRS of its own", who, geom);
+  return 0;
+}
+int pt_scene_geom_trs(const PtScene* s, int geom, float trs[9]) {
+  if (scene_geom(s, geom, trs, "pt_scene_geom_trs")) return -1;
+  std::memcpy(trs, s->scene.geom_trs[(size_t)geom].trs, 9 * sizeof(float));
+  return 0;
+}
+int pt_scene_set_geom_trs(PtScene* s, int geom, const float trs[9]) {
+  if (scene_geom(s, geom, trs, "pt_scene_set_geom_trs")) return -1;
+  for (int k = 0; k < 9; ++k)
+    if (!std::isfinite(trs[k])) return pt_fail("pt_scene_set_geom_trs: trs[%d] is not finite", k);
+  s->scene.placeGeom(geom, trs);
+  return 0;
+}
 int pt_scene_iterations(const PtScene* s) { return s ? (int)s->scene.state.iterations : 0; }
 const char* pt_scene_image_name(const PtScene* s) { return s ? s->scene.state.imageName.c_str() : ""; }
 
@@ -1004,27 +1023,40 @@ int pt_ctx_camera_refusal_ex(const PtContext* c, const PtCamera* cam, uint32_t f
   if (flags & ~(uint32_t)PT_SET_CAMERA_DEVICE_TABLES) return pt_fail("%s: undefined flag bit(s) 0x%x (defined: PT_SET_CAMERA_DEVICE_TABLES = 0x%x)", who, flags & ~(uint32_t)PT_SET_CAMERA_DEVICE_TABLES, PT_SET_CAMERA_DEVICE_TABLES);
   return pt_ctx_camera_refusal(c, cam, who);
 }
+// What pt_set_geoms refuses, under the name `who`; a group asks every context before it changes one.
+int pt_ctx_geoms_refusal(const PtContext* c, const PtGeom* geoms, int num_geoms, const char* who) {
+  if (need(c, who) || admit(*c, who, kNotFailed)) return -1;
+  if (!geoms) return pt_fail("%s: null geoms", who);
+  const std::vector<PtGeom>& have = c->camera_base.geoms;
+  if (num_geoms != (int)have.size())
+    return pt_fail("%s: %d geoms, but the renderer was created with %d; adding or removing objects needs pt_init", who, num_geoms, (int)have.size());
+  for (int i = 0; i < num_geoms; ++i)
+    if (geoms[i].type != have[(size_t)i].type || geoms[i].materialid != have[(size_t)i].materialid)
+      return pt_fail("%s: geom %d has type %d and material %d, the renderer's has type %d and material %d; only the transforms may change", who, i, geoms[i].type,
+                     geoms[i].materialid, have[(size_t)i].type, have[(size_t)i].materialid);
+  for (int i = 0; i < num_geoms; ++i)
+    for (const float* m : {geoms[i].transform, geoms[i].inverseTransform, geoms[i].invTranspose})
+      for (int k = 0; k < 16; ++k)
+        if (!std::isfinite(m[k])) return pt_fail("%s: geom %d has a matrix element that is not finite", who, i);
+  return 0;
+}
 namespace {
+template <typename T>
+void release(Ctx& g, const T* dev, size_t count) {  // a table of `count` entries that dalloc() gave: back to the device
+  if (!dev) return;
+  void* p = const_cast<T*>(dev);
+  (void)hipFree(p);
+  g.allocs.erase(std::remove(g.allocs.begin(), g.allocs.end(), p), g.allocs.end());
+  g.device_bytes -= (int64_t)std::max<size_t>(count * sizeof(T), 16);
+}
 template <typename T>
 int reupload(const T* dev, const std::vector<T>& v) {  // into a table of unchanged size
   HIP_OK(hipMemcpy(const_cast<T*>(dev), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
   return 0;
 }
-// The camera-dependent tables for g.cam, on the device (setup()'s build_scene_tables + upload_tables for that part).  The stream is idle.
-int move_tables(Ctx& g) {
-  pt::HostTables t;
-  std::memcpy(t.root_min, g.scene.root_min, 12);
-  std::memcpy(t.root_max, g.scene.root_max, 12);
-  const bool center_half = g.k->boxes_center_half != 0;
-  pt::camera_tables(t, g.camera_base, g.cam.position, g.debug_flags, center_half, g.grid_request);
-  ptk::SceneTables& s = g.scene;
-  if (reupload(s.nodes, t.nodes) || reupload(s.top, t.top)) return -1;
-  if (center_half && (reupload(s.nodes_b, t.nodes_b) || reupload(s.top_b, t.top_b))) return -1;
-  s.cull_margin = t.cull_margin;
-  g.tight_leaves = t.tight_leaves;
-  // The grid: the one choose_traversal() kept is rebuilt at its resolution, or dropped (the probe preferred the BVH scan, or
-  // build_grid refuses for this camera).  Cell table and records are reused where their sizes are unchanged.
-  const pt::Grid* gr = t.grids.empty() ? nullptr : &t.grids[0];
+// The grid: the one choose_traversal() kept is rebuilt at its resolution (gr), or dropped (nullptr: the probe preferred the BVH scan,
+// or build_grid refuses for this camera or these geoms).  Cell table and records are reused where their sizes are unchanged.
+int move_grid(Ctx& g, const pt::Grid* gr) {
   if (!g.grids.empty()) {
     Ctx::DeviceGrid& d = g.grids[g.grid_pick];
     if (gr && gr->start.size() == d.start.size() && gr->items.size() == d.items && gr->items_b.empty() == (d.d_items_b == d.d_items)) {
@@ -1039,6 +1071,21 @@ int move_tables(Ctx& g) {
   }
   return gr ? upload_grid(g, *gr) : 0;
 }
+// The camera-dependent tables for g.cam, on the device (setup()'s build_scene_tables + upload_tables for that part).  The stream is idle.
+int move_tables(Ctx& g) {
+  pt::HostTables t;
+  std::memcpy(t.root_min, g.scene.root_min, 12);
+  std::memcpy(t.root_max, g.scene.root_max, 12);
+  const bool center_half = g.k->boxes_center_half != 0;
+  pt::camera_tables(t, g.camera_base, g.cam.position, g.debug_flags, center_half, g.grid_request);
+  ptk::SceneTables& s = g.scene;
+  if (reupload(s.nodes, t.nodes) || reupload(s.top, t.top)) return -1;
+  if (center_half && (reupload(s.nodes_b, t.nodes_b) || reupload(s.top_b, t.top_b))) return -1;
+  s.cull_margin = t.cull_margin;
+  g.tight_leaves = t.tight_leaves;
+  return move_grid(g, t.grids.empty() ? nullptr : &t.grids[0]);
+}
+
 
 // The first device-path move of a renderer: camera_base on the device (base nodes, base top list, the fields of PtGeom the build reads)
 // and the build's workspace, sized for the grid the renderer rebuilds (grid_request never changes after setup()).
@@ -1053,6 +1100,7 @@ int ensure_device_base(Ctx& g) {
     geoms[i].type = cb.geoms[i].type;
   }
   if (!(b.nodes = upload(g, cb.nodes)) || !(b.top = upload(g, cb.top)) || !(b.geoms = upload(g, geoms))) return -1;
+  if (b.rec) return b.ready = true, 0;  // after pt_ctx_set_geoms: the workspace follows the grid's resolution and the leaf count, which stay
   if (dalloc(g, &b.rec, 1)) return -1;
   if (g.grid_request.kind == pt::GridRequest::kFixed) {
     int64_t ncell = 1, leaves = 0;
@@ -1187,6 +1235,71 @@ int set_camera(PtContext* c, const PtCamera* cam, uint32_t flags) {  // after th
   g.setup_times.set_camera_calls += 1;
   return 0;
 }
+
+// A table of the renderer with new contents: into the buffer it has where the length is unchanged, else into a new one.
+template <typename T>
+int replace_table(Ctx& g, const T*& dev, size_t old_count, const std::vector<T>& v) {
+  if (v.size() == old_count) return reupload(dev, v);
+  release(g, dev, old_count);
+  return (dev = upload(g, v)) ? 0 : -1;
+}
+int set_geoms(PtContext* c, const PtGeom* geoms, int num_geoms) {  // after the refusals
+  using clock = std::chrono::steady_clock;
+  auto ms_since = [](clock::time_point t0) { return std::chrono::duration<double, std::milli>(clock::now() - t0).count(); };
+  const auto t0 = clock::now();
+  Ctx& g = *c;
+  if (pt_ctx_sync(c)) return -1;
+  PtSetGeomsTimes times{};
+  // pt_init's build for these geoms and the renderer's camera, at the grid resolution pt_init chose; no materials: their table stays
+  const bool center_half = g.k->boxes_center_half != 0;
+  PtSceneDesc desc{};
+  desc.geoms = geoms, desc.num_geoms = num_geoms;
+  desc.camera = g.cam;
+  pt::CameraBase base;
+  const pt::HostTables t = pt::build_scene_tables(desc, g.debug_flags, center_half, g.grid_request, &base);
+  times.build_ms = ms_since(t0);
+  const auto t1 = clock::now();
+  ptk::SceneTables& s = g.scene;
+  const size_t old_nodes = (size_t)s.num_nodes, old_top = (size_t)s.num_top;
+  g.failed = true;  // (tables half replaced: nothing may render from them) until everything below has succeeded
+  if (replace_table(g, s.nodes, old_nodes, t.nodes) || replace_table(g, s.top, old_top, t.top) || replace_table(g, s.geoms, (size_t)s.num_geoms, t.geoms)) return -1;
+  if (center_half) {
+    if (replace_table(g, s.nodes_b, old_nodes, t.nodes_b) || replace_table(g, s.top_b, old_top, t.top_b)) return -1;
+  } else {
+    s.nodes_b = s.nodes, s.top_b = s.top;
+  }
+  s.num_nodes = (int)t.nodes.size(), s.num_top = (int)t.top.size();
+  std::memcpy(s.root_min, t.root_min, 12);
+  std::memcpy(s.root_max, t.root_max, 12);
+  s.cull_margin = t.cull_margin;
+  s.top_xor = t.top_xor;
+  g.tight_leaves = t.tight_leaves;
+  if (move_grid(g, t.grids.empty() ? nullptr : &t.grids[0])) return -1;
+  // the device copy of the camera-independent tables belongs to the old geoms: the next device-path move uploads the new one
+  if (Ctx::DeviceBase& b = g.device_base; b.ready) {
+    release(g, b.nodes, g.camera_base.nodes.size()), release(g, b.top, g.camera_base.top.size()), release(g, b.geoms, g.camera_base.geoms.size());
+    b.nodes = nullptr, b.top = nullptr, b.geoms = nullptr, b.ready = false;
+  }
+  g.camera_base = std::move(base);
+  g.hist_geoms_stale = true, g.hist_motion_fresh = false;  // (the next capture keeps these geoms; K and the kept geoms stay until then)
+  times.upload_ms = ms_since(t1);
+  const auto t2 = clock::now();
+  plan_launch(g);
+  g.record_form = g.gather_form = 0;
+  if (Ctx* w = g.worker) {  // as in set_camera()
+    static_cast<PtShared&>(*w) = g;
+    set_worker_live(*w, w->capacity);
+    plan_launch(*w);
+    if (rearm_batch_buffers(*w)) return -1;
+  }
+  if (rearm_batch_buffers(g)) return -1;
+  g.failed = false;
+  if (pt_ctx_clear(c)) return -1;
+  times.rearm_ms = ms_since(t2);
+  times.total_ms = ms_since(t0);
+  g.geoms_times = times;
+  return 0;
+}
 }  // namespace
 
 namespace ptc {
@@ -1208,6 +1321,16 @@ int pt_ctx_set_camera(PtContext* c, const PtCamera* cam) {
 int pt_ctx_set_camera_ex(PtContext* c, const PtCamera* cam, uint32_t flags) {
   if (pt_ctx_camera_refusal_ex(c, cam, flags, "pt_set_camera_ex")) return -1;
   return set_camera(c, cam, flags);
+}
+int pt_ctx_set_geoms(PtContext* c, const PtGeom* geoms, int num_geoms) {
+  if (pt_ctx_geoms_refusal(c, geoms, num_geoms, "pt_set_geoms")) return -1;
+  return set_geoms(c, geoms, num_geoms);
+}
+int pt_ctx_get_set_geoms_times(PtContext* c, PtSetGeomsTimes* out) {
+  if (need(c, "pt_get_set_geoms_times")) return -1;
+  if (!out) return pt_fail("pt_get_set_geoms_times: null");
+  *out = c->geoms_times;
+  return 0;
 }
 int pt_ctx_get_set_camera_times(PtContext* c, PtSetCameraTimes* out) {
   if (need(c, "pt_get_set_camera_times")) return -1;
@@ -1295,6 +1418,8 @@ int pt_clear(void) { return pt_ctx_clear(g_default); }
 int pt_set_camera(const PtCamera* cam) { return pt_ctx_set_camera(g_default, cam); }
 int pt_set_camera_ex(const PtCamera* cam, uint32_t flags) { return pt_ctx_set_camera_ex(g_default, cam, flags); }
 int pt_get_set_camera_times(PtSetCameraTimes* out) { return pt_ctx_get_set_camera_times(g_default, out); }
+int pt_set_geoms(const PtGeom* geoms, int num_geoms) { return pt_ctx_set_geoms(g_default, geoms, num_geoms); }
+int pt_get_set_geoms_times(PtSetGeomsTimes* out) { return pt_ctx_get_set_geoms_times(g_default, out); }
 int pt_get_setup_times(PtSetupTimes* out) { return pt_ctx_get_setup_times(g_default, out); }
 int pt_render_features(int iter_first, int iter_count) { return pt_ctx_render_features(g_default, iter_first, iter_count); }
 int pt_readback_features(float* planes_host) { return pt_ctx_readback_features(g_default, planes_host); }

@@ -169,6 +169,15 @@ struct PtContext : PtShared {
   void* d_hist_var = nullptr;      // pt_history_variance_bytes(N): VK, then VC; absent until the first capture with PT_HISTORY_VARIANCE or _MOMENTS
   uint32_t hist_var_kept = 0;      // the flag of the capture VK belongs to K0 by: the variance of K0 or its moments (0: a plain capture, K "kept without")
   uint32_t hist_var_current = 0;   // the flag of the lookup VC belongs to C by; 0 (absent) whenever C is
+  // The objects' motion (PT_HISTORY_MOTION): the geoms K is aligned to beside hist_cam, and the motion table of the last lookup that
+  // found a geom moved (absent until then): pthi::kMotionRow floats per geom, then one kind byte per geom
+  std::vector<PtGeom> hist_geoms;
+  bool hist_geoms_stale = true;    // pt_ctx_set_geoms has run since hist_geoms was copied (or nothing was copied yet)
+  void* d_hist_motion = nullptr;
+  std::vector<float> hist_motion_table;   // what d_hist_motion holds
+  std::vector<uint8_t> hist_motion_kind;
+  bool hist_motion_fresh = false;  // the table is that of hist_geoms and camera_base.geoms as they stand; hist_motion_moved: some kind != 0
+  bool hist_motion_moved = false;
   // The history round (pt_ctx_history_round): all of it absent until the first round that renders something
   float* d_hist_extra = nullptr;   // the extra plane E: N floats, the samples the image holds per pixel beyond the uniform ones
   bool hist_extra = false;         // E is present: from a round that rendered to pt_clear or a camera move, which zero it
@@ -193,6 +202,7 @@ struct PtContext : PtShared {
   };
   DeviceBase device_base;
   PtSetCameraTimes camera_times{};  // the last move (pt_get_set_camera_times)
+  PtSetGeomsTimes geoms_times{};    // the last pt_ctx_set_geoms (pt_get_set_geoms_times)
   bool adaptive = false;           // the adaptive state: from the first round to pt_clear
   int adaptive_rounds = 0;
   int64_t adaptive_last = 0;       // highest iteration number folded or merged
@@ -212,6 +222,7 @@ int pt_ctx_admit_state(const PtContext* c, const char* who, bool uniform);
 // whole contiguous rows; folds == false: apart from the state of the folds too (pt_render_threshold's first look).
 int pt_ctx_adaptive_refusal(const PtContext* c, const char* who, int iter_first, int group_iters, float max_fraction, bool folds);
 int pt_ctx_camera_refusal(const PtContext* c, const PtCamera* cam, const char* who);  // what pt_set_camera refuses, in its order; nothing changes
+int pt_ctx_geoms_refusal(const PtContext* c, const PtGeom* geoms, int num_geoms, const char* who);  // what pt_set_geoms refuses, in its order; nothing changes
 int pt_ctx_camera_refusal_ex(const PtContext* c, const PtCamera* cam, uint32_t flags, const char* who);  // ... with the undefined flag bit after the null camera
 int pt_ctx_enter_adaptive(PtContext* c);  // the count plane with the fold's (T, M) in every pixel, unless the context is in the adaptive state already
 

@@ -493,6 +493,14 @@ int pt_group_set_camera(PtGroup* g, const PtCamera* cam) {
   return 0;
 }
 
+int pt_group_set_geoms(PtGroup* g, const PtGeom* geoms, int num_geoms) {
+  if (!g) return pt_fail("pt_group_set_geoms: null group");
+  for (PtContext* c : g->ctx)
+    if (pt_ctx_geoms_refusal(c, geoms, num_geoms, "pt_group_set_geoms")) return -1;
+  for (PtContext* c : g->ctx)
+    if (pt_ctx_set_geoms(c, geoms, num_geoms)) return -1;
+  return 0;
+}
 int pt_group_set_camera_ex(PtGroup* g, const PtCamera* cam, uint32_t flags) {
   if (!g) return pt_fail("pt_group_set_camera_ex: null group");
   for (PtContext* c : g->ctx)

@@ -28,7 +28,7 @@
 //
 // Out of scope (pt_amd.h says the same): pt_group_* (a context's interleaved rows cannot look up their neighbours), feeding the
 // history into the noise estimate, the history round in groups of contexts, a key that uses the carried variance, feeding the FILTERED image back into the history (K keeps the unfiltered
-// blend), motion of anything but the camera, and correcting the smoothing the bilinear lookup adds — the carried image is a biased estimator, and the carried
+// blend), objects that are added, removed or deformed (rigid and affine motion of an object: PT_HISTORY_MOTION), and correcting the smoothing the bilinear lookup adds — the carried image is a biased estimator, and the carried
 // variance is interpolated linearly (as SVGF interpolates its moments), which overstates it: the lookup's smoothing lowers the true one.
 #pragma once
 #include <cstddef>
@@ -209,6 +209,13 @@ struct VarReproject {
   const P4* VK;
   P4* VC;
 };
+// ... and the motion of the objects since the capture (PT_HISTORY_MOTION): kMotionRow floats and one kind byte per geom.
+constexpr int kMotionRow = 24;
+constexpr uint8_t kStill = 0, kMoved = 1, kCarriesNothing = 2;
+struct Motion {
+  const float* table;
+  const uint8_t* kind;
+};
 
 // Pixel i of a tile of npix pixels: rgb_avg[3 i ..] = the blend.  C: the current plane, or nullptr (absent).
 // Ns: float, or Counted.
@@ -263,17 +270,42 @@ PT_HD void capture_pixel(size_t i, size_t npix, const float* S, const P4* feat, 
 // of each tap K1 is read first, then K2, and K0 only when the tap passed.  kVar: VK(q) is read after K0, for a tap that passed only;
 // vh receives VC's value for the pixel, all zero wherever the pixel is rejected (it is not touched otherwise).  kKind: kPlain reads no
 // VK; kVariance interpolates VK.xyz and writes w = +0; kMoments interpolates all four components (w: the sum of squared weights).
-template <int kKind, typename P4>
+//
+// kMotion (PT_HISTORY_MOTION): objects moved between the capture and now.  mo.table holds kMotionRow floats per geom — D, the 3 x 4
+// map from a point's current position to where it was at the capture, row-major, then Nm, the 3 x 3 map of its normal, then 3 zeros —
+// and mo.kind one byte per geom (motion_table below): 0 still, 1 moved, 2 carries nothing.  One step after the first rejections:
+// for kind 1 the pixel's p and n become p' = D (p, 1) and n' = Nm n / |Nm n|, and everything after reads those; an id outside
+// 1 .. num_geoms (seen only with keep_view_dependent) counts as still.  <..., false> is the body as it stood.
+template <int kKind, bool kMotion = false, typename P4>
 PT_HD P4 reproject_pixel_of(size_t i, const View& v, const P4* K, const P4* feat, const uint8_t* reject, int32_t num_geoms, const Params& P, const P4* VK,
-                            P4& vh) {
+                            P4& vh, const Motion& mo = Motion{}) {
 #pragma clang fp contract(off)
   const size_t npix = (size_t)v.W * v.R;
   const P4 zero{0.0f, 0.0f, 0.0f, 0.0f};
   constexpr bool kVar = kKind != kPlain;
   if constexpr (kVar) vh = zero;
-  const Surface s = surface(i, npix, feat);
+  Surface s = surface(i, npix, feat);
   if (!s.hit) return zero;
   if (!P.keep_view_dependent && (s.id < 1 || s.id > num_geoms || reject[s.id - 1])) return zero;
+  if constexpr (kMotion) {
+    const uint8_t kind = s.id >= 1 && s.id <= num_geoms ? mo.kind[s.id - 1] : (uint8_t)kStill;
+    if (kind == kCarriesNothing) return zero;
+    if (kind == kMoved) {
+      const float* D = mo.table + (size_t)(s.id - 1) * kMotionRow;
+      const float* Nm = D + 12;
+      const float qx = ((D[0] * s.px + D[1] * s.py) + D[2] * s.pz) + D[3];
+      const float qy = ((D[4] * s.px + D[5] * s.py) + D[6] * s.pz) + D[7];
+      const float qz = ((D[8] * s.px + D[9] * s.py) + D[10] * s.pz) + D[11];
+      const float mx = dot3(Nm[0], Nm[1], Nm[2], s.nx, s.ny, s.nz);
+      const float my = dot3(Nm[3], Nm[4], Nm[5], s.nx, s.ny, s.nz);
+      const float mz = dot3(Nm[6], Nm[7], Nm[8], s.nx, s.ny, s.nz);
+      const float l = dot3(mx, my, mz, mx, my, mz);
+      if (!(l > 0.0f)) return zero;
+      const float r = __builtin_sqrtf(l);
+      s.px = qx, s.py = qy, s.pz = qz;
+      s.nx = mx / r, s.ny = my / r, s.nz = mz / r;
+    }
+  }
   const float vx = s.px - v.pos[0], vy = s.py - v.pos[1], vz = s.pz - v.pos[2];
   const float dz = dot3(vx, vy, vz, v.view[0], v.view[1], v.view[2]);
   if (!(dz > 0.0f)) return zero;
@@ -366,6 +398,42 @@ inline void reproject_variance_host(const View& v, const float* K, const float* 
 inline void reproject_moments_host(const View& v, const float* K, const float* feat, const uint8_t* reject, int32_t num_geoms, const Params& P, const float* VK,
                                    float* C, float* VC) {
   reproject_with_host<kMoments>(v, K, feat, reject, num_geoms, P, VK, C, VC);
+}
+// ... and with the objects' motion: kKind as above; VK, VC unused (nullptr) for kPlain.
+template <int kKind>
+inline void reproject_motion_host(const View& v, const float* K, const float* feat, const uint8_t* reject, int32_t num_geoms, const Params& P, const float* VK,
+                                  const Motion& mo, float* C, float* VC) {
+  const size_t npix = (size_t)v.W * v.R;
+  F4 *out = reinterpret_cast<F4*>(C), *vout = reinterpret_cast<F4*>(VC);
+  F4 unused;
+  for (size_t i = 0; i < npix; ++i)
+    out[i] = reproject_pixel_of<kKind, true>(i, v, reinterpret_cast<const F4*>(K), reinterpret_cast<const F4*>(feat), reject, num_geoms, P,
+                                             reinterpret_cast<const F4*>(VK), kKind == kPlain ? unused : vout[i], mo);
+}
+// The motion table of pt_amd.h (pt_history_motion_host): row g and kind[g] from the kept and the current geom g.  Every factor is
+// widened to double, the products and sums are plain double operations in the order written, the result is rounded to float once.
+inline void motion_table(const PtGeom* kept, const PtGeom* cur, int n, float* table, uint8_t* kind) {
+#pragma clang fp contract(off)
+  for (int g = 0; g < n; ++g) {
+    float* row = table + (size_t)g * kMotionRow;
+    const PtGeom &k = kept[g], &c = cur[g];
+    auto at = [](const float* m, int r, int col) { return (double)m[col * 4 + r]; };  // column-major
+    for (int r = 0; r < 3; ++r)
+      for (int col = 0; col < 4; ++col)
+        row[r * 4 + col] = (float)(((at(k.transform, r, 0) * at(c.inverseTransform, 0, col) + at(k.transform, r, 1) * at(c.inverseTransform, 1, col)) +
+                                    at(k.transform, r, 2) * at(c.inverseTransform, 2, col)) +
+                                   at(k.transform, r, 3) * at(c.inverseTransform, 3, col));
+    for (int r = 0; r < 3; ++r)
+      for (int col = 0; col < 3; ++col)
+        row[12 + r * 3 + col] = (float)((at(k.invTranspose, r, 0) * at(c.transform, col, 0) + at(k.invTranspose, r, 1) * at(c.transform, col, 1)) +
+                                        at(k.invTranspose, r, 2) * at(c.transform, col, 2));
+    row[21] = row[22] = row[23] = 0.0f;
+    const bool same = __builtin_memcmp(k.transform, c.transform, 64) == 0 && __builtin_memcmp(k.inverseTransform, c.inverseTransform, 64) == 0 &&
+                      __builtin_memcmp(k.invTranspose, c.invTranspose, 64) == 0;
+    bool finite = true;
+    for (int j = 0; j < 21; ++j) finite = finite && row[j] - row[j] == 0.0f;
+    kind[g] = same ? kStill : (k.type == PT_GEOM_TRIANGLE || c.type == PT_GEOM_TRIANGLE || !finite) ? kCarriesNothing : kMoved;
+  }
 }
 inline void blend_host(size_t npix, const float* S, float samples, const float* C, float* rgb_avg) {
   for (size_t i = 0; i < npix; ++i) blend_pixel(i, S, samples, reinterpret_cast<const F4*>(C), rgb_avg);

@@ -18,6 +18,8 @@
 //   k_history_capture<kMoments>   + (when present) 16 B of VC in, 16 B of VK out per pixel; no fold is read
 //   k_history_reproject<kVariance>  + 16 B of VC out per pixel; per tap that passed 16 B of VK, read after K0 at the same index
 //   k_history_reproject<kMoments>   the same loads and stores; the fourth component of VK is interpolated too
+//   k_history_reproject_motion<kPlain | kVariance | kMoments>  the lookup with PT_HISTORY_MOTION: the loads and stores of the kernel
+//                        above, one kind byte per pixel and 84 B of a table row for a pixel of a moved geom; launched only when a geom moved
 // The history round (pt_history_round):
 //   k_history_key        a pure stream, one thread per tile pixel: the .w words of the feature sums s1 and s2 and (when present) of C
 //                        in, as 4-byte loads 16 bytes apart — 12 B per pixel asked for, whole lines moved: consecutive lanes sit in
@@ -66,6 +68,27 @@ __global__ __launch_bounds__(kBlock) void k_history_reproject(int npix, View v, 
     VC[i] = vh;
   } else {
     C[i] = pthi::reproject_pixel((size_t)i, v, K, feat, reject, num_geoms, P);
+  }
+}
+
+// ... with the objects' motion (PT_HISTORY_MOTION): a kernel of its own, so that the ones above are the code they were.  Per pixel
+// one byte of `mkind` for a hit that passed the first rejections and, for a moved geom, 84 B of its table row (a few rows per
+// frame: they stay in the caches); 11 multiply-adds, a square root and three divisions more.  In...: nothing, or VK and VC
+template <int kKind, typename... In>
+__global__ __launch_bounds__(kBlock) void k_history_reproject_motion(int npix, View v, const V4* __restrict__ K, const V4* __restrict__ feat,
+                                                                     const uint8_t* __restrict__ reject, int num_geoms, Params P,
+                                                                     const float* __restrict__ table, const uint8_t* __restrict__ mkind,
+                                                                     V4* __restrict__ C, In... in) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= npix) return;
+  const pthi::Motion mo{table, mkind};
+  V4 vh;
+  if constexpr (kKind != pthi::kPlain) {
+    const auto [VK, VC] = pthi::VarReproject<V4>{in...};
+    C[i] = pthi::reproject_pixel_of<kKind, true>((size_t)i, v, K, feat, reject, num_geoms, P, VK, vh, mo);
+    VC[i] = vh;
+  } else {
+    C[i] = pthi::reproject_pixel_of<kKind, true>((size_t)i, v, K, feat, reject, num_geoms, P, static_cast<const V4*>(nullptr), vh, mo);
   }
 }
 
@@ -172,6 +195,30 @@ int pt_history_reproject_variance_launch(hipStream_t stream, const pthi::View& v
 int pt_history_reproject_moments_launch(hipStream_t stream, const pthi::View& v, const void* kept_dev, const float* planes_dev, const uint8_t* reject_dev,
                                         int num_geoms, const pthi::Params& P, void* current_dev, const void* kept_var_dev, void* current_var_dev) {
   return reproject_with_launch<pthi::kMoments>(stream, v, kept_dev, planes_dev, reject_dev, num_geoms, P, current_dev, kept_var_dev, current_var_dev);
+}
+
+int pt_history_reproject_motion_launch(hipStream_t stream, uint32_t kind, const pthi::View& v, const void* kept_dev, const float* planes_dev,
+                                       const uint8_t* reject_dev, int num_geoms, const pthi::Params& P, void* current_dev, const void* kept_var_dev,
+                                       void* current_var_dev, const float* table_dev, const uint8_t* kind_dev) {
+  const char* who = "pt_history_reproject_ex";
+  if (bad_frame(v.W, v.R)) return pt_fail("%s: a tile of %d x %d pixels is not supported", who, v.W, v.R);
+  const bool with = kind != 0;
+  if (!kept_dev || !planes_dev || !current_dev || num_geoms < 1 || !table_dev || !kind_dev || (!P.keep_view_dependent && !reject_dev) ||
+      (kind != 0 && kind != PT_HISTORY_VARIANCE && kind != PT_HISTORY_MOMENTS) || with != (kept_var_dev != nullptr) || with != (current_var_dev != nullptr))
+    return pt_fail("%s: bad argument (motion)", who);
+  const int npix = v.W * v.R;
+  const dim3 grid((npix + kBlock - 1) / kBlock), block(kBlock);
+  const V4 *K = static_cast<const V4*>(kept_dev), *feat = reinterpret_cast<const V4*>(planes_dev), *VK = static_cast<const V4*>(kept_var_dev);
+  V4 *C = static_cast<V4*>(current_dev), *VC = static_cast<V4*>(current_var_dev);
+  if (kind == PT_HISTORY_VARIANCE)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_history_reproject_motion<pthi::kVariance, const V4*, V4*>), grid, block, 0, stream, npix, v, K, feat, reject_dev, num_geoms, P,
+                       table_dev, kind_dev, C, VK, VC);
+  else if (kind == PT_HISTORY_MOMENTS)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_history_reproject_motion<pthi::kMoments, const V4*, V4*>), grid, block, 0, stream, npix, v, K, feat, reject_dev, num_geoms, P,
+                       table_dev, kind_dev, C, VK, VC);
+  else
+    hipLaunchKernelGGL(k_history_reproject_motion<pthi::kPlain>, grid, block, 0, stream, npix, v, K, feat, reject_dev, num_geoms, P, table_dev, kind_dev, C);
+  return launched(who);
 }
 
 int pt_history_blend_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, float samples, const void* current_dev, float* rgb_avg_dev) {
@@ -346,6 +393,38 @@ extern "C" int pt_history_reproject_moments_host(int w, int rows, int row0, cons
   if (pt_history_reproject_check(who, w, rows, row0, kept_cam, kept_planes, feature_planes, reject_geom, num_geoms, opt, current_plane, &P)) return -1;
   if (!kept_var || !current_var) return pt_fail("%s: null argument", who);
   pthi::reproject_moments_host(pthi::make_view(*kept_cam, rows, row0), kept_planes, feature_planes, reject_geom, num_geoms, P, kept_var, current_plane, current_var);
+  return 0;
+}
+
+// ---- the objects' motion (PT_HISTORY_MOTION) -------------------------------------------------------------------------------
+extern "C" int pt_history_motion_host(const PtGeom* kept, const PtGeom* cur, int n, float* table, uint8_t* kind) {
+  if (!kept || !cur || n <= 0 || !table || !kind) return pt_fail("pt_history_motion_host: bad argument");
+  pthi::motion_table(kept, cur, n, table, kind);
+  return 0;
+}
+int pt_history_motion_check(const char* who, uint32_t flags, int num_geoms, const float* table, const uint8_t* kind, const float* kept_var,
+                            const float* current_var) {
+  constexpr uint32_t defined = PT_HISTORY_VARIANCE | PT_HISTORY_MOMENTS | PT_HISTORY_MOTION;
+  if (flags & ~defined) return pt_fail("%s: undefined flag bit(s) 0x%x (defined: PT_HISTORY_VARIANCE, PT_HISTORY_MOMENTS, PT_HISTORY_MOTION)", who, flags & ~defined);
+  if ((flags & PT_HISTORY_VARIANCE) && (flags & PT_HISTORY_MOMENTS)) return pt_fail("%s: the flags PT_HISTORY_VARIANCE and PT_HISTORY_MOMENTS exclude each other", who);
+  if (num_geoms < 1 || !table || !kind) return pt_fail("%s: a motion table and kinds for at least one geom are needed", who);
+  for (int g = 0; g < num_geoms; ++g)
+    if (kind[g] > pthi::kCarriesNothing) return pt_fail("%s: kind[%d] = %d is not 0, 1 or 2", who, g, (int)kind[g]);
+  if ((flags & (PT_HISTORY_VARIANCE | PT_HISTORY_MOMENTS)) && (!kept_var || !current_var)) return pt_fail("%s: null argument", who);
+  return 0;
+}
+extern "C" int pt_history_reproject_motion_host(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
+                                                const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, const float* kept_var,
+                                                const float* table, const uint8_t* kind, uint32_t flags, float* current_plane, float* current_var) {
+  pthi::Params P{};
+  const char* who = "pt_history_reproject_motion_host";
+  if (pt_history_reproject_check(who, w, rows, row0, kept_cam, kept_planes, feature_planes, reject_geom, num_geoms, opt, current_plane, &P)) return -1;
+  if (pt_history_motion_check(who, flags, num_geoms, table, kind, kept_var, current_var)) return -1;
+  const pthi::View v = pthi::make_view(*kept_cam, rows, row0);
+  const pthi::Motion mo{table, kind};
+  if (flags & PT_HISTORY_VARIANCE) pthi::reproject_motion_host<pthi::kVariance>(v, kept_planes, feature_planes, reject_geom, num_geoms, P, kept_var, mo, current_plane, current_var);
+  else if (flags & PT_HISTORY_MOMENTS) pthi::reproject_motion_host<pthi::kMoments>(v, kept_planes, feature_planes, reject_geom, num_geoms, P, kept_var, mo, current_plane, current_var);
+  else pthi::reproject_motion_host<pthi::kPlain>(v, kept_planes, feature_planes, reject_geom, num_geoms, P, nullptr, mo, current_plane, nullptr);
   return 0;
 }
 

@@ -125,6 +125,14 @@ int pt_history_capture_moments_launch(hipStream_t stream, int pixels, const floa
                                       void* kept_dev, const void* current_var_dev, void* kept_var_dev);
 int pt_history_reproject_moments_launch(hipStream_t stream, const pthi::View& v, const void* kept_dev, const float* planes_dev, const uint8_t* reject_dev,
                                         int num_geoms, const pthi::Params& P, void* current_dev, const void* kept_var_dev, void* current_var_dev);
+// The lookup with the objects' motion (PT_HISTORY_MOTION): kind 0 (plain), PT_HISTORY_VARIANCE or PT_HISTORY_MOMENTS; table_dev
+// pthi::kMotionRow floats and kind_dev one byte per geom (num_geoms >= 1); kept_var_dev / current_var_dev nullptr for kind 0.
+int pt_history_reproject_motion_launch(hipStream_t stream, uint32_t kind, const pthi::View& v, const void* kept_dev, const float* planes_dev,
+                                       const uint8_t* reject_dev, int num_geoms, const pthi::Params& P, void* current_dev, const void* kept_var_dev,
+                                       void* current_var_dev, const float* table_dev, const uint8_t* kind_dev);
+// What the host and stage forms of that lookup refuse after pt_history_reproject_check: the flag word, the table, the kinds, VK / VC.
+int pt_history_motion_check(const char* who, uint32_t flags, int num_geoms, const float* table, const uint8_t* kind, const float* kept_var,
+                            const float* current_var);
 int pt_history_blend_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, float samples, const void* current_dev, float* rgb_avg_dev);
 // The history round (pt_history_round): the key of every tile pixel into key_dev (pt_adaptive_select_keys of the selection's workspace;
 // emitter_dev one byte per geom), the merge of the worker's group sum (m >= 1 list entries) into the image and the extra plane E

@@ -476,10 +476,13 @@ static const char kNoFeatures[] = "%s: no feature pass has been rendered since t
 
 static pthi::V4* history_var_plane(const Ctx& g, int plane) { return static_cast<pthi::V4*>(g.d_hist_var) + (size_t)plane * g.N; }  // 0: VK, 1: VC
 // An undefined flag bit: what the _ex forms refuse right after a failed context.
-static int history_flags(const char* who, uint32_t flags) {
-  constexpr uint32_t defined = PT_HISTORY_VARIANCE | PT_HISTORY_MOMENTS;
-  if (flags & ~defined) return pt_fail("%s: undefined flag bit(s) 0x%x (defined: PT_HISTORY_VARIANCE, PT_HISTORY_MOMENTS)", who, flags & ~defined);
-  if (flags == defined) return pt_fail("%s: the flags PT_HISTORY_VARIANCE and PT_HISTORY_MOMENTS exclude each other", who);
+// motion: the lookup's word, which also defines PT_HISTORY_MOTION (alone or beside one of the two).
+static int history_flags(const char* who, uint32_t flags, bool motion = false) {
+  constexpr uint32_t kinds = PT_HISTORY_VARIANCE | PT_HISTORY_MOMENTS;
+  const uint32_t defined = kinds | (motion ? PT_HISTORY_MOTION : 0u);
+  if (flags & ~defined)
+    return pt_fail("%s: undefined flag bit(s) 0x%x (defined: PT_HISTORY_VARIANCE, PT_HISTORY_MOMENTS%s)", who, flags & ~defined, motion ? ", PT_HISTORY_MOTION" : "");
+  if ((flags & kinds) == kinds) return pt_fail("%s: the flags PT_HISTORY_VARIANCE and PT_HISTORY_MOMENTS exclude each other", who);
   return 0;
 }
 // What the variance needs of the folds: at least two, nothing rendered since, and `samples` the iterations they hold.
@@ -532,6 +535,7 @@ static int history_capture(PtContext* c, const char* who, float samples, uint32_
     return -1;
   }
   g.hist_cam = g.cam;
+  if (g.hist_geoms_stale) g.hist_geoms = g.camera_base.geoms, g.hist_geoms_stale = false, g.hist_motion_fresh = false;  // the kept geoms: retaken only after a pt_set_geoms
   g.hist_kept = true;
   g.hist_var_kept = flags;  // a plain capture: kept without variance or moments
   return 0;
@@ -556,10 +560,41 @@ static int history_reject_table(Ctx& g) {
   return 0;
 }
 
+// The motion table of the kept and the current geoms (pthi::motion_table) on the device, for a lookup with PT_HISTORY_MOTION.
+// *moved == false: every geom is still; nothing was allocated or uploaded and the caller launches the kernel without the flag.
+// The table follows from the kept and the current geoms alone, so it is computed by the first lookup after either changed (a capture
+// that retook the geoms, pt_ctx_set_geoms) and uploaded when it differs from what the device holds (synchronises then: the staging
+// is pageable); later lookups find it in place — on 10,170 geoms the host's 0.3 ms per call would otherwise be nine times the kernel.
+static int history_motion_table(Ctx& g, bool* moved) {
+  const std::vector<PtGeom>& cur = g.camera_base.geoms;
+  const size_t n = cur.size();
+  *moved = false;
+  if (g.hist_geoms.size() != n || n == 0) return 0;  // (nothing kept yet: the caller has refused already)
+  if (g.hist_motion_fresh) return *moved = g.hist_motion_moved, 0;
+  std::vector<float> table(n * pthi::kMotionRow);
+  std::vector<uint8_t> kind(n);
+  pthi::motion_table(g.hist_geoms.data(), cur.data(), (int)n, table.data(), kind.data());
+  for (uint8_t k : kind) *moved = *moved || k != pthi::kStill;
+  g.hist_motion_moved = *moved;
+  if (!*moved) return g.hist_motion_fresh = true, 0;
+  const size_t table_bytes = table.size() * sizeof(float);
+  if (ensure(g, g.d_hist_motion, table_bytes + n)) return -1;
+  if (table != g.hist_motion_table || kind != g.hist_motion_kind) {
+    HIP_OK(hipStreamSynchronize(g.stream));  // an earlier lookup may still read the rows
+    HIP_OK(hipMemcpy(g.d_hist_motion, table.data(), table_bytes, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(static_cast<char*>(g.d_hist_motion) + table_bytes, kind.data(), n, hipMemcpyHostToDevice));
+    g.hist_motion_table = std::move(table), g.hist_motion_kind = std::move(kind);
+  }
+  g.hist_motion_fresh = true;
+  return 0;
+}
+
 static int history_reproject(PtContext* c, const char* who, const PtHistoryOptions* opt, uint32_t flags, bool ex) {
   if (need(c, who)) return -1;
   Ctx& g = *c;
-  if (ex && (admit(g, who, kNotFailed) || history_flags(who, flags))) return -1;
+  if (ex && (admit(g, who, kNotFailed) || history_flags(who, flags, true))) return -1;
+  const bool motion = (flags & PT_HISTORY_MOTION) != 0;
+  flags &= ~PT_HISTORY_MOTION;  // what is left names the kind: 0, PT_HISTORY_VARIANCE or PT_HISTORY_MOMENTS
   if (history_admit(g, who)) return -1;
   if (!g.d_hist || !g.hist_kept) return pt_fail("%s: nothing has been captured (pt_history_capture)", who);
   if (!g.d_feat || !g.feat_fresh) return pt_fail(kNoFeatures, who);
@@ -575,7 +610,15 @@ static int history_reproject(PtContext* c, const char* who, const PtHistoryOptio
   const pthi::View v = pthi::make_view(g.hist_cam, g.N / W, g.pixel_begin / W);
   const float* feat = reinterpret_cast<const float*>(g.d_feat);
   const int num_geoms = (int)g.camera_base.geoms.size();
-  if (flags == PT_HISTORY_VARIANCE
+  bool moved = false;
+  if (motion && history_motion_table(g, &moved)) return -1;
+  if (moved) {
+    const float* table = static_cast<const float*>(g.d_hist_motion);
+    const uint8_t* kind = reinterpret_cast<const uint8_t*>(table + (size_t)num_geoms * pthi::kMotionRow);
+    if (pt_history_reproject_motion_launch(g.stream, flags, v, g.d_hist, feat, g.d_hist_reject, num_geoms, P, history_plane(g, pthi::kKeptPlanes),
+                                           flags ? history_var_plane(g, 0) : nullptr, flags ? history_var_plane(g, 1) : nullptr, table, kind))
+      return -1;
+  } else if (flags == PT_HISTORY_VARIANCE
           ? pt_history_reproject_variance_launch(g.stream, v, g.d_hist, feat, g.d_hist_reject, num_geoms, P, history_plane(g, pthi::kKeptPlanes),
                                                  history_var_plane(g, 0), history_var_plane(g, 1))
       : flags == PT_HISTORY_MOMENTS

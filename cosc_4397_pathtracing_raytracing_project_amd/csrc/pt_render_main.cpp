@@ -3,7 +3,7 @@
 // state.iterations iterations, write the PNG saveImage() would write.  Flags exist only because
 // the reference takes resolution, iteration count and depth from the scene file (scene.cpp:103-114).
 //
-//   pt_render SCENE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] [--orbit N [--device-tables] [--reproject [--history-cap C] [--denoise-history [--history-moments]] [--history-extra G [--history-min M] [--history-extra-cap F]]]]
+//   pt_render SCENE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] [--orbit N [--device-tables] [--move G:DX,DY,DZ] [--reproject [--history-cap C] [--denoise-history [--history-moments]] [--history-extra G [--history-min M] [--history-extra-cap F]]]]
 //                       [--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa]
 //                       [--preview N] [--convergence N | --reference FILE.pfm] [--clean-db X] [--features]
 //                       [--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]]
@@ -60,6 +60,10 @@
 // times once and per frame `orbit: frame f: camera x y z, set_camera a ms, render b ms`.  --device-tables (with --orbit): every move
 // passes PT_SET_CAMERA_DEVICE_TABLES (pt_set_camera_ex: the camera-dependent tables are rebuilt on the device, the same images), and the
 // frame's line ends `, tables a ms, rearm b ms (device|host tables)` from pt_get_set_camera_times.
+// --move G:DX,DY,DZ (with --orbit; works with --gpus / --devices and with --reproject): from frame 1 on the TRANS of geom G grows by the step
+// before the camera moves — the scene's geom is placed again as the loader would (pt_scene_set_geom_trs' code) and the live renderer
+// takes the new geoms (pt_set_geoms, pt_group_set_geoms).  Prints `move: frame f: geom G at x y z, set_geoms a ms`.  With --reproject
+// the lookup follows the object (PT_HISTORY_MOTION).
 // --reproject (with --orbit, excludes --gpus / --devices): the image is carried from view to view (pt_history_*).  After a frame's render
 // comes pt_render_features(1, 1); from frame 1 on pt_history_reproject; pt_history_resolve, written next to the raw frame as
 // <base>.orbit<fff>.reprojected.png (.pfm with --pfm); pt_history_capture; then the move.  --denoise-history (with --reproject, --spp >= 2;
@@ -108,6 +112,9 @@ int main(int argc, char** argv) {
   PtDenoiseOptions dn_opt{};
   int convergence = 0, until_group = 0, orbit = 0;  // orbit > 0: --orbit N
   bool device_tables = false;                       // --device-tables
+  bool move = false;                                // --move G:DX,DY,DZ
+  int move_geom = 0;
+  float move_step[3] = {0.0f, 0.0f, 0.0f};
   bool reproject = false;                           // --reproject
   bool dn_history = false;                          // --denoise-history
   bool hist_moments = false;                        // --history-moments
@@ -139,6 +146,15 @@ int main(int argc, char** argv) {
       orbit = (int)v;
     }
     else if (!std::strcmp(argv[i], "--device-tables")) device_tables = true;
+    else if (!std::strcmp(argv[i], "--move") && i + 1 < argc) {
+      char tail = 0;
+      if (std::sscanf(argv[++i], "%d:%f,%f,%f%c", &move_geom, &move_step[0], &move_step[1], &move_step[2], &tail) != 4 || move_geom < 0 ||
+          !std::isfinite(move_step[0]) || !std::isfinite(move_step[1]) || !std::isfinite(move_step[2])) {
+        std::fprintf(stderr, "--move wants G:DX,DY,DZ: the index of a geom and the step its TRANS takes from frame to frame, three finite numbers\n");
+        return 1;
+      }
+      move = true;
+    }
     else if (!std::strcmp(argv[i], "--reproject")) reproject = true;
     else if (!std::strcmp(argv[i], "--denoise-history")) dn_history = true;  // the blend filtered with the variance the history carries
     else if (!std::strcmp(argv[i], "--history-moments")) hist_moments = true;  // ... with the variance its moments give: no folds
@@ -357,6 +373,10 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--device-tables goes with --orbit N (it says how the camera moves rebuild the scene tables)\n");
     return 1;
   }
+  if (move && orbit <= 0) {
+    std::fprintf(stderr, "--move goes with --orbit N (it moves an object of the live renderer from frame to frame)\n");
+    return 1;
+  }
   if ((reproject && orbit <= 0) || (history_cap_given && !reproject)) {
     std::fprintf(stderr, "--reproject goes with --orbit N (it carries the image from view to view), --history-cap C with --reproject\n");
     return 1;
@@ -403,6 +423,11 @@ int main(int argc, char** argv) {
   if (spp > 0) scene->state.iterations = spp;
   if (depth > 0) scene->state.traceDepth = depth;
   scene->applyInitialCameraState();
+  if (move && ((size_t)move_geom >= scene->geoms.size() || scene->geom_trs[(size_t)move_geom].mesh)) {
+    std::fprintf(stderr, "--move: geom %d is %s\n", move_geom,
+                 (size_t)move_geom >= scene->geoms.size() ? "outside the scene's geoms" : "a triangle of a mesh object, which has no TRANS of its own");
+    return 1;
+  }
   const int W = scene->state.camera.resolution[0], H = scene->state.camera.resolution[1];
   int iters = (int)scene->state.iterations;  // with --until-db the cap, until the render has said how many it took
   if (guided && iters < 2) {
@@ -538,6 +563,19 @@ int main(int argc, char** argv) {
     for (int f = 0; f < orbit; ++f) {
       double move_ms = 0.0;
       PtSetCameraTimes ct{};
+      if (f > 0 && move) {  // the object first, then the camera: TRANS grows by the step, the live renderer takes the new geoms
+        float trs[9];
+        std::memcpy(trs, scene->geom_trs[(size_t)move_geom].trs, sizeof trs);
+        for (int k = 0; k < 3; ++k) trs[k] += move_step[k];
+        scene->placeGeom(move_geom, trs);
+        const auto g0 = std::chrono::high_resolution_clock::now();
+        if (grp ? pt_group_set_geoms(grp, scene->geoms.data(), (int)scene->geoms.size()) : pt_set_geoms(scene->geoms.data(), (int)scene->geoms.size())) {
+          std::fprintf(stderr, "HIP error (pt_set_geoms): %s\n", pt_last_error());
+          return EXIT_FAILURE;
+        }
+        const double geoms_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - g0).count();
+        std::printf("move: frame %d: geom %d at %.9g %.9g %.9g, set_geoms %.3f ms\n", f, move_geom, (double)trs[0], (double)trs[1], (double)trs[2], geoms_ms);
+      }
       if (f > 0) {
         scene->orbit(step, 0.0f, 0.0f);
         const uint32_t flags = device_tables ? PT_SET_CAMERA_DEVICE_TABLES : 0u;
@@ -582,7 +620,7 @@ int main(int argc, char** argv) {
       if (reproject) {  // the view's first hits, the history looked up from them, the blend written, the blend kept for the next view
         const uint32_t hflags = !dn_history ? 0u : hist_moments ? PT_HISTORY_MOMENTS : PT_HISTORY_VARIANCE;  // 0: the plain calls
         int fresh = 0, selected = 0;  // --history-extra: the round, between the lookup and the resolve
-        if (pt_render_features(1, 1) || (f > 0 && pt_history_reproject_ex(&hopt, hflags)) ||
+        if (pt_render_features(1, 1) || (f > 0 && pt_history_reproject_ex(&hopt, hflags | (move ? PT_HISTORY_MOTION : 0u))) ||
             (history_extra && pt_history_round(iter_first + iters, history_extra, &round_opt, &fresh, &selected)) || pt_history_resolve((float)iters, carried.data()) ||
             (dn_history && (hist_moments ? pt_history_denoise_ex((float)iters, &dn_opt, PT_HISTORY_MOMENTS, filtered.data())
                                          : pt_history_denoise((float)iters, &dn_opt, filtered.data()))) || pt_history_capture_ex((float)iters, hflags) ||

@@ -221,7 +221,7 @@ void parseMaterial(std::istream& in, const std::string& idWord, std::vector<PtMa
 // below).  OBJECT ids are checked against the
 // number of objects accepted so far (`objects`), which equals geoms.size() (the reference's check, scene.cpp:37) as long as
 // no mesh has expanded.
-void parseObject(std::istream& in, const std::string& idWord, std::vector<PtGeom>& geoms, int& objects) {
+void parseObject(std::istream& in, const std::string& idWord, std::vector<PtGeom>& geoms, std::vector<GeomTrs>& placed, int& objects) {
   if (atoi(idWord.c_str()) != objects) return;
   ++objects;
   PtGeom g{};
@@ -267,10 +267,12 @@ void parseObject(std::istream& in, const std::string& idWord, std::vector<PtGeom
           t.transform[3 * v + r] = (m[0 * 4 + r] * p[0] + m[1 * 4 + r] * p[1]) + (m[2 * 4 + r] * p[2] + m[3 * 4 + r] * 1.0f);
       }
       geoms.push_back(t);
+      placed.push_back(GeomTrs{{trs[0], trs[1], trs[2], trs[3], trs[4], trs[5], trs[6], trs[7], trs[8]}, true});
     }
     return;
   }
   geoms.push_back(g);
+  placed.push_back(GeomTrs{{trs[0], trs[1], trs[2], trs[3], trs[4], trs[5], trs[6], trs[7], trs[8]}, false});
 }
 
 void cameraScale(PtCamera& cam, float fovy) {  // scene.cpp:133-140
@@ -319,6 +321,12 @@ void parseCamera(std::istream& in, Scene& sc) {
 
 }  // namespace
 
+void Scene::placeGeom(int geom, const float trs[9]) {
+  PtGeom& g = geoms[(size_t)geom];
+  std::memcpy(geom_trs[(size_t)geom].trs, trs, 9 * sizeof(float));
+  buildTransform(trs, g.transform, g.inverseTransform, g.invTranspose);
+}
+
 void buildTransform(const float trs[9], float transform[16], float inverse[16], float invTranspose[16]) {
   const M4 I = identity();
   const M4 T = glmTranslate(I, {trs[0], trs[1], trs[2]});
@@ -345,7 +353,7 @@ Scene::Scene(const std::string& filename) {
     auto w = splitWords(line);
     if (w.empty()) continue;
     if (w[0] == "MATERIAL") parseMaterial(in, w.size() > 1 ? w[1] : "", materials);
-    else if (w[0] == "OBJECT") parseObject(in, w.size() > 1 ? w[1] : "", geoms, objects);
+    else if (w[0] == "OBJECT") parseObject(in, w.size() > 1 ? w[1] : "", geoms, geom_trs, objects);
     else if (w[0] == "CAMERA") parseCamera(in, *this);
   }
 }

@@ -21,10 +21,16 @@ struct RenderState {  // src/sceneStructs.h:61-67
   std::string imageName;
 };
 
+struct GeomTrs {  // the TRANS / ROTAT / SCALE of the OBJECT a geom came from; mesh: one triangle of a `mesh` object
+  float trs[9];
+  bool mesh;
+};
+
 class Scene {  // src/scene.h:11-26
  public:
   explicit Scene(const std::string& filename);  // throws std::runtime_error if unreadable
   std::vector<PtGeom> geoms;
+  std::vector<GeomTrs> geom_trs;  // beside geoms (pt_scene_geom_trs / pt_scene_set_geom_trs)
   std::vector<PtMaterial> materials;
   RenderState state;
   float fovy = 0.0f;
@@ -37,6 +43,9 @@ class Scene {  // src/scene.h:11-26
   void orbit(float dphi, float dtheta, float dzoom);
   float phi = 0.0f, theta = 0.0f, zoom = 0.0f;  // main.cpp:63-71, set by applyInitialCameraState()
   PtSceneDesc desc() const;
+  // A new TRANS / ROTAT / SCALE for the OBJECT geom `geom` came from (not a mesh triangle): geom_trs and the three matrices, through
+  // the loader's buildTransform.
+  void placeGeom(int geom, const float trs[9]);
 
  private:
   void applyOrbitState();  // main.cpp:112-126: the camera from phi, theta, zoom and lookAt

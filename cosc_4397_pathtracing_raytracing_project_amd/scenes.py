@@ -90,13 +90,18 @@ _LOOKAT = (0, 5, 0)
 
 
 def cornell_scene_text(res: Tuple[int, int] = (800, 800), iterations: int = 1000, depth: int = 8,
-                       name: str = "cornell", eye=None, lookat=None) -> str:
-    """Text equivalent to the reference's scenes/cornell.txt (RES/ITERATIONS/DEPTH adjustable)."""
+                       name: str = "cornell", eye=None, lookat=None, objects=None) -> str:
+    """Text equivalent to the reference's scenes/cornell.txt (RES/ITERATIONS/DEPTH adjustable).  objects: {index: fields} overrides
+    fields of cornell.txt's objects 0..6 by name (kind, material, trans, rotat, scale), e.g. {6: dict(trans=(-2.5, 4, -1), material=2)}
+    for a moved, diffuse sphere; None: the file as it is."""
     out: List[str] = []
     for i, m in enumerate(_CORNELL_MATERIALS):
         out.append(_material(i, **m))
     out.append(_camera(res, 45, iterations, depth, name, eye or _EYE, lookat or _LOOKAT, (0, 1, 0)))
-    for i, (kind, mat, t, r, s) in enumerate(_CORNELL_OBJECTS):
+    for i, obj in enumerate(_CORNELL_OBJECTS):
+        o = dict(zip(("kind", "material", "trans", "rotat", "scale"), obj))
+        o.update((objects or {}).get(i, {}))
+        kind, mat, t, r, s = (o[k] for k in ("kind", "material", "trans", "rotat", "scale"))
         out.append(_object(i, kind, mat, t, r, s))
     return "".join(out)
 

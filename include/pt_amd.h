@@ -237,6 +237,13 @@ int pt_scene_orbit(PtScene* s, float dphi, float dtheta, float dzoom);
 int pt_scene_camera(const PtScene* s, PtCamera* out);
 int pt_scene_orbit_state(const PtScene* s, float* phi, float* theta, float* zoom); /* any pointer may be NULL */
 const char* pt_scene_image_name(const PtScene* s);     /* CAMERA FILE */
+/* The TRANS / ROTAT / SCALE of the OBJECT geom `geom` came from, as the loader read them (trs[0..2] translation, [3..5] rotation in
+ * degrees, [6..8] scale), and moving that object as the loader would have placed it: the setter rebuilds the geom's three matrices
+ * through the loader's own code (pt_build_transform), so they are byte for byte what loading a file with that TRS gives.  Refused
+ * by name: a null argument, an index outside the scene's geoms, a geom that comes from a `mesh` object (its triangles hold
+ * world-space vertices), a component that is not finite.  pt_scene_desc must be called again afterwards, as after pt_scene_orbit. */
+int pt_scene_geom_trs(const PtScene* s, int geom, float trs[9]);
+int pt_scene_set_geom_trs(PtScene* s, int geom, const float trs[9]);
 
 /* BVH exactly as pathtraceInit builds it (pathtrace.cu:34-111, 483-489).
  * Returns node count (2n-1); writes up to `cap` nodes if `out` != NULL. */
@@ -368,6 +375,34 @@ typedef struct PtSetCameraTimes {
   int32_t fallback;  /* 0, or why a requested device build ran on the host (PT_DEVICE_TABLES_*); path is then 0            */
 } PtSetCameraTimes;
 int pt_get_set_camera_times(PtSetCameraTimes* out);
+/* ---- moving the objects of a live renderer: new transforms for the geoms it was created with, without pt_free + pt_init.
+ * Only the three matrices of a geom may change (for a PT_GEOM_TRIANGLE: its vertex words, which live in `transform`); num_geoms and
+ * every type and materialid stay, so the material table, the mesh switch and the per-geom tables of the history stay valid.
+ * Contract: pt_set_camera's, word for word — after a successful call every later call gives what a renderer freshly created from the
+ * same scene with these geoms, the same options and the renderer's current camera gives, bit for bit in all three PT_ARITH_* modes
+ * (image, feature buffers, noise planes, adaptive lists and counts, resolved and filtered images); the timing fields, which traversal
+ * structure is walked and PtStats.device_bytes may differ.
+ * What happens: synchronise; the scene tables are built on the host by the code pt_init runs (the BVH, the top list, the geom table,
+ * the root bounds, everything that follows the camera), with the grid resolution pt_init chose or no grid (a grid that cannot be
+ * built for the new geoms falls back to the BVH scan until a later call allows it again: the camera move's rule) and WITHOUT the
+ * materials: the material table on the device is left alone, so the renderer keeps no materials on the host.  Every table is written
+ * into the buffer it has where its size is unchanged, else into a new one (the top list's length follows the tree).  The device
+ * copy of the camera-independent tables (PT_SET_CAMERA_DEVICE_TABLES) is dropped; the next such move uploads the new one.  Then what
+ * pt_set_camera does after its tables: the launch plan, the worker, the batch buffers' first state, pt_clear.
+ * History: K, the kept camera and the kept geoms survive; C, VC and E become absent.  The plain lookup knows nothing of the move: it
+ * treats the world as static.  PT_HISTORY_MOTION (below) follows moved objects.
+ * Refused, in this order, with nothing changed, allocated or launched: no renderer; a failed renderer; null `geoms`; num_geoms other
+ * than the renderer's; the first geom whose type or materialid differs (named by index); the first geom with a matrix element
+ * that is not finite (named by index). */
+int pt_set_geoms(const PtGeom* geoms, int num_geoms);
+/* The last pt_set_geoms of the renderer, host wall clock, milliseconds; all zero before the first. */
+typedef struct PtSetGeomsTimes {
+  double build_ms;  /* synchronise + the host build of the tables                                          */
+  double upload_ms; /* the tables onto the device                                                          */
+  double rearm_ms;  /* launch plan, path buffers and records back to their first state, the worker, pt_clear */
+  double total_ms;
+} PtSetGeomsTimes;
+int pt_get_set_geoms_times(PtSetGeomsTimes* out);
 /* Host wall-clock times of a renderer's setup, in milliseconds: the host build of the scene tables, their upload, the
  * allocation of the batch buffers, the timing probe of the traversal structures (0 where none ran), and the last pt_set_camera
  * (its synchronise included) with the number of such calls since the renderer was created. */
@@ -1014,6 +1049,41 @@ int pt_history_denoise_moments_counted_host(int w, int rows, const float* rgb_su
                                             const float* current_plane, const float* current_var, const PtDenoiseOptions* opt, float* rgb_avg,
                                             float* var_raw, uint8_t* mark);
 
+/* ---- the history across a moved object: PT_HISTORY_MOTION for pt_history_reproject_ex.  The lookup above assumes a static world: a
+ * pixel of an object that pt_set_geoms moved projects to where the object is now, not to where it was at the capture.  With the flag,
+ * a pixel of a moved geom is first taken back to where its surface point was.
+ * Kept geoms: every capture remembers, beside the kept camera, the geoms the renderer had (a host copy, retaken only when
+ * pt_set_geoms has run since the last copy; a renderer that never moves an object copies once at most and uploads nothing).
+ * Motion table (pt_history_motion_host), per geom g from the kept and the current geom, matrices column-major m[c*4+r]:
+ *   kind[g] = 0 (still) when the 48 matrix words are bytewise equal; 2 (carries nothing) for a changed triangle or when an entry
+ *   below is not finite; 1 (moved) otherwise.
+ *   D[r][c] = (float)(((A_k[r][0]*B_c[0][c] + A_k[r][1]*B_c[1][c]) + A_k[r][2]*B_c[2][c]) + A_k[r][3]*B_c[3][c]), r = 0..2, c = 0..3:
+ *   A_k the kept transform, B_c the current inverseTransform; every factor widened to double, plain double operations in this order.
+ *   Nm[r][c] = (float)((IT_k[r][0]*A_c[c][0] + IT_k[r][1]*A_c[c][1]) + IT_k[r][2]*A_c[c][2]): IT_k the kept invTranspose, A_c the
+ *   current transform, 3 x 3 parts (a normal goes back through the current transform's transpose, forward through the kept inverse
+ *   transpose).  Row g of the table: D as 12 floats row-major, Nm as 9, then 3 zeros (24 floats).
+ * The lookup with the flag is pt_history_reproject[_ex]'s with one step after step 1, for the pixel's geom g = id - 1 (an id outside
+ * 1 .. num_geoms, possible only with keep_view_dependent, counts as still):  kind 0: nothing changes;  kind 2: rejected (C = VC = 0);
+ *   kind 1: p'_x = ((D00*p.x + D01*p.y) + D02*p.z) + D03, y and z likewise;  m = Nm n, each row a dot product as above;  l = m . m;
+ *   rejected unless l > 0;  r = sqrtf(l), correctly rounded;  n' = m / r;  steps 2 - 7 read p', n' for p, n (dz and the plane
+ *   tolerance follow p').  float32, separate IEEE operations, the same bits on host and device in all three builds.
+ * Flags: PT_HISTORY_MOTION alone, or with PT_HISTORY_VARIANCE or PT_HISTORY_MOMENTS (those two together stay refused, first).  Where no
+ * geom moved since the capture the renderer uploads nothing and launches the kernel of the call without the flag: the same planes
+ * bit for bit.  Otherwise 96 + 1 bytes per geom go to the device (allocated by the first such call, counted in device_bytes; the
+ * table is built and uploaded by the first lookup after a capture or a pt_set_geoms changed its inputs, which synchronises) and
+ * k_history_reproject_motion runs.  pt_history_capture_ex does not define the bit.  Without the flag the lookup is what it was and
+ * treats the world as static even after pt_set_geoms.
+ * Caveat: a moved object changes shadows and indirect light on surfaces that stand still.  Nothing detects that: their history goes
+ * stale until `cap` washes it out.
+ * Out of scope: adding or removing objects; material changes; deformation; a device-side tree build; history in groups. */
+#define PT_HISTORY_MOTION 4u
+int pt_history_motion_host(const PtGeom* kept, const PtGeom* cur, int n, float* table /* n * 24 */, uint8_t* kind /* n */);
+/* pt_history_reproject_host / _variance_host / _moments_host (flags & 3 picks which; kept_var, current_var NULL for the plain one)
+ * with the motion step: table and kind as above for num_geoms >= 1 geoms.  PT_HISTORY_MOTION in `flags` is implied. */
+int pt_history_reproject_motion_host(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
+                                     const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, const float* kept_var, const float* table,
+                                     const uint8_t* kind, uint32_t flags, float* current_plane, float* current_var);
+
 /* saveImage()'s per-pixel conversion (main.cpp:91-97 x mirror, image.cpp:26-30 clamp * 255 truncated) on the
  * device: pixel_count*3 bytes, row-major, x mirrored inside each row; the tile must consist of whole rows.
  * Reads back 3 B per pixel instead of 12. */
@@ -1038,6 +1108,8 @@ int pt_ctx_set_camera(PtContext* c, const PtCamera* cam);
 int pt_ctx_get_setup_times(PtContext* c, PtSetupTimes* out);
 int pt_ctx_set_camera_ex(PtContext* c, const PtCamera* cam, uint32_t flags);
 int pt_ctx_get_set_camera_times(PtContext* c, PtSetCameraTimes* out);
+int pt_ctx_set_geoms(PtContext* c, const PtGeom* geoms, int num_geoms);
+int pt_ctx_get_set_geoms_times(PtContext* c, PtSetGeomsTimes* out);
 int pt_ctx_set_reference(PtContext* c, const float* rgb_avg_host);
 int pt_ctx_get_convergence(PtContext* c, int iter_first, int iter_count, double* sse);
 int pt_ctx_iterations_to_clean(PtContext* c, float threshold_db, int* iteration);
@@ -1121,6 +1193,7 @@ int pt_group_sync(PtGroup* g);
  * the whole group as it was; the group's own buffers on the root device stay. */
 int pt_group_set_camera(PtGroup* g, const PtCamera* cam);
 int pt_group_set_camera_ex(PtGroup* g, const PtCamera* cam, uint32_t flags); /* pt_set_camera_ex on every context, asked first in the same way */
+int pt_group_set_geoms(PtGroup* g, const PtGeom* geoms, int num_geoms);      /* pt_set_geoms on every context, asked first in the same way */
 int pt_group_gather(PtGroup* g, float* rgb_sum_host);             /* W*H*3 floats, raw orientation */
 int pt_group_gather_u8(PtGroup* g, float samples, uint8_t* rgb8_host); /* W*H*3 bytes as pt_save_u8, converted on each device */
 /* The feature buffers of the whole frame: every context sums its own rows, the planes meet at the root like the image (one
@@ -1216,7 +1289,7 @@ int pt_stage_intersect_grid(int n, const float* origin, const float* dir, int pr
 int pt_stage_grid_info(PtGridInfo* info, int32_t* max_cell_records);
 /* The camera-dependent tables of the default renderer as they lie on the device, byte for byte: `which` 0 nodes, 1 their centre / half
  * extent copies, 2 the top list, 3 its copies, 4 the cell table of the grid with its guard cells, 5 the grid's records, 6 their copies,
- * 7 the cull margin (4 bytes).  *bytes receives the table's size; up to `cap` bytes of it go to `out` (may be NULL with cap 0).  A
+ * 7 the cull margin (4 bytes), 8 the geom table (which pt_set_geoms rewrites).  *bytes receives the table's size; up to `cap` bytes of it go to `out` (may be NULL with cap 0).  A
  * table the renderer does not have (copies outside the fast build, a grid where none is built) gives *bytes = 0.  Synchronises. */
 int pt_stage_read_tables(int which, void* out, uint64_t cap, uint64_t* bytes);
 /* Device self-check of csrc/pt_camera_tables.h, in the manner of pt_selfcheck_ieee: one of its functions runs on the GPU and on the
@@ -1275,6 +1348,10 @@ int pt_stage_history_denoise(int w, int rows, const float* rgb_sum, const float*
 int pt_stage_history_reproject_moments(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
                                        const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, const float* kept_var, float* current_plane,
                                        float* current_var);
+/* The lookup with the objects' motion through k_history_reproject_motion (pt_history_reproject_motion_host's arguments; rows < 32768). */
+int pt_stage_history_reproject_motion(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
+                                      const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, const float* kept_var, const float* table,
+                                      const uint8_t* kind, uint32_t flags, float* current_plane, float* current_var);
 int pt_stage_history_denoise_moments(int w, int rows, const float* rgb_sum, const float* planes, float samples, const float* current_plane,
                                      const float* current_var, const PtDenoiseOptions* opt, float* rgb_avg);
 /* The history round's key and selection, and its merge, through the device kernels on caller-supplied host arrays
