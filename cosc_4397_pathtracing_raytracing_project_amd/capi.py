@@ -100,6 +100,12 @@ class PtHistoryRoundOptions(C.Structure):
     _fields_ = [("min_history", C.c_float), ("max_fraction", C.c_float)]
 
 
+class PtHistoryProbeOptions(C.Structure):
+    """Options of the history probes' check (include/pt_amd.h: pt_history_probe_check); 0 in a field = its default (radius 0: the
+    pixel's own probe cell, gain 0.25); radius -1 = 0."""
+    _fields_ = [("radius", C.c_int32), ("gain", C.c_float)]
+
+
 class PtSetupTimes(C.Structure):
     """Host wall-clock times of a renderer's setup and of its last camera move, ms (include/pt_amd.h: pt_get_setup_times)."""
     _fields_ = [("tables_ms", C.c_double), ("upload_ms", C.c_double), ("buffers_ms", C.c_double), ("probe_ms", C.c_double),
@@ -409,6 +415,18 @@ def lib() -> C.CDLL:
         L.pt_history_motion_host.argtypes = [_gp, _gp, C.c_int, _fp, _u8p]
         L.pt_history_reproject_motion_host.argtypes = _reproject_motion
         L.pt_stage_history_reproject_motion.argtypes = _reproject_motion
+    if hasattr(L, "pt_history_probe_keep"):  # absent from older A/B builds of the library (tools/build_rev.sh)
+        _hpo = C.POINTER(PtHistoryProbeOptions)
+        L.pt_history_probe_keep.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.pt_history_probe_check.argtypes = [_hpo, _ip, _ip, _ip]
+        L.pt_readback_history_probe.argtypes = [_fp, _fp, _ip]
+        L.pt_ctx_history_probe_keep.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+        L.pt_ctx_history_probe_check.argtypes = [C.c_void_p, _hpo, _ip, _ip, _ip]
+        L.pt_ctx_readback_history_probe.argtypes = [C.c_void_p, _fp, _fp, _ip]
+        L.pt_history_probe_list_host.argtypes = [C.c_int, C.c_int, C.c_int, _ip, _ip]
+        L.pt_history_probe_keep_host.argtypes = [C.c_int, C.c_int, C.c_int, _fp, _fp, _fp]
+        L.pt_history_probe_gradient_host.argtypes = [C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _u8p, C.c_int, _fp, _ip, _ip]
+        L.pt_history_probe_apply_host.argtypes = [C.c_int, C.c_int, C.c_int, _fp, _fp, _u8p, C.c_int, _hpo, _fp]
     _lib = L
     return L
 
@@ -913,6 +931,69 @@ def stage_history_denoise_moments(rgb_sum, planes, w: int, rows: int, samples: f
                    None if v is None else _f(v), **opts)
 
 
+# ---- the history probes: kept samples rendered again after a move (include/pt_amd.h: pt_history_probe_keep) ----
+def history_probe_options(radius: int = 0, gain: float = 0.0) -> PtHistoryProbeOptions:
+    """PtHistoryProbeOptions; 0 = the default of a field, radius -1 = 0."""
+    return PtHistoryProbeOptions(int(radius), float(gain))
+
+
+def history_probe_list_host(w: int, rows: int, phase: int) -> np.ndarray:
+    """The tile pixels of the probes of a w x rows tile at `phase`, int32 [P], ascending (pt_history_probe_list_host; no GPU)."""
+    count = C.c_int32(-1)
+    _check(lib().pt_history_probe_list_host(int(w), int(rows), int(phase), None, C.byref(count)))
+    lst = np.full(count.value, -1, np.int32)
+    _check(lib().pt_history_probe_list_host(int(w), int(rows), int(phase), _i(lst) if lst.size else None, C.byref(count)))
+    return lst
+
+
+def _probe_moved(moved):
+    m = np.ascontiguousarray(moved, np.uint8).reshape(-1)
+    return m, (m.ctypes.data_as(C.POINTER(C.c_uint8)) if m.size else None)
+
+
+def history_probe_keep_host(rgb_sum, planes, w: int, rows: int, phase: int) -> np.ndarray:
+    """PK of pt_history_probe_keep on the host (no GPU): the SUM image [n, 3] and the feature SUM planes in, float32 [P, 4] out."""
+    s = np.ascontiguousarray(rgb_sum, np.float32).reshape(-1)
+    p = np.ascontiguousarray(planes, np.float32).reshape(-1)
+    n = w * rows
+    if s.size != 3 * n or p.size != 4 * FEATURE_PLANES * n:
+        raise PtError(f"history_probe_keep: {s.size} image and {p.size} plane floats for a tile of {w}x{rows}")
+    kept = np.zeros((history_probe_list_host(w, rows, phase).size, 4), np.float32)
+    _check(lib().pt_history_probe_keep_host(int(w), int(rows), int(phase), _f(s), _f(p), _f(kept) if kept.size else None))
+    return kept
+
+
+def history_probe_gradient_host(kept, group_sum, planes, w: int, rows: int, phase: int, moved=()):
+    """The probes' gradient on the host (pt_history_probe_gradient_host; no GPU): PK [P, 4], the replayed sums [P, 3], the feature
+    SUM planes and moved_geom in; (L float32 [P], changed, skipped) out."""
+    k = np.ascontiguousarray(kept, np.float32).reshape(-1)
+    b = np.ascontiguousarray(group_sum, np.float32).reshape(-1)
+    p = np.ascontiguousarray(planes, np.float32).reshape(-1)
+    P = history_probe_list_host(w, rows, phase).size
+    if k.size != 4 * P or b.size != 3 * P or p.size != 4 * FEATURE_PLANES * w * rows:
+        raise PtError(f"history_probe_gradient: {k.size} kept, {b.size} group and {p.size} plane floats for {P} probes of {w}x{rows}")
+    m, mp = _probe_moved(moved)
+    lam = np.zeros(P, np.float32)
+    changed, skipped = C.c_int32(-1), C.c_int32(-1)
+    _check(lib().pt_history_probe_gradient_host(int(w), int(rows), int(phase), _f(k) if P else None, _f(b) if P else None, _f(p), mp, int(m.size),
+                                                _f(lam) if P else None, C.byref(changed), C.byref(skipped)))
+    return lam, int(changed.value), int(skipped.value)
+
+
+def history_probe_apply_host(current, lam, planes, w: int, rows: int, phase: int, moved=(), radius: int = 0, gain: float = 0.0) -> np.ndarray:
+    """The probes' apply on the host (pt_history_probe_apply_host; no GPU): a copy of the current plane [n, 4] with C.w shortened."""
+    c = np.array(current, np.float32).reshape(-1)
+    l = np.ascontiguousarray(lam, np.float32).reshape(-1)
+    p = np.ascontiguousarray(planes, np.float32).reshape(-1)
+    n = w * rows
+    if c.size != 4 * n or p.size != 4 * FEATURE_PLANES * n or l.size != history_probe_list_host(w, rows, phase).size:
+        raise PtError(f"history_probe_apply: {c.size} current, {l.size} lam and {p.size} plane floats for a tile of {w}x{rows}")
+    m, mp = _probe_moved(moved)
+    opt = history_probe_options(radius, gain)
+    _check(lib().pt_history_probe_apply_host(int(w), int(rows), int(phase), _f(l) if l.size else None, _f(p), mp, int(m.size), C.byref(opt), _f(c)))
+    return c.reshape(-1, 4)
+
+
 # ---- the history round: extra samples for the pixels whose history is short (include/pt_amd.h: pt_history_round) ----
 HISTORY_ROUND_MIN_HISTORY = np.float32(4.0)  # PT_HISTORY_ROUND_MIN_HISTORY
 
@@ -1394,6 +1475,28 @@ class Renderer:
         fresh, selected = C.c_int32(-1), C.c_int32(-1)
         _check(lib().pt_history_round(int(iter_first), int(group_iters), C.byref(opt), C.byref(fresh), C.byref(selected)))
         return int(fresh.value), int(selected.value)
+
+    def history_probe_keep(self, iter_first: int, iter_count: int, phase: int = 0) -> None:
+        """Keeps every third pixel of every third row of the image — iterations iter_first .. iter_first + iter_count - 1, all it holds —
+        as probes for the next view (pt_history_probe_keep; asynchronous)."""
+        _check(lib().pt_history_probe_keep(int(iter_first), int(iter_count), int(phase)))
+
+    def history_probe_check(self, radius: int = 0, gain: float = 0.0):
+        """Renders the kept probes again in the world as it is now and shortens the carried history C.w around those that differ
+        (pt_history_probe_check; synchronises once): (probes, changed, skipped)."""
+        opt = history_probe_options(radius, gain)
+        probes, changed, skipped = C.c_int32(-1), C.c_int32(-1), C.c_int32(-1)
+        _check(lib().pt_history_probe_check(C.byref(opt), C.byref(probes), C.byref(changed), C.byref(skipped)))
+        return int(probes.value), int(changed.value), int(skipped.value)
+
+    def readback_history_probe(self):
+        """(PK float32 [P, 4], L float32 [P]; zeros before a check) of the kept probes; P = 0 when nothing is kept."""
+        count = C.c_int32(-1)
+        _check(lib().pt_readback_history_probe(None, None, C.byref(count)))
+        kept, lam = np.zeros((count.value, 4), np.float32), np.zeros(count.value, np.float32)
+        if count.value:
+            _check(lib().pt_readback_history_probe(_f(kept), _f(lam), C.byref(count)))
+        return kept, lam
 
     def readback_history_extra(self) -> np.ndarray:
         """The extra plane E, float32 [n]: the samples a pixel holds beyond the uniform ones; zeros while absent."""

@@ -989,6 +989,7 @@ int pt_ctx_clear(PtContext* c) {
   c->hist_var_current = 0;  // the history's current planes are absent; its kept planes stay (pt_history.h)
   if (c->d_hist_extra) HIP_OK(hipMemsetAsync(c->d_hist_extra, 0, (size_t)c->N * sizeof(float), c->stream));  // the extras belong to the image
   c->hist_extra = false;
+  c->probe_checked = c->probe_applied = false;  // the probes' L belongs to C; PK stays
   if (c->conv) {  // forget the curve, re-arm the capture (a supplied frame stays)
     HIP_OK(hipMemsetAsync(c->d_sse, 0xff, (size_t)PT_CONVERGENCE_CAPACITY * sizeof(double), c->stream));
     c->conv_last = 0;
@@ -1282,6 +1283,7 @@ int set_geoms(PtContext* c, const PtGeom* geoms, int num_geoms) {  // after the 
   }
   g.camera_base = std::move(base);
   g.hist_geoms_stale = true, g.hist_motion_fresh = false;  // (the next capture keeps these geoms; K and the kept geoms stay until then)
+  g.probe_geoms_stale = g.probe_geoms_changed = true;  // (the next keep copies these geoms; the next check compares them with the kept ones)
   times.upload_ms = ms_since(t1);
   const auto t2 = clock::now();
   plan_launch(g);
@@ -1465,6 +1467,11 @@ int pt_history_round(int iter_first, int group_iters, const PtHistoryRoundOption
   return pt_ctx_history_round(g_default, iter_first, group_iters, opt, fresh, selected);
 }
 int pt_readback_history_extra(float* extra_host) { return pt_ctx_readback_history_extra(g_default, extra_host); }
+int pt_history_probe_keep(int iter_first, int iter_count, int phase) { return pt_ctx_history_probe_keep(g_default, iter_first, iter_count, phase); }
+int pt_history_probe_check(const PtHistoryProbeOptions* opt, int* probes, int* changed, int* skipped) {
+  return pt_ctx_history_probe_check(g_default, opt, probes, changed, skipped);
+}
+int pt_readback_history_probe(float* kept, float* lam, int* count) { return pt_ctx_readback_history_probe(g_default, kept, lam, count); }
 int pt_set_reference(const float* rgb_avg_host) { return pt_ctx_set_reference(g_default, rgb_avg_host); }
 int pt_get_convergence(int iter_first, int iter_count, double* sse) { return pt_ctx_get_convergence(g_default, iter_first, iter_count, sse); }
 int pt_iterations_to_clean(float threshold_db, int* iteration) { return pt_ctx_iterations_to_clean(g_default, threshold_db, iteration); }

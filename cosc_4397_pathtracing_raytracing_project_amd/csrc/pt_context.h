@@ -182,6 +182,20 @@ struct PtContext : PtShared {
   float* d_hist_extra = nullptr;   // the extra plane E: N floats, the samples the image holds per pixel beyond the uniform ones
   bool hist_extra = false;         // E is present: from a round that rendered to pt_clear or a camera move, which zero it
   uint8_t* d_hist_emitter = nullptr;  // one byte per geom: its material emits (the first round builds it)
+  // The history probes (pt_ctx_history_probe_keep / _check): all of it absent until the first keep (d_probe) or check (the rest)
+  void* d_probe = nullptr;         // PK: 16 B per probe, for the probes of phase 0 (the most of any phase)
+  float* d_probe_lam = nullptr;    // L: one float per probe (as many as PK), then the two counts {changed, skipped} as int32
+  uint8_t* d_probe_moved = nullptr;  // one byte per geom: its matrices differ from the kept geoms'
+  std::vector<uint8_t> probe_moved_dev;  // what d_probe_moved holds
+  bool probe_kept = false;         // PK holds probes (pt_ctx_history_drop forgets them)
+  int probe_first = 0, probe_iters = 0, probe_phase = 0;  // the iterations S held at the keep, and the probes' phase
+  int probe_N = 0, probe_begin = 0;  // the tile they were kept for
+  PtCamera probe_cam{};            // the camera at the keep
+  std::vector<PtGeom> probe_geoms;  // the geoms at the keep
+  bool probe_geoms_stale = true;   // pt_ctx_set_geoms has run since probe_geoms was copied (or nothing was copied yet)
+  bool probe_geoms_changed = false;  // pt_ctx_set_geoms has run since the keep
+  bool probe_checked = false;      // L is the check of these probes against the C that is present
+  bool probe_applied = false;      // a check has been applied to this C (the next lookup clears it)
   bool feat_fresh = false;         // a feature pass has run since pt_init / pt_clear / the last camera move
   // Moving the camera (pt_ctx_set_camera): the camera-independent tables on the host, and the grid to rebuild (the one init kept)
   pt::CameraBase camera_base;

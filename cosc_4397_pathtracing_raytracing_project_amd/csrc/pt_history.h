@@ -26,6 +26,10 @@
 // moments read ns = samples + E_p where they read `samples`: the Counted instantiations, beside the ones that take a float and are
 // the bodies as they stood.
 //
+// The history probes (pt_history_probe_keep / _check; probe_grid, probe_keep, probe_gradient and probe_apply below): a sparse grid of
+// last view's sums, rendered again after an object moved — a sample is a pure function of (iteration, pixel, world), so the two sums
+// differ exactly where a path met something that changed — and C.w shortened around the probes that differ.
+//
 // Out of scope (pt_amd.h says the same): pt_group_* (a context's interleaved rows cannot look up their neighbours), feeding the
 // history into the noise estimate, the history round in groups of contexts, a key that uses the carried variance, feeding the FILTERED image back into the history (K keeps the unfiltered
 // blend), objects that are added, removed or deformed (rigid and affine motion of an object: PT_HISTORY_MOTION), and correcting the smoothing the bilinear lookup adds — the carried image is a biased estimator, and the carried
@@ -412,6 +416,10 @@ inline void reproject_motion_host(const View& v, const float* K, const float* fe
 }
 // The motion table of pt_amd.h (pt_history_motion_host): row g and kind[g] from the kept and the current geom g.  Every factor is
 // widened to double, the products and sums are plain double operations in the order written, the result is rounded to float once.
+inline bool same_matrices(const PtGeom& k, const PtGeom& c) {  // the 48 matrix words, bytewise
+  return __builtin_memcmp(k.transform, c.transform, 64) == 0 && __builtin_memcmp(k.inverseTransform, c.inverseTransform, 64) == 0 &&
+         __builtin_memcmp(k.invTranspose, c.invTranspose, 64) == 0;
+}
 inline void motion_table(const PtGeom* kept, const PtGeom* cur, int n, float* table, uint8_t* kind) {
 #pragma clang fp contract(off)
   for (int g = 0; g < n; ++g) {
@@ -428,8 +436,7 @@ inline void motion_table(const PtGeom* kept, const PtGeom* cur, int n, float* ta
         row[12 + r * 3 + col] = (float)((at(k.invTranspose, r, 0) * at(c.transform, col, 0) + at(k.invTranspose, r, 1) * at(c.transform, col, 1)) +
                                         at(k.invTranspose, r, 2) * at(c.transform, col, 2));
     row[21] = row[22] = row[23] = 0.0f;
-    const bool same = __builtin_memcmp(k.transform, c.transform, 64) == 0 && __builtin_memcmp(k.inverseTransform, c.inverseTransform, 64) == 0 &&
-                      __builtin_memcmp(k.invTranspose, c.invTranspose, 64) == 0;
+    const bool same = same_matrices(k, c);
     bool finite = true;
     for (int j = 0; j < 21; ++j) finite = finite && row[j] - row[j] == 0.0f;
     kind[g] = same ? kStill : (k.type == PT_GEOM_TRIANGLE || c.type == PT_GEOM_TRIANGLE || !finite) ? kCarriesNothing : kMoved;
@@ -513,6 +520,111 @@ inline void capture_moments_counted_host(size_t npix, const float* S, float samp
   const F4* c4 = reinterpret_cast<const F4*>(C);
   const MomCapture<F4> mom{reinterpret_cast<const F4*>(VC), reinterpret_cast<F4*>(VK)};
   for (size_t i = 0; i < npix; ++i) capture_moments_pixel(i, S, samples_of(Counted{samples, E}, i), c4 ? c4[i].w : 0.0f, mom);
+}
+
+// ── the history probes (pt_history_probe_keep / _check) ──────────────────────────────────────────────────────────────────
+// A sparse grid of last view's samples, rendered again in the world as it is now: a sample is a pure function of (iteration, pixel,
+// world), so the two sums differ exactly where a path met something that changed.  What the difference finds is written into C.w,
+// the carried weight, which everything downstream reads already.  probe_grid places the probes, probe_keep is what is kept of one,
+// probe_gradient compares a kept probe with its replay, probe_apply shortens the history of one tile pixel.
+struct ProbeGrid {
+  int ox, oy, PW, PR;  // probe (i, j) sits at tile pixel (3 i + ox, 3 j + oy); i < PW, j < PR
+};
+PT_HD ProbeGrid probe_grid(int W, int R, int phase) {
+  const int ox = phase % 3, oy = phase / 3;
+  return ProbeGrid{ox, oy, W > ox ? (W - ox + 2) / 3 : 0, R > oy ? (R - oy + 2) / 3 : 0};
+}
+PT_HD int probe_count(const ProbeGrid& pg) { return pg.PW * pg.PR; }
+// the tile pixel of probe s = j * PW + i: ascending in s
+PT_HD int32_t probe_pixel(const ProbeGrid& pg, int W, int s) { return (3 * (s / pg.PW) + pg.oy) * W + 3 * (s % pg.PW) + pg.ox; }
+// PtHistoryProbeOptions with the defaults filled in; the message of a refusal, or nullptr.
+struct ProbeParams {
+  int radius;
+  float gain;
+};
+inline const char* resolve_probe(const PtHistoryProbeOptions* opt, ProbeParams* out) {
+  PtHistoryProbeOptions o{};
+  if (opt) o = *opt;
+  if (o.radius == 0) o.radius = PT_HISTORY_PROBE_RADIUS;
+  if (o.radius == -1) o.radius = 0;
+  if (o.radius < 0 || o.radius > 4) return "radius is 1 .. 4, or -1 for 0";
+  if (!(o.gain - o.gain == 0.0f)) return "an option is not finite";
+  if (o.gain == 0.0f) o.gain = PT_HISTORY_PROBE_GAIN;
+  if (!(o.gain > 0.0f)) return "gain must be positive";
+  *out = ProbeParams{o.radius, o.gain};
+  return nullptr;
+}
+// What is kept of the probe at tile pixel p: its sum and the id of its first hit (0 on a miss), read as the capture reads it.
+template <typename P4>
+PT_HD P4 probe_keep(size_t p, size_t npix, const float* S, const P4* feat) {
+  const int32_t id = feat[npix + p].w > 0.0f ? float_bits(feat[2 * npix + p].w) : 0;
+  return P4{S[3 * p], S[3 * p + 1], S[3 * p + 2], bits_float(id)};
+}
+// L[s] of the kept probe k at tile pixel p against its replay Sw[3 s ..]: -1 skipped (the pixel shows another object now, nothing, an
+// id outside 1 .. num_geoms or a geom that moved: moved, one byte per geom), else the relative difference of the two sums, at most 1;
+// a NaN reads as 1.  Exactly +0 where the replayed paths met nothing that changed.
+template <typename P4>
+PT_HD float probe_gradient(size_t s, size_t p, size_t npix, const P4& k, const float* Sw, const P4* feat, const uint8_t* moved, int32_t num_geoms) {
+#pragma clang fp contract(off)
+  const int32_t id = feat[npix + p].w > 0.0f ? float_bits(feat[2 * npix + p].w) : 0;
+  if (id != float_bits(k.w) || id < 1 || id > num_geoms || moved[id - 1]) return -1.0f;
+  const float wx = Sw[3 * s], wy = Sw[3 * s + 1], wz = Sw[3 * s + 2];
+  const float d = (__builtin_fabsf(wx - k.x) + __builtin_fabsf(wy - k.y)) + __builtin_fabsf(wz - k.z);
+  const float mo = (k.x + k.y) + k.z, mw = (wx + wy) + wz;
+  const float m = mo > mw ? mo : mw;
+  const float lam = m > 0.0f ? d / m : 0.0f;
+  return lam < 1.0f ? lam : 1.0f;
+}
+// Tile pixel i = (x, r): C.w shortened by the largest L of the probes within `radius` probe cells; every word kept for a miss, an id
+// outside 1 .. num_geoms, a moved geom (PT_HISTORY_MOTION's business) and where that maximum is 0.  Only C[i].w is read and written.
+template <typename P4>
+PT_HD void probe_apply(size_t i, int W, int R, const ProbeGrid& pg, const float* L, const P4* feat, const uint8_t* moved, int32_t num_geoms,
+                       const ProbeParams& P, P4* C) {
+#pragma clang fp contract(off)
+  const size_t npix = (size_t)W * R;
+  const int32_t id = float_bits(feat[2 * npix + i].w);
+  if (!(feat[npix + i].w > 0.0f) || id < 1 || id > num_geoms || moved[id - 1]) return;
+  const int x = (int)(i % (size_t)W), r = (int)(i / (size_t)W);
+  const int i0 = x / 3, j0 = r / 3;
+  float lam = 0.0f;
+  for (int j = j0 - P.radius; j <= j0 + P.radius; ++j) {
+    if (j < 0 || j >= pg.PR) continue;
+    for (int ii = i0 - P.radius; ii <= i0 + P.radius; ++ii) {
+      if (ii < 0 || ii >= pg.PW) continue;
+      const float l = L[(size_t)j * pg.PW + ii];
+      lam = l > lam ? l : lam;
+    }
+  }
+  if (!(lam > 0.0f)) return;
+  float g = lam * P.gain;
+  g = g < 1.0f ? g : 1.0f;
+  C[i].w = C[i].w * (1.0f - g);
+}
+// 1 where the 48 matrix words of geom g differ bytewise from the kept geom's: motion_table's kind != kStill
+inline void probe_moved(const PtGeom* kept, const PtGeom* cur, int n, uint8_t* moved) {
+  for (int g = 0; g < n; ++g) moved[g] = same_matrices(kept[g], cur[g]) ? 0 : 1;
+}
+// The whole tile on the host.
+inline void probe_keep_host(int W, int R, int phase, const float* S, const float* feat, float* kept) {
+  const ProbeGrid pg = probe_grid(W, R, phase);
+  for (int s = 0; s < probe_count(pg); ++s)
+    reinterpret_cast<F4*>(kept)[s] = probe_keep((size_t)probe_pixel(pg, W, s), (size_t)W * R, S, reinterpret_cast<const F4*>(feat));
+}
+inline void probe_gradient_host(int W, int R, int phase, const float* kept, const float* Sw, const float* feat, const uint8_t* moved, int32_t num_geoms,
+                                float* L, int* changed, int* skipped) {
+  const ProbeGrid pg = probe_grid(W, R, phase);
+  int nc = 0, ns = 0;
+  for (int s = 0; s < probe_count(pg); ++s) {
+    L[s] = probe_gradient((size_t)s, (size_t)probe_pixel(pg, W, s), (size_t)W * R, reinterpret_cast<const F4*>(kept)[s], Sw, reinterpret_cast<const F4*>(feat),
+                          moved, num_geoms);
+    nc += L[s] > 0.0f, ns += L[s] < 0.0f;
+  }
+  if (changed) *changed = nc;
+  if (skipped) *skipped = ns;
+}
+inline void probe_apply_host(int W, int R, int phase, const float* L, const float* feat, const uint8_t* moved, int32_t num_geoms, const ProbeParams& P, float* C) {
+  const ProbeGrid pg = probe_grid(W, R, phase);
+  for (size_t i = 0; i < (size_t)W * R; ++i) probe_apply(i, W, R, pg, L, reinterpret_cast<const F4*>(feat), moved, num_geoms, P, reinterpret_cast<F4*>(C));
 }
 
 }  // namespace pthi

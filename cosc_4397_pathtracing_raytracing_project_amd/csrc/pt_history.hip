@@ -30,6 +30,15 @@
 //                        4 B of E read and written at the listed pixel
 //   k_history_capture_counted<kPlain | kMoments>, k_history_blend_counted   the kernels above with 4 B of E more per pixel in and
 //                        ns = samples + E_p for `samples` (pthi::Counted); launched only while E is present
+// The history probes (pt_history_probe_keep / _check), P probes of a tile of W x R:
+//   k_history_probe_keep      one thread per probe: 12 B of S and the .w words of s1 and s2 at every third pixel of every third row
+//                             (a gather: one pixel of three per line moved), 16 B of PK out, streaming
+//   k_history_probe_list      one thread per probe: 4 B of the rounds' list out
+//   k_history_probe_gradient  one thread per probe: 16 B of PK and 12 B of Sw in (streaming), the same two feature words, one byte of
+//                             `moved` for a hit, 4 B of L out; one integer atomic per wave and count (the compiler's wave reduction)
+//   k_history_probe_apply     one thread per tile pixel: the .w words of s1 and s2 as k_history_key reads them, one byte of `moved`,
+//                             up to (2 radius + 1)^2 words of L (4 B per probe: a ninth of a word per pixel, L1's and L2's), and
+//                             C.w read and written in place where the maximum is above 0.  No LDS, no scratch
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -122,6 +131,32 @@ __global__ __launch_bounds__(kBlock) void k_history_merge(int npix, int m, const
                                                           float* E) {
   const int i = blockIdx.x * kBlock + threadIdx.x;
   if (i < m && (uint32_t)list[i] < (uint32_t)npix) pthi::merge_entry((size_t)i, list, Sw, gf, S, E);
+}
+
+__global__ __launch_bounds__(kBlock) void k_history_probe_keep(int P, int W, int npix, pthi::ProbeGrid pg, const float* __restrict__ S, const V4* __restrict__ feat,
+                                                               V4* __restrict__ PK) {
+  const int s = blockIdx.x * kBlock + threadIdx.x;
+  if (s < P) PK[s] = pthi::probe_keep((size_t)pthi::probe_pixel(pg, W, s), (size_t)npix, S, feat);
+}
+__global__ __launch_bounds__(kBlock) void k_history_probe_list(int P, int W, pthi::ProbeGrid pg, int32_t* __restrict__ list) {
+  const int s = blockIdx.x * kBlock + threadIdx.x;
+  if (s < P) list[s] = pthi::probe_pixel(pg, W, s);
+}
+// counts: {changed, skipped}, zeroed on the stream before the launch
+__global__ __launch_bounds__(kBlock) void k_history_probe_gradient(int P, int W, int npix, pthi::ProbeGrid pg, const V4* __restrict__ PK, const float* __restrict__ Sw,
+                                                                   const V4* __restrict__ feat, const uint8_t* __restrict__ moved, int num_geoms,
+                                                                   float* __restrict__ L, int* counts) {
+  const int s = blockIdx.x * kBlock + threadIdx.x;
+  if (s >= P) return;
+  const float l = pthi::probe_gradient((size_t)s, (size_t)pthi::probe_pixel(pg, W, s), (size_t)npix, PK[s], Sw, feat, moved, num_geoms);
+  L[s] = l;
+  if (l > 0.0f) atomicAdd(&counts[0], 1);
+  if (l < 0.0f) atomicAdd(&counts[1], 1);
+}
+__global__ __launch_bounds__(kBlock) void k_history_probe_apply(int W, int R, pthi::ProbeGrid pg, const float* __restrict__ L, const V4* __restrict__ feat,
+                                                                const uint8_t* __restrict__ moved, int num_geoms, pthi::ProbeParams P, V4* C) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < W * R) pthi::probe_apply((size_t)i, W, R, pg, L, feat, moved, num_geoms, P, C);
 }
 
 int launched(const char* who) {
@@ -271,6 +306,56 @@ int pt_history_merge_launch(hipStream_t stream, int pixels, float* rgb_sum_dev, 
   hipLaunchKernelGGL(k_history_merge, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, pixels, m, list_dev, group_sum_dev, (float)group_iters, rgb_sum_dev,
                      extra_dev);
   return launched("pt_history_round");
+}
+
+// The history probes.  pg = pthi::probe_grid(w, rows, phase) with P = pthi::probe_count(pg) >= 1 probes; every index a kernel forms
+// lies inside the tile (probe_pixel < w * rows) or the P entries of probe_dev / list_dev / lam_dev / group_sum_dev.
+static bool bad_probes(int w, int rows, int phase) { return bad_frame(w, rows) || phase < 0 || phase > 8 || pthi::probe_count(pthi::probe_grid(w, rows, phase)) < 1; }
+int pt_history_probe_keep_launch(hipStream_t stream, int w, int rows, int phase, const float* rgb_sum_dev, const float* planes_dev, void* probe_dev) {
+  if (bad_probes(w, rows, phase) || !rgb_sum_dev || !planes_dev || !probe_dev) return pt_fail("pt_history_probe_keep: bad argument");
+  const pthi::ProbeGrid pg = pthi::probe_grid(w, rows, phase);
+  const int P = pthi::probe_count(pg);
+  hipLaunchKernelGGL(k_history_probe_keep, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, P, w, w * rows, pg, rgb_sum_dev,
+                     reinterpret_cast<const V4*>(planes_dev), static_cast<V4*>(probe_dev));
+  return launched("pt_history_probe_keep");
+}
+int pt_history_probe_list_launch(hipStream_t stream, int w, int rows, int phase, int32_t* list_dev) {
+  if (bad_probes(w, rows, phase) || !list_dev) return pt_fail("pt_history_probe_check: bad argument");
+  const pthi::ProbeGrid pg = pthi::probe_grid(w, rows, phase);
+  const int P = pthi::probe_count(pg);
+  hipLaunchKernelGGL(k_history_probe_list, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, P, w, pg, list_dev);
+  return launched("pt_history_probe_check");
+}
+// counts_dev: two int32 {changed, skipped}, zeroed here on the stream
+int pt_history_probe_gradient_launch(hipStream_t stream, int w, int rows, int phase, const void* probe_dev, const float* group_sum_dev, const float* planes_dev,
+                                     const uint8_t* moved_dev, int num_geoms, float* lam_dev, int* counts_dev) {
+  if (bad_probes(w, rows, phase) || !probe_dev || !group_sum_dev || !planes_dev || !lam_dev || !counts_dev || num_geoms < 0 || (num_geoms > 0 && !moved_dev))
+    return pt_fail("pt_history_probe_check: bad argument");
+  const pthi::ProbeGrid pg = pthi::probe_grid(w, rows, phase);
+  const int P = pthi::probe_count(pg);
+  if (hipMemsetAsync(counts_dev, 0, 2 * sizeof(int), stream) != hipSuccess) return pt_fail("pt_history_probe_check: clearing the counts failed");
+  hipLaunchKernelGGL(k_history_probe_gradient, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, P, w, w * rows, pg, static_cast<const V4*>(probe_dev),
+                     group_sum_dev, reinterpret_cast<const V4*>(planes_dev), moved_dev, num_geoms, lam_dev, counts_dev);
+  return launched("pt_history_probe_check");
+}
+int pt_history_probe_apply_launch(hipStream_t stream, int w, int rows, int phase, const float* lam_dev, const float* planes_dev, const uint8_t* moved_dev,
+                                  int num_geoms, const pthi::ProbeParams& P, void* current_dev) {
+  if (bad_probes(w, rows, phase) || !lam_dev || !planes_dev || !current_dev || num_geoms < 0 || (num_geoms > 0 && !moved_dev) || P.radius < 0 || P.radius > 4)
+    return pt_fail("pt_history_probe_check: bad argument");
+  const int npix = w * rows;
+  hipLaunchKernelGGL(k_history_probe_apply, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, w, rows, pthi::probe_grid(w, rows, phase), lam_dev,
+                     reinterpret_cast<const V4*>(planes_dev), moved_dev, num_geoms, P, static_cast<V4*>(current_dev));
+  return launched("pt_history_probe_check");
+}
+int pt_history_probe_options(const char* who, const PtHistoryProbeOptions* opt, pthi::ProbeParams* P) {
+  if (const char* msg = pthi::resolve_probe(opt, P)) return pt_fail("%s: %s", who, msg);
+  return 0;
+}
+// What the host forms refuse first: the frame and the phase.
+static int probe_frame_check(const char* who, int w, int rows, int phase) {
+  if (w <= 0 || rows <= 0 || (int64_t)w * rows > (1ll << 30)) return pt_fail("%s: a tile of %d x %d pixels is not supported", who, w, rows);
+  if (phase < 0 || phase > 8) return pt_fail("%s: phase %d is not in 0 .. 8", who, phase);
+  return 0;
 }
 
 int pt_history_round_options(const char* who, const PtHistoryRoundOptions* opt, pthi::RoundParams* P) {
@@ -471,5 +556,46 @@ extern "C" int pt_history_capture_moments_counted_host(int pixels, const float* 
   if (pt_history_check_samples(who, samples) || pt_history_check_extra(who, pixels, extra)) return -1;
   if (!current_plane != !current_var) return pt_fail("%s: the current plane and its moments come together or not at all", who);
   pthi::capture_moments_counted_host((size_t)pixels, rgb_sum, samples, extra, current_plane, current_var, kept_var);
+  return 0;
+}
+
+// ---- the history probes on the host ---------------------------------------------------------------------------------------
+extern "C" int pt_history_probe_list_host(int w, int rows, int phase, int32_t* list, int* count) {
+  const char* who = "pt_history_probe_list_host";
+  if (probe_frame_check(who, w, rows, phase)) return -1;
+  if (!count) return pt_fail("%s: null count", who);
+  const pthi::ProbeGrid pg = pthi::probe_grid(w, rows, phase);
+  *count = pthi::probe_count(pg);
+  for (int s = 0; list && s < *count; ++s) list[s] = pthi::probe_pixel(pg, w, s);
+  return 0;
+}
+extern "C" int pt_history_probe_keep_host(int w, int rows, int phase, const float* rgb_sum, const float* feature_planes, float* kept) {
+  const char* who = "pt_history_probe_keep_host";
+  if (probe_frame_check(who, w, rows, phase)) return -1;
+  const int P = pthi::probe_count(pthi::probe_grid(w, rows, phase));
+  if (!rgb_sum || !feature_planes || (P > 0 && !kept)) return pt_fail("%s: null argument", who);
+  pthi::probe_keep_host(w, rows, phase, rgb_sum, feature_planes, kept);
+  return 0;
+}
+extern "C" int pt_history_probe_gradient_host(int w, int rows, int phase, const float* kept, const float* group_sum, const float* feature_planes,
+                                              const uint8_t* moved_geom, int num_geoms, float* lam, int* changed, int* skipped) {
+  const char* who = "pt_history_probe_gradient_host";
+  if (probe_frame_check(who, w, rows, phase)) return -1;
+  const int P = pthi::probe_count(pthi::probe_grid(w, rows, phase));
+  if (!feature_planes || (P > 0 && (!kept || !group_sum || !lam))) return pt_fail("%s: null argument", who);
+  if (num_geoms < 0 || (num_geoms > 0 && !moved_geom)) return pt_fail("%s: null moved_geom for %d geoms", who, num_geoms);
+  pthi::probe_gradient_host(w, rows, phase, kept, group_sum, feature_planes, moved_geom, num_geoms, lam, changed, skipped);
+  return 0;
+}
+extern "C" int pt_history_probe_apply_host(int w, int rows, int phase, const float* lam, const float* feature_planes, const uint8_t* moved_geom, int num_geoms,
+                                           const PtHistoryProbeOptions* opt, float* current_plane) {
+  const char* who = "pt_history_probe_apply_host";
+  if (probe_frame_check(who, w, rows, phase)) return -1;
+  const int P = pthi::probe_count(pthi::probe_grid(w, rows, phase));
+  if (!feature_planes || !current_plane || (P > 0 && !lam)) return pt_fail("%s: null argument", who);
+  if (num_geoms < 0 || (num_geoms > 0 && !moved_geom)) return pt_fail("%s: null moved_geom for %d geoms", who, num_geoms);
+  pthi::ProbeParams pp{};
+  if (pt_history_probe_options(who, opt, &pp)) return -1;
+  pthi::probe_apply_host(w, rows, phase, lam, feature_planes, moved_geom, num_geoms, pp, current_plane);
   return 0;
 }

@@ -143,6 +143,20 @@ namespace pthi {
 struct RoundParams;
 }
 int pt_history_round_options(const char* who, const PtHistoryRoundOptions* opt, pthi::RoundParams* P);
+// The history probes (pt_history_probe_keep / _check) of a tile of w x rows at `phase` with at least one probe: probe_dev PK (16 B per
+// probe), list_dev the rounds' list, group_sum_dev the worker's sum, lam_dev L, counts_dev two int32 (zeroed by the gradient's launch),
+// moved_dev one byte per geom.
+struct PtHistoryProbeOptions;
+namespace pthi {
+struct ProbeParams;
+}
+int pt_history_probe_options(const char* who, const PtHistoryProbeOptions* opt, pthi::ProbeParams* P);
+int pt_history_probe_keep_launch(hipStream_t stream, int w, int rows, int phase, const float* rgb_sum_dev, const float* planes_dev, void* probe_dev);
+int pt_history_probe_list_launch(hipStream_t stream, int w, int rows, int phase, int32_t* list_dev);
+int pt_history_probe_gradient_launch(hipStream_t stream, int w, int rows, int phase, const void* probe_dev, const float* group_sum_dev, const float* planes_dev,
+                                     const uint8_t* moved_dev, int num_geoms, float* lam_dev, int* counts_dev);
+int pt_history_probe_apply_launch(hipStream_t stream, int w, int rows, int phase, const float* lam_dev, const float* planes_dev, const uint8_t* moved_dev,
+                                  int num_geoms, const pthi::ProbeParams& P, void* current_dev);
 int pt_history_select_check(const char* who, int w, int rows, const float* feature_planes, const uint8_t* emitter_geom, int num_geoms,
                             const PtHistoryRoundOptions* opt, const int32_t* list, const int* fresh, const int* m, pthi::RoundParams* P, int* cap);
 int pt_history_merge_check(const char* who, int pixels, const float* rgb_sum, const float* extra, const int32_t* list, int m, const float* group_sum,

@@ -3,6 +3,7 @@
 // are pt_features.inc (through KernelApi), pt_denoise.hip, pt_noise.hip, pt_adaptive.hip, pt_history.hip and (a striped tile's list) pt_group_select.hip; this file holds their host side: what
 // an entry point refuses, the buffers that exist from the first use on, and the launches.
 #include <cmath>
+#include <cstring>
 
 #include "pt_adaptive.h"
 #include "pt_context.h"
@@ -628,6 +629,7 @@ static int history_reproject(PtContext* c, const char* who, const PtHistoryOptio
     return -1;
   g.hist_current = true;
   g.hist_var_current = flags;
+  g.probe_applied = false;  // a new C: the probes may be checked against it
   return 0;
 }
 int pt_ctx_history_reproject(PtContext* c, const PtHistoryOptions* opt) { return history_reproject(c, "pt_history_reproject", opt, 0u, false); }
@@ -831,6 +833,131 @@ int pt_ctx_readback_history_extra(PtContext* c, float* extra_host) {
   return copy_out(c, "pt_readback_history_extra", extra_host, 1, [&](const float** d) { return *d = g.d_hist_extra, 0; });
 }
 
+// ---- the history probes: kept samples rendered again after a move; C.w shortened where they differ ------------------------------
+static bool same_camera(const PtCamera& a, const PtCamera& b) {
+  return !std::memcmp(a.position, b.position, sizeof a.position) && !std::memcmp(a.view, b.view, sizeof a.view) && !std::memcmp(a.up, b.up, sizeof a.up) &&
+         !std::memcmp(a.right, b.right, sizeof a.right) && !std::memcmp(a.fov, b.fov, sizeof a.fov) &&
+         !std::memcmp(a.pixelLength, b.pixelLength, sizeof a.pixelLength);
+}
+static int probe_capacity(const Ctx& g) {  // the probes of phase 0: no phase has more
+  const int W = g.cam.resolution[0];
+  return pthi::probe_count(pthi::probe_grid(W, g.N / W, 0));
+}
+
+int pt_ctx_history_probe_keep(PtContext* c, int iter_first, int iter_count, int phase) {
+  const char* who = "pt_history_probe_keep";
+  if (need(c, who)) return -1;
+  Ctx& g = *c;
+  if (admit(g, who, kNotFailed)) return -1;
+  if (iter_first < 1 || iter_count < 1 || (int64_t)iter_first + iter_count - 1 > INT32_MAX)
+    return pt_fail("%s: iterations %d, +%d: the first is >= 1, the count at least one", who, iter_first, iter_count);
+  if (phase < 0 || phase > 8) return pt_fail("%s: phase %d is not in 0 .. 8", who, phase);
+  if (admit(g, who, kWholeRows) || admit(g, who, kUniform)) return -1;
+  if (g.hist_extra)
+    return pt_fail("%s: the history round left extra samples in some pixels (pt_history_round): the image is no longer a uniform sum of iterations; call "
+                   "pt_history_probe_keep before pt_history_round, or return to the uniform state with pt_clear", who);
+  if (!g.d_feat || !g.feat_fresh) return pt_fail(kNoFeatures, who);
+  if ((int64_t)iter_count != g.rendered)
+    return pt_fail("%s: %d iterations of %d pixels, but %lld iteration(s) have been rendered since the last pt_clear: the probes keep the image's own samples", who,
+                   iter_count, g.N, (long long)g.rendered);
+  HIP_OK(hipSetDevice(g.device));
+  const int W = g.cam.resolution[0], R = g.N / W;
+  const int P = pthi::probe_count(pthi::probe_grid(W, R, phase));
+  if (ensure(g, g.d_probe, (size_t)probe_capacity(g) * sizeof(pthi::V4), Zero::on_stream)) return -1;  // the first keep of the context
+  if (P > 0 && pt_history_probe_keep_launch(g.stream, W, R, phase, g.d_image, reinterpret_cast<const float*>(g.d_feat), g.d_probe)) return -1;
+  g.probe_first = iter_first, g.probe_iters = iter_count, g.probe_phase = phase;
+  g.probe_N = g.N, g.probe_begin = g.pixel_begin;
+  g.probe_cam = g.cam;
+  if (g.probe_geoms_stale) g.probe_geoms = g.camera_base.geoms, g.probe_geoms_stale = false;  // retaken only after a pt_set_geoms
+  g.probe_geoms_changed = false;
+  g.probe_kept = true;
+  g.probe_checked = false;  // L, if any, was the check of other probes
+  return 0;
+}
+
+// `moved` of pt_amd.h on the device: all zero unless pt_set_geoms has run since the keep; uploaded only when it differs from what the
+// device holds (from a member that outlives the copy).
+static int probe_moved_table(Ctx& g) {
+  const std::vector<PtGeom>& cur = g.camera_base.geoms;
+  const size_t n = cur.size();
+  std::vector<uint8_t> moved(std::max<size_t>(n, 1), 0);
+  if (g.probe_geoms_changed) {
+    if (g.probe_geoms.size() == n) pthi::probe_moved(g.probe_geoms.data(), cur.data(), (int)n, moved.data());
+    else std::fill(moved.begin(), moved.end(), (uint8_t)1);
+  }
+  const bool first = !g.d_probe_moved;
+  if (ensure(g, g.d_probe_moved, moved.size(), Zero::on_stream)) return -1;
+  if (first) g.probe_moved_dev.assign(moved.size(), 0);
+  if (moved != g.probe_moved_dev) {
+    g.probe_moved_dev = std::move(moved);
+    HIP_OK(hipMemcpyAsync(g.d_probe_moved, g.probe_moved_dev.data(), g.probe_moved_dev.size(), hipMemcpyHostToDevice, g.stream));
+  }
+  return 0;
+}
+
+int pt_ctx_history_probe_check(PtContext* c, const PtHistoryProbeOptions* opt, int* probes, int* changed, int* skipped) {
+  const char* who = "pt_history_probe_check";
+  if (need(c, who)) return -1;
+  Ctx& g = *c;
+  if (admit(g, who, kNotFailed)) return -1;
+  if (g.conv) return pt_fail("%s: the renderer was created with PtOptions.convergence = %d; the convergence metric follows whole iterations", who, g.conv);
+  if (admit(g, who, kWholeRows) || admit(g, who, kUniform)) return -1;
+  if (!g.d_probe || !g.probe_kept) return pt_fail("%s: no probes have been kept (pt_history_probe_keep)", who);
+  if (g.probe_N != g.N || g.probe_begin != g.pixel_begin)
+    return pt_fail("%s: the probes were kept for a tile of %d pixels from %d, not %d from %d", who, g.probe_N, g.probe_begin, g.N, g.pixel_begin);
+  if (!same_camera(g.cam, g.probe_cam))
+    return pt_fail("%s: the camera has moved since pt_history_probe_keep: the probes answer for a camera that stands still (keep again after the move)", who);
+  if (!g.d_hist || !g.hist_current) return pt_fail("%s: the current plane is absent: no lookup since the last pt_clear or move (pt_history_reproject)", who);
+  if (g.probe_applied) return pt_fail("%s: a check has been applied to this current plane already; the next lookup (pt_history_reproject) makes a new one", who);
+  if (!g.d_feat || !g.feat_fresh) return pt_fail(kNoFeatures, who);
+  pthi::ProbeParams pp{};
+  if (pt_history_probe_options(who, opt, &pp)) return -1;
+  const int W = g.cam.resolution[0], R = g.N / W;
+  const int P = pthi::probe_count(pthi::probe_grid(W, R, g.probe_phase));
+  if (probes) *probes = P;
+  if (changed) *changed = 0;
+  if (skipped) *skipped = 0;
+  if (P == 0) return 0;
+  HIP_OK(hipSetDevice(g.device));
+  const int cap = probe_capacity(g);
+  if (ensure(g, g.d_probe_lam, ((size_t)cap + 2) * sizeof(float), Zero::on_stream) || probe_moved_table(g)) return -1;
+  if (g.worker && g.worker->capacity >= P) set_worker_live(*g.worker, P);
+  else if (ensure_worker(g, P)) return -1;
+  const float* feat = reinterpret_cast<const float*>(g.d_feat);
+  const int num_geoms = (int)g.camera_base.geoms.size();
+  int* counts = reinterpret_cast<int*>(g.d_probe_lam + cap);
+  if (pt_history_probe_list_launch(g.stream, W, R, g.probe_phase, g.d_list)) return -1;
+  if (render_list(g, g.probe_first, g.probe_iters)) return -1;
+  g.samples += (int64_t)g.probe_iters * P;
+  if (pt_history_probe_gradient_launch(g.stream, W, R, g.probe_phase, g.d_probe, g.worker->d_image, feat, g.d_probe_moved, num_geoms, g.d_probe_lam, counts))
+    return -1;
+  if (pt_history_probe_apply_launch(g.stream, W, R, g.probe_phase, g.d_probe_lam, feat, g.d_probe_moved, num_geoms, pp, history_plane(g, pthi::kKeptPlanes)))
+    return -1;
+  g.probe_checked = g.probe_applied = true;
+  int result[2] = {0, 0};  // changed, skipped: 8 bytes and ONE synchronise
+  HIP_OK(hipMemcpyAsync(result, counts, sizeof(result), hipMemcpyDeviceToHost, g.stream));
+  HIP_OK(hipStreamSynchronize(g.stream));
+  if (changed) *changed = result[0];
+  if (skipped) *skipped = result[1];
+  return 0;
+}
+
+int pt_ctx_readback_history_probe(PtContext* c, float* kept, float* lam, int* count) {
+  const char* who = "pt_readback_history_probe";
+  if (need(c, who)) return -1;
+  Ctx& g = *c;
+  const int W = g.cam.resolution[0];
+  const int P = g.probe_kept ? pthi::probe_count(pthi::probe_grid(W, g.N / W, g.probe_phase)) : 0;
+  const bool have_lam = g.probe_checked && g.hist_current && g.d_probe_lam;
+  HIP_OK(hipSetDevice(g.device));
+  if (kept && P > 0) HIP_OK(hipMemcpyAsync(kept, g.d_probe, (size_t)P * sizeof(pthi::V4), hipMemcpyDeviceToHost, g.stream));
+  if (lam && P > 0 && have_lam) HIP_OK(hipMemcpyAsync(lam, g.d_probe_lam, (size_t)P * sizeof(float), hipMemcpyDeviceToHost, g.stream));
+  if (pt_ctx_sync(c)) return -1;
+  if (lam && !have_lam) std::fill(lam, lam + P, 0.0f);
+  if (count) *count = P;
+  return 0;
+}
+
 int pt_ctx_history_drop(PtContext* c) {
   if (need(c, "pt_history_drop")) return -1;
   Ctx& g = *c;
@@ -841,6 +968,7 @@ int pt_ctx_history_drop(PtContext* c) {
   }
   g.hist_kept = g.hist_current = false;
   g.hist_var_kept = g.hist_var_current = 0;
+  g.probe_kept = g.probe_checked = g.probe_applied = false;  // the probes are forgotten with K, their L with C
   return 0;
 }
 

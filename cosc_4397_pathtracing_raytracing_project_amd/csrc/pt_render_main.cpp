@@ -3,7 +3,7 @@
 // state.iterations iterations, write the PNG saveImage() would write.  Flags exist only because
 // the reference takes resolution, iteration count and depth from the scene file (scene.cpp:103-114).
 //
-//   pt_render SCENE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] [--orbit N [--device-tables] [--move G:DX,DY,DZ] [--reproject [--history-cap C] [--denoise-history [--history-moments]] [--history-extra G [--history-min M] [--history-extra-cap F]]]]
+//   pt_render SCENE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] [--orbit N [--device-tables] [--move G:DX,DY,DZ [--orbit-still]] [--reproject [--history-cap C] [--denoise-history [--history-moments]] [--history-extra G [--history-min M] [--history-extra-cap F]] [--history-probe [--probe-radius R] [--probe-gain X]]]]
 //                       [--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa]
 //                       [--preview N] [--convergence N | --reference FILE.pfm] [--clean-db X] [--features]
 //                       [--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]]
@@ -79,6 +79,12 @@
 // pixels whose carried weight is below --history-min M (default 4) G further iterations, --history-extra-cap F of the frame at the
 // most (default 1); resolve, filter and capture then count them per pixel.  Frame f takes spp + G iteration numbers: the uniform ones
 // f (spp + G) + 1 .., then G for the round.  Prints per frame `history: frame f: <G> extra over <m> of <fresh> fresh pixels`.
+// --orbit-still (with --orbit N --move): the N frames keep the scene's camera — no pt_scene_orbit, no pt_set_camera between frames; only
+// the object moves.  --history-probe (with --orbit N --orbit-still --move --reproject): the history probes (pt_history_probe_*).  A
+// frame's order is render, features, lookup (with PT_HISTORY_MOTION), from frame 1 on pt_history_probe_check, then
+// pt_history_probe_keep with phase f % 9 and the frame's own iteration range, the round if asked, resolve / filter, capture, move.
+// --probe-radius R (0 .. 4) and --probe-gain X: PtHistoryProbeOptions (the defaults: pt_amd.h).  Prints per frame
+// `probe: frame f: <changed> of <probes> probes changed, <skipped> skipped`.
 // Output name: PREFIX.<spp>samp.png, or with --stamp the reference's own
 // <FILE>.<UTC start time>.<spp>samp.png (main.cpp:99-102).
 #include <hip/hip_runtime.h>
@@ -100,7 +106,7 @@
 int main(int argc, char** argv) {
   if (argc < 2) {
     std::printf("Usage: %s SCENEFILE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] "
-                "[--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa] [--orbit N [--device-tables] [--reproject [--history-cap C] [--denoise-history [--history-moments]] [--history-extra G [--history-min M] [--history-extra-cap F]]]] [--preview N] "
+                "[--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa] [--orbit N [--device-tables] [--reproject [--history-cap C] [--denoise-history [--history-moments]] [--history-extra G [--history-min M] [--history-extra-cap F]] [--history-probe [--probe-radius R] [--probe-gain X]]] [--move G:DX,DY,DZ [--orbit-still]]] [--preview N] "
                 "[--convergence N | --reference FILE.pfm] [--clean-db X] [--features] "
                 "[--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]] [--denoise-guided] [--until-db X [--until-group G] [--adaptive F [--denoise-adaptive]]] "
                 "[--adaptive-threshold E [--adaptive-cap F] [--adaptive-min-pixels P] [--until-group G] [--denoise-adaptive]]\n", argv[0]);
@@ -123,6 +129,10 @@ int main(int argc, char** argv) {
   int history_extra = 0;                            // --history-extra G (0: no rounds)
   PtHistoryRoundOptions round_opt{};                // --history-min M, --history-extra-cap F (0: the defaults)
   bool history_min_given = false, history_extra_cap_given = false;
+  bool orbit_still = false;                         // --orbit-still
+  bool history_probe = false;                       // --history-probe
+  PtHistoryProbeOptions probe_opt{};                // --probe-radius R, --probe-gain X (0: the defaults)
+  bool probe_opt_given = false;
   bool until = false, until_group_given = false;
   float clean_db = 35.0f, until_db = 0.0f, adaptive = 0.0f;  // adaptive > 0: --adaptive F
   float threshold = 0.0f, threshold_cap = 0.25f;           // --adaptive-threshold E, --adaptive-cap F
@@ -188,6 +198,26 @@ int main(int argc, char** argv) {
       history_extra_cap_given = true;
       if (!(round_opt.max_fraction > 0.0f && round_opt.max_fraction <= 1.0f)) {
         std::fprintf(stderr, "--history-extra-cap wants the largest share of the frame a round may render, in (0, 1]\n");
+        return 1;
+      }
+    }
+    else if (!std::strcmp(argv[i], "--orbit-still")) orbit_still = true;
+    else if (!std::strcmp(argv[i], "--history-probe")) history_probe = true;
+    else if (!std::strcmp(argv[i], "--probe-radius") && i + 1 < argc) {
+      char* end = nullptr;
+      const long v = std::strtol(argv[++i], &end, 10);
+      probe_opt_given = true;
+      if (end == argv[i] || *end || v < 0 || v > 4) {
+        std::fprintf(stderr, "--probe-radius wants the probe cells around a pixel's own whose probes shorten its history, 0 to 4\n");
+        return 1;
+      }
+      probe_opt.radius = v == 0 ? -1 : (int32_t)v;  // (PtHistoryProbeOptions: 0 is the default, -1 radius 0)
+    }
+    else if (!std::strcmp(argv[i], "--probe-gain") && i + 1 < argc) {
+      probe_opt.gain = (float)std::atof(argv[++i]);
+      probe_opt_given = true;
+      if (!std::isfinite(probe_opt.gain) || !(probe_opt.gain > 0.0f)) {
+        std::fprintf(stderr, "--probe-gain wants the factor between a probe's relative difference and the share of history dropped, a positive number\n");
         return 1;
       }
     }
@@ -393,6 +423,19 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--history-extra excludes --denoise-history without --history-moments: the folds' variance knows nothing of the extra samples\n");
     return 1;
   }
+  if (orbit_still && !move) {
+    std::fprintf(stderr, "--orbit-still wants --orbit N --move G:DX,DY,DZ (with the camera standing still and nothing moving every frame would be the same)\n");
+    return 1;
+  }
+  if (probe_opt_given && !history_probe) {
+    std::fprintf(stderr, "--probe-radius and --probe-gain go with --history-probe\n");
+    return 1;
+  }
+  if (history_probe && (!reproject || !move || !orbit_still)) {
+    std::fprintf(stderr, "--history-probe wants %s (it renders kept samples again after an object moved; the probes answer for a camera that stands still)\n",
+                 !reproject ? "--reproject" : !move ? "--move G:DX,DY,DZ" : "--orbit-still");
+    return 1;
+  }
   if (reproject && (gpus >= 0 || !device_list.empty())) {
     std::fprintf(stderr, "--reproject excludes --gpus / --devices: a context's interleaved rows cannot look up their neighbours in the previous view\n");
     return 1;
@@ -576,7 +619,7 @@ int main(int argc, char** argv) {
         const double geoms_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - g0).count();
         std::printf("move: frame %d: geom %d at %.9g %.9g %.9g, set_geoms %.3f ms\n", f, move_geom, (double)trs[0], (double)trs[1], (double)trs[2], geoms_ms);
       }
-      if (f > 0) {
+      if (f > 0 && !orbit_still) {
         scene->orbit(step, 0.0f, 0.0f);
         const uint32_t flags = device_tables ? PT_SET_CAMERA_DEVICE_TABLES : 0u;
         const auto m0 = std::chrono::high_resolution_clock::now();
@@ -620,7 +663,9 @@ int main(int argc, char** argv) {
       if (reproject) {  // the view's first hits, the history looked up from them, the blend written, the blend kept for the next view
         const uint32_t hflags = !dn_history ? 0u : hist_moments ? PT_HISTORY_MOMENTS : PT_HISTORY_VARIANCE;  // 0: the plain calls
         int fresh = 0, selected = 0;  // --history-extra: the round, between the lookup and the resolve
+        int probes = 0, changed = 0, skipped = 0;  // --history-probe: the check after the lookup, the keep before the round
         if (pt_render_features(1, 1) || (f > 0 && pt_history_reproject_ex(&hopt, hflags | (move ? PT_HISTORY_MOTION : 0u))) ||
+            (history_probe && ((f > 0 && pt_history_probe_check(&probe_opt, &probes, &changed, &skipped)) || pt_history_probe_keep(iter_first, iters, f % 9))) ||
             (history_extra && pt_history_round(iter_first + iters, history_extra, &round_opt, &fresh, &selected)) || pt_history_resolve((float)iters, carried.data()) ||
             (dn_history && (hist_moments ? pt_history_denoise_ex((float)iters, &dn_opt, PT_HISTORY_MOMENTS, filtered.data())
                                          : pt_history_denoise((float)iters, &dn_opt, filtered.data()))) || pt_history_capture_ex((float)iters, hflags) ||
@@ -633,6 +678,7 @@ int main(int argc, char** argv) {
         for (size_t p = 0; p < (size_t)W * H; ++p)
           if (current[4 * p + 3] > 0.0f) valid += 1, weight += (double)current[4 * p + 3];
         std::printf("history: frame %d: %zu of %zu pixels carried, mean weight %.3f\n", f, valid, (size_t)W * H, valid ? weight / (double)valid : 0.0);
+        if (history_probe) std::printf("probe: frame %d: %d of %d probes changed, %d skipped\n", f, changed, probes, skipped);
         if (history_extra) std::printf("history: frame %d: %d extra over %d of %d fresh pixels\n", f, history_extra, selected, fresh);
         if (pt_save_png((frame + ".reprojected.png").c_str(), carried.data(), W, H, 1.0f) == 0) std::printf("Saved %s.reprojected.png.\n", frame.c_str());
         if (pfm && pt_save_pfm((frame + ".reprojected.pfm").c_str(), carried.data(), W, H, 1.0f) == 0) std::printf("Saved %s.reprojected.pfm.\n", frame.c_str());

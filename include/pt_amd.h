@@ -1073,8 +1073,8 @@ int pt_history_denoise_moments_counted_host(int w, int rows, const float* rgb_su
  * table is built and uploaded by the first lookup after a capture or a pt_set_geoms changed its inputs, which synchronises) and
  * k_history_reproject_motion runs.  pt_history_capture_ex does not define the bit.  Without the flag the lookup is what it was and
  * treats the world as static even after pt_set_geoms.
- * Caveat: a moved object changes shadows and indirect light on surfaces that stand still.  Nothing detects that: their history goes
- * stale until `cap` washes it out.
+ * Caveat: a moved object changes shadows and indirect light on surfaces that stand still.  The lookup does not detect that: their
+ * history goes stale until `cap` washes it out, unless the history probes below shorten it (a camera that stands still only).
  * Out of scope: adding or removing objects; material changes; deformation; a device-side tree build; history in groups. */
 #define PT_HISTORY_MOTION 4u
 int pt_history_motion_host(const PtGeom* kept, const PtGeom* cur, int n, float* table /* n * 24 */, uint8_t* kind /* n */);
@@ -1083,6 +1083,82 @@ int pt_history_motion_host(const PtGeom* kept, const PtGeom* cur, int n, float* 
 int pt_history_reproject_motion_host(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
                                      const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, const float* kept_var, const float* table,
                                      const uint8_t* kind, uint32_t flags, float* current_plane, float* current_var);
+
+/* ---- the history probes: replay kept samples after a move, shorten the history where light changed.  A sample is a pure function
+ * of (iteration, pixel, world), and the adaptive rounds' worker renders a chosen list of pixels at chosen iterations bit for bit as a
+ * whole-frame render does.  So: keep a sparse set of last view's samples (pt_history_probe_keep), render the same (iteration, pixel)
+ * pairs again in the world as it is now (pt_history_probe_check) and compare.  The difference is exactly zero wherever the path met
+ * nothing that changed — no noise threshold — and non-zero elsewhere (the temporal gradient of Schied et al. 2018).  What the check
+ * finds is written into one word, C.w = Th, the carried weight, which the blend, both captures, the moments filter and the history
+ * round's key read already: stale pixels lose their history, are marked fresh, and are resampled.  No downstream step changes.
+ * Opt-in: a renderer that never calls these functions allocates and launches nothing for them; every other call keeps its kernels,
+ * memory, launches, results and refusals.  Specified like the rest of the history: float32, separate IEEE operations in the order
+ * written, one implementation for kernels and host loops, the same bits in all three PT_ARITH_* builds, host and device.
+ * The check compares pixel p then with pixel p now: it answers for a camera that stands still, and refuses a moved one by name.
+ * Probes: the tile is W x R whole rows; phase in 0 .. 8 gives ox = phase % 3, oy = phase / 3.  Probe (i, j) sits at tile pixel
+ *   (3 i + ox, 3 j + oy), i < PW = ceil((W - ox) / 3), j < PR = ceil((R - oy) / 3), each 0 when negative; P = PW * PR; probe index
+ *   s = j * PW + i, so the pixel list ascends with s (pt_history_probe_list_host).
+ * pt_history_probe_keep (asynchronous; k_history_probe_keep, one thread per probe): PK[s] = {S_p.xyz, bits(id_p)}, id_p read from the
+ *   feature sums as pt_history_capture reads it (s1.w > 0 ? bits(s2.w) : 0).  The host remembers iter_first, iter_count, phase, the
+ *   renderer's camera and its geoms (a host copy, retaken only when pt_set_geoms has run since the last copy).  State: 16 B per
+ *   probe, allocated by the first keep for the probes of phase 0 (the most of any phase) and counted in PtStats.device_bytes.  PK
+ *   survives pt_clear, pt_set_camera[_ex] and pt_set_geoms; pt_history_drop forgets it.  P == 0 is kept as "no probes".
+ *   Refuses, in this order, nothing changed, allocated or launched: no renderer or a failed context; iter_first < 1, iter_count < 1
+ *   or iterations past 2^31 - 1; phase outside 0 .. 8; a striped or ragged tile; the adaptive state; E present (S is no longer a
+ *   uniform sum: keep before pt_history_round; pt_clear is the way out); no feature pass since the last clear or move;
+ *   iter_count * pixel_count is not the samples rendered since the last clear.  iter_first is the caller's statement, as `samples`
+ *   is elsewhere.
+ * pt_history_probe_check (ONE synchronise, for the two counts):
+ *   1. the probes' pixels are written into the rounds' list;
+ *   2. the worker: the existing one as it is when its capacity is >= P, made live for P; else one built for P.  (The history round
+ *      with its default fraction asks for capacity N, so a frame that runs check then round rebuilds nothing.)
+ *   3. the worker renders the kept iterations of the listed pixels into its cleared sum Sw[P][3]; PtStats.samples grows by iter_count * P;
+ *   4. gradient (k_history_probe_gradient, one thread per probe), g = id - 1: the probe is skipped, L[s] = -1.0f, when the id now
+ *      at the pixel differs from the kept id, is 0 or outside 1 .. num_geoms, or moved[g] != 0 (moved[g] = 1 when the geom's 48 matrix
+ *      words differ bytewise from the kept geoms'; built on the host and uploaded, one byte per geom, only when pt_set_geoms has run
+ *      since the keep, otherwise all zero).  Otherwise, o = PK[s].xyz, w = Sw[s]:
+ *        d = (|w.x - o.x| + |w.y - o.y|) + |w.z - o.z|;  mo = (o.x + o.y) + o.z, mw likewise;  m = mo > mw ? mo : mw;
+ *        lam = m > 0 ? d / m : +0;  L[s] = lam < 1 ? lam : 1.0f (a NaN reads as 1).
+ *      changed = #{L[s] > 0}, skipped = #{L[s] < 0}: integer atomics, read back as 8 bytes;
+ *   5. apply (k_history_probe_apply, one thread per tile pixel (x, r)): every word is kept for a miss, an id outside 1 .. num_geoms
+ *      and a moved geom (left to PT_HISTORY_MOTION).  Otherwise i0 = x / 3, j0 = r / 3, lam_p = the maximum of L over the probes
+ *      (i, j) of the grid with |i - i0| <= radius, |j - j0| <= radius, starting at +0 (skipped probes add nothing).  lam_p == 0:
+ *      every word is kept.  Else g = lam_p * gain;  g = g < 1 ? g : 1.0f;  C.w = C.w * (1.0f - g).  Only C.w is written; VC is
+ *      untouched; the cap was applied by the lookup.
+ *   L: 4 B per probe (and the two counts), allocated by the first check; moved: one byte per geom.
+ *   Refuses, in this order: no renderer or a failed context; PtOptions.convergence != 0; a striped or ragged tile; the adaptive
+ *   state; nothing kept; a tile other than the one the probes were kept for; a camera that is not bytewise the kept one (position,
+ *   view, up, right, fov, pixelLength); C absent (no lookup since the last clear or move); a check already applied to this C (the
+ *   next lookup clears that); no feature pass since the last clear or move; an option out of range.  P == 0 succeeds with all counts
+ *   0 and launches nothing.  probes / changed / skipped may be NULL.
+ * Defaults: radius 0 (the probe of the pixel's own 3 x 3 cell) and gain 0.25, from tests/test_history_probe_sim.py (README "History
+ * probes"): at 4 spp per view one changed path of four already gives lam of a quarter and more, and in that simulation every larger
+ * radius or gain raised the frame's MSE — shortening history there trades little bias for much noise.  Radius 1 and gain 1 are what
+ * makes the history round resample the pixels a move touched; they cost 3.2 x the frame's MSE there.
+ * Not built: a camera that moves between keep and check (forward-projecting the probes needs camera rays off the pixel centres);
+ * pt_group_*; the shading of the moved object itself (PT_HISTORY_MOTION carries it, skipped here); material changes; feeding L into
+ * the filter's variance. */
+#define PT_HISTORY_PROBE_RADIUS 0    /* the default of PtHistoryProbeOptions.radius, in probe cells: the pixel's own cell */
+#define PT_HISTORY_PROBE_GAIN 0.25f /* the default of PtHistoryProbeOptions.gain */
+typedef struct PtHistoryProbeOptions { /* every field: 0 = the default */
+  int32_t radius; /* in probe cells: 1 .. 4, or -1 for radius 0; default (0): PT_HISTORY_PROBE_RADIUS, the pixel's own cell */
+  float gain;     /* finite and > 0; default (0): PT_HISTORY_PROBE_GAIN */
+} PtHistoryProbeOptions;
+int pt_history_probe_keep(int iter_first, int iter_count, int phase);
+int pt_history_probe_check(const PtHistoryProbeOptions* opt, int* probes, int* changed, int* skipped);
+/* kept: P * 4 floats (PK), lam: P floats — the last check's L when it was made of these probes, zeros otherwise (before a check, after
+ * a later keep, once C is absent); either may be NULL, *count = P (0: nothing kept).  Synchronises. */
+int pt_readback_history_probe(float* kept, float* lam, int* count);
+/* The same arithmetic on the host (no GPU); the device results equal these bit for bit.  w x rows the tile; feature_planes its feature
+ * SUM planes; moved_geom one byte per geom (may be NULL when num_geoms == 0). */
+int pt_history_probe_list_host(int w, int rows, int phase, int32_t* list /* P entries, or NULL */, int* count);
+int pt_history_probe_keep_host(int w, int rows, int phase, const float* rgb_sum, const float* feature_planes, float* kept /* P * 4 */);
+/* group_sum: the replay Sw, P * 3 floats in probe order; lam: P floats out; changed / skipped may be NULL */
+int pt_history_probe_gradient_host(int w, int rows, int phase, const float* kept, const float* group_sum, const float* feature_planes,
+                                   const uint8_t* moved_geom, int num_geoms, float* lam, int* changed, int* skipped);
+/* current_plane: w * rows * 4 floats, updated in place (its w words only) */
+int pt_history_probe_apply_host(int w, int rows, int phase, const float* lam, const float* feature_planes, const uint8_t* moved_geom, int num_geoms,
+                                const PtHistoryProbeOptions* opt, float* current_plane);
 
 /* saveImage()'s per-pixel conversion (main.cpp:91-97 x mirror, image.cpp:26-30 clamp * 255 truncated) on the
  * device: pixel_count*3 bytes, row-major, x mirrored inside each row; the tile must consist of whole rows.
@@ -1157,6 +1233,9 @@ int pt_ctx_history_denoise_ex(PtContext* c, float samples, const PtDenoiseOption
 int pt_ctx_history_denoise_ex_device(PtContext* c, float samples, const PtDenoiseOptions* opt, uint32_t flags, const float** rgb_dev); /* as pt_ctx_denoise_device */
 int pt_ctx_history_round(PtContext* c, int iter_first, int group_iters, const PtHistoryRoundOptions* opt, int* fresh, int* selected);
 int pt_ctx_readback_history_extra(PtContext* c, float* extra_host);
+int pt_ctx_history_probe_keep(PtContext* c, int iter_first, int iter_count, int phase);
+int pt_ctx_history_probe_check(PtContext* c, const PtHistoryProbeOptions* opt, int* probes, int* changed, int* skipped);
+int pt_ctx_readback_history_probe(PtContext* c, float* kept, float* lam, int* count);
 const float* pt_ctx_device_noise(PtContext* c); /* device pointer of plane 0; the planes are contiguous; NULL before the first fold */
 const float* pt_ctx_device_features(PtContext* c); /* device pointer of plane 0; the planes are contiguous; NULL before the first pt_ctx_render_features */
 const float* pt_ctx_device_image(PtContext* c); /* device pointer of the tile SUM image */
