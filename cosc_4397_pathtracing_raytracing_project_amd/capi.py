@@ -106,6 +106,12 @@ class PtHistoryProbeOptions(C.Structure):
     _fields_ = [("radius", C.c_int32), ("gain", C.c_float)]
 
 
+class PtHistoryFeedbackOptions(C.Structure):
+    """Options of the feedback (include/pt_amd.h: pt_history_denoise_feedback); 0 in a field = its default (level 1, rule 1); variance
+    -1 = rule 0."""
+    _fields_ = [("level", C.c_int32), ("variance", C.c_int32)]
+
+
 class PtSetupTimes(C.Structure):
     """Host wall-clock times of a renderer's setup and of its last camera move, ms (include/pt_amd.h: pt_get_setup_times)."""
     _fields_ = [("tables_ms", C.c_double), ("upload_ms", C.c_double), ("buffers_ms", C.c_double), ("probe_ms", C.c_double),
@@ -427,6 +433,19 @@ def lib() -> C.CDLL:
         L.pt_history_probe_keep_host.argtypes = [C.c_int, C.c_int, C.c_int, _fp, _fp, _fp]
         L.pt_history_probe_gradient_host.argtypes = [C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _u8p, C.c_int, _fp, _ip, _ip]
         L.pt_history_probe_apply_host.argtypes = [C.c_int, C.c_int, C.c_int, _fp, _fp, _u8p, C.c_int, _hpo, _fp]
+    if hasattr(L, "pt_history_denoise_feedback"):  # absent from older A/B builds of the library (tools/build_rev.sh)
+        _hio, _dno, _hfo, _cam = C.POINTER(PtHistoryOptions), C.POINTER(PtDenoiseOptions), C.POINTER(PtHistoryFeedbackOptions), C.POINTER(PtCamera)
+        _reproject_fb = [C.c_int, C.c_int, C.c_int, _cam, _fp, _fp, _u8p, C.c_int, _hio, _fp, _fp, _fp, _u8p, _fp, _fp, _fp]
+        _fdn = [C.c_int, C.c_int, _fp, _fp, C.c_float, _fp, _fp, _fp, _fp, _dno, _hfo, _fp, _fp]
+        L.pt_history_denoise_feedback.argtypes = [C.c_float, _dno, _hfo, _fp]
+        L.pt_readback_history_feedback.argtypes = [_fp, _fp, _fp]
+        L.pt_ctx_history_denoise_feedback.argtypes = [C.c_void_p, C.c_float, _dno, _hfo, _fp]
+        L.pt_ctx_history_denoise_feedback_device.argtypes = [C.c_void_p, C.c_float, _dno, _hfo, C.POINTER(C.c_void_p)]
+        L.pt_ctx_readback_history_feedback.argtypes = [C.c_void_p, _fp, _fp, _fp]
+        L.pt_history_reproject_feedback_host.argtypes = _reproject_fb
+        L.pt_stage_history_reproject_feedback.argtypes = _reproject_fb
+        L.pt_history_denoise_feedback_host.argtypes = _fdn + [_fp, _u8p]
+        L.pt_stage_history_denoise_feedback.argtypes = _fdn
     _lib = L
     return L
 
@@ -929,6 +948,88 @@ def stage_history_denoise_moments(rgb_sum, planes, w: int, rows: int, samples: f
     c, v = _history_planes(current, current_var, w, rows)
     return _filter(lib().pt_stage_history_denoise_moments, out, int(w), int(rows), _f(s), _f(p), C.c_float(samples), None if c is None else _f(c),
                    None if v is None else _f(v), **opts)
+
+
+# ---- the feedback: the filtered image fed back into the history (include/pt_amd.h: pt_history_denoise_feedback) ----
+HISTORY_FEEDBACK = 16  # PT_HISTORY_FEEDBACK
+
+
+def history_feedback_options(level: int = 0, variance: Optional[int] = None) -> PtHistoryFeedbackOptions:
+    """PtHistoryFeedbackOptions from a level (0 = the default) and a variance RULE: 0 or 1, None = the default; the field's own
+    encoding (0 = the default, -1 = rule 0) stays in here.  Any other number is passed on as it is, for the library to refuse."""
+    return PtHistoryFeedbackOptions(int(level), 0 if variance is None else -1 if variance == 0 else int(variance))
+
+
+def _history_reproject_feedback(call, kept_cam: PtCamera, kept, planes, reject, kept_var, kept_fb, w: int, rows: int, row0: int, table, kind, **opts):
+    n = w * rows
+    k = np.ascontiguousarray(kept, np.float32).reshape(-1)
+    p = np.ascontiguousarray(planes, np.float32).reshape(-1)
+    r = np.ascontiguousarray(reject, np.uint8).reshape(-1)
+    vk = np.ascontiguousarray(kept_var, np.float32).reshape(-1)
+    fk = np.ascontiguousarray(kept_fb, np.float32).reshape(-1)
+    t = None if table is None else np.ascontiguousarray(table, np.float32).reshape(-1)
+    kd = None if kind is None else np.ascontiguousarray(kind, np.uint8).reshape(-1)
+    if k.size != 4 * HISTORY_KEPT_PLANES * n or p.size != 4 * FEATURE_PLANES * n or vk.size != 4 * n or fk.size != 4 * n:
+        raise PtError(f"history_reproject_feedback: {k.size} kept, {p.size} plane, {vk.size} moment and {fk.size} feedback floats for a tile of {w}x{rows}")
+    if t is not None and (kd is None or t.size != HISTORY_MOTION_ROW * kd.size or kd.size != r.size):
+        raise PtError(f"history_reproject_feedback: {t.size} table floats for {r.size} geoms")
+    out, vout, fout = (np.empty((n, 4), np.float32) for _ in range(3))
+    opt = history_options(**opts)
+    u8 = C.POINTER(C.c_uint8)
+    _check(call(int(w), int(rows), int(row0), C.byref(kept_cam), _f(k), _f(p), r.ctypes.data_as(u8), int(r.size), C.byref(opt), _f(vk), _f(fk),
+                None if t is None else _f(t), None if kd is None else kd.ctypes.data_as(u8), _f(out), _f(vout), _f(fout)))
+    return out, vout, fout
+
+
+def history_reproject_feedback_host(kept_cam: PtCamera, kept, planes, reject, kept_var, kept_fb, w: int, rows: int, row0: int = 0, table=None, kind=None,
+                                    **opts):
+    """pt_history_reproject_ex with PT_HISTORY_MOMENTS | PT_HISTORY_FEEDBACK on the host (no GPU): history_reproject_moments_host's
+    arrays and FK [w*rows, 4] in, (C, VC, FC) out; table and kind (history_motion_host): the lookup with PT_HISTORY_MOTION as well."""
+    return _history_reproject_feedback(lib().pt_history_reproject_feedback_host, kept_cam, kept, planes, reject, kept_var, kept_fb, w, rows, row0, table, kind,
+                                       **opts)
+
+
+def stage_history_reproject_feedback(kept_cam: PtCamera, kept, planes, reject, kept_var, kept_fb, w: int, rows: int, row0: int = 0, table=None, kind=None,
+                                     **opts):
+    """history_reproject_feedback_host's arrays through the production kernel (pt_stage_history_reproject_feedback; a renderer must be live)."""
+    return _history_reproject_feedback(lib().pt_stage_history_reproject_feedback, kept_cam, kept, planes, reject, kept_var, kept_fb, w, rows, row0, table,
+                                       kind, **opts)
+
+
+def _history_denoise_feedback(call, host: bool, rgb_sum, planes, w: int, rows: int, samples: float, extra, current, current_var, current_fb, level: int,
+                              variance: Optional[int], stats, **opts):
+    s, p, out = _denoise_arrays(rgb_sum, planes, w, rows)
+    c, v = _history_planes(current, current_var, w, rows)
+    f, _ = _history_planes(current_fb, None, w, rows)
+    e = None if extra is None else _extra(extra, w * rows)
+    tap = np.empty((w * rows, 4), np.float32)
+    opt, fb = denoise_options(**opts), history_feedback_options(level, variance)
+    args = [int(w), int(rows), _f(s), _f(p), C.c_float(samples), None if e is None else _f(e), None if c is None else _f(c), None if v is None else _f(v),
+            None if f is None else _f(f), C.byref(opt), C.byref(fb), _f(out), _f(tap)]
+    if host:
+        var_raw = np.empty(w * rows, np.float32) if stats is not None else None
+        mark = np.empty(w * rows, np.uint8) if stats is not None else None
+        args += [None if var_raw is None else _f(var_raw), None if mark is None else mark.ctypes.data_as(C.POINTER(C.c_uint8))]
+    _check(call(*args))
+    if host and stats is not None:
+        stats.update(var_raw=var_raw, mark=mark.astype(bool))
+    return out, tap
+
+
+def history_denoise_feedback_host(rgb_sum, planes, w: int, rows: int, samples: float, extra=None, current=None, current_var=None, current_fb=None,
+                                  level: int = 0, variance: Optional[int] = None, stats: Optional[dict] = None, **opts):
+    """pt_history_denoise_feedback on the host (no GPU): history_denoise_moments_host's arrays, the extra plane E [w*rows] (None:
+    absent) and FC [w*rows, 4] beside C and VC (None: absent) in; (the filtered image [w*rows, 3], the tap plane P [w*rows, 4]) out.
+    stats (a dict) receives var_raw (after the spatial step) and mark (bool)."""
+    return _history_denoise_feedback(lib().pt_history_denoise_feedback_host, True, rgb_sum, planes, w, rows, samples, extra, current, current_var, current_fb,
+                                     level, variance, stats, **opts)
+
+
+def stage_history_denoise_feedback(rgb_sum, planes, w: int, rows: int, samples: float, extra=None, current=None, current_var=None, current_fb=None,
+                                   level: int = 0, variance: Optional[int] = None, **opts):
+    """history_denoise_feedback_host's arguments through the filter's kernels (pt_stage_history_denoise_feedback; a renderer must be live)."""
+    return _history_denoise_feedback(lib().pt_stage_history_denoise_feedback, False, rgb_sum, planes, w, rows, samples, extra, current, current_var,
+                                     current_fb, level, variance, None, **opts)
 
 
 # ---- the history probes: kept samples rendered again after a move (include/pt_amd.h: pt_history_probe_keep) ----
@@ -1467,6 +1568,20 @@ class Renderer:
         out = np.empty((self.n, 3), np.float32)
         _check(lib().pt_history_denoise_ex(C.c_float(samples), C.byref(opt), int(flags), _f(out)))
         return out
+
+    def history_denoise_feedback(self, samples: float, level: int = 0, variance: Optional[int] = None, **opts) -> np.ndarray:
+        """The blend of the new samples with the FILTERED history, filtered like history_denoise_ex's (pt_history_denoise_feedback);
+        the output of filter level `level` becomes the pending plane that history_capture_ex with HISTORY_FEEDBACK promotes."""
+        opt, fb = denoise_options(**opts), history_feedback_options(level, variance)
+        out = np.empty((self.n, 3), np.float32)
+        _check(lib().pt_history_denoise_feedback(C.c_float(samples), C.byref(opt), C.byref(fb), _f(out)))
+        return out
+
+    def readback_history_feedback(self):
+        """(FK, FC, P), float32 [n, 4] each; zeros while absent."""
+        fk, fc, pend = (np.empty((self.n, 4), np.float32) for _ in range(3))
+        _check(lib().pt_readback_history_feedback(_f(fk), _f(fc), _f(pend)))
+        return fk, fc, pend
 
     def history_round(self, iter_first: int, group_iters: int, min_history: float = 0, max_fraction: float = 0):
         """A group of further iterations for the pixels whose carried history weighs less than min_history samples, the shortest

@@ -848,6 +848,7 @@ int pt_ctx_render(PtContext* c, int iter_first, int iter_count) {
   HIP_OK(hipEventRecord(ev.b, g.stream));
   g.pending_render.push_back(ev);
   g.rendered += iter_count;
+  g.fb_pending = false;  // the feedback's pending plane was the filter of another image
   return 0;
 }
 
@@ -987,6 +988,7 @@ int pt_ctx_clear(PtContext* c) {
   c->adaptive_last = 0;
   c->hist_current = c->feat_fresh = false;
   c->hist_var_current = 0;  // the history's current planes are absent; its kept planes stay (pt_history.h)
+  c->fb_current = c->fb_pending = false;  // ... and so are the feedback's FC and P; FK stays
   if (c->d_hist_extra) HIP_OK(hipMemsetAsync(c->d_hist_extra, 0, (size_t)c->N * sizeof(float), c->stream));  // the extras belong to the image
   c->hist_extra = false;
   c->probe_checked = c->probe_applied = false;  // the probes' L belongs to C; PK stays
@@ -1462,6 +1464,10 @@ int pt_history_denoise(float samples, const PtDenoiseOptions* opt, float* rgb_av
 int pt_history_denoise_ex(float samples, const PtDenoiseOptions* opt, uint32_t flags, float* rgb_avg_host) {
   return pt_ctx_history_denoise_ex(g_default, samples, opt, flags, rgb_avg_host);
 }
+int pt_history_denoise_feedback(float samples, const PtDenoiseOptions* opt, const PtHistoryFeedbackOptions* fb, float* rgb_avg_host) {
+  return pt_ctx_history_denoise_feedback(g_default, samples, opt, fb, rgb_avg_host);
+}
+int pt_readback_history_feedback(float* kept, float* current, float* pending) { return pt_ctx_readback_history_feedback(g_default, kept, current, pending); }
 int pt_readback_history_variance(float* kept_var, float* current_var) { return pt_ctx_readback_history_variance(g_default, kept_var, current_var); }
 int pt_history_round(int iter_first, int group_iters, const PtHistoryRoundOptions* opt, int* fresh, int* selected) {
   return pt_ctx_history_round(g_default, iter_first, group_iters, opt, fresh, selected);

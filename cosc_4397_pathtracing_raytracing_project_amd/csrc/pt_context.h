@@ -169,6 +169,14 @@ struct PtContext : PtShared {
   void* d_hist_var = nullptr;      // pt_history_variance_bytes(N): VK, then VC; absent until the first capture with PT_HISTORY_VARIANCE or _MOMENTS
   uint32_t hist_var_kept = 0;      // the flag of the capture VK belongs to K0 by: the variance of K0 or its moments (0: a plain capture, K "kept without")
   uint32_t hist_var_current = 0;   // the flag of the lookup VC belongs to C by; 0 (absent) whenever C is
+  // The feedback (PT_HISTORY_FEEDBACK): absent until the first call that carries the flag.  Three planes whose roles rotate: a capture
+  // with the flag promotes the pending plane to FK by swapping two of these indices, it moves no bytes.
+  void* d_hist_fb = nullptr;       // pt_history_feedback_bytes(N): three planes of N float4
+  int fb_plane_kept = 0, fb_plane_current = 1, fb_plane_pending = 2;  // which plane holds FK, FC and P
+  bool fb_kept = false;            // FK belongs to K (a capture without the flag leaves K "kept without feedback")
+  bool fb_current = false;         // FC belongs to C; absent whenever C is
+  bool fb_pending = false;         // P holds the tap of pt_history_denoise_feedback for the image as it stands
+  int fb_keep_albedo = 0;          // the keep_albedo the last tap was made with: the unit of P.w, and of FK.w / FC.w after it
   // The objects' motion (PT_HISTORY_MOTION): the geoms K is aligned to beside hist_cam, and the motion table of the last lookup that
   // found a geom moved (absent until then): pthi::kMotionRow floats per geom, then one kind byte per geom
   std::vector<PtGeom> hist_geoms;

@@ -11,7 +11,11 @@
 // the variance; prefilter, levels and finish are the guided form's.  The moments form (pt_history_denoise_ex with PT_HISTORY_MOMENTS;
 // tests/history_moments_ref.py) is the history form without a fold: its prepare takes the blend's variance from the moments the history
 // carries (the differences between views), and marks the pixels whose history is too short; var_spatial_pixel — a step of its own
-// between prepare and the prefilter — gives those the variance of their 7 x 7 neighbourhood instead.
+// between prepare and the prefilter — gives those the variance of their 7 x 7 neighbourhood instead.  The feedback form
+// (pt_history_denoise_feedback; tests/history_feedback_ref.py) is the moments form over another colour: its prepare filters the blend of
+// the new samples with the FILTERED history FC (pt_history.h), the variance still comes from the raw chain (or, by option, from the
+// variance FC carries), and tap_pixel — a step of its own after level L - 1 — leaves {c_L remodulated, var_L}, the plane the next capture
+// promotes to FK.  Everything between is the moments form's.
 // Every float operation is a separate IEEE operation in the order pt_amd.h states (`#pragma clang fp contract(off)` in every body, correctly
 // rounded division, denormals kept), so the result does not depend on the arithmetic mode of the build or on the side it runs on.
 // Plain C++ apart from PT_HD: the system compiler accepts it (a host sanitizer run needs nothing else).
@@ -84,7 +88,8 @@ PT_HD float color_factor(const Params& P, int l) {
 // history's current plane C and its variance VC (both nullptr: absent).
 // Moments: what the blend reads only — samples, C and VC = {m2h.xyz, rh} (both nullptr: absent); no fold, no noise planes.
 // E (the moments form; nullptr: absent): the extra plane of the history round — the pixel's samples are samples + E_p (pthi::Counted).
-enum class Form { Plain, Guided, Adaptive, History, Moments };
+// Feedback: the moments form's and FC = {f.xyz, vf} beside C (nullptr: absent), and the variance rule (PtHistoryFeedbackOptions.variance).
+enum class Form { Plain, Guided, Adaptive, History, Moments, Feedback };
 struct Divisors {
   float Tf, Df;
   const ptad::Cnt* cnt;
@@ -92,6 +97,8 @@ struct Divisors {
   float samples;
   const V4 *C, *VC;
   const float* E;
+  const V4* FC;
+  int fb_variance;
 };
 // A prepare's D has a member E: Divisors (the host loop, and a launch's checks) and the counted kernel's arguments; the kernels that
 // existed before the history round take structs without one and are compiled as they were.
@@ -130,6 +137,13 @@ PT_HD float moments_variance(float m2b, float cb, float f, float albedo, int kee
   const float v = (d > 0.0f ? d : 0.0f) * f;
   return !keep_albedo && albedo > 0.0f ? v / (albedo * albedo) : v;
 }
+// feedback, variance rule 1: the per-view variance of one component from the raw chain, s = d / (1 - rb) (g = 1 - rb), demodulated likewise
+PT_HD float feedback_view_variance(float m2b, float cb, float g, float albedo, int keep_albedo) {
+#pragma clang fp contract(off)
+  const float d = m2b - cb * cb;
+  const float s = (d > 0.0f ? d : 0.0f) / g;
+  return !keep_albedo && albedo > 0.0f ? s / (albedo * albedo) : s;
+}
 // ... and what its prepare leaves in var_raw's place for a pixel whose history is too short to have one (every other var_raw is
 // >= 0 or NaN: sums of clamped terms times f >= 0)
 constexpr float kSpatialMark = -1.0f;
@@ -146,7 +160,7 @@ PT_HD void prepare_pixel_of(size_t i, size_t npix, const float* S, const V4* pla
     const int32_t Tp = d.cnt ? d.cnt[i].T : d.T, Mp = d.cnt ? d.cnt[i].M : d.M;
     Tf = (float)Tp;
     Df = (float)(Mp - 1) * Tf;
-  } else if constexpr (kForm != Form::Moments) {
+  } else if constexpr (kForm != Form::Moments && kForm != Form::Feedback) {
     Tf = d.Tf;
     if constexpr (kForm == Form::Guided || kForm == Form::History) Df = d.Df;
   }
@@ -161,7 +175,7 @@ PT_HD void prepare_pixel_of(size_t i, size_t npix, const float* S, const V4* pla
   V4 vc{0.0f, 0.0f, 0.0f, 0.0f};
   [[maybe_unused]] V4 hc{0.0f, 0.0f, 0.0f, 0.0f}, hv{0.0f, 0.0f, 0.0f, 0.0f};  // history: C and VC of the pixel (absent: +0)
   [[maybe_unused]] float ns = 0.0f;  // history: the pixel's samples (with its extras, where the history round left some)
-  if constexpr (kForm == Form::History || kForm == Form::Moments) {
+  if constexpr (kForm == Form::History || kForm == Form::Moments || kForm == Form::Feedback) {
     ns = history_samples(d, i);
     if (d.C) hc = d.C[i];
     if (d.VC) hv = d.VC[i];
@@ -172,6 +186,12 @@ PT_HD void prepare_pixel_of(size_t i, size_t npix, const float* S, const V4* pla
     vc.x = S[3 * i] / Tf, vc.y = S[3 * i + 1] / Tf, vc.z = S[3 * i + 2] / Tf;
   }
   [[maybe_unused]] const V4 cb = vc;  // (moments: the blend before demodulation)
+  if constexpr (kForm == Form::Feedback) {  // the colour that is filtered: the new samples with the FILTERED history, weighted as the raw blend
+    const V4 hf = d.FC ? d.FC[i] : V4{0.0f, 0.0f, 0.0f, 0.0f};
+    vc.x = pthi::blend_component(S[3 * i], ns, hf.x, hc.w);
+    vc.y = pthi::blend_component(S[3 * i + 1], ns, hf.y, hc.w);
+    vc.z = pthi::blend_component(S[3 * i + 2], ns, hf.z, hc.w);
+  }
   if (!keep_albedo) {
     vc.x = va.x > 0.0f ? vc.x / va.x : vc.x;
     vc.y = va.y > 0.0f ? vc.y / va.y : vc.y;
@@ -183,7 +203,7 @@ PT_HD void prepare_pixel_of(size_t i, size_t npix, const float* S, const V4* pla
     const float vy = history_variance(prev.y, q.y, va.y, Tf, Df, ns, hv.y, hc.w, keep_albedo);
     const float vz = history_variance(prev.z, q.z, va.z, Tf, Df, ns, hv.z, hc.w, keep_albedo);
     va.w = (vx + vy) + vz;
-  } else if constexpr (kForm == Form::Moments) {
+  } else if constexpr (kForm == Form::Moments || kForm == Form::Feedback) {
     const V4 mb = pthi::blend_moments(i, S, ns, hc.w, hv);
     if (mb.w <= PT_HISTORY_MOMENTS_R_MAX) {
       const float f = mb.w / (1.0f - mb.w);
@@ -191,6 +211,17 @@ PT_HD void prepare_pixel_of(size_t i, size_t npix, const float* S, const V4* pla
       const float vy = moments_variance(mb.y, cb.y, f, va.y, keep_albedo);
       const float vz = moments_variance(mb.z, cb.z, f, va.z, keep_albedo);
       va.w = (vx + vy) + vz;
+      if constexpr (kForm == Form::Feedback) {
+        if (d.fb_variance) {  // rule 1 in its place: the new view's variance and the one the filtered history carries, weighted as the blend
+          const float g = 1.0f - mb.w;
+          const float sx = feedback_view_variance(mb.x, cb.x, g, va.x, keep_albedo);
+          const float sy = feedback_view_variance(mb.y, cb.y, g, va.y, keep_albedo);
+          const float sz = feedback_view_variance(mb.z, cb.z, g, va.z, keep_albedo);
+          const float sv = (sx + sy) + sz;
+          const pthi::MomentWeights w = pthi::moment_weights(ns, hc.w);
+          va.w = (w.wn * w.wn) * sv + (w.wh * w.wh) * (d.FC ? d.FC[i].w : 0.0f);
+        }
+      }
     } else {
       va.w = kSpatialMark;  // too few views behind the blend (C absent included): var_spatial_pixel
     }
@@ -378,6 +409,16 @@ PT_HD void finish_pixel(size_t i, int keep_albedo, const V4* c, const V4* a, flo
   out[3 * i + 2] = demod && va.z > 0.0f ? vc.z * va.z : vc.z;
 }
 
+// feedback, the tap: pixel i of the pending plane P = {c_L remodulated as the finish step does, var_L}.  P4: a device plane (16-byte
+// stores) or a caller's host array (pthi::F4)
+template <typename P4>
+PT_HD void tap_pixel(size_t i, int keep_albedo, const V4* c, const V4* a, P4* tap) {
+#pragma clang fp contract(off)
+  const V4 vc = c[i], va = a[i];
+  const bool demod = !keep_albedo;
+  tap[i] = P4{demod && va.x > 0.0f ? vc.x * va.x : vc.x, demod && va.y > 0.0f ? vc.y * va.y : vc.y, demod && va.z > 0.0f ? vc.z * va.z : vc.z, vc.w};
+}
+
 // The colour buffer that holds c_l (prepare writes c_0 into buffer 0, level l reads l & 1 and writes the other); the finish step
 // writes its 12 bytes per pixel over the buffer that does not hold c_levels.
 PT_HD int color_buffer(int l) { return l & 1; }
@@ -390,12 +431,17 @@ struct Frame {
   const float *rgb_sum, *planes, *noise;
   const float *current = nullptr, *current_var = nullptr;
   const float* extra = nullptr;  // the moments form: the extra plane E, w * rows floats (null: absent)
+  const float* feedback = nullptr;  // the feedback form: the plane FC beside `current` (null: absent), which the host loop reads here
 };
+// tap_level, tap (the feedback form): after level tap_level - 1 the plane `tap` (w * rows float4: a device plane for a launch, a
+// caller's array for the host loop) receives tap_pixel of c_(tap_level); 1 .. P.levels.
 struct Job {
   Form form;
   Frame f;
   Divisors div;
   Params P;
+  int tap_level = 0;
+  void* tap = nullptr;
 };
 
 // The whole filter on the host, with the bodies above in the kernels' own thread order.  counts (the adaptive form): {T_p, M_p} per pixel
@@ -405,7 +451,8 @@ struct Job {
 inline void denoise_host(const Job& j, const int32_t* counts, float* out, float* var_raw = nullptr, float* var_0 = nullptr, uint8_t* mark = nullptr) {
   const int W = j.f.w, R = j.f.rows;
   const Params& P = j.P;
-  const bool guided = j.form != Form::Plain, folded = guided && j.form != Form::Moments, blended = j.form == Form::History || j.form == Form::Moments;
+  const bool feedback = j.form == Form::Feedback, moments = j.form == Form::Moments || feedback;
+  const bool guided = j.form != Form::Plain, folded = guided && !moments, blended = j.form == Form::History || moments;
   const size_t npix = (size_t)W * R;
   std::vector<V4> ws(kWorkspaceV4 * npix);
   V4 *n = ws.data(), *p = n + npix, *a = p + npix, *col[2] = {a + npix, a + 2 * npix};
@@ -423,16 +470,20 @@ inline void denoise_host(const Job& j, const int32_t* counts, float* out, float*
     hist[i] = V4{c[0], c[1], c[2], c[3]}, hist[npix + i] = V4{v[0], v[1], v[2], v[3]};
   }
   if (blended) d.C = hist.empty() ? nullptr : hist.data(), d.VC = hist.empty() ? nullptr : hist.data() + npix;
-  d.E = j.form == Form::Moments ? j.f.extra : nullptr;
+  std::vector<V4> fbc(feedback && j.f.feedback ? npix : 0);
+  for (size_t i = 0; i < fbc.size(); ++i) fbc[i] = V4{j.f.feedback[4 * i], j.f.feedback[4 * i + 1], j.f.feedback[4 * i + 2], j.f.feedback[4 * i + 3]};
+  d.FC = fbc.empty() ? nullptr : fbc.data();
+  d.E = moments ? j.f.extra : nullptr;
   for (size_t i = 0; i < npix; ++i) {
     if (j.form == Form::Plain) prepare_pixel_of<Form::Plain>(i, npix, j.f.rgb_sum, pl.data(), nz, d, P.keep_albedo, n, p, a, col[0]);
     else if (j.form == Form::Guided) prepare_pixel_of<Form::Guided>(i, npix, j.f.rgb_sum, pl.data(), nz, d, P.keep_albedo, n, p, a, col[0]);
     else if (j.form == Form::History) prepare_pixel_of<Form::History>(i, npix, j.f.rgb_sum, pl.data(), nz, d, P.keep_albedo, n, p, a, col[0]);
     else if (j.form == Form::Moments) prepare_pixel_of<Form::Moments>(i, npix, j.f.rgb_sum, pl.data(), nullptr, d, P.keep_albedo, n, p, a, col[0]);
+    else if (feedback) prepare_pixel_of<Form::Feedback>(i, npix, j.f.rgb_sum, pl.data(), nullptr, d, P.keep_albedo, n, p, a, col[0]);
     else prepare_pixel_of<Form::Adaptive>(i, npix, j.f.rgb_sum, pl.data(), nz, d, P.keep_albedo, n, p, a, col[0]);
   }
-  for (size_t i = 0; i < npix && mark; ++i) mark[i] = j.form == Form::Moments && spatial_marked(a[i].w) ? 1 : 0;
-  for (int y = 0; y < R && j.form == Form::Moments; ++y)
+  for (size_t i = 0; i < npix && mark; ++i) mark[i] = moments && spatial_marked(a[i].w) ? 1 : 0;
+  for (int y = 0; y < R && moments; ++y)
     for (int x = 0; x < W; ++x)
       if (spatial_marked(a[(size_t)y * W + x].w)) var_spatial_pixel(W, R, x, y, P, n, p, col[0], a);
   for (int y = 0; y < R && guided; ++y)
@@ -442,14 +493,17 @@ inline void denoise_host(const Job& j, const int32_t* counts, float* out, float*
     }
   for (size_t i = 0; i < npix && var_raw; ++i) var_raw[i] = a[i].w;
   for (size_t i = 0; i < npix && var_0; ++i) var_0[i] = col[0][i].w;
-  if (!out) return;
-  for (int l = 0; l < P.levels; ++l)
+  const bool tapped = feedback && j.tap;
+  if (!out && !tapped) return;
+  for (int l = 0; l < P.levels; ++l) {
     for (int ty = 0; ty < level_slots(R, l); ++ty)
       for (int x = 0; x < W; ++x) {
         if (guided) level_column_of<true>(W, R, x, ty, l, P, col[color_buffer(l)], n, p, col[color_buffer(l + 1)]);
         else level_column_of<false>(W, R, x, ty, l, P, col[color_buffer(l)], n, p, col[color_buffer(l + 1)]);
       }
-  for (size_t i = 0; i < npix; ++i) finish_pixel(i, P.keep_albedo, col[color_buffer(P.levels)], a, out);
+    for (size_t i = 0; i < npix && tapped && l + 1 == j.tap_level; ++i) tap_pixel(i, P.keep_albedo, col[color_buffer(l + 1)], a, static_cast<pthi::F4*>(j.tap));
+  }
+  for (size_t i = 0; i < npix && out; ++i) finish_pixel(i, P.keep_albedo, col[color_buffer(P.levels)], a, out);
 }
 
 }  // namespace ptdn

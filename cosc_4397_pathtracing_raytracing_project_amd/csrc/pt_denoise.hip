@@ -3,7 +3,8 @@
 // A translation unit of its own, compiled ONCE with -ffp-contract=off: the filter is specified as separate IEEE float32 operations
 // (pt_denoise.h), so there is nothing an arithmetic mode could change, and the path tracer's kernels (pt_kernels.hip) are not
 // rebuilt differently because of it.  The kernels are thin: thread indices in, the PT_HD bodies of pt_denoise.h, which the host
-// loop (ptdn::denoise_host, behind the pt_denoise*_host entry points) runs too.  Five templates, eleven kernels (ptdn::Form: Plain =
+// loop (ptdn::denoise_host, behind the pt_denoise*_host entry points) runs too.  Five templates, eleven kernels, and four for the
+// history round and the feedback, listed after them (ptdn::Form: Plain =
 // pt_denoise, Guided = pt_denoise_guided, Adaptive = pt_denoise_adaptive, History = pt_history_denoise, Moments = pt_history_denoise_ex
 // with PT_HISTORY_MOMENTS):
 //
@@ -32,6 +33,11 @@
 //                                  <true>, the guided forms: the same shape and loads (the variance rides in the colour's .w); per centre
 //                                  two more registers (its colour factor, the sum of w^2 var), per tap a multiply and a multiply-add
 //   k_denoise_finish               one thread per pixel: remodulation, 12 B per pixel
+// The feedback form (Feedback = pt_history_denoise_feedback) runs the moments form's kernels between two of its own:
+//   k_denoise_prepare_feedback<bool>  <Moments> with 16 B of FC more in per pixel (when present): the colour is the blend with the FILTERED
+//                                  history; var_raw from the raw chain, or from FC.w by option.  <true>: counted, 4 B of E more in
+//   k_history_feedback_tap         after level L - 1, one thread per pixel, streaming: 16 B of c_L and 16 B of the albedo buffer in, 16 B of
+//                                  the pending plane P out (48 B per pixel); no LDS
 #include <hip/hip_runtime.h>
 
 #include "pt_denoise.h"
@@ -103,6 +109,44 @@ __global__ __launch_bounds__(kBlock) void k_denoise_prepare_counted(int npix, co
   if (i < npix) ptdn::prepare_pixel_of<Form::Moments>((size_t)i, (size_t)npix, S, planes, nullptr, d, keep_albedo, n, p, a, c);
 }
 
+// The feedback form's prepare: kernels of their own, so that the moments form's keep their arguments and their code.
+struct PrepareInFeedback {
+  const V4* __restrict__ C;
+  const V4* __restrict__ VC;
+  const V4* __restrict__ FC;
+  float samples;
+  int fb_variance;
+};
+struct PrepareInFeedbackCounted {
+  const V4* __restrict__ C;
+  const V4* __restrict__ VC;
+  const V4* __restrict__ FC;
+  float samples;
+  int fb_variance;
+  const float* __restrict__ E;
+};
+template <bool kCounted>
+__global__ __launch_bounds__(kBlock) void k_denoise_prepare_feedback(int npix, const float* __restrict__ S, const V4* __restrict__ planes, const V4* __restrict__ C,
+                                                                     const V4* __restrict__ VC, const V4* __restrict__ FC, float samples, int fb_variance,
+                                                                     const float* __restrict__ E, int keep_albedo, V4* __restrict__ n, V4* __restrict__ p,
+                                                                     V4* __restrict__ a, V4* __restrict__ c) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= npix) return;
+  if constexpr (kCounted) {
+    const PrepareInFeedbackCounted d{C, VC, FC, samples, fb_variance, E};
+    ptdn::prepare_pixel_of<Form::Feedback>((size_t)i, (size_t)npix, S, planes, nullptr, d, keep_albedo, n, p, a, c);
+  } else {
+    const PrepareInFeedback d{C, VC, FC, samples, fb_variance};
+    ptdn::prepare_pixel_of<Form::Feedback>((size_t)i, (size_t)npix, S, planes, nullptr, d, keep_albedo, n, p, a, c);
+  }
+}
+// The tap: the pending plane P from c_L and the albedo buffer
+__global__ __launch_bounds__(kBlock) void k_history_feedback_tap(int npix, int keep_albedo, const V4* __restrict__ c, const V4* __restrict__ a,
+                                                                 pthi::V4* __restrict__ tap) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < npix) ptdn::tap_pixel((size_t)i, keep_albedo, c, a, tap);
+}
+
 // `a` is read (the lane's own mark) and written (the lane's own var_raw): no __restrict__ promise is needed or made for it.
 __global__ __launch_bounds__(kBlock) void k_denoise_var_spatial(int W, int R, Params P, const V4* __restrict__ n, const V4* __restrict__ p,
                                                                 const V4* __restrict__ c, V4* a) {
@@ -139,7 +183,8 @@ __global__ __launch_bounds__(kBlock) void k_denoise_finish(int npix, int keep_al
 
 // pt_internal.h.  Everything is checked before the first launch; no allocation, no synchronisation.
 int pt_denoise_launch(hipStream_t stream, const ptdn::Job& j, void* workspace_dev, const float** rgb_avg_dev) {
-  static const char* const kWho[] = {"pt_denoise", "pt_denoise_guided", "pt_denoise_adaptive", "pt_history_denoise", "pt_history_denoise_ex"};
+  static const char* const kWho[] = {"pt_denoise", "pt_denoise_guided", "pt_denoise_adaptive", "pt_history_denoise", "pt_history_denoise_ex",
+                                     "pt_history_denoise_feedback"};
   const char* who = kWho[(int)j.form];
   const int w = j.f.w, rows = j.f.rows;
   const Params& P = j.P;
@@ -149,14 +194,17 @@ int pt_denoise_launch(hipStream_t stream, const ptdn::Job& j, void* workspace_de
                   : j.form == Form::Guided   ? j.f.noise && d.Tf >= 2.0f && d.Df >= d.Tf
                   : j.form == Form::Adaptive ? j.f.noise && (d.cnt || (d.M >= 2 && d.T >= d.M))
                   : j.form == Form::Moments  ? d.samples > 0.0f && !d.C == !d.VC
+                  : j.form == Form::Feedback ? d.samples > 0.0f && !d.C == !d.VC && !d.C == !d.FC && (d.fb_variance == 0 || d.fb_variance == 1) && j.tap &&
+                                                   j.tap_level >= 1 && j.tap_level <= P.levels
                                              : j.f.noise && d.Tf >= 2.0f && d.Df >= d.Tf && d.samples > 0.0f && !d.C == !d.VC;
-  if (!j.f.rgb_sum || !j.f.planes || !workspace_dev || !ok || (d.E && j.form != Form::Moments) || P.levels < 1 || P.levels > ptdn::kMaxLevels) return pt_fail("%s: bad argument", who);
+  if (!j.f.rgb_sum || !j.f.planes || !workspace_dev || !ok || (d.E && j.form != Form::Moments && j.form != Form::Feedback) || P.levels < 1 || P.levels > ptdn::kMaxLevels) return pt_fail("%s: bad argument", who);
   const int npix = w * rows;
   V4* n = static_cast<V4*>(workspace_dev);
   V4 *p = n + npix, *a = p + npix, *col[2] = {a + npix, a + 2 * (size_t)npix};
   const int flat = (npix + kBlock - 1) / kBlock;
   const dim3 tiles((w + kLevelX - 1) / kLevelX, (rows + kLevelY - 1) / kLevelY);
-  const bool guided = j.form != Form::Plain, adaptive = j.form == Form::Adaptive, history = j.form == Form::History, moments = j.form == Form::Moments;
+  const bool guided = j.form != Form::Plain, adaptive = j.form == Form::Adaptive, history = j.form == Form::History, feedback = j.form == Form::Feedback,
+             moments = j.form == Form::Moments || feedback;
   const V4 *planes = reinterpret_cast<const V4*>(j.f.planes), *noise = reinterpret_cast<const V4*>(j.f.noise);
   if (adaptive)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_denoise_prepare<Form::Adaptive, const V4* __restrict__, const ptad::Cnt* __restrict__, int, int>), dim3(flat), dim3(kBlock),
@@ -164,6 +212,12 @@ int pt_denoise_launch(hipStream_t stream, const ptdn::Job& j, void* workspace_de
   else if (history)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_denoise_prepare<Form::History, const V4* __restrict__, const V4* __restrict__, const V4* __restrict__, float, float, float>),
                        dim3(flat), dim3(kBlock), 0, stream, npix, j.f.rgb_sum, planes, noise, d.C, d.VC, d.Tf, d.Df, d.samples, P.keep_albedo, n, p, a, col[0]);
+  else if (feedback && d.E)
+    hipLaunchKernelGGL(k_denoise_prepare_feedback<true>, dim3(flat), dim3(kBlock), 0, stream, npix, j.f.rgb_sum, planes, d.C, d.VC, d.FC, d.samples, d.fb_variance, d.E,
+                       P.keep_albedo, n, p, a, col[0]);
+  else if (feedback)
+    hipLaunchKernelGGL(k_denoise_prepare_feedback<false>, dim3(flat), dim3(kBlock), 0, stream, npix, j.f.rgb_sum, planes, d.C, d.VC, d.FC, d.samples, d.fb_variance,
+                       static_cast<const float*>(nullptr), P.keep_albedo, n, p, a, col[0]);
   else if (moments && d.E)
     hipLaunchKernelGGL(k_denoise_prepare_counted, dim3(flat), dim3(kBlock), 0, stream, npix, j.f.rgb_sum, planes, d.C, d.VC, d.samples, d.E, P.keep_albedo, n, p, a,
                        col[0]);
@@ -183,6 +237,9 @@ int pt_denoise_launch(hipStream_t stream, const ptdn::Job& j, void* workspace_de
     const dim3 grid(tiles.x, (ptdn::level_slots(rows, l) + kLevelY - 1) / kLevelY);
     hipLaunchKernelGGL(guided ? k_denoise_level<true> : k_denoise_level<false>, grid, dim3(kBlock), 0, stream, w, rows, l, P, col[ptdn::color_buffer(l)], n, p,
                        col[ptdn::color_buffer(l + 1)]);
+    if (feedback && l + 1 == j.tap_level)
+      hipLaunchKernelGGL(k_history_feedback_tap, dim3(flat), dim3(kBlock), 0, stream, npix, P.keep_albedo, col[ptdn::color_buffer(l + 1)], a,
+                         static_cast<pthi::V4*>(j.tap));
   }
   float* out = reinterpret_cast<float*>(col[ptdn::color_buffer(P.levels + 1)]);
   hipLaunchKernelGGL(k_denoise_finish, dim3(flat), dim3(kBlock), 0, stream, npix, P.keep_albedo, col[ptdn::color_buffer(P.levels)], a, out);
@@ -204,9 +261,10 @@ int pt_denoise_resolve(const char* who, ptdn::Form form, float samples, int grou
   }
   *j = ptdn::Job{};
   j->form = form;
-  if (const char* msg = ptdn::resolve(opt, &j->P, form == Form::Plain ? 4.0f : form == Form::History || form == Form::Moments ? ptdn::kHistorySigmaColor : ptdn::kGuidedSigmaColor)) return pt_fail("%s: %s", who, msg);
+  const bool blended = form == Form::History || form == Form::Moments || form == Form::Feedback;
+  if (const char* msg = ptdn::resolve(opt, &j->P, form == Form::Plain ? 4.0f : blended ? ptdn::kHistorySigmaColor : ptdn::kGuidedSigmaColor)) return pt_fail("%s: %s", who, msg);
   if (form == Form::Plain) j->div.Tf = samples;
-  if (form == Form::History || form == Form::Moments) j->div.samples = samples;
+  if (blended) j->div.samples = samples;
   if (form == Form::Guided || form == Form::History) {
     const ptnz::Fold f = ptnz::fold_scalars(1, groups, iters);
     j->div.Tf = f.Tf, j->div.Df = f.Df;
@@ -255,6 +313,30 @@ int pt_history_denoise_moments_check(const char* who, int w, int rows, const flo
     return pt_fail("%s: the current plane %s its moments: both or neither (a lookup made with PT_HISTORY_MOMENTS gives both)", who,
                    current_plane ? "comes without" : "is absent, but not");
   if (!has_output) return pt_fail("%s: null buffer", who);
+  return 0;
+}
+
+// ... and of the feedback form (pt_internal.h): the moments form's in their order, then fb out of range and C without FC.
+int pt_history_feedback_options(const char* who, const PtHistoryFeedbackOptions* fb, int levels, int* level, int* variance) {
+  PtHistoryFeedbackOptions o{};
+  if (fb) o = *fb;
+  if (o.level == 0) o.level = PT_HISTORY_FEEDBACK_LEVEL;
+  if (o.level < 1 || o.level > levels) return pt_fail("%s: feedback level %d is not in 1 .. %d (the filter's levels)", who, o.level, levels);
+  if (o.variance < -1 || o.variance > 1) return pt_fail("%s: feedback variance %d is not 1, or -1 for rule 0", who, o.variance);
+  if (o.variance == 0) o.variance = PT_HISTORY_FEEDBACK_VARIANCE;
+  if (o.variance == -1) o.variance = 0;
+  *level = o.level, *variance = o.variance;
+  return 0;
+}
+int pt_history_denoise_feedback_check(const char* who, int w, int rows, const float* rgb_sum, const float* planes, float samples, const float* current_plane,
+                                      const float* current_var, const float* current_fb, const PtDenoiseOptions* opt, const PtHistoryFeedbackOptions* fb,
+                                      bool has_output, ptdn::Job* j) {
+  if (pt_history_denoise_moments_check(who, w, rows, rgb_sum, planes, samples, current_plane, current_var, opt, has_output, j)) return -1;
+  j->form = Form::Feedback;
+  if (pt_history_feedback_options(who, fb, j->P.levels, &j->tap_level, &j->div.fb_variance)) return -1;
+  if (!current_plane != !current_fb)
+    return pt_fail("%s: the current plane %s its filtered colour: both or neither (a lookup made with PT_HISTORY_FEEDBACK gives both)", who,
+                   current_plane ? "comes without" : "is absent, but not");
   return 0;
 }
 
@@ -318,6 +400,20 @@ int pt_history_denoise_moments_counted_host(int w, int rows, const float* rgb_su
   if (pt_history_denoise_moments_check(who, w, rows, rgb_sum, planes, samples, current_plane, current_var, opt, rgb_avg || var_raw || mark, &j)) return -1;
   if (pt_history_check_extra(who, w * rows, extra)) return -1;
   j.f = {w, rows, rgb_sum, planes, nullptr, current_plane, current_var, extra};
+  ptdn::denoise_host(j, nullptr, rgb_avg, var_raw, nullptr, mark);
+  return 0;
+}
+int pt_history_denoise_feedback_host(int w, int rows, const float* rgb_sum, const float* planes, float samples, const float* extra, const float* current_plane,
+                                     const float* current_var, const float* current_fb, const PtDenoiseOptions* opt, const PtHistoryFeedbackOptions* fb,
+                                     float* rgb_avg, float* tap, float* var_raw, uint8_t* mark) {
+  const char* who = "pt_history_denoise_feedback_host";
+  ptdn::Job j{};
+  if (pt_history_denoise_feedback_check(who, w, rows, rgb_sum, planes, samples, current_plane, current_var, current_fb, opt, fb,
+                                        rgb_avg || tap || var_raw || mark, &j))
+    return -1;
+  if (extra && pt_history_check_extra(who, w * rows, extra)) return -1;
+  j.f = {w, rows, rgb_sum, planes, nullptr, current_plane, current_var, extra, current_fb};
+  j.tap = tap;
   ptdn::denoise_host(j, nullptr, rgb_avg, var_raw, nullptr, mark);
   return 0;
 }

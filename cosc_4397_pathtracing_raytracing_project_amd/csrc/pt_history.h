@@ -30,9 +30,13 @@
 // last view's sums, rendered again after an object moved — a sample is a pure function of (iteration, pixel, world), so the two sums
 // differ exactly where a path met something that changed — and C.w shortened around the probes that differ.
 //
+// The feedback (PT_HISTORY_FEEDBACK; reproject_pixel_of<kMoments, .., true>): a parallel plane pair for the FILTERED colour, FK = {f.xyz, vf}
+// beside K and FC beside C, resampled with the weights of the colour.  K0, VK, C and VC — the raw chain — are the bits they are
+// without it: the moments' variance m2b - cb^2 needs the raw first moment.  pt_history_denoise_feedback: ptdn::Form::Feedback in
+// pt_denoise.h, whose prepare filters blend(S, ns, FC, C.w) and whose tap leaves the plane the next capture promotes to FK.
+//
 // Out of scope (pt_amd.h says the same): pt_group_* (a context's interleaved rows cannot look up their neighbours), feeding the
-// history into the noise estimate, the history round in groups of contexts, a key that uses the carried variance, feeding the FILTERED image back into the history (K keeps the unfiltered
-// blend), objects that are added, removed or deformed (rigid and affine motion of an object: PT_HISTORY_MOTION), and correcting the smoothing the bilinear lookup adds — the carried image is a biased estimator, and the carried
+// history into the noise estimate, the history round in groups of contexts, a key that uses the carried variance, objects that are added, removed or deformed (rigid and affine motion of an object: PT_HISTORY_MOTION), and correcting the smoothing the bilinear lookup adds — the carried image is a biased estimator, and the carried
 // variance is interpolated linearly (as SVGF interpolates its moments), which overstates it: the lookup's smoothing lowers the true one.
 #pragma once
 #include <cstddef>
@@ -280,14 +284,20 @@ PT_HD void capture_pixel(size_t i, size_t npix, const float* S, const P4* feat, 
 // and mo.kind one byte per geom (motion_table below): 0 still, 1 moved, 2 carries nothing.  One step after the first rejections:
 // for kind 1 the pixel's p and n become p' = D (p, 1) and n' = Nm n / |Nm n|, and everything after reads those; an id outside
 // 1 .. num_geoms (seen only with keep_view_dependent) counts as still.  <..., false> is the body as it stood.
-template <int kKind, bool kMotion = false, typename P4>
+//
+// kFeedback (PT_HISTORY_FEEDBACK, with kMoments only): the filtered colour travels beside the raw chain.  FK(q) = {f.xyz, vf} is read
+// after VK(q), for a tap that passed only; all four components are interpolated with the weights of the colour, and *fc receives FC's
+// value for the pixel, all zero wherever the pixel is rejected.  The cap touches nothing of it.  C and vh are what <.., false> gives.
+template <int kKind, bool kMotion = false, bool kFeedback = false, typename P4>
 PT_HD P4 reproject_pixel_of(size_t i, const View& v, const P4* K, const P4* feat, const uint8_t* reject, int32_t num_geoms, const Params& P, const P4* VK,
-                            P4& vh, const Motion& mo = Motion{}) {
+                            P4& vh, const Motion& mo = Motion{}, [[maybe_unused]] const P4* FK = nullptr, [[maybe_unused]] P4* fc = nullptr) {
 #pragma clang fp contract(off)
+  static_assert(!kFeedback || kKind == kMoments, "the filtered colour travels beside the moments");
   const size_t npix = (size_t)v.W * v.R;
   const P4 zero{0.0f, 0.0f, 0.0f, 0.0f};
   constexpr bool kVar = kKind != kPlain;
   if constexpr (kVar) vh = zero;
+  if constexpr (kFeedback) *fc = zero;
   Surface s = surface(i, npix, feat);
   if (!s.hit) return zero;
   if (!P.keep_view_dependent && (s.id < 1 || s.id > num_geoms || reject[s.id - 1])) return zero;
@@ -322,6 +332,7 @@ PT_HD P4 reproject_pixel_of(size_t i, const View& v, const P4* K, const P4* feat
   const float tol = P.plane_tol * dz;
   float accx = 0.0f, accy = 0.0f, accz = 0.0f, tacc = 0.0f, wsum = 0.0f;
   [[maybe_unused]] float vaccx = 0.0f, vaccy = 0.0f, vaccz = 0.0f, vaccw = 0.0f;
+  [[maybe_unused]] float faccx = 0.0f, faccy = 0.0f, faccz = 0.0f, faccw = 0.0f;
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int qr = iy + j;
@@ -349,6 +360,10 @@ PT_HD P4 reproject_pixel_of(size_t i, const View& v, const P4* K, const P4* feat
         vaccx = vaccx + b * vk.x, vaccy = vaccy + b * vk.y, vaccz = vaccz + b * vk.z;
         if constexpr (kKind == kMoments) vaccw = vaccw + b * vk.w;
       }
+      if constexpr (kFeedback) {
+        const P4 fk = FK[q];
+        faccx = faccx + b * fk.x, faccy = faccy + b * fk.y, faccz = faccz + b * fk.z, faccw = faccw + b * fk.w;
+      }
       wsum = wsum + b;
     }
   }
@@ -356,6 +371,7 @@ PT_HD P4 reproject_pixel_of(size_t i, const View& v, const P4* K, const P4* feat
   const float tw = tacc / wsum;
   if constexpr (kKind == kVariance) vh = P4{vaccx / wsum, vaccy / wsum, vaccz / wsum, 0.0f};
   if constexpr (kKind == kMoments) vh = P4{vaccx / wsum, vaccy / wsum, vaccz / wsum, vaccw / wsum};
+  if constexpr (kFeedback) *fc = P4{faccx / wsum, faccy / wsum, faccz / wsum, faccw / wsum};
   return P4{accx / wsum, accy / wsum, accz / wsum, tw < P.cap ? tw : P.cap};
 }
 template <typename P4>
@@ -413,6 +429,17 @@ inline void reproject_motion_host(const View& v, const float* K, const float* fe
   for (size_t i = 0; i < npix; ++i)
     out[i] = reproject_pixel_of<kKind, true>(i, v, reinterpret_cast<const F4*>(K), reinterpret_cast<const F4*>(feat), reject, num_geoms, P,
                                              reinterpret_cast<const F4*>(VK), kKind == kPlain ? unused : vout[i], mo);
+}
+// ... and with the filtered colour (PT_HISTORY_FEEDBACK): the moments lookup, FK beside VK and FC beside VC; mo: the motion table, or
+// nullptr (the lookup without PT_HISTORY_MOTION).
+inline void reproject_feedback_host(const View& v, const float* K, const float* feat, const uint8_t* reject, int32_t num_geoms, const Params& P, const float* VK,
+                                    const float* FK, const Motion* mo, float* C, float* VC, float* FC) {
+  const size_t npix = (size_t)v.W * v.R;
+  F4 *out = reinterpret_cast<F4*>(C), *vout = reinterpret_cast<F4*>(VC), *fout = reinterpret_cast<F4*>(FC);
+  const F4 *k4 = reinterpret_cast<const F4*>(K), *f4 = reinterpret_cast<const F4*>(feat), *vk4 = reinterpret_cast<const F4*>(VK), *fk4 = reinterpret_cast<const F4*>(FK);
+  for (size_t i = 0; i < npix; ++i)
+    out[i] = mo ? reproject_pixel_of<kMoments, true, true>(i, v, k4, f4, reject, num_geoms, P, vk4, vout[i], *mo, fk4, &fout[i])
+                : reproject_pixel_of<kMoments, false, true>(i, v, k4, f4, reject, num_geoms, P, vk4, vout[i], Motion{}, fk4, &fout[i]);
 }
 // The motion table of pt_amd.h (pt_history_motion_host): row g and kind[g] from the kept and the current geom g.  Every factor is
 // widened to double, the products and sums are plain double operations in the order written, the result is rounded to float once.

@@ -20,6 +20,9 @@
 //   k_history_reproject<kMoments>   the same loads and stores; the fourth component of VK is interpolated too
 //   k_history_reproject_motion<kPlain | kVariance | kMoments>  the lookup with PT_HISTORY_MOTION: the loads and stores of the kernel
 //                        above, one kind byte per pixel and 84 B of a table row for a pixel of a moved geom; launched only when a geom moved
+//   k_history_reproject_feedback<bool kMotion>  the moments lookup with PT_HISTORY_FEEDBACK: + 16 B of FC out per pixel; per tap that passed
+//                        16 B of FK, read after VK at the same index; <true>: with the motion table, as k_history_reproject_motion.  Kernels
+//                        of their own: the ones above are the code they were
 // The history round (pt_history_round):
 //   k_history_key        a pure stream, one thread per tile pixel: the .w words of the feature sums s1 and s2 and (when present) of C
 //                        in, as 4-byte loads 16 bytes apart — 12 B per pixel asked for, whole lines moved: consecutive lanes sit in
@@ -99,6 +102,22 @@ __global__ __launch_bounds__(kBlock) void k_history_reproject_motion(int npix, V
   } else {
     C[i] = pthi::reproject_pixel_of<kKind, true>((size_t)i, v, K, feat, reject, num_geoms, P, static_cast<const V4*>(nullptr), vh, mo);
   }
+}
+
+// ... with the filtered colour beside the moments (PT_HISTORY_FEEDBACK): C and VC are the bits the kernels above write.  table, mkind:
+// read for kMotion only.
+template <bool kMotion>
+__global__ __launch_bounds__(kBlock) void k_history_reproject_feedback(int npix, View v, const V4* __restrict__ K, const V4* __restrict__ feat,
+                                                                       const uint8_t* __restrict__ reject, int num_geoms, Params P,
+                                                                       const float* __restrict__ table, const uint8_t* __restrict__ mkind,
+                                                                       V4* __restrict__ C, const V4* __restrict__ VK, V4* __restrict__ VC,
+                                                                       const V4* __restrict__ FK, V4* __restrict__ FC) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= npix) return;
+  V4 vh, fc;
+  C[i] = pthi::reproject_pixel_of<pthi::kMoments, kMotion, true>((size_t)i, v, K, feat, reject, num_geoms, P, VK, vh, pthi::Motion{table, mkind}, FK, &fc);
+  VC[i] = vh;
+  FC[i] = fc;
 }
 
 __global__ __launch_bounds__(kBlock) void k_history_blend(int npix, const float* __restrict__ S, float samples, const V4* __restrict__ C,
@@ -253,6 +272,25 @@ int pt_history_reproject_motion_launch(hipStream_t stream, uint32_t kind, const 
                        table_dev, kind_dev, C, VK, VC);
   else
     hipLaunchKernelGGL(k_history_reproject_motion<pthi::kPlain>, grid, block, 0, stream, npix, v, K, feat, reject_dev, num_geoms, P, table_dev, kind_dev, C);
+  return launched(who);
+}
+
+// The moments lookup with PT_HISTORY_FEEDBACK: kept_fb_dev FK, current_fb_dev FC; table_dev / kind_dev both null (no geom moved, or
+// no PT_HISTORY_MOTION) or both given (num_geoms >= 1).
+int pt_history_reproject_feedback_launch(hipStream_t stream, const pthi::View& v, const void* kept_dev, const float* planes_dev, const uint8_t* reject_dev,
+                                         int num_geoms, const pthi::Params& P, void* current_dev, const void* kept_var_dev, void* current_var_dev,
+                                         const void* kept_fb_dev, void* current_fb_dev, const float* table_dev, const uint8_t* kind_dev) {
+  const char* who = "pt_history_reproject_ex";
+  if (bad_frame(v.W, v.R)) return pt_fail("%s: a tile of %d x %d pixels is not supported", who, v.W, v.R);
+  const bool motion = table_dev != nullptr;
+  if (!kept_dev || !planes_dev || !current_dev || !kept_var_dev || !current_var_dev || !kept_fb_dev || !current_fb_dev || motion != (kind_dev != nullptr) ||
+      (motion && num_geoms < 1) || (!P.keep_view_dependent && (num_geoms < 0 || (num_geoms > 0 && !reject_dev))))
+    return pt_fail("%s: bad argument (feedback)", who);
+  const int npix = v.W * v.R;
+  hipLaunchKernelGGL(motion ? k_history_reproject_feedback<true> : k_history_reproject_feedback<false>, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream,
+                     npix, v, static_cast<const V4*>(kept_dev), reinterpret_cast<const V4*>(planes_dev), reject_dev, num_geoms, P, table_dev, kind_dev,
+                     static_cast<V4*>(current_dev), static_cast<const V4*>(kept_var_dev), static_cast<V4*>(current_var_dev), static_cast<const V4*>(kept_fb_dev),
+                     static_cast<V4*>(current_fb_dev));
   return launched(who);
 }
 
@@ -510,6 +548,31 @@ extern "C" int pt_history_reproject_motion_host(int w, int rows, int row0, const
   if (flags & PT_HISTORY_VARIANCE) pthi::reproject_motion_host<pthi::kVariance>(v, kept_planes, feature_planes, reject_geom, num_geoms, P, kept_var, mo, current_plane, current_var);
   else if (flags & PT_HISTORY_MOMENTS) pthi::reproject_motion_host<pthi::kMoments>(v, kept_planes, feature_planes, reject_geom, num_geoms, P, kept_var, mo, current_plane, current_var);
   else pthi::reproject_motion_host<pthi::kPlain>(v, kept_planes, feature_planes, reject_geom, num_geoms, P, nullptr, mo, current_plane, nullptr);
+  return 0;
+}
+
+// What the host and stage forms of the lookup with feedback refuse after pt_history_reproject_check: the planes, then a table without
+// kinds (or the reverse) and a kind that is none.
+int pt_history_reproject_feedback_check(const char* who, int num_geoms, const float* kept_var, const float* kept_fb, const float* table, const uint8_t* kind,
+                                        const float* current_var, const float* current_fb) {
+  if (!kept_var || !kept_fb || !current_var || !current_fb) return pt_fail("%s: null argument", who);
+  if (!table != !kind) return pt_fail("%s: the motion table and the kinds come together or not at all", who);
+  if (table && num_geoms < 1) return pt_fail("%s: a motion table and kinds for at least one geom are needed", who);
+  for (int g = 0; table && g < num_geoms; ++g)
+    if (kind[g] > pthi::kCarriesNothing) return pt_fail("%s: kind[%d] = %d is not 0, 1 or 2", who, g, (int)kind[g]);
+  return 0;
+}
+extern "C" int pt_history_reproject_feedback_host(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
+                                                  const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, const float* kept_var,
+                                                  const float* kept_fb, const float* table, const uint8_t* kind, float* current_plane, float* current_var,
+                                                  float* current_fb) {
+  pthi::Params P{};
+  const char* who = "pt_history_reproject_feedback_host";
+  if (pt_history_reproject_check(who, w, rows, row0, kept_cam, kept_planes, feature_planes, reject_geom, num_geoms, opt, current_plane, &P)) return -1;
+  if (pt_history_reproject_feedback_check(who, num_geoms, kept_var, kept_fb, table, kind, current_var, current_fb)) return -1;
+  const pthi::Motion mo{table, kind};
+  pthi::reproject_feedback_host(pthi::make_view(*kept_cam, rows, row0), kept_planes, feature_planes, reject_geom, num_geoms, P, kept_var, kept_fb,
+                                table ? &mo : nullptr, current_plane, current_var, current_fb);
   return 0;
 }
 

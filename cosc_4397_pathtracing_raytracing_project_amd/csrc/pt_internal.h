@@ -35,6 +35,16 @@ int pt_history_denoise_check(const char* who, int w, int rows, const float* rgb_
 int pt_history_denoise_moments_check(const char* who, int w, int rows, const float* rgb_sum, const float* planes, float samples, const float* current_plane,
                                      const float* current_var, const PtDenoiseOptions* opt, bool has_output, ptdn::Job* j);
 
+// The feedback form (ptdn::Form::Feedback, pt_history_denoise_feedback): the moments form's refusals, then fb out of range (level 1 ..
+// the filter's levels, variance 1 or -1 for rule 0; 0 / NULL: the defaults) and C without FC; j->tap_level and j->div.fb_variance (the
+// rule, 0 or 1) resolved.
+// A launch reads FC from j->div.FC and writes the pending plane j->tap (w * rows float4) after level j->tap_level - 1.
+struct PtHistoryFeedbackOptions;
+int pt_history_feedback_options(const char* who, const PtHistoryFeedbackOptions* fb, int levels, int* level, int* variance);
+int pt_history_denoise_feedback_check(const char* who, int w, int rows, const float* rgb_sum, const float* planes, float samples, const float* current_plane,
+                                      const float* current_var, const float* current_fb, const PtDenoiseOptions* opt, const PtHistoryFeedbackOptions* fb,
+                                      bool has_output, ptdn::Job* j);
+
 // The noise estimate (pt_noise.hip), on raw device pointers and a stream.  state_dev holds pt_noise_state_bytes(pixels) bytes:
 // PT_NOISE_PLANES planes of `pixels` float4, then one double per PT_NOISE_PIXELS_PER_PARTIAL pixels (k_noise_fold's partial sums),
 // then the double they add up to (k_noise_reduce).  pt_noise_launch: one fold of the SUM image rgb_sum_dev (pixels * 3 floats) with the
@@ -133,6 +143,14 @@ int pt_history_reproject_motion_launch(hipStream_t stream, uint32_t kind, const 
 // What the host and stage forms of that lookup refuse after pt_history_reproject_check: the flag word, the table, the kinds, VK / VC.
 int pt_history_motion_check(const char* who, uint32_t flags, int num_geoms, const float* table, const uint8_t* kind, const float* kept_var,
                             const float* current_var);
+// The moments lookup with the filtered colour (PT_HISTORY_FEEDBACK): FK beside VK, FC beside VC, `pixels` float4 each; table_dev and
+// kind_dev as above, or both nullptr (nothing moved).  C and VC are the bits pt_history_reproject_moments_launch / _motion_launch write.
+inline size_t pt_history_feedback_bytes(size_t pixels) { return 48 * pixels; }  // the feedback state: three planes, the roles FK, FC and P
+int pt_history_reproject_feedback_launch(hipStream_t stream, const pthi::View& v, const void* kept_dev, const float* planes_dev, const uint8_t* reject_dev,
+                                         int num_geoms, const pthi::Params& P, void* current_dev, const void* kept_var_dev, void* current_var_dev,
+                                         const void* kept_fb_dev, void* current_fb_dev, const float* table_dev, const uint8_t* kind_dev);
+int pt_history_reproject_feedback_check(const char* who, int num_geoms, const float* kept_var, const float* kept_fb, const float* table, const uint8_t* kind,
+                                        const float* current_var, const float* current_fb);
 int pt_history_blend_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, float samples, const void* current_dev, float* rgb_avg_dev);
 // The history round (pt_history_round): the key of every tile pixel into key_dev (pt_adaptive_select_keys of the selection's workspace;
 // emitter_dev one byte per geom), the merge of the worker's group sum (m >= 1 list entries) into the image and the extra plane E

@@ -37,6 +37,7 @@ int pt_ctx_render_features(PtContext* c, int iter_first, int iter_count) {
   g.k->features(g.stream, g.grid_features, sc, g.dcam, tile_batch(g, iter_first, iter_count), g.d_feat);
   HIP_OK(hipGetLastError());
   g.feat_fresh = true;
+  g.fb_pending = false;  // the feedback's pending plane was filtered along other features
   return 0;
 }
 
@@ -478,14 +479,23 @@ static const char kNoFeatures[] = "%s: no feature pass has been rendered since t
 static pthi::V4* history_var_plane(const Ctx& g, int plane) { return static_cast<pthi::V4*>(g.d_hist_var) + (size_t)plane * g.N; }  // 0: VK, 1: VC
 // An undefined flag bit: what the _ex forms refuse right after a failed context.
 // motion: the lookup's word, which also defines PT_HISTORY_MOTION (alone or beside one of the two).
+// PT_HISTORY_FEEDBACK is defined in both words, beside PT_HISTORY_MOMENTS only.
 static int history_flags(const char* who, uint32_t flags, bool motion = false) {
   constexpr uint32_t kinds = PT_HISTORY_VARIANCE | PT_HISTORY_MOMENTS;
-  const uint32_t defined = kinds | (motion ? PT_HISTORY_MOTION : 0u);
+  const uint32_t defined = kinds | PT_HISTORY_FEEDBACK | (motion ? PT_HISTORY_MOTION : 0u);
   if (flags & ~defined)
-    return pt_fail("%s: undefined flag bit(s) 0x%x (defined: PT_HISTORY_VARIANCE, PT_HISTORY_MOMENTS%s)", who, flags & ~defined, motion ? ", PT_HISTORY_MOTION" : "");
+    return pt_fail("%s: undefined flag bit(s) 0x%x (defined: PT_HISTORY_VARIANCE, PT_HISTORY_MOMENTS%s, PT_HISTORY_FEEDBACK)", who, flags & ~defined,
+                   motion ? ", PT_HISTORY_MOTION" : "");
   if ((flags & kinds) == kinds) return pt_fail("%s: the flags PT_HISTORY_VARIANCE and PT_HISTORY_MOMENTS exclude each other", who);
+  if ((flags & PT_HISTORY_FEEDBACK) && (flags & PT_HISTORY_VARIANCE))
+    return pt_fail("%s: PT_HISTORY_FEEDBACK travels beside the moments, not with PT_HISTORY_VARIANCE", who);
+  if ((flags & PT_HISTORY_FEEDBACK) && !(flags & PT_HISTORY_MOMENTS))
+    return pt_fail("%s: PT_HISTORY_FEEDBACK needs PT_HISTORY_MOMENTS: the filtered colour travels beside the moments", who);
   return 0;
 }
+static pthi::V4* history_fb_plane(const Ctx& g, int plane) { return static_cast<pthi::V4*>(g.d_hist_fb) + (size_t)plane * g.N; }
+// The feedback state: from the first call that carries the flag on
+static int history_fb_ensure(Ctx& g) { return ensure(g, g.d_hist_fb, pt_history_feedback_bytes((size_t)g.N), Zero::on_stream); }
 // What the variance needs of the folds: at least two, nothing rendered since, and `samples` the iterations they hold.
 static int history_folds(const Ctx& g, const char* who, float samples) {
   if (!g.d_noise || g.noise_groups < 1) return pt_fail("%s: nothing has been folded (pt_noise_fold)", who);
@@ -512,9 +522,11 @@ static int history_capture(PtContext* c, const char* who, float samples, uint32_
   if (history_admit(g, who)) return -1;
   if (!g.d_feat || !g.feat_fresh) return pt_fail(kNoFeatures, who);
   if (pt_history_check_samples(who, samples)) return -1;
-  const bool var = (flags & PT_HISTORY_VARIANCE) != 0, mom = (flags & PT_HISTORY_MOMENTS) != 0;
+  const bool var = (flags & PT_HISTORY_VARIANCE) != 0, mom = (flags & PT_HISTORY_MOMENTS) != 0, fb = (flags & PT_HISTORY_FEEDBACK) != 0;
   if (var && (admit(g, who, kNoExtras) || history_folds(g, who, samples) || history_current_variance(g, who))) return -1;
   if (mom && history_current_moments(g, who)) return -1;
+  if (fb && !g.fb_pending)
+    return pt_fail("%s: the pending plane is absent: filter first (pt_history_denoise_feedback after the last pt_render, pt_history_round or pt_render_features)", who);
   HIP_OK(hipSetDevice(g.device));
   if (ensure(g, g.d_hist, pt_history_state_bytes((size_t)g.N), Zero::on_stream)) return -1;  // the first capture of the context
   if ((var || mom) && ensure(g, g.d_hist_var, pt_history_variance_bytes((size_t)g.N), Zero::on_stream)) return -1;  // ... with variance or moments
@@ -538,7 +550,9 @@ static int history_capture(PtContext* c, const char* who, float samples, uint32_
   g.hist_cam = g.cam;
   if (g.hist_geoms_stale) g.hist_geoms = g.camera_base.geoms, g.hist_geoms_stale = false, g.hist_motion_fresh = false;  // the kept geoms: retaken only after a pt_set_geoms
   g.hist_kept = true;
-  g.hist_var_kept = flags;  // a plain capture: kept without variance or moments
+  g.hist_var_kept = flags & ~PT_HISTORY_FEEDBACK;  // a plain capture: kept without variance or moments
+  if (fb) std::swap(g.fb_plane_kept, g.fb_plane_pending), g.fb_pending = false;  // FK := P: the roles change, no bytes move
+  g.fb_kept = fb;  // a capture without the flag: kept without feedback
   return 0;
 }
 int pt_ctx_history_capture(PtContext* c, float samples) { return history_capture(c, "pt_history_capture", samples, 0u, false); }
@@ -594,8 +608,8 @@ static int history_reproject(PtContext* c, const char* who, const PtHistoryOptio
   if (need(c, who)) return -1;
   Ctx& g = *c;
   if (ex && (admit(g, who, kNotFailed) || history_flags(who, flags, true))) return -1;
-  const bool motion = (flags & PT_HISTORY_MOTION) != 0;
-  flags &= ~PT_HISTORY_MOTION;  // what is left names the kind: 0, PT_HISTORY_VARIANCE or PT_HISTORY_MOMENTS
+  const bool motion = (flags & PT_HISTORY_MOTION) != 0, fb = (flags & PT_HISTORY_FEEDBACK) != 0;
+  flags &= ~(PT_HISTORY_MOTION | PT_HISTORY_FEEDBACK);  // what is left names the kind: 0, PT_HISTORY_VARIANCE or PT_HISTORY_MOMENTS
   if (history_admit(g, who)) return -1;
   if (!g.d_hist || !g.hist_kept) return pt_fail("%s: nothing has been captured (pt_history_capture)", who);
   if (!g.d_feat || !g.feat_fresh) return pt_fail(kNoFeatures, who);
@@ -605,6 +619,8 @@ static int history_reproject(PtContext* c, const char* who, const PtHistoryOptio
     return pt_fail("%s: nothing has been captured with variance (pt_history_capture_ex with PT_HISTORY_VARIANCE)", who);
   if (flags == PT_HISTORY_MOMENTS && (!g.d_hist_var || g.hist_var_kept != PT_HISTORY_MOMENTS))
     return pt_fail("%s: nothing has been captured with moments (pt_history_capture_ex with PT_HISTORY_MOMENTS)", who);
+  if (fb && (!g.d_hist_fb || !g.fb_kept))
+    return pt_fail("%s: nothing has been captured with feedback (pt_history_capture_ex with PT_HISTORY_MOMENTS | PT_HISTORY_FEEDBACK)", who);
   HIP_OK(hipSetDevice(g.device));
   if (history_reject_table(g)) return -1;
   const int W = g.cam.resolution[0];
@@ -613,7 +629,13 @@ static int history_reproject(PtContext* c, const char* who, const PtHistoryOptio
   const int num_geoms = (int)g.camera_base.geoms.size();
   bool moved = false;
   if (motion && history_motion_table(g, &moved)) return -1;
-  if (moved) {
+  if (fb) {
+    const float* table = moved ? static_cast<const float*>(g.d_hist_motion) : nullptr;
+    const uint8_t* kind = moved ? reinterpret_cast<const uint8_t*>(table + (size_t)num_geoms * pthi::kMotionRow) : nullptr;
+    if (pt_history_reproject_feedback_launch(g.stream, v, g.d_hist, feat, g.d_hist_reject, num_geoms, P, history_plane(g, pthi::kKeptPlanes), history_var_plane(g, 0),
+                                             history_var_plane(g, 1), history_fb_plane(g, g.fb_plane_kept), history_fb_plane(g, g.fb_plane_current), table, kind))
+      return -1;
+  } else if (moved) {
     const float* table = static_cast<const float*>(g.d_hist_motion);
     const uint8_t* kind = reinterpret_cast<const uint8_t*>(table + (size_t)num_geoms * pthi::kMotionRow);
     if (pt_history_reproject_motion_launch(g.stream, flags, v, g.d_hist, feat, g.d_hist_reject, num_geoms, P, history_plane(g, pthi::kKeptPlanes),
@@ -629,6 +651,7 @@ static int history_reproject(PtContext* c, const char* who, const PtHistoryOptio
     return -1;
   g.hist_current = true;
   g.hist_var_current = flags;
+  g.fb_current = fb;  // a lookup without the flag leaves FC absent
   g.probe_applied = false;  // a new C: the probes may be checked against it
   return 0;
 }
@@ -716,6 +739,72 @@ int pt_ctx_history_denoise_ex(PtContext* c, float samples, const PtDenoiseOption
   ptdn::Job j{};
   if (flags ? history_denoise_moments_refusal(*c, who, samples, opt, &j) : history_denoise_refusal(*c, who, samples, opt, &j)) return -1;  // (before the null buffer)
   return copy_out(c, who, rgb_avg_host, 3, [&](const float** d) { return pt_ctx_history_denoise_ex_device(c, samples, opt, flags, d); });
+}
+
+// ---- ... and with the filtered history (ptdn::Form::Feedback) ----------------------------------------------------------------
+// Everything pt_history_denoise_feedback refuses but the null buffer, in its order: the moments form's, then fb out of range, C without
+// FC, and rule 1 in another unit than the one FC.w was tapped in; the job resolved.
+static int history_denoise_feedback_refusal(const Ctx& g, const char* who, float samples, const PtDenoiseOptions* opt, const PtHistoryFeedbackOptions* fb,
+                                            ptdn::Job* j) {
+  if (history_denoise_moments_refusal(g, who, samples, opt, j)) return -1;
+  j->form = ptdn::Form::Feedback;
+  if (pt_history_feedback_options(who, fb, j->P.levels, &j->tap_level, &j->div.fb_variance)) return -1;
+  if (g.hist_current && !g.fb_current)
+    return pt_fail("%s: the current plane has no filtered colour: the lookup was made without PT_HISTORY_FEEDBACK (pt_history_reproject_ex)", who);
+  if (j->div.fb_variance == 1 && g.fb_current && j->P.keep_albedo != g.fb_keep_albedo)
+    return pt_fail("%s: feedback variance 1 with keep_albedo %d, but the carried variance was tapped with keep_albedo %d: the two are in different units", who,
+                   j->P.keep_albedo, g.fb_keep_albedo);
+  return 0;
+}
+int pt_ctx_history_denoise_feedback_device(PtContext* c, float samples, const PtDenoiseOptions* opt, const PtHistoryFeedbackOptions* fb, const float** rgb_dev) {
+  const char* who = "pt_history_denoise_feedback";
+  if (need(c, who)) return -1;
+  Ctx& g = *c;
+  if (admit(g, who, kNotFailed)) return -1;
+  ptdn::Job j{};
+  if (history_denoise_feedback_refusal(g, who, samples, opt, fb, &j)) return -1;
+  if (!rgb_dev) return pt_fail("%s: null buffer", who);
+  HIP_OK(hipSetDevice(g.device));
+  if (ensure(g, g.d_denoise, pt_denoise_workspace_bytes((size_t)g.N)) || history_fb_ensure(g)) return -1;
+  const int W = g.cam.resolution[0];
+  j.f = {W, g.N / W, g.d_image, reinterpret_cast<const float*>(g.d_feat), nullptr};
+  if (g.hist_current) {
+    j.div.C = reinterpret_cast<const ptdn::V4*>(history_plane(g, pthi::kKeptPlanes));
+    j.div.VC = reinterpret_cast<const ptdn::V4*>(history_var_plane(g, 1));
+    j.div.FC = reinterpret_cast<const ptdn::V4*>(history_fb_plane(g, g.fb_plane_current));
+  }
+  j.div.E = g.hist_extra ? g.d_hist_extra : nullptr;  // counted: the prepare reads ns = samples + E_p
+  j.tap = history_fb_plane(g, g.fb_plane_pending);
+  g.fb_pending = false;
+  if (pt_denoise_launch(g.stream, j, g.d_denoise, rgb_dev)) return -1;
+  g.fb_pending = true;
+  g.fb_keep_albedo = j.P.keep_albedo;
+  return 0;
+}
+int pt_ctx_history_denoise_feedback(PtContext* c, float samples, const PtDenoiseOptions* opt, const PtHistoryFeedbackOptions* fb, float* rgb_avg_host) {
+  const char* who = "pt_history_denoise_feedback";
+  if (need(c, who)) return -1;
+  if (admit(*c, who, kNotFailed)) return -1;
+  ptdn::Job j{};
+  if (history_denoise_feedback_refusal(*c, who, samples, opt, fb, &j)) return -1;  // (before the null buffer)
+  return copy_out(c, who, rgb_avg_host, 3, [&](const float** d) { return pt_ctx_history_denoise_feedback_device(c, samples, opt, fb, d); });
+}
+
+// FK, FC and P, each N float4; an absent plane reads as zeros; any pointer may be NULL
+int pt_ctx_readback_history_feedback(PtContext* c, float* kept, float* current, float* pending) {
+  if (need(c, "pt_readback_history_feedback")) return -1;
+  Ctx& g = *c;
+  HIP_OK(hipSetDevice(g.device));
+  const size_t plane = (size_t)g.N * sizeof(pthi::V4);
+  float* const host[3] = {kept, current, pending};
+  const bool have[3] = {g.d_hist_fb && g.fb_kept, g.d_hist_fb && g.fb_current, g.d_hist_fb && g.fb_pending};
+  const int at[3] = {g.fb_plane_kept, g.fb_plane_current, g.fb_plane_pending};
+  for (int k = 0; k < 3; ++k)
+    if (host[k] && have[k]) HIP_OK(hipMemcpyAsync(host[k], history_fb_plane(g, at[k]), plane, hipMemcpyDeviceToHost, g.stream));
+  if (pt_ctx_sync(c)) return -1;
+  for (int k = 0; k < 3; ++k)
+    if (host[k] && !have[k]) std::fill(host[k], host[k] + 4 * (size_t)g.N, 0.0f);
+  return 0;
 }
 
 int pt_ctx_history_resolve_device(PtContext* c, float samples, const float** rgb_dev) {
@@ -811,6 +900,7 @@ int pt_ctx_history_round(PtContext* c, int iter_first, int group_iters, const Pt
   if (m < 0 || m > cap || (int)result[0] < m) return pt_fail("%s: the selection left %u fresh, a list of %u (cap %d)", who, result[0], result[1], cap);
   if (fresh) *fresh = (int)result[0];
   if (selected) *selected = m;
+  g.fb_pending = false;  // the feedback's pending plane is the filter of the image before the round, whatever the round renders
   if (m == 0) return 0;  // nothing rendered, merged or allocated; E keeps its state
   if (ensure(g, g.d_hist_extra, (size_t)g.N * sizeof(float), Zero::on_stream)) return -1;  // the first round that renders (pt_clear zeroes it from then on)
   set_worker_live(*g.worker, m);
@@ -968,6 +1058,7 @@ int pt_ctx_history_drop(PtContext* c) {
   }
   g.hist_kept = g.hist_current = false;
   g.hist_var_kept = g.hist_var_current = 0;
+  g.fb_kept = g.fb_current = g.fb_pending = false;  // the feedback's three planes are forgotten with K
   g.probe_kept = g.probe_checked = g.probe_applied = false;  // the probes are forgotten with K, their L with C
   return 0;
 }

@@ -3,7 +3,7 @@
 // state.iterations iterations, write the PNG saveImage() would write.  Flags exist only because
 // the reference takes resolution, iteration count and depth from the scene file (scene.cpp:103-114).
 //
-//   pt_render SCENE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] [--orbit N [--device-tables] [--move G:DX,DY,DZ [--orbit-still]] [--reproject [--history-cap C] [--denoise-history [--history-moments]] [--history-extra G [--history-min M] [--history-extra-cap F]] [--history-probe [--probe-radius R] [--probe-gain X]]]]
+//   pt_render SCENE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] [--orbit N [--device-tables] [--move G:DX,DY,DZ [--orbit-still]] [--reproject [--history-cap C] [--denoise-history [--history-moments [--history-feedback [--feedback-level L] [--feedback-variance V]]]] [--history-extra G [--history-min M] [--history-extra-cap F]] [--history-probe [--probe-radius R] [--probe-gain X]]]]
 //                       [--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa]
 //                       [--preview N] [--convergence N | --reference FILE.pfm] [--clean-db X] [--features]
 //                       [--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]]
@@ -74,6 +74,11 @@
 // capture carry the history's moments instead (PT_HISTORY_MOMENTS), the filter is pt_history_denoise_ex with them, and a frame is one
 // pt_render call without folds; the same output names.  --history-cap C: PtHistoryOptions.cap (default 32).  Prints per frame
 // `history: frame f: <valid> of <pixels> pixels carried, mean weight <x>`.
+// --history-feedback (with --denoise-history --history-moments; composes with --history-extra, --move and --history-probe): the filtered
+// image is fed back into the history (PT_HISTORY_FEEDBACK).  The lookup and the capture carry the flag and the filter is
+// pt_history_denoise_feedback, so a frame's order is render, features, lookup, check, round, filter, capture, move; the same output
+// names.  --feedback-level L (1 .. the filter's levels) and --feedback-variance V (the rule, 0 or 1): PtHistoryFeedbackOptions, whose
+// defaults (pt_amd.h) are level 1, rule 1.  Prints once `feedback: the output of filter level <L> is fed back, variance rule <V>`.
 // --history-extra G (with --reproject, alone or with --denoise-history --history-moments; refused with --denoise-history alone, whose
 // variance comes from the folds and knows nothing of extra samples): between the lookup and the resolve pt_history_round gives the
 // pixels whose carried weight is below --history-min M (default 4) G further iterations, --history-extra-cap F of the frame at the
@@ -106,7 +111,7 @@
 int main(int argc, char** argv) {
   if (argc < 2) {
     std::printf("Usage: %s SCENEFILE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] "
-                "[--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa] [--orbit N [--device-tables] [--reproject [--history-cap C] [--denoise-history [--history-moments]] [--history-extra G [--history-min M] [--history-extra-cap F]] [--history-probe [--probe-radius R] [--probe-gain X]]] [--move G:DX,DY,DZ [--orbit-still]]] [--preview N] "
+                "[--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa] [--orbit N [--device-tables] [--reproject [--history-cap C] [--denoise-history [--history-moments [--history-feedback [--feedback-level L] [--feedback-variance V]]]] [--history-extra G [--history-min M] [--history-extra-cap F]] [--history-probe [--probe-radius R] [--probe-gain X]]] [--move G:DX,DY,DZ [--orbit-still]]] [--preview N] "
                 "[--convergence N | --reference FILE.pfm] [--clean-db X] [--features] "
                 "[--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]] [--denoise-guided] [--until-db X [--until-group G] [--adaptive F [--denoise-adaptive]]] "
                 "[--adaptive-threshold E [--adaptive-cap F] [--adaptive-min-pixels P] [--until-group G] [--denoise-adaptive]]\n", argv[0]);
@@ -124,6 +129,9 @@ int main(int argc, char** argv) {
   bool reproject = false;                           // --reproject
   bool dn_history = false;                          // --denoise-history
   bool hist_moments = false;                        // --history-moments
+  bool hist_feedback = false;                       // --history-feedback
+  PtHistoryFeedbackOptions fb_opt{};                // --feedback-level, --feedback-variance
+  bool fb_opt_given = false;
   float history_cap = 0.0f;                         // --history-cap C (0: the default)
   bool history_cap_given = false;
   int history_extra = 0;                            // --history-extra G (0: no rounds)
@@ -168,6 +176,20 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[i], "--reproject")) reproject = true;
     else if (!std::strcmp(argv[i], "--denoise-history")) dn_history = true;  // the blend filtered with the variance the history carries
     else if (!std::strcmp(argv[i], "--history-moments")) hist_moments = true;  // ... with the variance its moments give: no folds
+    else if (!std::strcmp(argv[i], "--history-feedback")) hist_feedback = true;  // ... and its output fed back into the history
+    else if ((!std::strcmp(argv[i], "--feedback-level") || !std::strcmp(argv[i], "--feedback-variance")) && i + 1 < argc) {
+      const bool is_level = !std::strcmp(argv[i], "--feedback-level");
+      char* end = nullptr;
+      const long v = std::strtol(argv[++i], &end, 10);
+      if (end == argv[i] || *end || v < (is_level ? 1 : 0) || v > (is_level ? 8 : 1)) {
+        std::fprintf(stderr, is_level ? "--feedback-level wants the filter level whose output is fed back, 1 to the filter's levels\n"
+                                      : "--feedback-variance wants 0 (the variance of the raw chain) or 1 (the one the filtered history carries)\n");
+        return 1;
+      }
+      if (is_level) fb_opt.level = (int32_t)v;
+      else fb_opt.variance = v ? 1 : -1;  // (the field: 0 = the default, -1 = rule 0)
+      fb_opt_given = true;
+    }
     else if (!std::strcmp(argv[i], "--history-cap") && i + 1 < argc) {
       history_cap = (float)std::atof(argv[++i]);
       history_cap_given = true;
@@ -361,6 +383,14 @@ int main(int argc, char** argv) {
   }
   if (hist_moments && !dn_history) {
     std::fprintf(stderr, "--history-moments wants --denoise-history (it chooses what the filter over the blend takes its variance from)\n");
+    return 1;
+  }
+  if (hist_feedback && !hist_moments) {
+    std::fprintf(stderr, "--history-feedback wants --history-moments (the filtered colour travels beside the history's moments)\n");
+    return 1;
+  }
+  if (fb_opt_given && !hist_feedback) {
+    std::fprintf(stderr, "--feedback-level and --feedback-variance want --history-feedback\n");
     return 1;
   }
   if (!denoise && !guided && !dn_adaptive && !dn_history && (dn_opt.levels || dn_opt.keep_albedo || dn_opt.sigma_color != 0.0f || dn_opt.sigma_normal != 0.0f || dn_opt.sigma_position != 0.0f)) {
@@ -596,6 +626,8 @@ int main(int argc, char** argv) {
       carried.resize((size_t)W * H * 3);
       current.resize((size_t)W * H * 4);
       if (dn_history) filtered.resize((size_t)W * H * 3);
+      if (hist_feedback) std::printf("feedback: the output of filter level %d is fed back, variance rule %d\n", fb_opt.level ? fb_opt.level : PT_HISTORY_FEEDBACK_LEVEL,
+                                     fb_opt.variance ? (fb_opt.variance > 0 ? 1 : 0) : PT_HISTORY_FEEDBACK_VARIANCE);
       if (history_extra)
         std::printf("history: frame f renders iterations f * %d + 1 .. f * %d + %d, then %d more for the pixels whose history is short\n", iters + history_extra,
                     iters + history_extra, iters, history_extra);
@@ -661,14 +693,18 @@ int main(int argc, char** argv) {
       if (pfm && pt_save_pfm((frame + ".pfm").c_str(), scene->state.image.data(), W, H, (float)iters) == 0) std::printf("Saved %s.pfm.\n", frame.c_str());
       if (hdr && pt_save_hdr((frame + ".hdr").c_str(), scene->state.image.data(), W, H, (float)iters) == 0) std::printf("Saved %s.hdr.\n", frame.c_str());
       if (reproject) {  // the view's first hits, the history looked up from them, the blend written, the blend kept for the next view
-        const uint32_t hflags = !dn_history ? 0u : hist_moments ? PT_HISTORY_MOMENTS : PT_HISTORY_VARIANCE;  // 0: the plain calls
+        const uint32_t hflags = !dn_history     ? 0u  // 0: the plain calls
+                                : hist_feedback ? PT_HISTORY_MOMENTS | PT_HISTORY_FEEDBACK
+                                : hist_moments  ? PT_HISTORY_MOMENTS
+                                                : PT_HISTORY_VARIANCE;
         int fresh = 0, selected = 0;  // --history-extra: the round, between the lookup and the resolve
         int probes = 0, changed = 0, skipped = 0;  // --history-probe: the check after the lookup, the keep before the round
         if (pt_render_features(1, 1) || (f > 0 && pt_history_reproject_ex(&hopt, hflags | (move ? PT_HISTORY_MOTION : 0u))) ||
             (history_probe && ((f > 0 && pt_history_probe_check(&probe_opt, &probes, &changed, &skipped)) || pt_history_probe_keep(iter_first, iters, f % 9))) ||
             (history_extra && pt_history_round(iter_first + iters, history_extra, &round_opt, &fresh, &selected)) || pt_history_resolve((float)iters, carried.data()) ||
-            (dn_history && (hist_moments ? pt_history_denoise_ex((float)iters, &dn_opt, PT_HISTORY_MOMENTS, filtered.data())
-                                         : pt_history_denoise((float)iters, &dn_opt, filtered.data()))) || pt_history_capture_ex((float)iters, hflags) ||
+            (dn_history && (hist_feedback  ? pt_history_denoise_feedback((float)iters, &dn_opt, &fb_opt, filtered.data())
+                            : hist_moments ? pt_history_denoise_ex((float)iters, &dn_opt, PT_HISTORY_MOMENTS, filtered.data())
+                                           : pt_history_denoise((float)iters, &dn_opt, filtered.data()))) || pt_history_capture_ex((float)iters, hflags) ||
             pt_readback_history(nullptr, current.data())) {
           std::fprintf(stderr, "HIP error (pt_history): %s\n", pt_last_error());
           return EXIT_FAILURE;
@@ -682,7 +718,7 @@ int main(int argc, char** argv) {
         if (history_extra) std::printf("history: frame %d: %d extra over %d of %d fresh pixels\n", f, history_extra, selected, fresh);
         if (pt_save_png((frame + ".reprojected.png").c_str(), carried.data(), W, H, 1.0f) == 0) std::printf("Saved %s.reprojected.png.\n", frame.c_str());
         if (pfm && pt_save_pfm((frame + ".reprojected.pfm").c_str(), carried.data(), W, H, 1.0f) == 0) std::printf("Saved %s.reprojected.pfm.\n", frame.c_str());
-        if (dn_history) {  // the history keeps the unfiltered blend: the filtered one is written, not fed back
+        if (dn_history) {  // the history keeps the unfiltered blend; --history-feedback: and, beside it, the filtered one
           if (pt_save_png((frame + ".reprojected.denoised.png").c_str(), filtered.data(), W, H, 1.0f) == 0) std::printf("Saved %s.reprojected.denoised.png.\n", frame.c_str());
           if (pfm && pt_save_pfm((frame + ".reprojected.denoised.pfm").c_str(), filtered.data(), W, H, 1.0f) == 0)
             std::printf("Saved %s.reprojected.denoised.pfm.\n", frame.c_str());

@@ -466,6 +466,72 @@ int pt_stage_history_denoise_moments(int w, int rows, const float* rgb_sum, cons
   return filter_stage_job(g, who, w, rows, rgb_sum, planes, nullptr, rgb_avg, j);
 }
 
+// ... and the feedback form's (pt_history_denoise_feedback_host's arguments but var_raw and mark): the prepare with FC (counted when
+// `extra` is given), the moments form's kernels, the tap after level fb->level - 1; rgb_avg and tap, either may be null but not both
+int pt_stage_history_denoise_feedback(int w, int rows, const float* rgb_sum, const float* planes, float samples, const float* extra, const float* current_plane,
+                                      const float* current_var, const float* current_fb, const PtDenoiseOptions* opt, const PtHistoryFeedbackOptions* fb,
+                                      float* rgb_avg, float* tap) {
+  const char* who = "pt_stage_history_denoise_feedback";
+  if (need(default_context(), who)) return -1;
+  Ctx& g = *default_context();
+  if (rows >= 32768) return pt_fail("%s: a frame of %d x %d pixels is not supported", who, w, rows);
+  ptdn::Job j{};
+  if (pt_history_denoise_feedback_check(who, w, rows, rgb_sum, planes, samples, current_plane, current_var, current_fb, opt, fb, rgb_avg || tap, &j)) return -1;
+  const size_t n = (size_t)w * rows;
+  if (extra && pt_history_check_extra(who, (int)n, extra)) return -1;
+  Scratch hist_sc;  // (filter_stage synchronises before it returns)
+  float *d_cur = nullptr, *d_var = nullptr, *d_fb = nullptr, *d_extra = nullptr;
+  HIP_OK(hipSetDevice(g.device));
+  float* d_tap = hist_sc.get<float>(4 * n);
+  if (!d_tap) return pt_fail("%s: out of device memory", who);
+  HIP_OK(hipMemset(d_tap, 0xff, 4 * n * sizeof(float)));  // a pixel nobody wrote shows as NaNs
+  if (current_plane && (device_copy(hist_sc, who, current_plane, 4 * n, &d_cur) || device_copy(hist_sc, who, current_var, 4 * n, &d_var) ||
+                        device_copy(hist_sc, who, current_fb, 4 * n, &d_fb)))
+    return -1;
+  if (extra && device_copy(hist_sc, who, extra, n, &d_extra)) return -1;
+  j.div.C = reinterpret_cast<const ptdn::V4*>(d_cur), j.div.VC = reinterpret_cast<const ptdn::V4*>(d_var), j.div.FC = reinterpret_cast<const ptdn::V4*>(d_fb);
+  j.div.E = d_extra;
+  j.tap = d_tap;
+  std::vector<float> avg(rgb_avg ? 0 : 3 * n);  // (filter_stage writes an image)
+  if (filter_stage_job(g, who, w, rows, rgb_sum, planes, nullptr, rgb_avg ? rgb_avg : avg.data(), j)) return -1;
+  if (tap) HIP_OK(hipMemcpy(tap, d_tap, 4 * n * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// The lookup with the filtered colour on caller-supplied host arrays (pt_history_reproject_feedback_host's arguments)
+int pt_stage_history_reproject_feedback(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
+                                        const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, const float* kept_var, const float* kept_fb,
+                                        const float* table, const uint8_t* kind, float* current_plane, float* current_var, float* current_fb) {
+  const char* who = "pt_stage_history_reproject_feedback";
+  if (need(default_context(), who)) return -1;
+  Ctx& g = *default_context();
+  pthi::Params P{};
+  if (pt_history_reproject_check(who, w, rows, row0, kept_cam, kept_planes, feature_planes, reject_geom, num_geoms, opt, current_plane, &P)) return -1;
+  if (pt_history_reproject_feedback_check(who, num_geoms, kept_var, kept_fb, table, kind, current_var, current_fb)) return -1;
+  if (rows >= 32768) return pt_fail("%s: a tile of %d x %d pixels is not supported", who, w, rows);
+  HIP_OK(hipSetDevice(g.device));
+  Scratch sc;
+  const size_t n = (size_t)w * rows;
+  float *d_kept = nullptr, *d_feat = nullptr, *d_kvar = nullptr, *d_kfb = nullptr, *d_table = nullptr;
+  uint8_t *d_reject = nullptr, *d_kind = nullptr;
+  float* d_cur = sc.get<float>(12 * n);  // C, then VC, then FC
+  if (!d_cur) return pt_fail("%s: out of device memory", who);
+  if (device_copy(sc, who, kept_planes, 4 * PT_HISTORY_KEPT_PLANES * n, &d_kept) || device_copy(sc, who, feature_planes, 4 * PT_FEATURE_PLANES * n, &d_feat) ||
+      device_copy(sc, who, kept_var, 4 * n, &d_kvar) || device_copy(sc, who, kept_fb, 4 * n, &d_kfb))
+    return -1;
+  if (table && (device_copy(sc, who, table, (size_t)pthi::kMotionRow * num_geoms, &d_table) || device_copy(sc, who, kind, (size_t)num_geoms, &d_kind))) return -1;
+  if (!P.keep_view_dependent && num_geoms > 0 && device_copy(sc, who, reject_geom, (size_t)num_geoms, &d_reject)) return -1;
+  HIP_OK(hipMemset(d_cur, 0xff, 12 * n * sizeof(float)));  // a pixel nobody wrote shows as NaNs
+  if (pt_history_reproject_feedback_launch(g.stream, pthi::make_view(*kept_cam, rows, row0), d_kept, d_feat, d_reject, num_geoms, P, d_cur, d_kvar, d_cur + 4 * n,
+                                           d_kfb, d_cur + 8 * n, d_table, d_kind))
+    return -1;
+  HIP_OK(hipStreamSynchronize(g.stream));
+  HIP_OK(hipMemcpy(current_plane, d_cur, 4 * n * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(current_var, d_cur + 4 * n, 4 * n * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(current_fb, d_cur + 8 * n, 4 * n * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
 // The selection's kernels on caller-supplied host arrays (pt_adaptive_select_host's arguments)
 int pt_stage_adaptive_select(int w, int rows, const float* noise_planes, const int32_t* counts, int m, int32_t* list) {
   if (need(default_context(), "pt_stage_adaptive_select")) return -1;

@@ -893,7 +893,8 @@ int pt_history_blend_host(int pixels, const float* rgb_sum, float samples, const
  * 4.525e-4, the filtered blend 1.396e-4 (0.3086 of it), pt_denoise_guided on the last view's own 4 spp 4.539e-4 (the filtered blend is
  * 0.3076 of it): history plus filter beats either alone.  The carried variance reads high (sum of VK 15.39 against the blend's squared
  * error 7.037 over the last view): recorded, not bounded.  One scene, one orbit: no claim beyond it.
- * Out of scope: feeding the FILTERED image back into the history (K keeps the unfiltered blend); pt_group_*.  A view with fewer than 2
+ * Out of scope: pt_group_*.  (K keeps the unfiltered blend; feeding the FILTERED image back beside it: "the feedback" below, with the
+ * moments kind only.)  A view with fewer than 2
  * folds (1 spp per frame) and a spatial estimate for disoccluded pixels: PT_HISTORY_MOMENTS, "moments with the history" below. */
 #define PT_HISTORY_VARIANCE 1u
 int pt_history_capture_ex(float samples, uint32_t flags);
@@ -964,8 +965,9 @@ int pt_history_denoise_host(int w, int rows, const float* rgb_sum, const float* 
  * C present with VC absent or of the variance kind; a null buffer.
  * What it buys: README "Moments with the history" (tests/test_history_moments_sim.py on the CPU, tests/test_gpu_history_moments.py on
  * an MI355X, the same digits).  One scene, one orbit: no claim beyond it.
- * Out of scope: feeding the FILTERED image back into the history; pt_group_*; feeding the history into the noise estimate; a
- * luminance-only variant; motion of anything but the camera.  (Extra samples for the marked pixels: "the history round" below.) */
+ * Out of scope: pt_group_*; feeding the history into the noise estimate; a luminance-only variant; motion of anything but the
+ * camera.  (Extra samples for the marked pixels: "the history round" below; feeding the FILTERED image back into the history: "the
+ * feedback" below, opt-in — without it K keeps the unfiltered blend.) */
 #define PT_HISTORY_MOMENTS 2u
 #define PT_HISTORY_MOMENTS_R_MAX 0.3f /* four equal views or more (r = 1/4): the literature's history length 4 */
 int pt_history_denoise_ex(float samples, const PtDenoiseOptions* opt, uint32_t flags, float* rgb_avg_host); /* synchronises */
@@ -1160,6 +1162,76 @@ int pt_history_probe_gradient_host(int w, int rows, int phase, const float* kept
 int pt_history_probe_apply_host(int w, int rows, int phase, const float* lam, const float* feature_planes, const uint8_t* moved_geom, int num_geoms,
                                 const PtHistoryProbeOptions* opt, float* current_plane);
 
+/* ---- the feedback: the FILTERED image fed back into the history (recurrent SVGF, Schied et al. 2017).  Without it every view filters
+ * the raw blend from scratch and the result is shown once; with it the output of filter level L is what the next view accumulates
+ * onto.  A fourth kind of history state, beside the moments.  Opt-in: a renderer that never passes PT_HISTORY_FEEDBACK allocates and
+ * launches nothing for it, and every other call keeps its kernels, memory, launches, results and refusals.  Specified like the rest
+ * of the history: float32, separate IEEE operations in the order written, one implementation for kernels and host loops, the same
+ * bits in all three PT_ARITH_* builds, host and device.
+ * The raw chain is not touched: K0 keeps the unfiltered blend and VK = {m2.xyz, r} (the moments' variance m2b - cb^2 needs the RAW
+ * first moment).  With the flag, K, VK, C, VC and pt_history_resolve's blend are bit for bit those of the same calls without it.
+ * State: a buffer of its own, three planes of pixel_count float4, 48 bytes per tile pixel.  The first call that carries the flag (or
+ * the first pt_history_denoise_feedback) allocates and zeroes it; PtStats.device_bytes counts it from then on.
+ *   P  (pending) = {f.xyz, vf}: the filter's colour after level L, remodulated (radiance), and the variance the guided levels
+ *        propagated for it, c_L.w, in the filter's unit (demodulated unless keep_albedo).  Aligned with the current camera.
+ *   FK = P as promoted by the last capture with the flag; aligned with K.
+ *   FC = FK resampled to the current camera; aligned with C.
+ *   FK lives as K does: it survives pt_clear, pt_set_camera[_ex] and pt_set_geoms.  FC and P become absent on all three.  P also
+ *   becomes absent on any pt_render, pt_history_round or pt_render_features after the tap.  pt_history_drop forgets all three.  A
+ *   capture without the flag after one with it leaves FK invalid (K "kept without feedback"); a lookup without it leaves FC absent.
+ *   The renderer remembers the keep_albedo the tap was made with.
+ * PT_HISTORY_FEEDBACK in pt_history_reproject_ex and pt_history_capture_ex: only together with PT_HISTORY_MOMENTS (the lookup: also
+ *   with PT_HISTORY_MOTION); without PT_HISTORY_MOMENTS, or with PT_HISTORY_VARIANCE, the call is refused, right where the flag word
+ *   is checked.  pt_history_denoise_ex keeps refusing the bit.
+ *   The lookup with the flag: C and VC as without it, the same bits.  Step 6 also starts facc = 0 over four components and, for a
+ *        tap that passed every test, adds after vacc  facc_k = facc_k + b * FK(q).k;  FK(q) is read after VK(q), for such a tap only.
+ *        Step 7: FC.k = facc_k / wsum for the four; a rejected pixel gets FC = 0; the cap touches nothing of FC.
+ *        Refused after the existing refusals: nothing captured with feedback.
+ *   The capture with the flag: K and VK exactly as the moments capture writes them (counted while E is present); FK := P — the planes
+ *        change roles, no bytes move — and P becomes absent.  Refused after the existing refusals: P absent (filter first:
+ *        pt_history_denoise_feedback).
+ * pt_history_denoise_feedback(samples, opt, fb, rgb_avg_host): the moments form of pt_history_denoise_ex with two changes.
+ *   fb: level (1 .. the filter's levels; 0 = PT_HISTORY_FEEDBACK_LEVEL) and the variance rule (1, or -1 for rule 0; 0 =
+ *        PT_HISTORY_FEEDBACK_VARIANCE); NULL = the defaults.  The defaults are the pair that tests/test_history_feedback_sim.py measured
+ *        lowest both on its orbit and with the camera standing still.
+ *   prepare: n, a, p, the hit flag, ns, cb_k, m2b, rb and d_k exactly as the moments form.  The colour that is filtered is
+ *        cf_k = blend(S_k, ns, FC.k, C.w), demodulated as every form's (FC and C absent: S_k / ns).
+ *        rule 0: var_raw and the spatial mark are the moments form's, from the raw chain (SVGF's choice; conservative: it
+ *        overstates the variance of a colour that was filtered before).
+ *        rule 1, where rb <= PT_HISTORY_MOMENTS_R_MAX:  g = 1.0f - rb;  s_k = d_k / g;  unless keep_albedo
+ *        s_k = a_k > 0 ? s_k / (a_k * a_k) : s_k;  sv = (s_x + s_y) + s_z;  wn = ns / (ns + C.w), wh = C.w / (ns + C.w);
+ *        var_raw = (wn * wn) * sv + (wh * wh) * FC.w.  Otherwise the mark.
+ *   then the moments form's spatial estimate, prefilter and levels, unchanged: the same kernels.  After level L - 1 a streaming kernel
+ *        writes P[i] = {finish(c_L, a).xyz, c_L.w} (48 B per pixel moved, no LDS); the remaining levels and the finish run unchanged.
+ *        With L == levels the tap's xyz equal the output.
+ *   Refusals: the moments form's, in their order; then fb out of range; C present with FC absent; rule 1 with a keep_albedo
+ *        other than the remembered one while FC is present; a null buffer.
+ * pt_readback_history_feedback(kept, current, pending): FK, FC and P, pixel_count * 4 floats each; an absent plane reads as zeros;
+ *   any pointer may be NULL.  Synchronises.
+ * What it buys: README "Feedback" (tests/test_history_feedback_sim.py on the CPU, tests/test_gpu_history_feedback.py on an MI355X, the
+ * same digits).  One scene, one orbit: no claim beyond it.
+ * Out of scope: groups of contexts; the variance kind. */
+#define PT_HISTORY_FEEDBACK 16u /* (8u stays undefined) */
+#define PT_HISTORY_FEEDBACK_LEVEL 1
+#define PT_HISTORY_FEEDBACK_VARIANCE 1
+typedef struct PtHistoryFeedbackOptions { /* every field: 0 = the default */
+  int32_t level;    /* the filter level whose output is fed back: 1 .. the filter's levels; default (0): PT_HISTORY_FEEDBACK_LEVEL */
+  int32_t variance; /* the rule: 1: var_raw from the new view's variance and the one FC carries; -1: rule 0, var_raw from the raw chain;
+                       default (0): PT_HISTORY_FEEDBACK_VARIANCE */
+} PtHistoryFeedbackOptions;
+int pt_history_denoise_feedback(float samples, const PtDenoiseOptions* opt, const PtHistoryFeedbackOptions* fb, float* rgb_avg_host); /* synchronises */
+int pt_readback_history_feedback(float* kept, float* current, float* pending);
+/* The same arithmetic on the host (no GPU); the device results equal these bit for bit.  The lookup: pt_history_reproject_moments_host's
+ * arguments, FK and FC beside VK and VC, and a motion table with its kinds (pt_history_reproject_motion_host's) or both NULL.  The
+ * filter: pt_history_denoise_moments_host's arguments, extra (the plane E, or NULL), FC beside C and VC (all three or none), fb, and the
+ * tap plane (w*rows*4 floats) as a further optional output; with var_raw or mark alone no level runs. */
+int pt_history_reproject_feedback_host(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
+                                       const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, const float* kept_var, const float* kept_fb,
+                                       const float* table, const uint8_t* kind, float* current_plane, float* current_var, float* current_fb);
+int pt_history_denoise_feedback_host(int w, int rows, const float* rgb_sum, const float* planes, float samples, const float* extra, const float* current_plane,
+                                     const float* current_var, const float* current_fb, const PtDenoiseOptions* opt, const PtHistoryFeedbackOptions* fb,
+                                     float* rgb_avg, float* tap, float* var_raw, uint8_t* mark);
+
 /* saveImage()'s per-pixel conversion (main.cpp:91-97 x mirror, image.cpp:26-30 clamp * 255 truncated) on the
  * device: pixel_count*3 bytes, row-major, x mirrored inside each row; the tile must consist of whole rows.
  * Reads back 3 B per pixel instead of 12. */
@@ -1236,6 +1308,10 @@ int pt_ctx_readback_history_extra(PtContext* c, float* extra_host);
 int pt_ctx_history_probe_keep(PtContext* c, int iter_first, int iter_count, int phase);
 int pt_ctx_history_probe_check(PtContext* c, const PtHistoryProbeOptions* opt, int* probes, int* changed, int* skipped);
 int pt_ctx_readback_history_probe(PtContext* c, float* kept, float* lam, int* count);
+int pt_ctx_history_denoise_feedback(PtContext* c, float samples, const PtDenoiseOptions* opt, const PtHistoryFeedbackOptions* fb, float* rgb_avg_host);
+int pt_ctx_history_denoise_feedback_device(PtContext* c, float samples, const PtDenoiseOptions* opt, const PtHistoryFeedbackOptions* fb,
+                                           const float** rgb_dev); /* as pt_ctx_denoise_device */
+int pt_ctx_readback_history_feedback(PtContext* c, float* kept, float* current, float* pending);
 const float* pt_ctx_device_noise(PtContext* c); /* device pointer of plane 0; the planes are contiguous; NULL before the first fold */
 const float* pt_ctx_device_features(PtContext* c); /* device pointer of plane 0; the planes are contiguous; NULL before the first pt_ctx_render_features */
 const float* pt_ctx_device_image(PtContext* c); /* device pointer of the tile SUM image */
@@ -1439,6 +1515,15 @@ int pt_stage_history_denoise_moments(int w, int rows, const float* rgb_sum, cons
 int pt_stage_history_select(int w, int rows, const float* feature_planes, const float* current_plane, const uint8_t* emitter_geom, int num_geoms,
                             const PtHistoryRoundOptions* opt, int32_t* list, int* fresh, int* m);
 int pt_stage_history_merge(int pixels, float* rgb_sum, float* extra, const int32_t* list, int m, const float* group_sum, int group_iters);
+/* The lookup with the filtered colour through k_history_reproject_feedback, and the feedback form of the filter — its prepare (counted
+ * when `extra` is given), the moments form's kernels, the tap — on caller-supplied host arrays (the host forms' arguments but var_raw and
+ * mark; rgb_avg or tap may be NULL, not both; rows < 32768). */
+int pt_stage_history_reproject_feedback(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
+                                        const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, const float* kept_var, const float* kept_fb,
+                                        const float* table, const uint8_t* kind, float* current_plane, float* current_var, float* current_fb);
+int pt_stage_history_denoise_feedback(int w, int rows, const float* rgb_sum, const float* planes, float samples, const float* extra, const float* current_plane,
+                                      const float* current_var, const float* current_fb, const PtDenoiseOptions* opt, const PtHistoryFeedbackOptions* fb,
+                                      float* rgb_avg, float* tap);
 
 /* ---- image output (src/image.cpp:22-45, src/main.cpp:86-107) ------------- */
 /* rgb_sum: W*H*3 floats (raw orientation); writes <path> as 8-bit PNG of

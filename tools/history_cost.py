@@ -25,7 +25,13 @@ pt_history_denoise_ex (device form) runs with C absent — the first view: every
 for each — and pt_history_capture_ex with the flag.  Then an orbit of 8 views 2 pi / 120 apart is run through lookup, filter and
 capture, and at its last view — a steady view — pt_history_reproject_ex and pt_history_denoise_ex are timed per repetition, beside
 pt_denoise (device form) on the same frame for scale; nothing is captured between the repetitions, so each looks the same history
-up and marks the same pixels, whose share is printed with the times.  pt_history_capture_ex is timed afterwards, on its own."""
+up and marks the same pixels, whose share is printed with the times.  pt_history_capture_ex is timed afterwards, on its own.
+
+Then the feedback (PT_HISTORY_FEEDBACK; profiles/history_feedback_cost.log holds this library's run between two of the parent
+revision's), on every scene, last, so that the steps above run as they ran: the same orbit of 8 views with the flag in lookup, filter
+(pt_history_denoise_feedback, the library's defaults) and capture; at its last view, per repetition, the moments lookup and then the
+lookup with the flag, pt_history_denoise_ex and then pt_history_denoise_feedback (device forms); then the filter and the capture with the
+flag as a pair (a capture promotes the pending plane, so each needs a tap before it), and the moments capture alone."""
 import argparse
 import ctypes as C
 import os
@@ -209,13 +215,8 @@ for name, text in (("cornell (7 primitives)", scenes.cornell_scene_text(res=(W, 
         if not hasattr(L, "pt_ctx_history_denoise_ex_device"):
             say("### this build of the library has no PT_HISTORY_MOMENTS")
             continue
-        if not name.startswith("cornell"):
-            continue
         MOM = capi.HISTORY_MOMENTS
-        capi._check(L.pt_ctx_history_drop(ctx))
-        capi._check(L.pt_ctx_clear(ctx))
-        capi._check(L.pt_ctx_render(ctx, 1, 1))
-        capi._check(L.pt_ctx_render_features(ctx, 1, 1))
+        one = C.c_float(1.0)
 
         def timed(calls):
             """calls: (name, function) run back to back per repetition between HIP events; the first repetition is dropped."""
@@ -234,6 +235,54 @@ for name, text in (("cornell (7 primitives)", scenes.cornell_scene_text(res=(W, 
                 hip.hipEventDestroy(e)
             return t
 
+        def feedback_part():
+            """The feedback, last on every scene: the orbit of 8 views with the flag, then the steady view's steps beside the moments kind's."""
+            if not hasattr(L, "pt_ctx_history_denoise_feedback_device"):
+                say("### this build of the library has no PT_HISTORY_FEEDBACK")
+                return
+            FB = MOM | capi.HISTORY_FEEDBACK
+            capi._check(L.pt_ctx_get_stats(ctx, C.byref(st)))
+            before = st.device_bytes
+            capi._check(L.pt_ctx_history_drop(ctx))
+            capi._check(L.pt_ctx_clear(ctx))
+            for f in range(8):
+                if f:
+                    cam = scene.orbit(np.float32(2 * np.pi / 120), 0.0, 0.0)
+                    capi._check(L.pt_ctx_set_camera(ctx, C.byref(cam)))
+                capi._check(L.pt_ctx_render(ctx, f + 1, 1))
+                capi._check(L.pt_ctx_render_features(ctx, 1, 1))
+                if f:
+                    capi._check(L.pt_ctx_history_reproject_ex(ctx, C.byref(hopt), FB))
+                if f < 7:
+                    capi._check(L.pt_ctx_history_denoise_feedback_device(ctx, one, None, None, C.byref(dev)))
+                    capi._check(L.pt_ctx_history_capture_ex(ctx, one, FB))
+            t = timed([("moments lookup", lambda: L.pt_ctx_history_reproject_ex(ctx, C.byref(hopt), MOM)),
+                       ("lookup", lambda: L.pt_ctx_history_reproject_ex(ctx, C.byref(hopt), FB)),
+                       ("moments filter", lambda: L.pt_ctx_history_denoise_ex_device(ctx, one, None, MOM, C.byref(dev))),
+                       ("filter", lambda: L.pt_ctx_history_denoise_feedback_device(ctx, one, None, None, C.byref(dev)))])
+            t.update(timed([("filter before a capture", lambda: L.pt_ctx_history_denoise_feedback_device(ctx, one, None, None, C.byref(dev))),
+                            ("capture", lambda: L.pt_ctx_history_capture_ex(ctx, one, FB))]))
+            t.update(timed([("moments capture", lambda: L.pt_ctx_history_capture_ex(ctx, one, MOM))]))
+            capi._check(L.pt_ctx_get_stats(ctx, C.byref(st)))
+            say(f"### with PT_HISTORY_FEEDBACK, a steady view (the 8th of an orbit, 1 iteration each): {(st.device_bytes - before) / 2**20:.1f} MB more state (FK, FC, P)")
+            line("reproject_ex, moments", t["moments lookup"], 48 + 16 + 16 + 4 * 64)
+            line("reproject_ex, + feedback", t["lookup"], 48 + 16 + 16 + 16 + 4 * 80)
+            line("pt_history_denoise_ex (dev.)", t["moments filter"])
+            line("denoise_feedback (dev.)", t["filter"])
+            line("capture_ex, moments", t["moments capture"], 12 + 48 + 16 + 48 + 16 + 16)
+            line("capture_ex, + feedback", t["capture"], 12 + 48 + 16 + 48 + 16 + 16)
+            say(f"the lookup with the flag against the moments lookup: {statistics.median(t['lookup']) - statistics.median(t['moments lookup']):+.4f} ms (16 B more out, "
+                f"16 B more per tap that passed); the feedback filter against pt_history_denoise_ex: "
+                f"{statistics.median(t['filter']) - statistics.median(t['moments filter']):+.4f} ms (the tap, 48 B per pixel, and 16 B per pixel more in prepare)")
+
+        if not name.startswith("cornell"):
+            feedback_part()
+            continue
+        capi._check(L.pt_ctx_history_drop(ctx))
+        capi._check(L.pt_ctx_clear(ctx))
+        capi._check(L.pt_ctx_render(ctx, 1, 1))
+        capi._check(L.pt_ctx_render_features(ctx, 1, 1))
+
         def marked_share():
             """The share of pixels pt_history_denoise_ex's prepare marks at this view: rb > PT_HISTORY_MOMENTS_R_MAX, from the readbacks."""
             vc, c4 = np.empty((W * H, 4), np.float32), np.empty((W * H, 4), np.float32)
@@ -244,7 +293,6 @@ for name, text in (("cornell (7 primitives)", scenes.cornell_scene_text(res=(W, 
             rb = wn * wn + (wh * wh) * vc[:, 3]
             return float((~(rb <= capi.HISTORY_MOMENTS_R_MAX)).mean())
 
-        one = C.c_float(1.0)
         t = timed([("denoise", lambda: L.pt_ctx_history_denoise_ex_device(ctx, one, None, MOM, C.byref(dev))),
                    ("capture", lambda: L.pt_ctx_history_capture_ex(ctx, one, MOM))])
         say("### with PT_HISTORY_MOMENTS, the first view (C absent): every pixel is marked for the spatial estimate")
@@ -271,6 +319,7 @@ for name, text in (("cornell (7 primitives)", scenes.cornell_scene_text(res=(W, 
         line("pt_denoise (device)", t["plain"])
         say(f"the steady-view filter against pt_history_denoise above: {statistics.median(t['denoise']) - history_denoise_median:+.4f} ms "
             f"(one launch more, k_denoise_var_spatial, which leaves on a ballot in every wave without a marked pixel; no noise planes read)")
+        feedback_part()
     finally:
         L.pt_ctx_destroy(ctx)
 out.close()
