@@ -446,6 +446,17 @@ def lib() -> C.CDLL:
         L.pt_stage_history_reproject_feedback.argtypes = _reproject_fb
         L.pt_history_denoise_feedback_host.argtypes = _fdn + [_fp, _u8p]
         L.pt_stage_history_denoise_feedback.argtypes = _fdn
+    if hasattr(L, "pt_history_noise"):  # absent from older A/B builds of the library (tools/build_rev.sh)
+        _hnz = [C.c_int, _fp, C.c_int, C.c_int64, C.c_float, _fp, _fp, _fp, _dp]
+        _huntil = [C.c_int, C.c_int, C.c_int, C.c_float, _ip, _fp, _fp]
+        L.pt_history_noise.argtypes = [C.c_float, C.c_uint32, _dp]
+        L.pt_readback_history_noise.argtypes = [_fp]
+        L.pt_history_render_until.argtypes = _huntil
+        L.pt_ctx_history_noise.argtypes = [C.c_void_p, C.c_float, C.c_uint32, _dp]
+        L.pt_ctx_readback_history_noise.argtypes = [C.c_void_p, _fp]
+        L.pt_ctx_history_render_until.argtypes = [C.c_void_p] + _huntil
+        L.pt_history_noise_host.argtypes = _hnz
+        L.pt_stage_history_noise.argtypes = _hnz
     _lib = L
     return L
 
@@ -828,6 +839,32 @@ def stage_history_denoise(rgb_sum, planes, noise_planes, w: int, rows: int, grou
                           **opts) -> np.ndarray:
     """history_denoise_host's arguments through the filter's kernels (pt_stage_history_denoise; a renderer must be live)."""
     return _history_denoise(lib().pt_stage_history_denoise, rgb_sum, planes, noise_planes, w, rows, groups, iters, samples, current, current_var, **opts)
+
+
+def _history_noise(call, noise_planes, groups: int, iters: int, samples: float, current, current_var):
+    z = np.ascontiguousarray(noise_planes, np.float32).reshape(-1)
+    n = z.size // (4 * NOISE_PLANES)
+    c = None if current is None else np.ascontiguousarray(current, np.float32).reshape(-1)
+    v = None if current_var is None else np.ascontiguousarray(current_var, np.float32).reshape(-1)
+    if z.size != 4 * NOISE_PLANES * n or any(a is not None and a.size != 4 * n for a in (c, v)):
+        raise PtError(f"history_noise: {z.size} noise plane floats")
+    w, sse = np.empty(n, np.float32), C.c_double(-1.0)
+    _check(call(n, _f(z), int(groups), int(iters), C.c_float(samples), None if c is None else _f(c), None if v is None else _f(v), _f(w), C.byref(sse)))
+    return w, float(sse.value)
+
+
+def history_noise_host(noise_planes: np.ndarray, groups: int, iters: int, samples: float, current: Optional[np.ndarray] = None,
+                       current_var: Optional[np.ndarray] = None):
+    """pt_history_noise on the host (no GPU): the fold's planes [PT_NOISE_PLANES, n, 4] with their counters M, T, and the planes C, VC
+    [n, 4] (None: absent) in; (W float32 [n], SSE_blend added in pixel order) out."""
+    return _history_noise(lib().pt_history_noise_host, noise_planes, groups, iters, samples, current, current_var)
+
+
+def stage_history_noise(noise_planes: np.ndarray, groups: int, iters: int, samples: float, current: Optional[np.ndarray] = None,
+                        current_var: Optional[np.ndarray] = None):
+    """history_noise_host's arguments through the production kernels (pt_stage_history_noise; a renderer must be live): (W, the
+    device's SSE_blend)."""
+    return _history_noise(lib().pt_stage_history_noise, noise_planes, groups, iters, samples, current, current_var)
 
 
 HISTORY_MOMENTS = 2  # PT_HISTORY_MOMENTS
@@ -1624,6 +1661,27 @@ class Renderer:
         vk, vc = np.empty((self.n, 4), np.float32), np.empty((self.n, 4), np.float32)
         _check(lib().pt_readback_history_variance(_f(vk), _f(vc)))
         return vk, vc
+
+    def history_noise(self, samples: float, flags: int = HISTORY_VARIANCE) -> float:
+        """SSE_blend: the variance of the blend of the image with the reprojected history, summed over the tile (pt_history_noise;
+        synchronises); psnr_from_sse(sse, n) is the estimated PSNR of the blend."""
+        sse = C.c_double(-1.0)
+        _check(lib().pt_history_noise(C.c_float(samples), int(flags), C.byref(sse)))
+        return float(sse.value)
+
+    def readback_history_noise(self) -> np.ndarray:
+        """The plane W of the last history_noise / history_render_until, float32 [n]."""
+        out = np.empty(self.n, np.float32)
+        _check(lib().pt_readback_history_noise(_f(out)))
+        return out
+
+    def history_render_until(self, iter_first: int, max_iters: int, target_db: float, group_iters: int = 0):
+        """render_until judging the blend with the history (pt_history_render_until): (iterations rendered, the blend's last estimated
+        PSNR in dB or -1, the view's own at the same fold or -1)."""
+        done, psnr, view = C.c_int32(0), C.c_float(-1.0), C.c_float(-1.0)
+        _check(lib().pt_history_render_until(int(iter_first), int(max_iters), int(group_iters), C.c_float(target_db), C.byref(done), C.byref(psnr),
+                                             C.byref(view)))
+        return int(done.value), float(psnr.value), float(view.value)
 
     def denoise(self, samples: float, **opts) -> np.ndarray:
         """The image filtered by the edge-avoiding filter over the feature buffers (pt_denoise; options: denoise_options):

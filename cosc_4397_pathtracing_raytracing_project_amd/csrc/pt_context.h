@@ -186,6 +186,9 @@ struct PtContext : PtShared {
   std::vector<uint8_t> hist_motion_kind;
   bool hist_motion_fresh = false;  // the table is that of hist_geoms and camera_base.geoms as they stand; hist_motion_moved: some kind != 0
   bool hist_motion_moved = false;
+  // The noise estimate of the blend (pt_ctx_history_noise): absent until the first estimate
+  void* d_hist_noise = nullptr;    // pt_history_noise_bytes(N): the partial sums, SSE_blend, then the plane W
+  bool hist_noise = false;         // W holds an estimate of the image as it stood; pt_clear and a move make it absent
   // The history round (pt_ctx_history_round): all of it absent until the first round that renders something
   float* d_hist_extra = nullptr;   // the extra plane E: N floats, the samples the image holds per pixel beyond the uniform ones
   bool hist_extra = false;         // E is present: from a round that rendered to pt_clear or a camera move, which zero it

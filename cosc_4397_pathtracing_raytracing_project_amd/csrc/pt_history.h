@@ -35,8 +35,12 @@
 // without it: the moments' variance m2b - cb^2 needs the raw first moment.  pt_history_denoise_feedback: ptdn::Form::Feedback in
 // pt_denoise.h, whose prepare filters blend(S, ns, FC, C.w) and whose tap leaves the plane the next capture promotes to FK.
 //
+// The noise estimate of the blend (pt_history_noise, pt_history_render_until; noise_value and noise_pixel below): the blend's variance of
+// the variance side, summed over the channels per pixel — what pt_noise.hip's k_history_noise and k_noise_fold_history sum over the tile
+// the way the fold sums its own estimate.
+//
 // Out of scope (pt_amd.h says the same): pt_group_* (a context's interleaved rows cannot look up their neighbours), feeding the
-// history into the noise estimate, the history round in groups of contexts, a key that uses the carried variance, objects that are added, removed or deformed (rigid and affine motion of an object: PT_HISTORY_MOTION), and correcting the smoothing the bilinear lookup adds — the carried image is a biased estimator, and the carried
+// moments into the noise estimate of the blend (noise_value below: the variance kind only), the history round in groups of contexts, a key that uses the carried variance, objects that are added, removed or deformed (rigid and affine motion of an object: PT_HISTORY_MOTION), and correcting the smoothing the bilinear lookup adds — the carried image is a biased estimator, and the carried
 // variance is interpolated linearly (as SVGF interpolates its moments), which overstates it: the lookup's smoothing lowers the true one.
 #pragma once
 #include <cstddef>
@@ -471,6 +475,35 @@ inline void motion_table(const PtGeom* kept, const PtGeom* cur, int n, float* ta
 }
 inline void blend_host(size_t npix, const float* S, float samples, const float* C, float* rgb_avg) {
   for (size_t i = 0; i < npix; ++i) blend_pixel(i, S, samples, reinterpret_cast<const F4*>(C), rgb_avg);
+}
+
+// ── the noise estimate of the blend (pt_history_noise) ───────────────────────────────────────────────────────────────────
+// w of one pixel: the blend's variance vb summed over the channels, from the two words the fold left for the pixel (prev, q: any
+// float4 type), Tf and Df of the folds so far, and the pixel's Th = C.w and vh = VC (C absent: Th = +0, vh all +0).  With C absent
+// wn = 1 and wh = +0, so w is the fold's own plane-0 .w bit for bit.
+template <typename N4, typename P4>
+PT_HD float noise_value(const N4& prev, const N4& q, float Tf, float Df, float samples, float Th, const P4& vh) {
+#pragma clang fp contract(off)
+  const float vx = blend_variance(sample_variance(prev.x, q.x, Tf, Df), samples, vh.x, Th);
+  const float vy = blend_variance(sample_variance(prev.y, q.y, Tf, Df), samples, vh.y, Th);
+  const float vz = blend_variance(sample_variance(prev.z, q.z, Tf, Df), samples, vh.z, Th);
+  return (vx + vy) + vz;
+}
+// Pixel i of a tile of npix pixels: noise = the fold's two planes; C, VC the current plane and its variance, or both nullptr.
+template <typename N4, typename P4>
+PT_HD float noise_pixel(size_t i, size_t npix, const N4* noise, float Tf, float Df, float samples, const P4* C, const P4* VC) {
+  const P4 zero{0.0f, 0.0f, 0.0f, 0.0f};
+  return noise_value(noise[i], noise[npix + i], Tf, Df, samples, C ? C[i].w : 0.0f, VC ? VC[i] : zero);
+}
+// The whole tile on the host; W (or nullptr) receives the plane, the estimates are added in pixel order.
+inline double noise_host(size_t npix, const float* noise, float Tf, float Df, float samples, const float* C, const float* VC, float* W) {
+  double sse = 0.0;
+  for (size_t i = 0; i < npix; ++i) {
+    const float w = noise_pixel(i, npix, reinterpret_cast<const F4*>(noise), Tf, Df, samples, reinterpret_cast<const F4*>(C), reinterpret_cast<const F4*>(VC));
+    if (W) W[i] = w;
+    sse += (double)w;
+  }
+  return sse;
 }
 
 // ── the history round (pt_history_round) ─────────────────────────────────────────────────────────────────────────────────

@@ -59,6 +59,20 @@ int64_t pt_ctx_unfolded_iterations(const PtContext* c);  // iterations rendered 
 int pt_noise_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, void* state_dev, const ptnz::Fold& f);
 // k_noise_reduce alone: *sse_dev = partial_dev[0] + ... + partial_dev[count - 1] in index order (one thread adds).
 int pt_noise_reduce_launch(hipStream_t stream, int count, const double* partial_dev, double* sse_dev);
+// The noise estimate of the blend (pt_history_noise; pt_noise.hip k_history_noise).  out_dev holds pt_history_noise_bytes(pixels)
+// bytes: one double per PT_NOISE_PIXELS_PER_PARTIAL pixels, the double they add up to (pt_history_noise_result), then the plane W of
+// `pixels` floats (the doubles first: 4 * pixels is no multiple of 8 for an odd tile).  state_dev: the fold's state; Tf, Df:
+// ptnz::fold_scalars' of the folds so far; current_dev / current_var_dev: C and VC, both or neither.
+// pt_noise_fold_history_launch: pt_noise_launch and pt_history_noise_launch as ONE kernel and the two reductions; f.have_variance.
+inline size_t pt_history_noise_bytes(size_t pixels) { return 4 * pixels + 8 * (pt_noise_partials(pixels) + 1); }
+inline const double* pt_history_noise_result(const void* out_dev, size_t pixels) { return static_cast<const double*>(out_dev) + pt_noise_partials(pixels); }
+inline float* pt_history_noise_plane(void* out_dev, size_t pixels) { return reinterpret_cast<float*>(static_cast<double*>(out_dev) + pt_noise_partials(pixels) + 1); }
+int pt_history_noise_launch(hipStream_t stream, int pixels, const void* state_dev, float Tf, float Df, float samples, const void* current_dev,
+                            const void* current_var_dev, void* out_dev);
+int pt_noise_fold_history_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, void* state_dev, const ptnz::Fold& f, float samples,
+                                 const void* current_dev, const void* current_var_dev, void* out_dev);
+int pt_history_noise_check(const char* who, int pixels, const float* noise_planes, int groups, int64_t iters, float samples, const float* current_plane,
+                           const float* current_var);
 
 // Adaptive sampling (pt_adaptive.hip), on raw device pointers and a stream; everything asynchronous, nothing allocated.
 // counts_dev: the plane `cnt`, pixels * {int32 T_p, int32 M_p}.  noise_dev / noise_state_dev: the fold's state (pt_noise_state_bytes).

@@ -48,8 +48,9 @@ PT_HD float fold_component(float s, float prev, float* q, const Fold& f) {
 }
 
 // Pixel i of a tile of npix pixels: S holds npix * 3 floats, planes PT_NOISE_PLANES * npix float4 (P4: V4 or F4).  Returns w.
+// kept (or nullptr): receives the two words the pixel's planes now hold, for a caller that goes on with them (k_noise_fold_history).
 template <typename P4>
-PT_HD float fold_pixel(size_t i, size_t npix, const float* S, P4* planes, const Fold& f) {
+PT_HD float fold_pixel(size_t i, size_t npix, const float* S, P4* planes, const Fold& f, P4* kept = nullptr) {
 #pragma clang fp contract(off)
   const float sx = S[3 * i], sy = S[3 * i + 1], sz = S[3 * i + 2];
   const P4 prev = planes[i];
@@ -60,6 +61,7 @@ PT_HD float fold_pixel(size_t i, size_t npix, const float* S, P4* planes, const 
   const float w = f.have_variance ? (vx + vy) + vz : 0.0f;
   planes[i] = P4{sx, sy, sz, w};
   planes[npix + i] = P4{q.x, q.y, q.z, 0.0f};
+  if (kept) kept[0] = P4{sx, sy, sz, w}, kept[1] = P4{q.x, q.y, q.z, 0.0f};
   return w;
 }
 

@@ -1048,6 +1048,96 @@ int pt_ctx_readback_history_probe(PtContext* c, float* kept, float* lam, int* co
   return 0;
 }
 
+// ---- the noise estimate of the blend, and rendering a view until the blend is clean (csrc/pt_noise.hip k_history_noise) ---------
+// What both entry points refuse after their own first checks, in the estimate's order: a striped or ragged tile, the adaptive state,
+// the extra plane.
+static int history_noise_admit(const Ctx& g, const char* who) {
+  return admit(g, who, kWholeRows) || admit(g, who, kUniform) || admit(g, who, kNoExtras) ? -1 : 0;
+}
+static const pthi::V4* history_noise_current(const Ctx& g, int plane) {  // C (0) or VC (1), nullptr while C is absent
+  if (!g.hist_current) return nullptr;
+  return plane ? history_var_plane(g, 1) : history_plane(g, pthi::kKeptPlanes);
+}
+
+int pt_ctx_history_noise(PtContext* c, float samples, uint32_t flags, double* sse) {
+  const char* who = "pt_history_noise";
+  if (need(c, who)) return -1;
+  Ctx& g = *c;
+  if (admit(g, who, kNotFailed)) return -1;
+  if (flags == PT_HISTORY_MOMENTS)
+    return pt_fail("%s: PT_HISTORY_MOMENTS is not built: the moments give an estimate only for pixels with four views of history (defined: PT_HISTORY_VARIANCE)", who);
+  if (flags != PT_HISTORY_VARIANCE) return pt_fail("%s: flags 0x%x: the only defined value is PT_HISTORY_VARIANCE = 0x%x", who, flags, PT_HISTORY_VARIANCE);
+  if (history_noise_admit(g, who)) return -1;
+  if (pt_history_check_samples(who, samples)) return -1;
+  if (history_folds(g, who, samples) || history_current_variance(g, who)) return -1;
+  HIP_OK(hipSetDevice(g.device));
+  if (ensure(g, g.d_hist_noise, pt_history_noise_bytes((size_t)g.N))) return -1;  // the first estimate of the context (every word is written before it is read)
+  const ptnz::Fold f = ptnz::fold_scalars(1, g.noise_groups, g.noise_iters);
+  g.hist_noise = false;
+  if (pt_history_noise_launch(g.stream, g.N, g.d_noise, f.Tf, f.Df, samples, history_noise_current(g, 0), history_noise_current(g, 1), g.d_hist_noise)) return -1;
+  g.hist_noise = true;
+  double result = -1.0;
+  HIP_OK(hipMemcpyAsync(&result, pt_history_noise_result(g.d_hist_noise, (size_t)g.N), sizeof(double), hipMemcpyDeviceToHost, g.stream));
+  if (pt_ctx_sync(c)) return -1;
+  if (sse) *sse = result;
+  return 0;
+}
+
+int pt_ctx_readback_history_noise(PtContext* c, float* w_host) {
+  if (need(c, "pt_readback_history_noise")) return -1;
+  return copy_out(c, "pt_readback_history_noise", w_host, 1, [&](const float** d) {
+    if (!c->d_hist_noise || !c->hist_noise)
+      return pt_fail("pt_readback_history_noise: no estimate has been made since the last pt_clear or move (pt_history_noise)");
+    return *d = pt_history_noise_plane(c->d_hist_noise, (size_t)c->N), 0;
+  });
+}
+
+int pt_ctx_history_render_until(PtContext* c, int iter_first, int max_iters, int group_iters, float target_db, int* iters_done, float* psnr_db,
+                                float* view_psnr_db) {
+  const char* who = "pt_history_render_until";
+  if (need(c, who)) return -1;
+  Ctx& g = *c;
+  if (iter_first < 1 || max_iters < 1 || (int64_t)iter_first + max_iters - 1 > INT32_MAX || group_iters < 0 || !std::isfinite(target_db))
+    return pt_fail("%s: iterations %d, +%d in groups of %d until %g dB: the first is >= 1, the count >= 1, the group >= 0 (0 = a batch), the target finite",
+                   who, iter_first, max_iters, group_iters, (double)target_db);
+  if (admit(g, who, kNotFailed) || history_noise_admit(g, who) || history_current_variance(g, who)) return -1;
+  const int group = group_iters ? group_iters : g.K;
+  int done = 0;
+  float psnr = -1.0f, view_psnr = -1.0f;
+  while (done < max_iters) {
+    const int n = std::min(group, max_iters - done);
+    if (pt_ctx_render(c, iter_first + done, n)) return -1;
+    done += n;
+    // the fold of pt_ctx_noise_fold and, once it leaves a variance, the estimate of the blend in the same launch
+    const int64_t unfolded = g.rendered - g.noise_iters;
+    if (unfolded <= 0) continue;
+    HIP_OK(hipSetDevice(g.device));
+    if (ensure(g, g.d_noise, pt_noise_state_bytes((size_t)g.N), Zero::on_stream)) return -1;
+    const ptnz::Fold f = ptnz::fold_scalars(unfolded, g.noise_groups + 1, g.noise_iters + unfolded);
+    if (!f.have_variance) {  // one group says nothing about the spread
+      if (pt_noise_launch(g.stream, g.N, g.d_image, g.d_noise, f)) return -1;
+      g.noise_groups += 1, g.noise_iters += unfolded;
+      continue;
+    }
+    if (ensure(g, g.d_hist_noise, pt_history_noise_bytes((size_t)g.N))) return -1;
+    g.hist_noise = false;
+    if (pt_noise_fold_history_launch(g.stream, g.N, g.d_image, g.d_noise, f, f.Tf, history_noise_current(g, 0), history_noise_current(g, 1), g.d_hist_noise)) return -1;
+    g.noise_groups += 1, g.noise_iters += unfolded;
+    g.hist_noise = true;
+    double sse[2] = {-1.0, -1.0};  // the view's own, the blend's: 16 bytes and ONE synchronise
+    HIP_OK(hipMemcpyAsync(&sse[0], static_cast<const char*>(g.d_noise) + pt_noise_state_bytes((size_t)g.N) - sizeof(double), sizeof(double), hipMemcpyDeviceToHost, g.stream));
+    HIP_OK(hipMemcpyAsync(&sse[1], pt_history_noise_result(g.d_hist_noise, (size_t)g.N), sizeof(double), hipMemcpyDeviceToHost, g.stream));
+    if (pt_ctx_sync(c)) return -1;
+    view_psnr = pt_psnr_from_sse(sse[0], g.N);
+    psnr = pt_psnr_from_sse(sse[1], g.N);
+    if (psnr > target_db) break;
+  }
+  if (iters_done) *iters_done = done;
+  if (psnr_db) *psnr_db = psnr;
+  if (view_psnr_db) *view_psnr_db = view_psnr;
+  return 0;
+}
+
 int pt_ctx_history_drop(PtContext* c) {
   if (need(c, "pt_history_drop")) return -1;
   Ctx& g = *c;

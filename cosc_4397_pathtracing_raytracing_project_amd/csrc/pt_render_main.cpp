@@ -79,6 +79,11 @@
 // pt_history_denoise_feedback, so a frame's order is render, features, lookup, check, round, filter, capture, move; the same output
 // names.  --feedback-level L (1 .. the filter's levels) and --feedback-variance V (the rule, 0 or 1): PtHistoryFeedbackOptions, whose
 // defaults (pt_amd.h) are level 1, rule 1.  Prints once `feedback: the output of filter level <L> is fed back, variance rule <V>`.
+// --history-until-db X (with --denoise-history; excludes --history-moments, --history-extra, --history-probe and --history-feedback): a
+// view renders until the estimated PSNR of the BLEND with the carried history is above X (pt_history_render_until), --spp being the cap
+// per view.  A frame's order becomes features, lookup, render, resolve, filter, capture, move, with the iterations the view took in
+// `samples`; the same output names.  --history-until-group G: the iterations per group (default ceil(spp / 4); 0 = one batch).  Prints
+// per frame `until: frame f: <iterations> iterations, <groups> groups, estimated PSNR of the blend <x> dB (the view alone <y> dB)`.
 // --history-extra G (with --reproject, alone or with --denoise-history --history-moments; refused with --denoise-history alone, whose
 // variance comes from the folds and knows nothing of extra samples): between the lookup and the resolve pt_history_round gives the
 // pixels whose carried weight is below --history-min M (default 4) G further iterations, --history-extra-cap F of the frame at the
@@ -141,6 +146,9 @@ int main(int argc, char** argv) {
   bool history_probe = false;                       // --history-probe
   PtHistoryProbeOptions probe_opt{};                // --probe-radius R, --probe-gain X (0: the defaults)
   bool probe_opt_given = false;
+  bool hist_until = false, hist_until_group_given = false;  // --history-until-db X, --history-until-group G
+  float hist_until_db = 0.0f;
+  int hist_until_group = 0;
   bool until = false, until_group_given = false;
   float clean_db = 35.0f, until_db = 0.0f, adaptive = 0.0f;  // adaptive > 0: --adaptive F
   float threshold = 0.0f, threshold_cap = 0.25f;           // --adaptive-threshold E, --adaptive-cap F
@@ -177,6 +185,23 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[i], "--denoise-history")) dn_history = true;  // the blend filtered with the variance the history carries
     else if (!std::strcmp(argv[i], "--history-moments")) hist_moments = true;  // ... with the variance its moments give: no folds
     else if (!std::strcmp(argv[i], "--history-feedback")) hist_feedback = true;  // ... and its output fed back into the history
+    else if (!std::strcmp(argv[i], "--history-until-db") && i + 1 < argc) {
+      char* end = nullptr;
+      hist_until_db = std::strtof(argv[++i], &end);
+      if (end == argv[i] || *end || !std::isfinite(hist_until_db)) {
+        std::fprintf(stderr, "--history-until-db wants the estimated PSNR of the blend in dB at which a view stops, a finite number\n");
+        return 1;
+      }
+      hist_until = true;
+    } else if (!std::strcmp(argv[i], "--history-until-group") && i + 1 < argc) {
+      char* end = nullptr;
+      const long v = std::strtol(argv[++i], &end, 10);
+      if (end == argv[i] || *end || v < 0 || v > INT32_MAX) {
+        std::fprintf(stderr, "--history-until-group wants the iterations per group of --history-until-db, G >= 0 (0 = one batch)\n");
+        return 1;
+      }
+      hist_until_group = (int)v, hist_until_group_given = true;
+    }
     else if ((!std::strcmp(argv[i], "--feedback-level") || !std::strcmp(argv[i], "--feedback-variance")) && i + 1 < argc) {
       const bool is_level = !std::strcmp(argv[i], "--feedback-level");
       char* end = nullptr;
@@ -375,6 +400,19 @@ int main(int argc, char** argv) {
   }
   if (dn_adaptive && !(adaptive > 0.0f) && !by_threshold) {
     std::fprintf(stderr, "--denoise-adaptive wants --adaptive or --adaptive-threshold (the filter of an adaptively sampled image)\n");
+    return 1;
+  }
+  if (hist_until_group_given && !hist_until) {
+    std::fprintf(stderr, "--history-until-group wants --history-until-db (the estimated PSNR of the blend at which a view stops)\n");
+    return 1;
+  }
+  if (hist_until && !dn_history) {
+    std::fprintf(stderr, "--history-until-db wants --orbit N --reproject --denoise-history (it stops a view on the variance the history carries)\n");
+    return 1;
+  }
+  if (hist_until && (hist_moments || history_extra || history_probe || hist_feedback)) {
+    std::fprintf(stderr, "--history-until-db excludes %s: the estimate of the blend's noise is built for the variance kind of history over uniform samples\n",
+                 hist_feedback ? "--history-feedback" : history_probe ? "--history-probe" : history_extra ? "--history-extra" : "--history-moments");
     return 1;
   }
   if (dn_history && (orbit <= 0 || !reproject)) {
@@ -669,7 +707,15 @@ int main(int argc, char** argv) {
       const auto t0 = std::chrono::high_resolution_clock::now();
       const int iter_first = reproject ? f * (iters + history_extra) + 1 : 1;
       bool render_failed = false;
-      if (dn_history && !hist_moments) {  // the view's iterations in groups of ceil(spp / 4), a fold after each: the variance of the view's own samples
+      int frame_iters = iters;  // --history-until-db: what the view took
+      int until_groups = 0;
+      float until_psnr = -1.0f, until_view_psnr = -1.0f;
+      if (hist_until) {  // the lookup needs the view's first hits only: features, lookup, then groups until the BLEND is clean
+        render_failed = pt_render_features(1, 1) || (f > 0 && pt_history_reproject_ex(&hopt, PT_HISTORY_VARIANCE | (move ? PT_HISTORY_MOTION : 0u))) ||
+                        pt_history_render_until(iter_first, iters, hist_until_group_given ? hist_until_group : fold_group, hist_until_db, &frame_iters, &until_psnr,
+                                                &until_view_psnr) ||
+                        pt_get_noise(nullptr, &until_groups, nullptr) || pt_readback(scene->state.image.data());
+      } else if (dn_history && !hist_moments) {  // the view's iterations in groups of ceil(spp / 4), a fold after each: the variance of the view's own samples
         for (int done = 0; done < iters && !render_failed; done += fold_group)
           render_failed = pt_render(iter_first + done, std::min(fold_group, iters - done)) || pt_noise_fold();
         render_failed = render_failed || pt_readback(scene->state.image.data());
@@ -689,9 +735,9 @@ int main(int argc, char** argv) {
       char tag[32];
       std::snprintf(tag, sizeof tag, ".orbit%03d", f);
       const std::string frame = base + tag;
-      if (pt_save_png((frame + ".png").c_str(), scene->state.image.data(), W, H, (float)iters) == 0) std::printf("Saved %s.png.\n", frame.c_str());
-      if (pfm && pt_save_pfm((frame + ".pfm").c_str(), scene->state.image.data(), W, H, (float)iters) == 0) std::printf("Saved %s.pfm.\n", frame.c_str());
-      if (hdr && pt_save_hdr((frame + ".hdr").c_str(), scene->state.image.data(), W, H, (float)iters) == 0) std::printf("Saved %s.hdr.\n", frame.c_str());
+      if (pt_save_png((frame + ".png").c_str(), scene->state.image.data(), W, H, (float)frame_iters) == 0) std::printf("Saved %s.png.\n", frame.c_str());
+      if (pfm && pt_save_pfm((frame + ".pfm").c_str(), scene->state.image.data(), W, H, (float)frame_iters) == 0) std::printf("Saved %s.pfm.\n", frame.c_str());
+      if (hdr && pt_save_hdr((frame + ".hdr").c_str(), scene->state.image.data(), W, H, (float)frame_iters) == 0) std::printf("Saved %s.hdr.\n", frame.c_str());
       if (reproject) {  // the view's first hits, the history looked up from them, the blend written, the blend kept for the next view
         const uint32_t hflags = !dn_history     ? 0u  // 0: the plain calls
                                 : hist_feedback ? PT_HISTORY_MOMENTS | PT_HISTORY_FEEDBACK
@@ -699,12 +745,13 @@ int main(int argc, char** argv) {
                                                 : PT_HISTORY_VARIANCE;
         int fresh = 0, selected = 0;  // --history-extra: the round, between the lookup and the resolve
         int probes = 0, changed = 0, skipped = 0;  // --history-probe: the check after the lookup, the keep before the round
-        if (pt_render_features(1, 1) || (f > 0 && pt_history_reproject_ex(&hopt, hflags | (move ? PT_HISTORY_MOTION : 0u))) ||
+        // (--history-until-db: the features and the lookup came before the render)
+        if ((!hist_until && (pt_render_features(1, 1) || (f > 0 && pt_history_reproject_ex(&hopt, hflags | (move ? PT_HISTORY_MOTION : 0u))))) ||
             (history_probe && ((f > 0 && pt_history_probe_check(&probe_opt, &probes, &changed, &skipped)) || pt_history_probe_keep(iter_first, iters, f % 9))) ||
-            (history_extra && pt_history_round(iter_first + iters, history_extra, &round_opt, &fresh, &selected)) || pt_history_resolve((float)iters, carried.data()) ||
-            (dn_history && (hist_feedback  ? pt_history_denoise_feedback((float)iters, &dn_opt, &fb_opt, filtered.data())
-                            : hist_moments ? pt_history_denoise_ex((float)iters, &dn_opt, PT_HISTORY_MOMENTS, filtered.data())
-                                           : pt_history_denoise((float)iters, &dn_opt, filtered.data()))) || pt_history_capture_ex((float)iters, hflags) ||
+            (history_extra && pt_history_round(iter_first + iters, history_extra, &round_opt, &fresh, &selected)) || pt_history_resolve((float)frame_iters, carried.data()) ||
+            (dn_history && (hist_feedback  ? pt_history_denoise_feedback((float)frame_iters, &dn_opt, &fb_opt, filtered.data())
+                            : hist_moments ? pt_history_denoise_ex((float)frame_iters, &dn_opt, PT_HISTORY_MOMENTS, filtered.data())
+                                           : pt_history_denoise((float)frame_iters, &dn_opt, filtered.data()))) || pt_history_capture_ex((float)frame_iters, hflags) ||
             pt_readback_history(nullptr, current.data())) {
           std::fprintf(stderr, "HIP error (pt_history): %s\n", pt_last_error());
           return EXIT_FAILURE;
@@ -714,6 +761,9 @@ int main(int argc, char** argv) {
         for (size_t p = 0; p < (size_t)W * H; ++p)
           if (current[4 * p + 3] > 0.0f) valid += 1, weight += (double)current[4 * p + 3];
         std::printf("history: frame %d: %zu of %zu pixels carried, mean weight %.3f\n", f, valid, (size_t)W * H, valid ? weight / (double)valid : 0.0);
+        if (hist_until)
+          std::printf("until: frame %d: %d iterations, %d groups, estimated PSNR of the blend %.9g dB (the view alone %.9g dB)\n", f, frame_iters, until_groups,
+                      (double)until_psnr, (double)until_view_psnr);
         if (history_probe) std::printf("probe: frame %d: %d of %d probes changed, %d skipped\n", f, changed, probes, skipped);
         if (history_extra) std::printf("history: frame %d: %d extra over %d of %d fresh pixels\n", f, history_extra, selected, fresh);
         if (pt_save_png((frame + ".reprojected.png").c_str(), carried.data(), W, H, 1.0f) == 0) std::printf("Saved %s.reprojected.png.\n", frame.c_str());

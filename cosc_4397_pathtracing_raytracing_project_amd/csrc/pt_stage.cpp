@@ -635,6 +635,30 @@ int pt_stage_history_merge(int pixels, float* rgb_sum, float* extra, const int32
   return 0;
 }
 
+// The estimate of the blend's noise on caller-supplied host arrays (pt_history_noise_host's arguments): k_history_noise and the reduction
+int pt_stage_history_noise(int pixels, const float* noise_planes, int groups, int64_t iters, float samples, const float* current_plane, const float* current_var,
+                           float* w_out, double* sse) {
+  const char* who = "pt_stage_history_noise";
+  if (need(default_context(), who)) return -1;
+  Ctx& g = *default_context();
+  if (pt_history_noise_check(who, pixels, noise_planes, groups, iters, samples, current_plane, current_var)) return -1;
+  HIP_OK(hipSetDevice(g.device));
+  Scratch sc;
+  const size_t n = (size_t)pixels;
+  float *d_noise = nullptr, *d_cur = nullptr, *d_var = nullptr;
+  char* d_out = sc.get<char>(pt_history_noise_bytes(n));
+  if (!d_out) return pt_fail("%s: out of device memory", who);
+  if (device_copy(sc, who, noise_planes, 4 * PT_NOISE_PLANES * n, &d_noise)) return -1;
+  if (current_plane && (device_copy(sc, who, current_plane, 4 * n, &d_cur) || device_copy(sc, who, current_var, 4 * n, &d_var))) return -1;
+  HIP_OK(hipMemsetAsync(d_out, 0xff, pt_history_noise_bytes(n), g.stream));  // a word nobody wrote shows as a NaN (on the kernels' stream: ordered before them)
+  const ptnz::Fold f = ptnz::fold_scalars(1, groups, iters);
+  if (pt_history_noise_launch(g.stream, pixels, d_noise, f.Tf, f.Df, samples, d_cur, d_var, d_out)) return -1;
+  HIP_OK(hipStreamSynchronize(g.stream));
+  if (w_out) HIP_OK(hipMemcpy(w_out, pt_history_noise_plane(d_out, n), n * sizeof(float), hipMemcpyDeviceToHost));
+  if (sse) HIP_OK(hipMemcpy(sse, pt_history_noise_result(d_out, n), sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
 // The partition's kernels on caller-supplied host arrays (pt_group_partition_host's arguments).  The list's length reaches the kernels
 // as it does in a group's round: in the second of two words on the device.
 int pt_stage_group_partition(int w, int h, int n, const int32_t* list, int m, int32_t* parts, int32_t* counts) {

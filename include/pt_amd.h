@@ -821,9 +821,10 @@ int pt_denoise_adaptive_variance_host(int w, int rows, const float* rgb_sum, con
  *     7  wsum >= 0.015625f:  h = acc / wsum;  t = tacc / wsum;  Th = t < cap ? t : cap;   else C = 0
  * The defaults are those of a CPU simulation on the cornell box (tests/test_history_sim.py; README "Reprojected history" has its
  * figures).  The bilinear lookup also smooths: the carried image is a BIASED estimator, and nothing here corrects that.
- * Out of scope: pt_group_* (a context's interleaved rows cannot look up their neighbours); feeding the history into the noise
- * estimate; a selection key that uses the carried variance; motion of anything but the camera.  (The filter over the blend: "variance of
- * the history" below; extra samples for short histories: "the history round" below.) */
+ * Out of scope: pt_group_* (a context's interleaved rows cannot look up their neighbours); a selection key that uses the carried
+ * variance; motion of anything but the camera.  (The filter over the blend: "variance of the history" below; extra samples for short
+ * histories: "the history round" below; the history in the noise estimate, and a view rendered until the blend is clean: "the noise
+ * estimate of the blend" below.) */
 #define PT_HISTORY_KEPT_PLANES 3
 typedef struct PtHistoryOptions { /* every field: 0 = the default */
   float cap;                   /* default 32: the most samples a carried colour counts for; finite and > 0                 */
@@ -965,7 +966,7 @@ int pt_history_denoise_host(int w, int rows, const float* rgb_sum, const float* 
  * C present with VC absent or of the variance kind; a null buffer.
  * What it buys: README "Moments with the history" (tests/test_history_moments_sim.py on the CPU, tests/test_gpu_history_moments.py on
  * an MI355X, the same digits).  One scene, one orbit: no claim beyond it.
- * Out of scope: pt_group_*; feeding the history into the noise estimate; a luminance-only variant; motion of anything but the
+ * Out of scope: pt_group_*; feeding the moments into the noise estimate ("the noise estimate of the blend" below says why); a luminance-only variant; motion of anything but the
  * camera.  (Extra samples for the marked pixels: "the history round" below; feeding the FILTERED image back into the history: "the
  * feedback" below, opt-in — without it K keeps the unfiltered blend.) */
 #define PT_HISTORY_MOMENTS 2u
@@ -1025,7 +1026,7 @@ int pt_history_denoise_moments_host(int w, int rows, const float* rgb_sum, const
  *        feature pass since the last clear or move; an option that is not finite or out of range.  It needs no capture and no
  *        lookup: with C absent every non-emitter hit pixel is fresh (the first view).  fresh / selected may be NULL.
  * What it buys: README "History-guided sampling" (tests/test_history_round_sim.py).
- * Out of scope: pt_group_*; feeding the history into the noise estimate; scaling the spatial variance estimate by a pixel's extras;
+ * Out of scope: pt_group_*; a noise estimate of the blend while E is present (pt_history_noise refuses); scaling the spatial variance estimate by a pixel's extras;
  * a key that uses rh or the carried variance; motion of anything but the camera. */
 #define PT_HISTORY_ROUND_MIN_HISTORY 4.0f /* the default of PtHistoryRoundOptions.min_history, in samples */
 typedef struct PtHistoryRoundOptions { /* every field: 0 = the default */
@@ -1232,6 +1233,62 @@ int pt_history_denoise_feedback_host(int w, int rows, const float* rgb_sum, cons
                                      const float* current_var, const float* current_fb, const PtDenoiseOptions* opt, const PtHistoryFeedbackOptions* fb,
                                      float* rgb_avg, float* tap, float* var_raw, uint8_t* mark);
 
+/* ---- the noise estimate of the blend, and rendering a view until the BLEND is clean.  pt_get_noise and pt_render_until judge the
+ * view's own samples; a view that starts with a carried history is cleaner than they say.  pt_history_noise sums the variance of the
+ * blend, which the capture and pt_history_denoise form per pixel already, into a frame statistic in pt_get_noise's unit, and
+ * pt_history_render_until is pt_render_until's loop stopping on it: what makes a carried history save time as well as samples.
+ * Opt-in: a renderer that never calls these functions allocates and launches nothing new, and every other call keeps its kernels,
+ * memory, launches, results and refusals.  Specified like the rest of the history: float32 throughout, every operation a separate
+ * IEEE operation in the order written, no FMA contraction, correctly rounded division, denormals kept; one implementation for the
+ * kernels and the host loop (csrc/pt_history.h noise_value); the same bits in all three PT_ARITH_* builds, host and device.
+ * pt_history_noise(samples, flags, &sse): the only defined value of flags is PT_HISTORY_VARIANCE.  Per tile pixel, with prev, q the
+ *   fold's planes, Tf = (float)T, Df = (float)(M - 1) * Tf, C = {h, Th} and VC = {vh, +0} (both absent: Th = vh = +0), per component k:
+ *            vn_k = sample_variance(prev_k, q_k, Tf, Df);  vb_k = blend_variance(vn_k, samples, vh_k, Th)      ("variance of the history")
+ *            w = (vb_x + vb_y) + vb_z;   W[p] = w, a plane of pixel_count floats
+ *   SSE_blend = sum over the tile of (double)w, in pt_noise_fold's way: a workgroup of 256 threads owns PT_NOISE_PIXELS_PER_PARTIAL
+ *   consecutive pixels and leaves one double from the same fixed tree, and the fold's second launch adds the partials in index order.
+ *   No atomics: equal inputs give equal bits.  The call synchronises once, for the one double; sse may be NULL.  Estimated PSNR of
+ *   the blend = pt_psnr_from_sse(SSE_blend, pixel_count).
+ *   With C and VC absent wn = 1 and wh = +0, so w is the fold's plane-0 .w and SSE_blend is pt_get_noise's double, bit for bit.
+ *   Memory: 4 * N + 8 * (ceil(N / PT_NOISE_PIXELS_PER_PARTIAL) + 1) bytes, allocated by the first estimate, part of
+ *   PtStats.device_bytes from then on, kept across pt_clear.  pt_readback_history_noise returns W (synchronises); an error before the
+ *   first estimate and after pt_clear, pt_set_camera[_ex] or pt_set_geoms, which make W absent.
+ *   Refusals, each naming the function, nothing allocated or launched, in this order: no renderer, or a failed context; a flags word
+ *   other than PT_HISTORY_VARIANCE (PT_HISTORY_MOMENTS: "not built", below); a striped or ragged tile; the adaptive state; the extra
+ *   plane E present (the message of the other uniform-sum readers: pt_history_resolve, pt_clear); samples not finite or <= 0; nothing
+ *   folded, fewer than 2 groups folded, iterations rendered since the last fold ("fold first"), samples != (float)T; C present with
+ *   VC absent or of the moments kind.
+ * pt_history_render_until(iter_first, max_iters, group_iters, target_db, &iters_done, &psnr_db, &view_psnr_db): pt_render_until's
+ *   loop, judging the blend.  Groups of group_iters iterations (0 = a batch; the last one cut at max_iters); after each a fold and,
+ *   once the fold leaves a variance (groups >= 2), the estimate above with samples = (float)T — both in ONE launch
+ *   (k_noise_fold_history: fold_pixel, then the estimate on the two words it just wrote; the planes, W and both doubles equal those of
+ *   pt_noise_fold followed by pt_history_noise bit for bit).  One synchronise per group that has an estimate, reading both doubles.
+ *   Stops after the first fold with groups >= 2 whose blend PSNR is > target_db, or at max_iters; returns 0 either way.
+ *   *psnr_db: the blend's last estimate, *view_psnr_db: the view's own (pt_get_noise's) at the same fold, -1 when there is none; all
+ *   three outputs may be NULL.  Groups folded before the call count, and iterations rendered but not yet folded join the first group,
+ *   as in pt_render_until.  With C absent the call is pt_render_until: the same iterations, PSNR bits, image and planes.
+ *   Refusals: no renderer; pt_render_until's argument check, word for word under this name; a failed context; a striped or ragged
+ *   tile; the adaptive state; E present; C present with VC absent or of the moments kind.
+ *   A view goes: pt_set_camera, pt_render_features(1, 1), pt_history_reproject_ex(PT_HISTORY_VARIANCE), pt_history_render_until,
+ *   pt_history_denoise, pt_history_capture_ex(samples = T, PT_HISTORY_VARIANCE) — the lookup needs the view's first hits only, and C
+ *   and VC stay until pt_clear, pt_set_camera[_ex] or pt_set_geoms, so rendering after the lookup is within the rules above.
+ * What it buys, and how far the estimate is from the truth: README "Noise estimate of the blend" (tests/test_history_noise_sim.py).
+ *   The estimate is a variance: the smoothing the lookup adds is not in it, and the carried variance reads high, so on that orbit
+ *   it is conservative.  Recorded, not bounded.  One scene, one orbit: no claim beyond it.
+ * Out of scope: the moments kind (PT_HISTORY_MOMENTS) — its estimate exists only for pixels with four views of history (none in the
+ *   first three views of an orbit at 1 spp; 2000 - 2316 of 5184 pixels from view 3 on), reads 2.2 - 3.1 x high there, and the pixels
+ *   without one hold 15 - 31 % of the blend's squared error; rendering longer inside a view raises rb towards 1 and takes estimates
+ *   away, so a stopping rule does not fit that kind.  Groups of contexts; a per-pixel threshold round over vb (the adaptive state and
+ *   the history refuse each other); correcting the blend's bias; lowering the floor of two folds per view. */
+int pt_history_noise(float samples, uint32_t flags, double* sse);
+int pt_readback_history_noise(float* w_host); /* pixel_count floats */
+int pt_history_render_until(int iter_first, int max_iters, int group_iters, float target_db, int* iters_done, float* psnr_db, float* view_psnr_db);
+/* The same arithmetic on the host (no GPU): the fold's planes with their counters (groups = M >= 2, iters = T, samples == (float)T)
+ * and C, VC (both NULL: absent) in; w_out (pixels floats, may be NULL) and *sse (may be NULL) out.  The device's W equals w_out bit for
+ * bit; the host adds in pixel order, so the double may differ from the device's in the last bits, as pt_noise_fold_host's does. */
+int pt_history_noise_host(int pixels, const float* noise_planes, int groups, int64_t iters, float samples, const float* current_plane,
+                          const float* current_var, float* w_out, double* sse);
+
 /* saveImage()'s per-pixel conversion (main.cpp:91-97 x mirror, image.cpp:26-30 clamp * 255 truncated) on the
  * device: pixel_count*3 bytes, row-major, x mirrored inside each row; the tile must consist of whole rows.
  * Reads back 3 B per pixel instead of 12. */
@@ -1308,6 +1365,10 @@ int pt_ctx_readback_history_extra(PtContext* c, float* extra_host);
 int pt_ctx_history_probe_keep(PtContext* c, int iter_first, int iter_count, int phase);
 int pt_ctx_history_probe_check(PtContext* c, const PtHistoryProbeOptions* opt, int* probes, int* changed, int* skipped);
 int pt_ctx_readback_history_probe(PtContext* c, float* kept, float* lam, int* count);
+int pt_ctx_history_noise(PtContext* c, float samples, uint32_t flags, double* sse);
+int pt_ctx_readback_history_noise(PtContext* c, float* w_host);
+int pt_ctx_history_render_until(PtContext* c, int iter_first, int max_iters, int group_iters, float target_db, int* iters_done, float* psnr_db,
+                                float* view_psnr_db);
 int pt_ctx_history_denoise_feedback(PtContext* c, float samples, const PtDenoiseOptions* opt, const PtHistoryFeedbackOptions* fb, float* rgb_avg_host);
 int pt_ctx_history_denoise_feedback_device(PtContext* c, float samples, const PtDenoiseOptions* opt, const PtHistoryFeedbackOptions* fb,
                                            const float** rgb_dev); /* as pt_ctx_denoise_device */
@@ -1515,6 +1576,10 @@ int pt_stage_history_denoise_moments(int w, int rows, const float* rgb_sum, cons
 int pt_stage_history_select(int w, int rows, const float* feature_planes, const float* current_plane, const uint8_t* emitter_geom, int num_geoms,
                             const PtHistoryRoundOptions* opt, int32_t* list, int* fresh, int* m);
 int pt_stage_history_merge(int pixels, float* rgb_sum, float* extra, const int32_t* list, int m, const float* group_sum, int group_iters);
+/* The estimate of the blend's noise through k_history_noise and the reduction, on caller-supplied host arrays (pt_history_noise_host's
+ * arguments and refusals; *sse is the device's double). */
+int pt_stage_history_noise(int pixels, const float* noise_planes, int groups, int64_t iters, float samples, const float* current_plane,
+                           const float* current_var, float* w_out, double* sse);
 /* The lookup with the filtered colour through k_history_reproject_feedback, and the feedback form of the filter — its prepare (counted
  * when `extra` is given), the moments form's kernels, the tap — on caller-supplied host arrays (the host forms' arguments but var_raw and
  * mark; rgb_avg or tap may be NULL, not both; rows < 32768). */

@@ -31,7 +31,15 @@ Then the feedback (PT_HISTORY_FEEDBACK; profiles/history_feedback_cost.log holds
 revision's), on every scene, last, so that the steps above run as they ran: the same orbit of 8 views with the flag in lookup, filter
 (pt_history_denoise_feedback, the library's defaults) and capture; at its last view, per repetition, the moments lookup and then the
 lookup with the flag, pt_history_denoise_ex and then pt_history_denoise_feedback (device forms); then the filter and the capture with the
-flag as a pair (a capture promotes the pending plane, so each needs a tap before it), and the moments capture alone."""
+flag as a pair (a capture promotes the pending plane, so each needs a tap before it), and the moments capture alone.
+
+Then the noise estimate of the blend (pt_history_noise, pt_history_render_until; profiles/history_noise_cost.log holds this library's run
+between two of the parent revision's), last of all on every scene: a view with a carried history, and per repetition one iteration of
+pt_render, pt_noise_fold, pt_get_noise (a synchronise and 8 bytes read back, no kernel) and pt_history_noise (whose time holds the same
+synchronise and readback beside its two kernels); then one group of
+the driver — an iteration and the fused launch — against those three.  Last an orbit of 8 views 2 pi / 120 apart, at most 16
+iterations per view in groups of 1, timed on the wall clock under pt_render_until and under pt_history_render_until (features, lookups
+and captures included) with the iterations each took; the target is the estimate view 0 alone shows after 8 iterations."""
 import argparse
 import ctypes as C
 import os
@@ -275,8 +283,91 @@ for name, text in (("cornell (7 primitives)", scenes.cornell_scene_text(res=(W, 
                 f"16 B more per tap that passed); the feedback filter against pt_history_denoise_ex: "
                 f"{statistics.median(t['filter']) - statistics.median(t['moments filter']):+.4f} ms (the tap, 48 B per pixel, and 16 B per pixel more in prepare)")
 
+        def noise_part():
+            """The noise estimate of the blend and its driver, after everything else on every scene: the steps, then an orbit's wall time."""
+            if not hasattr(L, "pt_ctx_history_noise"):
+                say("### this build of the library has no pt_history_noise")
+                return
+            import time
+            capi._check(L.pt_ctx_get_stats(ctx, C.byref(st)))
+            before = st.device_bytes
+            step = np.float32(2 * np.pi / 120)
+            done, psnr, view, sse = C.c_int32(0), C.c_float(-1.0), C.c_float(-1.0), C.c_double(-1.0)
+            count = [0]  # iterations the image holds
+
+            def start_view(move):
+                if move:
+                    cam = scene.orbit(step, 0.0, 0.0)
+                    capi._check(L.pt_ctx_set_camera(ctx, C.byref(cam)))
+                else:
+                    capi._check(L.pt_ctx_clear(ctx))
+                capi._check(L.pt_ctx_render_features(ctx, 1, 1))
+                count[0] = 0
+
+            def one(first=1000):
+                count[0] += 1
+                return L.pt_ctx_render(ctx, first + count[0], 1)
+
+            capi._check(L.pt_ctx_history_drop(ctx))
+            start_view(False)
+            for g in range(SPP):
+                capi._check(one() or L.pt_ctx_noise_fold(ctx))
+            capi._check(L.pt_ctx_history_capture_ex(ctx, C.c_float(SPP), VAR))
+            start_view(True)
+            capi._check(L.pt_ctx_history_reproject_ex(ctx, C.byref(hopt), VAR))
+            for g in range(2):
+                capi._check(one() or L.pt_ctx_noise_fold(ctx))
+            # (pt_get_noise launches nothing: a synchronise and 8 bytes read back, what pt_history_noise's time holds beside its kernels)
+            t = timed([("render", one), ("fold", lambda: L.pt_ctx_noise_fold(ctx)), ("sync", lambda: L.pt_ctx_get_noise(ctx, C.byref(sse), None, None)),
+                       ("noise", lambda: L.pt_ctx_history_noise(ctx, C.c_float(count[0]), VAR, C.byref(sse)))])
+
+            def fused():
+                count[0] += 1
+                return L.pt_ctx_history_render_until(ctx, 1000 + count[0], 1, 1, C.c_float(1000.0), None, None, None)
+
+            t.update(timed([("fused step", fused)]))
+            capi._check(L.pt_ctx_get_stats(ctx, C.byref(st)))
+            say(f"### the noise estimate of the blend, a view with history (C and VC present): {(st.device_bytes - before) / 2**20:.1f} MB more state (W and the partial sums)")
+            line("pt_render, 1 iteration", t["render"])
+            line("pt_noise_fold", t["fold"], 12 + 32 + 32)
+            line("pt_get_noise (a sync, 8 B)", t["sync"])
+            line("pt_history_noise (with its sync)", t["noise"], 32 + 32 + 4)
+            say(f"pt_history_noise less pt_get_noise's synchronise and readback: {statistics.median(t['noise']) - statistics.median(t['sync']):.4f} ms for k_history_noise and "
+                f"the reduction, beside the fold's {statistics.median(t['fold']):.4f} ms for k_noise_fold and the same reduction")
+            line("render + fused fold/estimate", t["fused step"])
+            sep = statistics.median(t["render"]) + statistics.median(t["fold"]) + statistics.median(t["noise"])
+            say(f"one group of the driver (an iteration, k_noise_fold_history, two reductions, 16 B read back) against the three separate steps: "
+                f"{statistics.median(t['fused step']):.4f} ms against {sep:.4f} ms ({statistics.median(t['fused step']) - sep:+.4f} ms)")
+            # ---- the orbit's wall time: 8 views, at most CAP iterations each in groups of 1; the target is what view 0 alone shows after 8 iterations
+            CAP, VIEWS = 16, 8
+            fresh = capi.Scene(path, res=(W, H))  # both rules see the same eight cameras: the scene's own and seven steps on
+            cams = [fresh.camera] + [fresh.orbit(step, 0.0, 0.0) for _ in range(VIEWS - 1)]
+            capi._check(L.pt_ctx_history_drop(ctx))
+            capi._check(L.pt_ctx_set_camera(ctx, C.byref(cams[0])))
+            capi._check(L.pt_ctx_render_until(ctx, 1, 8, 1, C.c_float(1000.0), C.byref(done), C.byref(psnr)))
+            target = C.c_float(psnr.value)
+            for rule in ("pt_render_until", "pt_history_render_until"):
+                capi._check(L.pt_ctx_history_drop(ctx))
+                capi._check(L.pt_ctx_sync(ctx))
+                iters, t0 = [], time.perf_counter()
+                for f in range(VIEWS):
+                    capi._check(L.pt_ctx_set_camera(ctx, C.byref(cams[f])))
+                    if rule == "pt_render_until":
+                        capi._check(L.pt_ctx_render_until(ctx, f * CAP + 1, CAP, 1, target, C.byref(done), C.byref(psnr)))
+                    else:
+                        capi._check(L.pt_ctx_render_features(ctx, 1, 1))
+                        if f:
+                            capi._check(L.pt_ctx_history_reproject_ex(ctx, C.byref(hopt), VAR))
+                        capi._check(L.pt_ctx_history_render_until(ctx, f * CAP + 1, CAP, 1, target, C.byref(done), C.byref(psnr), C.byref(view)))
+                        capi._check(L.pt_ctx_history_capture_ex(ctx, C.c_float(done.value), VAR))
+                    iters.append(done.value)
+                capi._check(L.pt_ctx_sync(ctx))
+                say(f"orbit of {VIEWS} views, target {target.value:.3f} dB, cap {CAP}, groups of 1, {rule:24s}: {1e3 * (time.perf_counter() - t0):9.2f} ms wall (moves, "
+                    f"features, lookups and captures included), iterations per view {iters} = {sum(iters)}")
+
         if not name.startswith("cornell"):
             feedback_part()
+            noise_part()
             continue
         capi._check(L.pt_ctx_history_drop(ctx))
         capi._check(L.pt_ctx_clear(ctx))
@@ -320,6 +411,7 @@ for name, text in (("cornell (7 primitives)", scenes.cornell_scene_text(res=(W, 
         say(f"the steady-view filter against pt_history_denoise above: {statistics.median(t['denoise']) - history_denoise_median:+.4f} ms "
             f"(one launch more, k_denoise_var_spatial, which leaves on a ballot in every wave without a marked pixel; no noise planes read)")
         feedback_part()
+        noise_part()
     finally:
         L.pt_ctx_destroy(ctx)
 out.close()
