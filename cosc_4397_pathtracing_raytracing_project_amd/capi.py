@@ -457,6 +457,23 @@ def lib() -> C.CDLL:
         L.pt_ctx_history_render_until.argtypes = [C.c_void_p] + _huntil
         L.pt_history_noise_host.argtypes = _hnz
         L.pt_stage_history_noise.argtypes = _hnz
+    if hasattr(L, "pt_group_history_round"):  # absent from older A/B builds of the library (tools/build_rev.sh)
+        _hio, _hro, _dno = C.POINTER(PtHistoryOptions), C.POINTER(PtHistoryRoundOptions), C.POINTER(PtDenoiseOptions)
+        L.pt_history_round_list.argtypes = [C.c_int, C.c_int, _ip, C.c_int, C.c_int]
+        L.pt_ctx_history_round_list.argtypes = [C.c_void_p, C.c_int, C.c_int, _ip, C.c_int, C.c_int]
+        L.pt_ctx_history_round_list_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]
+        L.pt_group_clear.argtypes = [C.c_void_p]
+        L.pt_group_history_capture_ex.argtypes = [C.c_void_p, C.c_float, C.c_uint32]
+        L.pt_group_history_reproject_ex.argtypes = [C.c_void_p, _hio, C.c_uint32]
+        L.pt_group_history_resolve.argtypes = [C.c_void_p, C.c_float, _fp]
+        L.pt_group_history_denoise_ex.argtypes = [C.c_void_p, C.c_float, _dno, C.c_uint32, _fp]
+        L.pt_group_history_round.argtypes = [C.c_void_p, C.c_int, C.c_int, _hro, _ip, _ip]
+        L.pt_group_history_drop.argtypes = [C.c_void_p]
+        L.pt_group_readback_history.argtypes = [C.c_void_p, _fp, _fp]
+        L.pt_group_readback_history_variance.argtypes = [C.c_void_p, _fp, _fp]
+        L.pt_group_readback_history_extra.argtypes = [C.c_void_p, _fp]
+        L.pt_group_device_bytes.argtypes = [C.c_void_p]
+        L.pt_group_device_bytes.restype = C.c_int64
     _lib = L
     return L
 
@@ -1628,6 +1645,13 @@ class Renderer:
         _check(lib().pt_history_round(int(iter_first), int(group_iters), C.byref(opt), C.byref(fresh), C.byref(selected)))
         return int(fresh.value), int(selected.value)
 
+    def history_round_list(self, iter_first: int, group_iters: int, pixel_list: np.ndarray, capacity: int) -> None:
+        """history_round without key and selection, over the caller's list (pt_history_round_list): distinct tile indices in ascending
+        order, at most `capacity`, on the worker kept for `capacity` pixels; any tile, striped ones included.  Asynchronous."""
+        lst = np.ascontiguousarray(pixel_list, np.int32).reshape(-1)
+        self._round_list = lst  # (the upload is queued on the renderer's stream)
+        _check(lib().pt_history_round_list(int(iter_first), int(group_iters), _i(lst), lst.size, int(capacity)))
+
     def history_probe_keep(self, iter_first: int, iter_count: int, phase: int = 0) -> None:
         """Keeps every third pixel of every third row of the image — iterations iter_first .. iter_first + iter_count - 1, all it holds —
         as probes for the next view (pt_history_probe_keep; asynchronous)."""
@@ -1982,6 +2006,78 @@ class Group:
         """Renderer.denoise_adaptive of the whole frame (pt_group_denoise_adaptive): float32 [W*H, 3], raw orientation."""
         w, h = self.scene.resolution
         return _filter(lib().pt_group_denoise_adaptive, np.empty((w * h, 3), np.float32), self._h, **opts)
+
+    # ---- the reprojected history of the whole frame (include/pt_amd.h: "history in groups") ----
+    def clear(self) -> None:
+        """Renderer.clear on every context (pt_group_clear); the history's current planes become absent."""
+        _check(lib().pt_group_clear(self._h))
+
+    def history_capture_ex(self, samples: float, flags: int = HISTORY_MOMENTS) -> None:
+        """Renderer.history_capture_ex of the whole frame (pt_group_history_capture_ex): flags 0 or HISTORY_MOMENTS."""
+        _check(lib().pt_group_history_capture_ex(self._h, C.c_float(samples), int(flags)))
+
+    def history_capture(self, samples: float) -> None:
+        self.history_capture_ex(samples, 0)
+
+    def history_reproject_ex(self, flags: int = HISTORY_MOMENTS, **opts) -> None:
+        """Renderer.history_reproject_ex of the whole frame (pt_group_history_reproject_ex): 0 or HISTORY_MOMENTS, each alone or with
+        HISTORY_MOTION."""
+        opt = history_options(**opts)
+        _check(lib().pt_group_history_reproject_ex(self._h, C.byref(opt), int(flags)))
+
+    def history_reproject(self, **opts) -> None:
+        self.history_reproject_ex(0, **opts)
+
+    def history_resolve(self, samples: float) -> np.ndarray:
+        """Renderer.history_resolve of the whole frame (pt_group_history_resolve): float32 [W*H, 3], raw orientation."""
+        w, h = self.scene.resolution
+        out = np.empty((w * h, 3), np.float32)
+        _check(lib().pt_group_history_resolve(self._h, C.c_float(samples), _f(out)))
+        return out
+
+    def history_denoise_ex(self, samples: float, flags: int = HISTORY_MOMENTS, **opts) -> np.ndarray:
+        """Renderer.history_denoise_ex of the whole frame (pt_group_history_denoise_ex; HISTORY_MOMENTS only): float32 [W*H, 3]."""
+        w, h = self.scene.resolution
+        opt = denoise_options(**opts)
+        out = np.empty((w * h, 3), np.float32)
+        _check(lib().pt_group_history_denoise_ex(self._h, C.c_float(samples), C.byref(opt), int(flags), _f(out)))
+        return out
+
+    def history_round(self, iter_first: int, group_iters: int, min_history: float = 0, max_fraction: float = 0):
+        """Renderer.history_round of the whole frame (pt_group_history_round): (fresh pixels, pixels rendered)."""
+        opt = history_round_options(min_history, max_fraction)
+        fresh, selected = C.c_int32(-1), C.c_int32(-1)
+        _check(lib().pt_group_history_round(self._h, int(iter_first), int(group_iters), C.byref(opt), C.byref(fresh), C.byref(selected)))
+        return int(fresh.value), int(selected.value)
+
+    def history_drop(self) -> None:
+        _check(lib().pt_group_history_drop(self._h))
+
+    def readback_history(self):
+        """(kept planes [PT_HISTORY_KEPT_PLANES, W*H, 4], current plane [W*H, 4]; zeros while it is absent) of the frame."""
+        w, h = self.scene.resolution
+        kept = np.empty((HISTORY_KEPT_PLANES, w * h, 4), np.float32)
+        cur = np.empty((w * h, 4), np.float32)
+        _check(lib().pt_group_readback_history(self._h, _f(kept), _f(cur)))
+        return kept, cur
+
+    def readback_history_variance(self):
+        """(VK, VC) of the frame, float32 [W*H, 4] each; zeros while absent."""
+        w, h = self.scene.resolution
+        vk, vc = np.empty((w * h, 4), np.float32), np.empty((w * h, 4), np.float32)
+        _check(lib().pt_group_readback_history_variance(self._h, _f(vk), _f(vc)))
+        return vk, vc
+
+    def readback_history_extra(self) -> np.ndarray:
+        """The extra plane E of the frame, float32 [W*H]; zeros while absent."""
+        w, h = self.scene.resolution
+        out = np.empty(w * h, np.float32)
+        _check(lib().pt_group_readback_history_extra(self._h, _f(out)))
+        return out
+
+    def device_bytes(self) -> int:
+        """Bytes of the group's own device buffers (pt_group_device_bytes); the contexts': stats(i).device_bytes."""
+        return int(lib().pt_group_device_bytes(self._h))
 
     def context(self, i: int) -> int:
         """The handle of context i for the pt_ctx_* functions (pt_group_context)."""

@@ -1285,7 +1285,7 @@ int set_geoms(PtContext* c, const PtGeom* geoms, int num_geoms) {  // after the 
     b.nodes = nullptr, b.top = nullptr, b.geoms = nullptr, b.ready = false;
   }
   g.camera_base = std::move(base);
-  g.hist_geoms_stale = true, g.hist_motion_fresh = false;  // (the next capture keeps these geoms; K and the kept geoms stay until then)
+  g.hist_motion.geoms_stale = true, g.hist_motion.fresh = false;  // (the next capture keeps these geoms; K and the kept geoms stay until then)
   g.probe_geoms_stale = g.probe_geoms_changed = true;  // (the next keep copies these geoms; the next check compares them with the kept ones)
   times.upload_ms = ms_since(t1);
   const auto t2 = clock::now();
@@ -1472,6 +1472,9 @@ int pt_readback_history_feedback(float* kept, float* current, float* pending) { 
 int pt_readback_history_variance(float* kept_var, float* current_var) { return pt_ctx_readback_history_variance(g_default, kept_var, current_var); }
 int pt_history_round(int iter_first, int group_iters, const PtHistoryRoundOptions* opt, int* fresh, int* selected) {
   return pt_ctx_history_round(g_default, iter_first, group_iters, opt, fresh, selected);
+}
+int pt_history_round_list(int iter_first, int group_iters, const int32_t* list_host, int m, int capacity) {
+  return pt_ctx_history_round_list(g_default, iter_first, group_iters, list_host, m, capacity);
 }
 int pt_readback_history_extra(float* extra_host) { return pt_ctx_readback_history_extra(g_default, extra_host); }
 int pt_history_probe_keep(int iter_first, int iter_count, int phase) { return pt_ctx_history_probe_keep(g_default, iter_first, iter_count, phase); }

@@ -72,6 +72,19 @@ struct PtShared {
   bool aa_jitter = false;
 };
 
+// The objects' motion as a history sees it (PT_HISTORY_MOTION): the geoms its K is aligned to, and the motion table of the last lookup
+// that found a geom moved.  A context holds one for its tile's K, a group (pt_group.cpp) one for the frame's; the device table belongs
+// to the context that built it (history_motion_table in pt_post.cpp).
+struct PtHistoryMotion {
+  std::vector<PtGeom> geoms;     // the kept geoms, taken by a capture
+  bool geoms_stale = true;       // pt_ctx_set_geoms has run since `geoms` was copied (or nothing was copied yet)
+  void* d_table = nullptr;       // pthi::kMotionRow floats per geom, then one kind byte per geom
+  std::vector<float> table;      // what d_table holds
+  std::vector<uint8_t> kind;
+  bool fresh = false;            // the table is that of `geoms` and the current geoms as they stand; moved: some kind != 0
+  bool moved = false;
+};
+
 // One renderer instance = one device, one stream, one tile of the framebuffer.  The reference keeps this state in
 // file-scope statics (pathtrace.cu:446-456); here it is an object so that one process can drive several GPUs
 // (pt_group_*, pt_group.cpp) — the old single-instance entry points act on a default context.
@@ -179,13 +192,7 @@ struct PtContext : PtShared {
   int fb_keep_albedo = 0;          // the keep_albedo the last tap was made with: the unit of P.w, and of FK.w / FC.w after it
   // The objects' motion (PT_HISTORY_MOTION): the geoms K is aligned to beside hist_cam, and the motion table of the last lookup that
   // found a geom moved (absent until then): pthi::kMotionRow floats per geom, then one kind byte per geom
-  std::vector<PtGeom> hist_geoms;
-  bool hist_geoms_stale = true;    // pt_ctx_set_geoms has run since hist_geoms was copied (or nothing was copied yet)
-  void* d_hist_motion = nullptr;
-  std::vector<float> hist_motion_table;   // what d_hist_motion holds
-  std::vector<uint8_t> hist_motion_kind;
-  bool hist_motion_fresh = false;  // the table is that of hist_geoms and camera_base.geoms as they stand; hist_motion_moved: some kind != 0
-  bool hist_motion_moved = false;
+  PtHistoryMotion hist_motion;
   // The noise estimate of the blend (pt_ctx_history_noise): absent until the first estimate
   void* d_hist_noise = nullptr;    // pt_history_noise_bytes(N): the partial sums, SSE_blend, then the plane W
   bool hist_noise = false;         // W holds an estimate of the image as it stood; pt_clear and a move make it absent
@@ -250,6 +257,23 @@ int pt_ctx_camera_refusal(const PtContext* c, const PtCamera* cam, const char* w
 int pt_ctx_geoms_refusal(const PtContext* c, const PtGeom* geoms, int num_geoms, const char* who);  // what pt_set_geoms refuses, in its order; nothing changes
 int pt_ctx_camera_refusal_ex(const PtContext* c, const PtCamera* cam, uint32_t flags, const char* who);  // ... with the undefined flag bit after the null camera
 int pt_ctx_enter_adaptive(PtContext* c);  // the count plane with the fold's (T, M) in every pixel, unless the context is in the adaptive state already
+// The history of a group (pt_group_history_*): the frame's K, C, VK and VC live with the group; a context is asked for what only it knows.
+int pt_ctx_admit_no_extras(const PtContext* c, const char* who);  // the refusal of a context that holds the extra plane E (what reads a uniform SUM)
+bool pt_ctx_features_fresh(const PtContext* c);                   // a feature pass has run since the last clear or move
+bool pt_ctx_history_extra_present(const PtContext* c);            // E is present
+const float* pt_ctx_device_history_extra(PtContext* c);           // E of the tile on the device, nullptr while absent
+int pt_history_check_flags(const char* who, uint32_t flags, bool motion);  // the flag word of pt_history_capture_ex / (motion) _reproject_ex
+int pt_history_check_denoise_flags(const char* who, uint32_t flags);       // the flag word of pt_history_denoise_ex
+// What pt_history_round refuses before its options, in its order and under the name `who`, apart from a tile that is not whole rows.
+int pt_ctx_history_round_refusal(const PtContext* c, const char* who, int iter_first, int group_iters);
+// The per-geom tables of a history on the context's device, built at first use and kept by the context: reject_geom (the lookup) or
+// emitter_geom (the round's key); *num_geoms the geoms of the scene.  Blocking the first time.
+int pt_ctx_history_geom_table(PtContext* c, bool emitter, const uint8_t** table_dev, int* num_geoms);
+// The motion table of `m`'s kept geoms against the context's current ones, on the context's device: *table_dev and *kind_dev, both
+// nullptr when no geom moved (nothing allocated or uploaded then).
+int pt_ctx_history_motion_table(PtContext* c, PtHistoryMotion* m, const float** table_dev, const uint8_t** kind_dev);
+const std::vector<PtGeom>& pt_ctx_geoms(const PtContext* c);  // the geoms as they stand
+const PtCamera& pt_ctx_camera(const PtContext* c);            // the camera as it stands
 
 namespace ptc {
 using Ctx = PtContext;

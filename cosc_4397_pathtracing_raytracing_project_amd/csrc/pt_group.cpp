@@ -38,6 +38,7 @@
 #include "pt_context.h"  // HIP_OK; a group reaches its contexts through the C ABI and the helpers declared there
 #include "pt_denoise.h"
 #include "pt_group_select.h"
+#include "pt_history.h"
 #define NCCL_OK(expr)                                                                                      \
   do {                                                                                                     \
     ncclResult_t r_ = (expr);                                                                              \
@@ -55,6 +56,7 @@ struct PtGroup {
   std::vector<size_t> recv_off;  // pixel offset of device i's tile in the root's receive buffer (i >= 1)
   size_t recv_pixels = 0;
   std::vector<std::pair<int, void*>> owned;  // (device, buffer): every device buffer below; ensure() allocates it at its first use, release() frees it
+  int64_t owned_bytes = 0;                   // what `owned` adds up to (pt_group_device_bytes)
   // root: THE receive buffer of every write-out, the tiles of devices 1..n-1 back to back, kRecvBytes (the widest payload) per pixel.
   // Payloads of different widths follow each other in it with nothing but stream order between them.  That is sound because all three
   // parties are queued on the ROOT context's stream: the COPY transport's copies into it, RCCL's ncclRecv into it, and the placement
@@ -78,6 +80,19 @@ struct PtGroup {
   int32_t* d_parts = nullptr;      // root: the contexts' lists back to back
   uint32_t* d_result = nullptr;    // root: above, m, m_0 .. m_(n-1)
   hipEvent_t parts_ready = nullptr;  // root: the parts are complete (recorded on the root's stream)
+  // The reprojected history of the frame (pt_group_history_*): the single context's state (pt_context.h) over W*H pixels, all of it on
+  // the root and absent until the first capture.  pt_group_clear, pt_group_set_camera[_ex] and pt_group_set_geoms make C and VC absent.
+  void* d_hist = nullptr;            // root: pt_history_state_bytes(W*H): the kept planes K0 K1 K2, then the current plane C
+  void* d_hist_var = nullptr;        // root: pt_history_variance_bytes(W*H): VK, then VC; from the first capture with PT_HISTORY_MOMENTS
+  float* d_blend = nullptr;          // root: the blend of pt_group_history_resolve, W*H*3 floats
+  float* d_full_extra = nullptr;     // root: the assembled extra plane E, W*H floats
+  hipEvent_t tiles_read = nullptr;   // root, COPY transport: the root's stream has read the tiles (release_tiles)
+  PtCamera hist_cam{};               // the camera K is aligned to
+  bool hist_kept = false;            // K holds a capture (pt_group_history_drop forgets it)
+  bool hist_current = false;         // C holds a lookup for the current camera
+  uint32_t hist_var_kept = 0;        // the kind VK holds: 0 (a plain capture) or PT_HISTORY_MOMENTS
+  uint32_t hist_var_current = 0;     // ... and VC; 0 whenever C is absent
+  PtHistoryMotion hist_motion;       // the kept geoms with their stale flag and the motion table (its device copy: context 0's)
 };
 
 namespace {
@@ -89,9 +104,9 @@ struct Payload {
   int elems;
 };
 constexpr size_t kRecvBytes = 16;  // per pixel of PtGroup::d_recv
-constexpr Payload kRgb{12, ncclFloat, 3}, kPlane{16, ncclFloat, 4}, kPair{8, ncclInt32, 2}, kRgb8{3, ncclUint8, 3}, kRgba8{4, ncclUint8, 4};
+constexpr Payload kRgb{12, ncclFloat, 3}, kPlane{16, ncclFloat, 4}, kPair{8, ncclInt32, 2}, kRgb8{3, ncclUint8, 3}, kRgba8{4, ncclUint8, 4}, kExtra{4, ncclFloat, 1};
 constexpr bool payload_ok(Payload p, size_t elem_bytes) { return p.bytes == p.elems * elem_bytes && p.bytes <= kRecvBytes; }
-static_assert(payload_ok(kRgb, 4) && payload_ok(kPlane, 4) && payload_ok(kPair, 4) && payload_ok(kRgb8, 1) && payload_ok(kRgba8, 1), "a payload wider than the receive buffer's pixel");
+static_assert(payload_ok(kRgb, 4) && payload_ok(kPlane, 4) && payload_ok(kPair, 4) && payload_ok(kRgb8, 1) && payload_ok(kRgba8, 1) && payload_ok(kExtra, 4), "a payload wider than the receive buffer's pixel");
 
 size_t frame_pixels(const PtGroup* g) { return (size_t)g->W * g->H; }
 hipStream_t stream(const PtGroup* g, int i) { return (hipStream_t)pt_ctx_stream(g->ctx[i]); }
@@ -102,6 +117,7 @@ int ensure(PtGroup* g, int i, T*& p, size_t bytes) {
   if (p) return 0;
   HIP_OK(hipMalloc((void**)&p, bytes));
   g->owned.emplace_back(g->devices[i], p);
+  g->owned_bytes += (int64_t)bytes;
   return 0;
 }
 
@@ -119,6 +135,7 @@ void release(PtGroup* g) {
     }
   if (!g->devices.empty()) (void)hipSetDevice(g->devices[0]);
   if (g->parts_ready) (void)hipEventDestroy(g->parts_ready);
+  if (g->tiles_read) (void)hipEventDestroy(g->tiles_read);
   for (const auto& [device, p] : g->owned) {
     (void)hipSetDevice(device);
     (void)hipFree(p);
@@ -301,7 +318,7 @@ int shared_state(PtGroup* g, const char* who, PtCtxState* out) {
 // The head, after the arguments: no context failed half-way (uniform: or is in the adaptive state), every context has its features.
 int filter_admit(PtGroup* g, const char* who, bool uniform) {
   for (PtContext* c : g->ctx)  // (a group's rounds bring its contexts into the adaptive state: one sample count no longer describes the image)
-    if (pt_ctx_admit_state(c, who, uniform)) return -1;
+    if (pt_ctx_admit_state(c, who, uniform) || pt_ctx_admit_no_extras(c, who)) return -1;  // (... nor do the extras of a history round)
   return need_features(g, who);
 }
 // The tail, after the last refusal: a context owns interleaved rows and cannot filter its own tile, so the SUM image, the feature
@@ -318,21 +335,11 @@ int filter_run(PtGroup* g, bool noise, bool counts, float* rgb_avg_host, Launch 
   return to_host(g, rgb_avg_host, d_out, frame * 12);
 }
 
-// One round of pt_group_adaptive_round_threshold for n > 1, after the arguments' refusals; the driver's min_pixels as in the context's round.
-int group_round(PtGroup* g, const char* who, int iter_first, int group_iters, float threshold, float max_fraction, int min_pixels, int* above, int* selected) {
-  const int n = g->n, W = g->W, H = g->H;
+// ---- what the group's two rounds (the threshold round, the history round) share around their keys
+// The buffers of the frame's selection on the root and of the parts' way back, at the first round of either kind.
+int selection_buffers(PtGroup* g) {
+  const int n = g->n;
   const size_t frame = frame_pixels(g);
-  for (int i = 0; i < n; ++i)
-    if (pt_ctx_adaptive_refusal(g->ctx[i], who, iter_first, group_iters, max_fraction, true)) return -1;
-  if (pt_adaptive_check_threshold(who, threshold)) return -1;
-  if (n > ptgs::kMaxParts || H >= 32768 || frame > ((size_t)1 << 30))
-    return pt_fail("%s: %d contexts on a frame of %d x %d: at most %d contexts, fewer than 32768 rows, at most 2^30 pixels", who, n, W, H, ptgs::kMaxParts);
-  PtCtxState shared{};
-  if (shared_state(g, who, &shared)) return -1;
-  const int cap = ptad::list_length((double)max_fraction, (int64_t)frame);
-  hipStream_t root = stream(g, 0);
-
-  // the group's buffers: the first round
   HIP_OK(hipSetDevice(g->devices[0]));
   if (ensure(g, 0, g->d_select, pt_adaptive_select_bytes(frame)) || ensure(g, 0, g->d_partition, pt_group_partition_bytes(frame, n)) ||
       ensure(g, 0, g->d_list, frame * sizeof(int32_t)) || ensure(g, 0, g->d_parts, frame * sizeof(int32_t)) ||
@@ -340,10 +347,54 @@ int group_round(PtGroup* g, const char* who, int iter_first, int group_iters, fl
     return -1;
   if (!g->parts_ready) HIP_OK(hipEventCreateWithFlags(&g->parts_ready, hipEventDisableTiming));
   if (g->d_pack.empty()) g->d_pack.assign(n, nullptr), g->d_part.assign(n, nullptr);
-  for (int i = 0; i < n; ++i) {
-    const size_t pixels = (size_t)pt_ctx_pixel_count(g->ctx[i]);
+  for (int i = 1; i < n; ++i) {
     HIP_OK(hipSetDevice(g->devices[i]));
-    if (ensure(g, i, g->d_pack[i], pixels * 8) || (i >= 1 && ensure(g, i, g->d_part[i], pixels * sizeof(int32_t)))) return -1;
+    if (ensure(g, i, g->d_part[i], (size_t)pt_ctx_pixel_count(g->ctx[i]) * sizeof(int32_t))) return -1;
+  }
+  HIP_OK(hipSetDevice(g->devices[0]));
+  return 0;
+}
+// d_result after the partition: {count, m, m_0 .. m_(n-1)}, 8 + 4n bytes behind ONE synchronise of the root's stream, and checked: the
+// list fits the cap and the count (`count_name` in the message), the parts add up to it, every part fits its context.
+int read_selection(PtGroup* g, const char* who, int cap, const char* count_name, std::vector<uint32_t>* out) {
+  const int n = g->n;
+  hipStream_t root = stream(g, 0);
+  std::vector<uint32_t>& result = *out;
+  result.assign(2 + (size_t)n, 0u);
+  HIP_OK(hipMemcpyAsync(result.data(), g->d_result, result.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, root));
+  HIP_OK(hipStreamSynchronize(root));
+  const int m = (int)result[1];
+  int64_t sum = 0;
+  for (int i = 0; i < n; ++i) sum += result[2 + (size_t)i];
+  bool fits = m >= 0 && m <= cap && (int)result[0] >= m && sum == m;
+  for (int i = 0; i < n && fits; ++i) fits = (int64_t)result[2 + (size_t)i] <= pt_ctx_pixel_count(g->ctx[i]);
+  if (!fits) return pt_fail("%s: the selection left %u %s, a list of %u (cap %d) in parts that add up to %lld", who, result[0], count_name, result[1], cap, (long long)sum);
+  return 0;
+}
+int round_limits(PtGroup* g, const char* who) {
+  if (g->n > ptgs::kMaxParts || g->H >= 32768 || frame_pixels(g) > ((size_t)1 << 30))
+    return pt_fail("%s: %d contexts on a frame of %d x %d: at most %d contexts, fewer than 32768 rows, at most 2^30 pixels", who, g->n, g->W, g->H, ptgs::kMaxParts);
+  return 0;
+}
+
+// One round of pt_group_adaptive_round_threshold for n > 1, after the arguments' refusals; the driver's min_pixels as in the context's round.
+int group_round(PtGroup* g, const char* who, int iter_first, int group_iters, float threshold, float max_fraction, int min_pixels, int* above, int* selected) {
+  const int n = g->n, W = g->W, H = g->H;
+  const size_t frame = frame_pixels(g);
+  for (int i = 0; i < n; ++i)
+    if (pt_ctx_adaptive_refusal(g->ctx[i], who, iter_first, group_iters, max_fraction, true)) return -1;
+  if (pt_adaptive_check_threshold(who, threshold)) return -1;
+  if (round_limits(g, who)) return -1;
+  PtCtxState shared{};
+  if (shared_state(g, who, &shared)) return -1;
+  const int cap = ptad::list_length((double)max_fraction, (int64_t)frame);
+  hipStream_t root = stream(g, 0);
+
+  // the group's buffers: the first round
+  if (selection_buffers(g)) return -1;
+  for (int i = 0; i < n; ++i) {
+    HIP_OK(hipSetDevice(g->devices[i]));
+    if (ensure(g, i, g->d_pack[i], (size_t)pt_ctx_pixel_count(g->ctx[i]) * 8)) return -1;
   }
 
   // collect on the root: every context packs on its own stream, one exchange, the rows into the frame, key, select, partition
@@ -360,15 +411,9 @@ int group_round(PtGroup* g, const char* who, int iter_first, int group_iters, fl
     return fail_after_drain(g);
 
   // read back: above, m and the parts' lengths, 8 + 4n bytes and ONE synchronise
-  std::vector<uint32_t> result(2 + (size_t)n, 0u);
-  HIP_OK(hipMemcpyAsync(result.data(), g->d_result, result.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, root));
-  HIP_OK(hipStreamSynchronize(root));
+  std::vector<uint32_t> result;
+  if (read_selection(g, who, cap, "above", &result)) return -1;
   const int m = (int)result[1];
-  int64_t sum = 0;
-  for (int i = 0; i < n; ++i) sum += result[2 + (size_t)i];
-  bool fits = m >= 0 && m <= cap && (int)result[0] >= m && sum == m;
-  for (int i = 0; i < n && fits; ++i) fits = (int64_t)result[2 + (size_t)i] <= pt_ctx_pixel_count(g->ctx[i]);
-  if (!fits) return pt_fail("%s: the selection left %u above, a list of %u (cap %d) in parts that add up to %lld", who, result[0], result[1], cap, (long long)sum);
   const bool render = m > 0 && (int)result[0] > min_pixels;
   if (above) *above = (int)result[0];
   if (selected) *selected = render ? m : 0;
@@ -391,6 +436,71 @@ int group_or_batch(PtGroup* g, int group_iters, int* group) {
   *group = group_iters ? group_iters : st.iters_per_batch;
   return 0;
 }
+
+// ---- the reprojected history of the frame (n > 1).  A context owns interleaved rows and cannot look up its neighbours, so every call
+// follows the filters' shape: its refusals, the gathers of what it reads onto the root, the single context's launch on the root's
+// stream over W*H pixels (the view: pthi::make_view(kept camera, H, 0)), to_host() where something is returned.  Nothing assembled is
+// kept from one call to the next.
+pthi::V4* history_plane(const PtGroup* g, int plane) { return static_cast<pthi::V4*>(g->d_hist) + (size_t)plane * frame_pixels(g); }  // K0 K1 K2, C
+pthi::V4* history_var_plane(const PtGroup* g, int plane) { return static_cast<pthi::V4*>(g->d_hist_var) + (size_t)plane * frame_pixels(g); }  // 0: VK, 1: VC
+const pthi::V4* current_plane(const PtGroup* g) { return g->hist_current ? history_plane(g, pthi::kKeptPlanes) : nullptr; }
+
+// What pt_history_* refuses of any context, in the single context's order and apart from the tile's rows: a failed context, the flag
+// word (check_flags()), the adaptive state, (features) no feature pass since the last clear or move.  Each condition over the contexts in turn.
+template <typename Flags>
+int history_admit(PtGroup* g, const char* who, bool features, Flags check_flags) {
+  for (PtContext* c : g->ctx)
+    if (pt_ctx_admit_state(c, who, false)) return -1;
+  if (check_flags()) return -1;
+  for (PtContext* c : g->ctx)
+    if (pt_ctx_admit_state(c, who, true)) return -1;
+  for (PtContext* c : g->ctx)
+    if (features && !pt_ctx_features_fresh(c))
+      return pt_fail("%s: no feature pass has been rendered since the last pt_group_clear or move (pt_group_render_features)", who);
+  return 0;
+}
+int no_flags() { return 0; }
+// The kinds and forms a group does not have, by name.
+int history_not_built(const char* who, uint32_t flags) {
+  if (flags & PT_HISTORY_VARIANCE) return pt_fail("%s: PT_HISTORY_VARIANCE is not built for a group (the moments kind is: PT_HISTORY_MOMENTS)", who);
+  if (flags & PT_HISTORY_FEEDBACK) return pt_fail("%s: PT_HISTORY_FEEDBACK is not built for a group", who);
+  return 0;
+}
+int history_current_moments(const PtGroup* g, const char* who) {
+  if (g->hist_current && g->hist_var_current != PT_HISTORY_MOMENTS)
+    return pt_fail("%s: the current plane has no moments: the lookup was made without PT_HISTORY_MOMENTS (pt_group_history_reproject_ex)", who);
+  return 0;
+}
+// The contexts of a group agree on whether the extra plane E is present (the group's round makes it present in all of them, a clear or
+// a move absent; pt_group_context lets a caller break it): the first context that differs from context 0 is the refusal.
+int shared_extras(PtGroup* g, const char* who, bool* present) {
+  *present = pt_ctx_history_extra_present(g->ctx[0]);
+  for (int i = 1; i < g->n; ++i)
+    if (pt_ctx_history_extra_present(g->ctx[i]) != *present)
+      return pt_fail("%s: context %d %s the extra plane of the history round, context 0 %s it; the contexts of a group share it", who, i,
+                     *present ? "does not hold" : "holds", *present ? "holds" : "does not hold");
+  return 0;
+}
+int gather_extra(PtGroup* g) {  // -> g->d_full_extra: W*H floats, the contexts' E planes (all present)
+  return gather(g, kExtra, [&](int i) { return pt_ctx_device_history_extra(g->ctx[i]); }, g->d_full_extra);
+}
+// The end of a call that returns nothing to the host (the capture, the lookup).  COPY transport: the root's stream pulled the tiles out
+// of the contexts' buffers, so context i's stream waits until it has before anything that follows (a render, a clear) may overwrite
+// them.  RCCL: the sends are on the contexts' own streams already.  (A call that ends in to_host() synchronises everything.)
+int release_tiles(PtGroup* g) {
+  if (g->transport != PT_GROUP_TRANSPORT_COPY) return 0;
+  HIP_OK(hipSetDevice(g->devices[0]));
+  if (!g->tiles_read) HIP_OK(hipEventCreateWithFlags(&g->tiles_read, hipEventDisableTiming));
+  HIP_OK(hipEventRecord(g->tiles_read, stream(g, 0)));
+  for (int i = 1; i < g->n; ++i) {
+    HIP_OK(hipSetDevice(g->devices[i]));
+    HIP_OK(hipStreamWaitEvent(stream(g, i), g->tiles_read, 0));
+  }
+  HIP_OK(hipSetDevice(g->devices[0]));
+  return 0;
+}
+// C and VC become absent: pt_group_clear and the moves (K, VK, the kept camera and the kept geoms stay).
+void history_current_absent(PtGroup* g) { g->hist_current = false, g->hist_var_current = 0; }
 
 }  // namespace
 
@@ -488,6 +598,7 @@ int pt_group_set_camera(PtGroup* g, const PtCamera* cam) {
   if (!g) return pt_fail("pt_group_set_camera: null group");
   for (PtContext* c : g->ctx)
     if (pt_ctx_camera_refusal(c, cam, "pt_group_set_camera")) return -1;
+  history_current_absent(g);  // (the history: as pt_set_camera leaves a context's)
   for (PtContext* c : g->ctx)
     if (pt_ctx_set_camera(c, cam)) return -1;
   return 0;
@@ -497,14 +608,27 @@ int pt_group_set_geoms(PtGroup* g, const PtGeom* geoms, int num_geoms) {
   if (!g) return pt_fail("pt_group_set_geoms: null group");
   for (PtContext* c : g->ctx)
     if (pt_ctx_geoms_refusal(c, geoms, num_geoms, "pt_group_set_geoms")) return -1;
+  history_current_absent(g);
+  g->hist_motion.geoms_stale = true, g->hist_motion.fresh = false;  // (the next capture keeps these geoms; K and the kept geoms stay until then)
   for (PtContext* c : g->ctx)
     if (pt_ctx_set_geoms(c, geoms, num_geoms)) return -1;
   return 0;
 }
+
+// pt_ctx_clear on every context; the group's buffers stay, and of its history K, VK, the kept camera and the kept geoms.
+int pt_group_clear(PtGroup* g) {
+  if (!g) return pt_fail("pt_group_clear: null group");
+  history_current_absent(g);
+  for (PtContext* c : g->ctx)
+    if (pt_ctx_clear(c)) return -1;
+  return 0;
+}
+int64_t pt_group_device_bytes(const PtGroup* g) { return g ? g->owned_bytes : 0; }
 int pt_group_set_camera_ex(PtGroup* g, const PtCamera* cam, uint32_t flags) {
   if (!g) return pt_fail("pt_group_set_camera_ex: null group");
   for (PtContext* c : g->ctx)
     if (pt_ctx_camera_refusal_ex(c, cam, flags, "pt_group_set_camera_ex")) return -1;
+  history_current_absent(g);
   for (PtContext* c : g->ctx)
     if (pt_ctx_set_camera_ex(c, cam, flags)) return -1;
   return 0;
@@ -601,6 +725,8 @@ int pt_group_render_until(PtGroup* g, int iter_first, int max_iters, int group_i
   if (iter_first < 1 || max_iters < 1 || (int64_t)iter_first + max_iters - 1 > INT32_MAX || group_iters < 0 || !std::isfinite(target_db))
     return pt_fail("pt_group_render_until: iterations %d, +%d in groups of %d until %g dB: the first is >= 1, the count >= 1, the group >= 0 (0 = a batch), the target finite",
                    iter_first, max_iters, group_iters, (double)target_db);
+  for (PtContext* c : g->ctx)  // (before the first group is rendered: the fold would refuse the extras of a history round after it)
+    if (pt_ctx_admit_no_extras(c, "pt_group_render_until")) return -1;
   int group = 0;
   if (group_or_batch(g, group_iters, &group)) return -1;
   int done = 0;
@@ -789,6 +915,8 @@ int pt_group_iterations_to_clean(PtGroup* g, float threshold_db, int* iteration)
 int pt_group_preview_rgba8(PtGroup* g, int iterations, uint8_t* rgba_host) {
   if (!g || !rgba_host || iterations <= 0) return pt_fail("pt_group_preview_rgba8: bad argument");
   const size_t frame = frame_pixels(g);
+  for (PtContext* c : g->ctx)  // (before the tiles' buffers are allocated)
+    if (pt_ctx_admit_no_extras(c, "pt_group_preview_rgba8")) return -1;
   if (g->d_prev.empty()) g->d_prev.assign(g->n, nullptr);
   for (int i = 0; i < g->n; ++i) {
     HIP_OK(hipSetDevice(g->devices[i]));
@@ -799,6 +927,237 @@ int pt_group_preview_rgba8(PtGroup* g, int iterations, uint8_t* rgba_host) {
   if (g->n == 1) return to_host(g, rgba_host, g->d_prev[0], frame * 4);
   if (gather(g, kRgba8, [&](int i) { return g->d_prev[i]; }, g->d_full_prev)) return -1;
   return to_host(g, rgba_host, g->d_full_prev, frame * 4);
+}
+
+// ---- the reprojected history across the group (include/pt_amd.h "history in groups"): after the same calls a group holds what ONE
+// renderer of the whole frame holds, bit for bit.  n == 1 forwards to context 0, whose own state it then is.
+int pt_group_history_capture_ex(PtGroup* g, float samples, uint32_t flags) {
+  const char* who = "pt_group_history_capture_ex";
+  if (!g) return pt_fail("%s: null group", who);
+  if (g->n == 1) return pt_ctx_history_capture_ex(g->ctx[0], samples, flags);
+  if (history_admit(g, who, true, [&] { return pt_history_check_flags(who, flags, false); })) return -1;
+  if (pt_history_check_samples(who, samples) || history_not_built(who, flags)) return -1;
+  const bool mom = (flags & PT_HISTORY_MOMENTS) != 0;
+  bool extras = false;
+  if ((mom && history_current_moments(g, who)) || shared_extras(g, who, &extras)) return -1;
+  const size_t frame = frame_pixels(g);
+  hipStream_t root = stream(g, 0);
+  HIP_OK(hipSetDevice(g->devices[0]));
+  if (!g->d_hist) {  // the first capture of the group: zeroed like a context's
+    if (ensure(g, 0, g->d_hist, pt_history_state_bytes(frame))) return -1;
+    HIP_OK(hipMemsetAsync(g->d_hist, 0, pt_history_state_bytes(frame), root));
+  }
+  if (mom && !g->d_hist_var) {  // ... with moments
+    if (ensure(g, 0, g->d_hist_var, pt_history_variance_bytes(frame))) return -1;
+    HIP_OK(hipMemsetAsync(g->d_hist_var, 0, pt_history_variance_bytes(frame), root));
+  }
+  if (gather_image(g) || gather_features(g) || (extras && gather_extra(g))) return -1;
+  const pthi::V4* current = current_plane(g);
+  const void* current_var = current && mom ? history_var_plane(g, 1) : nullptr;
+  const int N = (int)frame;
+  const int rc = mom ? (extras ? pt_history_capture_moments_counted_launch(root, N, g->d_full, g->d_full_feat, current, samples, g->d_full_extra, g->d_hist, current_var,
+                                                                            history_var_plane(g, 0))
+                               : pt_history_capture_moments_launch(root, N, g->d_full, g->d_full_feat, current, samples, g->d_hist, current_var, history_var_plane(g, 0)))
+                     : (extras ? pt_history_capture_counted_launch(root, N, g->d_full, g->d_full_feat, current, samples, g->d_full_extra, g->d_hist)
+                               : pt_history_capture_launch(root, N, g->d_full, g->d_full_feat, current, samples, g->d_hist));
+  if (rc) return fail_after_drain(g);
+  if (release_tiles(g)) return -1;
+  g->hist_cam = pt_ctx_camera(g->ctx[0]);
+  if (PtHistoryMotion& hm = g->hist_motion; hm.geoms_stale) hm.geoms = pt_ctx_geoms(g->ctx[0]), hm.geoms_stale = false, hm.fresh = false;  // retaken only after a pt_group_set_geoms
+  g->hist_kept = true;
+  g->hist_var_kept = flags;  // a plain capture: kept without moments
+  return 0;
+}
+
+int pt_group_history_reproject_ex(PtGroup* g, const PtHistoryOptions* opt, uint32_t flags) {
+  const char* who = "pt_group_history_reproject_ex";
+  if (!g) return pt_fail("%s: null group", who);
+  if (g->n == 1) return pt_ctx_history_reproject_ex(g->ctx[0], opt, flags);
+  if (history_admit(g, who, true, [&] { return pt_history_check_flags(who, flags, true); })) return -1;
+  pthi::Params P{};
+  if (pt_history_resolve_options(who, opt, &P) || history_not_built(who, flags)) return -1;
+  const bool motion = (flags & PT_HISTORY_MOTION) != 0;
+  const uint32_t kind = flags & ~PT_HISTORY_MOTION;  // 0 or PT_HISTORY_MOMENTS
+  if (!g->d_hist || !g->hist_kept) return pt_fail("%s: nothing has been captured (pt_group_history_capture_ex)", who);
+  if (kind == PT_HISTORY_MOMENTS && (!g->d_hist_var || g->hist_var_kept != PT_HISTORY_MOMENTS))
+    return pt_fail("%s: nothing has been captured with moments (pt_group_history_capture_ex with PT_HISTORY_MOMENTS)", who);
+  // the per-geom tables are the same for every context: context 0 builds and keeps them on the root device
+  const uint8_t* reject = nullptr;
+  const float* table = nullptr;
+  const uint8_t* table_kind = nullptr;
+  int num_geoms = 0;
+  if (pt_ctx_history_geom_table(g->ctx[0], false, &reject, &num_geoms)) return -1;
+  if (motion && pt_ctx_history_motion_table(g->ctx[0], &g->hist_motion, &table, &table_kind)) return -1;
+  hipStream_t root = stream(g, 0);
+  HIP_OK(hipSetDevice(g->devices[0]));
+  if (gather_features(g)) return -1;
+  const pthi::View v = pthi::make_view(g->hist_cam, g->H, 0);
+  void* C = history_plane(g, pthi::kKeptPlanes);
+  void* VK = kind ? history_var_plane(g, 0) : nullptr;
+  void* VC = kind ? history_var_plane(g, 1) : nullptr;
+  const int rc = table  ? pt_history_reproject_motion_launch(root, kind, v, g->d_hist, g->d_full_feat, reject, num_geoms, P, C, VK, VC, table, table_kind)
+                 : kind ? pt_history_reproject_moments_launch(root, v, g->d_hist, g->d_full_feat, reject, num_geoms, P, C, VK, VC)
+                        : pt_history_reproject_launch(root, v, g->d_hist, g->d_full_feat, reject, num_geoms, P, C);
+  if (rc) return fail_after_drain(g);
+  if (release_tiles(g)) return -1;
+  g->hist_current = true;
+  g->hist_var_current = kind;
+  return 0;
+}
+
+int pt_group_history_resolve(PtGroup* g, float samples, float* rgb_avg_host) {
+  const char* who = "pt_group_history_resolve";
+  if (!g) return pt_fail("%s: null group", who);
+  if (g->n == 1) return pt_ctx_history_resolve(g->ctx[0], samples, rgb_avg_host);
+  bool extras = false;
+  if (history_admit(g, who, false, no_flags) || pt_history_check_samples(who, samples) || shared_extras(g, who, &extras)) return -1;
+  if (!rgb_avg_host) return pt_fail("%s: null buffer", who);
+  const size_t frame = frame_pixels(g);
+  hipStream_t root = stream(g, 0);
+  HIP_OK(hipSetDevice(g->devices[0]));
+  if (ensure(g, 0, g->d_blend, frame * 12)) return -1;
+  if (gather_image(g) || (extras && gather_extra(g))) return -1;
+  if (extras ? pt_history_blend_counted_launch(root, (int)frame, g->d_full, samples, g->d_full_extra, current_plane(g), g->d_blend)
+             : pt_history_blend_launch(root, (int)frame, g->d_full, samples, current_plane(g), g->d_blend))
+    return fail_after_drain(g);
+  return to_host(g, rgb_avg_host, g->d_blend, frame * 12);
+}
+
+int pt_group_history_denoise_ex(PtGroup* g, float samples, const PtDenoiseOptions* opt, uint32_t flags, float* rgb_avg_host) {
+  const char* who = "pt_group_history_denoise_ex";
+  if (!g) return pt_fail("%s: null group", who);
+  if (g->n == 1) return pt_ctx_history_denoise_ex(g->ctx[0], samples, opt, flags, rgb_avg_host);
+  if (history_admit(g, who, true, [&] { return pt_history_check_denoise_flags(who, flags); })) return -1;
+  ptdn::Job j{};
+  if (pt_history_check_samples(who, samples) || pt_denoise_resolve(who, ptdn::Form::Moments, samples, 0, 0, opt, &j)) return -1;
+  if (flags != PT_HISTORY_MOMENTS)
+    return pt_fail("%s: the filter with the fold's variance (flags 0, PT_HISTORY_VARIANCE's side) is not built for a group; pass PT_HISTORY_MOMENTS", who);
+  bool extras = false;
+  if (history_current_moments(g, who) || shared_extras(g, who, &extras)) return -1;
+  if (!rgb_avg_host) return pt_fail("%s: null buffer", who);
+  const size_t frame = frame_pixels(g);
+  HIP_OK(hipSetDevice(g->devices[0]));
+  if (ensure(g, 0, g->d_denoise, pt_denoise_workspace_bytes(frame))) return -1;
+  if (gather_image(g) || gather_features(g) || (extras && gather_extra(g))) return -1;
+  j.f = {g->W, g->H, g->d_full, g->d_full_feat, nullptr};
+  if (g->hist_current) {
+    j.div.C = reinterpret_cast<const ptdn::V4*>(history_plane(g, pthi::kKeptPlanes));
+    j.div.VC = reinterpret_cast<const ptdn::V4*>(history_var_plane(g, 1));
+  }
+  j.div.E = extras ? g->d_full_extra : nullptr;  // counted: the prepare reads ns = samples + E_p
+  const float* d_out = nullptr;
+  if (pt_denoise_launch(stream(g, 0), j, g->d_denoise, &d_out)) return fail_after_drain(g);
+  return to_host(g, rgb_avg_host, d_out, frame * 12);
+}
+
+// The history round: group_round()'s shape with the history's key.  The frame's selection runs once, on the root, over the assembled
+// features and the group's C; every context renders and merges its own part (pt_ctx_history_round_list_device).
+//
+// Buffer order.  d_full_feat, the keys, d_list and d_parts are written and read on the root's stream only, behind the gathers that the
+// root's stream ordered after the contexts' feature passes (exchange()).  The read-back synchronises the root's stream, so when a
+// context's render begins the root has read that context's feature planes.  The parts go back as scatter_parts() says; context i's
+// render and merge are queued on ITS stream behind the copy (or receive) of its part.  The next exchange that reads a context's image
+// or E — the resolve, the filter, the capture, the next round — waits for ready[i], recorded on context i's stream behind that merge
+// (COPY), or sends on that stream (RCCL); and the group's C, which the key read, is next written by a lookup on the root's stream.
+int pt_group_history_round(PtGroup* g, int iter_first, int group_iters, const PtHistoryRoundOptions* opt, int* fresh, int* selected) {
+  const char* who = "pt_group_history_round";
+  if (!g) return pt_fail("%s: null group", who);
+  if (g->n == 1) return pt_ctx_history_round(g->ctx[0], iter_first, group_iters, opt, fresh, selected);
+  const int n = g->n, W = g->W, H = g->H;
+  const size_t frame = frame_pixels(g);
+  for (PtContext* c : g->ctx)
+    if (pt_ctx_history_round_refusal(c, who, iter_first, group_iters)) return -1;
+  pthi::RoundParams P{};
+  bool extras = false;
+  if (pt_history_round_options(who, opt, &P) || shared_extras(g, who, &extras) || round_limits(g, who)) return -1;
+  const int cap = ptad::list_length((double)P.max_fraction, (int64_t)frame);
+  hipStream_t root = stream(g, 0);
+  const uint8_t* emitter = nullptr;
+  int num_geoms = 0;
+  if (pt_ctx_history_geom_table(g->ctx[0], true, &emitter, &num_geoms) || selection_buffers(g)) return -1;
+
+  // collect on the root: the features, key, select, partition
+  if (gather_features(g)) return -1;
+  if (pt_history_key_launch(root, (int)frame, g->d_full_feat, current_plane(g), emitter, num_geoms, P.min_history, pt_adaptive_select_keys(g->d_select, frame)) ||
+      pt_adaptive_select_threshold_keys_launch(root, W, H, 0.0f, cap, g->d_select, g->d_list) ||
+      pt_group_partition_launch(root, W, n, g->d_list, pt_adaptive_select_result(g->d_select, frame), cap, g->d_partition, g->d_parts, g->d_result))
+    return fail_after_drain(g);
+
+  // read back: fresh, m and the parts' lengths
+  std::vector<uint32_t> result;
+  if (read_selection(g, who, cap, "fresh", &result)) return -1;
+  const int m = (int)result[1];
+  if (fresh) *fresh = (int)result[0];
+  if (selected) *selected = m;
+  if (m == 0) return 0;  // nothing rendered, merged or allocated; E keeps its state
+
+  // distribute and render: part i to context i, on context i's stream; a context with an empty part runs it too, so that all hold E
+  if (scatter_parts(g, result.data() + 2)) return -1;
+  for (int i = 0; i < n; ++i) {
+    const int pixels = pt_ctx_pixel_count(g->ctx[i]);
+    if (pt_ctx_history_round_list_device(g->ctx[i], iter_first, group_iters, i == 0 ? g->d_parts : g->d_part[i], (int)result[2 + (size_t)i], cap < pixels ? cap : pixels))
+      return fail_after_drain(g);
+  }
+  return 0;
+}
+
+int pt_group_history_drop(PtGroup* g) {
+  if (!g) return pt_fail("pt_group_history_drop: null group");
+  if (g->n == 1) return pt_ctx_history_drop(g->ctx[0]);
+  const size_t frame = frame_pixels(g);
+  if (g->d_hist) {  // forgotten, not freed
+    HIP_OK(hipSetDevice(g->devices[0]));
+    HIP_OK(hipMemsetAsync(g->d_hist, 0, pt_history_state_bytes(frame), stream(g, 0)));
+    if (g->d_hist_var) HIP_OK(hipMemsetAsync(g->d_hist_var, 0, pt_history_variance_bytes(frame), stream(g, 0)));
+  }
+  g->hist_kept = false, g->hist_var_kept = 0;
+  history_current_absent(g);
+  return 0;
+}
+
+int pt_group_readback_history(PtGroup* g, float* kept_planes, float* current_plane_host) {
+  const char* who = "pt_group_readback_history";
+  if (!g) return pt_fail("%s: null group", who);
+  if (g->n == 1) return pt_ctx_readback_history(g->ctx[0], kept_planes, current_plane_host);
+  if (!g->d_hist) return pt_fail("%s: nothing has been captured (pt_group_history_capture_ex)", who);
+  const size_t frame = frame_pixels(g), plane = frame * sizeof(pthi::V4);
+  HIP_OK(hipSetDevice(g->devices[0]));
+  if (kept_planes) HIP_OK(hipMemcpyAsync(kept_planes, g->d_hist, pthi::kKeptPlanes * plane, hipMemcpyDeviceToHost, stream(g, 0)));
+  if (current_plane_host && g->hist_current) HIP_OK(hipMemcpyAsync(current_plane_host, current_plane(g), plane, hipMemcpyDeviceToHost, stream(g, 0)));
+  if (pt_group_sync(g)) return -1;
+  if (current_plane_host && !g->hist_current) std::fill(current_plane_host, current_plane_host + 4 * frame, 0.0f);
+  return 0;
+}
+
+int pt_group_readback_history_variance(PtGroup* g, float* kept_var, float* current_var) {
+  if (!g) return pt_fail("pt_group_readback_history_variance: null group");
+  if (g->n == 1) return pt_ctx_readback_history_variance(g->ctx[0], kept_var, current_var);
+  const size_t frame = frame_pixels(g), plane = frame * sizeof(pthi::V4);
+  const bool kept = g->d_hist_var && g->hist_var_kept, current = g->d_hist_var && g->hist_var_current;
+  HIP_OK(hipSetDevice(g->devices[0]));
+  if (kept_var && kept) HIP_OK(hipMemcpyAsync(kept_var, history_var_plane(g, 0), plane, hipMemcpyDeviceToHost, stream(g, 0)));
+  if (current_var && current) HIP_OK(hipMemcpyAsync(current_var, history_var_plane(g, 1), plane, hipMemcpyDeviceToHost, stream(g, 0)));
+  if (pt_group_sync(g)) return -1;
+  if (kept_var && !kept) std::fill(kept_var, kept_var + 4 * frame, 0.0f);
+  if (current_var && !current) std::fill(current_var, current_var + 4 * frame, 0.0f);
+  return 0;
+}
+
+int pt_group_readback_history_extra(PtGroup* g, float* extra) {
+  const char* who = "pt_group_readback_history_extra";
+  if (!g) return pt_fail("%s: null group", who);
+  if (g->n == 1) return pt_ctx_readback_history_extra(g->ctx[0], extra);
+  if (!extra) return pt_fail("%s: null buffer", who);
+  bool extras = false;
+  if (shared_extras(g, who, &extras)) return -1;
+  if (!extras) {
+    if (pt_group_sync(g)) return -1;
+    std::fill(extra, extra + frame_pixels(g), 0.0f);
+    return 0;
+  }
+  HIP_OK(hipSetDevice(g->devices[0]));
+  if (gather_extra(g)) return -1;
+  return to_host(g, extra, g->d_full_extra, frame_pixels(g) * sizeof(float));
 }
 
 }  // extern "C"

@@ -548,7 +548,7 @@ static int history_capture(PtContext* c, const char* who, float samples, uint32_
     return -1;
   }
   g.hist_cam = g.cam;
-  if (g.hist_geoms_stale) g.hist_geoms = g.camera_base.geoms, g.hist_geoms_stale = false, g.hist_motion_fresh = false;  // the kept geoms: retaken only after a pt_set_geoms
+  if (PtHistoryMotion& hm = g.hist_motion; hm.geoms_stale) hm.geoms = g.camera_base.geoms, hm.geoms_stale = false, hm.fresh = false;  // the kept geoms: retaken only after a pt_set_geoms
   g.hist_kept = true;
   g.hist_var_kept = flags & ~PT_HISTORY_FEEDBACK;  // a plain capture: kept without variance or moments
   if (fb) std::swap(g.fb_plane_kept, g.fb_plane_pending), g.fb_pending = false;  // FK := P: the roles change, no bytes move
@@ -558,49 +558,52 @@ static int history_capture(PtContext* c, const char* who, float samples, uint32_
 int pt_ctx_history_capture(PtContext* c, float samples) { return history_capture(c, "pt_history_capture", samples, 0u, false); }
 int pt_ctx_history_capture_ex(PtContext* c, float samples, uint32_t flags) { return history_capture(c, "pt_history_capture_ex", samples, flags, true); }
 
-// reject_geom of pt_amd.h from the tables the renderer holds: the geoms' material ids (host) and the materials (device).  Blocking;
-// once per context.
-static int history_reject_table(Ctx& g) {
-  if (g.d_hist_reject) return 0;
+// A per-geom table of pt_amd.h, one byte per geom: 1 where `field` of the geom's material is positive (reject_geom: reflective;
+// emitter_geom: emittance), from the tables the renderer holds — the geoms' material ids (host) and the materials (device).  Blocking;
+// once per context and table.
+static int history_geom_table(Ctx& g, uint8_t*& d_table, float ptd::Mat::*field) {
+  if (d_table) return 0;
   std::vector<ptd::Mat> mats((size_t)std::max(g.scene.num_mats, 0));
   if (!mats.empty()) HIP_OK(hipMemcpy(mats.data(), g.scene.mats, mats.size() * sizeof(ptd::Mat), hipMemcpyDeviceToHost));
   const std::vector<PtGeom>& geoms = g.camera_base.geoms;
-  std::vector<uint8_t> reject(std::max<size_t>(geoms.size(), 1), 0);
+  std::vector<uint8_t> table(std::max<size_t>(geoms.size(), 1), 0);
   for (size_t i = 0; i < geoms.size(); ++i) {
     const int32_t m = geoms[i].materialid;
-    reject[i] = m >= 0 && (size_t)m < mats.size() && mats[(size_t)m].reflective > 0.0f ? 1 : 0;
+    table[i] = m >= 0 && (size_t)m < mats.size() && mats[(size_t)m].*field > 0.0f ? 1 : 0;
   }
-  if (ensure(g, g.d_hist_reject, reject.size())) return -1;
-  HIP_OK(hipMemcpy(g.d_hist_reject, reject.data(), reject.size(), hipMemcpyHostToDevice));
+  if (ensure(g, d_table, table.size())) return -1;
+  HIP_OK(hipMemcpy(d_table, table.data(), table.size(), hipMemcpyHostToDevice));
   return 0;
 }
+static int history_reject_table(Ctx& g) { return history_geom_table(g, g.d_hist_reject, &ptd::Mat::reflective); }
 
-// The motion table of the kept and the current geoms (pthi::motion_table) on the device, for a lookup with PT_HISTORY_MOTION.
+// The motion table of the kept geoms of `hm` and the current geoms (pthi::motion_table) on g's device, for a lookup with
+// PT_HISTORY_MOTION; hm: the context's own, or the one a group keeps for the frame's K (then g is the group's root context).
 // *moved == false: every geom is still; nothing was allocated or uploaded and the caller launches the kernel without the flag.
 // The table follows from the kept and the current geoms alone, so it is computed by the first lookup after either changed (a capture
 // that retook the geoms, pt_ctx_set_geoms) and uploaded when it differs from what the device holds (synchronises then: the staging
 // is pageable); later lookups find it in place — on 10,170 geoms the host's 0.3 ms per call would otherwise be nine times the kernel.
-static int history_motion_table(Ctx& g, bool* moved) {
+static int history_motion_table(Ctx& g, PtHistoryMotion& hm, bool* moved) {
   const std::vector<PtGeom>& cur = g.camera_base.geoms;
   const size_t n = cur.size();
   *moved = false;
-  if (g.hist_geoms.size() != n || n == 0) return 0;  // (nothing kept yet: the caller has refused already)
-  if (g.hist_motion_fresh) return *moved = g.hist_motion_moved, 0;
+  if (hm.geoms.size() != n || n == 0) return 0;  // (nothing kept yet: the caller has refused already)
+  if (hm.fresh) return *moved = hm.moved, 0;
   std::vector<float> table(n * pthi::kMotionRow);
   std::vector<uint8_t> kind(n);
-  pthi::motion_table(g.hist_geoms.data(), cur.data(), (int)n, table.data(), kind.data());
+  pthi::motion_table(hm.geoms.data(), cur.data(), (int)n, table.data(), kind.data());
   for (uint8_t k : kind) *moved = *moved || k != pthi::kStill;
-  g.hist_motion_moved = *moved;
-  if (!*moved) return g.hist_motion_fresh = true, 0;
+  hm.moved = *moved;
+  if (!*moved) return hm.fresh = true, 0;
   const size_t table_bytes = table.size() * sizeof(float);
-  if (ensure(g, g.d_hist_motion, table_bytes + n)) return -1;
-  if (table != g.hist_motion_table || kind != g.hist_motion_kind) {
+  if (ensure(g, hm.d_table, table_bytes + n)) return -1;
+  if (table != hm.table || kind != hm.kind) {
     HIP_OK(hipStreamSynchronize(g.stream));  // an earlier lookup may still read the rows
-    HIP_OK(hipMemcpy(g.d_hist_motion, table.data(), table_bytes, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(static_cast<char*>(g.d_hist_motion) + table_bytes, kind.data(), n, hipMemcpyHostToDevice));
-    g.hist_motion_table = std::move(table), g.hist_motion_kind = std::move(kind);
+    HIP_OK(hipMemcpy(hm.d_table, table.data(), table_bytes, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(static_cast<char*>(hm.d_table) + table_bytes, kind.data(), n, hipMemcpyHostToDevice));
+    hm.table = std::move(table), hm.kind = std::move(kind);
   }
-  g.hist_motion_fresh = true;
+  hm.fresh = true;
   return 0;
 }
 
@@ -628,15 +631,15 @@ static int history_reproject(PtContext* c, const char* who, const PtHistoryOptio
   const float* feat = reinterpret_cast<const float*>(g.d_feat);
   const int num_geoms = (int)g.camera_base.geoms.size();
   bool moved = false;
-  if (motion && history_motion_table(g, &moved)) return -1;
+  if (motion && history_motion_table(g, g.hist_motion, &moved)) return -1;
   if (fb) {
-    const float* table = moved ? static_cast<const float*>(g.d_hist_motion) : nullptr;
+    const float* table = moved ? static_cast<const float*>(g.hist_motion.d_table) : nullptr;
     const uint8_t* kind = moved ? reinterpret_cast<const uint8_t*>(table + (size_t)num_geoms * pthi::kMotionRow) : nullptr;
     if (pt_history_reproject_feedback_launch(g.stream, v, g.d_hist, feat, g.d_hist_reject, num_geoms, P, history_plane(g, pthi::kKeptPlanes), history_var_plane(g, 0),
                                              history_var_plane(g, 1), history_fb_plane(g, g.fb_plane_kept), history_fb_plane(g, g.fb_plane_current), table, kind))
       return -1;
   } else if (moved) {
-    const float* table = static_cast<const float*>(g.d_hist_motion);
+    const float* table = static_cast<const float*>(g.hist_motion.d_table);
     const uint8_t* kind = reinterpret_cast<const uint8_t*>(table + (size_t)num_geoms * pthi::kMotionRow);
     if (pt_history_reproject_motion_launch(g.stream, flags, v, g.d_hist, feat, g.d_hist_reject, num_geoms, P, history_plane(g, pthi::kKeptPlanes),
                                            flags ? history_var_plane(g, 0) : nullptr, flags ? history_var_plane(g, 1) : nullptr, table, kind))
@@ -856,32 +859,107 @@ int pt_ctx_readback_history_variance(PtContext* c, float* kept_var, float* curre
 }
 
 // ---- the history round: a group of further iterations for the pixels whose history is short --------------------------------
-// emitter_geom of pt_amd.h from the tables the renderer holds, as history_reject_table.  Blocking; once per context.
-static int history_emitter_table(Ctx& g) {
-  if (g.d_hist_emitter) return 0;
-  std::vector<ptd::Mat> mats((size_t)std::max(g.scene.num_mats, 0));
-  if (!mats.empty()) HIP_OK(hipMemcpy(mats.data(), g.scene.mats, mats.size() * sizeof(ptd::Mat), hipMemcpyDeviceToHost));
-  const std::vector<PtGeom>& geoms = g.camera_base.geoms;
-  std::vector<uint8_t> emitter(std::max<size_t>(geoms.size(), 1), 0);
-  for (size_t i = 0; i < geoms.size(); ++i) {
-    const int32_t m = geoms[i].materialid;
-    emitter[i] = m >= 0 && (size_t)m < mats.size() && mats[(size_t)m].emittance > 0.0f ? 1 : 0;
-  }
-  if (ensure(g, g.d_hist_emitter, emitter.size())) return -1;
-  HIP_OK(hipMemcpy(g.d_hist_emitter, emitter.data(), emitter.size(), hipMemcpyHostToDevice));
+// emitter_geom of pt_amd.h, as history_reject_table.
+static int history_emitter_table(Ctx& g) { return history_geom_table(g, g.d_hist_emitter, &ptd::Mat::emittance); }
+
+// What the round and the round over a caller's list refuse first: a failed context, the iteration range, the convergence metric.
+static int history_round_head(const Ctx& g, const char* who, int iter_first, int group_iters) {
+  if (admit(g, who, kNotFailed)) return -1;
+  if (iter_first < 1 || group_iters < 1 || (int64_t)iter_first + group_iters - 1 > INT32_MAX)
+    return pt_fail("%s: iterations %d, +%d: the first is >= 1, the group holds at least one", who, iter_first, group_iters);
+  if (g.conv) return pt_fail("%s: the renderer was created with PtOptions.convergence = %d; the convergence metric follows whole iterations", who, g.conv);
   return 0;
+}
+// Everything pt_history_round refuses before its options; rows == false: apart from the tile's rows (a group's context).
+static int history_round_refusal(const Ctx& g, const char* who, int iter_first, int group_iters, bool rows) {
+  if (history_round_head(g, who, iter_first, group_iters)) return -1;
+  if ((rows && admit(g, who, kWholeRows)) || admit(g, who, kUniform)) return -1;
+  if (!g.d_feat || !g.feat_fresh) return pt_fail(kNoFeatures, who);
+  return 0;
+}
+
+// The second half of a round, after key and selection: the m >= 0 pixels of g.d_list on the worker's live tile, merged into the image
+// and E.  E is ensured (zeroed) and made present even for m == 0, so that the contexts of a group agree on whether it exists.
+static int history_render_and_merge(Ctx& g, int iter_first, int group_iters, int m) {
+  if (ensure(g, g.d_hist_extra, (size_t)g.N * sizeof(float), Zero::on_stream)) return -1;  // the first round that renders (pt_clear zeroes it from then on)
+  g.hist_extra = true;
+  if (m == 0) return 0;
+  set_worker_live(*g.worker, m);
+  if (render_list(g, iter_first, group_iters)) return -1;
+  if (pt_history_merge_launch(g.stream, g.N, g.d_image, g.d_hist_extra, g.d_list, m, g.worker->d_image, group_iters)) return -1;
+  g.samples += (int64_t)group_iters * m;
+  return 0;
+}
+
+// pt_history_round_list: to pt_history_round what pt_adaptive_round_list is to the threshold round — the round without key and
+// selection, over a caller's list of tile pixels; allowed on a striped tile (it reads no features and no C, and needs no whole rows).
+// `list` on the host or on the context's device, as in round_list().
+static int history_round_list(PtContext* c, const char* who, int iter_first, int group_iters, const int32_t* list, bool host, int m, int capacity) {
+  if (need(c, who)) return -1;
+  Ctx& g = *c;
+  if (history_round_head(g, who, iter_first, group_iters) || admit(g, who, kUniform)) return -1;
+  if (capacity < 1 || capacity > g.N || m < 0 || m > capacity)
+    return pt_fail("%s: a list of %d on a worker for %d out of %d pixels: the capacity is 1 .. the tile, the list 0 .. the capacity", who, m, capacity, g.N);
+  if (m > 0 && !list) return pt_fail("%s: null list", who);
+  for (int i = 0; host && i < m; ++i)
+    if (list[i] < 0 || list[i] >= g.N || (i > 0 && list[i] <= list[i - 1]))
+      return pt_fail("%s: list[%d] = %d is outside the tile or not above its predecessor", who, i, list[i]);
+  HIP_OK(hipSetDevice(g.device));
+  if (ensure_worker(g, capacity)) return -1;
+  if (m > 0) {
+    HIP_OK(hipMemcpyAsync(g.d_list, list, (size_t)m * sizeof(int32_t), host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, g.stream));
+    if (g.stripe && pt_group_offsets_launch(g.stream, g.d_list, m, g.stripe, g.stripe_stride - g.stripe, g.d_list_frame)) return -1;
+  }
+  g.fb_pending = false;  // as in pt_history_round: the pending plane is the filter of the image before the round
+  return history_render_and_merge(g, iter_first, group_iters, m);
+}
+
+}  // extern "C"
+// pt_context.h: what a group's history asks of its contexts
+int pt_ctx_admit_no_extras(const PtContext* c, const char* who) { return need(c, who) ? -1 : admit(*c, who, kNoExtras); }
+bool pt_ctx_features_fresh(const PtContext* c) { return c && c->d_feat && c->feat_fresh; }
+bool pt_ctx_history_extra_present(const PtContext* c) { return c && c->hist_extra; }
+const float* pt_ctx_device_history_extra(PtContext* c) { return c && c->hist_extra ? c->d_hist_extra : nullptr; }
+int pt_history_check_flags(const char* who, uint32_t flags, bool motion) { return history_flags(who, flags, motion); }
+int pt_history_check_denoise_flags(const char* who, uint32_t flags) { return history_denoise_flags(who, flags); }
+int pt_ctx_history_round_refusal(const PtContext* c, const char* who, int iter_first, int group_iters) {
+  return need(c, who) ? -1 : history_round_refusal(*c, who, iter_first, group_iters, false);
+}
+int pt_ctx_history_geom_table(PtContext* c, bool emitter, const uint8_t** table_dev, int* num_geoms) {
+  if (need(c, "pt_group_history")) return -1;
+  Ctx& g = *c;
+  HIP_OK(hipSetDevice(g.device));
+  if (emitter ? history_emitter_table(g) : history_reject_table(g)) return -1;
+  *table_dev = emitter ? g.d_hist_emitter : g.d_hist_reject;
+  *num_geoms = (int)g.camera_base.geoms.size();
+  return 0;
+}
+int pt_ctx_history_motion_table(PtContext* c, PtHistoryMotion* m, const float** table_dev, const uint8_t** kind_dev) {
+  if (need(c, "pt_group_history")) return -1;
+  Ctx& g = *c;
+  HIP_OK(hipSetDevice(g.device));
+  bool moved = false;
+  if (history_motion_table(g, *m, &moved)) return -1;
+  *table_dev = moved ? static_cast<const float*>(m->d_table) : nullptr;
+  *kind_dev = moved ? reinterpret_cast<const uint8_t*>(*table_dev + g.camera_base.geoms.size() * pthi::kMotionRow) : nullptr;
+  return 0;
+}
+const std::vector<PtGeom>& pt_ctx_geoms(const PtContext* c) { return c->camera_base.geoms; }
+const PtCamera& pt_ctx_camera(const PtContext* c) { return c->cam; }
+extern "C" {
+
+int pt_ctx_history_round_list(PtContext* c, int iter_first, int group_iters, const int32_t* list_host, int m, int capacity) {
+  return history_round_list(c, "pt_history_round_list", iter_first, group_iters, list_host, true, m, capacity);
+}
+int pt_ctx_history_round_list_device(PtContext* c, int iter_first, int group_iters, const int32_t* list_dev, int m, int capacity) {
+  return history_round_list(c, "pt_history_round_list", iter_first, group_iters, list_dev, false, m, capacity);
 }
 
 int pt_ctx_history_round(PtContext* c, int iter_first, int group_iters, const PtHistoryRoundOptions* opt, int* fresh, int* selected) {
   const char* who = "pt_history_round";
   if (need(c, who)) return -1;
   Ctx& g = *c;
-  if (admit(g, who, kNotFailed)) return -1;
-  if (iter_first < 1 || group_iters < 1 || (int64_t)iter_first + group_iters - 1 > INT32_MAX)
-    return pt_fail("%s: iterations %d, +%d: the first is >= 1, the group holds at least one", who, iter_first, group_iters);
-  if (g.conv) return pt_fail("%s: the renderer was created with PtOptions.convergence = %d; the convergence metric follows whole iterations", who, g.conv);
-  if (admit(g, who, kWholeRows) || admit(g, who, kUniform)) return -1;
-  if (!g.d_feat || !g.feat_fresh) return pt_fail(kNoFeatures, who);
+  if (history_round_refusal(g, who, iter_first, group_iters, true)) return -1;
   pthi::RoundParams P{};
   if (pt_history_round_options(who, opt, &P)) return -1;
   HIP_OK(hipSetDevice(g.device));
@@ -902,13 +980,7 @@ int pt_ctx_history_round(PtContext* c, int iter_first, int group_iters, const Pt
   if (selected) *selected = m;
   g.fb_pending = false;  // the feedback's pending plane is the filter of the image before the round, whatever the round renders
   if (m == 0) return 0;  // nothing rendered, merged or allocated; E keeps its state
-  if (ensure(g, g.d_hist_extra, (size_t)g.N * sizeof(float), Zero::on_stream)) return -1;  // the first round that renders (pt_clear zeroes it from then on)
-  set_worker_live(*g.worker, m);
-  if (render_list(g, iter_first, group_iters)) return -1;
-  if (pt_history_merge_launch(g.stream, g.N, g.d_image, g.d_hist_extra, g.d_list, m, g.worker->d_image, group_iters)) return -1;
-  g.hist_extra = true;
-  g.samples += (int64_t)group_iters * m;
-  return 0;
+  return history_render_and_merge(g, iter_first, group_iters, m);
 }
 
 int pt_ctx_readback_history_extra(PtContext* c, float* extra_host) {

@@ -821,7 +821,8 @@ int pt_denoise_adaptive_variance_host(int w, int rows, const float* rgb_sum, con
  *     7  wsum >= 0.015625f:  h = acc / wsum;  t = tacc / wsum;  Th = t < cap ? t : cap;   else C = 0
  * The defaults are those of a CPU simulation on the cornell box (tests/test_history_sim.py; README "Reprojected history" has its
  * figures).  The bilinear lookup also smooths: the carried image is a BIASED estimator, and nothing here corrects that.
- * Out of scope: pt_group_* (a context's interleaved rows cannot look up their neighbours); a selection key that uses the carried
+ * Groups of contexts: "history in groups" below (pt_group_history_*: a context's interleaved rows cannot look up their neighbours,
+ * so the frame's history lives on the root device).  Out of scope: a selection key that uses the carried
  * variance; motion of anything but the camera.  (The filter over the blend: "variance of the history" below; extra samples for short
  * histories: "the history round" below; the history in the noise estimate, and a view rendered until the blend is clean: "the noise
  * estimate of the blend" below.) */
@@ -966,7 +967,7 @@ int pt_history_denoise_host(int w, int rows, const float* rgb_sum, const float* 
  * C present with VC absent or of the variance kind; a null buffer.
  * What it buys: README "Moments with the history" (tests/test_history_moments_sim.py on the CPU, tests/test_gpu_history_moments.py on
  * an MI355X, the same digits).  One scene, one orbit: no claim beyond it.
- * Out of scope: pt_group_*; feeding the moments into the noise estimate ("the noise estimate of the blend" below says why); a luminance-only variant; motion of anything but the
+ * Groups of contexts: "history in groups" below.  Out of scope: feeding the moments into the noise estimate ("the noise estimate of the blend" below says why); a luminance-only variant; motion of anything but the
  * camera.  (Extra samples for the marked pixels: "the history round" below; feeding the FILTERED image back into the history: "the
  * feedback" below, opt-in — without it K keeps the unfiltered blend.) */
 #define PT_HISTORY_MOMENTS 2u
@@ -1026,7 +1027,7 @@ int pt_history_denoise_moments_host(int w, int rows, const float* rgb_sum, const
  *        feature pass since the last clear or move; an option that is not finite or out of range.  It needs no capture and no
  *        lookup: with C absent every non-emitter hit pixel is fresh (the first view).  fresh / selected may be NULL.
  * What it buys: README "History-guided sampling" (tests/test_history_round_sim.py).
- * Out of scope: pt_group_*; a noise estimate of the blend while E is present (pt_history_noise refuses); scaling the spatial variance estimate by a pixel's extras;
+ * Groups of contexts: "history in groups" below (pt_group_history_round).  Out of scope: a noise estimate of the blend while E is present (pt_history_noise refuses); scaling the spatial variance estimate by a pixel's extras;
  * a key that uses rh or the carried variance; motion of anything but the camera. */
 #define PT_HISTORY_ROUND_MIN_HISTORY 4.0f /* the default of PtHistoryRoundOptions.min_history, in samples */
 typedef struct PtHistoryRoundOptions { /* every field: 0 = the default */
@@ -1035,6 +1036,16 @@ typedef struct PtHistoryRoundOptions { /* every field: 0 = the default */
 } PtHistoryRoundOptions;
 int pt_history_round(int iter_first, int group_iters, const PtHistoryRoundOptions* opt, int* fresh, int* selected);
 int pt_readback_history_extra(float* extra_host); /* pixel_count floats, zeros while E is absent; synchronises */
+/* The round over a caller's list: to pt_history_round what pt_adaptive_round_list is to the threshold round — its second half,
+ * without key and selection.  list_host holds m distinct tile indices in ascending order; the worker is kept for `capacity` pixels and
+ * live for m; render and merge as above; PtStats.samples grows by G * m.  It reads no features and no C and needs no whole rows, so it
+ * is allowed on a striped tile (the list then goes through the stripe's offsets as in pt_adaptive_round_list): this is what every
+ * context of a group runs over its part of the frame's list (pt_group_history_round).  With m == 0 nothing is rendered, but E is still
+ * ensured (zeroed) and made present, so that the contexts of a group agree on whether E exists.  Asynchronous.
+ * Refuses, in this order, nothing allocated or launched: no renderer or a failed context; iter_first < 1, group_iters < 1 or iterations
+ * past 2^31 - 1; PtOptions.convergence != 0; the adaptive state; capacity outside 1 .. pixel_count or m outside 0 .. capacity; a null
+ * list with m > 0; an entry outside the tile or not above its predecessor. */
+int pt_history_round_list(int iter_first, int group_iters, const int32_t* list_host, int m, int capacity);
 /* The same arithmetic on the host (no GPU); the device results equal these bit for bit.  list: cap = clamp(ceil(max_fraction * w * rows),
  * 1, w * rows) entries, of which the first *m are written.  current_plane may be NULL (absent); emitter_geom may be NULL when num_geoms == 0. */
 int pt_history_select_host(int w, int rows, const float* feature_planes, const float* current_plane, const uint8_t* emitter_geom, int num_geoms,
@@ -1078,7 +1089,7 @@ int pt_history_denoise_moments_counted_host(int w, int rows, const float* rgb_su
  * treats the world as static even after pt_set_geoms.
  * Caveat: a moved object changes shadows and indirect light on surfaces that stand still.  The lookup does not detect that: their
  * history goes stale until `cap` washes it out, unless the history probes below shorten it (a camera that stands still only).
- * Out of scope: adding or removing objects; material changes; deformation; a device-side tree build; history in groups. */
+ * Out of scope: adding or removing objects; material changes; deformation; a device-side tree build.  (Groups of contexts: "history in groups" below.) */
 #define PT_HISTORY_MOTION 4u
 int pt_history_motion_host(const PtGeom* kept, const PtGeom* cur, int n, float* table /* n * 24 */, uint8_t* kind /* n */);
 /* pt_history_reproject_host / _variance_host / _moments_host (flags & 3 picks which; kept_var, current_var NULL for the plain one)
@@ -1362,6 +1373,9 @@ int pt_ctx_history_denoise_ex(PtContext* c, float samples, const PtDenoiseOption
 int pt_ctx_history_denoise_ex_device(PtContext* c, float samples, const PtDenoiseOptions* opt, uint32_t flags, const float** rgb_dev); /* as pt_ctx_denoise_device */
 int pt_ctx_history_round(PtContext* c, int iter_first, int group_iters, const PtHistoryRoundOptions* opt, int* fresh, int* selected);
 int pt_ctx_readback_history_extra(PtContext* c, float* extra_host);
+int pt_ctx_history_round_list(PtContext* c, int iter_first, int group_iters, const int32_t* list_host, int m, int capacity);
+/* the same with the list in device memory of the context's device (its entries are not checked); copied on the context's stream */
+int pt_ctx_history_round_list_device(PtContext* c, int iter_first, int group_iters, const int32_t* list_dev, int m, int capacity);
 int pt_ctx_history_probe_keep(PtContext* c, int iter_first, int iter_count, int phase);
 int pt_ctx_history_probe_check(PtContext* c, const PtHistoryProbeOptions* opt, int* probes, int* changed, int* skipped);
 int pt_ctx_readback_history_probe(PtContext* c, float* kept, float* lam, int* count);
@@ -1474,6 +1488,62 @@ int pt_group_partition_host(int w, int h, int n, const int32_t* list, int m, int
 /* Progressive preview of the running average (sendImageToPBO, pathtrace.cu:250-268, which the reference runs after every
  * iteration): W*H RGBA8 bytes, raw orientation, converted on each device, one exchange of 4 B per pixel. */
 int pt_group_preview_rgba8(PtGroup* g, int iterations, uint8_t* rgba_host);
+
+/* ---- history in groups: the reprojected history of the whole frame (pt_history_capture_ex / _reproject_ex / _resolve /
+ * _denoise_ex with PT_HISTORY_MOMENTS / pt_history_round / pt_history_drop and their readbacks).  A context owns the rows i, i + n, ...
+ * and cannot look up its neighbours, so the group keeps the history of the FRAME on the root device and runs the single context's
+ * kernels there over W x H pixels; no kernel is the group's own.  Contract: after the same sequence of calls a group of n contexts
+ * holds what ONE renderer of the whole frame holds, bit for bit, in PT_ARITH_EXACT, _FMA and _FAST — K0..K2, C, VK, VC and E in frame
+ * order, the blend, the filtered image, the gathered SUM image, (fresh, selected) of every round; the contexts' PtStats.samples add up
+ * to the renderer's.  Built: the plain kind, the moments kind (PT_HISTORY_MOMENTS), the objects' motion (PT_HISTORY_MOTION) and the round.
+ * State, all of it on the root device, allocated (and zeroed) at first use and counted by pt_group_device_bytes: 64 bytes per frame pixel
+ *   for K0 K1 K2 and C from the first capture; 32 for VK and VC from the first capture with PT_HISTORY_MOMENTS; 12 for the blend from the
+ *   first resolve; 4 for the assembled E from the first call that reads E; beside the frames every filter of a group assembles (the SUM
+ *   image, the features, the filter's workspace) and the selection's buffers of the threshold round, which the history round shares.
+ *   On the host: the kept camera, kept / current, the kind VK and VC hold, the kept geoms and the motion table, as a context has them.
+ *   reject_geom, emitter_geom and the motion table are per geom and the same for every context: context 0 builds and keeps them.
+ * Lifetimes, a single context's: K, VK, the kept camera and the kept geoms survive pt_group_clear, pt_group_set_camera[_ex] and
+ *   pt_group_set_geoms; C and VC become absent on each of them; pt_group_history_drop forgets K, C, VK and VC and keeps the memory.  E
+ *   lives in the contexts, beside their rows of the image.  A caller who clears, moves or runs rounds on single contexts through
+ *   pt_group_context breaks the group, exactly as for the fold counters; where it shows (contexts that disagree on E) the call refuses.
+ * Steps of every call for n > 1: the refusals; the gathers onto the root (one exchange and row placement per payload, as every
+ *   write-out) — the capture assembles S, the features and E, the lookup the features, the resolve S and E, the filter S, the features
+ *   and E; E travels as a payload of 4 bytes per pixel and only while it is present, when the counted launches run; the single context's
+ *   launch on the root's stream with the view of the kept camera over H rows from row 0; one copy to the host and a synchronise of every
+ *   context where something is returned.  The capture and the lookup return nothing and do not synchronise.  Nothing assembled is kept
+ *   from one call to the next.  n == 1 forwards to context 0.
+ * The round: what pt_history_round refuses of any context; the features gathered; the key over the frame with the group's C (absent:
+ *   every non-emitter hit pixel is fresh); the threshold selection with threshold bits 0 and cap = clamp(ceil((double)max_fraction *
+ *   W*H), 1, W*H); the partition; fresh, m and the n lengths read back, 8 + 4n bytes behind ONE synchronise of the root's stream.
+ *   m == 0: nothing is rendered, merged or allocated, E keeps its state.  Otherwise part i goes to context i as in the threshold round
+ *   and every context runs pt_ctx_history_round_list_device over it on a worker for min(cap, its pixels), contexts with an empty part
+ *   included (they render nothing and hold E from then on); the contexts render concurrently, the call returns without a further synchronise.
+ * Refuses, under the group function's name, nothing allocated or launched, nothing changed in the group or in any context — first what
+ *   pt_history_* refuses of any context, in the single context's order and apart from the tile's rows, each condition over the contexts
+ *   in turn: a failed context; an undefined flag bit or an excluded pair; the adaptive state; no feature pass since the last clear or
+ *   move (not the resolve); samples; the options (the round: the iterations and PtOptions.convergence come right after the failed
+ *   context) — then the group's own: PT_HISTORY_VARIANCE, PT_HISTORY_FEEDBACK and pt_group_history_denoise_ex with flags 0, "not built
+ *   for a group"; nothing captured, or nothing captured with moments (the lookup); a C without moments (the capture with
+ *   PT_HISTORY_MOMENTS, the filter); contexts that disagree on E being present, naming the context; for the round the threshold
+ *   round's limits (at most 64 contexts, fewer than 32768 rows, at most 2^30 pixels); last a null output buffer.
+ * While any context holds E, every group entry point that reads the image as a uniform SUM refuses as the single context does:
+ *   pt_group_denoise, _denoise_guided, _denoise_adaptive, pt_group_noise_fold, pt_group_render_until, the adaptive round and driver,
+ *   pt_group_resolve, pt_group_gather_u8, pt_group_preview_rgba8; nothing allocated or launched.  pt_group_gather keeps working.
+ * Cost on one GPU and what share of a view the gathers take: README "History in groups" (profiles/group_history_cost.log).
+ * Out of scope: PT_HISTORY_VARIANCE, pt_history_noise / _render_until, the probes and the feedback in groups; the command line
+ *   (pt_render refuses --reproject with --gpus); caching assembled frames between calls; distributing the lookup or the filter over
+ *   the devices; load balance between parts. */
+int pt_group_clear(PtGroup* g); /* pt_clear on every context; the group's C and VC become absent */
+int pt_group_history_capture_ex(PtGroup* g, float samples, uint32_t flags);             /* flags: 0 or PT_HISTORY_MOMENTS */
+int pt_group_history_reproject_ex(PtGroup* g, const PtHistoryOptions* opt, uint32_t flags); /* 0 or PT_HISTORY_MOMENTS, each alone or with PT_HISTORY_MOTION */
+int pt_group_history_resolve(PtGroup* g, float samples, float* rgb_avg_host);           /* W*H*3 floats, raw orientation */
+int pt_group_history_denoise_ex(PtGroup* g, float samples, const PtDenoiseOptions* opt, uint32_t flags, float* rgb_avg_host); /* flags == PT_HISTORY_MOMENTS */
+int pt_group_history_round(PtGroup* g, int iter_first, int group_iters, const PtHistoryRoundOptions* opt, int* fresh, int* selected);
+int pt_group_history_drop(PtGroup* g);
+int pt_group_readback_history(PtGroup* g, float* kept_planes, float* current_plane);    /* pt_readback_history's layouts over W*H pixels */
+int pt_group_readback_history_variance(PtGroup* g, float* kept_var, float* current_var);
+int pt_group_readback_history_extra(PtGroup* g, float* extra);                          /* E of the frame, W*H floats; zeros while absent */
+int64_t pt_group_device_bytes(const PtGroup* g); /* bytes of the group's own device buffers, on every device (the contexts': PtStats.device_bytes) */
 
 /* The convergence metric of the whole frame: the reference frame is a W*H image (raw orientation, averaged radiance) of which
  * every context receives its rows; the contexts' SSEs are added in context order (one double per iteration and context crosses to
