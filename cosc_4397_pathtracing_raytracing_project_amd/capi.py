@@ -457,6 +457,39 @@ def lib() -> C.CDLL:
         L.pt_ctx_history_render_until.argtypes = [C.c_void_p] + _huntil
         L.pt_history_noise_host.argtypes = _hnz
         L.pt_stage_history_noise.argtypes = _hnz
+    if hasattr(L, "pt_history_round_threshold"):  # absent from older A/B builds of the library (tools/build_rev.sh)
+        _i64p, _dno = C.POINTER(C.c_int64), C.POINTER(PtDenoiseOptions)
+        _hthreshold = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _ip, _i64p, _ip]
+        _hnza = [C.c_int, _fp, _ip, _fp, _fp, _fp, _fp]
+        _hselect = [C.c_int, C.c_int, _fp, _ip, _fp, _fp, C.c_float, C.c_int, _ip, _ip, _ip]
+        _hcapture = [C.c_int, _fp, _fp, _fp, _ip, _fp, _fp, _fp, _fp]
+        _hdna = [C.c_int, C.c_int, _fp, _fp, _fp, _ip, _fp, _fp, _dno]
+        L.pt_history_noise_adaptive.argtypes = [_dp]
+        L.pt_readback_history_noise_samples.argtypes = [_fp]
+        L.pt_history_round_threshold.argtypes = [C.c_int, C.c_int, C.c_float, C.c_float, _ip, _ip]
+        L.pt_history_render_threshold.argtypes = _hthreshold
+        L.pt_history_resolve_adaptive.argtypes = [_fp]
+        L.pt_history_capture_adaptive.argtypes = []
+        L.pt_history_denoise_adaptive.argtypes = [_dno, _fp]
+        L.pt_ctx_history_noise_adaptive.argtypes = [C.c_void_p, _dp]
+        L.pt_ctx_readback_history_noise_samples.argtypes = [C.c_void_p, _fp]
+        L.pt_ctx_history_round_threshold.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, _ip, _ip]
+        L.pt_ctx_history_render_threshold.argtypes = [C.c_void_p] + _hthreshold
+        L.pt_ctx_history_resolve_adaptive.argtypes = [C.c_void_p, _fp]
+        L.pt_ctx_history_resolve_adaptive_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        L.pt_ctx_history_capture_adaptive.argtypes = [C.c_void_p]
+        L.pt_ctx_history_denoise_adaptive.argtypes = [C.c_void_p, _dno, _fp]
+        L.pt_ctx_history_denoise_adaptive_device.argtypes = [C.c_void_p, _dno, C.POINTER(C.c_void_p)]
+        L.pt_history_noise_adaptive_host.argtypes = _hnza + [_fp, _dp]
+        L.pt_stage_history_noise_adaptive.argtypes = _hnza + [_dp]
+        L.pt_history_select_threshold_blend_host.argtypes = _hselect
+        L.pt_stage_history_select_threshold_blend.argtypes = _hselect
+        L.pt_history_blend_adaptive_host.argtypes = [C.c_int, _fp, _ip, _fp, _fp]
+        L.pt_history_capture_adaptive_host.argtypes = _hcapture
+        L.pt_stage_history_capture_adaptive.argtypes = _hcapture + [_fp]
+        L.pt_history_denoise_adaptive_host.argtypes = _hdna + [_fp]
+        L.pt_stage_history_denoise_adaptive.argtypes = _hdna + [_fp]
+        L.pt_history_denoise_adaptive_variance_host.argtypes = _hdna + [_fp, _fp]
     if hasattr(L, "pt_group_history_round"):  # absent from older A/B builds of the library (tools/build_rev.sh)
         _hio, _hro, _dno = C.POINTER(PtHistoryOptions), C.POINTER(PtHistoryRoundOptions), C.POINTER(PtDenoiseOptions)
         L.pt_history_round_list.argtypes = [C.c_int, C.c_int, _ip, C.c_int, C.c_int]
@@ -882,6 +915,135 @@ def stage_history_noise(noise_planes: np.ndarray, groups: int, iters: int, sampl
     """history_noise_host's arguments through the production kernels (pt_stage_history_noise; a renderer must be live): (W, the
     device's SSE_blend)."""
     return _history_noise(lib().pt_stage_history_noise, noise_planes, groups, iters, samples, current, current_var)
+
+
+# ---- threshold rounds over the blend: the history steps with per-pixel counts (include/pt_amd.h: pt_history_round_threshold) ----
+def _blend_arrays(who: str, n: int, counts, current, current_var):
+    """counts int32 [n, 2] flat, and C, VC [n, 4] as ctypes arguments (None: absent)."""
+    c = np.ascontiguousarray(counts, np.int32).reshape(-1)
+    cur = None if current is None else np.ascontiguousarray(current, np.float32).reshape(-1)
+    var = None if current_var is None else np.ascontiguousarray(current_var, np.float32).reshape(-1)
+    if c.size != 2 * n or any(a is not None and a.size != 4 * n for a in (cur, var)):
+        raise PtError(f"{who}: {c.size} counts, or a current plane or variance that is not [{n}, 4]")
+    return c, cur, var, None if cur is None else _f(cur), None if var is None else _f(var)
+
+
+def _history_noise_adaptive(call, host: bool, noise_planes, counts, current, current_var):
+    z = np.ascontiguousarray(noise_planes, np.float32).reshape(-1)
+    n = z.size // (4 * NOISE_PLANES)
+    if z.size != 4 * NOISE_PLANES * n:
+        raise PtError(f"history_noise_adaptive: {z.size} noise plane floats")
+    c, cur, var, pc, pv = _blend_arrays("history_noise_adaptive", n, counts, current, current_var)
+    w, ne, vb, sse = np.empty(n, np.float32), np.empty(n, np.float32), np.empty((n, 4), np.float32), C.c_double(-1.0)
+    if host:
+        _check(call(n, _f(z), _i(c), pc, pv, _f(w), _f(ne), _f(vb), C.byref(sse)))
+        return w, ne, vb, float(sse.value)
+    _check(call(n, _f(z), _i(c), pc, pv, _f(w), _f(ne), C.byref(sse)))
+    return w, ne, float(sse.value)
+
+
+def history_noise_adaptive_host(noise_planes, counts, current=None, current_var=None):
+    """Pass A of a threshold round over the blend on the host (pt_history_noise_adaptive_host; no GPU): the fold's planes
+    [PT_NOISE_PLANES, n, 4], counts int32 [n, 2] (T_p, M_p) and the planes C, VC [n, 4] (None: absent) in; (W [n], NE [n], the
+    per-channel vb [n, 4], SSE_blend added in pixel order) out."""
+    return _history_noise_adaptive(lib().pt_history_noise_adaptive_host, True, noise_planes, counts, current, current_var)
+
+
+def stage_history_noise_adaptive(noise_planes, counts, current=None, current_var=None):
+    """history_noise_adaptive_host's arguments through the production kernels (pt_stage_history_noise_adaptive; a renderer must be
+    live): (W, NE, the device's SSE_blend)."""
+    return _history_noise_adaptive(lib().pt_stage_history_noise_adaptive, False, noise_planes, counts, current, current_var)
+
+
+def _select_threshold_blend(call, noise_planes, counts, w: int, rows: int, threshold: float, cap: int, current, current_var):
+    z, c, out = _select_arrays(noise_planes, counts, w, rows, cap)
+    _, cur, var, pc, pv = _blend_arrays("history_select_threshold_blend", int(w) * int(rows), counts, current, current_var)
+    above, m = C.c_int32(-1), C.c_int32(-1)
+    _check(call(int(w), int(rows), _f(z), _i(c), pc, pv, C.c_float(threshold), int(cap), _i(out), C.byref(above), C.byref(m)))
+    if not 0 <= m.value <= int(cap):
+        raise PtError(f"history_select_threshold_blend: a list of {m.value} (cap {cap})")
+    return out, int(above.value), int(m.value)
+
+
+def history_select_threshold_blend_host(noise_planes, counts, w: int, rows: int, threshold: float, cap: int, current=None, current_var=None):
+    """The selection of a threshold round over the blend on the host (pt_history_select_threshold_blend_host; no GPU):
+    adaptive_select_threshold_host's arguments and C, VC -> (the list's first m entries, above, m)."""
+    out, above, m = _select_threshold_blend(lib().pt_history_select_threshold_blend_host, noise_planes, counts, w, rows, threshold, cap, current, current_var)
+    return out[:m].copy(), above, m
+
+
+def stage_history_select_threshold_blend(noise_planes, counts, w: int, rows: int, threshold: float, cap: int, current=None, current_var=None):
+    """The same through passes A and B and the round's selection launches (pt_stage_history_select_threshold_blend; needs a Renderer);
+    the entries behind the list's length must still be -1."""
+    out, above, m = _select_threshold_blend(lib().pt_stage_history_select_threshold_blend, noise_planes, counts, w, rows, threshold, cap, current, current_var)
+    if (out[m:] != -1).any():
+        raise PtError(f"history_select_threshold_blend: a list of {m} (cap {cap}) with entries written behind it")
+    return out[:m].copy(), above, m
+
+
+def history_blend_adaptive_host(rgb_sum, counts, current=None) -> np.ndarray:
+    """pt_history_resolve_adaptive's blend on the host (no GPU): SUM image [n, 3], counts int32 [n, 2] and C [n, 4] (None: absent)
+    in, averaged radiance [n, 3] out."""
+    s = np.ascontiguousarray(rgb_sum, np.float32).reshape(-1)
+    n = s.size // 3
+    c, cur, _, pc, _ = _blend_arrays("history_blend_adaptive_host", n, counts, current, None)
+    out = np.empty((n, 3), np.float32)
+    _check(lib().pt_history_blend_adaptive_host(n, _f(s), _i(c), pc, _f(out)))
+    return out
+
+
+def _history_capture_adaptive(call, stage: bool, rgb_sum, planes, noise_planes, counts, current, current_var):
+    s = np.ascontiguousarray(rgb_sum, np.float32).reshape(-1)
+    p = np.ascontiguousarray(planes, np.float32).reshape(-1)
+    z = np.ascontiguousarray(noise_planes, np.float32).reshape(-1)
+    n = s.size // 3
+    if s.size != 3 * n or p.size != 4 * FEATURE_PLANES * n or z.size != 4 * NOISE_PLANES * n:
+        raise PtError(f"history_capture_adaptive: {s.size} image, {p.size} plane and {z.size} noise plane floats")
+    c, cur, var, pc, pv = _blend_arrays("history_capture_adaptive", n, counts, current, current_var)
+    kept, kvar = np.empty((HISTORY_KEPT_PLANES, n, 4), np.float32), np.empty((n, 4), np.float32)
+    if not stage:
+        _check(call(n, _f(s), _f(p), _f(z), _i(c), pc, pv, _f(kept), _f(kvar)))
+        return kept, kvar
+    avg = np.empty((n, 3), np.float32)
+    _check(call(n, _f(s), _f(p), _f(z), _i(c), pc, pv, _f(kept), _f(kvar), _f(avg)))
+    return kept, kvar, avg
+
+
+def history_capture_adaptive_host(rgb_sum, planes, noise_planes, counts, current=None, current_var=None):
+    """pt_history_capture_adaptive on the host (no GPU): SUM image [n, 3], feature SUM planes, the fold's planes, counts int32 [n, 2]
+    and C, VC (None: absent) in; (K [PT_HISTORY_KEPT_PLANES, n, 4], VK [n, 4]) out."""
+    return _history_capture_adaptive(lib().pt_history_capture_adaptive_host, False, rgb_sum, planes, noise_planes, counts, current, current_var)
+
+
+def stage_history_capture_adaptive(rgb_sum, planes, noise_planes, counts, current=None, current_var=None):
+    """The same through the capture's and the blend's kernels (pt_stage_history_capture_adaptive; needs a Renderer): (K, VK, the blend [n, 3])."""
+    return _history_capture_adaptive(lib().pt_stage_history_capture_adaptive, True, rgb_sum, planes, noise_planes, counts, current, current_var)
+
+
+def _history_denoise_adaptive(call, rgb_sum, planes, noise_planes, counts, w: int, rows: int, current, current_var, **opts):
+    s, p, z, c, out = _denoise_arrays(rgb_sum, planes, w, rows, noise_planes, counts)
+    _, cur, var, pc, pv = _blend_arrays("history_denoise_adaptive", int(w) * int(rows), counts, current, current_var)
+    return _filter(call, out, int(w), int(rows), _f(s), _f(p), _f(z), _i(c), pc, pv, **opts)
+
+
+def history_denoise_adaptive_host(rgb_sum, planes, noise_planes, counts, w: int, rows: int, current=None, current_var=None, **opts) -> np.ndarray:
+    """pt_history_denoise_adaptive on the host (no GPU): denoise_adaptive_host's arrays and the planes C, VC [w*rows, 4] (None: absent)."""
+    return _history_denoise_adaptive(lib().pt_history_denoise_adaptive_host, rgb_sum, planes, noise_planes, counts, w, rows, current, current_var, **opts)
+
+
+def stage_history_denoise_adaptive(rgb_sum, planes, noise_planes, counts, w: int, rows: int, current=None, current_var=None, **opts) -> np.ndarray:
+    """history_denoise_adaptive_host's arguments through the filter's kernels (pt_stage_history_denoise_adaptive; needs a Renderer)."""
+    return _history_denoise_adaptive(lib().pt_stage_history_denoise_adaptive, rgb_sum, planes, noise_planes, counts, w, rows, current, current_var, **opts)
+
+
+def history_denoise_adaptive_variance_host(rgb_sum, planes, noise_planes, counts, w: int, rows: int, current=None, current_var=None, **opts):
+    """The two variances that filter's levels start from (pt_history_denoise_adaptive_variance_host): (var_raw, var_0), [w*rows] each."""
+    s, p, z, c, _ = _denoise_arrays(rgb_sum, planes, w, rows, noise_planes, counts)
+    _, cur, var, pc, pv = _blend_arrays("history_denoise_adaptive", int(w) * int(rows), counts, current, current_var)
+    raw, pre = np.empty(w * rows, np.float32), np.empty(w * rows, np.float32)
+    opt = denoise_options(**opts)
+    _check(lib().pt_history_denoise_adaptive_variance_host(int(w), int(rows), _f(s), _f(p), _f(z), _i(c), pc, pv, C.byref(opt), _f(raw), _f(pre)))
+    return raw, pre
 
 
 HISTORY_MOMENTS = 2  # PT_HISTORY_MOMENTS
@@ -1706,6 +1868,51 @@ class Renderer:
         _check(lib().pt_history_render_until(int(iter_first), int(max_iters), int(group_iters), C.c_float(target_db), C.byref(done), C.byref(psnr),
                                              C.byref(view)))
         return int(done.value), float(psnr.value), float(view.value)
+
+    # ---- threshold rounds over the blend (include/pt_amd.h: pt_history_round_threshold) ----
+    def history_noise_adaptive(self) -> float:
+        """history_noise with the sample counts of every pixel, valid in the adaptive state too (pt_history_noise_adaptive; synchronises):
+        SSE_blend.  readback_history_noise returns W, readback_history_noise_samples NE."""
+        sse = C.c_double(-1.0)
+        _check(lib().pt_history_noise_adaptive(C.byref(sse)))
+        return float(sse.value)
+
+    def readback_history_noise_samples(self) -> np.ndarray:
+        """The plane NE beside W: the blend's effective sample count Tf_p + Th per pixel, float32 [n]."""
+        out = np.empty(self.n, np.float32)
+        _check(lib().pt_readback_history_noise_samples(_f(out)))
+        return out
+
+    def history_round_threshold(self, iter_first: int, group_iters: int, threshold: float, max_fraction: float = 1.0):
+        """adaptive_round_threshold keyed by the variance of the blend with the reprojected history (pt_history_round_threshold):
+        (pixels above, pixels rendered)."""
+        above, selected = C.c_int32(-1), C.c_int32(-1)
+        _check(lib().pt_history_round_threshold(int(iter_first), int(group_iters), C.c_float(threshold), C.c_float(max_fraction), C.byref(above),
+                                                C.byref(selected)))
+        return int(above.value), int(selected.value)
+
+    def history_render_threshold(self, iter_first: int, max_iters: int, threshold: float, max_fraction: float = 0.25, group_iters: int = 0,
+                                 min_pixels: int = 0):
+        """render_threshold over those rounds (pt_history_render_threshold): (iteration numbers used, pixel-samples rendered, pixels
+        above at the last count or -1)."""
+        done, samples, above = C.c_int32(0), C.c_int64(0), C.c_int32(-1)
+        _check(lib().pt_history_render_threshold(int(iter_first), int(max_iters), int(group_iters), C.c_float(threshold), C.c_float(max_fraction),
+                                                 int(min_pixels), C.byref(done), C.byref(samples), C.byref(above)))
+        return int(done.value), int(samples.value), int(above.value)
+
+    def history_resolve_adaptive(self) -> np.ndarray:
+        """history_resolve with every pixel's own sample count (pt_history_resolve_adaptive): float32 [n, 3]."""
+        out = np.empty((self.n, 3), np.float32)
+        _check(lib().pt_history_resolve_adaptive(_f(out)))
+        return out
+
+    def history_capture_adaptive(self) -> None:
+        """history_capture_ex(HISTORY_VARIANCE) with every pixel's own counts (pt_history_capture_adaptive)."""
+        _check(lib().pt_history_capture_adaptive())
+
+    def history_denoise_adaptive(self, **opts) -> np.ndarray:
+        """history_denoise with every pixel's own counts (pt_history_denoise_adaptive): float32 [n, 3]."""
+        return _filter(lib().pt_history_denoise_adaptive, np.empty((self.n, 3), np.float32), **opts)
 
     def denoise(self, samples: float, **opts) -> np.ndarray:
         """The image filtered by the edge-avoiding filter over the feature buffers (pt_denoise; options: denoise_options):

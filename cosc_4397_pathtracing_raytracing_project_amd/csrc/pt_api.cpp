@@ -991,7 +991,7 @@ int pt_ctx_clear(PtContext* c) {
   c->fb_current = c->fb_pending = false;  // ... and so are the feedback's FC and P; FK stays
   if (c->d_hist_extra) HIP_OK(hipMemsetAsync(c->d_hist_extra, 0, (size_t)c->N * sizeof(float), c->stream));  // the extras belong to the image
   c->hist_extra = false;
-  c->hist_noise = false;  // the blend's noise plane W described the image that was
+  c->hist_noise = c->hist_ne = false;  // the blend's noise plane W (and NE beside it) described the image that was
   c->probe_checked = c->probe_applied = false;  // the probes' L belongs to C; PK stays
   if (c->conv) {  // forget the curve, re-arm the capture (a supplied frame stays)
     HIP_OK(hipMemsetAsync(c->d_sse, 0xff, (size_t)PT_CONVERGENCE_CAPACITY * sizeof(double), c->stream));
@@ -1487,6 +1487,18 @@ int pt_readback_history_noise(float* w_host) { return pt_ctx_readback_history_no
 int pt_history_render_until(int iter_first, int max_iters, int group_iters, float target_db, int* iters_done, float* psnr_db, float* view_psnr_db) {
   return pt_ctx_history_render_until(g_default, iter_first, max_iters, group_iters, target_db, iters_done, psnr_db, view_psnr_db);
 }
+int pt_history_noise_adaptive(double* sse) { return pt_ctx_history_noise_adaptive(g_default, sse); }
+int pt_readback_history_noise_samples(float* ne_host) { return pt_ctx_readback_history_noise_samples(g_default, ne_host); }
+int pt_history_round_threshold(int iter_first, int group_iters, float threshold, float max_fraction, int* above, int* selected) {
+  return pt_ctx_history_round_threshold(g_default, iter_first, group_iters, threshold, max_fraction, above, selected);
+}
+int pt_history_render_threshold(int iter_first, int max_iters, int group_iters, float threshold, float max_fraction, int min_pixels, int* iters_done,
+                                int64_t* samples_done, int* above_left) {
+  return pt_ctx_history_render_threshold(g_default, iter_first, max_iters, group_iters, threshold, max_fraction, min_pixels, iters_done, samples_done, above_left);
+}
+int pt_history_resolve_adaptive(float* rgb_avg_host) { return pt_ctx_history_resolve_adaptive(g_default, rgb_avg_host); }
+int pt_history_capture_adaptive(void) { return pt_ctx_history_capture_adaptive(g_default); }
+int pt_history_denoise_adaptive(const PtDenoiseOptions* opt, float* rgb_avg_host) { return pt_ctx_history_denoise_adaptive(g_default, opt, rgb_avg_host); }
 int pt_set_reference(const float* rgb_avg_host) { return pt_ctx_set_reference(g_default, rgb_avg_host); }
 int pt_get_convergence(int iter_first, int iter_count, double* sse) { return pt_ctx_get_convergence(g_default, iter_first, iter_count, sse); }
 int pt_iterations_to_clean(float threshold_db, int* iteration) { return pt_ctx_iterations_to_clean(g_default, threshold_db, iteration); }

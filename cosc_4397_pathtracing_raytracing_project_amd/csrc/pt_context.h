@@ -196,6 +196,8 @@ struct PtContext : PtShared {
   // The noise estimate of the blend (pt_ctx_history_noise): absent until the first estimate
   void* d_hist_noise = nullptr;    // pt_history_noise_bytes(N): the partial sums, SSE_blend, then the plane W
   bool hist_noise = false;         // W holds an estimate of the image as it stood; pt_clear and a move make it absent
+  float* d_hist_ne = nullptr;      // the plane NE beside W (pt_ctx_history_noise_adaptive, pt_ctx_history_round_threshold): N floats; absent until the first of those
+  bool hist_ne = false;            // NE belongs to the W that is present: pass A of those calls wrote both; absent whenever W is
   // The history round (pt_ctx_history_round): all of it absent until the first round that renders something
   float* d_hist_extra = nullptr;   // the extra plane E: N floats, the samples the image holds per pixel beyond the uniform ones
   bool hist_extra = false;         // E is present: from a round that rendered to pt_clear or a camera move, which zero it

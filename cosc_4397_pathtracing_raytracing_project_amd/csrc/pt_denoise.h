@@ -15,7 +15,9 @@
 // (pt_history_denoise_feedback; tests/history_feedback_ref.py) is the moments form over another colour: its prepare filters the blend of
 // the new samples with the FILTERED history FC (pt_history.h), the variance still comes from the raw chain (or, by option, from the
 // variance FC carries), and tap_pixel — a step of its own after level L - 1 — leaves {c_L remodulated, var_L}, the plane the next capture
-// promotes to FK.  Everything between is the moments form's.
+// promotes to FK.  Everything between is the moments form's.  The history form with per-pixel counts (pt_history_denoise_adaptive;
+// tests/history_threshold_ref.py) is the history form's prepare with the counts of every pixel (Tf_p, Df_p; the blend's samples are
+// Tf_p) and NE_p = Tf_p + Th in the position buffer's spare word, followed by the adaptive form's prefilter, levels and finish.
 // Every float operation is a separate IEEE operation in the order pt_amd.h states (`#pragma clang fp contract(off)` in every body, correctly
 // rounded division, denormals kept), so the result does not depend on the arithmetic mode of the build or on the side it runs on.
 // Plain C++ apart from PT_HD: the system compiler accepts it (a host sanitizer run needs nothing else).
@@ -89,7 +91,8 @@ PT_HD float color_factor(const Params& P, int l) {
 // Moments: what the blend reads only — samples, C and VC = {m2h.xyz, rh} (both nullptr: absent); no fold, no noise planes.
 // E (the moments form; nullptr: absent): the extra plane of the history round — the pixel's samples are samples + E_p (pthi::Counted).
 // Feedback: the moments form's and FC = {f.xyz, vf} beside C (nullptr: absent), and the variance rule (PtHistoryFeedbackOptions.variance).
-enum class Form { Plain, Guided, Adaptive, History, Moments, Feedback };
+// HistoryAdaptive: the adaptive form's counts and the history form's C and VC; the blend's samples are the pixel's own Tf_p.
+enum class Form { Plain, Guided, Adaptive, History, Moments, Feedback, HistoryAdaptive };
 struct Divisors {
   float Tf, Df;
   const ptad::Cnt* cnt;
@@ -149,14 +152,15 @@ PT_HD float feedback_view_variance(float m2b, float cb, float g, float albedo, i
 constexpr float kSpatialMark = -1.0f;
 PT_HD bool spatial_marked(float var_raw) { return var_raw == kSpatialMark; }
 // The guided forms (noise: the fold's two planes) leave var_raw in the albedo buffer's spare word.  The adaptive form leaves Tf_p in
-// the position buffer's spare word, which no tap reads (dist2: xyz) and the other two leave 0.
+// the position buffer's spare word, which no tap reads (dist2: xyz) and the other two leave 0; the history form with counts leaves
+// NE_p = Tf_p + Th there.
 // D: Divisors, or the members of it that the form reads (a kernel takes no more than those).
 template <Form kForm, typename D>
 PT_HD void prepare_pixel_of(size_t i, size_t npix, const float* S, const V4* planes, const V4* noise, const D& d, int keep_albedo, V4* n, V4* p, V4* a,
                             V4* c) {
 #pragma clang fp contract(off)
   [[maybe_unused]] float Tf = 0.0f, Df = 0.0f;
-  if constexpr (kForm == Form::Adaptive) {
+  if constexpr (kForm == Form::Adaptive || kForm == Form::HistoryAdaptive) {
     const int32_t Tp = d.cnt ? d.cnt[i].T : d.T, Mp = d.cnt ? d.cnt[i].M : d.M;
     Tf = (float)Tp;
     Df = (float)(Mp - 1) * Tf;
@@ -175,8 +179,9 @@ PT_HD void prepare_pixel_of(size_t i, size_t npix, const float* S, const V4* pla
   V4 vc{0.0f, 0.0f, 0.0f, 0.0f};
   [[maybe_unused]] V4 hc{0.0f, 0.0f, 0.0f, 0.0f}, hv{0.0f, 0.0f, 0.0f, 0.0f};  // history: C and VC of the pixel (absent: +0)
   [[maybe_unused]] float ns = 0.0f;  // history: the pixel's samples (with its extras, where the history round left some)
-  if constexpr (kForm == Form::History || kForm == Form::Moments || kForm == Form::Feedback) {
-    ns = history_samples(d, i);
+  if constexpr (kForm == Form::History || kForm == Form::Moments || kForm == Form::Feedback || kForm == Form::HistoryAdaptive) {
+    if constexpr (kForm == Form::HistoryAdaptive) ns = Tf;
+    else ns = history_samples(d, i);
     if (d.C) hc = d.C[i];
     if (d.VC) hv = d.VC[i];
     vc.x = pthi::blend_component(S[3 * i], ns, hc.x, hc.w);
@@ -197,7 +202,7 @@ PT_HD void prepare_pixel_of(size_t i, size_t npix, const float* S, const V4* pla
     vc.y = va.y > 0.0f ? vc.y / va.y : vc.y;
     vc.z = va.z > 0.0f ? vc.z / va.z : vc.z;
   }
-  if constexpr (kForm == Form::History) {
+  if constexpr (kForm == Form::History || kForm == Form::HistoryAdaptive) {
     const V4 prev = noise[i], q = noise[npix + i];
     const float vx = history_variance(prev.x, q.x, va.x, Tf, Df, ns, hv.x, hc.w, keep_albedo);
     const float vy = history_variance(prev.y, q.y, va.y, Tf, Df, ns, hv.y, hc.w, keep_albedo);
@@ -232,6 +237,7 @@ PT_HD void prepare_pixel_of(size_t i, size_t npix, const float* S, const V4* pla
     const float vz = guided_variance(prev.z, q.z, va.z, Tf, Df, keep_albedo);
     va.w = (vx + vy) + vz;
   }
+  if constexpr (kForm == Form::HistoryAdaptive) vp.w = Tf + hc.w;  // NE_p, the blend's effective sample count: what the prefilter scales by
   n[i] = vn, p[i] = vp, a[i] = va, c[i] = vc;
 }
 
@@ -452,7 +458,8 @@ inline void denoise_host(const Job& j, const int32_t* counts, float* out, float*
   const int W = j.f.w, R = j.f.rows;
   const Params& P = j.P;
   const bool feedback = j.form == Form::Feedback, moments = j.form == Form::Moments || feedback;
-  const bool guided = j.form != Form::Plain, folded = guided && !moments, blended = j.form == Form::History || moments;
+  const bool counted = j.form == Form::Adaptive || j.form == Form::HistoryAdaptive;
+  const bool guided = j.form != Form::Plain, folded = guided && !moments, blended = j.form == Form::History || j.form == Form::HistoryAdaptive || moments;
   const size_t npix = (size_t)W * R;
   std::vector<V4> ws(kWorkspaceV4 * npix);
   V4 *n = ws.data(), *p = n + npix, *a = p + npix, *col[2] = {a + npix, a + 2 * npix};
@@ -480,6 +487,7 @@ inline void denoise_host(const Job& j, const int32_t* counts, float* out, float*
     else if (j.form == Form::History) prepare_pixel_of<Form::History>(i, npix, j.f.rgb_sum, pl.data(), nz, d, P.keep_albedo, n, p, a, col[0]);
     else if (j.form == Form::Moments) prepare_pixel_of<Form::Moments>(i, npix, j.f.rgb_sum, pl.data(), nullptr, d, P.keep_albedo, n, p, a, col[0]);
     else if (feedback) prepare_pixel_of<Form::Feedback>(i, npix, j.f.rgb_sum, pl.data(), nullptr, d, P.keep_albedo, n, p, a, col[0]);
+    else if (j.form == Form::HistoryAdaptive) prepare_pixel_of<Form::HistoryAdaptive>(i, npix, j.f.rgb_sum, pl.data(), nz, d, P.keep_albedo, n, p, a, col[0]);
     else prepare_pixel_of<Form::Adaptive>(i, npix, j.f.rgb_sum, pl.data(), nz, d, P.keep_albedo, n, p, a, col[0]);
   }
   for (size_t i = 0; i < npix && mark; ++i) mark[i] = moments && spatial_marked(a[i].w) ? 1 : 0;
@@ -488,7 +496,7 @@ inline void denoise_host(const Job& j, const int32_t* counts, float* out, float*
       if (spatial_marked(a[(size_t)y * W + x].w)) var_spatial_pixel(W, R, x, y, P, n, p, col[0], a);
   for (int y = 0; y < R && guided; ++y)
     for (int x = 0; x < W; ++x) {
-      if (j.form == Form::Adaptive) var_prefilter_of<true>(W, R, x, y, n, a, p, col[0]);
+      if (counted) var_prefilter_of<true>(W, R, x, y, n, a, p, col[0]);
       else var_prefilter_of<false>(W, R, x, y, n, a, p, col[0]);
     }
   for (size_t i = 0; i < npix && var_raw; ++i) var_raw[i] = a[i].w;

@@ -16,6 +16,9 @@
 //                                  present); per pixel 12 B of S, 48 B of features, 32 B of noise, 16 + 16 B of history in, 64 B out
 //                                  <Moments>: the blend and its variance from the history's moments, no noise planes: per pixel 12 B of
 //                                  S, 48 B of features, 16 + 16 B of history in, 64 B out; var_raw = -1 marks a pixel for the next kernel
+//                                  <HistoryAdaptive> (pt_history_denoise_adaptive): <History> with the pixel's own counts as <Adaptive>
+//                                  reads them (8 B more in) and Tf_p for the blend's samples; NE_p = Tf_p + Th out in the position's spare
+//                                  word, so that k_denoise_var_prefilter<true> and everything behind it run unchanged
 //   k_denoise_prepare_counted      <Moments> while the history round's extra plane is present (pt_history_round): + 4 B of E in per pixel,
 //                                  the pixel's samples are samples + E_p; a twelfth kernel, launched only then
 //   k_denoise_var_spatial          the moments form, between prepare and the prefilter; the level kernel's shape (64 x 4 tiles, a wave is
@@ -76,6 +79,14 @@ struct PrepareIn<Form::History> {
   const V4* __restrict__ C;
   const V4* __restrict__ VC;
   float Tf, Df, samples;
+};
+template <>
+struct PrepareIn<Form::HistoryAdaptive> {
+  const V4* __restrict__ noise;
+  const ptad::Cnt* __restrict__ cnt;
+  const V4* __restrict__ C;
+  const V4* __restrict__ VC;
+  int T, M;
 };
 template <>
 struct PrepareIn<Form::Moments> {
@@ -184,7 +195,7 @@ __global__ __launch_bounds__(kBlock) void k_denoise_finish(int npix, int keep_al
 // pt_internal.h.  Everything is checked before the first launch; no allocation, no synchronisation.
 int pt_denoise_launch(hipStream_t stream, const ptdn::Job& j, void* workspace_dev, const float** rgb_avg_dev) {
   static const char* const kWho[] = {"pt_denoise", "pt_denoise_guided", "pt_denoise_adaptive", "pt_history_denoise", "pt_history_denoise_ex",
-                                     "pt_history_denoise_feedback"};
+                                     "pt_history_denoise_feedback", "pt_history_denoise_adaptive"};
   const char* who = kWho[(int)j.form];
   const int w = j.f.w, rows = j.f.rows;
   const Params& P = j.P;
@@ -193,6 +204,7 @@ int pt_denoise_launch(hipStream_t stream, const ptdn::Job& j, void* workspace_de
   const bool ok = j.form == Form::Plain      ? d.Tf > 0.0f
                   : j.form == Form::Guided   ? j.f.noise && d.Tf >= 2.0f && d.Df >= d.Tf
                   : j.form == Form::Adaptive ? j.f.noise && (d.cnt || (d.M >= 2 && d.T >= d.M))
+                  : j.form == Form::HistoryAdaptive ? j.f.noise && (d.cnt || (d.M >= 2 && d.T >= d.M)) && !d.C == !d.VC
                   : j.form == Form::Moments  ? d.samples > 0.0f && !d.C == !d.VC
                   : j.form == Form::Feedback ? d.samples > 0.0f && !d.C == !d.VC && !d.C == !d.FC && (d.fb_variance == 0 || d.fb_variance == 1) && j.tap &&
                                                    j.tap_level >= 1 && j.tap_level <= P.levels
@@ -203,12 +215,17 @@ int pt_denoise_launch(hipStream_t stream, const ptdn::Job& j, void* workspace_de
   V4 *p = n + npix, *a = p + npix, *col[2] = {a + npix, a + 2 * (size_t)npix};
   const int flat = (npix + kBlock - 1) / kBlock;
   const dim3 tiles((w + kLevelX - 1) / kLevelX, (rows + kLevelY - 1) / kLevelY);
+  const bool blend_counts = j.form == Form::HistoryAdaptive;
   const bool guided = j.form != Form::Plain, adaptive = j.form == Form::Adaptive, history = j.form == Form::History, feedback = j.form == Form::Feedback,
              moments = j.form == Form::Moments || feedback;
   const V4 *planes = reinterpret_cast<const V4*>(j.f.planes), *noise = reinterpret_cast<const V4*>(j.f.noise);
   if (adaptive)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_denoise_prepare<Form::Adaptive, const V4* __restrict__, const ptad::Cnt* __restrict__, int, int>), dim3(flat), dim3(kBlock),
                        0, stream, npix, j.f.rgb_sum, planes, noise, d.cnt, d.T, d.M, P.keep_albedo, n, p, a, col[0]);
+  else if (blend_counts)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_denoise_prepare<Form::HistoryAdaptive, const V4* __restrict__, const ptad::Cnt* __restrict__, const V4* __restrict__,
+                                                         const V4* __restrict__, int, int>),
+                       dim3(flat), dim3(kBlock), 0, stream, npix, j.f.rgb_sum, planes, noise, d.cnt, d.C, d.VC, d.T, d.M, P.keep_albedo, n, p, a, col[0]);
   else if (history)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_denoise_prepare<Form::History, const V4* __restrict__, const V4* __restrict__, const V4* __restrict__, float, float, float>),
                        dim3(flat), dim3(kBlock), 0, stream, npix, j.f.rgb_sum, planes, noise, d.C, d.VC, d.Tf, d.Df, d.samples, P.keep_albedo, n, p, a, col[0]);
@@ -232,7 +249,7 @@ int pt_denoise_launch(hipStream_t stream, const ptdn::Job& j, void* workspace_de
                        a, col[0]);
   if (moments) hipLaunchKernelGGL(k_denoise_var_spatial, tiles, dim3(kBlock), 0, stream, w, rows, P, n, p, col[0], a);
   if (guided)
-    hipLaunchKernelGGL(adaptive ? k_denoise_var_prefilter<true> : k_denoise_var_prefilter<false>, tiles, dim3(kBlock), 0, stream, w, rows, n, a, p, col[0]);
+    hipLaunchKernelGGL(adaptive || blend_counts ? k_denoise_var_prefilter<true> : k_denoise_var_prefilter<false>, tiles, dim3(kBlock), 0, stream, w, rows, n, a, p, col[0]);
   for (int l = 0; l < P.levels; ++l) {
     const dim3 grid(tiles.x, (ptdn::level_slots(rows, l) + kLevelY - 1) / kLevelY);
     hipLaunchKernelGGL(guided ? k_denoise_level<true> : k_denoise_level<false>, grid, dim3(kBlock), 0, stream, w, rows, l, P, col[ptdn::color_buffer(l)], n, p,
@@ -261,7 +278,7 @@ int pt_denoise_resolve(const char* who, ptdn::Form form, float samples, int grou
   }
   *j = ptdn::Job{};
   j->form = form;
-  const bool blended = form == Form::History || form == Form::Moments || form == Form::Feedback;
+  const bool blended = form == Form::History || form == Form::Moments || form == Form::Feedback || form == Form::HistoryAdaptive;
   if (const char* msg = ptdn::resolve(opt, &j->P, form == Form::Plain ? 4.0f : blended ? ptdn::kHistorySigmaColor : ptdn::kGuidedSigmaColor)) return pt_fail("%s: %s", who, msg);
   if (form == Form::Plain) j->div.Tf = samples;
   if (blended) j->div.samples = samples;
@@ -269,7 +286,7 @@ int pt_denoise_resolve(const char* who, ptdn::Form form, float samples, int grou
     const ptnz::Fold f = ptnz::fold_scalars(1, groups, iters);
     j->div.Tf = f.Tf, j->div.Df = f.Df;
   }
-  if (form == Form::Adaptive) j->div.T = (int32_t)iters, j->div.M = groups;
+  if (form == Form::Adaptive || form == Form::HistoryAdaptive) j->div.T = (int32_t)iters, j->div.M = groups;
   return 0;
 }
 
@@ -299,6 +316,19 @@ int pt_history_denoise_check(const char* who, int w, int rows, const float* rgb_
     return pt_fail("%s: the current plane %s its variance: both or neither (a lookup made with PT_HISTORY_VARIANCE gives both)", who,
                    current_plane ? "comes without" : "is absent, but not");
   if (!rgb_avg) return pt_fail("%s: null buffer", who);
+  return 0;
+}
+
+// ... and of the history form with per-pixel counts: the arrays' shape and the counts (pt_denoise_adaptive_check's words), the options, C
+// without VC, no output.
+int pt_history_denoise_adaptive_check(const char* who, int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, const int32_t* counts,
+                                      const float* current_plane, const float* current_var, const PtDenoiseOptions* opt, bool has_output, ptdn::Job* j) {
+  if (pt_denoise_adaptive_check(who, w, rows, rgb_sum, planes, noise_planes, counts, opt, j)) return -1;
+  if (pt_denoise_resolve(who, Form::HistoryAdaptive, 0.0f, 0, 0, opt, j)) return -1;
+  if (!current_plane != !current_var)
+    return pt_fail("%s: the current plane %s its variance: both or neither (a lookup made with PT_HISTORY_VARIANCE gives both)", who,
+                   current_plane ? "comes without" : "is absent, but not");
+  if (!has_output) return pt_fail("%s: null buffer", who);
   return 0;
 }
 
@@ -415,6 +445,26 @@ int pt_history_denoise_feedback_host(int w, int rows, const float* rgb_sum, cons
   j.f = {w, rows, rgb_sum, planes, nullptr, current_plane, current_var, extra, current_fb};
   j.tap = tap;
   ptdn::denoise_host(j, nullptr, rgb_avg, var_raw, nullptr, mark);
+  return 0;
+}
+int pt_history_denoise_adaptive_host(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, const int32_t* counts,
+                                     const float* current_plane, const float* current_var, const PtDenoiseOptions* opt, float* rgb_avg) {
+  ptdn::Job j{};
+  if (pt_history_denoise_adaptive_check("pt_history_denoise_adaptive_host", w, rows, rgb_sum, planes, noise_planes, counts, current_plane, current_var, opt,
+                                        rgb_avg != nullptr, &j))
+    return -1;
+  j.f = {w, rows, rgb_sum, planes, noise_planes, current_plane, current_var};
+  ptdn::denoise_host(j, counts, rgb_avg);
+  return 0;
+}
+int pt_history_denoise_adaptive_variance_host(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, const int32_t* counts,
+                                              const float* current_plane, const float* current_var, const PtDenoiseOptions* opt, float* var_raw, float* var_0) {
+  ptdn::Job j{};
+  if (pt_history_denoise_adaptive_check("pt_history_denoise_adaptive_variance_host", w, rows, rgb_sum, planes, noise_planes, counts, current_plane, current_var, opt,
+                                        var_raw || var_0, &j))
+    return -1;
+  j.f = {w, rows, rgb_sum, planes, noise_planes, current_plane, current_var};
+  ptdn::denoise_host(j, counts, nullptr, var_raw, var_0);
   return 0;
 }
 int pt_denoise_adaptive_host(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, const int32_t* counts,

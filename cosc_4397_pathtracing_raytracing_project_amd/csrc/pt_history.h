@@ -40,7 +40,7 @@
 // the way the fold sums its own estimate.
 //
 // Out of scope (pt_amd.h says the same): pt_group_* (a context's interleaved rows cannot look up their neighbours), feeding the
-// moments into the noise estimate of the blend (noise_value below: the variance kind only), the history round in groups of contexts, a key that uses the carried variance, objects that are added, removed or deformed (rigid and affine motion of an object: PT_HISTORY_MOTION), and correcting the smoothing the bilinear lookup adds — the carried image is a biased estimator, and the carried
+// moments into the noise estimate of the blend (noise_value below: the variance kind only), the history round in groups of contexts, a key of that round that uses the carried variance (threshold rounds keyed by the blend's variance: further down), objects that are added, removed or deformed (rigid and affine motion of an object: PT_HISTORY_MOTION), and correcting the smoothing the bilinear lookup adds — the carried image is a biased estimator, and the carried
 // variance is interpolated linearly (as SVGF interpolates its moments), which overstates it: the lookup's smoothing lowers the true one.
 #pragma once
 #include <cstddef>
@@ -504,6 +504,123 @@ inline double noise_host(size_t npix, const float* noise, float Tf, float Df, fl
     sse += (double)w;
   }
   return sse;
+}
+
+// ── threshold rounds over the blend (pt_history_round_threshold; the kernels: pt_history_threshold.hip) ─────────────────────────
+// The steps above with the sample counts of every pixel, cnt = {T_p, M_p}: Tf = (float)T_p, Df = (float)(M_p - 1) * Tf.  Counts names
+// them for pixel i: the plane `cnt` of the adaptive state, or (cnt == nullptr, the uniform state) the fold's T and M for every pixel.
+struct Counts {
+  const ptad::Cnt* cnt;
+  int32_t T, M;
+};
+struct Divisors {
+  float Tf, Df;
+};
+PT_HD Divisors divisors_of(const Counts& c, size_t i) {
+#pragma clang fp contract(off)
+  const int32_t T = c.cnt ? c.cnt[i].T : c.T, M = c.cnt ? c.cnt[i].M : c.M;
+  const float Tf = (float)T;
+  return Divisors{Tf, (float)(M - 1) * Tf};
+}
+// {vb.xyz, +0} of pixel i: the variance of the blend per channel (pass A; what the capture keeps as VK).  noise: the fold's two
+// planes (N4: any float4 type); Th = C.w of the pixel and vh = VC (C absent: Th = +0, vh all +0).
+template <typename N4, typename P4>
+PT_HD P4 blend_variance_pixel(size_t i, size_t npix, const N4* noise, const Divisors& d, float Th, const P4& vh) {
+  const N4 prev = noise[i], q = noise[npix + i];
+  return P4{blend_variance(sample_variance(prev.x, q.x, d.Tf, d.Df), d.Tf, vh.x, Th), blend_variance(sample_variance(prev.y, q.y, d.Tf, d.Df), d.Tf, vh.y, Th),
+            blend_variance(sample_variance(prev.z, q.z, d.Tf, d.Df), d.Tf, vh.z, Th), 0.0f};
+}
+// Pass A for pixel i: W[i] = (vb.x + vb.y) + vb.z, NE[i] = Tf + Th, the blend's effective sample count.  C, VC: both or nullptr.
+// vb (or nullptr): receives {vb.xyz, +0}.  Returns W[i].
+template <typename N4, typename P4>
+PT_HD float noise_counts_pixel(size_t i, size_t npix, const N4* noise, const Counts& cnt, const P4* C, const P4* VC, float* W, float* NE, P4* vb) {
+#pragma clang fp contract(off)
+  const Divisors d = divisors_of(cnt, i);
+  const float Th = C ? C[i].w : 0.0f;
+  const P4 v = blend_variance_pixel(i, npix, noise, d, Th, VC ? VC[i] : P4{0.0f, 0.0f, 0.0f, 0.0f});
+  const float w = (v.x + v.y) + v.z;
+  W[i] = w;
+  NE[i] = d.Tf + Th;
+  if (vb) vb[i] = v;
+  return w;
+}
+// Pass B for pixel (x, y) of a tile of W x R: ptad::key_pixel's arithmetic over (Wp, NE) in place of (plane0.w, T) — the 3 x 3
+// binomial prefilter of the per-sample variance s = Wp * NE, back in the unit of Wp.
+PT_HD uint32_t key_blend_pixel(int x, int y, int W, int R, const float* Wp, const float* NE) {
+#pragma clang fp contract(off)
+  float num = 0.0f, den = 0.0f;
+  for (int j = -1; j <= 1; ++j) {
+    const int yy = y + j;
+    if (yy < 0 || yy >= R) continue;
+    for (int i = -1; i <= 1; ++i) {
+      const int xx = x + i;
+      if (xx < 0 || xx >= W) continue;
+      const size_t q = (size_t)yy * W + xx;
+      const float g = (j == 0 ? 0.5f : 0.25f) * (i == 0 ? 0.5f : 0.25f);
+      const float s = Wp[q] * NE[q];
+      num = num + g * s;
+      den = den + g;
+    }
+  }
+  const float f = num / den;
+  return ptad::key_bits(f / NE[(size_t)y * W + x]);
+}
+// The blend of pixel i with the pixel's own count: blend_pixel with samples = Tf_p.
+template <typename P4>
+PT_HD void blend_counts_pixel(size_t i, const float* S, const Counts& cnt, const P4* C, float* rgb_avg) {
+  blend_pixel(i, S, divisors_of(cnt, i).Tf, C, rgb_avg);
+}
+// The capture of pixel i with the pixel's own counts: capture_pixel_of<kVariance> with samples = Tf_p and the pixel's divisors, so
+// K0 = {blend, Tf_p + Th}, K1 and K2 the capture's, VK = {vb.xyz, +0} of pass A.
+template <typename P4, typename N4>
+PT_HD void capture_counts_pixel(size_t i, size_t npix, const float* S, const P4* feat, const N4* noise, const Counts& cnt, const P4* C, const P4* VC, P4* K,
+                                P4* VK) {
+  const Divisors d = divisors_of(cnt, i);
+  capture_pixel_of<kPlain>(i, npix, S, feat, C, d.Tf, K, VarCapture<P4>{});
+  VK[i] = blend_variance_pixel(i, npix, noise, d, C ? C[i].w : 0.0f, VC ? VC[i] : P4{0.0f, 0.0f, 0.0f, 0.0f});
+}
+
+// The whole tile on the host.  counts: npix * {T_p, M_p}.  W, NE: npix floats; vb (or nullptr): npix float4.  The estimates are added
+// in pixel order.
+inline double noise_counts_host(size_t npix, const float* noise, const int32_t* counts, const float* C, const float* VC, float* W, float* NE, float* vb) {
+  const Counts cnt{reinterpret_cast<const ptad::Cnt*>(counts), 0, 0};
+  double sse = 0.0;
+  for (size_t i = 0; i < npix; ++i)
+    sse += (double)noise_counts_pixel(i, npix, reinterpret_cast<const F4*>(noise), cnt, reinterpret_cast<const F4*>(C), reinterpret_cast<const F4*>(VC), W, NE,
+                                      reinterpret_cast<F4*>(vb));
+  return sse;
+}
+inline std::vector<uint32_t> keys_blend_host(int W, int R, const float* Wp, const float* NE) {
+  std::vector<uint32_t> key((size_t)W * R);
+  for (int y = 0; y < R; ++y)
+    for (int x = 0; x < W; ++x) key[(size_t)y * W + x] = key_blend_pixel(x, y, W, R, Wp, NE);
+  return key;
+}
+// The selection by threshold on the blend's keys: passes A and B, then ptad::select_threshold_host's steps on those keys.
+inline void select_threshold_blend_host(int W, int R, const float* noise, const int32_t* counts, const float* C, const float* VC, float threshold, int cap,
+                                        int32_t* list, int* above, int* m) {
+  const size_t npix = (size_t)W * R;
+  std::vector<float> Wp(npix), NE(npix);
+  noise_counts_host(npix, noise, counts, C, VC, Wp.data(), NE.data(), nullptr);
+  const std::vector<uint32_t> key = keys_blend_host(W, R, Wp.data(), NE.data());
+  const uint32_t thr = ptad::threshold_bits(threshold);
+  const ptad::Cut top = ptad::cut_host(key, cap);
+  uint32_t n_above = 0;
+  for (uint32_t k : key) n_above += ptad::above_threshold(k, thr) ? 1u : 0u;
+  ptad::scatter_host(key, ptad::threshold_cut(top.tau, top.r, thr), list);
+  *above = (int)n_above;
+  *m = (int)ptad::threshold_length(n_above, (uint32_t)cap);
+}
+inline void blend_counts_host(size_t npix, const float* S, const int32_t* counts, const float* C, float* rgb_avg) {
+  const Counts cnt{reinterpret_cast<const ptad::Cnt*>(counts), 0, 0};
+  for (size_t i = 0; i < npix; ++i) blend_counts_pixel(i, S, cnt, reinterpret_cast<const F4*>(C), rgb_avg);
+}
+inline void capture_counts_host(size_t npix, const float* S, const float* feat, const float* noise, const int32_t* counts, const float* C, const float* VC, float* K,
+                                float* VK) {
+  const Counts cnt{reinterpret_cast<const ptad::Cnt*>(counts), 0, 0};
+  for (size_t i = 0; i < npix; ++i)
+    capture_counts_pixel(i, npix, S, reinterpret_cast<const F4*>(feat), reinterpret_cast<const F4*>(noise), cnt, reinterpret_cast<const F4*>(C),
+                         reinterpret_cast<const F4*>(VC), reinterpret_cast<F4*>(K), reinterpret_cast<F4*>(VK));
 }
 
 // ── the history round (pt_history_round) ─────────────────────────────────────────────────────────────────────────────────

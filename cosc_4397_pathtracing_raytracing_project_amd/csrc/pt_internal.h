@@ -30,6 +30,10 @@ int pt_denoise_launch(hipStream_t stream, const ptdn::Job& j, void* workspace_de
 // the job resolved; a launch reads the planes C and VC from j->div.C and j->div.VC (both or neither), the host loop from j->f.
 int pt_history_denoise_check(const char* who, int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, int groups, int64_t iters,
                              float samples, const float* current_plane, const float* current_var, const PtDenoiseOptions* opt, const float* rgb_avg, ptdn::Job* j);
+// The history form with per-pixel counts (ptdn::Form::HistoryAdaptive, pt_history_denoise_adaptive): the same for it; counts as
+// pt_denoise_adaptive_check reads them, and a launch reads the count plane from j->div.cnt (nullptr: (div.T, div.M) for every pixel).
+int pt_history_denoise_adaptive_check(const char* who, int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, const int32_t* counts,
+                                      const float* current_plane, const float* current_var, const PtDenoiseOptions* opt, bool has_output, ptdn::Job* j);
 // The moments form (ptdn::Form::Moments, pt_history_denoise_ex with PT_HISTORY_MOMENTS): the same for it; no fold, no noise planes.
 // has_output: the caller gave a buffer to write to.
 int pt_history_denoise_moments_check(const char* who, int w, int rows, const float* rgb_sum, const float* planes, float samples, const float* current_plane,
@@ -204,3 +208,19 @@ int pt_history_capture_moments_counted_launch(hipStream_t stream, int pixels, co
                                               float samples, const float* extra_dev, void* kept_dev, const void* current_var_dev, void* kept_var_dev);
 int pt_history_blend_counted_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, float samples, const float* extra_dev, const void* current_dev,
                                     float* rgb_avg_dev);
+
+// Threshold rounds over the blend (pt_history_round_threshold; pt_history_threshold.hip): the history steps with per-pixel counts.
+// counts_dev: the plane `cnt` of the adaptive state, or nullptr: every pixel has the fold's (iters, groups), groups >= 2.
+// pt_history_noise_counts_launch: pass A — W into out_dev's plane (pt_history_noise_plane) and the partial sums in front of it, NE into
+// ne_dev (`pixels` floats); reduce: k_noise_reduce leaves their sum at pt_history_noise_result.  pt_history_key_blend_launch: pass B,
+// the keys of a tile of w x rows from W and NE into key_dev (pt_adaptive_select_keys).  The blend and the capture read Tf_p from the counts;
+// the capture writes K (three planes) and VK.  pt_history_counts_check: what the host and stage forms refuse in their counts.
+int pt_history_noise_counts_launch(hipStream_t stream, int pixels, const void* state_dev, const void* counts_dev, int iters, int groups, const void* current_dev,
+                                   const void* current_var_dev, void* out_dev, float* ne_dev, bool reduce);
+int pt_history_key_blend_launch(hipStream_t stream, int w, int rows, const float* w_dev, const float* ne_dev, uint32_t* key_dev);
+int pt_history_blend_counts_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, const void* counts_dev, int iters, int groups,
+                                   const void* current_dev, float* rgb_avg_dev);
+int pt_history_capture_counts_launch(hipStream_t stream, int pixels, const float* rgb_sum_dev, const float* planes_dev, const void* state_dev,
+                                     const void* counts_dev, int iters, int groups, const void* current_dev, const void* current_var_dev, void* kept_dev,
+                                     void* kept_var_dev);
+int pt_history_counts_check(const char* who, int pixels, const int32_t* counts, const float* current_plane, const float* current_var);

@@ -165,6 +165,13 @@ int pt_ctx_render_until(PtContext* c, int iter_first, int max_iters, int group_i
 
 }  // extern "C"
 
+// Threshold rounds over the blend (further down): the keys of passes A and B into the selection's workspace, and what those rounds refuse
+// after the adaptive rounds' own refusals.
+extern "C" {
+static int history_blend_keys(PtContext& g);
+static int history_threshold_refusal(const PtContext& g, const char* who);
+}
+
 // ---- adaptive sampling: further groups over the noisiest pixels only (csrc/pt_adaptive.hip) -------------------------------
 namespace ptc {
 // A round over m <= capacity pixels on a worker planned for `capacity`: only what follows from N is planned again — the chunks per
@@ -262,24 +269,29 @@ static int render_and_merge(Ctx& g, int iter_first, int group_iters, int m) {
   g.adaptive_rounds += 1;
   g.adaptive_last = std::max<int64_t>(g.adaptive_last, (int64_t)iter_first + group_iters - 1);
   g.samples += (int64_t)group_iters * m;  // (live_rays and the kernel timings stay the parent's own launches')
+  g.hist_noise = g.hist_ne = false;  // the blend's W and NE described the image that was
   return 0;
 }
 
 // A threshold round after its refusals: key and select, the two counts read back (8 bytes and ONE synchronise, which a fixed-fraction
 // round does not have: the list's length decides the launches that follow), then the group over the first m entries unless
-// above <= min_pixels.  *selected: the pixels rendered, 0 when nothing was.
-static int threshold_round(Ctx& g, int iter_first, int group_iters, float threshold, float max_fraction, int min_pixels, int* above, int* selected) {
+// above <= min_pixels.  *selected: the pixels rendered, 0 when nothing was.  blend (pt_history_round_threshold): the keys are those of the
+// blend's variance (history_blend_keys) in place of k_adaptive_key's; everything behind the keys is the same.
+static int threshold_round(Ctx& g, const char* who, bool blend, int iter_first, int group_iters, float threshold, float max_fraction, int min_pixels, int* above,
+                           int* selected) {
   HIP_OK(hipSetDevice(g.device));
   const int W = g.cam.resolution[0];
   if (enter_adaptive(g) || ensure(g, g.d_select, pt_adaptive_select_bytes((size_t)g.N))) return -1;
   const int cap = ptad::list_length((double)max_fraction, g.N);
   if (ensure_worker(g, cap)) return -1;
-  if (pt_adaptive_select_threshold_launch(g.stream, W, g.N / W, static_cast<const float*>(g.d_noise), g.d_acnt, threshold, cap, g.d_select, g.d_list)) return -1;
+  if (blend ? history_blend_keys(g) || pt_adaptive_select_threshold_keys_launch(g.stream, W, g.N / W, threshold, cap, g.d_select, g.d_list)
+            : pt_adaptive_select_threshold_launch(g.stream, W, g.N / W, static_cast<const float*>(g.d_noise), g.d_acnt, threshold, cap, g.d_select, g.d_list))
+    return -1;
   uint32_t result[2] = {0u, 0u};  // above, m
   HIP_OK(hipMemcpyAsync(result, pt_adaptive_select_result(g.d_select, (size_t)g.N), sizeof(result), hipMemcpyDeviceToHost, g.stream));
   HIP_OK(hipStreamSynchronize(g.stream));
   const int m = (int)result[1];
-  if (m < 0 || m > cap || (int)result[0] < m) return pt_fail("pt_adaptive_round_threshold: the selection left %u above, a list of %u (cap %d)", result[0], result[1], cap);
+  if (m < 0 || m > cap || (int)result[0] < m) return pt_fail("%s: the selection left %u above, a list of %u (cap %d)", who, result[0], result[1], cap);
   const bool render = m > 0 && (int)result[0] > min_pixels;
   if (above) *above = (int)result[0];
   if (selected) *selected = render ? m : 0;
@@ -359,24 +371,35 @@ int pt_ctx_adaptive_round(PtContext* c, int iter_first, int group_iters, float f
   return render_and_merge(g, iter_first, group_iters, m);
 }
 
-int pt_ctx_adaptive_round_threshold(PtContext* c, int iter_first, int group_iters, float threshold, float max_fraction, int* above, int* selected) {
-  if (need(c, "pt_adaptive_round_threshold")) return -1;
+// blend: pt_history_round_threshold, the same round keyed by the variance of the blend
+static int round_threshold_entry(PtContext* c, const char* who, bool blend, int iter_first, int group_iters, float threshold, float max_fraction, int* above,
+                                 int* selected) {
+  if (need(c, who)) return -1;
   Ctx& g = *c;
-  if (adaptive_refusal(g, "pt_adaptive_round_threshold", iter_first, group_iters, &max_fraction)) return -1;
-  if (pt_adaptive_check_threshold("pt_adaptive_round_threshold", threshold)) return -1;
-  return threshold_round(g, iter_first, group_iters, threshold, max_fraction, 0, above, selected);
+  if (adaptive_refusal(g, who, iter_first, group_iters, &max_fraction)) return -1;
+  if (pt_adaptive_check_threshold(who, threshold)) return -1;
+  if (blend && history_threshold_refusal(g, who)) return -1;
+  return threshold_round(g, who, blend, iter_first, group_iters, threshold, max_fraction, 0, above, selected);
+}
+int pt_ctx_adaptive_round_threshold(PtContext* c, int iter_first, int group_iters, float threshold, float max_fraction, int* above, int* selected) {
+  return round_threshold_entry(c, "pt_adaptive_round_threshold", false, iter_first, group_iters, threshold, max_fraction, above, selected);
+}
+int pt_ctx_history_round_threshold(PtContext* c, int iter_first, int group_iters, float threshold, float max_fraction, int* above, int* selected) {
+  return round_threshold_entry(c, "pt_history_round_threshold", true, iter_first, group_iters, threshold, max_fraction, above, selected);
 }
 
-int pt_ctx_render_threshold(PtContext* c, int iter_first, int max_iters, int group_iters, float threshold, float max_fraction, int min_pixels,
-                            int* iters_done, int64_t* samples_done, int* above_left) {
-  if (need(c, "pt_render_threshold")) return -1;
+// blend: pt_history_render_threshold, the same driver over rounds keyed by the variance of the blend
+static int render_threshold_entry(PtContext* c, const char* who, bool blend, int iter_first, int max_iters, int group_iters, float threshold, float max_fraction,
+                                  int min_pixels, int* iters_done, int64_t* samples_done, int* above_left) {
+  if (need(c, who)) return -1;
   Ctx& g = *c;
   if (max_iters < 1 || (int64_t)iter_first + max_iters - 1 > INT32_MAX || group_iters < 0 || min_pixels < 0)
-    return pt_fail("pt_render_threshold: iterations %d, +%d in groups of %d until at most %d pixels are above: the count is >= 1, the group >= 0 (0 = a batch of the worker), the pixels >= 0",
-                iter_first, max_iters, group_iters, min_pixels);
+    return pt_fail("%s: iterations %d, +%d in groups of %d until at most %d pixels are above: the count is >= 1, the group >= 0 (0 = a batch of the worker), the pixels >= 0",
+                who, iter_first, max_iters, group_iters, min_pixels);
   // what a round would refuse, apart from the state of the folds, which the uniform groups below establish
-  if (adaptive_refusal(g, "pt_render_threshold", iter_first, group_iters, &max_fraction, false)) return -1;
-  if (pt_adaptive_check_threshold("pt_render_threshold", threshold)) return -1;
+  if (adaptive_refusal(g, who, iter_first, group_iters, &max_fraction, false)) return -1;
+  if (pt_adaptive_check_threshold(who, threshold)) return -1;
+  if (blend && history_threshold_refusal(g, who)) return -1;
   const int cap = ptad::list_length((double)max_fraction, g.N);
   const int group = group_iters ? group_iters : g.worker && g.worker->capacity == cap ? g.worker->K : batch_iters_for(g.opt_iters_per_batch, cap, nullptr);
   int done = 0, above = -1;
@@ -388,9 +411,9 @@ int pt_ctx_render_threshold(PtContext* c, int iter_first, int max_iters, int gro
       samples += (int64_t)n * g.N;
     } else {
       if (!g.adaptive && g.rendered != g.noise_iters && pt_ctx_noise_fold(c)) return -1;  // iterations of the caller's, not yet folded
-      if (adaptive_refusal(g, "pt_render_threshold", iter_first + done, n, &max_fraction)) return -1;
+      if (adaptive_refusal(g, who, iter_first + done, n, &max_fraction)) return -1;
       int m = 0;
-      if (threshold_round(g, iter_first + done, n, threshold, max_fraction, min_pixels, &above, &m)) return -1;
+      if (threshold_round(g, who, blend, iter_first + done, n, threshold, max_fraction, min_pixels, &above, &m)) return -1;
       if (above <= min_pixels) break;  // nothing was rendered
       samples += (int64_t)n * m;
     }
@@ -400,6 +423,16 @@ int pt_ctx_render_threshold(PtContext* c, int iter_first, int max_iters, int gro
   if (samples_done) *samples_done = samples;
   if (above_left) *above_left = above;
   return 0;
+}
+int pt_ctx_render_threshold(PtContext* c, int iter_first, int max_iters, int group_iters, float threshold, float max_fraction, int min_pixels,
+                            int* iters_done, int64_t* samples_done, int* above_left) {
+  return render_threshold_entry(c, "pt_render_threshold", false, iter_first, max_iters, group_iters, threshold, max_fraction, min_pixels, iters_done, samples_done,
+                                above_left);
+}
+int pt_ctx_history_render_threshold(PtContext* c, int iter_first, int max_iters, int group_iters, float threshold, float max_fraction, int min_pixels,
+                                    int* iters_done, int64_t* samples_done, int* above_left) {
+  return render_threshold_entry(c, "pt_history_render_threshold", true, iter_first, max_iters, group_iters, threshold, max_fraction, min_pixels, iters_done,
+                                samples_done, above_left);
 }
 
 int pt_ctx_render_adaptive(PtContext* c, int iter_first, int max_iters, int group_iters, float fraction, float target_db, int* iters_done,
@@ -1208,6 +1241,145 @@ int pt_ctx_history_render_until(PtContext* c, int iter_first, int max_iters, int
   if (psnr_db) *psnr_db = psnr;
   if (view_psnr_db) *view_psnr_db = view_psnr;
   return 0;
+}
+
+// ---- threshold rounds over the blend: the history steps with per-pixel counts (csrc/pt_history_threshold.hip) -----------------------
+// What the rounds refuse after the adaptive rounds' own refusals.
+static int history_threshold_refusal(const PtContext& g, const char* who) { return history_current_variance(g, who); }
+// The counts the steps read: the plane cnt in the adaptive state, else the fold's (T, M) for every pixel.
+static const void* history_counts(const Ctx& g) { return g.adaptive ? g.d_acnt : nullptr; }
+// What the steps need of the folds in either state: at least two, nothing rendered since, counts that fit an int32.
+static int history_counts_folds(const Ctx& g, const char* who) {
+  if (!g.d_noise || g.noise_groups < 1) return pt_fail("%s: nothing has been folded (pt_noise_fold)", who);
+  if (g.noise_groups < 2) return pt_fail("%s: %d group(s) folded; a variance needs at least 2 (pt_noise_fold after each group of iterations)", who, g.noise_groups);
+  if (admit(g, who, kFoldedAll)) return -1;
+  if (g.noise_iters > INT32_MAX) return pt_fail("%s: %lld iterations folded: the per-pixel counts are int32", who, (long long)g.noise_iters);
+  return 0;
+}
+// W, the partial sums and NE: from the first call that needs them on (every word is written before it is read)
+static int history_noise_ensure(Ctx& g) {
+  return ensure(g, g.d_hist_noise, pt_history_noise_bytes((size_t)g.N)) || ensure(g, g.d_hist_ne, (size_t)g.N * sizeof(float)) ? -1 : 0;
+}
+// Pass A; reduce: with the fold's second launch behind it.
+static int history_noise_counts(Ctx& g, bool reduce) {
+  g.hist_noise = g.hist_ne = false;
+  if (pt_history_noise_counts_launch(g.stream, g.N, g.d_noise, history_counts(g), (int)g.noise_iters, g.noise_groups, history_noise_current(g, 0),
+                                     history_noise_current(g, 1), g.d_hist_noise, g.d_hist_ne, reduce))
+    return -1;
+  g.hist_noise = g.hist_ne = true;
+  return 0;
+}
+// Passes A and B of a round (the context is in the adaptive state, the selection's workspace exists).
+static int history_blend_keys(PtContext& g) {
+  const int W = g.cam.resolution[0];
+  if (history_noise_ensure(g) || history_noise_counts(g, false)) return -1;
+  return pt_history_key_blend_launch(g.stream, W, g.N / W, pt_history_noise_plane(g.d_hist_noise, (size_t)g.N), g.d_hist_ne,
+                                     pt_adaptive_select_keys(g.d_select, (size_t)g.N));
+}
+// What the steps refuse in both states, in their order; features: the capture's feature pass.
+static int history_counts_refusal(const Ctx& g, const char* who, bool features) {
+  if (admit(g, who, kNotFailed) || admit(g, who, kWholeRows)) return -1;
+  if (features && (!g.d_feat || !g.feat_fresh)) return pt_fail(kNoFeatures, who);
+  if (admit(g, who, kNoExtras) || history_counts_folds(g, who)) return -1;
+  return history_current_variance(g, who);
+}
+
+int pt_ctx_history_noise_adaptive(PtContext* c, double* sse) {
+  const char* who = "pt_history_noise_adaptive";
+  if (need(c, who)) return -1;
+  Ctx& g = *c;
+  if (history_counts_refusal(g, who, false)) return -1;
+  HIP_OK(hipSetDevice(g.device));
+  if (history_noise_ensure(g) || history_noise_counts(g, true)) return -1;
+  double result = -1.0;
+  HIP_OK(hipMemcpyAsync(&result, pt_history_noise_result(g.d_hist_noise, (size_t)g.N), sizeof(double), hipMemcpyDeviceToHost, g.stream));
+  if (pt_ctx_sync(c)) return -1;
+  if (sse) *sse = result;
+  return 0;
+}
+
+int pt_ctx_readback_history_noise_samples(PtContext* c, float* ne_host) {
+  if (need(c, "pt_readback_history_noise_samples")) return -1;
+  return copy_out(c, "pt_readback_history_noise_samples", ne_host, 1, [&](const float** d) {
+    if (!c->d_hist_ne || !c->hist_ne)
+      return pt_fail("pt_readback_history_noise_samples: no estimate with per-pixel counts has been made since the last pt_clear, move or round (pt_history_noise_adaptive)");
+    return *d = c->d_hist_ne, 0;
+  });
+}
+
+int pt_ctx_history_resolve_adaptive_device(PtContext* c, const float** rgb_dev) {
+  const char* who = "pt_history_resolve_adaptive";
+  if (need(c, who)) return -1;
+  Ctx& g = *c;
+  if (history_counts_refusal(g, who, false)) return -1;
+  if (!rgb_dev) return pt_fail("%s: null buffer", who);
+  HIP_OK(hipSetDevice(g.device));
+  if (ensure(g, g.d_resolved, 3 * (size_t)g.N * sizeof(float))) return -1;
+  if (pt_history_blend_counts_launch(g.stream, g.N, g.d_image, history_counts(g), (int)g.noise_iters, g.noise_groups, history_noise_current(g, 0), g.d_resolved))
+    return -1;
+  *rgb_dev = g.d_resolved;
+  return 0;
+}
+int pt_ctx_history_resolve_adaptive(PtContext* c, float* rgb_avg_host) {
+  const char* who = "pt_history_resolve_adaptive";
+  if (need(c, who)) return -1;
+  if (history_counts_refusal(*c, who, false)) return -1;  // (before the null buffer)
+  return copy_out(c, who, rgb_avg_host, 3, [&](const float** d) { return pt_ctx_history_resolve_adaptive_device(c, d); });
+}
+
+int pt_ctx_history_capture_adaptive(PtContext* c) {
+  const char* who = "pt_history_capture_adaptive";
+  if (need(c, who)) return -1;
+  Ctx& g = *c;
+  if (history_counts_refusal(g, who, true)) return -1;
+  HIP_OK(hipSetDevice(g.device));
+  if (ensure(g, g.d_hist, pt_history_state_bytes((size_t)g.N), Zero::on_stream)) return -1;  // the first capture of the context
+  if (ensure(g, g.d_hist_var, pt_history_variance_bytes((size_t)g.N), Zero::on_stream)) return -1;
+  if (pt_history_capture_counts_launch(g.stream, g.N, g.d_image, reinterpret_cast<const float*>(g.d_feat), g.d_noise, history_counts(g), (int)g.noise_iters,
+                                       g.noise_groups, history_noise_current(g, 0), history_noise_current(g, 1), g.d_hist, history_var_plane(g, 0)))
+    return -1;
+  g.hist_cam = g.cam;
+  if (PtHistoryMotion& hm = g.hist_motion; hm.geoms_stale) hm.geoms = g.camera_base.geoms, hm.geoms_stale = false, hm.fresh = false;  // as in any capture
+  g.hist_kept = true;
+  g.hist_var_kept = PT_HISTORY_VARIANCE;
+  g.fb_kept = false;  // kept without feedback
+  return 0;
+}
+
+// The guided filter over the blend with per-pixel counts (ptdn::Form::HistoryAdaptive): everything it refuses but the null buffer, in
+// pt_history_denoise's order without the adaptive state and `samples`; the job resolved.
+static int history_denoise_adaptive_refusal(const Ctx& g, const char* who, const PtDenoiseOptions* opt, ptdn::Job* j) {
+  if (admit(g, who, kNotFailed) || admit(g, who, kWholeRows) || admit(g, who, kNoExtras)) return -1;
+  if (!g.d_feat || !g.feat_fresh) return pt_fail(kNoFeatures, who);
+  ptdn::Params P{};
+  if (const char* msg = ptdn::resolve(opt, &P, ptdn::kHistorySigmaColor)) return pt_fail("%s: %s", who, msg);
+  if (history_counts_folds(g, who) || history_current_variance(g, who)) return -1;
+  return pt_denoise_resolve(who, ptdn::Form::HistoryAdaptive, 0.0f, g.noise_groups, g.noise_iters, opt, j);
+}
+int pt_ctx_history_denoise_adaptive_device(PtContext* c, const PtDenoiseOptions* opt, const float** rgb_dev) {
+  const char* who = "pt_history_denoise_adaptive";
+  if (need(c, who)) return -1;
+  Ctx& g = *c;
+  ptdn::Job j{};
+  if (history_denoise_adaptive_refusal(g, who, opt, &j)) return -1;
+  if (!rgb_dev) return pt_fail("%s: null buffer", who);
+  HIP_OK(hipSetDevice(g.device));
+  if (ensure(g, g.d_denoise, pt_denoise_workspace_bytes((size_t)g.N))) return -1;  // the first denoise call of the context, of any kind
+  const int W = g.cam.resolution[0];
+  j.f = {W, g.N / W, g.d_image, reinterpret_cast<const float*>(g.d_feat), static_cast<const float*>(g.d_noise)};
+  j.div.cnt = static_cast<const ptad::Cnt*>(history_counts(g));
+  if (g.hist_current) {
+    j.div.C = reinterpret_cast<const ptdn::V4*>(history_plane(g, pthi::kKeptPlanes));
+    j.div.VC = reinterpret_cast<const ptdn::V4*>(history_var_plane(g, 1));
+  }
+  return pt_denoise_launch(g.stream, j, g.d_denoise, rgb_dev);
+}
+int pt_ctx_history_denoise_adaptive(PtContext* c, const PtDenoiseOptions* opt, float* rgb_avg_host) {
+  const char* who = "pt_history_denoise_adaptive";
+  if (need(c, who)) return -1;
+  ptdn::Job j{};
+  if (history_denoise_adaptive_refusal(*c, who, opt, &j)) return -1;  // (before the null buffer)
+  return copy_out(c, who, rgb_avg_host, 3, [&](const float** d) { return pt_ctx_history_denoise_adaptive_device(c, opt, d); });
 }
 
 int pt_ctx_history_drop(PtContext* c) {

@@ -3,7 +3,7 @@
 // state.iterations iterations, write the PNG saveImage() would write.  Flags exist only because
 // the reference takes resolution, iteration count and depth from the scene file (scene.cpp:103-114).
 //
-//   pt_render SCENE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] [--orbit N [--device-tables] [--move G:DX,DY,DZ [--orbit-still]] [--reproject [--history-cap C] [--denoise-history [--history-moments [--history-feedback [--feedback-level L] [--feedback-variance V]]]] [--history-extra G [--history-min M] [--history-extra-cap F]] [--history-probe [--probe-radius R] [--probe-gain X]]]]
+//   pt_render SCENE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] [--orbit N [--device-tables] [--move G:DX,DY,DZ [--orbit-still]] [--reproject [--history-cap C] [--denoise-history [--history-moments [--history-feedback [--feedback-level L] [--feedback-variance V]]] [--history-threshold E [--history-threshold-cap F] [--history-threshold-min-pixels P] [--history-threshold-group G]]] [--history-extra G [--history-min M] [--history-extra-cap F]] [--history-probe [--probe-radius R] [--probe-gain X]]]]
 //                       [--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa]
 //                       [--preview N] [--convergence N | --reference FILE.pfm] [--clean-db X] [--features]
 //                       [--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]]
@@ -84,6 +84,12 @@
 // per view.  A frame's order becomes features, lookup, render, resolve, filter, capture, move, with the iterations the view took in
 // `samples`; the same output names.  --history-until-group G: the iterations per group (default ceil(spp / 4); 0 = one batch).  Prints
 // per frame `until: frame f: <iterations> iterations, <groups> groups, estimated PSNR of the blend <x> dB (the view alone <y> dB)`.
+// --history-threshold E (with --denoise-history; excludes --history-until-db, --history-moments, --history-extra, --history-probe,
+// --history-feedback and --gpus / --devices): a view is features, lookup, then pt_history_render_threshold — uniform groups until two are
+// folded, then rounds over the pixels whose blend's standard error is above E, at most the fraction --history-threshold-cap F (default
+// 0.25) of them, until at most --history-threshold-min-pixels P (default 0) are above or --spp iteration numbers are used, in groups of
+// --history-threshold-group G (default ceil(spp / 4); 0 = one batch) — then pt_history_resolve_adaptive, pt_history_denoise_adaptive and
+// pt_history_capture_adaptive; the same output names, the raw frame resolved by every pixel's own count.  Prints `threshold: frame f: ...`.
 // --history-extra G (with --reproject, alone or with --denoise-history --history-moments; refused with --denoise-history alone, whose
 // variance comes from the folds and knows nothing of extra samples): between the lookup and the resolve pt_history_round gives the
 // pixels whose carried weight is below --history-min M (default 4) G further iterations, --history-extra-cap F of the frame at the
@@ -116,7 +122,7 @@
 int main(int argc, char** argv) {
   if (argc < 2) {
     std::printf("Usage: %s SCENEFILE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] "
-                "[--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa] [--orbit N [--device-tables] [--reproject [--history-cap C] [--denoise-history [--history-moments [--history-feedback [--feedback-level L] [--feedback-variance V]]]] [--history-extra G [--history-min M] [--history-extra-cap F]] [--history-probe [--probe-radius R] [--probe-gain X]]] [--move G:DX,DY,DZ [--orbit-still]]] [--preview N] "
+                "[--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa] [--orbit N [--device-tables] [--reproject [--history-cap C] [--denoise-history [--history-moments [--history-feedback [--feedback-level L] [--feedback-variance V]]] [--history-threshold E [--history-threshold-cap F] [--history-threshold-min-pixels P] [--history-threshold-group G]]] [--history-extra G [--history-min M] [--history-extra-cap F]] [--history-probe [--probe-radius R] [--probe-gain X]]] [--move G:DX,DY,DZ [--orbit-still]]] [--preview N] "
                 "[--convergence N | --reference FILE.pfm] [--clean-db X] [--features] "
                 "[--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]] [--denoise-guided] [--until-db X [--until-group G] [--adaptive F [--denoise-adaptive]]] "
                 "[--adaptive-threshold E [--adaptive-cap F] [--adaptive-min-pixels P] [--until-group G] [--denoise-adaptive]]\n", argv[0]);
@@ -147,6 +153,10 @@ int main(int argc, char** argv) {
   PtHistoryProbeOptions probe_opt{};                // --probe-radius R, --probe-gain X (0: the defaults)
   bool probe_opt_given = false;
   bool hist_until = false, hist_until_group_given = false;  // --history-until-db X, --history-until-group G
+  bool hist_threshold = false;                      // --history-threshold E: threshold rounds keyed by the variance of the blend
+  float hist_threshold_e = 0.0f, hist_threshold_cap = 0.25f;  // ... --history-threshold-cap F
+  int hist_threshold_min_pixels = 0, hist_threshold_group = 0;  // ... --history-threshold-min-pixels P, --history-threshold-group G
+  bool hist_threshold_cap_given = false, hist_threshold_min_given = false, hist_threshold_group_given = false;
   float hist_until_db = 0.0f;
   int hist_until_group = 0;
   bool until = false, until_group_given = false;
@@ -201,6 +211,34 @@ int main(int argc, char** argv) {
         return 1;
       }
       hist_until_group = (int)v, hist_until_group_given = true;
+    }
+    else if (!std::strcmp(argv[i], "--history-threshold") && i + 1 < argc) {
+      char* end = nullptr;
+      hist_threshold_e = std::strtof(argv[++i], &end);
+      if (end == argv[i] || *end || !std::isfinite(hist_threshold_e) || hist_threshold_e < 0.0f) {
+        std::fprintf(stderr, "--history-threshold wants the standard error of the blend above which a pixel gets further samples, finite and >= 0\n");
+        return 1;
+      }
+      hist_threshold = true;
+    } else if (!std::strcmp(argv[i], "--history-threshold-cap") && i + 1 < argc) {
+      char* end = nullptr;
+      hist_threshold_cap = std::strtof(argv[++i], &end);
+      if (end == argv[i] || *end || !(hist_threshold_cap > 0.0f && hist_threshold_cap <= 1.0f)) {
+        std::fprintf(stderr, "--history-threshold-cap wants the largest fraction of the pixels a round renders, in (0, 1]\n");
+        return 1;
+      }
+      hist_threshold_cap_given = true;
+    } else if ((!std::strcmp(argv[i], "--history-threshold-min-pixels") || !std::strcmp(argv[i], "--history-threshold-group")) && i + 1 < argc) {
+      const bool is_group = !std::strcmp(argv[i], "--history-threshold-group");
+      char* end = nullptr;
+      const long v = std::strtol(argv[++i], &end, 10);
+      if (end == argv[i] || *end || v < 0 || v > INT32_MAX) {
+        std::fprintf(stderr, "%s\n", is_group ? "--history-threshold-group wants the iterations per group and round of --history-threshold, G >= 0 (0 = one batch)"
+                                              : "--history-threshold-min-pixels wants the pixels above the threshold at which a view stops, P >= 0");
+        return 1;
+      }
+      if (is_group) hist_threshold_group = (int)v, hist_threshold_group_given = true;
+      else hist_threshold_min_pixels = (int)v, hist_threshold_min_given = true;
     }
     else if ((!std::strcmp(argv[i], "--feedback-level") || !std::strcmp(argv[i], "--feedback-variance")) && i + 1 < argc) {
       const bool is_level = !std::strcmp(argv[i], "--feedback-level");
@@ -400,6 +438,21 @@ int main(int argc, char** argv) {
   }
   if (dn_adaptive && !(adaptive > 0.0f) && !by_threshold) {
     std::fprintf(stderr, "--denoise-adaptive wants --adaptive or --adaptive-threshold (the filter of an adaptively sampled image)\n");
+    return 1;
+  }
+  if ((hist_threshold_cap_given || hist_threshold_min_given || hist_threshold_group_given) && !hist_threshold) {
+    std::fprintf(stderr, "%s wants --history-threshold E (the threshold rounds it configures)\n",
+                 hist_threshold_cap_given ? "--history-threshold-cap" : hist_threshold_min_given ? "--history-threshold-min-pixels" : "--history-threshold-group");
+    return 1;
+  }
+  if (hist_threshold && !dn_history) {
+    std::fprintf(stderr, "--history-threshold wants --orbit N --reproject --denoise-history (its rounds are keyed by the variance the history carries)\n");
+    return 1;
+  }
+  if (hist_threshold && (hist_until || hist_moments || history_extra || history_probe || hist_feedback || gpus >= 0 || !device_list.empty())) {
+    std::fprintf(stderr, "--history-threshold excludes %s: threshold rounds over the blend are built for the variance kind of history on one context\n",
+                 hist_until ? "--history-until-db" : hist_feedback ? "--history-feedback" : history_probe ? "--history-probe" : history_extra ? "--history-extra"
+                 : hist_moments ? "--history-moments" : "--gpus / --devices");
     return 1;
   }
   if (hist_until_group_given && !hist_until) {
@@ -710,7 +763,14 @@ int main(int argc, char** argv) {
       int frame_iters = iters;  // --history-until-db: what the view took
       int until_groups = 0;
       float until_psnr = -1.0f, until_view_psnr = -1.0f;
-      if (hist_until) {  // the lookup needs the view's first hits only: features, lookup, then groups until the BLEND is clean
+      int64_t thr_samples = 0;  // --history-threshold: the pixel-samples of the view, the pixels above at the last count, the rounds
+      int thr_above = -1, thr_groups = 0;
+      if (hist_threshold) {  // features, lookup, then uniform groups until two are folded and rounds over the pixels whose BLEND is above the threshold
+        render_failed = pt_render_features(1, 1) || (f > 0 && pt_history_reproject_ex(&hopt, PT_HISTORY_VARIANCE | (move ? PT_HISTORY_MOTION : 0u))) ||
+                        pt_history_render_threshold(iter_first, iters, hist_threshold_group_given ? hist_threshold_group : fold_group, hist_threshold_e,
+                                                    hist_threshold_cap, hist_threshold_min_pixels, &frame_iters, &thr_samples, &thr_above) ||
+                        pt_get_noise(nullptr, &thr_groups, nullptr) || pt_resolve(scene->state.image.data());
+      } else if (hist_until) {  // the lookup needs the view's first hits only: features, lookup, then groups until the BLEND is clean
         render_failed = pt_render_features(1, 1) || (f > 0 && pt_history_reproject_ex(&hopt, PT_HISTORY_VARIANCE | (move ? PT_HISTORY_MOTION : 0u))) ||
                         pt_history_render_until(iter_first, iters, hist_until_group_given ? hist_until_group : fold_group, hist_until_db, &frame_iters, &until_psnr,
                                                 &until_view_psnr) ||
@@ -735,9 +795,10 @@ int main(int argc, char** argv) {
       char tag[32];
       std::snprintf(tag, sizeof tag, ".orbit%03d", f);
       const std::string frame = base + tag;
-      if (pt_save_png((frame + ".png").c_str(), scene->state.image.data(), W, H, (float)frame_iters) == 0) std::printf("Saved %s.png.\n", frame.c_str());
-      if (pfm && pt_save_pfm((frame + ".pfm").c_str(), scene->state.image.data(), W, H, (float)frame_iters) == 0) std::printf("Saved %s.pfm.\n", frame.c_str());
-      if (hdr && pt_save_hdr((frame + ".hdr").c_str(), scene->state.image.data(), W, H, (float)frame_iters) == 0) std::printf("Saved %s.hdr.\n", frame.c_str());
+      const float frame_scale = hist_threshold ? 1.0f : (float)frame_iters;  // --history-threshold: the image was resolved by every pixel's own count
+      if (pt_save_png((frame + ".png").c_str(), scene->state.image.data(), W, H, frame_scale) == 0) std::printf("Saved %s.png.\n", frame.c_str());
+      if (pfm && pt_save_pfm((frame + ".pfm").c_str(), scene->state.image.data(), W, H, frame_scale) == 0) std::printf("Saved %s.pfm.\n", frame.c_str());
+      if (hdr && pt_save_hdr((frame + ".hdr").c_str(), scene->state.image.data(), W, H, frame_scale) == 0) std::printf("Saved %s.hdr.\n", frame.c_str());
       if (reproject) {  // the view's first hits, the history looked up from them, the blend written, the blend kept for the next view
         const uint32_t hflags = !dn_history     ? 0u  // 0: the plain calls
                                 : hist_feedback ? PT_HISTORY_MOMENTS | PT_HISTORY_FEEDBACK
@@ -745,8 +806,15 @@ int main(int argc, char** argv) {
                                                 : PT_HISTORY_VARIANCE;
         int fresh = 0, selected = 0;  // --history-extra: the round, between the lookup and the resolve
         int probes = 0, changed = 0, skipped = 0;  // --history-probe: the check after the lookup, the keep before the round
-        // (--history-until-db: the features and the lookup came before the render)
-        if ((!hist_until && (pt_render_features(1, 1) || (f > 0 && pt_history_reproject_ex(&hopt, hflags | (move ? PT_HISTORY_MOTION : 0u))))) ||
+        double thr_sse = -1.0;
+        // (--history-until-db, --history-threshold: the features and the lookup came before the render)
+        if (hist_threshold) {  // the steps that read every pixel's own count
+          if (pt_history_resolve_adaptive(carried.data()) || pt_history_denoise_adaptive(&dn_opt, filtered.data()) || pt_history_noise_adaptive(&thr_sse) ||
+              pt_history_capture_adaptive() || pt_readback_history(nullptr, current.data())) {
+            std::fprintf(stderr, "HIP error (pt_history): %s\n", pt_last_error());
+            return EXIT_FAILURE;
+          }
+        } else if ((!hist_until && (pt_render_features(1, 1) || (f > 0 && pt_history_reproject_ex(&hopt, hflags | (move ? PT_HISTORY_MOTION : 0u))))) ||
             (history_probe && ((f > 0 && pt_history_probe_check(&probe_opt, &probes, &changed, &skipped)) || pt_history_probe_keep(iter_first, iters, f % 9))) ||
             (history_extra && pt_history_round(iter_first + iters, history_extra, &round_opt, &fresh, &selected)) || pt_history_resolve((float)frame_iters, carried.data()) ||
             (dn_history && (hist_feedback  ? pt_history_denoise_feedback((float)frame_iters, &dn_opt, &fb_opt, filtered.data())
@@ -764,6 +832,10 @@ int main(int argc, char** argv) {
         if (hist_until)
           std::printf("until: frame %d: %d iterations, %d groups, estimated PSNR of the blend %.9g dB (the view alone %.9g dB)\n", f, frame_iters, until_groups,
                       (double)until_psnr, (double)until_view_psnr);
+        if (hist_threshold)
+          std::printf("threshold: frame %d: %d iterations, %d rounds, %lld samples (%.4f of uniform), %d pixels above, estimated PSNR of the blend %.9g dB\n", f,
+                      frame_iters, std::max(0, thr_groups - 2), (long long)thr_samples, (double)thr_samples / ((double)iters * W * H), thr_above,
+                      (double)pt_psnr_from_sse(thr_sse, W * H));
         if (history_probe) std::printf("probe: frame %d: %d of %d probes changed, %d skipped\n", f, changed, probes, skipped);
         if (history_extra) std::printf("history: frame %d: %d extra over %d of %d fresh pixels\n", f, history_extra, selected, fresh);
         if (pt_save_png((frame + ".reprojected.png").c_str(), carried.data(), W, H, 1.0f) == 0) std::printf("Saved %s.reprojected.png.\n", frame.c_str());

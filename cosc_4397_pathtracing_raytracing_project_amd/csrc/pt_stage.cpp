@@ -659,6 +659,130 @@ int pt_stage_history_noise(int pixels, const float* noise_planes, int groups, in
   return 0;
 }
 
+// ---- threshold rounds over the blend on caller-supplied host arrays (pt_history_threshold.hip; the *_host twins' arguments) ----------
+namespace {
+// counts, C and VC on the device; C and VC stay nullptr when absent
+struct BlendInputs {
+  int32_t* counts = nullptr;
+  float *cur = nullptr, *var = nullptr;
+};
+int blend_inputs(Scratch& sc, const char* who, size_t n, const int32_t* counts, const float* current_plane, const float* current_var, BlendInputs* in) {
+  if (device_copy(sc, who, counts, 2 * n, &in->counts)) return -1;
+  if (current_plane && (device_copy(sc, who, current_plane, 4 * n, &in->cur) || device_copy(sc, who, current_var, 4 * n, &in->var))) return -1;
+  return 0;
+}
+}  // namespace
+
+// Pass A and the reduction: W, NE and the double.
+int pt_stage_history_noise_adaptive(int pixels, const float* noise_planes, const int32_t* counts, const float* current_plane, const float* current_var,
+                                    float* w_out, float* ne_out, double* sse) {
+  const char* who = "pt_stage_history_noise_adaptive";
+  if (need(default_context(), who)) return -1;
+  Ctx& g = *default_context();
+  if (pixels <= 0 || pixels > (1 << 30) || !noise_planes) return pt_fail("%s: bad argument", who);
+  if (pt_history_counts_check(who, pixels, counts, current_plane, current_var)) return -1;
+  HIP_OK(hipSetDevice(g.device));
+  Scratch sc;
+  const size_t n = (size_t)pixels;
+  float* d_noise = nullptr;
+  BlendInputs in;
+  char* d_out = sc.get<char>(pt_history_noise_bytes(n));
+  float* d_ne = sc.get<float>(n);
+  if (!d_out || !d_ne) return pt_fail("%s: out of device memory", who);
+  if (device_copy(sc, who, noise_planes, 4 * PT_NOISE_PLANES * n, &d_noise) || blend_inputs(sc, who, n, counts, current_plane, current_var, &in)) return -1;
+  HIP_OK(hipMemsetAsync(d_out, 0xff, pt_history_noise_bytes(n), g.stream));  // a word nobody wrote shows as a NaN
+  HIP_OK(hipMemsetAsync(d_ne, 0xff, n * sizeof(float), g.stream));
+  if (pt_history_noise_counts_launch(g.stream, pixels, d_noise, in.counts, 0, 0, in.cur, in.var, d_out, d_ne, true)) return -1;
+  HIP_OK(hipStreamSynchronize(g.stream));
+  if (w_out) HIP_OK(hipMemcpy(w_out, pt_history_noise_plane(d_out, n), n * sizeof(float), hipMemcpyDeviceToHost));
+  if (ne_out) HIP_OK(hipMemcpy(ne_out, d_ne, n * sizeof(float), hipMemcpyDeviceToHost));
+  if (sse) HIP_OK(hipMemcpy(sse, pt_history_noise_result(d_out, n), sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// Passes A and B into the selection's workspace, then the round's own selection launches.
+int pt_stage_history_select_threshold_blend(int w, int rows, const float* noise_planes, const int32_t* counts, const float* current_plane, const float* current_var,
+                                            float threshold, int cap, int32_t* list, int* above, int* m) {
+  const char* who = "pt_stage_history_select_threshold_blend";
+  if (need(default_context(), who)) return -1;
+  Ctx& g = *default_context();
+  if (pt_adaptive_check_select(who, w, rows, noise_planes, counts, cap, list)) return -1;
+  if (pt_adaptive_check_threshold(who, threshold)) return -1;
+  if (!above || !m) return pt_fail("%s: bad argument", who);
+  if (pt_history_counts_check(who, w * rows, counts, current_plane, current_var)) return -1;
+  HIP_OK(hipSetDevice(g.device));
+  Scratch sc;
+  const size_t n = (size_t)w * rows;
+  float* d_noise = nullptr;
+  BlendInputs in;
+  char* d_out = sc.get<char>(pt_history_noise_bytes(n));
+  float* d_ne = sc.get<float>(n);
+  char* d_ws = sc.get<char>(pt_adaptive_select_bytes(n));
+  int32_t* d_list = sc.get<int32_t>((size_t)cap);
+  if (!d_out || !d_ne || !d_ws || !d_list) return pt_fail("%s: out of device memory", who);
+  if (device_copy(sc, who, noise_planes, 4 * PT_NOISE_PLANES * n, &d_noise) || blend_inputs(sc, who, n, counts, current_plane, current_var, &in)) return -1;
+  HIP_OK(hipMemset(d_list, 0xff, (size_t)cap * sizeof(int32_t)));  // an entry nobody wrote shows as -1
+  if (pt_history_noise_counts_launch(g.stream, (int)n, d_noise, in.counts, 0, 0, in.cur, in.var, d_out, d_ne, false)) return -1;
+  if (pt_history_key_blend_launch(g.stream, w, rows, pt_history_noise_plane(d_out, n), d_ne, pt_adaptive_select_keys(d_ws, n))) return -1;
+  if (pt_adaptive_select_threshold_keys_launch(g.stream, w, rows, threshold, cap, d_ws, d_list)) return -1;
+  HIP_OK(hipStreamSynchronize(g.stream));
+  uint32_t result[2] = {0u, 0u};
+  HIP_OK(hipMemcpy(result, pt_adaptive_select_result(d_ws, n), sizeof(result), hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(list, d_list, (size_t)cap * sizeof(int32_t), hipMemcpyDeviceToHost));  // all cap entries: those behind m must still be -1
+  *above = (int)result[0], *m = (int)result[1];
+  return 0;
+}
+
+// The capture and the blend: K, VK and (rgb_avg, may be NULL) the resolve.
+int pt_stage_history_capture_adaptive(int pixels, const float* rgb_sum, const float* feature_planes, const float* noise_planes, const int32_t* counts,
+                                      const float* current_plane, const float* current_var, float* kept_planes, float* kept_var, float* rgb_avg) {
+  const char* who = "pt_stage_history_capture_adaptive";
+  if (need(default_context(), who)) return -1;
+  Ctx& g = *default_context();
+  if (pixels <= 0 || pixels > (1 << 30) || !rgb_sum || !feature_planes || !noise_planes || !kept_planes || !kept_var) return pt_fail("%s: bad argument", who);
+  if (pt_history_counts_check(who, pixels, counts, current_plane, current_var)) return -1;
+  HIP_OK(hipSetDevice(g.device));
+  Scratch sc;
+  const size_t n = (size_t)pixels;
+  float *d_img = nullptr, *d_feat = nullptr, *d_noise = nullptr;
+  BlendInputs in;
+  float* d_kept = sc.get<float>(4 * PT_HISTORY_KEPT_PLANES * n);
+  float* d_kvar = sc.get<float>(4 * n);
+  float* d_avg = sc.get<float>(3 * n);
+  if (!d_kept || !d_kvar || !d_avg) return pt_fail("%s: out of device memory", who);
+  if (device_copy(sc, who, rgb_sum, 3 * n, &d_img) || device_copy(sc, who, feature_planes, 4 * PT_FEATURE_PLANES * n, &d_feat) ||
+      device_copy(sc, who, noise_planes, 4 * PT_NOISE_PLANES * n, &d_noise) || blend_inputs(sc, who, n, counts, current_plane, current_var, &in))
+    return -1;
+  HIP_OK(hipMemsetAsync(d_kept, 0xff, 4 * PT_HISTORY_KEPT_PLANES * n * sizeof(float), g.stream));
+  HIP_OK(hipMemsetAsync(d_kvar, 0xff, 4 * n * sizeof(float), g.stream));
+  HIP_OK(hipMemsetAsync(d_avg, 0xff, 3 * n * sizeof(float), g.stream));
+  if (pt_history_capture_counts_launch(g.stream, pixels, d_img, d_feat, d_noise, in.counts, 0, 0, in.cur, in.var, d_kept, d_kvar)) return -1;
+  if (pt_history_blend_counts_launch(g.stream, pixels, d_img, in.counts, 0, 0, in.cur, d_avg)) return -1;
+  HIP_OK(hipStreamSynchronize(g.stream));
+  HIP_OK(hipMemcpy(kept_planes, d_kept, 4 * PT_HISTORY_KEPT_PLANES * n * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(kept_var, d_kvar, 4 * n * sizeof(float), hipMemcpyDeviceToHost));
+  if (rgb_avg) HIP_OK(hipMemcpy(rgb_avg, d_avg, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// The filter over the blend with per-pixel counts (pt_history_denoise_adaptive_host's arguments)
+int pt_stage_history_denoise_adaptive(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, const int32_t* counts,
+                                      const float* current_plane, const float* current_var, const PtDenoiseOptions* opt, float* rgb_avg) {
+  const char* who = "pt_stage_history_denoise_adaptive";
+  if (need(default_context(), who)) return -1;
+  Ctx& g = *default_context();
+  if (rows >= 32768) return pt_fail("%s: a frame of %d x %d pixels is not supported", who, w, rows);
+  ptdn::Job j{};
+  if (pt_history_denoise_adaptive_check(who, w, rows, rgb_sum, planes, noise_planes, counts, current_plane, current_var, opt, rgb_avg != nullptr, &j)) return -1;
+  Scratch in_sc;  // (filter_stage synchronises before it returns)
+  BlendInputs in;
+  HIP_OK(hipSetDevice(g.device));
+  if (blend_inputs(in_sc, who, (size_t)w * rows, counts, current_plane, current_var, &in)) return -1;
+  j.div.cnt = reinterpret_cast<const ptad::Cnt*>(in.counts);
+  j.div.C = reinterpret_cast<const ptdn::V4*>(in.cur), j.div.VC = reinterpret_cast<const ptdn::V4*>(in.var);
+  return filter_stage_job(g, who, w, rows, rgb_sum, planes, noise_planes, rgb_avg, j);
+}
+
 // The partition's kernels on caller-supplied host arrays (pt_group_partition_host's arguments).  The list's length reaches the kernels
 // as it does in a group's round: in the second of two words on the device.
 int pt_stage_group_partition(int w, int h, int n, const int32_t* list, int m, int32_t* parts, int32_t* counts) {

@@ -1028,7 +1028,7 @@ int pt_history_denoise_moments_host(int w, int rows, const float* rgb_sum, const
  *        lookup: with C absent every non-emitter hit pixel is fresh (the first view).  fresh / selected may be NULL.
  * What it buys: README "History-guided sampling" (tests/test_history_round_sim.py).
  * Groups of contexts: "history in groups" below (pt_group_history_round).  Out of scope: a noise estimate of the blend while E is present (pt_history_noise refuses); scaling the spatial variance estimate by a pixel's extras;
- * a key that uses rh or the carried variance; motion of anything but the camera. */
+ * a key that uses rh (one that uses the carried variance: "threshold rounds over the blend" below); motion of anything but the camera. */
 #define PT_HISTORY_ROUND_MIN_HISTORY 4.0f /* the default of PtHistoryRoundOptions.min_history, in samples */
 typedef struct PtHistoryRoundOptions { /* every field: 0 = the default */
   float min_history;  /* default 4.0 (samples): finite and > 0 */
@@ -1289,8 +1289,8 @@ int pt_history_denoise_feedback_host(int w, int rows, const float* rgb_sum, cons
  * Out of scope: the moments kind (PT_HISTORY_MOMENTS) — its estimate exists only for pixels with four views of history (none in the
  *   first three views of an orbit at 1 spp; 2000 - 2316 of 5184 pixels from view 3 on), reads 2.2 - 3.1 x high there, and the pixels
  *   without one hold 15 - 31 % of the blend's squared error; rendering longer inside a view raises rb towards 1 and takes estimates
- *   away, so a stopping rule does not fit that kind.  Groups of contexts; a per-pixel threshold round over vb (the adaptive state and
- *   the history refuse each other); correcting the blend's bias; lowering the floor of two folds per view. */
+ *   away, so a stopping rule does not fit that kind.  Groups of contexts; correcting the blend's bias; lowering the floor of two
+ *   folds per view.  (A per-pixel threshold round over vb: "threshold rounds over the blend" below.) */
 int pt_history_noise(float samples, uint32_t flags, double* sse);
 int pt_readback_history_noise(float* w_host); /* pixel_count floats */
 int pt_history_render_until(int iter_first, int max_iters, int group_iters, float target_db, int* iters_done, float* psnr_db, float* view_psnr_db);
@@ -1299,6 +1299,89 @@ int pt_history_render_until(int iter_first, int max_iters, int group_iters, floa
  * bit; the host adds in pixel order, so the double may differ from the device's in the last bits, as pt_noise_fold_host's does. */
 int pt_history_noise_host(int pixels, const float* noise_planes, int groups, int64_t iters, float samples, const float* current_plane,
                           const float* current_var, float* w_out, double* sse);
+
+/* ---- threshold rounds over the blend: the history in the adaptive state.  pt_adaptive_round_threshold keys a pixel by the variance of
+ * its own samples; a view that starts with a carried history is clean nearly everywhere, and pt_history_render_until can answer the
+ * exceptions (disocclusions, mirrors, the frame's edge) with whole-frame iterations only.  Here a threshold round is keyed by the
+ * variance of the BLEND, and the history steps that follow it read per-pixel counts, so a view sampled that way can be resolved and
+ * captured and the next view can carry it on.  The variance kind only.  Opt-in: a renderer that never calls these functions allocates
+ * and launches nothing new, and every other call keeps its kernels, memory, launches, results and refusals.  Specified like the rest
+ * of the history (float32, separate IEEE operations in the order written, no contraction, correctly rounded division, denormals kept;
+ * one implementation for kernels and host loops: csrc/pt_history.h Counts .. capture_counts_pixel; kernels: csrc/pt_history_threshold.hip).
+ * Notation: S the SUM image; prev, q the two noise planes; cnt = {T_p, M_p} (the uniform state: the fold's (T, M) in every pixel);
+ * C = {h, Th}, VC = {vh, +0} (absent: all +0).
+ * Pass A (k_history_noise_counts), per tile pixel p and component k:
+ *            Tf = (float)T_p;  Df = (float)(M_p - 1) * Tf
+ *            vn_k = sample_variance(prev_k, q_k, Tf, Df);  vb_k = blend_variance(vn_k, Tf, vh_k, Th)
+ *            W[p] = (vb_x + vb_y) + vb_z   (pt_history_noise's plane);   NE[p] = Tf + Th   (the blend's effective sample count, what a
+ *            capture writes to K0.w)
+ * pt_history_noise_adaptive(&sse): pass A, then the fold's reduction exactly as pt_history_noise (one double per
+ *   PT_NOISE_PIXELS_PER_PARTIAL pixels from the fixed tree, added in index order, no atomics); one synchronise; sse may be NULL.  Valid
+ *   in both states.  pt_readback_history_noise returns W as before, pt_readback_history_noise_samples NE.  NE is a plane of its own,
+ *   4 * N bytes, allocated by the first call that needs it and part of PtStats.device_bytes from then on (the first call also
+ *   allocates pt_history_noise's buffer if no estimate was made before).  W and NE become absent on pt_clear, pt_set_camera[_ex] and
+ *   pt_set_geoms, and after any adaptive round that rendered: the image they described is gone.
+ *   Refusals, in this order: no renderer, or a failed context; a striped or ragged tile; the extra plane E present; nothing folded,
+ *   fewer than 2 groups folded, iterations rendered since the last fold; C present with VC absent or of the moments kind.
+ * Pass B (k_history_key_blend): pt_adaptive_round's key over (W, NE) in place of (plane 0's w, T) — the 3 x 3 binomial prefilter over
+ *   the per-sample variance s(q) = W[q] * NE[q], rows outer, taps outside the tile skipped, num = num + g * s, den = den + g;
+ *   key = (num / den) / NE[p], a NaN becomes 0xffffffff.  With vh ~ sigma^2 / Th, vb * (T + Th) ~ sigma^2: the one quantity that
+ *   neighbours with different counts and different histories share.
+ * pt_history_round_threshold(iter_first, group_iters, threshold, max_fraction, &above, &selected) and
+ * pt_history_render_threshold(iter_first, max_iters, group_iters, threshold, max_fraction, min_pixels, &iters_done, &samples_done,
+ *   &above_left): pt_adaptive_round_threshold and pt_render_threshold word for word, with the key of passes A and B in place of the
+ *   adaptive key: the same entry into the adaptive state, worker, selection (thr = threshold * threshold), one synchronise for 8
+ *   bytes, render and merge, counters and PtStats.samples; the driver's uniform groups and folds are pt_render_threshold's.
+ *   Refusals: what those two refuse, in their order (E included), under these names; then C present with VC absent or of the moments
+ *   kind.  C absent is allowed: the calls are then the adaptive ones, bit for bit.
+ *   pt_history_reproject_ex keeps refusing the adaptive state, so a view goes: pt_set_camera, pt_render_features(1, 1),
+ *   pt_history_reproject_ex(PT_HISTORY_VARIANCE), pt_history_render_threshold, pt_history_denoise_adaptive,
+ *   pt_history_capture_adaptive; the move then leaves the adaptive state as pt_clear does.  C and VC stay valid through the rounds.
+ * pt_history_resolve_adaptive(rgb_avg_host) (k_history_blend_counts): c_k = blend_component(S_k, Tf_p, C.k, C.w).
+ * pt_history_capture_adaptive() (k_history_capture_counts): K0 = {blend, Tf_p + Th}, K1 and K2 pt_history_capture's,
+ *   VK = {vb.xyz, +0} of pass A; the kept camera and geoms as in any capture; K is "kept with variance" afterwards, so the next view's
+ *   pt_history_reproject_ex(PT_HISTORY_VARIANCE) runs unchanged.  Needs a feature pass since the last clear or move.
+ *   Both are valid in both states and take no `samples`: the counts say it.  In the uniform state with counts (T, M) and C, VC present
+ *   they equal pt_history_resolve / pt_history_capture_ex(PT_HISTORY_VARIANCE) at samples = (float)T bit for bit, and with C absent the
+ *   resolve is pt_resolve.  Refusals: no renderer or a failed context; a striped or ragged tile; (the capture) no feature pass; E present;
+ *   nothing folded, fewer than 2 groups folded, iterations rendered since the last fold; C present with VC absent or of the moments kind.
+ * pt_history_denoise_adaptive(opt, rgb_avg_host) (ptdn::Form::HistoryAdaptive; a _device form on a context): the guided filter over that
+ *   blend.  Prepare: pt_history_denoise's with Tf_p, Df_p per pixel — the colour is the blend, v_k = vb_k, demodulated as there,
+ *   var_raw = (v_x + v_y) + v_z — and NE[p] = Tf_p + Th in the position buffer's spare word, where pt_denoise_adaptive keeps Tf_p.
+ *   Prefilter (the per-sample one, reading that word), levels and finish are pt_denoise_adaptive's kernels, unchanged: only the prepare
+ *   is a new kernel instantiation, and the workspace is the shared 80 B per pixel.  sigma_color == 0 means 8.0, as in the history
+ *   form.  With C absent the result is pt_denoise_adaptive's bit for bit.  Valid in both states.  Refusals: pt_history_denoise's in
+ *   its order, without the adaptive state and `samples`.
+ * pt_render --orbit N --reproject --denoise-history --history-threshold E [--history-threshold-cap F] [--history-threshold-min-pixels P]
+ *   [--history-threshold-group G] runs a view this way per frame.  What it buys and costs: README "Threshold rounds over the blend"
+ *   (tests/test_history_threshold_sim.py, profiles/history_threshold_cost.log).
+ * Not built: the moments kind, the probes and the feedback beside these calls (the moments kind is refused by name; the other two
+ *   need it); pt_group_*. */
+int pt_history_noise_adaptive(double* sse);
+int pt_readback_history_noise_samples(float* ne_host); /* pixel_count floats: NE */
+int pt_history_round_threshold(int iter_first, int group_iters, float threshold, float max_fraction, int* above, int* selected);
+int pt_history_render_threshold(int iter_first, int max_iters, int group_iters, float threshold, float max_fraction, int min_pixels, int* iters_done,
+                                int64_t* samples_done, int* above_left);
+int pt_history_resolve_adaptive(float* rgb_avg_host);
+int pt_history_capture_adaptive(void);
+int pt_history_denoise_adaptive(const PtDenoiseOptions* opt, float* rgb_avg_host);
+/* The same arithmetic on the host (no GPU).  counts: pixels * {T_p, M_p}; the first pixel with M_p < 2 or T_p < M_p is named in a
+ * refusal.  current_plane / current_var: C and VC, both NULL: absent.  pt_history_noise_adaptive_host: w_out, ne_out (pixels floats),
+ * vb_out (pixels float4: {vb.xyz, +0}) and *sse, any of them NULL.  pt_history_select_threshold_blend_host:
+ * pt_adaptive_select_threshold_host's arguments and C, VC.  pt_history_capture_adaptive_host: kept_planes (PT_HISTORY_KEPT_PLANES
+ * planes) and kept_var (VK). */
+int pt_history_noise_adaptive_host(int pixels, const float* noise_planes, const int32_t* counts, const float* current_plane, const float* current_var,
+                                   float* w_out, float* ne_out, float* vb_out, double* sse);
+int pt_history_select_threshold_blend_host(int w, int rows, const float* noise_planes, const int32_t* counts, const float* current_plane,
+                                           const float* current_var, float threshold, int cap, int32_t* list, int* above, int* m);
+int pt_history_blend_adaptive_host(int pixels, const float* rgb_sum, const int32_t* counts, const float* current_plane, float* rgb_avg);
+int pt_history_capture_adaptive_host(int pixels, const float* rgb_sum, const float* feature_planes, const float* noise_planes, const int32_t* counts,
+                                     const float* current_plane, const float* current_var, float* kept_planes, float* kept_var);
+/* pt_denoise_adaptive_host's arguments and C, VC; the _variance_host form gives var_raw and var_0 (either may be NULL, not both). */
+int pt_history_denoise_adaptive_host(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, const int32_t* counts,
+                                     const float* current_plane, const float* current_var, const PtDenoiseOptions* opt, float* rgb_avg);
+int pt_history_denoise_adaptive_variance_host(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, const int32_t* counts,
+                                              const float* current_plane, const float* current_var, const PtDenoiseOptions* opt, float* var_raw, float* var_0);
 
 /* saveImage()'s per-pixel conversion (main.cpp:91-97 x mirror, image.cpp:26-30 clamp * 255 truncated) on the
  * device: pixel_count*3 bytes, row-major, x mirrored inside each row; the tile must consist of whole rows.
@@ -1381,6 +1464,16 @@ int pt_ctx_history_probe_check(PtContext* c, const PtHistoryProbeOptions* opt, i
 int pt_ctx_readback_history_probe(PtContext* c, float* kept, float* lam, int* count);
 int pt_ctx_history_noise(PtContext* c, float samples, uint32_t flags, double* sse);
 int pt_ctx_readback_history_noise(PtContext* c, float* w_host);
+int pt_ctx_history_noise_adaptive(PtContext* c, double* sse);
+int pt_ctx_readback_history_noise_samples(PtContext* c, float* ne_host);
+int pt_ctx_history_round_threshold(PtContext* c, int iter_first, int group_iters, float threshold, float max_fraction, int* above, int* selected);
+int pt_ctx_history_render_threshold(PtContext* c, int iter_first, int max_iters, int group_iters, float threshold, float max_fraction, int min_pixels,
+                                    int* iters_done, int64_t* samples_done, int* above_left);
+int pt_ctx_history_resolve_adaptive(PtContext* c, float* rgb_avg_host);
+int pt_ctx_history_resolve_adaptive_device(PtContext* c, const float** rgb_dev);
+int pt_ctx_history_capture_adaptive(PtContext* c);
+int pt_ctx_history_denoise_adaptive(PtContext* c, const PtDenoiseOptions* opt, float* rgb_avg_host);
+int pt_ctx_history_denoise_adaptive_device(PtContext* c, const PtDenoiseOptions* opt, const float** rgb_dev);
 int pt_ctx_history_render_until(PtContext* c, int iter_first, int max_iters, int group_iters, float target_db, int* iters_done, float* psnr_db,
                                 float* view_psnr_db);
 int pt_ctx_history_denoise_feedback(PtContext* c, float samples, const PtDenoiseOptions* opt, const PtHistoryFeedbackOptions* fb, float* rgb_avg_host);
@@ -1650,6 +1743,17 @@ int pt_stage_history_merge(int pixels, float* rgb_sum, float* extra, const int32
  * arguments and refusals; *sse is the device's double). */
 int pt_stage_history_noise(int pixels, const float* noise_planes, int groups, int64_t iters, float samples, const float* current_plane,
                            const float* current_var, float* w_out, double* sse);
+/* Threshold rounds over the blend through their kernels on caller-supplied host arrays (the *_host twins' arguments and refusals;
+ * rows < 32768): pass A and the reduction (*sse is the device's double); passes A and B and the round's selection (list: all cap
+ * entries are returned, those behind *m are -1); the capture and the blend (rgb_avg may be NULL); the filter. */
+int pt_stage_history_noise_adaptive(int pixels, const float* noise_planes, const int32_t* counts, const float* current_plane, const float* current_var,
+                                    float* w_out, float* ne_out, double* sse);
+int pt_stage_history_select_threshold_blend(int w, int rows, const float* noise_planes, const int32_t* counts, const float* current_plane, const float* current_var,
+                                            float threshold, int cap, int32_t* list, int* above, int* m);
+int pt_stage_history_capture_adaptive(int pixels, const float* rgb_sum, const float* feature_planes, const float* noise_planes, const int32_t* counts,
+                                      const float* current_plane, const float* current_var, float* kept_planes, float* kept_var, float* rgb_avg);
+int pt_stage_history_denoise_adaptive(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, const int32_t* counts,
+                                      const float* current_plane, const float* current_var, const PtDenoiseOptions* opt, float* rgb_avg);
 /* The lookup with the filtered colour through k_history_reproject_feedback, and the feedback form of the filter — its prepare (counted
  * when `extra` is given), the moments form's kernels, the tap — on caller-supplied host arrays (the host forms' arguments but var_raw and
  * mark; rgb_avg or tap may be NULL, not both; rows < 32768). */
