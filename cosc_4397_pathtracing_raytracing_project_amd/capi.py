@@ -60,6 +60,13 @@ class PtGridRecord(C.Structure):
     _fields_ = [("bmin", C.c_float * 3), ("bmax", C.c_float * 3), ("leaf", C.c_int32), ("neighbours", C.c_int32)]
 
 
+class PtCameraGridResult(C.Structure):
+    """What pt_stage_camera_grid and pt_camera_grid_host report (include/pt_amd.h): status 0 built, PT_DEVICE_TABLES_LIST,
+    PT_DEVICE_TABLES_CELLS or PT_CAMERA_GRID_NONE."""
+    _fields_ = [("res", C.c_int32 * 3), ("origin", C.c_float * 3), ("cell_size", C.c_float * 3), ("inv_cell_size", C.c_float * 3), ("pad", C.c_float),
+                ("guard", C.c_uint32), ("num_cells", C.c_int64), ("refs", C.c_uint64), ("longest", C.c_uint32), ("status", C.c_int32)]
+
+
 class PtSceneDesc(C.Structure):
     _fields_ = [("geoms", C.POINTER(PtGeom)), ("num_geoms", C.c_int32), ("materials", C.POINTER(PtMaterial)),
                 ("num_materials", C.c_int32), ("camera", PtCamera), ("trace_depth", C.c_int32)]
@@ -131,6 +138,9 @@ class PtSetGeomsTimes(C.Structure):
 
 PT_SET_CAMERA_DEVICE_TABLES = 1
 PT_DEVICE_TABLES_LIST, PT_DEVICE_TABLES_CELLS = 1, 2
+PT_CAMERA_GRID_NONE = 3
+# PtTableNode and PtGridRecord, 32 bytes each (csrc/pt_device.h ptd::Node)
+TABLE_NODE = np.dtype([("bmin", np.float32, 3), ("bmax", np.float32, 3), ("skip", np.int32), ("geom", np.int32)])
 TABLE_NAMES = ("nodes", "nodes_b", "top", "top_b", "grid_start", "grid_items", "grid_items_b", "cull_margin", "geoms")  # pt_stage_read_tables' `which`
 
 
@@ -343,6 +353,11 @@ def lib() -> C.CDLL:
         L.pt_ctx_get_set_camera_times.argtypes = [C.c_void_p, C.POINTER(PtSetCameraTimes)]
         L.pt_stage_read_tables.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.pt_selfcheck_camera_math.argtypes = [C.c_int, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
+        if hasattr(L, "pt_stage_camera_grid"):  # absent from older A/B builds of the library (tools/build_rev.sh)
+            _grid = [C.c_void_p, C.c_int, _ip, C.c_int, _fp, _fp, C.c_double, _ip, C.c_int, C.POINTER(PtCameraGridResult), C.c_void_p, C.c_uint64,
+                     C.c_void_p, C.c_void_p, C.c_uint64]
+            L.pt_stage_camera_grid.argtypes = _grid
+            L.pt_camera_grid_host.argtypes = _grid
         L.pt_scene_camera.argtypes = [C.c_void_p, _cam]
         L.pt_scene_orbit_state.argtypes = [C.c_void_p, _fp, _fp, _fp]
     if hasattr(L, "pt_history_capture"):  # absent from older A/B builds of the library (tools/build_rev.sh)
@@ -672,6 +687,38 @@ def camera_tables_host(scene: "Scene", cam: PtCamera, debug_flags: int = 0, cent
     _check(lib().pt_camera_tables_host(C.byref(scene.desc), C.byref(cam), int(debug_flags), int(bool(center_half)), res,
                                        C.byref(tight), C.byref(differing)))
     return tuple(res), int(tight.value), int(differing.value)
+
+
+def camera_grid(nodes: np.ndarray, geom_types: np.ndarray, root_min, root_max, res, center_half: bool = False, coord_mag: float = 0.0,
+                device: bool = False, caps: Optional[Tuple[int, int]] = None):
+    """The grid of the camera-dependent tables over caller-supplied nodes (a TABLE_NODE array): pt_camera_grid_host, or with `device`
+    pt_stage_camera_grid (the kernels of csrc/pt_camera_tables.hip; needs the default renderer).  Returns (PtCameraGridResult, start,
+    items, items_b): uint32 words, the records as [refs, 8] words, None where the status is not 0 (and items_b without center_half).
+    caps: the capacities (words, records) to allocate; None asks the function for the sizes first."""
+    fn = lib().pt_stage_camera_grid if device else lib().pt_camera_grid_host
+    assert nodes.dtype == TABLE_NODE and nodes.flags.c_contiguous
+    types = np.ascontiguousarray(geom_types, np.int32)
+    lo, hi = np.ascontiguousarray(root_min, np.float32), np.ascontiguousarray(root_max, np.float32)
+    r = np.ascontiguousarray(res, np.int32)
+    out = PtCameraGridResult()
+
+    def call(start, items, items_b, words, records):
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        _check(fn(nodes.ctypes.data_as(C.c_void_p), int(nodes.size), _i(types), int(types.size), _f(lo), _f(hi), float(coord_mag), _i(r),
+                  int(bool(center_half)), C.byref(out), ptr(start), words, ptr(items), ptr(items_b), records))
+
+    if caps is None:
+        call(None, None, None, 0, 0)
+        if out.status != 0:
+            return out, None, None, None
+        caps = (int(out.num_cells) + 1 + 2 * int(out.guard), int(out.refs))
+    start, items = np.zeros(max(caps[0], 1), np.uint32), np.zeros((max(caps[1], 1), 8), np.uint32)
+    items_b = np.zeros_like(items) if center_half else None
+    call(start, items, items_b, start.size, items.shape[0])
+    if out.status != 0:
+        return out, None, None, None
+    words, refs = int(out.num_cells) + 1 + 2 * int(out.guard), int(out.refs)
+    return out, start[:words], items[:refs], (items_b[:refs] if center_half else None)
 
 
 def build_transform(trs: Sequence[float]):

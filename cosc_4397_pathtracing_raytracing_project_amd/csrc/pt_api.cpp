@@ -1141,14 +1141,12 @@ int move_tables_device(Ctx& g, int32_t* fallback) {
   if (want_grid) {
     double cam_mag = 0.0;
     for (int k = 0; k < 3; ++k) cam_mag = std::max(cam_mag, std::fabs((double)g.cam.position[k]));
-    want_grid = pt::grid_frame(s.root_min, s.root_max, cam_mag, a.frame);
-    if (want_grid) {
-      for (int k = 0; k < 3; ++k) a.frame.res[k] = std::min(512, std::max(1, g.grid_request.res[k]));
-      const int64_t ncell = pt::grid_shape(a.frame, shape);
-      if (ncell > (int64_t)64 * 1024 * 1024 || (int64_t)cb.geoms.size() > (1 << 24)) want_grid = false;  // build_grid's refusals
-      else if (ncell > ptct::kDeviceMaxCells) return *fallback = PT_DEVICE_TABLES_CELLS, 0;
-      a.ncell = (uint32_t)ncell, a.guard = (uint32_t)pt::grid_guard(shape);
-    }
+    int64_t ncell = 0;
+    size_t guard = 0;
+    const pt::GridVerdict v = pt::device_grid_scalars(s.root_min, s.root_max, cam_mag, g.grid_request.res, (int64_t)cb.geoms.size(), a.frame, shape, &ncell, &guard);
+    if (v == pt::kGridCells) return *fallback = PT_DEVICE_TABLES_CELLS, 0;
+    want_grid = v == pt::kGridBuild;
+    a.ncell = (uint32_t)ncell, a.guard = (uint32_t)guard;
   }
   if (ensure_device_base(g)) return -1;
   const Ctx::DeviceBase& b = g.device_base;
@@ -1166,9 +1164,9 @@ int move_tables_device(Ctx& g, int32_t* fallback) {
   }
   g.tight_leaves = (int)rec.tight;
   if (want_grid) {  // build_grid's refusals on what the kernels counted
-    const int64_t leaves = ((int64_t)cb.nodes.size() + 1) / 2;
-    if ((int64_t)rec.refs > ptct::kMaxRefs || (!forced && (int64_t)rec.refs > 64 * leaves) || (!forced && rec.longest > 4096)) want_grid = false;
-    else if (rec.longest > ptct::kDeviceMaxList || rec.refs > b.scratch_cap) return *fallback = PT_DEVICE_TABLES_LIST, 0;
+    const pt::GridVerdict v = pt::device_grid_counted(forced, ((int64_t)cb.nodes.size() + 1) / 2, rec.refs, rec.longest, b.scratch_cap);
+    if (v == pt::kGridList) return *fallback = PT_DEVICE_TABLES_LIST, 0;
+    want_grid = v == pt::kGridBuild;
   }
   // the grid's buffers: reused where the sizes are unchanged, else replaced (move_tables' rule)
   if (!g.grids.empty()) {
@@ -1356,6 +1354,25 @@ int pt_camera_tables_host(const PtSceneDesc* scene, const PtCamera* cam, int deb
   if (!scene || !cam || !grid_res_out || !tight_leaves || !differing || !scene->geoms || scene->num_geoms <= 0 || !scene->materials || scene->num_materials <= 0)
     return pt_fail("pt_camera_tables_host: null argument");
   return pt::camera_tables_check(*scene, *cam, debug_flags, center_half != 0, grid_res_out, tight_leaves, differing);
+}
+
+int pt_camera_grid_host(const PtTableNode* nodes, int num_nodes, const int32_t* geom_types, int num_geoms, const float root_min[3],
+                        const float root_max[3], double coord_mag, const int32_t res[3], int center_half, PtCameraGridResult* out,
+                        uint32_t* start, uint64_t start_cap, PtGridRecord* items, PtGridRecord* items_b, uint64_t items_cap) {
+  if (const char* why = pt::camera_grid_refusal(nodes, num_nodes, geom_types, num_geoms, root_min, root_max, coord_mag, res, out))
+    return pt_fail("pt_camera_grid_host: %s", why);
+  const bool query = !start && !items;
+  if (!query && (!start || !items || (center_half && !items_b))) return pt_fail("pt_camera_grid_host: null argument");
+  pt::Grid grid;
+  pt::camera_grid_host(reinterpret_cast<const ptd::Node*>(nodes), num_nodes, geom_types, num_geoms, root_min, root_max, coord_mag, res, center_half != 0, out, grid);
+  if (out->status != 0 || query) return 0;
+  if (grid.start.size() > start_cap || grid.items.size() > items_cap)
+    return pt_fail("pt_camera_grid_host: the grid needs %zu words and %zu records, the arrays hold %llu and %llu", grid.start.size(), grid.items.size(),
+                   (unsigned long long)start_cap, (unsigned long long)items_cap);
+  std::memcpy(start, grid.start.data(), grid.start.size() * sizeof(uint32_t));
+  if (!grid.items.empty()) std::memcpy(items, grid.items.data(), grid.items.size() * sizeof(ptd::Node));
+  if (center_half && !grid.items_b.empty()) std::memcpy(items_b, grid.items_b.data(), grid.items_b.size() * sizeof(ptd::Node));
+  return 0;
 }
 
 // ---- convergence metric ---------------------------------------------------------------------

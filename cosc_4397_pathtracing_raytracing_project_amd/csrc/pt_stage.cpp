@@ -230,6 +230,64 @@ int pt_selfcheck_camera_math(int kind, uint64_t count, uint32_t seed, uint64_t* 
   return pt_camera_math_check(kind, count, seed, mismatches);
 }
 
+// The grid launches of move_tables_device (pt_api.cpp) on the caller's nodes, with that function's scalars and decisions for a forced grid
+// (pt_tables.h device_grid_*); pt_camera_grid_host is the host side of the comparison.
+int pt_stage_camera_grid(const PtTableNode* nodes, int num_nodes, const int32_t* geom_types, int num_geoms, const float root_min[3],
+                         const float root_max[3], double coord_mag, const int32_t res[3], int center_half, PtCameraGridResult* out,
+                         uint32_t* start, uint64_t start_cap, PtGridRecord* items, PtGridRecord* items_b, uint64_t items_cap) {
+  const char* who = "pt_stage_camera_grid";
+  if (need(default_context(), who)) return -1;
+  Ctx& g = *default_context();
+  if (const char* why = pt::camera_grid_refusal(nodes, num_nodes, geom_types, num_geoms, root_min, root_max, coord_mag, res, out)) return pt_fail("%s: %s", who, why);
+  const bool query = !start && !items;
+  if (!query && (!start || !items || (center_half && !items_b))) return pt_fail("%s: null argument", who);
+  ptct::BuildArgs a{};
+  a.num_nodes = num_nodes, a.center_half = center_half ? 1 : 0;
+  pt::GridShape shape{};
+  int64_t ncell = 0;
+  size_t guard = 0;
+  const int want[3] = {res[0], res[1], res[2]};
+  pt::GridVerdict v = pt::device_grid_scalars(root_min, root_max, coord_mag, want, num_geoms, a.frame, shape, &ncell, &guard);
+  if (v != pt::kGridBuild) return pt::camera_grid_result(shape, guard, ncell, 0, 0, v, out), 0;  // nothing is launched
+  a.ncell = (uint32_t)ncell, a.guard = (uint32_t)guard;
+  HIP_OK(hipSetDevice(g.device));
+  Scratch sc;
+  ptd::Node* d_nodes = nullptr;
+  ptct::DeviceGeom* d_geoms = nullptr;
+  std::vector<ptct::DeviceGeom> geoms((size_t)num_geoms, ptct::DeviceGeom{});
+  for (int i = 0; i < num_geoms; ++i) geoms[(size_t)i].type = geom_types[i];
+  if (device_copy(sc, who, reinterpret_cast<const ptd::Node*>(nodes), (size_t)num_nodes, &d_nodes) || device_copy(sc, who, geoms.data(), geoms.size(), &d_geoms)) return -1;
+  ptct::BuildRecord* d_rec = sc.get<ptct::BuildRecord>(1);
+  uint32_t* d_count = sc.get<uint32_t>((size_t)ncell);
+  uint32_t* d_sums = sc.get<uint32_t>(pt_camera_tables_scan_blocks((size_t)ncell));
+  if (!d_rec || !d_count || !d_sums) return pt_fail("%s: out of device memory", who);
+  HIP_OK(hipMemsetAsync(d_rec, 0, sizeof(ptct::BuildRecord), g.stream));  // (pt_camera_tables_nodes_launch zeroes it for a renderer)
+  if (pt_camera_tables_count_launch(g.stream, a, d_nodes, d_count, d_rec)) return -1;
+  ptct::BuildRecord rec{};
+  HIP_OK(hipMemcpyAsync(&rec, d_rec, sizeof(rec), hipMemcpyDeviceToHost, g.stream));
+  HIP_OK(hipStreamSynchronize(g.stream));
+  int64_t leaves = 0;
+  for (int i = 0; i < num_nodes; ++i) leaves += nodes[i].geom >= 0 ? 1 : 0;
+  v = pt::device_grid_counted(true, leaves, rec.refs, rec.longest, (size_t)ptct::kMaxRefs);
+  pt::camera_grid_result(shape, guard, ncell, rec.refs, rec.longest, v, out);
+  if (v != pt::kGridBuild || query) return 0;
+  const size_t words = (size_t)ncell + 1 + 2 * guard, refs = (size_t)rec.refs;
+  if (words > start_cap || refs > items_cap)
+    return pt_fail("%s: the grid needs %zu words and %zu records, the arrays hold %llu and %llu", who, words, refs, (unsigned long long)start_cap,
+                   (unsigned long long)items_cap);
+  uint32_t* d_scratch = sc.get<uint32_t>(refs);
+  uint32_t* d_start = sc.get<uint32_t>(words);
+  ptd::Node* d_items = sc.get<ptd::Node>(refs);
+  ptd::Node* d_items_b = center_half ? sc.get<ptd::Node>(refs) : nullptr;
+  if (!d_scratch || !d_start || !d_items || (center_half && !d_items_b)) return pt_fail("%s: out of device memory", who);
+  if (pt_camera_tables_grid_launch(g.stream, a, d_nodes, d_geoms, d_count, d_sums, d_scratch, (uint32_t)refs, d_start, d_items, d_items_b)) return -1;
+  HIP_OK(hipStreamSynchronize(g.stream));
+  HIP_OK(hipMemcpy(start, d_start, words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(items, d_items, refs * sizeof(ptd::Node), hipMemcpyDeviceToHost));
+  if (center_half) HIP_OK(hipMemcpy(items_b, d_items_b, refs * sizeof(ptd::Node), hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int pt_stage_shade(int n, int depth, const int32_t* iter, const int32_t* pixel, const float* t, const float* normal,
                    const int32_t* material, const float* point, float* origin, float* dir, float* color,
                    int32_t* alive) {

@@ -210,6 +210,26 @@ int64_t grid_shape(const ptct::GridFrame& f, GridShape& s) {
 }
 size_t grid_guard(const GridShape& s) { return (size_t)s.res[0] * s.res[1] + s.res[0] + 2; }
 
+// The scalars as camera_tables() and build_grid() compute them for a kFixed request, with build_grid's refusals that need no count
+// and the device build's limit on the cells.
+GridVerdict device_grid_scalars(const float root_min[3], const float root_max[3], double coord_mag, const int res[3], int64_t num_geoms,
+                                ptct::GridFrame& frame, GridShape& shape, int64_t* ncell, size_t* guard) {
+  *ncell = 0, *guard = 0;
+  if (!grid_frame(root_min, root_max, coord_mag, frame)) return kGridNone;
+  for (int k = 0; k < 3; ++k) frame.res[k] = std::min(512, std::max(1, res[k]));
+  *ncell = grid_shape(frame, shape);
+  *guard = grid_guard(shape);
+  if (*ncell > (int64_t)64 * 1024 * 1024 || num_geoms > (1 << 24)) return kGridNone;  // build_grid's refusals
+  if (*ncell > ptct::kDeviceMaxCells) return kGridCells;
+  return kGridBuild;
+}
+// build_grid's refusals on what the kernels counted (no reference: no leaf, which a renderer's tree never is), then the device build's limits
+GridVerdict device_grid_counted(bool forced, int64_t leaves, unsigned long long refs, uint32_t longest, size_t scratch_cap) {
+  if (refs == 0 || (int64_t)refs > ptct::kMaxRefs || (!forced && (int64_t)refs > 64 * leaves) || (!forced && longest > 4096)) return kGridNone;
+  if (longest > ptct::kDeviceMaxList || refs > scratch_cap) return kGridList;
+  return kGridBuild;
+}
+
 bool build_grid(const std::vector<ptd::Node>& nodes, const PtGeom* geoms, int num_geoms, const float root_min[3], const float root_max[3],
                 double coord_mag, double density, bool forced, Grid& grid, const int* fixed_res) {
   std::vector<int> leaves;
@@ -325,6 +345,20 @@ double scene_magnitude(const float root_min[3], const float root_max[3], const f
   return m;
 }
 
+// What a renderer's grid has beyond build_grid's: the guard cells and, for the fast build, the copies of the records.
+static void renderer_grid(Grid& grid, bool center_half) {
+  // the cell table with empty cells before and after it: a walk may run up to one cell per axis past the grid's far side
+  // before its distance test ends it (pt_grid.inc CellWalk)
+  grid.guard = grid_guard(grid.shape);
+  const uint32_t total = grid.start.back();
+  grid.start.insert(grid.start.begin(), grid.guard, 0u);
+  grid.start.resize(grid.start.size() + grid.guard, total);
+  if (center_half) {  // the grid's records are leaf boxes
+    grid.items_b = grid.items;
+    for (ptd::Node& n : grid.items_b) center_half_box(n.bmin, n.bmax, false, 0.0);
+  }
+}
+
 // What follows the camera position (pt_tables.h).  The order matters: the copies and the grids are made from the tightened boxes.
 void camera_tables(HostTables& t, const CameraBase& base, const float cam[3], int debug_flags, bool center_half, const GridRequest& request) {
   t.nodes = base.nodes;
@@ -371,16 +405,7 @@ void camera_tables(HostTables& t, const CameraBase& base, const float cam[3], in
       bool repeat = false;
       for (const Grid& o : t.grids) repeat = repeat || std::equal(o.shape.res, o.shape.res + 3, grid.shape.res);
       if (repeat) continue;
-      // the cell table with empty cells before and after it: a walk may run up to one cell per axis past the grid's far side
-      // before its distance test ends it (pt_grid.inc CellWalk)
-      grid.guard = grid_guard(grid.shape);
-      const uint32_t total = grid.start.back();
-      grid.start.insert(grid.start.begin(), grid.guard, 0u);
-      grid.start.resize(grid.start.size() + grid.guard, total);
-      if (center_half) {  // the grid's records are leaf boxes
-        grid.items_b = grid.items;
-        for (ptd::Node& n : grid.items_b) center_half_box(n.bmin, n.bmax, false, 0.0);
-      }
+      renderer_grid(grid, center_half);
       t.grids.push_back(std::move(grid));
     }
   }
@@ -482,6 +507,64 @@ int camera_tables_check(const PtSceneDesc& desc, const PtCamera& cam, int debug_
   *tight_leaves = fresh.tight_leaves;
   *differing = d;
   return 0;
+}
+
+// ---- pt_camera_grid_host / pt_stage_camera_grid --------------------------------------------------------------------------------------
+static_assert(sizeof(PtTableNode) == sizeof(ptd::Node) && sizeof(PtCameraGridResult) == 80, "the grid stage's records");
+const char* camera_grid_refusal(const PtTableNode* nodes, int num_nodes, const int32_t* geom_types, int num_geoms, const float* root_min, const float* root_max,
+                                double coord_mag, const int32_t* res, const PtCameraGridResult* out) {
+  if (!nodes || !geom_types || !root_min || !root_max || !res || !out) return "null argument";
+  if (num_nodes < 1 || num_geoms < 1) return "no nodes or no geoms";
+  if (!(coord_mag >= 0.0) || !std::isfinite(coord_mag)) return "coord_mag is negative or not finite";
+  for (int i = 0; i < num_nodes; ++i) {
+    if (nodes[i].geom < -1 || nodes[i].geom >= num_geoms) return "a node's geom is outside [-1, num_geoms)";
+    // (the host's reference count and the kernels' per-axis clamp agree only on boxes that are boxes)
+    for (int a = 0; a < 3; ++a)
+      if (!(nodes[i].bmin[a] <= nodes[i].bmax[a])) return "a node's box has bmin > bmax or a NaN";
+  }
+  return nullptr;
+}
+void camera_grid_result(const GridShape& s, size_t guard, int64_t ncell, unsigned long long refs, uint32_t longest, GridVerdict status, PtCameraGridResult* out) {
+  std::memset(out, 0, sizeof(*out));
+  for (int a = 0; a < 3; ++a) out->res[a] = s.res[a], out->origin[a] = s.gmin[a], out->cell_size[a] = s.cs[a], out->inv_cell_size[a] = s.inv_cs[a];
+  out->pad = s.pad;
+  out->guard = (uint32_t)guard, out->num_cells = ncell, out->refs = refs, out->longest = longest, out->status = (int32_t)status;
+}
+void camera_grid_host(const ptd::Node* nodes, int num_nodes, const int32_t* geom_types, int num_geoms, const float root_min[3], const float root_max[3],
+                      double coord_mag, const int32_t res[3], bool center_half, PtCameraGridResult* out, Grid& grid) {
+  grid = Grid{};
+  ptct::GridFrame frame{};
+  GridShape shape{};
+  int64_t ncell = 0;
+  size_t guard = 0;
+  const int want[3] = {res[0], res[1], res[2]};
+  GridVerdict v = device_grid_scalars(root_min, root_max, coord_mag, want, num_geoms, frame, shape, &ncell, &guard);
+  unsigned long long refs = 0;
+  uint32_t longest = 0;
+  if (v == kGridBuild) {  // what k_ct_refs adds up, whether or not a grid follows
+    int64_t leaves = 0;
+    for (int i = 0; i < num_nodes; ++i) {
+      if (nodes[i].geom < 0) continue;
+      int c0[3], c1[3];
+      ptct::cell_range(nodes[i].bmin, nodes[i].bmax, frame, c0, c1);
+      refs += (unsigned long long)ptct::cell_references(c0, c1);
+      ++leaves;
+    }
+    bool built = false;
+    if (refs <= (unsigned long long)ptct::kMaxRefs) {  // (beyond it build_grid refuses, and the kernels count nothing: longest stays 0)
+      std::vector<PtGeom> geoms((size_t)num_geoms, PtGeom{});
+      for (int i = 0; i < num_geoms; ++i) geoms[(size_t)i].type = geom_types[i];
+      const std::vector<ptd::Node> list(nodes, nodes + num_nodes);
+      built = build_grid(list, geoms.data(), num_geoms, root_min, root_max, coord_mag, 0.0, true, grid, want);
+      if (built)
+        for (size_t c = 0; c + 1 < grid.start.size(); ++c) longest = std::max(longest, grid.start[c + 1] - grid.start[c]);
+    }
+    v = device_grid_counted(true, leaves, refs, longest, (size_t)ptct::kMaxRefs);
+    if (v == kGridBuild && !built) v = kGridNone;
+    if (v == kGridBuild) renderer_grid(grid, center_half);
+    else grid = Grid{};
+  }
+  camera_grid_result(shape, guard, ncell, refs, longest, v, out);
 }
 
 }  // namespace pt

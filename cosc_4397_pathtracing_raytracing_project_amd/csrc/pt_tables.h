@@ -42,6 +42,14 @@ bool build_grid(const std::vector<ptd::Node>& nodes, const PtGeom* geoms, int nu
 bool grid_frame(const float root_min[3], const float root_max[3], double coord_mag, ptct::GridFrame& frame);
 int64_t grid_shape(const ptct::GridFrame& frame, GridShape& shape);
 size_t grid_guard(const GridShape& shape);
+// What the device build of a kFixed grid decides on the host (pt_api.cpp move_tables_device, pt_stage.cpp pt_stage_camera_grid), and the
+// host twin of that stage with it (camera_grid_host): build_grid's refusals (kGridNone) and the device build's own limits.
+enum GridVerdict { kGridBuild = 0, kGridList = PT_DEVICE_TABLES_LIST, kGridCells = PT_DEVICE_TABLES_CELLS, kGridNone = PT_CAMERA_GRID_NONE };
+// Before anything is counted: the frame for these bounds with `res` clamped to [1, 512], its shape, cells and guard cells.
+GridVerdict device_grid_scalars(const float root_min[3], const float root_max[3], double coord_mag, const int res[3], int64_t num_geoms,
+                                ptct::GridFrame& frame, GridShape& shape, int64_t* ncell, size_t* guard);
+// On what the kernels counted.  leaves: as build_grid counts them for its 64-per-leaf rule; scratch_cap: the references the workspace holds.
+GridVerdict device_grid_counted(bool forced, int64_t leaves, unsigned long long refs, uint32_t longest, size_t scratch_cap);
 void origin_region(const float root_min[3], const float root_max[3], const float cam[3], double olo[3], double ohi[3]);
 int tighten_sphere_leaves(std::vector<ptd::Node>& nodes, const PtGeom* geoms, const double origin_lo[3], const double origin_hi[3]);
 double scene_magnitude(const float root_min[3], const float root_max[3], const float cam[3]);
@@ -83,5 +91,12 @@ GridRequest first_grid_request(const HostTables& t);
 // pt_camera_tables_host (include/pt_amd.h).
 int camera_tables_check(const PtSceneDesc& desc, const PtCamera& cam, int debug_flags, bool center_half, int32_t grid_res_out[3], int32_t* tight_leaves,
                         int32_t* differing);
+// pt_camera_grid_host and pt_stage_camera_grid (include/pt_amd.h).  What both refuse about their inputs: nullptr, or the reason.
+const char* camera_grid_refusal(const PtTableNode* nodes, int num_nodes, const int32_t* geom_types, int num_geoms, const float* root_min, const float* root_max,
+                                double coord_mag, const int32_t* res, const PtCameraGridResult* out);
+void camera_grid_result(const GridShape& shape, size_t guard, int64_t ncell, unsigned long long refs, uint32_t longest, GridVerdict status, PtCameraGridResult* out);
+// The host twin: *out as the stage fills it, and with status kGridBuild `grid` (guard cells in, items_b with center_half).
+void camera_grid_host(const ptd::Node* nodes, int num_nodes, const int32_t* geom_types, int num_geoms, const float root_min[3], const float root_max[3],
+                      double coord_mag, const int32_t res[3], bool center_half, PtCameraGridResult* out, Grid& grid);
 
 }  // namespace pt

@@ -421,6 +421,28 @@ int pt_get_setup_times(PtSetupTimes* out);
  * the FAST build uploads. */
 int pt_camera_tables_host(const PtSceneDesc* scene, const PtCamera* cam, int debug_flags, int center_half, int32_t grid_res_out[3],
                           int32_t* tight_leaves, int32_t* differing);
+/* Host-only: the grid of a kFixed request over caller-supplied nodes, as the host build makes it for a forced grid and with the
+ * decisions of the device build, so that it can be compared with pt_stage_camera_grid (below) byte for byte; the arguments, the
+ * outputs and the refusals are that function's, under the name pt_camera_grid_host.  The grid is pt::build_grid's (forced, `res` taken as
+ * given) with the guard cells and the centre / half extent copies camera_tables() adds. */
+typedef struct PtTableNode { /* a node of the threaded BVH as the tables hold it (csrc/pt_device.h ptd::Node), 32 bytes */
+  float bmin[3], bmax[3];
+  int32_t skip; /* not read by the grid build                   */
+  int32_t geom; /* >= 0: a leaf of that geom; -1: an inner node */
+} PtTableNode;
+#define PT_CAMERA_GRID_NONE 3 /* status: no grid (no frame for these bounds, no leaf, or more than 2^22 references) */
+typedef struct PtCameraGridResult {
+  int32_t res[3];                           /* `res` clamped to [1, 512]                                                         */
+  float origin[3], cell_size[3], inv_cell_size[3], pad; /* the shape the kernels read (SceneTables::grid_*)                      */
+  uint32_t guard;                           /* guard cells in front of and behind the cell table proper                          */
+  int64_t num_cells;
+  uint64_t refs;                            /* (leaf, cell) references; 0 where nothing was counted (PT_DEVICE_TABLES_CELLS, no frame) */
+  uint32_t longest;                         /* records of the fullest cell; 0 where refs exceeds 2^22 (nothing is counted then)   */
+  int32_t status;                           /* 0 built, PT_DEVICE_TABLES_LIST, PT_DEVICE_TABLES_CELLS or PT_CAMERA_GRID_NONE      */
+} PtCameraGridResult;
+int pt_camera_grid_host(const PtTableNode* nodes, int num_nodes, const int32_t* geom_types, int num_geoms, const float root_min[3],
+                        const float root_max[3], double coord_mag, const int32_t res[3], int center_half, PtCameraGridResult* out,
+                        uint32_t* start, uint64_t start_cap, PtGridRecord* items, PtGridRecord* items_b, uint64_t items_cap);
 const char* pt_last_error(void);
 /* Device self-check.  The exact and fma kernels (and depth 0 of every mode) take correctly rounded square roots,
  * reciprocals and quotients from instruction sequences shorter than the compiler's general expansions whenever every
@@ -1678,6 +1700,21 @@ int pt_stage_read_tables(int which, void* out, uint64_t cap, uint64_t* bytes);
  * The operands are a fixed list of edge values per kind (+-0, denormals, the largest finite values, values that convert to infinity,
  * singular matrices) followed by `count` pseudo-random sets derived from `seed`.  Needs no renderer; runs on the current device. */
 int pt_selfcheck_camera_math(int kind, uint64_t count, uint32_t seed, uint64_t* mismatches);
+/* The grid half of the device build (csrc/pt_camera_tables.hip: count, scan, scatter, records) on caller-supplied nodes instead of a
+ * scene's: `num_nodes` nodes of which those with geom >= 0 are leaves, the types of `num_geoms` geoms, the bounds and the coordinate
+ * magnitude the frame is computed from (pt::grid_frame), the resolution (clamped to [1, 512] per axis) and whether the centre / half
+ * extent copies are made.  The scalars, the launches and the decisions between them are those of pt_set_camera_ex with
+ * PT_SET_CAMERA_DEVICE_TABLES on a renderer with a forced grid (debug_flags 256).  Needs the default renderer for its device and
+ * stream only: the workspace is scratch, the renderer's tables and its device copy of the camera-independent tables are left alone.
+ * *out always receives the shape, the guard, the cells, and what was counted; with status 0 `start` receives the cell table with
+ * both runs of guard cells (num_cells + 1 + 2 * guard words), `items` the records (refs of them) and, with center_half, `items_b`
+ * their copies.  start_cap and items_cap are the arrays' capacities in words and records: a built grid that does not fit is refused.
+ * With `start` and `items` both NULL nothing is built beyond the count (a query for the sizes).
+ * Refused: no renderer; a null pointer (items_b only with center_half); num_nodes < 1 or num_geoms < 1; a coord_mag that is negative
+ * or not finite; a node whose geom is outside [-1, num_geoms); a node whose box has bmin > bmax or a NaN. */
+int pt_stage_camera_grid(const PtTableNode* nodes, int num_nodes, const int32_t* geom_types, int num_geoms, const float root_min[3],
+                         const float root_max[3], double coord_mag, const int32_t res[3], int center_half, PtCameraGridResult* out,
+                         uint32_t* start, uint64_t start_cap, PtGridRecord* items, PtGridRecord* items_b, uint64_t items_cap);
 /* shadeAndExtendRays (pathtrace.cu:336-437) for live paths at `depth`:
  * in/out origin, dir, color; out alive[n] (1 = path continues).  Dead paths get the
  * retirement colour (sky factor applied (trace_depth - depth) times on a miss). */
