@@ -131,6 +131,11 @@ class PtSetCameraTimes(C.Structure):
     _fields_ = [("tables_ms", C.c_double), ("rearm_ms", C.c_double), ("total_ms", C.c_double), ("path", C.c_int32), ("fallback", C.c_int32)]
 
 
+class PtSetMaterialsTimes(C.Structure):
+    """Host wall-clock times of a renderer's last pt_set_materials, ms (include/pt_amd.h: pt_get_set_materials_times)."""
+    _fields_ = [("upload_ms", C.c_double), ("rearm_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 class PtSetGeomsTimes(C.Structure):
     """Host wall-clock times of a renderer's last pt_set_geoms, ms (include/pt_amd.h: pt_get_set_geoms_times)."""
     _fields_ = [("build_ms", C.c_double), ("upload_ms", C.c_double), ("rearm_ms", C.c_double), ("total_ms", C.c_double)]
@@ -436,6 +441,19 @@ def lib() -> C.CDLL:
         L.pt_history_motion_host.argtypes = [_gp, _gp, C.c_int, _fp, _u8p]
         L.pt_history_reproject_motion_host.argtypes = _reproject_motion
         L.pt_stage_history_reproject_motion.argtypes = _reproject_motion
+    if hasattr(L, "pt_set_materials"):  # absent from older A/B builds of the library (tools/build_rev.sh)
+        _mp, _gp, _cam, _hio = C.POINTER(PtMaterial), C.POINTER(PtGeom), C.POINTER(PtCamera), C.POINTER(PtHistoryOptions)
+        _reproject_materials = [C.c_int, C.c_int, C.c_int, _cam, _fp, _fp, _u8p, C.c_int, _hio, _fp, _fp, _u8p, _fp, _u8p, C.c_uint32, _fp, _fp]
+        L.pt_set_materials.argtypes = [_mp, C.c_int]
+        L.pt_ctx_set_materials.argtypes = [C.c_void_p, _mp, C.c_int]
+        L.pt_group_set_materials.argtypes = [C.c_void_p, _mp, C.c_int]
+        L.pt_get_set_materials_times.argtypes = [C.POINTER(PtSetMaterialsTimes)]
+        L.pt_ctx_get_set_materials_times.argtypes = [C.c_void_p, C.POINTER(PtSetMaterialsTimes)]
+        L.pt_scene_material.argtypes = [C.c_void_p, C.c_int, _mp]
+        L.pt_scene_set_material.argtypes = [C.c_void_p, C.c_int, _mp]
+        L.pt_history_recolor_host.argtypes = [_mp, _mp, C.c_int, _gp, C.c_int, _fp, _u8p]
+        L.pt_history_reproject_materials_host.argtypes = _reproject_materials
+        L.pt_stage_history_reproject_materials.argtypes = _reproject_materials
     if hasattr(L, "pt_history_probe_keep"):  # absent from older A/B builds of the library (tools/build_rev.sh)
         _hpo = C.POINTER(PtHistoryProbeOptions)
         L.pt_history_probe_keep.argtypes = [C.c_int, C.c_int, C.c_int]
@@ -618,6 +636,18 @@ class Scene:
 
     def materials(self):
         return [self.desc.materials[i] for i in range(self.desc.num_materials)]
+
+    def material(self, m: int) -> PtMaterial:
+        """Material `m` as the scene holds it, a copy (pt_scene_material)."""
+        out = PtMaterial()
+        _check(lib().pt_scene_material(self._h, int(m), C.byref(out)))
+        return out
+
+    def set_material(self, m: int, material: PtMaterial) -> None:
+        """A new material in the place of material `m` (pt_scene_set_material); `desc` follows.  Renderer.set_materials(scene) hands
+        the edited materials to a live renderer."""
+        _check(lib().pt_scene_set_material(self._h, int(m), C.byref(material)))
+        _check(lib().pt_scene_desc(self._h, C.byref(self.desc)))
 
     def grid(self, forced: bool = False):
         """The uniform grid of the cost model's resolution over the reference's leaf boxes, without the camera (pt_build_grid):
@@ -1135,6 +1165,14 @@ def _geom_array(geoms):
     return (PtGeom * max(len(seq), 1))(*seq), len(seq)
 
 
+def _material_array(materials):
+    """A ctypes array of PtMaterial from a Scene, a ctypes array or a sequence of PtMaterial; (array, count)."""
+    if isinstance(materials, Scene):
+        return materials.desc.materials, materials.desc.num_materials
+    seq = list(materials)
+    return (PtMaterial * max(len(seq), 1))(*seq), len(seq)
+
+
 def history_motion_host(kept, cur):
     """The motion table of PT_HISTORY_MOTION (pt_history_motion_host, no GPU): the kept and the current geoms (Scene, or sequences of
     PtGeom) in, (table float32 [n, 24], kind uint8 [n]) out: 0 still, 1 moved, 2 carries nothing."""
@@ -1178,6 +1216,62 @@ def stage_history_reproject_motion(kept_cam: PtCamera, kept, planes, reject, tab
                                    kept_var=None, **opts):
     """history_reproject_motion_host's arrays through the production kernel (pt_stage_history_reproject_motion; a renderer must be live)."""
     return _history_reproject_motion(lib().pt_stage_history_reproject_motion, kept_cam, kept, planes, reject, table, kind, w, rows, row0, flags, kept_var, **opts)
+
+
+HISTORY_MATERIALS = 32  # PT_HISTORY_MATERIALS
+HISTORY_RECOLOR_ROW = 4  # floats per geom of the recolour table
+
+
+def history_recolor_host(kept, cur, geoms):
+    """The recolour table of PT_HISTORY_MATERIALS (pt_history_recolor_host; no GPU): the kept and the current materials and the geoms
+    (Scenes or sequences) in, (table float32 [n, 4], kind uint8 [n]) out, n the geoms: 0 unchanged, 1 recoloured, 2 carries nothing."""
+    ka, kn = _material_array(kept)
+    ca, cn = _material_array(cur)
+    ga, gn = _geom_array(geoms)
+    if kn != cn or kn < 1 or gn < 1:
+        raise PtError(f"history_recolor_host: {kn} kept and {cn} current materials, {gn} geoms")
+    table, kind = np.empty((gn, HISTORY_RECOLOR_ROW), np.float32), np.empty(gn, np.uint8)
+    _check(lib().pt_history_recolor_host(ka, ca, kn, ga, gn, _f(table), kind.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return table, kind
+
+
+def _history_reproject_materials(call, kept_cam: PtCamera, kept, planes, reject, recolor, rkind, w: int, rows: int, row0: int, flags: int, kept_var, table, kind, **opts):
+    k = np.ascontiguousarray(kept, np.float32).reshape(-1)
+    p = np.ascontiguousarray(planes, np.float32).reshape(-1)
+    r = np.ascontiguousarray(reject, np.uint8).reshape(-1)
+    rt = np.ascontiguousarray(recolor, np.float32).reshape(-1)
+    rk = np.ascontiguousarray(rkind, np.uint8).reshape(-1)
+    t = None if table is None else np.ascontiguousarray(table, np.float32).reshape(-1)
+    kd = None if kind is None else np.ascontiguousarray(kind, np.uint8).reshape(-1)
+    vk = None if kept_var is None else np.ascontiguousarray(kept_var, np.float32).reshape(-1)
+    if k.size != 4 * HISTORY_KEPT_PLANES * w * rows or p.size != 4 * FEATURE_PLANES * w * rows or (vk is not None and vk.size != 4 * w * rows):
+        raise PtError(f"history_reproject_materials: {k.size} kept and {p.size} plane floats for a tile of {w}x{rows}")
+    if rt.size != HISTORY_RECOLOR_ROW * rk.size or rk.size != r.size or (t is not None and (kd is None or t.size != HISTORY_MOTION_ROW * r.size or kd.size != r.size)):
+        raise PtError(f"history_reproject_materials: {rt.size} table floats and {rk.size} kinds for {r.size} geoms")
+    out = np.empty((w * rows, 4), np.float32)
+    vout = None if vk is None else np.empty((w * rows, 4), np.float32)
+    opt = history_options(**opts)
+    u8 = C.POINTER(C.c_uint8)
+    _check(call(int(w), int(rows), int(row0), C.byref(kept_cam), _f(k), _f(p), r.ctypes.data_as(u8), int(r.size), C.byref(opt), None if vk is None else _f(vk),
+                None if t is None else _f(t), None if kd is None else kd.ctypes.data_as(u8), _f(rt), rk.ctypes.data_as(u8), int(flags), _f(out),
+                None if vout is None else _f(vout)))
+    return out if vk is None else (out, vout)
+
+
+def history_reproject_materials_host(kept_cam: PtCamera, kept, planes, reject, recolor, rkind, w: int, rows: int, row0: int = 0, flags: int = HISTORY_MATERIALS,
+                                     kept_var=None, table=None, kind=None, **opts):
+    """pt_history_reproject_ex with PT_HISTORY_MATERIALS on the host (no GPU): history_reproject_host's arrays, the recolour table and
+    its kinds (history_recolor_host) in, with HISTORY_MOTION in `flags` also the motion table and kinds; C [w*rows, 4] out, or (C, VC)
+    with HISTORY_VARIANCE or HISTORY_MOMENTS in `flags` and VK in kept_var."""
+    return _history_reproject_materials(lib().pt_history_reproject_materials_host, kept_cam, kept, planes, reject, recolor, rkind, w, rows, row0, flags, kept_var,
+                                        table, kind, **opts)
+
+
+def stage_history_reproject_materials(kept_cam: PtCamera, kept, planes, reject, recolor, rkind, w: int, rows: int, row0: int = 0, flags: int = HISTORY_MATERIALS,
+                                      kept_var=None, table=None, kind=None, **opts):
+    """history_reproject_materials_host's arrays through the production kernel (pt_stage_history_reproject_materials; a renderer must be live)."""
+    return _history_reproject_materials(lib().pt_stage_history_reproject_materials, kept_cam, kept, planes, reject, recolor, rkind, w, rows, row0, flags, kept_var,
+                                        table, kind, **opts)
 
 
 def _history_planes(current, current_var, w: int, rows: int):
@@ -1743,6 +1837,18 @@ class Renderer:
         arr, n = _geom_array(geoms)
         _check(lib().pt_set_geoms(arr, n))
 
+    def set_materials(self, materials) -> None:
+        """New materials for the live renderer (pt_set_materials): a Scene (after Scene.set_material) or a sequence of PtMaterial.
+        From here on the renderer gives what one freshly created with these materials gives; camera and geoms stay."""
+        arr, n = _material_array(materials)
+        _check(lib().pt_set_materials(arr, n))
+
+    def set_materials_times(self) -> PtSetMaterialsTimes:
+        """Upload / re-arm / total milliseconds of the last set_materials (pt_get_set_materials_times)."""
+        t = PtSetMaterialsTimes()
+        _check(lib().pt_get_set_materials_times(C.byref(t)))
+        return t
+
     def set_geoms_times(self) -> PtSetGeomsTimes:
         """Build / upload / re-arm / total milliseconds of the last set_geoms (pt_get_set_geoms_times)."""
         t = PtSetGeomsTimes()
@@ -2182,6 +2288,11 @@ class Group:
             _check(lib().pt_group_set_camera_ex(self._h, C.byref(cam), PT_SET_CAMERA_DEVICE_TABLES))
         else:
             _check(lib().pt_group_set_camera(self._h, C.byref(cam)))
+
+    def set_materials(self, materials) -> None:
+        """Renderer.set_materials on every context (pt_group_set_materials); a refusal leaves every context as it was."""
+        arr, n = _material_array(materials)
+        _check(lib().pt_group_set_materials(self._h, arr, n))
 
     def set_geoms(self, geoms) -> None:
         """Renderer.set_geoms on every context (pt_group_set_geoms); a refusal leaves every context as it was."""

@@ -598,6 +598,7 @@ static int setup(Ctx& g, const PtSceneDesc* sc, const PtOptions& opt) {
   const pt::HostTables host = pt::build_scene_tables(*sc, g.debug_flags, g.k->boxes_center_half != 0, pt::GridRequest{}, &g.camera_base);
   g.setup_times.tables_ms = ms_since(t0), t0 = clock::now();
   if (upload_tables(g, host)) return -1;
+  g.materials.assign(sc->materials, sc->materials + sc->num_materials);
   g.setup_times.upload_ms = ms_since(t0), t0 = clock::now();
   plan_launch(g);
   if (alloc_batch_buffers(g)) return -1;
@@ -736,6 +737,22 @@ int pt_scene_set_geom_trs(PtScene* s, int geom, const float trs[9]) {
   for (int k = 0; k < 9; ++k)
     if (!std::isfinite(trs[k])) return pt_fail("pt_scene_set_geom_trs: trs[%d] is not finite", k);
   s->scene.placeGeom(geom, trs);
+  return 0;
+}
+// The material's slot, or the refusal under the name `who`.
+static int scene_material(const PtScene* s, int m, const void* arg, const char* who) {
+  if (!s || !arg) return pt_fail("%s: null argument", who);
+  if (m < 0 || (size_t)m >= s->scene.materials.size()) return pt_fail("%s: material %d is outside the scene's %zu materials", who, m, s->scene.materials.size());
+  return 0;
+}
+int pt_scene_material(const PtScene* s, int m, PtMaterial* out) {
+  if (scene_material(s, m, out, "pt_scene_material")) return -1;
+  *out = s->scene.materials[(size_t)m];
+  return 0;
+}
+int pt_scene_set_material(PtScene* s, int m, const PtMaterial* material) {
+  if (scene_material(s, m, material, "pt_scene_set_material")) return -1;
+  if (!s->scene.setMaterial(m, *material)) return pt_fail("pt_scene_set_material: material %d has a word that is not finite", m);
   return 0;
 }
 int pt_scene_iterations(const PtScene* s) { return s ? (int)s->scene.state.iterations : 0; }
@@ -1044,6 +1061,25 @@ int pt_ctx_geoms_refusal(const PtContext* c, const PtGeom* geoms, int num_geoms,
         if (!std::isfinite(m[k])) return pt_fail("%s: geom %d has a matrix element that is not finite", who, i);
   return 0;
 }
+// What pt_set_materials refuses, under the name `who`; a group asks every context before it changes one.
+int pt_ctx_materials_refusal(const PtContext* c, const PtMaterial* materials, int num_materials, const char* who) {
+  if (need(c, who) || admit(*c, who, kNotFailed)) return -1;
+  if (!materials) return pt_fail("%s: null materials", who);
+  if (num_materials != (int)c->materials.size())
+    return pt_fail("%s: %d materials, but the renderer was created with %d; adding or removing materials needs pt_init", who, num_materials, (int)c->materials.size());
+  for (int i = 0; i < num_materials; ++i) {
+    const PtMaterial& m = materials[i];
+    const struct {
+      const char* name;
+      const float* v;
+      int n;
+    } fields[] = {{"color", m.color, 3}, {"specular_color", m.specular_color, 3}, {"hasReflective", &m.hasReflective, 1}, {"hasRefractive", &m.hasRefractive, 1}, {"emittance", &m.emittance, 1}};
+    for (const auto& f : fields)
+      for (int k = 0; k < f.n; ++k)
+        if (!std::isfinite(f.v[k])) return pt_fail("%s: %s of material %d is not finite", who, f.name, i);
+  }
+  return 0;
+}
 namespace {
 template <typename T>
 void release(Ctx& g, const T* dev, size_t count) {  // a table of `count` entries that dalloc() gave: back to the device
@@ -1303,6 +1339,38 @@ int set_geoms(PtContext* c, const PtGeom* geoms, int num_geoms) {  // after the 
   g.geoms_times = times;
   return 0;
 }
+int set_materials(PtContext* c, const PtMaterial* materials, int num_materials) {  // after the refusals
+  using clock = std::chrono::steady_clock;
+  auto ms_since = [](clock::time_point t0) { return std::chrono::duration<double, std::milli>(clock::now() - t0).count(); };
+  const auto t0 = clock::now();
+  Ctx& g = *c;
+  if (pt_ctx_sync(c)) return -1;
+  PtSetMaterialsTimes times{};
+  // pt_init's table for these materials, into the buffer the renderer has: the count is the renderer's, so nothing is allocated
+  if (reupload(g.scene.mats, pt::material_table(materials, num_materials))) return g.failed = true, -1;
+  g.materials.assign(materials, materials + num_materials);
+  g.hist_reject_stale = g.hist_emitter_stale = true;  // the per-geom tables of the history follow the materials: rebuilt at their next use
+  g.hist_materials.stale = true, g.hist_materials.fresh = false;  // (the next capture keeps these materials; K and the kept materials stay until then)
+  g.probe_materials_stale = g.probe_materials_changed = true;     // (the next keep copies these materials; the next check compares them with the kept ones)
+  times.upload_ms = ms_since(t0);
+  const auto t1 = clock::now();
+  // Whether a camera ray survives depth 0 follows the emittance of what it hits, and the primary kernel's records are reused from
+  // batch to batch: the whole re-arm of a camera move
+  plan_launch(g);
+  g.record_form = g.gather_form = 0;
+  if (Ctx* w = g.worker) {  // as in set_camera()
+    static_cast<PtShared&>(*w) = g;
+    set_worker_live(*w, w->capacity);
+    plan_launch(*w);
+    if (rearm_batch_buffers(*w)) return g.failed = true, -1;
+  }
+  if (rearm_batch_buffers(g)) return g.failed = true, -1;
+  if (pt_ctx_clear(c)) return -1;
+  times.rearm_ms = ms_since(t1);
+  times.total_ms = ms_since(t0);
+  g.materials_times = times;
+  return 0;
+}
 }  // namespace
 
 namespace ptc {
@@ -1333,6 +1401,16 @@ int pt_ctx_get_set_geoms_times(PtContext* c, PtSetGeomsTimes* out) {
   if (need(c, "pt_get_set_geoms_times")) return -1;
   if (!out) return pt_fail("pt_get_set_geoms_times: null");
   *out = c->geoms_times;
+  return 0;
+}
+int pt_ctx_set_materials(PtContext* c, const PtMaterial* materials, int num_materials) {
+  if (pt_ctx_materials_refusal(c, materials, num_materials, "pt_set_materials")) return -1;
+  return set_materials(c, materials, num_materials);
+}
+int pt_ctx_get_set_materials_times(PtContext* c, PtSetMaterialsTimes* out) {
+  if (need(c, "pt_get_set_materials_times")) return -1;
+  if (!out) return pt_fail("pt_get_set_materials_times: null");
+  *out = c->materials_times;
   return 0;
 }
 int pt_ctx_get_set_camera_times(PtContext* c, PtSetCameraTimes* out) {
@@ -1442,6 +1520,8 @@ int pt_set_camera_ex(const PtCamera* cam, uint32_t flags) { return pt_ctx_set_ca
 int pt_get_set_camera_times(PtSetCameraTimes* out) { return pt_ctx_get_set_camera_times(g_default, out); }
 int pt_set_geoms(const PtGeom* geoms, int num_geoms) { return pt_ctx_set_geoms(g_default, geoms, num_geoms); }
 int pt_get_set_geoms_times(PtSetGeomsTimes* out) { return pt_ctx_get_set_geoms_times(g_default, out); }
+int pt_set_materials(const PtMaterial* materials, int num_materials) { return pt_ctx_set_materials(g_default, materials, num_materials); }
+int pt_get_set_materials_times(PtSetMaterialsTimes* out) { return pt_ctx_get_set_materials_times(g_default, out); }
 int pt_get_setup_times(PtSetupTimes* out) { return pt_ctx_get_setup_times(g_default, out); }
 int pt_render_features(int iter_first, int iter_count) { return pt_ctx_render_features(g_default, iter_first, iter_count); }
 int pt_readback_features(float* planes_host) { return pt_ctx_readback_features(g_default, planes_host); }

@@ -85,6 +85,18 @@ struct PtHistoryMotion {
   bool moved = false;
 };
 
+// The materials as a history sees them (PT_HISTORY_MATERIALS): the materials its K was rendered with, and the recolour table of the
+// last lookup that found a material changed (history_recolor_table in pt_post.cpp).
+struct PtHistoryMaterials {
+  std::vector<PtMaterial> materials;  // the kept materials, taken by a capture
+  bool stale = true;             // pt_ctx_set_materials has run since `materials` was copied (or nothing was copied yet)
+  void* d_table = nullptr;       // pthi::kRecolorRow floats per geom, then one kind byte per geom
+  std::vector<float> table;      // what d_table holds
+  std::vector<uint8_t> kind;
+  bool fresh = false;            // the table is that of `materials` and the current materials as they stand; changed: some kind != 0
+  bool changed = false;
+};
+
 // One renderer instance = one device, one stream, one tile of the framebuffer.  The reference keeps this state in
 // file-scope statics (pathtrace.cu:446-456); here it is an object so that one process can drive several GPUs
 // (pt_group_*, pt_group.cpp) — the old single-instance entry points act on a default context.
@@ -193,6 +205,9 @@ struct PtContext : PtShared {
   // The objects' motion (PT_HISTORY_MOTION): the geoms K is aligned to beside hist_cam, and the motion table of the last lookup that
   // found a geom moved (absent until then): pthi::kMotionRow floats per geom, then one kind byte per geom
   PtHistoryMotion hist_motion;
+  // The materials' edits (PT_HISTORY_MATERIALS): the materials K was rendered with, and the recolour table of the last lookup that
+  // found one changed (absent until then)
+  PtHistoryMaterials hist_materials;
   // The noise estimate of the blend (pt_ctx_history_noise): absent until the first estimate
   void* d_hist_noise = nullptr;    // pt_history_noise_bytes(N): the partial sums, SSE_blend, then the plane W
   bool hist_noise = false;         // W holds an estimate of the image as it stood; pt_clear and a move make it absent
@@ -205,7 +220,7 @@ struct PtContext : PtShared {
   // The history probes (pt_ctx_history_probe_keep / _check): all of it absent until the first keep (d_probe) or check (the rest)
   void* d_probe = nullptr;         // PK: 16 B per probe, for the probes of phase 0 (the most of any phase)
   float* d_probe_lam = nullptr;    // L: one float per probe (as many as PK), then the two counts {changed, skipped} as int32
-  uint8_t* d_probe_moved = nullptr;  // one byte per geom: its matrices differ from the kept geoms'
+  uint8_t* d_probe_moved = nullptr;  // one byte per geom: its matrices differ from the kept geoms', or its material from the kept materials'
   std::vector<uint8_t> probe_moved_dev;  // what d_probe_moved holds
   bool probe_kept = false;         // PK holds probes (pt_ctx_history_drop forgets them)
   int probe_first = 0, probe_iters = 0, probe_phase = 0;  // the iterations S held at the keep, and the probes' phase
@@ -214,6 +229,9 @@ struct PtContext : PtShared {
   std::vector<PtGeom> probe_geoms;  // the geoms at the keep
   bool probe_geoms_stale = true;   // pt_ctx_set_geoms has run since probe_geoms was copied (or nothing was copied yet)
   bool probe_geoms_changed = false;  // pt_ctx_set_geoms has run since the keep
+  std::vector<PtMaterial> probe_materials;  // the materials at the keep
+  bool probe_materials_stale = true;     // pt_ctx_set_materials has run since probe_materials was copied (or nothing was copied yet)
+  bool probe_materials_changed = false;  // pt_ctx_set_materials has run since the keep
   bool probe_checked = false;      // L is the check of these probes against the C that is present
   bool probe_applied = false;      // a check has been applied to this C (the next lookup clears it)
   bool feat_fresh = false;         // a feature pass has run since pt_init / pt_clear / the last camera move
@@ -237,6 +255,10 @@ struct PtContext : PtShared {
   DeviceBase device_base;
   PtSetCameraTimes camera_times{};  // the last move (pt_get_set_camera_times)
   PtSetGeomsTimes geoms_times{};    // the last pt_ctx_set_geoms (pt_get_set_geoms_times)
+  // Editing the materials (pt_ctx_set_materials): the PtMaterials the device table was made from, kept from pt_init on (44 B each)
+  std::vector<PtMaterial> materials;
+  PtSetMaterialsTimes materials_times{};  // the last pt_ctx_set_materials (pt_get_set_materials_times)
+  bool hist_reject_stale = false, hist_emitter_stale = false;  // pt_ctx_set_materials has run since d_hist_reject / d_hist_emitter was built
   bool adaptive = false;           // the adaptive state: from the first round to pt_clear
   int adaptive_rounds = 0;
   int64_t adaptive_last = 0;       // highest iteration number folded or merged
@@ -257,6 +279,7 @@ int pt_ctx_admit_state(const PtContext* c, const char* who, bool uniform);
 int pt_ctx_adaptive_refusal(const PtContext* c, const char* who, int iter_first, int group_iters, float max_fraction, bool folds);
 int pt_ctx_camera_refusal(const PtContext* c, const PtCamera* cam, const char* who);  // what pt_set_camera refuses, in its order; nothing changes
 int pt_ctx_geoms_refusal(const PtContext* c, const PtGeom* geoms, int num_geoms, const char* who);  // what pt_set_geoms refuses, in its order; nothing changes
+int pt_ctx_materials_refusal(const PtContext* c, const PtMaterial* materials, int num_materials, const char* who);  // what pt_set_materials refuses, in its order; nothing changes
 int pt_ctx_camera_refusal_ex(const PtContext* c, const PtCamera* cam, uint32_t flags, const char* who);  // ... with the undefined flag bit after the null camera
 int pt_ctx_enter_adaptive(PtContext* c);  // the count plane with the fold's (T, M) in every pixel, unless the context is in the adaptive state already
 // The history of a group (pt_group_history_*): the frame's K, C, VK and VC live with the group; a context is asked for what only it knows.

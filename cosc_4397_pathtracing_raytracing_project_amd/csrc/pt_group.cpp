@@ -464,6 +464,7 @@ int no_flags() { return 0; }
 int history_not_built(const char* who, uint32_t flags) {
   if (flags & PT_HISTORY_VARIANCE) return pt_fail("%s: PT_HISTORY_VARIANCE is not built for a group (the moments kind is: PT_HISTORY_MOMENTS)", who);
   if (flags & PT_HISTORY_FEEDBACK) return pt_fail("%s: PT_HISTORY_FEEDBACK is not built for a group", who);
+  if (flags & PT_HISTORY_MATERIALS) return pt_fail("%s: PT_HISTORY_MATERIALS is not built for a group", who);
   return 0;
 }
 int history_current_moments(const PtGroup* g, const char* who) {
@@ -612,6 +613,17 @@ int pt_group_set_geoms(PtGroup* g, const PtGeom* geoms, int num_geoms) {
   g->hist_motion.geoms_stale = true, g->hist_motion.fresh = false;  // (the next capture keeps these geoms; K and the kept geoms stay until then)
   for (PtContext* c : g->ctx)
     if (pt_ctx_set_geoms(c, geoms, num_geoms)) return -1;
+  return 0;
+}
+
+// pt_ctx_set_materials on every context, asked first in the same way; of the group's history K, VK, the kept camera and geoms stay.
+int pt_group_set_materials(PtGroup* g, const PtMaterial* materials, int num_materials) {
+  if (!g) return pt_fail("pt_group_set_materials: null group");
+  for (PtContext* c : g->ctx)
+    if (pt_ctx_materials_refusal(c, materials, num_materials, "pt_group_set_materials")) return -1;
+  history_current_absent(g);
+  for (PtContext* c : g->ctx)
+    if (pt_ctx_set_materials(c, materials, num_materials)) return -1;
   return 0;
 }
 

@@ -292,9 +292,12 @@ PT_HD void capture_pixel(size_t i, size_t npix, const float* S, const P4* feat, 
 // kFeedback (PT_HISTORY_FEEDBACK, with kMoments only): the filtered colour travels beside the raw chain.  FK(q) = {f.xyz, vf} is read
 // after VK(q), for a tap that passed only; all four components are interpolated with the weights of the colour, and *fc receives FC's
 // value for the pixel, all zero wherever the pixel is rejected.  The cap touches nothing of it.  C and vh are what <.., false> gives.
-template <int kKind, bool kMotion = false, bool kFeedback = false, typename P4>
+//
+// kTell (the recolour step of PT_HISTORY_MATERIALS): *passed = true where the pixel was not rejected; not touched otherwise, nor without kTell.
+template <int kKind, bool kMotion = false, bool kFeedback = false, bool kTell = false, typename P4>
 PT_HD P4 reproject_pixel_of(size_t i, const View& v, const P4* K, const P4* feat, const uint8_t* reject, int32_t num_geoms, const Params& P, const P4* VK,
-                            P4& vh, const Motion& mo = Motion{}, [[maybe_unused]] const P4* FK = nullptr, [[maybe_unused]] P4* fc = nullptr) {
+                            P4& vh, const Motion& mo = Motion{}, [[maybe_unused]] const P4* FK = nullptr, [[maybe_unused]] P4* fc = nullptr,
+                            [[maybe_unused]] bool* passed = nullptr) {
 #pragma clang fp contract(off)
   static_assert(!kFeedback || kKind == kMoments, "the filtered colour travels beside the moments");
   const size_t npix = (size_t)v.W * v.R;
@@ -376,6 +379,7 @@ PT_HD P4 reproject_pixel_of(size_t i, const View& v, const P4* K, const P4* feat
   if constexpr (kKind == kVariance) vh = P4{vaccx / wsum, vaccy / wsum, vaccz / wsum, 0.0f};
   if constexpr (kKind == kMoments) vh = P4{vaccx / wsum, vaccy / wsum, vaccz / wsum, vaccw / wsum};
   if constexpr (kFeedback) *fc = P4{faccx / wsum, faccy / wsum, faccz / wsum, faccw / wsum};
+  if constexpr (kTell) *passed = true;
   return P4{accx / wsum, accy / wsum, accz / wsum, tw < P.cap ? tw : P.cap};
 }
 template <typename P4>
@@ -471,6 +475,77 @@ inline void motion_table(const PtGeom* kept, const PtGeom* cur, int n, float* ta
     bool finite = true;
     for (int j = 0; j < 21; ++j) finite = finite && row[j] - row[j] == 0.0f;
     kind[g] = same ? kStill : (k.type == PT_GEOM_TRIANGLE || c.type == PT_GEOM_TRIANGLE || !finite) ? kCarriesNothing : kMoved;
+  }
+}
+
+// ── the materials' edits since the capture (PT_HISTORY_MATERIALS) ────────────────────────────────────────────────────────
+// kRecolorRow floats and one kind byte per geom (recolor_table below): {r_x, r_y, r_z, +0} and 0 unchanged, 1 recoloured, 2 carries nothing.
+constexpr int kRecolorRow = 4;
+constexpr uint8_t kUnchanged = 0, kRecolored = 1;  // (2: kCarriesNothing)
+struct Recolor {
+  const float* table;
+  const uint8_t* kind;
+};
+// The lookup with the recolour step: reproject_pixel_of<kKind, kMotion> as it stands — not a line of it changes — with the pixel's
+// geom looked at before (kind 2: rejected, C = VC = 0) and the result scaled after (kind 1): h_j = h_j * r_j, vh_j = (vh_j * r_j) * r_j,
+// Th and the moments' rh untouched, for a pixel that was not rejected (kTell: a rejected pixel keeps +0 in every word even where r_j
+// is -0).  An id outside 1 .. num_geoms counts as unchanged.  The row is one 16-byte load.
+template <int kKind, bool kMotion, typename P4>
+PT_HD P4 reproject_pixel_materials(size_t i, const View& v, const P4* K, const P4* feat, const uint8_t* reject, int32_t num_geoms, const Params& P, const P4* VK,
+                                   P4& vh, const Motion& mo, const Recolor& rc) {
+#pragma clang fp contract(off)
+  const size_t npix = (size_t)v.W * v.R;
+  const Surface s = surface(i, npix, feat);
+  const uint8_t kind = s.hit && s.id >= 1 && s.id <= num_geoms ? rc.kind[s.id - 1] : (uint8_t)kUnchanged;
+  if (kind == kCarriesNothing) {
+    if constexpr (kKind != kPlain) vh = P4{0.0f, 0.0f, 0.0f, 0.0f};
+    return P4{0.0f, 0.0f, 0.0f, 0.0f};
+  }
+  bool passed = false;
+  P4 c = reproject_pixel_of<kKind, kMotion, false, true>(i, v, K, feat, reject, num_geoms, P, VK, vh, mo, static_cast<const P4*>(nullptr), static_cast<P4*>(nullptr), &passed);
+  if (kind == kRecolored && passed) {
+    const P4 r = reinterpret_cast<const P4*>(rc.table)[s.id - 1];
+    c.x = c.x * r.x, c.y = c.y * r.y, c.z = c.z * r.z;
+    if constexpr (kKind != kPlain) vh.x = (vh.x * r.x) * r.x, vh.y = (vh.y * r.y) * r.y, vh.z = (vh.z * r.z) * r.z;
+  }
+  return c;
+}
+// The whole tile on the host; mo: the motion table, or nullptr (the lookup without PT_HISTORY_MOTION).  VK, VC unused (nullptr) for kPlain.
+template <int kKind>
+inline void reproject_materials_host(const View& v, const float* K, const float* feat, const uint8_t* reject, int32_t num_geoms, const Params& P, const float* VK,
+                                     const Motion* mo, const Recolor& rc, float* C, float* VC) {
+  const size_t npix = (size_t)v.W * v.R;
+  F4 *out = reinterpret_cast<F4*>(C), *vout = reinterpret_cast<F4*>(VC);
+  const F4 *k4 = reinterpret_cast<const F4*>(K), *f4 = reinterpret_cast<const F4*>(feat), *vk4 = reinterpret_cast<const F4*>(VK);
+  F4 unused;
+  for (size_t i = 0; i < npix; ++i)
+    out[i] = mo ? reproject_pixel_materials<kKind, true>(i, v, k4, f4, reject, num_geoms, P, vk4, kKind == kPlain ? unused : vout[i], *mo, rc)
+                : reproject_pixel_materials<kKind, false>(i, v, k4, f4, reject, num_geoms, P, vk4, kKind == kPlain ? unused : vout[i], Motion{}, rc);
+}
+// The recolour table of pt_amd.h (pt_history_recolor_host): mk per material from the kept and the current one, then row g and kind[g]
+// from geoms[g].materialid (a material id outside 0 .. num_materials - 1: unchanged).  mk and ratio: num_materials entries of scratch.
+inline uint8_t recolor_material(const PtMaterial& k, const PtMaterial& c, float ratio[3]) {
+#pragma clang fp contract(off)
+  ratio[0] = ratio[1] = ratio[2] = 0.0f;
+  const bool rest_same = __builtin_memcmp(k.specular_color, c.specular_color, 12) == 0 && __builtin_memcmp(&k.hasReflective, &c.hasReflective, 4) == 0 &&
+                         __builtin_memcmp(&k.hasRefractive, &c.hasRefractive, 4) == 0 && __builtin_memcmp(&k.emittance, &c.emittance, 4) == 0;
+  if (rest_same && __builtin_memcmp(k.color, c.color, 12) == 0) return kUnchanged;
+  if (!rest_same || k.emittance > 0.0f || k.hasReflective > 0.0f) return kCarriesNothing;
+  float r[3];
+  for (int j = 0; j < 3; ++j) {
+    if (!(k.color[j] > 0.0f) || !(c.color[j] >= 0.0f)) return kCarriesNothing;
+    r[j] = c.color[j] / k.color[j];
+    if (!(r[j] - r[j] == 0.0f)) return kCarriesNothing;
+  }
+  ratio[0] = r[0], ratio[1] = r[1], ratio[2] = r[2];
+  return kRecolored;
+}
+inline void recolor_table(const PtMaterial* kept, const PtMaterial* cur, int num_materials, const PtGeom* geoms, int num_geoms, float* table, uint8_t* kind) {
+  for (int g = 0; g < num_geoms; ++g) {
+    float* row = table + (size_t)g * kRecolorRow;
+    row[0] = row[1] = row[2] = row[3] = 0.0f;
+    const int32_t m = geoms[g].materialid;
+    kind[g] = m >= 0 && m < num_materials ? recolor_material(kept[m], cur[m], row) : kUnchanged;
   }
 }
 inline void blend_host(size_t npix, const float* S, float samples, const float* C, float* rgb_avg) {

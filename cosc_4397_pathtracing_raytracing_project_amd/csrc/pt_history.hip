@@ -104,6 +104,29 @@ __global__ __launch_bounds__(kBlock) void k_history_reproject_motion(int npix, V
   }
 }
 
+// ... with the materials' edits (PT_HISTORY_MATERIALS): kernels of their own again.  Per pixel one byte of `rkind` for a hit and, for a
+// recoloured geom, the 16 B of its row of `recolor` (one load; a few rows per frame: they stay in the caches); three multiplies more,
+// nine with a variance or moments side.  table, mkind: read for kMotion only.  In...: nothing, or VK and VC
+template <int kKind, bool kMotion, typename... In>
+__global__ __launch_bounds__(kBlock) void k_history_reproject_materials(int npix, View v, const V4* __restrict__ K, const V4* __restrict__ feat,
+                                                                        const uint8_t* __restrict__ reject, int num_geoms, Params P,
+                                                                        const float* __restrict__ table, const uint8_t* __restrict__ mkind,
+                                                                        const float* __restrict__ recolor, const uint8_t* __restrict__ rkind,
+                                                                        V4* __restrict__ C, In... in) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= npix) return;
+  const pthi::Motion mo{table, mkind};
+  const pthi::Recolor rc{recolor, rkind};
+  V4 vh;
+  if constexpr (kKind != pthi::kPlain) {
+    const auto [VK, VC] = pthi::VarReproject<V4>{in...};
+    C[i] = pthi::reproject_pixel_materials<kKind, kMotion>((size_t)i, v, K, feat, reject, num_geoms, P, VK, vh, mo, rc);
+    VC[i] = vh;
+  } else {
+    C[i] = pthi::reproject_pixel_materials<kKind, kMotion>((size_t)i, v, K, feat, reject, num_geoms, P, static_cast<const V4*>(nullptr), vh, mo, rc);
+  }
+}
+
 // ... with the filtered colour beside the moments (PT_HISTORY_FEEDBACK): C and VC are the bits the kernels above write.  table, mkind:
 // read for kMotion only.
 template <bool kMotion>
@@ -272,6 +295,43 @@ int pt_history_reproject_motion_launch(hipStream_t stream, uint32_t kind, const 
                        table_dev, kind_dev, C, VK, VC);
   else
     hipLaunchKernelGGL(k_history_reproject_motion<pthi::kPlain>, grid, block, 0, stream, npix, v, K, feat, reject_dev, num_geoms, P, table_dev, kind_dev, C);
+  return launched(who);
+}
+
+template <int kKind, bool kMotion>
+static void reproject_materials_launch(hipStream_t stream, int npix, const pthi::View& v, const V4* K, const V4* feat, const uint8_t* reject_dev, int num_geoms,
+                                       const pthi::Params& P, const float* table_dev, const uint8_t* kind_dev, const float* recolor_dev, const uint8_t* rkind_dev, V4* C,
+                                       const V4* VK, V4* VC) {
+  const dim3 grid((npix + kBlock - 1) / kBlock), block(kBlock);
+  if constexpr (kKind == pthi::kPlain)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_history_reproject_materials<kKind, kMotion>), grid, block, 0, stream, npix, v, K, feat, reject_dev, num_geoms, P, table_dev, kind_dev,
+                       recolor_dev, rkind_dev, C);
+  else
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_history_reproject_materials<kKind, kMotion, const V4*, V4*>), grid, block, 0, stream, npix, v, K, feat, reject_dev, num_geoms, P,
+                       table_dev, kind_dev, recolor_dev, rkind_dev, C, VK, VC);
+}
+// The lookup with PT_HISTORY_MATERIALS: kind as pt_history_reproject_motion_launch takes it; recolor_dev pthi::kRecolorRow floats (16-byte
+// aligned) and rkind_dev one byte per geom (num_geoms >= 1); table_dev / kind_dev both null (no geom moved, or no PT_HISTORY_MOTION) or both given.
+int pt_history_reproject_materials_launch(hipStream_t stream, uint32_t kind, const pthi::View& v, const void* kept_dev, const float* planes_dev,
+                                          const uint8_t* reject_dev, int num_geoms, const pthi::Params& P, void* current_dev, const void* kept_var_dev,
+                                          void* current_var_dev, const float* table_dev, const uint8_t* kind_dev, const float* recolor_dev, const uint8_t* rkind_dev) {
+  const char* who = "pt_history_reproject_ex";
+  if (bad_frame(v.W, v.R)) return pt_fail("%s: a tile of %d x %d pixels is not supported", who, v.W, v.R);
+  const bool with = kind != 0, motion = table_dev != nullptr;
+  if (!kept_dev || !planes_dev || !current_dev || num_geoms < 1 || !recolor_dev || !rkind_dev || ((uintptr_t)recolor_dev & 15) || motion != (kind_dev != nullptr) ||
+      (!P.keep_view_dependent && !reject_dev) || (kind != 0 && kind != PT_HISTORY_VARIANCE && kind != PT_HISTORY_MOMENTS) || with != (kept_var_dev != nullptr) ||
+      with != (current_var_dev != nullptr))
+    return pt_fail("%s: bad argument (materials)", who);
+  const int npix = v.W * v.R;
+  const V4 *K = static_cast<const V4*>(kept_dev), *feat = reinterpret_cast<const V4*>(planes_dev), *VK = static_cast<const V4*>(kept_var_dev);
+  V4 *C = static_cast<V4*>(current_dev), *VC = static_cast<V4*>(current_var_dev);
+  auto go = [&](auto k, auto m) {
+    reproject_materials_launch<decltype(k)::value, decltype(m)::value>(stream, npix, v, K, feat, reject_dev, num_geoms, P, table_dev, kind_dev, recolor_dev, rkind_dev, C, VK, VC);
+  };
+  auto by_motion = [&](auto k) { motion ? go(k, std::true_type{}) : go(k, std::false_type{}); };
+  if (kind == PT_HISTORY_VARIANCE) by_motion(std::integral_constant<int, pthi::kVariance>{});
+  else if (kind == PT_HISTORY_MOMENTS) by_motion(std::integral_constant<int, pthi::kMoments>{});
+  else by_motion(std::integral_constant<int, pthi::kPlain>{});
   return launched(who);
 }
 
@@ -548,6 +608,45 @@ extern "C" int pt_history_reproject_motion_host(int w, int rows, int row0, const
   if (flags & PT_HISTORY_VARIANCE) pthi::reproject_motion_host<pthi::kVariance>(v, kept_planes, feature_planes, reject_geom, num_geoms, P, kept_var, mo, current_plane, current_var);
   else if (flags & PT_HISTORY_MOMENTS) pthi::reproject_motion_host<pthi::kMoments>(v, kept_planes, feature_planes, reject_geom, num_geoms, P, kept_var, mo, current_plane, current_var);
   else pthi::reproject_motion_host<pthi::kPlain>(v, kept_planes, feature_planes, reject_geom, num_geoms, P, nullptr, mo, current_plane, nullptr);
+  return 0;
+}
+
+// ---- the materials' edits (PT_HISTORY_MATERIALS) -----------------------------------------------------------------------------
+extern "C" int pt_history_recolor_host(const PtMaterial* kept, const PtMaterial* cur, int num_materials, const PtGeom* geoms, int num_geoms, float* table,
+                                       uint8_t* kind) {
+  if (!kept || !cur || num_materials <= 0 || !geoms || num_geoms <= 0 || !table || !kind) return pt_fail("pt_history_recolor_host: bad argument");
+  pthi::recolor_table(kept, cur, num_materials, geoms, num_geoms, table, kind);
+  return 0;
+}
+int pt_history_materials_check(const char* who, uint32_t flags, int num_geoms, const float* table, const uint8_t* kind, const float* recolor, const uint8_t* rkind,
+                               const float* kept_var, const float* current_var) {
+  constexpr uint32_t defined = PT_HISTORY_VARIANCE | PT_HISTORY_MOMENTS | PT_HISTORY_MOTION | PT_HISTORY_MATERIALS;
+  if (flags & ~defined)
+    return pt_fail("%s: undefined flag bit(s) 0x%x (defined: PT_HISTORY_VARIANCE, PT_HISTORY_MOMENTS, PT_HISTORY_MOTION, PT_HISTORY_MATERIALS)", who, flags & ~defined);
+  if ((flags & PT_HISTORY_VARIANCE) && (flags & PT_HISTORY_MOMENTS)) return pt_fail("%s: the flags PT_HISTORY_VARIANCE and PT_HISTORY_MOMENTS exclude each other", who);
+  if (num_geoms < 1 || !recolor || !rkind) return pt_fail("%s: a recolour table and kinds for at least one geom are needed", who);
+  if (((flags & PT_HISTORY_MOTION) && (!table || !kind)) || (!table != !kind)) return pt_fail("%s: the motion table and its kinds come together, and with PT_HISTORY_MOTION", who);
+  for (int g = 0; g < num_geoms; ++g)
+    if (rkind[g] > pthi::kCarriesNothing || (kind && kind[g] > pthi::kCarriesNothing))
+      return pt_fail("%s: kind[%d] = %d (motion) or %d (recolour) is not 0, 1 or 2", who, g, kind ? (int)kind[g] : 0, (int)rkind[g]);
+  if ((flags & (PT_HISTORY_VARIANCE | PT_HISTORY_MOMENTS)) && (!kept_var || !current_var)) return pt_fail("%s: null argument", who);
+  return 0;
+}
+extern "C" int pt_history_reproject_materials_host(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
+                                                   const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, const float* kept_var,
+                                                   const float* table, const uint8_t* kind, const float* recolor, const uint8_t* rkind, uint32_t flags,
+                                                   float* current_plane, float* current_var) {
+  pthi::Params P{};
+  const char* who = "pt_history_reproject_materials_host";
+  if (pt_history_reproject_check(who, w, rows, row0, kept_cam, kept_planes, feature_planes, reject_geom, num_geoms, opt, current_plane, &P)) return -1;
+  if (pt_history_materials_check(who, flags, num_geoms, table, kind, recolor, rkind, kept_var, current_var)) return -1;
+  const pthi::View v = pthi::make_view(*kept_cam, rows, row0);
+  const pthi::Motion mo{table, kind};
+  const pthi::Motion* mop = table ? &mo : nullptr;
+  const pthi::Recolor rc{recolor, rkind};
+  if (flags & PT_HISTORY_VARIANCE) pthi::reproject_materials_host<pthi::kVariance>(v, kept_planes, feature_planes, reject_geom, num_geoms, P, kept_var, mop, rc, current_plane, current_var);
+  else if (flags & PT_HISTORY_MOMENTS) pthi::reproject_materials_host<pthi::kMoments>(v, kept_planes, feature_planes, reject_geom, num_geoms, P, kept_var, mop, rc, current_plane, current_var);
+  else pthi::reproject_materials_host<pthi::kPlain>(v, kept_planes, feature_planes, reject_geom, num_geoms, P, nullptr, mop, rc, current_plane, nullptr);
   return 0;
 }
 

@@ -161,6 +161,14 @@ int pt_history_reproject_motion_launch(hipStream_t stream, uint32_t kind, const 
 // What the host and stage forms of that lookup refuse after pt_history_reproject_check: the flag word, the table, the kinds, VK / VC.
 int pt_history_motion_check(const char* who, uint32_t flags, int num_geoms, const float* table, const uint8_t* kind, const float* kept_var,
                             const float* current_var);
+// The lookup with the materials' edits (PT_HISTORY_MATERIALS): kind as above; recolor_dev pthi::kRecolorRow floats (16-byte aligned) and
+// rkind_dev one byte per geom (num_geoms >= 1); table_dev and kind_dev as above, or both nullptr (nothing moved, or no PT_HISTORY_MOTION).
+int pt_history_reproject_materials_launch(hipStream_t stream, uint32_t kind, const pthi::View& v, const void* kept_dev, const float* planes_dev,
+                                          const uint8_t* reject_dev, int num_geoms, const pthi::Params& P, void* current_dev, const void* kept_var_dev,
+                                          void* current_var_dev, const float* table_dev, const uint8_t* kind_dev, const float* recolor_dev, const uint8_t* rkind_dev);
+// What the host and stage forms of that lookup refuse after pt_history_reproject_check: the flag word, the tables, the kinds, VK / VC.
+int pt_history_materials_check(const char* who, uint32_t flags, int num_geoms, const float* table, const uint8_t* kind, const float* recolor, const uint8_t* rkind,
+                               const float* kept_var, const float* current_var);
 // The moments lookup with the filtered colour (PT_HISTORY_FEEDBACK): FK beside VK, FC beside VC, `pixels` float4 each; table_dev and
 // kind_dev as above, or both nullptr (nothing moved).  C and VC are the bits pt_history_reproject_moments_launch / _motion_launch write.
 inline size_t pt_history_feedback_bytes(size_t pixels) { return 48 * pixels; }  // the feedback state: three planes, the roles FK, FC and P

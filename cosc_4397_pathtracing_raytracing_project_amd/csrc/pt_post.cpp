@@ -511,15 +511,17 @@ static const char kNoFeatures[] = "%s: no feature pass has been rendered since t
 
 static pthi::V4* history_var_plane(const Ctx& g, int plane) { return static_cast<pthi::V4*>(g.d_hist_var) + (size_t)plane * g.N; }  // 0: VK, 1: VC
 // An undefined flag bit: what the _ex forms refuse right after a failed context.
-// motion: the lookup's word, which also defines PT_HISTORY_MOTION (alone or beside one of the two).
+// motion: the lookup's word, which also defines PT_HISTORY_MOTION and PT_HISTORY_MATERIALS (alone or beside one of the two).
 // PT_HISTORY_FEEDBACK is defined in both words, beside PT_HISTORY_MOMENTS only.
 static int history_flags(const char* who, uint32_t flags, bool motion = false) {
   constexpr uint32_t kinds = PT_HISTORY_VARIANCE | PT_HISTORY_MOMENTS;
-  const uint32_t defined = kinds | PT_HISTORY_FEEDBACK | (motion ? PT_HISTORY_MOTION : 0u);
+  const uint32_t defined = kinds | PT_HISTORY_FEEDBACK | (motion ? PT_HISTORY_MOTION | PT_HISTORY_MATERIALS : 0u);
   if (flags & ~defined)
     return pt_fail("%s: undefined flag bit(s) 0x%x (defined: PT_HISTORY_VARIANCE, PT_HISTORY_MOMENTS%s, PT_HISTORY_FEEDBACK)", who, flags & ~defined,
-                   motion ? ", PT_HISTORY_MOTION" : "");
+                   motion ? ", PT_HISTORY_MOTION, PT_HISTORY_MATERIALS" : "");
   if ((flags & kinds) == kinds) return pt_fail("%s: the flags PT_HISTORY_VARIANCE and PT_HISTORY_MOMENTS exclude each other", who);
+  if ((flags & PT_HISTORY_MATERIALS) && (flags & PT_HISTORY_FEEDBACK))  // (the lookup's word only: the capture's has refused the bit above)
+    return pt_fail("%s: PT_HISTORY_MATERIALS is not built beside PT_HISTORY_FEEDBACK: FC carries one variance for three channels, which a per-channel factor cannot scale", who);
   if ((flags & PT_HISTORY_FEEDBACK) && (flags & PT_HISTORY_VARIANCE))
     return pt_fail("%s: PT_HISTORY_FEEDBACK travels beside the moments, not with PT_HISTORY_VARIANCE", who);
   if ((flags & PT_HISTORY_FEEDBACK) && !(flags & PT_HISTORY_MOMENTS))
@@ -582,6 +584,7 @@ static int history_capture(PtContext* c, const char* who, float samples, uint32_
   }
   g.hist_cam = g.cam;
   if (PtHistoryMotion& hm = g.hist_motion; hm.geoms_stale) hm.geoms = g.camera_base.geoms, hm.geoms_stale = false, hm.fresh = false;  // the kept geoms: retaken only after a pt_set_geoms
+  if (PtHistoryMaterials& hm = g.hist_materials; hm.stale) hm.materials = g.materials, hm.stale = false, hm.fresh = false;  // the kept materials: retaken only after a pt_set_materials
   g.hist_kept = true;
   g.hist_var_kept = flags & ~PT_HISTORY_FEEDBACK;  // a plain capture: kept without variance or moments
   if (fb) std::swap(g.fb_plane_kept, g.fb_plane_pending), g.fb_pending = false;  // FK := P: the roles change, no bytes move
@@ -592,12 +595,12 @@ int pt_ctx_history_capture(PtContext* c, float samples) { return history_capture
 int pt_ctx_history_capture_ex(PtContext* c, float samples, uint32_t flags) { return history_capture(c, "pt_history_capture_ex", samples, flags, true); }
 
 // A per-geom table of pt_amd.h, one byte per geom: 1 where `field` of the geom's material is positive (reject_geom: reflective;
-// emitter_geom: emittance), from the tables the renderer holds — the geoms' material ids (host) and the materials (device).  Blocking;
-// once per context and table.
-static int history_geom_table(Ctx& g, uint8_t*& d_table, float ptd::Mat::*field) {
-  if (d_table) return 0;
-  std::vector<ptd::Mat> mats((size_t)std::max(g.scene.num_mats, 0));
-  if (!mats.empty()) HIP_OK(hipMemcpy(mats.data(), g.scene.mats, mats.size() * sizeof(ptd::Mat), hipMemcpyDeviceToHost));
+// emitter_geom: emittance), from the tables the renderer holds on the host — the geoms' material ids and the materials.  Blocking;
+// once per context and table, and once more after every pt_ctx_set_materials (stale; that call synchronised, and nothing has read the
+// table since, so it is written in place).
+static int history_geom_table(Ctx& g, uint8_t*& d_table, bool& stale, float ptd::Mat::*field) {
+  if (d_table && !stale) return 0;
+  const std::vector<ptd::Mat> mats = pt::material_table(g.materials.data(), (int)g.materials.size());  // what the device table holds
   const std::vector<PtGeom>& geoms = g.camera_base.geoms;
   std::vector<uint8_t> table(std::max<size_t>(geoms.size(), 1), 0);
   for (size_t i = 0; i < geoms.size(); ++i) {
@@ -606,9 +609,10 @@ static int history_geom_table(Ctx& g, uint8_t*& d_table, float ptd::Mat::*field)
   }
   if (ensure(g, d_table, table.size())) return -1;
   HIP_OK(hipMemcpy(d_table, table.data(), table.size(), hipMemcpyHostToDevice));
+  stale = false;
   return 0;
 }
-static int history_reject_table(Ctx& g) { return history_geom_table(g, g.d_hist_reject, &ptd::Mat::reflective); }
+static int history_reject_table(Ctx& g) { return history_geom_table(g, g.d_hist_reject, g.hist_reject_stale, &ptd::Mat::reflective); }
 
 // The motion table of the kept geoms of `hm` and the current geoms (pthi::motion_table) on g's device, for a lookup with
 // PT_HISTORY_MOTION; hm: the context's own, or the one a group keeps for the frame's K (then g is the group's root context).
@@ -640,12 +644,40 @@ static int history_motion_table(Ctx& g, PtHistoryMotion& hm, bool* moved) {
   return 0;
 }
 
+// The recolour table of the kept materials of `hm` and the current ones (pthi::recolor_table) on g's device, for a lookup with
+// PT_HISTORY_MATERIALS, as history_motion_table: *edited == false: every material is what it was at the capture; nothing was allocated
+// or uploaded and the caller launches the kernel of the same call without the flag.  Computed by the first lookup after a capture
+// that retook the materials or a pt_ctx_set_materials, uploaded when it differs from what the device holds (synchronises then).
+static int history_recolor_table(Ctx& g, PtHistoryMaterials& hm, bool* edited) {
+  const std::vector<PtGeom>& geoms = g.camera_base.geoms;
+  const size_t n = geoms.size();
+  *edited = false;
+  if (hm.materials.size() != g.materials.size() || n == 0) return 0;  // (nothing kept yet: the caller has refused already — every capture keeps the materials)
+  if (hm.fresh) return *edited = hm.changed, 0;
+  std::vector<float> table(n * pthi::kRecolorRow);
+  std::vector<uint8_t> kind(n);
+  pthi::recolor_table(hm.materials.data(), g.materials.data(), (int)g.materials.size(), geoms.data(), (int)n, table.data(), kind.data());
+  for (uint8_t k : kind) *edited = *edited || k != pthi::kUnchanged;
+  hm.changed = *edited;
+  if (!*edited) return hm.fresh = true, 0;
+  const size_t table_bytes = table.size() * sizeof(float);
+  if (ensure(g, hm.d_table, table_bytes + n)) return -1;
+  if (table != hm.table || kind != hm.kind) {
+    HIP_OK(hipStreamSynchronize(g.stream));  // an earlier lookup may still read the rows
+    HIP_OK(hipMemcpy(hm.d_table, table.data(), table_bytes, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(static_cast<char*>(hm.d_table) + table_bytes, kind.data(), n, hipMemcpyHostToDevice));
+    hm.table = std::move(table), hm.kind = std::move(kind);
+  }
+  hm.fresh = true;
+  return 0;
+}
+
 static int history_reproject(PtContext* c, const char* who, const PtHistoryOptions* opt, uint32_t flags, bool ex) {
   if (need(c, who)) return -1;
   Ctx& g = *c;
   if (ex && (admit(g, who, kNotFailed) || history_flags(who, flags, true))) return -1;
-  const bool motion = (flags & PT_HISTORY_MOTION) != 0, fb = (flags & PT_HISTORY_FEEDBACK) != 0;
-  flags &= ~(PT_HISTORY_MOTION | PT_HISTORY_FEEDBACK);  // what is left names the kind: 0, PT_HISTORY_VARIANCE or PT_HISTORY_MOMENTS
+  const bool motion = (flags & PT_HISTORY_MOTION) != 0, fb = (flags & PT_HISTORY_FEEDBACK) != 0, materials = (flags & PT_HISTORY_MATERIALS) != 0;
+  flags &= ~(PT_HISTORY_MOTION | PT_HISTORY_FEEDBACK | PT_HISTORY_MATERIALS);  // what is left names the kind: 0, PT_HISTORY_VARIANCE or PT_HISTORY_MOMENTS
   if (history_admit(g, who)) return -1;
   if (!g.d_hist || !g.hist_kept) return pt_fail("%s: nothing has been captured (pt_history_capture)", who);
   if (!g.d_feat || !g.feat_fresh) return pt_fail(kNoFeatures, who);
@@ -665,7 +697,17 @@ static int history_reproject(PtContext* c, const char* who, const PtHistoryOptio
   const int num_geoms = (int)g.camera_base.geoms.size();
   bool moved = false;
   if (motion && history_motion_table(g, g.hist_motion, &moved)) return -1;
-  if (fb) {
+  bool edited = false;
+  if (materials && history_recolor_table(g, g.hist_materials, &edited)) return -1;
+  if (edited) {  // (never beside fb: the flag word refused that)
+    const float* table = moved ? static_cast<const float*>(g.hist_motion.d_table) : nullptr;
+    const uint8_t* kind = moved ? reinterpret_cast<const uint8_t*>(table + (size_t)num_geoms * pthi::kMotionRow) : nullptr;
+    const float* recolor = static_cast<const float*>(g.hist_materials.d_table);
+    const uint8_t* rkind = reinterpret_cast<const uint8_t*>(recolor + (size_t)num_geoms * pthi::kRecolorRow);
+    if (pt_history_reproject_materials_launch(g.stream, flags, v, g.d_hist, feat, g.d_hist_reject, num_geoms, P, history_plane(g, pthi::kKeptPlanes),
+                                              flags ? history_var_plane(g, 0) : nullptr, flags ? history_var_plane(g, 1) : nullptr, table, kind, recolor, rkind))
+      return -1;
+  } else if (fb) {
     const float* table = moved ? static_cast<const float*>(g.hist_motion.d_table) : nullptr;
     const uint8_t* kind = moved ? reinterpret_cast<const uint8_t*>(table + (size_t)num_geoms * pthi::kMotionRow) : nullptr;
     if (pt_history_reproject_feedback_launch(g.stream, v, g.d_hist, feat, g.d_hist_reject, num_geoms, P, history_plane(g, pthi::kKeptPlanes), history_var_plane(g, 0),
@@ -893,7 +935,7 @@ int pt_ctx_readback_history_variance(PtContext* c, float* kept_var, float* curre
 
 // ---- the history round: a group of further iterations for the pixels whose history is short --------------------------------
 // emitter_geom of pt_amd.h, as history_reject_table.
-static int history_emitter_table(Ctx& g) { return history_geom_table(g, g.d_hist_emitter, &ptd::Mat::emittance); }
+static int history_emitter_table(Ctx& g) { return history_geom_table(g, g.d_hist_emitter, g.hist_emitter_stale, &ptd::Mat::emittance); }
 
 // What the round and the round over a caller's list refuse first: a failed context, the iteration range, the convergence metric.
 static int history_round_head(const Ctx& g, const char* who, int iter_first, int group_iters) {
@@ -1065,13 +1107,15 @@ int pt_ctx_history_probe_keep(PtContext* c, int iter_first, int iter_count, int 
   g.probe_cam = g.cam;
   if (g.probe_geoms_stale) g.probe_geoms = g.camera_base.geoms, g.probe_geoms_stale = false;  // retaken only after a pt_set_geoms
   g.probe_geoms_changed = false;
+  if (g.probe_materials_stale) g.probe_materials = g.materials, g.probe_materials_stale = false;  // retaken only after a pt_set_materials
+  g.probe_materials_changed = false;
   g.probe_kept = true;
   g.probe_checked = false;  // L, if any, was the check of other probes
   return 0;
 }
 
-// `moved` of pt_amd.h on the device: all zero unless pt_set_geoms has run since the keep; uploaded only when it differs from what the
-// device holds (from a member that outlives the copy).
+// `moved` of pt_amd.h on the device: all zero unless pt_set_geoms or pt_set_materials has run since the keep; uploaded only when it
+// differs from what the device holds (from a member that outlives the copy).
 static int probe_moved_table(Ctx& g) {
   const std::vector<PtGeom>& cur = g.camera_base.geoms;
   const size_t n = cur.size();
@@ -1079,6 +1123,15 @@ static int probe_moved_table(Ctx& g) {
   if (g.probe_geoms_changed) {
     if (g.probe_geoms.size() == n) pthi::probe_moved(g.probe_geoms.data(), cur.data(), (int)n, moved.data());
     else std::fill(moved.begin(), moved.end(), (uint8_t)1);
+  }
+  if (g.probe_materials_changed) {  // ... or its material is not what it was at the keep (pthi::recolor_material's mk != 0)
+    const std::vector<PtMaterial>&kept = g.probe_materials, &now = g.materials;
+    for (size_t i = 0; i < n; ++i) {
+      const int32_t m = cur[i].materialid;
+      float ratio[3];
+      if (kept.size() != now.size()) moved[i] = 1;
+      else if (m >= 0 && (size_t)m < now.size() && pthi::recolor_material(kept[(size_t)m], now[(size_t)m], ratio) != pthi::kUnchanged) moved[i] = 1;
+    }
   }
   const bool first = !g.d_probe_moved;
   if (ensure(g, g.d_probe_moved, moved.size(), Zero::on_stream)) return -1;
@@ -1340,6 +1393,7 @@ int pt_ctx_history_capture_adaptive(PtContext* c) {
     return -1;
   g.hist_cam = g.cam;
   if (PtHistoryMotion& hm = g.hist_motion; hm.geoms_stale) hm.geoms = g.camera_base.geoms, hm.geoms_stale = false, hm.fresh = false;  // as in any capture
+  if (PtHistoryMaterials& hm = g.hist_materials; hm.stale) hm.materials = g.materials, hm.stale = false, hm.fresh = false;  // ... and the materials
   g.hist_kept = true;
   g.hist_var_kept = PT_HISTORY_VARIANCE;
   g.fb_kept = false;  // kept without feedback

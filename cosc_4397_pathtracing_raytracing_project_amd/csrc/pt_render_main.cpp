@@ -3,7 +3,7 @@
 // state.iterations iterations, write the PNG saveImage() would write.  Flags exist only because
 // the reference takes resolution, iteration count and depth from the scene file (scene.cpp:103-114).
 //
-//   pt_render SCENE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] [--orbit N [--device-tables] [--move G:DX,DY,DZ [--orbit-still]] [--reproject [--history-cap C] [--denoise-history [--history-moments [--history-feedback [--feedback-level L] [--feedback-variance V]]] [--history-threshold E [--history-threshold-cap F] [--history-threshold-min-pixels P] [--history-threshold-group G]]] [--history-extra G [--history-min M] [--history-extra-cap F]] [--history-probe [--probe-radius R] [--probe-gain X]]]]
+//   pt_render SCENE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] [--orbit N [--device-tables] [--move G:DX,DY,DZ] [--recolor M:DR,DG,DB] [--emit M:DE] [--orbit-still] [--reproject [--history-cap C] [--denoise-history [--history-moments [--history-feedback [--feedback-level L] [--feedback-variance V]]] [--history-threshold E [--history-threshold-cap F] [--history-threshold-min-pixels P] [--history-threshold-group G]]] [--history-extra G [--history-min M] [--history-extra-cap F]] [--history-probe [--probe-radius R] [--probe-gain X]]]]
 //                       [--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa]
 //                       [--preview N] [--convergence N | --reference FILE.pfm] [--clean-db X] [--features]
 //                       [--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]]
@@ -95,6 +95,10 @@
 // pixels whose carried weight is below --history-min M (default 4) G further iterations, --history-extra-cap F of the frame at the
 // most (default 1); resolve, filter and capture then count them per pixel.  Frame f takes spp + G iteration numbers: the uniform ones
 // f (spp + G) + 1 .., then G for the round.  Prints per frame `history: frame f: <G> extra over <m> of <fresh> fresh pixels`.
+// --recolor M:DR,DG,DB / --emit M:DE (with --orbit; each may stand where --move stands, and composes with it; works with --gpus / --devices;
+// excludes --history-feedback): from frame 1 on the colour of material M grows by the step (--emit: its emittance by DE) before the camera
+// moves, and the live renderer takes the new materials (pt_set_materials, pt_group_set_materials).  Prints `material: frame f: material M
+// colour r g b emittance e, set_materials a ms`.  With --reproject the lookup passes PT_HISTORY_MATERIALS.
 // --orbit-still (with --orbit N --move): the N frames keep the scene's camera — no pt_scene_orbit, no pt_set_camera between frames; only
 // the object moves.  --history-probe (with --orbit N --orbit-still --move --reproject): the history probes (pt_history_probe_*).  A
 // frame's order is render, features, lookup (with PT_HISTORY_MOTION), from frame 1 on pt_history_probe_check, then
@@ -114,6 +118,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/pathtrace_amd.hpp"
@@ -122,7 +127,7 @@
 int main(int argc, char** argv) {
   if (argc < 2) {
     std::printf("Usage: %s SCENEFILE.txt [--res WxH] [--spp N] [--depth D] [--out PREFIX] [--pfm] [--hdr] "
-                "[--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa] [--orbit N [--device-tables] [--reproject [--history-cap C] [--denoise-history [--history-moments [--history-feedback [--feedback-level L] [--feedback-variance V]]] [--history-threshold E [--history-threshold-cap F] [--history-threshold-min-pixels P] [--history-threshold-group G]]] [--history-extra G [--history-min M] [--history-extra-cap F]] [--history-probe [--probe-radius R] [--probe-gain X]]] [--move G:DX,DY,DZ [--orbit-still]]] [--preview N] "
+                "[--arith exact|fma|fast] [--gpus K | --devices LIST] [--transport rccl|copy] [--stamp] [--aa] [--orbit N [--device-tables] [--reproject [--history-cap C] [--denoise-history [--history-moments [--history-feedback [--feedback-level L] [--feedback-variance V]]] [--history-threshold E [--history-threshold-cap F] [--history-threshold-min-pixels P] [--history-threshold-group G]]] [--history-extra G [--history-min M] [--history-extra-cap F]] [--history-probe [--probe-radius R] [--probe-gain X]]] [--move G:DX,DY,DZ] [--recolor M:DR,DG,DB] [--emit M:DE] [--orbit-still]] [--preview N] "
                 "[--convergence N | --reference FILE.pfm] [--clean-db X] [--features] "
                 "[--denoise [--denoise-levels N] [--denoise-sigma C,N,P] [--denoise-keep-albedo]] [--denoise-guided] [--until-db X [--until-group G] [--adaptive F [--denoise-adaptive]]] "
                 "[--adaptive-threshold E [--adaptive-cap F] [--adaptive-min-pixels P] [--until-group G] [--denoise-adaptive]]\n", argv[0]);
@@ -149,6 +154,9 @@ int main(int argc, char** argv) {
   PtHistoryRoundOptions round_opt{};                // --history-min M, --history-extra-cap F (0: the defaults)
   bool history_min_given = false, history_extra_cap_given = false;
   bool orbit_still = false;                         // --orbit-still
+  bool recolor = false, emit = false;               // --recolor M:DR,DG,DB, --emit M:DE
+  int recolor_mat = 0, emit_mat = 0;
+  float recolor_step[3] = {0.0f, 0.0f, 0.0f}, emit_step = 0.0f;
   bool history_probe = false;                       // --history-probe
   PtHistoryProbeOptions probe_opt{};                // --probe-radius R, --probe-gain X (0: the defaults)
   bool probe_opt_given = false;
@@ -287,6 +295,22 @@ int main(int argc, char** argv) {
       }
     }
     else if (!std::strcmp(argv[i], "--orbit-still")) orbit_still = true;
+    else if (!std::strcmp(argv[i], "--recolor") && i + 1 < argc) {
+      char tail = 0;
+      if (std::sscanf(argv[++i], "%d:%f,%f,%f%c", &recolor_mat, &recolor_step[0], &recolor_step[1], &recolor_step[2], &tail) != 4 || recolor_mat < 0 ||
+          !std::isfinite(recolor_step[0]) || !std::isfinite(recolor_step[1]) || !std::isfinite(recolor_step[2])) {
+        std::fprintf(stderr, "--recolor wants M:DR,DG,DB: the index of a material and the step its colour takes from frame to frame, three finite numbers\n");
+        return 1;
+      }
+      recolor = true;
+    } else if (!std::strcmp(argv[i], "--emit") && i + 1 < argc) {
+      char tail = 0;
+      if (std::sscanf(argv[++i], "%d:%f%c", &emit_mat, &emit_step, &tail) != 2 || emit_mat < 0 || !std::isfinite(emit_step)) {
+        std::fprintf(stderr, "--emit wants M:DE: the index of a material and the step its emittance takes from frame to frame, a finite number\n");
+        return 1;
+      }
+      emit = true;
+    }
     else if (!std::strcmp(argv[i], "--history-probe")) history_probe = true;
     else if (!std::strcmp(argv[i], "--probe-radius") && i + 1 < argc) {
       char* end = nullptr;
@@ -544,7 +568,15 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--history-extra excludes --denoise-history without --history-moments: the folds' variance knows nothing of the extra samples\n");
     return 1;
   }
-  if (orbit_still && !move) {
+  if ((recolor || emit) && orbit <= 0) {
+    std::fprintf(stderr, "%s goes with --orbit N (it edits a material of the live renderer from frame to frame)\n", recolor ? "--recolor" : "--emit");
+    return 1;
+  }
+  if ((recolor || emit) && hist_feedback) {
+    std::fprintf(stderr, "%s excludes --history-feedback: the recolour step (PT_HISTORY_MATERIALS) is not built beside the feedback kind\n", recolor ? "--recolor" : "--emit");
+    return 1;
+  }
+  if (orbit_still && !move && !recolor && !emit) {
     std::fprintf(stderr, "--orbit-still wants --orbit N --move G:DX,DY,DZ (with the camera standing still and nothing moving every frame would be the same)\n");
     return 1;
   }
@@ -552,9 +584,9 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--probe-radius and --probe-gain go with --history-probe\n");
     return 1;
   }
-  if (history_probe && (!reproject || !move || !orbit_still)) {
+  if (history_probe && (!reproject || !(move || recolor || emit) || !orbit_still)) {
     std::fprintf(stderr, "--history-probe wants %s (it renders kept samples again after an object moved; the probes answer for a camera that stands still)\n",
-                 !reproject ? "--reproject" : !move ? "--move G:DX,DY,DZ" : "--orbit-still");
+                 !reproject ? "--reproject" : !(move || recolor || emit) ? "--move G:DX,DY,DZ" : "--orbit-still");
     return 1;
   }
   if (reproject && (gpus >= 0 || !device_list.empty())) {
@@ -590,6 +622,11 @@ int main(int argc, char** argv) {
   if (move && ((size_t)move_geom >= scene->geoms.size() || scene->geom_trs[(size_t)move_geom].mesh)) {
     std::fprintf(stderr, "--move: geom %d is %s\n", move_geom,
                  (size_t)move_geom >= scene->geoms.size() ? "outside the scene's geoms" : "a triangle of a mesh object, which has no TRANS of its own");
+    return 1;
+  }
+  if ((recolor && (size_t)recolor_mat >= scene->materials.size()) || (emit && (size_t)emit_mat >= scene->materials.size())) {
+    const bool first = recolor && (size_t)recolor_mat >= scene->materials.size();
+    std::fprintf(stderr, "%s: material %d is outside the scene's %zu materials\n", first ? "--recolor" : "--emit", first ? recolor_mat : emit_mat, scene->materials.size());
     return 1;
   }
   const int W = scene->state.camera.resolution[0], H = scene->state.camera.resolution[1];
@@ -726,6 +763,7 @@ int main(int argc, char** argv) {
         std::printf("history: frame f renders iterations f * %d + 1 .. (f + 1) * %d, not 1 .. %d: repeated iteration numbers would repeat the paths\n", iters, iters, iters);
     }
     const float step = (float)(2.0 * 3.14159265358979323846 / orbit);
+    const uint32_t edit_flag = (recolor || emit) ? PT_HISTORY_MATERIALS : 0u;  // the lookup follows the edited material
     for (int f = 0; f < orbit; ++f) {
       double move_ms = 0.0;
       PtSetCameraTimes ct{};
@@ -741,6 +779,33 @@ int main(int argc, char** argv) {
         }
         const double geoms_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - g0).count();
         std::printf("move: frame %d: geom %d at %.9g %.9g %.9g, set_geoms %.3f ms\n", f, move_geom, (double)trs[0], (double)trs[1], (double)trs[2], geoms_ms);
+      }
+      if (f > 0 && (recolor || emit)) {  // ... and the material: its colour or its emittance grows by the step, the live renderer takes the new materials
+        for (int pass = 0; pass < 2; ++pass) {  // through pt_scene_set_material's code, which refuses a word that is not finite
+          if (!(pass == 0 ? recolor : emit)) continue;
+          const int mi = pass == 0 ? recolor_mat : emit_mat;
+          PtMaterial m = scene->materials[(size_t)mi];
+          if (pass == 0)
+            for (int k = 0; k < 3; ++k) m.color[k] += recolor_step[k];
+          else
+            m.emittance += emit_step;
+          if (!scene->setMaterial(mi, m)) {
+            std::fprintf(stderr, "%s: at frame %d material %d has a word that is not finite\n", pass == 0 ? "--recolor" : "--emit", f, mi);
+            return EXIT_FAILURE;
+          }
+        }
+        const auto g0 = std::chrono::high_resolution_clock::now();
+        if (grp ? pt_group_set_materials(grp, scene->materials.data(), (int)scene->materials.size()) : pt_set_materials(scene->materials.data(), (int)scene->materials.size())) {
+          std::fprintf(stderr, "HIP error (pt_set_materials): %s\n", pt_last_error());
+          return EXIT_FAILURE;
+        }
+        const double materials_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - g0).count();
+        for (const auto& e : {std::make_pair(recolor, recolor_mat), std::make_pair(emit && !(recolor && emit_mat == recolor_mat), emit_mat)})
+          if (e.first) {
+            const PtMaterial& m = scene->materials[(size_t)e.second];
+            std::printf("material: frame %d: material %d colour %.9g %.9g %.9g emittance %.9g, set_materials %.3f ms\n", f, e.second, (double)m.color[0], (double)m.color[1],
+                        (double)m.color[2], (double)m.emittance, materials_ms);
+          }
       }
       if (f > 0 && !orbit_still) {
         scene->orbit(step, 0.0f, 0.0f);
@@ -766,12 +831,12 @@ int main(int argc, char** argv) {
       int64_t thr_samples = 0;  // --history-threshold: the pixel-samples of the view, the pixels above at the last count, the rounds
       int thr_above = -1, thr_groups = 0;
       if (hist_threshold) {  // features, lookup, then uniform groups until two are folded and rounds over the pixels whose BLEND is above the threshold
-        render_failed = pt_render_features(1, 1) || (f > 0 && pt_history_reproject_ex(&hopt, PT_HISTORY_VARIANCE | (move ? PT_HISTORY_MOTION : 0u))) ||
+        render_failed = pt_render_features(1, 1) || (f > 0 && pt_history_reproject_ex(&hopt, PT_HISTORY_VARIANCE | (move ? PT_HISTORY_MOTION : 0u) | edit_flag)) ||
                         pt_history_render_threshold(iter_first, iters, hist_threshold_group_given ? hist_threshold_group : fold_group, hist_threshold_e,
                                                     hist_threshold_cap, hist_threshold_min_pixels, &frame_iters, &thr_samples, &thr_above) ||
                         pt_get_noise(nullptr, &thr_groups, nullptr) || pt_resolve(scene->state.image.data());
       } else if (hist_until) {  // the lookup needs the view's first hits only: features, lookup, then groups until the BLEND is clean
-        render_failed = pt_render_features(1, 1) || (f > 0 && pt_history_reproject_ex(&hopt, PT_HISTORY_VARIANCE | (move ? PT_HISTORY_MOTION : 0u))) ||
+        render_failed = pt_render_features(1, 1) || (f > 0 && pt_history_reproject_ex(&hopt, PT_HISTORY_VARIANCE | (move ? PT_HISTORY_MOTION : 0u) | edit_flag)) ||
                         pt_history_render_until(iter_first, iters, hist_until_group_given ? hist_until_group : fold_group, hist_until_db, &frame_iters, &until_psnr,
                                                 &until_view_psnr) ||
                         pt_get_noise(nullptr, &until_groups, nullptr) || pt_readback(scene->state.image.data());
@@ -814,7 +879,7 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "HIP error (pt_history): %s\n", pt_last_error());
             return EXIT_FAILURE;
           }
-        } else if ((!hist_until && (pt_render_features(1, 1) || (f > 0 && pt_history_reproject_ex(&hopt, hflags | (move ? PT_HISTORY_MOTION : 0u))))) ||
+        } else if ((!hist_until && (pt_render_features(1, 1) || (f > 0 && pt_history_reproject_ex(&hopt, hflags | (move ? PT_HISTORY_MOTION : 0u) | edit_flag)))) ||
             (history_probe && ((f > 0 && pt_history_probe_check(&probe_opt, &probes, &changed, &skipped)) || pt_history_probe_keep(iter_first, iters, f % 9))) ||
             (history_extra && pt_history_round(iter_first + iters, history_extra, &round_opt, &fresh, &selected)) || pt_history_resolve((float)frame_iters, carried.data()) ||
             (dn_history && (hist_feedback  ? pt_history_denoise_feedback((float)frame_iters, &dn_opt, &fb_opt, filtered.data())

@@ -321,6 +321,15 @@ void parseCamera(std::istream& in, Scene& sc) {
 
 }  // namespace
 
+bool Scene::setMaterial(int m, const PtMaterial& material) {
+  const float read[] = {material.color[0], material.color[1], material.color[2], material.specular_color[0], material.specular_color[1], material.specular_color[2],
+                        material.hasReflective, material.hasRefractive, material.emittance};
+  for (float v : read)
+    if (!std::isfinite(v)) return false;
+  materials[(size_t)m] = material;
+  return true;
+}
+
 void Scene::placeGeom(int geom, const float trs[9]) {
   PtGeom& g = geoms[(size_t)geom];
   std::memcpy(geom_trs[(size_t)geom].trs, trs, 9 * sizeof(float));

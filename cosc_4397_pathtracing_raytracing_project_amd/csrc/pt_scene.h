@@ -46,6 +46,9 @@ class Scene {  // src/scene.h:11-26
   // A new TRANS / ROTAT / SCALE for the OBJECT geom `geom` came from (not a mesh triangle): geom_trs and the three matrices, through
   // the loader's buildTransform.
   void placeGeom(int geom, const float trs[9]);
+  // A new material in the place of material m (an index inside `materials`): all eleven words as given.  false, nothing changed: one of
+  // the words the renderer reads (color, specular_color, hasReflective, hasRefractive, emittance) is not finite.
+  bool setMaterial(int m, const PtMaterial& material);
 
  private:
   void applyOrbitState();  // main.cpp:112-126: the camera from phi, theta, zoom and lookAt

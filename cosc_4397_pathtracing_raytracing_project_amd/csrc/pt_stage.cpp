@@ -488,6 +488,41 @@ int pt_stage_history_reproject_motion(int w, int rows, int row0, const PtCamera*
   return 0;
 }
 
+// ... with the materials' edits (pt_history_reproject_materials_host's arguments): k_history_reproject_materials of the kind `flags` names
+int pt_stage_history_reproject_materials(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
+                                         const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, const float* kept_var, const float* table,
+                                         const uint8_t* kind, const float* recolor, const uint8_t* rkind, uint32_t flags, float* current_plane, float* current_var) {
+  const char* who = "pt_stage_history_reproject_materials";
+  if (need(default_context(), who)) return -1;
+  Ctx& g = *default_context();
+  pthi::Params P{};
+  if (pt_history_reproject_check(who, w, rows, row0, kept_cam, kept_planes, feature_planes, reject_geom, num_geoms, opt, current_plane, &P)) return -1;
+  if (pt_history_materials_check(who, flags, num_geoms, table, kind, recolor, rkind, kept_var, current_var)) return -1;
+  if (rows >= 32768) return pt_fail("%s: a tile of %d x %d pixels is not supported", who, w, rows);
+  const uint32_t with = flags & (PT_HISTORY_VARIANCE | PT_HISTORY_MOMENTS);
+  HIP_OK(hipSetDevice(g.device));
+  Scratch sc;
+  const size_t n = (size_t)w * rows;
+  float *d_kept = nullptr, *d_feat = nullptr, *d_kvar = nullptr, *d_table = nullptr, *d_recolor = nullptr;
+  uint8_t *d_reject = nullptr, *d_kind = nullptr, *d_rkind = nullptr;
+  float* d_cur = sc.get<float>(8 * n);  // C, then VC
+  if (!d_cur) return pt_fail("%s: out of device memory", who);
+  if (device_copy(sc, who, kept_planes, 4 * PT_HISTORY_KEPT_PLANES * n, &d_kept) || device_copy(sc, who, feature_planes, 4 * PT_FEATURE_PLANES * n, &d_feat) ||
+      device_copy(sc, who, recolor, (size_t)pthi::kRecolorRow * num_geoms, &d_recolor) || device_copy(sc, who, rkind, (size_t)num_geoms, &d_rkind))
+    return -1;
+  if (table && (device_copy(sc, who, table, (size_t)pthi::kMotionRow * num_geoms, &d_table) || device_copy(sc, who, kind, (size_t)num_geoms, &d_kind))) return -1;
+  if (with && device_copy(sc, who, kept_var, 4 * n, &d_kvar)) return -1;
+  if (!P.keep_view_dependent && device_copy(sc, who, reject_geom, (size_t)num_geoms, &d_reject)) return -1;
+  HIP_OK(hipMemset(d_cur, 0xff, 8 * n * sizeof(float)));  // a pixel nobody wrote shows as NaNs
+  if (pt_history_reproject_materials_launch(g.stream, with, pthi::make_view(*kept_cam, rows, row0), d_kept, d_feat, d_reject, num_geoms, P, d_cur, d_kvar,
+                                            with ? d_cur + 4 * n : nullptr, d_table, d_kind, d_recolor, d_rkind))
+    return -1;
+  HIP_OK(hipStreamSynchronize(g.stream));
+  HIP_OK(hipMemcpy(current_plane, d_cur, 4 * n * sizeof(float), hipMemcpyDeviceToHost));
+  if (with) HIP_OK(hipMemcpy(current_var, d_cur + 4 * n, 4 * n * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
 // The history filter's kernels on caller-supplied host arrays (pt_history_denoise_host's arguments); C and VC travel beside the frame
 int pt_stage_history_denoise(int w, int rows, const float* rgb_sum, const float* planes, const float* noise_planes, int groups, int64_t iters, float samples,
                              const float* current_plane, const float* current_var, const PtDenoiseOptions* opt, float* rgb_avg) {

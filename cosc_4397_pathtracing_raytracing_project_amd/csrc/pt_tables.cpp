@@ -411,6 +411,17 @@ void camera_tables(HostTables& t, const CameraBase& base, const float cam[3], in
   }
 }
 
+std::vector<ptd::Mat> material_table(const PtMaterial* materials, int num_materials) {
+  std::vector<ptd::Mat> mats((size_t)std::max(num_materials, 0), ptd::Mat{});
+  for (int i = 0; i < num_materials; ++i) {
+    const PtMaterial& m = materials[i];
+    std::memcpy(mats[i].color, m.color, 12);
+    std::memcpy(mats[i].spec, m.specular_color, 12);
+    mats[i].reflective = m.hasReflective, mats[i].refractive = m.hasRefractive, mats[i].emittance = m.emittance;
+  }
+  return mats;
+}
+
 HostTables build_scene_tables(const PtSceneDesc& desc, int debug_flags, bool center_half, const GridRequest& request, CameraBase* keep) {
   HostTables t;
   CameraBase base;
@@ -444,13 +455,7 @@ HostTables build_scene_tables(const PtSceneDesc& desc, int debug_flags, bool cen
     pack_rows(gm.invTranspose, dg.invT);
     box_normal_table(dg.invT, dg.box_normal);
   }
-  t.mats.assign(desc.num_materials, ptd::Mat{});
-  for (int i = 0; i < desc.num_materials; ++i) {
-    const PtMaterial& m = desc.materials[i];
-    std::memcpy(t.mats[i].color, m.color, 12);
-    std::memcpy(t.mats[i].spec, m.specular_color, 12);
-    t.mats[i].reflective = m.hasReflective, t.mats[i].refractive = m.hasRefractive, t.mats[i].emittance = m.emittance;
-  }
+  t.mats = material_table(desc.materials, desc.num_materials);
   camera_tables(t, base, desc.camera.position, debug_flags, center_half, request);
   if (keep) *keep = std::move(base);
   return t;

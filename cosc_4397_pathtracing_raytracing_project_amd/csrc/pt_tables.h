@@ -86,6 +86,9 @@ void camera_tables(HostTables& t, const CameraBase& base, const float cam[3], in
 // debug_flags: PtOptions.debug_flags; center_half: ptk::KernelApi::boxes_center_half; keep: receives the CameraBase
 HostTables build_scene_tables(const PtSceneDesc& desc, int debug_flags, bool center_half, const GridRequest& request = GridRequest{},
                               CameraBase* keep = nullptr);
+// The material table (ptd::Mat: the nine words the kernels read of a PtMaterial): build_scene_tables' for pt_init, and what
+// pt_ctx_set_materials uploads into the table a live renderer has.
+std::vector<ptd::Mat> material_table(const PtMaterial* materials, int num_materials);
 // The grid a renderer without a timing probe has in use after build_scene_tables(): the cost model's candidate, as a request.
 GridRequest first_grid_request(const HostTables& t);
 // pt_camera_tables_host (include/pt_amd.h).

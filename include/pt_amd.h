@@ -244,6 +244,12 @@ const char* pt_scene_image_name(const PtScene* s);     /* CAMERA FILE */
  * world-space vertices), a component that is not finite.  pt_scene_desc must be called again afterwards, as after pt_scene_orbit. */
 int pt_scene_geom_trs(const PtScene* s, int geom, float trs[9]);
 int pt_scene_set_geom_trs(PtScene* s, int geom, const float trs[9]);
+/* Material `m` of the scene as the loader read it, and a new one in its place (all eleven words are stored as given; pt_set_materials
+ * hands the edited materials to a live renderer).  Refused by name: a null argument, an index outside the scene's materials, a word
+ * the renderer reads (color, specular_color, hasReflective, hasRefractive, emittance) that is not finite.  pt_scene_desc must be
+ * called again afterwards. */
+int pt_scene_material(const PtScene* s, int m, PtMaterial* out);
+int pt_scene_set_material(PtScene* s, int m, const PtMaterial* material);
 
 /* BVH exactly as pathtraceInit builds it (pathtrace.cu:34-111, 483-489).
  * Returns node count (2n-1); writes up to `cap` nodes if `out` != NULL. */
@@ -403,6 +409,33 @@ typedef struct PtSetGeomsTimes {
   double total_ms;
 } PtSetGeomsTimes;
 int pt_get_set_geoms_times(PtSetGeomsTimes* out);
+/* ---- editing the materials of a live renderer: new PtMaterials for the ones it was created with, without pt_free + pt_init.
+ * The count stays; every word of a material may change.  The words the renderer reads are color, specular_color, hasReflective,
+ * hasRefractive and emittance (the nine words of the device table).
+ * Contract: pt_set_camera's and pt_set_geoms', word for word — after a successful call every later call gives what a renderer
+ * freshly created from the same scene with these materials, the same options and the renderer's current camera and geoms gives, bit
+ * for bit in all three PT_ARITH_* modes (image, feature buffers — the albedo plane changes —, noise planes, adaptive lists and
+ * counts, resolved and filtered images); the timing fields, which traversal structure is walked and PtStats.device_bytes may differ.
+ * What happens: synchronise; the material table is made by the code pt_init runs and uploaded into the table the renderer has
+ * (nothing is allocated); the per-geom tables of the history that follow the materials (reject_geom, emitter_geom) are rebuilt at
+ * their next use, in place; then what pt_set_camera does after its tables: the launch plan, the worker, the batch buffers' first
+ * state, pt_clear.  The full re-arm is deliberate: whether a camera ray survives depth 0 follows the emittance of what it hits, and
+ * the first-hit records are reused from batch to batch.  The renderer keeps a host copy of its PtMaterials from pt_init on (44 B each).
+ * History: K, VK, FK, the kept camera, the kept geoms and the kept materials survive, and so do the probes PK; C, VC, FC, P and E
+ * become absent.  The lookup without PT_HISTORY_MATERIALS (below) knows nothing of the edit.
+ * Refused, in this order, with nothing changed, allocated or launched: no renderer; a failed renderer; null `materials`;
+ * num_materials other than the renderer's (adding or removing materials needs pt_init); the first material, named by index, with a
+ * word the renderer reads that is not finite.
+ * Not built: adding or removing materials or objects; textures; a re-arm lighter than the camera move's; the pathtrace.h shim, which
+ * keeps re-initialising when materials differ. */
+int pt_set_materials(const PtMaterial* materials, int num_materials);
+/* The last pt_set_materials of the renderer, host wall clock, milliseconds; all zero before the first. */
+typedef struct PtSetMaterialsTimes {
+  double upload_ms; /* synchronise + the table onto the device                                             */
+  double rearm_ms;  /* launch plan, path buffers and records back to their first state, the worker, pt_clear */
+  double total_ms;
+} PtSetMaterialsTimes;
+int pt_get_set_materials_times(PtSetMaterialsTimes* out);
 /* Host wall-clock times of a renderer's setup, in milliseconds: the host build of the scene tables, their upload, the
  * allocation of the batch buffers, the timing probe of the traversal structures (0 where none ran), and the last pt_set_camera
  * (its synchronise included) with the number of such calls since the renderer was created. */
@@ -1111,7 +1144,7 @@ int pt_history_denoise_moments_counted_host(int w, int rows, const float* rgb_su
  * treats the world as static even after pt_set_geoms.
  * Caveat: a moved object changes shadows and indirect light on surfaces that stand still.  The lookup does not detect that: their
  * history goes stale until `cap` washes it out, unless the history probes below shorten it (a camera that stands still only).
- * Out of scope: adding or removing objects; material changes; deformation; a device-side tree build.  (Groups of contexts: "history in groups" below.) */
+ * Out of scope: adding or removing objects; deformation; a device-side tree build.  (Material edits: PT_HISTORY_MATERIALS below.  Groups of contexts: "history in groups" below.) */
 #define PT_HISTORY_MOTION 4u
 int pt_history_motion_host(const PtGeom* kept, const PtGeom* cur, int n, float* table /* n * 24 */, uint8_t* kind /* n */);
 /* pt_history_reproject_host / _variance_host / _moments_host (flags & 3 picks which; kept_var, current_var NULL for the plain one)
@@ -1119,6 +1152,46 @@ int pt_history_motion_host(const PtGeom* kept, const PtGeom* cur, int n, float* 
 int pt_history_reproject_motion_host(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
                                      const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, const float* kept_var, const float* table,
                                      const uint8_t* kind, uint32_t flags, float* current_plane, float* current_var);
+
+/* ---- the history across a recoloured surface: PT_HISTORY_MATERIALS for pt_history_reproject_ex.  The lookup above knows nothing of
+ * pt_set_materials: a pixel of a wall whose colour changed since the capture carries the old colour.  With the flag the history of
+ * such a pixel is scaled by the ratio of the colours, and the history of a pixel whose material changed in any other way is dropped.
+ * Kept materials: every capture remembers, beside the kept camera and geoms, the materials the renderer had (a host copy, retaken
+ * only when pt_set_materials has run since the last copy; a renderer that never edits copies once at most and uploads nothing).
+ * Recolour table (pt_history_recolor_host), per material m with k the kept and c the current material; "the nine words" are color,
+ * specular_color, hasReflective, hasRefractive and emittance:
+ *   mk = 0 (unchanged) when the nine words are bytewise equal;
+ *   mk = 2 (carries nothing) when any of the six words that are not `color` differs bytewise, or k.emittance > 0 (an emitter's pixel
+ *   is its colour times its emittance), or k.hasReflective > 0 (a mix of two colours, not a product), or for some channel j
+ *   !(k.color[j] > 0), or !(c.color[j] >= 0), or r_j = c.color[j] / k.color[j] (float32, correctly rounded) is not finite;
+ *   mk = 1 (recoloured) otherwise: only the colour of a diffuse material that does not emit changed.
+ *   Row g of the table: {r_x, r_y, r_z, +0} of geoms[g].materialid for kind 1, four zeros otherwise; kind[g] = mk of that material.
+ * The lookup with the flag is the lookup without it (with PT_HISTORY_MOTION: that lookup) with one step more for the pixel's geom
+ * g = id - 1 (an id outside 1 .. num_geoms counts as unchanged, as the motion step has it):  kind 0: nothing changes;  kind 2:
+ * rejected (C = VC = 0);  kind 1, after step 7, for a pixel that was not rejected: h_j = h_j * r_j, Th untouched; the variance kind
+ * vh_j = (vh_j * r_j) * r_j; the moments kind m2h_j = (m2h_j * r_j) * r_j, rh untouched.  float32, separate IEEE multiplications in
+ * the order written, the same bits on host and device in all three builds.  Every tap that passed has the pixel's own object id and
+ * therefore one factor, so scaling after the bilinear average is the demodulate-then-remodulate step of SVGF applied to a history
+ * that stores modulated radiance.  It corrects the first-hit albedo; it does NOT correct the colour that the recoloured surface
+ * bleeds onto other surfaces, whose history stays stale until `cap` washes it out.
+ * Flags: PT_HISTORY_MATERIALS alone, or with PT_HISTORY_VARIANCE or PT_HISTORY_MOMENTS, each also with PT_HISTORY_MOTION.  With
+ * PT_HISTORY_FEEDBACK it is refused by name (FC carries one variance for three channels, which a per-channel factor cannot scale: not
+ * built).  pt_history_capture_ex does not define the bit; a group refuses it by name (not built for a group).  Where no material
+ * changed since the capture the renderer uploads nothing and launches the kernel of the same call without the flag: the same planes
+ * bit for bit, no growth of device_bytes.  Otherwise 16 + 1 bytes per geom go to the device (allocated by the first such call, counted
+ * in device_bytes; the table is built and uploaded by the first lookup after a capture or a pt_set_materials changed its inputs,
+ * which synchronises) and k_history_reproject_materials runs.
+ * Out of scope: the recolour step beside the feedback kind and in groups; textures.  (The light an edit changes on OTHER surfaces: the
+ * history probes below.) */
+#define PT_HISTORY_MATERIALS 32u
+int pt_history_recolor_host(const PtMaterial* kept, const PtMaterial* cur, int num_materials, const PtGeom* geoms, int num_geoms,
+                            float* table /* num_geoms * 4 */, uint8_t* kind /* num_geoms */);
+/* pt_history_reproject_motion_host with the recolour step: recolor and rkind as above for num_geoms >= 1 geoms; table and kind (the
+ * motion table) may both be NULL when PT_HISTORY_MOTION is not in `flags`.  flags & 3 picks the kind; PT_HISTORY_MATERIALS is implied. */
+int pt_history_reproject_materials_host(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
+                                        const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, const float* kept_var, const float* table,
+                                        const uint8_t* kind, const float* recolor, const uint8_t* rkind, uint32_t flags, float* current_plane,
+                                        float* current_var);
 
 /* ---- the history probes: replay kept samples after a move, shorten the history where light changed.  A sample is a pure function
  * of (iteration, pixel, world), and the adaptive rounds' worker renders a chosen list of pixels at chosen iterations bit for bit as a
@@ -1136,9 +1209,9 @@ int pt_history_reproject_motion_host(int w, int rows, int row0, const PtCamera* 
  *   s = j * PW + i, so the pixel list ascends with s (pt_history_probe_list_host).
  * pt_history_probe_keep (asynchronous; k_history_probe_keep, one thread per probe): PK[s] = {S_p.xyz, bits(id_p)}, id_p read from the
  *   feature sums as pt_history_capture reads it (s1.w > 0 ? bits(s2.w) : 0).  The host remembers iter_first, iter_count, phase, the
- *   renderer's camera and its geoms (a host copy, retaken only when pt_set_geoms has run since the last copy).  State: 16 B per
- *   probe, allocated by the first keep for the probes of phase 0 (the most of any phase) and counted in PtStats.device_bytes.  PK
- *   survives pt_clear, pt_set_camera[_ex] and pt_set_geoms; pt_history_drop forgets it.  P == 0 is kept as "no probes".
+ *   renderer's camera, its geoms and its materials (host copies, retaken only when pt_set_geoms / pt_set_materials has run since the
+ *   last copy).  State: 16 B per probe, allocated by the first keep for the probes of phase 0 (the most of any phase) and counted in
+ *   PtStats.device_bytes.  PK survives pt_clear, pt_set_camera[_ex], pt_set_geoms and pt_set_materials; pt_history_drop forgets it.  P == 0 is kept as "no probes".
  *   Refuses, in this order, nothing changed, allocated or launched: no renderer or a failed context; iter_first < 1, iter_count < 1
  *   or iterations past 2^31 - 1; phase outside 0 .. 8; a striped or ragged tile; the adaptive state; E present (S is no longer a
  *   uniform sum: keep before pt_history_round; pt_clear is the way out); no feature pass since the last clear or move;
@@ -1151,13 +1224,16 @@ int pt_history_reproject_motion_host(int w, int rows, int row0, const PtCamera* 
  *   3. the worker renders the kept iterations of the listed pixels into its cleared sum Sw[P][3]; PtStats.samples grows by iter_count * P;
  *   4. gradient (k_history_probe_gradient, one thread per probe), g = id - 1: the probe is skipped, L[s] = -1.0f, when the id now
  *      at the pixel differs from the kept id, is 0 or outside 1 .. num_geoms, or moved[g] != 0 (moved[g] = 1 when the geom's 48 matrix
- *      words differ bytewise from the kept geoms'; built on the host and uploaded, one byte per geom, only when pt_set_geoms has run
- *      since the keep, otherwise all zero).  Otherwise, o = PK[s].xyz, w = Sw[s]:
+ *      words differ bytewise from the kept geoms', or mk of its material against the kept materials — PT_HISTORY_MATERIALS above — is
+ *      not 0; built on the host and uploaded, one byte per geom, only when pt_set_geoms or pt_set_materials has run since the keep,
+ *      otherwise all zero).  So after a material edit the probes on the edited surface are skipped — its own shading is the recolour
+ *      step's business — and every other probe is replayed: L is exactly zero wherever the path met nothing that changed, and
+ *      non-zero where it met the recoloured wall or the dimmed light.  Otherwise, o = PK[s].xyz, w = Sw[s]:
  *        d = (|w.x - o.x| + |w.y - o.y|) + |w.z - o.z|;  mo = (o.x + o.y) + o.z, mw likewise;  m = mo > mw ? mo : mw;
  *        lam = m > 0 ? d / m : +0;  L[s] = lam < 1 ? lam : 1.0f (a NaN reads as 1).
  *      changed = #{L[s] > 0}, skipped = #{L[s] < 0}: integer atomics, read back as 8 bytes;
  *   5. apply (k_history_probe_apply, one thread per tile pixel (x, r)): every word is kept for a miss, an id outside 1 .. num_geoms
- *      and a moved geom (left to PT_HISTORY_MOTION).  Otherwise i0 = x / 3, j0 = r / 3, lam_p = the maximum of L over the probes
+ *      and a moved or edited geom (left to PT_HISTORY_MOTION / PT_HISTORY_MATERIALS).  Otherwise i0 = x / 3, j0 = r / 3, lam_p = the maximum of L over the probes
  *      (i, j) of the grid with |i - i0| <= radius, |j - j0| <= radius, starting at +0 (skipped probes add nothing).  lam_p == 0:
  *      every word is kept.  Else g = lam_p * gain;  g = g < 1 ? g : 1.0f;  C.w = C.w * (1.0f - g).  Only C.w is written; VC is
  *      untouched; the cap was applied by the lookup.
@@ -1172,8 +1248,8 @@ int pt_history_reproject_motion_host(int w, int rows, int row0, const PtCamera* 
  * radius or gain raised the frame's MSE — shortening history there trades little bias for much noise.  Radius 1 and gain 1 are what
  * makes the history round resample the pixels a move touched; they cost 3.2 x the frame's MSE there.
  * Not built: a camera that moves between keep and check (forward-projecting the probes needs camera rays off the pixel centres);
- * pt_group_*; the shading of the moved object itself (PT_HISTORY_MOTION carries it, skipped here); material changes; feeding L into
- * the filter's variance. */
+ * pt_group_*; the shading of the moved object itself (PT_HISTORY_MOTION carries it, skipped here); remodulating the probes' kept sums after a recolour
+ * (a probe on a recoloured surface is skipped); feeding L into the filter's variance. */
 #define PT_HISTORY_PROBE_RADIUS 0    /* the default of PtHistoryProbeOptions.radius, in probe cells: the pixel's own cell */
 #define PT_HISTORY_PROBE_GAIN 0.25f /* the default of PtHistoryProbeOptions.gain */
 typedef struct PtHistoryProbeOptions { /* every field: 0 = the default */
@@ -1431,6 +1507,8 @@ int pt_ctx_set_camera_ex(PtContext* c, const PtCamera* cam, uint32_t flags);
 int pt_ctx_get_set_camera_times(PtContext* c, PtSetCameraTimes* out);
 int pt_ctx_set_geoms(PtContext* c, const PtGeom* geoms, int num_geoms);
 int pt_ctx_get_set_geoms_times(PtContext* c, PtSetGeomsTimes* out);
+int pt_ctx_set_materials(PtContext* c, const PtMaterial* materials, int num_materials);
+int pt_ctx_get_set_materials_times(PtContext* c, PtSetMaterialsTimes* out);
 int pt_ctx_set_reference(PtContext* c, const float* rgb_avg_host);
 int pt_ctx_get_convergence(PtContext* c, int iter_first, int iter_count, double* sse);
 int pt_ctx_iterations_to_clean(PtContext* c, float threshold_db, int* iteration);
@@ -1539,6 +1617,7 @@ int pt_group_sync(PtGroup* g);
 int pt_group_set_camera(PtGroup* g, const PtCamera* cam);
 int pt_group_set_camera_ex(PtGroup* g, const PtCamera* cam, uint32_t flags); /* pt_set_camera_ex on every context, asked first in the same way */
 int pt_group_set_geoms(PtGroup* g, const PtGeom* geoms, int num_geoms);      /* pt_set_geoms on every context, asked first in the same way */
+int pt_group_set_materials(PtGroup* g, const PtMaterial* materials, int num_materials);  /* pt_set_materials on every context, asked first in the same way */
 int pt_group_gather(PtGroup* g, float* rgb_sum_host);             /* W*H*3 floats, raw orientation */
 int pt_group_gather_u8(PtGroup* g, float samples, uint8_t* rgb8_host); /* W*H*3 bytes as pt_save_u8, converted on each device */
 /* The feature buffers of the whole frame: every context sums its own rows, the planes meet at the root like the image (one
@@ -1768,6 +1847,11 @@ int pt_stage_history_reproject_moments(int w, int rows, int row0, const PtCamera
 int pt_stage_history_reproject_motion(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
                                       const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, const float* kept_var, const float* table,
                                       const uint8_t* kind, uint32_t flags, float* current_plane, float* current_var);
+/* The lookup with the materials' edits through k_history_reproject_materials (pt_history_reproject_materials_host's arguments; rows < 32768). */
+int pt_stage_history_reproject_materials(int w, int rows, int row0, const PtCamera* kept_cam, const float* kept_planes, const float* feature_planes,
+                                         const uint8_t* reject_geom, int num_geoms, const PtHistoryOptions* opt, const float* kept_var, const float* table,
+                                         const uint8_t* kind, const float* recolor, const uint8_t* rkind, uint32_t flags, float* current_plane,
+                                         float* current_var);
 int pt_stage_history_denoise_moments(int w, int rows, const float* rgb_sum, const float* planes, float samples, const float* current_plane,
                                      const float* current_var, const PtDenoiseOptions* opt, float* rgb_avg);
 /* The history round's key and selection, and its merge, through the device kernels on caller-supplied host arrays
